@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- GCUPS of the Smith-Waterman database search on N MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run (no --config, no --full) does only what the headline needs: it sets up the headline's database,
+warms up, times exactly --steps steps and prints the JSON line.  `--full` adds everything else described below:
+the blocks of the other configurations, the reference's CPU fill as `cpu_baseline`, the top-K check against the
+oracle and the host-inclusive leg.  A run with `--config C` is a run of that configuration with all of its legs and
+checks, as with --full.  `--dump-outputs DIR` writes, after the timed steps, the top-K the last timed step returned
+(`topk_score.npy`, `topk_index.npy`: float64, best first); the databases are generated from fixed seeds, so two
+builds given the same arguments can be compared output for output.
 
 `--gpus N` (N > 1) started WITHOUT a launcher's environment starts its N ranks itself: before anything touches
 torch or HIP it runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
@@ -12,11 +20,11 @@ its return code (`--spawn-dry-run` prints that command instead of running it).
 A step = one pass of the hot path (swg_search: int16 fill, saturation re-score when possible,
 top-K) over one resident synthetic database of the shapes of SURVEY 8d.
 
-One GPU, no --config: the JSON line's headline (`value`, `config`, `roofline`, `cpu_baseline`, exactly
+One GPU, no --config: the JSON line's headline (`value`, `config`, `roofline`, with --full `cpu_baseline`, exactly
 --steps timed steps after --warmup untimed ones) is config 4's ONE 10M-sequence database (3000 aa query) searched
 WHOLE on this GPU through the sharded path with one shard -- the very workload `--gpus N` deals over N ranks, so
 value(N) / (N * value(1)) compares one workload with itself (it is the configuration BASELINE.json quotes its scaling
-target on, and it fits one GPU: 3.8 GB of residues).  The `configs` object holds one block of the same shape for each
+target on, and it fits one GPU: 3.8 GB of residues).  With --full, the `configs` object holds one block of the same shape for each
 of configs 3 (round 3's headline), 2, 4 (one GPU's eighth of the 10M-sequence database), "4_relatives" (that share
 with a family of 30-70 %-identity relatives of the query: the f16 flag-and-re-run route, first search and steady
 state), 5 and 5's stress variant, "peptides" (not a BASELINE shape: 2 million sequences of 20-40 residues, which the
@@ -27,12 +35,12 @@ one rank): config 4 as ONE 10M-sequence database.  Every rank derives the same g
 generates only the residues of its own bins (round-robin by bin: swg_synth_db_shard), packs them
 (swg_db_pack_shard) and searches them with no data-path collective; the only exchange is one RCCL
 max-all-reduce of the n*K top-K keys per step.  Total work is fixed as N grows: `scaling: "strong"`,
-value = cells of the whole database * steps / max-over-ranks time.  Once, outside the timed region,
+value = cells of the whole database * steps / max-over-ranks time.  With --full, once, outside the timed region,
 the merged top-K is checked: every candidate's score against the int32 oracle, a seeded sample of
 each shard against the K-th key, and the all-reduce merge against a plain gather-and-sort.
 
 The JSON line carries BASELINE.json's metric (GCUPS = lq * sum(len) / t / 1e9 over real residues),
-the HBM roofline of the fill kernel beside the roof that binds it (VALU issue), and the reference's
+the HBM roofline of the fill kernel beside the roof that binds it (VALU issue), and with --full the reference's
 own AVX2+OpenMP fill timed on this host (oracle/_ref, built from the reference's sources) as
 `cpu_baseline`.  The oracle is used as the checker only, never inside a timed region.
 """
@@ -122,7 +130,8 @@ def parse_args():
                     help="skip the one-off search from host buffers (PCIe-inclusive figure, reported beside value)")
     ap.add_argument("--no-verify", action="store_true", help="skip the top-K check against the oracle (outside the timed region)")
     ap.add_argument("--no-scaling-reference", action="store_true", help="(accepted and ignored: the 10M-sequence database is the headline now)")
-    ap.add_argument("--only-headline", action="store_true", help="one GPU: the headline configuration alone")
+    ap.add_argument("--only-headline", action="store_true",
+                    help="one GPU, with --full: the headline configuration alone (with its CPU baseline and check)")
     ap.add_argument("--whole", action="store_true",
                     help="one GPU, with --config 4 or 5: the configuration's WHOLE 10M-sequence database through the sharded path "
                          "with one shard -- the N = 1 point of the curve `--gpus N --config C` continues")
@@ -139,7 +148,18 @@ def parse_args():
                     help="experiment: any swg_set_option key (repeatable), e.g. --opt batch=0")
     ap.add_argument("--spawn-dry-run", action="store_true",
                     help="--gpus N without a launcher: print the launch command as JSON instead of running it")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other configurations' blocks, the CPU baseline, the top-K check against "
+                         "the oracle and the host-inclusive leg (implied by --config)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the top-K of the last timed step as DIR/topk_score.npy and "
+                         "DIR/topk_index.npy (float64, best first)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.config:
+        args.full = True    # a run of one configuration keeps all of its legs and checks
+    return args
 
 
 class Env:
@@ -226,11 +246,12 @@ def make_context(env, q, sc):
 
 
 def run_config(env, cnum, steps, warmup, sharded=False, n_override=0, host_inclusive_leg=False, cpu_leg=False, legs=(),
-               first_search_leg=False):
+               first_search_leg=False, dump=None):
     """One configuration: generate, pack, upload, warm up, time exactly `steps` steps between fences.
     sharded: the database is ONE global database dealt by bins over the ranks (strong scaling), else an
     independent database on this rank.  legs: ((name, {option: value}), ...): the same resident database timed
-    again with those options set (block[name]).  Returns the block dict (rank 0) or None."""
+    again with those options set (block[name]).  dump: directory for the last timed step's top-K (rank 0).
+    Returns the block dict (rank 0) or None."""
     a, swg = env.args, env.swg
     cfg = dict(CONFIGS[cnum])
     if a.lq:
@@ -319,6 +340,8 @@ def run_config(env, cnum, steps, warmup, sharded=False, n_override=0, host_inclu
 
     elapsed, fill_ms, total_ms, lasts, last_hits = timed(steps, warmup)
     last = lasts[-1]
+    if dump and env.rank == 0:
+        dump_outputs(dump, last_hits[0])
     elapsed_own = elapsed
 
     torch, dist = env.torch, env.dist
@@ -347,7 +370,7 @@ def run_config(env, cnum, steps, warmup, sharded=False, n_override=0, host_inclu
     cells_local = float(lq) * residues
 
     verify = None
-    if not a.no_verify:
+    if a.full and not a.no_verify:
         verify = verify_topk(env, ctx, db, q, sc, flat, off, index, K, merger, last_hits[0])
 
     block = None
@@ -427,6 +450,15 @@ def run_config(env, cnum, steps, warmup, sharded=False, n_override=0, host_inclu
     db.close()
     ctx.close()
     return block
+
+
+def dump_outputs(path, hits):
+    """--dump-outputs: what a caller of the timed search receives, the top-K hits (score, database index), best
+    first, as float64 arrays (exact for both: scores and indices stay below 2**53)."""
+    os.makedirs(path, exist_ok=True)
+    h = np.array(hits, dtype=np.float64).reshape(-1, 2)
+    np.save(os.path.join(path, "topk_score.npy"), h[:, 0])
+    np.save(os.path.join(path, "topk_index.npy"), h[:, 1])
 
 
 def plan_of(last):
@@ -841,29 +873,31 @@ def main():
         # one global database dealt by bins; total work fixed as the number of GPUs grows
         cnum = args.config or SHARDED
         n_full = args.nseq or CONFIGS[cnum].get("n_full", CONFIGS[cnum]["n"])
-        block = run_config(env, cnum, K, W, sharded=True, n_override=n_full, cpu_leg=True)
+        block = run_config(env, cnum, K, W, sharded=True, n_override=n_full, cpu_leg=args.full, dump=args.dump_outputs)
         if env.rank == 0:
             emit(line_from(block, env, "strong"))
     elif args.config and args.whole and CONFIGS[args.config].get("n_full"):
-        block = run_config(env, args.config, K, W, sharded=True, n_override=args.nseq or CONFIGS[args.config]["n_full"], cpu_leg=True)
+        block = run_config(env, args.config, K, W, sharded=True, n_override=args.nseq or CONFIGS[args.config]["n_full"], cpu_leg=True,
+                           dump=args.dump_outputs)
         out = line_from(block, env, "strong")
         out["configs"] = {"%d_whole" % args.config: {k: v for k, v in block.items() if k != "cpu_baseline"}}
         emit(out)
     elif args.config:
         block = run_config(env, args.config, K, W, host_inclusive_leg=True, cpu_leg=True,
-                           legs=CONFIG_LEGS.get(args.config, ()))
+                           legs=CONFIG_LEGS.get(args.config, ()), dump=args.dump_outputs)
         out = line_from(block, env, "strong")
         out["configs"] = {str(args.config): {k: v for k, v in block.items() if k not in ("cpu_baseline", "host_inclusive")}}
         emit(out)
     else:
         # The headline first (exactly K timed steps after W warm-up steps): config 4's ONE 10M-sequence database,
         # whole, on this GPU -- through the sharded path with one shard, i.e. the very workload `--gpus N` deals over
-        # N ranks, so that value(N) / (N * value(1)) compares one workload with itself.  Then the other shapes with
-        # step counts scaled to their step time so the whole run stays within minutes.
+        # N ranks, so that value(N) / (N * value(1)) compares one workload with itself.  With --full, then the other
+        # shapes with step counts scaled to their step time so the whole run stays within minutes.
         blocks = {}
-        head = run_config(env, SHARDED, K, W, sharded=True, n_override=CONFIGS[SHARDED]["n_full"], cpu_leg=True)
+        head = run_config(env, SHARDED, K, W, sharded=True, n_override=CONFIGS[SHARDED]["n_full"], cpu_leg=args.full,
+                          dump=args.dump_outputs)
         out = line_from(head, env, "strong")
-        if not args.only_headline:
+        if args.full and not args.only_headline:
             blocks["3"] = run_config(env, 3, K, W)
             # (a step of config 2 is 2 ms: W such steps are over before the clocks have settled after the host-side
             # set-up of the block, so this block warms up for 30 steps)

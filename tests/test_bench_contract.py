@@ -1,9 +1,12 @@
 """CPU: the shape of bench.py's one JSON line (the driver's contract) checked on the line committed
-under profiles/ by the last GPU run, and the parts of bench.py that need no GPU."""
+under profiles/ by the last GPU run, and the parts of bench.py that need no GPU.  GPU: --dump-outputs."""
 import json
 import os
 import subprocess
 import sys
+
+import numpy as np
+import pytest
 
 from conftest import ROOT
 
@@ -89,14 +92,18 @@ def test_every_point_of_the_scaling_curve_is_the_same_workload():
     assert one["roofline"]["launches_per_step"] == dist["roofline"]["launches_per_step"] == 48
     # and the code path: both go through run_config(..., sharded=True) on config 4's full size
     src = open(os.path.join(ROOT, "bench.py")).read()
-    assert src.count('run_config(env, SHARDED, K, W, sharded=True, n_override=CONFIGS[SHARDED]["n_full"], cpu_leg=True)') == 1
-    assert "run_config(env, cnum, K, W, sharded=True, n_override=n_full, cpu_leg=True)" in src
+    assert src.count('run_config(env, SHARDED, K, W, sharded=True, n_override=CONFIGS[SHARDED]["n_full"], cpu_leg=args.full,') == 1
+    assert "run_config(env, cnum, K, W, sharded=True, n_override=n_full, cpu_leg=args.full, dump=args.dump_outputs)" in src
 
 
 def test_bench_help_and_launch_rule_need_no_gpu():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, text=True, timeout=300)
     assert r.returncode == 0 and "--gpus" in r.stdout and "--steps" in r.stdout and "--warmup" in r.stdout
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stdout
     # N > 1 without a launcher: bench.py starts its ranks itself, as child processes of a parent that has not
     # touched torch or HIP -- the command it would run (nothing is launched here)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
@@ -112,3 +119,26 @@ def test_bench_help_and_launch_rule_need_no_gpu():
     # under a launcher (RANK / WORLD_SIZE set) it does not spawn again
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert '"RANK" not in os.environ and "WORLD_SIZE" not in os.environ' in src
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_steps_top_k(orc, tmp_path):
+    """--dump-outputs: after exactly --steps timed steps, the top-K the last one returned, as float64 arrays, equal to
+    the oracle's top-K of the same seeded database (config 1: the seeds bench.py derives from the config number)."""
+    import swg_loader
+    swg = swg_loader.load()
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "1", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["verify"]["ok"] is True
+    score, index = np.load(out / "topk_score.npy"), np.load(out / "topk_index.npy")
+    assert score.dtype == np.float64 and index.dtype == np.float64 and score.shape == index.shape == (100,)
+    q = swg.synth_query(0x5EED0001, 128)
+    flat, off = swg.synth_db(0x5EED0001, 1024)
+    want = orc.topk(orc.score_db(q, flat, off, swg.load_scoring("BLOSUM62").table(), -2, -1), 100)
+    assert [(int(s), int(i)) for s, i in zip(score, index)] == want
