@@ -183,6 +183,7 @@ _sig("swg_debug_fail_alloc", None, [C.c_int])
 _sig("swg_debug_sort_count", C.c_ulong, [])
 _sig("swg_debug_engine", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_int, _vp])
 _sig("swg_debug_plan", C.c_int, [_vp, C.c_size_t, C.c_int, _vp])
+_sig("swg_debug_plan_f16", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_long, _vp])
 _sig("swg_debug_split", C.c_int, [_vp, C.c_size_t, C.c_uint64, _vp])
 _sig("swg_debug_list_plan", C.c_int, [C.c_size_t, C.c_uint32, C.c_int, _vp, _vp])
 _sig("swg_debug_pair_tokens", C.c_int, [_vp, _vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
@@ -414,12 +415,17 @@ class Database:
             return np.zeros(0, dtype=np.uint32)
         return np.ctypeslib.as_array(lib.swg_db_order(self.handle), shape=(self.count,)).copy()
 
-    def debug_plan(self, lq, n_cu=256):
-        """Test hook: the cost model's first choice for this database and a query of lq residues (no device needed)."""
-        out = np.zeros(13, dtype=np.int32)
-        _check(lib.swg_debug_plan(self.handle, lq, n_cu, out.ctypes.data_as(_vp)))
+    def debug_plan(self, lq, n_cu=256, f16_pair=None):
+        """Test hook: the cost model's first choice for this database and a query of lq residues (no device needed).
+        f16_pair None: for the int16 cells; 0 (auto), 1 (v_perm_b32) or 2 (fma): for the packed-f16 cells with that
+        pairing option, which adds the plan's pairing (fma, long_fma: 1 = v_pk_fma_f16) and the workgroup's LDS bytes."""
+        out = np.zeros(16, dtype=np.int32)
+        if f16_pair is None:
+            _check(lib.swg_debug_plan(self.handle, lq, n_cu, out.ctypes.data_as(_vp)))
+        else:
+            _check(lib.swg_debug_plan_f16(self.handle, lq, n_cu, f16_pair, out.ctypes.data_as(_vp)))
         keys = ("classes", "K", "G", "W", "passes", "workgroups", "long_pairs", "long_K", "long_G", "long_W", "long_workgroups", "est_us",
-                "last_pass_cols")
+                "last_pass_cols") + (() if f16_pair is None else ("fma", "lds_bytes", "long_fma"))
         return dict(zip(keys, (int(v) for v in out)))
 
     def debug_engine(self, lq, n_cu=256, form=2):

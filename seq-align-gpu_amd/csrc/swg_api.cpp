@@ -283,6 +283,10 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
     } else if (!strcmp(key, "f16")) {
         if (value < 0 || value > 2) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "f16 must be 0 (off), 1 (auto) or 2 (whenever the gap scores allow)");
         ctx->opt_f16 = value;
+    } else if (!strcmp(key, "f16_pair")) {
+        if (value < 0 || value > 2)
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "f16_pair must be 0 (auto), 1 (v_perm_b32) or 2 (v_pk_fma_f16 wherever it fits)");
+        ctx->opt_f16_pair = value;
     } else if (!strcmp(key, "last_pass")) {
         ctx->opt_last_pass = value != 0;
     } else if (!strcmp(key, "qq")) {
@@ -731,6 +735,13 @@ static int diag_class_form(const swg_ctx *ctx, const swg_db *db, const SwgDiagPl
     return pl.wide ? 1 : 0;
 }
 
+// The f16 cells of a class pair the two sequences' scores with v_pk_fma_f16 (the planner's choice, SwgDiagPlan::fma);
+// its profile layout: (score, 1.0) dwords, 2 columns per chunk.
+static bool diag_class_fma(const swg_ctx *ctx, const swg_db *db, const SwgDiagPlan &pl)
+{
+    return pl.fma && diag_class_form(ctx, db, pl) == 2;
+}
+
 // An integer 0..2048 as an f16 bit pattern (exact), in both halves of a dword.
 static uint32_t f16x2_of(int v)
 {
@@ -752,7 +763,7 @@ static int diag_class_workgroups(const swg_ctx *ctx, const swg_db *db, const Swg
     const SwgDiagPlan &pl = wk.plan[c];
     if (c != 0 || !diag_class_is_dynamic(ctx, db, pl)) return pl.workgroups;
     const SwgKernelInfo info = swg_diag_variant_info(pl.variant);
-    const size_t lds = swg_diag_dyn_lds_bytes(pl.K, pl.G, pl.W);
+    const size_t lds = swg_diag_dyn_lds_bytes(pl.K, pl.G, pl.W, diag_class_fma(ctx, db, pl));
     const int per_cu = std::max(1, std::min<int>(info.max_waves / pl.W, (int)((160 * 1024) / lds)));
     if (ctx->opt_wave_budget > 0 && wk.n_classes == 1) // experiment: more resident wavefronts than the planner's 16 per CU
         return std::max(1, ctx->n_cu * std::max(1, std::min<int>((int)ctx->opt_wave_budget / pl.W, (int)((160 * 1024) / lds))));
@@ -821,18 +832,21 @@ static int prepare_diag(swg_ctx *ctx, swg_db *db, const SwgDiagWork &wk)
             HIP_TRY(ctx, hipMalloc(&db->ptok.d_edge[1], bytes));
             db->ptok.edge_blocks = db->ptok.total_blocks;
         }
-        const int kp = swg_diag_padded_cols(pl.K);
+        // (the f16 cells with the fma pairing: (score, 1.0) dwords in 2-column chunks, K padded to 2 columns)
+        const bool fma = diag_class_fma(ctx, db, pl);
+        const int kp = swg_diag_padded_cols(pl.K, fma);
         // (a last pass with a geometry of its own: its slice follows the other passes' in the same buffer)
         const bool own_last = pl.npass > 1 && pl.last_variant >= 0 && diag_class_is_dynamic(ctx, db, pl);
-        const int kp_last = own_last ? swg_diag_padded_cols(pl.last_K) : kp;
+        const int kp_last = own_last ? swg_diag_padded_cols(pl.last_K, fma) : kp;
         const uint32_t tail = own_last ? (uint32_t)(pl.G * kp_last) : 0u;
         const uint32_t ncols = (uint32_t)((pl.npass - (own_last ? 1 : 0)) * pl.G * kp) + tail;
         const uint32_t qcol0 = (uint32_t)((pl.npass - 1) * pl.G * pl.K);
-        int rc = ensure_profile_cols(ctx, diag_profile_slot(pl, c), ncols, 2,
-                                     (1ull << 55) | ((uint64_t)pl.K << 40) | ((uint64_t)pl.G << 32) | (uint64_t)ncols, pl.K, kp, 4,
-                                     SWG_LDS_SWIZZLE ? pl.G : 0, diag_class_form(ctx, db, pl) == 2, tail, pl.last_K, kp_last, qcol0);
+        int rc = ensure_profile_cols(ctx, diag_profile_slot(pl, c), ncols, fma ? 4 : 2,
+                                     (1ull << 55) | ((uint64_t)fma << 51) | ((uint64_t)pl.K << 40) | ((uint64_t)pl.G << 32) | (uint64_t)ncols,
+                                     pl.K, kp, fma ? 2 : 4, SWG_LDS_SWIZZLE ? pl.G : 0, diag_class_form(ctx, db, pl) == 2, tail, pl.last_K,
+                                     kp_last, qcol0);
         if (rc != SWG_OK) return rc;
-        if (pl.f16_from > 0) { // both forms in this class: the f16 cells' profile of the same geometry
+        if (pl.f16_from > 0) { // both forms in this class: the f16 cells' profile of the same geometry (v_perm_b32 pairing)
             rc = ensure_profile_cols(ctx, 7, ncols, 2, (1ull << 55) | ((uint64_t)pl.K << 40) | ((uint64_t)pl.G << 32) | (uint64_t)ncols,
                                      pl.K, kp, 4, SWG_LDS_SWIZZLE ? pl.G : 0, 1, tail, pl.last_K, kp_last, qcol0);
             if (rc != SWG_OK) return rc;
@@ -949,7 +963,8 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
             // start / end wall-clock stamps of single-pass launches: words 8..15 of the counters
             q.stamps = pl.npass == 1 ? reinterpret_cast<unsigned long long *>(db->d_counters + 8 + 4 * c) : nullptr;
             const bool edges = pl.npass > 1 || form == 1;
-            const size_t slice = (size_t)pl.G * swg_diag_padded_cols(pl.K) * 64;
+            const bool fma = diag_class_fma(ctx, db, pl); // (never with a split: its f16 part takes the v_perm_b32 profile)
+            const size_t slice = swg_diag_slice_bytes(pl.K, pl.G, fma);
             hipStream_t qs = c == 1 ? ctx->stream2 : s;
             // The form with edges addresses a launch's tokens and edges by 32-bit offsets: pairs whose
             // token blocks span more than SWG_DYN_SEG_BLOCKS go in several launches per pass, each over a
@@ -1009,7 +1024,7 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
                         const int wgs_c = diag_class_workgroups(ctx, db, wk, c);
                         // (with long_helps the long class's kernel reads the bulk's counters too, as single pairs: no zones then)
                         if (!(ctx->opt_long_helps && wk.n_classes == 2)) dyn_batch_zones(ctx, T, &q, (uint64_t)wgs_c * pl.W * (64 / pl.G), swg_diag_variant_info(variant).K, pl.G, pform);
-                        HIP_TRY(ctx, swg_launch_diag_dyn(variant, edges, pform, pl.W, wgs_c, q, qs));
+                        HIP_TRY(ctx, swg_launch_diag_dyn(variant, edges, pform, pl.W, wgs_c, q, qs, 1, fma));
                         ++launches;
                         if (split && part == 1) ++f16_launches;
                     }
@@ -1574,7 +1589,7 @@ static int autotune_diag(swg_ctx *ctx, swg_db *db, size_t lq, int go, int ge, Sw
     SwgDiagWork *best = &tuned->wk;
     std::vector<SwgDiagWork> cands;
     const bool work_queue = ctx->opt_dynamic != 0 && db->ptok.ok;
-    if (swg_plan_diag_candidates(db, lq, ctx->n_cu, 0, 0, 0, 0, true, work_queue, &cands, 1.0, form) <= 0) return SWG_ERR_ARG;
+    if (swg_plan_diag_candidates(db, lq, ctx->n_cu, 0, 0, 0, 0, true, work_queue, &cands, 1.0, form, ctx->opt_f16_pair) <= 0) return SWG_ERR_ARG;
     for (SwgDiagWork &c : cands) // (the trials run on the cells the search will use)
         for (int k = 0; k < c.n_classes; ++k) c.plan[k].f16 = form == 2;
     // distinct (K, G, W, split) among the best-ranked
@@ -1651,7 +1666,7 @@ static int autotune_diag(swg_ctx *ctx, swg_db *db, size_t lq, int go, int ge, Sw
             const long thr = (long)std::max(64.0, (dyn ? fr_dyn[i] : fr_static[i]) * unit);
             std::vector<SwgDiagWork> alt;
             if (swg_plan_diag_candidates(db, lq, ctx->n_cu, base.plan[0].K, base.plan[0].G, base.plan[0].W, thr, true,
-                                         work_queue, &alt, 1.0, form) <= 0)
+                                         work_queue, &alt, 1.0, form, ctx->opt_f16_pair) <= 0)
                 continue;
             for (SwgDiagWork &c : alt)
                 for (int k = 0; k < c.n_classes; ++k) c.plan[k].f16 = form == 2;
@@ -1830,7 +1845,8 @@ static int search_begin(swg_ctx *ctx, const swg_db *db, bool want_scores, size_t
         const bool free_geometry = ctx->opt_cols == 0 && ctx->opt_group == 0 && ctx->opt_max_waves == 0 &&
                                    ctx->opt_long_split == 0 && ctx->opt_workgroups == 0;
         swg_db *mdb = const_cast<swg_db *>(db);
-        const uint64_t tuned_key = (uint64_t)lq | ((uint64_t)plan_form << 40); // (a geometry is tuned for the cells it ran on)
+        // (a geometry is tuned for the cells it ran on, and the pairings it was allowed)
+        const uint64_t tuned_key = (uint64_t)lq | ((uint64_t)plan_form << 40) | ((uint64_t)ctx->opt_f16_pair << 44);
         auto it = free_geometry ? mdb->tuned.find(tuned_key) : mdb->tuned.end();
         if (it == mdb->tuned.end() && free_geometry && ctx->opt_autotune && ctx->opt_engine == 0 &&
             db->n_local >= 4096 && db->n_local <= (4u << 20)) {
@@ -1855,7 +1871,7 @@ static int search_begin(swg_ctx *ctx, const swg_db *db, bool want_scores, size_t
         if (!use_diag && !tuned_systolic)
             use_diag = swg_plan_diag_work(db, lq, ctx->n_cu, ctx->opt_cols, ctx->opt_group, ctx->opt_max_waves,
                                           ctx->opt_long_split, ctx->opt_workgroups == 0,
-                                          ctx->opt_dynamic != 0 && db->ptok.ok, &wk, 1.0, plan_form) > 0;
+                                          ctx->opt_dynamic != 0 && db->ptok.ok, &wk, 1.0, plan_form, ctx->opt_f16_pair) > 0;
         // The cost model's word on the ENGINE (round 4; until then only the autotuner could pick the systolic one, and it
         // is off for databases beyond 4 M sequences and wherever the caller turned it off): a database of short sequences
         // of near-equal length -- peptides -- is what the systolic engine is good at (no reset rows, no flags, nothing per
@@ -2611,7 +2627,7 @@ static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const int8_t *queri
         if (rc != SWG_OK) return rc;
         fast = db->ptok.ok &&
                swg_plan_diag_work(db, lq_max, ctx->n_cu, 0, 0, 0, ctx->opt_long_split, true, true, &wk,
-                                  (double)std::min(n_queries, Qb_max), form) > 0;
+                                  (double)std::min(n_queries, Qb_max), form, 1) > 0; // (batches: v_perm_b32 pairing)
         for (int c = 0; fast && c < wk.n_classes; ++c)
             fast = wk.plan[c].npass == 1 && diag_class_is_dynamic(ctx, db, wk.plan[c]) && (size_t)wk.plan[c].G * wk.plan[c].K >= lq_max;
         // A database of short sequences is faster on the systolic engine, one query after another (no batch form of

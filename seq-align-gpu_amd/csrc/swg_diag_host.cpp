@@ -7,7 +7,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <mutex>
 #include <queue>
+
+static std::mutex g_plan_cache_mutex; // (swg_db::plan_key, plan_last: databases may be searched from several threads)
 
 // Cycles one SIMD needs per packed-int16 / DPP / v_perm wave-instruction when `wps` waves share
 // it.  One wave: the microbenchmark (profiles/r01_valu_issue_rates.txt).  Two to four: from the
@@ -62,18 +65,44 @@ uint64_t swg_db_pairs_longer_than(const swg_db *db, uint64_t rows)
 //   dominate small databases.
 // 10 per column pair plus the row's bookkeeping: 14 instructions, but worth about 30 issue slots
 // (DPP wait states, the wait for the row's first profile read) by the K = 16 / 24 / 32 comparison
-// (the packed-f16 cells, form 2, take 8.5 per column pair: DESIGN 4.1)
-static double instr_per_row(int K, int G, int form = 0) { return (form == 2 ? 8.5 : 10.0) * K + (G == 32 ? 34.0 : 30.0); }
+// (the packed-f16 cells, form 2, take 8.5 per column pair, 7.5 with the fma pairing: DESIGN 4.1)
+static double instr_per_row(int K, int G, int form = 0, bool fma = false)
+{
+    return (form == 2 ? (fma ? 7.5 : 8.5) : 10.0) * K + (G == 32 ? 34.0 : 30.0);
+}
+
+// The f16 cells' pairings a geometry may take (f16_pair: 0 both, ranked by the model; 1 v_perm_b32 only; 2 the fma
+// pairing wherever its doubled profile fits, v_perm_b32 elsewhere): bit 0 perm, bit 1 fma.  W: the wavefronts whose
+// lane-group records share the LDS with the profile (0: the profile alone).  edges: one pass of several.  (The fma
+// form's instantiations with edges at 23 and 24 columns do not fit their 128 registers -- 19 and 22 spilled -- and are
+// left out.)
+static int pairings(int form, int K, int G, int W, bool edges, long f16_pair)
+{
+    if (form != 2) return 1;
+    const bool fits = (W > 0 ? swg_diag_dyn_lds_bytes(K, G, W, true) : swg_diag_slice_bytes(K, G, true)) <= 160 * 1024;
+    if (!fits || f16_pair == 1 || (edges && (K == 23 || K == 24))) return 1;
+    return f16_pair == 2 ? 2 : 3;
+}
 // one pass of several through the work queue: row index, edge hand-over to the leader, the tail's
 // edge store
 static const double kEdgeInstr = 7.0;
+
+// Wavefronts per SIMD the work-queue kernel reaches at (K, G) with the perm pairing's profile, at its best workgroup size
+static int perm_occupancy(const SwgKernelInfo &info, int G)
+{
+    int best = 0;
+    for (int W = 4; W <= info.max_waves; W += 4)
+        best = std::max(best, std::min(4, W / 4 * std::max(1, std::min<int>(info.max_waves / W, (int)((160 * 1024) / swg_diag_dyn_lds_bytes(info.K, G, W))))));
+    return best;
+}
 
 // Long class: the cheapest geometry (instructions per pair-row, column padding included)
 // whose longest chain still finishes within `budget_cycles`; if none does, the shortest chain.
 long g_swg_long_cols = 0;  // experiment switch: restrict the long class to this K (0 = free)
 long g_swg_long_group = 0; // experiment switch: restrict the long class to this G (0 = free)
 
-static bool long_class_geometry(size_t lq, uint64_t longest_rows, double budget_cycles, bool dynamic, SwgDiagPlan *lp, int form)
+static bool long_class_geometry(size_t lq, uint64_t longest_rows, double budget_cycles, bool dynamic, SwgDiagPlan *lp, int form,
+                                long f16_pair)
 {
     bool ok = false, ok_fit = false;
     double best_cost = 1e300, best_depth = 1e300;
@@ -94,7 +123,9 @@ static bool long_class_geometry(size_t lq, uint64_t longest_rows, double budget_
             if ((size_t)G * swg_diag_padded_cols(info.K) * 64 > 160 * 1024) continue;
             const int npass = (int)((lq + cols - 1) / cols);
             if (dynamic && npass > 1) continue; // the queue serves single-pass classes only
-            const double instr = npass * instr_per_row(info.K, G, form);
+            // (the f16 cells: the fma pairing where it fits beside the records of the class's four wavefronts)
+            const bool fma = pairings(form, info.K, G, 4, npass > 1, f16_pair) & 2;
+            const double instr = npass * instr_per_row(info.K, G, form, fma);
             const double cost = instr / (64 / G);                     // per pair-row
             const double depth = ((double)longest_rows + G) * instr * kHotCycles;
             SwgDiagPlan c;
@@ -103,7 +134,8 @@ static bool long_class_geometry(size_t lq, uint64_t longest_rows, double budget_
             c.G = G;
             c.npass = npass;
             c.W = 4;
-            c.lds_bytes = (size_t)G * swg_diag_padded_cols(info.K) * 64;
+            c.fma = fma ? 1 : 0;
+            c.lds_bytes = swg_diag_slice_bytes(info.K, G, fma);
             if (depth <= budget_cycles && cost < best_cost) {
                 best_cost = cost;
                 fit = c;
@@ -120,9 +152,10 @@ static bool long_class_geometry(size_t lq, uint64_t longest_rows, double budget_
     return ok;
 }
 
-int swg_plan_diag_candidates(const swg_db *db, size_t lq, int n_cu, long opt_cols, long opt_group, long opt_waves,
-                             long opt_long_split, bool allow_split, bool work_queue, std::vector<SwgDiagWork> *cands,
-                             double copies, int form)
+// sorted = false: only cands[0] is the first-ranked plan (what swg_plan_diag_work needs, on every search: no sort)
+static int plan_candidates(const swg_db *db, size_t lq, int n_cu, long opt_cols, long opt_group, long opt_waves,
+                           long opt_long_split, bool allow_split, bool work_queue, std::vector<SwgDiagWork> *cands,
+                           double copies, int form, long f16_pair, bool sorted)
 {
     // copies > 1: the same database is searched by that many queries in ONE launch (swg_search_multi):
     // all throughput terms grow with it, the longest chain of rows does not
@@ -143,15 +176,19 @@ int swg_plan_diag_candidates(const swg_db *db, size_t lq, int n_cu, long opt_col
             const int G = groups[gi];
             if (opt_group > 0 && G != (int)opt_group) continue;
             const size_t cols = (size_t)G * info.K;
-            const size_t lds = (size_t)G * swg_diag_padded_cols(info.K) * 64;
-            if (lds > 160 * 1024) continue;
+            if (swg_diag_slice_bytes(info.K, G) > 160 * 1024) continue;
             const int npass = (int)((lq + cols - 1) / cols);
             const int NG = 64 / G;
             // with the work queue (several passes: one launch per pass) there are no fixed shares, the
             // chain that matters is the longest pair at the rate of a wavefront that gets its fair
             // share of the SIMD
             const bool dynamic = work_queue && (npass == 1 || db->n_local < (1u << 30));
-            const double instr = instr_per_row(info.K, G, form) + (dynamic && npass > 1 ? kEdgeInstr : 0.0);
+            // the f16 cells' two pairings are two candidates: the fma one's profile is twice the size (occupancy)
+            for (int fma = 0; fma <= 1; ++fma) {
+            // (the f16 cells run on the work queue only)
+            if (!(pairings(form, info.K, G, 0, npass > 1, f16_pair) & (1 << fma)) || (fma && !dynamic)) continue;
+            const size_t lds = swg_diag_slice_bytes(info.K, G, fma);
+            const double instr = instr_per_row(info.K, G, form, fma) + (dynamic && npass > 1 ? kEdgeInstr : 0.0);
             for (int wps = 1; wps <= 4; ++wps) {
                 const int W = 4 * wps;
                 if (W > info.max_waves) continue;
@@ -164,7 +201,7 @@ int swg_plan_diag_candidates(const swg_db *db, size_t lq, int n_cu, long opt_col
                     // (occupancy by the workgroup's real LDS size, lane-group records included: at exactly two
                     // profiles per CU they decide whether a second workgroup fits)
                     auto occupancy = [&](int w) {
-                        const size_t l = swg_diag_dyn_lds_bytes(info.K, G, 4 * w);
+                        const size_t l = swg_diag_dyn_lds_bytes(info.K, G, 4 * w, fma);
                         return std::min(4, w * std::max(1, std::min<int>(info.max_waves / (4 * w), (int)((160 * 1024) / l))));
                     };
                     bool improves = true;
@@ -173,9 +210,14 @@ int swg_plan_diag_candidates(const swg_db *db, size_t lq, int n_cu, long opt_col
                     if (!improves) continue;
                 }
                 // (the work-queue kernels keep a 512-byte record per lane group behind the profile)
-                const size_t lds_wg = dynamic ? swg_diag_dyn_lds_bytes(info.K, G, W) : lds;
+                if (fma && swg_diag_dyn_lds_bytes(info.K, G, W, true) > 160 * 1024) continue;
+                const size_t lds_wg = dynamic ? swg_diag_dyn_lds_bytes(info.K, G, W, fma) : lds;
                 const int per_cu = std::max(1, std::min<int>(info.max_waves / W, (int)((160 * 1024) / lds_wg)));
                 const int eff_wps = std::min(4, wps * per_cu);
+                // the fma pairing only where its doubled profile costs no resident wavefronts: at fewer per SIMD than the
+                // perm pairing reaches with the same columns and lanes it measured slower (config 2, 16 x 23: two
+                // wavefronts per SIMD instead of four, -1.6 %), whatever the instruction count says
+                if (fma && eff_wps < perm_occupancy(info, G)) continue;
                 const uint64_t spw = (uint64_t)W * NG;
                 const uint64_t hw_streams = (uint64_t)n_cu * per_cu * spw;
                 // (a long class beside a multi-pass queue launch would need its own edge buffers: not built)
@@ -231,8 +273,9 @@ int swg_plan_diag_candidates(const swg_db *db, size_t lq, int n_cu, long opt_col
                             lp.G = G;
                             lp.npass = npass;
                             lp.W = 4;
+                            lp.fma = fma;
                             lp.lds_bytes = lds;
-                        } else if (!long_class_geometry(lq, longest_long, 0.8 * bulk_cycles, dynamic, &lp, form)) {
+                        } else if (!long_class_geometry(lq, longest_long, 0.8 * bulk_cycles, dynamic, &lp, form, f16_pair)) {
                             continue;
                         }
                         const uint64_t lspw = 4ull * (64 / lp.G);
@@ -240,7 +283,7 @@ int swg_plan_diag_candidates(const swg_db *db, size_t lq, int n_cu, long opt_col
                         lstreams = std::max<uint64_t>(1, std::min<uint64_t>(dynamic ? (uint64_t)((double)n_long * copies) : (n_long + 1) / 2,
                                                                             (uint64_t)n_cu * lspw));
                         lstreams = (lstreams + lspw - 1) / lspw * lspw;
-                        const double linstr = instr_per_row(lp.K, lp.G, form);
+                        const double linstr = instr_per_row(lp.K, lp.G, form, lp.fma != 0);
                         work += rows_long / (64 / lp.G) * lp.npass * linstr * cps;
                         const double lcrit = (std::max<double>(rows_long / lstreams, (double)longest_long) + lp.G) *
                                              lp.npass * linstr * kHotCycles;
@@ -274,6 +317,7 @@ int swg_plan_diag_candidates(const swg_db *db, size_t lq, int n_cu, long opt_col
                         b.G = G;
                         b.npass = npass;
                         b.W = W;
+                        b.fma = fma;
                         b.n_streams = (uint32_t)streams;
                         b.workgroups = (int)(streams / spw);
                         b.lds_bytes = lds;
@@ -294,26 +338,54 @@ int swg_plan_diag_candidates(const swg_db *db, size_t lq, int n_cu, long opt_col
                     }
                 }
             }
+            }
         }
     }
     // (a positive long_split is a request: plans with the class it asks for rank before those without, whatever
     // the model thinks of them -- when no pair is that long there are none, and the rest is ranked as usual)
     const bool want_long = have_long && opt_long_split > 0;
-    std::stable_sort(cands->begin(), cands->end(), [want_long](const SwgDiagWork &a, const SwgDiagWork &b) {
+    auto before = [want_long](const SwgDiagWork &a, const SwgDiagWork &b) {
         const bool la = want_long && a.n_classes == 2, lb = want_long && b.n_classes == 2;
         return la != lb ? la : a.plan[0].est_ms < b.plan[0].est_ms;
-    });
+    };
+    if (sorted) std::stable_sort(cands->begin(), cands->end(), before);
+    else if (!cands->empty()) std::iter_swap(cands->begin(), std::min_element(cands->begin(), cands->end(), before)); // (the first of equals, as the stable sort)
     return (int)cands->size();
 }
 
-int swg_plan_diag_work(const swg_db *db, size_t lq, int n_cu, long opt_cols, long opt_group, long opt_waves,
-                       long opt_long_split, bool allow_split, bool work_queue, SwgDiagWork *wk, double copies, int form)
+int swg_plan_diag_candidates(const swg_db *db, size_t lq, int n_cu, long opt_cols, long opt_group, long opt_waves,
+                             long opt_long_split, bool allow_split, bool work_queue, std::vector<SwgDiagWork> *cands,
+                             double copies, int form, long f16_pair)
 {
+    return plan_candidates(db, lq, n_cu, opt_cols, opt_group, opt_waves, opt_long_split, allow_split, work_queue, cands, copies,
+                           form, f16_pair, true);
+}
+
+int swg_plan_diag_work(const swg_db *db, size_t lq, int n_cu, long opt_cols, long opt_group, long opt_waves,
+                       long opt_long_split, bool allow_split, bool work_queue, SwgDiagWork *wk, double copies, int form, long f16_pair)
+{
+    // (the experiment switches of the long class are part of the question too)
+    const std::vector<double> key = {(double)lq, (double)n_cu, (double)opt_cols, (double)opt_group, (double)opt_waves,
+                                     (double)opt_long_split, (double)allow_split, (double)work_queue, copies, (double)form,
+                                     (double)f16_pair, (double)g_swg_long_cols, (double)g_swg_long_group,
+                                     (double)swg_db_pair_count(db)};
+    swg_db *mdb = const_cast<swg_db *>(db);
+    {
+        std::lock_guard<std::mutex> lock(g_plan_cache_mutex);
+        if (mdb->plan_key == key) {
+            *wk = mdb->plan_last;
+            return mdb->plan_last_n;
+        }
+    }
     std::vector<SwgDiagWork> c;
     wk->n_classes = 0;
-    if (swg_plan_diag_candidates(db, lq, n_cu, opt_cols, opt_group, opt_waves, opt_long_split, allow_split, work_queue,
-                                 &c, copies, form) > 0)
+    if (plan_candidates(db, lq, n_cu, opt_cols, opt_group, opt_waves, opt_long_split, allow_split, work_queue, &c, copies, form,
+                        f16_pair, false) > 0)
         *wk = c[0];
+    std::lock_guard<std::mutex> lock(g_plan_cache_mutex);
+    mdb->plan_key = key;
+    mdb->plan_last = *wk;
+    mdb->plan_last_n = wk->n_classes;
     return wk->n_classes;
 }
 
@@ -548,7 +620,7 @@ double swg_diag_short_pair_factor(const swg_db *db, const SwgDiagPlan &pl, int f
     const double L = std::max(4.0, (double)swg_db_pair_rows(db, 0, n_pairs, &longest) / (double)n_pairs);
     auto p_flag = [](double rows) { return 1.0 - std::pow(std::max(0.0, 1.0 - 3.0 / rows), 64.0); };
     const double extra = 19.0 * std::max(0.0, p_flag(L) - p_flag(380.0));
-    return 1.0 + extra / instr_per_row(pl.K, pl.G, form);
+    return 1.0 + extra / instr_per_row(pl.K, pl.G, form, form == 2 && pl.fma);
 }
 
 // test hook: both engines' estimates for a database and a query length (cells: 0 int16, 2 packed f16), without a device:
@@ -578,12 +650,12 @@ extern "C" int swg_debug_engine(const swg_db *db, size_t lq, int n_cu, int form,
 // for a packed database and a query length on a device of n_cu compute units, without a device.
 // out[0..12] = classes, K, G, W, passes, workgroups, long pairs, long K, long G, long W, long workgroups,
 // estimated microseconds, columns per lane of the last pass (0: as the other passes).
-extern "C" int swg_debug_plan(const swg_db *db, size_t lq, int n_cu, int32_t *out)
+static int debug_plan(const swg_db *db, size_t lq, int n_cu, int form, long f16_pair, int32_t *out)
 {
-    if (!db || !out || lq == 0 || n_cu <= 0) return SWG_ERR_ARG;
+    if (!db || !out || lq == 0 || n_cu <= 0 || f16_pair < 0 || f16_pair > 2) return SWG_ERR_ARG;
     SwgDiagWork wk;
     try {
-        if (swg_plan_diag_work(db, lq, n_cu, 0, 0, 0, 0, true, true, &wk) <= 0) return SWG_ERR_ARG;
+        if (swg_plan_diag_work(db, lq, n_cu, 0, 0, 0, 0, true, true, &wk, 1.0, form, f16_pair) <= 0) return SWG_ERR_ARG;
     } catch (const std::exception &) {
         return SWG_ERR_NOMEM;
     }
@@ -594,5 +666,17 @@ extern "C" int swg_debug_plan(const swg_db *db, size_t lq, int n_cu, int32_t *ou
     const int32_t v[13] = {wk.n_classes, b.K, b.G, b.W, b.npass, b.workgroups, two ? (int32_t)(wk.pair_end[1] - wk.pair_begin[1]) : 0,
                            two ? l.K : 0, two ? l.G : 0, two ? l.W : 0, two ? l.workgroups : 0, (int32_t)(b.est_ms * 1e3), last_K};
     memcpy(out, v, sizeof v);
+    if (form == 2) {
+        out[13] = b.fma;
+        out[14] = (int32_t)swg_diag_dyn_lds_bytes(b.K, b.G, b.W, b.fma != 0);
+        out[15] = two ? l.fma : 0;
+    }
     return SWG_OK;
+}
+
+extern "C" int swg_debug_plan(const swg_db *db, size_t lq, int n_cu, int32_t *out) { return debug_plan(db, lq, n_cu, 0, 0, out); }
+
+extern "C" int swg_debug_plan_f16(const swg_db *db, size_t lq, int n_cu, long f16_pair, int32_t *out)
+{
+    return debug_plan(db, lq, n_cu, 2, f16_pair, out);
 }

@@ -84,6 +84,9 @@ struct SwgDiagPlan {
     // Several passes: the last one covers what is left of the query with the fewest columns per lane that do
     // (its own kernel instantiation and profile layout; edges do not depend on the geometry).  -1: as the others.
     int last_variant = -1, last_K = 0;
+    // f16 cells (form 2): the fma pairing (CellsDiag FMA: (score, 1.0) profile of twice the size, 7.5 instructions per
+    // column pair) instead of v_perm_b32 (8.5); ignored on the other cells
+    int fma = 0;
     uint32_t n_streams = 0;
     size_t lds_bytes = 0;
     double est_ms = 0.0;
@@ -127,6 +130,11 @@ struct swg_db {
     SwgPairTokens ptok;             // pair-major tokens (work-queue form of the diagonal engine)
     SwgDiagLayout diag[2];          // stream layouts of the diagonal engine: [0] bulk, [1] long pairs
     std::vector<uint64_t> pair_rows_prefix; // rows of the pairs before pair p (swg_db_pair_rows: built on first use)
+    // swg_plan_diag_work's last answer and what it was asked (the model is a pure function of the lengths and of
+    // these): a search that repeats the previous one's question does not rank the geometries again
+    std::vector<double> plan_key;
+    SwgDiagWork plan_last;
+    int plan_last_n = 0;
     std::map<uint64_t, SwgTuned> tuned; // query length -> engine + geometry that measured fastest on this device
     // What the last finished search of this database saw (plans of later searches only: results never depend
     // on it).  sat_hint: sequences its 16-bit fill flagged for the re-score (-1: no search yet), by which
@@ -237,7 +245,7 @@ struct swg_ctx {
     hipEvent_t ev_query_stage[4] = {nullptr, nullptr, nullptr, nullptr};
     int query_stage_next = 0;
     // options
-    long opt_force_bits = 0, opt_cols = 0, opt_max_waves = 0, opt_workgroups = 0, opt_engine = 0, opt_group = 0, opt_long_split = 0, opt_autotune = 1, opt_dynamic = 1, opt_prio_share = 150, opt_long_helps = 0, opt_wide = 1, opt_side_readout = 1, opt_f16 = 1, opt_qq = 1, opt_last_pass = 1;
+    long opt_force_bits = 0, opt_cols = 0, opt_max_waves = 0, opt_workgroups = 0, opt_engine = 0, opt_group = 0, opt_long_split = 0, opt_autotune = 1, opt_dynamic = 1, opt_prio_share = 150, opt_long_helps = 0, opt_wide = 1, opt_side_readout = 1, opt_f16 = 1, opt_qq = 1, opt_last_pass = 1, opt_f16_pair = 0;
     long opt_wave_budget = 0, opt_q32_waves = 0;
     long opt_batch = 8, opt_batch_blocks = 0; // work queue: pairs one request claims where pairs are short (blocks; 0: about 40 us of work, from the geometry)
     uint32_t opt_seg_blocks = SWG_DYN_SEG_BLOCKS; // token blocks per launch of the multi-pass fill (option "segment_blocks": tests)
@@ -269,6 +277,9 @@ void swg_db_release_device(swg_db *db);
 // test hook: the next visit of the named site throws std::bad_alloc (swg_api.cpp); 0 disarms
 extern "C" void swg_debug_fail_alloc(int site);
 extern "C" int swg_debug_plan(const swg_db *db, size_t lq, int n_cu, int32_t *out);
+// the same for the packed-f16 cells (option f16_pair: 0 auto, 1 perm, 2 fma), out[0..15]: swg_debug_plan's 13 values, then
+// the bulk's pairing (1 fma, 0 v_perm_b32), its workgroup's LDS bytes, the long class's pairing
+extern "C" int swg_debug_plan_f16(const swg_db *db, size_t lq, int n_cu, long f16_pair, int32_t *out);
 // the systolic engine's estimate from the host's bin table (swg_diag_host.cpp); it is picked over the lane groups when it
 // wins by this margin (both models are good to about 10 %)
 #define SWG_SYSTOLIC_MARGIN 0.85
@@ -288,11 +299,12 @@ extern "C" int swg_debug_pair_tokens(swg_ctx *ctx, swg_db *db, int from_host, ui
 // classes (0: the diagonal engine cannot run this with the given options)
 int swg_plan_diag_work(const swg_db *db, size_t lq, int n_cu, long opt_cols, long opt_group, long opt_waves,
                        long opt_long_split, bool allow_split, bool work_queue, SwgDiagWork *wk, double copies = 1.0,
-                       int form = 0); // form: the cells the plan is for (2: packed f16, 8.5 instead of 10 instructions per column pair)
+                       int form = 0, // form: the cells the plan is for (2: packed f16, 8.5 instead of 10 instructions per column pair)
+                       long f16_pair = 0); // form 2: the pairings to consider (option f16_pair: 0 both, 1 perm only, 2 fma where it fits)
 // every geometry the model considered, best estimate first (the autotuner times the first few)
 int swg_plan_diag_candidates(const swg_db *db, size_t lq, int n_cu, long opt_cols, long opt_group, long opt_waves,
                              long opt_long_split, bool allow_split, bool work_queue,
-                             std::vector<SwgDiagWork> *cands, double copies = 1.0, int form = 0);
+                             std::vector<SwgDiagWork> *cands, double copies = 1.0, int form = 0, long f16_pair = 0);
 // 0 on success; -1 when the database is too large for 32-bit block offsets.  tok == NULL: only
 // pair_off (the tokens themselves are built on the device, swg_launch_build_tokens); otherwise also
 // the host builder's token image, which the tests compare the device's with.

@@ -197,10 +197,12 @@ int swg_num_diag_variants();
 SwgKernelInfo swg_diag_variant_info(int variant); // K, max_waves (wave budget of one CU)
 hipError_t swg_launch_diag(int variant, bool multipass, bool wide, int W, int workgroups, size_t lds_bytes,
                            const SwgDiagParams &p, hipStream_t stream);
-size_t swg_diag_dyn_lds_bytes(int K, int G, int W);
-// form: the cells (CellsDiag): 0 packed int16, 1 wide int16 (edges only), 2 packed f16 with three-operand maxima
+// fma: the f16 cells' fma pairing (CellsDiag FMA): (score, 1.0) dwords, twice the profile of the other forms
+size_t swg_diag_dyn_lds_bytes(int K, int G, int W, bool fma = false);
+// form: the cells (CellsDiag): 0 packed int16, 1 wide int16 (edges only), 2 packed f16 with three-operand maxima;
+// fma (form 2 only): with the fma pairing, profile built by swg_launch_build_profile with elem_size 4, 2-column chunks
 hipError_t swg_launch_diag_dyn(int variant, bool edges, int form, int W, int workgroups, const SwgDiagDynParams &p,
-                               hipStream_t stream, int n_queries = 1);
+                               hipStream_t stream, int n_queries = 1, bool fma = false);
 // profiles of n_queries queries (query i = queries[q_off[i] .. q_off[i+1])) in one launch: query i's
 // profile of ncols layout columns goes to d_profiles + i * ncols * 32 * 2 (int16)
 hipError_t swg_launch_build_profiles_multi(const int8_t *d_sub, const int8_t *d_queries, const uint32_t *d_q_off,
@@ -225,9 +227,11 @@ hipError_t swg_launch_build_profiles_multi(const int8_t *d_sub, const int8_t *d_
 hipError_t swg_launch_build_profile(const int8_t *d_sub, const int8_t *d_query,
                                     uint32_t lq, uint32_t ncols, int elem_size, int chunk_cols, int k_real,
                                     int k_padded, uint8_t *d_profile, hipStream_t stream, int swizzle_lanes = 0,
-                                    int f16 = 0, // f16: elem_size 2 entries are f16 numbers (pad -65504) for the packed-f16 cells
+                                    int f16 = 0, // f16: elem_size 2 entries are f16 numbers (pad -65504) for the packed-f16 cells;
+                                                 // elem_size 4: (f16 score, 1.0) pairs for their fma pairing (chunk_cols 2)
                                     uint32_t qcol0 = 0); // the query column layout column 0 stands for
-int swg_diag_padded_cols(int K); // layout columns of a lane's slice
+int swg_diag_padded_cols(int K, bool fma = false); // layout columns of a lane's slice
+size_t swg_diag_slice_bytes(int K, int G, bool fma = false); // profile bytes of one pass: G lanes' slices
 
 // Per-database layouts from the uploaded residue dwords (d_code_off in dwords): the pair-major
 // token array of the diagonal engine, and the bin image of the systolic engine / int32 kernels.

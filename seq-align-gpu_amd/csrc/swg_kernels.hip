@@ -41,7 +41,8 @@
 //  * No MFMA: the recurrence is integer max/add with a loop-carried dependency.  The bound is VALU
 //    issue: 10 packed instructions per 2 cells on the int16 cells, 8.5 on the packed-f16 cells that gfx950's
 //    three-operand maximum allows (CellsDiag FORM 2: exact below a score of 4096, anything above flagged and run
-//    again), 7.5 with two queries of a batch per lane (swg_diag_qq_kernel).
+//    again), 7.5 on those with the fma pairing where its doubled profile fits (CellsDiag FMA) and with two queries of
+//    a batch per lane (swg_diag_qq_kernel).
 //
 // int16 fast path (gap_open <= 0 and gap_extend <= 0, the normal case): with
 // M = max(H,A,B) the recurrence collapses to
@@ -594,16 +595,34 @@ __global__ __launch_bounds__(MAXW * 64) void swg_fill_kernel(const SwgFillParams
 #define SWG_F16_ZERO 0xE800E800u // -2048.0 in both halves: score 0
 #define SWG_F16_FLAG 0x6800u     // +2048.0 = score 4096: a pair that reaches it is flagged
 #define SWG_F16_CEILING 4096
-template <int K, int FORM = 0> struct CellsDiag {
+#ifndef SWG_FMA_FENCE_CHUNKS
+#define SWG_FMA_FENCE_CHUNKS 2
+#endif
+// v_pk_fma_f16 with the operand halves crossed: (x.lo * y.hi + d.lo, x.hi * y.lo + d.hi).  With profile dwords of
+// (score, 1.0) -- x from sequence X's residue row, y from Y's -- that is (S[X] + d.lo, S[Y] + d.hi): the pairing of the
+// two sequences' scores and the diagonal add in one instruction, each half the exact sum rounded once, as
+// v_pk_add_f16 gives it.  (The compiler does not form it from builtins.)
+DEVINL uint32_t pk_fma_pair_f16(uint32_t x, uint32_t y, uint32_t d)
+{
+    uint32_t r;
+    asm("v_pk_fma_f16 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(x), "v"(y), "v"(d));
+    return r;
+}
+// FMA (FORM 2 only): the profile holds (score, 1.0) f16 pairs, 2 columns per 256-byte chunk, and the cells pair the two
+// sequences' scores with pk_fma_pair_f16 instead of v_perm_b32 + v_pk_add_f16: 7.5 instructions per column pair instead
+// of 8.5, for twice the profile (G * KP * 128 bytes of LDS) and twice the profile reads per row.
+template <int K, int FORM = 0, bool FMA = false> struct CellsDiag {
     static constexpr bool WIDE = FORM == 1, F16 = FORM == 2;
+    static_assert(!FMA || F16, "the fma pairing exists for the f16 cells only");
     static constexpr uint32_t ZERO = WIDE ? 0x80008000u : F16 ? SWG_F16_ZERO : 0u;
     DEVINL static uint32_t sub(uint32_t a, uint32_t b) { return F16 ? pk_sub_f16(a, b) : WIDE ? pk_sub_i16_sat(a, b) : pk_sub_u16_sat(a, b); }
-    // A profile chunk is [32 residues][4 columns] int16 = 256 bytes; a lane's slice of the profile
-    // is KP = K rounded up to whole chunks, the columns it works on are the first K (any K: G*K
-    // lands within G/2 columns of the query length on average instead of 2*G).
-    static constexpr int CH = 4;
+    // A profile chunk is [32 residues][4 columns] int16 = 256 bytes ([32 residues][2 columns] of (f16, f16) pairs with
+    // FMA); a lane's slice of the profile is KP = K rounded up to whole chunks, the columns it works on are the first K
+    // (any K: G*K lands within G/2 columns of the query length on average instead of 2*G).
+    static constexpr int CH = FMA ? 2 : 4;
     static constexpr int KP = (K + CH - 1) / CH * CH;
-    static constexpr int CHUNK = 32 * CH * 2;
+    static constexpr int CHUNK = 32 * CH * (FMA ? 4 : 2);
+    static constexpr int SLICE = KP / CH * CHUNK; // bytes of a lane's slice
     uint32_t M[K], G[K], A[K];
     uint32_t best, mdl;
 
@@ -642,10 +661,12 @@ template <int K, int FORM = 0> struct CellsDiag {
     // arithmetic and nothing moves across the chunk boundary, so at most two chunks' words (8
     // registers) are in flight.  Left alone the scheduler hoists eight reads and K=24 spills.
     // zero: F16 only: score 0 (SWG_F16_ZERO) in a register the caller keeps (a literal would be re-materialised per use)
+    // (FMA: a fence every SWG_FMA_FENCE_CHUNKS chunks, the prefetch stays one chunk deep)
     template <bool FENCED = false>
     DEVINL uint2 row(uint32_t ax, uint32_t ay, uint32_t em, uint32_t eb, uint32_t go, uint32_t ge, uint32_t zero = 0u)
     {
         constexpr int NCH = KP / CH;
+        constexpr int FENCE_CHUNKS = FMA ? SWG_FMA_FENCE_CHUNKS : 1;
         uint32_t md = mdl;
         uint32_t gl = sub(em, go);
         uint32_t bl = eb;
@@ -657,18 +678,20 @@ template <int K, int FORM = 0> struct CellsDiag {
                 nx = lds_read_u2(ax + (c + 1) * CHUNK);
                 ny = lds_read_u2(ay + (c + 1) * CHUNK);
             }
-            uint32_t s[CH];
-            s[0] = __builtin_amdgcn_perm(wy.x, wx.x, 0x05040100u);
-            s[1] = __builtin_amdgcn_perm(wy.x, wx.x, 0x07060302u);
-            s[2] = __builtin_amdgcn_perm(wy.y, wx.y, 0x05040100u);
-            s[3] = __builtin_amdgcn_perm(wy.y, wx.y, 0x07060302u);
+            uint32_t s[4];
+            if (!FMA) {
+                s[0] = __builtin_amdgcn_perm(wy.x, wx.x, 0x05040100u);
+                s[1] = __builtin_amdgcn_perm(wy.x, wx.x, 0x07060302u);
+                s[2] = __builtin_amdgcn_perm(wy.y, wx.y, 0x05040100u);
+                s[3] = __builtin_amdgcn_perm(wy.y, wx.y, 0x07060302u);
+            }
             uint32_t mprev = 0u;
 #pragma unroll
             for (int u = 0; u < CH; ++u) {
                 const int k = CH * c + u;
                 if (k >= K) break; // unused tail of the last chunk
                 if (F16) {
-                    const uint32_t t = pk_add_f16(md, s[u]);
+                    const uint32_t t = FMA ? pk_fma_pair_f16(u ? wx.y : wx.x, u ? wy.y : wy.x, md) : pk_add_f16(md, s[u]);
                     md = M[k];
                     const uint32_t a = pk_max3_f16(G[k], pk_sub_f16(A[k], ge), zero);
                     const uint32_t b = pk_max3_f16(gl, pk_sub_f16(bl, ge), zero);
@@ -694,7 +717,7 @@ template <int K, int FORM = 0> struct CellsDiag {
                     best = pk_max_i16(best, m);
                 }
             }
-            if (FENCED && c + 1 < NCH) __builtin_amdgcn_sched_barrier(0);
+            if (FENCED && c + 1 < NCH && (c + 1) % FENCE_CHUNKS == 0) __builtin_amdgcn_sched_barrier(0);
         }
         mdl = em;
         return make_uint2(M[K - 1], bl);
@@ -992,10 +1015,12 @@ DEVINL uint32_t quad_bcast(uint32_t x, int r)
 // leader that finds the queue empty -- reaches it.
 // FORM: the cells (see CellsDiag): 0 packed int16, 1 wide (scores to 65535; needs EDGES: a query that can pass
 // 32767 is long), 2 packed f16 with three-operand maxima (scores below 4096, anything above is flagged).
-template <int K, int MAXW, bool EDGES = false, int FORM = 0>
+// FMA: FORM 2 with the (score, 1.0) profile and the v_pk_fma_f16 pairing (see CellsDiag).
+template <int K, int MAXW, bool EDGES = false, int FORM = 0, bool FMA = false>
 __global__ __launch_bounds__(MAXW * 64) void swg_diag_dyn_kernel(const SwgDiagDynParams p)
 {
     constexpr bool WIDE = FORM == 1, F16 = FORM == 2;
+    using Cells = CellsDiag<K, FORM, FMA>;
     static_assert(EDGES || !WIDE, "the wide form is instantiated with edges only");
     extern __shared__ __attribute__((aligned(256))) uint8_t smem[]; // query profile, then the group records
     const int lane = threadIdx.x & 63;
@@ -1005,9 +1030,9 @@ __global__ __launch_bounds__(MAXW * 64) void swg_diag_dyn_kernel(const SwgDiagDy
     const int gshift = G == 16 ? 4 : G == 32 ? 5 : 6;
     const int g = lane & (G - 1);
     const bool leader = g == 0, tail = g == G - 1;
-    constexpr uint32_t Z = CellsDiag<K, FORM>::ZERO; // score 0 in the cells' representation
-    const uint32_t base = prof_base(SWG_LDS_ADDRESS(smem) + (uint32_t)g * (CellsDiag<K>::KP / 4) * CellsDiag<K>::CHUNK, g);
-    const uint32_t slice = (uint32_t)G * CellsDiag<K>::KP * 64u;
+    constexpr uint32_t Z = Cells::ZERO; // score 0 in the cells' representation
+    const uint32_t base = prof_base(SWG_LDS_ADDRESS(smem) + (uint32_t)g * Cells::SLICE, g);
+    const uint32_t slice = (uint32_t)G * Cells::SLICE;
     // recomputed where it is needed (rarely) instead of living in a register
     auto record = [&]() -> uint32_t * {
         const uint32_t l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -1041,7 +1066,7 @@ __global__ __launch_bounds__(MAXW * 64) void swg_diag_dyn_kernel(const SwgDiagDy
         if ((uint32_t)w >= max(4u, (want + 3u) & ~3u)) return;
     }
 
-    CellsDiag<K, FORM> cells;
+    Cells cells;
     cells.reset();
     uint32_t tok = 0u, m_out = Z, b_out = Z;
     // F16 without edges: score 0 is not a zero bit pattern, so a lane without a DPP source (the leader) cannot be
@@ -2107,6 +2132,9 @@ __global__ void swg_build_profile_kernel(const int8_t *sub, const int8_t *query,
     const size_t e = (size_t)(col / ch) * (32u * ch) + row * ch + (col % ch); // [col/ch][32][ch]
     if (elem_size == 2 && f16) // packed-f16 cells: the score as an f16 number, -65504 for padding
         reinterpret_cast<_Float16 *>(out)[e] = pad ? (_Float16)-65504.0f : (_Float16)(float)v;
+    else if (elem_size == 4 && f16) // the same with the fma pairing: (score, 1.0) in every entry, padding included
+        reinterpret_cast<uint32_t *>(out)[e] =
+            (uint32_t)__builtin_bit_cast(unsigned short, pad ? (_Float16)-65504.0f : (_Float16)(float)v) | 0x3C000000u;
     else if (elem_size == 2)
         reinterpret_cast<int16_t *>(out)[e] = pad ? (int16_t)-32768 : (int16_t)v;
     else
@@ -2626,7 +2654,7 @@ typedef void (*SwgDynKernel)(const SwgDiagDynParams);
 typedef void (*SwgQ32Kernel)(const SwgDiagQ32Params);
 typedef void (*SwgQQKernel)(const SwgDiagQQParams);
 // kernel of a variant, from the part that instantiates it: which = 0 single pass / 1 one pass of several / 2 the same,
-// wide form (int16 cells); 0 single pass / 1 one pass of several (f16 cells)
+// wide form (int16 cells); 0 single pass / 1 one pass of several (f16 cells), 2 / 3 the same with the fma pairing
 SwgDynKernel swg_dyn_kernel_i16(int variant, int which);
 SwgDynKernel swg_dyn_kernel_f16(int variant, int which);
 
@@ -2643,8 +2671,9 @@ SwgDynKernel swg_dyn_kernel_i16(int variant, int which)
 #if SWG_HAS_PART(2)
 SwgDynKernel swg_dyn_kernel_f16(int variant, int which)
 {
-#define SWG_ROW(K, W) {swg_diag_dyn_kernel<K, W, false, 2>, swg_diag_dyn_kernel<K, W, true, 2>},
-    static const SwgDynKernel t[][2] = {SWG_DIAG_VARIANTS(SWG_ROW)};
+#define SWG_ROW(K, W) {swg_diag_dyn_kernel<K, W, false, 2>, swg_diag_dyn_kernel<K, W, true, 2>, swg_diag_dyn_kernel<K, W, false, 2, true>, \
+                       swg_diag_dyn_kernel<K, W, true, 2, true>},
+    static const SwgDynKernel t[][4] = {SWG_DIAG_VARIANTS(SWG_ROW)};
 #undef SWG_ROW
     return t[variant][which];
 }
@@ -2807,15 +2836,17 @@ hipError_t swg_launch_diag(int variant, bool multipass, bool wide, int W, int wo
     return hipGetLastError();
 }
 
-int swg_diag_padded_cols(int K) { return (K + 3) / 4 * 4; }
+int swg_diag_padded_cols(int K, bool fma) { return fma ? (K + 1) / 2 * 2 : (K + 3) / 4 * 4; }
 
-size_t swg_diag_dyn_lds_bytes(int K, int G, int W)
+size_t swg_diag_slice_bytes(int K, int G, bool fma) { return (size_t)G * swg_diag_padded_cols(K, fma) * (fma ? 128u : 64u); }
+
+size_t swg_diag_dyn_lds_bytes(int K, int G, int W, bool fma)
 {
-    return (size_t)G * swg_diag_padded_cols(K) * 64u + (size_t)W * (64 / G) * SWG_DYN_STATE * 4u;
+    return swg_diag_slice_bytes(K, G, fma) + (size_t)W * (64 / G) * SWG_DYN_STATE * 4u;
 }
 
 hipError_t swg_launch_diag_dyn(int variant, bool edges, int form, int W, int workgroups, const SwgDiagDynParams &p,
-                               hipStream_t stream, int n_queries)
+                               hipStream_t stream, int n_queries, bool fma)
 {
     if (n_queries < 1 || n_queries > 65535) return hipErrorInvalidValue;
     int n;
@@ -2823,9 +2854,9 @@ hipError_t swg_launch_diag_dyn(int variant, bool edges, int form, int W, int wor
     if (variant < 0 || variant >= n || W < 1 || W > v[variant].max_waves || workgroups < 1 ||
         (p.G != 16 && p.G != 32 && p.G != 64) || p.q_end < p.q_begin)
         return hipErrorInvalidValue;
-    const size_t lds = swg_diag_dyn_lds_bytes(v[variant].K, (int)p.G, W);
-    if (form < 0 || form > 2 || (form == 1 && !edges)) return hipErrorInvalidValue;
-    auto k = form == 2 ? swg_dyn_kernel_f16(variant, edges ? 1 : 0) : swg_dyn_kernel_i16(variant, form == 1 ? 2 : edges ? 1 : 0);
+    const size_t lds = swg_diag_dyn_lds_bytes(v[variant].K, (int)p.G, W, fma);
+    if (form < 0 || form > 2 || (form == 1 && !edges) || (fma && form != 2) || lds > 160 * 1024) return hipErrorInvalidValue;
+    auto k = form == 2 ? swg_dyn_kernel_f16(variant, (fma ? 2 : 0) + (edges ? 1 : 0)) : swg_dyn_kernel_i16(variant, form == 1 ? 2 : edges ? 1 : 0);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
