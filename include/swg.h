@@ -168,6 +168,19 @@ int swg_set_scoring(swg_ctx *ctx, const int8_t sub[32][32], int gap_open, int ga
  * idx[lq] are table indices; the library copies them. */
 int swg_set_query(swg_ctx *ctx, const int8_t *idx, size_t lq);
 
+/* A position-specific query (a PSSM: PSI-BLAST, an HMM-derived profile, ...): pssm[i*32 + b] = score of query
+ * position i against database residue index b (same coordinates as sub[a][b]; column 0, the padding residue, is
+ * ignored).  Replaces the context's query (an index query set by swg_set_query, or an earlier PSSM); swg_set_query
+ * replaces a PSSM in turn.  Gap scores still come from swg_set_scoring, which must have been called before a
+ * search; the substitution table is not read while a PSSM is the query.  Any int8 value is accepted.  The library
+ * copies the lq*32 bytes; like swg_set_query the copy is queued behind the searches in flight (no wait), so PSSMs
+ * and index queries can be streamed between swg_search_begin calls.  Every query-dependent call follows the PSSM:
+ * swg_search, swg_search_begin/end, swg_fill_batches16, swg_align_hits, swg_align_ops_bound (swg_search_multi
+ * takes index queries of its own and leaves the PSSM in place).  A PSSM search has the plan an index query of the
+ * same scores would have, so the same fill kernels at the same speed; its score bound (which decides the cells
+ * and the re-score) is the sum of each position's best entry over residues 1..31. */
+int swg_set_query_pssm(swg_ctx *ctx, const int8_t *pssm, size_t lq);
+
 /* ---- database --------------------------------------------------------- */
 
 /* Host-only (needs no GPU).  Replaces the 16-lane transpose+pad packer of
@@ -252,7 +265,7 @@ int swg_search_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, cons
  * src/alignment_cmdline.c:434,445), padded rows included and computed as real
  * rows like the reference does; max_scores receives
  * aligner_t.max_scores for lanes 0..vector_size-1, saturated to int16.
- * Uses the scoring and query already set on ctx. */
+ * Uses the scoring and query already set on ctx (a PSSM query included; its scores saturate the same way). */
 typedef struct swg_batch16 {
     const int8_t *db_idx_t;
     size_t max_len;
@@ -318,6 +331,7 @@ const char *swg_group_last_error(const swg_group *g);
 int swg_group_set_option(swg_group *g, const char *key, long value);
 int swg_group_set_scoring(swg_group *g, const int8_t sub[32][32], int gap_open, int gap_extend);
 int swg_group_set_query(swg_group *g, const int8_t *idx, size_t lq);
+int swg_group_set_query_pssm(swg_group *g, const int8_t *pssm, size_t lq); /* swg_set_query_pssm on every device */
 int swg_group_load(swg_group *g, const int8_t *flat, const uint64_t *offsets, size_t n);
 int swg_group_search(swg_group *g, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
                      swg_stats *stats);

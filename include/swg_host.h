@@ -44,6 +44,18 @@ int swg_scoring_add(swg_scoring *sc, int a, int b, int score);
  * in err (the reference prints and exits). */
 int swg_scoring_load_matrix(swg_scoring *sc, const char *path, char *err, size_t errlen);
 
+/* PSI-BLAST's ASCII PSSM (psiblast -out_ascii_pssm): free text, then a header line whose first 20 whitespace
+ * tokens are single letters (the score columns; what follows them, such as the percentages, is ignored), then one
+ * line per query position, `pos letter s1 .. s20 [anything]` with pos = 1, 2, 3, ..., up to the first blank line
+ * (the Lambda/K footer after it is not read).  -> *pssm_out [lq*32] in swg_set_query_pssm's layout: the header's
+ * columns from the file, every other residue code b (B, J, O, U, X, Z, '*', ...) sc->sub[query residue][b],
+ * column 0 zero; *query_out [lq] the residue column as table indices.  gzip-transparent.  On a missing header,
+ * a value outside -128..127, a gap in the positions, an illegal residue letter or a short line: SWG_ERR_IO and a
+ * message naming the line in err.  Release both buffers with swg_pssm_free. */
+int swg_pssm_load(const char *path, const swg_scoring *sc, int8_t **pssm_out, int8_t **query_out, size_t *lq_out,
+                  char *err, size_t errlen);
+void swg_pssm_free(int8_t *pssm, int8_t *query);
+
 /* Query sanitisation of the reference driver (src/alignment_cmdline.c:391-396):
  * a residue whose self-pair is undefined in the table becomes 'X'. */
 void swg_query_sanitize(const swg_scoring *sc, int8_t *idx, size_t n);

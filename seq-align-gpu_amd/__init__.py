@@ -32,18 +32,18 @@ SWG_ERR_STATE, SWG_ERR_RESIDUE, SWG_ERR_IO, SWG_ERR_NODEVICE = -4, -5, -6, -7
 # every symbol declared in include/swg.h and include/swg_host.h
 ABI_SYMBOLS = [
     "swg_create", "swg_destroy", "swg_last_error", "swg_global_error", "swg_abi_version",
-    "swg_set_option", "swg_set_scoring", "swg_set_query", "swg_db_pack", "swg_db_pack_shard", "swg_db_pack_shards", "swg_db_upload",
+    "swg_set_option", "swg_set_scoring", "swg_set_query", "swg_set_query_pssm", "swg_db_pack", "swg_db_pack_shard", "swg_db_pack_shards", "swg_db_upload",
     "swg_db_free", "swg_db_save", "swg_db_load", "swg_db_count", "swg_db_total_count", "swg_db_residues",
     "swg_db_packed_bytes", "swg_db_order", "swg_search", "swg_search_begin", "swg_search_end", "swg_search_multi",
     "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_hit_key",
     "swg_key_hit", "swg_topk_merge_keys",
     "swg_group_create", "swg_group_destroy", "swg_group_size", "swg_group_last_error", "swg_group_set_option",
-    "swg_group_set_scoring", "swg_group_set_query", "swg_group_load", "swg_group_search",
+    "swg_group_set_scoring", "swg_group_set_query", "swg_group_set_query_pssm", "swg_group_load", "swg_group_search",
     "swg_group_align_hits", "swg_group_align_ops_bound",
     "swg_letter_index", "swg_index_letter", "swg_scoring_init", "swg_scoring_add",
     "swg_scoring_load_matrix", "swg_query_sanitize", "swg_seqs_read", "swg_seqs_free",
     "swg_seqs_to_indices", "swg_synth_db", "swg_synth_query", "swg_synth_db_similar", "swg_synth_db_family", "swg_synth_db_shard",
-    "swg_synth_free", "swg_host_threads",
+    "swg_synth_free", "swg_host_threads", "swg_pssm_load", "swg_pssm_free",
 ]
 
 
@@ -122,6 +122,7 @@ _sig("swg_abi_version", C.c_int, [])
 _sig("swg_set_option", C.c_int, [_vp, C.c_char_p, C.c_long])
 _sig("swg_set_scoring", C.c_int, [_vp, _vp, C.c_int, C.c_int])
 _sig("swg_set_query", C.c_int, [_vp, _vp, C.c_size_t])
+_sig("swg_set_query_pssm", C.c_int, [_vp, _vp, C.c_size_t])
 _sig("swg_db_pack", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(_vp)])
 _sig("swg_db_pack_shard", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(_vp)])
 _sig("swg_db_pack_shards", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.POINTER(_vp)])
@@ -153,6 +154,7 @@ _sig("swg_group_last_error", C.c_char_p, [_vp])
 _sig("swg_group_set_option", C.c_int, [_vp, C.c_char_p, C.c_long])
 _sig("swg_group_set_scoring", C.c_int, [_vp, _vp, C.c_int, C.c_int])
 _sig("swg_group_set_query", C.c_int, [_vp, _vp, C.c_size_t])
+_sig("swg_group_set_query_pssm", C.c_int, [_vp, _vp, C.c_size_t])
 _sig("swg_group_load", C.c_int, [_vp, _vp, _vp, C.c_size_t])
 _sig("swg_group_search", C.c_int, [_vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(Stats)])
 _sig("swg_letter_index", C.c_int, [C.c_int])
@@ -178,6 +180,9 @@ _sig("swg_synth_db_shard", C.c_int, [C.c_uint64, C.c_size_t, C.c_double, C.c_dou
                                      C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_size_t),
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)])
 _sig("swg_synth_free", None, [_vp])
+_sig("swg_pssm_load", C.c_int, [C.c_char_p, C.POINTER(Scoring), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_size_t),
+                                C.c_char_p, C.c_size_t])
+_sig("swg_pssm_free", None, [_vp, _vp])
 # test hook, declared in csrc/swg_host_internal.h (not part of the public ABI)
 _sig("swg_debug_fail_alloc", None, [C.c_int])
 _sig("swg_debug_sort_count", C.c_ulong, [])
@@ -198,6 +203,17 @@ def _check(rc, ctx=None):
 def _i8(a):
     a = np.ascontiguousarray(a, dtype=np.int8)
     return a, a.ctypes.data_as(_vp)
+
+
+def _pssm(pssm):
+    """(lq, 32) int8 PSSM -> (array, pointer, lq); values must already be int8."""
+    a = np.asarray(pssm)
+    if a.ndim != 2 or a.shape[1] != 32:
+        raise ValueError("a PSSM is an (lq, 32) array, got shape %s" % (a.shape,))
+    if a.dtype != np.int8 and a.size and (a.min() < -128 or a.max() > 127):
+        raise ValueError("PSSM values must fit int8")
+    p, pp = _i8(a)
+    return p, pp, a.shape[0]
 
 
 # ---------------------------------------------------------------------------
@@ -227,6 +243,23 @@ def load_scoring(name_or_path, gap_open=-2, gap_extend=-1):
         raise SwgError(rc, err.value.decode())
     sc.gap_open, sc.gap_extend = gap_open, gap_extend
     return sc
+
+
+def read_pssm(path, scoring):
+    """PSI-BLAST ASCII PSSM (swg_pssm_load) -> (pssm int8[lq, 32], query residue indices int8[lq]).  Residues the
+    file has no column for score as `scoring` (a Scoring) scores them against each position's residue."""
+    pp, qp, n = _vp(), _vp(), C.c_size_t(0)
+    err = C.create_string_buffer(512)
+    rc = lib.swg_pssm_load(path.encode(), C.byref(scoring), C.byref(pp), C.byref(qp), C.byref(n), err, 512)
+    if rc != SWG_OK:
+        raise SwgError(rc, err.value.decode())
+    try:
+        lq = n.value
+        pssm = np.ctypeslib.as_array(C.cast(pp, C.POINTER(C.c_int8)), shape=(lq * 32,)).reshape(lq, 32).copy()
+        query = np.ctypeslib.as_array(C.cast(qp, C.POINTER(C.c_int8)), shape=(lq,)).copy()
+    finally:
+        lib.swg_pssm_free(pp, qp)
+    return pssm, query
 
 
 def read_seqs(path, max_records=0):
@@ -490,6 +523,11 @@ class Context:
         q, qp = _i8(idx)
         _check(lib.swg_set_query(self.handle, qp, q.size), self.handle)
 
+    def set_query_pssm(self, pssm):
+        """A position-specific query: pssm int8[lq, 32], row i = query position i's scores by residue index."""
+        p, pp, lq = _pssm(pssm)
+        _check(lib.swg_set_query_pssm(self.handle, pp, lq), self.handle)
+
     def search(self, db, want_scores=True, k=0):
         """-> (scores int32[total] or None, hits [(score, index)], stats dict)."""
         scores = np.zeros(db.total_count, dtype=np.int32) if want_scores else None
@@ -637,6 +675,10 @@ class Group:
     def set_query(self, idx):
         q, qp = _i8(idx)
         self._chk(lib.swg_group_set_query(self.handle, qp, q.size))
+
+    def set_query_pssm(self, pssm):
+        p, pp, lq = _pssm(pssm)
+        self._chk(lib.swg_group_set_query_pssm(self.handle, pp, lq))
 
     def load(self, flat, offsets):
         f, fp = _i8(flat)

@@ -216,6 +216,7 @@ extern "C" void swg_destroy(swg_ctx *ctx)
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(ctx->d_sub);
     (void)hipFree(ctx->d_query);
+    (void)hipFree(ctx->d_pssm);
     (void)hipFree(ctx->d_profile[0]);
     (void)hipFree(ctx->d_profile[1]);
     (void)hipFree(ctx->d_profile[2]);
@@ -342,6 +343,30 @@ extern "C" int swg_set_scoring(swg_ctx *ctx, const int8_t sub[32][32], int gap_o
     return SWG_OK;
 }
 
+// Queues a copy of the query (index bytes or a PSSM) to dst on the context's stream.  No wait here: the copy and the
+// profile build that consumes it are ordered on the context's stream behind any search still in flight, so a caller
+// can stream queries against a resident database (set_query, search_begin, set_query, search_begin, search_end, ...).
+// The copy reads a pinned staging buffer of its own (four in rotation, each guarded by an event): the host copy
+// ctx->query / ctx->pssm is rewritten by the next call while this one's transfer may still be queued.
+static int stage_query(swg_ctx *ctx, int8_t *dst, const int8_t *src, size_t bytes)
+{
+    const int b = ctx->query_stage_next;
+    ctx->query_stage_next = (b + 1) % 4;
+    if (!ctx->ev_query_stage[b]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_query_stage[b], hipEventDisableTiming));
+    else HIP_TRY(ctx, hipEventSynchronize(ctx->ev_query_stage[b])); // (four transfers ago: long done)
+    if (bytes > ctx->h_query_stage_cap[b]) {
+        (void)hipHostFree(ctx->h_query_stage[b]);
+        ctx->h_query_stage[b] = nullptr;
+        ctx->h_query_stage_cap[b] = 0;
+        HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_query_stage[b]), bytes, hipHostMallocDefault));
+        ctx->h_query_stage_cap[b] = bytes;
+    }
+    memcpy(ctx->h_query_stage[b], src, bytes);
+    HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->h_query_stage[b], bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_query_stage[b], ctx->stream));
+    return SWG_OK;
+}
+
 extern "C" int swg_set_query(swg_ctx *ctx, const int8_t *idx, size_t lq)
 {
     if (!ctx || !idx || lq == 0)
@@ -359,28 +384,34 @@ extern "C" int swg_set_query(swg_ctx *ctx, const int8_t *idx, size_t lq)
         HIP_TRY(ctx, hipMalloc(&ctx->d_query, lq));
         ctx->d_query_cap = lq;
     }
-    // No wait here: the copy and the profile build that consumes it are ordered on the context's
-    // stream behind any search still in flight, so a caller can stream queries against a resident
-    // database (set_query, search_begin, set_query, search_begin, search_end, ...).  The copy reads a
-    // pinned staging buffer of its own (four in rotation, each guarded by an event): the host copy
-    // ctx->query is rewritten by the next call while this one's transfer may still be queued.
     ctx->query.assign(idx, idx + lq);
-    {
-        const int b = ctx->query_stage_next;
-        ctx->query_stage_next = (b + 1) % 4;
-        if (!ctx->ev_query_stage[b]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_query_stage[b], hipEventDisableTiming));
-        else HIP_TRY(ctx, hipEventSynchronize(ctx->ev_query_stage[b])); // (four transfers ago: long done)
-        if (lq > ctx->h_query_stage_cap[b]) {
-            (void)hipHostFree(ctx->h_query_stage[b]);
-            ctx->h_query_stage[b] = nullptr;
-            ctx->h_query_stage_cap[b] = 0;
-            HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_query_stage[b]), lq, hipHostMallocDefault));
-            ctx->h_query_stage_cap[b] = lq;
-        }
-        memcpy(ctx->h_query_stage[b], idx, lq);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_query, ctx->h_query_stage[b], lq, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_query_stage[b], ctx->stream));
+    ctx->pssm.clear();
+    ctx->query_pssm = false;
+    const int rc = stage_query(ctx, ctx->d_query, idx, lq);
+    if (rc != SWG_OK) return rc;
+    ctx->epoch = g_epoch.fetch_add(1) + 1;
+    return SWG_OK;
+}
+
+extern "C" int swg_set_query_pssm(swg_ctx *ctx, const int8_t *pssm, size_t lq)
+{
+    if (!ctx || !pssm || lq == 0)
+        return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_set_query_pssm: NULL or empty PSSM");
+    if (lq > (1u << 24)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_set_query_pssm: query too long");
+    const size_t bytes = lq * 32;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (bytes > ctx->d_pssm_cap) {
+        (void)hipFree(ctx->d_pssm);
+        ctx->d_pssm = nullptr;
+        ctx->d_pssm_cap = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->d_pssm, bytes));
+        ctx->d_pssm_cap = bytes;
     }
+    ctx->pssm.assign(pssm, pssm + bytes);
+    ctx->query.clear();
+    ctx->query_pssm = true;
+    const int rc = stage_query(ctx, ctx->d_pssm, pssm, bytes);
+    if (rc != SWG_OK) return rc;
     ctx->epoch = g_epoch.fetch_add(1) + 1;
     return SWG_OK;
 }
@@ -548,7 +579,7 @@ static int make_plan(swg_ctx *ctx, int bits, uint32_t n_items, Plan *pl)
     const SwgKernelInfo info = swg_variant_info(bits, variant);
     int maxw = info.max_waves;
     if (ctx->opt_max_waves > 0) maxw = std::min<int>(maxw, (int)ctx->opt_max_waves);
-    const size_t lq = ctx->query.size();
+    const size_t lq = ctx->query_len();
     const size_t cols_per_pass_max = (size_t)maxw * info.K;
     const int npass = (int)((lq + cols_per_pass_max - 1) / cols_per_pass_max);
     const int W = (int)((lq + (size_t)npass * info.K - 1) / ((size_t)npass * info.K));
@@ -588,13 +619,15 @@ static int ensure_profile_cols(swg_ctx *ctx, int which, uint32_t ncols, int elem
         HIP_TRY(ctx, hipMalloc(&ctx->d_profile[which], bytes));
         ctx->d_profile_cap[which] = bytes;
     }
-    HIP_TRY(ctx, swg_launch_build_profile(ctx->d_sub, ctx->d_query, (uint32_t)ctx->query.size(), ncols - tail_cols,
+    // (a PSSM query: the scores come from the PSSM's rows instead of the table's, every layout the same)
+    const int8_t *d_pssm = ctx->query_pssm ? ctx->d_pssm : nullptr;
+    HIP_TRY(ctx, swg_launch_build_profile(ctx->d_sub, ctx->d_query, (uint32_t)ctx->query_len(), ncols - tail_cols,
                                           elem_size, chunk_cols, k_real, k_padded, ctx->d_profile[which], ctx->stream,
-                                          swizzle_lanes, f16));
+                                          swizzle_lanes, f16, 0, d_pssm));
     if (tail_cols > 0)
-        HIP_TRY(ctx, swg_launch_build_profile(ctx->d_sub, ctx->d_query, (uint32_t)ctx->query.size(), tail_cols, elem_size, chunk_cols,
+        HIP_TRY(ctx, swg_launch_build_profile(ctx->d_sub, ctx->d_query, (uint32_t)ctx->query_len(), tail_cols, elem_size, chunk_cols,
                                               tail_k_real, tail_k_padded, ctx->d_profile[which] + (size_t)(ncols - tail_cols) * 32 * elem_size,
-                                              ctx->stream, swizzle_lanes, f16, tail_qcol0));
+                                              ctx->stream, swizzle_lanes, f16, tail_qcol0, d_pssm));
     ctx->profile_tag[which] = tag;
     return SWG_OK;
 }
@@ -1766,7 +1799,7 @@ static int search_begin(swg_ctx *ctx, const swg_db *db, bool want_scores, size_t
 {
     if (!ctx || !db) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_search: NULL argument");
     if (!ctx->have_scoring) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search: no scoring set");
-    if (ctx->query.empty()) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search: no query set");
+    if (ctx->query_len() == 0) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search: no query set");
     if (db->device != ctx->device || !db->d_codes)
         return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search: database is not resident on device %d",
                                  ctx->device);
@@ -1786,7 +1819,7 @@ static int search_begin(swg_ctx *ctx, const swg_db *db, bool want_scores, size_t
     S->want_scores = want_scores;
     swg_stats &st = S->st;
     memset(&st, 0, sizeof st);
-    const size_t lq = ctx->query.size();
+    const size_t lq = ctx->query_len();
     const uint32_t n_bins = db->n_bins;
     const size_t n_slots = (size_t)n_bins * SWG_BIN;
     st.cells = (uint64_t)lq * db->residues;
@@ -1806,15 +1839,25 @@ static int search_begin(swg_ctx *ctx, const swg_db *db, bool want_scores, size_t
     // How high can a score get?  Not above the query's best possible total (every column paired
     // with its best-scoring residue) nor above the longest sequence times the largest table entry.
     // Below 32767 nothing can saturate; below 65535 the wide form of the diagonal engine (values
-    // biased by -32768, same instruction count) is exact and nothing needs the int32 re-score.
+    // biased by -32768, same instruction count) is exact and nothing needs the int32 re-score.  A PSSM query
+    // bounds the same way by its own rows: its largest entry, and the sum of each position's best entry.
     int smax = 0;
     uint64_t qbound = 0;
-    for (int a = 0; a < 32; ++a)
-        for (int b = 0; b < 32; ++b) smax = std::max<int>(smax, ctx->sub[a][b]);
-    for (size_t i = 0; i < lq; ++i) {
-        int best = 0;
-        for (int b = 1; b < 32; ++b) best = std::max<int>(best, ctx->sub[(uint8_t)ctx->query[i] & 31][b]);
-        qbound += (uint64_t)best;
+    if (ctx->query_pssm) {
+        for (size_t i = 0; i < lq; ++i) {
+            int best = 0;
+            for (int b = 1; b < 32; ++b) best = std::max<int>(best, ctx->pssm[i * 32 + b]);
+            smax = std::max(smax, best);
+            qbound += (uint64_t)best;
+        }
+    } else {
+        for (int a = 0; a < 32; ++a)
+            for (int b = 0; b < 32; ++b) smax = std::max<int>(smax, ctx->sub[a][b]);
+        for (size_t i = 0; i < lq; ++i) {
+            int best = 0;
+            for (int b = 1; b < 32; ++b) best = std::max<int>(best, ctx->sub[(uint8_t)ctx->query[i] & 31][b]);
+            qbound += (uint64_t)best;
+        }
     }
     const uint64_t longest = (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK;
     const uint64_t score_bound = std::min<uint64_t>(qbound, std::min<uint64_t>(lq, longest) * (uint64_t)smax);
@@ -2641,8 +2684,9 @@ static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const int8_t *queri
         }
     }
     if (!fast) {
-        // one after another; the context's own query is put back afterwards
-        const std::vector<int8_t> keep = ctx->query;
+        // one after another; the context's own query is put back afterwards (a PSSM as a PSSM)
+        const bool keep_pssm = ctx->query_pssm;
+        const std::vector<int8_t> keep = keep_pssm ? ctx->pssm : ctx->query;
         int rc = SWG_OK;
         swg_stats one;
         for (size_t i = 0; i < n_queries && rc == SWG_OK; ++i) {
@@ -2669,7 +2713,7 @@ static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const int8_t *queri
             }
         }
         if (!keep.empty()) {
-            const int rq = swg_set_query(ctx, keep.data(), keep.size());
+            const int rq = keep_pssm ? swg_set_query_pssm(ctx, keep.data(), keep.size() / 32) : swg_set_query(ctx, keep.data(), keep.size());
             if (rc == SWG_OK) rc = rq;
         } else {
             ctx->query.clear();
@@ -2953,7 +2997,7 @@ static int fill_batches16_device(swg_ctx *ctx, const swg_batch16 *batches, size_
 {
     typedef std::chrono::steady_clock clk;
     const clk::time_point t0 = clk::now();
-    if (ctx->opt_engine == 1 || ctx->opt_dynamic == 0 || !ctx->have_scoring || ctx->query.empty()) return 1;
+    if (ctx->opt_engine == 1 || ctx->opt_dynamic == 0 || !ctx->have_scoring || ctx->query_len() == 0) return 1;
     for (const SwgSlot &sl : ctx->slots)
         if (sl.busy) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_fill_batches16: searches are in flight on this context");
     HIP_TRY(ctx, hipSetDevice(ctx->device));

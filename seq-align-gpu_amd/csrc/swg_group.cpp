@@ -167,6 +167,16 @@ extern "C" int swg_group_set_query(swg_group *g, const int8_t *idx, size_t lq)
     return SWG_OK;
 }
 
+extern "C" int swg_group_set_query_pssm(swg_group *g, const int8_t *pssm, size_t lq)
+{
+    if (!g) return swg_set_global_error(SWG_ERR_ARG, "swg_group_set_query_pssm: NULL group");
+    for (swg_ctx *c : g->ctx) {
+        const int rc = swg_set_query_pssm(c, pssm, lq);
+        if (rc != SWG_OK) return gerr(g, rc, swg_last_error(c));
+    }
+    return SWG_OK;
+}
+
 extern "C" int swg_group_load(swg_group *g, const int8_t *flat, const uint64_t *offsets, size_t n)
 {
     if (!g) return swg_set_global_error(SWG_ERR_ARG, "swg_group_load: NULL group");

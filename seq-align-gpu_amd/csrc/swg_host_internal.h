@@ -244,6 +244,12 @@ struct swg_ctx {
     size_t h_query_stage_cap[4] = {0, 0, 0, 0};
     hipEvent_t ev_query_stage[4] = {nullptr, nullptr, nullptr, nullptr};
     int query_stage_next = 0;
+    // a position-specific query (swg_set_query_pssm): pssm[i*32 + b] scores query position i against residue b.  While
+    // query_pssm is set it is the query (and `query` is empty); swg_set_query clears it again.
+    std::vector<int8_t> pssm;
+    bool query_pssm = false;
+    // query length of either form: what every lq of the planner, the profiles and the traceback is
+    size_t query_len() const { return query_pssm ? pssm.size() / 32 : query.size(); }
     // options
     long opt_force_bits = 0, opt_cols = 0, opt_max_waves = 0, opt_workgroups = 0, opt_engine = 0, opt_group = 0, opt_long_split = 0, opt_autotune = 1, opt_dynamic = 1, opt_prio_share = 150, opt_long_helps = 0, opt_wide = 1, opt_side_readout = 1, opt_f16 = 1, opt_qq = 1, opt_last_pass = 1, opt_f16_pair = 0;
     long opt_wave_budget = 0, opt_q32_waves = 0;
@@ -253,6 +259,8 @@ struct swg_ctx {
     int8_t *d_sub = nullptr;
     int8_t *d_query = nullptr;
     size_t d_query_cap = 0;
+    int8_t *d_pssm = nullptr; // [lq][32], the device copy of pssm
+    size_t d_pssm_cap = 0;
     // [0] int16, whole 4-column chunks per lane; [1] int32 (bin-based kernels); [2] / [3] int16 in per-lane
     // slices padded to whole chunks, long class / bulk; [4] / [5] int32 in 2-column chunks (work-queue
     // int32 kernel), bulk or list / long class

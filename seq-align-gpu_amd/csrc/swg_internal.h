@@ -217,7 +217,7 @@ hipError_t swg_launch_build_profiles_multi(const int8_t *d_sub, const int8_t *d_
 #define SWG_LDS_SWIZZLE 1
 #endif
 
-// profile[(col/4)*32*4 + code*4 + col%4] = sub[query[col]][code] (code 0 and
+// profile[(col/4)*32*4 + code*4 + col%4] = sub[query[col]][code] or pssm[col][code] (code 0 and
 // col >= lq: pad value).  elem_size 2 -> int16 pad -32768, 4 -> int32 pad -2^29.
 // chunk_cols: columns per chunk, [col/chunk][32][chunk] (4 everywhere except diagonal K % 4 == 2)
 // k_real / k_padded: a lane's slice of the diagonal engine is k_padded layout columns holding k_real
@@ -229,7 +229,8 @@ hipError_t swg_launch_build_profile(const int8_t *d_sub, const int8_t *d_query,
                                     int k_padded, uint8_t *d_profile, hipStream_t stream, int swizzle_lanes = 0,
                                     int f16 = 0, // f16: elem_size 2 entries are f16 numbers (pad -65504) for the packed-f16 cells;
                                                  // elem_size 4: (f16 score, 1.0) pairs for their fma pairing (chunk_cols 2)
-                                    uint32_t qcol0 = 0); // the query column layout column 0 stands for
+                                    uint32_t qcol0 = 0, // the query column layout column 0 stands for
+                                    const int8_t *d_pssm = nullptr); // a PSSM query ([lq][32]): scores from its rows, d_query unread
 int swg_diag_padded_cols(int K, bool fma = false); // layout columns of a lane's slice
 size_t swg_diag_slice_bytes(int K, int G, bool fma = false); // profile bytes of one pass: G lanes' slices
 

@@ -2115,7 +2115,9 @@ __global__ __launch_bounds__(MAXW * 64) void swg_diag_qq_kernel(const SwgDiagQQP
 // ---------------------------------------------------------------------------
 // small kernels
 // ---------------------------------------------------------------------------
-__global__ void swg_build_profile_kernel(const int8_t *sub, const int8_t *query, uint32_t lq,
+// pssm != nullptr: a position-specific query, the score of (query column, residue) is pssm[qcol*32 + code] instead of
+// sub[query[qcol]][code] (query is not read); every layout below is the same for both sources.
+__global__ void swg_build_profile_kernel(const int8_t *sub, const int8_t *query, const int8_t *pssm, uint32_t lq,
                                          uint32_t ncols, int elem_size, uint32_t ch, uint32_t k_real,
                                          uint32_t k_padded, uint32_t swizzle_lanes, int f16, uint32_t qcol0, uint8_t *out)
 {
@@ -2126,7 +2128,7 @@ __global__ void swg_build_profile_kernel(const int8_t *sub, const int8_t *query,
     // column of layout column 0 -- the last pass of a long query may have a geometry of its own)
     const uint32_t j = col % k_padded, qcol = qcol0 + (col / k_padded) * k_real + j;
     const bool pad = (j >= k_real) || (qcol >= lq) || (code == 0u);
-    const int v = pad ? 0 : (int)sub[(int)query[qcol] * 32 + (int)code];
+    const int v = pad ? 0 : pssm ? (int)pssm[(size_t)qcol * 32u + code] : (int)sub[(int)query[qcol] * 32 + (int)code];
     // row of this residue inside its chunk: the residue itself, or swizzled by the reading lane (SWG_LDS_SWIZZLE)
     const uint32_t row = swizzle_lanes ? code ^ (((col / k_padded) % swizzle_lanes) & 31u) : code;
     const size_t e = (size_t)(col / ch) * (32u * ch) + row * ch + (col % ch); // [col/ch][32][ch]
@@ -2909,12 +2911,13 @@ hipError_t swg_launch_fill(int bits, int variant, int W, int workgroups, const S
 
 hipError_t swg_launch_build_profile(const int8_t *d_sub, const int8_t *d_query, uint32_t lq,
                                     uint32_t ncols, int elem_size, int chunk_cols, int k_real, int k_padded,
-                                    uint8_t *d_profile, hipStream_t stream, int swizzle_lanes, int f16, uint32_t qcol0)
+                                    uint8_t *d_profile, hipStream_t stream, int swizzle_lanes, int f16, uint32_t qcol0,
+                                    const int8_t *d_pssm)
 {
     const uint32_t n = ncols * 32u;
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(swg_build_profile_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_sub,
-                       d_query, lq, ncols, elem_size, (uint32_t)chunk_cols, (uint32_t)k_real, (uint32_t)k_padded,
+                       d_query, d_pssm, lq, ncols, elem_size, (uint32_t)chunk_cols, (uint32_t)k_real, (uint32_t)k_padded,
                        (uint32_t)swizzle_lanes, f16, qcol0, d_profile);
     return hipGetLastError();
 }

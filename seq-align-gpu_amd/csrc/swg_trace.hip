@@ -32,6 +32,7 @@ struct SwgTraceOut {
 struct SwgTraceParams {
     const int8_t *query; // [lq] table indices
     const int8_t *sub;   // [32][32], row = query residue
+    const int8_t *pssm;  // PSSM kernel: [lq][32], row = query position (query and sub unread)
     const int8_t *res;   // database residue indices of the jobs, back to back
     const SwgTraceJob *jobs;
     int32_t *diag;       // per job 9 * (lq + 1): three rotating anti-diagonals of H, A and B
@@ -53,7 +54,9 @@ __device__ __forceinline__ uint32_t trace_pick(int32_t m, int32_t x, int32_t y)
 
 // IN_LDS: the nine rotating anti-diagonals live in the workgroup's LDS (queries up to
 // SWG_TRACE_LDS_COLS columns; one dependent sweep then waits for LDS, not for L2).
-template <bool IN_LDS>
+// PSSM: a position-specific query; a cell's score is read from row i-1 of the PSSM in global memory (32 * lq bytes,
+// more than LDS holds for a long query; a sweep reads consecutive rows, which stay in cache) instead of the table.
+template <bool IN_LDS, bool PSSM>
 __global__ __launch_bounds__(SWG_TRACE_THREADS) void swg_trace_kernel(SwgTraceParams p)
 {
     extern __shared__ int32_t s_diag[];
@@ -63,7 +66,8 @@ __global__ __launch_bounds__(SWG_TRACE_THREADS) void swg_trace_kernel(SwgTracePa
     __shared__ uint32_t s_n;
     const SwgTraceJob job = p.jobs[blockIdx.x];
     const uint32_t lq = p.lq, len = job.len, tid = threadIdx.x, w = lq + 1;
-    for (uint32_t k = tid; k < 1024; k += SWG_TRACE_THREADS) s_sub[k] = p.sub[k];
+    if (!PSSM)
+        for (uint32_t k = tid; k < 1024; k += SWG_TRACE_THREADS) s_sub[k] = p.sub[k];
     if (tid == 0) {
         s_best = 0;
         s_pos = ~0ull;
@@ -96,7 +100,8 @@ __global__ __launch_bounds__(SWG_TRACE_THREADS) void swg_trace_kernel(SwgTracePa
                 if (i > 1) hd = H2[i - 1], ad = A2[i - 1], bd = B2[i - 1];
             }
             if (i > 1) hl = H1[i - 1], al = A1[i - 1], bl = B1[i - 1];
-            const int32_t s = s_sub[(int)p.query[i - 1] * 32 + (int)d[j - 1]];
+            const int32_t s = PSSM ? (int32_t)p.pssm[(size_t)(i - 1) * 32 + (int)d[j - 1]]
+                                   : (int32_t)s_sub[(int)p.query[i - 1] * 32 + (int)d[j - 1]];
             const int32_t mh = max(max(hd, ad), max(bd, 0));
             const int32_t xa = hu + go, ya = au + ge, za = bu + go;
             const int32_t ma = max(max(xa, ya), max(za, 0));
@@ -163,7 +168,7 @@ extern "C" size_t swg_align_ops_bound(const swg_ctx *ctx, const swg_db *db)
     if (!ctx || !db) return 0;
     uint32_t longest = 0;
     for (uint32_t l : db->lens) longest = std::max(longest, l);
-    return ctx->query.size() + longest + 1;
+    return ctx->query_len() + longest + 1;
 }
 
 extern "C" int swg_align_hits(swg_ctx *ctx, const swg_db *db, const swg_hit *hits, size_t n_hits,
@@ -172,12 +177,13 @@ extern "C" int swg_align_hits(swg_ctx *ctx, const swg_db *db, const swg_hit *hit
     if (!ctx) return swg_set_global_error(SWG_ERR_ARG, "swg_align_hits: NULL context");
     if (!db || (n_hits && (!hits || !out)))
         return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_align_hits: NULL argument");
-    if (!ctx->have_scoring || ctx->query.empty())
+    if (!ctx->have_scoring || ctx->query_len() == 0)
         return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_align_hits: scoring and query must be set first");
     if (ops && ops_stride == 0) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_align_hits: ops_stride is 0");
     if (n_hits == 0) return SWG_OK;
     if (n_hits > (1u << 20)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_align_hits: more than 2^20 hits");
-    const size_t lq = ctx->query.size();
+    const size_t lq = ctx->query_len();
+    const bool pssm = ctx->query_pssm;
 
     // original index -> slot of the sorted order, for the wanted sequences only
     std::unordered_map<uint32_t, size_t> slot_of;
@@ -237,16 +243,21 @@ extern "C" int swg_align_hits(swg_ctx *ctx, const swg_db *db, const swg_hit *hit
         }
     }
     TRACE_TRY(ctx, hipSetDevice(ctx->device));
-    TRACE_TRY(ctx, hipMalloc(&d_query, lq));
-    TRACE_TRY(ctx, hipMalloc(&d_sub, 1024));
+    // the query's scores: index query + table, or the PSSM (then d_sub holds it and d_query is not needed)
+    TRACE_TRY(ctx, hipMalloc(&d_query, pssm ? 4 : lq));
+    TRACE_TRY(ctx, hipMalloc(&d_sub, pssm ? lq * 32 : 1024));
     TRACE_TRY(ctx, hipMalloc(&d_res, std::max<size_t>(res.size(), 4)));
     TRACE_TRY(ctx, hipMalloc(&d_jobs, n_hits * sizeof(SwgTraceJob)));
     TRACE_TRY(ctx, hipMalloc(&d_diag, in_lds ? 16 : max_chunk * 9 * (lq + 1) * sizeof(int32_t)));
     TRACE_TRY(ctx, hipMalloc(&d_dir, std::max<size_t>(max_dir, 4)));
     TRACE_TRY(ctx, hipMalloc(&d_ops, max_chunk * dev_stride));
     TRACE_TRY(ctx, hipMalloc(&d_out, n_hits * sizeof(SwgTraceOut)));
-    TRACE_TRY(ctx, hipMemcpyAsync(d_query, ctx->query.data(), lq, hipMemcpyHostToDevice, ctx->stream));
-    TRACE_TRY(ctx, hipMemcpyAsync(d_sub, &ctx->sub[0][0], 1024, hipMemcpyHostToDevice, ctx->stream));
+    if (pssm) {
+        TRACE_TRY(ctx, hipMemcpyAsync(d_sub, ctx->pssm.data(), lq * 32, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        TRACE_TRY(ctx, hipMemcpyAsync(d_query, ctx->query.data(), lq, hipMemcpyHostToDevice, ctx->stream));
+        TRACE_TRY(ctx, hipMemcpyAsync(d_sub, &ctx->sub[0][0], 1024, hipMemcpyHostToDevice, ctx->stream));
+    }
     TRACE_TRY(ctx, hipMemcpyAsync(d_res, res.data(), res.size(), hipMemcpyHostToDevice, ctx->stream));
     if (ops) h_ops.resize(max_chunk * dev_stride);
     for (size_t b = 0; b < n_hits;) {
@@ -263,14 +274,19 @@ extern "C" int swg_align_hits(swg_ctx *ctx, const swg_db *db, const swg_hit *hit
         TRACE_TRY(ctx, hipMemcpyAsync(d_jobs + b, jobs.data() + b, nb * sizeof(SwgTraceJob), hipMemcpyHostToDevice,
                                       ctx->stream));
         SwgTraceParams p;
-        p.query = d_query, p.sub = d_sub, p.res = d_res, p.jobs = d_jobs + b, p.diag = d_diag, p.dir = d_dir;
+        p.query = d_query, p.sub = d_sub, p.pssm = pssm ? d_sub : nullptr, p.res = d_res, p.jobs = d_jobs + b, p.diag = d_diag, p.dir = d_dir;
         p.ops = d_ops, p.out = d_out + b, p.lq = (uint32_t)lq, p.ops_stride = (uint32_t)dev_stride;
         p.go = ctx->gap_open + ctx->gap_extend, p.ge = ctx->gap_extend; // src/alignment.c:58-59
-        if (in_lds)
-            hipLaunchKernelGGL(swg_trace_kernel<true>, dim3((unsigned)nb), dim3(SWG_TRACE_THREADS),
+        if (in_lds && !pssm)
+            hipLaunchKernelGGL((swg_trace_kernel<true, false>), dim3((unsigned)nb), dim3(SWG_TRACE_THREADS),
+                               9 * (lq + 1) * sizeof(int32_t), ctx->stream, p);
+        else if (!pssm)
+            hipLaunchKernelGGL((swg_trace_kernel<false, false>), dim3((unsigned)nb), dim3(SWG_TRACE_THREADS), 0, ctx->stream, p);
+        else if (in_lds)
+            hipLaunchKernelGGL((swg_trace_kernel<true, true>), dim3((unsigned)nb), dim3(SWG_TRACE_THREADS),
                                9 * (lq + 1) * sizeof(int32_t), ctx->stream, p);
         else
-            hipLaunchKernelGGL(swg_trace_kernel<false>, dim3((unsigned)nb), dim3(SWG_TRACE_THREADS), 0, ctx->stream, p);
+            hipLaunchKernelGGL((swg_trace_kernel<false, true>), dim3((unsigned)nb), dim3(SWG_TRACE_THREADS), 0, ctx->stream, p);
         TRACE_TRY(ctx, hipGetLastError());
         TRACE_TRY(ctx, hipMemcpyAsync(h_out.data() + b, d_out + b, nb * sizeof(SwgTraceOut), hipMemcpyDeviceToHost,
                                       ctx->stream));

@@ -13,7 +13,9 @@
  *   - --topk K appends a ranked report, --align the alignments of those K (the traceback the
  *     reference's fork removed, re-run for the reported pairs only: swg_align_hits);
  *     --gpu N selects the device; --gpus N shards the database over devices 0..N-1 (one RCCL
- *     all-reduce merges the top-K lists).
+ *     all-reduce merges the top-K lists); --pssm F scores the query by a PSI-BLAST ASCII PSSM
+ *     (swg_pssm_load, swg_set_query_pssm) instead of the matrix (the matrix still fills the PSSM's
+ *     unnamed columns).
  * There is no CPU backend: without a GPU the tool fails with a message.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -41,6 +43,7 @@ static void usage(const char *argv0, const char *err)
             "  record of a database (FASTA/FASTQ/plain, gzip ok), on an AMD MI355X.\n\n"
             "  OPTIONS:\n"
             "    --files <f1> <f2>    query file (first record) and database file\n"
+            "    --pssm <file>        score the query by this PSI-BLAST ASCII PSSM (-out_ascii_pssm; its residues must be the query's)\n"
             "    --substitution_matrix <file>  scoring matrix (see data/*.txt)\n"
             "    --gapopen <score>    [default: -2]\n"
             "    --gapextend <score>  [default: -1]   gap of length N costs open + N*extend\n"
@@ -155,7 +158,7 @@ int main(int argc, char **argv)
 {
     swg_scoring sc;
     swg_scoring_init(&sc);
-    const char *qpath = NULL, *dbpath = NULL, *savedb = NULL;
+    const char *qpath = NULL, *dbpath = NULL, *savedb = NULL, *pssm_path = NULL;
     int print_seq = 0, print_fasta = 0, have_matrix = 0, packed = 0, allq = 0;
     long topk = 0, gpu = 0, gpus = 0, v;
     int align = 0;
@@ -207,6 +210,8 @@ int main(int argc, char **argv)
         } else if (!strcasecmp(a, "--topk")) {
             if (!parse_int(argv[i + 1], 0, 1 << 20, &topk)) usage(argv[0], "Invalid --topk argument");
             i++;
+        } else if (!strcasecmp(a, "--pssm")) {
+            pssm_path = argv[++i];
         } else if (!strcasecmp(a, "--savedb")) {
             if (i >= argc - 1) usage(argv[0], "--savedb takes a file name");
             savedb = argv[++i];
@@ -239,6 +244,7 @@ int main(int argc, char **argv)
     if (packed && (print_seq || print_fasta)) usage(argv[0], "--printseq/--printfasta need the FASTA database, not --packed");
     if ((packed || savedb || allq) && gpus > 0) usage(argv[0], "--packed/--savedb/--allqueries work with one GPU (--gpu)");
     if (align && topk == 0) usage(argv[0], "--align reports the alignments of the --topk hits: give --topk K");
+    if (pssm_path && allq) usage(argv[0], "--pssm scores one query: it does not combine with --allqueries");
 
     char err[512];
     swg_seqs q, db;
@@ -285,6 +291,24 @@ int main(int argc, char **argv)
         q1.n = 1;
         if (swg_seqs_to_indices(&q1, qidx, &bad) != SWG_OK) die_illegal(bad);
     }
+    /* --pssm: the PSSM's residue column must spell the query record (case aside) */
+    int8_t *pssm = NULL;
+    if (pssm_path) {
+        int8_t *pq = NULL;
+        size_t plq = 0;
+        if (swg_pssm_load(pssm_path, &sc, &pssm, &pq, &plq, err, sizeof err) != SWG_OK) {
+            fprintf(stderr, "Error: %s\n", err);
+            return leave(EXIT_FAILURE);
+        }
+        size_t at = 0;
+        while (at < lq && at < plq && pq[at] == qidx[at]) at++;
+        swg_pssm_free(NULL, pq);
+        if (at < lq || plq != lq) {
+            fprintf(stderr, "Error: the PSSM %s (%lu positions) does not spell the query (%lu residues): they differ at position %lu\n",
+                    pssm_path, (unsigned long)plq, (unsigned long)lq, (unsigned long)at + 1);
+            return leave(EXIT_FAILURE);
+        }
+    }
     swg_query_sanitize(&sc, qidx, lq); /* reference src/alignment_cmdline.c:391-396 */
     if (!packed && swg_seqs_to_indices(&db, didx, &bad) != SWG_OK) die_illegal(bad);
 
@@ -312,7 +336,7 @@ int main(int argc, char **argv)
         /* one search per query length: timing candidate geometries first would cost more than it saves */
         rc = swg_group_set_option(grp, "autotune", 0);
         if (rc == SWG_OK) rc = swg_group_set_scoring(grp, (const int8_t(*)[32])sc.sub, sc.gap_open, sc.gap_extend);
-        if (rc == SWG_OK) rc = swg_group_set_query(grp, qidx, lq);
+        if (rc == SWG_OK) rc = pssm ? swg_group_set_query_pssm(grp, pssm, lq) : swg_group_set_query(grp, qidx, lq);
         if (rc == SWG_OK) rc = swg_group_load(grp, didx, db.seq_off, db.n);
         phase("pack, shard and upload");
         if (rc == SWG_OK) rc = swg_group_search(grp, scores, hits, (size_t)topk, &n_hits, st);
@@ -348,7 +372,7 @@ int main(int argc, char **argv)
         /* one search per query length: timing candidate geometries first would cost more than it saves */
         if (rc == SWG_OK) rc = swg_set_option(ctx, "autotune", 0);
         if (rc == SWG_OK) rc = swg_set_scoring(ctx, (const int8_t(*)[32])sc.sub, sc.gap_open, sc.gap_extend);
-        if (rc == SWG_OK) rc = swg_set_query(ctx, qidx, lq);
+        if (rc == SWG_OK) rc = pssm ? swg_set_query_pssm(ctx, pssm, lq) : swg_set_query(ctx, qidx, lq);
         if (rc == SWG_OK && savedb) {
             if (swg_db_save(pdb, savedb) != SWG_OK) {
                 fprintf(stderr, "Error: %s\n", swg_global_error());
@@ -519,6 +543,7 @@ next_query:
     swg_seqs_free(&q);
     swg_seqs_free(&db);
     free(qidx);
+    swg_pssm_free(pssm, NULL);
     free(didx);
     free(scores);
     free(hits);

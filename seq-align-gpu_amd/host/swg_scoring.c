@@ -232,3 +232,144 @@ done:
     free(lb.buf);
     return rc;
 }
+
+/* ---- PSI-BLAST ASCII PSSM (psiblast -out_ascii_pssm) ---------------------- */
+static int pssm_fail(char *err, size_t errlen, const char *path, long line, const char *msg)
+{
+    if (err && errlen) {
+        if (line >= 0)
+            snprintf(err, errlen, "PSSM : %s (file %s, line %ld)", msg, path, line);
+        else
+            snprintf(err, errlen, "PSSM : %s (file %s)", msg, path);
+    }
+    return SWG_ERR_IO;
+}
+
+/* splits s in place into at most max whitespace-separated tokens; returns how many */
+static int split_ws(char *s, char **tok, int max)
+{
+    int n = 0;
+    while (*s && n < max) {
+        while (*s && isspace((unsigned char)*s)) s++;
+        if (!*s) break;
+        tok[n++] = s;
+        while (*s && !isspace((unsigned char)*s)) s++;
+        if (*s) *s++ = '\0';
+    }
+    return n;
+}
+
+/* a whole token as a decimal integer */
+static int token_long(const char *t, long *v)
+{
+    char *end = NULL;
+    *v = strtol(t, &end, 10);
+    return end != t && *end == '\0';
+}
+
+int swg_pssm_load(const char *path, const swg_scoring *sc, int8_t **pssm_out, int8_t **query_out, size_t *lq_out,
+                  char *err, size_t errlen)
+{
+    if (!path || !sc || !pssm_out || !query_out || !lq_out) return SWG_ERR_ARG;
+    *pssm_out = NULL;
+    *query_out = NULL;
+    *lq_out = 0;
+    linebuf lb = {0};
+    lb.f = gzopen(path, "r");
+    if (!lb.f) return pssm_fail(err, errlen, path, -1, "couldn't read file");
+    int rc = SWG_OK, got;
+    long line = 0;
+    int cols[20]; /* residue code of each score column */
+    int have_header = 0;
+    int8_t *pssm = NULL, *query = NULL;
+    size_t lq = 0, cap = 0;
+    char *tok[22];
+    /* header: the first line whose first 20 tokens are single residue letters (the free text before it is skipped) */
+    while (!have_header && (got = lb_next(&lb)) > 0) {
+        line++;
+        const int n = split_ws(lb.buf, tok, 20);
+        if (n < 20) continue;
+        int ok = 1;
+        for (int c = 0; c < 20 && ok; c++) {
+            ok = tok[c][1] == '\0' && isalpha((unsigned char)tok[c][0]);
+            if (ok) cols[c] = swg_letter_index(tok[c][0]);
+        }
+        have_header = ok;
+    }
+    if (!have_header) {
+        rc = pssm_fail(err, errlen, path, -1, "no header line (20 single-letter column headings)");
+        goto done;
+    }
+    /* one line per position up to the first blank line: pos letter s1 .. s20 [anything] */
+    while ((got = lb_next(&lb)) > 0) {
+        line++;
+        if (all_space(lb.buf)) break;
+        const int n = split_ws(lb.buf, tok, 22);
+        long v;
+        if (n < 22) {
+            rc = pssm_fail(err, errlen, path, line, "expected a position, a residue letter and 20 scores");
+            goto done;
+        }
+        if (!token_long(tok[0], &v) || v != (long)lq + 1) {
+            rc = pssm_fail(err, errlen, path, line, "positions must be 1, 2, 3, ... without a gap");
+            goto done;
+        }
+        const int q = tok[1][1] == '\0' ? swg_letter_index(tok[1][0]) : -1;
+        if (q < 0) {
+            rc = pssm_fail(err, errlen, path, line, "illegal residue letter");
+            goto done;
+        }
+        if (lq == cap) {
+            const size_t ncap = cap ? cap * 2 : 256;
+            int8_t *np = (int8_t *)realloc(pssm, ncap * 32), *nq;
+            if (np) pssm = np;
+            nq = np ? (int8_t *)realloc(query, ncap) : NULL;
+            if (!np || !nq) {
+                rc = pssm_fail(err, errlen, path, line, "out of memory");
+                goto done;
+            }
+            query = nq;
+            cap = ncap;
+        }
+        int8_t *row = pssm + lq * 32;
+        /* residues the file has no column for score as the matrix scores them against this position's residue */
+        row[0] = 0;
+        for (int b = 1; b < 32; b++) row[b] = sc->sub[q][b];
+        for (int c = 0; c < 20; c++) {
+            if (!token_long(tok[2 + c], &v)) {
+                rc = pssm_fail(err, errlen, path, line, "missing or malformed score");
+                goto done;
+            }
+            if (v < -128 || v > 127) {
+                rc = pssm_fail(err, errlen, path, line, "score outside -128..127");
+                goto done;
+            }
+            row[cols[c]] = (int8_t)v;
+        }
+        query[lq++] = (int8_t)q;
+    }
+    if (got < 0) {
+        rc = pssm_fail(err, errlen, path, line, "out of memory");
+        goto done;
+    }
+    if (lq == 0) {
+        rc = pssm_fail(err, errlen, path, line, "no positions after the header");
+        goto done;
+    }
+    *pssm_out = pssm;
+    *query_out = query;
+    *lq_out = lq;
+    pssm = query = NULL;
+done:
+    free(pssm);
+    free(query);
+    gzclose(lb.f);
+    free(lb.buf);
+    return rc;
+}
+
+void swg_pssm_free(int8_t *pssm, int8_t *query)
+{
+    free(pssm);
+    free(query);
+}
