@@ -176,7 +176,8 @@ int swg_set_query(swg_ctx *ctx, const int8_t *idx, size_t lq);
  * copies the lq*32 bytes; like swg_set_query the copy is queued behind the searches in flight (no wait), so PSSMs
  * and index queries can be streamed between swg_search_begin calls.  Every query-dependent call follows the PSSM:
  * swg_search, swg_search_begin/end, swg_fill_batches16, swg_align_hits, swg_align_ops_bound (swg_search_multi
- * takes index queries of its own and leaves the PSSM in place).  A PSSM search has the plan an index query of the
+ * takes index queries of its own and leaves the PSSM in place; swg_search_multi_pssm runs a batch of PSSMs in one
+ * pass the same way).  A PSSM search has the plan an index query of the
  * same scores would have, so the same fill kernels at the same speed; its score bound (which decides the cells
  * and the re-score) is the sum of each position's best entry over residues 1..31. */
 int swg_set_query_pssm(swg_ctx *ctx, const int8_t *pssm, size_t lq);
@@ -258,6 +259,14 @@ int swg_search_end(swg_ctx *ctx, int ticket, int32_t *scores_out, swg_hit *topk_
 int swg_search_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets,
                      size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
                      swg_stats *stats);
+
+/* Many position-specific queries against one resident database in ONE pass: swg_search_multi with PSSMs.
+ * PSSM i is pssms[(q_offsets[i] + p)*32 + b] for p < q_offsets[i+1] - q_offsets[i] (offsets count POSITIONS,
+ * not bytes; column 0 ignored; any int8 accepted).  Gap scores are the context's; the context's own query
+ * (index or PSSM) is left as it was.  Outputs, batching, fall-backs and stats as swg_search_multi. */
+int swg_search_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets,
+                          size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
+                          swg_stats *stats);
 
 /* Reference-shaped replay of the call site itself: n_batches 16-lane batches
  * exactly as `alignment_fill_matrices` receives them -- db_idx_t is

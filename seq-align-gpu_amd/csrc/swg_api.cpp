@@ -2584,7 +2584,15 @@ static void multi_deliver(const swg_db *db, const int32_t *h_scores, size_t n_sl
     }
 }
 
-static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets,
+// The queries of a batch: index bytes (one per position), or PSSM rows (32 bytes per position); q_offsets count
+// positions either way.
+struct MultiQueries {
+    const int8_t *src;
+    bool pssm;
+    const char *fn; // the entry point, for messages
+};
+
+static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const MultiQueries &mq, const uint64_t *q_offsets,
                              size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
                              swg_stats *stats);
 
@@ -2593,7 +2601,8 @@ extern "C" int swg_search_multi(swg_ctx *ctx, const swg_db *db, const int8_t *qu
                                 swg_stats *stats)
 {
     try { // no C++ exception crosses the ABI (the body sizes host vectors by the batch)
-        return search_multi_impl(ctx, db, queries, q_offsets, n_queries, scores_out, topk_out, k, n_hits, stats);
+        return search_multi_impl(ctx, db, MultiQueries{queries, false, "swg_search_multi"}, q_offsets, n_queries, scores_out,
+                                 topk_out, k, n_hits, stats);
     } catch (const std::bad_alloc &) {
         return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "swg_search_multi: out of host memory");
     } catch (const std::exception &e) {
@@ -2601,30 +2610,47 @@ extern "C" int swg_search_multi(swg_ctx *ctx, const swg_db *db, const int8_t *qu
     }
 }
 
-static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets,
+extern "C" int swg_search_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets,
+                                     size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
+                                     swg_stats *stats)
+{
+    try {
+        return search_multi_impl(ctx, db, MultiQueries{pssms, true, "swg_search_multi_pssm"}, q_offsets, n_queries, scores_out,
+                                 topk_out, k, n_hits, stats);
+    } catch (const std::bad_alloc &) {
+        return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "swg_search_multi_pssm: out of host memory");
+    } catch (const std::exception &e) {
+        return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "swg_search_multi_pssm: %s", e.what());
+    }
+}
+
+static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const MultiQueries &mq, const uint64_t *q_offsets,
                              size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
                              swg_stats *stats)
 {
+    const char *fn = mq.fn;
+    const int8_t *queries = mq.src;
+    const size_t row_bytes = mq.pssm ? 32 : 1; // bytes per query position
     if (!ctx || !db || (n_queries && (!queries || !q_offsets)))
-        return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_search_multi: NULL argument");
-    if (k > 0 && !topk_out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_search_multi: k > 0 but topk_out NULL");
-    if (!ctx->have_scoring) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search_multi: no scoring set");
+        return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: NULL argument", fn);
+    if (k > 0 && !topk_out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: k > 0 but topk_out NULL", fn);
+    if (!ctx->have_scoring) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: no scoring set", fn);
     if (db->device != ctx->device || !db->d_codes)
-        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search_multi: database is not resident on device %d", ctx->device);
+        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: database is not resident on device %d", fn, ctx->device);
     for (const SwgSlot &sl : ctx->slots)
-        if (sl.busy) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search_multi: searches are in flight on this context");
+        if (sl.busy) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: searches are in flight on this context", fn);
     swg_stats st;
     memset(&st, 0, sizeof st);
     size_t lq_max = 0;
     for (size_t i = 0; i < n_queries; ++i) {
         if (q_offsets[i + 1] <= q_offsets[i])
-            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_search_multi: query %zu is empty or the offsets are not increasing", i);
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: query %zu is empty or the offsets are not increasing", fn, i);
         const size_t lq = (size_t)(q_offsets[i + 1] - q_offsets[i]);
-        if (lq > (1u << 24)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_search_multi: query %zu too long", i);
+        if (lq > (1u << 24)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: query %zu too long", fn, i);
         lq_max = std::max(lq_max, lq);
-        for (uint64_t j = q_offsets[i]; j < q_offsets[i + 1]; ++j)
+        for (uint64_t j = q_offsets[i]; j < q_offsets[i + 1] && !mq.pssm; ++j) // (a PSSM takes any int8)
             if (queries[j] < 1 || queries[j] > 31)
-                return swg_set_ctx_error(ctx, SWG_ERR_RESIDUE, "swg_search_multi: residue index %d in query %zu outside 1..31",
+                return swg_set_ctx_error(ctx, SWG_ERR_RESIDUE, "%s: residue index %d in query %zu outside 1..31", fn,
                                          queries[j], i);
         st.cells += (uint64_t)lq * db->residues;
         st.bytes_alg += db->residues + 8ull * db->n_local + 32ull * lq + 1024ull;
@@ -2644,17 +2670,22 @@ static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const int8_t *queri
     const size_t Qb_max = 256; // queries per launch
     uint64_t bound_max = 0;    // the largest score any query of the batch can reach
     if (fast) {
-        // no score of any query may reach the int16 ceiling (the batch path has no re-score)
+        // no score of any query may reach the int16 ceiling (the batch path has no re-score).  A PSSM bounds by its
+        // own rows, as a single PSSM search does: its largest entry, and the sum of each position's best entry.
         int smax = 0;
-        for (int a = 0; a < 32; ++a)
-            for (int b = 0; b < 32; ++b) smax = std::max<int>(smax, ctx->sub[a][b]);
+        if (!mq.pssm)
+            for (int a = 0; a < 32; ++a)
+                for (int b = 0; b < 32; ++b) smax = std::max<int>(smax, ctx->sub[a][b]);
         const uint64_t longest = (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK;
         for (size_t i = 0; i < n_queries && fast; ++i) {
             uint64_t qbound = 0;
             const uint64_t lq = q_offsets[i + 1] - q_offsets[i];
+            if (mq.pssm) smax = 0;
             for (uint64_t j = q_offsets[i]; j < q_offsets[i + 1]; ++j) {
+                const int8_t *row = mq.pssm ? queries + j * 32 : ctx->sub[(uint8_t)queries[j] & 31];
                 int best = 0;
-                for (int b = 1; b < 32; ++b) best = std::max<int>(best, ctx->sub[(uint8_t)queries[j] & 31][b]);
+                for (int b = 1; b < 32; ++b) best = std::max<int>(best, row[b]);
+                if (mq.pssm) smax = std::max(smax, best);
                 qbound += (uint64_t)best;
             }
             const uint64_t bound = std::min<uint64_t>(qbound, std::min<uint64_t>(lq, longest) * (uint64_t)smax);
@@ -2690,7 +2721,8 @@ static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const int8_t *queri
         int rc = SWG_OK;
         swg_stats one;
         for (size_t i = 0; i < n_queries && rc == SWG_OK; ++i) {
-            rc = swg_set_query(ctx, queries + q_offsets[i], (size_t)(q_offsets[i + 1] - q_offsets[i]));
+            const size_t lq = (size_t)(q_offsets[i + 1] - q_offsets[i]);
+            rc = mq.pssm ? swg_set_query_pssm(ctx, queries + q_offsets[i] * 32, lq) : swg_set_query(ctx, queries + q_offsets[i], lq);
             if (rc == SWG_OK)
                 rc = swg_search(ctx, db, scores_out ? scores_out + i * n_total : nullptr, topk_out ? topk_out + i * k : nullptr, k,
                                 n_hits ? n_hits + i : nullptr, &one);
@@ -2765,7 +2797,7 @@ static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const int8_t *queri
     for (size_t q0 = 0; q0 < n_queries; q0 += Qb_max) {
         const size_t Qb = std::min(Qb_max, n_queries - q0);
         const size_t Qrows = qq ? (Qb + 1) / 2 : Qb; // rows of the grid: query pairs, or queries
-        const uint64_t qbytes = q_offsets[q0 + Qb] - q_offsets[q0];
+        const uint64_t qbytes = (q_offsets[q0 + Qb] - q_offsets[q0]) * row_bytes;
         try {
             qoff32.resize(Qb + 1);
             if (!dev_topk) h_scores.resize(Qb * n_slots);
@@ -2774,7 +2806,7 @@ static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const int8_t *queri
                 h_cand.resize(Qb * (size_t)SWG_TOPK_MULTI_CAP);
             }
         } catch (const std::exception &) {
-            return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "swg_search_multi: out of host memory");
+            return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "%s: out of host memory", fn);
         }
         for (size_t i = 0; i <= Qb; ++i) qoff32[i] = (uint32_t)(q_offsets[q0 + i] - q_offsets[q0]);
         // qq: queries of similar length share a lane (row r of the score buffer belongs to query order[r] of this chunk)
@@ -2818,23 +2850,25 @@ static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const int8_t *queri
         (void)hipFree(B.d_q);
         B.d_q = nullptr;
         HIP_TRY(ctx, hipMalloc(&B.d_q, std::max<uint64_t>(4, qbytes)));
-        HIP_TRY(ctx, hipMemcpyAsync(B.d_q, queries + q_offsets[q0], qbytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(B.d_q, queries + q_offsets[q0] * row_bytes, qbytes, hipMemcpyHostToDevice, s));
         HIP_TRY(ctx, hipMemcpyAsync(B.d_qoff, qoff32.data(), (Qb + 1) * 4, hipMemcpyHostToDevice, s));
         order.push_back(order.back()); // (qq, odd batch: the last pair's absent partner is its query once more)
         HIP_TRY(ctx, hipMemcpyAsync(B.d_order, order.data(), (Qb + 1) * 4, hipMemcpyHostToDevice, s));
         order.pop_back();
         HIP_TRY(ctx, hipMemsetAsync(B.d_scores, 0, (qq ? 2 * Qrows : Qb) * n_slots * 4, s));
         HIP_TRY(ctx, hipMemsetAsync(B.d_cnt, 0, (Qb_max * 2 * cnt_class + 2 * SWG_DYN_SIMD_SLOTS) * 4, s));
+        const int8_t *d_idx = mq.pssm ? nullptr : B.d_q, *d_pssms = mq.pssm ? B.d_q : nullptr; // (the builders' two sources)
         for (int c = 0; c < wk.n_classes; ++c) {
             const SwgDiagPlan &pl = wk.plan[c];
             if (qq)
-                HIP_TRY(ctx, swg_launch_build_profiles_qq(ctx->d_sub, B.d_q, B.d_qoff, B.d_order, (uint32_t)Qb,
+                HIP_TRY(ctx, swg_launch_build_profiles_qq(ctx->d_sub, d_idx, B.d_qoff, B.d_order, (uint32_t)Qb,
                                                           (uint32_t)(pl.G * swg_q32_padded_cols(pl.K)), pl.K, swg_q32_padded_cols(pl.K),
-                                                          B.d_prof[c], s, SWG_LDS_SWIZZLE ? pl.G : 0));
+                                                          B.d_prof[c], s, SWG_LDS_SWIZZLE ? pl.G : 0, d_pssms));
             else
-                HIP_TRY(ctx, swg_launch_build_profiles_multi(ctx->d_sub, B.d_q, B.d_qoff, (uint32_t)Qb,
+                HIP_TRY(ctx, swg_launch_build_profiles_multi(ctx->d_sub, d_idx, B.d_qoff, (uint32_t)Qb,
                                                              (uint32_t)(pl.G * swg_diag_padded_cols(pl.K)), pl.K,
-                                                             swg_diag_padded_cols(pl.K), B.d_prof[c], s, SWG_LDS_SWIZZLE ? pl.G : 0, form == 2));
+                                                             swg_diag_padded_cols(pl.K), B.d_prof[c], s, SWG_LDS_SWIZZLE ? pl.G : 0, form == 2,
+                                                             d_pssms));
         }
         // workgroups per query: the chip's resident workgroups shared out over the batch
         int wgs[2] = {1, 1};

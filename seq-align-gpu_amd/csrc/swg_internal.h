@@ -158,10 +158,11 @@ struct SwgDiagQQParams {
 };
 hipError_t swg_launch_diag_qq(int variant, int W, int workgroups, int n_pairs, const SwgDiagQQParams &p, hipStream_t stream);
 // profiles of the query pairs (order[2y], order[2y+1]) of a batch: pair y's profile of ncols layout columns goes to
-// d_profiles + y * ncols * 32 * 4
+// d_profiles + y * ncols * 32 * 4.  d_pssms: a batch of PSSMs (query i = rows q_off[i] .. q_off[i+1] of [..][32]),
+// d_queries unread
 hipError_t swg_launch_build_profiles_qq(const int8_t *d_sub, const int8_t *d_queries, const uint32_t *d_q_off, const uint32_t *d_order,
                                         uint32_t n_queries, uint32_t ncols, int k_real, int k_padded, uint8_t *d_profiles,
-                                        hipStream_t stream, int swizzle_lanes = 0);
+                                        hipStream_t stream, int swizzle_lanes = 0, const int8_t *d_pssms = nullptr);
 int swg_q32_padded_cols(int K);
 size_t swg_diag32q_lds_bytes(int K, int G, int W);
 // variant: index into the diagonal variants (swg_diag_variant_info gives its K)
@@ -204,10 +205,12 @@ size_t swg_diag_dyn_lds_bytes(int K, int G, int W, bool fma = false);
 hipError_t swg_launch_diag_dyn(int variant, bool edges, int form, int W, int workgroups, const SwgDiagDynParams &p,
                                hipStream_t stream, int n_queries = 1, bool fma = false);
 // profiles of n_queries queries (query i = queries[q_off[i] .. q_off[i+1])) in one launch: query i's
-// profile of ncols layout columns goes to d_profiles + i * ncols * 32 * 2 (int16)
+// profile of ncols layout columns goes to d_profiles + i * ncols * 32 * 2 (int16).  d_pssms: a batch of PSSMs
+// (query i = rows q_off[i] .. q_off[i+1] of [..][32]), d_queries unread
 hipError_t swg_launch_build_profiles_multi(const int8_t *d_sub, const int8_t *d_queries, const uint32_t *d_q_off,
                                            uint32_t n_queries, uint32_t ncols, int k_real, int k_padded,
-                                           uint8_t *d_profiles, hipStream_t stream, int swizzle_lanes = 0, int f16 = 0);
+                                           uint8_t *d_profiles, hipStream_t stream, int swizzle_lanes = 0, int f16 = 0,
+                                           const int8_t *d_pssms = nullptr);
 
 // LDS bank swizzle of the lane-group kernels' profile (1 = on): lane g of a group keeps the row of residue r
 // of each of its chunks at position r ^ (g & 31) instead of r, and forms its read address with an XOR instead

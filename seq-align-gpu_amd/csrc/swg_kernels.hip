@@ -2144,19 +2144,20 @@ __global__ void swg_build_profile_kernel(const int8_t *sub, const int8_t *query,
 }
 
 // The same for several queries at once (swg_search_multi): grid.y = query; int16, 4-column chunks.
-__global__ void swg_build_profiles_multi_kernel(const int8_t *sub, const int8_t *queries, const uint32_t *q_off,
-                                                uint32_t ncols, uint32_t k_real, uint32_t k_padded, uint32_t swizzle_lanes,
-                                                int f16, uint8_t *out)
+// pssms != nullptr: a batch of PSSMs (swg_search_multi_pssm), query qi's score of (query column, residue) is row
+// q_off[qi] + qcol of pssms[..][32] instead of sub[query[qcol]][code] (queries is not read); the rest is shared.
+__global__ void swg_build_profiles_multi_kernel(const int8_t *sub, const int8_t *queries, const int8_t *pssms,
+                                                const uint32_t *q_off, uint32_t ncols, uint32_t k_real, uint32_t k_padded,
+                                                uint32_t swizzle_lanes, int f16, uint8_t *out)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; // one (layout column, code)
     if (t >= ncols * 32u) return;
     const uint32_t qi = blockIdx.y;
-    const int8_t *query = queries + q_off[qi];
-    const uint32_t lq = q_off[qi + 1u] - q_off[qi];
+    const uint32_t q0 = q_off[qi], lq = q_off[qi + 1u] - q0;
     const uint32_t col = t >> 5, code = t & 31u;
     const uint32_t j = col % k_padded, qcol = (col / k_padded) * k_real + j;
     const bool pad = (j >= k_real) || (qcol >= lq) || (code == 0u);
-    const int v = pad ? 0 : (int)sub[(int)query[qcol] * 32 + (int)code];
+    const int v = pad ? 0 : pssms ? (int)pssms[((size_t)q0 + qcol) * 32u + code] : (int)sub[(int)queries[q0 + qcol] * 32 + (int)code];
     const uint32_t row = swizzle_lanes ? code ^ (((col / k_padded) % swizzle_lanes) & 31u) : code;
     const size_t e = (size_t)(col / 4u) * 128u + row * 4u + (col % 4u); // [col/4][32][4]
     if (f16) reinterpret_cast<_Float16 *>(out + (size_t)qi * ncols * 64u)[e] = pad ? (_Float16)-65504.0f : (_Float16)(float)v;
@@ -2166,10 +2167,10 @@ __global__ void swg_build_profiles_multi_kernel(const int8_t *sub, const int8_t 
 // Profiles of query PAIRS for swg_diag_qq_kernel: grid.y = pair; entry (column, residue) = the two queries' scores as
 // f16 numbers side by side (-65504 where a query has no such column), [col/2][32 residues][2 columns] x 4 bytes, rows
 // swizzled by the reading lane like the other lane-group profiles.  Pair y = queries 2y and 2y+1 of `order` (an odd
-// batch's last pair holds its query twice).
-__global__ void swg_build_profiles_qq_kernel(const int8_t *sub, const int8_t *queries, const uint32_t *q_off, const uint32_t *order,
-                                             uint32_t n_queries, uint32_t ncols, uint32_t k_real, uint32_t k_padded,
-                                             uint32_t swizzle_lanes, uint8_t *out)
+// batch's last pair holds its query twice).  pssms != nullptr: the scores come from a batch of PSSMs, as above.
+__global__ void swg_build_profiles_qq_kernel(const int8_t *sub, const int8_t *queries, const int8_t *pssms, const uint32_t *q_off,
+                                             const uint32_t *order, uint32_t n_queries, uint32_t ncols, uint32_t k_real,
+                                             uint32_t k_padded, uint32_t swizzle_lanes, uint8_t *out)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; // one (layout column, code)
     if (t >= ncols * 32u) return;
@@ -2178,10 +2179,10 @@ __global__ void swg_build_profiles_qq_kernel(const int8_t *sub, const int8_t *qu
     uint32_t word = 0u;
     for (uint32_t h = 0; h < 2u; ++h) {
         const uint32_t qi = order[min(2u * blockIdx.y + h, n_queries - 1u)];
-        const int8_t *query = queries + q_off[qi];
-        const uint32_t lq = q_off[qi + 1u] - q_off[qi];
+        const uint32_t q0 = q_off[qi], lq = q_off[qi + 1u] - q0;
         const bool pad = (j >= k_real) || (qcol >= lq) || (code == 0u);
-        const _Float16 v = pad ? (_Float16)-65504.0f : (_Float16)(float)sub[(int)query[qcol] * 32 + (int)code];
+        const int s = pad ? 0 : pssms ? (int)pssms[((size_t)q0 + qcol) * 32u + code] : (int)sub[(int)queries[q0 + qcol] * 32 + (int)code];
+        const _Float16 v = pad ? (_Float16)-65504.0f : (_Float16)(float)s;
         word |= (uint32_t)__builtin_bit_cast(unsigned short, v) << (16u * h);
     }
     const uint32_t row = swizzle_lanes ? code ^ (((col / k_padded) % swizzle_lanes) & 31u) : code;
@@ -2191,22 +2192,23 @@ __global__ void swg_build_profiles_qq_kernel(const int8_t *sub, const int8_t *qu
 
 hipError_t swg_launch_build_profiles_qq(const int8_t *d_sub, const int8_t *d_queries, const uint32_t *d_q_off, const uint32_t *d_order,
                                         uint32_t n_queries, uint32_t ncols, int k_real, int k_padded, uint8_t *d_profiles,
-                                        hipStream_t stream, int swizzle_lanes)
+                                        hipStream_t stream, int swizzle_lanes, const int8_t *d_pssms)
 {
     if (n_queries == 0 || ncols == 0) return hipSuccess;
     hipLaunchKernelGGL(swg_build_profiles_qq_kernel, dim3((ncols * 32u + 255u) / 256u, (n_queries + 1u) / 2u), dim3(256), 0, stream,
-                       d_sub, d_queries, d_q_off, d_order, n_queries, ncols, (uint32_t)k_real, (uint32_t)k_padded,
+                       d_sub, d_queries, d_pssms, d_q_off, d_order, n_queries, ncols, (uint32_t)k_real, (uint32_t)k_padded,
                        (uint32_t)swizzle_lanes, d_profiles);
     return hipGetLastError();
 }
 
 hipError_t swg_launch_build_profiles_multi(const int8_t *d_sub, const int8_t *d_queries, const uint32_t *d_q_off,
                                            uint32_t n_queries, uint32_t ncols, int k_real, int k_padded,
-                                           uint8_t *d_profiles, hipStream_t stream, int swizzle_lanes, int f16)
+                                           uint8_t *d_profiles, hipStream_t stream, int swizzle_lanes, int f16,
+                                           const int8_t *d_pssms)
 {
     if (n_queries == 0 || ncols == 0) return hipSuccess;
     hipLaunchKernelGGL(swg_build_profiles_multi_kernel, dim3((ncols * 32u + 255u) / 256u, n_queries), dim3(256), 0, stream,
-                       d_sub, d_queries, d_q_off, ncols, (uint32_t)k_real, (uint32_t)k_padded, (uint32_t)swizzle_lanes,
+                       d_sub, d_queries, d_pssms, d_q_off, ncols, (uint32_t)k_real, (uint32_t)k_padded, (uint32_t)swizzle_lanes,
                        f16, d_profiles);
     return hipGetLastError();
 }

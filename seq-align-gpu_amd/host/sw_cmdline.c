@@ -15,7 +15,8 @@
  *     --gpu N selects the device; --gpus N shards the database over devices 0..N-1 (one RCCL
  *     all-reduce merges the top-K lists); --pssm F scores the query by a PSI-BLAST ASCII PSSM
  *     (swg_pssm_load, swg_set_query_pssm) instead of the matrix (the matrix still fills the PSSM's
- *     unnamed columns).
+ *     unnamed columns); --pssmlist F does the same for every record of --allqueries, one PSSM file
+ *     named per line (the records after the first go through swg_search_multi_pssm).
  * There is no CPU backend: without a GPU the tool fails with a message.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -44,6 +45,7 @@ static void usage(const char *argv0, const char *err)
             "  OPTIONS:\n"
             "    --files <f1> <f2>    query file (first record) and database file\n"
             "    --pssm <file>        score the query by this PSI-BLAST ASCII PSSM (-out_ascii_pssm; its residues must be the query's)\n"
+            "    --pssmlist <file>    with --allqueries: line i names the PSSM of query record i (each must spell its record)\n"
             "    --substitution_matrix <file>  scoring matrix (see data/*.txt)\n"
             "    --gapopen <score>    [default: -2]\n"
             "    --gapextend <score>  [default: -1]   gap of length N costs open + N*extend\n"
@@ -158,7 +160,7 @@ int main(int argc, char **argv)
 {
     swg_scoring sc;
     swg_scoring_init(&sc);
-    const char *qpath = NULL, *dbpath = NULL, *savedb = NULL, *pssm_path = NULL;
+    const char *qpath = NULL, *dbpath = NULL, *savedb = NULL, *pssm_path = NULL, *pssmlist_path = NULL;
     int print_seq = 0, print_fasta = 0, have_matrix = 0, packed = 0, allq = 0;
     long topk = 0, gpu = 0, gpus = 0, v;
     int align = 0;
@@ -212,6 +214,8 @@ int main(int argc, char **argv)
             i++;
         } else if (!strcasecmp(a, "--pssm")) {
             pssm_path = argv[++i];
+        } else if (!strcasecmp(a, "--pssmlist")) {
+            pssmlist_path = argv[++i];
         } else if (!strcasecmp(a, "--savedb")) {
             if (i >= argc - 1) usage(argv[0], "--savedb takes a file name");
             savedb = argv[++i];
@@ -242,6 +246,9 @@ int main(int argc, char **argv)
     if (!qpath || !dbpath) usage(argv[0], "No input specified"); /* reference src/alignment_cmdline.c:303-305 */
     if (!have_matrix) usage(argv[0], "--substitution_matrix is required (the fill scores from the matrix only)");
     if (packed && (print_seq || print_fasta)) usage(argv[0], "--printseq/--printfasta need the FASTA database, not --packed");
+    if (pssmlist_path && !allq) usage(argv[0], "--pssmlist names the PSSMs of --allqueries' records: give --allqueries");
+    if (pssmlist_path && pssm_path) usage(argv[0], "--pssmlist and --pssm do not combine (the list names the first record's PSSM too)");
+    if (pssmlist_path && gpus > 0) usage(argv[0], "--pssmlist works with one GPU (--gpu)");
     if ((packed || savedb || allq) && gpus > 0) usage(argv[0], "--packed/--savedb/--allqueries work with one GPU (--gpu)");
     if (align && topk == 0) usage(argv[0], "--align reports the alignments of the --topk hits: give --topk K");
     if (pssm_path && allq) usage(argv[0], "--pssm scores one query: it does not combine with --allqueries");
@@ -309,6 +316,71 @@ int main(int argc, char **argv)
             return leave(EXIT_FAILURE);
         }
     }
+    /* --pssmlist: one PSSM per query record, line i of the list names record i's; each must spell its record.
+     * Every record's rows go into one array, record i's from row q.seq_off[i] on (a batch's offsets are its records'). */
+    int8_t *plist = NULL;
+    if (pssmlist_path) {
+        FILE *lf = fopen(pssmlist_path, "r");
+        if (!lf) {
+            fprintf(stderr, "Error: couldn't open the PSSM list %s\n", pssmlist_path);
+            return leave(EXIT_FAILURE);
+        }
+        char **names = NULL;
+        size_t n_names = 0, cap = 0;
+        char line[4096];
+        while (fgets(line, sizeof line, lf)) {
+            char *b = line, *e = line + strlen(line);
+            while (*b == ' ' || *b == '\t') b++;
+            while (e > b && (e[-1] == '\n' || e[-1] == '\r' || e[-1] == ' ' || e[-1] == '\t')) e--;
+            if (e == b) continue; /* (blank lines name nothing) */
+            *e = 0;
+            if (n_names == cap) {
+                cap = cap ? 2 * cap : 64;
+                char **grown = (char **)realloc(names, cap * sizeof *names);
+                if (!grown) return leave(EXIT_FAILURE);
+                names = grown;
+            }
+            if (!(names[n_names++] = strdup(b))) return leave(EXIT_FAILURE);
+        }
+        fclose(lf);
+        if (n_names != q.n) {
+            fprintf(stderr, "Error: the PSSM list %s names %lu PSSMs for %lu query records\n", pssmlist_path,
+                    (unsigned long)n_names, (unsigned long)q.n);
+            return leave(EXIT_FAILURE);
+        }
+        plist = (int8_t *)malloc((size_t)q.seq_off[q.n] * 32);
+        if (!plist) {
+            fprintf(stderr, "Error: out of memory\n");
+            return leave(EXIT_FAILURE);
+        }
+        for (size_t r = 0; r < q.n; r++) {
+            int8_t *pr = NULL, *pq = NULL;
+            size_t plq = 0;
+            if (swg_pssm_load(names[r], &sc, &pr, &pq, &plq, err, sizeof err) != SWG_OK) {
+                fprintf(stderr, "Error: PSSM list entry %lu (query record #%lu): %s\n", (unsigned long)r + 1, (unsigned long)r, err);
+                return leave(EXIT_FAILURE);
+            }
+            const char *rs = q.seq + q.seq_off[r];
+            const size_t rl = (size_t)(q.seq_off[r + 1] - q.seq_off[r]);
+            size_t at = 0;
+            for (; at < rl && at < plq; at++) {
+                const int c = swg_letter_index((unsigned char)rs[at]);
+                if (c < 0) die_illegal(rs[at]);
+                if (pq[at] != c) break;
+            }
+            if (at < rl || plq != rl) {
+                fprintf(stderr, "Error: the PSSM %s (list entry %lu, %lu positions) does not spell query record #%lu (%lu residues): "
+                        "they differ at position %lu\n", names[r], (unsigned long)r + 1, (unsigned long)plq, (unsigned long)r,
+                        (unsigned long)rl, (unsigned long)at + 1);
+                return leave(EXIT_FAILURE);
+            }
+            memcpy(plist + (size_t)q.seq_off[r] * 32, pr, rl * 32);
+            swg_pssm_free(pr, pq);
+            free(names[r]);
+        }
+        free(names);
+    }
+    const int8_t *pssm0 = pssm ? pssm : plist; /* the first record's PSSM, if any */
     swg_query_sanitize(&sc, qidx, lq); /* reference src/alignment_cmdline.c:391-396 */
     if (!packed && swg_seqs_to_indices(&db, didx, &bad) != SWG_OK) die_illegal(bad);
 
@@ -336,7 +408,7 @@ int main(int argc, char **argv)
         /* one search per query length: timing candidate geometries first would cost more than it saves */
         rc = swg_group_set_option(grp, "autotune", 0);
         if (rc == SWG_OK) rc = swg_group_set_scoring(grp, (const int8_t(*)[32])sc.sub, sc.gap_open, sc.gap_extend);
-        if (rc == SWG_OK) rc = pssm ? swg_group_set_query_pssm(grp, pssm, lq) : swg_group_set_query(grp, qidx, lq);
+        if (rc == SWG_OK) rc = pssm0 ? swg_group_set_query_pssm(grp, pssm0, lq) : swg_group_set_query(grp, qidx, lq);
         if (rc == SWG_OK) rc = swg_group_load(grp, didx, db.seq_off, db.n);
         phase("pack, shard and upload");
         if (rc == SWG_OK) rc = swg_group_search(grp, scores, hits, (size_t)topk, &n_hits, st);
@@ -372,7 +444,7 @@ int main(int argc, char **argv)
         /* one search per query length: timing candidate geometries first would cost more than it saves */
         if (rc == SWG_OK) rc = swg_set_option(ctx, "autotune", 0);
         if (rc == SWG_OK) rc = swg_set_scoring(ctx, (const int8_t(*)[32])sc.sub, sc.gap_open, sc.gap_extend);
-        if (rc == SWG_OK) rc = pssm ? swg_set_query_pssm(ctx, pssm, lq) : swg_set_query(ctx, qidx, lq);
+        if (rc == SWG_OK) rc = pssm0 ? swg_set_query_pssm(ctx, pssm0, lq) : swg_set_query(ctx, qidx, lq);
         if (rc == SWG_OK && savedb) {
             if (swg_db_save(pdb, savedb) != SWG_OK) {
                 fprintf(stderr, "Error: %s\n", swg_global_error());
@@ -462,7 +534,8 @@ next_query:
     if (allq && ++qi < q.n) {
         /* The database stays resident; the remaining queries go through swg_search_multi in chunks (one
          * launch per class for a whole chunk: a small database is filled with many queries at once),
-         * results are kept per query and printed in order. */
+         * results are kept per query and printed in order.  With --pssmlist the chunk's PSSMs go through
+         * swg_search_multi_pssm instead. */
         static int32_t *mq_scores = NULL;
         static swg_hit *mq_hits = NULL;
         static size_t *mq_nhits = NULL;
@@ -505,7 +578,9 @@ next_query:
             }
             swg_stats st;
             memset(&st, 0, sizeof st);
-            const int rc = swg_search_multi(ctx, pdb, qx, qoff, chunk_n, mq_scores, mq_hits, (size_t)topk, mq_nhits, &st);
+            const int rc = plist ? swg_search_multi_pssm(ctx, pdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff, chunk_n, mq_scores,
+                                                         mq_hits, (size_t)topk, mq_nhits, &st)
+                                 : swg_search_multi(ctx, pdb, qx, qoff, chunk_n, mq_scores, mq_hits, (size_t)topk, mq_nhits, &st);
             if (rc != SWG_OK) {
                 fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
                 return leave(EXIT_FAILURE);
@@ -519,8 +594,10 @@ next_query:
         memcpy(scores, mq_scores + at * (db.n ? db.n : 1), db.n * sizeof(int32_t));
         n_hits = mq_nhits[at];
         memcpy(hits, mq_hits + at * (topk ? (size_t)topk : 1), n_hits * sizeof(swg_hit));
-        if (align && swg_set_query(ctx, qx + qoff[at], (size_t)(qoff[at + 1] - qoff[at])) != SWG_OK) {
-            /* (the alignments of the hits are made against the context's query) */
+        const size_t lq_at = (size_t)(qoff[at + 1] - qoff[at]);
+        if (align && (plist ? swg_set_query_pssm(ctx, plist + (size_t)q.seq_off[qi] * 32, lq_at) : swg_set_query(ctx, qx + qoff[at], lq_at)) !=
+                         SWG_OK) {
+            /* (the alignments of the hits are made against the context's query: the record's PSSM with --pssmlist) */
             fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
             return leave(EXIT_FAILURE);
         }
@@ -544,6 +621,7 @@ next_query:
     swg_seqs_free(&db);
     free(qidx);
     swg_pssm_free(pssm, NULL);
+    free(plist);
     free(didx);
     free(scores);
     free(hits);
