@@ -313,6 +313,24 @@ int swg_align_hits(swg_ctx *ctx, const swg_db *db, const swg_hit *hits, size_t n
                    swg_alignment *out, char *ops, size_t ops_stride);
 size_t swg_align_ops_bound(const swg_ctx *ctx, const swg_db *db);
 
+/* The alignments of a batch's hits in one call: query i is queries[q_offsets[i] .. q_offsets[i+1]) (table
+ * indices, as swg_search_multi takes them), its hits are hits[i*k .. i*k + n_hits[i]) (n_hits[i] <= k; only .index
+ * is read; any order, and a sequence may appear in several rows), i.e. swg_search_multi's topk_out / n_hits.
+ * out[i*k + j] and, when ops is not NULL, the path at ops + (i*k + j)*ops_stride belong to hit j of query i; slots
+ * past n_hits[i] are not written.  Every field and path equals swg_set_query(query i) + swg_align_hits.  Scoring
+ * is the context's; the context's own query (index, PSSM or none) is neither read nor changed.  The database must
+ * be resident.  swg_align_ops_bound_multi(db, q_offsets, n_queries) = longest query + longest sequence + 1 is
+ * always enough for ops_stride (0 for NULL arguments; host only). */
+int swg_align_hits_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets,
+                         size_t n_queries, const swg_hit *hits, size_t k, const size_t *n_hits,
+                         swg_alignment *out, char *ops, size_t ops_stride);
+/* The same with position-specific queries: PSSM i is pssms[(q_offsets[i] + p)*32 + b] as swg_search_multi_pssm
+ * takes it; equals swg_set_query_pssm(PSSM i) + swg_align_hits. */
+int swg_align_hits_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets,
+                              size_t n_queries, const swg_hit *hits, size_t k, const size_t *n_hits,
+                              swg_alignment *out, char *ops, size_t ops_stride);
+size_t swg_align_ops_bound_multi(const swg_db *db, const uint64_t *q_offsets, size_t n_queries);
+
 /* ---- multi-GPU merge -------------------------------------------------- */
 
 /* 64-bit sort key of a hit: (score << 32) | (0xFFFFFFFF - index).  Larger key =

@@ -35,7 +35,8 @@ ABI_SYMBOLS = [
     "swg_set_option", "swg_set_scoring", "swg_set_query", "swg_set_query_pssm", "swg_db_pack", "swg_db_pack_shard", "swg_db_pack_shards", "swg_db_upload",
     "swg_db_free", "swg_db_save", "swg_db_load", "swg_db_count", "swg_db_total_count", "swg_db_residues",
     "swg_db_packed_bytes", "swg_db_order", "swg_search", "swg_search_begin", "swg_search_end", "swg_search_multi",
-    "swg_search_multi_pssm", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_hit_key",
+    "swg_search_multi_pssm", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_align_hits_multi",
+    "swg_align_hits_multi_pssm", "swg_align_ops_bound_multi", "swg_hit_key",
     "swg_key_hit", "swg_topk_merge_keys",
     "swg_group_create", "swg_group_destroy", "swg_group_size", "swg_group_last_error", "swg_group_set_option",
     "swg_group_set_scoring", "swg_group_set_query", "swg_group_set_query_pssm", "swg_group_load", "swg_group_search",
@@ -143,6 +144,9 @@ _sig("swg_search_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp
 _sig("swg_fill_batches16", C.c_int, [_vp, C.POINTER(Batch16), C.c_size_t, C.POINTER(C.c_double)])
 _sig("swg_align_hits", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t])
 _sig("swg_align_ops_bound", C.c_size_t, [_vp, _vp])
+_sig("swg_align_hits_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t])
+_sig("swg_align_hits_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t])
+_sig("swg_align_ops_bound_multi", C.c_size_t, [_vp, _vp, C.c_size_t])
 _sig("swg_hit_key", C.c_uint64, [C.c_int32, C.c_uint32])
 _sig("swg_key_hit", None, [C.c_uint64, C.POINTER(Hit)])
 _sig("swg_topk_merge_keys", C.c_size_t, [_vp, C.c_size_t, C.c_size_t, _vp])
@@ -615,6 +619,52 @@ class Context:
             if want_ops:
                 a["ops"] = ops.raw[i * stride:i * stride + a["n_ops"]].decode()
             res.append(a)
+        return res
+
+    def align_hits_multi(self, db, queries, hits, want_ops=True, ops_stride=None):
+        """Alignments of a batch's hits in one call: queries as search_multi takes them, hits the list of lists of
+        (score, index) it returns -> list of lists of align_hits' dicts.  The context's own query is left as it was."""
+        qoff = np.zeros(len(queries) + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in queries])
+        qflat = np.ascontiguousarray(np.concatenate(queries) if len(queries) else np.zeros(0), dtype=np.int8)
+        return self._align_multi(lib.swg_align_hits_multi, db, qflat, qoff, hits, want_ops, ops_stride)
+
+    def align_hits_multi_pssm(self, db, pssms, hits, want_ops=True, ops_stride=None):
+        """align_hits_multi with position-specific queries: pssms as search_multi_pssm takes them."""
+        rows = [_pssm(p)[0] for p in pssms]
+        qoff = np.zeros(len(rows) + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([r.shape[0] for r in rows])
+        pflat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 32)), dtype=np.int8)
+        return self._align_multi(lib.swg_align_hits_multi_pssm, db, pflat, qoff, hits, want_ops, ops_stride)
+
+    def _align_multi(self, fn, db, qflat, qoff, hits, want_ops, ops_stride):
+        nq = len(qoff) - 1
+        if len(hits) != nq:
+            raise ValueError("hits: %d rows for %d queries" % (len(hits), nq))
+        k = max((len(row) for row in hits), default=0)
+        arr = (Hit * max(nq * k, 1))()
+        nh = (C.c_size_t * max(nq, 1))()
+        for i, row in enumerate(hits):
+            nh[i] = len(row)
+            for j, (sc, ix) in enumerate(row):
+                arr[i * k + j].score, arr[i * k + j].index = int(sc), int(ix)
+        out = (Alignment * max(nq * k, 1))()
+        stride = int(ops_stride if ops_stride is not None else
+                     lib.swg_align_ops_bound_multi(db.handle, qoff.ctypes.data_as(_vp), nq))
+        ops = C.create_string_buffer(max(1, nq * k * stride)) if want_ops else None
+        _check(fn(self.handle, db.handle, qflat.ctypes.data_as(_vp), qoff.ctypes.data_as(_vp), nq, C.cast(arr, _vp), k,
+                  C.cast(nh, _vp), C.cast(out, _vp), C.cast(ops, _vp) if want_ops else None, stride), self.handle)
+        raw = ops.raw if want_ops else None          # (one copy: .raw copies the whole buffer on every access)
+        res = []
+        for i, row in enumerate(hits):
+            r = []
+            for j in range(len(row)):
+                h = i * k + j
+                a = {f: int(getattr(out[h], f)) for f, _ in Alignment._fields_ if f != "reserved"}
+                if want_ops:
+                    a["ops"] = raw[h * stride:h * stride + a["n_ops"]].decode()
+                r.append(a)
+            res.append(r)
         return res
 
     @staticmethod

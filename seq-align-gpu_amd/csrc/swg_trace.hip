@@ -7,21 +7,30 @@
 // database): one workgroup per pair sweeps the anti-diagonals of the pair's matrix, 256 cells at a
 // time, in int32, three rotating diagonals per state (in LDS for queries up to 1700 columns, else
 // in HBM/L2), one predecessor byte per cell stored diagonal-major (coalesced), then one lane follows
-// the bytes back.  Everything runs on
+// the bytes back.  A call may hold the hits of a whole batch of queries (swg_align_hits_multi): each
+// pair carries its own query.  Everything runs on
 // the GPU; like the rest of the library there is no CPU path.
 #include "swg_host_internal.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <new>
+#include <stdexcept>
 #include <cstring>
 #include <unordered_map>
 
+// One pair.  A job carries its own query, so one launch can hold the hits of several queries of a batch; the offsets
+// into the launch's predecessor bytes, rotating diagonals and paths are the job's own because all three are sized by
+// its lq (and the path by its len).
 struct SwgTraceJob {
-    uint64_t res_off; // into the gathered residue indices
-    uint64_t dir_off; // into the predecessor bytes
-    uint32_t len;     // database sequence length
-    uint32_t pad;
+    uint64_t q_off;    // into the batch's query: first index byte, or first PSSM row
+    uint64_t res_off;  // into the gathered residue indices
+    uint64_t dir_off;  // into the launch's predecessor bytes: (lq + len - 1) * lq of them
+    uint64_t diag_off; // into the launch's rotating anti-diagonals (kernels without LDS): 9 * (lq + 1) words
+    uint64_t ops_off;  // into the launch's paths: lq + len + 1 bytes (a path has at most lq + len steps)
+    uint32_t lq;       // query length
+    uint32_t len;      // database sequence length
 };
 
 struct SwgTraceOut {
@@ -30,16 +39,15 @@ struct SwgTraceOut {
 };
 
 struct SwgTraceParams {
-    const int8_t *query; // [lq] table indices
-    const int8_t *sub;   // [32][32], row = query residue
-    const int8_t *pssm;  // PSSM kernel: [lq][32], row = query position (query and sub unread)
-    const int8_t *res;   // database residue indices of the jobs, back to back
+    const int8_t *query; // table indices of the batch's queries, back to back (PSSM kernel: unread)
+    const int8_t *sub;   // [32][32], row = query residue (PSSM kernel: unread)
+    const int8_t *pssm;  // PSSM kernel: the batch's PSSM rows [positions][32], row = query position
+    const int8_t *res;   // database residue indices of the jobs' sequences
     const SwgTraceJob *jobs;
-    int32_t *diag;       // per job 9 * (lq + 1): three rotating anti-diagonals of H, A and B
-    uint8_t *dir;        // per job (lq + len - 1) * lq predecessor bytes, diagonal-major
-    char *ops;           // per job ops_stride bytes
+    int32_t *diag;       // three rotating anti-diagonals of H, A and B per job (kernels without LDS)
+    uint8_t *dir;        // predecessor bytes per job, diagonal-major
+    char *ops;           // path per job
     SwgTraceOut *out;
-    uint32_t lq, ops_stride;
     int go, ge;
 };
 
@@ -53,7 +61,8 @@ __device__ __forceinline__ uint32_t trace_pick(int32_t m, int32_t x, int32_t y)
 }
 
 // IN_LDS: the nine rotating anti-diagonals live in the workgroup's LDS (queries up to
-// SWG_TRACE_LDS_COLS columns; one dependent sweep then waits for LDS, not for L2).
+// SWG_TRACE_LDS_COLS columns; one dependent sweep then waits for LDS, not for L2), sized by the longest query of
+// the launch.
 // PSSM: a position-specific query; a cell's score is read from row i-1 of the PSSM in global memory (32 * lq bytes,
 // more than LDS holds for a long query; a sweep reads consecutive rows, which stay in cache) instead of the table.
 template <bool IN_LDS, bool PSSM>
@@ -65,7 +74,8 @@ __global__ __launch_bounds__(SWG_TRACE_THREADS) void swg_trace_kernel(SwgTracePa
     __shared__ unsigned long long s_pos;
     __shared__ uint32_t s_n;
     const SwgTraceJob job = p.jobs[blockIdx.x];
-    const uint32_t lq = p.lq, len = job.len, tid = threadIdx.x, w = lq + 1;
+    const uint32_t lq = job.lq, len = job.len, tid = threadIdx.x, w = lq + 1;
+    const int8_t *query = PSSM ? nullptr : p.query + job.q_off, *pssm = PSSM ? p.pssm + job.q_off * 32 : nullptr;
     if (!PSSM)
         for (uint32_t k = tid; k < 1024; k += SWG_TRACE_THREADS) s_sub[k] = p.sub[k];
     if (tid == 0) {
@@ -75,7 +85,7 @@ __global__ __launch_bounds__(SWG_TRACE_THREADS) void swg_trace_kernel(SwgTracePa
     }
     int32_t *X;
     if (IN_LDS) X = s_diag;
-    else X = p.diag + (size_t)blockIdx.x * 9 * w;
+    else X = p.diag + job.diag_off;
     const int8_t *d = p.res + job.res_off;
     uint8_t *dir = p.dir + job.dir_off;
     const int go = p.go, ge = p.ge;
@@ -100,8 +110,8 @@ __global__ __launch_bounds__(SWG_TRACE_THREADS) void swg_trace_kernel(SwgTracePa
                 if (i > 1) hd = H2[i - 1], ad = A2[i - 1], bd = B2[i - 1];
             }
             if (i > 1) hl = H1[i - 1], al = A1[i - 1], bl = B1[i - 1];
-            const int32_t s = PSSM ? (int32_t)p.pssm[(size_t)(i - 1) * 32 + (int)d[j - 1]]
-                                   : (int32_t)s_sub[(int)p.query[i - 1] * 32 + (int)d[j - 1]];
+            const int32_t s = PSSM ? (int32_t)pssm[(size_t)(i - 1) * 32 + (int)d[j - 1]]
+                                   : (int32_t)s_sub[(int)query[i - 1] * 32 + (int)d[j - 1]];
             const int32_t mh = max(max(hd, ad), max(bd, 0));
             const int32_t xa = hu + go, ya = au + ge, za = bu + go;
             const int32_t ma = max(max(xa, ya), max(za, 0));
@@ -121,7 +131,7 @@ __global__ __launch_bounds__(SWG_TRACE_THREADS) void swg_trace_kernel(SwgTracePa
     if (best == s_best && best > 0) atomicMin(&s_pos, (unsigned long long)bj << 32 | bi);
     __syncthreads();
 
-    char *ops = p.ops + (size_t)blockIdx.x * p.ops_stride;
+    char *ops = p.ops + job.ops_off;
     if (tid == 0) {
         SwgTraceOut o = {};
         uint32_t n = 0;
@@ -129,7 +139,7 @@ __global__ __launch_bounds__(SWG_TRACE_THREADS) void swg_trace_kernel(SwgTracePa
             uint32_t j = (uint32_t)(s_pos >> 32), i = (uint32_t)s_pos;
             o.score = s_best, o.q_end = i, o.d_end = j;
             uint32_t state = 1;
-            while (j > 0 && i > 0 && n + 1 < p.ops_stride) {
+            while (j > 0 && i > 0 && n < lq + len) {
                 const uint32_t c = dir[(size_t)(i + j - 2) * lq + (i - 1)];
                 uint32_t from;
                 if (state == 1) ops[n++] = 'M', from = c & 3, --j, --i;
@@ -163,12 +173,205 @@ __global__ __launch_bounds__(SWG_TRACE_THREADS) void swg_trace_kernel(SwgTracePa
         }                                                                                               \
     } while (0)
 
+static size_t longest_sequence(const swg_db *db)
+{
+    uint32_t longest = 0;
+    for (uint32_t l : db->lens) longest = std::max(longest, l);
+    return longest;
+}
+
 extern "C" size_t swg_align_ops_bound(const swg_ctx *ctx, const swg_db *db)
 {
     if (!ctx || !db) return 0;
-    uint32_t longest = 0;
-    for (uint32_t l : db->lens) longest = std::max(longest, l);
-    return ctx->query_len() + longest + 1;
+    return ctx->query_len() + longest_sequence(db) + 1;
+}
+
+extern "C" size_t swg_align_ops_bound_multi(const swg_db *db, const uint64_t *q_offsets, size_t n_queries)
+{
+    if (!db || !q_offsets) return 0;
+    uint64_t lq_max = 0;
+    for (size_t i = 0; i < n_queries; ++i)
+        if (q_offsets[i + 1] > q_offsets[i]) lq_max = std::max<uint64_t>(lq_max, q_offsets[i + 1] - q_offsets[i]);
+    return (size_t)lq_max + longest_sequence(db) + 1;
+}
+
+// The pairs of one call: query i is src[q_offsets[i] .. q_offsets[i+1]) in positions (index bytes, or PSSM rows of 32
+// bytes), its hits are hits[i*k .. i*k + n_hits[i]), and out / ops take the same layout.  swg_align_hits is the batch
+// of one query, the context's.
+struct TraceBatch {
+    const char *fn; // the entry point, for messages
+    const int8_t *src;
+    bool pssm;
+    const uint64_t *q_offsets;
+    size_t n_queries;
+    const swg_hit *hits;
+    size_t k;
+    const size_t *n_hits;
+};
+
+// One launch: jobs [b, e) of the launch order, the bytes its buffers need, its longest query.
+struct TraceLaunch {
+    size_t b, e;
+    uint64_t dir, diag, ops;
+    uint32_t lq_max;
+};
+
+// A launch holds the queries of one class: one power-of-two range of lengths among those whose diagonals fit LDS (so
+// its dynamic LDS, sized by its longest query, is less than twice what any of its jobs needs), or every longer query.
+static int trace_class(uint32_t lq) { return lq > SWG_TRACE_LDS_COLS ? 0 : 32 - __builtin_clz(lq); }
+
+// Every hit of a checked batch (total > 0 hits): the shared body of all three entry points.  Device buffers are
+// allocated once per call; jobs are ordered by query length and cut into launches by class and by the 2 GiB budget of
+// predecessor bytes; each launch ends in one stream synchronisation, then its results are copied out.
+static int align_batch(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, size_t total, swg_alignment *out, char *ops,
+                       size_t ops_stride)
+{
+    const char *fn = tb.fn;
+    // original index -> slot of the sorted order, for the wanted sequences only
+    std::unordered_map<uint32_t, size_t> slot_of;
+    slot_of.reserve(total * 2);
+    for (size_t i = 0; i < tb.n_queries; ++i)
+        for (size_t j = 0; j < tb.n_hits[i]; ++j) slot_of[tb.hits[i * tb.k + j].index] = SIZE_MAX;
+    for (size_t s = 0; s < db->order.size(); ++s) {
+        if (db->order[s] == ~0u) continue;
+        auto it = slot_of.find(db->order[s]);
+        if (it != slot_of.end()) it->second = s;
+    }
+    std::vector<SwgTraceJob> in_order;
+    std::vector<size_t> dest_in_order; // out[] index of each job
+    in_order.reserve(total), dest_in_order.reserve(total);
+    std::unordered_map<size_t, uint64_t> res_of; // slot -> its residues in `res` (a sequence is gathered once)
+    std::vector<int8_t> res;
+    for (size_t i = 0; i < tb.n_queries; ++i) {
+        const size_t lq = (size_t)(tb.q_offsets[i + 1] - tb.q_offsets[i]);
+        for (size_t j = 0; j < tb.n_hits[i]; ++j) {
+            const uint32_t index = tb.hits[i * tb.k + j].index;
+            const size_t s = slot_of[index];
+            if (s == SIZE_MAX)
+                return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: sequence %u is not in this database shard", fn, index);
+            const size_t len = db->lens[s];
+            const uint64_t cells = (uint64_t)(lq + len) * lq;
+            if (len == 0 || cells > (16ull << 30))
+                return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: pair %u (%zu x %zu) is outside what a traceback holds", fn,
+                                         index, lq, len);
+            const auto r = res_of.emplace(s, (uint64_t)res.size());
+            if (r.second) {
+                const uint8_t *c = db->codes.data() + db->code_off[s];
+                for (size_t x = 0; x < len; ++x) res.push_back((int8_t)(c[x] >> 3)); // codes are index << 3
+            }
+            SwgTraceJob jb = {};
+            jb.q_off = tb.q_offsets[i] - tb.q_offsets[0];
+            jb.res_off = r.first->second;
+            jb.lq = (uint32_t)lq, jb.len = (uint32_t)len;
+            in_order.push_back(jb), dest_in_order.push_back(i * tb.k + j);
+        }
+    }
+    // launch order: by query length (stable), then cut where the class changes or the predecessor bytes would pass
+    // 2 GiB (a single larger pair goes alone)
+    const size_t n = in_order.size();
+    std::vector<size_t> perm(n);
+    for (size_t h = 0; h < n; ++h) perm[h] = h;
+    std::stable_sort(perm.begin(), perm.end(), [&](size_t a, size_t b) { return in_order[a].lq < in_order[b].lq; });
+    std::vector<SwgTraceJob> jobs(n);
+    std::vector<size_t> dest(n);
+    for (size_t h = 0; h < n; ++h) jobs[h] = in_order[perm[h]], dest[h] = dest_in_order[perm[h]];
+    std::vector<TraceLaunch> launches;
+    uint64_t max_dir = 4, max_diag = 4, max_ops = 4;
+    for (size_t b = 0; b < n;) {
+        const uint64_t budget = 2ull << 30;
+        TraceLaunch L = {b, b, 0, 0, 0, 0};
+        for (; L.e < n; ++L.e) {
+            SwgTraceJob &jb = jobs[L.e];
+            const uint64_t need = (uint64_t)(jb.lq + jb.len - 1) * jb.lq;
+            if (L.e > b && (L.dir + need > budget || trace_class(jb.lq) != trace_class(jobs[b].lq))) break;
+            jb.dir_off = L.dir, jb.diag_off = L.diag, jb.ops_off = L.ops;
+            L.dir += need, L.diag += 9ull * (jb.lq + 1), L.ops += (uint64_t)jb.lq + jb.len + 1;
+            L.lq_max = std::max(L.lq_max, jb.lq);
+        }
+        max_dir = std::max(max_dir, L.dir), max_ops = std::max(max_ops, L.ops);
+        if (L.lq_max > SWG_TRACE_LDS_COLS) max_diag = std::max(max_diag, L.diag);
+        launches.push_back(L);
+        b = L.e;
+    }
+    const size_t row_bytes = tb.pssm ? 32 : 1;
+    const size_t q_bytes = (size_t)(tb.q_offsets[tb.n_queries] - tb.q_offsets[0]) * row_bytes;
+    std::vector<SwgTraceOut> h_out(n);
+    std::vector<char> h_ops(ops ? max_ops : 0);
+
+    int rc = SWG_OK;
+    int8_t *d_query = nullptr, *d_sub = nullptr, *d_res = nullptr;
+    SwgTraceJob *d_jobs = nullptr;
+    int32_t *d_diag = nullptr;
+    uint8_t *d_dir = nullptr;
+    char *d_ops = nullptr;
+    SwgTraceOut *d_out = nullptr;
+    TRACE_TRY(ctx, hipSetDevice(ctx->device));
+    // the queries' scores: index queries + table, or the PSSM rows (then the table is not read)
+    TRACE_TRY(ctx, hipMalloc(&d_query, q_bytes));
+    TRACE_TRY(ctx, hipMalloc(&d_sub, 1024));
+    TRACE_TRY(ctx, hipMalloc(&d_res, std::max<size_t>(res.size(), 4)));
+    TRACE_TRY(ctx, hipMalloc(&d_jobs, n * sizeof(SwgTraceJob)));
+    TRACE_TRY(ctx, hipMalloc(&d_diag, max_diag * sizeof(int32_t)));
+    TRACE_TRY(ctx, hipMalloc(&d_dir, max_dir));
+    TRACE_TRY(ctx, hipMalloc(&d_ops, max_ops));
+    TRACE_TRY(ctx, hipMalloc(&d_out, n * sizeof(SwgTraceOut)));
+    TRACE_TRY(ctx, hipMemcpyAsync(d_query, tb.src + tb.q_offsets[0] * row_bytes, q_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (!tb.pssm) TRACE_TRY(ctx, hipMemcpyAsync(d_sub, &ctx->sub[0][0], 1024, hipMemcpyHostToDevice, ctx->stream));
+    TRACE_TRY(ctx, hipMemcpyAsync(d_res, res.data(), res.size(), hipMemcpyHostToDevice, ctx->stream));
+    TRACE_TRY(ctx, hipMemcpyAsync(d_jobs, jobs.data(), n * sizeof(SwgTraceJob), hipMemcpyHostToDevice, ctx->stream));
+    for (const TraceLaunch &L : launches) {
+        const size_t nb = L.e - L.b;
+        SwgTraceParams p;
+        p.query = d_query, p.sub = d_sub, p.pssm = d_query, p.res = d_res, p.jobs = d_jobs + L.b, p.diag = d_diag, p.dir = d_dir;
+        p.ops = d_ops, p.out = d_out + L.b;
+        p.go = ctx->gap_open + ctx->gap_extend, p.ge = ctx->gap_extend; // src/alignment.c:58-59
+        const bool in_lds = L.lq_max <= SWG_TRACE_LDS_COLS;
+        const size_t lds = in_lds ? 9 * ((size_t)L.lq_max + 1) * sizeof(int32_t) : 0;
+        if (in_lds && !tb.pssm)
+            hipLaunchKernelGGL((swg_trace_kernel<true, false>), dim3((unsigned)nb), dim3(SWG_TRACE_THREADS), lds, ctx->stream, p);
+        else if (!tb.pssm)
+            hipLaunchKernelGGL((swg_trace_kernel<false, false>), dim3((unsigned)nb), dim3(SWG_TRACE_THREADS), 0, ctx->stream, p);
+        else if (in_lds)
+            hipLaunchKernelGGL((swg_trace_kernel<true, true>), dim3((unsigned)nb), dim3(SWG_TRACE_THREADS), lds, ctx->stream, p);
+        else
+            hipLaunchKernelGGL((swg_trace_kernel<false, true>), dim3((unsigned)nb), dim3(SWG_TRACE_THREADS), 0, ctx->stream, p);
+        TRACE_TRY(ctx, hipGetLastError());
+        TRACE_TRY(ctx, hipMemcpyAsync(h_out.data() + L.b, d_out + L.b, nb * sizeof(SwgTraceOut), hipMemcpyDeviceToHost,
+                                      ctx->stream));
+        if (ops) TRACE_TRY(ctx, hipMemcpyAsync(h_ops.data(), d_ops, L.ops, hipMemcpyDeviceToHost, ctx->stream));
+        TRACE_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (size_t h = L.b; h < L.e; ++h) {
+            const SwgTraceOut &o = h_out[h];
+            swg_alignment &a = out[dest[h]];
+            a.score = o.score, a.index = tb.hits[dest[h]].index;
+            a.q_begin = o.q_begin, a.q_end = o.q_end, a.d_begin = o.d_begin, a.d_end = o.d_end;
+            a.n_ops = o.n_ops, a.reserved = 0;
+            if (!ops) continue;
+            if ((size_t)o.n_ops + 1 > ops_stride) {
+                rc = swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: ops_stride %zu too small for a path of %u steps "
+                                       "(swg_align_ops_bound() / swg_align_ops_bound_multi() is always enough)", fn, ops_stride, o.n_ops);
+                goto done;
+            }
+            memcpy(ops + dest[h] * ops_stride, h_ops.data() + jobs[h].ops_off, (size_t)o.n_ops + 1);
+        }
+    }
+done:
+    (void)hipFree(d_query), (void)hipFree(d_sub), (void)hipFree(d_res), (void)hipFree(d_jobs);
+    (void)hipFree(d_diag), (void)hipFree(d_dir), (void)hipFree(d_ops), (void)hipFree(d_out);
+    return rc;
+}
+
+// try/catch: no C++ exception crosses the ABI (the host vectors are sized by the batch)
+static int align_batch_guarded(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, size_t total, swg_alignment *out,
+                               char *ops, size_t ops_stride)
+{
+    try {
+        return align_batch(ctx, db, tb, total, out, ops, ops_stride);
+    } catch (const std::bad_alloc &) {
+        return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "%s: out of host memory", tb.fn);
+    } catch (const std::exception &e) {
+        return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "%s: %s", tb.fn, e.what());
+    }
 }
 
 extern "C" int swg_align_hits(swg_ctx *ctx, const swg_db *db, const swg_hit *hits, size_t n_hits,
@@ -182,135 +385,57 @@ extern "C" int swg_align_hits(swg_ctx *ctx, const swg_db *db, const swg_hit *hit
     if (ops && ops_stride == 0) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_align_hits: ops_stride is 0");
     if (n_hits == 0) return SWG_OK;
     if (n_hits > (1u << 20)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_align_hits: more than 2^20 hits");
-    const size_t lq = ctx->query_len();
-    const bool pssm = ctx->query_pssm;
+    const uint64_t q_offsets[2] = {0, ctx->query_len()};
+    const TraceBatch tb = {"swg_align_hits", ctx->query_pssm ? ctx->pssm.data() : ctx->query.data(), ctx->query_pssm,
+                           q_offsets, 1, hits, n_hits, &n_hits};
+    return align_batch_guarded(ctx, db, tb, n_hits, out, ops, ops_stride);
+}
 
-    // original index -> slot of the sorted order, for the wanted sequences only
-    std::unordered_map<uint32_t, size_t> slot_of;
-    slot_of.reserve(n_hits * 2);
-    for (size_t h = 0; h < n_hits; ++h) slot_of[hits[h].index] = SIZE_MAX;
-    for (size_t s = 0; s < db->order.size(); ++s) {
-        if (db->order[s] == ~0u) continue;
-        auto it = slot_of.find(db->order[s]);
-        if (it != slot_of.end()) it->second = s;
+// The batch entry points: the queries are checked as search_multi_impl checks them, the rows of hits against k.
+static int align_hits_multi(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, swg_alignment *out, char *ops,
+                            size_t ops_stride)
+{
+    const char *fn = tb.fn;
+    if (!ctx) return swg_set_global_error(SWG_ERR_ARG, "%s: NULL context", fn);
+    if (!db || (tb.n_queries && (!tb.src || !tb.q_offsets || !tb.n_hits)))
+        return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: NULL argument", fn);
+    if (!ctx->have_scoring) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: no scoring set", fn);
+    if (db->device != ctx->device || !db->d_codes)
+        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: database is not resident on device %d", fn, ctx->device);
+    if (ops && ops_stride == 0) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: ops_stride is 0", fn);
+    size_t total = 0;
+    for (size_t i = 0; i < tb.n_queries; ++i) {
+        if (tb.q_offsets[i + 1] <= tb.q_offsets[i])
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: query %zu is empty or the offsets are not increasing", fn, i);
+        if (tb.q_offsets[i + 1] - tb.q_offsets[i] > (1u << 24))
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: query %zu too long", fn, i);
+        for (uint64_t j = tb.q_offsets[i]; j < tb.q_offsets[i + 1] && !tb.pssm; ++j) // (a PSSM takes any int8)
+            if (tb.src[j] < 1 || tb.src[j] > 31)
+                return swg_set_ctx_error(ctx, SWG_ERR_RESIDUE, "%s: residue index %d in query %zu outside 1..31", fn,
+                                         tb.src[j], i);
+        if (tb.n_hits[i] > tb.k)
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: row %zu holds %zu hits, more than k = %zu", fn, i, tb.n_hits[i],
+                                     tb.k);
+        total += tb.n_hits[i];
     }
-    std::vector<SwgTraceJob> jobs(n_hits);
-    std::vector<int8_t> res;
-    size_t longest = 0;
-    for (size_t h = 0; h < n_hits; ++h) {
-        const size_t s = slot_of[hits[h].index];
-        if (s == SIZE_MAX)
-            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_align_hits: sequence %u is not in this database shard",
-                                     hits[h].index);
-        const size_t len = db->lens[s];
-        const uint64_t cells = (uint64_t)(lq + len) * lq;
-        if (len == 0 || cells > (16ull << 30))
-            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_align_hits: pair %u (%zu x %zu) is outside what a traceback holds",
-                                     hits[h].index, lq, len);
-        jobs[h].res_off = res.size();
-        jobs[h].len = (uint32_t)len;
-        jobs[h].pad = 0;
-        const uint8_t *c = db->codes.data() + db->code_off[s];
-        for (size_t r = 0; r < len; ++r) res.push_back((int8_t)(c[r] >> 3)); // codes are index << 3
-        longest = std::max(longest, len);
-    }
-    const size_t dev_stride = lq + longest + 1; // a path has at most lq + len steps
+    if (total == 0) return SWG_OK;
+    if (!tb.hits || !out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: NULL argument", fn);
+    if (total > (1u << 20)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: more than 2^20 hits", fn);
+    return align_batch_guarded(ctx, db, tb, total, out, ops, ops_stride);
+}
 
-    int rc = SWG_OK;
-    int8_t *d_query = nullptr, *d_sub = nullptr, *d_res = nullptr;
-    SwgTraceJob *d_jobs = nullptr;
-    int32_t *d_diag = nullptr;
-    uint8_t *d_dir = nullptr;
-    char *d_ops = nullptr;
-    SwgTraceOut *d_out = nullptr;
-    std::vector<SwgTraceOut> h_out(n_hits);
-    std::vector<char> h_ops;
-    size_t max_chunk = 0, max_dir = 0;
-    const bool in_lds = lq <= SWG_TRACE_LDS_COLS;
-    {
-        // chunks of consecutive hits whose predecessor bytes fit 2 GiB together (a single larger pair goes alone)
-        const uint64_t budget = 2ull << 30;
-        for (size_t b = 0; b < n_hits;) {
-            uint64_t bytes = 0;
-            size_t e = b;
-            while (e < n_hits) {
-                const uint64_t need = (uint64_t)(lq + jobs[e].len - 1) * lq;
-                if (e > b && bytes + need > budget) break;
-                bytes += need, ++e;
-            }
-            max_chunk = std::max(max_chunk, e - b), max_dir = std::max<size_t>(max_dir, bytes);
-            b = e;
-        }
-    }
-    TRACE_TRY(ctx, hipSetDevice(ctx->device));
-    // the query's scores: index query + table, or the PSSM (then d_sub holds it and d_query is not needed)
-    TRACE_TRY(ctx, hipMalloc(&d_query, pssm ? 4 : lq));
-    TRACE_TRY(ctx, hipMalloc(&d_sub, pssm ? lq * 32 : 1024));
-    TRACE_TRY(ctx, hipMalloc(&d_res, std::max<size_t>(res.size(), 4)));
-    TRACE_TRY(ctx, hipMalloc(&d_jobs, n_hits * sizeof(SwgTraceJob)));
-    TRACE_TRY(ctx, hipMalloc(&d_diag, in_lds ? 16 : max_chunk * 9 * (lq + 1) * sizeof(int32_t)));
-    TRACE_TRY(ctx, hipMalloc(&d_dir, std::max<size_t>(max_dir, 4)));
-    TRACE_TRY(ctx, hipMalloc(&d_ops, max_chunk * dev_stride));
-    TRACE_TRY(ctx, hipMalloc(&d_out, n_hits * sizeof(SwgTraceOut)));
-    if (pssm) {
-        TRACE_TRY(ctx, hipMemcpyAsync(d_sub, ctx->pssm.data(), lq * 32, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        TRACE_TRY(ctx, hipMemcpyAsync(d_query, ctx->query.data(), lq, hipMemcpyHostToDevice, ctx->stream));
-        TRACE_TRY(ctx, hipMemcpyAsync(d_sub, &ctx->sub[0][0], 1024, hipMemcpyHostToDevice, ctx->stream));
-    }
-    TRACE_TRY(ctx, hipMemcpyAsync(d_res, res.data(), res.size(), hipMemcpyHostToDevice, ctx->stream));
-    if (ops) h_ops.resize(max_chunk * dev_stride);
-    for (size_t b = 0; b < n_hits;) {
-        const uint64_t budget = 2ull << 30;
-        uint64_t bytes = 0;
-        size_t e = b;
-        while (e < n_hits) {
-            const uint64_t need = (uint64_t)(lq + jobs[e].len - 1) * lq;
-            if (e > b && bytes + need > budget) break;
-            jobs[e].dir_off = bytes;
-            bytes += need, ++e;
-        }
-        const size_t nb = e - b;
-        TRACE_TRY(ctx, hipMemcpyAsync(d_jobs + b, jobs.data() + b, nb * sizeof(SwgTraceJob), hipMemcpyHostToDevice,
-                                      ctx->stream));
-        SwgTraceParams p;
-        p.query = d_query, p.sub = d_sub, p.pssm = pssm ? d_sub : nullptr, p.res = d_res, p.jobs = d_jobs + b, p.diag = d_diag, p.dir = d_dir;
-        p.ops = d_ops, p.out = d_out + b, p.lq = (uint32_t)lq, p.ops_stride = (uint32_t)dev_stride;
-        p.go = ctx->gap_open + ctx->gap_extend, p.ge = ctx->gap_extend; // src/alignment.c:58-59
-        if (in_lds && !pssm)
-            hipLaunchKernelGGL((swg_trace_kernel<true, false>), dim3((unsigned)nb), dim3(SWG_TRACE_THREADS),
-                               9 * (lq + 1) * sizeof(int32_t), ctx->stream, p);
-        else if (!pssm)
-            hipLaunchKernelGGL((swg_trace_kernel<false, false>), dim3((unsigned)nb), dim3(SWG_TRACE_THREADS), 0, ctx->stream, p);
-        else if (in_lds)
-            hipLaunchKernelGGL((swg_trace_kernel<true, true>), dim3((unsigned)nb), dim3(SWG_TRACE_THREADS),
-                               9 * (lq + 1) * sizeof(int32_t), ctx->stream, p);
-        else
-            hipLaunchKernelGGL((swg_trace_kernel<false, true>), dim3((unsigned)nb), dim3(SWG_TRACE_THREADS), 0, ctx->stream, p);
-        TRACE_TRY(ctx, hipGetLastError());
-        TRACE_TRY(ctx, hipMemcpyAsync(h_out.data() + b, d_out + b, nb * sizeof(SwgTraceOut), hipMemcpyDeviceToHost,
-                                      ctx->stream));
-        if (ops)
-            TRACE_TRY(ctx, hipMemcpyAsync(h_ops.data(), d_ops, nb * dev_stride, hipMemcpyDeviceToHost, ctx->stream));
-        TRACE_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (size_t h = b; h < e; ++h) {
-            const SwgTraceOut &o = h_out[h];
-            swg_alignment &a = out[h];
-            a.score = o.score, a.index = hits[h].index;
-            a.q_begin = o.q_begin, a.q_end = o.q_end, a.d_begin = o.d_begin, a.d_end = o.d_end;
-            a.n_ops = o.n_ops, a.reserved = 0;
-            if (!ops) continue;
-            if ((size_t)o.n_ops + 1 > ops_stride) {
-                rc = swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_align_hits: ops_stride %zu too small for a path of %u steps "
-                                       "(swg_align_ops_bound() is always enough)", ops_stride, o.n_ops);
-                goto done;
-            }
-            memcpy(ops + h * ops_stride, h_ops.data() + (h - b) * dev_stride, (size_t)o.n_ops + 1);
-        }
-        b = e;
-    }
-done:
-    (void)hipFree(d_query), (void)hipFree(d_sub), (void)hipFree(d_res), (void)hipFree(d_jobs);
-    (void)hipFree(d_diag), (void)hipFree(d_dir), (void)hipFree(d_ops), (void)hipFree(d_out);
-    return rc;
+extern "C" int swg_align_hits_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets,
+                                    size_t n_queries, const swg_hit *hits, size_t k, const size_t *n_hits,
+                                    swg_alignment *out, char *ops, size_t ops_stride)
+{
+    const TraceBatch tb = {"swg_align_hits_multi", queries, false, q_offsets, n_queries, hits, k, n_hits};
+    return align_hits_multi(ctx, db, tb, out, ops, ops_stride);
+}
+
+extern "C" int swg_align_hits_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets,
+                                         size_t n_queries, const swg_hit *hits, size_t k, const size_t *n_hits,
+                                         swg_alignment *out, char *ops, size_t ops_stride)
+{
+    const TraceBatch tb = {"swg_align_hits_multi_pssm", pssms, true, q_offsets, n_queries, hits, k, n_hits};
+    return align_hits_multi(ctx, db, tb, out, ops, ops_stride);
 }

@@ -466,6 +466,16 @@ int main(int argc, char **argv)
     /* reference src/tools/sw_cmdline.c:38-75: per 16 records the query lines, then per record */
     const char *qname = q.names + q.name_off[0];
     size_t qi = 0;
+    /* --allqueries --align: the alignments of queries [al_first, al_first + al_n) of the current chunk, hit j of query
+     * al_first + i at mq_al[i*topk + j] and mq_ops + (i*topk + j)*al_stride */
+    swg_alignment *mq_al = NULL;
+    char *mq_ops = NULL;
+    size_t al_first = 0, al_n = 0, al_stride = 0, al_records = 0, al_calls = 0;
+    double al_ms = 0.0;
+    /* after a failed call: one record per call, and the error of the record that fails is reported where its
+     * alignments would print, after its own search results (as when each record was aligned on its own) */
+    int al_one_by_one = 0, al_failed = 0;
+    char al_err[512] = "";
 next_query:
     if (allq) printf("Query #%lu: %s\n", (unsigned long)qi, qname);
     for (size_t i = 0; i < db.n; i++) {
@@ -499,19 +509,32 @@ next_query:
             printf("%d\t%u\t%s\n", hits[i].score, hits[i].index, packed ? "" : db.names + db.name_off[hits[i].index]);
     }
     if (align && n_hits > 0) {
-        const size_t stride = grp ? swg_group_align_ops_bound(grp) : swg_align_ops_bound(ctx, pdb);
-        swg_alignment *al = (swg_alignment *)calloc(n_hits, sizeof *al);
-        char *ops = (char *)malloc(n_hits * stride);
-        char *line = (char *)malloc(stride);
-        if (!al || !ops || !line) return leave(EXIT_FAILURE);
-        if ((grp ? swg_group_align_hits(grp, hits, n_hits, al, ops, stride)
-                 : swg_align_hits(ctx, pdb, hits, n_hits, al, ops, stride)) != SWG_OK) {
-            fprintf(stderr, "Error: %s\n", grp ? swg_group_last_error(grp) : swg_last_error(ctx));
+        /* the first record against the context's query; the others were aligned with their chunk (below) */
+        size_t stride = al_stride;
+        swg_alignment *al = NULL;
+        char *ops = NULL;
+        if (qi > 0 && al_failed) {
+            fprintf(stderr, "Error: %s\n", al_err);
             return leave(EXIT_FAILURE);
         }
+        if (qi == 0) {
+            stride = grp ? swg_group_align_ops_bound(grp) : swg_align_ops_bound(ctx, pdb);
+            al = (swg_alignment *)calloc(n_hits, sizeof *al);
+            ops = (char *)malloc(n_hits * stride);
+            if (!al || !ops) return leave(EXIT_FAILURE);
+            if ((grp ? swg_group_align_hits(grp, hits, n_hits, al, ops, stride)
+                     : swg_align_hits(ctx, pdb, hits, n_hits, al, ops, stride)) != SWG_OK) {
+                fprintf(stderr, "Error: %s\n", grp ? swg_group_last_error(grp) : swg_last_error(ctx));
+                return leave(EXIT_FAILURE);
+            }
+        }
+        const swg_alignment *al_q = al ? al : mq_al + (qi - al_first) * (size_t)topk;
+        const char *ops_q = ops ? ops : mq_ops + (qi - al_first) * (size_t)topk * stride;
+        char *line = (char *)malloc(stride);
+        if (!line) return leave(EXIT_FAILURE);
         for (size_t i = 0; i < n_hits; i++) {
-            const swg_alignment *a = &al[i];
-            const char *o = ops + i * stride;
+            const swg_alignment *a = &al_q[i];
+            const char *o = ops_q + i * stride;
             printf("Alignment #%lu: entry %u score %d query %u..%u entry %u..%u\n", (unsigned long)i, a->index,
                    a->score, a->q_begin, a->q_end, a->d_begin, a->d_end);
             if (packed) { /* no letters in a packed database: the path itself */
@@ -594,17 +617,50 @@ next_query:
         memcpy(scores, mq_scores + at * (db.n ? db.n : 1), db.n * sizeof(int32_t));
         n_hits = mq_nhits[at];
         memcpy(hits, mq_hits + at * (topk ? (size_t)topk : 1), n_hits * sizeof(swg_hit));
-        const size_t lq_at = (size_t)(qoff[at + 1] - qoff[at]);
-        if (align && (plist ? swg_set_query_pssm(ctx, plist + (size_t)q.seq_off[qi] * 32, lq_at) : swg_set_query(ctx, qx + qoff[at], lq_at)) !=
-                         SWG_OK) {
-            /* (the alignments of the hits are made against the context's query: the record's PSSM with --pssmlist) */
-            fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
-            return leave(EXIT_FAILURE);
+        if (align && qi >= al_first + al_n) {
+            /* The alignments of the chunk's hits from this query on, in one swg_align_hits_multi call (with --pssmlist
+             * swg_align_hits_multi_pssm: each record against its own PSSM).  A call takes at most 2^20 hits, and its
+             * paths are kept to about 256 MB, so a chunk past either is aligned in several calls. */
+            const size_t left = chunk_first + chunk_n - qi, kk = (size_t)topk;
+            al_first = qi;
+            al_stride = swg_align_ops_bound_multi(pdb, qoff + at, left);
+            size_t per = ((size_t)256 << 20) / (kk * al_stride);
+            if (per > ((size_t)1 << 20) / kk) per = ((size_t)1 << 20) / kk;
+            if (per < 1 || al_one_by_one) per = 1;
+            al_n = left < per ? left : per;
+            free(mq_al);
+            free(mq_ops);
+            mq_al = (swg_alignment *)calloc(al_n * kk, sizeof *mq_al);
+            mq_ops = (char *)malloc(al_n * kk * al_stride);
+            if (!mq_al || !mq_ops) {
+                fprintf(stderr, "Error: out of memory\n");
+                return leave(EXIT_FAILURE);
+            }
+            for (;;) {
+                const double t0 = now_ms();
+                const int rc = plist ? swg_align_hits_multi_pssm(ctx, pdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff + at,
+                                                                 al_n, mq_hits + at * kk, kk, mq_nhits + at, mq_al, mq_ops, al_stride)
+                                     : swg_align_hits_multi(ctx, pdb, qx, qoff + at, al_n, mq_hits + at * kk, kk, mq_nhits + at,
+                                                            mq_al, mq_ops, al_stride);
+                al_ms += now_ms() - t0, ++al_calls;
+                if (rc == SWG_OK) break;
+                if (al_n == 1) {
+                    snprintf(al_err, sizeof al_err, "%s", swg_last_error(ctx));
+                    al_failed = 1;
+                    break;
+                }
+                /* a record of this call cannot be aligned: the records before it still print first */
+                al_one_by_one = 1, al_n = 1;
+            }
+            al_records += al_n;
         }
         total_ms = chunk_ms;
         qname = q.names + q.name_off[qi];
         goto next_query;
     }
+    if (timing && al_calls)
+        fprintf(stderr, "[timing] %lu records aligned in %lu calls: %.3f ms\n", (unsigned long)al_records,
+                (unsigned long)al_calls, al_ms);
     fflush(stdout);
     phase("print");
     /* The run is over and its output is out: the process ends here, without walking the runtime's teardown (streams,
@@ -625,6 +681,8 @@ next_query:
     free(didx);
     free(scores);
     free(hits);
+    free(mq_al);
+    free(mq_ops);
     phase("release (context, buffers)");
     return leave(EXIT_SUCCESS);
 }
