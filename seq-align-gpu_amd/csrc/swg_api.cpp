@@ -1003,7 +1003,10 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
             // token blocks span more than SWG_DYN_SEG_BLOCKS go in several launches per pass, each over a
             // run of consecutive pairs (a segment).  Normally there is one, the whole token buffer.
             std::vector<std::pair<uint32_t, uint32_t>> segs; // pair ranges
-            if (!edges || T.total_blocks <= ctx->opt_seg_blocks) {
+            // (cut: every launch addresses the buffer from its segment's origin -- also where this CLASS fits one
+            // segment and only the whole buffer does not: the bulk behind a long class begins far from block 0)
+            const bool cut = edges && T.total_blocks > ctx->opt_seg_blocks;
+            if (!cut) {
                 segs.push_back(std::make_pair(q.q_begin, q.q_end));
                 q.seg_origin = 0;
                 q.seg_blocks = (uint32_t)std::min<uint64_t>(T.total_blocks, ctx->opt_seg_blocks);
@@ -1049,7 +1052,7 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
                         first_launch = false;
                         q.q_begin = b;
                         q.q_end = en;
-                        if (segs.size() > 1) {
+                        if (cut) {
                             q.seg_origin = T.pair_blocks_prefix[sg.first];
                             q.seg_blocks = T.pair_blocks_prefix[sg.second] - q.seg_origin;
                         }
@@ -1605,7 +1608,7 @@ static int launch_dyn_list(swg_ctx *ctx, swg_db *db, const SwgDiagPlan &pl, bool
             first_launch = false;
             q.q_begin = sg.first;
             q.q_end = sg.second;
-            if (segs.size() > 1) {
+            if (segs.size() > 1) { // (the list spans the whole buffer: cut into segments means more than one, unlike a class's)
                 q.seg_origin = T.pair_blocks_prefix[sg.first];
                 q.seg_blocks = T.pair_blocks_prefix[sg.second] - q.seg_origin;
             }

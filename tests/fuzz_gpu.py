@@ -1,14 +1,42 @@
 #!/usr/bin/env python3
 """Randomised parity soak: random databases (tiny to long-tailed), query lengths, scoring tables,
 gap scores and engine options through the C ABI, every score against the int32 oracle.
-usage: python tests/fuzz_gpu.py [seconds] [seed]"""
+scoring "edges": the tables and gap points of tests/scoring_edges.py (entries over all of int8, gap magnitudes at the
+hand-overs between cell forms) with split_db's relatives planted among the random sequences.
+usage: python tests/fuzz_gpu.py [seconds] [seed] [classic|edges]"""
 import sys, time, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import swg_loader
+import scoring_edges as se
 
-def main(budget=300.0, seed=1):
+def edge_case(rng, b62, q, seqs):
+    """scoring "edges": -> (table, gap_open, gap_extend, query, sequences).  diag127 (half of the draws) comes with a
+    query of two flanks and its relatives, so that the gap magnitude shows; the other tables keep the random query
+    and sequences (alphabet 1 .. 31) and take an edge gap point or a small one."""
+    p = se.GAP_POINTS[int(rng.integers(0, len(se.GAP_POINTS)))]
+    tname = "diag127" if rng.random() < 0.5 else str(rng.choice(se.TABLES[1:]))
+    sub = se.table(tname, b62)
+    go, ge = p["go"], p["ge"]
+    if tname == "diag127":
+        q, flat, off, _ = se.split_db(p["g"], int(rng.integers(11, 40)), rng)
+        rel = se.seqs_of(flat, off)
+        seqs = [s for s in seqs if len(s) <= 4 * len(q)][:400] + rel
+        order = rng.permutation(len(seqs))
+        seqs = [seqs[i] for i in order]
+    else:
+        if rng.random() < 0.5:
+            go, ge = [(-2, -1), (-11, -1), (0, -1), (-3, 0)][int(rng.integers(0, 4))]
+        q = rng.integers(1, 32, size=len(q)).astype(np.int8)
+        seqs = [rng.integers(1, 32, size=len(s)).astype(np.int8) for s in seqs]
+        for i in rng.integers(0, len(seqs), size=min(5, len(seqs))):
+            m = min(len(seqs[i]), len(q)); seqs[i][:m] = q[:m]
+    return sub, go, ge, q, seqs
+
+def main(budget=300.0, seed=1, scoring="classic"):
     swg = swg_loader.load(); orc = swg_loader.oracle()
+    assert scoring in ("classic", "edges")
     rng = np.random.default_rng(seed)
     ctx = swg.Context(0)
     mats = ["BLOSUM62", "PAM250", "BLOSUM45"]
@@ -51,9 +79,15 @@ def main(budget=300.0, seed=1):
         if rng.random() < 0.3 and lq > 50:   # plant similar sequences
             for i in rng.integers(0, len(seqs), size=min(5, len(seqs))):
                 L = len(seqs[i]); m = min(L, lq); seqs[i][:m] = q[:m]
+        tab = sc.table()
+        if scoring == "edges":
+            tab, go, ge, q, seqs = edge_case(rng, swg.load_scoring("BLOSUM62").table(), q, seqs)
+            lens = [len(s_) for s_ in seqs]; lq = len(q); n = len(seqs)
+            if sum(lens) * lq > 6e9:
+                continue
         flat = np.concatenate(seqs); off = np.zeros(len(lens) + 1, dtype=np.uint64); off[1:] = np.cumsum(lens)
-        want = orc.score_db(q, flat, off, sc.table(), go, ge)
-        ctx.set_scoring(sc, go, ge); ctx.set_query(q)
+        want = orc.score_db(q, flat, off, tab, go, ge)
+        ctx.set_scoring(tab, go, ge); ctx.set_query(q)
         for k in ("force_bits", "engine", "cols_per_wave", "max_waves", "group_lanes", "long_split", "workgroups", "segment_blocks"):
             ctx.set_option(k, 0)
         for k in ("work_queue", "wide16", "autotune", "side_readout", "f16", "last_pass"):
@@ -110,4 +144,5 @@ def main(budget=300.0, seed=1):
     return 0
 
 if __name__ == "__main__":
-    sys.exit(main(float(sys.argv[1]) if len(sys.argv) > 1 else 300.0, int(sys.argv[2]) if len(sys.argv) > 2 else 1))
+    sys.exit(main(float(sys.argv[1]) if len(sys.argv) > 1 else 300.0, int(sys.argv[2]) if len(sys.argv) > 2 else 1,
+                  sys.argv[3] if len(sys.argv) > 3 else "classic"))

@@ -4,15 +4,42 @@ sizes and query lengths (equal, mixed, some beyond one pass, some high-scoring r
 tables, gap scores, cell forms (option f16 0 / 1 / 2), two queries per lane on or off (option qq), with and without
 the score array (hits only: the batch's top-K selected on the device).  Every score against the int32 oracle, every
 hit list against the oracle's order.
-usage: python tests/fuzz_multi_gpu.py [seconds] [seed]"""
+scoring "edges": the tables and gap points of tests/scoring_edges.py, the first query one of two flanks with split_db's
+relatives planted among the random sequences.
+usage: python tests/fuzz_multi_gpu.py [seconds] [seed] [classic|edges]"""
 import sys, time, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import swg_loader
+import scoring_edges as se
 
 
-def main(budget=300.0, seed=1):
+def edge_case(rng, b62, queries, seqs):
+    """scoring "edges": -> (table, gap_open, gap_extend, queries, sequences).  diag127 (half of the draws): the first
+    query becomes one of two flanks, its relatives join the sequences; the other tables keep the random batch
+    (alphabet 1 .. 31).  Gap points: the 16-bit ones mostly (a batch in int32 goes one query after another)."""
+    pts = [p for p in se.GAP_POINTS if p["g"] <= 16000] if rng.random() < 0.8 else se.GAP_POINTS
+    p = pts[int(rng.integers(0, len(pts)))]
+    tname = "diag127" if rng.random() < 0.5 else str(rng.choice(se.TABLES[1:]))
+    sub = se.table(tname, b62)
+    go, ge = p["go"], p["ge"]
+    if tname == "diag127":
+        q, flat, off, _ = se.split_db(p["g"], int(rng.integers(11, 40)), rng)
+        queries = [q] + queries[1:]
+        seqs = [s for s in seqs if len(s) <= 4 * len(q)][:300] + se.seqs_of(flat, off)
+        seqs = [seqs[i] for i in rng.permutation(len(seqs))]
+    else:
+        if rng.random() < 0.5:
+            go, ge = [(-2, -1), (-11, -1), (0, -1), (-3, 0)][int(rng.integers(0, 4))]
+        queries = [rng.integers(1, 32, size=len(x)).astype(np.int8) for x in queries]
+        seqs = [rng.integers(1, 32, size=len(x)).astype(np.int8) for x in seqs]
+    return sub, go, ge, queries, seqs
+
+
+def main(budget=300.0, seed=1, scoring="classic"):
     swg = swg_loader.load(); orc = swg_loader.oracle()
+    assert scoring in ("classic", "edges")
     rng = np.random.default_rng(seed)
     ctx = swg.Context(0)
     mats = ["BLOSUM62", "PAM250", "BLOSUM45"]
@@ -51,8 +78,14 @@ def main(budget=300.0, seed=1):
                 qi, si = int(rng.integers(0, nq)), int(rng.integers(0, len(seqs)))
                 m = min(len(queries[qi]), len(seqs[si]))
                 seqs[si][:m] = queries[qi][:m]
+        tab = sc.table()
+        if scoring == "edges":
+            tab, go, ge, queries, seqs = edge_case(rng, swg.load_scoring("BLOSUM62").table(), queries, seqs)
+            lens = [len(s_) for s_ in seqs]; qlens = [len(q_) for q_ in queries]; n = len(seqs)
+            if sum(lens) * sum(qlens) > 4e9:
+                continue
         flat = np.concatenate(seqs); off = np.zeros(len(lens) + 1, dtype=np.uint64); off[1:] = np.cumsum(lens)
-        ctx.set_scoring(sc, go, ge)
+        ctx.set_scoring(tab, go, ge)
         for k_ in ("force_bits", "engine", "cols_per_wave", "max_waves", "group_lanes", "long_split", "workgroups", "segment_blocks"):
             ctx.set_option(k_, 0)
         for k_ in ("work_queue", "wide16", "autotune", "side_readout", "f16", "qq", "last_pass"):
@@ -72,7 +105,7 @@ def main(budget=300.0, seed=1):
         want_scores = bool(rng.random() < 0.6) or k == 0
         got, hits, st = ctx.search_multi(db, queries, k=k, want_scores=want_scores)
         for i, q in enumerate(queries):
-            want = orc.score_db(q, flat, off, sc.table(), go, ge)
+            want = orc.score_db(q, flat, off, tab, go, ge)
             if want_scores and not np.array_equal(got[i], want):
                 bad = np.nonzero(got[i] != want)[0]
                 print("MISMATCH case", cases, "query", i, "of", nq, "lq", len(q), "n", n, "gaps", go, ge, "opts", opts, "stats", st)
@@ -94,4 +127,5 @@ def main(budget=300.0, seed=1):
 
 
 if __name__ == "__main__":
-    sys.exit(main(float(sys.argv[1]) if len(sys.argv) > 1 else 300.0, int(sys.argv[2]) if len(sys.argv) > 2 else 1))
+    sys.exit(main(float(sys.argv[1]) if len(sys.argv) > 1 else 300.0, int(sys.argv[2]) if len(sys.argv) > 2 else 1,
+                  sys.argv[3] if len(sys.argv) > 3 else "classic"))

@@ -25,6 +25,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import scoring_edges  # noqa: E402
 import swg_loader  # noqa: E402
 
 orc = swg_loader.oracle()
@@ -159,8 +161,39 @@ def f16_boundary_cases():
         emit(name, sub, go, ge, q, flat, offsets, np.full(6, 16, dtype=np.int32))
 
 
+def gap_edge_cases():
+    """Gap magnitudes at the hand-overs between cell forms (tests/scoring_edges.py): 2047 / 2048 (the last of the f16
+    cells), 2049, 16000, 32767 (the last of the 16-bit cells) and 32768 (int32), with the table diag127 -- 127 on the
+    diagonal, -128 .. -100 elsewhere, row and column 0 zero -- and split_db's relatives of a query of two flanks, so
+    that best alignments go through a gap wherever one can pay below 32767.  48 records in batches of 16, the first of
+    each batch the longest.  The reference's lanes are int16: a record that would score more than 32767 is cut to its
+    first 258 residues (258 * 127 = 32766), so ref_valid = 1 throughout.  Residues 1 .. 26: the batches' filler is
+    index 31, which the query must not hold."""
+    sub = scoring_edges.diag127(zero0=True)
+    for name, go, ge in (("gapedge_2047_1", -2047, -1), ("gapedge_0_2048", 0, -2048), ("gapedge_2048_1", -2048, -1),
+                         ("gapedge_15999_1", -15999, -1), ("gapedge_32766_1", -32766, -1), ("gapedge_32767_1", -32767, -1)):
+        g = -(go + ge)
+        rng = np.random.default_rng([20261016, g, -ge])
+        q, flat, offsets, kinds = scoring_edges.split_db(g, 49, rng, hi=26)
+        seqs = scoring_edges.seqs_of(flat, offsets)[:48]
+        seqs = [s[:258] if orc.pair(q, s, sub, go, ge) > 32767 else s for s in seqs]
+        ordered = []
+        for b in range(0, 48, 16):
+            batch = seqs[b:b + 16]
+            longest = max(range(16), key=lambda i: len(batch[i]))
+            batch[0], batch[longest] = batch[longest], batch[0]
+            ordered += batch
+        flat = np.concatenate(ordered)
+        offsets = np.zeros(49, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(s) for s in ordered])
+        emit(name, sub, go, ge, q, flat, offsets, np.full(3, 16, dtype=np.int32))
+
+
 def main():
     assert orc.have_ref(), "build oracle/_ref first (make -C oracle)"
+    if "--gap-edges" in sys.argv:              # only the fixtures of the scoring-parameter edges
+        gap_edge_cases()
+        return
     if "--positive-gaps" in sys.argv:          # only the fixtures added in round 2 (the others stay byte for byte)
         positive_gap_cases()
         return
@@ -212,6 +245,7 @@ def main():
     emit("pam250_overflow_w", pam, -2, -1, q, flat, offsets, np.array([16], dtype=np.int32), ref_valid=False)
     positive_gap_cases()
     f16_boundary_cases()
+    gap_edge_cases()
 
 
 if __name__ == "__main__":

@@ -44,7 +44,8 @@ def test_golden_both_pairings(swg, ctx, name):
     assert np.array_equal(s2, s1), (name, st2)
     assert h1 == h2
     assert st1["cell_form"] == st2["cell_form"] and st1["n_rescored"] == st2["n_rescored"], (st1, st2)
-    if go <= 0 and ge <= 0 and -go <= 2048 and -ge <= 2048:
+    # (the magnitude of a gap's first position is -(gap_open + gap_extend): gapedge_2048_1 is 2049 and takes int16 cells)
+    if go <= 0 and ge <= 0 and -(go + ge) <= 2048 and -ge <= 2048:
         assert st2["cell_form"] == 2 and st2["n_rescored"] == int((g["oracle32"] >= 4096).sum()), st2
 
 

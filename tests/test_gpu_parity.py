@@ -45,13 +45,17 @@ def test_golden_through_search(swg, ctx, name, engine, cells):
     g = load_golden(name)
     _setup(ctx, g)
     gaps_ok = g["gaps"][0] <= 0 and g["gaps"][1] <= 0
+    # the magnitudes of a gap's first and of every further position: the f16 cells take both up to 2048, the 16-bit
+    # cells a first position up to 32767 (the gapedge_* fixtures lie either side of both)
+    gap_first, gap_next = -int(g["gaps"][0] + g["gaps"][1]), -int(g["gaps"][1])
+    f16_ok = gaps_ok and gap_first <= 2048 and gap_next <= 2048
     ctx.set_option("engine", engine)         # 1 systolic, 2 diagonal (both arithmetic widths)
     ctx.set_option("f16", {"auto": 1, "int16": 0, "f16": 2}[cells])
     db = swg.Database(g["flat"], g["offsets"]).upload(ctx)
     scores, hits, st = ctx.search(db, k=10)
     ctx.set_option("f16", 1)
     assert np.array_equal(scores, _truth(g)), (name, st)
-    if engine == 1 and gaps_ok and cells != "int16":
+    if engine == 1 and f16_ok and cells != "int16":
         # the systolic engine takes the packed-f16 cells exactly where no score of the search can reach their ceiling
         # (it has no flag-and-re-run route): longest sequence x largest table entry, or the query's best total
         lens = np.diff(g["offsets"].astype(np.int64))
@@ -59,7 +63,7 @@ def test_golden_through_search(swg, ctx, name, engine, cells):
                     min(len(g["query"]), (int(lens.max()) + 3) // 4 * 4) * int(g["sub"].max()))
         assert st["cell_form"] == (2 if bound < 4096 else 0), (bound, st)
         assert bound >= 4096 or st["n_rescored"] == 0
-    elif cells == "int16" or engine == 1 or not gaps_ok:
+    elif cells == "int16" or engine == 1 or not f16_ok:
         assert st["cell_form"] in (0, 1)
     elif cells == "f16":
         assert st["cell_form"] == 2 and st["n_rescored"] == int((_truth(g) >= 4096).sum()), st
@@ -67,7 +71,7 @@ def test_golden_through_search(swg, ctx, name, engine, cells):
         assert np.array_equal(scores, g["ref16"].astype(np.int32))
     best = sorted(((-int(s), i) for i, s in enumerate(_truth(g))))[:10]
     assert hits == [(-s, i) for s, i in best]
-    assert st["path_bits"] == (16 if gaps_ok else 32)
+    assert st["path_bits"] == (16 if gaps_ok and gap_first <= 32767 else 32)
     assert st["engine"] == engine
     assert st["cells"] == len(g["query"]) * len(g["flat"])
     db.close()
@@ -89,7 +93,9 @@ def test_golden_forced_int32(swg, ctx, name, engine):
 
 @pytest.mark.parametrize("name", ["pam250_lq128", "blosum62_lq367", "pam250_partial_lanes",
                                   "blosum62_gap_0_1", "blosum62_gap_pos1_m3", "blosum62_query_bzx",
-                                  "blosum62_gap_pos5_m1", "blosum62_gap_0_pos1"])
+                                  "blosum62_gap_pos5_m1", "blosum62_gap_0_pos1",
+                                  "gapedge_2047_1", "gapedge_0_2048", "gapedge_2048_1", "gapedge_15999_1",
+                                  "gapedge_32766_1", "gapedge_32767_1"])
 @pytest.mark.parametrize("route", ["device", "host"])
 def test_golden_through_reference_shaped_batches(swg, ctx, orc, name, route):
     """swg_fill_batches16 replays exactly what alignment_fill_matrices receives.  route "device": the batches are
@@ -1091,6 +1097,22 @@ def test_randomised_soak_of_query_batches():
     fuzz = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(fuzz)
     assert fuzz.main(20.0, 3) == 0
+
+
+def test_randomised_soak_of_scoring_edges():
+    """Both fuzzers with scoring "edges" for twenty seconds each: the tables of tests/scoring_edges.py (entries over all
+    of int8, garbage in row and column 0) and its gap points (magnitudes 2047 .. 65536, either side of every hand-over
+    between cell forms), split_db's relatives planted among the random sequences, under the same random options.
+    How many cases twenty seconds reach depends on the machine: a finding of the soak is pinned by a test of its own
+    (test_gpu_scoring_edges.test_bulk_behind_a_long_class_in_one_segment is one), not by this one."""
+    import importlib.util
+    import os
+    from conftest import ROOT
+    for name, seed in (("fuzz_gpu", 11), ("fuzz_multi_gpu", 3)):
+        spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", name + ".py"))
+        fuzz = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(fuzz)
+        assert fuzz.main(20.0, seed, scoring="edges") == 0, name
 
 
 def _db_with_empties(swg, seed, n, n_empty, max_len):
