@@ -536,7 +536,7 @@ static int ensure_bins(swg_ctx *ctx, swg_db *db)
 {
     if (db->d_packed || db->n_bins == 0) return SWG_OK;
     if (db->tokens_only)
-        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "this search needs the bin image, which a database built from 16-lane batches does not have");
+        return swg_set_ctx_error(ctx, SWG_TAKE_HOST_ROUTE, "this search needs the bin image, which a database built from 16-lane batches does not have");
     const size_t nb = db->n_bins;
     const uint64_t dwords = db->bin_off[nb - 1] + (uint64_t)db->bin_nblk[nb - 1] * SWG_BIN;
     HIP_TRY(ctx, hipMalloc(&db->d_bin_off, nb * 8));
@@ -558,23 +558,18 @@ static int ensure_bins(swg_ctx *ctx, swg_db *db)
 // ---------------------------------------------------------------------------
 // planning
 // ---------------------------------------------------------------------------
-struct Plan {
-    int bits, variant, K, W, npass, workgroups;
-    SwgKernelInfo info;
-    int f16; // systolic int16 plan on the packed-f16 cells (one pass, no score of the search can reach 4096)
-};
-
-static int make_plan(swg_ctx *ctx, int bits, uint32_t n_items, Plan *pl)
+// cols > 0: the instantiation with that many columns per wavefront (option cols_per_wave, or a measured / modelled choice)
+static int make_plan(swg_ctx *ctx, int bits, uint32_t n_items, long cols, SwgSystolicPlan *pl)
 {
     const int nv = swg_num_variants(bits);
     int variant = 0;
-    if (ctx->opt_cols > 0) {
+    if (cols > 0) {
         variant = -1;
         for (int v = 0; v < nv; ++v)
-            if (swg_variant_info(bits, v).K == (int)ctx->opt_cols) variant = v;
+            if (swg_variant_info(bits, v).K == (int)cols) variant = v;
         if (variant < 0)
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "cols_per_wave=%ld not built for the %d-bit path",
-                                     ctx->opt_cols, bits);
+                                     cols, bits);
     }
     const SwgKernelInfo info = swg_variant_info(bits, variant);
     int maxw = info.max_waves;
@@ -632,7 +627,7 @@ static int ensure_profile_cols(swg_ctx *ctx, int which, uint32_t ncols, int elem
     return SWG_OK;
 }
 
-static int ensure_profile(swg_ctx *ctx, const Plan &pl)
+static int ensure_profile(swg_ctx *ctx, const SwgSystolicPlan &pl)
 {
     return ensure_profile_cols(ctx, pl.bits == 16 ? 0 : 1, (uint32_t)(pl.npass * pl.W * pl.K), pl.info.elem_size,
                                ((uint64_t)pl.K << 20) ^ ((uint64_t)pl.W << 12) ^ (uint64_t)pl.npass, 1, 1, 4, 0, pl.bits == 16 && pl.f16);
@@ -843,6 +838,75 @@ static int ensure_scratch(swg_ctx *ctx, size_t dwords)
 // group of G: the layout depends on (K, G).  ([0] and [1] are the systolic engine's, in plain order.)
 static int diag_profile_slot(const SwgDiagPlan &, int cls) { return cls == 0 ? 3 : 2; }
 
+// The (M,B) edges of the rows between consecutive passes of the work-queue fill, ping-pong: allocated for the token
+// blocks of the database, and again when a re-filled database has grown.
+static int ensure_edges(swg_ctx *ctx, SwgPairTokens *T)
+{
+    if (T->d_edge[0] && T->edge_blocks >= T->total_blocks) return SWG_OK;
+    (void)hipFree(T->d_edge[0]);
+    (void)hipFree(T->d_edge[1]);
+    T->d_edge[0] = T->d_edge[1] = nullptr;
+    const size_t bytes = std::max<size_t>(8, (size_t)T->total_blocks * 4 * sizeof(uint2));
+    HIP_TRY(ctx, hipMalloc(&T->d_edge[0], bytes));
+    HIP_TRY(ctx, hipMalloc(&T->d_edge[1], bytes));
+    T->edge_blocks = T->total_blocks;
+    return SWG_OK;
+}
+
+// A gap magnitude as the cells of `form` take it, in both halves of a dword: an f16 integer (form 2) or 16 bits.
+static uint32_t gap_word(int form, int gap)
+{
+    const uint32_t m = (uint32_t)(-gap) & 0xFFFFu;
+    return form == 2 ? f16x2_of(-gap) : m | (m << 16);
+}
+
+// What every launch of the work-queue kernel (swg_diag_dyn_kernel) is told the same way: the pair tokens and their
+// offsets, the score array of n_slots entries and its pair limit, the lane-group width, the gap words of the cells
+// `form`, the turn levels (three beside a second class, else four) and the per-SIMD rank words.
+static SwgDiagDynParams dyn_params_base(const SwgPairTokens &T, int32_t *scores, size_t n_slots, int G, int form, int go, int ge,
+                                        int n_classes, uint32_t *simd_ranks)
+{
+    SwgDiagDynParams q;
+    memset(&q, 0, sizeof q);
+    q.tok = T.d_tok;
+    q.zero_block = (uint32_t)T.total_blocks;
+    q.pair_off = T.d_pair_off;
+    q.scores = scores;
+    q.pair_limit = (uint32_t)(n_slots / 2);
+    q.G = (uint32_t)G;
+    q.go = gap_word(form, go);
+    q.ge = gap_word(form, ge);
+    q.turn_levels = n_classes == 2 ? 3u : 4u;
+    q.simd_ranks = simd_ranks;
+    return q;
+}
+
+// The launches of one pass over the pairs [begin, end).  The form with edges addresses a launch's tokens and edges by
+// 32-bit offsets: where the token buffer spans more than seg_blocks, the pairs go in several launches per pass, each
+// over a run of consecutive pairs (a segment) and addressing the buffer from its segment's origin (*cut) -- also where
+// this range fits one segment and only the whole buffer does not: the bulk behind a long class begins far from block 0.
+// Normally there is one run, the whole range.  False: one pair alone is beyond a segment.
+static bool token_segments(const SwgPairTokens &T, uint32_t begin, uint32_t end, uint32_t seg_blocks, bool edges,
+                           std::vector<std::pair<uint32_t, uint32_t>> *segs, bool *cut)
+{
+    segs->clear();
+    *cut = edges && T.total_blocks > seg_blocks;
+    if (!*cut) {
+        segs->push_back(std::make_pair(begin, end));
+        return true;
+    }
+    const std::vector<uint32_t> &pre = T.pair_blocks_prefix;
+    for (uint32_t b = begin; b < end;) {
+        const uint64_t limit = (uint64_t)pre[b] + seg_blocks;
+        const uint32_t e = (uint32_t)(std::upper_bound(pre.begin() + b, pre.begin() + end + 1, limit,
+                                                       [](uint64_t v, uint32_t x) { return v < (uint64_t)x; }) - pre.begin()) - 1u;
+        if (e <= b) return false;
+        segs->push_back(std::make_pair(b, e));
+        b = e;
+    }
+    return true;
+}
+
 static int prepare_diag(swg_ctx *ctx, swg_db *db, const SwgDiagWork &wk)
 {
     if (ctx->opt_dynamic) {
@@ -853,17 +917,12 @@ static int prepare_diag(swg_ctx *ctx, swg_db *db, const SwgDiagWork &wk)
         const SwgDiagPlan &pl = wk.plan[c];
         if (!diag_class_is_dynamic(ctx, db, pl)) {
             if (db->tokens_only)
-                return swg_set_ctx_error(ctx, SWG_ERR_STATE, "this search needs fixed streams, which a database built from 16-lane batches does not have");
+                return swg_set_ctx_error(ctx, SWG_TAKE_HOST_ROUTE, "this search needs fixed streams, which a database built from 16-lane batches does not have");
             int rc = ensure_diag_layout(ctx, db, c, pl, wk.pair_begin[c], wk.pair_end[c]);
             if (rc != SWG_OK) return rc;
-        } else if (pl.npass > 1 && (!db->ptok.d_edge[0] || db->ptok.edge_blocks < db->ptok.total_blocks)) {
-            (void)hipFree(db->ptok.d_edge[0]);
-            (void)hipFree(db->ptok.d_edge[1]);
-            db->ptok.d_edge[0] = db->ptok.d_edge[1] = nullptr;
-            const size_t bytes = std::max<size_t>(8, (size_t)db->ptok.total_blocks * 4 * sizeof(uint2));
-            HIP_TRY(ctx, hipMalloc(&db->ptok.d_edge[0], bytes));
-            HIP_TRY(ctx, hipMalloc(&db->ptok.d_edge[1], bytes));
-            db->ptok.edge_blocks = db->ptok.total_blocks;
+        } else if (pl.npass > 1) {
+            int rc = ensure_edges(ctx, &db->ptok);
+            if (rc != SWG_OK) return rc;
         }
         // (the f16 cells with the fma pairing: (score, 1.0) dwords in 2-column chunks, K padded to 2 columns)
         const bool fma = diag_class_fma(ctx, db, pl);
@@ -932,7 +991,6 @@ static void dyn_batch_zones(const swg_ctx *ctx, const SwgPairTokens &T, SwgDiagD
 static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, int go, int ge, bool *two_ends)
 {
     hipStream_t s = ctx->stream;
-    const uint32_t g = (uint32_t)(-go) & 0xFFFFu, e = (uint32_t)(-ge) & 0xFFFFu;
     *two_ends = false;
     // diagnostics: SWG_TRACE=<file> dumps one line per wavefront (class, workgroup, wave, start and
     // end in 10 ns ticks, blocks of its longest stream) for every diagonal fill
@@ -957,21 +1015,13 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
         const SwgDiagPlan &pl = wk.plan[c];
         if (diag_class_is_dynamic(ctx, db, pl)) {
             const SwgPairTokens &T = db->ptok;
-            SwgDiagDynParams q;
-            memset(&q, 0, sizeof q);
-            q.tok = T.d_tok;
-            q.zero_block = (uint32_t)T.total_blocks;
-            q.pair_off = T.d_pair_off;
+            const int form = diag_class_form(ctx, db, pl);
+            SwgDiagDynParams q = dyn_params_base(T, db->d_scores, (size_t)db->n_bins * SWG_BIN, pl.G, form, go, ge, wk.n_classes,
+                                                 db->d_counters + SWG_RANK_WORD(c));
             q.q_begin = (uint32_t)wk.pair_begin[c];
             q.q_end = (uint32_t)wk.pair_end[c];
             q.queue = db->d_counters + SWG_QUEUE_WORD(c); // zeroed with the other counters before the fill
             q.profile = ctx->d_profile[diag_profile_slot(pl, c)];
-            q.scores = db->d_scores;
-            q.pair_limit = (uint32_t)(((size_t)db->n_bins * SWG_BIN) / 2);
-            q.G = (uint32_t)pl.G;
-            const int form = diag_class_form(ctx, db, pl);
-            q.go = form == 2 ? f16x2_of(-go) : g | (g << 16);
-            q.ge = form == 2 ? f16x2_of(-ge) : e | (e << 16);
             // the long class always runs at raised priority; in the bulk, a pair that alone is well
             // above an average lane group's whole share
             auto bulk_prio = [&]() -> uint32_t {
@@ -988,10 +1038,8 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
                 q.queue2 = db->d_counters + SWG_QUEUE_WORD(0);
                 q.prio_blocks2 = bulk_prio();
             }
-            q.turn_levels = wk.n_classes == 2 ? 3u : 4u;
-            q.simd_ranks = db->d_counters + SWG_RANK_WORD(c);
             // (f16 sums round to nearest: a computed 32768 needs a true score within a few units of it)
-            q.f16_wipe = ctx->cur->score_bound >= 32000ull ? 1u : 0u;
+            q.f16_wipe = ctx->cur->plan.score_bound >= 32000ull ? 1u : 0u;
             q.trace = d_trace[c];
             // start / end wall-clock stamps of single-pass launches: words 8..15 of the counters
             q.stamps = pl.npass == 1 ? reinterpret_cast<unsigned long long *>(db->d_counters + 8 + 4 * c) : nullptr;
@@ -999,32 +1047,17 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
             const bool fma = diag_class_fma(ctx, db, pl); // (never with a split: its f16 part takes the v_perm_b32 profile)
             const size_t slice = swg_diag_slice_bytes(pl.K, pl.G, fma);
             hipStream_t qs = c == 1 ? ctx->stream2 : s;
-            // The form with edges addresses a launch's tokens and edges by 32-bit offsets: pairs whose
-            // token blocks span more than SWG_DYN_SEG_BLOCKS go in several launches per pass, each over a
-            // run of consecutive pairs (a segment).  Normally there is one, the whole token buffer.
-            std::vector<std::pair<uint32_t, uint32_t>> segs; // pair ranges
-            // (cut: every launch addresses the buffer from its segment's origin -- also where this CLASS fits one
-            // segment and only the whole buffer does not: the bulk behind a long class begins far from block 0)
-            const bool cut = edges && T.total_blocks > ctx->opt_seg_blocks;
-            if (!cut) {
-                segs.push_back(std::make_pair(q.q_begin, q.q_end));
-                q.seg_origin = 0;
-                q.seg_blocks = (uint32_t)std::min<uint64_t>(T.total_blocks, ctx->opt_seg_blocks);
-            } else {
-                const std::vector<uint32_t> &pre = T.pair_blocks_prefix;
-                for (uint32_t b = q.q_begin; b < q.q_end;) {
-                    const uint64_t limit = (uint64_t)pre[b] + ctx->opt_seg_blocks;
-                    const uint32_t e = (uint32_t)(std::upper_bound(pre.begin() + b, pre.begin() + q.q_end + 1, limit,
-                                                                   [](uint64_t v, uint32_t x) { return v < (uint64_t)x; }) -
-                                                  pre.begin()) - 1u;
-                    if (e <= b) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "a pair of sequences too long for the multi-pass fill");
-                    segs.push_back(std::make_pair(b, e));
-                    b = e;
-                }
+            std::vector<std::pair<uint32_t, uint32_t>> segs; // pair ranges (token_segments)
+            bool cut = false;
+            if (!token_segments(T, q.q_begin, q.q_end, ctx->opt_seg_blocks, edges, &segs, &cut))
+                return swg_set_ctx_error(ctx, SWG_ERR_ARG, "a pair of sequences too long for the multi-pass fill");
+            q.seg_origin = 0;
+            q.seg_blocks = (uint32_t)std::min<uint64_t>(T.total_blocks, ctx->opt_seg_blocks);
+            if (cut) {
                 q.q2_begin = q.q2_end = 0; // (the other class's pairs lie outside a segment)
                 q.queue2 = nullptr;
             }
-            // Both 16-bit forms in one class (pl.f16_from, see swg_search_begin): the pairs before it -- the longest --
+            // Both 16-bit forms in one class (pl.f16_from, see plan_search): the pairs before it -- the longest --
             // take all their passes on the wide form, then the rest theirs on the f16 cells, the same geometry
             // throughout; ev[5] between the two parts tells their times apart.
             const uint32_t class_begin = q.q_begin, class_end = q.q_end;
@@ -1036,8 +1069,8 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
                 const uint32_t part_begin = split && part == 1 ? pl.f16_from : class_begin;
                 const uint32_t part_end = split && part == 0 ? pl.f16_from : class_end;
                 const uint8_t *prof = ctx->d_profile[split && part == 1 ? 7 : diag_profile_slot(pl, c)];
-                q.go = pform == 2 ? f16x2_of(-go) : g | (g << 16);
-                q.ge = pform == 2 ? f16x2_of(-ge) : e | (e << 16);
+                q.go = gap_word(pform, go);
+                q.ge = gap_word(pform, ge);
                 if (split && part == 1) HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[5], qs));
                 for (int pass = 0; pass < pl.npass; ++pass) {
                     // one launch per pass: the kernel boundary is what lets any lane group take any pair
@@ -1081,8 +1114,8 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
         d.scratch = L.d_scratch;
         d.npass = (uint32_t)pl.npass;
         d.G = (uint32_t)pl.G;
-        d.go = g | (g << 16);
-        d.ge = e | (e << 16);
+        d.go = gap_word(0, go);
+        d.ge = gap_word(0, ge);
         // wavefronts on the critical path get issue priority over the ones they share a SIMD
         // with: all of the long class; in the bulk, streams that hold little more than one very
         // long pair
@@ -1136,10 +1169,9 @@ static int diag_fill_ms(swg_ctx *ctx, bool two_ends, double *out)
     return SWG_OK;
 }
 
-// Launches the systolic int16/int32 fill of one plan over the whole database (events ev[1], ev[2]).
-static int launch_systolic(swg_ctx *ctx, const swg_db *db, const Plan &pl, int go, int ge)
+// What every bin-based launch (systolic fill, int32 kernels) is told the same way: the bin image, the scores, the scratch.
+static SwgFillParams fill_params_base(const swg_ctx *ctx, const swg_db *db)
 {
-    hipStream_t s = ctx->stream;
     SwgFillParams p;
     memset(&p, 0, sizeof p);
     p.residues = db->d_packed;
@@ -1148,6 +1180,14 @@ static int launch_systolic(swg_ctx *ctx, const swg_db *db, const Plan &pl, int g
     p.n_bins = db->n_bins;
     p.scores = db->d_scores;
     p.scratch = ctx->d_scratch;
+    return p;
+}
+
+// Launches the systolic int16/int32 fill of one plan over the whole database (events ev[1], ev[2]).
+static int launch_systolic(swg_ctx *ctx, const swg_db *db, const SwgSystolicPlan &pl, int go, int ge)
+{
+    hipStream_t s = ctx->stream;
+    SwgFillParams p = fill_params_base(ctx, db);
     p.profile = ctx->d_profile[pl.bits == 16 ? 0 : 1];
     p.queue = db->d_counters + 0;
     p.n_items = pl.bits == 16 ? db->n_bins : db->n_bins * 2;
@@ -1170,9 +1210,9 @@ static int launch_systolic(swg_ctx *ctx, const swg_db *db, const Plan &pl, int g
     return SWG_OK;
 }
 
-static int prepare_systolic(swg_ctx *ctx, const swg_db *db, const Plan &pl)
+static int prepare_systolic(swg_ctx *ctx, swg_db *db, const SwgSystolicPlan &pl)
 {
-    int rc = ensure_bins(ctx, const_cast<swg_db *>(db));
+    int rc = ensure_bins(ctx, db);
     if (rc != SWG_OK) return rc;
     if ((rc = ensure_profile(ctx, pl)) != SWG_OK) return rc;
     const size_t need = pl.npass > 1 ? (size_t)pl.workgroups * db->max_nblk * SWG_ROWS_PER_BLK * 64 * pl.info.nb : 0;
@@ -1245,6 +1285,21 @@ static bool q32_plan_fits(const SwgDiagWork &wk, size_t lq)
     return true;
 }
 
+// One class of one geometry for the int32 work-queue kernel (workgroups of four wavefronts) over the pairs [0, n_pairs);
+// a list's plan has no pair range.
+static SwgDiagWork q32_one_class(int variant, int K, int G, size_t npass, uint64_t n_pairs = 0)
+{
+    SwgDiagWork wk;
+    wk.n_classes = 1;
+    wk.plan[0].variant = variant;
+    wk.plan[0].K = K;
+    wk.plan[0].G = G;
+    wk.plan[0].W = 4;
+    wk.plan[0].npass = (int)npass;
+    wk.pair_end[0] = n_pairs;
+    return wk;
+}
+
 // Geometry for a list of `n_items` flagged sequences (or, with a plan the int16 planner's choice does not
 // fit, the whole database): few items get 64 lanes each (the shortest chain per row), many the narrowest
 // lane group that covers the query in one pass.  A query no single pass holds (LDS: G*K int32 columns of
@@ -1253,15 +1308,6 @@ static bool q32_list_plan(const swg_ctx *ctx, size_t lq, uint32_t n_items, SwgDi
 {
     const bool few = n_items <= 8u * (uint32_t)ctx->n_cu;
     const int order[3] = {few ? 64 : 16, 32, few ? 16 : 64};
-    auto set = [&](int v, int K, int G, int npass) {
-        *wk = SwgDiagWork();
-        wk->n_classes = 1;
-        wk->plan[0].variant = v;
-        wk->plan[0].K = K;
-        wk->plan[0].G = G;
-        wk->plan[0].W = 4;
-        wk->plan[0].npass = npass;
-    };
     for (int gi = 0; gi < 3; ++gi) {
         const int G = order[gi];
         int best = -1, bestK = 1 << 30;
@@ -1273,7 +1319,7 @@ static bool q32_list_plan(const swg_ctx *ctx, size_t lq, uint32_t n_items, SwgDi
             }
         }
         if (best >= 0) {
-            set(best, bestK, G, 1);
+            *wk = q32_one_class(best, bestK, G, 1);
             return true;
         }
     }
@@ -1299,7 +1345,7 @@ static bool q32_list_plan(const swg_ctx *ctx, size_t lq, uint32_t n_items, SwgDi
             bestK = K;
         }
     }
-    set(best, bestK, G, (int)npass);
+    *wk = q32_one_class(best, bestK, G, npass);
     return true;
 }
 
@@ -1308,17 +1354,7 @@ static bool q32_list_plan(const swg_ctx *ctx, size_t lq, uint32_t n_items, SwgDi
 // group_lanes are honoured where they fit), else several passes of 64 lanes.
 static bool x32_plan(const swg_ctx *ctx, const swg_db *db, size_t lq, SwgDiagWork *wk)
 {
-    auto set = [&](int v, int K, int G, size_t npass) {
-        *wk = SwgDiagWork();
-        wk->n_classes = 1;
-        wk->plan[0].variant = v;
-        wk->plan[0].K = K;
-        wk->plan[0].G = G;
-        wk->plan[0].W = 4;
-        wk->plan[0].npass = (int)npass;
-        wk->pair_begin[0] = 0;
-        wk->pair_end[0] = swg_db_pair_count(db);
-    };
+    auto set = [&](int v, int K, int G, size_t npass) { *wk = q32_one_class(v, K, G, npass, swg_db_pair_count(db)); };
     auto fits = [&](int K, int G) { return K <= SWG_X32_MAX_K && swg_diag32q_lds_bytes(K, G, 4) <= 160 * 1024; };
     if (ctx->opt_cols > 0 && ctx->opt_group > 0) {
         for (int v = 0; v < swg_num_diag_variants(); ++v) {
@@ -1363,12 +1399,12 @@ static bool x32_plan(const swg_ctx *ctx, const swg_db *db, size_t lq, SwgDiagWor
 // Launches the int32 work-queue fill: every sequence of the plan's classes (list == NULL), or the
 // device-side list of ranks with one class.  A plan of several passes (one class) is one launch per
 // pass, the rows' edges going from launch to launch through memory.  Events as launch_diag.
-static int launch_q32(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, int go, int ge, const uint32_t *d_list,
+static int launch_q32(swg_ctx *ctx, swg_db *db, const SwgDiagWork &wk, int go, int ge, const uint32_t *d_list,
                       const uint32_t *d_list_count, uint32_t list_items, uint32_t *queue_words, bool *two_ends,
                       bool timing_events = true, bool exact = false)
 {
     hipStream_t s = ctx->stream;
-    SwgPairTokens &T = const_cast<swg_db *>(db)->ptok;
+    SwgPairTokens &T = db->ptok;
     const size_t n_slots = (size_t)db->n_bins * SWG_BIN;
     *two_ends = false;
     const int npass = wk.plan[0].npass;
@@ -1544,59 +1580,30 @@ static int launch_dyn_list(swg_ctx *ctx, swg_db *db, const SwgDiagPlan &pl, bool
     SwgPairTokens &T = db->ptok;
     const int form = wide ? 1 : 0;
     const bool edges = pl.npass > 1 || form == 1;
-    if (pl.npass > 1 && (!T.d_edge[0] || T.edge_blocks < T.total_blocks)) {
-        (void)hipFree(T.d_edge[0]);
-        (void)hipFree(T.d_edge[1]);
-        T.d_edge[0] = T.d_edge[1] = nullptr;
-        const size_t bytes = std::max<size_t>(8, (size_t)T.total_blocks * 4 * sizeof(uint2));
-        HIP_TRY(ctx, hipMalloc(&T.d_edge[0], bytes));
-        HIP_TRY(ctx, hipMalloc(&T.d_edge[1], bytes));
-        T.edge_blocks = T.total_blocks;
-    }
+    int rc = pl.npass > 1 ? ensure_edges(ctx, &T) : SWG_OK;
+    if (rc != SWG_OK) return rc;
     const int kp = swg_diag_padded_cols(pl.K);
     const uint32_t ncols = (uint32_t)(pl.npass * pl.G * kp);
-    int rc = ensure_profile_cols(ctx, 6, ncols, 2, (1ull << 52) | ((uint64_t)pl.K << 40) | ((uint64_t)pl.G << 32) | (uint64_t)ncols, pl.K, kp,
-                                 4, SWG_LDS_SWIZZLE ? pl.G : 0, 0);
+    rc = ensure_profile_cols(ctx, 6, ncols, 2, (1ull << 52) | ((uint64_t)pl.K << 40) | ((uint64_t)pl.G << 32) | (uint64_t)ncols, pl.K, kp,
+                             4, SWG_LDS_SWIZZLE ? pl.G : 0, 0);
     if (rc != SWG_OK) return rc;
-    const uint32_t g = (uint32_t)(-go) & 0xFFFFu, e = (uint32_t)(-ge) & 0xFFFFu;
-    SwgDiagDynParams q;
-    memset(&q, 0, sizeof q);
-    q.tok = T.d_tok;
-    q.zero_block = (uint32_t)T.total_blocks;
-    q.pair_off = T.d_pair_off;
+    SwgDiagDynParams q = dyn_params_base(T, db->d_scores, (size_t)db->n_bins * SWG_BIN, pl.G, form, go, ge, 1, db->d_counters + SWG_RANK_WORD(0));
     q.list = d_list;
     q.list_count = d_count;
     q.queue = db->d_counters + SWG_QUEUE_WORD(0);
-    q.scores = db->d_scores;
-    q.pair_limit = (uint32_t)(((size_t)db->n_bins * SWG_BIN) / 2);
-    q.G = (uint32_t)pl.G;
-    q.go = g | (g << 16);
-    q.ge = e | (e << 16);
     q.prio_blocks = 0xFFFFFFFFu;
     q.prio_blocks2 = 0xFFFFFFFFu;
-    q.turn_levels = 4u;
-    q.simd_ranks = db->d_counters + SWG_RANK_WORD(0);
     const SwgKernelInfo info = swg_diag_variant_info(pl.variant);
     const size_t lds = swg_diag_dyn_lds_bytes(pl.K, pl.G, pl.W);
     const int per_cu = std::max(1, std::min<int>(info.max_waves / pl.W, (int)((160 * 1024) / lds)));
     const int wgs = ctx->n_cu * std::min(per_cu, 3);
     const uint32_t n_pairs = (uint32_t)swg_db_pair_count(db);
-    std::vector<std::pair<uint32_t, uint32_t>> segs;
-    if (!edges || T.total_blocks <= ctx->opt_seg_blocks) {
-        segs.push_back(std::make_pair(0u, n_pairs));
-        q.seg_origin = 0;
-        q.seg_blocks = (uint32_t)std::min<uint64_t>(T.total_blocks, ctx->opt_seg_blocks);
-    } else {
-        const std::vector<uint32_t> &pre = T.pair_blocks_prefix;
-        for (uint32_t b = 0; b < n_pairs;) {
-            const uint64_t limit = (uint64_t)pre[b] + ctx->opt_seg_blocks;
-            const uint32_t en = (uint32_t)(std::upper_bound(pre.begin() + b, pre.begin() + n_pairs + 1, limit,
-                                                            [](uint64_t v, uint32_t x) { return v < (uint64_t)x; }) - pre.begin()) - 1u;
-            if (en <= b) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "a pair of sequences too long for the multi-pass fill");
-            segs.push_back(std::make_pair(b, en));
-            b = en;
-        }
-    }
+    std::vector<std::pair<uint32_t, uint32_t>> segs; // (the list spans the whole token buffer)
+    bool cut = false;
+    if (!token_segments(T, 0u, n_pairs, ctx->opt_seg_blocks, edges, &segs, &cut))
+        return swg_set_ctx_error(ctx, SWG_ERR_ARG, "a pair of sequences too long for the multi-pass fill");
+    q.seg_origin = 0;
+    q.seg_blocks = (uint32_t)std::min<uint64_t>(T.total_blocks, ctx->opt_seg_blocks);
     const size_t slice = (size_t)pl.G * kp * 64;
     bool first_launch = true;
     for (int pass = 0; pass < pl.npass; ++pass) {
@@ -1608,7 +1615,7 @@ static int launch_dyn_list(swg_ctx *ctx, swg_db *db, const SwgDiagPlan &pl, bool
             first_launch = false;
             q.q_begin = sg.first;
             q.q_end = sg.second;
-            if (segs.size() > 1) { // (the list spans the whole buffer: cut into segments means more than one, unlike a class's)
+            if (cut) {
                 q.seg_origin = T.pair_blocks_prefix[sg.first];
                 q.seg_blocks = T.pair_blocks_prefix[sg.second] - q.seg_origin;
             }
@@ -1728,13 +1735,9 @@ static int autotune_diag(swg_ctx *ctx, swg_db *db, size_t lq, int go, int ge, Sw
     // third stage: the systolic engine (less bookkeeping per row, coarse work units); it has not won
     // a measured case since the diagonal engine got its work queue and is only tried where a trial
     // is cheap
-    const long keep_cols = ctx->opt_cols;
     for (int v = 0; v < swg_num_variants(16) && tuned->ms < 100.0; ++v) {
-        Plan pl;
-        memset(&pl, 0, sizeof pl);
-        ctx->opt_cols = swg_variant_info(16, v).K;
-        int rc = make_plan(ctx, 16, db->n_bins, &pl);
-        ctx->opt_cols = keep_cols;
+        SwgSystolicPlan pl;
+        int rc = make_plan(ctx, 16, db->n_bins, swg_variant_info(16, v).K, &pl);
         if (rc != SWG_OK) continue;
         if ((rc = prepare_systolic(ctx, db, pl)) != SWG_OK) return rc;
         double ms_min = 1e300;
@@ -1795,190 +1798,164 @@ static int slot_scores(swg_ctx *ctx, SwgSlot *S, size_t n)
     return SWG_OK;
 }
 
-// Queues one whole search on the context's stream and returns without waiting (except on the
-// first search of a query length, which tunes the geometry, and when int16 scores may
-// saturate, where the number of flagged sequences is read back to size the re-score).
-static int search_begin(swg_ctx *ctx, const swg_db *db, bool want_scores, size_t k, SwgSlot *S)
+// ---------------------------------------------------------------------------
+// one search: what it decides (plan_search), then what it queues (the other stages of search_begin)
+// ---------------------------------------------------------------------------
+// The cost model's word on the ENGINE (round 4; until then only the autotuner could pick the systolic one, and it
+// is off for databases beyond 4 M sequences and wherever the caller turned it off): a database of short sequences
+// of near-equal length -- peptides -- is what the systolic engine is good at (no reset rows, no flags, nothing per
+// pair: 2 M peptides of 20-40 residues, lq 128: 6 570 GCUPS against the lane groups' 4 840, lq 30: 4 820 against
+// 1 930), and the two estimates tell: the lane groups' from the planner (plan0, on the cells `form`), the systolic one
+// from the bin table, for n_queries queries one after another (no batch form of that engine exists).  It has to win by
+// 15 % (both models are good to about 10 %).  bound: the largest score of the search(es), which decides the systolic
+// engine's cells; *sys_K: the columns per wavefront of its best instantiation.
+static bool systolic_beats_lane_groups(const swg_ctx *ctx, const swg_db *db, size_t lq, const SwgDiagPlan &plan0, int form,
+                                       uint64_t bound, size_t n_queries, int *sys_K)
 {
-    if (!ctx || !db) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_search: NULL argument");
-    if (!ctx->have_scoring) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search: no scoring set");
-    if (ctx->query_len() == 0) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search: no query set");
-    if (db->device != ctx->device || !db->d_codes)
-        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search: database is not resident on device %d",
-                                 ctx->device);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    {
-        const int rs = ensure_slot(ctx, S);
-        if (rs != SWG_OK) return rs;
+    *sys_K = 0;
+    if (ctx->opt_engine != 0 || ctx->opt_f16 == 2 || db->tokens_only || !(plan0.est_ms > 0.0)) return false;
+    const bool sys_f16 = ctx->opt_f16 != 0 && swg_f16_gaps_ok(ctx->gap_open + ctx->gap_extend, ctx->gap_extend) && bound < SWG_F16_CEILING;
+    const double sys_ms = swg_systolic_estimate_ms(db, lq, ctx->n_cu, sys_K, sys_f16) * (double)n_queries;
+    return *sys_K > 0 && sys_ms < SWG_SYSTOLIC_MARGIN * plan0.est_ms * swg_diag_short_pair_factor(db, plan0, form);
+}
+
+// One class of exactly (K = cols, G = group) over the whole database for the int32 work-queue kernel, a launch per pass,
+// if its int32 profile fits LDS (a forced geometry that needs several passes, or whose long class did not fit).
+static bool q32_forced_plan(const swg_db *db, size_t lq, long cols, long group, SwgDiagWork *wk)
+{
+    for (int v = 0; v < swg_num_diag_variants(); ++v) {
+        const int K = swg_diag_variant_info(v).K, G = (int)group;
+        if (K != (int)cols || swg_diag32q_lds_bytes(K, G, 4) > 160 * 1024) continue;
+        const size_t np = (lq + (size_t)G * K - 1) / ((size_t)G * K);
+        if (np > 64 || (np > 1 && db->ptok.total_blocks >= (1ull << 28))) continue;
+        *wk = q32_one_class(v, K, G, np, swg_db_pair_count(db));
+        return true;
     }
-    ctx->cur = S;
-    {
-        const int rb = select_bufs(ctx, const_cast<swg_db *>(db), (int)(S - ctx->slots));
-        if (rb != SWG_OK) return rb;
-    }
-    S->bufs = db->bufs[S - ctx->slots];
-    S->db = db;
-    S->k = k;
-    S->want_scores = want_scores;
-    swg_stats &st = S->st;
-    memset(&st, 0, sizeof st);
+    return false;
+}
+
+// Every decision of one search: arithmetic, cell forms and their hand-overs, engines and geometries.  It allocates no
+// profile, scratch or bin image and puts no launch on the search's own timeline; the only device work it may do is what
+// the decisions themselves read: the pair tokens of the database (ensure_pair_tokens, built once per database) and the
+// timed trials of the first search of a query length (autotune_diag, which end in a stream synchronisation).  *plan is
+// the slot's own plan: launch_diag reads its score_bound inside the tuner's trials, so the bound is written first.
+static int plan_search(swg_ctx *ctx, swg_db *db, bool allow_autotune, SwgSearchPlan *plan)
+{
+    *plan = SwgSearchPlan();
+    SwgSearchPlan &P = *plan;
+    SwgDiagWork &wk = P.wk, &wk32 = P.wk32;
     const size_t lq = ctx->query_len();
     const uint32_t n_bins = db->n_bins;
     const size_t n_slots = (size_t)n_bins * SWG_BIN;
-    st.cells = (uint64_t)lq * db->residues;
-    st.bytes_alg = db->residues + 8ull * db->n_local + 32ull * lq + 1024ull;
-    S->bits = 0; // marks "nothing queued" for an empty database
-    if (n_bins == 0) return SWG_OK;
+    P.epoch = ctx->epoch;
 
     // which arithmetic: the packed int16 form needs non-positive gap scores
-    const int go = ctx->gap_open + ctx->gap_extend, ge = ctx->gap_extend;
-    const bool fast_ok = ctx->gap_open <= 0 && ctx->gap_extend <= 0 && -go <= 32767;
-    int bits = fast_ok ? 16 : 32;
-    if (ctx->opt_force_bits == 32) bits = 32;
+    const int go = P.go = ctx->gap_open + ctx->gap_extend, ge = P.ge = ctx->gap_extend;
+    const bool fast_ok = P.fast_ok = ctx->gap_open <= 0 && ctx->gap_extend <= 0 && -go <= SWG_I16_CEILING;
+    const int bits = P.bits = fast_ok && ctx->opt_force_bits != 32 ? 16 : 32;
     if (ctx->opt_force_bits == 16 && !fast_ok)
         return swg_set_ctx_error(ctx, SWG_ERR_ARG,
                                  "force_bits=16 needs gap_open <= 0 and gap_extend <= 0");
 
-    // How high can a score get?  Not above the query's best possible total (every column paired
-    // with its best-scoring residue) nor above the longest sequence times the largest table entry.
-    // Below 32767 nothing can saturate; below 65535 the wide form of the diagonal engine (values
-    // biased by -32768, same instruction count) is exact and nothing needs the int32 re-score.  A PSSM query
-    // bounds the same way by its own rows: its largest entry, and the sum of each position's best entry.
-    int smax = 0;
-    uint64_t qbound = 0;
-    if (ctx->query_pssm) {
-        for (size_t i = 0; i < lq; ++i) {
-            int best = 0;
-            for (int b = 1; b < 32; ++b) best = std::max<int>(best, ctx->pssm[i * 32 + b]);
-            smax = std::max(smax, best);
-            qbound += (uint64_t)best;
-        }
-    } else {
-        for (int a = 0; a < 32; ++a)
-            for (int b = 0; b < 32; ++b) smax = std::max<int>(smax, ctx->sub[a][b]);
-        for (size_t i = 0; i < lq; ++i) {
-            int best = 0;
-            for (int b = 1; b < 32; ++b) best = std::max<int>(best, ctx->sub[(uint8_t)ctx->query[i] & 31][b]);
-            qbound += (uint64_t)best;
-        }
-    }
+    // How high can a score get (swg_score_bound)?  Below the int16 ceiling nothing can saturate; below the wide form's
+    // (values biased by -32768, same instruction count) that form is exact and nothing needs the int32 re-score.
     const uint64_t longest = (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK;
-    const uint64_t score_bound = std::min<uint64_t>(qbound, std::min<uint64_t>(lq, longest) * (uint64_t)smax);
-    S->score_bound = score_bound;
-    bool wide = bits == 16 && score_bound >= 32767ull && ctx->opt_engine != 1 && ctx->opt_wide != 0;
+    const SwgScoreBound sb = ctx->query_pssm ? swg_score_bound(ctx->pssm.data(), nullptr, lq, longest)
+                                             : swg_score_bound(&ctx->sub[0][0], ctx->query.data(), lq, longest);
+    const uint64_t score_bound = P.score_bound = sb.bound, qbound = P.qbound = sb.qbound;
+    const bool f16_gaps = ctx->opt_f16 != 0 && swg_f16_gaps_ok(go, ge); // the f16 cells are allowed and hold the gap magnitudes
+    P.wide = bits == 16 && score_bound >= SWG_I16_CEILING && ctx->opt_engine != 1 && ctx->opt_wide != 0;
     // The packed-f16 cells (three-operand maxima, 8.5 instead of 10 instructions per column pair) are exact
     // while scores stay below 4096; a sequence that reaches it is flagged and re-scored in int32.  They are the
     // first step whenever the gap magnitudes are f16 integers and the query is not so long that scores are
     // expected far beyond (where the wide form is exact on its own) -- unless this database has shown, for this
     // query, that a good part of its rows gets flagged ("f16" option: 0 never, 2 regardless of both).
-    const bool want_f16 = bits == 16 && ctx->opt_engine != 1 && ctx->opt_dynamic != 0 && ctx->opt_f16 != 0 && -go <= 2048 &&
-                          -ge <= 2048 && (ctx->opt_f16 == 2 || (score_bound < 32767ull && db->f16_veto_epoch != ctx->epoch));
-    if (want_f16) wide = false; // (only with f16 = 2: the f16 cells first, whatever the score bound)
+    const bool want_f16 = bits == 16 && ctx->opt_engine != 1 && ctx->opt_dynamic != 0 && f16_gaps &&
+                          (ctx->opt_f16 == 2 || (score_bound < SWG_I16_CEILING && db->f16_veto_epoch != ctx->epoch));
+    if (want_f16) P.wide = false; // (only with f16 = 2: the f16 cells first, whatever the score bound)
     const int plan_form = want_f16 ? 2 : 0;
 
-    Plan main_pl, re_pl;
-    memset(&main_pl, 0, sizeof main_pl);
-    memset(&re_pl, 0, sizeof re_pl);
     // (the systolic plan: only the systolic engine needs it to exist -- a cols_per_wave meant for the
     // diagonal engine has no systolic instantiation, and with engine != 1 both widths run on lane groups)
-    int rc = make_plan(ctx, bits, bits == 16 ? n_bins : n_bins * 2, &main_pl);
+    int rc = make_plan(ctx, bits, bits == 16 ? n_bins : n_bins * 2, ctx->opt_cols, &P.main_pl);
     if (rc != SWG_OK && ctx->opt_engine == 1) return rc;
     // int16: the diagonal engine unless the systolic one is asked for
-    SwgDiagWork wk;
-    bool use_diag = false, tuned_systolic = false;
+    bool tuned_systolic = false;
     if (bits == 16 && ctx->opt_engine != 1) {
-        if (ctx->opt_dynamic && (rc = ensure_pair_tokens(ctx, const_cast<swg_db *>(db))) != SWG_OK) return rc;
+        // pair tokens, first condition: the lane groups' planner and the tuner's trials want the work queue
+        if (ctx->opt_dynamic && (rc = ensure_pair_tokens(ctx, db)) != SWG_OK) return rc;
         const bool free_geometry = ctx->opt_cols == 0 && ctx->opt_group == 0 && ctx->opt_max_waves == 0 &&
                                    ctx->opt_long_split == 0 && ctx->opt_workgroups == 0;
-        swg_db *mdb = const_cast<swg_db *>(db);
         // (a geometry is tuned for the cells it ran on, and the pairings it was allowed)
         const uint64_t tuned_key = (uint64_t)lq | ((uint64_t)plan_form << 40) | ((uint64_t)ctx->opt_f16_pair << 44);
-        auto it = free_geometry ? mdb->tuned.find(tuned_key) : mdb->tuned.end();
-        if (it == mdb->tuned.end() && free_geometry && ctx->opt_autotune && ctx->opt_engine == 0 &&
+        auto it = free_geometry ? db->tuned.find(tuned_key) : db->tuned.end();
+        if (it == db->tuned.end() && free_geometry && allow_autotune && ctx->opt_engine == 0 &&
             db->n_local >= 4096 && db->n_local <= (4u << 20)) {
             SwgTuned tn;
-            if (autotune_diag(ctx, mdb, lq, go, ge, &tn, plan_form) == SWG_OK && tn.wk.n_classes > 0)
-                it = mdb->tuned.insert(std::make_pair(tuned_key, tn)).first;
+            if (autotune_diag(ctx, db, lq, go, ge, &tn, plan_form) == SWG_OK && tn.wk.n_classes > 0)
+                it = db->tuned.insert(std::make_pair(tuned_key, tn)).first;
         }
-        if (it != mdb->tuned.end() && !(wide && it->second.engine == 1)) {
+        if (it != db->tuned.end() && !(P.wide && it->second.engine == 1)) {
             if (it->second.engine == 1 && ctx->opt_engine == 0) {
                 // the systolic engine measured faster for this database and query length
-                const long keep = ctx->opt_cols;
-                ctx->opt_cols = it->second.systolic_K;
-                rc = make_plan(ctx, 16, n_bins, &main_pl);
-                ctx->opt_cols = keep;
-                if (rc != SWG_OK) return rc;
+                if ((rc = make_plan(ctx, 16, n_bins, it->second.systolic_K, &P.main_pl)) != SWG_OK) return rc;
                 tuned_systolic = true;
             } else {
                 wk = it->second.wk;
-                use_diag = true;
+                P.use_diag = true;
             }
         }
-        if (!use_diag && !tuned_systolic)
-            use_diag = swg_plan_diag_work(db, lq, ctx->n_cu, ctx->opt_cols, ctx->opt_group, ctx->opt_max_waves,
-                                          ctx->opt_long_split, ctx->opt_workgroups == 0,
-                                          ctx->opt_dynamic != 0 && db->ptok.ok, &wk, 1.0, plan_form, ctx->opt_f16_pair) > 0;
-        // The cost model's word on the ENGINE (round 4; until then only the autotuner could pick the systolic one, and it
-        // is off for databases beyond 4 M sequences and wherever the caller turned it off): a database of short sequences
-        // of near-equal length -- peptides -- is what the systolic engine is good at (no reset rows, no flags, nothing per
-        // pair: 2 M peptides of 20-40 residues, lq 128: 6 570 GCUPS against the lane groups' 4 840, lq 30: 4 820 against
-        // 1 930), and the two estimates tell: the lane groups' from the planner, the systolic one from the bin table.
-        // It has to win by 15 % (both models are good to about 10 %).
-        if (use_diag && !tuned_systolic && free_geometry && ctx->opt_engine == 0 && ctx->opt_f16 != 2 && !wide && !db->tokens_only && it == mdb->tuned.end() &&
-            wk.plan[0].est_ms > 0.0) {
-            int sys_K = 0;
-            const bool sys_f16 = ctx->opt_f16 != 0 && -go <= 2048 && -ge <= 2048 && score_bound < 4096ull;
-            const double sys_ms = swg_systolic_estimate_ms(db, lq, ctx->n_cu, &sys_K, sys_f16);
-            if (sys_K > 0 && sys_ms < SWG_SYSTOLIC_MARGIN * wk.plan[0].est_ms * swg_diag_short_pair_factor(db, wk.plan[0], plan_form)) {
-                const long keep = ctx->opt_cols;
-                ctx->opt_cols = sys_K;
-                const int rs = make_plan(ctx, 16, n_bins, &main_pl);
-                ctx->opt_cols = keep;
-                if (rs == SWG_OK) {
-                    use_diag = false;
-                    tuned_systolic = true;
-                }
+        if (!P.use_diag && !tuned_systolic)
+            P.use_diag = swg_plan_diag_work(db, lq, ctx->n_cu, ctx->opt_cols, ctx->opt_group, ctx->opt_max_waves,
+                                            ctx->opt_long_split, ctx->opt_workgroups == 0,
+                                            ctx->opt_dynamic != 0 && db->ptok.ok, &wk, 1.0, plan_form, ctx->opt_f16_pair) > 0;
+        // the cost model's own comparison of the engines, where nothing was measured and nothing forced
+        int sys_K = 0;
+        if (P.use_diag && !tuned_systolic && free_geometry && !P.wide && it == db->tuned.end() &&
+            systolic_beats_lane_groups(ctx, db, lq, wk.plan[0], plan_form, score_bound, 1, &sys_K)) {
+            if (make_plan(ctx, 16, n_bins, sys_K, &P.main_pl) == SWG_OK) { // (a failed make_plan leaves the plan as it was)
+                P.use_diag = false;
+                tuned_systolic = true;
             }
         }
-        if (!use_diag && !tuned_systolic && ctx->opt_engine == 2)
+        if (!P.use_diag && !tuned_systolic && ctx->opt_engine == 2)
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "no diagonal-engine geometry for these options");
-        if (use_diag && ctx->opt_workgroups > 0) {
+        if (P.use_diag && ctx->opt_workgroups > 0) {
             SwgDiagPlan &d0 = wk.plan[0];
             const uint64_t per_wg = (uint64_t)d0.W * (64 / d0.G);
             d0.workgroups = (int)std::min<long>(ctx->opt_workgroups, d0.workgroups);
             d0.n_streams = (uint32_t)((uint64_t)d0.workgroups * per_wg);
         }
-        if (!use_diag && !tuned_systolic && rc != SWG_OK) return rc;
+        if (!P.use_diag && !tuned_systolic && rc != SWG_OK) return rc;
         // the wide form exists in the diagonal engine only
-        if (wide && use_diag)
+        if (P.wide && P.use_diag)
             for (int c = 0; c < wk.n_classes; ++c) wk.plan[c].wide = 1;
         else
-            wide = false;
+            P.wide = false;
     }
     // The systolic engine on packed-f16 cells (round 4: 8.5 instead of 10 instructions per column pair) where NO score of
     // this search can reach their ceiling -- the engine has no flag-and-re-run route, and the databases the cost model
     // gives it are the ones whose longest sequence is short (372 residues x BLOSUM62's 11 < 4096).
-    if (bits == 16 && !use_diag && main_pl.npass == 1 && ctx->opt_f16 != 0 && -go <= 2048 && -ge <= 2048 && score_bound < 4096ull)
-        main_pl.f16 = 1;
+    if (bits == 16 && !P.use_diag && P.main_pl.npass == 1 && f16_gaps && score_bound < SWG_F16_CEILING) P.main_pl.f16 = 1;
     // int32 work (forced / unusual gap scores / re-score of saturated sequences) also runs on
     // the diagonal engine unless the systolic one is asked for
-    const bool use_diag32 = ctx->opt_engine != 1;
+    P.use_diag32 = ctx->opt_engine != 1;
     // Non-positive gap scores: the int32 work-queue kernel (8 instructions per cell, any lane-group
     // geometry, sequences off the queue) instead of the bin-based one (12 per cell, 64 lanes x 16 columns
-    // whatever the query length).
-    bool q32_ok = fast_ok && use_diag32 && ctx->opt_dynamic != 0;
-    {
-        SwgDiagWork probe; // (one pass up to about 1150 columns, else several)
-        q32_ok = q32_ok && q32_list_plan(ctx, lq, 1, &probe);
-    }
+    // whatever the query length).  Probed twice: before the token build for the query alone (one pass up to about
+    // 1150 columns, else several: a query no geometry holds never builds tokens for this), and after it for what the
+    // tokens add (they exist, and several passes fit the kernel's 32-bit edge indices).
+    SwgDiagWork probe;
+    P.q32_ok = fast_ok && P.use_diag32 && ctx->opt_dynamic != 0 && q32_list_plan(ctx, lq, 1, &probe);
     // the f16 cells: every class on the work queue, and a re-score path for what they flag
-    bool use_f16 = want_f16 && use_diag;
-    for (int c = 0; use_f16 && c < wk.n_classes; ++c) use_f16 = diag_class_is_dynamic(ctx, db, wk.plan[c]);
-    if (q32_ok && (bits == 32 || score_bound >= (wide ? 65535ull : 32767ull))) {
-        if ((rc = ensure_pair_tokens(ctx, const_cast<swg_db *>(db))) != SWG_OK) return rc;
-        SwgDiagWork probe;
-        q32_ok = db->ptok.ok && q32_list_plan(ctx, lq, 1, &probe) &&
-                 (probe.plan[0].npass == 1 || db->ptok.total_blocks < (1ull << 28)); // (32-bit edge indices)
+    P.use_f16 = want_f16 && P.use_diag;
+    for (int c = 0; P.use_f16 && c < wk.n_classes; ++c) P.use_f16 = diag_class_is_dynamic(ctx, db, wk.plan[c]);
+    if (P.q32_ok && (bits == 32 || score_bound >= (uint64_t)(P.wide ? SWG_WIDE_CEILING : SWG_I16_CEILING))) {
+        // pair tokens, second condition: an int32 level on the work queue may follow (work_queue = 1 with the
+        // systolic 16-bit fill, or a forced 32-bit search, has not built them above)
+        if ((rc = ensure_pair_tokens(ctx, db)) != SWG_OK) return rc;
+        P.q32_ok = db->ptok.ok && q32_list_plan(ctx, lq, 1, &probe) &&
+                   (probe.plan[0].npass == 1 || db->ptok.total_blocks < (1ull << 28)); // (32-bit edge indices)
     }
     // A query long enough to score beyond 32767 gets the wide form (wide16 = 0: plain int16 cells and the int32
     // re-score from 32767) -- but only a sequence that is long itself can get
@@ -1987,56 +1964,51 @@ static int search_begin(swg_ctx *ctx, const swg_db *db, bool want_scores, size_t
     // 730 rows with BLOSUM62) take the f16 cells, 8.5 instructions per column pair instead of 10, in launches of
     // their own after the long ones' (launch_diag).  The threshold is an expectation, not a bound: whatever the f16
     // cells flag all the same is run again on the wide form like any other flagged pair, so results do not depend on it.
-    uint32_t split_at = 0, split_rows = 0;
-    uint64_t split_residues = 0;
-    if (!use_f16 && bits == 16 && score_bound >= 32767ull && use_diag && ctx->opt_f16 == 1 && db->f16_veto_epoch != ctx->epoch && -go <= 2048 && -ge <= 2048 &&
-        wk.n_classes == 1 && diag_class_is_dynamic(ctx, db, wk.plan[0]) && !db->tokens_only && qbound > 0) {
+    if (!P.use_f16 && bits == 16 && score_bound >= SWG_I16_CEILING && P.use_diag && ctx->opt_f16 == 1 && db->f16_veto_epoch != ctx->epoch &&
+        swg_f16_gaps_ok(go, ge) && wk.n_classes == 1 && diag_class_is_dynamic(ctx, db, wk.plan[0]) && !db->tokens_only && qbound > 0) {
         const uint32_t rows = swg_split_rows(lq, qbound);
-        swg_db_split_at(const_cast<swg_db *>(db), rows); // (per database and length: a binary search and one pass over the lengths)
+        swg_db_split_at(db, rows); // (per database and length: a binary search and one pass over the lengths)
         const uint32_t cut = std::max<uint32_t>(db->split_pair, (uint32_t)wk.pair_begin[0]);
-        if (cut <= wk.pair_begin[0] && (score_bound < 65535ull || q32_ok)) {
+        if (cut <= wk.pair_begin[0] && (score_bound < SWG_WIDE_CEILING || P.q32_ok)) {
             // nothing long in this database: the f16 cells for all of it (what they flag: the wide form, as below)
-            use_f16 = true;
-            wide = false;
+            P.use_f16 = true;
+            P.wide = false;
             wk.plan[0].wide = 0;
         } else if (cut > wk.pair_begin[0] && cut < wk.pair_end[0]) {
-            split_at = cut;
-            split_rows = rows;
-            split_residues = db->split_residues;
+            P.split_at = cut;
+            P.split_rows = rows;
+            P.split_residues = db->split_residues;
         }
     }
-    wk.plan[0].f16_from = split_at;
+    wk.plan[0].f16_from = P.split_at; // (0 without a split, and never read without the diagonal engine)
     // Several passes of G*K columns each leave the last one partly empty (3000 columns in 6 passes of 512: 72 of them,
     // 2.3 % of the work): it runs the instantiation with the fewest columns per lane that cover what is left.
     for (int c = 0; c < wk.n_classes; ++c) {
         SwgDiagPlan &pl = wk.plan[c];
         pl.last_variant = -1;
         pl.last_K = 0;
-        if (!use_diag || wk.n_classes != 1 || pl.npass < 2 || !diag_class_is_dynamic(ctx, db, pl) || ctx->opt_last_pass == 0) continue;
+        if (!P.use_diag || wk.n_classes != 1 || pl.npass < 2 || !diag_class_is_dynamic(ctx, db, pl) || ctx->opt_last_pass == 0) continue;
         if (!swg_plan_last_pass(pl, lq, &pl.last_variant, &pl.last_K)) pl.last_variant = -1, pl.last_K = 0;
     }
     // what the f16 cells flag is run again on int16 cells (the wide form if scores may pass 32767); only what
     // saturates those too needs the int32 kernel
-    const bool rerun_wide = (use_f16 && score_bound >= 32767ull && ctx->opt_wide != 0) || (split_at != 0u && wide);
-    if (use_f16 && score_bound >= (rerun_wide ? 65535ull : 32767ull) && !q32_ok) use_f16 = false;
-    for (int c = 0; c < wk.n_classes; ++c) wk.plan[c].f16 = use_f16 ? 1 : 0;
-    const bool some_f16 = use_f16 || split_at != 0u; // some pairs run on the f16 cells: their flags are collected and re-run
-    const int32_t ceiling = use_f16 ? 4096 : wide ? 65535 : 32767;
-    const bool may_saturate = bits == 16 && (score_bound >= (uint64_t)ceiling || split_at != 0u);
-    if (may_saturate) {
-        const long keep_cols = ctx->opt_cols;
-        ctx->opt_cols = 0; // the int32 re-score uses its default geometry
-        rc = make_plan(ctx, 32, (uint32_t)std::min<size_t>(n_slots / 64, 1u << 30), &re_pl);
-        ctx->opt_cols = keep_cols;
-        if (rc != SWG_OK) return rc;
-    }
-    const int npass32 = (int)((lq + 64 * SWG_DIAG32_K - 1) / (64 * SWG_DIAG32_K));
-    SwgDiagWork wk32;
-    bool use_q32 = false, exact32 = false;
-    if (bits == 32 && !fast_ok && use_diag32 && ctx->opt_dynamic != 0) {
+    P.rerun_wide = (P.use_f16 && score_bound >= SWG_I16_CEILING && ctx->opt_wide != 0) || (P.split_at != 0u && P.wide);
+    const int32_t rerun_ceiling = P.rerun_wide ? SWG_WIDE_CEILING : SWG_I16_CEILING;
+    if (P.use_f16 && score_bound >= (uint64_t)rerun_ceiling && !P.q32_ok) P.use_f16 = false;
+    for (int c = 0; c < wk.n_classes; ++c) wk.plan[c].f16 = P.use_f16 ? 1 : 0;
+    P.ceiling = P.use_f16 ? SWG_F16_CEILING : P.wide ? SWG_WIDE_CEILING : SWG_I16_CEILING;
+    P.may_saturate = bits == 16 && (score_bound >= (uint64_t)P.ceiling || P.split_at != 0u);
+    // (the int32 level follows the last 16-bit one: the fill's own cells, or the re-run's when f16 cells came first)
+    P.level_ceiling = P.some_f16() ? rerun_ceiling : P.ceiling;
+    P.int32_level = bits == 16 && score_bound >= (uint64_t)P.level_ceiling;
+    // (the systolic int32 re-score uses its default geometry, whatever cols_per_wave asks of the fill)
+    if (P.may_saturate && (rc = make_plan(ctx, 32, (uint32_t)std::min<size_t>(n_slots / 64, 1u << 30), 0, &P.re_pl)) != SWG_OK) return rc;
+    P.npass32 = (int)((lq + 64 * SWG_DIAG32_K - 1) / (64 * SWG_DIAG32_K));
+    if (bits == 32 && !fast_ok && P.use_diag32 && ctx->opt_dynamic != 0) {
         // gap scores the reduced algebra cannot express (a positive one): the same work-queue kernel on the
-        // exact cells, unless the token array is beyond its 32-bit edge indices
-        if ((rc = ensure_pair_tokens(ctx, const_cast<swg_db *>(db))) != SWG_OK) return rc;
+        // exact cells, unless the token array is beyond its 32-bit edge indices.  Pair tokens, third condition: q32_ok
+        // is false here (it needs fast_ok), so neither of the two above has built them.
+        if ((rc = ensure_pair_tokens(ctx, db)) != SWG_OK) return rc;
         if (db->ptok.ok) {
             // the planner's split into a bulk and a long class where it fits the int32 profile and the exact cells'
             // register budget (config 2's shape: 2 580 GCUPS as one class, the longest pairs' chains last), else one class
@@ -2044,155 +2016,112 @@ static int search_begin(swg_ctx *ctx, const swg_db *db, bool want_scores, size_t
                                           ctx->opt_workgroups == 0, true, &wk32) > 0 && q32_plan_fits(wk32, lq);
             for (int c = 0; two && c < wk32.n_classes; ++c) two = wk32.plan[c].K <= SWG_X32_MAX_K;
             if (two || (x32_plan(ctx, db, lq, &wk32) && (wk32.plan[0].npass == 1 || db->ptok.total_blocks < (1ull << 28))))
-                use_q32 = exact32 = true;
+                P.use_q32 = P.exact32 = true;
         }
     }
-    if (bits == 32 && q32_ok) {
-        use_q32 = swg_plan_diag_work(db, lq, ctx->n_cu, ctx->opt_cols, ctx->opt_group, ctx->opt_max_waves, ctx->opt_long_split,
-                                     ctx->opt_workgroups == 0, true, &wk32) > 0 && q32_plan_fits(wk32, lq);
-        if (!use_q32 && ctx->opt_cols > 0 && ctx->opt_group > 0) {
-            // a forced geometry that needs several passes (or whose long class did not fit): one class of exactly
-            // that geometry, a launch per pass -- if its int32 profile fits LDS; otherwise the library's own pick
-            // below, which swg_stats reports
-            for (int v = 0; v < swg_num_diag_variants() && !use_q32; ++v) {
-                const int K = swg_diag_variant_info(v).K, G = (int)ctx->opt_group;
-                if (K != (int)ctx->opt_cols || swg_diag32q_lds_bytes(K, G, 4) > 160 * 1024) continue;
-                const size_t np = (lq + (size_t)G * K - 1) / ((size_t)G * K);
-                if (np > 64 || (np > 1 && db->ptok.total_blocks >= (1ull << 28))) continue;
-                wk32 = SwgDiagWork();
-                wk32.n_classes = 1;
-                wk32.plan[0].variant = v;
-                wk32.plan[0].K = K;
-                wk32.plan[0].G = G;
-                wk32.plan[0].W = 4;
-                wk32.plan[0].npass = (int)np;
-                wk32.pair_begin[0] = 0;
-                wk32.pair_end[0] = swg_db_pair_count(db);
-                use_q32 = true;
-            }
-        }
-        if (!use_q32) {
+    if (bits == 32 && P.q32_ok) {
+        P.use_q32 = swg_plan_diag_work(db, lq, ctx->n_cu, ctx->opt_cols, ctx->opt_group, ctx->opt_max_waves, ctx->opt_long_split,
+                                       ctx->opt_workgroups == 0, true, &wk32) > 0 && q32_plan_fits(wk32, lq);
+        // a forced geometry as it is where it can run; otherwise the library's own pick below, which swg_stats reports
+        if (!P.use_q32 && ctx->opt_cols > 0 && ctx->opt_group > 0) P.use_q32 = q32_forced_plan(db, lq, ctx->opt_cols, ctx->opt_group, &wk32);
+        if (!P.use_q32) {
             // the int16 planner's choice does not fit (LDS holds half as many int32 columns): fewest lanes that do
-            use_q32 = q32_list_plan(ctx, lq, (uint32_t)std::min<size_t>(n_slots, 1u << 30), &wk32);
-            if (use_q32) {
-                wk32.pair_begin[0] = 0;
-                wk32.pair_end[0] = swg_db_pair_count(db);
-            }
+            P.use_q32 = q32_list_plan(ctx, lq, (uint32_t)std::min<size_t>(n_slots, 1u << 30), &wk32);
+            if (P.use_q32) wk32.pair_end[0] = swg_db_pair_count(db);
         }
     }
-    // (the int32 level follows the last 16-bit one: the fill's own cells, or the re-run's when f16 cells came first)
-    const bool int32_level_planned = bits == 16 && score_bound >= (use_f16 ? (rerun_wide ? 65535ull : 32767ull) : (uint64_t)ceiling);
-    const bool bin32 = use_diag32 && ((bits == 32 && !use_q32) || (int32_level_planned && !q32_ok)); // the bin-based int32 kernel is needed
-    if (bin32) {
-        rc = ensure_profile_cols(ctx, 1, (uint32_t)(npass32 * 64 * SWG_DIAG32_K), 4, (1ull << 30) ^ (uint64_t)npass32);
+    P.bin32 = P.use_diag32 && ((bits == 32 && !P.use_q32) || (P.int32_level && !P.q32_ok)); // the bin-based int32 kernel is needed
+    return SWG_OK;
+}
+
+// Profiles, scratch and the bin image of a planned search.
+static int prepare_search(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P)
+{
+    int rc = SWG_OK;
+    const bool systolic_fill = !P.use_diag && !P.use_q32 && !(P.bits == 32 && P.use_diag32);
+    const bool systolic_rescore = P.may_saturate && !P.use_diag32;
+    const size_t bin32_scratch = P.bin32 && P.npass32 > 1 ? ((size_t)db->max_nblk * 4 + 4) * 4 * 16 * (size_t)ctx->n_cu : 0; // dwords: one uint4 per stream row
+    if (P.bin32) {
+        rc = ensure_profile_cols(ctx, 1, (uint32_t)(P.npass32 * 64 * SWG_DIAG32_K), 4, (1ull << 30) ^ (uint64_t)P.npass32);
         if (rc != SWG_OK) return rc;
-        const size_t per_wave = ((size_t)db->max_nblk * 4 + 4) * 4; // dwords: one uint4 per stream row
-        if ((rc = ensure_scratch(ctx, npass32 > 1 ? per_wave * 16 * (size_t)ctx->n_cu : 0)) != SWG_OK) return rc;
+        if ((rc = ensure_scratch(ctx, bin32_scratch)) != SWG_OK) return rc;
     }
-    if (use_diag) {
-        rc = prepare_diag(ctx, const_cast<swg_db *>(db), wk);
-    } else if (use_q32) {
-        rc = SWG_OK; // profiles are built at the launch
-    } else if (!(bits == 32 && use_diag32)) {
-        rc = ensure_profile(ctx, main_pl);
-    }
+    if (P.use_diag) rc = prepare_diag(ctx, db, P.wk);
+    else if (systolic_fill) rc = ensure_profile(ctx, P.main_pl);
+    // (the int32 work-queue fill builds its profiles at the launch)
     if (rc != SWG_OK) return rc;
-    if (may_saturate && !use_diag32 && (rc = ensure_profile(ctx, re_pl)) != SWG_OK) return rc;
-    {
-        size_t need = 0;
-        if (bin32 && npass32 > 1) need = ((size_t)db->max_nblk * 4 + 4) * 4 * 16 * (size_t)ctx->n_cu;
-        if (!use_diag && !(bits == 32 && use_diag32) && main_pl.npass > 1)
-            need = std::max(need, (size_t)main_pl.workgroups * db->max_nblk * SWG_ROWS_PER_BLK * 64 * main_pl.info.nb);
-        if (may_saturate && !use_diag32 && re_pl.npass > 1)
-            need = std::max(need, (size_t)re_pl.workgroups * db->max_nblk * SWG_ROWS_PER_BLK * 64 * re_pl.info.nb);
-        if ((rc = ensure_scratch(ctx, need)) != SWG_OK) return rc;
-    }
-
+    if (systolic_rescore && (rc = ensure_profile(ctx, P.re_pl)) != SWG_OK) return rc;
+    size_t need = bin32_scratch;
+    if (systolic_fill && P.main_pl.npass > 1)
+        need = std::max(need, (size_t)P.main_pl.workgroups * db->max_nblk * SWG_ROWS_PER_BLK * 64 * P.main_pl.info.nb);
+    if (systolic_rescore && P.re_pl.npass > 1)
+        need = std::max(need, (size_t)P.re_pl.workgroups * db->max_nblk * SWG_ROWS_PER_BLK * 64 * P.re_pl.info.nb);
+    if ((rc = ensure_scratch(ctx, need)) != SWG_OK) return rc;
     // the systolic engine and the bin-based int32 kernel read the bin image (built on the device on first use)
-    if (((!use_diag && !use_q32) || (int32_level_planned && !q32_ok)) && (rc = ensure_bins(ctx, const_cast<swg_db *>(db))) != SWG_OK)
-        return rc;
+    if ((!P.use_diag && !P.use_q32) || (P.int32_level && !P.q32_ok)) return ensure_bins(ctx, db);
+    return SWG_OK;
+}
 
+// The first level on the main stream: the diagonal engine, the int32 work queue, the bin-based int32 kernel or the
+// systolic engine (events ev[0] before the buffers are cleared, ev[1] .. ev[2] around the fill).
+static int enqueue_fill(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P, SwgSlot *S)
+{
     hipStream_t s = ctx->stream;
-    HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[0], s));
+    const size_t n_slots = (size_t)db->n_bins * SWG_BIN;
+    HIP_TRY(ctx, hipEventRecord(S->ev[0], s));
     HIP_TRY(ctx, swg_launch_zero2(db->d_scores, n_slots * 4, db->d_counters, SWG_COUNTER_BYTES, s)); // (one launch, not two memsets)
+    S->two_ends = false;
+    S->fill_launches = 0;
+    if (P.use_diag) return launch_diag(ctx, db, P.wk, P.go, P.ge, &S->two_ends);
+    if (P.use_q32)
+        return launch_q32(ctx, db, P.wk32, P.go, P.ge, nullptr, nullptr, 0, db->d_counters + SWG_QUEUE_WORD(0), &S->two_ends, true, P.exact32);
+    if (!(P.bits == 32 && P.use_diag32)) return launch_systolic(ctx, db, P.main_pl, P.go, P.ge);
+    SwgFillParams p = fill_params_base(ctx, db);
+    p.profile = ctx->d_profile[1];
+    p.queue = db->d_counters + 0;
+    p.n_items = (uint32_t)n_slots;
+    p.npass = (uint32_t)P.npass32;
+    p.go = P.go;
+    p.ge = P.ge;
+    p.scratch_wg_dwords = ((uint64_t)db->max_nblk * 4 + 4) * 4;
+    HIP_TRY(ctx, hipEventRecord(S->ev[1], s));
+    HIP_TRY(ctx, swg_launch_diag32(16, (int)std::min<size_t>((size_t)ctx->n_cu, (n_slots + 15) / 16), p, s));
+    HIP_TRY(ctx, hipEventRecord(S->ev[2], s));
+    return SWG_OK;
+}
 
-    SwgFillParams p;
-    memset(&p, 0, sizeof p);
-    p.residues = db->d_packed;
-    p.bin_off = db->d_bin_off;
-    p.bin_nblk = db->d_bin_nblk;
-    p.n_bins = n_bins;
-    p.scores = db->d_scores;
-    p.scratch = ctx->d_scratch;
-
-    bool two_ends = false;
-    ctx->cur->fill_launches = 0;
-    if (!use_diag && !use_q32) HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[1], s));
-    if (use_diag) {
-        if ((rc = launch_diag(ctx, db, wk, go, ge, &two_ends)) != SWG_OK) return rc;
-    } else if (use_q32) {
-        if ((rc = launch_q32(ctx, db, wk32, go, ge, nullptr, nullptr, 0, db->d_counters + SWG_QUEUE_WORD(0), &two_ends, true, exact32)) != SWG_OK)
-            return rc;
-    } else if (bits == 32 && use_diag32) {
-        p.profile = ctx->d_profile[1];
-        p.queue = db->d_counters + 0;
-        p.list = nullptr;
-        p.list_count = nullptr;
-        p.n_items = (uint32_t)n_slots;
-        p.npass = (uint32_t)npass32;
-        p.go = go;
-        p.ge = ge;
-        p.scratch_wg_dwords = ((uint64_t)db->max_nblk * 4 + 4) * 4;
-        HIP_TRY(ctx, swg_launch_diag32(16, (int)std::min<size_t>((size_t)ctx->n_cu, (n_slots + 15) / 16), p, s));
-    } else {
-        p.profile = ctx->d_profile[bits == 16 ? 0 : 1];
-        p.queue = db->d_counters + 0;
-        p.list = nullptr;
-        p.list_count = nullptr;
-        p.n_items = bits == 16 ? n_bins : n_bins * 2;
-        p.npass = (uint32_t)main_pl.npass;
-        if (bits == 16 && main_pl.f16) {
-            p.go = (int32_t)f16x2_of(-go);
-            p.ge = (int32_t)f16x2_of(-ge);
-        } else if (bits == 16) {
-            const uint32_t g = (uint32_t)(-go) & 0xFFFFu, e = (uint32_t)(-ge) & 0xFFFFu;
-            p.go = (int32_t)(g | (g << 16));
-            p.ge = (int32_t)(e | (e << 16));
-        } else {
-            p.go = go;
-            p.ge = ge;
-        }
-        p.scratch_wg_dwords = (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK * 64 * main_pl.info.nb;
-        HIP_TRY(ctx, swg_launch_fill(bits, main_pl.variant, main_pl.W, main_pl.workgroups, p, s, bits == 16 && main_pl.f16 != 0));
-    }
-    if (!use_diag && !use_q32) HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[2], s));
-    int32_t level_ceiling = ceiling; // what the fill before the int32 level saturates at
-    bool int32_level = may_saturate;
+// The levels behind the first: the pairs the f16 cells flagged are collected and run again on int16 cells, then what
+// saturated the last 16-bit level is collected and re-scored in int32 (event ev[3] at the end).
+static int enqueue_rescore(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P, SwgSlot *S)
+{
+    hipStream_t s = ctx->stream;
+    const size_t lq = ctx->query_len();
+    const size_t n_slots = (size_t)db->n_bins * SWG_BIN;
+    const bool some_f16 = P.some_f16();
+    int rc = SWG_OK;
     uint32_t *seq_list = db->d_list;
-    if (may_saturate && some_f16) {
+    if (P.may_saturate && some_f16) {
         // counters [17] = flagged pairs (the list's length), [16] = flagged sequences, [6] = their rows / 16 (the veto's input)
-        HIP_TRY(ctx, swg_launch_collect_flagged_pairs(db->d_scores, split_at, (uint32_t)(n_slots / 2), 4096, db->d_list, db->d_counters + 17,
+        HIP_TRY(ctx, swg_launch_collect_flagged_pairs(db->d_scores, P.split_at, (uint32_t)(n_slots / 2), SWG_F16_CEILING, db->d_list, db->d_counters + 17,
                                                       db->d_counters + 16, db->d_lens, db->d_counters + 6, s));
         SwgDiagPlan lp;
         const uint32_t guess = db->sat_hint > 0 ? (uint32_t)std::min<long long>(db->sat_hint, 1ll << 30) : 1u;
-        if (!i16_list_plan(ctx->n_cu, lq, guess, wk.plan[0], &lp)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "no geometry for the int16 re-run");
+        if (!i16_list_plan(ctx->n_cu, lq, guess, P.wk.plan[0], &lp)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "no geometry for the int16 re-run");
         HIP_TRY(ctx, hipMemsetAsync(db->d_counters + SWG_QUEUE_WORD(0), 0, (size_t)(SWG_COUNTER_BYTES - SWG_QUEUE_WORD(0) * 4u), s));
-        if ((rc = launch_dyn_list(ctx, const_cast<swg_db *>(db), lp, rerun_wide, go, ge, db->d_list, db->d_counters + 17, s)) != SWG_OK) return rc;
-        level_ceiling = rerun_wide ? 65535 : 32767;
-        int32_level = score_bound >= (uint64_t)level_ceiling;
+        if ((rc = launch_dyn_list(ctx, db, lp, P.rerun_wide, P.go, P.ge, db->d_list, db->d_counters + 17, s)) != SWG_OK) return rc;
         seq_list = db->d_list + n_slots; // (the pair list keeps the first half)
     }
-    if (int32_level) {
+    if (P.int32_level) {
         // counters [1] = saturated sequences (the list's length), [6] = their rows in units of 16
-        HIP_TRY(ctx, swg_launch_collect_saturated(db->d_scores, (uint32_t)n_slots, level_ceiling, seq_list, db->d_counters + 1,
+        HIP_TRY(ctx, swg_launch_collect_saturated(db->d_scores, (uint32_t)n_slots, P.level_ceiling, seq_list, db->d_counters + 1,
                                                   some_f16 ? nullptr : db->d_lens, db->d_counters + 6, s));
+        SwgFillParams p = fill_params_base(ctx, db);
         p.profile = ctx->d_profile[1];
         p.queue = db->d_counters + 2;
         p.list = seq_list;
         p.list_count = db->d_counters + 1;
-        p.n_items = 0;
-        p.go = go;
-        p.ge = ge;
+        p.go = P.go;
+        p.ge = P.ge;
         SwgDiagWork wkl;
         // The work-queue re-score reads the count on the device and leaves at once when it is zero, so it is queued
         // behind every fill that may flag something and the host never waits for the count in the middle of a
@@ -2200,16 +2129,16 @@ static int search_begin(swg_ctx *ctx, const swg_db *db, bool want_scores, size_t
         // swg_search_begin).  Only its lane-group width is a guess -- few flagged sequences get 64 lanes each,
         // many the narrowest group that covers the query -- made from what the last search of this database saw.
         const uint32_t guess = !some_f16 && db->sat_hint > 0 ? (uint32_t)std::min<long long>(db->sat_hint, 1ll << 30) : 1u;
-        if (use_diag32 && q32_ok && q32_list_plan(ctx, lq, guess, &wkl)) {
+        if (P.use_diag32 && P.q32_ok && q32_list_plan(ctx, lq, guess, &wkl)) {
             // (fresh queue counters and rank table: the fill's are spent; no events of its own: the
             // re-score is timed as ev[2] .. ev[3] like the other re-score forms)
             HIP_TRY(ctx, hipMemsetAsync(db->d_counters + SWG_QUEUE_WORD(0), 0,
                                         (size_t)(SWG_COUNTER_BYTES - SWG_QUEUE_WORD(0) * 4u), s));
             bool two = false;
-            rc = launch_q32(ctx, db, wkl, go, ge, seq_list, db->d_counters + 1, std::max<uint32_t>(2u * guess, 4096u),
+            rc = launch_q32(ctx, db, wkl, P.go, P.ge, seq_list, db->d_counters + 1, std::max<uint32_t>(2u * guess, 4096u),
                             db->d_counters + SWG_QUEUE_WORD(0), &two, false);
             if (rc != SWG_OK) return rc;
-        } else if (use_diag32) {
+        } else if (P.use_diag32) {
             // the bin-based kernel (positive gap scores never get here; a database beyond the queue's
             // indices, work_queue = 0): its shape comes from the count, read back over PCIe
             uint32_t n_sat = 0;
@@ -2219,64 +2148,52 @@ static int search_begin(swg_ctx *ctx, const swg_db *db, bool want_scores, size_t
                 int W = (int)((n_sat + (uint32_t)ctx->n_cu - 1) / (uint32_t)ctx->n_cu);
                 W = std::min(16, std::max(4, (W + 3) / 4 * 4));
                 const int wgs = (int)std::min<uint32_t>((uint32_t)ctx->n_cu, (n_sat + W - 1) / W);
-                p.npass = (uint32_t)npass32;
+                p.npass = (uint32_t)P.npass32;
                 p.scratch_wg_dwords = ((uint64_t)db->max_nblk * 4 + 4) * 4;
                 HIP_TRY(ctx, swg_launch_diag32(W, wgs, p, s));
             }
         } else {
-            p.npass = (uint32_t)re_pl.npass;
-            p.scratch_wg_dwords = (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK * 64 * re_pl.info.nb;
-            HIP_TRY(ctx, swg_launch_fill(32, re_pl.variant, re_pl.W, re_pl.workgroups, p, s));
+            p.npass = (uint32_t)P.re_pl.npass;
+            p.scratch_wg_dwords = (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK * 64 * P.re_pl.info.nb;
+            HIP_TRY(ctx, swg_launch_fill(32, P.re_pl.variant, P.re_pl.W, P.re_pl.workgroups, p, s));
         }
     }
-    HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[3], s));
+    HIP_TRY(ctx, hipEventRecord(S->ev[3], s));
+    return SWG_OK;
+}
 
-    // Top-K and read-out go to their own stream: the next search's fill is queued right behind this
-    // one's on the main stream and these small kernels run beside its start instead of holding it
-    // up (the output buffers belong to this in-flight slot until swg_search_end).
+// Top-K and read-out go to their own stream: the next search's fill is queued right behind this
+// one's on the main stream and these small kernels run beside its start instead of holding it
+// up (the output buffers belong to this in-flight slot until swg_search_end).  swg_search_end waits for ev_done.
+static int enqueue_readout(swg_ctx *ctx, swg_db *db, SwgSlot *S)
+{
+    hipStream_t s = ctx->stream;
+    const size_t n_slots = (size_t)db->n_bins * SWG_BIN;
+    const size_t k = S->k;
     // (the read-out stream exists from the context's second search on: ensure_stream3)
     S->side = false;
     if (ctx->opt_side_readout && ctx->n_begun > 0) {
         const int r3 = ensure_stream3(ctx);
         if (r3 != SWG_OK) return r3;
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream3, ctx->cur->ev[3], 0));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream3, S->ev[3], 0));
         s = ctx->stream3;
         S->side = true;
     }
     ++ctx->n_begun;
     // top-K on the device unless every score goes to the host anyway
-    const bool dev_topk = k > 0 && !want_scores && k <= SWG_TOPK_CAND_CAP / 2;
-    if (dev_topk)
+    S->dev_topk = k > 0 && !S->want_scores && k <= SWG_TOPK_CAND_CAP / 2;
+    if (S->dev_topk)
         HIP_TRY(ctx, swg_launch_topk(db->d_scores, db->d_order, (uint32_t)n_slots, (uint32_t)k, db->d_hist,
                                      db->d_counters + 4, db->d_keys, SWG_TOPK_CAND_CAP, db->d_counters + 3, s));
-    HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[4], s));
-
-    // read-out, queued behind the kernels; swg_search_end waits for it
-    S->bits = bits;
-    S->dev_topk = dev_topk;
-    S->need_scores = want_scores || (k > 0 && !dev_topk);
+    HIP_TRY(ctx, hipEventRecord(S->ev[4], s));
+    // read-out, queued behind the kernels
+    S->need_scores = S->want_scores || (k > 0 && !S->dev_topk);
     S->first_chunk = SWG_TOPK_CAND_CAP;
-    S->two_ends = two_ends;
-    S->may_saturate = may_saturate;
-    S->use_diag = use_diag;
-    S->use_diag32 = use_diag32;
-    S->use_q32 = use_q32;
-    S->used_f16 = some_f16;
-    S->split_rows = split_rows;
-    S->split_residues = split_residues;
-    S->epoch = ctx->epoch;
-    S->wk32 = wk32;
-    S->npass32 = npass32;
-    S->wk = wk;
-    S->main_K = main_pl.K;
-    S->main_f16 = main_pl.f16 != 0;
-    S->main_W = main_pl.W;
-    S->main_npass = main_pl.npass;
-    S->main_wgs = main_pl.workgroups;
-    if (dev_topk)
+    if (S->dev_topk)
         HIP_TRY(ctx, hipMemcpyAsync(S->h_cand, db->d_keys, S->first_chunk * 8, hipMemcpyDeviceToHost, s));
     if (S->need_scores) {
-        if ((rc = slot_scores(ctx, S, n_slots)) != SWG_OK) return rc;
+        const int rc = slot_scores(ctx, S, n_slots);
+        if (rc != SWG_OK) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(S->h_scores, db->d_scores, n_slots * 4, hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(ctx, hipMemcpyAsync(S->h_counters, db->d_counters, 128, hipMemcpyDeviceToHost, s));
@@ -2284,17 +2201,75 @@ static int search_begin(swg_ctx *ctx, const swg_db *db, bool want_scores, size_t
     return SWG_OK;
 }
 
+// Queues one whole search on the context's stream and returns without waiting (except on the
+// first search of a query length, which tunes the geometry when allow_autotune says so, and when int16 scores may
+// saturate without the work queue, where the number of flagged sequences is read back to size the re-score).
+static int search_begin(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, bool allow_autotune, SwgSlot *S)
+{
+    if (!ctx || !db) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_search: NULL argument");
+    if (!ctx->have_scoring) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search: no scoring set");
+    if (ctx->query_len() == 0) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search: no query set");
+    if (db->device != ctx->device || !db->d_codes)
+        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search: database is not resident on device %d",
+                                 ctx->device);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_slot(ctx, S);
+    if (rc != SWG_OK) return rc;
+    ctx->cur = S;
+    if ((rc = select_bufs(ctx, db, (int)(S - ctx->slots))) != SWG_OK) return rc;
+    S->bufs = db->bufs[S - ctx->slots];
+    S->db = db;
+    S->k = k;
+    S->want_scores = want_scores;
+    memset(&S->st, 0, sizeof S->st);
+    S->st.cells = (uint64_t)ctx->query_len() * db->residues;
+    S->st.bytes_alg = db->residues + 8ull * db->n_local + 32ull * ctx->query_len() + 1024ull;
+    S->plan = SwgSearchPlan(); // (bits = 0 marks "nothing queued" for an empty database)
+    if (db->n_bins == 0) return SWG_OK;
+    if ((rc = plan_search(ctx, db, allow_autotune, &S->plan)) != SWG_OK) return rc;
+    if ((rc = prepare_search(ctx, db, S->plan)) != SWG_OK) return rc;
+    if ((rc = enqueue_fill(ctx, db, S->plan, S)) != SWG_OK) return rc;
+    if ((rc = enqueue_rescore(ctx, db, S->plan, S)) != SWG_OK) return rc;
+    return enqueue_readout(ctx, db, S);
+}
+
+// Scores by sorted rank to the caller's order, and the k best of them selected on the host.
+static void deliver_scores(const swg_db *db, const int32_t *h_scores, size_t n_slots, int32_t *scores_out, swg_hit *topk_out,
+                           size_t k, size_t *n_hits)
+{
+    if (scores_out)
+        for (size_t i = 0; i < n_slots; ++i) {
+            const uint32_t oi = db->order[i];
+            if (oi != 0xFFFFFFFFu) scores_out[oi] = h_scores[i];
+        }
+    if (k > 0 && topk_out) {
+        std::vector<uint64_t> keys;
+        keys.reserve(db->n_local);
+        for (size_t i = 0; i < n_slots; ++i) {
+            const uint32_t oi = db->order[i];
+            if (oi != 0xFFFFFFFFu) keys.push_back(swg_hit_key(h_scores[i], oi));
+        }
+        const size_t m = std::min(k, keys.size());
+        std::partial_sort(keys.begin(), keys.begin() + m, keys.end(), std::greater<uint64_t>());
+        for (size_t i = 0; i < m; ++i) swg_key_hit(keys[i], &topk_out[i]);
+        if (n_hits) *n_hits = m;
+    } else if (n_hits) {
+        *n_hits = 0;
+    }
+}
+
 static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *topk_out, size_t *n_hits,
                       swg_stats *stats)
 {
-    const swg_db *db = S->db;
+    swg_db *db = S->db;
     const size_t k = S->k;
     if (n_hits) *n_hits = 0;
     if (k > 0 && !topk_out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_search: k > 0 but topk_out NULL");
     if (scores_out && !S->want_scores)
         return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_search_end: scores were not requested at swg_search_begin");
     swg_stats &st = S->st;
-    if (S->bits == 0) { // empty database
+    const SwgSearchPlan &P = S->plan;
+    if (P.bits == 0) { // empty database
         if (stats) *stats = st;
         return SWG_OK;
     }
@@ -2310,54 +2285,49 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
 #endif
     }
     const size_t n_slots = (size_t)db->n_bins * SWG_BIN;
-    const bool dev_topk = S->dev_topk, two_ends = S->two_ends, may_saturate = S->may_saturate;
-    const bool use_diag = S->use_diag, use_diag32 = S->use_diag32;
-    const int bits = S->bits, npass32 = S->npass32;
-    const SwgDiagWork &wk = S->wk;
+    const bool some_f16 = P.some_f16();
+    const SwgDiagWork &wk = P.wk;
     const SwgDiagPlan &dpl = wk.plan[0];
-    uint32_t *h_counters = S->h_counters;
-    uint64_t *h_cand = S->h_cand;
-    int32_t *&h_scores = S->h_scores;
+    const uint32_t *h_counters = S->h_counters;
     int rc = SWG_OK;
-    bool cand_ok = dev_topk && h_counters[5] == 0 && h_counters[3] <= SWG_TOPK_CAND_CAP;
-    if (dev_topk && !cand_ok) { // threshold beyond the histogram or too many ties: select on the host
+    const bool cand_ok = S->dev_topk && h_counters[5] == 0 && h_counters[3] <= SWG_TOPK_CAND_CAP;
+    if (S->dev_topk && !cand_ok) { // threshold beyond the histogram or too many ties: select on the host
         if ((rc = slot_scores(ctx, S, n_slots)) != SWG_OK) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(h_scores, S->bufs.d_scores, n_slots * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipMemcpyAsync(S->h_scores, S->bufs.d_scores, n_slots * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, spin_sync(ctx, s));
     }
 
     float ms = 0.f;
-    if ((rc = diag_fill_ms(ctx, two_ends, &st.fill_ms)) != SWG_OK) return rc;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->cur->ev[2], ctx->cur->ev[3]));
-    st.rescore_ms = may_saturate ? ms : 0.0;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->cur->ev[0], ctx->cur->ev[4]));
+    if ((rc = diag_fill_ms(ctx, S->two_ends, &st.fill_ms)) != SWG_OK) return rc;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, S->ev[2], S->ev[3]));
+    st.rescore_ms = P.may_saturate ? ms : 0.0;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, S->ev[0], S->ev[4]));
     st.total_ms = ms;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->cur->ev[3], ctx->cur->ev[4]));
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, S->ev[3], S->ev[4]));
     const double topk_dev_ms = ms;
-    st.n_rescored = S->used_f16 ? h_counters[16] : h_counters[1];
-    st.path_bits = bits;
-    st.cell_form = use_diag ? diag_class_form(ctx, db, dpl) : S->main_f16 ? 2 : 0;
-    if (use_diag && dpl.f16_from != 0u) {
+    st.n_rescored = some_f16 ? h_counters[16] : h_counters[1];
+    st.path_bits = P.bits;
+    st.cell_form = P.use_diag ? diag_class_form(ctx, db, dpl) : P.main_pl.f16 ? 2 : 0;
+    if (P.use_diag && dpl.f16_from != 0u) {
         st.cell_form = dpl.wide ? 4 : 5;
         st.n_rescored = (uint64_t)h_counters[16] + h_counters[1]; // flagged by the f16 cells + saturated on the wide form
-        st.split_rows = (int32_t)S->split_rows;
+        st.split_rows = (int32_t)P.split_rows;
         st.fill_f16_launches = S->fill_f16_launches;
-        st.cells_f16 = st.cells / std::max<uint64_t>(1, db->residues) * S->split_residues; // (cells = lq * residues)
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->cur->ev[5], ctx->cur->ev[2]));
+        st.cells_f16 = st.cells / std::max<uint64_t>(1, db->residues) * P.split_residues; // (cells = lq * residues)
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, S->ev[5], S->ev[2]));
         st.fill_f16_ms = ms;
     }
-    if (may_saturate) {
+    if (P.may_saturate) {
         // what the next search's plan may assume (never its results)
-        swg_db *mdb = const_cast<swg_db *>(db);
-        mdb->sat_hint = (long long)(S->used_f16 ? h_counters[17] : h_counters[1]); // (f16: pairs; else sequences)
+        db->sat_hint = (long long)(some_f16 ? h_counters[17] : h_counters[1]); // (f16: pairs; else sequences)
         // f16 cells whose flagged pairs hold more than 1/16 of the pair rows (counter 6: rows of the flagged pairs / 16;
         // a pair row is two residues) cost more in re-runs than they save: the cells save 15 % of the fill, the list
         // re-run of a share f of the rows costs f x 10 / 8.5 at about half the fill's efficiency.  Measured on config
         // 4's share with 4 % of the pair rows flagged: f16 + re-run 191 ms, int16 cells alone 200.
-        if (S->used_f16 && (uint64_t)h_counters[6] * 16ull * 2ull * 16ull > db->residues + 2ull * db->n_local) mdb->f16_veto_epoch = S->epoch;
+        if (some_f16 && (uint64_t)h_counters[6] * 16ull * 2ull * 16ull > db->residues + 2ull * db->n_local) db->f16_veto_epoch = P.epoch;
     }
     st.classes_overlapped = -1;
-    if (use_diag && wk.n_classes == 2 && wk.plan[0].npass == 1 && wk.plan[1].npass == 1) {
+    if (P.use_diag && wk.n_classes == 2 && wk.plan[0].npass == 1 && wk.plan[1].npass == 1) {
         // did the two classes run side by side?  (stamps: complement of the earliest start, latest end)
         unsigned long long t[4];
         memcpy(t, h_counters + 8, sizeof t);
@@ -2366,7 +2336,7 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
             st.classes_overlapped = (bulk_end > bulk_start && long_start < bulk_start + (bulk_end - bulk_start) / 10) ? 1 : 0;
         }
     }
-    if (use_diag) {
+    if (P.use_diag) {
         st.engine = 2;
         st.cols_per_wave = dpl.K;
         st.group_lanes = dpl.G;
@@ -2386,8 +2356,8 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
             st.long_streams = (int32_t)diag_class_streams(ctx, db, wk, 1);
             st.cells_padded += 2ull * lp.npass * lp.G * lp.K * diag_class_blocks(ctx, db, wk, 1) * 4ull;
         }
-    } else if (S->use_q32) {
-        const SwgDiagWork &w32 = S->wk32;
+    } else if (P.use_q32) {
+        const SwgDiagWork &w32 = P.wk32;
         st.engine = 2;
         st.work_queue = 1;
         st.cols_per_wave = w32.plan[0].K;
@@ -2404,54 +2374,43 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
             st.long_pairs = (int32_t)(w32.pair_end[1] - w32.pair_begin[1]);
             st.long_cols_per_lane = w32.plan[1].K;
         }
-    } else if (bits == 32 && use_diag32) {
+    } else if (P.bits == 32 && P.use_diag32) {
         st.engine = 2;
         st.cols_per_wave = SWG_DIAG32_K;
         st.group_lanes = 64;
         st.waves = 16;
-        st.passes = npass32;
+        st.passes = P.npass32;
         st.workgroups = (int)std::min<size_t>((size_t)ctx->n_cu, (n_slots + 15) / 16);
-        st.cells_padded = (uint64_t)npass32 * 64 * SWG_DIAG32_K * ((uint64_t)db->rows_padded);
+        st.cells_padded = (uint64_t)P.npass32 * 64 * SWG_DIAG32_K * ((uint64_t)db->rows_padded);
     } else {
+        const SwgSystolicPlan &mp = P.main_pl;
         st.engine = 1;
-        st.cols_per_wave = S->main_K;
-        st.waves = S->main_W;
-        st.passes = S->main_npass;
-        st.workgroups = S->main_wgs;
-        st.cells_padded = (uint64_t)S->main_npass * S->main_W * S->main_K * db->rows_padded;
+        st.cols_per_wave = mp.K;
+        st.waves = mp.W;
+        st.passes = mp.npass;
+        st.workgroups = mp.workgroups;
+        st.cells_padded = (uint64_t)mp.npass * mp.W * mp.K * db->rows_padded;
     }
     if (st.fill_launches <= 0) st.fill_launches = std::max(1, st.passes);
 
     const auto t0 = std::chrono::steady_clock::now();
-    if (scores_out) {
-        for (size_t i = 0; i < n_slots; ++i) {
-            const uint32_t oi = db->order[i];
-            if (oi != 0xFFFFFFFFu) scores_out[oi] = h_scores[i];
-        }
-    }
-    if (k > 0) {
-        std::vector<uint64_t> keys;
-        if (cand_ok) {
-            keys.assign(h_cand, h_cand + h_counters[3]);
-        } else {
-            fail_alloc_here(3);
-            keys.reserve(db->n_local);
-            for (size_t i = 0; i < n_slots; ++i) {
-                const uint32_t oi = db->order[i];
-                if (oi != 0xFFFFFFFFu) keys.push_back(swg_hit_key(h_scores[i], oi));
-            }
-        }
-        const size_t m = std::min(k, keys.size());
-        std::partial_sort(keys.begin(), keys.begin() + m, keys.end(), std::greater<uint64_t>());
+    if (k > 0 && cand_ok) { // (the device's candidates: every hit with a score >= the k-th best one; no score array was asked for)
+        uint64_t *keys = S->h_cand;
+        const size_t nc = h_counters[3], m = std::min(k, nc);
+        std::partial_sort(keys, keys + m, keys + nc, std::greater<uint64_t>());
         for (size_t i = 0; i < m; ++i) swg_key_hit(keys[i], &topk_out[i]);
         if (n_hits) *n_hits = m;
+    } else {
+        if (k > 0) fail_alloc_here(3);
+        deliver_scores(db, S->h_scores, n_slots, scores_out, topk_out, k, n_hits);
     }
     st.topk_ms = topk_dev_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = st;
     return SWG_OK;
 }
 
-extern "C" int swg_search_begin(swg_ctx *ctx, const swg_db *db, int want_scores, size_t k, int *ticket)
+// The body of swg_search_begin; allow_autotune: the first search of a query length may time geometries on the device.
+static int search_begin_ticket(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, bool allow_autotune, int *ticket)
 {
     return ctx_guarded(ctx, "swg_search_begin", [&]() -> int {
         fail_alloc_here(1);
@@ -2466,13 +2425,20 @@ extern "C" int swg_search_begin(swg_ctx *ctx, const swg_db *db, int want_scores,
         }
         if (slot < 0)
             return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search_begin: %d searches already in flight", SWG_MAX_INFLIGHT);
-        const int rc = search_begin(ctx, db, want_scores != 0, k, &ctx->slots[slot]);
+        const int rc = search_begin(ctx, db, want_scores, k, allow_autotune, &ctx->slots[slot]);
         if (rc != SWG_OK) return rc;
         ctx->slots[slot].busy = true;
         ctx->next_slot = (slot + 1) % SWG_MAX_INFLIGHT;
         *ticket = slot;
         return SWG_OK;
     });
+}
+
+// (the database handle is const in the ABI; a search keeps plans, hints and lazily built device images in it: the entry
+// points cast once, everything below them takes swg_db *)
+extern "C" int swg_search_begin(swg_ctx *ctx, const swg_db *db, int want_scores, size_t k, int *ticket)
+{
+    return search_begin_ticket(ctx, const_cast<swg_db *>(db), want_scores != 0, k, ctx && ctx->opt_autotune != 0, ticket);
 }
 
 extern "C" int swg_search_end(swg_ctx *ctx, int ticket, int32_t *scores_out, swg_hit *topk_out, size_t *n_hits,
@@ -2490,14 +2456,21 @@ extern "C" int swg_search_end(swg_ctx *ctx, int ticket, int32_t *scores_out, swg
     return rc;
 }
 
-extern "C" int swg_search(swg_ctx *ctx, const swg_db *db, int32_t *scores_out, swg_hit *topk_out, size_t k,
-                          size_t *n_hits, swg_stats *stats)
+// The body of swg_search: one search from begin to end.
+static int search_now(swg_ctx *ctx, swg_db *db, bool allow_autotune, int32_t *scores_out, swg_hit *topk_out, size_t k,
+                      size_t *n_hits, swg_stats *stats)
 {
     if (k > 0 && !topk_out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_search: k > 0 but topk_out NULL");
     int ticket = -1;
-    const int rc = swg_search_begin(ctx, db, scores_out != nullptr, k, &ticket);
+    const int rc = search_begin_ticket(ctx, db, scores_out != nullptr, k, allow_autotune, &ticket);
     if (rc != SWG_OK) return rc;
     return swg_search_end(ctx, ticket, scores_out, topk_out, n_hits, stats);
+}
+
+extern "C" int swg_search(swg_ctx *ctx, const swg_db *db, int32_t *scores_out, swg_hit *topk_out, size_t k,
+                          size_t *n_hits, swg_stats *stats)
+{
+    return search_now(ctx, const_cast<swg_db *>(db), ctx && ctx->opt_autotune != 0, scores_out, topk_out, k, n_hits, stats);
 }
 
 // ---------------------------------------------------------------------------
@@ -2563,30 +2536,6 @@ static int multi_rows_ok(swg_ctx *ctx, const MultiBufs &B, bool qq, size_t Qb, s
     return SWG_OK;
 }
 
-static void multi_deliver(const swg_db *db, const int32_t *h_scores, size_t n_slots, int32_t *scores_out, swg_hit *topk_out,
-                          size_t k, size_t *n_hits)
-{
-    if (scores_out)
-        for (size_t i = 0; i < n_slots; ++i) {
-            const uint32_t oi = db->order[i];
-            if (oi != 0xFFFFFFFFu) scores_out[oi] = h_scores[i];
-        }
-    if (k > 0 && topk_out) {
-        std::vector<uint64_t> keys;
-        keys.reserve(db->n_local);
-        for (size_t i = 0; i < n_slots; ++i) {
-            const uint32_t oi = db->order[i];
-            if (oi != 0xFFFFFFFFu) keys.push_back(swg_hit_key(h_scores[i], oi));
-        }
-        const size_t m = std::min(k, keys.size());
-        std::partial_sort(keys.begin(), keys.begin() + m, keys.end(), std::greater<uint64_t>());
-        for (size_t i = 0; i < m; ++i) swg_key_hit(keys[i], &topk_out[i]);
-        if (n_hits) *n_hits = m;
-    } else if (n_hits) {
-        *n_hits = 0;
-    }
-}
-
 // The queries of a batch: index bytes (one per position), or PSSM rows (32 bytes per position); q_offsets count
 // positions either way.
 struct MultiQueries {
@@ -2595,7 +2544,7 @@ struct MultiQueries {
     const char *fn; // the entry point, for messages
 };
 
-static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const MultiQueries &mq, const uint64_t *q_offsets,
+static int search_multi_impl(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, const uint64_t *q_offsets,
                              size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
                              swg_stats *stats);
 
@@ -2604,8 +2553,8 @@ extern "C" int swg_search_multi(swg_ctx *ctx, const swg_db *db, const int8_t *qu
                                 swg_stats *stats)
 {
     try { // no C++ exception crosses the ABI (the body sizes host vectors by the batch)
-        return search_multi_impl(ctx, db, MultiQueries{queries, false, "swg_search_multi"}, q_offsets, n_queries, scores_out,
-                                 topk_out, k, n_hits, stats);
+        return search_multi_impl(ctx, const_cast<swg_db *>(db), MultiQueries{queries, false, "swg_search_multi"}, q_offsets, n_queries,
+                                 scores_out, topk_out, k, n_hits, stats);
     } catch (const std::bad_alloc &) {
         return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "swg_search_multi: out of host memory");
     } catch (const std::exception &e) {
@@ -2618,8 +2567,8 @@ extern "C" int swg_search_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_
                                      swg_stats *stats)
 {
     try {
-        return search_multi_impl(ctx, db, MultiQueries{pssms, true, "swg_search_multi_pssm"}, q_offsets, n_queries, scores_out,
-                                 topk_out, k, n_hits, stats);
+        return search_multi_impl(ctx, const_cast<swg_db *>(db), MultiQueries{pssms, true, "swg_search_multi_pssm"}, q_offsets, n_queries,
+                                 scores_out, topk_out, k, n_hits, stats);
     } catch (const std::bad_alloc &) {
         return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "swg_search_multi_pssm: out of host memory");
     } catch (const std::exception &e) {
@@ -2627,7 +2576,7 @@ extern "C" int swg_search_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_
     }
 }
 
-static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const MultiQueries &mq, const uint64_t *q_offsets,
+static int search_multi_impl(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, const uint64_t *q_offsets,
                              size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
                              swg_stats *stats)
 {
@@ -2666,56 +2615,38 @@ static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const MultiQueries 
 
     // ---- can the batch go through one launch? ------------------------------------------------
     const int go = ctx->gap_open + ctx->gap_extend, ge = ctx->gap_extend;
-    bool fast = ctx->gap_open <= 0 && ctx->gap_extend <= 0 && -go <= 32767 && ctx->opt_force_bits != 32 &&
+    bool fast = ctx->gap_open <= 0 && ctx->gap_extend <= 0 && -go <= SWG_I16_CEILING && ctx->opt_force_bits != 32 &&
                 ctx->opt_engine != 1 && ctx->opt_dynamic != 0 && db->n_bins > 0 && n_queries > 1 && ctx->opt_cols == 0 &&
                 ctx->opt_group == 0 && ctx->opt_max_waves == 0 && ctx->opt_workgroups == 0;
     SwgDiagWork wk;
     const size_t Qb_max = 256; // queries per launch
     uint64_t bound_max = 0;    // the largest score any query of the batch can reach
-    if (fast) {
-        // no score of any query may reach the int16 ceiling (the batch path has no re-score).  A PSSM bounds by its
-        // own rows, as a single PSSM search does: its largest entry, and the sum of each position's best entry.
-        int smax = 0;
-        if (!mq.pssm)
-            for (int a = 0; a < 32; ++a)
-                for (int b = 0; b < 32; ++b) smax = std::max<int>(smax, ctx->sub[a][b]);
-        const uint64_t longest = (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK;
-        for (size_t i = 0; i < n_queries && fast; ++i) {
-            uint64_t qbound = 0;
-            const uint64_t lq = q_offsets[i + 1] - q_offsets[i];
-            if (mq.pssm) smax = 0;
-            for (uint64_t j = q_offsets[i]; j < q_offsets[i + 1]; ++j) {
-                const int8_t *row = mq.pssm ? queries + j * 32 : ctx->sub[(uint8_t)queries[j] & 31];
-                int best = 0;
-                for (int b = 1; b < 32; ++b) best = std::max<int>(best, row[b]);
-                if (mq.pssm) smax = std::max(smax, best);
-                qbound += (uint64_t)best;
-            }
-            const uint64_t bound = std::min<uint64_t>(qbound, std::min<uint64_t>(lq, longest) * (uint64_t)smax);
-            bound_max = std::max(bound_max, bound);
-            if (bound >= 32767ull) fast = false;
-        }
+    // no score of any query may reach the int16 ceiling (the batch path has no re-score): each query's swg_score_bound,
+    // as a single search bounds it
+    const uint64_t longest = (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK;
+    for (size_t i = 0; i < n_queries && fast; ++i) {
+        const size_t lq = (size_t)(q_offsets[i + 1] - q_offsets[i]);
+        const SwgScoreBound sb = mq.pssm ? swg_score_bound(queries + q_offsets[i] * 32, nullptr, lq, longest)
+                                         : swg_score_bound(&ctx->sub[0][0], queries + q_offsets[i], lq, longest);
+        bound_max = std::max(bound_max, sb.bound);
+        if (sb.bound >= SWG_I16_CEILING) fast = false;
     }
     // the packed-f16 cells (8.5 instead of 10 instructions per column pair) where no query of the batch can reach
     // their ceiling: the batch path has no re-run either
-    const int form = fast && ctx->opt_f16 != 0 && bound_max < 4096ull && -go <= 2048 && -ge <= 2048 ? 2 : 0;
+    const int form = fast && ctx->opt_f16 != 0 && bound_max < SWG_F16_CEILING && swg_f16_gaps_ok(go, ge) ? 2 : 0;
     if (fast) {
-        int rc = ensure_pair_tokens(ctx, const_cast<swg_db *>(db));
+        int rc = ensure_pair_tokens(ctx, db);
         if (rc != SWG_OK) return rc;
         fast = db->ptok.ok &&
                swg_plan_diag_work(db, lq_max, ctx->n_cu, 0, 0, 0, ctx->opt_long_split, true, true, &wk,
                                   (double)std::min(n_queries, Qb_max), form, 1) > 0; // (batches: v_perm_b32 pairing)
         for (int c = 0; fast && c < wk.n_classes; ++c)
             fast = wk.plan[c].npass == 1 && diag_class_is_dynamic(ctx, db, wk.plan[c]) && (size_t)wk.plan[c].G * wk.plan[c].K >= lq_max;
-        // A database of short sequences is faster on the systolic engine, one query after another (no batch form of
-        // that engine exists), than as a batch on the lane groups: 16 queries against 500 000 peptides 3 720 GCUPS as a
-        // batch, ~7 000 one by one.  Same comparison as a single search makes (swg_search_begin), per query.
-        if (fast && ctx->opt_engine == 0 && ctx->opt_f16 != 2 && !db->tokens_only && wk.plan[0].est_ms > 0.0) {
-            int sys_K = 0;
-            const bool sys_f16 = ctx->opt_f16 != 0 && -go <= 2048 && -ge <= 2048 && bound_max < 4096ull;
-            const double sys_ms = swg_systolic_estimate_ms(db, lq_max, ctx->n_cu, &sys_K, sys_f16) * (double)std::min(n_queries, Qb_max);
-            if (sys_K > 0 && sys_ms < SWG_SYSTOLIC_MARGIN * wk.plan[0].est_ms * swg_diag_short_pair_factor(db, wk.plan[0], form)) fast = false;
-        }
+        // A database of short sequences is faster on the systolic engine, one query after another, than as a batch on
+        // the lane groups: 16 queries against 500 000 peptides 3 720 GCUPS as a batch, ~7 000 one by one.  Same
+        // comparison as a single search makes, per query.
+        int sys_K = 0;
+        if (fast && systolic_beats_lane_groups(ctx, db, lq_max, wk.plan[0], form, bound_max, std::min(n_queries, Qb_max), &sys_K)) fast = false;
     }
     if (!fast) {
         // one after another; the context's own query is put back afterwards (a PSSM as a PSSM)
@@ -2727,8 +2658,8 @@ static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const MultiQueries 
             const size_t lq = (size_t)(q_offsets[i + 1] - q_offsets[i]);
             rc = mq.pssm ? swg_set_query_pssm(ctx, queries + q_offsets[i] * 32, lq) : swg_set_query(ctx, queries + q_offsets[i], lq);
             if (rc == SWG_OK)
-                rc = swg_search(ctx, db, scores_out ? scores_out + i * n_total : nullptr, topk_out ? topk_out + i * k : nullptr, k,
-                                n_hits ? n_hits + i : nullptr, &one);
+                rc = search_now(ctx, db, ctx->opt_autotune != 0, scores_out ? scores_out + i * n_total : nullptr,
+                                topk_out ? topk_out + i * k : nullptr, k, n_hits ? n_hits + i : nullptr, &one);
             if (rc == SWG_OK) {
                 st.fill_ms += one.fill_ms;
                 st.rescore_ms += one.rescore_ms;
@@ -2785,7 +2716,6 @@ static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const MultiQueries 
         else wk.plan[0].W = best_W;
     }
     const SwgPairTokens &T = db->ptok;
-    const uint32_t gm = (uint32_t)(-go) & 0xFFFFu, em = (uint32_t)(-ge) & 0xFFFFu;
     const uint32_t cnt_class = SWG_DYN_SHARDS * SWG_DYN_SHARD_STRIDE; // queue dwords of one class of one query
     MultiBufs B;
     std::vector<int32_t> h_scores;
@@ -2928,29 +2858,19 @@ static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const MultiQueries 
                 HIP_TRY(ctx, swg_launch_diag_qq(pl.variant, pl.W, wgs[c], (int)Qrows, q, c == 1 ? ctx->stream2 : s));
                 continue;
             }
-            SwgDiagDynParams q;
-            memset(&q, 0, sizeof q);
-            q.tok = T.d_tok;
-            q.zero_block = (uint32_t)T.total_blocks;
-            q.pair_off = T.d_pair_off;
+            SwgDiagDynParams q = dyn_params_base(T, B.d_scores, n_slots, pl.G, form, go, ge, wk.n_classes,
+                                                 B.d_cnt + Qb_max * 2 * cnt_class + (size_t)c * SWG_DYN_SIMD_SLOTS);
             q.q_begin = (uint32_t)wk.pair_begin[c];
             q.q_end = (uint32_t)wk.pair_end[c];
             q.queue = B.d_cnt + (size_t)c * cnt_class;
             q.queue_stride = 2 * cnt_class;
             q.profile = B.d_prof[c];
             q.profile_stride = (uint64_t)pl.G * swg_diag_padded_cols(pl.K) * 64;
-            q.scores = B.d_scores;
             q.score_stride = n_slots;
-            q.pair_limit = (uint32_t)(n_slots / 2);
-            q.G = (uint32_t)pl.G;
-            q.go = form == 2 ? f16x2_of(-go) : gm | (gm << 16);
-            q.ge = form == 2 ? f16x2_of(-ge) : em | (em << 16);
             if (c == 0) {
                 const uint64_t blocks = (uint64_t)(T.pair_blocks_prefix[wk.pair_end[0]] - T.pair_blocks_prefix[wk.pair_begin[0]]) * Qb;
                 q.prio_blocks = (uint32_t)std::max<uint64_t>(8, (uint64_t)(ctx->opt_prio_share * 0.01 * (double)blocks / (double)groups0));
             }
-            q.turn_levels = wk.n_classes == 2 ? 3u : 4u;
-            q.simd_ranks = B.d_cnt + Qb_max * 2 * cnt_class + (size_t)c * SWG_DYN_SIMD_SLOTS;
             dyn_batch_zones(ctx, T, &q, (uint64_t)wgs[c] * pl.W * (64 / pl.G), pl.K, pl.G, form);
             HIP_TRY(ctx, swg_launch_diag_dyn(pl.variant, false, form, pl.W, wgs[c], q, c == 1 ? ctx->stream2 : s, (int)Qb));
         }
@@ -2988,11 +2908,11 @@ static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const MultiQueries 
                 if (h_scores.size() < n_slots) h_scores.resize(n_slots);
                 HIP_TRY(ctx, hipMemcpyAsync(h_scores.data(), B.d_scores + r * n_slots, n_slots * 4, hipMemcpyDeviceToHost, s));
                 HIP_TRY(ctx, spin_sync(ctx, s));
-                multi_deliver(db, h_scores.data(), n_slots, nullptr, topk_out + (q0 + i) * k, k, n_hits ? n_hits + q0 + i : nullptr);
+                deliver_scores(db, h_scores.data(), n_slots, nullptr, topk_out + (q0 + i) * k, k, n_hits ? n_hits + q0 + i : nullptr);
                 continue;
             }
-            multi_deliver(db, h_scores.data() + r * n_slots, n_slots, scores_out ? scores_out + (q0 + i) * n_total : nullptr,
-                          topk_out ? topk_out + (q0 + i) * k : nullptr, k, n_hits ? n_hits + q0 + i : nullptr);
+            deliver_scores(db, h_scores.data() + r * n_slots, n_slots, scores_out ? scores_out + (q0 + i) * n_total : nullptr,
+                           topk_out ? topk_out + (q0 + i) * k : nullptr, k, n_hits ? n_hits + q0 + i : nullptr);
         }
         st.topk_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         st.workgroups = wgs[0] * (int)Qrows;
@@ -3026,15 +2946,15 @@ static int search_multi_impl(swg_ctx *ctx, const swg_db *db, const MultiQueries 
 // device: the two sequences of a pair are two adjacent lanes of one batch, so a row's two residues are two adjacent
 // bytes (swg_build_tokens16_kernel).  Nothing is un-transposed or re-coded on the host, and nothing is allocated or
 // freed per call once the buffers have grown to the size of the caller's macro-batches (round 2 rebuilt a whole
-// database per call: 26-34 ms of host work and hipFree around 2.5 ms of device time).  Returns 1 when the search
-// cannot take this route (options that ask for an engine that reads the bin image, a query the work-queue kernels
+// database per call: 26-34 ms of host work and hipFree around 2.5 ms of device time).  Returns SWG_TAKE_HOST_ROUTE when
+// the search cannot take this route (options that ask for an engine that reads the bin image, a query the work-queue kernels
 // cannot hold): the caller falls back to the host route.
 static int fill_batches16_device(swg_ctx *ctx, const swg_batch16 *batches, size_t n_batches, size_t n_records,
                                  const size_t *first_rec, double *fill_seconds, double *t_ms)
 {
     typedef std::chrono::steady_clock clk;
     const clk::time_point t0 = clk::now();
-    if (ctx->opt_engine == 1 || ctx->opt_dynamic == 0 || !ctx->have_scoring || ctx->query_len() == 0) return 1;
+    if (ctx->opt_engine == 1 || ctx->opt_dynamic == 0 || !ctx->have_scoring || ctx->query_len() == 0) return SWG_TAKE_HOST_ROUTE;
     for (const SwgSlot &sl : ctx->slots)
         if (sl.busy) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_fill_batches16: searches are in flight on this context");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3059,7 +2979,7 @@ static int fill_batches16_device(swg_ctx *ctx, const swg_batch16 *batches, size_
         residues += (uint64_t)bt.vector_size * bt.max_len;
         longest = std::max<uint64_t>(longest, bt.max_len);
     }
-    if (n_pairs >= (1ull << 31) || total_blocks + 1 >= (1ull << 32)) return 1;
+    if (n_pairs >= (1ull << 31) || total_blocks + 1 >= (1ull << 32)) return SWG_TAKE_HOST_ROUTE;
     const size_t n_slots = (2 * n_pairs + SWG_BIN - 1) / SWG_BIN * SWG_BIN;
     // ---- buffers: grown, never shrunk ---------------------------------------------------------
     if (!C.db || n_slots > C.slots_cap || n_pairs > C.pairs_cap || total_blocks > C.blocks_cap || stage_bytes > C.stage_cap) {
@@ -3200,17 +3120,14 @@ static int fill_batches16_device(swg_ctx *ctx, const swg_batch16 *batches, size_
                                            T.d_tok, d_bad, s));
     // ---- the search itself (the cost model's geometry: this database is searched once) ----------------------
     swg_stats st;
-    const auto keep_autotune = ctx->opt_autotune;
-    ctx->opt_autotune = 0;
-    int rc = search_begin(ctx, db, true, 0, &ctx->slots[0]);
+    int rc = search_begin(ctx, db, true, 0, false, &ctx->slots[0]);
     if (rc == SWG_OK) {
         ctx->slots[0].busy = true;
         // (scores by record index: straight from the slot's pinned landing buffer, no int32 array in between)
         rc = search_end(ctx, &ctx->slots[0], nullptr, nullptr, nullptr, &st);
         ctx->slots[0].busy = false;
     }
-    ctx->opt_autotune = keep_autotune;
-    if (rc != SWG_OK) return rc == SWG_ERR_STATE && strstr(ctx->err.c_str(), "built from 16-lane batches") ? 1 : rc;
+    if (rc != SWG_OK) return rc; // (SWG_TAKE_HOST_ROUTE from the search itself: it needs what this database does not have)
     uint32_t bad = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, spin_sync(ctx, s));
@@ -3223,8 +3140,8 @@ static int fill_batches16_device(swg_ctx *ctx, const swg_batch16 *batches, size_
         for (size_t k = 0; k < n_batches; ++k) {
             const swg_batch16 &bt = batches[bo[k]];
             for (size_t i = 0; 2 * i < bt.vector_size; ++i, ++p) {
-                bt.max_scores[2 * i] = (int16_t)std::min<int32_t>(hs[2 * p], 32767);
-                if (2 * i + 1 < bt.vector_size) bt.max_scores[2 * i + 1] = (int16_t)std::min<int32_t>(hs[2 * p + 1], 32767);
+                bt.max_scores[2 * i] = (int16_t)std::min<int32_t>(hs[2 * p], INT16_MAX);
+                if (2 * i + 1 < bt.vector_size) bt.max_scores[2 * i + 1] = (int16_t)std::min<int32_t>(hs[2 * p + 1], INT16_MAX);
             }
         }
     }
@@ -3283,7 +3200,7 @@ static int fill_batches16_impl(swg_ctx *ctx, const swg_batch16 *batches, size_t 
         } catch (const std::exception &) {
             return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "swg_fill_batches16: out of host memory");
         }
-        if (rd != 1) {
+        if (rd != SWG_TAKE_HOST_ROUTE) {
             if (rd == SWG_OK && timing)
                 fprintf(stderr, "[swg_fill_batches16] %zu records, device route: tables %.2f ms, staging copy %.2f, upload + tokens + search + "
                                 "read-out %.2f (device, first kernel to last: %.2f), scores to the batches %.2f; wall %.2f\n",
@@ -3317,10 +3234,7 @@ static int fill_batches16_impl(swg_ctx *ctx, const swg_batch16 *batches, size_t 
     }
     swg_stats st;
     // (this database is searched exactly once: the cost model's geometry, no timed trials)
-    const auto keep_autotune = ctx->opt_autotune;
-    ctx->opt_autotune = 0;
-    if (rc == SWG_OK) rc = swg_search(ctx, db, scores.data(), nullptr, 0, nullptr, &st);
-    ctx->opt_autotune = keep_autotune;
+    if (rc == SWG_OK) rc = search_now(ctx, db, false, scores.data(), nullptr, 0, nullptr, &st);
     tp[4] = clk::now();
     swg_db_free(db);
     tp[5] = clk::now();
@@ -3328,7 +3242,7 @@ static int fill_batches16_impl(swg_ctx *ctx, const swg_batch16 *batches, size_t 
     size_t i = 0;
     for (size_t b = 0; b < n_batches; ++b)
         for (size_t l = 0; l < batches[b].vector_size; ++l, ++i)
-            batches[b].max_scores[l] = (int16_t)std::min<int32_t>(scores[i], 32767);
+            batches[b].max_scores[l] = (int16_t)std::min<int32_t>(scores[i], INT16_MAX);
     if (fill_seconds) *fill_seconds = st.total_ms * 1e-3;
     if (timing) {
         auto ms = [&](int i) { return std::chrono::duration<double, std::milli>(tp[i + 1] - tp[i]).count(); };

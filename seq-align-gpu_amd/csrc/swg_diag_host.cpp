@@ -528,13 +528,42 @@ bool swg_plan_last_pass(const SwgDiagPlan &pl, size_t lq, int *variant, int *K)
     return true;
 }
 
-// Both 16-bit forms in one search (swg_search_begin): the length from which a sequence can reach the f16 cells' ceiling
+// How high can a score get (declared in swg_host_internal.h)?  Below SWG_I16_CEILING nothing can saturate the int16
+// cells; below SWG_WIDE_CEILING the wide form is exact and nothing needs the int32 re-score; below SWG_F16_CEILING the f16
+// cells flag nothing.
+SwgScoreBound swg_score_bound(const int8_t *rows, const int8_t *idx, size_t lq, uint64_t longest)
+{
+    SwgScoreBound r;
+    if (idx) // (the table's largest entry: any of its 32 x 32)
+        for (int i = 0; i < 32 * 32; ++i) r.smax = std::max<int>(r.smax, rows[i]);
+    for (size_t i = 0; i < lq; ++i) {
+        const int8_t *row = idx ? rows + 32 * ((uint8_t)idx[i] & 31) : rows + 32 * i;
+        int best = 0;
+        for (int b = 1; b < 32; ++b) best = std::max<int>(best, row[b]);
+        if (!idx) r.smax = std::max(r.smax, best);
+        r.qbound += (uint64_t)best;
+    }
+    r.bound = std::min<uint64_t>(r.qbound, std::min<uint64_t>(lq, longest) * (uint64_t)r.smax);
+    return r;
+}
+
+extern "C" int swg_debug_score_bound(const int8_t *rows, const int8_t *idx, size_t lq, uint64_t longest, uint64_t *out)
+{
+    if (!rows || !out) return SWG_ERR_ARG;
+    const SwgScoreBound r = swg_score_bound(rows, idx, lq, longest);
+    out[0] = r.qbound;
+    out[1] = (uint64_t)r.smax;
+    out[2] = r.bound;
+    return SWG_OK;
+}
+
+// Both 16-bit forms in one search (plan_search in swg_api.cpp): the length from which a sequence can reach the f16 cells' ceiling
 // as an exact copy of a stretch of the query -- such a copy scores qbound / lq per row on average, qbound being the
 // query's best possible total --, and where that length cuts the sorted pair order (kept per database and length).
 uint32_t swg_split_rows(size_t lq, uint64_t qbound)
 {
     if (qbound == 0) return 0u;
-    return (uint32_t)std::min<uint64_t>((4096ull * lq + qbound - 1) / qbound, 1u << 30);
+    return (uint32_t)std::min<uint64_t>(((uint64_t)SWG_F16_CEILING * lq + qbound - 1) / qbound, 1u << 30);
 }
 
 void swg_db_split_at(swg_db *db, uint32_t rows)

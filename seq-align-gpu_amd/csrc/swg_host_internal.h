@@ -143,7 +143,7 @@ struct swg_db {
     // database full of close relatives of the query) that the int16 cells are the faster first step.
     long long sat_hint = -1;
     uint64_t f16_veto_epoch = 0;
-    // both 16-bit forms in one search (swg_search_begin): for the last length threshold asked about, the first pair
+    // both 16-bit forms in one search (plan_search): for the last length threshold asked about, the first pair
     // of the sorted order whose sequences are all shorter, and the residues from it on
     uint32_t split_rows = 0, split_pair = 0;
     uint64_t split_residues = 0;
@@ -179,6 +179,62 @@ struct swg_db {
     uint32_t *d_hist = nullptr;
 };
 
+// The score ceilings of the cell forms, and the largest gap magnitude the packed-f16 cells hold as an exact integer.
+// A score that reaches a form's ceiling is flagged and handed to the next form.
+#define SWG_F16_GAP_MAX 2048
+#define SWG_F16_CEILING 4096
+#define SWG_I16_CEILING 32767 // (also the largest gap magnitude of the packed int16 cells)
+#define SWG_WIDE_CEILING 65535
+// gap magnitudes (of non-positive gap scores go = open + extend, ge = extend) fit the f16 cells
+inline bool swg_f16_gaps_ok(int go, int ge) { return -go <= SWG_F16_GAP_MAX && -ge <= SWG_F16_GAP_MAX; }
+
+// The largest score a query can reach against sequences of at most `longest` rows: not above the query's best possible
+// total (every column paired with its best-scoring residue of 1 .. 31: qbound) nor above min(lq, longest) times the
+// largest entry (smax).  idx != NULL: rows is the 32 x 32 table and idx the query's lq residue indices; idx == NULL: rows
+// are the lq x 32 rows of a PSSM, whose largest entry is the largest of its positions' best ones.
+struct SwgScoreBound {
+    uint64_t qbound = 0, bound = 0;
+    int smax = 0;
+};
+SwgScoreBound swg_score_bound(const int8_t *rows, const int8_t *idx, size_t lq, uint64_t longest);
+// test hook: out[0..2] = qbound, smax, bound
+extern "C" int swg_debug_score_bound(const int8_t *rows, const int8_t *idx, size_t lq, uint64_t longest, uint64_t *out);
+
+// Geometry of the systolic engine (bin-based kernels) for one query length.
+struct SwgSystolicPlan {
+    int bits = 0, variant = 0, K = 0, W = 0, npass = 0, workgroups = 0;
+    SwgKernelInfo info = {};
+    int f16 = 0; // int16 plan on the packed-f16 cells (one pass, no score of the search can reach their ceiling)
+};
+
+// Everything a search decides before it queues anything (swg_api.cpp: plan_search writes it, the stages that allocate
+// and launch only read it, and swg_search_end reports from it).
+struct SwgSearchPlan {
+    int bits = 0;          // 16 / 32; 0: nothing queued (an empty database)
+    bool fast_ok = false;  // the gap scores fit the packed forms (non-positive, magnitude within int16)
+    int go = 0, ge = 0;    // gap_open + gap_extend, gap_extend
+    uint64_t score_bound = ~0ull, qbound = 0; // swg_score_bound of this query against this database
+    uint64_t epoch = 0;    // the context's (query, scoring) epoch the plan was made under
+    // the first level's cells, and where their flags go
+    bool use_f16 = false;  // every class on the packed-f16 cells
+    bool wide = false;     // the wide int16 form (scores to SWG_WIDE_CEILING)
+    uint32_t split_at = 0, split_rows = 0; // both forms in one class: first pair of the f16 part, the length threshold
+    uint64_t split_residues = 0;           // ... and the residues that run on the f16 cells
+    bool rerun_wide = false;   // what the f16 cells flag is run again on the wide form (else plain int16)
+    int32_t ceiling = 0;       // what the first level saturates at
+    int32_t level_ceiling = 0; // ... and the last 16-bit level (the re-run's, when f16 cells came first)
+    bool may_saturate = false; // a second level is queued
+    bool int32_level = false;  // an int32 level follows the last 16-bit one,
+    bool q32_ok = false;       // on the work-queue kernel,
+    bool bin32 = false;        // or on the bin-based one (also a whole 32-bit fill without the work queue)
+    bool some_f16() const { return use_f16 || split_at != 0u; } // some pairs run on the f16 cells: their flags are collected and re-run
+    // engines
+    bool use_diag = false, use_diag32 = false, use_q32 = false, exact32 = false;
+    SwgDiagWork wk, wk32;            // lane groups: the 16-bit fill; the int32 work-queue fill of the whole database
+    SwgSystolicPlan main_pl, re_pl;  // systolic engine: the fill; the int32 re-score
+    int npass32 = 0;                 // passes of the bin-based int32 kernel
+};
+
 // One search in flight: its timing events, host-side landing buffers and what swg_search_end
 // needs to finish it.  Device buffers are shared: everything of one context runs in stream
 // order, so search i+1 cannot touch them before search i has copied its results out.
@@ -186,24 +242,15 @@ struct swg_db {
 struct SwgSlot {
     hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_done = nullptr; // polled from user space instead of a blocking stream sync
-    uint64_t score_bound = ~0ull; // the largest score this search's query can reach against this database (launch_diag: f16_wipe)
-    bool main_f16 = false;        // the systolic fill ran on the packed-f16 cells
+    SwgSearchPlan plan;           // what the search decided (launch_diag reads its score_bound: f16_wipe)
     bool side = false;            // this search's top-K and read-out were queued on the read-out stream (stream3)
     bool busy = false;
-    const swg_db *db = nullptr;
+    swg_db *db = nullptr;
     swg_db::Bufs bufs; // the output buffers this search writes
     size_t k = 0, first_chunk = 0;
-    bool want_scores = false, dev_topk = false, need_scores = false, two_ends = false, may_saturate = false;
-    bool use_diag = false, use_diag32 = false, use_q32 = false;
-    bool used_f16 = false;  // the fill ran on the packed-f16 cells (all of it, or the pairs from plan.f16_from on)
-    uint32_t split_rows = 0;     // both forms: the length threshold, and the residues that ran on the f16 cells
-    uint64_t split_residues = 0;
-    uint64_t epoch = 0;     // the context's (query, scoring) epoch the search was queued under
-    SwgDiagWork wk32; // int32 work-queue fill of the whole database
-    int bits = 0, npass32 = 0, main_K = 0, main_W = 0, main_npass = 0, main_wgs = 0;
+    bool want_scores = false, dev_topk = false, need_scores = false, two_ends = false;
     int fill_launches = 0; // launches of the bulk class's fill kernel (passes x segments)
     int fill_f16_launches = 0; // both forms in one class: those of them that ran the f16 cells
-    SwgDiagWork wk;
     swg_stats st;
     uint64_t *h_cand = nullptr;     // pinned, SWG_TOPK_CAND_CAP keys
     uint32_t *h_counters = nullptr; // pinned, 32 words
@@ -277,6 +324,9 @@ struct swg_ctx {
     int next_slot = 0;
 };
 
+// Internal status (positive: never a public SWG_ERR_*): a database built from 16-lane batches has pair tokens only, and
+// this search needs residue bytes by rank (the bin image, fixed streams); swg_fill_batches16 then takes its host route.
+#define SWG_TAKE_HOST_ROUTE 1
 int swg_set_global_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 int swg_set_ctx_error(swg_ctx *ctx, int code, const char *fmt, ...)
     __attribute__((format(printf, 3, 4)));
@@ -295,7 +345,7 @@ double swg_systolic_estimate_ms(const swg_db *db, size_t lq, int n_cu, int *best
 double swg_diag_short_pair_factor(const swg_db *db, const SwgDiagPlan &pl, int form); // lane groups on short pairs: what the fitted estimate misses
 extern "C" int swg_debug_engine(const swg_db *db, size_t lq, int n_cu, int form, int32_t *out);
 extern "C" int swg_debug_split(swg_db *db, size_t lq, uint64_t qbound, uint64_t *out);
-// decisions swg_search_begin makes on top of the planner's geometry (host only: swg_diag_host.cpp)
+// decisions plan_search (swg_api.cpp) makes on top of the planner's geometry (host only: swg_diag_host.cpp)
 bool swg_plan_last_pass(const SwgDiagPlan &pl, size_t lq, int *variant, int *K);
 uint32_t swg_split_rows(size_t lq, uint64_t qbound);
 void swg_db_split_at(swg_db *db, uint32_t rows);

@@ -123,3 +123,62 @@ def test_gap_edge_fixtures_hold_what_they_are_for(orc, name, go, ge):
         sc, _, ops = orc.pair_trace(g["query"], d, g["sub"], go, ge)
         gapped += sc > 127 * F and ("I" in ops or "D" in ops)
     assert gapped >= 5 if -(go + ge) <= 16000 else gapped == 0, gapped
+
+
+def _lib_score_bound(swg, rows, idx, longest):
+    """swg_debug_score_bound (csrc/swg_host_internal.h): (qbound, smax, bound) of a table + query indices, or of PSSM
+    rows (idx None), against sequences of at most `longest` rows."""
+    import ctypes as C
+    fn = swg.lib.swg_debug_score_bound
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]
+    rows = np.ascontiguousarray(rows, dtype=np.int8)
+    idx = None if idx is None else np.ascontiguousarray(idx, dtype=np.int8)
+    out = np.zeros(3, dtype=np.uint64)
+    lq = rows.shape[0] if idx is None else len(idx)
+    assert fn(rows.ctypes.data, None if idx is None else idx.ctypes.data, lq, longest, out.ctypes.data) == 0
+    return tuple(int(x) for x in out)
+
+
+def _pssm_bound_model(pssm, longest):
+    """A PSSM bounds by its own rows: each position's best entry over residues 1 .. 31 (never below 0), their sum, and
+    the largest of them times min(lq, longest)."""
+    best = np.asarray(pssm).astype(np.int64)[:, 1:].max(axis=1).clip(min=0)
+    return int(best.sum()), int(best.max()), min(int(best.sum()), min(len(best), longest) * int(best.max()))
+
+
+def test_score_bound_equals_the_python_model(swg):
+    """The one bound every search and every batch plans by (swg_score_bound), against the model the GPU module's route
+    expectations use (test_gpu_scoring_edges._score_bound), for a table query and for a PSSM, on both arms of the
+    minimum: the query's best total, and min(lq, longest) x the largest entry."""
+    from test_gpu_scoring_edges import _score_bound
+    rng = np.random.default_rng(20261017)
+    b62 = swg.load_scoring("BLOSUM62").table()
+    arms = set()
+    for sub in (b62, se.diag127(), se.full_range(), se.blosum62_dirty0(b62), se.all_m128()):
+        for lq, max_len in ((1, 1), (37, 5), (37, 6), (300, 41), (300, 4000), (3000, 372), (3000, 35000)):
+            q = rng.integers(1, 32, size=lq).astype(np.int8)
+            lens = np.array([1, max_len])
+            longest = (max_len + 3) // 4 * 4
+            qbound, smax, bound = _lib_score_bound(swg, sub, q, longest)
+            assert bound == _score_bound(sub, q, lens), (lq, max_len)
+            assert smax == max(0, int(np.asarray(sub).max()))
+            assert qbound == int(np.asarray(sub).astype(np.int64)[q.astype(np.int64)][:, 1:].max(axis=1).clip(min=0).sum())
+            assert bound == min(qbound, min(lq, longest) * smax)
+            arms.add("total" if qbound < min(lq, longest) * smax else "longest" if qbound > min(lq, longest) * smax else "tie")
+            # the same query as a PSSM (its rows of the table): the same total; the largest entry is the rows' own
+            pssm = np.asarray(sub)[q.astype(np.int64)]
+            assert _lib_score_bound(swg, pssm, None, longest) == _pssm_bound_model(pssm, longest)
+            assert _lib_score_bound(swg, pssm, None, longest)[0] == qbound
+    assert {"total", "longest"} <= arms, arms
+    # PSSMs of any int8, column 0 (never a database residue) holding the largest entries
+    for lq, longest in ((1, 4), (50, 8), (50, 4000), (700, 64)):
+        pssm = rng.integers(-128, 128, size=(lq, 32)).astype(np.int8)
+        pssm[:, 0] = 127
+        pssm[::3, 1:] = rng.integers(-128, 0, size=pssm[::3, 1:].shape)  # positions with no positive entry count 0
+        got = _lib_score_bound(swg, pssm, None, longest)
+        assert got == _pssm_bound_model(pssm, longest), (lq, longest)
+    pssm = np.zeros((50, 32), dtype=np.int8)
+    pssm[:, 5] = 100
+    pssm[0, 7] = 127
+    assert _lib_score_bound(swg, pssm, None, 8) == (5027, 127, 8 * 127)      # the min(lq, longest) * smax arm
+    assert _lib_score_bound(swg, pssm, None, 4000) == (5027, 127, 5027)      # the query's best total
