@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -118,6 +119,28 @@ static int ensure_stream2(swg_ctx *ctx)
     int least = 0, greatest = 0;
     HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
     HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, greatest));
+    return SWG_OK;
+}
+
+// A plan of two classes forks before its launches and joins after them: stream2 waits for what the main stream has
+// queued so far (ev[6]), the long class is launched on stream2 and the bulk on the main stream, and the main stream
+// then waits for the end of stream2's work (ev[7]); bulk_end: ev[5] marks the end of the bulk's launches first, for a
+// search that times the two classes (diag_fill_ms).  A plan of one class does neither.
+static int fork_long_class(swg_ctx *ctx, const SwgDiagWork &wk)
+{
+    if (wk.n_classes != 2) return SWG_OK;
+    const int r2 = ensure_stream2(ctx);
+    if (r2 != SWG_OK) return r2;
+    HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[6], ctx->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->cur->ev[6], 0));
+    return SWG_OK;
+}
+static int join_long_class(swg_ctx *ctx, const SwgDiagWork &wk, bool bulk_end)
+{
+    if (wk.n_classes != 2) return SWG_OK;
+    if (bulk_end) HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[5], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[7], ctx->stream2));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->cur->ev[7], 0));
     return SWG_OK;
 }
 
@@ -581,9 +604,7 @@ static int make_plan(swg_ctx *ctx, int bits, uint32_t n_items, long cols, SwgSys
     // residency: info.max_waves is also the wave budget of one CU for this
     // instantiation's register allocation; LDS is the other limit
     const size_t lds = info.lds_per_wave * (size_t)W + info.lds_fixed;
-    int per_cu = std::max(1, info.max_waves / W);
-    per_cu = std::max(1, std::min<int>(per_cu, (int)((160 * 1024) / lds)));
-    long wgs = (long)ctx->n_cu * per_cu;
+    long wgs = (long)ctx->n_cu * swg_workgroups_per_cu(info.max_waves, W, lds);
     if (ctx->opt_workgroups > 0) wgs = ctx->opt_workgroups;
     wgs = std::max<long>(1, std::min<long>(wgs, (long)n_items));
     pl->bits = bits;
@@ -792,9 +813,9 @@ static int diag_class_workgroups(const swg_ctx *ctx, const swg_db *db, const Swg
     if (c != 0 || !diag_class_is_dynamic(ctx, db, pl)) return pl.workgroups;
     const SwgKernelInfo info = swg_diag_variant_info(pl.variant);
     const size_t lds = swg_diag_dyn_lds_bytes(pl.K, pl.G, pl.W, diag_class_fma(ctx, db, pl));
-    const int per_cu = std::max(1, std::min<int>(info.max_waves / pl.W, (int)((160 * 1024) / lds)));
+    const int per_cu = swg_workgroups_per_cu(info.max_waves, pl.W, lds);
     if (ctx->opt_wave_budget > 0 && wk.n_classes == 1) // experiment: more resident wavefronts than the planner's 16 per CU
-        return std::max(1, ctx->n_cu * std::max(1, std::min<int>((int)ctx->opt_wave_budget / pl.W, (int)((160 * 1024) / lds))));
+        return std::max(1, ctx->n_cu * swg_workgroups_per_cu((int)ctx->opt_wave_budget, pl.W, lds));
     const int capacity = ctx->n_cu * per_cu;
     int displaced = 0;
     if (wk.n_classes == 2 && diag_class_is_dynamic(ctx, db, wk.plan[1]))
@@ -838,20 +859,23 @@ static int ensure_scratch(swg_ctx *ctx, size_t dwords)
 // group of G: the layout depends on (K, G).  ([0] and [1] are the systolic engine's, in plain order.)
 static int diag_profile_slot(const SwgDiagPlan &, int cls) { return cls == 0 ? 3 : 2; }
 
-// The (M,B) edges of the rows between consecutive passes of the work-queue fill, ping-pong: allocated for the token
-// blocks of the database, and again when a re-filled database has grown.
-static int ensure_edges(swg_ctx *ctx, SwgPairTokens *T)
+// The edges of the rows between consecutive passes of a work-queue fill, ping-pong: one of the three buffer pairs of
+// SwgPairTokens, `block_bytes` per 4-row token block, allocated for the token blocks of the database (*cap_blocks), and
+// again when a re-filled database has grown.
+template <class E> static int ensure_edge_pair(swg_ctx *ctx, const SwgPairTokens &T, E *(&d_edge)[2], uint64_t *cap_blocks, size_t block_bytes)
 {
-    if (T->d_edge[0] && T->edge_blocks >= T->total_blocks) return SWG_OK;
-    (void)hipFree(T->d_edge[0]);
-    (void)hipFree(T->d_edge[1]);
-    T->d_edge[0] = T->d_edge[1] = nullptr;
-    const size_t bytes = std::max<size_t>(8, (size_t)T->total_blocks * 4 * sizeof(uint2));
-    HIP_TRY(ctx, hipMalloc(&T->d_edge[0], bytes));
-    HIP_TRY(ctx, hipMalloc(&T->d_edge[1], bytes));
-    T->edge_blocks = T->total_blocks;
+    if (d_edge[0] && *cap_blocks >= T.total_blocks) return SWG_OK;
+    (void)hipFree(d_edge[0]);
+    (void)hipFree(d_edge[1]);
+    d_edge[0] = d_edge[1] = nullptr;
+    const size_t bytes = std::max<size_t>(8, (size_t)T.total_blocks * block_bytes);
+    HIP_TRY(ctx, hipMalloc(&d_edge[0], bytes));
+    HIP_TRY(ctx, hipMalloc(&d_edge[1], bytes));
+    *cap_blocks = T.total_blocks;
     return SWG_OK;
 }
+// the 16-bit kernels' (M,B) per row (prepare_diag and the list re-run)
+static int ensure_edges(swg_ctx *ctx, SwgPairTokens *T) { return ensure_edge_pair(ctx, *T, T->d_edge, &T->edge_blocks, 4 * sizeof(uint2)); }
 
 // A gap magnitude as the cells of `form` take it, in both halves of a dword: an f16 integer (form 2) or 16 bits.
 static uint32_t gap_word(int form, int gap)
@@ -860,25 +884,41 @@ static uint32_t gap_word(int form, int gap)
     return form == 2 ? f16x2_of(-gap) : m | (m << 16);
 }
 
-// What every launch of the work-queue kernel (swg_diag_dyn_kernel) is told the same way: the pair tokens and their
-// offsets, the score array of n_slots entries and its pair limit, the lane-group width, the gap words of the cells
-// `form`, the turn levels (three beside a second class, else four) and the per-SIMD rank words.
-static SwgDiagDynParams dyn_params_base(const SwgPairTokens &T, int32_t *scores, size_t n_slots, int G, int form, int go, int ge,
-                                        int n_classes, uint32_t *simd_ranks)
+// What every work-queue kernel (P: SwgDiagDynParams, SwgDiagQ32Params, SwgDiagQQParams) is told the same way, the rest
+// zero: the pair tokens and their offsets, the lane-group width, the turn levels (three beside a second class, else
+// four) and the per-SIMD rank words.
+template <class P> static P token_params(const SwgPairTokens &T, int G, int n_classes, uint32_t *simd_ranks)
 {
-    SwgDiagDynParams q;
+    P q;
     memset(&q, 0, sizeof q);
     q.tok = T.d_tok;
     q.zero_block = (uint32_t)T.total_blocks;
     q.pair_off = T.d_pair_off;
-    q.scores = scores;
-    q.pair_limit = (uint32_t)(n_slots / 2);
     q.G = (uint32_t)G;
-    q.go = gap_word(form, go);
-    q.ge = gap_word(form, ge);
     q.turn_levels = n_classes == 2 ? 3u : 4u;
     q.simd_ranks = simd_ranks;
     return q;
+}
+
+// ... and every launch of swg_diag_dyn_kernel besides: the score array of n_slots entries and its pair limit, the gap
+// words of the cells `form`.
+static SwgDiagDynParams dyn_params_base(const SwgPairTokens &T, int32_t *scores, size_t n_slots, int G, int form, int go, int ge,
+                                        int n_classes, uint32_t *simd_ranks)
+{
+    SwgDiagDynParams q = token_params<SwgDiagDynParams>(T, G, n_classes, simd_ranks);
+    q.scores = scores;
+    q.pair_limit = (uint32_t)(n_slots / 2);
+    q.go = gap_word(form, go);
+    q.ge = gap_word(form, ge);
+    return q;
+}
+
+// The bulk's priority threshold: an item (pair, or sequence) of at least this many token blocks runs at raised
+// priority -- one that alone is well above an average lane group's whole share of the class's `blocks`: prio_share
+// percent of it, times `factor`; never fewer than 8 blocks.
+static uint32_t bulk_prio_blocks(const swg_ctx *ctx, uint64_t blocks, uint64_t groups, double factor = 1.0)
+{
+    return (uint32_t)std::max<uint64_t>(8, (uint64_t)(ctx->opt_prio_share * 0.01 * factor * (double)blocks / (double)std::max<uint64_t>(1, groups)));
 }
 
 // The launches of one pass over the pairs [begin, end).  The form with edges addresses a launch's tokens and edges by
@@ -1003,13 +1043,9 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
             HIP_TRY(ctx, hipMemsetAsync(d_trace[c], 0, bytes, s));
         }
     HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[1], s));
-    if (wk.n_classes == 2) {
-        const int r2 = ensure_stream2(ctx);
-        if (r2 != SWG_OK) return r2;
-        // fork: the long pairs start first, on their own stream, beside the bulk
-        HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[6], s));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->cur->ev[6], 0));
-    }
+    // the long pairs start first, on their own stream, beside the bulk
+    int rf = fork_long_class(ctx, wk);
+    if (rf != SWG_OK) return rf;
     for (int c = wk.n_classes - 1; c >= 0; --c) {
         const SwgDiagLayout &L = db->diag[c];
         const SwgDiagPlan &pl = wk.plan[c];
@@ -1026,9 +1062,7 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
             // above an average lane group's whole share
             auto bulk_prio = [&]() -> uint32_t {
                 const uint64_t blocks = T.pair_blocks_prefix[wk.pair_end[0]] - T.pair_blocks_prefix[wk.pair_begin[0]];
-                const uint64_t groups = (uint64_t)diag_class_workgroups(ctx, db, wk, 0) * wk.plan[0].W * (64 / wk.plan[0].G);
-                return (uint32_t)std::max<uint64_t>(8, (uint64_t)(ctx->opt_prio_share * 0.01 * (double)blocks /
-                                                                  (double)std::max<uint64_t>(1, groups)));
+                return bulk_prio_blocks(ctx, blocks, (uint64_t)diag_class_workgroups(ctx, db, wk, 0) * wk.plan[0].W * (64 / wk.plan[0].G));
             };
             q.prio_blocks = c == 1 ? 0u : bulk_prio();
             if (c == 1 && ctx->opt_long_helps && diag_class_is_dynamic(ctx, db, wk.plan[0])) {
@@ -1127,13 +1161,10 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
         HIP_TRY(ctx, swg_launch_diag(pl.variant, pl.npass > 1, pl.wide != 0, pl.W, pl.workgroups, pl.lds_bytes, d,
                                      c == 1 ? ctx->stream2 : s));
     }
-    if (wk.n_classes == 2) {
-        // join; the end of the fill is the later of the two kernels' ends
-        HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[5], s));
-        HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[7], ctx->stream2));
-        HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->cur->ev[7], 0));
-        *two_ends = true;
-    }
+    // the end of the fill is the later of the two kernels' ends
+    rf = join_long_class(ctx, wk, true);
+    if (rf != SWG_OK) return rf;
+    *two_ends = wk.n_classes == 2;
     HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[2], s));
     if (trace_path) {
         HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -1222,16 +1253,17 @@ static int prepare_systolic(swg_ctx *ctx, swg_db *db, const SwgSystolicPlan &pl)
 // ---------------------------------------------------------------------------
 // int32 with a work queue (swg_diag32q_kernel): non-positive gap scores, one pass
 // ---------------------------------------------------------------------------
-// Occupancy of an int32 work plan.  The int32 profile is twice the int16 one, so LDS, not registers,
-// decides how many workgroups a CU holds: the long class keeps one workgroup of four wavefronts per
-// CU, and the bulk takes the smallest workgroup size W (4, 8, 12 wavefronts sharing one profile) with
-// which the LDS that is left still holds three wavefronts per SIMD, or as many as it can.
-static void q32_occupancy(const swg_ctx *ctx, const SwgDiagWork &wk, int *bulk_W, int *bulk_per_cu)
+// The bulk's workgroup size where the profile is twice the int16 one (the int32 kernel's, the query pairs'), so that
+// LDS, not registers, decides how many workgroups a CU holds: the long class keeps one workgroup of four wavefronts per
+// CU, and the bulk takes the smallest workgroup size W (4, 8, 12 or 16 wavefronts sharing one profile) that leaves the
+// most wavefronts resident in the LDS that is left, `wave_cap` per CU at most.  forced_W > 0: that size where it fits
+// (one class only).  False: not even one workgroup of four fits; *bulk_W and *bulk_per_cu are then 4 and 1.
+static bool lds_bound_workgroup(const SwgDiagWork &wk, int wave_cap, long forced_W, int *bulk_W, int *bulk_per_cu)
 {
     const SwgDiagPlan &pl = wk.plan[0];
     const SwgKernelInfo info = swg_diag_variant_info(pl.variant);
-    size_t room = 160 * 1024;
-    int cap_waves = std::min(12, info.max_waves);
+    size_t room = SWG_LDS_PER_CU;
+    int cap_waves = std::min(wave_cap, info.max_waves);
     if (wk.n_classes == 2) {
         room -= std::min(room, swg_diag32q_lds_bytes(wk.plan[1].K, wk.plan[1].G, 4));
         cap_waves = std::min(cap_waves, info.max_waves - 4);
@@ -1246,29 +1278,30 @@ static void q32_occupancy(const swg_ctx *ctx, const SwgDiagWork &wk, int *bulk_W
             best_n = n;
         }
     }
-    if (ctx->opt_q32_waves > 0 && ctx->opt_q32_waves <= info.max_waves && wk.n_classes == 1 &&
-        swg_diag32q_lds_bytes(pl.K, pl.G, (int)ctx->opt_q32_waves) <= room) { // experiment: the workgroup size of an int32 launch
-        best_W = (int)ctx->opt_q32_waves;
+    if (forced_W > 0 && forced_W <= info.max_waves && wk.n_classes == 1 && swg_diag32q_lds_bytes(pl.K, pl.G, (int)forced_W) <= room) {
+        best_W = (int)forced_W;
         best_n = std::max(1, std::min<int>((int)(room / swg_diag32q_lds_bytes(pl.K, pl.G, best_W)), cap_waves / best_W));
     }
     *bulk_W = best_W;
     *bulk_per_cu = best_n;
+    return best_waves > 0;
 }
 
-static int q32_class_workgroups(const swg_ctx *ctx, const SwgDiagWork &wk, int c, uint64_t items)
+// Occupancy of an int32 work plan: three wavefronts per SIMD, or as many as LDS holds; a plan nothing fits runs one
+// workgroup of four per CU.  (Option q32_waves, an experiment: the workgroup size of an int32 launch.)
+static void q32_occupancy(const swg_ctx *ctx, const SwgDiagWork &wk, int *bulk_W, int *bulk_per_cu)
 {
-    const SwgDiagPlan &pl = wk.plan[c];
-    int W = 4, per_cu = 1;
-    if (c == 0) q32_occupancy(ctx, wk, &W, &per_cu);
-    const uint64_t per_wg = (uint64_t)W * (64 / pl.G);
+    (void)lds_bound_workgroup(wk, 12, ctx->opt_q32_waves, bulk_W, bulk_per_cu);
+}
+
+// Workgroups of class c over `items` sequences, and (*waves) their size
+static int q32_class_workgroups(const swg_ctx *ctx, const SwgDiagWork &wk, int c, uint64_t items, int *waves)
+{
+    int per_cu = 1;
+    *waves = 4;
+    if (c == 0) q32_occupancy(ctx, wk, waves, &per_cu);
+    const uint64_t per_wg = (uint64_t)*waves * (64 / wk.plan[c].G);
     return (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)ctx->n_cu * per_cu, (items + per_wg - 1) / per_wg));
-}
-
-static int q32_class_waves(const swg_ctx *ctx, const SwgDiagWork &wk, int c)
-{
-    int W = 4, per_cu = 1;
-    if (c == 0) q32_occupancy(ctx, wk, &W, &per_cu);
-    return W;
 }
 
 static bool q32_plan_fits(const SwgDiagWork &wk, size_t lq)
@@ -1276,11 +1309,11 @@ static bool q32_plan_fits(const SwgDiagWork &wk, size_t lq)
     if (wk.n_classes < 1) return false;
     for (int c = 0; c < wk.n_classes; ++c) {
         const SwgDiagPlan &pl = wk.plan[c];
-        if (pl.npass != 1 || (size_t)pl.G * pl.K < lq || swg_diag32q_lds_bytes(pl.K, pl.G, 4) > 160 * 1024) return false;
+        if (pl.npass != 1 || (size_t)pl.G * pl.K < lq || swg_diag32q_lds_bytes(pl.K, pl.G, 4) > SWG_LDS_PER_CU) return false;
     }
     // both classes run side by side on every CU
     if (wk.n_classes == 2 && swg_diag32q_lds_bytes(wk.plan[0].K, wk.plan[0].G, 4) + swg_diag32q_lds_bytes(wk.plan[1].K, wk.plan[1].G, 4) >
-                                 160 * 1024)
+                                 SWG_LDS_PER_CU)
         return false;
     return true;
 }
@@ -1300,6 +1333,26 @@ static SwgDiagWork q32_one_class(int variant, int K, int G, size_t npass, uint64
     return wk;
 }
 
+// Columns per lane for lane groups of G lanes whose profile `fits` LDS.  one_pass: the fewest that cover the query in
+// one pass.  Otherwise the most that fit give the number of passes, and then the fewest that still need no more passes
+// are taken (less padding in the last one).  Returns the variant (-1: none) with its K and the passes.
+template <class Fits> static int cols_per_lane(int G, size_t lq, bool one_pass, Fits fits, int *K_out, size_t *npass)
+{
+    int best = -1, bestK = one_pass ? 1 << 30 : 0;
+    for (int v = 0; v < swg_num_diag_variants(); ++v) {
+        const int K = swg_diag_variant_info(v).K;
+        if (fits(K, G) && (one_pass ? (size_t)G * K >= lq && K < bestK : K > bestK)) best = v, bestK = K;
+    }
+    if (best < 0) return -1;
+    *npass = one_pass ? 1 : (lq + (size_t)G * bestK - 1) / ((size_t)G * bestK);
+    for (int v = 0; v < swg_num_diag_variants() && !one_pass; ++v) {
+        const int K = swg_diag_variant_info(v).K;
+        if (K < bestK && (size_t)G * K * *npass >= lq) best = v, bestK = K;
+    }
+    *K_out = bestK;
+    return best;
+}
+
 // Geometry for a list of `n_items` flagged sequences (or, with a plan the int16 planner's choice does not
 // fit, the whole database): few items get 64 lanes each (the shortest chain per row), many the narrowest
 // lane group that covers the query in one pass.  A query no single pass holds (LDS: G*K int32 columns of
@@ -1307,46 +1360,18 @@ static SwgDiagWork q32_one_class(int variant, int K, int G, size_t npass, uint64
 static bool q32_list_plan(const swg_ctx *ctx, size_t lq, uint32_t n_items, SwgDiagWork *wk)
 {
     const bool few = n_items <= 8u * (uint32_t)ctx->n_cu;
-    const int order[3] = {few ? 64 : 16, 32, few ? 16 : 64};
-    for (int gi = 0; gi < 3; ++gi) {
-        const int G = order[gi];
-        int best = -1, bestK = 1 << 30;
-        for (int v = 0; v < swg_num_diag_variants(); ++v) {
-            const int K = swg_diag_variant_info(v).K;
-            if ((size_t)G * K >= lq && K < bestK && swg_diag32q_lds_bytes(K, G, 4) <= 160 * 1024) {
-                best = v;
-                bestK = K;
-            }
-        }
-        if (best >= 0) {
-            *wk = q32_one_class(best, bestK, G, 1);
-            return true;
-        }
+    auto fits = [](int K, int G) { return swg_diag32q_lds_bytes(K, G, 4) <= SWG_LDS_PER_CU; };
+    const int order[4] = {few ? 64 : 16, 32, few ? 16 : 64, few ? 64 : 32}; // (the last: several passes, few items 64 lanes, many 32)
+    for (int gi = 0; gi < 4; ++gi) {
+        int K = 0;
+        size_t npass = 0;
+        const int v = cols_per_lane(order[gi], lq, gi < 3, fits, &K, &npass);
+        if (v < 0) continue;
+        if (npass > 64) return false;
+        *wk = q32_one_class(v, K, order[gi], npass);
+        return true;
     }
-    // several passes: the most columns per pass that fit LDS (few items: 64 lanes; many: 32)
-    const int G = few ? 64 : 32;
-    int best = -1, bestK = 0;
-    for (int v = 0; v < swg_num_diag_variants(); ++v) {
-        const int K = swg_diag_variant_info(v).K;
-        if (K > bestK && swg_diag32q_lds_bytes(K, G, 4) <= 160 * 1024) {
-            best = v;
-            bestK = K;
-        }
-    }
-    if (best < 0) return false;
-    const size_t cols = (size_t)G * bestK;
-    const size_t npass = (lq + cols - 1) / cols;
-    if (npass > 64) return false;
-    // the fewest columns per lane that still need no more passes (less padding in the last one)
-    for (int v = 0; v < swg_num_diag_variants(); ++v) {
-        const int K = swg_diag_variant_info(v).K;
-        if (K < bestK && (size_t)G * K * npass >= lq) {
-            best = v;
-            bestK = K;
-        }
-    }
-    *wk = q32_one_class(best, bestK, G, npass);
-    return true;
+    return false;
 }
 
 // Geometry of the exact int32 cells (gap scores of any sign) for a whole database: one class; the narrowest lane
@@ -1355,7 +1380,7 @@ static bool q32_list_plan(const swg_ctx *ctx, size_t lq, uint32_t n_items, SwgDi
 static bool x32_plan(const swg_ctx *ctx, const swg_db *db, size_t lq, SwgDiagWork *wk)
 {
     auto set = [&](int v, int K, int G, size_t npass) { *wk = q32_one_class(v, K, G, npass, swg_db_pair_count(db)); };
-    auto fits = [&](int K, int G) { return K <= SWG_X32_MAX_K && swg_diag32q_lds_bytes(K, G, 4) <= 160 * 1024; };
+    auto fits = [&](int K, int G) { return K <= SWG_X32_MAX_K && swg_diag32q_lds_bytes(K, G, 4) <= SWG_LDS_PER_CU; };
     if (ctx->opt_cols > 0 && ctx->opt_group > 0) {
         for (int v = 0; v < swg_num_diag_variants(); ++v) {
             const int K = swg_diag_variant_info(v).K, G = (int)ctx->opt_group;
@@ -1366,34 +1391,17 @@ static bool x32_plan(const swg_ctx *ctx, const swg_db *db, size_t lq, SwgDiagWor
             return true;
         }
     }
-    const int groups[3] = {16, 32, 64};
-    for (int gi = 0; gi < 3; ++gi) {
-        const int G = groups[gi];
-        int best = -1, bestK = 1 << 30;
-        for (int v = 0; v < swg_num_diag_variants(); ++v) {
-            const int K = swg_diag_variant_info(v).K;
-            if ((size_t)G * K >= lq && K < bestK && fits(K, G)) best = v, bestK = K;
-        }
-        if (best >= 0) {
-            set(best, bestK, G, 1);
-            return true;
-        }
+    const int groups[4] = {16, 32, 64, 64}; // (the last: several passes)
+    for (int gi = 0; gi < 4; ++gi) {
+        int K = 0;
+        size_t npass = 0;
+        const int v = cols_per_lane(groups[gi], lq, gi < 3, fits, &K, &npass);
+        if (v < 0) continue;
+        if (npass > 64) return false;
+        set(v, K, groups[gi], npass);
+        return true;
     }
-    const int G = 64;
-    int best = -1, bestK = 0;
-    for (int v = 0; v < swg_num_diag_variants(); ++v) {
-        const int K = swg_diag_variant_info(v).K;
-        if (K > bestK && fits(K, G)) best = v, bestK = K;
-    }
-    if (best < 0) return false;
-    const size_t npass = (lq + (size_t)G * bestK - 1) / ((size_t)G * bestK);
-    if (npass > 64) return false;
-    for (int v = 0; v < swg_num_diag_variants(); ++v) {
-        const int K = swg_diag_variant_info(v).K;
-        if (K < bestK && (size_t)G * K * npass >= lq) best = v, bestK = K;
-    }
-    set(best, bestK, G, npass);
-    return true;
+    return false;
 }
 
 // Launches the int32 work-queue fill: every sequence of the plan's classes (list == NULL), or the
@@ -1411,24 +1419,10 @@ static int launch_q32(swg_ctx *ctx, swg_db *db, const SwgDiagWork &wk, int go, i
     if (npass > 1) {
         if (wk.n_classes != 1 || T.total_blocks >= (1ull << 28))
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "int32 multi-pass fill: plan not supported");
-        if (!T.d_edge32[0] || T.edge32_blocks < T.total_blocks) {
-            (void)hipFree(T.d_edge32[0]);
-            (void)hipFree(T.d_edge32[1]);
-            T.d_edge32[0] = T.d_edge32[1] = nullptr;
-            const size_t bytes = std::max<size_t>(8, (size_t)T.total_blocks * 4 * 2 * sizeof(int2));
-            HIP_TRY(ctx, hipMalloc(&T.d_edge32[0], bytes));
-            HIP_TRY(ctx, hipMalloc(&T.d_edge32[1], bytes));
-            T.edge32_blocks = T.total_blocks;
-        }
-        if (exact && (!T.d_edge32d[0] || T.edge32d_blocks < T.total_blocks)) { // the exact cells' third edge value
-            (void)hipFree(T.d_edge32d[0]);
-            (void)hipFree(T.d_edge32d[1]);
-            T.d_edge32d[0] = T.d_edge32d[1] = nullptr;
-            const size_t bytes = std::max<size_t>(8, (size_t)T.total_blocks * 4 * 2 * sizeof(int32_t));
-            HIP_TRY(ctx, hipMalloc(&T.d_edge32d[0], bytes));
-            HIP_TRY(ctx, hipMalloc(&T.d_edge32d[1], bytes));
-            T.edge32d_blocks = T.total_blocks;
-        }
+        // per row and per sequence of the pair; the exact cells' third edge value beside it
+        int rc = ensure_edge_pair(ctx, T, T.d_edge32, &T.edge32_blocks, 4 * 2 * sizeof(int2));
+        if (rc == SWG_OK && exact) rc = ensure_edge_pair(ctx, T, T.d_edge32d, &T.edge32d_blocks, 4 * 2 * sizeof(int32_t));
+        if (rc != SWG_OK) return rc;
     }
     for (int c = 0; c < wk.n_classes; ++c) {
         const SwgDiagPlan &pl = wk.plan[c];
@@ -1439,19 +1433,11 @@ static int launch_q32(swg_ctx *ctx, swg_db *db, const SwgDiagWork &wk, int go, i
         if (rc != SWG_OK) return rc;
     }
     if (timing_events) HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[1], s));
-    if (wk.n_classes == 2) {
-        const int r2 = ensure_stream2(ctx);
-        if (r2 != SWG_OK) return r2;
-        HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[6], s));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->cur->ev[6], 0));
-    }
+    int rf = fork_long_class(ctx, wk);
+    if (rf != SWG_OK) return rf;
     for (int c = wk.n_classes - 1; c >= 0; --c) {
         const SwgDiagPlan &pl = wk.plan[c];
-        SwgDiagQ32Params q;
-        memset(&q, 0, sizeof q);
-        q.tok = T.d_tok;
-        q.zero_block = (uint32_t)T.total_blocks;
-        q.pair_off = T.d_pair_off;
+        SwgDiagQ32Params q = token_params<SwgDiagQ32Params>(T, pl.G, wk.n_classes, db->d_counters + SWG_RANK_WORD(c));
         uint64_t items;
         if (d_list) {
             q.list = d_list;
@@ -1465,18 +1451,13 @@ static int launch_q32(swg_ctx *ctx, swg_db *db, const SwgDiagWork &wk, int go, i
         q.queue = queue_words + (size_t)c * SWG_DYN_SHARDS * SWG_DYN_SHARD_STRIDE;
         q.scores = db->d_scores;
         q.seq_limit = (uint32_t)n_slots;
-        q.G = (uint32_t)pl.G;
         q.go = exact ? go : -go; // (the exact cells add the signed scores, the reduced ones subtract magnitudes)
         q.ge = exact ? ge : -ge;
-        q.turn_levels = wk.n_classes == 2 ? 3u : 4u;
-        q.simd_ranks = db->d_counters + SWG_RANK_WORD(c);
-        const int wgs = q32_class_workgroups(ctx, wk, c, items);
-        const int W = q32_class_waves(ctx, wk, c);
+        int W = 4;
+        const int wgs = q32_class_workgroups(ctx, wk, c, items, &W);
         if (c == 0 && !d_list) {
             const uint64_t blocks = T.pair_blocks_prefix[wk.pair_end[0]] - T.pair_blocks_prefix[wk.pair_begin[0]];
-            const uint64_t groups = (uint64_t)wgs * W * (64 / pl.G);
-            q.prio_blocks = (uint32_t)std::max<uint64_t>(8, (uint64_t)(ctx->opt_prio_share * 0.01 * 2.0 * (double)blocks /
-                                                                       (double)std::max<uint64_t>(1, groups)));
+            q.prio_blocks = bulk_prio_blocks(ctx, blocks, (uint64_t)wgs * W * (64 / pl.G), 2.0); // (the int32 kernel's rule has a factor 2)
         } else {
             q.prio_blocks = c == 1 ? 0u : 0xFFFFFFFFu;
         }
@@ -1492,12 +1473,9 @@ static int launch_q32(swg_ctx *ctx, swg_db *db, const SwgDiagWork &wk, int go, i
             HIP_TRY(ctx, swg_launch_diag32q(pl.variant, pl.npass > 1, exact, W, wgs, q, qs));
         }
     }
-    if (wk.n_classes == 2) {
-        HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[5], s));
-        HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[7], ctx->stream2));
-        HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->cur->ev[7], 0));
-        *two_ends = true;
-    }
+    rf = join_long_class(ctx, wk, true);
+    if (rf != SWG_OK) return rf;
+    *two_ends = wk.n_classes == 2;
     if (timing_events) HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[2], s));
     return SWG_OK;
 }
@@ -1528,17 +1506,10 @@ static bool i16_list_plan(int n_cu, size_t lq, uint32_t n_pairs_guess, const Swg
         return true;
     }
     const int G = 64;
-    int best = -1, bestK = 0;
-    for (int v = 0; v < swg_num_diag_variants(); ++v) { // the most columns per pass that fit LDS
-        const int K = swg_diag_variant_info(v).K;
-        if (K > bestK && swg_diag_dyn_lds_bytes(K, G, 4) <= 160 * 1024) best = v, bestK = K;
-    }
+    int bestK = 0;
+    size_t npass = 0;
+    const int best = cols_per_lane(G, lq, false, [](int K, int g) { return swg_diag_dyn_lds_bytes(K, g, 4) <= SWG_LDS_PER_CU; }, &bestK, &npass);
     if (best < 0) return false;
-    const size_t npass = (lq + (size_t)G * bestK - 1) / ((size_t)G * bestK);
-    for (int v = 0; v < swg_num_diag_variants(); ++v) { // the fewest columns per lane that need no more passes
-        const int K = swg_diag_variant_info(v).K;
-        if (K < bestK && (size_t)G * K * npass >= lq) best = v, bestK = K;
-    }
     *out = SwgDiagPlan();
     out->variant = best;
     out->K = bestK;
@@ -1550,7 +1521,7 @@ static bool i16_list_plan(int n_cu, size_t lq, uint32_t n_pairs_guess, const Swg
     // 3 100 pairs took three rounds and 28 left-overs on 1 024 wavefronts (7.7 ms per pass, now 5.3; the text of
     // DESIGN 9 counted 3 072).
     int W = swg_diag_variant_info(best).max_waves / 4 * 4;
-    while (W > 4 && swg_diag_dyn_lds_bytes(bestK, G, W) > 160 * 1024) W -= 4;
+    while (W > 4 && swg_diag_dyn_lds_bytes(bestK, G, W) > SWG_LDS_PER_CU) W -= 4;
     out->W = std::max(4, W);
     out->npass = (int)npass;
     return true;
@@ -1593,9 +1564,7 @@ static int launch_dyn_list(swg_ctx *ctx, swg_db *db, const SwgDiagPlan &pl, bool
     q.queue = db->d_counters + SWG_QUEUE_WORD(0);
     q.prio_blocks = 0xFFFFFFFFu;
     q.prio_blocks2 = 0xFFFFFFFFu;
-    const SwgKernelInfo info = swg_diag_variant_info(pl.variant);
-    const size_t lds = swg_diag_dyn_lds_bytes(pl.K, pl.G, pl.W);
-    const int per_cu = std::max(1, std::min<int>(info.max_waves / pl.W, (int)((160 * 1024) / lds)));
+    const int per_cu = swg_workgroups_per_cu(swg_diag_variant_info(pl.variant).max_waves, pl.W, swg_diag_dyn_lds_bytes(pl.K, pl.G, pl.W));
     const int wgs = ctx->n_cu * std::min(per_cu, 3);
     const uint32_t n_pairs = (uint32_t)swg_db_pair_count(db);
     std::vector<std::pair<uint32_t, uint32_t>> segs; // (the list spans the whole token buffer)
@@ -1825,7 +1794,7 @@ static bool q32_forced_plan(const swg_db *db, size_t lq, long cols, long group, 
 {
     for (int v = 0; v < swg_num_diag_variants(); ++v) {
         const int K = swg_diag_variant_info(v).K, G = (int)group;
-        if (K != (int)cols || swg_diag32q_lds_bytes(K, G, 4) > 160 * 1024) continue;
+        if (K != (int)cols || swg_diag32q_lds_bytes(K, G, 4) > SWG_LDS_PER_CU) continue;
         const size_t np = (lq + (size_t)G * K - 1) / ((size_t)G * K);
         if (np > 64 || (np > 1 && db->ptok.total_blocks >= (1ull << 28))) continue;
         *wk = q32_one_class(v, K, G, np, swg_db_pair_count(db));
@@ -2362,10 +2331,9 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
         st.work_queue = 1;
         st.cols_per_wave = w32.plan[0].K;
         st.group_lanes = w32.plan[0].G;
-        st.waves = q32_class_waves(ctx, w32, 0);
         st.passes = w32.plan[0].npass;
         const uint64_t items0 = 2 * (w32.pair_end[0] - w32.pair_begin[0]);
-        st.workgroups = q32_class_workgroups(ctx, w32, 0, items0);
+        st.workgroups = q32_class_workgroups(ctx, w32, 0, items0, &st.waves);
         st.streams = st.workgroups * st.waves * (64 / w32.plan[0].G);
         for (int c = 0; c < w32.n_classes; ++c)
             st.cells_padded += 2ull * w32.plan[c].npass * w32.plan[c].G * w32.plan[c].K *
@@ -2485,6 +2453,7 @@ extern "C" int swg_search(swg_ctx *ctx, const swg_db *db, int32_t *scores_out, s
 // scores outside the packed form, options that ask for another engine) are searched one after
 // another with swg_search: same results, no batching.
 namespace {
+// The device buffers of one batch call, and the host vectors a chunk is staged from and read back into.
 struct MultiBufs {
     int8_t *d_q = nullptr;
     uint32_t *d_qoff = nullptr;
@@ -2499,35 +2468,45 @@ struct MultiBufs {
     // queries 2y and 2y+1, so a batch of odd size indexes ONE ROW MORE than it has queries.  Round 3 sized these
     // buffers by the queries and a wavefront of the last pair ran off the end ("the fault of round 3").
     size_t rows_scores = 0, rows_order = 0, rows_prof[2] = {0, 0}, rows_cnt = 0, rows_topk = 0;
+    std::vector<int32_t> h_scores;
+    std::vector<uint32_t> qoff32, order, h_meta; // order: row r of the score buffer belongs to query order[r] of the chunk
+    std::vector<uint64_t> h_cand;
     ~MultiBufs()
     {
-        (void)hipFree(d_hist);
-        (void)hipFree(d_meta);
-        (void)hipFree(d_cand);
-        (void)hipFree(d_q);
-        (void)hipFree(d_qoff);
-        (void)hipFree(d_order);
-        (void)hipFree(d_prof[0]);
-        (void)hipFree(d_prof[1]);
-        (void)hipFree(d_scores);
-        (void)hipFree(d_cnt);
+        for (void *p : {(void *)d_hist, (void *)d_meta, (void *)d_cand, (void *)d_q, (void *)d_qoff, (void *)d_order, (void *)d_prof[0],
+                        (void *)d_prof[1], (void *)d_scores, (void *)d_cnt})
+            (void)hipFree(p);
     }
+};
+
+// The queries of a batch: index bytes (one per position), or PSSM rows (32 bytes per position); the n + 1 offsets count
+// positions either way.
+struct MultiQueries {
+    const int8_t *src;
+    const uint64_t *off;
+    size_t n;
+    bool pssm;
+    const char *fn; // the entry point, for messages
+    size_t row_bytes() const { return pssm ? 32 : 1; } // bytes per query position
+    size_t len(size_t i) const { return (size_t)(off[i + 1] - off[i]); }
+    const int8_t *at(size_t i) const { return src + off[i] * row_bytes(); }
 };
 } // namespace
 
-// Every per-query buffer of a batch launch against the rows the launch indexes: Qb queries, Qrows grid rows (query
+// Every per-query buffer of a batch launch against the rows the launch indexes: Qb queries on Qrows grid rows (query
 // pairs when two queries share a lane: the kernels then address score rows 2y and 2y+1 for y < Qrows, i.e. Qb + 1
-// rows for an odd batch).  A mismatch is a bug of this file; it is reported, not launched.
-static int multi_rows_ok(swg_ctx *ctx, const MultiBufs &B, bool qq, size_t Qb, size_t Qrows, int n_classes, bool dev_topk)
+// rows for an odd batch).  What the buffers hold was written down where they were allocated; what the launch indexes
+// comes from the plan, as the launch's own arguments do.  A mismatch is a bug of this file; it is reported, not launched.
+static int multi_rows_ok(swg_ctx *ctx, const MultiBufs &B, const SwgBatchPlan &P, size_t Qb, size_t Qrows)
 {
-    const size_t score_rows = qq ? 2 * Qrows : Qb; // rows of d_scores a launch may write
-    const size_t order_rows = qq ? 2 * Qrows : 0;  // entries of d_order the profile builder may read
+    const bool qq = P.qq;
+    const size_t order_rows = qq ? P.score_rows(Qb) : 0; // entries of d_order the profile builder may read
     struct { const char *name; size_t have, need; } chk[] = {
-        {"d_scores", B.rows_scores, score_rows},       {"d_order", B.rows_order, order_rows},
-        {"d_prof[0]", B.rows_prof[0], Qrows},          {"d_prof[1]", n_classes == 2 ? B.rows_prof[1] : Qrows, Qrows},
-        {"d_cnt", B.rows_cnt, Qrows},                  {"d_hist/d_meta/d_cand", dev_topk ? B.rows_topk : Qb, Qb},
+        {"d_scores", B.rows_scores, P.score_rows(Qb)}, {"d_order", B.rows_order, order_rows},
+        {"d_prof[0]", B.rows_prof[0], Qrows},          {"d_prof[1]", P.wk.n_classes == 2 ? B.rows_prof[1] : Qrows, Qrows},
+        {"d_cnt", B.rows_cnt, Qrows},                  {"d_hist/d_meta/d_cand", P.dev_topk ? B.rows_topk : Qb, Qb},
     };
-    if ((qq && Qrows != (Qb + 1) / 2) || (!qq && Qrows != Qb))
+    if (Qrows != P.grid_rows(Qb))
         return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search_multi: %zu grid rows for %zu queries (qq %d)", Qrows, Qb, (int)qq);
     for (const auto &c : chk)
         if (c.have < c.need)
@@ -2536,54 +2515,12 @@ static int multi_rows_ok(swg_ctx *ctx, const MultiBufs &B, bool qq, size_t Qb, s
     return SWG_OK;
 }
 
-// The queries of a batch: index bytes (one per position), or PSSM rows (32 bytes per position); q_offsets count
-// positions either way.
-struct MultiQueries {
-    const int8_t *src;
-    bool pssm;
-    const char *fn; // the entry point, for messages
-};
-
-static int search_multi_impl(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, const uint64_t *q_offsets,
-                             size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
-                             swg_stats *stats);
-
-extern "C" int swg_search_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets,
-                                size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
-                                swg_stats *stats)
-{
-    try { // no C++ exception crosses the ABI (the body sizes host vectors by the batch)
-        return search_multi_impl(ctx, const_cast<swg_db *>(db), MultiQueries{queries, false, "swg_search_multi"}, q_offsets, n_queries,
-                                 scores_out, topk_out, k, n_hits, stats);
-    } catch (const std::bad_alloc &) {
-        return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "swg_search_multi: out of host memory");
-    } catch (const std::exception &e) {
-        return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "swg_search_multi: %s", e.what());
-    }
-}
-
-extern "C" int swg_search_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets,
-                                     size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
-                                     swg_stats *stats)
-{
-    try {
-        return search_multi_impl(ctx, const_cast<swg_db *>(db), MultiQueries{pssms, true, "swg_search_multi_pssm"}, q_offsets, n_queries,
-                                 scores_out, topk_out, k, n_hits, stats);
-    } catch (const std::bad_alloc &) {
-        return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "swg_search_multi_pssm: out of host memory");
-    } catch (const std::exception &e) {
-        return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "swg_search_multi_pssm: %s", e.what());
-    }
-}
-
-static int search_multi_impl(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, const uint64_t *q_offsets,
-                             size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
-                             swg_stats *stats)
+// What the call's arguments and the context's state rule out, and what the batch is worth whichever way it is searched:
+// the real cells and the algorithmic bytes of all its queries.
+static int validate_batch(swg_ctx *ctx, const swg_db *db, const MultiQueries &mq, const swg_hit *topk_out, size_t k, swg_stats *st)
 {
     const char *fn = mq.fn;
-    const int8_t *queries = mq.src;
-    const size_t row_bytes = mq.pssm ? 32 : 1; // bytes per query position
-    if (!ctx || !db || (n_queries && (!queries || !q_offsets)))
+    if (!ctx || !db || (mq.n && (!mq.src || !mq.off)))
         return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: NULL argument", fn);
     if (k > 0 && !topk_out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: k > 0 but topk_out NULL", fn);
     if (!ctx->have_scoring) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: no scoring set", fn);
@@ -2591,351 +2528,409 @@ static int search_multi_impl(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, c
         return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: database is not resident on device %d", fn, ctx->device);
     for (const SwgSlot &sl : ctx->slots)
         if (sl.busy) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: searches are in flight on this context", fn);
-    swg_stats st;
-    memset(&st, 0, sizeof st);
-    size_t lq_max = 0;
-    for (size_t i = 0; i < n_queries; ++i) {
-        if (q_offsets[i + 1] <= q_offsets[i])
+    for (size_t i = 0; i < mq.n; ++i) {
+        if (mq.off[i + 1] <= mq.off[i])
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: query %zu is empty or the offsets are not increasing", fn, i);
-        const size_t lq = (size_t)(q_offsets[i + 1] - q_offsets[i]);
+        const size_t lq = mq.len(i);
         if (lq > (1u << 24)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: query %zu too long", fn, i);
-        lq_max = std::max(lq_max, lq);
-        for (uint64_t j = q_offsets[i]; j < q_offsets[i + 1] && !mq.pssm; ++j) // (a PSSM takes any int8)
-            if (queries[j] < 1 || queries[j] > 31)
-                return swg_set_ctx_error(ctx, SWG_ERR_RESIDUE, "%s: residue index %d in query %zu outside 1..31", fn,
-                                         queries[j], i);
-        st.cells += (uint64_t)lq * db->residues;
-        st.bytes_alg += db->residues + 8ull * db->n_local + 32ull * lq + 1024ull;
+        for (size_t j = 0; j < lq && !mq.pssm; ++j) // (a PSSM takes any int8)
+            if (mq.at(i)[j] < 1 || mq.at(i)[j] > 31)
+                return swg_set_ctx_error(ctx, SWG_ERR_RESIDUE, "%s: residue index %d in query %zu outside 1..31", fn, mq.at(i)[j], i);
+        st->cells += (uint64_t)lq * db->residues;
+        st->bytes_alg += db->residues + 8ull * db->n_local + 32ull * lq + 1024ull;
     }
-    if (stats) *stats = st;
-    if (n_queries == 0) return SWG_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t n_slots = (size_t)db->n_bins * SWG_BIN;
-    const size_t n_total = db->n_total;
+    return SWG_OK;
+}
 
-    // ---- can the batch go through one launch? ------------------------------------------------
-    const int go = ctx->gap_open + ctx->gap_extend, ge = ctx->gap_extend;
-    bool fast = ctx->gap_open <= 0 && ctx->gap_extend <= 0 && -go <= SWG_I16_CEILING && ctx->opt_force_bits != 32 &&
-                ctx->opt_engine != 1 && ctx->opt_dynamic != 0 && db->n_bins > 0 && n_queries > 1 && ctx->opt_cols == 0 &&
+// Decides how the batch is searched.  One launch per class for a chunk of queries where every query takes one pass of a
+// work-queue class, no score can reach the ceiling of the cells (the batch path has no re-score and no re-run), the gap
+// scores fit the packed form and no option asks for another engine; otherwise one query after another.
+static int plan_batch(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, bool want_scores, size_t k, SwgBatchPlan *plan)
+{
+    *plan = SwgBatchPlan(); // (one after another, unless everything below allows the launch)
+    SwgBatchPlan P;
+    P.chunk_queries = 256;
+    P.first_chunk = std::min(P.chunk_queries, mq.n);
+    P.n_slots = (size_t)db->n_bins * SWG_BIN;
+    P.go = ctx->gap_open + ctx->gap_extend;
+    P.ge = ctx->gap_extend;
+    for (size_t i = 0; i < mq.n; ++i) P.lq_max = std::max(P.lq_max, mq.len(i));
+    bool fast = ctx->gap_open <= 0 && ctx->gap_extend <= 0 && -P.go <= SWG_I16_CEILING && ctx->opt_force_bits != 32 &&
+                ctx->opt_engine != 1 && ctx->opt_dynamic != 0 && db->n_bins > 0 && mq.n > 1 && ctx->opt_cols == 0 &&
                 ctx->opt_group == 0 && ctx->opt_max_waves == 0 && ctx->opt_workgroups == 0;
-    SwgDiagWork wk;
-    const size_t Qb_max = 256; // queries per launch
-    uint64_t bound_max = 0;    // the largest score any query of the batch can reach
-    // no score of any query may reach the int16 ceiling (the batch path has no re-score): each query's swg_score_bound,
-    // as a single search bounds it
+    // no score of any query may reach the int16 ceiling: each query's swg_score_bound, as a single search bounds it
     const uint64_t longest = (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK;
-    for (size_t i = 0; i < n_queries && fast; ++i) {
-        const size_t lq = (size_t)(q_offsets[i + 1] - q_offsets[i]);
-        const SwgScoreBound sb = mq.pssm ? swg_score_bound(queries + q_offsets[i] * 32, nullptr, lq, longest)
-                                         : swg_score_bound(&ctx->sub[0][0], queries + q_offsets[i], lq, longest);
-        bound_max = std::max(bound_max, sb.bound);
+    for (size_t i = 0; i < mq.n && fast; ++i) {
+        const SwgScoreBound sb = mq.pssm ? swg_score_bound(mq.at(i), nullptr, mq.len(i), longest)
+                                         : swg_score_bound(&ctx->sub[0][0], mq.at(i), mq.len(i), longest);
+        P.bound_max = std::max(P.bound_max, sb.bound);
         if (sb.bound >= SWG_I16_CEILING) fast = false;
     }
+    if (!fast) return SWG_OK;
     // the packed-f16 cells (8.5 instead of 10 instructions per column pair) where no query of the batch can reach
-    // their ceiling: the batch path has no re-run either
-    const int form = fast && ctx->opt_f16 != 0 && bound_max < SWG_F16_CEILING && swg_f16_gaps_ok(go, ge) ? 2 : 0;
-    if (fast) {
-        int rc = ensure_pair_tokens(ctx, db);
-        if (rc != SWG_OK) return rc;
-        fast = db->ptok.ok &&
-               swg_plan_diag_work(db, lq_max, ctx->n_cu, 0, 0, 0, ctx->opt_long_split, true, true, &wk,
-                                  (double)std::min(n_queries, Qb_max), form, 1) > 0; // (batches: v_perm_b32 pairing)
-        for (int c = 0; fast && c < wk.n_classes; ++c)
-            fast = wk.plan[c].npass == 1 && diag_class_is_dynamic(ctx, db, wk.plan[c]) && (size_t)wk.plan[c].G * wk.plan[c].K >= lq_max;
-        // A database of short sequences is faster on the systolic engine, one query after another, than as a batch on
-        // the lane groups: 16 queries against 500 000 peptides 3 720 GCUPS as a batch, ~7 000 one by one.  Same
-        // comparison as a single search makes, per query.
-        int sys_K = 0;
-        if (fast && systolic_beats_lane_groups(ctx, db, lq_max, wk.plan[0], form, bound_max, std::min(n_queries, Qb_max), &sys_K)) fast = false;
-    }
-    if (!fast) {
-        // one after another; the context's own query is put back afterwards (a PSSM as a PSSM)
-        const bool keep_pssm = ctx->query_pssm;
-        const std::vector<int8_t> keep = keep_pssm ? ctx->pssm : ctx->query;
-        int rc = SWG_OK;
-        swg_stats one;
-        for (size_t i = 0; i < n_queries && rc == SWG_OK; ++i) {
-            const size_t lq = (size_t)(q_offsets[i + 1] - q_offsets[i]);
-            rc = mq.pssm ? swg_set_query_pssm(ctx, queries + q_offsets[i] * 32, lq) : swg_set_query(ctx, queries + q_offsets[i], lq);
-            if (rc == SWG_OK)
-                rc = search_now(ctx, db, ctx->opt_autotune != 0, scores_out ? scores_out + i * n_total : nullptr,
-                                topk_out ? topk_out + i * k : nullptr, k, n_hits ? n_hits + i : nullptr, &one);
-            if (rc == SWG_OK) {
-                st.fill_ms += one.fill_ms;
-                st.rescore_ms += one.rescore_ms;
-                st.topk_ms += one.topk_ms;
-                st.total_ms += one.total_ms;
-                st.n_rescored += one.n_rescored;
-                st.cells_padded += one.cells_padded;
-                st.path_bits = one.path_bits;
-                st.cell_form = one.cell_form;
-                st.engine = one.engine;
-                st.cols_per_wave = one.cols_per_wave;
-                st.group_lanes = one.group_lanes;
-                st.waves = one.waves;
-                st.passes = one.passes;
-                st.workgroups = one.workgroups;
-                st.work_queue = one.work_queue;
-            }
-        }
-        if (!keep.empty()) {
-            const int rq = keep_pssm ? swg_set_query_pssm(ctx, keep.data(), keep.size() / 32) : swg_set_query(ctx, keep.data(), keep.size());
-            if (rc == SWG_OK) rc = rq;
-        } else {
-            ctx->query.clear();
-        }
-        if (stats) *stats = st;
-        return rc;
-    }
-
-    // ---- one launch per class for up to Qb_max queries ----------------------------------------
+    // their ceiling
+    P.form = ctx->opt_f16 != 0 && P.bound_max < SWG_F16_CEILING && swg_f16_gaps_ok(P.go, P.ge) ? 2 : 0;
+    int rc = ensure_pair_tokens(ctx, db);
+    if (rc != SWG_OK) return rc;
+    SwgDiagWork &wk = P.wk;
+    fast = db->ptok.ok && swg_plan_diag_work(db, P.lq_max, ctx->n_cu, 0, 0, 0, ctx->opt_long_split, true, true, &wk, (double)P.first_chunk,
+                                             P.form, 1) > 0; // (batches: v_perm_b32 pairing)
+    for (int c = 0; fast && c < wk.n_classes; ++c)
+        fast = wk.plan[c].npass == 1 && diag_class_is_dynamic(ctx, db, wk.plan[c]) && (size_t)wk.plan[c].G * wk.plan[c].K >= P.lq_max;
+    // A database of short sequences is faster on the systolic engine, one query after another, than as a batch on
+    // the lane groups: 16 queries against 500 000 peptides 3 720 GCUPS as a batch, ~7 000 one by one.  Same
+    // comparison as a single search makes, per query.
+    int sys_K = 0;
+    if (!fast || systolic_beats_lane_groups(ctx, db, P.lq_max, wk.plan[0], P.form, P.bound_max, P.first_chunk, &sys_K)) return SWG_OK;
     // Two queries per lane (swg_diag_qq_kernel, 7.5 instead of 8.5 instructions per column pair: the two halves of a
     // register hold two QUERIES against one sequence, so no v_perm pairs two sequences' profile words) where the batch
     // runs on the f16 cells and the pairs' 4-byte profile fits LDS beside the other class's; option "qq" = 0 turns it off.
-    bool qq = form == 2 && ctx->opt_qq != 0;
-    int qq_per_cu = 1;
-    if (qq) {
-        // The pairs' profile is twice the size, so LDS decides the occupancy (as for the int32 kernel): the long class
-        // keeps one workgroup of four wavefronts per CU, the bulk takes the workgroup size -- 4, 8, 12 or 16 wavefronts
-        // sharing one profile -- that leaves the most wavefronts resident (four 57 KB workgroups of four do not fit a
-        // CU; two of eight do: the first version of this path ran at two wavefronts per SIMD and lost to the perm).
-        size_t room = 160 * 1024;
-        const SwgKernelInfo info = swg_diag_variant_info(wk.plan[0].variant);
-        int cap_waves = info.max_waves;
-        if (wk.n_classes == 2) {
-            wk.plan[1].W = 4;
-            room -= std::min(room, swg_diag32q_lds_bytes(wk.plan[1].K, wk.plan[1].G, 4));
-            cap_waves -= 4;
-        }
-        int best_W = 0, best_waves = 0;
-        for (int W = 4; W <= info.max_waves; W += 4) {
-            const int n = std::min<int>((int)(room / swg_diag32q_lds_bytes(wk.plan[0].K, wk.plan[0].G, W)), cap_waves / W);
-            if (n >= 1 && n * W > best_waves) best_waves = n * W, best_W = W, qq_per_cu = n;
-        }
-        if (best_W == 0) qq = false; // (no room beside the long class: two sequences per lane, as before)
-        else wk.plan[0].W = best_W;
+    // The pairs' profile is twice the size, so LDS decides the occupancy (as for the int32 kernel, but up to every
+    // wavefront the instantiation allows): four 57 KB workgroups of four do not fit a CU, two of eight do -- the first
+    // version of this path ran at two wavefronts per SIMD and lost to the perm.  No room beside the long class: two
+    // sequences per lane, as without the option.
+    int qq_W = 0;
+    P.qq = P.form == 2 && ctx->opt_qq != 0 && lds_bound_workgroup(wk, INT_MAX, 0, &qq_W, &P.qq_per_cu);
+    if (P.qq) {
+        wk.plan[0].W = qq_W;
+        if (wk.n_classes == 2) wk.plan[1].W = 4;
     }
-    const SwgPairTokens &T = db->ptok;
-    const uint32_t cnt_class = SWG_DYN_SHARDS * SWG_DYN_SHARD_STRIDE; // queue dwords of one class of one query
-    MultiBufs B;
-    std::vector<int32_t> h_scores;
-    std::vector<uint32_t> qoff32, order, h_meta;
-    std::vector<uint64_t> h_cand;
     // Top-K only (no score array asked for): selected on the device for the whole batch in three launches, and a few
     // hundred keys per query come back instead of every score (round 3: with 32 queries against 100 000 sequences the
     // copy and the host's selection took longer than the fill: 82 ms of wall time for 49 ms of device time).
-    const bool dev_topk = scores_out == nullptr && k > 0 && k <= SWG_TOPK_MULTI_CAP / 2;
-    hipStream_t s = ctx->stream;
-    ctx->cur = &ctx->slots[0];
-    for (size_t q0 = 0; q0 < n_queries; q0 += Qb_max) {
-        const size_t Qb = std::min(Qb_max, n_queries - q0);
-        const size_t Qrows = qq ? (Qb + 1) / 2 : Qb; // rows of the grid: query pairs, or queries
-        const uint64_t qbytes = (q_offsets[q0 + Qb] - q_offsets[q0]) * row_bytes;
-        try {
-            qoff32.resize(Qb + 1);
-            if (!dev_topk) h_scores.resize(Qb * n_slots);
-            if (dev_topk) {
-                h_meta.resize(Qb * 4);
-                h_cand.resize(Qb * (size_t)SWG_TOPK_MULTI_CAP);
-            }
-        } catch (const std::exception &) {
-            return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "%s: out of host memory", fn);
-        }
-        for (size_t i = 0; i <= Qb; ++i) qoff32[i] = (uint32_t)(q_offsets[q0 + i] - q_offsets[q0]);
-        // qq: queries of similar length share a lane (row r of the score buffer belongs to query order[r] of this chunk)
-        order.resize(Qb);
-        for (size_t i = 0; i < Qb; ++i) order[i] = (uint32_t)i;
-        if (qq)
-            std::stable_sort(order.begin(), order.end(),
-                             [&](uint32_t a, uint32_t b) { return qoff32[a + 1] - qoff32[a] > qoff32[b + 1] - qoff32[b]; });
-        if (q0 == 0) {
-            // rows are counted in QUERIES for scores / order / top-K, in grid rows (query pairs with qq) for the
-            // profiles and the queues; a qq batch gets an even number of query rows, so that the absent partner of an
-            // odd batch's last query has a row of its own everywhere (nothing reads it back)
-            const size_t qm = std::min(Qb_max, n_queries);
-            const size_t q_rows = qq ? (qm + 1) / 2 * 2 : qm, g_rows = qq ? (qm + 1) / 2 : qm;
-            const size_t cnt_dwords = Qb_max * 2 * cnt_class + 2 * SWG_DYN_SIMD_SLOTS;
-            HIP_TRY(ctx, hipMalloc(&B.d_cnt, cnt_dwords * 4));
-            B.rows_cnt = Qb_max;
-            HIP_TRY(ctx, hipMalloc(&B.d_scores, q_rows * n_slots * 4));
-            B.rows_scores = q_rows;
-            HIP_TRY(ctx, hipMalloc(&B.d_qoff, (Qb_max + 1) * 4));
-            HIP_TRY(ctx, hipMalloc(&B.d_order, (Qb_max + 1) * 4));
-            B.rows_order = Qb_max + 1;
-            if (dev_topk) {
-                HIP_TRY(ctx, hipMalloc(&B.d_hist, qm * 4096 * 4));
-                HIP_TRY(ctx, hipMalloc(&B.d_meta, qm * 16));
-                HIP_TRY(ctx, hipMalloc(&B.d_cand, qm * (size_t)SWG_TOPK_MULTI_CAP * 8));
-                B.rows_topk = qm;
-            }
-            for (int c = 0; c < wk.n_classes; ++c) {
-                // (qq: one profile of 128 bytes per column per query PAIR, and an odd batch's last pair is a whole pair)
-                const size_t per_row = (size_t)wk.plan[c].G * (qq ? (size_t)swg_q32_padded_cols(wk.plan[c].K) * 128 : (size_t)swg_diag_padded_cols(wk.plan[c].K) * 64);
-                HIP_TRY(ctx, hipMalloc(&B.d_prof[c], g_rows * per_row));
-                B.rows_prof[c] = g_rows;
-            }
-        }
-        {
-            // the fence: what this chunk's launches will index, against what the buffers hold
-            const int rf = multi_rows_ok(ctx, B, qq, Qb, Qrows, wk.n_classes, dev_topk);
-            if (rf != SWG_OK) return rf;
-        }
-        (void)hipFree(B.d_q);
-        B.d_q = nullptr;
-        HIP_TRY(ctx, hipMalloc(&B.d_q, std::max<uint64_t>(4, qbytes)));
-        HIP_TRY(ctx, hipMemcpyAsync(B.d_q, queries + q_offsets[q0] * row_bytes, qbytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(B.d_qoff, qoff32.data(), (Qb + 1) * 4, hipMemcpyHostToDevice, s));
-        order.push_back(order.back()); // (qq, odd batch: the last pair's absent partner is its query once more)
-        HIP_TRY(ctx, hipMemcpyAsync(B.d_order, order.data(), (Qb + 1) * 4, hipMemcpyHostToDevice, s));
-        order.pop_back();
-        HIP_TRY(ctx, hipMemsetAsync(B.d_scores, 0, (qq ? 2 * Qrows : Qb) * n_slots * 4, s));
-        HIP_TRY(ctx, hipMemsetAsync(B.d_cnt, 0, (Qb_max * 2 * cnt_class + 2 * SWG_DYN_SIMD_SLOTS) * 4, s));
-        const int8_t *d_idx = mq.pssm ? nullptr : B.d_q, *d_pssms = mq.pssm ? B.d_q : nullptr; // (the builders' two sources)
-        for (int c = 0; c < wk.n_classes; ++c) {
-            const SwgDiagPlan &pl = wk.plan[c];
-            if (qq)
-                HIP_TRY(ctx, swg_launch_build_profiles_qq(ctx->d_sub, d_idx, B.d_qoff, B.d_order, (uint32_t)Qb,
-                                                          (uint32_t)(pl.G * swg_q32_padded_cols(pl.K)), pl.K, swg_q32_padded_cols(pl.K),
-                                                          B.d_prof[c], s, SWG_LDS_SWIZZLE ? pl.G : 0, d_pssms));
-            else
-                HIP_TRY(ctx, swg_launch_build_profiles_multi(ctx->d_sub, d_idx, B.d_qoff, (uint32_t)Qb,
-                                                             (uint32_t)(pl.G * swg_diag_padded_cols(pl.K)), pl.K,
-                                                             swg_diag_padded_cols(pl.K), B.d_prof[c], s, SWG_LDS_SWIZZLE ? pl.G : 0, form == 2,
-                                                             d_pssms));
-        }
-        // workgroups per query: the chip's resident workgroups shared out over the batch
-        int wgs[2] = {1, 1};
-        uint64_t groups0 = 1;
-        for (int c = 0; c < wk.n_classes; ++c) {
-            const SwgDiagPlan &pl = wk.plan[c];
-            const SwgKernelInfo info = swg_diag_variant_info(pl.variant);
-            const size_t lds = qq ? swg_diag32q_lds_bytes(pl.K, pl.G, pl.W) : swg_diag_dyn_lds_bytes(pl.K, pl.G, pl.W);
-            const int per_cu = qq ? (c == 0 ? qq_per_cu : 1) : std::max(1, std::min<int>(info.max_waves / pl.W, (int)((160 * 1024) / lds)));
-            int total = ctx->n_cu * per_cu;
-            if (wk.n_classes == 2 && !qq) total = c == 1 ? ctx->n_cu : std::max(ctx->n_cu, total - ctx->n_cu); // one wavefront per SIMD for the long class
-            const uint64_t items = (wk.pair_end[c] - wk.pair_begin[c]) * (qq ? 2u : 1u); // pairs, or (qq) single sequences
-            const uint64_t per_wg = (uint64_t)pl.W * (64 / pl.G);
-            wgs[c] = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)total / Qrows, (items + per_wg - 1) / per_wg));
-            if (c == 0) groups0 = (uint64_t)wgs[0] * Qrows * per_wg;
-        }
-        HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[1], s));
-        if (wk.n_classes == 2) {
-            const int r2 = ensure_stream2(ctx);
-            if (r2 != SWG_OK) return r2;
-            HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[6], s));
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->cur->ev[6], 0));
-        }
-        for (int c = wk.n_classes - 1; c >= 0; --c) {
-            const SwgDiagPlan &pl = wk.plan[c];
-            if (qq) {
-                SwgDiagQQParams q;
-                memset(&q, 0, sizeof q);
-                q.tok = T.d_tok;
-                q.zero_block = (uint32_t)T.total_blocks;
-                q.pair_off = T.d_pair_off;
-                q.q_begin = (uint32_t)std::min<uint64_t>(2 * wk.pair_begin[c], n_slots);
-                q.q_end = (uint32_t)std::min<uint64_t>(2 * wk.pair_end[c], n_slots);
-                q.queue = B.d_cnt + (size_t)c * cnt_class;
-                q.queue_stride = 2 * cnt_class;
-                q.profile = B.d_prof[c];
-                q.profile_stride = (uint64_t)pl.G * swg_q32_padded_cols(pl.K) * 128;
-                q.scores = B.d_scores;
-                q.score_stride = n_slots;
-                q.n_queries = (uint32_t)Qb;
-                q.seq_limit = (uint32_t)n_slots;
-                q.G = (uint32_t)pl.G;
-                q.go = f16x2_of(-go);
-                q.ge = f16x2_of(-ge);
-                q.prio_blocks = 0xFFFFFFFFu;
-                if (c == 0) {
-                    const uint64_t blocks = 2ull * (uint64_t)(T.pair_blocks_prefix[wk.pair_end[0]] - T.pair_blocks_prefix[wk.pair_begin[0]]) * Qrows;
-                    q.prio_blocks = (uint32_t)std::max<uint64_t>(8, (uint64_t)(ctx->opt_prio_share * 0.01 * (double)blocks / (double)groups0));
-                } else {
-                    q.prio_blocks = 0u;
-                }
-                q.turn_levels = wk.n_classes == 2 ? 3u : 4u;
-                q.simd_ranks = B.d_cnt + Qb_max * 2 * cnt_class + (size_t)c * SWG_DYN_SIMD_SLOTS;
-                HIP_TRY(ctx, swg_launch_diag_qq(pl.variant, pl.W, wgs[c], (int)Qrows, q, c == 1 ? ctx->stream2 : s));
-                continue;
-            }
-            SwgDiagDynParams q = dyn_params_base(T, B.d_scores, n_slots, pl.G, form, go, ge, wk.n_classes,
-                                                 B.d_cnt + Qb_max * 2 * cnt_class + (size_t)c * SWG_DYN_SIMD_SLOTS);
-            q.q_begin = (uint32_t)wk.pair_begin[c];
-            q.q_end = (uint32_t)wk.pair_end[c];
-            q.queue = B.d_cnt + (size_t)c * cnt_class;
-            q.queue_stride = 2 * cnt_class;
-            q.profile = B.d_prof[c];
-            q.profile_stride = (uint64_t)pl.G * swg_diag_padded_cols(pl.K) * 64;
-            q.score_stride = n_slots;
-            if (c == 0) {
-                const uint64_t blocks = (uint64_t)(T.pair_blocks_prefix[wk.pair_end[0]] - T.pair_blocks_prefix[wk.pair_begin[0]]) * Qb;
-                q.prio_blocks = (uint32_t)std::max<uint64_t>(8, (uint64_t)(ctx->opt_prio_share * 0.01 * (double)blocks / (double)groups0));
-            }
-            dyn_batch_zones(ctx, T, &q, (uint64_t)wgs[c] * pl.W * (64 / pl.G), pl.K, pl.G, form);
-            HIP_TRY(ctx, swg_launch_diag_dyn(pl.variant, false, form, pl.W, wgs[c], q, c == 1 ? ctx->stream2 : s, (int)Qb));
-        }
-        if (wk.n_classes == 2) {
-            HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[7], ctx->stream2));
-            HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->cur->ev[7], 0));
-        }
-        HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[2], s));
-        if (dev_topk) {
-            HIP_TRY(ctx, swg_launch_topk_multi(B.d_scores, n_slots, db->d_order, (uint32_t)n_slots, (uint32_t)Qb, (uint32_t)k, B.d_hist,
-                                               B.d_meta, B.d_cand, SWG_TOPK_MULTI_CAP, s));
-            HIP_TRY(ctx, hipMemcpyAsync(h_meta.data(), B.d_meta, Qb * 16, hipMemcpyDeviceToHost, s));
-            HIP_TRY(ctx, hipMemcpyAsync(h_cand.data(), B.d_cand, Qb * (size_t)SWG_TOPK_MULTI_CAP * 8, hipMemcpyDeviceToHost, s));
-        } else {
-            HIP_TRY(ctx, hipMemcpyAsync(h_scores.data(), B.d_scores, Qb * n_slots * 4, hipMemcpyDeviceToHost, s));
-        }
-        HIP_TRY(ctx, spin_sync(ctx, s));
-        float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->cur->ev[1], ctx->cur->ev[2]));
-        st.fill_ms += ms;
-        st.total_ms += ms;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (size_t r = 0; r < Qb; ++r) { // (row r of the score buffer = query order[r] of this chunk)
-            const size_t i = order[r];
-            if (dev_topk && h_meta[4 * r + 1] == 0 && h_meta[4 * r + 2] <= SWG_TOPK_MULTI_CAP) {
-                // every hit with a score >= the k-th best one: sort those few keys
-                uint64_t *c = h_cand.data() + r * (size_t)SWG_TOPK_MULTI_CAP;
-                const size_t nc = h_meta[4 * r + 2], m = std::min(k, nc);
-                std::partial_sort(c, c + m, c + nc, std::greater<uint64_t>());
-                for (size_t j = 0; j < m; ++j) swg_key_hit(c[j], &topk_out[(q0 + i) * k + j]);
-                if (n_hits) n_hits[q0 + i] = m;
-                continue;
-            }
-            if (dev_topk) { // threshold beyond the histogram, or too many ties: this query's scores to the host after all
-                if (h_scores.size() < n_slots) h_scores.resize(n_slots);
-                HIP_TRY(ctx, hipMemcpyAsync(h_scores.data(), B.d_scores + r * n_slots, n_slots * 4, hipMemcpyDeviceToHost, s));
-                HIP_TRY(ctx, spin_sync(ctx, s));
-                deliver_scores(db, h_scores.data(), n_slots, nullptr, topk_out + (q0 + i) * k, k, n_hits ? n_hits + q0 + i : nullptr);
-                continue;
-            }
-            deliver_scores(db, h_scores.data() + r * n_slots, n_slots, scores_out ? scores_out + (q0 + i) * n_total : nullptr,
-                           topk_out ? topk_out + (q0 + i) * k : nullptr, k, n_hits ? n_hits + q0 + i : nullptr);
-        }
-        st.topk_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        st.workgroups = wgs[0] * (int)Qrows;
-        st.streams = (int32_t)groups0;
+    P.dev_topk = !want_scores && k > 0 && k <= SWG_TOPK_MULTI_CAP / 2;
+    // The buffers: rows are counted in QUERIES for scores / order / top-K, in grid rows (query pairs with qq) for the
+    // profiles and the queues.
+    P.score_rows_cap = P.score_rows(P.first_chunk);
+    P.grid_rows_cap = P.grid_rows(P.first_chunk);
+    P.order_entries = P.chunk_queries + 1;
+    P.class_queue_dwords = SWG_DYN_SHARDS * SWG_DYN_SHARD_STRIDE;
+    P.rank_word_base = P.chunk_queries * 2 * P.class_queue_dwords; // (the queues serve a full chunk's grid rows)
+    P.queue_dwords = P.rank_word_base + 2 * SWG_DYN_SIMD_SLOTS;
+    for (int c = 0; c < wk.n_classes; ++c) // (qq: one profile of 128 bytes per column per query PAIR, and an odd batch's last pair is a whole pair)
+        P.prof_row_bytes[c] = (size_t)wk.plan[c].G * (P.qq ? (size_t)swg_q32_padded_cols(wk.plan[c].K) * 128 : (size_t)swg_diag_padded_cols(wk.plan[c].K) * 64);
+    P.one_launch = true;
+    *plan = P;
+    return SWG_OK;
+}
+
+// One query after another with swg_search's own body; the context's own query is put back afterwards (a PSSM as a
+// PSSM), whether or not a query failed.  Statistics: the times, the re-scored sequences and the padded cells add up,
+// the geometry is the last search's; what a single search reports beyond that (lane groups, the long class, launches)
+// stays zero, as this route has always reported it.
+static int search_batch_one_by_one(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, int32_t *scores_out, swg_hit *topk_out, size_t k,
+                                   size_t *n_hits, swg_stats *st)
+{
+    const bool keep_pssm = ctx->query_pssm;
+    const std::vector<int8_t> keep = keep_pssm ? ctx->pssm : ctx->query;
+    int rc = SWG_OK;
+    for (size_t i = 0; i < mq.n && rc == SWG_OK; ++i) {
+        swg_stats one;
+        rc = mq.pssm ? swg_set_query_pssm(ctx, mq.at(i), mq.len(i)) : swg_set_query(ctx, mq.at(i), mq.len(i));
+        if (rc == SWG_OK)
+            rc = search_now(ctx, db, ctx->opt_autotune != 0, scores_out ? scores_out + i * db->n_total : nullptr,
+                            topk_out ? topk_out + i * k : nullptr, k, n_hits ? n_hits + i : nullptr, &one);
+        if (rc != SWG_OK) break;
+        st->fill_ms += one.fill_ms;
+        st->rescore_ms += one.rescore_ms;
+        st->topk_ms += one.topk_ms;
+        st->total_ms += one.total_ms;
+        st->n_rescored += one.n_rescored;
+        st->cells_padded += one.cells_padded;
+        st->path_bits = one.path_bits;
+        st->cell_form = one.cell_form;
+        st->engine = one.engine;
+        st->cols_per_wave = one.cols_per_wave;
+        st->group_lanes = one.group_lanes;
+        st->waves = one.waves;
+        st->passes = one.passes;
+        st->workgroups = one.workgroups;
+        st->work_queue = one.work_queue;
     }
-    st.path_bits = 16;
-    st.engine = 2;
-    st.work_queue = 1;
-    st.classes_overlapped = -1; // (not measured for a batch)
-    st.cell_form = qq ? 3 : form;
-    st.cols_per_wave = wk.plan[0].K;
-    st.group_lanes = wk.plan[0].G;
-    st.waves = wk.plan[0].W;
-    st.passes = 1;
-    st.fill_launches = 1;
+    if (!keep.empty()) {
+        const int rq = keep_pssm ? swg_set_query_pssm(ctx, keep.data(), keep.size() / 32) : swg_set_query(ctx, keep.data(), keep.size());
+        if (rc == SWG_OK) rc = rq;
+    } else {
+        ctx->query.clear();
+    }
+    return rc;
+}
+
+// ---- one launch per class for up to chunk_queries queries: the stages -----------------------------
+// Every device buffer of the call, by the plan's sizes, each with the rows it holds written beside it (multi_rows_ok).
+static int batch_allocate(swg_ctx *ctx, const SwgBatchPlan &P, MultiBufs *B)
+{
+    HIP_TRY(ctx, hipMalloc(&B->d_cnt, P.queue_dwords * 4));
+    B->rows_cnt = P.chunk_queries;
+    HIP_TRY(ctx, hipMalloc(&B->d_scores, P.score_rows_cap * P.n_slots * 4));
+    B->rows_scores = P.score_rows_cap;
+    HIP_TRY(ctx, hipMalloc(&B->d_qoff, P.order_entries * 4));
+    HIP_TRY(ctx, hipMalloc(&B->d_order, P.order_entries * 4));
+    B->rows_order = P.order_entries;
+    if (P.dev_topk) {
+        HIP_TRY(ctx, hipMalloc(&B->d_hist, P.first_chunk * 4096 * 4));
+        HIP_TRY(ctx, hipMalloc(&B->d_meta, P.first_chunk * 16));
+        HIP_TRY(ctx, hipMalloc(&B->d_cand, P.first_chunk * (size_t)SWG_TOPK_MULTI_CAP * 8));
+        B->rows_topk = P.first_chunk;
+    }
+    for (int c = 0; c < P.wk.n_classes; ++c) {
+        HIP_TRY(ctx, hipMalloc(&B->d_prof[c], P.grid_rows_cap * P.prof_row_bytes[c]));
+        B->rows_prof[c] = P.grid_rows_cap;
+    }
+    return SWG_OK;
+}
+
+// The queries [q0, q0 + Qb) to the device -- their bytes, their offsets, (qq) the order that pairs them --, scores and
+// queues zeroed, and every class's profiles built.
+static int batch_stage_chunk(swg_ctx *ctx, const SwgBatchPlan &P, const MultiQueries &mq, size_t q0, size_t Qb, MultiBufs *B)
+{
+    hipStream_t s = ctx->stream;
+    std::vector<uint32_t> &qoff32 = B->qoff32, &order = B->order;
+    qoff32.resize(Qb + 1); // (a failed host allocation is reported by the entry point's guard)
+    if (P.dev_topk) {
+        B->h_meta.resize(Qb * 4);
+        B->h_cand.resize(Qb * (size_t)SWG_TOPK_MULTI_CAP);
+    } else {
+        B->h_scores.resize(Qb * P.n_slots);
+    }
+    for (size_t i = 0; i <= Qb; ++i) qoff32[i] = (uint32_t)(mq.off[q0 + i] - mq.off[q0]);
+    // qq: queries of similar length share a lane
+    order.resize(Qb);
+    for (size_t i = 0; i < Qb; ++i) order[i] = (uint32_t)i;
+    if (P.qq)
+        std::stable_sort(order.begin(), order.end(),
+                         [&](uint32_t a, uint32_t b) { return qoff32[a + 1] - qoff32[a] > qoff32[b + 1] - qoff32[b]; });
+    const uint64_t qbytes = (mq.off[q0 + Qb] - mq.off[q0]) * mq.row_bytes();
+    (void)hipFree(B->d_q);
+    B->d_q = nullptr;
+    HIP_TRY(ctx, hipMalloc(&B->d_q, std::max<uint64_t>(4, qbytes)));
+    HIP_TRY(ctx, hipMemcpyAsync(B->d_q, mq.at(q0), qbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(B->d_qoff, qoff32.data(), (Qb + 1) * 4, hipMemcpyHostToDevice, s));
+    order.push_back(order.back()); // (qq, odd batch: the last pair's absent partner is its query once more)
+    HIP_TRY(ctx, hipMemcpyAsync(B->d_order, order.data(), (Qb + 1) * 4, hipMemcpyHostToDevice, s));
+    order.pop_back();
+    HIP_TRY(ctx, hipMemsetAsync(B->d_scores, 0, P.score_rows(Qb) * P.n_slots * 4, s));
+    HIP_TRY(ctx, hipMemsetAsync(B->d_cnt, 0, P.queue_dwords * 4, s));
+    const int8_t *d_idx = mq.pssm ? nullptr : B->d_q, *d_pssms = mq.pssm ? B->d_q : nullptr; // (the builders' two sources)
+    for (int c = 0; c < P.wk.n_classes; ++c) {
+        const SwgDiagPlan &pl = P.wk.plan[c];
+        if (P.qq)
+            HIP_TRY(ctx, swg_launch_build_profiles_qq(ctx->d_sub, d_idx, B->d_qoff, B->d_order, (uint32_t)Qb,
+                                                      (uint32_t)(pl.G * swg_q32_padded_cols(pl.K)), pl.K, swg_q32_padded_cols(pl.K),
+                                                      B->d_prof[c], s, SWG_LDS_SWIZZLE ? pl.G : 0, d_pssms));
+        else
+            HIP_TRY(ctx, swg_launch_build_profiles_multi(ctx->d_sub, d_idx, B->d_qoff, (uint32_t)Qb,
+                                                         (uint32_t)(pl.G * swg_diag_padded_cols(pl.K)), pl.K,
+                                                         swg_diag_padded_cols(pl.K), B->d_prof[c], s, SWG_LDS_SWIZZLE ? pl.G : 0, P.form == 2,
+                                                         d_pssms));
+    }
+    return SWG_OK;
+}
+
+// Workgroups per grid row of each class for a chunk of Qrows grid rows -- the chip's resident workgroups shared out
+// over the chunk -- and the bulk's lane groups over the whole grid.
+static void batch_chunk_workgroups(const SwgBatchPlan &P, size_t Qrows, int n_cu, int wgs[2], uint64_t *groups0)
+{
+    const SwgDiagWork &wk = P.wk;
+    wgs[0] = wgs[1] = 1;
+    *groups0 = 1;
+    for (int c = 0; c < wk.n_classes; ++c) {
+        const SwgDiagPlan &pl = wk.plan[c];
+        const int per_cu = P.qq ? (c == 0 ? P.qq_per_cu : 1)
+                                : swg_workgroups_per_cu(swg_diag_variant_info(pl.variant).max_waves, pl.W, swg_diag_dyn_lds_bytes(pl.K, pl.G, pl.W));
+        int total = n_cu * per_cu;
+        if (wk.n_classes == 2 && !P.qq) total = c == 1 ? n_cu : std::max(n_cu, total - n_cu); // one wavefront per SIMD for the long class
+        const uint64_t items = (wk.pair_end[c] - wk.pair_begin[c]) * (P.qq ? 2u : 1u); // pairs, or (qq) single sequences
+        const uint64_t per_wg = (uint64_t)pl.W * (64 / pl.G);
+        wgs[c] = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)total / Qrows, (items + per_wg - 1) / per_wg));
+        if (c == 0) *groups0 = (uint64_t)wgs[0] * Qrows * per_wg;
+    }
+}
+
+// The fill of one chunk: a launch per class, the grid's row y working for query (qq: query pair) y.  Events: ev[1]
+// before, ev[2] after on the main stream.
+static int batch_launch_chunk(swg_ctx *ctx, const swg_db *db, const SwgBatchPlan &P, const MultiBufs &B, size_t Qb, size_t Qrows)
+{
+    hipStream_t s = ctx->stream;
+    const SwgDiagWork &wk = P.wk;
+    const SwgPairTokens &T = db->ptok;
+    const size_t n_slots = P.n_slots;
+    int wgs[2];
+    uint64_t groups0;
+    batch_chunk_workgroups(P, Qrows, ctx->n_cu, wgs, &groups0);
+    const uint64_t bulk_blocks = (uint64_t)(T.pair_blocks_prefix[wk.pair_end[0]] - T.pair_blocks_prefix[wk.pair_begin[0]]);
+    HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[1], s));
+    int rf = fork_long_class(ctx, wk);
+    if (rf != SWG_OK) return rf;
+    for (int c = wk.n_classes - 1; c >= 0; --c) {
+        const SwgDiagPlan &pl = wk.plan[c];
+        uint32_t *simd_ranks = B.d_cnt + P.rank_word_base + (size_t)c * SWG_DYN_SIMD_SLOTS;
+        hipStream_t qs = c == 1 ? ctx->stream2 : s;
+        auto per_row = [&](auto *q) { // grid row y: its own queue, profile and score rows
+            q->queue = B.d_cnt + (size_t)c * P.class_queue_dwords;
+            q->queue_stride = 2 * P.class_queue_dwords;
+            q->profile = B.d_prof[c];
+            q->profile_stride = P.prof_row_bytes[c];
+            q->score_stride = n_slots;
+        };
+        if (P.qq) {
+            SwgDiagQQParams q = token_params<SwgDiagQQParams>(T, pl.G, wk.n_classes, simd_ranks);
+            per_row(&q);
+            q.q_begin = (uint32_t)std::min<uint64_t>(2 * wk.pair_begin[c], n_slots);
+            q.q_end = (uint32_t)std::min<uint64_t>(2 * wk.pair_end[c], n_slots);
+            q.scores = B.d_scores;
+            q.n_queries = (uint32_t)Qb;
+            q.seq_limit = (uint32_t)n_slots;
+            q.go = f16x2_of(-P.go);
+            q.ge = f16x2_of(-P.ge);
+            q.prio_blocks = c == 0 ? bulk_prio_blocks(ctx, 2ull * bulk_blocks * Qrows, groups0) : 0u;
+            HIP_TRY(ctx, swg_launch_diag_qq(pl.variant, pl.W, wgs[c], (int)Qrows, q, qs));
+            continue;
+        }
+        SwgDiagDynParams q = dyn_params_base(T, B.d_scores, n_slots, pl.G, P.form, P.go, P.ge, wk.n_classes, simd_ranks);
+        per_row(&q);
+        q.q_begin = (uint32_t)wk.pair_begin[c];
+        q.q_end = (uint32_t)wk.pair_end[c];
+        if (c == 0) q.prio_blocks = bulk_prio_blocks(ctx, bulk_blocks * Qb, groups0);
+        dyn_batch_zones(ctx, T, &q, (uint64_t)wgs[c] * pl.W * (64 / pl.G), pl.K, pl.G, P.form);
+        HIP_TRY(ctx, swg_launch_diag_dyn(pl.variant, false, P.form, pl.W, wgs[c], q, qs, (int)Qb));
+    }
+    rf = join_long_class(ctx, wk, false); // (a batch does not time its classes)
+    if (rf != SWG_OK) return rf;
+    HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[2], s));
+    return SWG_OK;
+}
+
+// What a chunk's fill left, to the caller: (device top-K) the few keys per query, or every score, after which the host
+// selects.  Adds the chunk's times to *st.
+static int batch_deliver_chunk(swg_ctx *ctx, const swg_db *db, const SwgBatchPlan &P, MultiBufs *B, size_t q0, size_t Qb, size_t k,
+                               int32_t *scores_out, swg_hit *topk_out, size_t *n_hits, swg_stats *st)
+{
+    hipStream_t s = ctx->stream;
+    const size_t n_slots = P.n_slots, n_total = db->n_total;
+    std::vector<int32_t> &h_scores = B->h_scores;
+    const std::vector<uint32_t> &h_meta = B->h_meta;
+    if (P.dev_topk) {
+        HIP_TRY(ctx, swg_launch_topk_multi(B->d_scores, n_slots, db->d_order, (uint32_t)n_slots, (uint32_t)Qb, (uint32_t)k, B->d_hist,
+                                           B->d_meta, B->d_cand, SWG_TOPK_MULTI_CAP, s));
+        HIP_TRY(ctx, hipMemcpyAsync(B->h_meta.data(), B->d_meta, Qb * 16, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipMemcpyAsync(B->h_cand.data(), B->d_cand, Qb * (size_t)SWG_TOPK_MULTI_CAP * 8, hipMemcpyDeviceToHost, s));
+    } else {
+        HIP_TRY(ctx, hipMemcpyAsync(h_scores.data(), B->d_scores, Qb * n_slots * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(ctx, spin_sync(ctx, s));
+    float ms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->cur->ev[1], ctx->cur->ev[2]));
+    st->fill_ms += ms;
+    st->total_ms += ms;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (size_t r = 0; r < Qb; ++r) { // (row r of the score buffer = query order[r] of this chunk)
+        const size_t i = q0 + B->order[r];
+        if (P.dev_topk && h_meta[4 * r + 1] == 0 && h_meta[4 * r + 2] <= SWG_TOPK_MULTI_CAP) {
+            // every hit with a score >= the k-th best one: sort those few keys
+            uint64_t *c = B->h_cand.data() + r * (size_t)SWG_TOPK_MULTI_CAP;
+            const size_t nc = h_meta[4 * r + 2], m = std::min(k, nc);
+            std::partial_sort(c, c + m, c + nc, std::greater<uint64_t>());
+            for (size_t j = 0; j < m; ++j) swg_key_hit(c[j], &topk_out[i * k + j]);
+            if (n_hits) n_hits[i] = m;
+            continue;
+        }
+        if (P.dev_topk) { // threshold beyond the histogram, or too many ties: this query's scores to the host after all
+            if (h_scores.size() < n_slots) h_scores.resize(n_slots);
+            HIP_TRY(ctx, hipMemcpyAsync(h_scores.data(), B->d_scores + r * n_slots, n_slots * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, spin_sync(ctx, s));
+            deliver_scores(db, h_scores.data(), n_slots, nullptr, topk_out + i * k, k, n_hits ? n_hits + i : nullptr);
+            continue;
+        }
+        deliver_scores(db, h_scores.data() + r * n_slots, n_slots, scores_out ? scores_out + i * n_total : nullptr,
+                       topk_out ? topk_out + i * k : nullptr, k, n_hits ? n_hits + i : nullptr);
+    }
+    st->topk_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SWG_OK;
+}
+
+// The statistics of a batch that went through the launches, from its plan (workgroups and lane groups: the last chunk's).
+static void batch_report(const swg_ctx *ctx, const swg_db *db, const SwgBatchPlan &P, size_t n_queries, swg_stats *st)
+{
+    const SwgDiagWork &wk = P.wk;
+    const size_t last_rows = P.grid_rows(n_queries - (n_queries - 1) / P.chunk_queries * P.chunk_queries);
+    int wgs[2];
+    uint64_t groups0;
+    batch_chunk_workgroups(P, last_rows, ctx->n_cu, wgs, &groups0);
+    st->workgroups = wgs[0] * (int)last_rows;
+    st->streams = (int32_t)groups0;
+    st->path_bits = 16;
+    st->engine = 2;
+    st->work_queue = 1;
+    st->classes_overlapped = -1; // (not measured for a batch)
+    st->cell_form = P.qq ? 3 : P.form;
+    st->cols_per_wave = wk.plan[0].K;
+    st->group_lanes = wk.plan[0].G;
+    st->waves = wk.plan[0].W;
+    st->passes = 1;
+    st->fill_launches = 1;
     if (wk.n_classes == 2) {
-        st.long_pairs = (int32_t)(wk.pair_end[1] - wk.pair_begin[1]);
-        st.long_cols_per_lane = wk.plan[1].K;
+        st->long_pairs = (int32_t)(wk.pair_end[1] - wk.pair_begin[1]);
+        st->long_cols_per_lane = wk.plan[1].K;
     }
     for (int c = 0; c < wk.n_classes; ++c)
-        st.cells_padded += 2ull * wk.plan[c].G * wk.plan[c].K * diag_class_blocks(ctx, db, wk, c) * 4ull * n_queries;
+        st->cells_padded += 2ull * wk.plan[c].G * wk.plan[c].K * diag_class_blocks(ctx, db, wk, c) * 4ull * n_queries;
+}
+
+static int search_multi_impl(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, int32_t *scores_out, swg_hit *topk_out, size_t k,
+                             size_t *n_hits, swg_stats *stats)
+{
+    swg_stats st;
+    memset(&st, 0, sizeof st);
+    int rc = validate_batch(ctx, db, mq, topk_out, k, &st);
+    if (rc != SWG_OK) return rc;
+    if (stats) *stats = st;
+    if (mq.n == 0) return SWG_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    SwgBatchPlan P;
+    rc = plan_batch(ctx, db, mq, scores_out != nullptr, k, &P);
+    if (rc != SWG_OK) return rc;
+    if (!P.one_launch) {
+        rc = search_batch_one_by_one(ctx, db, mq, scores_out, topk_out, k, n_hits, &st);
+        if (stats) *stats = st;
+        return rc;
+    }
+    MultiBufs B;
+    ctx->cur = &ctx->slots[0];
+    rc = batch_allocate(ctx, P, &B);
+    for (size_t q0 = 0; q0 < mq.n && rc == SWG_OK; q0 += P.chunk_queries) {
+        const size_t Qb = std::min(P.chunk_queries, mq.n - q0);
+        const size_t Qrows = P.grid_rows(Qb); // rows of the grid: query pairs, or queries
+        // the fence: what this chunk's launches will index, against what the buffers hold
+        rc = multi_rows_ok(ctx, B, P, Qb, Qrows);
+        if (rc == SWG_OK) rc = batch_stage_chunk(ctx, P, mq, q0, Qb, &B);
+        if (rc == SWG_OK) rc = batch_launch_chunk(ctx, db, P, B, Qb, Qrows);
+        if (rc == SWG_OK) rc = batch_deliver_chunk(ctx, db, P, &B, q0, Qb, k, scores_out, topk_out, n_hits, &st);
+    }
+    if (rc != SWG_OK) return rc;
+    batch_report(ctx, db, P, mq.n, &st);
     if (stats) *stats = st;
     return SWG_OK;
+}
+
+extern "C" int swg_search_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets,
+                                size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
+                                swg_stats *stats)
+{
+    return ctx_guarded(ctx, "swg_search_multi", [&]() -> int { // (the body sizes host vectors by the batch)
+        return search_multi_impl(ctx, const_cast<swg_db *>(db), MultiQueries{queries, q_offsets, n_queries, false, "swg_search_multi"},
+                                 scores_out, topk_out, k, n_hits, stats);
+    });
+}
+
+extern "C" int swg_search_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets,
+                                     size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
+                                     swg_stats *stats)
+{
+    return ctx_guarded(ctx, "swg_search_multi_pssm", [&]() -> int {
+        return search_multi_impl(ctx, const_cast<swg_db *>(db), MultiQueries{pssms, q_offsets, n_queries, true, "swg_search_multi_pssm"},
+                                 scores_out, topk_out, k, n_hits, stats);
+    });
 }
 
 // ---------------------------------------------------------------------------

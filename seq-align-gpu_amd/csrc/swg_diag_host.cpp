@@ -79,7 +79,7 @@ static double instr_per_row(int K, int G, int form = 0, bool fma = false)
 static int pairings(int form, int K, int G, int W, bool edges, long f16_pair)
 {
     if (form != 2) return 1;
-    const bool fits = (W > 0 ? swg_diag_dyn_lds_bytes(K, G, W, true) : swg_diag_slice_bytes(K, G, true)) <= 160 * 1024;
+    const bool fits = (W > 0 ? swg_diag_dyn_lds_bytes(K, G, W, true) : swg_diag_slice_bytes(K, G, true)) <= SWG_LDS_PER_CU;
     if (!fits || f16_pair == 1 || (edges && (K == 23 || K == 24))) return 1;
     return f16_pair == 2 ? 2 : 3;
 }
@@ -92,7 +92,7 @@ static int perm_occupancy(const SwgKernelInfo &info, int G)
 {
     int best = 0;
     for (int W = 4; W <= info.max_waves; W += 4)
-        best = std::max(best, std::min(4, W / 4 * std::max(1, std::min<int>(info.max_waves / W, (int)((160 * 1024) / swg_diag_dyn_lds_bytes(info.K, G, W))))));
+        best = std::max(best, std::min(4, W / 4 * swg_workgroups_per_cu(info.max_waves, W, swg_diag_dyn_lds_bytes(info.K, G, W))));
     return best;
 }
 
@@ -120,7 +120,7 @@ static bool long_class_geometry(size_t lq, uint64_t longest_rows, double budget_
             const int G = groups[gi];
             if (g_swg_long_group > 0 && G != (int)g_swg_long_group) continue;
             const size_t cols = (size_t)G * info.K;
-            if ((size_t)G * swg_diag_padded_cols(info.K) * 64 > 160 * 1024) continue;
+            if ((size_t)G * swg_diag_padded_cols(info.K) * 64 > SWG_LDS_PER_CU) continue;
             const int npass = (int)((lq + cols - 1) / cols);
             if (dynamic && npass > 1) continue; // the queue serves single-pass classes only
             // (the f16 cells: the fma pairing where it fits beside the records of the class's four wavefronts)
@@ -176,7 +176,7 @@ static int plan_candidates(const swg_db *db, size_t lq, int n_cu, long opt_cols,
             const int G = groups[gi];
             if (opt_group > 0 && G != (int)opt_group) continue;
             const size_t cols = (size_t)G * info.K;
-            if (swg_diag_slice_bytes(info.K, G) > 160 * 1024) continue;
+            if (swg_diag_slice_bytes(info.K, G) > SWG_LDS_PER_CU) continue;
             const int npass = (int)((lq + cols - 1) / cols);
             const int NG = 64 / G;
             // with the work queue (several passes: one launch per pass) there are no fixed shares, the
@@ -202,7 +202,7 @@ static int plan_candidates(const swg_db *db, size_t lq, int n_cu, long opt_cols,
                     // profiles per CU they decide whether a second workgroup fits)
                     auto occupancy = [&](int w) {
                         const size_t l = swg_diag_dyn_lds_bytes(info.K, G, 4 * w, fma);
-                        return std::min(4, w * std::max(1, std::min<int>(info.max_waves / (4 * w), (int)((160 * 1024) / l))));
+                        return std::min(4, w * swg_workgroups_per_cu(info.max_waves, 4 * w, l));
                     };
                     bool improves = true;
                     for (int w2 = 1; w2 < wps; ++w2)
@@ -210,9 +210,9 @@ static int plan_candidates(const swg_db *db, size_t lq, int n_cu, long opt_cols,
                     if (!improves) continue;
                 }
                 // (the work-queue kernels keep a 512-byte record per lane group behind the profile)
-                if (fma && swg_diag_dyn_lds_bytes(info.K, G, W, true) > 160 * 1024) continue;
+                if (fma && swg_diag_dyn_lds_bytes(info.K, G, W, true) > SWG_LDS_PER_CU) continue;
                 const size_t lds_wg = dynamic ? swg_diag_dyn_lds_bytes(info.K, G, W, fma) : lds;
-                const int per_cu = std::max(1, std::min<int>(info.max_waves / W, (int)((160 * 1024) / lds_wg)));
+                const int per_cu = swg_workgroups_per_cu(info.max_waves, W, lds_wg);
                 const int eff_wps = std::min(4, wps * per_cu);
                 // the fma pairing only where its doubled profile costs no resident wavefronts: at fewer per SIMD than the
                 // perm pairing reaches with the same columns and lanes it measured slower (config 2, 16 x 23: two
@@ -614,7 +614,7 @@ double swg_systolic_estimate_ms(const swg_db *db, size_t lq, int n_cu, int *best
         if (W > info.max_waves) continue; // (several passes: never the better engine)
         if (info.K > 32) continue;         // (the 48-column instantiation runs at two wavefronts per SIMD: measured 45 % over its count)
         const size_t lds = info.lds_per_wave * (size_t)W + info.lds_fixed;
-        const int per_cu = std::max(1, std::min<int>(info.max_waves / W, (int)((160 * 1024) / lds)));
+        const int per_cu = swg_workgroups_per_cu(info.max_waves, W, lds);
         const double waves_per_simd = std::max(1.0, per_cu * W / 4.0);
         const double instr = (f16 ? 8.5 : 10.0) * info.K + 12.0; // (packed-f16 cells where no score can reach 4096)
         const double thr = (rows * W * instr * 4.06 + (double)db->n_bins * W * 5000.0) / (4.0 * n_cu);

@@ -4,6 +4,7 @@
 #include "../../include/swg.h"
 #include "swg_internal.h"
 
+#include <algorithm>
 #include <functional>
 #include <map>
 #include <memory>
@@ -188,6 +189,15 @@ struct swg_db {
 // gap magnitudes (of non-positive gap scores go = open + extend, ge = extend) fit the f16 cells
 inline bool swg_f16_gaps_ok(int go, int ge) { return -go <= SWG_F16_GAP_MAX && -ge <= SWG_F16_GAP_MAX; }
 
+// LDS of one CU, and the workgroups of W wavefronts and `lds` bytes each that a CU holds: `wave_budget` (an
+// instantiation's max_waves, which is also the wave budget of one CU for its register allocation) is one limit, LDS the
+// other; never fewer than one.
+#define SWG_LDS_PER_CU ((size_t)160 * 1024)
+inline int swg_workgroups_per_cu(int wave_budget, int W, size_t lds)
+{
+    return std::max(1, std::min<int>(wave_budget / W, (int)(SWG_LDS_PER_CU / lds)));
+}
+
 // The largest score a query can reach against sequences of at most `longest` rows: not above the query's best possible
 // total (every column paired with its best-scoring residue of 1 .. 31: qbound) nor above min(lq, longest) times the
 // largest entry (smax).  idx != NULL: rows is the 32 x 32 table and idx the query's lq residue indices; idx == NULL: rows
@@ -233,6 +243,35 @@ struct SwgSearchPlan {
     SwgDiagWork wk, wk32;            // lane groups: the 16-bit fill; the int32 work-queue fill of the whole database
     SwgSystolicPlan main_pl, re_pl;  // systolic engine: the fill; the int32 re-score
     int npass32 = 0;                 // passes of the bin-based int32 kernel
+};
+
+// Everything a query batch (swg_search_multi, swg_search_multi_pssm) decides before it queues anything: plan_batch
+// (swg_api.cpp) writes it once, the stages that allocate, launch and deliver only read it, and the batch's swg_stats are
+// reported from it.  The queries go through the launches in chunks of at most chunk_queries; the buffers are allocated
+// once, for the first chunk, which is the largest.
+struct SwgBatchPlan {
+    bool one_launch = false; // else the queries are searched one after another, and nothing below is set
+    int go = 0, ge = 0;      // gap_open + gap_extend, gap_extend
+    int form = 0;            // the cells: 0 packed int16, 2 packed f16
+    bool qq = false;         // two queries per lane (swg_diag_qq_kernel): row y of the grid is the query pair (2y, 2y + 1)
+    SwgDiagWork wk;          // the classes, each with the W it is launched with
+    int qq_per_cu = 1;       // qq: the bulk's workgroups per CU (LDS decides)
+    uint64_t bound_max = 0;  // the largest score any query of the batch can reach
+    size_t lq_max = 0;
+    bool dev_topk = false;   // the top-K is selected on the device (no score array asked for, k within its capacity)
+    size_t n_slots = 0;      // scores per query: the database's slots
+    size_t chunk_queries = 0, first_chunk = 0;
+    // What a chunk of Qb queries indexes, in the units the kernels index by: rows of the grid (profiles, queues), and rows
+    // of n_slots scores.  With qq an odd chunk indexes ONE SCORE ROW MORE than it has queries -- the absent partner of its
+    // last query has a row of its own everywhere (nothing reads it back).
+    size_t grid_rows(size_t Qb) const { return qq ? (Qb + 1) / 2 : Qb; }
+    size_t score_rows(size_t Qb) const { return qq ? 2 * grid_rows(Qb) : Qb; }
+    // what the buffers hold
+    size_t score_rows_cap = 0, grid_rows_cap = 0; // score_rows / grid_rows of the first chunk
+    size_t order_entries = 0;                     // query offsets and (qq) query order of a chunk: one more than its queries
+    uint32_t class_queue_dwords = 0;              // queue dwords of one class of one grid row (a row's stride is twice that)
+    size_t rank_word_base = 0, queue_dwords = 0;  // the per-SIMD rank words of the two classes follow the queues
+    size_t prof_row_bytes[2] = {0, 0};            // profile bytes of one grid row, per class
 };
 
 // One search in flight: its timing events, host-side landing buffers and what swg_search_end
