@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomised parity soak: random databases (tiny to long-tailed), query lengths, scoring tables,
-gap scores and engine options through the C ABI, every score against the int32 oracle.
+gap scores and engine options through the C ABI, every score against the int32 oracle, and the hits of a
+search without a score array (k small, or around the number of sequences) against the oracle's top-K.
 scoring "edges": the tables and gap points of tests/scoring_edges.py (entries over all of int8, gap magnitudes at the
 hand-overs between cell forms) with split_db's relatives planted among the random sequences.
 usage: python tests/fuzz_gpu.py [seconds] [seed] [classic|edges]"""
@@ -38,6 +39,7 @@ def main(budget=300.0, seed=1, scoring="classic"):
     swg = swg_loader.load(); orc = swg_loader.oracle()
     assert scoring in ("classic", "edges")
     rng = np.random.default_rng(seed)
+    rng_k = np.random.default_rng([seed, 4096])   # (its own stream: the cases of a seed stay what they were)
     ctx = swg.Context(0)
     mats = ["BLOSUM62", "PAM250", "BLOSUM45"]
     t_end = time.time() + budget
@@ -134,6 +136,12 @@ def main(budget=300.0, seed=1, scoring="classic"):
             bad = np.nonzero(got != want)[0]
             print("MISMATCH case", cases, "n", n, "lq", lq, "shape", shape, "gaps", go, ge, "opts", opts, "stats", st)
             print("  first bad:", bad[:10], got[bad[:10]], want[bad[:10]])
+            return 1
+        # hits only (the top-K is selected on the device for k <= 4096): k around the number of sequences, or small
+        k_hits = max(1, len(lens) + int(rng_k.integers(-2, 3))) if rng_k.random() < 0.5 else int(rng_k.integers(1, 20))
+        none, hits_only, _ = ctx.search(db, want_scores=False, k=k_hits)
+        if none is not None or hits_only != orc.topk(want, k_hits):
+            print("TOP-K MISMATCH case", cases, "n", len(lens), "lq", lq, "k", k_hits, "gaps", go, ge, "opts", opts, "stats", st)
             return 1
         db.close()
         cases += 1
