@@ -209,6 +209,26 @@ int swg_db_pack_shard(const int8_t *flat, const uint64_t *offsets, size_t n_loca
  * should not sort a 10M-sequence database once per device).  On error no shard is returned. */
 int swg_db_pack_shards(const int8_t *flat, const uint64_t *offsets, size_t n, int shard_count, swg_db **out);
 int swg_db_upload(swg_ctx *ctx, swg_db *db); /* H2D; db becomes resident on ctx's GPU */
+/* A view of `parent` (resident on ctx's device): the sequences whose ORIGINAL indices are listed, as a database of
+ * its own.  No residue byte is copied or uploaded: the view reads the parent's bytes where they lie, on the host and
+ * on the device, and 4 bytes per selected sequence cross PCIe.  Every call that takes a swg_db takes a view, and
+ * runs the kernels and plans it would run on a packed and uploaded database of the same sequences.
+ *   indices    original indices, in any order; duplicates collapse.  An index >= swg_db_total_count(parent) is
+ *              SWG_ERR_ARG.  An index of the whole database that this shard does not hold is ignored, so every rank
+ *              of a sharded run passes the same global list.  n == 0, or nothing of the list in this shard: an empty
+ *              view, whose searches return no hits and write no score.
+ *   parent     must be resident on ctx's device (else SWG_ERR_STATE).  A view of a view is a view of the database
+ *              the first one was taken of, holding what both select; it does not depend on the view it was made from.
+ * Of a view, swg_db_count is the number of sequences selected in this shard, swg_db_total_count the parent's
+ * (scores_out stays indexed by original index and only selected entries are written; hits carry original indices),
+ * swg_db_residues the selection's, swg_db_order the view's own order (the parent's sorted order, kept) and
+ * swg_db_packed_bytes what the view itself sends to the GPU.  A view is resident from creation: swg_db_upload of a
+ * view is SWG_ERR_STATE, swg_db_save of one SWG_ERR_ARG.  Plans, tuned geometries, hints, device layouts and output
+ * buffers are the view's own: nothing a view learns changes its parent's searches, or the reverse.
+ * Lifetime: the residue bytes live as long as the parent's handle or any view of it.  swg_db_free(parent) while
+ * views live only ends the caller's use of the parent (its own search buffers are released); the bytes go with the
+ * last view, whichever order the frees come in.  swg_db_upload(ctx, parent) while views live is SWG_ERR_STATE. */
+int swg_db_view(swg_ctx *ctx, swg_db *parent, const uint32_t *indices, size_t n, swg_db **out);
 /* Packed-database file (host-only): the sorted, re-coded image of swg_db_pack,
  * so a large database is ingested once; swg_db_load validates the structure it reads. */
 int swg_db_save(const swg_db *db, const char *path);
@@ -366,6 +386,11 @@ int swg_group_search(swg_group *g, int32_t *scores_out, swg_hit *topk_out, size_
 int swg_group_align_hits(swg_group *g, const swg_hit *hits, size_t n_hits, swg_alignment *out, char *ops,
                          size_t ops_stride);
 size_t swg_group_align_ops_bound(const swg_group *g);
+/* Restrict the group to the listed sequences (original indices of the loaded database; the rules of swg_db_view):
+ * every device makes a view of its shard from the same list, and swg_group_search, swg_group_align_hits and
+ * swg_group_align_ops_bound use the views until the next swg_group_select.  indices == NULL returns to the whole
+ * database.  swg_group_load drops a selection. */
+int swg_group_select(swg_group *g, const uint32_t *indices, size_t n);
 
 #ifdef __cplusplus
 }

@@ -32,7 +32,7 @@ SWG_ERR_STATE, SWG_ERR_RESIDUE, SWG_ERR_IO, SWG_ERR_NODEVICE = -4, -5, -6, -7
 # every symbol declared in include/swg.h and include/swg_host.h
 ABI_SYMBOLS = [
     "swg_create", "swg_destroy", "swg_last_error", "swg_global_error", "swg_abi_version",
-    "swg_set_option", "swg_set_scoring", "swg_set_query", "swg_set_query_pssm", "swg_db_pack", "swg_db_pack_shard", "swg_db_pack_shards", "swg_db_upload",
+    "swg_set_option", "swg_set_scoring", "swg_set_query", "swg_set_query_pssm", "swg_db_pack", "swg_db_pack_shard", "swg_db_pack_shards", "swg_db_upload", "swg_db_view",
     "swg_db_free", "swg_db_save", "swg_db_load", "swg_db_count", "swg_db_total_count", "swg_db_residues",
     "swg_db_packed_bytes", "swg_db_order", "swg_search", "swg_search_begin", "swg_search_end", "swg_search_multi",
     "swg_search_multi_pssm", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_align_hits_multi",
@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "swg_key_hit", "swg_topk_merge_keys",
     "swg_group_create", "swg_group_destroy", "swg_group_size", "swg_group_last_error", "swg_group_set_option",
     "swg_group_set_scoring", "swg_group_set_query", "swg_group_set_query_pssm", "swg_group_load", "swg_group_search",
-    "swg_group_align_hits", "swg_group_align_ops_bound",
+    "swg_group_align_hits", "swg_group_align_ops_bound", "swg_group_select",
     "swg_letter_index", "swg_index_letter", "swg_scoring_init", "swg_scoring_add",
     "swg_scoring_load_matrix", "swg_query_sanitize", "swg_seqs_read", "swg_seqs_free",
     "swg_seqs_to_indices", "swg_synth_db", "swg_synth_query", "swg_synth_db_similar", "swg_synth_db_family", "swg_synth_db_shard",
@@ -128,6 +128,7 @@ _sig("swg_db_pack", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(
 _sig("swg_db_pack_shard", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(_vp)])
 _sig("swg_db_pack_shards", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.POINTER(_vp)])
 _sig("swg_db_upload", C.c_int, [_vp, _vp])
+_sig("swg_db_view", C.c_int, [_vp, _vp, _vp, C.c_size_t, C.POINTER(_vp)])
 _sig("swg_db_free", None, [_vp])
 _sig("swg_db_save", C.c_int, [_vp, C.c_char_p])
 _sig("swg_db_load", C.c_int, [C.c_char_p, C.POINTER(_vp)])
@@ -152,6 +153,7 @@ _sig("swg_key_hit", None, [C.c_uint64, C.POINTER(Hit)])
 _sig("swg_topk_merge_keys", C.c_size_t, [_vp, C.c_size_t, C.c_size_t, _vp])
 _sig("swg_group_align_hits", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t])
 _sig("swg_group_align_ops_bound", C.c_size_t, [_vp])
+_sig("swg_group_select", C.c_int, [_vp, _vp, C.c_size_t])
 _sig("swg_group_create", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)])
 _sig("swg_group_destroy", None, [_vp])
 _sig("swg_group_size", C.c_int, [_vp])
@@ -197,6 +199,7 @@ _sig("swg_debug_plan_f16", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_long, _vp])
 _sig("swg_debug_split", C.c_int, [_vp, C.c_size_t, C.c_uint64, _vp])
 _sig("swg_debug_list_plan", C.c_int, [C.c_size_t, C.c_uint32, C.c_int, _vp, _vp])
 _sig("swg_debug_pair_tokens", C.c_int, [_vp, _vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
+_sig("swg_debug_view_ranks", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.POINTER(C.c_size_t)])
 
 
 def _check(rc, ctx=None):
@@ -489,6 +492,26 @@ class Database:
                                          out.size, C.byref(n)), ctx.handle)
         return out
 
+    def debug_view_ranks(self, indices):
+        """Test hook: the sorted ranks (slots of this database; of its parent database for a view) that view(ctx,
+        indices) would select, ascending (no device needed)."""
+        ix = np.ascontiguousarray(indices, dtype=np.uint32)
+        out = np.zeros(max(ix.size, 1), dtype=np.uint32)
+        n = C.c_size_t(0)
+        _check(lib.swg_debug_view_ranks(self.handle, ix.ctypes.data_as(_vp), ix.size, out.ctypes.data_as(_vp), C.byref(n)))
+        return out[:n.value].copy()
+
+    def view(self, ctx, indices):
+        """The sequences with the listed ORIGINAL indices (any order, duplicates collapse, those of other shards
+        ignored) as a Database of its own that reads this one's resident bytes (swg_db_view).  Scores stay indexed by
+        original index and only the selected entries are written.  Either object may be closed first."""
+        ix = np.ascontiguousarray(indices, dtype=np.uint32)
+        h = _vp()
+        _check(lib.swg_db_view(ctx.handle, self.handle, ix.ctypes.data_as(_vp), ix.size, C.byref(h)), ctx.handle)
+        v = Database.__new__(Database)
+        v.handle = h
+        return v
+
     def save(self, path):
         _check(lib.swg_db_save(self.handle, path.encode()))
 
@@ -759,6 +782,16 @@ class Group:
         self._chk(lib.swg_group_search(self.handle, scores.ctypes.data_as(_vp) if want_scores else None,
                                        C.cast(hits, _vp) if k else None, k, C.byref(nh), st))
         return scores, [(int(hits[i].score), int(hits[i].index)) for i in range(nh.value)], [s.as_dict() for s in st]
+
+    def select(self, indices):
+        """Restrict search / align_hits to the listed original indices (every device takes a view of its shard);
+        None returns to the whole database."""
+        if indices is None:
+            self._chk(lib.swg_group_select(self.handle, None, 0))
+            return
+        ix = np.ascontiguousarray(indices, dtype=np.uint32)
+        keep = ix if ix.size else np.zeros(1, dtype=np.uint32)   # (an empty list is a list: never a NULL pointer)
+        self._chk(lib.swg_group_select(self.handle, keep.ctypes.data_as(_vp), ix.size))
 
     def align_hits(self, hits):
         """Alignments of hits of a group search (see Context.align_hits)."""

@@ -442,17 +442,13 @@ extern "C" int swg_set_query_pssm(swg_ctx *ctx, const int8_t *pssm, size_t lq)
 // ---------------------------------------------------------------------------
 // database residency
 // ---------------------------------------------------------------------------
-void swg_db_release_device(swg_db *db)
+void swg_db_release_search_state(swg_db *db)
 {
     if (!db || db->device < 0) return;
     (void)hipSetDevice(db->device);
-    (void)hipFree(db->d_codes);
-    (void)hipFree(db->d_code_off);
-    (void)hipFree(db->d_lens);
     (void)hipFree(db->d_packed);
     (void)hipFree(db->d_bin_off);
     (void)hipFree(db->d_bin_nblk);
-    (void)hipFree(db->d_order);
     for (swg_db::Bufs &b : db->bufs) {
         (void)hipFree(b.d_scores);
         (void)hipFree(b.d_list);
@@ -478,18 +474,28 @@ void swg_db_release_device(swg_db *db)
         (void)hipFree(L.d_scratch);
         L = SwgDiagLayout();
     }
-    db->d_codes = nullptr;
-    db->d_code_off = nullptr;
-    db->d_lens = nullptr;
     db->d_packed = nullptr;
     db->d_bin_off = nullptr;
     db->d_bin_nblk = nullptr;
-    db->d_order = nullptr;
     db->d_scores = nullptr;
     db->d_list = nullptr;
     db->d_counters = nullptr;
     db->d_keys = nullptr;
     db->d_hist = nullptr;
+}
+
+void swg_db_release_device(swg_db *db)
+{
+    if (!db || db->device < 0) return;
+    swg_db_release_search_state(db);
+    if (!db->root) (void)hipFree(db->d_codes); // (a view's residue bytes are its root's)
+    (void)hipFree(db->d_code_off);
+    (void)hipFree(db->d_lens);
+    (void)hipFree(db->d_order);
+    db->d_codes = nullptr;
+    db->d_code_off = nullptr;
+    db->d_lens = nullptr;
+    db->d_order = nullptr;
     db->device = -1;
 }
 
@@ -520,6 +526,10 @@ static int select_bufs(swg_ctx *ctx, swg_db *db, int slot)
 extern "C" int swg_db_upload(swg_ctx *ctx, swg_db *db)
 {
     if (!ctx || !db) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_db_upload: NULL argument");
+    if (db->root) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_db_upload: a view is resident from its creation, where its parent is");
+    if (swg_db_views_alive(db) > 0)
+        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_db_upload: %zu views read this database's resident bytes: free them first",
+                                 swg_db_views_alive(db));
     swg_db_release_device(db);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     db->device = ctx->device;
@@ -539,7 +549,7 @@ extern "C" int swg_db_upload(swg_ctx *ctx, swg_db *db)
         int rb = select_bufs(ctx, db, 0);
         if (rb != SWG_OK) return rb;
         if (!db->codes.empty())
-            HIP_TRY(ctx, hipMemcpyAsync(db->d_codes, db->codes.data(), db->codes.size(), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(db->d_codes, swg_db_codes(db), db->codes.size(), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(db->d_code_off, off_dw.data(), (ns + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         if (ns) {
             HIP_TRY(ctx, hipMemcpyAsync(db->d_lens, db->lens.data(), ns * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -551,6 +561,54 @@ extern "C" int swg_db_upload(swg_ctx *ctx, swg_db *db)
     }();
     if (rc != SWG_OK) swg_db_release_device(db);
     return rc;
+}
+
+// A view: the listed sequences of a resident database as a database of its own.  The host image (swg_view_host) is made
+// from the parent's without touching a residue byte; what crosses PCIe is the selected slots, 4 bytes each, from which
+// swg_gather_view_kernel writes the view's three words per slot out of the root's resident ones.  d_codes is the root's
+// pointer; pair tokens, bins and output buffers come from the same lazy paths as any database's.
+extern "C" int swg_db_view(swg_ctx *ctx, swg_db *parent, const uint32_t *indices, size_t n, swg_db **out)
+{
+    if (out) *out = nullptr;
+    if (!ctx || !parent || !out || (n > 0 && !indices)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_db_view: NULL argument");
+    return ctx_guarded(ctx, "swg_db_view", [&]() -> int {
+        if (parent->device != ctx->device || !parent->d_codes)
+            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_db_view: the parent is not resident on device %d", ctx->device);
+        if (parent->tokens_only)
+            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_db_view: a database built from 16-lane batches has no residue bytes to view");
+        std::vector<uint32_t> slots;
+        const int rs = swg_view_select(parent, indices, n, &slots);
+        if (rs != SWG_OK) return swg_set_ctx_error(ctx, rs, "%s", swg_global_error());
+        swg_db *root = parent->root ? parent->root : parent;
+        swg_db *v = swg_view_host(parent, slots);
+        const size_t ns = (size_t)v->n_bins * SWG_BIN;
+        slots.resize(ns, 0xFFFFFFFFu); // the empty slots of the last bin
+        uint32_t *d_slots = nullptr;
+        const int rc = [&]() -> int {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            v->device = ctx->device;
+            v->d_codes = root->d_codes;
+            HIP_TRY(ctx, hipMalloc(&v->d_code_off, (ns + 1) * 8));
+            HIP_TRY(ctx, hipMalloc(&v->d_lens, std::max<size_t>(4, ns * 4)));
+            HIP_TRY(ctx, hipMalloc(&v->d_order, std::max<size_t>(4, ns * 4)));
+            HIP_TRY(ctx, hipMalloc(&d_slots, std::max<size_t>(4, ns * 4)));
+            const int rb = select_bufs(ctx, v, 0);
+            if (rb != SWG_OK) return rb;
+            if (ns) HIP_TRY(ctx, hipMemcpyAsync(d_slots, slots.data(), ns * 4, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, swg_launch_gather_view(d_slots, (uint32_t)ns, (uint32_t)root->order.size(), root->d_code_off, root->d_lens,
+                                                root->d_order, v->d_code_off, v->d_lens, v->d_order, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // `slots` goes out of scope; the view may be used from any context of the device
+            v->upload_bytes = ns * 4;
+            return SWG_OK;
+        }();
+        (void)hipFree(d_slots);
+        if (rc != SWG_OK) {
+            swg_db_free(v);
+            return rc;
+        }
+        *out = v;
+        return SWG_OK;
+    });
 }
 
 // The bin image: built on the device from the residue dwords the first time an engine that reads

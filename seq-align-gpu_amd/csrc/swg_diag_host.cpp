@@ -402,8 +402,8 @@ static uint64_t write_pair_tokens(const swg_db *db, size_t p, uint32_t *t)
     const uint32_t lx = db->lens[2 * p];
     const bool has_y = 2 * p + 1 < n_slots && db->order[2 * p + 1] != 0xFFFFFFFFu;
     const uint32_t ly = has_y ? db->lens[2 * p + 1] : 0;
-    const uint8_t *cx = db->codes.data() + db->code_off[2 * p];
-    const uint8_t *cy = has_y ? db->codes.data() + db->code_off[2 * p + 1] : nullptr;
+    const uint8_t *cx = swg_db_codes(db) + db->code_off[2 * p];
+    const uint8_t *cy = has_y ? swg_db_codes(db) + db->code_off[2 * p + 1] : nullptr;
     t[0] = kTokReset; // reset rows: padding residue for both sequences
     t[1] = kTokReset | SWG_TOK_RESET2;
     uint32_t *r = t + 2;

@@ -61,6 +61,9 @@ struct swg_group {
     std::vector<int> devices;
     std::vector<swg_ctx *> ctx;
     std::vector<swg_db *> db;
+    std::vector<swg_db *> view; // swg_group_select: each device's view of its shard (all null: the whole database)
+    // what searches and alignments run on
+    swg_db *use(int i) const { return view[i] ? view[i] : db[i]; }
     std::vector<ncclComm_t> comm;
     std::vector<uint64_t *> d_keys; // [n] device buffers of n*kcap keys
     size_t kcap = 0;
@@ -80,6 +83,7 @@ extern "C" const char *swg_group_last_error(const swg_group *g) { return g ? g->
 extern "C" void swg_group_destroy(swg_group *g)
 {
     if (!g) return;
+    for (size_t i = 0; i < g->view.size(); ++i) swg_db_free(g->view[i]);
     for (size_t i = 0; i < g->db.size(); ++i) swg_db_free(g->db[i]);
     for (size_t i = 0; i < g->d_keys.size(); ++i)
         if (g->d_keys[i]) {
@@ -114,6 +118,7 @@ extern "C" int swg_group_create(const int *devices, int n, int force_collective,
         g->ctx.push_back(c);
     }
     g->db.assign(n, nullptr);
+    g->view.assign(n, nullptr);
     g->d_keys.assign(n, nullptr);
     for (int i = 0; i < n; ++i)
         for (int j = 0; j < i; ++j)
@@ -181,6 +186,8 @@ extern "C" int swg_group_load(swg_group *g, const int8_t *flat, const uint64_t *
 {
     if (!g) return swg_set_global_error(SWG_ERR_ARG, "swg_group_load: NULL group");
     for (int i = 0; i < g->n; ++i) {
+        swg_db_free(g->view[i]);
+        g->view[i] = nullptr;
         swg_db_free(g->db[i]);
         g->db[i] = nullptr;
     }
@@ -206,6 +213,28 @@ extern "C" int swg_group_load(swg_group *g, const int8_t *flat, const uint64_t *
     return SWG_OK;
 }
 
+extern "C" int swg_group_select(swg_group *g, const uint32_t *indices, size_t n)
+{
+    if (!g) return swg_set_global_error(SWG_ERR_ARG, "swg_group_select: NULL group");
+    for (int i = 0; i < g->n; ++i)
+        if (!g->db[i]) return gerr(g, SWG_ERR_STATE, "swg_group_select: no database loaded");
+    // the new views first: a list that is refused leaves the selection as it was
+    std::vector<swg_db *> fresh((size_t)g->n, nullptr);
+    if (indices)
+        for (int i = 0; i < g->n; ++i) {
+            const int rc = swg_db_view(g->ctx[i], g->db[i], indices, n, &fresh[i]);
+            if (rc != SWG_OK) {
+                for (int j = 0; j < i; ++j) swg_db_free(fresh[j]);
+                return gerr(g, rc, swg_last_error(g->ctx[i]));
+            }
+        }
+    for (int i = 0; i < g->n; ++i) {
+        swg_db_free(g->view[i]);
+        g->view[i] = fresh[i];
+    }
+    return SWG_OK;
+}
+
 extern "C" int swg_group_search(swg_group *g, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
                                 swg_stats *stats /* [n] or NULL */)
 {
@@ -217,7 +246,7 @@ extern "C" int swg_group_search(swg_group *g, int32_t *scores_out, swg_hit *topk
     // every GPU starts its shard; nothing waits until all are queued
     std::vector<int> ticket(g->n, -1);
     for (int i = 0; i < g->n; ++i) {
-        const int rc = swg_search_begin(g->ctx[i], g->db[i], scores_out != nullptr, k, &ticket[i]);
+        const int rc = swg_search_begin(g->ctx[i], g->use(i), scores_out != nullptr, k, &ticket[i]);
         if (rc != SWG_OK) {
             for (int j = 0; j < i; ++j) (void)swg_search_end(g->ctx[j], ticket[j], nullptr, nullptr, nullptr, nullptr);
             return gerr(g, rc, swg_last_error(g->ctx[i]));
@@ -292,7 +321,7 @@ extern "C" size_t swg_group_align_ops_bound(const swg_group *g)
     size_t b = 0;
     if (g)
         for (int i = 0; i < g->n; ++i)
-            if (g->db[i]) b = std::max(b, swg_align_ops_bound(g->ctx[i], g->db[i]));
+            if (g->db[i]) b = std::max(b, swg_align_ops_bound(g->ctx[i], g->use(i)));
     return b;
 }
 
@@ -311,7 +340,7 @@ extern "C" int swg_group_align_hits(swg_group *g, const swg_hit *hits, size_t n_
         owner.reserve(n_hits * 2);
         for (size_t h = 0; h < n_hits; ++h) owner[hits[h].index] = -1;
         for (int i = 0; i < g->n; ++i) {
-            for (const uint32_t oi : g->db[i]->order) { // ~0u marks an empty slot of the last bin
+            for (const uint32_t oi : g->use(i)->order) { // ~0u marks an empty slot of the last bin
                 auto it = oi == 0xFFFFFFFFu ? owner.end() : owner.find(oi);
                 if (it != owner.end()) it->second = i;
             }
@@ -332,7 +361,7 @@ extern "C" int swg_group_align_hits(swg_group *g, const swg_hit *hits, size_t n_
         std::vector<swg_alignment> al(mine.size());
         std::vector<char> sub_ops(ops ? mine.size() * ops_stride : 0);
         for (size_t m = 0; m < mine.size(); ++m) sub[m] = hits[mine[m]];
-        const int rc = swg_align_hits(g->ctx[i], g->db[i], sub.data(), sub.size(), al.data(), ops ? sub_ops.data() : nullptr,
+        const int rc = swg_align_hits(g->ctx[i], g->use(i), sub.data(), sub.size(), al.data(), ops ? sub_ops.data() : nullptr,
                                       ops_stride);
         if (rc != SWG_OK) return gerr(g, rc, swg_last_error(g->ctx[i]));
         for (size_t m = 0; m < mine.size(); ++m) {

@@ -151,6 +151,17 @@ struct swg_db {
     // a database whose pair tokens were built straight from reference-shaped 16-lane batches
     // (swg_fill_batches16): there are no residue bytes by sorted rank, so nothing that needs them can run
     bool tokens_only = false;
+    // A view (swg_db_view): a database of its own whose slots are some of `root`'s sequences.  Its residue bytes are the
+    // root's on the host and on the device -- codes is empty, code_off[s] is the ROOT's byte offset of slot s's sequence
+    // (so consecutive slots are not adjacent in memory: a sequence ends at code_off[s] + its length, never at
+    // code_off[s + 1]), d_codes is the root's pointer -- and everything else (lens, order, bins, pair tokens, plans,
+    // hints, output buffers) is its own.  root_slot[s] = the root's slot of this view's slot s (ascending: the root's
+    // sorted order is kept).  A root lives as long as its caller's handle or any view of it: refs counts both.
+    swg_db *root = nullptr;
+    std::vector<uint32_t> root_slot; // view: [n_local]
+    size_t refs = 1;                 // root: the caller's handle (while handle_live) + the views alive
+    bool handle_live = true;         // root: swg_db_free has not been called on it yet
+    std::vector<uint32_t> slot_of;   // root: [n_total] slot of each original index, ~0u = not in this shard (built by the first view)
     // device image (valid after swg_db_upload): the residue bytes and three words per slot; the pair
     // tokens (ptok) and the bin image are built FROM them on the device, the bins only when an
     // engine that reads them is used (swg_ensure_bins)
@@ -370,6 +381,19 @@ int swg_set_global_error(int code, const char *fmt, ...) __attribute__((format(p
 int swg_set_ctx_error(swg_ctx *ctx, int code, const char *fmt, ...)
     __attribute__((format(printf, 3, 4)));
 void swg_db_release_device(swg_db *db);
+// everything a search built or allocated for this database on the device (layouts, output buffers); the uploaded image stays
+void swg_db_release_search_state(swg_db *db);
+// the residue bytes a database's code_off points into: its own, or for a view its root's
+inline const uint8_t *swg_db_codes(const swg_db *db) { return (db->root ? db->root : db)->codes.data(); }
+// Views, host side (swg_pack.cpp; no GPU).  swg_view_select: the ROOT's slots that `indices` (original indices, any
+// order, duplicates collapse, those of other shards ignored) select among parent's sequences, ascending; SWG_ERR_ARG for
+// an index outside the whole database.  swg_view_host: the view of those slots with its whole host image, holding a
+// reference on the root.  swg_db_views_alive: views that keep this database's bytes alive.
+int swg_view_select(const swg_db *parent, const uint32_t *indices, size_t n, std::vector<uint32_t> *slots);
+swg_db *swg_view_host(swg_db *parent, const std::vector<uint32_t> &slots);
+size_t swg_db_views_alive(const swg_db *db);
+// test hook: swg_view_select's answer (out has room for n entries; slots of the root of `db`)
+extern "C" int swg_debug_view_ranks(const swg_db *db, const uint32_t *indices, size_t n, uint32_t *out, size_t *n_out);
 // test hook: the pair-token image as the device built it, or as the host restatement builds it
 // test hook: the next visit of the named site throws std::bad_alloc (swg_api.cpp); 0 disarms
 extern "C" void swg_debug_fail_alloc(int site);

@@ -252,6 +252,13 @@ hipError_t swg_launch_build_bins(const uint32_t *d_codes, const uint64_t *d_code
                                  const uint64_t *d_bin_off, const uint32_t *d_bin_nblk, uint32_t n_bins,
                                  uint32_t *d_packed, hipStream_t stream);
 
+// The three words per slot of a view (swg_db_view) from its parent's resident ones: view slot s is the parent's slot
+// d_slots[s] (~0u, or anything not below parent_slots: an empty slot -- offset 0, length 0, order ~0u); d_code_off has
+// n_slots + 1 entries like an uploaded database's, the last one 0.
+hipError_t swg_launch_gather_view(const uint32_t *d_slots, uint32_t n_slots, uint32_t parent_slots, const uint64_t *p_code_off,
+                                  const uint32_t *p_lens, const uint32_t *p_order, uint64_t *d_code_off, uint32_t *d_lens,
+                                  uint32_t *d_order, hipStream_t stream);
+
 // Appends every slot id whose 16-bit score saturated (>= ceiling: 32767, 65535 in the wide form, 4096 for the
 // packed-f16 cells) to list.
 hipError_t swg_launch_zero2(void *a, size_t a_bytes, void *b, size_t b_bytes, hipStream_t stream);

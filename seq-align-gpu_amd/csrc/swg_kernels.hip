@@ -2338,6 +2338,34 @@ hipError_t swg_launch_build_bins(const uint32_t *d_codes, const uint64_t *d_code
     return hipGetLastError();
 }
 
+// A view's slot words (swg_db_view): thread s gathers slot s's offset, length and original index from the parent's slot
+// slots[s]; the parent's offsets stay what they are, so the view's sequences are read where the parent's lie.
+__global__ void swg_gather_view_kernel(const uint32_t *slots, uint32_t n_slots, uint32_t parent_slots, const uint64_t *p_code_off,
+                                       const uint32_t *p_lens, const uint32_t *p_order, uint64_t *code_off, uint32_t *lens,
+                                       uint32_t *order)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s > n_slots) return;
+    if (s == n_slots) { // (the entry behind the last slot: nothing reads it as an end)
+        code_off[s] = 0ull;
+        return;
+    }
+    const uint32_t r = slots[s];
+    const bool real = r < parent_slots;
+    code_off[s] = real ? p_code_off[r] : 0ull;
+    lens[s] = real ? p_lens[r] : 0u;
+    order[s] = real ? p_order[r] : 0xFFFFFFFFu;
+}
+
+hipError_t swg_launch_gather_view(const uint32_t *d_slots, uint32_t n_slots, uint32_t parent_slots, const uint64_t *p_code_off,
+                                  const uint32_t *p_lens, const uint32_t *p_order, uint64_t *d_code_off, uint32_t *d_lens,
+                                  uint32_t *d_order, hipStream_t stream)
+{
+    hipLaunchKernelGGL(swg_gather_view_kernel, dim3(n_slots / 256u + 1u), dim3(256), 0, stream, d_slots, n_slots, parent_slots,
+                       p_code_off, p_lens, p_order, d_code_off, d_lens, d_order);
+    return hipGetLastError();
+}
+
 __global__ void swg_collect_saturated_kernel(const int32_t *scores, uint32_t n, int32_t ceiling, uint32_t *list,
                                              uint32_t *count, const uint32_t *lens, uint32_t *rows16)
 {

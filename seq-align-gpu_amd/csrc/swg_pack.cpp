@@ -18,6 +18,7 @@
 #include <cstring>
 #include <exception>
 #include <functional>
+#include <mutex>
 #include <new>
 #include <string>
 #include <thread>
@@ -39,9 +40,10 @@ static void derive_tables(swg_db *db)
         dwords += (uint64_t)nblk * SWG_BIN;
         rows_padded += (uint64_t)nblk * SWG_ROWS_PER_BLK * SWG_BIN;
     }
-    db->code_off.assign(ns + 1, 0);
+    // (a view's offsets are its root's, filled in by swg_view_host: its sequences are not laid end to end)
+    if (!db->root) db->code_off.assign(ns + 1, 0);
     for (size_t i = 0; i < ns; ++i) {
-        db->code_off[i + 1] = db->code_off[i] + ((uint64_t)db->lens[i] + 3) / 4 * 4;
+        if (!db->root) db->code_off[i + 1] = db->code_off[i] + ((uint64_t)db->lens[i] + 3) / 4 * 4;
         residues += db->lens[i];
         n_local += db->order[i] != 0xFFFFFFFFu;
     }
@@ -312,6 +314,7 @@ void swg_untranspose_batches16(const swg_batch16 *batches, size_t n_batches, con
 extern "C" int swg_db_save(const swg_db *db, const char *path)
 {
     if (!db || !path) return swg_set_global_error(SWG_ERR_ARG, "swg_db_save: NULL argument");
+    if (db->root) return swg_set_global_error(SWG_ERR_ARG, "swg_db_save: a view has no residue bytes of its own to write");
     FILE *f = fopen(path, "wb");
     if (!f) return swg_set_global_error(SWG_ERR_IO, "swg_db_save: cannot write %s", path);
     FileHeader h;
@@ -384,7 +387,7 @@ static int load_impl(const char *path, swg_db **out)
         const long long nsl = (long long)ns;
 #pragma omp parallel for schedule(dynamic, 512) reduction(| : bad) num_threads(swg_host_threads())
         for (long long s = 0; s < nsl; ++s) {
-            const uint8_t *cd = db->codes.data() + db->code_off[s];
+            const uint8_t *cd = swg_db_codes(db) + db->code_off[s];
             const uint32_t len = db->lens[s];
             for (uint32_t j = 0; j < len; ++j) bad |= (cd[j] & 7u) != 0 || cd[j] == 0;
             for (uint32_t j = len; j < (len + 3) / 4 * 4; ++j) bad |= cd[j] != 0;
@@ -403,9 +406,117 @@ extern "C" int swg_db_load(const char *path, swg_db **out)
     return guarded("swg_db_load", [&] { return load_impl(path, out); });
 }
 
+// ---------------------------------------------------------------------------
+// views: a chosen subset of a database as a database of its own (swg_db_view), host side
+// ---------------------------------------------------------------------------
+// The database is sorted by length, so any subset taken in sorted order is sorted too: the selected slots of the root,
+// ascending, ARE the view's slots 0 .. n-1 -- nothing is sorted and no residue byte is touched.
+static std::mutex g_view_mutex; // reference counts and the lazily built slot_of table of every root
+
+int swg_view_select(const swg_db *parent, const uint32_t *indices, size_t n, std::vector<uint32_t> *slots)
+{
+    slots->clear();
+    if (!parent || (n > 0 && !indices)) return swg_set_global_error(SWG_ERR_ARG, "swg_db_view: NULL argument");
+    swg_db *root = const_cast<swg_db *>(parent->root ? parent->root : parent);
+    for (size_t i = 0; i < n; ++i)
+        if (indices[i] >= root->n_total)
+            return swg_set_global_error(SWG_ERR_ARG, "swg_db_view: index %u (entry %zu of the list) is outside the database of %zu sequences",
+                                        indices[i], i, root->n_total);
+    {
+        std::lock_guard<std::mutex> lock(g_view_mutex);
+        if (root->slot_of.size() != root->n_total) {
+            root->slot_of.assign(root->n_total, 0xFFFFFFFFu);
+            for (size_t s = 0; s < root->order.size(); ++s)
+                if (root->order[s] != 0xFFFFFFFFu) root->slot_of[root->order[s]] = (uint32_t)s;
+        }
+    }
+    // marks instead of a sort: duplicates collapse, and a walk in slot order gives the slots ascending
+    std::vector<uint8_t> mark(root->order.size(), 0);
+    size_t marked = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t s = root->slot_of[indices[i]];
+        if (s != 0xFFFFFFFFu && !mark[s]) mark[s] = 1, ++marked; // (~0u: a sequence of another shard)
+    }
+    if (parent->root) { // a view of a view: what both select
+        for (const uint32_t s : parent->root_slot)
+            if (mark[s]) slots->push_back(s);
+    } else {
+        slots->reserve(marked);
+        for (size_t s = 0; s < mark.size() && slots->size() < marked; ++s)
+            if (mark[s]) slots->push_back((uint32_t)s);
+    }
+    return SWG_OK;
+}
+
+swg_db *swg_view_host(swg_db *parent, const std::vector<uint32_t> &slots)
+{
+    swg_db *root = parent->root ? parent->root : parent;
+    std::unique_ptr<swg_db> v(new swg_db());
+    const size_t n = slots.size(), nb = (n + SWG_BIN - 1) / SWG_BIN, ns = nb * SWG_BIN;
+    v->n_total = root->n_total;
+    v->n_bins = (uint32_t)nb;
+    v->order.assign(ns, 0xFFFFFFFFu);
+    v->lens.assign(ns, 0u);
+    v->code_off.assign(ns + 1, 0);
+    v->root_slot = slots;
+    for (size_t s = 0; s < n; ++s) {
+        v->order[s] = root->order[slots[s]];
+        v->lens[s] = root->lens[slots[s]];
+        v->code_off[s] = root->code_off[slots[s]];
+    }
+    v->root = root; // (before the tables: derive_tables leaves a view's offsets alone)
+    derive_tables(v.get());
+    std::lock_guard<std::mutex> lock(g_view_mutex);
+    ++root->refs;
+    return v.release();
+}
+
+size_t swg_db_views_alive(const swg_db *db)
+{
+    std::lock_guard<std::mutex> lock(g_view_mutex);
+    return db->root ? 0 : db->refs - (db->handle_live ? 1 : 0);
+}
+
+extern "C" int swg_debug_view_ranks(const swg_db *db, const uint32_t *indices, size_t n, uint32_t *out, size_t *n_out)
+{
+    if (!db || !n_out || (n > 0 && !out)) return swg_set_global_error(SWG_ERR_ARG, "swg_debug_view_ranks: NULL argument");
+    *n_out = 0;
+    return guarded("swg_debug_view_ranks", [&] {
+        std::vector<uint32_t> slots;
+        const int rc = swg_view_select(db, indices, n, &slots);
+        if (rc != SWG_OK) return rc;
+        std::copy(slots.begin(), slots.end(), out);
+        *n_out = slots.size();
+        return (int)SWG_OK;
+    });
+}
+
+// A root goes when its caller's handle and its last view are gone, whichever order they go in; until then a root whose
+// handle was freed keeps what its views read (the residue bytes and the slot words, host and device) and nothing else.
 extern "C" void swg_db_free(swg_db *db)
 {
     if (!db) return;
+    swg_db *root = db->root;
+    size_t left;
+    {
+        std::lock_guard<std::mutex> lock(g_view_mutex);
+        swg_db *counted = root ? root : db;
+        if (!root) db->handle_live = false;
+        left = --counted->refs;
+    }
+    if (root) {
+        swg_db_release_device(db);
+        delete db;
+        if (left == 0) {
+            swg_db_release_device(root);
+            delete root;
+        }
+        return;
+    }
+    if (left > 0) {
+        swg_db_release_search_state(db);
+        return;
+    }
     swg_db_release_device(db);
     delete db;
 }
@@ -419,6 +530,7 @@ extern "C" uint64_t swg_db_packed_bytes(const swg_db *db)
 {
     if (!db) return 0;
     const uint64_t ns = (uint64_t)db->n_bins * SWG_BIN;
+    if (db->root) return ns * 4u + (ns / 2 + 1) * 4u; // a view: its slots in the root, and the pair offsets
     return (uint64_t)db->codes.size() + ns * 16u + 8u + (ns / 2 + 1) * 4u;
 }
 extern "C" const uint32_t *swg_db_order(const swg_db *db) { return db ? db->order.data() : nullptr; }

@@ -256,7 +256,7 @@ static int align_batch(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, siz
                                          index, lq, len);
             const auto r = res_of.emplace(s, (uint64_t)res.size());
             if (r.second) {
-                const uint8_t *c = db->codes.data() + db->code_off[s];
+                const uint8_t *c = swg_db_codes(db) + db->code_off[s];
                 for (size_t x = 0; x < len; ++x) res.push_back((int8_t)(c[x] >> 3)); // codes are index << 3
             }
             SwgTraceJob jb = {};

@@ -16,7 +16,8 @@
  *     all-reduce merges the top-K lists); --pssm F scores the query by a PSI-BLAST ASCII PSSM
  *     (swg_pssm_load, swg_set_query_pssm) instead of the matrix (the matrix still fills the PSSM's
  *     unnamed columns); --pssmlist F does the same for every record of --allqueries, one PSSM file
- *     named per line (the records after the first go through swg_search_multi_pssm).
+ *     named per line (the records after the first go through swg_search_multi_pssm); --seqidlist F searches only
+ *     the database entries whose numbers F lists (a view of the resident database: swg_db_view, swg_group_select).
  * There is no CPU backend: without a GPU the tool fails with a message.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -63,7 +64,10 @@ static void usage(const char *argv0, const char *err)
             "    --packed             the database file is such a packed database: no parsing,\n"
             "                         no sorting; record names and sequences are not in it\n"
             "    --allqueries         every record of the query file against the resident database\n"
-            "                         (one block of output per query, headed `Query #n: name`)\n",
+            "                         (one block of output per query, headed `Query #n: name`)\n"
+            "    --seqidlist <file>   search only the listed database entries: one entry number per line, the\n"
+            "                         numbers of the `Entry #n` lines ('#' starts a comment, blank lines are skipped);\n"
+            "                         the Entry lines, Total Entries, --topk and --align report the listed entries only\n",
             argv0);
     exit(EXIT_FAILURE);
 }
@@ -160,7 +164,7 @@ int main(int argc, char **argv)
 {
     swg_scoring sc;
     swg_scoring_init(&sc);
-    const char *qpath = NULL, *dbpath = NULL, *savedb = NULL, *pssm_path = NULL, *pssmlist_path = NULL;
+    const char *qpath = NULL, *dbpath = NULL, *savedb = NULL, *pssm_path = NULL, *pssmlist_path = NULL, *idlist_path = NULL;
     int print_seq = 0, print_fasta = 0, have_matrix = 0, packed = 0, allq = 0;
     long topk = 0, gpu = 0, gpus = 0, v;
     int align = 0;
@@ -216,6 +220,8 @@ int main(int argc, char **argv)
             pssm_path = argv[++i];
         } else if (!strcasecmp(a, "--pssmlist")) {
             pssmlist_path = argv[++i];
+        } else if (!strcasecmp(a, "--seqidlist")) {
+            idlist_path = argv[++i];
         } else if (!strcasecmp(a, "--savedb")) {
             if (i >= argc - 1) usage(argv[0], "--savedb takes a file name");
             savedb = argv[++i];
@@ -285,6 +291,52 @@ int main(int argc, char **argv)
         return leave(EXIT_SUCCESS);
     }
     phase(packed ? "read query, load packed db" : "read query and database");
+    /* --seqidlist: the entries to search, and a mark per entry for the printing */
+    uint32_t *ids = NULL;
+    size_t n_ids = 0, n_listed = 0;
+    unsigned char *listed = NULL;
+    if (idlist_path) {
+        FILE *lf = fopen(idlist_path, "r");
+        if (!lf) {
+            fprintf(stderr, "Error: couldn't open the entry list %s\n", idlist_path);
+            return leave(EXIT_FAILURE);
+        }
+        listed = (unsigned char *)calloc(db.n ? db.n : 1, 1);
+        size_t cap = 0;
+        unsigned long line_no = 0;
+        char line[4096];
+        while (listed && fgets(line, sizeof line, lf)) {
+            line_no++;
+            char *b = line, *e = strchr(line, '#');
+            if (!e) e = line + strlen(line);
+            while (*b == ' ' || *b == '\t') b++;
+            while (e > b && (e[-1] == '\n' || e[-1] == '\r' || e[-1] == ' ' || e[-1] == '\t')) e--;
+            if (e <= b) continue;
+            *e = 0;
+            char *end = NULL;
+            const unsigned long long num = strtoull(b, &end, 10);
+            if (*b < '0' || *b > '9' || *end != 0 || num >= (unsigned long long)db.n) {
+                char msg[512];
+                snprintf(msg, sizeof msg, "--seqidlist %s line %lu: '%s' is not an entry number of this database (0..%lu)", idlist_path,
+                         line_no, b, (unsigned long)db.n - 1);
+                (void)leave(0);
+                usage(argv[0], msg);
+            }
+            if (n_ids == cap) {
+                cap = cap ? 2 * cap : 1024;
+                uint32_t *grown = (uint32_t *)realloc(ids, cap * sizeof *ids);
+                if (!grown) return leave(EXIT_FAILURE);
+                ids = grown;
+            }
+            ids[n_ids++] = (uint32_t)num;
+            if (!listed[num]) listed[num] = 1, n_listed++;
+        }
+        fclose(lf);
+        if (!listed || (!ids && !(ids = (uint32_t *)malloc(sizeof *ids)))) { /* (an empty list is a list: ids is not NULL) */
+            fprintf(stderr, "Error: out of memory\n");
+            return leave(EXIT_FAILURE);
+        }
+    }
     const size_t lq = (size_t)q.seq_off[1];
     int8_t *qidx = (int8_t *)malloc(lq);
     int8_t *didx = (int8_t *)malloc(db.n && !packed ? (size_t)db.seq_off[db.n] + 1 : 1);
@@ -395,6 +447,7 @@ int main(int argc, char **argv)
     double total_ms = 0.0;
     swg_ctx *ctx = NULL;
     swg_group *grp = NULL;
+    swg_db *sdb = NULL; /* what is searched: the database, or with --seqidlist the view of its listed entries */
     if (gpus > 0) {
         /* database sharded over several GPUs of this process */
         swg_stats *st = (swg_stats *)calloc((size_t)gpus, sizeof(swg_stats));
@@ -411,6 +464,10 @@ int main(int argc, char **argv)
         if (rc == SWG_OK) rc = pssm0 ? swg_group_set_query_pssm(grp, pssm0, lq) : swg_group_set_query(grp, qidx, lq);
         if (rc == SWG_OK) rc = swg_group_load(grp, didx, db.seq_off, db.n);
         phase("pack, shard and upload");
+        if (rc == SWG_OK && ids) {
+            rc = swg_group_select(grp, ids, n_ids);
+            phase("select the listed entries");
+        }
         if (rc == SWG_OK) rc = swg_group_search(grp, scores, hits, (size_t)topk, &n_hits, st);
         phase("search");
         if (rc != SWG_OK) {
@@ -454,7 +511,12 @@ int main(int argc, char **argv)
         }
         if (rc == SWG_OK) rc = swg_db_upload(ctx, pdb);
         phase("upload");
-        if (rc == SWG_OK) rc = swg_search(ctx, pdb, scores, hits, (size_t)topk, &n_hits, &st);
+        sdb = pdb;
+        if (rc == SWG_OK && ids) {
+            rc = swg_db_view(ctx, pdb, ids, n_ids, &sdb);
+            phase("select the listed entries");
+        }
+        if (rc == SWG_OK) rc = swg_search(ctx, sdb, scores, hits, (size_t)topk, &n_hits, &st);
         phase("search (first of this database)");
         if (rc != SWG_OK) {
             fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
@@ -478,8 +540,9 @@ int main(int argc, char **argv)
     char al_err[512] = "";
 next_query:
     if (allq) printf("Query #%lu: %s\n", (unsigned long)qi, qname);
-    for (size_t i = 0; i < db.n; i++) {
-        if (i % 16 == 0) {
+    for (size_t i = 0, shown = 0; i < db.n; i++) {
+        if (listed && !listed[i]) continue;
+        if (shown++ % 16 == 0) {
             if (print_fasta) {
                 fputs(qname, stdout);
                 putc('\n', stdout);
@@ -502,7 +565,7 @@ next_query:
     }
     /* reference src/alignment_cmdline.c:529-530; the time is the device time of the fill */
     printf("Total Time: %f\n", total_ms * 1e-3);
-    printf("Total Entries: %lu\n", (unsigned long)db.n);
+    printf("Total Entries: %lu\n", (unsigned long)(listed ? n_listed : db.n));
     if (topk > 0) {
         printf("Top %lu hits (score, entry, name):\n", (unsigned long)n_hits);
         for (size_t i = 0; i < n_hits; i++)
@@ -518,12 +581,12 @@ next_query:
             return leave(EXIT_FAILURE);
         }
         if (qi == 0) {
-            stride = grp ? swg_group_align_ops_bound(grp) : swg_align_ops_bound(ctx, pdb);
+            stride = grp ? swg_group_align_ops_bound(grp) : swg_align_ops_bound(ctx, sdb);
             al = (swg_alignment *)calloc(n_hits, sizeof *al);
             ops = (char *)malloc(n_hits * stride);
             if (!al || !ops) return leave(EXIT_FAILURE);
             if ((grp ? swg_group_align_hits(grp, hits, n_hits, al, ops, stride)
-                     : swg_align_hits(ctx, pdb, hits, n_hits, al, ops, stride)) != SWG_OK) {
+                     : swg_align_hits(ctx, sdb, hits, n_hits, al, ops, stride)) != SWG_OK) {
                 fprintf(stderr, "Error: %s\n", grp ? swg_group_last_error(grp) : swg_last_error(ctx));
                 return leave(EXIT_FAILURE);
             }
@@ -601,9 +664,9 @@ next_query:
             }
             swg_stats st;
             memset(&st, 0, sizeof st);
-            const int rc = plist ? swg_search_multi_pssm(ctx, pdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff, chunk_n, mq_scores,
+            const int rc = plist ? swg_search_multi_pssm(ctx, sdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff, chunk_n, mq_scores,
                                                          mq_hits, (size_t)topk, mq_nhits, &st)
-                                 : swg_search_multi(ctx, pdb, qx, qoff, chunk_n, mq_scores, mq_hits, (size_t)topk, mq_nhits, &st);
+                                 : swg_search_multi(ctx, sdb, qx, qoff, chunk_n, mq_scores, mq_hits, (size_t)topk, mq_nhits, &st);
             if (rc != SWG_OK) {
                 fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
                 return leave(EXIT_FAILURE);
@@ -623,7 +686,7 @@ next_query:
              * paths are kept to about 256 MB, so a chunk past either is aligned in several calls. */
             const size_t left = chunk_first + chunk_n - qi, kk = (size_t)topk;
             al_first = qi;
-            al_stride = swg_align_ops_bound_multi(pdb, qoff + at, left);
+            al_stride = swg_align_ops_bound_multi(sdb, qoff + at, left);
             size_t per = ((size_t)256 << 20) / (kk * al_stride);
             if (per > ((size_t)1 << 20) / kk) per = ((size_t)1 << 20) / kk;
             if (per < 1 || al_one_by_one) per = 1;
@@ -638,9 +701,9 @@ next_query:
             }
             for (;;) {
                 const double t0 = now_ms();
-                const int rc = plist ? swg_align_hits_multi_pssm(ctx, pdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff + at,
+                const int rc = plist ? swg_align_hits_multi_pssm(ctx, sdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff + at,
                                                                  al_n, mq_hits + at * kk, kk, mq_nhits + at, mq_al, mq_ops, al_stride)
-                                     : swg_align_hits_multi(ctx, pdb, qx, qoff + at, al_n, mq_hits + at * kk, kk, mq_nhits + at,
+                                     : swg_align_hits_multi(ctx, sdb, qx, qoff + at, al_n, mq_hits + at * kk, kk, mq_nhits + at,
                                                             mq_al, mq_ops, al_stride);
                 al_ms += now_ms() - t0, ++al_calls;
                 if (rc == SWG_OK) break;
@@ -670,6 +733,7 @@ next_query:
         fflush(stderr);
         _exit(leave(EXIT_SUCCESS));
     }
+    if (sdb != pdb) swg_db_free(sdb);
     swg_db_free(pdb);
     swg_destroy(ctx);
     swg_group_destroy(grp);
@@ -679,6 +743,8 @@ next_query:
     swg_pssm_free(pssm, NULL);
     free(plist);
     free(didx);
+    free(ids);
+    free(listed);
     free(scores);
     free(hits);
     free(mq_al);
