@@ -288,6 +288,38 @@ int swg_search_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, c
                           size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
                           swg_stats *stats);
 
+/* Every query of a batch against ITS OWN candidate list in one pass: what a prefilter, a PSI-BLAST iteration or a list
+ * of family members per query hands to the alignment step.  Query i is queries[q_offsets[i] .. q_offsets[i+1]) as
+ * swg_search_multi takes it; its candidates are cand[c_offsets[i] .. c_offsets[i+1]): ORIGINAL database indices, in any
+ * order, duplicates allowed, the list possibly empty.  The result for query i is by definition what
+ * swg_db_view(ctx, db, list i) + swg_set_query(query i) + swg_search(view) reports: exact int32 scores, hits ordered
+ * by higher score first, ties by lower index.  All lists of a chunk of 256 queries run in ONE launch over a table of
+ * (query, sequence) jobs; device memory and PCIe traffic grow with the total length of the lists, never with
+ * n_queries x database.  Batches that cannot take that launch (a query of several passes, scores that may pass 32767,
+ * gap scores outside the packed int16 form, engine or geometry options) go one list after another through a view: same
+ * results, swg_stats.fill_launches 0.
+ *   cand        an index >= swg_db_total_count(db) is SWG_ERR_ARG (the message names the query and the entry).  An
+ *               index this shard does not hold is ignored, and so is one that db, itself a view, does not select:
+ *               every rank of a sharded run passes the same lists.
+ *   db          resident (else SWG_ERR_STATE); one built from 16-lane batches is SWG_ERR_STATE as for swg_db_view.
+ *               Searches in flight on the context: SWG_ERR_STATE, as for swg_search_multi.
+ *   scores_out  NULL, or c_offsets[n_queries] int32 PARALLEL TO cand: scores_out[c_offsets[i] + j] is query i against
+ *               cand[c_offsets[i] + j]; duplicates each get the score, an ignored entry is not written.
+ *   topk_out/k  NULL/0, or n_queries rows of k hits with ORIGINAL indices (swg_align_hits_multi takes them against db
+ *               unchanged); n_hits NULL or n_queries counts, each at most the distinct candidates of its list held
+ *               here, 0 for an empty list.
+ *   stats       NULL, or ONE record for the batch: cells = sum over i of lq_i x the residues of list i's distinct
+ *               held candidates; the one launch reports engine 2, work_queue 1, path_bits 16, cell_form 0 or 2,
+ *               passes 1 and fill_launches = the chunks launched.
+ * The context's own query (index or PSSM) is left as it was. */
+int swg_search_lists(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets, size_t n_queries,
+                     const uint32_t *cand, const uint64_t *c_offsets, int32_t *scores_out, swg_hit *topk_out, size_t k,
+                     size_t *n_hits, swg_stats *stats);
+/* The same with position-specific queries: PSSM i is pssms[(q_offsets[i] + p)*32 + b], as swg_search_multi_pssm takes it. */
+int swg_search_lists_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets, size_t n_queries,
+                          const uint32_t *cand, const uint64_t *c_offsets, int32_t *scores_out, swg_hit *topk_out, size_t k,
+                          size_t *n_hits, swg_stats *stats);
+
 /* Reference-shaped replay of the call site itself: n_batches 16-lane batches
  * exactly as `alignment_fill_matrices` receives them -- db_idx_t is
  * aligner_t.seq_b_batch_indexes, [max_len][16] int8 (src/alignment.h:28,

@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "swg_set_option", "swg_set_scoring", "swg_set_query", "swg_set_query_pssm", "swg_db_pack", "swg_db_pack_shard", "swg_db_pack_shards", "swg_db_upload", "swg_db_view",
     "swg_db_free", "swg_db_save", "swg_db_load", "swg_db_count", "swg_db_total_count", "swg_db_residues",
     "swg_db_packed_bytes", "swg_db_order", "swg_search", "swg_search_begin", "swg_search_end", "swg_search_multi",
-    "swg_search_multi_pssm", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_align_hits_multi",
+    "swg_search_multi_pssm", "swg_search_lists", "swg_search_lists_pssm", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_align_hits_multi",
     "swg_align_hits_multi_pssm", "swg_align_ops_bound_multi", "swg_hit_key",
     "swg_key_hit", "swg_topk_merge_keys",
     "swg_group_create", "swg_group_destroy", "swg_group_size", "swg_group_last_error", "swg_group_set_option",
@@ -142,6 +142,8 @@ _sig("swg_search_begin", C.c_int, [_vp, _vp, C.c_int, C.c_size_t, C.POINTER(C.c_
 _sig("swg_search_end", C.c_int, [_vp, C.c_int, _vp, _vp, C.POINTER(C.c_size_t), C.POINTER(Stats)])
 _sig("swg_search_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
 _sig("swg_search_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
+_sig("swg_search_lists", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
+_sig("swg_search_lists_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
 _sig("swg_fill_batches16", C.c_int, [_vp, C.POINTER(Batch16), C.c_size_t, C.POINTER(C.c_double)])
 _sig("swg_align_hits", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t])
 _sig("swg_align_ops_bound", C.c_size_t, [_vp, _vp])
@@ -200,6 +202,8 @@ _sig("swg_debug_split", C.c_int, [_vp, C.c_size_t, C.c_uint64, _vp])
 _sig("swg_debug_list_plan", C.c_int, [C.c_size_t, C.c_uint32, C.c_int, _vp, _vp])
 _sig("swg_debug_pair_tokens", C.c_int, [_vp, _vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 _sig("swg_debug_view_ranks", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.POINTER(C.c_size_t)])
+_sig("swg_debug_list_jobs", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t), _vp])
+_sig("swg_debug_list_deal", C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 
 
 def _check(rc, ctx=None):
@@ -222,6 +226,17 @@ def _pssm(pssm):
         raise ValueError("PSSM values must fit int8")
     p, pp = _i8(a)
     return p, pp, a.shape[0]
+
+
+def _lists(lists):
+    """Candidate lists (one sequence of original indices per query) -> (flat uint32, offsets uint64[n + 1])."""
+    arrs = [np.ascontiguousarray(l, dtype=np.uint32).reshape(-1) for l in lists]
+    off = np.zeros(len(arrs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([a.size for a in arrs])
+    flat = np.concatenate(arrs) if arrs else np.zeros(0, dtype=np.uint32)
+    if flat.size == 0:
+        flat = np.zeros(1, dtype=np.uint32)           # (empty lists are lists: never a NULL pointer)
+    return np.ascontiguousarray(flat, dtype=np.uint32), off
 
 
 # ---------------------------------------------------------------------------
@@ -501,6 +516,32 @@ class Database:
         _check(lib.swg_debug_view_ranks(self.handle, ix.ctypes.data_as(_vp), ix.size, out.ctypes.data_as(_vp), C.byref(n)))
         return out[:n.value].copy()
 
+    def debug_list_jobs(self, lists):
+        """Test hook: the job table search_lists builds from one candidate list per query (no device needed) ->
+        (slots uint32: the job database's slots as slots of this database -- of its parent for a view --, ~0 = the empty
+        slot that ends an odd list; prefix uint64[n + 1]: row i's pairs are [prefix[i], prefix[i + 1]))."""
+        flat, off = _lists(lists)
+        n = C.c_size_t(0)
+        prefix = np.zeros(len(lists) + 1, dtype=np.uint64)
+        _check(lib.swg_debug_list_jobs(self.handle, flat.ctypes.data_as(_vp), off.ctypes.data_as(_vp), len(lists), None, 0,
+                                       C.byref(n), prefix.ctypes.data_as(_vp)))
+        slots = np.zeros(max(n.value, 1), dtype=np.uint32)
+        _check(lib.swg_debug_list_jobs(self.handle, flat.ctypes.data_as(_vp), off.ctypes.data_as(_vp), len(lists),
+                                       slots.ctypes.data_as(_vp), slots.size, C.byref(n), prefix.ctypes.data_as(_vp)))
+        return slots[:n.value].copy(), prefix
+
+    def debug_list_deal(self, lists, per_wg, resident):
+        """Test hook: the workgroups of search_lists' one launch over these lists, dealt by work (no device needed): an
+        (n, 2) array of (row, index within the row) per workgroup, for per_wg lane groups per workgroup and `resident`
+        workgroups on the chip."""
+        flat, off = _lists(lists)
+        n = C.c_size_t(0)
+        args = (self.handle, flat.ctypes.data_as(_vp), off.ctypes.data_as(_vp), len(lists), per_wg, resident)
+        _check(lib.swg_debug_list_deal(*args, None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 2), dtype=np.uint32)
+        _check(lib.swg_debug_list_deal(*args, out.ctypes.data_as(_vp), out.shape[0], C.byref(n)))
+        return out[:n.value].copy()
+
     def view(self, ctx, indices):
         """The sequences with the listed ORIGINAL indices (any order, duplicates collapse, those of other shards
         ignored) as a Database of its own that reads this one's resident bytes (swg_db_view).  Scores stay indexed by
@@ -585,6 +626,42 @@ class Context:
         qoff[1:] = np.cumsum([r.shape[0] for r in rows])
         pflat = np.ascontiguousarray(np.concatenate(rows) if nq else np.zeros((0, 32)), dtype=np.int8)
         return self._multi(lib.swg_search_multi_pssm, db, pflat, qoff, k, want_scores)
+
+    def search_lists(self, db, queries, lists, k=0, want_scores=True, fill=0):
+        """Every query against its own candidate list (original indices, any order, duplicates allowed, possibly empty)
+        in one pass -> (scores: list of int32 arrays parallel to each list, or None; hits: list of lists; stats dict).
+        Entries the library ignores (another shard's, outside a view) keep `fill`."""
+        nq = len(queries)
+        qoff = np.zeros(nq + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in queries])
+        qflat = np.ascontiguousarray(np.concatenate(queries) if nq else np.zeros(0), dtype=np.int8)
+        return self._lists_call(lib.swg_search_lists, db, qflat, qoff, lists, k, want_scores, fill)
+
+    def search_lists_pssm(self, db, pssms, lists, k=0, want_scores=True, fill=0):
+        """search_lists with position-specific queries: pssms as search_multi_pssm takes them."""
+        nq = len(pssms)
+        rows = [_pssm(p)[0] for p in pssms]
+        qoff = np.zeros(nq + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([r.shape[0] for r in rows])
+        pflat = np.ascontiguousarray(np.concatenate(rows) if nq else np.zeros((0, 32)), dtype=np.int8)
+        return self._lists_call(lib.swg_search_lists_pssm, db, pflat, qoff, lists, k, want_scores, fill)
+
+    def _lists_call(self, fn, db, qflat, qoff, lists, k, want_scores, fill):
+        nq = len(qoff) - 1
+        if len(lists) != nq:
+            raise ValueError("lists: %d for %d queries" % (len(lists), nq))
+        cflat, coff = _lists(lists)
+        scores = np.full(max(int(coff[nq]), 1), fill, dtype=np.int32) if want_scores else None
+        hits = (Hit * max(k * nq, 1))()
+        nh = (C.c_size_t * max(nq, 1))()
+        st = Stats()
+        rc = fn(self.handle, db.handle, qflat.ctypes.data_as(_vp), qoff.ctypes.data_as(_vp), nq, cflat.ctypes.data_as(_vp),
+                coff.ctypes.data_as(_vp), scores.ctypes.data_as(_vp) if want_scores else None, C.cast(hits, _vp) if k else None, k,
+                C.cast(nh, _vp), C.byref(st))
+        _check(rc, self.handle)
+        out = [[(int(hits[i * k + j].score), int(hits[i * k + j].index)) for j in range(nh[i])] for i in range(nq)]
+        per = [scores[int(coff[i]):int(coff[i + 1])].copy() for i in range(nq)] if want_scores else None
+        return per, out, st.as_dict()
 
     def _multi(self, fn, db, qflat, qoff, k, want_scores):
         nq = len(qoff) - 1

@@ -2676,11 +2676,46 @@ static int plan_batch(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, bool wan
 // PSSM), whether or not a query failed.  Statistics: the times, the re-scored sequences and the padded cells add up,
 // the geometry is the last search's; what a single search reports beyond that (lane groups, the long class, launches)
 // stays zero, as this route has always reported it.
+namespace {
+struct KeptQuery { // the context's own query across a batch searched one by one
+    bool pssm;
+    std::vector<int8_t> bytes;
+    explicit KeptQuery(const swg_ctx *ctx) : pssm(ctx->query_pssm), bytes(ctx->query_pssm ? ctx->pssm : ctx->query) {}
+    int restore(swg_ctx *ctx, int rc) const
+    {
+        if (!bytes.empty()) {
+            const int rq = pssm ? swg_set_query_pssm(ctx, bytes.data(), bytes.size() / 32) : swg_set_query(ctx, bytes.data(), bytes.size());
+            if (rc == SWG_OK) rc = rq;
+        } else {
+            ctx->query.clear();
+        }
+        return rc;
+    }
+};
+} // namespace
+static void add_one_search(swg_stats *st, const swg_stats &one)
+{
+    st->fill_ms += one.fill_ms;
+    st->rescore_ms += one.rescore_ms;
+    st->topk_ms += one.topk_ms;
+    st->total_ms += one.total_ms;
+    st->n_rescored += one.n_rescored;
+    st->cells_padded += one.cells_padded;
+    st->path_bits = one.path_bits;
+    st->cell_form = one.cell_form;
+    st->engine = one.engine;
+    st->cols_per_wave = one.cols_per_wave;
+    st->group_lanes = one.group_lanes;
+    st->waves = one.waves;
+    st->passes = one.passes;
+    st->workgroups = one.workgroups;
+    st->work_queue = one.work_queue;
+}
+
 static int search_batch_one_by_one(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, int32_t *scores_out, swg_hit *topk_out, size_t k,
                                    size_t *n_hits, swg_stats *st)
 {
-    const bool keep_pssm = ctx->query_pssm;
-    const std::vector<int8_t> keep = keep_pssm ? ctx->pssm : ctx->query;
+    const KeptQuery keep(ctx);
     int rc = SWG_OK;
     for (size_t i = 0; i < mq.n && rc == SWG_OK; ++i) {
         swg_stats one;
@@ -2689,29 +2724,9 @@ static int search_batch_one_by_one(swg_ctx *ctx, swg_db *db, const MultiQueries 
             rc = search_now(ctx, db, ctx->opt_autotune != 0, scores_out ? scores_out + i * db->n_total : nullptr,
                             topk_out ? topk_out + i * k : nullptr, k, n_hits ? n_hits + i : nullptr, &one);
         if (rc != SWG_OK) break;
-        st->fill_ms += one.fill_ms;
-        st->rescore_ms += one.rescore_ms;
-        st->topk_ms += one.topk_ms;
-        st->total_ms += one.total_ms;
-        st->n_rescored += one.n_rescored;
-        st->cells_padded += one.cells_padded;
-        st->path_bits = one.path_bits;
-        st->cell_form = one.cell_form;
-        st->engine = one.engine;
-        st->cols_per_wave = one.cols_per_wave;
-        st->group_lanes = one.group_lanes;
-        st->waves = one.waves;
-        st->passes = one.passes;
-        st->workgroups = one.workgroups;
-        st->work_queue = one.work_queue;
+        add_one_search(st, one);
     }
-    if (!keep.empty()) {
-        const int rq = keep_pssm ? swg_set_query_pssm(ctx, keep.data(), keep.size() / 32) : swg_set_query(ctx, keep.data(), keep.size());
-        if (rc == SWG_OK) rc = rq;
-    } else {
-        ctx->query.clear();
-    }
-    return rc;
+    return keep.restore(ctx, rc);
 }
 
 // ---- one launch per class for up to chunk_queries queries: the stages -----------------------------
@@ -2988,6 +3003,483 @@ extern "C" int swg_search_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_
     return ctx_guarded(ctx, "swg_search_multi_pssm", [&]() -> int {
         return search_multi_impl(ctx, const_cast<swg_db *>(db), MultiQueries{pssms, q_offsets, n_queries, true, "swg_search_multi_pssm"},
                                  scores_out, topk_out, k, n_hits, stats);
+    });
+}
+
+
+// ---------------------------------------------------------------------------
+// every query of a batch against its own candidate list in one pass
+// ---------------------------------------------------------------------------
+// swg_search_multi searches the same sequences for every query and keeps n_queries x n_slots scores on the device; a
+// prefilter hands over a list per query, 0.01 % of the database each.  Here the lists become one job database J
+// (swg_list_jobs: a view-like selection per query, laid end to end, aliasing the resident residue bytes), J gets slot words,
+// pair offsets and pair tokens by the kernels every database gets them from, and ONE launch of the work-queue fill's
+// LISTS instantiation runs it: workgroup b works for the row its table entry names, with that row's profile and queue, on
+// that row's pairs of J only, and every pair writes its two scores into the one score array of J.  What comes back is 4
+// bytes per job; the host scatters them to the caller's entries and selects each row's top-K.
+namespace {
+// One chunk of queries [q0, q0 + Qb): its job database on the host and how the launch's workgroups are dealt.
+struct ListChunk {
+    size_t q0 = 0, Qb = 0;
+    SwgListJobs J;
+    std::vector<uint32_t> pair_off;  // [pairs + 1] token blocks before each pair of J
+    std::vector<uint32_t> row_pairs; // [Qb + 1] J.row_pairs in the kernel's 32 bits
+    std::vector<uint2> wg_rows;      // the grid: (row, index within the row), rows with the most work first
+    size_t n_slots() const { return J.slots.size(); }
+    size_t n_pairs() const { return J.slots.size() / 2; }
+    uint64_t blocks() const { return pair_off.empty() ? 0 : pair_off.back(); }
+};
+// What a lists call decides before it queues anything: written once by plan_lists, read by the stages.
+struct SwgListsPlan {
+    bool one_launch = false; // else one list after another through a view, and nothing below is set
+    int go = 0, ge = 0, form = 0;
+    SwgDiagPlan pl;          // the one class
+    uint64_t bound_max = 0;
+    size_t lq_max = 0;
+    size_t chunk_queries = 256;
+    int resident_wgs = 0;    // workgroups of this geometry the chip holds
+    bool equal_shares = false; // experiment (SWG_LISTS_EQUAL_SHARES): workgroups dealt one share per row instead of by work
+    uint32_t class_queue_dwords = 0;
+    size_t rank_word_base = 0, queue_dwords = 0, prof_row_bytes = 0;
+};
+// Device buffers of a lists call, grown to the largest chunk; beside each what it holds (lists_fence).
+struct ListBufs {
+    uint32_t *d_slots = nullptr, *d_lens = nullptr, *d_order = nullptr, *d_pair_off = nullptr, *d_row_pairs = nullptr, *d_cnt = nullptr,
+             *d_qoff = nullptr;
+    uint64_t *d_code_off = nullptr;
+    uint4 *d_tok = nullptr;
+    uint2 *d_wg_rows = nullptr;
+    int32_t *d_scores = nullptr;
+    uint8_t *d_prof = nullptr;
+    int8_t *d_q = nullptr;
+    size_t cap_slots = 0, cap_pairs = 0, cap_rows = 0, cap_wgs = 0, cap_prof_rows = 0, cap_q = 0, cnt_rows = 0;
+    uint64_t cap_blocks = 0;
+    std::vector<int32_t> h_scores;
+    std::vector<uint32_t> qoff32;
+    std::vector<uint64_t> keys;
+    ~ListBufs()
+    {
+        for (void *p : {(void *)d_slots, (void *)d_lens, (void *)d_order, (void *)d_pair_off, (void *)d_row_pairs, (void *)d_cnt, (void *)d_qoff,
+                        (void *)d_code_off, (void *)d_tok, (void *)d_wg_rows, (void *)d_scores, (void *)d_prof, (void *)d_q})
+            (void)hipFree(p);
+    }
+};
+const uint64_t kListChunkBlocks = 1ull << 28; // token blocks of one chunk's J (4 GB of tokens); well inside pair_off's 32 bits
+} // namespace
+
+// The host image of every chunk: the job tables, their pair offsets, and the cells the batch is worth.  A chunk is at
+// most chunk_queries queries and is cut further where its J would pass the 32-bit limits of the slot count or the pair
+// offsets; a single list beyond them has no chunk (*too_large: the call then goes one list after another).
+static int lists_build_chunks(swg_ctx *ctx, const swg_db *db, const MultiQueries &mq, const uint32_t *cand, const uint64_t *c_off,
+                              size_t chunk_queries, std::vector<ListChunk> *chunks, bool *too_large, swg_stats *st)
+{
+    chunks->clear();
+    *too_large = false;
+    st->cells = st->bytes_alg = 0;
+    for (size_t q0 = 0; q0 < mq.n;) {
+        size_t Qb = std::min(chunk_queries, mq.n - q0);
+        ListChunk C;
+        for (;;) {
+            C = ListChunk();
+            C.q0 = q0;
+            C.Qb = Qb;
+            const int rc = swg_list_jobs(db, cand, c_off, q0, Qb, &C.J);
+            if (rc != SWG_OK) return swg_set_ctx_error(ctx, rc, "%s", swg_global_error());
+            const size_t np = C.n_pairs();
+            const uint64_t total = C.J.pair_blocks.back();
+            C.pair_off.assign(np + 1, 0u);
+            for (size_t p = 0; p <= np; ++p) C.pair_off[p] = (uint32_t)std::min<uint64_t>(C.J.pair_blocks[p], 0xFFFFFFFFull);
+            if (total <= kListChunkBlocks && C.n_slots() < (1ull << 31)) break;
+            if (Qb == 1) {
+                *too_large = true;
+                break;
+            }
+            Qb = (Qb + 1) / 2;
+        }
+        C.row_pairs.resize(Qb + 1);
+        for (size_t i = 0; i <= Qb; ++i) C.row_pairs[i] = (uint32_t)C.J.row_pairs[i];
+        for (size_t i = 0; i < Qb; ++i) {
+            st->cells += (uint64_t)mq.len(q0 + i) * C.J.row_residues[i];
+            st->bytes_alg += C.J.row_residues[i] + 8ull * (C.J.row_pairs[i + 1] - C.J.row_pairs[i]) * 2 + 32ull * mq.len(q0 + i) + 1024ull;
+        }
+        chunks->push_back(std::move(C));
+        q0 += Qb;
+    }
+    return SWG_OK;
+}
+
+// plan_batch's rules applied to the job database: the gap scores fit the packed form, no option asks for an engine or a
+// geometry, every query takes one pass of the class and no score can reach the int16 ceiling -- each query bounded by the
+// longest sequence of ITS OWN list --; the f16 cells where no query's bound reaches theirs.  One class takes all pairs
+// (the many rows amortise the chains: DESIGN 4.2), one pair per request, no two queries per lane (they would need the same
+// sequence).  The geometry is the planner's for the chunk with the most work, its pairs longest first.
+static int plan_lists(swg_ctx *ctx, const swg_db *db, const MultiQueries &mq, const std::vector<ListChunk> &chunks, bool too_large,
+                      SwgListsPlan *plan)
+{
+    *plan = SwgListsPlan();
+    SwgListsPlan P;
+    const swg_db *root = db->root ? db->root : db;
+    P.go = ctx->gap_open + ctx->gap_extend;
+    P.ge = ctx->gap_extend;
+    for (size_t i = 0; i < mq.n; ++i) P.lq_max = std::max(P.lq_max, mq.len(i));
+    bool fast = ctx->gap_open <= 0 && ctx->gap_extend <= 0 && -P.go <= SWG_I16_CEILING && ctx->opt_force_bits != 32 &&
+                ctx->opt_engine != 1 && ctx->opt_dynamic != 0 && !too_large && ctx->opt_cols == 0 && ctx->opt_group == 0 &&
+                ctx->opt_max_waves == 0 && ctx->opt_workgroups == 0;
+    const ListChunk *big = nullptr;
+    for (const ListChunk &C : chunks) {
+        if (!big || C.blocks() > big->blocks()) big = &C;
+        for (size_t i = 0; i < C.Qb && fast; ++i) {
+            if (C.J.row_pairs[i + 1] == C.J.row_pairs[i]) continue; // (an empty list scores nothing)
+            const size_t q = C.q0 + i;
+            const uint64_t longest = ((uint64_t)C.J.row_longest[i] + SWG_ROWS_PER_BLK - 1) / SWG_ROWS_PER_BLK * SWG_ROWS_PER_BLK;
+            const SwgScoreBound sb = mq.pssm ? swg_score_bound(mq.at(q), nullptr, mq.len(q), longest)
+                                             : swg_score_bound(&ctx->sub[0][0], mq.at(q), mq.len(q), longest);
+            P.bound_max = std::max(P.bound_max, sb.bound);
+            if (sb.bound >= SWG_I16_CEILING) fast = false;
+        }
+    }
+    if (!fast || !big || big->n_pairs() == 0) { // (nothing to launch anywhere: the route that launches nothing)
+        plan->lq_max = P.lq_max;
+        return SWG_OK;
+    }
+    P.form = ctx->opt_f16 != 0 && P.bound_max < SWG_F16_CEILING && swg_f16_gaps_ok(P.go, P.ge) ? 2 : 0;
+    // the planner's model of J: its pairs, longest first (the planner reads lengths and nothing else)
+    swg_db M;
+    {
+        const size_t np = big->n_pairs();
+        std::vector<std::pair<uint32_t, uint32_t>> pairs(np);
+        for (size_t p = 0; p < np; ++p) {
+            const uint32_t sy = big->J.slots[2 * p + 1];
+            pairs[p] = std::make_pair(root->lens[big->J.slots[2 * p]], sy == 0xFFFFFFFFu ? 0u : root->lens[sy]);
+        }
+        std::sort(pairs.begin(), pairs.end(), std::greater<std::pair<uint32_t, uint32_t>>());
+        M.n_local = 2 * np;
+        M.n_bins = (uint32_t)((2 * np + SWG_BIN - 1) / SWG_BIN);
+        M.lens.assign((size_t)M.n_bins * SWG_BIN, 0u);
+        for (size_t p = 0; p < np; ++p) M.lens[2 * p] = pairs[p].first, M.lens[2 * p + 1] = pairs[p].second;
+    }
+    SwgDiagWork wk;
+    fast = swg_plan_diag_work(&M, P.lq_max, ctx->n_cu, 0, 0, 0, -1, false, true, &wk, 1.0, P.form, 1) == 1 && wk.plan[0].npass == 1 &&
+           (size_t)wk.plan[0].G * wk.plan[0].K >= P.lq_max;
+    if (!fast) {
+        plan->lq_max = P.lq_max;
+        return SWG_OK;
+    }
+    P.pl = wk.plan[0];
+    P.resident_wgs = ctx->n_cu * swg_workgroups_per_cu(swg_diag_variant_info(P.pl.variant).max_waves, P.pl.W,
+                                                       swg_diag_dyn_lds_bytes(P.pl.K, P.pl.G, P.pl.W));
+    static const bool equal_shares = getenv("SWG_LISTS_EQUAL_SHARES") != nullptr;
+    P.equal_shares = equal_shares;
+    P.class_queue_dwords = SWG_DYN_SHARDS * SWG_DYN_SHARD_STRIDE;
+    P.rank_word_base = P.chunk_queries * P.class_queue_dwords; // (the queues serve a full chunk's rows)
+    P.queue_dwords = P.rank_word_base + SWG_DYN_SIMD_SLOTS;
+    P.prof_row_bytes = (size_t)P.pl.G * (size_t)swg_diag_padded_cols(P.pl.K) * 64;
+    P.one_launch = true;
+    *plan = P;
+    return SWG_OK;
+}
+
+// The workgroups of one chunk's launch, dealt by work: every row with pairs gets one, and the rest of the chip's
+// resident workgroups go to the rows in proportion to their token blocks -- never more than a row's pairs can keep busy
+// (one pair per lane group).  Rows with the most work come first in the grid; empty rows get none.  With 256 rows per
+// chunk and a workgroup per CU the grid stays within what the chip holds at once.
+static void lists_deal_workgroups(const SwgListsPlan &P, ListChunk *C)
+{
+    swg_lists_deal(C->J, (uint64_t)P.pl.W * (64 / P.pl.G), (uint64_t)std::max(0, P.resident_wgs), P.equal_shares, &C->wg_rows);
+}
+
+template <class T> static int lists_grow(swg_ctx *ctx, T **d, size_t *cap, size_t need, size_t extra = 0)
+{
+    if (*d && *cap >= need) return SWG_OK;
+    (void)hipFree(*d);
+    *d = nullptr;
+    *cap = 0;
+    HIP_TRY(ctx, hipMalloc(d, std::max<size_t>(16, (need + extra) * sizeof(T))));
+    *cap = need;
+    return SWG_OK;
+}
+
+// The device buffers for one chunk, each with what it holds written beside it.
+static int lists_allocate(swg_ctx *ctx, const SwgListsPlan &P, const ListChunk &C, const MultiQueries &mq, ListBufs *B)
+{
+    int rc;
+    size_t cap = B->cap_slots;
+    if ((rc = lists_grow(ctx, &B->d_slots, &cap, C.n_slots())) != SWG_OK) return rc;
+    cap = B->cap_slots;
+    if ((rc = lists_grow(ctx, &B->d_lens, &cap, C.n_slots())) != SWG_OK) return rc;
+    cap = B->cap_slots;
+    if ((rc = lists_grow(ctx, &B->d_order, &cap, C.n_slots())) != SWG_OK) return rc;
+    cap = B->cap_slots;
+    if ((rc = lists_grow(ctx, &B->d_code_off, &cap, C.n_slots(), 1)) != SWG_OK) return rc;
+    if ((rc = lists_grow(ctx, &B->d_scores, &B->cap_slots, C.n_slots())) != SWG_OK) return rc;
+    if ((rc = lists_grow(ctx, &B->d_pair_off, &B->cap_pairs, C.n_pairs(), 1)) != SWG_OK) return rc;
+    size_t cb = (size_t)B->cap_blocks;
+    if ((rc = lists_grow(ctx, &B->d_tok, &cb, (size_t)C.blocks(), 1)) != SWG_OK) return rc; // (+ the block of zeros behind the last pair)
+    B->cap_blocks = cb;
+    if ((rc = lists_grow(ctx, &B->d_row_pairs, &B->cap_rows, C.Qb, 1)) != SWG_OK) return rc;
+    cap = B->cap_prof_rows;
+    if ((rc = lists_grow(ctx, &B->d_qoff, &cap, C.Qb, 1)) != SWG_OK) return rc;
+    if (!B->d_prof || B->cap_prof_rows < C.Qb) {
+        (void)hipFree(B->d_prof);
+        B->d_prof = nullptr;
+        B->cap_prof_rows = 0;
+        HIP_TRY(ctx, hipMalloc(&B->d_prof, C.Qb * P.prof_row_bytes));
+        B->cap_prof_rows = C.Qb;
+    }
+    if ((rc = lists_grow(ctx, &B->d_wg_rows, &B->cap_wgs, C.wg_rows.size())) != SWG_OK) return rc;
+    if (!B->d_cnt) {
+        HIP_TRY(ctx, hipMalloc(&B->d_cnt, P.queue_dwords * 4));
+        B->cnt_rows = P.chunk_queries;
+    }
+    const size_t qbytes = (size_t)(mq.off[C.q0 + C.Qb] - mq.off[C.q0]) * mq.row_bytes();
+    return lists_grow(ctx, &B->d_q, &B->cap_q, qbytes);
+}
+
+// The fence before every launch, in the manner of multi_rows_ok: what the launch will index -- from the chunk's tables,
+// as the launch's own arguments are -- against what the buffers hold.  A violation is a bug of this file; it is reported
+// as SWG_ERR_STATE, not launched (the fault of round 3 was a row count that disagreed with a buffer: DESIGN 4.2).
+static int lists_fence(swg_ctx *ctx, const SwgListsPlan &P, const ListChunk &C, const ListBufs &B, size_t grid)
+{
+    const char *fn = "swg_search_lists";
+    const size_t np = C.n_pairs();
+    if (C.wg_rows.size() != grid || grid == 0 || B.cap_wgs < grid)
+        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: the workgroup table has %zu entries (room for %zu), the grid %zu", fn, C.wg_rows.size(), B.cap_wgs, grid);
+    for (size_t b = 0; b < grid; ++b)
+        if (C.wg_rows[b].x >= C.Qb)
+            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: workgroup %zu is dealt to row %u of a chunk of %zu rows", fn, b, C.wg_rows[b].x, C.Qb);
+    if (C.row_pairs.size() != C.Qb + 1 || C.row_pairs[0] != 0u || C.pair_off.size() != np + 1)
+        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: %zu range entries and %zu pair offsets for %zu rows and %zu pairs", fn, C.row_pairs.size(),
+                                 C.pair_off.size(), C.Qb, np);
+    for (size_t i = 0; i < C.Qb; ++i) // disjoint and ascending by construction of a prefix: each range within J, none reversed
+        if (C.row_pairs[i + 1] < C.row_pairs[i] || C.row_pairs[i + 1] > np)
+            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: row %zu takes pairs [%u, %u) of a job table of %zu pairs", fn, i, C.row_pairs[i],
+                                     C.row_pairs[i + 1], np);
+    struct { const char *name; size_t have, need; } chk[] = {
+        {"d_scores / slot words", B.cap_slots, C.n_slots()}, {"d_pair_off", B.cap_pairs, np},
+        {"d_tok", (size_t)B.cap_blocks, (size_t)C.blocks()},  {"d_row_pairs", B.cap_rows, C.Qb},
+        {"d_prof", B.cap_prof_rows, C.Qb},                    {"d_cnt", B.cnt_rows, C.Qb},
+        {"queue words", P.queue_dwords, C.Qb * (size_t)P.class_queue_dwords + SWG_DYN_SIMD_SLOTS},
+    };
+    for (const auto &c : chk)
+        if (c.have < c.need)
+            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: %s holds %zu, the launch indexes %zu (chunk of %zu rows, %zu jobs)", fn, c.name, c.have,
+                                     c.need, C.Qb, C.n_slots());
+    if (2 * np != C.n_slots()) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: %zu slots are not %zu whole pairs", fn, C.n_slots(), np);
+    return SWG_OK;
+}
+
+// One chunk to the device: J's slots (4 bytes per job) and pair offsets, from which the gather and token kernels write
+// its slot words and tokens out of the root's resident ones; the queries, their profiles; scores and queues zeroed.
+static int lists_stage_chunk(swg_ctx *ctx, const swg_db *db, const SwgListsPlan &P, const MultiQueries &mq, const ListChunk &C, ListBufs *B)
+{
+    hipStream_t s = ctx->stream;
+    const swg_db *root = db->root ? db->root : db;
+    const size_t ns = C.n_slots(), np = C.n_pairs(), Qb = C.Qb;
+    HIP_TRY(ctx, hipMemcpyAsync(B->d_slots, C.J.slots.data(), ns * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(B->d_pair_off, C.pair_off.data(), (np + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(B->d_row_pairs, C.row_pairs.data(), (Qb + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(B->d_wg_rows, C.wg_rows.data(), C.wg_rows.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, swg_launch_gather_view(B->d_slots, (uint32_t)ns, (uint32_t)root->order.size(), root->d_code_off, root->d_lens, root->d_order,
+                                        B->d_code_off, B->d_lens, B->d_order, s));
+    HIP_TRY(ctx, hipMemsetAsync(B->d_tok + C.blocks(), 0, 16, s));
+    HIP_TRY(ctx, swg_launch_build_tokens(root->d_codes, B->d_code_off, B->d_lens, B->d_pair_off, (uint32_t)np, C.blocks(), B->d_tok, s));
+    std::vector<uint32_t> &qoff32 = B->qoff32;
+    qoff32.resize(Qb + 1);
+    for (size_t i = 0; i <= Qb; ++i) qoff32[i] = (uint32_t)(mq.off[C.q0 + i] - mq.off[C.q0]);
+    const size_t qbytes = (size_t)(mq.off[C.q0 + Qb] - mq.off[C.q0]) * mq.row_bytes();
+    HIP_TRY(ctx, hipMemcpyAsync(B->d_q, mq.at(C.q0), qbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(B->d_qoff, qoff32.data(), (Qb + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(B->d_scores, 0, ns * 4, s));
+    HIP_TRY(ctx, hipMemsetAsync(B->d_cnt, 0, P.queue_dwords * 4, s));
+    const int kp = swg_diag_padded_cols(P.pl.K);
+    HIP_TRY(ctx, swg_launch_build_profiles_multi(ctx->d_sub, mq.pssm ? nullptr : B->d_q, B->d_qoff, (uint32_t)Qb, (uint32_t)(P.pl.G * kp), P.pl.K, kp,
+                                                 B->d_prof, s, SWG_LDS_SWIZZLE ? P.pl.G : 0, P.form == 2, mq.pssm ? B->d_q : nullptr));
+    return SWG_OK;
+}
+
+// The fill of one chunk: one launch, a 1-D grid of the dealt workgroups.  Events: ev[1] before, ev[2] after.
+static int lists_launch_chunk(swg_ctx *ctx, const SwgListsPlan &P, const ListChunk &C, const ListBufs &B)
+{
+    hipStream_t s = ctx->stream;
+    SwgPairTokens T; // (what the launch's token parameters are read from: this chunk's J)
+    T.d_tok = B.d_tok;
+    T.d_pair_off = B.d_pair_off;
+    T.total_blocks = C.blocks();
+    SwgDiagDynParams q = dyn_params_base(T, B.d_scores, C.n_slots(), P.pl.G, P.form, P.go, P.ge, 1, B.d_cnt + P.rank_word_base);
+    q.queue = B.d_cnt;
+    q.queue_stride = P.class_queue_dwords;
+    q.profile = B.d_prof;
+    q.profile_stride = P.prof_row_bytes;
+    q.score_stride = 0;
+    q.q_begin = 0;
+    q.q_end = (uint32_t)C.n_pairs();
+    q.row_pairs = B.d_row_pairs;
+    q.wg_rows = B.d_wg_rows;
+    q.prio_blocks = bulk_prio_blocks(ctx, C.blocks(), (uint64_t)C.wg_rows.size() * P.pl.W * (64 / P.pl.G));
+    HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[1], s));
+    HIP_TRY(ctx, swg_launch_diag_lists(P.pl.variant, P.form, P.pl.W, (int)C.wg_rows.size(), q, s));
+    HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[2], s));
+    return SWG_OK;
+}
+
+// A row's results from J's scores (host): the caller's entries through the entry-to-job map -- duplicates get the same
+// score, ignored entries none -- and the row's k best by swg_hit_key's order over its non-empty slots.
+static void lists_deliver_rows(const swg_db *db, const ListChunk &C, const int32_t *h_scores, const uint64_t *c_off, size_t k,
+                               int32_t *scores_out, swg_hit *topk_out, size_t *n_hits, std::vector<uint64_t> *keys)
+{
+    const swg_db *root = db->root ? db->root : db;
+    if (scores_out)
+        for (size_t e = 0; e < C.J.entry_job.size(); ++e)
+            if (C.J.entry_job[e] != 0xFFFFFFFFu) scores_out[C.J.entry0 + e] = h_scores[C.J.entry_job[e]];
+    (void)c_off;
+    for (size_t i = 0; i < C.Qb; ++i) {
+        size_t m = 0;
+        if (k > 0 && topk_out) {
+            keys->clear();
+            for (size_t j = 2 * C.J.row_pairs[i]; j < 2 * C.J.row_pairs[i + 1]; ++j)
+                if (C.J.slots[j] != 0xFFFFFFFFu) keys->push_back(swg_hit_key(h_scores[j], root->order[C.J.slots[j]]));
+            m = std::min(k, keys->size());
+            std::partial_sort(keys->begin(), keys->begin() + m, keys->end(), std::greater<uint64_t>());
+            for (size_t j = 0; j < m; ++j) swg_key_hit((*keys)[j], &topk_out[(C.q0 + i) * k + j]);
+        }
+        if (n_hits) n_hits[C.q0 + i] = m;
+    }
+}
+
+// One device-to-host copy of J's scores (4 bytes per job) behind the chunk's fill, then the rows on the host.
+static int lists_deliver_chunk(swg_ctx *ctx, const swg_db *db, const ListChunk &C, ListBufs *B, const uint64_t *c_off, size_t k,
+                               int32_t *scores_out, swg_hit *topk_out, size_t *n_hits, swg_stats *st)
+{
+    hipStream_t s = ctx->stream;
+    B->h_scores.resize(C.n_slots());
+    HIP_TRY(ctx, hipMemcpyAsync(B->h_scores.data(), B->d_scores, C.n_slots() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, spin_sync(ctx, s));
+    float ms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->cur->ev[1], ctx->cur->ev[2]));
+    st->fill_ms += ms;
+    st->total_ms += ms;
+    const auto t0 = std::chrono::steady_clock::now();
+    lists_deliver_rows(db, C, B->h_scores.data(), c_off, k, scores_out, topk_out, n_hits, &B->keys);
+    st->topk_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SWG_OK;
+}
+
+// One list after another: a view per list, then swg_search's own body; the context's query is put back afterwards.
+// Statistics as search_batch_one_by_one reports them (fill_launches stays 0).
+static int lists_one_by_one(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, const std::vector<ListChunk> &chunks, const uint32_t *cand,
+                            const uint64_t *c_off, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits, swg_stats *st)
+{
+    const KeptQuery keep(ctx);
+    std::vector<int32_t> by_index(scores_out ? db->n_total : 0);
+    int rc = SWG_OK;
+    for (const ListChunk &C : chunks)
+        for (size_t i = 0; i < C.Qb && rc == SWG_OK; ++i) {
+            const size_t q = C.q0 + i;
+            const uint64_t e0 = c_off[q], e1 = c_off[q + 1];
+            if (n_hits) n_hits[q] = 0;
+            if (C.J.row_pairs[i + 1] == C.J.row_pairs[i]) continue; // nothing of the list is held here
+            swg_db *view = nullptr;
+            swg_stats one;
+            rc = swg_db_view(ctx, db, cand + e0, (size_t)(e1 - e0), &view);
+            if (rc == SWG_OK) rc = mq.pssm ? swg_set_query_pssm(ctx, mq.at(q), mq.len(q)) : swg_set_query(ctx, mq.at(q), mq.len(q));
+            if (rc == SWG_OK)
+                rc = search_now(ctx, view, ctx->opt_autotune != 0, scores_out ? by_index.data() : nullptr, topk_out ? topk_out + q * k : nullptr, k,
+                                n_hits ? n_hits + q : nullptr, &one);
+            swg_db_free(view);
+            if (rc != SWG_OK) break;
+            for (uint64_t e = e0; e < e1 && scores_out; ++e)
+                if (C.J.entry_job[(size_t)(e - C.J.entry0)] != 0xFFFFFFFFu) scores_out[e] = by_index[cand[e]];
+            add_one_search(st, one);
+        }
+    return keep.restore(ctx, rc);
+}
+
+// The statistics of a lists call that went through the launches, from its plan and its chunks.
+static void lists_report(const SwgListsPlan &P, const std::vector<ListChunk> &chunks, int launches, swg_stats *st)
+{
+    st->path_bits = 16;
+    st->engine = 2;
+    st->work_queue = 1;
+    st->classes_overlapped = -1;
+    st->cell_form = P.form;
+    st->cols_per_wave = P.pl.K;
+    st->group_lanes = P.pl.G;
+    st->waves = P.pl.W;
+    st->passes = 1;
+    st->fill_launches = launches;
+    for (const ListChunk &C : chunks) {
+        if (C.wg_rows.empty()) continue;
+        st->workgroups = (int32_t)C.wg_rows.size(); // (the last launch's)
+        st->streams = (int32_t)(C.wg_rows.size() * P.pl.W * (64 / P.pl.G));
+        st->cells_padded += 2ull * P.pl.G * P.pl.K * C.blocks() * 4ull;
+    }
+}
+
+static int search_lists_impl(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, const uint32_t *cand, const uint64_t *c_off,
+                             int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits, swg_stats *stats)
+{
+    swg_stats st;
+    memset(&st, 0, sizeof st);
+    int rc = validate_batch(ctx, db, mq, topk_out, k, &st);
+    if (rc != SWG_OK) return rc;
+    if (mq.n && (!c_off || (c_off[mq.n] > c_off[0] && !cand))) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: NULL argument", mq.fn);
+    if (db->tokens_only)
+        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: a database built from 16-lane batches has no residue bytes to list candidates of", mq.fn);
+    st.cells = st.bytes_alg = 0;
+    if (stats) *stats = st;
+    if (mq.n == 0) return SWG_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<ListChunk> chunks;
+    bool too_large = false;
+    rc = lists_build_chunks(ctx, db, mq, cand, c_off, 256, &chunks, &too_large, &st);
+    if (rc != SWG_OK) return rc;
+    SwgListsPlan P;
+    rc = plan_lists(ctx, db, mq, chunks, too_large, &P);
+    if (rc != SWG_OK) return rc;
+    if (!P.one_launch) {
+        rc = lists_one_by_one(ctx, db, mq, chunks, cand, c_off, scores_out, topk_out, k, n_hits, &st);
+        if (stats) *stats = st;
+        return rc;
+    }
+    ListBufs B;
+    ctx->cur = &ctx->slots[0];
+    int launches = 0;
+    for (ListChunk &C : chunks) {
+        lists_deal_workgroups(P, &C);
+        if (C.wg_rows.empty()) { // every list of the chunk is empty here: nothing to launch, nothing to write
+            for (size_t i = 0; i < C.Qb && n_hits; ++i) n_hits[C.q0 + i] = 0;
+            continue;
+        }
+        rc = lists_allocate(ctx, P, C, mq, &B);
+        if (rc == SWG_OK) rc = lists_fence(ctx, P, C, B, C.wg_rows.size()); // what this chunk's launch will index, against the buffers
+        if (rc == SWG_OK) rc = lists_stage_chunk(ctx, db, P, mq, C, &B);
+        if (rc == SWG_OK) rc = lists_launch_chunk(ctx, P, C, B);
+        if (rc == SWG_OK) rc = lists_deliver_chunk(ctx, db, C, &B, c_off, k, scores_out, topk_out, n_hits, &st);
+        if (rc != SWG_OK) return rc;
+        ++launches;
+    }
+    lists_report(P, chunks, launches, &st);
+    if (stats) *stats = st;
+    return SWG_OK;
+}
+
+extern "C" int swg_search_lists(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets, size_t n_queries,
+                                const uint32_t *cand, const uint64_t *c_offsets, int32_t *scores_out, swg_hit *topk_out, size_t k,
+                                size_t *n_hits, swg_stats *stats)
+{
+    return ctx_guarded(ctx, "swg_search_lists", [&]() -> int {
+        return search_lists_impl(ctx, const_cast<swg_db *>(db), MultiQueries{queries, q_offsets, n_queries, false, "swg_search_lists"}, cand,
+                                 c_offsets, scores_out, topk_out, k, n_hits, stats);
+    });
+}
+
+extern "C" int swg_search_lists_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets, size_t n_queries,
+                                     const uint32_t *cand, const uint64_t *c_offsets, int32_t *scores_out, swg_hit *topk_out, size_t k,
+                                     size_t *n_hits, swg_stats *stats)
+{
+    return ctx_guarded(ctx, "swg_search_lists_pssm", [&]() -> int {
+        return search_lists_impl(ctx, const_cast<swg_db *>(db), MultiQueries{pssms, q_offsets, n_queries, true, "swg_search_lists_pssm"}, cand,
+                                 c_offsets, scores_out, topk_out, k, n_hits, stats);
     });
 }
 

@@ -389,11 +389,39 @@ inline const uint8_t *swg_db_codes(const swg_db *db) { return (db->root ? db->ro
 // order, duplicates collapse, those of other shards ignored) select among parent's sequences, ascending; SWG_ERR_ARG for
 // an index outside the whole database.  swg_view_host: the view of those slots with its whole host image, holding a
 // reference on the root.  swg_db_views_alive: views that keep this database's bytes alive.
-int swg_view_select(const swg_db *parent, const uint32_t *indices, size_t n, std::vector<uint32_t> *slots);
+// marks (or NULL): a scratch vector the caller keeps between many calls on one database, all zero between them -- a short
+// list then costs its own length, not the database's.
+int swg_view_select(const swg_db *parent, const uint32_t *indices, size_t n, std::vector<uint32_t> *slots,
+                    std::vector<uint8_t> *marks = nullptr);
 swg_db *swg_view_host(swg_db *parent, const std::vector<uint32_t> &slots);
 size_t swg_db_views_alive(const swg_db *db);
 // test hook: swg_view_select's answer (out has room for n entries; slots of the root of `db`)
 extern "C" int swg_debug_view_ranks(const swg_db *db, const uint32_t *indices, size_t n, uint32_t *out, size_t *n_out);
+// Candidate lists (swg_search_lists), host side (swg_pack.cpp; no GPU): the job database J of the queries
+// [q0, q0 + nq) -- query i's candidates are cand[c_off[i] .. c_off[i + 1]) --, a view-like selection per query laid end to
+// end.  Segment i = the distinct slots of db's root that list i selects (swg_view_select: ascending, so longest first),
+// filled up to a whole pair with an empty slot (~0u); row i's pairs are [row_pairs[i], row_pairs[i + 1]).
+struct SwgListJobs {
+    std::vector<uint32_t> slots;        // J slot -> the root's slot, ~0u = the empty slot that ends an odd segment
+    std::vector<uint64_t> row_pairs;    // [nq + 1]
+    std::vector<uint32_t> entry_job;    // [entries of the nq lists] J slot of entry c_off[q0] + e, ~0u = ignored (not held here)
+    std::vector<uint64_t> row_residues; // [nq] residues of the row's distinct held candidates
+    std::vector<uint32_t> row_longest;  // [nq] the longest of them
+    std::vector<uint64_t> pair_blocks;  // [pairs + 1] 4-row token blocks before each pair of J (two reset rows + the longer sequence)
+    uint64_t entry0 = 0;                // c_off[q0]
+};
+int swg_list_jobs(const swg_db *db, const uint32_t *cand, const uint64_t *c_off, size_t q0, size_t nq, SwgListJobs *J);
+// The workgroups of one launch over J, dealt by work: every row with pairs gets one, the rest of `resident` (the chip's
+// resident workgroups of the launch's geometry) goes to the rows in proportion to their token blocks (equal_shares: one
+// share per row, the comparison the dealing is measured against), never more than a row's pairs can keep busy at per_wg
+// lane groups per workgroup; rows with the most work first, empty rows none.  out: (row, index within the row) per workgroup.
+void swg_lists_deal(const SwgListJobs &J, uint64_t per_wg, uint64_t resident, bool equal_shares, std::vector<uint2> *out);
+// test hook: that table for the lists' job database, two words per workgroup (copied when it fits cap workgroups)
+extern "C" int swg_debug_list_deal(const swg_db *db, const uint32_t *cand, const uint64_t *c_off, size_t n_queries, uint64_t per_wg,
+                                   uint64_t resident, uint32_t *out, size_t cap, size_t *n_wgs);
+// test hook: J's slots (copied when they fit cap) and the n_queries + 1 pair-range prefix
+extern "C" int swg_debug_list_jobs(const swg_db *db, const uint32_t *cand, const uint64_t *c_off, size_t n_queries, uint32_t *slots_out,
+                                   size_t cap, size_t *n_slots, uint64_t *row_pairs_out);
 // test hook: the pair-token image as the device built it, or as the host restatement builds it
 // test hook: the next visit of the named site throws std::bad_alloc (swg_api.cpp); 0 disarms
 extern "C" void swg_debug_fail_alloc(int site);

@@ -106,6 +106,12 @@ struct SwgDiagDynParams {
     // diagnostics that cost nothing: [0] wall clock when the first wavefront of the launch started
     // (atomic min), [1] when the last one ended (atomic max); zero-initialised = not run.  Null: none.
     unsigned long long *stamps;
+    // candidate lists (swg_search_lists, the LISTS instantiations only; a 1-D grid): workgroup b works for row
+    // wg_rows[b].x of the launch -- that row's profile and queue as above -- as the wg_rows[b].y-th of the row's workgroups
+    // (its home shard), and takes the pairs [row_pairs[row], row_pairs[row + 1]) of the job database and only those
+    // (q_begin / q_end are not read).  Pair ids are unique across rows: one score array, score_stride 0.
+    const uint32_t *row_pairs; // [rows + 1]
+    const uint2 *wg_rows;      // [grid]
 };
 
 // The int32 fill with a work queue (swg_diag32q_kernel): items are sequences (sorted ranks), either
@@ -204,6 +210,8 @@ size_t swg_diag_dyn_lds_bytes(int K, int G, int W, bool fma = false);
 // fma (form 2 only): with the fma pairing, profile built by swg_launch_build_profile with elem_size 4, 2-column chunks
 hipError_t swg_launch_diag_dyn(int variant, bool edges, int form, int W, int workgroups, const SwgDiagDynParams &p,
                                hipStream_t stream, int n_queries = 1, bool fma = false);
+// The LISTS instantiations (single pass, form 0 or 2, v_perm_b32 pairing): a 1-D grid of `workgroups` = entries of p.wg_rows
+hipError_t swg_launch_diag_lists(int variant, int form, int W, int workgroups, const SwgDiagDynParams &p, hipStream_t stream);
 // profiles of n_queries queries (query i = queries[q_off[i] .. q_off[i+1])) in one launch: query i's
 // profile of ncols layout columns goes to d_profiles + i * ncols * 32 * 2 (int16).  d_pssms: a batch of PSSMs
 // (query i = rows q_off[i] .. q_off[i+1] of [..][32]), d_queries unread

@@ -1016,10 +1016,14 @@ DEVINL uint32_t quad_bcast(uint32_t x, int r)
 // FORM: the cells (see CellsDiag): 0 packed int16, 1 wide (scores to 65535; needs EDGES: a query that can pass
 // 32767 is long), 2 packed f16 with three-operand maxima (scores below 4096, anything above is flagged).
 // FMA: FORM 2 with the (score, 1.0) profile and the v_pk_fma_f16 pairing (see CellsDiag).
-template <int K, int MAXW, bool EDGES = false, int FORM = 0, bool FMA = false>
+// LISTS: every query of a batch against its own candidate list (swg_search_lists): a 1-D grid whose workgroups are dealt
+// to the rows by a host-built table, each row with its own range of pairs (see SwgDiagDynParams::wg_rows).  Only the
+// set-up and the queue's event code know of it; the flag is a constant that folds away everywhere else.
+template <int K, int MAXW, bool EDGES = false, int FORM = 0, bool FMA = false, bool LISTS = false>
 __global__ __launch_bounds__(MAXW * 64) void swg_diag_dyn_kernel(const SwgDiagDynParams p)
 {
     constexpr bool WIDE = FORM == 1, F16 = FORM == 2;
+    static_assert(!LISTS || (!EDGES && !FMA && FORM != 1), "lists: single pass, int16 or f16 cells with the perm pairing");
     using Cells = CellsDiag<K, FORM, FMA>;
     static_assert(EDGES || !WIDE, "the wide form is instantiated with edges only");
     extern __shared__ __attribute__((aligned(256))) uint8_t smem[]; // query profile, then the group records
@@ -1046,9 +1050,18 @@ __global__ __launch_bounds__(MAXW * 64) void swg_diag_dyn_kernel(const SwgDiagDy
     const uint64_t t_start = p.trace ? wall_clock64() : 0ull;
     if (p.stamps && lane == 0) atomicMax(p.stamps, ~(unsigned long long)wall_clock64()); // earliest start, as the maximum of the complements (0 = not run)
     // several queries in one launch: row y of the grid works for query y (its profile, its queue, its scores)
-    const uint8_t *profile = p.profile + (size_t)blockIdx.y * p.profile_stride;
-    uint32_t *const queue = p.queue + (size_t)blockIdx.y * p.queue_stride;
-    int32_t *const scores = p.scores + (size_t)blockIdx.y * p.score_stride;
+    // (LISTS: the row and the workgroup's place in it come from the table; the row's pairs from the range prefix)
+    uint32_t l_row = 0u, l_home = 0u, l_begin = 0u, l_end = 0u;
+    if (LISTS) {
+        const uint2 e = p.wg_rows[blockIdx.x];
+        l_row = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.x);
+        l_home = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.y);
+        l_begin = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.row_pairs[l_row]);
+        l_end = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.row_pairs[l_row + 1u]);
+    }
+    const uint8_t *profile = p.profile + (size_t)(LISTS ? l_row : blockIdx.y) * p.profile_stride;
+    uint32_t *const queue = p.queue + (size_t)(LISTS ? l_row : blockIdx.y) * p.queue_stride;
+    int32_t *const scores = LISTS ? p.scores : p.scores + (size_t)blockIdx.y * p.score_stride;
     for (uint32_t o = threadIdx.x * 16u; o < slice; o += blockDim.x * 16u)
         *reinterpret_cast<uint4 *>(smem + o) = *reinterpret_cast<const uint4 *>(profile + o);
     {
@@ -1166,7 +1179,7 @@ __global__ __launch_bounds__(MAXW * 64) void swg_diag_dyn_kernel(const SwgDiagDy
                 bool second = (fl & SWG_DYN_SECOND) != 0u;
                 uint32_t tried = fl >> 8;
                 uint32_t nq = SWG_DYN_NONE, first = 0u, len = 0u;
-                const uint32_t left = p.batch_B > 1u ? st[3] : 0u; // pairs of the group's own batch not handed out yet
+                const uint32_t left = !LISTS && p.batch_B > 1u ? st[3] : 0u; // pairs of the group's own batch not handed out yet (LISTS: one pair per request)
                 if (left != 0u) {
                     nq = st[4];
                     const uint32_t j = nq - st[6];
@@ -1179,12 +1192,21 @@ __global__ __launch_bounds__(MAXW * 64) void swg_diag_dyn_kernel(const SwgDiagDy
                 uint32_t claimed = 1u;
                 for (;;) {
                     if (tried >= SWG_DYN_SHARDS) {
-                        if (second || p.q2_end <= p.q2_begin) break;
+                        if (LISTS || second || p.q2_end <= p.q2_begin) break; // (LISTS: a row's workgroups stay with their row)
                         second = true; // own range empty: go on with the other launch's
                         tried = 0u;
                     }
-                    const uint32_t shard = (blockIdx.x + tried) & (SWG_DYN_SHARDS - 1u);
+                    const uint32_t shard = ((LISTS ? l_home : blockIdx.x) + tried) & (SWG_DYN_SHARDS - 1u);
                     uint32_t *ctr = (second ? p.queue2 : queue) + shard * SWG_DYN_SHARD_STRIDE;
+                    if (LISTS) {
+                        const uint32_t cand = l_begin + shard + SWG_DYN_SHARDS * atomicAdd(ctr, 1u);
+                        if (cand < l_end) {
+                            nq = cand;
+                            break;
+                        }
+                        ++tried;
+                        continue;
+                    }
                     if (p.list) {
                         const uint32_t at = shard + SWG_DYN_SHARDS * atomicAdd(ctr, 1u);
                         if (at < n_list) {
@@ -2690,7 +2712,18 @@ typedef void (*SwgQQKernel)(const SwgDiagQQParams);
 SwgDynKernel swg_dyn_kernel_i16(int variant, int which);
 SwgDynKernel swg_dyn_kernel_f16(int variant, int which);
 
+// LISTS: form 0 from part 1, form 2 from part 2
+SwgDynKernel swg_dyn_kernel_lists_i16(int variant);
+SwgDynKernel swg_dyn_kernel_lists_f16(int variant);
+
 #if SWG_HAS_PART(1)
+SwgDynKernel swg_dyn_kernel_lists_i16(int variant)
+{
+#define SWG_ROW(K, W) swg_diag_dyn_kernel<K, W, false, 0, false, true>,
+    static const SwgDynKernel t[] = {SWG_DIAG_VARIANTS(SWG_ROW)};
+#undef SWG_ROW
+    return t[variant];
+}
 SwgDynKernel swg_dyn_kernel_i16(int variant, int which)
 {
 #define SWG_ROW(K, W) {swg_diag_dyn_kernel<K, W, false, 0>, swg_diag_dyn_kernel<K, W, true, 0>, swg_diag_dyn_kernel<K, W, true, 1>},
@@ -2701,6 +2734,13 @@ SwgDynKernel swg_dyn_kernel_i16(int variant, int which)
 #endif
 
 #if SWG_HAS_PART(2)
+SwgDynKernel swg_dyn_kernel_lists_f16(int variant)
+{
+#define SWG_ROW(K, W) swg_diag_dyn_kernel<K, W, false, 2, false, true>,
+    static const SwgDynKernel t[] = {SWG_DIAG_VARIANTS(SWG_ROW)};
+#undef SWG_ROW
+    return t[variant];
+}
 SwgDynKernel swg_dyn_kernel_f16(int variant, int which)
 {
 #define SWG_ROW(K, W) {swg_diag_dyn_kernel<K, W, false, 2>, swg_diag_dyn_kernel<K, W, true, 2>, swg_diag_dyn_kernel<K, W, false, 2, true>, \
@@ -2893,6 +2933,22 @@ hipError_t swg_launch_diag_dyn(int variant, bool edges, int form, int W, int wor
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(workgroups, n_queries), dim3(W * 64), lds, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t swg_launch_diag_lists(int variant, int form, int W, int workgroups, const SwgDiagDynParams &p, hipStream_t stream)
+{
+    int n;
+    const DiagVariant *v = diag_variants(&n);
+    if (variant < 0 || variant >= n || W < 1 || W > v[variant].max_waves || workgroups < 1 || (p.G != 16 && p.G != 32 && p.G != 64) ||
+        (form != 0 && form != 2) || !p.row_pairs || !p.wg_rows || p.list || p.score_stride != 0u || p.batch_B > 1u)
+        return hipErrorInvalidValue;
+    const size_t lds = swg_diag_dyn_lds_bytes(v[variant].K, (int)p.G, W, false);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    auto k = form == 2 ? swg_dyn_kernel_lists_f16(variant) : swg_dyn_kernel_lists_i16(variant);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3(workgroups), dim3(W * 64), lds, stream, p);
     return hipGetLastError();
 }
 

@@ -413,7 +413,7 @@ extern "C" int swg_db_load(const char *path, swg_db **out)
 // ascending, ARE the view's slots 0 .. n-1 -- nothing is sorted and no residue byte is touched.
 static std::mutex g_view_mutex; // reference counts and the lazily built slot_of table of every root
 
-int swg_view_select(const swg_db *parent, const uint32_t *indices, size_t n, std::vector<uint32_t> *slots)
+int swg_view_select(const swg_db *parent, const uint32_t *indices, size_t n, std::vector<uint32_t> *slots, std::vector<uint8_t> *marks)
 {
     slots->clear();
     if (!parent || (n > 0 && !indices)) return swg_set_global_error(SWG_ERR_ARG, "swg_db_view: NULL argument");
@@ -429,6 +429,23 @@ int swg_view_select(const swg_db *parent, const uint32_t *indices, size_t n, std
             for (size_t s = 0; s < root->order.size(); ++s)
                 if (root->order[s] != 0xFFFFFFFFu) root->slot_of[root->order[s]] = (uint32_t)s;
         }
+    }
+    if (marks) {
+        // Many short lists against one database (swg_search_lists): the caller's marks, all zero between calls, so that a
+        // list costs what its own length costs -- the slots are collected as they are first marked and sorted, and only
+        // their marks are cleared again.
+        marks->resize(root->order.size(), 0);
+        for (size_t i = 0; i < n; ++i) {
+            const uint32_t s = root->slot_of[indices[i]];
+            if (s != 0xFFFFFFFFu && !(*marks)[s]) (*marks)[s] = 1, slots->push_back(s);
+        }
+        for (const uint32_t s : *slots) (*marks)[s] = 0;
+        std::sort(slots->begin(), slots->end());
+        if (parent->root) // a view: what both select
+            slots->erase(std::remove_if(slots->begin(), slots->end(), [&](uint32_t s) {
+                             return !std::binary_search(parent->root_slot.begin(), parent->root_slot.end(), s);
+                         }), slots->end());
+        return SWG_OK;
     }
     // marks instead of a sort: duplicates collapse, and a walk in slot order gives the slots ascending
     std::vector<uint8_t> mark(root->order.size(), 0);
@@ -487,6 +504,114 @@ extern "C" int swg_debug_view_ranks(const swg_db *db, const uint32_t *indices, s
         if (rc != SWG_OK) return rc;
         std::copy(slots.begin(), slots.end(), out);
         *n_out = slots.size();
+        return (int)SWG_OK;
+    });
+}
+
+// ---------------------------------------------------------------------------
+// candidate lists: every query of a batch against its own list (swg_search_lists), host side
+// ---------------------------------------------------------------------------
+// The lists of the queries [q0, q0 + nq) as ONE job database J, built the way a view is: segment i holds the distinct
+// selected slots of the root for list i, ascending (= longest first: the root is sorted by length), filled up to a whole
+// pair with an empty slot (~0u).  Nothing is sorted across segments and no residue byte is read.
+int swg_list_jobs(const swg_db *db, const uint32_t *cand, const uint64_t *c_off, size_t q0, size_t nq, SwgListJobs *J)
+{
+    *J = SwgListJobs();
+    if (!db || !c_off || (c_off[q0 + nq] > c_off[q0] && !cand)) return swg_set_global_error(SWG_ERR_ARG, "swg_search_lists: NULL argument");
+    const swg_db *root = db->root ? db->root : db;
+    for (size_t i = 0; i < nq; ++i) {
+        if (c_off[q0 + i + 1] < c_off[q0 + i])
+            return swg_set_global_error(SWG_ERR_ARG, "swg_search_lists: the candidate offsets decrease at query %zu", q0 + i);
+        for (uint64_t e = c_off[q0 + i]; e < c_off[q0 + i + 1]; ++e)
+            if (cand[e] >= root->n_total)
+                return swg_set_global_error(SWG_ERR_ARG, "swg_search_lists: index %u (entry %llu of the list of query %zu) is outside the database of %zu sequences",
+                                            cand[e], (unsigned long long)(e - c_off[q0 + i]), q0 + i, root->n_total);
+    }
+    J->entry0 = c_off[q0];
+    J->row_pairs.assign(nq + 1, 0);
+    J->row_residues.assign(nq, 0);
+    J->row_longest.assign(nq, 0);
+    J->entry_job.assign((size_t)(c_off[q0 + nq] - c_off[q0]), 0xFFFFFFFFu);
+    std::vector<uint32_t> sel;
+    std::vector<uint8_t> marks;
+    for (size_t i = 0; i < nq; ++i) {
+        const uint64_t e0 = c_off[q0 + i], e1 = c_off[q0 + i + 1];
+        const int rc = swg_view_select(db, e1 > e0 ? cand + e0 : nullptr, (size_t)(e1 - e0), &sel, &marks);
+        if (rc != SWG_OK) return rc;
+        const size_t b = J->slots.size();
+        if (b + sel.size() + 1 >= 0xFFFFFFF0ull) return swg_set_global_error(SWG_ERR_ARG, "swg_search_lists: too many jobs in one chunk");
+        for (const uint32_t s : sel) J->row_residues[i] += root->lens[s];
+        J->row_longest[i] = sel.empty() ? 0u : root->lens[sel.front()];
+        // an entry's job: where its sequence's slot stands in the segment (none: another shard's, or outside the view)
+        for (uint64_t e = e0; e < e1; ++e) {
+            const uint32_t s = root->slot_of[cand[e]];
+            const auto at = std::lower_bound(sel.begin(), sel.end(), s);
+            if (s != 0xFFFFFFFFu && at != sel.end() && *at == s) J->entry_job[(size_t)(e - J->entry0)] = (uint32_t)(b + (size_t)(at - sel.begin()));
+        }
+        J->slots.insert(J->slots.end(), sel.begin(), sel.end());
+        if (sel.size() & 1u) J->slots.push_back(0xFFFFFFFFu);
+        J->row_pairs[i + 1] = J->slots.size() / 2;
+    }
+    const size_t np = J->slots.size() / 2;
+    J->pair_blocks.assign(np + 1, 0);
+    for (size_t p = 0; p < np; ++p) // (a segment is sorted: the pair's first sequence is its longer)
+        J->pair_blocks[p + 1] = J->pair_blocks[p] + (2ull + root->lens[J->slots[2 * p]] + 3) / 4;
+    return SWG_OK;
+}
+
+void swg_lists_deal(const SwgListJobs &J, uint64_t per_wg, uint64_t resident, bool equal_shares, std::vector<uint2> *out)
+{
+    out->clear();
+    const size_t nq = J.row_pairs.size() - 1;
+    per_wg = std::max<uint64_t>(1, per_wg);
+    std::vector<uint32_t> rows;
+    for (size_t i = 0; i < nq; ++i)
+        if (J.row_pairs[i + 1] > J.row_pairs[i]) rows.push_back((uint32_t)i);
+    if (rows.empty()) return;
+    auto blocks_of = [&](uint32_t r) { return J.pair_blocks[J.row_pairs[r + 1]] - J.pair_blocks[J.row_pairs[r]]; };
+    std::stable_sort(rows.begin(), rows.end(), [&](uint32_t a, uint32_t b) { return blocks_of(a) > blocks_of(b); });
+    const uint64_t spare = resident > rows.size() ? resident - rows.size() : 0;
+    const uint64_t total = std::max<uint64_t>(1, J.pair_blocks.back());
+    for (const uint32_t r : rows) {
+        const uint64_t pairs = J.row_pairs[r + 1] - J.row_pairs[r];
+        const uint64_t share = equal_shares ? spare / rows.size() : (uint64_t)((long double)spare * blocks_of(r) / total);
+        const uint64_t n = std::min<uint64_t>(1 + share, (pairs + per_wg - 1) / per_wg);
+        for (uint64_t j = 0; j < n; ++j) out->push_back(make_uint2(r, (uint32_t)j));
+    }
+}
+
+extern "C" int swg_debug_list_deal(const swg_db *db, const uint32_t *cand, const uint64_t *c_off, size_t n_queries, uint64_t per_wg,
+                                   uint64_t resident, uint32_t *out, size_t cap, size_t *n_wgs)
+{
+    if (!db || !n_wgs || (n_queries > 0 && !c_off)) return swg_set_global_error(SWG_ERR_ARG, "swg_debug_list_deal: NULL argument");
+    *n_wgs = 0;
+    return guarded("swg_debug_list_deal", [&] {
+        SwgListJobs J;
+        const uint64_t none[1] = {0};
+        const int rc = swg_list_jobs(db, cand, n_queries ? c_off : none, 0, n_queries, &J);
+        if (rc != SWG_OK) return rc;
+        std::vector<uint2> wgs;
+        swg_lists_deal(J, per_wg, resident, false, &wgs);
+        *n_wgs = wgs.size();
+        if (out && wgs.size() <= cap)
+            for (size_t b = 0; b < wgs.size(); ++b) out[2 * b] = wgs[b].x, out[2 * b + 1] = wgs[b].y;
+        return (int)SWG_OK;
+    });
+}
+
+extern "C" int swg_debug_list_jobs(const swg_db *db, const uint32_t *cand, const uint64_t *c_off, size_t n_queries, uint32_t *slots_out,
+                                   size_t cap, size_t *n_slots, uint64_t *row_pairs_out)
+{
+    if (!db || !n_slots || (n_queries > 0 && !c_off)) return swg_set_global_error(SWG_ERR_ARG, "swg_debug_list_jobs: NULL argument");
+    *n_slots = 0;
+    return guarded("swg_debug_list_jobs", [&] {
+        SwgListJobs J;
+        const uint64_t none[1] = {0};
+        const int rc = swg_list_jobs(db, cand, n_queries ? c_off : none, 0, n_queries, &J);
+        if (rc != SWG_OK) return rc;
+        *n_slots = J.slots.size();
+        if (slots_out && J.slots.size() <= cap) std::copy(J.slots.begin(), J.slots.end(), slots_out);
+        if (row_pairs_out) std::copy(J.row_pairs.begin(), J.row_pairs.end(), row_pairs_out);
         return (int)SWG_OK;
     });
 }

@@ -17,7 +17,9 @@
  *     (swg_pssm_load, swg_set_query_pssm) instead of the matrix (the matrix still fills the PSSM's
  *     unnamed columns); --pssmlist F does the same for every record of --allqueries, one PSSM file
  *     named per line (the records after the first go through swg_search_multi_pssm); --seqidlist F searches only
- *     the database entries whose numbers F lists (a view of the resident database: swg_db_view, swg_group_select).
+ *     the database entries whose numbers F lists (a view of the resident database: swg_db_view, swg_group_select);
+ *     --allqueries --candidates F searches every query record against its own entries, F's `query entry` lines (one
+ *     pass for all records: swg_search_lists).
  * There is no CPU backend: without a GPU the tool fails with a message.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -67,7 +69,12 @@ static void usage(const char *argv0, const char *err)
             "                         (one block of output per query, headed `Query #n: name`)\n"
             "    --seqidlist <file>   search only the listed database entries: one entry number per line, the\n"
             "                         numbers of the `Entry #n` lines ('#' starts a comment, blank lines are skipped);\n"
-            "                         the Entry lines, Total Entries, --topk and --align report the listed entries only\n",
+            "                         the Entry lines, Total Entries, --topk and --align report the listed entries only\n"
+            "    --candidates <file>  with --allqueries: every query record against its own candidates, all records in one\n"
+            "                         pass: one `query_record_number entry_number` pair per line, numbered as `Query #n` and\n"
+            "                         `Entry #n` ('#' starts a comment, blank lines are skipped); a record without lines has an\n"
+            "                         empty list; per query the Entry lines, Total Entries, --topk and --align report its own\n"
+            "                         entries only\n",
             argv0);
     exit(EXIT_FAILURE);
 }
@@ -164,7 +171,7 @@ int main(int argc, char **argv)
 {
     swg_scoring sc;
     swg_scoring_init(&sc);
-    const char *qpath = NULL, *dbpath = NULL, *savedb = NULL, *pssm_path = NULL, *pssmlist_path = NULL, *idlist_path = NULL;
+    const char *qpath = NULL, *dbpath = NULL, *savedb = NULL, *pssm_path = NULL, *pssmlist_path = NULL, *idlist_path = NULL, *cand_path = NULL;
     int print_seq = 0, print_fasta = 0, have_matrix = 0, packed = 0, allq = 0;
     long topk = 0, gpu = 0, gpus = 0, v;
     int align = 0;
@@ -222,6 +229,8 @@ int main(int argc, char **argv)
             pssmlist_path = argv[++i];
         } else if (!strcasecmp(a, "--seqidlist")) {
             idlist_path = argv[++i];
+        } else if (!strcasecmp(a, "--candidates")) {
+            cand_path = argv[++i];
         } else if (!strcasecmp(a, "--savedb")) {
             if (i >= argc - 1) usage(argv[0], "--savedb takes a file name");
             savedb = argv[++i];
@@ -258,6 +267,10 @@ int main(int argc, char **argv)
     if ((packed || savedb || allq) && gpus > 0) usage(argv[0], "--packed/--savedb/--allqueries work with one GPU (--gpu)");
     if (align && topk == 0) usage(argv[0], "--align reports the alignments of the --topk hits: give --topk K");
     if (pssm_path && allq) usage(argv[0], "--pssm scores one query: it does not combine with --allqueries");
+    if (cand_path && !allq) usage(argv[0], "--candidates lists the entries of --allqueries' records: give --allqueries");
+    if (cand_path && gpus > 0) usage(argv[0], "--candidates works with one GPU (--gpu)");
+    if (cand_path && idlist_path) usage(argv[0], "--candidates and --seqidlist do not combine (the candidates are the entries to search)");
+    if (cand_path && pssm_path) usage(argv[0], "--candidates and --pssm do not combine (--pssmlist names a PSSM per record)");
 
     char err[512];
     swg_seqs q, db;
@@ -336,6 +349,76 @@ int main(int argc, char **argv)
             fprintf(stderr, "Error: out of memory\n");
             return leave(EXIT_FAILURE);
         }
+    }
+    /* --candidates: record r's entries are cands[c_off[r] .. c_off[r + 1]) in the file's order; lsc is parallel to cands
+     * (swg_search_lists' scores_out), and `listed` marks the current record's entries for the printing */
+    uint32_t *cands = NULL;
+    uint64_t *c_off = NULL;
+    int32_t *lsc = NULL;
+    if (cand_path) {
+        FILE *lf = fopen(cand_path, "r");
+        if (!lf) {
+            fprintf(stderr, "Error: couldn't open the candidate list %s\n", cand_path);
+            return leave(EXIT_FAILURE);
+        }
+        uint32_t *rec = NULL, *ent = NULL; /* the lines as they come */
+        size_t n_lines = 0, cap = 0;
+        unsigned long line_no = 0;
+        char line[4096];
+        while (fgets(line, sizeof line, lf)) {
+            line_no++;
+            char *b = line, *e = strchr(line, '#');
+            if (!e) e = line + strlen(line);
+            while (*b == ' ' || *b == '\t') b++;
+            while (e > b && (e[-1] == '\n' || e[-1] == '\r' || e[-1] == ' ' || e[-1] == '\t')) e--;
+            if (e <= b) continue;
+            *e = 0;
+            char *t2 = b;
+            while (*t2 && *t2 != ' ' && *t2 != '\t') t2++;
+            if (*t2) *t2++ = 0;
+            while (*t2 == ' ' || *t2 == '\t') t2++;
+            char *end = NULL;
+            const unsigned long long rn = strtoull(b, &end, 10);
+            if (*b < '0' || *b > '9' || *end != 0 || rn >= (unsigned long long)q.n) {
+                char msg[512];
+                snprintf(msg, sizeof msg, "--candidates %s line %lu: '%s' is not a query record number of this query file (0..%lu)",
+                         cand_path, line_no, b, (unsigned long)q.n - 1);
+                (void)leave(0);
+                usage(argv[0], msg);
+            }
+            const unsigned long long en = strtoull(t2, &end, 10);
+            if (*t2 < '0' || *t2 > '9' || *end != 0 || en >= (unsigned long long)db.n) {
+                char msg[512];
+                snprintf(msg, sizeof msg, "--candidates %s line %lu: '%s' is not an entry number of this database (0..%lu)", cand_path,
+                         line_no, t2, (unsigned long)db.n - 1);
+                (void)leave(0);
+                usage(argv[0], msg);
+            }
+            if (n_lines == cap) {
+                cap = cap ? 2 * cap : 1024;
+                uint32_t *g1 = (uint32_t *)realloc(rec, cap * sizeof *rec);
+                if (g1) rec = g1;
+                uint32_t *g2 = (uint32_t *)realloc(ent, cap * sizeof *ent);
+                if (g2) ent = g2;
+                if (!g1 || !g2) return leave(EXIT_FAILURE);
+            }
+            rec[n_lines] = (uint32_t)rn;
+            ent[n_lines++] = (uint32_t)en;
+        }
+        fclose(lf);
+        c_off = (uint64_t *)calloc(q.n + 2, sizeof *c_off);
+        cands = (uint32_t *)malloc((n_lines ? n_lines : 1) * sizeof *cands);
+        lsc = (int32_t *)calloc(n_lines ? n_lines : 1, sizeof *lsc);
+        listed = (unsigned char *)calloc(db.n ? db.n : 1, 1);
+        if (!c_off || !cands || !lsc || !listed) {
+            fprintf(stderr, "Error: out of memory\n");
+            return leave(EXIT_FAILURE);
+        }
+        for (size_t l = 0; l < n_lines; l++) c_off[rec[l] + 2]++; /* (counting sort by record, the file's order kept) */
+        for (size_t r = 0; r < q.n; r++) c_off[r + 2] += c_off[r + 1];
+        for (size_t l = 0; l < n_lines; l++) cands[c_off[rec[l] + 1]++] = ent[l];
+        free(rec);
+        free(ent);
     }
     const size_t lq = (size_t)q.seq_off[1];
     int8_t *qidx = (int8_t *)malloc(lq);
@@ -516,7 +599,13 @@ int main(int argc, char **argv)
             rc = swg_db_view(ctx, pdb, ids, n_ids, &sdb);
             phase("select the listed entries");
         }
-        if (rc == SWG_OK) rc = swg_search(ctx, sdb, scores, hits, (size_t)topk, &n_hits, &st);
+        if (rc == SWG_OK && cands) { /* the first record against its own entries */
+            const uint64_t off01[2] = {0, lq};
+            rc = pssm0 ? swg_search_lists_pssm(ctx, sdb, pssm0, off01, 1, cands, c_off, lsc, hits, (size_t)topk, &n_hits, &st)
+                       : swg_search_lists(ctx, sdb, qidx, off01, 1, cands, c_off, lsc, hits, (size_t)topk, &n_hits, &st);
+        } else if (rc == SWG_OK) {
+            rc = swg_search(ctx, sdb, scores, hits, (size_t)topk, &n_hits, &st);
+        }
         phase("search (first of this database)");
         if (rc != SWG_OK) {
             fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
@@ -539,6 +628,15 @@ int main(int argc, char **argv)
     int al_one_by_one = 0, al_failed = 0;
     char al_err[512] = "";
 next_query:
+    if (cands) { /* this record's entries: marks for the printing, scores by entry */
+        if (qi > 0)
+            for (uint64_t e = c_off[qi - 1]; e < c_off[qi]; e++) listed[cands[e]] = 0;
+        n_listed = 0;
+        for (uint64_t e = c_off[qi]; e < c_off[qi + 1]; e++) {
+            if (!listed[cands[e]]) listed[cands[e]] = 1, n_listed++;
+            scores[cands[e]] = lsc[e];
+        }
+    }
     if (allq) printf("Query #%lu: %s\n", (unsigned long)qi, qname);
     for (size_t i = 0, shown = 0; i < db.n; i++) {
         if (listed && !listed[i]) continue;
@@ -630,7 +728,7 @@ next_query:
         static int8_t *qx = NULL;     /* the chunk's queries as table indices */
         static uint64_t *qoff = NULL;
         if (qi >= chunk_first + chunk_n) {
-            size_t budget = ((size_t)256 << 20) / (sizeof(int32_t) * (db.n ? db.n : 1));
+            size_t budget = cands ? 1024 : ((size_t)256 << 20) / (sizeof(int32_t) * (db.n ? db.n : 1));
             if (budget < 1) budget = 1;
             if (budget > 1024) budget = 1024;
             chunk_first = qi;
@@ -643,7 +741,7 @@ next_query:
             free(mq_scores);
             free(mq_hits);
             free(mq_nhits);
-            mq_scores = (int32_t *)calloc(chunk_n * (db.n ? db.n : 1), sizeof(int32_t));
+            mq_scores = (int32_t *)calloc(cands ? 1 : chunk_n * (db.n ? db.n : 1), sizeof(int32_t)); /* (--candidates: lsc) */
             mq_hits = (swg_hit *)calloc(chunk_n * (topk ? (size_t)topk : 1), sizeof(swg_hit));
             mq_nhits = (size_t *)calloc(chunk_n, sizeof(size_t));
             if (!qx || !qoff || !mq_scores || !mq_hits || !mq_nhits) return leave(EXIT_FAILURE);
@@ -664,9 +762,16 @@ next_query:
             }
             swg_stats st;
             memset(&st, 0, sizeof st);
-            const int rc = plist ? swg_search_multi_pssm(ctx, sdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff, chunk_n, mq_scores,
-                                                         mq_hits, (size_t)topk, mq_nhits, &st)
-                                 : swg_search_multi(ctx, sdb, qx, qoff, chunk_n, mq_scores, mq_hits, (size_t)topk, mq_nhits, &st);
+            int rc;
+            if (cands) /* every record of the chunk against its own entries, in one pass */
+                rc = plist ? swg_search_lists_pssm(ctx, sdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff, chunk_n, cands,
+                                                   c_off + chunk_first, lsc, mq_hits, (size_t)topk, mq_nhits, &st)
+                           : swg_search_lists(ctx, sdb, qx, qoff, chunk_n, cands, c_off + chunk_first, lsc, mq_hits, (size_t)topk,
+                                              mq_nhits, &st);
+            else
+                rc = plist ? swg_search_multi_pssm(ctx, sdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff, chunk_n, mq_scores,
+                                                   mq_hits, (size_t)topk, mq_nhits, &st)
+                           : swg_search_multi(ctx, sdb, qx, qoff, chunk_n, mq_scores, mq_hits, (size_t)topk, mq_nhits, &st);
             if (rc != SWG_OK) {
                 fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
                 return leave(EXIT_FAILURE);
@@ -677,7 +782,7 @@ next_query:
                         st.fill_ms, st.fill_ms > 0 ? (double)st.cells / (st.fill_ms * 1e-3) / 1e9 : 0.0);
         }
         const size_t at = qi - chunk_first;
-        memcpy(scores, mq_scores + at * (db.n ? db.n : 1), db.n * sizeof(int32_t));
+        if (!cands) memcpy(scores, mq_scores + at * (db.n ? db.n : 1), db.n * sizeof(int32_t));
         n_hits = mq_nhits[at];
         memcpy(hits, mq_hits + at * (topk ? (size_t)topk : 1), n_hits * sizeof(swg_hit));
         if (align && qi >= al_first + al_n) {
@@ -745,6 +850,9 @@ next_query:
     free(didx);
     free(ids);
     free(listed);
+    free(cands);
+    free(c_off);
+    free(lsc);
     free(scores);
     free(hits);
     free(mq_al);
