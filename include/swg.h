@@ -105,7 +105,9 @@ typedef struct swg_stats {
      * forms in one search: a query long enough to score beyond 32767 runs the sequences that could reach the f16
      * cells' ceiling -- those of split_rows rows or more -- on the wide form and everything shorter on the f16
      * cells (what those flag all the same is run again on the wide form, so the scores are exact either way), 5 the same
-     * with option wide16 = 0: the long sequences on the plain int16 cells, everything from 32767 up re-scored in int32 */
+     * with option wide16 = 0: the long sequences on the plain int16 cells, everything from 32767 up re-scored in int32,
+     * 6 (swg_search_gapless only) the gapless cells: one state per column in the arithmetic of form 2 (exact below
+     * 4096, flagged from there and run again like form 2's flags, with the gaps priced out) */
     int32_t cell_form;
     int32_t split_rows;     /* cell_form 4, 5: the length from which sequences took the int16 cells; else 0 */
     int32_t fill_f16_launches; /* cell_form 4, 5: how many of fill_launches ran the f16 cells; else 0 */
@@ -287,6 +289,31 @@ int swg_search_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, cons
 int swg_search_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets,
                           size_t n_queries, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
                           swg_stats *stats);
+
+/* The gapless prefilter score: the best-scoring UNGAPPED diagonal segment of query x sequence,
+ *     H[i][j] = max(0, H[i-1][j-1] + S(q_i, d_j)),  score = max over all cells,
+ * for the context's query (index or PSSM, whichever was set last) against every sequence of a resident database: what
+ * MMseqs2-style pipelines rank the database by before they spend the affine-gap fill on the best candidates
+ * (swg_search_lists takes its top-N).  Outputs, hit order (higher score first, ties by lower original index), shards
+ * and views exactly as swg_search; scores are exact int32 for every input.
+ * The gap scores of swg_set_scoring are NOT read -- the result is the same whatever they are -- but scoring must have
+ * been set: the table is needed, and a PSSM query needs the usual call order.
+ * Where the query fits one pass of a lane-group geometry (at most 2048 columns; a forced cols_per_wave / group_lanes must
+ * still cover it), the database was not built from 16-lane batches and the options do not rule it out (f16 = 0,
+ * engine = 1, work_queue = 0), the fill runs the gapless cells: 3.5 packed instructions per column pair instead of
+ * 8.5, swg_stats.cell_form 6, path_bits 16, engine 2, work_queue 1, passes 1, n_rescored = the sequences that reached
+ * 4096 and were run again.  Everything else runs the gapped machinery with the gaps priced out (never cell_form 6):
+ * same scores.  autotune, max_waves, workgroups, batch and batch_blocks act as for swg_search; tuned geometries are
+ * kept apart from the gapped searches'.  Searches in flight on the context: SWG_ERR_STATE. */
+int swg_search_gapless(swg_ctx *ctx, const swg_db *db, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
+                       swg_stats *stats);
+/* A batch of queries, by definition the loop "set query i, swg_search_gapless" (queries, offsets, outputs and the one
+ * summed stats record as swg_search_multi / swg_search_multi_pssm take and give them).  The context's own query is left
+ * as it was. */
+int swg_search_gapless_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets, size_t n_queries,
+                             int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits, swg_stats *stats);
+int swg_search_gapless_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets, size_t n_queries,
+                                  int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits, swg_stats *stats);
 
 /* Every query of a batch against ITS OWN candidate list in one pass: what a prefilter, a PSI-BLAST iteration or a list
  * of family members per query hands to the alignment step.  Query i is queries[q_offsets[i] .. q_offsets[i+1]) as

@@ -35,7 +35,8 @@ ABI_SYMBOLS = [
     "swg_set_option", "swg_set_scoring", "swg_set_query", "swg_set_query_pssm", "swg_db_pack", "swg_db_pack_shard", "swg_db_pack_shards", "swg_db_upload", "swg_db_view",
     "swg_db_free", "swg_db_save", "swg_db_load", "swg_db_count", "swg_db_total_count", "swg_db_residues",
     "swg_db_packed_bytes", "swg_db_order", "swg_search", "swg_search_begin", "swg_search_end", "swg_search_multi",
-    "swg_search_multi_pssm", "swg_search_lists", "swg_search_lists_pssm", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_align_hits_multi",
+    "swg_search_multi_pssm", "swg_search_lists", "swg_search_lists_pssm", "swg_search_gapless", "swg_search_gapless_multi",
+    "swg_search_gapless_multi_pssm", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_align_hits_multi",
     "swg_align_hits_multi_pssm", "swg_align_ops_bound_multi", "swg_hit_key",
     "swg_key_hit", "swg_topk_merge_keys",
     "swg_group_create", "swg_group_destroy", "swg_group_size", "swg_group_last_error", "swg_group_set_option",
@@ -142,6 +143,9 @@ _sig("swg_search_begin", C.c_int, [_vp, _vp, C.c_int, C.c_size_t, C.POINTER(C.c_
 _sig("swg_search_end", C.c_int, [_vp, C.c_int, _vp, _vp, C.POINTER(C.c_size_t), C.POINTER(Stats)])
 _sig("swg_search_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
 _sig("swg_search_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
+_sig("swg_search_gapless", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(Stats)])
+_sig("swg_search_gapless_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
+_sig("swg_search_gapless_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
 _sig("swg_search_lists", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
 _sig("swg_search_lists_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
 _sig("swg_fill_batches16", C.c_int, [_vp, C.POINTER(Batch16), C.c_size_t, C.POINTER(C.c_double)])
@@ -198,6 +202,7 @@ _sig("swg_debug_sort_count", C.c_ulong, [])
 _sig("swg_debug_engine", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_int, _vp])
 _sig("swg_debug_plan", C.c_int, [_vp, C.c_size_t, C.c_int, _vp])
 _sig("swg_debug_plan_f16", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_long, _vp])
+_sig("swg_debug_plan_gapless", C.c_int, [_vp, C.c_size_t, C.c_int, _vp])
 _sig("swg_debug_split", C.c_int, [_vp, C.c_size_t, C.c_uint64, _vp])
 _sig("swg_debug_list_plan", C.c_int, [C.c_size_t, C.c_uint32, C.c_int, _vp, _vp])
 _sig("swg_debug_pair_tokens", C.c_int, [_vp, _vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
@@ -484,6 +489,13 @@ class Database:
                 "last_pass_cols") + (() if f16_pair is None else ("fma", "lds_bytes", "long_fma"))
         return dict(zip(keys, (int(v) for v in out)))
 
+    def debug_plan_gapless(self, lq, n_cu=256):
+        """Test hook: what search_gapless would plan for a query of lq residues with default options (no device needed):
+        route 1 = the gapless cells, 0 = the gapped machinery with the gaps priced out; the fill's geometry either way."""
+        out = np.zeros(6, dtype=np.int32)
+        _check(lib.swg_debug_plan_gapless(self.handle, lq, n_cu, out.ctypes.data_as(_vp)))
+        return dict(zip(("route", "K", "G", "W", "workgroups", "passes"), (int(v) for v in out)))
+
     def debug_engine(self, lq, n_cu=256, form=2):
         """Test hook: the cost model's estimates of both engines for this database and a query of lq residues (no device
         needed) -> dict(diag_us, systolic_us, systolic_K, systolic: the model picks the systolic engine)."""
@@ -597,16 +609,38 @@ class Context:
         p, pp, lq = _pssm(pssm)
         _check(lib.swg_set_query_pssm(self.handle, pp, lq), self.handle)
 
-    def search(self, db, want_scores=True, k=0):
+    def search(self, db, want_scores=True, k=0, _fn=None):
         """-> (scores int32[total] or None, hits [(score, index)], stats dict)."""
         scores = np.zeros(db.total_count, dtype=np.int32) if want_scores else None
         hits = (Hit * max(k, 1))()
         nh = C.c_size_t(0)
         st = Stats()
-        rc = lib.swg_search(self.handle, db.handle, scores.ctypes.data_as(_vp) if want_scores else None,
-                            C.cast(hits, _vp) if k else None, k, C.byref(nh), C.byref(st))
+        rc = (_fn or lib.swg_search)(self.handle, db.handle, scores.ctypes.data_as(_vp) if want_scores else None,
+                                     C.cast(hits, _vp) if k else None, k, C.byref(nh), C.byref(st))
         _check(rc, self.handle)
         return scores, [(int(hits[i].score), int(hits[i].index)) for i in range(nh.value)], st.as_dict()
+
+    def search_gapless(self, db, want_scores=True, k=0):
+        """The gapless prefilter score (best ungapped diagonal segment) of the context's query against db, shaped like
+        search; the gap scores of set_scoring are not read (swg_search_gapless)."""
+        return self.search(db, want_scores, k, _fn=lib.swg_search_gapless)
+
+    def search_gapless_multi(self, db, queries, k=0, want_scores=True):
+        """search_gapless for a list of index queries, shaped like search_multi; the context's own query is kept."""
+        nq = len(queries)
+        qoff = np.zeros(nq + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in queries])
+        qflat = np.ascontiguousarray(np.concatenate(queries) if nq else np.zeros(0), dtype=np.int8)
+        return self._multi(lib.swg_search_gapless_multi, db, qflat, qoff, k, want_scores)
+
+    def search_gapless_multi_pssm(self, db, pssms, k=0, want_scores=True):
+        """search_gapless for a list of (lq, 32) int8 PSSMs, shaped like search_multi_pssm."""
+        nq = len(pssms)
+        rows = [_pssm(p)[0] for p in pssms]
+        qoff = np.zeros(nq + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([r.shape[0] for r in rows])
+        pflat = np.ascontiguousarray(np.concatenate(rows) if nq else np.zeros((0, 32)), dtype=np.int8)
+        return self._multi(lib.swg_search_gapless_multi_pssm, db, pflat, qoff, k, want_scores)
 
     def search_multi(self, db, queries, k=0, want_scores=True):
         """Several queries (list of index arrays) against db in one pass -> (scores int32[nq, total] or None,

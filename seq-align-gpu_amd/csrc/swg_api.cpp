@@ -838,7 +838,7 @@ static bool diag_class_is_dynamic(const swg_ctx *ctx, const swg_db *db, const Sw
 // (the wide form also in the fixed-stream one).
 static int diag_class_form(const swg_ctx *ctx, const swg_db *db, const SwgDiagPlan &pl)
 {
-    if (pl.f16 && diag_class_is_dynamic(ctx, db, pl)) return 2;
+    if (pl.f16 && diag_class_is_dynamic(ctx, db, pl)) return pl.gapless ? 3 : 2;
     return pl.wide ? 1 : 0;
 }
 
@@ -1033,7 +1033,7 @@ static int prepare_diag(swg_ctx *ctx, swg_db *db, const SwgDiagWork &wk)
         const uint32_t qcol0 = (uint32_t)((pl.npass - 1) * pl.G * pl.K);
         int rc = ensure_profile_cols(ctx, diag_profile_slot(pl, c), ncols, fma ? 4 : 2,
                                      (1ull << 55) | ((uint64_t)fma << 51) | ((uint64_t)pl.K << 40) | ((uint64_t)pl.G << 32) | (uint64_t)ncols,
-                                     pl.K, kp, fma ? 2 : 4, SWG_LDS_SWIZZLE ? pl.G : 0, diag_class_form(ctx, db, pl) == 2, tail, pl.last_K,
+                                     pl.K, kp, fma ? 2 : 4, SWG_LDS_SWIZZLE ? pl.G : 0, diag_class_form(ctx, db, pl) >= 2, tail, pl.last_K,
                                      kp_last, qcol0);
         if (rc != SWG_OK) return rc;
         if (pl.f16_from > 0) { // both forms in this class: the f16 cells' profile of the same geometry (v_perm_b32 pairing)
@@ -1064,7 +1064,7 @@ static void dyn_batch_zones(const swg_ctx *ctx, const SwgPairTokens &T, SwgDiagD
     uint32_t N = (uint32_t)std::min<long>(ctx->opt_batch_blocks, 1l << 30);
     if (ctx->opt_batch_blocks <= 0) {
         const double waves_per_simd = std::min(4.0, std::max(1.0, (double)groups * G / 64.0 / (4.0 * ctx->n_cu)));
-        const double block_us = 4.0 * ((form == 2 ? 8.5 : 10.0) * K + 30.0) * 4.06 * waves_per_simd / 2.4e3;
+        const double block_us = 4.0 * ((form == 3 ? 3.5 : form == 2 ? 8.5 : 10.0) * K + 30.0) * 4.06 * waves_per_simd / 2.4e3;
         N = (uint32_t)std::max(2.0, 40.0 / block_us);
     }
     uint32_t lo = q->q_begin, hi = q->q_end; // first pair with at most N blocks
@@ -1659,9 +1659,9 @@ static int autotune_diag(swg_ctx *ctx, swg_db *db, size_t lq, int go, int ge, Sw
     SwgDiagWork *best = &tuned->wk;
     std::vector<SwgDiagWork> cands;
     const bool work_queue = ctx->opt_dynamic != 0 && db->ptok.ok;
-    if (swg_plan_diag_candidates(db, lq, ctx->n_cu, 0, 0, 0, 0, true, work_queue, &cands, 1.0, form, ctx->opt_f16_pair) <= 0) return SWG_ERR_ARG;
+    if (swg_plan_diag_candidates(db, lq, ctx->n_cu, 0, 0, 0, 0, true, work_queue, &cands, 1.0, form, form == 3 ? 1 : ctx->opt_f16_pair) <= 0) return SWG_ERR_ARG;
     for (SwgDiagWork &c : cands) // (the trials run on the cells the search will use)
-        for (int k = 0; k < c.n_classes; ++k) c.plan[k].f16 = form == 2;
+        for (int k = 0; k < c.n_classes; ++k) c.plan[k].f16 = form >= 2, c.plan[k].gapless = form == 3;
     // distinct (K, G, W, split) among the best-ranked
     std::vector<SwgDiagWork> pick;
     for (const SwgDiagWork &c : cands) {
@@ -1739,7 +1739,7 @@ static int autotune_diag(swg_ctx *ctx, swg_db *db, size_t lq, int go, int ge, Sw
                                          work_queue, &alt, 1.0, form, ctx->opt_f16_pair) <= 0)
                 continue;
             for (SwgDiagWork &c : alt)
-                for (int k = 0; k < c.n_classes; ++k) c.plan[k].f16 = form == 2;
+                for (int k = 0; k < c.n_classes; ++k) c.plan[k].f16 = form >= 2, c.plan[k].gapless = form == 3;
             const SwgDiagWork *same = nullptr;
             for (const SwgDiagWork &c : alt)
                 if (c.n_classes == 2 && c.plan[1].K == base.plan[1].K && c.plan[1].G == base.plan[1].G) {
@@ -1762,7 +1762,7 @@ static int autotune_diag(swg_ctx *ctx, swg_db *db, size_t lq, int go, int ge, Sw
     // third stage: the systolic engine (less bookkeeping per row, coarse work units); it has not won
     // a measured case since the diagonal engine got its work queue and is only tried where a trial
     // is cheap
-    for (int v = 0; v < swg_num_variants(16) && tuned->ms < 100.0; ++v) {
+    for (int v = 0; v < swg_num_variants(16) && tuned->ms < 100.0 && form != 3; ++v) { // (the gapless cells exist on lane groups only)
         SwgSystolicPlan pl;
         int rc = make_plan(ctx, 16, db->n_bins, swg_variant_info(16, v).K, &pl);
         if (rc != SWG_OK) continue;
@@ -1876,31 +1876,59 @@ static int plan_search(swg_ctx *ctx, swg_db *db, bool allow_autotune, SwgSearchP
     const size_t n_slots = (size_t)n_bins * SWG_BIN;
     P.epoch = ctx->epoch;
 
-    // which arithmetic: the packed int16 form needs non-positive gap scores
-    const int go = P.go = ctx->gap_open + ctx->gap_extend, ge = P.ge = ctx->gap_extend;
-    const bool fast_ok = P.fast_ok = ctx->gap_open <= 0 && ctx->gap_extend <= 0 && -go <= SWG_I16_CEILING;
-    const int bits = P.bits = fast_ok && ctx->opt_force_bits != 32 ? 16 : 32;
-    if (ctx->opt_force_bits == 16 && !fast_ok)
-        return swg_set_ctx_error(ctx, SWG_ERR_ARG,
-                                 "force_bits=16 needs gap_open <= 0 and gap_extend <= 0");
-
     // How high can a score get (swg_score_bound)?  Below the int16 ceiling nothing can saturate; below the wide form's
     // (values biased by -32768, same instruction count) that form is exact and nothing needs the int32 re-score.
     const uint64_t longest = (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK;
     const SwgScoreBound sb = ctx->query_pssm ? swg_score_bound(ctx->pssm.data(), nullptr, lq, longest)
                                              : swg_score_bound(&ctx->sub[0][0], ctx->query.data(), lq, longest);
     const uint64_t score_bound = P.score_bound = sb.bound, qbound = P.qbound = sb.qbound;
+    // A gapless search (swg_search_gapless) never reads the context's gap scores: every level that has gap operands runs
+    // with the gaps priced out.  A path with a gap can beat the best ungapped segment only if the segments on both sides
+    // of the gap each score more than the gap costs.  The packed int16 cells stick at 32767, so with a magnitude of 32767
+    // -- their saturating ceiling -- no such segment exists below the flag level: they are exact whatever the query.
+    // The wide form and the int32 cells hold larger values: 32767 serves them while no score can pass 2 x 32767 (the
+    // two segments use different query columns and different rows, so their sum is within score_bound); beyond that the
+    // wide form is not used and the int32 levels take a magnitude above the score bound itself.
+    const bool gapless = ctx->gapless;
+    const bool gl_small = score_bound <= 2ull * SWG_I16_CEILING;
+    const int gl_gap32 = gl_small ? -SWG_I16_CEILING : -(int)std::min<uint64_t>(score_bound + 1, 1u << 30);
+    // which arithmetic: the packed int16 form needs non-positive gap scores
+    const bool gl_bits32 = gapless && ctx->opt_force_bits == 32;
+    const int go = P.go = gapless ? (gl_bits32 ? gl_gap32 : -SWG_I16_CEILING) : ctx->gap_open + ctx->gap_extend;
+    const int ge = P.ge = gapless ? go : ctx->gap_extend;
+    P.go32 = gapless ? gl_gap32 : go;
+    P.ge32 = gapless ? gl_gap32 : ge;
+    const bool fast_ok = P.fast_ok = gapless || (ctx->gap_open <= 0 && ctx->gap_extend <= 0 && -go <= SWG_I16_CEILING);
+    const int bits = P.bits = fast_ok && ctx->opt_force_bits != 32 ? 16 : 32;
+    if (ctx->opt_force_bits == 16 && !fast_ok)
+        return swg_set_ctx_error(ctx, SWG_ERR_ARG,
+                                 "force_bits=16 needs gap_open <= 0 and gap_extend <= 0");
+
     const bool f16_gaps = ctx->opt_f16 != 0 && swg_f16_gaps_ok(go, ge); // the f16 cells are allowed and hold the gap magnitudes
-    P.wide = bits == 16 && score_bound >= SWG_I16_CEILING && ctx->opt_engine != 1 && ctx->opt_wide != 0;
+    const bool wide_ok = ctx->opt_wide != 0 && (!gapless || gl_small);
+    P.wide = bits == 16 && score_bound >= SWG_I16_CEILING && ctx->opt_engine != 1 && wide_ok;
+    // Gapless, route 1: the gapless cells (CellsGapless, form 3) where the query fits one pass of a geometry the table
+    // offers (a forced cols_per_wave / group_lanes included), on the work queue, unless the options rule the f16 cells or
+    // the lane groups out or the database came from 16-lane batches.  Everything else is route 0: the machinery below
+    // as it stands, with the gap magnitudes above.
+    bool gl_route1 = gapless && bits == 16 && ctx->opt_engine != 1 && ctx->opt_dynamic != 0 && ctx->opt_f16 != 0 && !db->tokens_only &&
+                     lq <= 64u * 32u;
+    if (gl_route1) {
+        int rc1 = ensure_pair_tokens(ctx, db);
+        if (rc1 != SWG_OK) return rc1;
+        SwgDiagWork probe1;
+        gl_route1 = db->ptok.ok && swg_plan_diag_work(db, lq, ctx->n_cu, ctx->opt_cols, ctx->opt_group, ctx->opt_max_waves, ctx->opt_long_split,
+                                                      ctx->opt_workgroups == 0, true, &probe1, 1.0, 3, 1) > 0;
+    }
     // The packed-f16 cells (three-operand maxima, 8.5 instead of 10 instructions per column pair) are exact
     // while scores stay below 4096; a sequence that reaches it is flagged and re-scored in int32.  They are the
     // first step whenever the gap magnitudes are f16 integers and the query is not so long that scores are
     // expected far beyond (where the wide form is exact on its own) -- unless this database has shown, for this
     // query, that a good part of its rows gets flagged ("f16" option: 0 never, 2 regardless of both).
-    const bool want_f16 = bits == 16 && ctx->opt_engine != 1 && ctx->opt_dynamic != 0 && f16_gaps &&
-                          (ctx->opt_f16 == 2 || (score_bound < SWG_I16_CEILING && db->f16_veto_epoch != ctx->epoch));
+    const bool want_f16 = gl_route1 || (bits == 16 && ctx->opt_engine != 1 && ctx->opt_dynamic != 0 && f16_gaps &&
+                                        (ctx->opt_f16 == 2 || (score_bound < SWG_I16_CEILING && db->f16_veto_epoch != ctx->epoch)));
     if (want_f16) P.wide = false; // (only with f16 = 2: the f16 cells first, whatever the score bound)
-    const int plan_form = want_f16 ? 2 : 0;
+    const int plan_form = gl_route1 ? 3 : want_f16 ? 2 : 0;
 
     // (the systolic plan: only the systolic engine needs it to exist -- a cols_per_wave meant for the
     // diagonal engine has no systolic instantiation, and with engine != 1 both widths run on lane groups)
@@ -1914,7 +1942,8 @@ static int plan_search(swg_ctx *ctx, swg_db *db, bool allow_autotune, SwgSearchP
         const bool free_geometry = ctx->opt_cols == 0 && ctx->opt_group == 0 && ctx->opt_max_waves == 0 &&
                                    ctx->opt_long_split == 0 && ctx->opt_workgroups == 0;
         // (a geometry is tuned for the cells it ran on, and the pairings it was allowed)
-        const uint64_t tuned_key = (uint64_t)lq | ((uint64_t)plan_form << 40) | ((uint64_t)ctx->opt_f16_pair << 44);
+        // (and a gapless search keeps its picks apart from the gapped searches')
+        const uint64_t tuned_key = (uint64_t)lq | ((uint64_t)plan_form << 40) | ((uint64_t)ctx->opt_f16_pair << 44) | ((uint64_t)gapless << 48);
         auto it = free_geometry ? db->tuned.find(tuned_key) : db->tuned.end();
         if (it == db->tuned.end() && free_geometry && allow_autotune && ctx->opt_engine == 0 &&
             db->n_local >= 4096 && db->n_local <= (4u << 20)) {
@@ -1935,10 +1964,10 @@ static int plan_search(swg_ctx *ctx, swg_db *db, bool allow_autotune, SwgSearchP
         if (!P.use_diag && !tuned_systolic)
             P.use_diag = swg_plan_diag_work(db, lq, ctx->n_cu, ctx->opt_cols, ctx->opt_group, ctx->opt_max_waves,
                                             ctx->opt_long_split, ctx->opt_workgroups == 0,
-                                            ctx->opt_dynamic != 0 && db->ptok.ok, &wk, 1.0, plan_form, ctx->opt_f16_pair) > 0;
+                                            ctx->opt_dynamic != 0 && db->ptok.ok, &wk, 1.0, plan_form, gl_route1 ? 1 : ctx->opt_f16_pair) > 0;
         // the cost model's own comparison of the engines, where nothing was measured and nothing forced
         int sys_K = 0;
-        if (P.use_diag && !tuned_systolic && free_geometry && !P.wide && it == db->tuned.end() &&
+        if (P.use_diag && !tuned_systolic && free_geometry && !P.wide && it == db->tuned.end() && !gl_route1 &&
             systolic_beats_lane_groups(ctx, db, lq, wk.plan[0], plan_form, score_bound, 1, &sys_K)) {
             if (make_plan(ctx, 16, n_bins, sys_K, &P.main_pl) == SWG_OK) { // (a failed make_plan leaves the plan as it was)
                 P.use_diag = false;
@@ -1991,7 +2020,7 @@ static int plan_search(swg_ctx *ctx, swg_db *db, bool allow_autotune, SwgSearchP
     // 730 rows with BLOSUM62) take the f16 cells, 8.5 instructions per column pair instead of 10, in launches of
     // their own after the long ones' (launch_diag).  The threshold is an expectation, not a bound: whatever the f16
     // cells flag all the same is run again on the wide form like any other flagged pair, so results do not depend on it.
-    if (!P.use_f16 && bits == 16 && score_bound >= SWG_I16_CEILING && P.use_diag && ctx->opt_f16 == 1 && db->f16_veto_epoch != ctx->epoch &&
+    if (!gapless && !P.use_f16 && bits == 16 && score_bound >= SWG_I16_CEILING && P.use_diag && ctx->opt_f16 == 1 && db->f16_veto_epoch != ctx->epoch &&
         swg_f16_gaps_ok(go, ge) && wk.n_classes == 1 && diag_class_is_dynamic(ctx, db, wk.plan[0]) && !db->tokens_only && qbound > 0) {
         const uint32_t rows = swg_split_rows(lq, qbound);
         swg_db_split_at(db, rows); // (per database and length: a binary search and one pass over the lengths)
@@ -2019,10 +2048,13 @@ static int plan_search(swg_ctx *ctx, swg_db *db, bool allow_autotune, SwgSearchP
     }
     // what the f16 cells flag is run again on int16 cells (the wide form if scores may pass 32767); only what
     // saturates those too needs the int32 kernel
-    P.rerun_wide = (P.use_f16 && score_bound >= SWG_I16_CEILING && ctx->opt_wide != 0) || (P.split_at != 0u && P.wide);
+    P.rerun_wide = (P.use_f16 && score_bound >= SWG_I16_CEILING && wide_ok) || (P.split_at != 0u && P.wide);
     const int32_t rerun_ceiling = P.rerun_wide ? SWG_WIDE_CEILING : SWG_I16_CEILING;
     if (P.use_f16 && score_bound >= (uint64_t)rerun_ceiling && !P.q32_ok) P.use_f16 = false;
     for (int c = 0; c < wk.n_classes; ++c) wk.plan[c].f16 = P.use_f16 ? 1 : 0;
+    P.gapless = gapless;
+    P.gapless_cells = gl_route1 && P.use_f16; // (route 1 stands: the gapless cells fill, their flags take the list re-run)
+    for (int c = 0; c < wk.n_classes; ++c) wk.plan[c].gapless = P.gapless_cells ? 1 : 0;
     P.ceiling = P.use_f16 ? SWG_F16_CEILING : P.wide ? SWG_WIDE_CEILING : SWG_I16_CEILING;
     P.may_saturate = bits == 16 && (score_bound >= (uint64_t)P.ceiling || P.split_at != 0u);
     // (the int32 level follows the last 16-bit one: the fill's own cells, or the re-run's when f16 cells came first)
@@ -2147,8 +2179,8 @@ static int enqueue_rescore(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P, Swg
         p.queue = db->d_counters + 2;
         p.list = seq_list;
         p.list_count = db->d_counters + 1;
-        p.go = P.go;
-        p.ge = P.ge;
+        p.go = P.go32; // (the first level's gap scores, except in a gapless search: see plan_search)
+        p.ge = P.ge32;
         SwgDiagWork wkl;
         // The work-queue re-score reads the count on the device and leaves at once when it is zero, so it is queued
         // behind every fill that may flag something and the host never waits for the count in the middle of a
@@ -2162,7 +2194,7 @@ static int enqueue_rescore(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P, Swg
             HIP_TRY(ctx, hipMemsetAsync(db->d_counters + SWG_QUEUE_WORD(0), 0,
                                         (size_t)(SWG_COUNTER_BYTES - SWG_QUEUE_WORD(0) * 4u), s));
             bool two = false;
-            rc = launch_q32(ctx, db, wkl, P.go, P.ge, seq_list, db->d_counters + 1, std::max<uint32_t>(2u * guess, 4096u),
+            rc = launch_q32(ctx, db, wkl, P.go32, P.ge32, seq_list, db->d_counters + 1, std::max<uint32_t>(2u * guess, 4096u),
                             db->d_counters + SWG_QUEUE_WORD(0), &two, false);
             if (rc != SWG_OK) return rc;
         } else if (P.use_diag32) {
@@ -2335,6 +2367,7 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
     st.n_rescored = some_f16 ? h_counters[16] : h_counters[1];
     st.path_bits = P.bits;
     st.cell_form = P.use_diag ? diag_class_form(ctx, db, dpl) : P.main_pl.f16 ? 2 : 0;
+    if (st.cell_form == 3) st.cell_form = 6; // (the gapless cells: kernel form 3, reported as 6 -- 3 .. 5 are taken, see swg.h)
     if (P.use_diag && dpl.f16_from != 0u) {
         st.cell_form = dpl.wide ? 4 : 5;
         st.n_rescored = (uint64_t)h_counters[16] + h_counters[1]; // flagged by the f16 cells + saturated on the wide form
@@ -2351,7 +2384,7 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
         // a pair row is two residues) cost more in re-runs than they save: the cells save 15 % of the fill, the list
         // re-run of a share f of the rows costs f x 10 / 8.5 at about half the fill's efficiency.  Measured on config
         // 4's share with 4 % of the pair rows flagged: f16 + re-run 191 ms, int16 cells alone 200.
-        if (some_f16 && (uint64_t)h_counters[6] * 16ull * 2ull * 16ull > db->residues + 2ull * db->n_local) db->f16_veto_epoch = P.epoch;
+        if (some_f16 && !P.gapless && (uint64_t)h_counters[6] * 16ull * 2ull * 16ull > db->residues + 2ull * db->n_local) db->f16_veto_epoch = P.epoch;
     }
     st.classes_overlapped = -1;
     if (P.use_diag && wk.n_classes == 2 && wk.plan[0].npass == 1 && wk.plan[1].npass == 1) {
@@ -3006,6 +3039,64 @@ extern "C" int swg_search_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_
     });
 }
 
+// ---------------------------------------------------------------------------
+// the gapless prefilter score
+// ---------------------------------------------------------------------------
+// swg_search_gapless is swg_search with another recurrence, H[i][j] = max(0, H[i-1][j-1] + S(q_i, d_j)): the context's
+// query, the database, the outputs and the whole stream of one search (fill, re-run of what the f16 cells flagged, int32
+// level, top-K, read-out) are the gapped search's.  What differs is decided in plan_search under ctx->gapless: the cells of
+// the fill (route 1: CellsGapless on the work queue) and the gap magnitudes of every level that has gap operands (priced
+// out; the context's own are not read).  The batch calls are the loop "set query i, search" over that path.
+namespace {
+struct GaplessMode { // ctx->gapless for the duration of a call
+    swg_ctx *ctx;
+    explicit GaplessMode(swg_ctx *c) : ctx(c) { ctx->gapless = true; }
+    ~GaplessMode() { ctx->gapless = false; }
+};
+} // namespace
+
+extern "C" int swg_search_gapless(swg_ctx *ctx, const swg_db *db, int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits,
+                                  swg_stats *stats)
+{
+    if (!ctx || !db) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_search_gapless: NULL argument");
+    for (const SwgSlot &sl : ctx->slots)
+        if (sl.busy) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search_gapless: searches are in flight on this context");
+    const GaplessMode mode(ctx);
+    return search_now(ctx, const_cast<swg_db *>(db), ctx->opt_autotune != 0, scores_out, topk_out, k, n_hits, stats);
+}
+
+static int search_gapless_multi_impl(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, int32_t *scores_out, swg_hit *topk_out, size_t k,
+                                     size_t *n_hits, swg_stats *stats)
+{
+    swg_stats st;
+    memset(&st, 0, sizeof st);
+    int rc = validate_batch(ctx, db, mq, topk_out, k, &st);
+    if (rc != SWG_OK) return rc;
+    if (stats) *stats = st;
+    if (mq.n == 0) return SWG_OK;
+    const GaplessMode mode(ctx);
+    rc = search_batch_one_by_one(ctx, db, mq, scores_out, topk_out, k, n_hits, &st);
+    if (stats) *stats = st;
+    return rc;
+}
+
+extern "C" int swg_search_gapless_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets, size_t n_queries,
+                                        int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits, swg_stats *stats)
+{
+    return ctx_guarded(ctx, "swg_search_gapless_multi", [&]() -> int {
+        return search_gapless_multi_impl(ctx, const_cast<swg_db *>(db), MultiQueries{queries, q_offsets, n_queries, false, "swg_search_gapless_multi"},
+                                         scores_out, topk_out, k, n_hits, stats);
+    });
+}
+
+extern "C" int swg_search_gapless_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets, size_t n_queries,
+                                             int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits, swg_stats *stats)
+{
+    return ctx_guarded(ctx, "swg_search_gapless_multi_pssm", [&]() -> int {
+        return search_gapless_multi_impl(ctx, const_cast<swg_db *>(db), MultiQueries{pssms, q_offsets, n_queries, true, "swg_search_gapless_multi_pssm"},
+                                         scores_out, topk_out, k, n_hits, stats);
+    });
+}
 
 // ---------------------------------------------------------------------------
 // every query of a batch against its own candidate list in one pass

@@ -68,7 +68,8 @@ uint64_t swg_db_pairs_longer_than(const swg_db *db, uint64_t rows)
 // (the packed-f16 cells, form 2, take 8.5 per column pair, 7.5 with the fma pairing: DESIGN 4.1)
 static double instr_per_row(int K, int G, int form = 0, bool fma = false)
 {
-    return (form == 2 ? (fma ? 7.5 : 8.5) : 10.0) * K + (G == 32 ? 34.0 : 30.0);
+    // (the gapless cells, form 3: 3.5 per column pair)
+    return (form == 3 ? 3.5 : form == 2 ? (fma ? 7.5 : 8.5) : 10.0) * K + (G == 32 ? 34.0 : 30.0);
 }
 
 // The f16 cells' pairings a geometry may take (f16_pair: 0 both, ranked by the model; 1 v_perm_b32 only; 2 the fma
@@ -178,6 +179,7 @@ static int plan_candidates(const swg_db *db, size_t lq, int n_cu, long opt_cols,
             const size_t cols = (size_t)G * info.K;
             if (swg_diag_slice_bytes(info.K, G) > SWG_LDS_PER_CU) continue;
             const int npass = (int)((lq + cols - 1) / cols);
+            if (form == 3 && npass > 1) continue; // the gapless cells have no edges: one pass or not at all
             const int NG = 64 / G;
             // with the work queue (several passes: one launch per pass) there are no fixed shares, the
             // chain that matters is the longest pair at the rate of a wavefront that gets its fair
@@ -704,6 +706,26 @@ static int debug_plan(const swg_db *db, size_t lq, int n_cu, int form, long f16_
 }
 
 extern "C" int swg_debug_plan(const swg_db *db, size_t lq, int n_cu, int32_t *out) { return debug_plan(db, lq, n_cu, 0, 0, out); }
+
+// Test hook: what a gapless search (swg_search_gapless) of a packed database would plan for a query of lq columns with
+// default options, without a device.  out[0..4] = route (1: the gapless cells; 0: the gapped machinery with the gaps
+// priced out), K, lanes per group, wavefronts per workgroup, workgroups (route 0: the int16 planner's first choice).
+extern "C" int swg_debug_plan_gapless(const swg_db *db, size_t lq, int n_cu, int32_t *out)
+{
+    if (!db || !out || lq == 0 || n_cu <= 0) return SWG_ERR_ARG;
+    SwgDiagWork wk;
+    int route = 0;
+    try {
+        route = !db->tokens_only && lq <= 64u * 32u && swg_plan_diag_work(db, lq, n_cu, 0, 0, 0, 0, true, true, &wk, 1.0, 3, 1) > 0 ? 1 : 0;
+        if (!route && swg_plan_diag_work(db, lq, n_cu, 0, 0, 0, 0, true, true, &wk, 1.0, 0, 0) <= 0) return SWG_ERR_ARG;
+    } catch (const std::exception &) {
+        return SWG_ERR_NOMEM;
+    }
+    const SwgDiagPlan &b = wk.plan[0];
+    const int32_t v[6] = {route, b.K, b.G, b.W, b.workgroups, b.npass};
+    memcpy(out, v, sizeof v);
+    return SWG_OK;
+}
 
 extern "C" int swg_debug_plan_f16(const swg_db *db, size_t lq, int n_cu, long f16_pair, int32_t *out)
 {

@@ -88,6 +88,7 @@ struct SwgDiagPlan {
     // f16 cells (form 2): the fma pairing (CellsDiag FMA: (score, 1.0) profile of twice the size, 7.5 instructions per
     // column pair) instead of v_perm_b32 (8.5); ignored on the other cells
     int fma = 0;
+    int gapless = 0; // f16 != 0: the gapless cells (CellsGapless, kernel form 3) instead of the three-state f16 cells
     uint32_t n_streams = 0;
     size_t lds_bytes = 0;
     double est_ms = 0.0;
@@ -234,6 +235,9 @@ struct SwgSearchPlan {
     int bits = 0;          // 16 / 32; 0: nothing queued (an empty database)
     bool fast_ok = false;  // the gap scores fit the packed forms (non-positive, magnitude within int16)
     int go = 0, ge = 0;    // gap_open + gap_extend, gap_extend
+    int go32 = 0, ge32 = 0; // the same for the int32 level behind the 16-bit ones (they differ in a gapless search only)
+    bool gapless = false;       // a gapless search (swg_search_gapless): go / ge are priced out, not the context's
+    bool gapless_cells = false; // ... on the gapless cells (route 1); else the gapped machinery with those gaps (route 0)
     uint64_t score_bound = ~0ull, qbound = 0; // swg_score_bound of this query against this database
     uint64_t epoch = 0;    // the context's (query, scoring) epoch the plan was made under
     // the first level's cells, and where their flags go
@@ -345,6 +349,7 @@ struct swg_ctx {
     // query_pssm is set it is the query (and `query` is empty); swg_set_query clears it again.
     std::vector<int8_t> pssm;
     bool query_pssm = false;
+    bool gapless = false; // set for the duration of a swg_search_gapless call: plan_search prices the gaps out
     // query length of either form: what every lq of the planner, the profiles and the traceback is
     size_t query_len() const { return query_pssm ? pssm.size() / 32 : query.size(); }
     // options
@@ -426,6 +431,8 @@ extern "C" int swg_debug_list_jobs(const swg_db *db, const uint32_t *cand, const
 // test hook: the next visit of the named site throws std::bad_alloc (swg_api.cpp); 0 disarms
 extern "C" void swg_debug_fail_alloc(int site);
 extern "C" int swg_debug_plan(const swg_db *db, size_t lq, int n_cu, int32_t *out);
+// a gapless search's plan: out[0..5] = route (1 gapless cells, 0 gapped machinery), K, G, W, workgroups, passes
+extern "C" int swg_debug_plan_gapless(const swg_db *db, size_t lq, int n_cu, int32_t *out);
 // the same for the packed-f16 cells (option f16_pair: 0 auto, 1 perm, 2 fma), out[0..15]: swg_debug_plan's 13 values, then
 // the bulk's pairing (1 fma, 0 v_perm_b32), its workgroup's LDS bytes, the long class's pairing
 extern "C" int swg_debug_plan_f16(const swg_db *db, size_t lq, int n_cu, long f16_pair, int32_t *out);

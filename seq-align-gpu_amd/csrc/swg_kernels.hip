@@ -63,6 +63,7 @@
 //      launchers that only choose among other parts' kernels
 //   1  swg_diag_dyn_kernel on the int16 and wide cells     2  swg_diag_dyn_kernel on the f16 cells
 //   3  swg_diag32q_kernel (reduced and exact cells)        4  swg_diag_qq_kernel
+//   5  swg_diag_dyn_kernel on the gapless cells (FORM 3)
 // Undefined: everything in one unit (tools/probe_isa.sh with SWG_PROBE_VARIANT).
 #ifdef SWG_PART
 #define SWG_HAS_PART(n) (SWG_PART == (n))
@@ -724,6 +725,85 @@ template <int K, int FORM = 0, bool FMA = false> struct CellsDiag {
     }
 };
 
+// ---------------------------------------------------------------------------
+// Gapless cells (FORM 3 of swg_diag_dyn_kernel): the prefilter score, the best ungapped diagonal segment
+//     H[i][j] = max(0, H[i-1][j-1] + S(q_i, d_j)),  score = max H
+// in the arithmetic of FORM 2 (packed f16, a score v held as v - 2048, exact for 0 .. 4095, a pair whose best reaches
+// +2048.0 is flagged and run again) with the interface of CellsDiag.  State per column is M[k] alone: no G, no A, no B
+// and no eb edge between lanes (the row returns score 0 in its place).  Per column pair: one v_perm_b32 and one
+// v_pk_add_f16 per column, one maximum against the floor per column, one three-operand maximum for the running best of
+// both = 7 instructions per 2 columns of 2 sequences, "3.5 per column pair" where the gapped f16 cells take 8.5.
+// The columns are worked from the strip's last to its first, each M[k] written in place from M[k-1] of the row above: no
+// copies, and the edge the next lane waits for comes first.
+// Reset and padding rows need no gap operand: the padding residue's profile row is -65504 in every column, so one such
+// row floors every M below 63456 to score 0 (the token stream has two between pairs, and the rows that pad the shorter
+// sequence of a pair floor its half on every row; -65504 + M is never above M, so a padding row cannot raise best).
+// Only -inf + finite and +inf + finite arise, never a NaN; a lane whose best ran to 32768 or beyond is wiped explicitly,
+// as in FORM 2 (best_is_huge, p.f16_wipe).
+template <int K> struct CellsGapless {
+    static constexpr uint32_t ZERO = SWG_F16_ZERO;
+    static constexpr int CH = 4;
+    static constexpr int KP = (K + CH - 1) / CH * CH;
+    static constexpr int CHUNK = 32 * CH * 2;
+    static constexpr int SLICE = KP / CH * CHUNK;
+    uint32_t M[K];
+    uint32_t best, mdl;
+
+    DEVINL void reset()
+    {
+#pragma unroll
+        for (int k = 0; k < K; ++k) M[k] = ZERO;
+        best = ZERO;
+        mdl = ZERO;
+    }
+
+    DEVINL void wipe(uint32_t fm)
+    {
+#pragma unroll
+        for (int k = 0; k < K; ++k) M[k] = (M[k] & ~fm) | (ZERO & fm);
+        best = (best & ~fm) | (ZERO & fm);
+        mdl = (mdl & ~fm) | (ZERO & fm);
+    }
+
+    DEVINL uint32_t best_is_huge() const
+    {
+        return 0u - (uint32_t)((((best & 0x78007800u) + 0x08000800u) & 0x80008000u) != 0u);
+    }
+
+    // ax / ay, em, zero as CellsDiag::row; eb, go and ge are not read.  Returns (M of the strip's last column, score 0).
+    template <bool FENCED = false>
+    DEVINL uint2 row(uint32_t ax, uint32_t ay, uint32_t em, uint32_t, uint32_t, uint32_t, uint32_t zero)
+    {
+        constexpr int NCH = KP / CH;
+        uint2 nx = lds_read_u2(ax + (NCH - 1) * CHUNK), ny = lds_read_u2(ay + (NCH - 1) * CHUNK);
+#pragma unroll
+        for (int c = NCH - 1; c >= 0; --c) {
+            const uint2 wx = nx, wy = ny;
+            if (c > 0) {
+                nx = lds_read_u2(ax + (c - 1) * CHUNK);
+                ny = lds_read_u2(ay + (c - 1) * CHUNK);
+            }
+            uint32_t mhi = 0u;
+#pragma unroll
+            for (int u = CH - 1; u >= 0; --u) {
+                const int k = CH * c + u;
+                if (k >= K) continue; // unused tail of the last chunk
+                const uint32_t w = u < 2 ? __builtin_amdgcn_perm(wy.x, wx.x, (u & 1) ? 0x07060302u : 0x05040100u)
+                                         : __builtin_amdgcn_perm(wy.y, wx.y, (u & 1) ? 0x07060302u : 0x05040100u);
+                const uint32_t m = pk_max3_f16(pk_add_f16(k > 0 ? M[k - 1] : mdl, w), zero, zero);
+                M[k] = m;
+                // the running best takes two columns at a time (the last one of an odd K alone)
+                if (!(u & 1) && k == K - 1) best = pk_max3_f16(best, m, m);
+                else if (!(u & 1)) best = pk_max3_f16(best, mhi, m);
+                mhi = m;
+            }
+            if (FENCED && c > 0) __builtin_amdgcn_sched_barrier(0);
+        }
+        mdl = em;
+        return make_uint2(M[K - 1], zero);
+    }
+};
+
 // The LDS maximum of the f16 bests is taken on order-preserving 16-bit keys: a non-negative value's bits with the
 // sign bit set, a negative value's bits complemented (so 0 = below everything: an untouched slot).
 DEVINL uint32_t f16_key(uint32_t bits) { return (bits & 0x8000u) ? (~bits & 0xFFFFu) : (bits | 0x8000u); }
@@ -1016,15 +1096,18 @@ DEVINL uint32_t quad_bcast(uint32_t x, int r)
 // FORM: the cells (see CellsDiag): 0 packed int16, 1 wide (scores to 65535; needs EDGES: a query that can pass
 // 32767 is long), 2 packed f16 with three-operand maxima (scores below 4096, anything above is flagged).
 // FMA: FORM 2 with the (score, 1.0) profile and the v_pk_fma_f16 pairing (see CellsDiag).
+// FORM 3: the gapless cells (CellsGapless) in the arithmetic of FORM 2: single pass, v_perm_b32 pairing, p.go / p.ge not
+// read -- the padding profile row clears the state on reset rows, the best is reset and a huge lane wiped as in FORM 2.
 // LISTS: every query of a batch against its own candidate list (swg_search_lists): a 1-D grid whose workgroups are dealt
 // to the rows by a host-built table, each row with its own range of pairs (see SwgDiagDynParams::wg_rows).  Only the
 // set-up and the queue's event code know of it; the flag is a constant that folds away everywhere else.
 template <int K, int MAXW, bool EDGES = false, int FORM = 0, bool FMA = false, bool LISTS = false>
 __global__ __launch_bounds__(MAXW * 64) void swg_diag_dyn_kernel(const SwgDiagDynParams p)
 {
-    constexpr bool WIDE = FORM == 1, F16 = FORM == 2;
-    static_assert(!LISTS || (!EDGES && !FMA && FORM != 1), "lists: single pass, int16 or f16 cells with the perm pairing");
-    using Cells = CellsDiag<K, FORM, FMA>;
+    constexpr bool WIDE = FORM == 1, GAPLESS = FORM == 3, F16 = FORM == 2 || GAPLESS;
+    static_assert(!LISTS || (!EDGES && !FMA && FORM != 1 && !GAPLESS), "lists: single pass, int16 or f16 cells with the perm pairing");
+    static_assert(!GAPLESS || (!EDGES && !FMA), "gapless: single pass, perm pairing");
+    using Cells = typename std::conditional<GAPLESS, CellsGapless<K>, CellsDiag<K, GAPLESS ? 2 : FORM, FMA>>::type;
     static_assert(EDGES || !WIDE, "the wide form is instantiated with edges only");
     extern __shared__ __attribute__((aligned(256))) uint8_t smem[]; // query profile, then the group records
     const int lane = threadIdx.x & 63;
@@ -1392,8 +1475,10 @@ __global__ __launch_bounds__(MAXW * 64) void swg_diag_dyn_kernel(const SwgDiagDy
                         if (__builtin_amdgcn_ballot_w64(fi != 0u) != 0ull) cells.wipe(fi);
                     }
                     cells.best = (cells.best & ~fm) | (Z & fm);
-                    go_v = (go_v & ~fm) | (SWG_F16_BIG & fm);
-                    ge_v = (ge_v & ~fm) | (SWG_F16_BIG & fm);
+                    if (!GAPLESS) { // (gapless: the reset row's own profile row, -65504, floors every M)
+                        go_v = (go_v & ~fm) | (SWG_F16_BIG & fm);
+                        ge_v = (ge_v & ~fm) | (SWG_F16_BIG & fm);
+                    }
                 } else {
                     cells.best &= ~fm;
                     go_v |= fm;
@@ -1413,7 +1498,7 @@ __global__ __launch_bounds__(MAXW * 64) void swg_diag_dyn_kernel(const SwgDiagDy
             const uint2 e = cells.template row<(SWG_DYN_FENCE_ABOVE < K)>(prof_addr<0>(base, tok), prof_addr<1>(base, tok),
                                                                            em, eb, go_v, ge_v, zero_v);
             if (special) {
-                if (!WIDE) {
+                if (!WIDE && !GAPLESS) {
                     go_v = p.go;
                     ge_v = p.ge;
                 }
@@ -2715,6 +2800,8 @@ SwgDynKernel swg_dyn_kernel_f16(int variant, int which);
 // LISTS: form 0 from part 1, form 2 from part 2
 SwgDynKernel swg_dyn_kernel_lists_i16(int variant);
 SwgDynKernel swg_dyn_kernel_lists_f16(int variant);
+// the gapless cells (form 3, single pass), from part 5
+SwgDynKernel swg_dyn_kernel_gapless(int variant);
 
 #if SWG_HAS_PART(1)
 SwgDynKernel swg_dyn_kernel_lists_i16(int variant)
@@ -2748,6 +2835,16 @@ SwgDynKernel swg_dyn_kernel_f16(int variant, int which)
     static const SwgDynKernel t[][4] = {SWG_DIAG_VARIANTS(SWG_ROW)};
 #undef SWG_ROW
     return t[variant][which];
+}
+#endif
+
+#if SWG_HAS_PART(5)
+SwgDynKernel swg_dyn_kernel_gapless(int variant)
+{
+#define SWG_ROW(K, W) swg_diag_dyn_kernel<K, W, false, 3>,
+    static const SwgDynKernel t[] = {SWG_DIAG_VARIANTS(SWG_ROW)};
+#undef SWG_ROW
+    return t[variant];
 }
 #endif
 
@@ -2927,8 +3024,8 @@ hipError_t swg_launch_diag_dyn(int variant, bool edges, int form, int W, int wor
         (p.G != 16 && p.G != 32 && p.G != 64) || p.q_end < p.q_begin)
         return hipErrorInvalidValue;
     const size_t lds = swg_diag_dyn_lds_bytes(v[variant].K, (int)p.G, W, fma);
-    if (form < 0 || form > 2 || (form == 1 && !edges) || (fma && form != 2) || lds > 160 * 1024) return hipErrorInvalidValue;
-    auto k = form == 2 ? swg_dyn_kernel_f16(variant, (fma ? 2 : 0) + (edges ? 1 : 0)) : swg_dyn_kernel_i16(variant, form == 1 ? 2 : edges ? 1 : 0);
+    if (form < 0 || form > 3 || (form == 1 && !edges) || (fma && form != 2) || (form == 3 && edges) || lds > 160 * 1024) return hipErrorInvalidValue;
+    auto k = form == 3 ? swg_dyn_kernel_gapless(variant) : form == 2 ? swg_dyn_kernel_f16(variant, (fma ? 2 : 0) + (edges ? 1 : 0)) : swg_dyn_kernel_i16(variant, form == 1 ? 2 : edges ? 1 : 0);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

@@ -19,7 +19,9 @@
  *     named per line (the records after the first go through swg_search_multi_pssm); --seqidlist F searches only
  *     the database entries whose numbers F lists (a view of the resident database: swg_db_view, swg_group_select);
  *     --allqueries --candidates F searches every query record against its own entries, F's `query entry` lines (one
- *     pass for all records: swg_search_lists).
+ *     pass for all records: swg_search_lists); --gapless reports the gapless prefilter score (best ungapped diagonal
+ *     segment: swg_search_gapless) instead of the alignment score; --prefilter N --topk K closes the pipeline: per query
+ *     the gapless top-N become the candidate list of swg_search_lists, whose K best are reported (and aligned).
  * There is no CPU backend: without a GPU the tool fails with a message.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -74,7 +76,12 @@ static void usage(const char *argv0, const char *err)
             "                         pass: one `query_record_number entry_number` pair per line, numbered as `Query #n` and\n"
             "                         `Entry #n` ('#' starts a comment, blank lines are skipped); a record without lines has an\n"
             "                         empty list; per query the Entry lines, Total Entries, --topk and --align report its own\n"
-            "                         entries only\n",
+            "                         entries only\n"
+            "    --gapless            report the gapless score (best ungapped diagonal segment; the gap scores are not used)\n"
+            "                         instead of the alignment score; not with --align, --candidates or --gpus\n"
+            "    --prefilter <N>      with --topk K: per query (every record with --allqueries) the N best entries by gapless\n"
+            "                         score are searched with gaps and the K best of those reported (--align: aligned);\n"
+            "                         no Entry lines are printed; not with --gpus, --candidates or --gapless\n",
             argv0);
     exit(EXIT_FAILURE);
 }
@@ -173,8 +180,8 @@ int main(int argc, char **argv)
     swg_scoring_init(&sc);
     const char *qpath = NULL, *dbpath = NULL, *savedb = NULL, *pssm_path = NULL, *pssmlist_path = NULL, *idlist_path = NULL, *cand_path = NULL;
     int print_seq = 0, print_fasta = 0, have_matrix = 0, packed = 0, allq = 0;
-    long topk = 0, gpu = 0, gpus = 0, v;
-    int align = 0;
+    long topk = 0, gpu = 0, gpus = 0, prefilter = 0, v;
+    int align = 0, gapless = 0;
     if (argc == 1) usage(argv[0], NULL);
     for (int i = 1; i < argc; i++)
         if (!strcasecmp(argv[i], "--help") || !strcasecmp(argv[i], "-help") || !strcasecmp(argv[i], "-h"))
@@ -193,6 +200,8 @@ int main(int argc, char **argv)
             packed = 1;
         } else if (!strcasecmp(a, "--align")) {
             align = 1;
+        } else if (!strcasecmp(a, "--gapless")) {
+            gapless = 1;
         } else if (!strcasecmp(a, "--timing")) {
             timing = 1;
         } else if (!strcasecmp(a, "--allqueries")) {
@@ -222,6 +231,9 @@ int main(int argc, char **argv)
             i++;
         } else if (!strcasecmp(a, "--topk")) {
             if (!parse_int(argv[i + 1], 0, 1 << 20, &topk)) usage(argv[0], "Invalid --topk argument");
+            i++;
+        } else if (!strcasecmp(a, "--prefilter")) {
+            if (!parse_int(argv[i + 1], 1, 1 << 20, &prefilter)) usage(argv[0], "Invalid --prefilter argument: the number of candidates per query, 1 or more");
             i++;
         } else if (!strcasecmp(a, "--pssm")) {
             pssm_path = argv[++i];
@@ -271,6 +283,11 @@ int main(int argc, char **argv)
     if (cand_path && gpus > 0) usage(argv[0], "--candidates works with one GPU (--gpu)");
     if (cand_path && idlist_path) usage(argv[0], "--candidates and --seqidlist do not combine (the candidates are the entries to search)");
     if (cand_path && pssm_path) usage(argv[0], "--candidates and --pssm do not combine (--pssmlist names a PSSM per record)");
+    if (gapless && align) usage(argv[0], "--gapless reports scores of ungapped segments: it does not combine with --align");
+    if (gapless && (gpus > 0 || cand_path)) usage(argv[0], "--gapless works with one GPU (--gpu) and without --candidates");
+    if (prefilter && topk == 0) usage(argv[0], "--prefilter N reports the --topk hits among the N gapless candidates: give --topk K");
+    if (prefilter && gpus > 0) usage(argv[0], "--prefilter works with one GPU (--gpu)");
+    if (prefilter && (cand_path || gapless)) usage(argv[0], "--prefilter makes the candidate lists itself: it does not combine with --candidates or --gapless");
 
     char err[512];
     swg_seqs q, db;
@@ -419,6 +436,22 @@ int main(int argc, char **argv)
         for (size_t l = 0; l < n_lines; l++) cands[c_off[rec[l] + 1]++] = ent[l];
         free(rec);
         free(ent);
+    }
+    /* --prefilter: the lists are made by the gapless search, record by record as the chunks come; they take the place
+     * of --candidates' lists from there on (pf_hits: the gapless top-N of one chunk's records) */
+    const size_t pf_n = prefilter ? ((size_t)prefilter < db.n ? (size_t)prefilter : db.n) : 0;
+    swg_hit *pf_hits = NULL;
+    size_t *pf_nhits = NULL;
+    if (prefilter) {
+        const size_t cap = q.n * (pf_n ? pf_n : 1);
+        c_off = (uint64_t *)calloc(q.n + 2, sizeof *c_off);
+        cands = (uint32_t *)malloc(cap * sizeof *cands);
+        lsc = (int32_t *)calloc(cap, sizeof *lsc);
+        if (!listed) listed = (unsigned char *)calloc(db.n ? db.n : 1, 1);
+        if (!c_off || !cands || !lsc || !listed) {
+            fprintf(stderr, "Error: out of memory\n");
+            return leave(EXIT_FAILURE);
+        }
     }
     const size_t lq = (size_t)q.seq_off[1];
     int8_t *qidx = (int8_t *)malloc(lq);
@@ -599,12 +632,25 @@ int main(int argc, char **argv)
             rc = swg_db_view(ctx, pdb, ids, n_ids, &sdb);
             phase("select the listed entries");
         }
+        if (rc == SWG_OK && prefilter) { /* the first record's candidates: its gapless top-N */
+            memset(listed, 0, db.n ? db.n : 1); /* (--seqidlist's marks: no Entry lines here, the marks count the candidates) */
+            pf_hits = (swg_hit *)calloc(pf_n ? pf_n : 1, sizeof *pf_hits);
+            size_t got = 0;
+            if (!pf_hits) return leave(EXIT_FAILURE);
+            rc = swg_search_gapless(ctx, sdb, NULL, pf_hits, pf_n, &got, NULL);
+            for (size_t i = 0; rc == SWG_OK && i < got; i++) cands[i] = pf_hits[i].index;
+            c_off[1] = got;
+            free(pf_hits);
+            pf_hits = NULL;
+            phase("prefilter (gapless top-N)");
+        }
         if (rc == SWG_OK && cands) { /* the first record against its own entries */
             const uint64_t off01[2] = {0, lq};
             rc = pssm0 ? swg_search_lists_pssm(ctx, sdb, pssm0, off01, 1, cands, c_off, lsc, hits, (size_t)topk, &n_hits, &st)
                        : swg_search_lists(ctx, sdb, qidx, off01, 1, cands, c_off, lsc, hits, (size_t)topk, &n_hits, &st);
         } else if (rc == SWG_OK) {
-            rc = swg_search(ctx, sdb, scores, hits, (size_t)topk, &n_hits, &st);
+            rc = gapless ? swg_search_gapless(ctx, sdb, scores, hits, (size_t)topk, &n_hits, &st)
+                         : swg_search(ctx, sdb, scores, hits, (size_t)topk, &n_hits, &st);
         }
         phase("search (first of this database)");
         if (rc != SWG_OK) {
@@ -638,7 +684,7 @@ next_query:
         }
     }
     if (allq) printf("Query #%lu: %s\n", (unsigned long)qi, qname);
-    for (size_t i = 0, shown = 0; i < db.n; i++) {
+    for (size_t i = 0, shown = 0; i < db.n && !prefilter; i++) {
         if (listed && !listed[i]) continue;
         if (shown++ % 16 == 0) {
             if (print_fasta) {
@@ -763,11 +809,37 @@ next_query:
             swg_stats st;
             memset(&st, 0, sizeof st);
             int rc;
+            if (prefilter) { /* the chunk's candidate lists: each record's gapless top-N, appended behind the lists so far */
+                const double t0 = now_ms();
+                free(pf_hits);
+                free(pf_nhits);
+                pf_hits = (swg_hit *)calloc(chunk_n * (pf_n ? pf_n : 1), sizeof *pf_hits);
+                pf_nhits = (size_t *)calloc(chunk_n, sizeof *pf_nhits);
+                if (!pf_hits || !pf_nhits) return leave(EXIT_FAILURE);
+                rc = plist ? swg_search_gapless_multi_pssm(ctx, sdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff, chunk_n, NULL,
+                                                           pf_hits, pf_n, pf_nhits, NULL)
+                           : swg_search_gapless_multi(ctx, sdb, qx, qoff, chunk_n, NULL, pf_hits, pf_n, pf_nhits, NULL);
+                if (rc != SWG_OK) {
+                    fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
+                    return leave(EXIT_FAILURE);
+                }
+                for (size_t i = 0; i < chunk_n; i++) {
+                    const uint64_t at0 = c_off[chunk_first + i];
+                    for (size_t j = 0; j < pf_nhits[i]; j++) cands[at0 + j] = pf_hits[i * pf_n + j].index;
+                    c_off[chunk_first + i + 1] = at0 + pf_nhits[i];
+                }
+                if (timing)
+                    fprintf(stderr, "[timing] prefilter (gapless top-N) of %lu queries: %.3f ms\n", (unsigned long)chunk_n, now_ms() - t0);
+            }
             if (cands) /* every record of the chunk against its own entries, in one pass */
                 rc = plist ? swg_search_lists_pssm(ctx, sdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff, chunk_n, cands,
                                                    c_off + chunk_first, lsc, mq_hits, (size_t)topk, mq_nhits, &st)
                            : swg_search_lists(ctx, sdb, qx, qoff, chunk_n, cands, c_off + chunk_first, lsc, mq_hits, (size_t)topk,
                                               mq_nhits, &st);
+            else if (gapless)
+                rc = plist ? swg_search_gapless_multi_pssm(ctx, sdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff, chunk_n, mq_scores,
+                                                           mq_hits, (size_t)topk, mq_nhits, &st)
+                           : swg_search_gapless_multi(ctx, sdb, qx, qoff, chunk_n, mq_scores, mq_hits, (size_t)topk, mq_nhits, &st);
             else
                 rc = plist ? swg_search_multi_pssm(ctx, sdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff, chunk_n, mq_scores,
                                                    mq_hits, (size_t)topk, mq_nhits, &st)
@@ -853,6 +925,8 @@ next_query:
     free(cands);
     free(c_off);
     free(lsc);
+    free(pf_hits);
+    free(pf_nhits);
     free(scores);
     free(hits);
     free(mq_al);

@@ -1,6 +1,6 @@
 """Static instruction mix of one database row of the work-queue fill kernel, from the built library.
 
-    python tools/row_isa.py [K] [edges] [wide|f16] [fma] > profiles/rNN_kK_row_isa.txt
+    python tools/row_isa.py [K] [edges] [wide|f16|gapless] [fma] > profiles/rNN_kK_row_isa.txt
 
 Extracts the gfx950 code object from seq-align-gpu_amd/libswg.so (llvm-objdump --offloading),
 disassembles swg_diag_dyn_kernel<K,16,false,false> and classifies the instructions of the first
@@ -12,7 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 K = int(sys.argv[1]) if len(sys.argv) > 1 else 23
 EDGES = int("edges" in sys.argv[2:])     # the several-pass variant (edge columns through HBM)
-WIDE = 1 if "wide" in sys.argv[2:] else 2 if "f16" in sys.argv[2:] else 0   # the cells: 0 int16, 1 wide (to 65535), 2 packed f16 with max3
+# the cells: 0 int16, 1 wide (to 65535), 2 packed f16 with max3, 3 gapless (swg_search_gapless: one state per column, f16 arithmetic)
+WIDE = 1 if "wide" in sys.argv[2:] else 2 if "f16" in sys.argv[2:] else 3 if "gapless" in sys.argv[2:] else 0
 FMA = int("fma" in sys.argv[2:])         # f16 cells: the v_pk_fma_f16 pairing instead of v_perm_b32
 tmp = tempfile.mkdtemp()
 lib = os.path.join(tmp, "libswg.so")
@@ -73,7 +74,7 @@ for l in body[a:b]:
     if not k.startswith("VALU recurrence"):
         others.append("    %-22s %s" % (p[0], p[1][:80]))
 print("kernel %s...%s%s%s, %d instructions in all; one unrolled row = %d static instructions"
-      % (name, " EDGES" * EDGES, " WIDE" * WIDE, " FMA" * FMA, len(body), b - a))
+      % (name, " EDGES" * EDGES, ("", " WIDE", " F16", " GAPLESS")[WIDE], " FMA" * FMA, len(body), b - a))
 print("(a row of the loop for 16-lane groups; the skipped score-store / flag blocks are in the listing)")
 for k, v in sorted(mix.items(), key=lambda kv: -kv[1]):
     print("  %4d  %s" % (v, k))
