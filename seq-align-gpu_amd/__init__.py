@@ -203,6 +203,9 @@ _sig("swg_debug_engine", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_int, _vp])
 _sig("swg_debug_plan", C.c_int, [_vp, C.c_size_t, C.c_int, _vp])
 _sig("swg_debug_plan_f16", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_long, _vp])
 _sig("swg_debug_plan_gapless", C.c_int, [_vp, C.c_size_t, C.c_int, _vp])
+_sig("swg_debug_plan_forced", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int, C.c_long, C.c_int, _vp])
+_sig("swg_debug_launch_log", None, [C.c_int])
+_sig("swg_debug_launch_log_read", C.c_size_t, [_vp, C.c_size_t])
 _sig("swg_debug_split", C.c_int, [_vp, C.c_size_t, C.c_uint64, _vp])
 _sig("swg_debug_list_plan", C.c_int, [C.c_size_t, C.c_uint32, C.c_int, _vp, _vp])
 _sig("swg_debug_pair_tokens", C.c_int, [_vp, _vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
@@ -400,6 +403,37 @@ def debug_list_plan(lq, n_pairs_guess, n_cu=256, main=(32, 16, 4)):
     return {"K": int(out[0]), "G": int(out[1]), "W": int(out[2]), "passes": int(out[3])}
 
 
+LAUNCH_FAMILIES = ("dyn", "lists", "q32", "qq", "streams", "systolic")
+
+
+def debug_launch_log(on):
+    """Test hook: clears the launch log and switches it on or off (off by default)."""
+    lib.swg_debug_launch_log(1 if on else 0)
+
+
+def debug_launch_log_read():
+    """Test hook: the fill-kernel launches since the log was switched on, in launch order, as dicts: family (one of
+    LAUNCH_FAMILIES: the launcher), K (columns per lane of the instantiation launched), G (lanes per group), W, form (the
+    cells: 0 packed int16, 1 wide, 2 packed f16, 3 gapless), edges (the instantiation of one pass of several), fma (the
+    f16 cells' pairing) / exact (the int32 cells' recurrence): the same flag under the name that fits the family,
+    workgroups, grid_rows, list (1: the launch works off a device-side list -- a re-run of what an earlier launch
+    flagged -- or the lists' row table, not off a range of the database).  Raises if the log overflowed."""
+    seen = lib.swg_debug_launch_log_read(None, 0)              # how many launches there were: as many rows are asked for
+    out = np.zeros((max(seen, 1), 10), dtype=np.int32)
+    lib.swg_debug_launch_log_read(out.ctypes.data_as(_vp), seen)
+    kept = int(np.count_nonzero(out[:seen, 1]))                # (a record's K is never 0: rows beyond the log's bound stay empty)
+    if kept < seen:
+        raise SwgError(SWG_ERR_STATE, "launch log: %d launches, %d kept" % (seen, kept))
+    keys = ("family", "K", "G", "W", "form", "edges", "flag", "workgroups", "grid_rows", "list")
+    recs = []
+    for row in out[:seen]:
+        r = dict(zip(keys, (int(v) for v in row)))
+        r["family"] = LAUNCH_FAMILIES[r["family"]]
+        r["fma"] = r["exact"] = r.pop("flag")
+        recs.append(r)
+    return recs
+
+
 def synth_query(seed, lq):
     out = np.empty(lq, dtype=np.int8)
     lib.swg_synth_query(seed, lq, out.ctypes.data_as(_vp))
@@ -488,6 +522,19 @@ class Database:
         keys = ("classes", "K", "G", "W", "passes", "workgroups", "long_pairs", "long_K", "long_G", "long_W", "long_workgroups", "est_us",
                 "last_pass_cols") + (() if f16_pair is None else ("fma", "lds_bytes", "long_fma"))
         return dict(zip(keys, (int(v) for v in out)))
+
+    def debug_plan_forced(self, lq, cols=0, group=0, waves=0, form=0, f16_pair=0, last_pass=True, n_cu=256):
+        """Test hook: the planner's answer for a forced geometry (options cols_per_wave, group_lanes, max_waves; long_split
+        -1) on cells of `form` (0 int16 or wide, 2 packed f16, 3 gapless), no device needed -> debug_plan's dict with fma,
+        lds_bytes and last_pass_cols for every form and "planned"; no plan is an answer: planned False, classes 0."""
+        out = np.zeros(16, dtype=np.int32)
+        _check(lib.swg_debug_plan_forced(self.handle, lq, n_cu, cols, group, waves, form, f16_pair, 1 if last_pass else 0,
+                                         out.ctypes.data_as(_vp)))
+        keys = ("classes", "K", "G", "W", "passes", "workgroups", "long_pairs", "long_K", "long_G", "long_W", "long_workgroups", "est_us",
+                "last_pass_cols", "fma", "lds_bytes", "long_fma")
+        d = dict(zip(keys, (int(v) for v in out)))
+        d["planned"] = d["classes"] > 0
+        return d
 
     def debug_plan_gapless(self, lq, n_cu=256):
         """Test hook: what search_gapless would plan for a query of lq residues with default options (no device needed):

@@ -5,6 +5,7 @@
 #include "../../include/swg_host.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -76,13 +77,14 @@ static double instr_per_row(int K, int G, int form = 0, bool fma = false)
 // pairing wherever its doubled profile fits, v_perm_b32 elsewhere): bit 0 perm, bit 1 fma.  W: the wavefronts whose
 // lane-group records share the LDS with the profile (0: the profile alone).  edges: one pass of several.  (The fma
 // form's instantiations with edges at 23 and 24 columns do not fit their 128 registers -- 19 and 22 spilled -- and are
-// left out.)
+// left out.)  With f16_pair = 2 both bits are set where the fma pairing fits: the caller takes the fma pairing and
+// keeps v_perm_b32 for the geometries whose fma candidate its later rules drop (plan_candidates).
 static int pairings(int form, int K, int G, int W, bool edges, long f16_pair)
 {
     if (form != 2) return 1;
     const bool fits = (W > 0 ? swg_diag_dyn_lds_bytes(K, G, W, true) : swg_diag_slice_bytes(K, G, true)) <= SWG_LDS_PER_CU;
     if (!fits || f16_pair == 1 || (edges && (K == 23 || K == 24))) return 1;
-    return f16_pair == 2 ? 2 : 3;
+    return 3;
 }
 // one pass of several through the work queue: row index, edge hand-over to the leader, the tail's
 // edge store
@@ -185,8 +187,15 @@ static int plan_candidates(const swg_db *db, size_t lq, int n_cu, long opt_cols,
             // chain that matters is the longest pair at the rate of a wavefront that gets its fair
             // share of the SIMD
             const bool dynamic = work_queue && (npass == 1 || db->n_local < (1u << 30));
-            // the f16 cells' two pairings are two candidates: the fma one's profile is twice the size (occupancy)
-            for (int fma = 0; fma <= 1; ++fma) {
+            // the f16 cells' two pairings are two candidates: the fma one's profile is twice the size (occupancy).
+            // f16_pair = 2 ("fma wherever it fits, v_perm_b32 elsewhere"): the fma candidates first, and the perm ones
+            // of this (K, G) only when the rules below left none of them standing -- the records do not fit beside the
+            // doubled profile at the workgroup size asked for, or it would cost resident wavefronts -- so that the
+            // option plans wherever f16_pair = 1 does
+            const size_t n_before = cands->size();
+            for (int step = 0; step <= 1; ++step) {
+            const int fma = f16_pair == 2 ? 1 - step : step;
+            if (f16_pair == 2 && !fma && cands->size() > n_before) continue;
             // (the f16 cells run on the work queue only)
             if (!(pairings(form, info.K, G, 0, npass > 1, f16_pair) & (1 << fma)) || (fma && !dynamic)) continue;
             const size_t lds = swg_diag_slice_bytes(info.K, G, fma);
@@ -730,4 +739,62 @@ extern "C" int swg_debug_plan_gapless(const swg_db *db, size_t lq, int n_cu, int
 extern "C" int swg_debug_plan_f16(const swg_db *db, size_t lq, int n_cu, long f16_pair, int32_t *out)
 {
     return debug_plan(db, lq, n_cu, 2, f16_pair, out);
+}
+
+// Test hook: the planner's answer for a forced geometry, as a search with options cols_per_wave, group_lanes, max_waves,
+// long_split = -1, f16_pair and last_pass asks it (plan_search in swg_api.cpp).  No plan: SWG_OK and out all zero.
+extern "C" int swg_debug_plan_forced(const swg_db *db, size_t lq, int n_cu, long cols, long group, long waves, int form,
+                                     long f16_pair, int last_pass, int32_t *out)
+{
+    if (!db || !out || lq == 0 || n_cu <= 0 || (form != 0 && form != 2 && form != 3) || f16_pair < 0 || f16_pair > 2 || cols < 0 ||
+        group < 0 || waves < 0)
+        return SWG_ERR_ARG;
+    memset(out, 0, 16 * sizeof(int32_t));
+    SwgDiagWork wk;
+    try {
+        if (swg_plan_diag_work(db, lq, n_cu, cols, group, waves, -1, true, true, &wk, 1.0, form, form == 3 ? 1 : f16_pair) <= 0) return SWG_OK;
+    } catch (const std::exception &) {
+        return SWG_ERR_NOMEM;
+    }
+    const SwgDiagPlan &b = wk.plan[0];
+    int last_variant = -1, last_K = 0;
+    if (!last_pass || wk.n_classes != 1 || !swg_plan_last_pass(b, lq, &last_variant, &last_K)) last_K = 0;
+    const bool fma = form == 2 && b.fma != 0;
+    const int32_t v[16] = {wk.n_classes, b.K, b.G, b.W, b.npass, b.workgroups, 0, 0, 0, 0, 0, (int32_t)(b.est_ms * 1e3), last_K,
+                           fma ? 1 : 0, (int32_t)swg_diag_dyn_lds_bytes(b.K, b.G, b.W, fma), 0};
+    memcpy(out, v, sizeof v);
+    return SWG_OK;
+}
+
+// The launch log (test hook, swg_internal.h): which instantiation each launcher of a fill kernel was asked for.  Host-side
+// bookkeeping: off by default, bounded, and nothing of what is launched depends on it.
+static std::mutex g_launch_log_mutex;
+static std::atomic<bool> g_launch_log_on{false};
+static size_t g_launch_log_seen = 0;
+static std::vector<int32_t> g_launch_log;
+
+void swg_launch_log_add(int family, int K, int G, int W, int form, bool edges, bool flag, int workgroups, int grid_rows, bool list)
+{
+    if (!g_launch_log_on.load(std::memory_order_relaxed)) return;
+    std::lock_guard<std::mutex> lock(g_launch_log_mutex);
+    if (g_launch_log_seen++ >= SWG_LAUNCH_LOG_CAP) return;
+    const int32_t r[SWG_LAUNCH_LOG_FIELDS] = {family, K, G, W, form, edges ? 1 : 0, flag ? 1 : 0, workgroups, grid_rows, list ? 1 : 0};
+    g_launch_log.insert(g_launch_log.end(), r, r + SWG_LAUNCH_LOG_FIELDS);
+}
+
+extern "C" void swg_debug_launch_log(int on)
+{
+    std::lock_guard<std::mutex> lock(g_launch_log_mutex);
+    g_launch_log_on = on != 0;
+    g_launch_log_seen = 0;
+    g_launch_log.clear();
+    if (on) g_launch_log.reserve((size_t)SWG_LAUNCH_LOG_CAP * SWG_LAUNCH_LOG_FIELDS); // (the launchers never allocate)
+}
+
+extern "C" size_t swg_debug_launch_log_read(int32_t *out, size_t cap)
+{
+    std::lock_guard<std::mutex> lock(g_launch_log_mutex);
+    const size_t held = g_launch_log.size() / SWG_LAUNCH_LOG_FIELDS, n = std::min(held, cap);
+    if (out && n > 0) memcpy(out, g_launch_log.data(), n * SWG_LAUNCH_LOG_FIELDS * sizeof(int32_t));
+    return g_launch_log_seen;
 }

@@ -436,6 +436,21 @@ extern "C" int swg_debug_plan_gapless(const swg_db *db, size_t lq, int n_cu, int
 // the same for the packed-f16 cells (option f16_pair: 0 auto, 1 perm, 2 fma), out[0..15]: swg_debug_plan's 13 values, then
 // the bulk's pairing (1 fma, 0 v_perm_b32), its workgroup's LDS bytes, the long class's pairing
 extern "C" int swg_debug_plan_f16(const swg_db *db, size_t lq, int n_cu, long f16_pair, int32_t *out);
+// test hook: the planner's answer for a FORCED geometry (options cols_per_wave, group_lanes, max_waves; 0 = free) with
+// long_split = -1 (one class), on cells of `form` (0 int16 -- the wide form plans alike --, 2 packed f16, 3 gapless) with
+// option f16_pair, without a device.  "No plan" is an answer, not an error: SWG_OK with out[0] = 0 and the rest zero.
+// out[0..15] as swg_debug_plan_f16 (the pairing and the LDS bytes for every form); out[12], the last pass's own columns
+// per lane, is 0 with last_pass = 0 (option last_pass).
+extern "C" int swg_debug_plan_forced(const swg_db *db, size_t lq, int n_cu, long cols, long group, long waves, int form,
+                                     long f16_pair, int last_pass, int32_t *out);
+// test hook: the launch log (swg_launch_log_add, swg_internal.h).  swg_debug_launch_log(on): clears the log and switches
+// it on (1) or off (0); off by default.  While on, the launchers append records until SWG_LAUNCH_LOG_CAP are held (later
+// launches are counted, not kept).  swg_debug_launch_log_read: copies up to cap records of SWG_LAUNCH_LOG_FIELDS int32
+// each {family, K, G, W, form, edges, flag, workgroups, grid_rows, list}; returns the launches seen since the log was cleared.
+#define SWG_LAUNCH_LOG_CAP 4096
+#define SWG_LAUNCH_LOG_FIELDS 10
+extern "C" void swg_debug_launch_log(int on);
+extern "C" size_t swg_debug_launch_log_read(int32_t *out, size_t cap);
 // the systolic engine's estimate from the host's bin table (swg_diag_host.cpp); it is picked over the lane groups when it
 // wins by this margin (both models are good to about 10 %)
 #define SWG_SYSTOLIC_MARGIN 0.85

@@ -188,6 +188,21 @@ struct SwgKernelInfo {
     int elem_size; // profile element bytes
 };
 
+// Test hook (swg_diag_host.cpp; host-side bookkeeping, off unless swg_debug_launch_log switched it on): every launcher
+// of a fill kernel reports which instantiation it is about to launch.  family: the SWG_LOG_* below; K: columns per lane
+// (systolic: per wavefront) of the variant launched; G: lanes per group (systolic: 0); form: the cells (CellsDiag FORM:
+// 0 packed int16, 1 wide, 2 packed f16, 3 gapless; the int32 families 0; systolic: 2 on its f16 cells); edges: the
+// instantiation of one pass of several; flag: the f16 cells' fma pairing / the int32 cells' exact recurrence / the systolic engine's int32 cells; grid_rows:
+// the grid's second dimension (queries or query pairs of a batch, else 1); list: the launch takes its work from a
+// device-side list (a re-run of flagged pairs or sequences) or from the lists' row table instead of a range of the database.
+#define SWG_LOG_DYN 0      // swg_launch_diag_dyn
+#define SWG_LOG_LISTS 1    // swg_launch_diag_lists
+#define SWG_LOG_Q32 2      // swg_launch_diag32q
+#define SWG_LOG_QQ 3       // swg_launch_diag_qq
+#define SWG_LOG_STREAMS 4  // swg_launch_diag (fixed streams)
+#define SWG_LOG_SYSTOLIC 5 // swg_launch_fill
+void swg_launch_log_add(int family, int K, int G, int W, int form, bool edges, bool flag, int workgroups, int grid_rows, bool list);
+
 // Launchers (swg_kernels.hip).  variant selects the (K, MAXW) instantiation.
 int swg_num_variants(int bits);
 SwgKernelInfo swg_variant_info(int bits, int variant);

@@ -2868,6 +2868,7 @@ hipError_t swg_launch_diag32q(int variant, bool edges, bool exact, int W, int wo
     auto k = t[variant][(exact ? 2 : 0) + (edges ? 1 : 0)];
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
+    swg_launch_log_add(SWG_LOG_Q32, swg_diag_variant_info(variant).K, (int)p.G, W, 0, edges, exact, workgroups, 1, p.list != nullptr);
     hipLaunchKernelGGL(k, dim3(workgroups), dim3(W * 64), lds, stream, p);
     return hipGetLastError();
 }
@@ -2888,6 +2889,7 @@ hipError_t swg_launch_diag_qq(int variant, int W, int workgroups, int n_pairs, c
     auto k = t[variant];
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
+    swg_launch_log_add(SWG_LOG_QQ, swg_diag_variant_info(variant).K, (int)p.G, W, 2, false, false, workgroups, n_pairs, false);
     hipLaunchKernelGGL(k, dim3(workgroups, n_pairs), dim3(W * 64), lds, stream, p);
     return hipGetLastError();
 }
@@ -3001,6 +3003,7 @@ hipError_t swg_launch_diag(int variant, bool multipass, bool wide, int W, int wo
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return e;
+    swg_launch_log_add(SWG_LOG_STREAMS, v[variant].K, (int)p.G, W, wide ? 1 : 0, multipass || wide, false, workgroups, 1, false);
     hipLaunchKernelGGL(k, dim3(workgroups), dim3(W * 64), lds_bytes, stream, p);
     return hipGetLastError();
 }
@@ -3029,6 +3032,7 @@ hipError_t swg_launch_diag_dyn(int variant, bool edges, int form, int W, int wor
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
+    swg_launch_log_add(SWG_LOG_DYN, v[variant].K, (int)p.G, W, form, edges, fma, workgroups, n_queries, p.list != nullptr);
     hipLaunchKernelGGL(k, dim3(workgroups, n_queries), dim3(W * 64), lds, stream, p);
     return hipGetLastError();
 }
@@ -3045,6 +3049,7 @@ hipError_t swg_launch_diag_lists(int variant, int form, int W, int workgroups, c
     auto k = form == 2 ? swg_dyn_kernel_lists_f16(variant) : swg_dyn_kernel_lists_i16(variant);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
+    swg_launch_log_add(SWG_LOG_LISTS, v[variant].K, (int)p.G, W, form, false, false, workgroups, 1, true);
     hipLaunchKernelGGL(k, dim3(workgroups), dim3(W * 64), lds, stream, p);
     return hipGetLastError();
 }
@@ -3088,6 +3093,7 @@ hipError_t swg_launch_fill(int bits, int variant, int W, int workgroups, const S
     const size_t lds = v[variant].info.lds_per_wave * (size_t)W + v[variant].info.lds_fixed;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
+    swg_launch_log_add(SWG_LOG_SYSTOLIC, v[variant].info.K, 0, W, f16 ? 2 : 0, p.npass > 1, bits == 32, workgroups, 1, p.list != nullptr);
     hipLaunchKernelGGL(k, dim3(workgroups), dim3(W * 64), lds, stream, p);
     return hipGetLastError();
 }
