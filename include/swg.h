@@ -410,6 +410,22 @@ int swg_align_hits_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssm
                               swg_alignment *out, char *ops, size_t ops_stride);
 size_t swg_align_ops_bound_multi(const swg_db *db, const uint64_t *q_offsets, size_t n_queries);
 
+/* The coordinates without the path: swg_align_bounds / _multi / _multi_pssm write, for the same arguments, every field
+ * (score, index, q_begin, q_end, d_begin, d_end, n_ops, reserved = 0) that swg_align_hits / _multi / _multi_pssm write
+ * with ops == NULL -- same tie rules, same errors, hits in any order and repeated, slots past n_hits[i] not written --
+ * but from a forward pass alone: every state of the recurrence carries the origin and the length of its path, so there
+ * is no predecessor byte per cell and no walk.  One lane group takes a pair; the residues are read from the
+ * resident database (a view is accepted), so the database must be resident for all three calls.  A pair the kernel
+ * cannot hold (a query of more than 1024 columns, a sequence of 2^20 residues or more) goes through the traceback's
+ * kernel in the same call, with the same results.  swg_align_bounds uses the context's query (index or PSSM); the
+ * batch calls neither read nor change it.  For what is printed, swg_align_hits gives the path. */
+int swg_align_bounds(swg_ctx *ctx, const swg_db *db, const swg_hit *hits, size_t n_hits, swg_alignment *out);
+int swg_align_bounds_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets,
+                           size_t n_queries, const swg_hit *hits, size_t k, const size_t *n_hits, swg_alignment *out);
+int swg_align_bounds_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets,
+                                size_t n_queries, const swg_hit *hits, size_t k, const size_t *n_hits,
+                                swg_alignment *out);
+
 /* ---- multi-GPU merge -------------------------------------------------- */
 
 /* 64-bit sort key of a hit: (score << 32) | (0xFFFFFFFF - index).  Larger key =

@@ -37,7 +37,8 @@ ABI_SYMBOLS = [
     "swg_db_packed_bytes", "swg_db_order", "swg_search", "swg_search_begin", "swg_search_end", "swg_search_multi",
     "swg_search_multi_pssm", "swg_search_lists", "swg_search_lists_pssm", "swg_search_gapless", "swg_search_gapless_multi",
     "swg_search_gapless_multi_pssm", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_align_hits_multi",
-    "swg_align_hits_multi_pssm", "swg_align_ops_bound_multi", "swg_hit_key",
+    "swg_align_hits_multi_pssm", "swg_align_ops_bound_multi", "swg_align_bounds", "swg_align_bounds_multi",
+    "swg_align_bounds_multi_pssm", "swg_hit_key",
     "swg_key_hit", "swg_topk_merge_keys",
     "swg_group_create", "swg_group_destroy", "swg_group_size", "swg_group_last_error", "swg_group_set_option",
     "swg_group_set_scoring", "swg_group_set_query", "swg_group_set_query_pssm", "swg_group_load", "swg_group_search",
@@ -157,6 +158,9 @@ _sig("swg_align_ops_bound_multi", C.c_size_t, [_vp, _vp, C.c_size_t])
 _sig("swg_hit_key", C.c_uint64, [C.c_int32, C.c_uint32])
 _sig("swg_key_hit", None, [C.c_uint64, C.POINTER(Hit)])
 _sig("swg_topk_merge_keys", C.c_size_t, [_vp, C.c_size_t, C.c_size_t, _vp])
+_sig("swg_align_bounds", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp])
+_sig("swg_align_bounds_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp])
+_sig("swg_align_bounds_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp])
 _sig("swg_group_align_hits", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t])
 _sig("swg_group_align_ops_bound", C.c_size_t, [_vp])
 _sig("swg_group_select", C.c_int, [_vp, _vp, C.c_size_t])
@@ -198,6 +202,7 @@ _sig("swg_pssm_load", C.c_int, [C.c_char_p, C.POINTER(Scoring), C.POINTER(_vp), 
 _sig("swg_pssm_free", None, [_vp, _vp])
 # test hook, declared in csrc/swg_host_internal.h (not part of the public ABI)
 _sig("swg_debug_fail_alloc", None, [C.c_int])
+_sig("swg_debug_bounds_last", C.c_int, [_vp, _vp])
 _sig("swg_debug_sort_count", C.c_ulong, [])
 _sig("swg_debug_engine", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_int, _vp])
 _sig("swg_debug_plan", C.c_int, [_vp, C.c_size_t, C.c_int, _vp])
@@ -818,7 +823,39 @@ class Context:
         pflat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 32)), dtype=np.int8)
         return self._align_multi(lib.swg_align_hits_multi_pssm, db, pflat, qoff, hits, want_ops, ops_stride)
 
-    def _align_multi(self, fn, db, qflat, qoff, hits, want_ops, ops_stride):
+    def align_bounds(self, db, hits):
+        """align_hits(db, hits, want_ops=False) from a forward pass alone (swg_align_bounds: no traceback is run)."""
+        n = len(hits)
+        arr = (Hit * max(n, 1))()
+        for i, (sc, ix) in enumerate(hits):
+            arr[i].score, arr[i].index = int(sc), int(ix)
+        out = (Alignment * max(n, 1))()
+        _check(lib.swg_align_bounds(self.handle, db.handle, C.cast(arr, _vp), n, C.cast(out, _vp)), self.handle)
+        return [{f: int(getattr(out[i], f)) for f, _ in Alignment._fields_ if f != "reserved"} for i in range(n)]
+
+    def align_bounds_multi(self, db, queries, hits):
+        """align_hits_multi(db, queries, hits, want_ops=False) from a forward pass alone (swg_align_bounds_multi)."""
+        qoff = np.zeros(len(queries) + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in queries])
+        qflat = np.ascontiguousarray(np.concatenate(queries) if len(queries) else np.zeros(0), dtype=np.int8)
+        return self._align_multi(lib.swg_align_bounds_multi, db, qflat, qoff, hits, False, None, bounds=True)
+
+    def align_bounds_multi_pssm(self, db, pssms, hits):
+        """align_bounds_multi with position-specific queries: pssms as search_multi_pssm takes them."""
+        rows = [_pssm(p)[0] for p in pssms]
+        qoff = np.zeros(len(rows) + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([r.shape[0] for r in rows])
+        pflat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 32)), dtype=np.int8)
+        return self._align_multi(lib.swg_align_bounds_multi_pssm, db, pflat, qoff, hits, False, None, bounds=True)
+
+    def debug_bounds_last(self):
+        """What the last align_bounds* call of this context did (swg_debug_bounds_last) -> dict: pairs on the bounds kernel,
+        pairs on the fallback (the traceback's kernel), launches of the bounds kernel, its column limit."""
+        out = np.zeros(4, dtype=np.uint32)
+        _check(lib.swg_debug_bounds_last(self.handle, out.ctypes.data_as(_vp)), self.handle)
+        return dict(zip(("kernel_pairs", "fallback_pairs", "launches", "column_limit"), (int(v) for v in out)))
+
+    def _align_multi(self, fn, db, qflat, qoff, hits, want_ops, ops_stride, bounds=False):
         nq = len(qoff) - 1
         if len(hits) != nq:
             raise ValueError("hits: %d rows for %d queries" % (len(hits), nq))
@@ -830,11 +867,12 @@ class Context:
             for j, (sc, ix) in enumerate(row):
                 arr[i * k + j].score, arr[i * k + j].index = int(sc), int(ix)
         out = (Alignment * max(nq * k, 1))()
-        stride = int(ops_stride if ops_stride is not None else
-                     lib.swg_align_ops_bound_multi(db.handle, qoff.ctypes.data_as(_vp), nq))
+        stride = 0 if bounds else int(ops_stride if ops_stride is not None else
+                                      lib.swg_align_ops_bound_multi(db.handle, qoff.ctypes.data_as(_vp), nq))
         ops = C.create_string_buffer(max(1, nq * k * stride)) if want_ops else None
-        _check(fn(self.handle, db.handle, qflat.ctypes.data_as(_vp), qoff.ctypes.data_as(_vp), nq, C.cast(arr, _vp), k,
-                  C.cast(nh, _vp), C.cast(out, _vp), C.cast(ops, _vp) if want_ops else None, stride), self.handle)
+        args = (self.handle, db.handle, qflat.ctypes.data_as(_vp), qoff.ctypes.data_as(_vp), nq, C.cast(arr, _vp), k,
+                C.cast(nh, _vp), C.cast(out, _vp))
+        _check(fn(*args) if bounds else fn(*args, C.cast(ops, _vp) if want_ops else None, stride), self.handle)
         raw = ops.raw if want_ops else None          # (one copy: .raw copies the whole buffer on every access)
         res = []
         for i, row in enumerate(hits):

@@ -40,7 +40,7 @@ ARCH = "gfx950"
 DEVICE_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-load-store-opt",
                 "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 
-HIP_SOURCES = ["swg_kernels.hip", "swg_trace.hip", "swg_api.cpp", "swg_group.cpp"]
+HIP_SOURCES = ["swg_kernels.hip", "swg_trace.hip", "swg_bounds.hip", "swg_api.cpp", "swg_group.cpp"]
 KERNEL_PARTS = [0, 1, 2, 3, 4, 5]  # swg_kernels.hip is compiled once per part (-DSWG_PART=n), in parallel
 CXX_SOURCES = ["swg_pack.cpp", "swg_diag_host.cpp"]  # host-only C++, OpenMP via g++
 C_SOURCES = ["swg_scoring.c", "swg_seqio.c", "swg_synth.c", "swg_threads.c"]
@@ -61,6 +61,12 @@ def _stale(target, deps):
         return True
     t = os.path.getmtime(target)
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
+
+
+def _obj_stale(obj, deps):
+    """An object file that is not there is out of date only if the library is: a copy of a built tree that left the
+    object files behind (they are build products of a build product) compiles nothing again."""
+    return _stale(obj if os.path.exists(obj) else LIB, deps)
 
 
 def _headers():
@@ -156,7 +162,7 @@ def build(force=False, verbose=True):
         parts = KERNEL_PARTS if src == "swg_kernels.hip" else [None]
         for part in parts:
             o = os.path.join(OBJ, src + (".o" if part is None else ".part%d.o" % part))
-            if force or _stale(o, [s] + hdrs):
+            if force or _obj_stale(o, [s] + hdrs):
                 jobs.append(("[hipcc] " + src + ("" if part is None else " part %d" % part),
                              [HIPCC, "--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-c"] + DEVICE_FLAGS
                              + ([] if part is None else ["-DSWG_PART=%d" % part]) + ["-o", o, "-x", "hip", s]))
@@ -164,16 +170,18 @@ def build(force=False, verbose=True):
     for src in CXX_SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJ, src + ".o")
-        if force or _stale(o, [s] + hdrs):
+        if force or _obj_stale(o, [s] + hdrs):
             jobs.append(("[g++] " + src, ["g++", "-O2", "-fPIC", "-fopenmp", "-std=c++17", "-D__HIP_PLATFORM_AMD__",
                                           "-I" + os.path.join(ROCM, "include"), "-c", "-o", o, s]))
         objs.append(o)
     for src in C_SOURCES:
         s = os.path.join(HOST, src)
         o = os.path.join(OBJ, src + ".o")
-        if force or _stale(o, [s] + hdrs):
+        if force or _obj_stale(o, [s] + hdrs):
             jobs.append(("[gcc] " + src, ["gcc", "-O2", "-fPIC", "-fopenmp", "-std=c11", "-Wall", "-c", "-o", o, s]))
         objs.append(o)
+    if not force and jobs and any(not os.path.exists(o) for o in objs):
+        return build(force=True, verbose=verbose)  # something changed in a tree without its objects: all of them are needed to link
     if jobs:
         from concurrent.futures import ThreadPoolExecutor
         if verbose:

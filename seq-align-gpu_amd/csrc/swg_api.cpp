@@ -311,6 +311,9 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
         if (value < 0 || value > 2)
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "f16_pair must be 0 (auto), 1 (v_perm_b32) or 2 (v_pk_fma_f16 wherever it fits)");
         ctx->opt_f16_pair = value;
+    } else if (!strcmp(key, "bounds_groups")) {
+        if (value < 0) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "bounds_groups must be 0 (auto) or the most lane groups of a bounds launch");
+        ctx->opt_bounds_groups = value;
     } else if (!strcmp(key, "last_pass")) {
         ctx->opt_last_pass = value != 0;
     } else if (!strcmp(key, "qq")) {

@@ -355,6 +355,8 @@ struct swg_ctx {
     // options
     long opt_force_bits = 0, opt_cols = 0, opt_max_waves = 0, opt_workgroups = 0, opt_engine = 0, opt_group = 0, opt_long_split = 0, opt_autotune = 1, opt_dynamic = 1, opt_prio_share = 150, opt_long_helps = 0, opt_wide = 1, opt_side_readout = 1, opt_f16 = 1, opt_qq = 1, opt_last_pass = 1, opt_f16_pair = 0;
     long opt_wave_budget = 0, opt_q32_waves = 0;
+    long opt_bounds_groups = 0; // lane groups of a bounds launch (swg_align_bounds*), 0: auto (option "bounds_groups": tests)
+    uint32_t bounds_last[4] = {0, 0, 0, 0}; // the last bounds call: pairs on its kernel, pairs on the fallback, its launches, its column limit
     long opt_batch = 8, opt_batch_blocks = 0; // work queue: pairs one request claims where pairs are short (blocks; 0: about 40 us of work, from the geometry)
     uint32_t opt_seg_blocks = SWG_DYN_SEG_BLOCKS; // token blocks per launch of the multi-pass fill (option "segment_blocks": tests)
     // device state
@@ -464,6 +466,32 @@ uint32_t swg_split_rows(size_t lq, uint64_t qbound);
 void swg_db_split_at(swg_db *db, uint32_t rows);
 extern "C" int swg_debug_pair_tokens(swg_ctx *ctx, swg_db *db, int from_host, uint32_t *out, size_t cap_dwords,
                                      size_t *n_dwords);
+
+// swg_trace.hip: the pairs of one alignment call.  Query i is src[q_offsets[i] .. q_offsets[i+1]) in positions (index
+// bytes, or PSSM rows of 32 bytes), its hits are hits[i*k .. i*k + n_hits[i]), and out / ops take the same layout.
+// swg_align_hits is the batch of one query, the context's.
+struct SwgTraceBatch {
+    const char *fn; // the entry point, for messages
+    const int8_t *src;
+    bool pssm;
+    const uint64_t *q_offsets;
+    size_t n_queries;
+    const swg_hit *hits;
+    size_t k;
+    const size_t *n_hits;
+};
+// The argument checks of the batch entry points (*total = hits of all rows; SWG_OK with 0: nothing to do), and every hit
+// of a checked batch through the traceback's kernel, guarded against C++ exceptions (ops == NULL: coordinates only).
+// stride0: paths are wanted with an ops_stride of 0 (refused where it always was: after the database, before the rows)
+int swg_trace_check_batch(swg_ctx *ctx, const swg_db *db, const SwgTraceBatch &tb, const swg_alignment *out, bool stride0,
+                          size_t *total);
+int swg_trace_align_batch(swg_ctx *ctx, const swg_db *db, const SwgTraceBatch &tb, size_t total, swg_alignment *out, char *ops,
+                          size_t ops_stride);
+// swg_bounds.hip, test hook: what the context's last swg_align_bounds* call did -- out[0..3] = pairs on the bounds kernel,
+// pairs on the fallback (the traceback's kernel), launches of the bounds kernel, its column limit
+#define SWG_BOUNDS_COLS 1024         /* 64 lanes x 16 columns */
+#define SWG_BOUNDS_LEN (1u << 20)    /* a sequence below this many residues: the tag holds its origin in 20 bits */
+extern "C" int swg_debug_bounds_last(const swg_ctx *ctx, uint32_t out[4]);
 
 // swg_diag_host.cpp (host only)
 // geometry of both classes for one query length on one device; returns the number of

@@ -195,19 +195,7 @@ extern "C" size_t swg_align_ops_bound_multi(const swg_db *db, const uint64_t *q_
     return (size_t)lq_max + longest_sequence(db) + 1;
 }
 
-// The pairs of one call: query i is src[q_offsets[i] .. q_offsets[i+1]) in positions (index bytes, or PSSM rows of 32
-// bytes), its hits are hits[i*k .. i*k + n_hits[i]), and out / ops take the same layout.  swg_align_hits is the batch
-// of one query, the context's.
-struct TraceBatch {
-    const char *fn; // the entry point, for messages
-    const int8_t *src;
-    bool pssm;
-    const uint64_t *q_offsets;
-    size_t n_queries;
-    const swg_hit *hits;
-    size_t k;
-    const size_t *n_hits;
-};
+using TraceBatch = SwgTraceBatch; // (swg_host_internal.h: the bounds calls hand their fallback pairs over as one)
 
 // One launch: jobs [b, e) of the launch order, the bytes its buffers need, its longest query.
 struct TraceLaunch {
@@ -362,8 +350,8 @@ done:
 }
 
 // try/catch: no C++ exception crosses the ABI (the host vectors are sized by the batch)
-static int align_batch_guarded(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, size_t total, swg_alignment *out,
-                               char *ops, size_t ops_stride)
+int swg_trace_align_batch(swg_ctx *ctx, const swg_db *db, const SwgTraceBatch &tb, size_t total, swg_alignment *out, char *ops,
+                          size_t ops_stride)
 {
     try {
         return align_batch(ctx, db, tb, total, out, ops, ops_stride);
@@ -388,21 +376,22 @@ extern "C" int swg_align_hits(swg_ctx *ctx, const swg_db *db, const swg_hit *hit
     const uint64_t q_offsets[2] = {0, ctx->query_len()};
     const TraceBatch tb = {"swg_align_hits", ctx->query_pssm ? ctx->pssm.data() : ctx->query.data(), ctx->query_pssm,
                            q_offsets, 1, hits, n_hits, &n_hits};
-    return align_batch_guarded(ctx, db, tb, n_hits, out, ops, ops_stride);
+    return swg_trace_align_batch(ctx, db, tb, n_hits, out, ops, ops_stride);
 }
 
 // The batch entry points: the queries are checked as search_multi_impl checks them, the rows of hits against k.
-static int align_hits_multi(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, swg_alignment *out, char *ops,
-                            size_t ops_stride)
+int swg_trace_check_batch(swg_ctx *ctx, const swg_db *db, const SwgTraceBatch &tb, const swg_alignment *out, bool stride0,
+                          size_t *total_out)
 {
     const char *fn = tb.fn;
+    *total_out = 0;
     if (!ctx) return swg_set_global_error(SWG_ERR_ARG, "%s: NULL context", fn);
     if (!db || (tb.n_queries && (!tb.src || !tb.q_offsets || !tb.n_hits)))
         return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: NULL argument", fn);
     if (!ctx->have_scoring) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: no scoring set", fn);
     if (db->device != ctx->device || !db->d_codes)
         return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: database is not resident on device %d", fn, ctx->device);
-    if (ops && ops_stride == 0) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: ops_stride is 0", fn);
+    if (stride0) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: ops_stride is 0", fn);
     size_t total = 0;
     for (size_t i = 0; i < tb.n_queries; ++i) {
         if (tb.q_offsets[i + 1] <= tb.q_offsets[i])
@@ -421,7 +410,17 @@ static int align_hits_multi(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb
     if (total == 0) return SWG_OK;
     if (!tb.hits || !out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: NULL argument", fn);
     if (total > (1u << 20)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: more than 2^20 hits", fn);
-    return align_batch_guarded(ctx, db, tb, total, out, ops, ops_stride);
+    *total_out = total;
+    return SWG_OK;
+}
+
+static int align_hits_multi(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, swg_alignment *out, char *ops,
+                            size_t ops_stride)
+{
+    size_t total = 0;
+    const int rc = swg_trace_check_batch(ctx, db, tb, out, ops && ops_stride == 0, &total);
+    if (rc != SWG_OK || total == 0) return rc;
+    return swg_trace_align_batch(ctx, db, tb, total, out, ops, ops_stride);
 }
 
 extern "C" int swg_align_hits_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets,

@@ -21,7 +21,9 @@
  *     --allqueries --candidates F searches every query record against its own entries, F's `query entry` lines (one
  *     pass for all records: swg_search_lists); --gapless reports the gapless prefilter score (best ungapped diagonal
  *     segment: swg_search_gapless) instead of the alignment score; --prefilter N --topk K closes the pipeline: per query
- *     the gapless top-N become the candidate list of swg_search_lists, whose K best are reported (and aligned).
+ *     the gapless top-N become the candidate list of swg_search_lists, whose K best are reported (and aligned);
+ *     --bounds with --topk K appends the coordinates and the length of every reported hit's alignment without its
+ *     path (swg_align_bounds, with --allqueries swg_align_bounds_multi / _multi_pssm: no traceback is run).
  * There is no CPU backend: without a GPU the tool fails with a message.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -61,6 +63,9 @@ static void usage(const char *argv0, const char *err)
             "    --topk <K>           append the K best hits (score, index, name)\n"
             "    --align              with --topk: append the alignment of every reported hit\n"
             "                         (query line over database line, '-' = gap; coordinates 0-based, end exclusive)\n"
+            "    --bounds             with --topk: append one line per reported hit, `Bounds #i: entry E score S query a..b entry c..d\n"
+            "                         length N` (the alignment's coordinates, 0-based, end exclusive, and its number of steps; no\n"
+            "                         alignment text); not with --align, --gapless or --gpus\n"
             "    --timing             wall time of every phase (reading, packing, upload, search, printing) on stderr\n"
             "    --gpu <N>            HIP device ordinal [default: 0]\n"
             "    --gpus <N>           shard the database over GPUs 0..N-1 (RCCL top-K merge)\n"
@@ -181,7 +186,7 @@ int main(int argc, char **argv)
     const char *qpath = NULL, *dbpath = NULL, *savedb = NULL, *pssm_path = NULL, *pssmlist_path = NULL, *idlist_path = NULL, *cand_path = NULL;
     int print_seq = 0, print_fasta = 0, have_matrix = 0, packed = 0, allq = 0;
     long topk = 0, gpu = 0, gpus = 0, prefilter = 0, v;
-    int align = 0, gapless = 0;
+    int align = 0, gapless = 0, bounds = 0;
     if (argc == 1) usage(argv[0], NULL);
     for (int i = 1; i < argc; i++)
         if (!strcasecmp(argv[i], "--help") || !strcasecmp(argv[i], "-help") || !strcasecmp(argv[i], "-h"))
@@ -202,6 +207,8 @@ int main(int argc, char **argv)
             align = 1;
         } else if (!strcasecmp(a, "--gapless")) {
             gapless = 1;
+        } else if (!strcasecmp(a, "--bounds")) {
+            bounds = 1;
         } else if (!strcasecmp(a, "--timing")) {
             timing = 1;
         } else if (!strcasecmp(a, "--allqueries")) {
@@ -278,6 +285,10 @@ int main(int argc, char **argv)
     if (pssmlist_path && gpus > 0) usage(argv[0], "--pssmlist works with one GPU (--gpu)");
     if ((packed || savedb || allq) && gpus > 0) usage(argv[0], "--packed/--savedb/--allqueries work with one GPU (--gpu)");
     if (align && topk == 0) usage(argv[0], "--align reports the alignments of the --topk hits: give --topk K");
+    if (bounds && topk == 0) usage(argv[0], "--bounds reports the alignment coordinates of the --topk hits: give --topk K");
+    if (bounds && align) usage(argv[0], "--bounds reports coordinates without the alignments: it does not combine with --align (whose headers carry them)");
+    if (bounds && gapless) usage(argv[0], "--bounds reports coordinates of gapped alignments: it does not combine with --gapless");
+    if (bounds && gpus > 0) usage(argv[0], "--bounds works with one GPU (--gpu)");
     if (pssm_path && allq) usage(argv[0], "--pssm scores one query: it does not combine with --allqueries");
     if (cand_path && !allq) usage(argv[0], "--candidates lists the entries of --allqueries' records: give --allqueries");
     if (cand_path && gpus > 0) usage(argv[0], "--candidates works with one GPU (--gpu)");
@@ -673,6 +684,10 @@ int main(int argc, char **argv)
      * alignments would print, after its own search results (as when each record was aligned on its own) */
     int al_one_by_one = 0, al_failed = 0;
     char al_err[512] = "";
+    /* --allqueries --bounds: the coordinates of queries [bd_first, bd_first + bd_n) of the current chunk, hit j of query
+     * bd_first + i at mq_bd[i*topk + j] */
+    swg_alignment *mq_bd = NULL;
+    size_t bd_first = 0, bd_n = 0;
 next_query:
     if (cands) { /* this record's entries: marks for the printing, scores by entry */
         if (qi > 0)
@@ -760,6 +775,23 @@ next_query:
         free(al);
         free(ops);
         free(line);
+    }
+    if (bounds && n_hits > 0) {
+        /* the first record against the context's query; the others came with their chunk (below) */
+        swg_alignment *bd = NULL;
+        if (qi == 0) {
+            bd = (swg_alignment *)calloc(n_hits, sizeof *bd);
+            if (!bd) return leave(EXIT_FAILURE);
+            if (swg_align_bounds(ctx, sdb, hits, n_hits, bd) != SWG_OK) {
+                fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
+                return leave(EXIT_FAILURE);
+            }
+        }
+        const swg_alignment *bd_q = bd ? bd : mq_bd + (qi - bd_first) * (size_t)topk;
+        for (size_t i = 0; i < n_hits; i++)
+            printf("Bounds #%lu: entry %u score %d query %u..%u entry %u..%u length %u\n", (unsigned long)i, bd_q[i].index,
+                   bd_q[i].score, bd_q[i].q_begin, bd_q[i].q_end, bd_q[i].d_begin, bd_q[i].d_end, bd_q[i].n_ops);
+        free(bd);
     }
     if (allq && ++qi < q.n) {
         /* The database stays resident; the remaining queries go through swg_search_multi in chunks (one
@@ -894,6 +926,30 @@ next_query:
             }
             al_records += al_n;
         }
+        if (bounds && qi >= bd_first + bd_n) {
+            /* the coordinates of the chunk's hits from this query on, in one swg_align_bounds_multi call (with --pssmlist
+             * swg_align_bounds_multi_pssm); a call takes at most 2^20 hits */
+            const size_t left = chunk_first + chunk_n - qi, kk = (size_t)topk;
+            size_t per = ((size_t)1 << 20) / kk;
+            if (per < 1) per = 1;
+            bd_first = qi;
+            bd_n = left < per ? left : per;
+            free(mq_bd);
+            mq_bd = (swg_alignment *)calloc(bd_n * kk, sizeof *mq_bd);
+            if (!mq_bd) {
+                fprintf(stderr, "Error: out of memory\n");
+                return leave(EXIT_FAILURE);
+            }
+            const double t0 = now_ms();
+            const int rc = plist ? swg_align_bounds_multi_pssm(ctx, sdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff + at, bd_n,
+                                                               mq_hits + at * kk, kk, mq_nhits + at, mq_bd)
+                                 : swg_align_bounds_multi(ctx, sdb, qx, qoff + at, bd_n, mq_hits + at * kk, kk, mq_nhits + at, mq_bd);
+            if (rc != SWG_OK) {
+                fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
+                return leave(EXIT_FAILURE);
+            }
+            if (timing) fprintf(stderr, "[timing] bounds of %lu records in one call: %.3f ms\n", (unsigned long)bd_n, now_ms() - t0);
+        }
         total_ms = chunk_ms;
         qname = q.names + q.name_off[qi];
         goto next_query;
@@ -931,6 +987,7 @@ next_query:
     free(hits);
     free(mq_al);
     free(mq_ops);
+    free(mq_bd);
     phase("release (context, buffers)");
     return leave(EXIT_SUCCESS);
 }
