@@ -267,6 +267,34 @@ int swg_search_begin(swg_ctx *ctx, const swg_db *db, int want_scores, size_t k, 
 int swg_search_end(swg_ctx *ctx, int ticket, int32_t *scores_out, swg_hit *topk_out, size_t *n_hits,
                    swg_stats *stats);
 
+/* Hits-only pruning.  A search that returns hits and no score array (k > 0, want_scores == 0) need not fill a pair of
+ * sequences that cannot be among the k best: with non-positive gap scores a sequence scores at most the sum, over its
+ * residues, of each residue's best score against any query column, and once k sequences are known to score T or more a
+ * sequence whose sum is below T is out whatever the ties.  The 16-bit fill of the lane groups' work queue then runs in
+ * stages and skips, from the second stage on, the pairs behind the last one whose bound reaches the
+ * k-th best score so far.  Hits are exactly those of the unpruned search.  swg_stats is unchanged by it (cells stays the
+ * nominal lq x residues); swg_prune_last tells what the search LAST ENDED on the context left out:
+ *   pruned             1: the search ran in stages; 0: it did not (the rest is then 0 except pair_rows)
+ *   threshold          the last T the stages used (scores of 4095 and more count as 4095)
+ *   pairs_skipped      pairs of sequences no launch filled
+ *   pair_rows_skipped  their rows, in whole 4-row token blocks (two reset rows + the longer sequence of the pair)
+ *   pair_rows          the rows of all pairs of the fill, in the same unit
+ * Options (swg_set_option): "prune" 0 off | 1 (default) auto: hits-only searches on the 16-bit lane-group work queue with
+ * non-positive gap scores, one class and one cell form, whose range spans several launch segments (a database of some
+ * millions of sequences) and has at least 4 x prune_head pairs per resident lane group; never a gapless search, a batch call (swg_search_multi*, swg_search_lists*) or anything on other engines |
+ * 2 DIAGNOSTIC, for tests: prune wherever it is structurally possible, ignoring the size rule, and also when scores are
+ * requested -- the sequences of skipped pairs then report a score of 0, which is NOT their score.  "prune_head" (default 4):
+ * under "prune" 2 a range of one segment runs its longest pairs first, unpruned -- at least k sequences and prune_head pairs per lane
+ * group -- so that the rest has a threshold to be cut by. */
+typedef struct swg_prune_info {
+    uint64_t pairs_skipped;
+    uint64_t pair_rows_skipped;
+    uint64_t pair_rows;
+    uint32_t threshold;
+    int32_t pruned;
+} swg_prune_info;
+int swg_prune_last(const swg_ctx *ctx, swg_prune_info *out);
+
 /* Many queries against one resident database in ONE pass of the hot path.  The reference takes a
  * single query per run (src/alignment_cmdline.c:381-396); its report says the design "extends
  * naturally" to many-to-many (Final Report p.7).  Query i is queries[q_offsets[i] .. q_offsets[i+1])

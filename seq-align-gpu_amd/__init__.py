@@ -31,7 +31,7 @@ SWG_ERR_STATE, SWG_ERR_RESIDUE, SWG_ERR_IO, SWG_ERR_NODEVICE = -4, -5, -6, -7
 
 # every symbol declared in include/swg.h and include/swg_host.h
 ABI_SYMBOLS = [
-    "swg_create", "swg_destroy", "swg_last_error", "swg_global_error", "swg_abi_version",
+    "swg_create", "swg_destroy", "swg_last_error", "swg_global_error", "swg_abi_version", "swg_prune_last",
     "swg_set_option", "swg_set_scoring", "swg_set_query", "swg_set_query_pssm", "swg_db_pack", "swg_db_pack_shard", "swg_db_pack_shards", "swg_db_upload", "swg_db_view",
     "swg_db_free", "swg_db_save", "swg_db_load", "swg_db_count", "swg_db_total_count", "swg_db_residues",
     "swg_db_packed_bytes", "swg_db_order", "swg_search", "swg_search_begin", "swg_search_end", "swg_search_multi",
@@ -216,6 +216,9 @@ _sig("swg_debug_list_plan", C.c_int, [C.c_size_t, C.c_uint32, C.c_int, _vp, _vp]
 _sig("swg_debug_pair_tokens", C.c_int, [_vp, _vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 _sig("swg_debug_view_ranks", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.POINTER(C.c_size_t)])
 _sig("swg_debug_list_jobs", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t), _vp])
+_sig("swg_prune_last", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_bound", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp])
+_sig("swg_debug_prune_plan", C.c_int, [_vp, _vp])
 _sig("swg_debug_list_deal", C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 
 
@@ -406,6 +409,46 @@ def debug_list_plan(lq, n_pairs_guess, n_cu=256, main=(32, 16, 4)):
     out = np.zeros(4, dtype=np.int32)
     _check(lib.swg_debug_list_plan(lq, n_pairs_guess, n_cu, m.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
     return {"K": int(out[0]), "G": int(out[1]), "W": int(out[2]), "passes": int(out[3])}
+
+
+def debug_prune_bound(rows, query, flat, offsets):
+    """Test hook (no device needed): the host mirror of the pruning bound.  rows: the 32 x 32 table with `query` the
+    index query, or an (lq, 32) PSSM with query None.  -> (colmax uint8[32], U uint64[n]) for the sequences
+    flat[offsets[i] .. offsets[i+1])."""
+    r, rp = _i8(rows)
+    lq = r.size // 32
+    qp = None
+    if query is not None:
+        q, qp = _i8(query)
+        lq = q.size
+    f, fp = _i8(flat)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = off.size - 1
+    cm = np.zeros(32, dtype=np.uint8)
+    u = np.zeros(max(n, 1), dtype=np.uint64)
+    _check(lib.swg_debug_prune_bound(rp, qp, lq, fp, off.ctypes.data_as(_vp), n, cm.ctypes.data_as(_vp), u.ctypes.data_as(_vp)))
+    return cm, u[:n]
+
+
+PRUNE_PLAN_KEYS = ("mode", "k", "want_scores", "gap_open", "gap_extend", "bits", "use_diag", "n_classes", "work_queue", "both_forms",
+                   "gapless", "batch", "range_pairs", "groups", "prune_head", "n_segments")
+
+
+def debug_prune_plan(**ask):
+    """Test hook (no device needed): what a search decides about pruning (swg_prune_plan).  Keyword arguments as
+    PRUNE_PLAN_KEYS; the defaults describe a hits-only search that is pruned: mode 1, k 100, gaps (-2, -1), 16-bit lane
+    groups off the work queue, one class, one form, 1 000 000 pairs in 8 segments on 1024 lane groups, prune_head 4.
+    -> (pruned, head pairs; 0: the stages are the segments)."""
+    d = dict(mode=1, k=100, want_scores=0, gap_open=-2, gap_extend=-1, bits=16, use_diag=1, n_classes=1, work_queue=1, both_forms=0,
+             gapless=0, batch=0, range_pairs=1000000, groups=1024, prune_head=4, n_segments=8)
+    unknown = set(ask) - set(d)
+    if unknown:
+        raise TypeError("debug_prune_plan: unknown arguments %s" % sorted(unknown))
+    d.update(ask)
+    a = np.array([int(d[k]) for k in PRUNE_PLAN_KEYS], dtype=np.int64)
+    out = np.zeros(2, dtype=np.int64)
+    _check(lib.swg_debug_prune_plan(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
+    return bool(out[0]), int(out[1])
 
 
 LAUNCH_FAMILIES = ("dyn", "lists", "q32", "qq", "streams", "systolic")
@@ -847,6 +890,19 @@ class Context:
         qoff[1:] = np.cumsum([r.shape[0] for r in rows])
         pflat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 32)), dtype=np.int8)
         return self._align_multi(lib.swg_align_bounds_multi_pssm, db, pflat, qoff, hits, False, None, bounds=True)
+
+    def prune_last(self):
+        """What the search last ended on this context left out (swg_prune_last) -> dict: pruned (bool), threshold (the
+        last T), pairs_skipped, pair_rows_skipped and pair_rows (rows in whole 4-row token blocks)."""
+
+        class _Info(C.Structure):
+            _fields_ = [("pairs_skipped", C.c_uint64), ("pair_rows_skipped", C.c_uint64), ("pair_rows", C.c_uint64),
+                        ("threshold", C.c_uint32), ("pruned", C.c_int32)]
+
+        i = _Info()
+        _check(lib.swg_prune_last(self.handle, C.cast(C.byref(i), _vp)), self.handle)
+        return {"pruned": bool(i.pruned), "threshold": int(i.threshold), "pairs_skipped": int(i.pairs_skipped),
+                "pair_rows_skipped": int(i.pair_rows_skipped), "pair_rows": int(i.pair_rows)}
 
     def debug_bounds_last(self):
         """What the last align_bounds* call of this context did (swg_debug_bounds_last) -> dict: pairs on the bounds kernel,

@@ -325,6 +325,13 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
         if (value < 0 || value > (long)SWG_DYN_SEG_BLOCKS)
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "segment_blocks must be 0 (default) .. 2^26-64");
         ctx->opt_seg_blocks = value ? (uint32_t)value : SWG_DYN_SEG_BLOCKS;
+    } else if (!strcmp(key, "prune")) {
+        if (value < 0 || value > 2)
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune must be 0 (off), 1 (auto) or 2 (wherever it is structurally possible: diagnostic)");
+        ctx->opt_prune = value;
+    } else if (!strcmp(key, "prune_head")) {
+        if (value < 0 || value > 4096) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_head must be 0..4096 (pairs per lane group)");
+        ctx->opt_prune_head = value;
     } else if (!strcmp(key, "q32_waves")) {
         ctx->opt_q32_waves = value;
     } else if (!strcmp(key, "wave_budget")) {
@@ -458,6 +465,7 @@ void swg_db_release_search_state(swg_db *db)
         (void)hipFree(b.d_counters);
         (void)hipFree(b.d_keys);
         (void)hipFree(b.d_hist);
+        (void)hipFree(b.d_pair_bound);
         b = swg_db::Bufs();
     }
     (void)hipFree(db->ptok.d_tok);
@@ -485,6 +493,7 @@ void swg_db_release_search_state(swg_db *db)
     db->d_counters = nullptr;
     db->d_keys = nullptr;
     db->d_hist = nullptr;
+    db->d_pair_bound = nullptr;
 }
 
 void swg_db_release_device(swg_db *db)
@@ -519,6 +528,7 @@ static int select_bufs(swg_ctx *ctx, swg_db *db, int slot)
     db->d_counters = b.d_counters;
     db->d_keys = b.d_keys;
     db->d_hist = b.d_hist;
+    db->d_pair_bound = b.d_pair_bound;
     return SWG_OK;
 }
 
@@ -1089,7 +1099,10 @@ static void dyn_batch_zones(const swg_ctx *ctx, const SwgPairTokens &T, SwgDiagD
 
 // Launches the fill of one work plan.  Events: ev[1] before, ev[2] after on the main stream;
 // with a long class also ev[5] (bulk end) and ev[7] (long end).
-static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, int go, int ge, bool *two_ends)
+// prune (or null: the whole range, pass by pass): a pruned search runs stage by stage -- all passes of a
+// stage, then the threshold so far and the next stage's cut, both on the fill's stream with no host wait.
+static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, int go, int ge, bool *two_ends,
+                       const SwgPrunePlan *prune = nullptr, size_t prune_k = 0)
 {
     hipStream_t s = ctx->stream;
     *two_ends = false;
@@ -1159,6 +1172,70 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
             const bool split = c == 0 && wk.n_classes == 1 && form != 2 && pl.f16_from > class_begin && pl.f16_from < class_end;
             bool first_launch = true;
             int launches = 0, f16_launches = 0;
+            // (plan_prune decided; what swg_prune_last reports is what was launched)
+            const bool pruned = prune && prune->on && c == 0 && wk.n_classes == 1 && !split && db->d_pair_bound;
+            if (c == 0) ctx->cur->pruned = pruned;
+            // one launch: pass `pass` over the pairs [b, en) of segment sg on the cells pform
+            auto launch_one = [&](int pass, const std::pair<uint32_t, uint32_t> &sg, uint32_t b, uint32_t en, int pform, const uint8_t *prof,
+                                  bool f16_part) -> int {
+                // one launch per pass: the kernel boundary is what lets any lane group take any pair
+                q.profile = prof + (size_t)pass * slice;
+                q.edge_in = pass > 0 ? T.d_edge[(pass - 1) & 1] : nullptr;
+                q.edge_out = pass + 1 < pl.npass ? T.d_edge[pass & 1] : nullptr;
+                if (!first_launch)
+                    HIP_TRY(ctx, hipMemsetAsync(q.queue, 0, (size_t)SWG_DYN_SHARDS * SWG_DYN_SHARD_STRIDE * 4, qs));
+                first_launch = false;
+                q.q_begin = b;
+                q.q_end = en;
+                if (cut) {
+                    q.seg_origin = T.pair_blocks_prefix[sg.first];
+                    q.seg_blocks = T.pair_blocks_prefix[sg.second] - q.seg_origin;
+                }
+                const int variant = pass + 1 == pl.npass && pl.npass > 1 && pl.last_variant >= 0 ? pl.last_variant : pl.variant;
+                const int wgs_c = diag_class_workgroups(ctx, db, wk, c);
+                // (with long_helps the long class's kernel reads the bulk's counters too, as single pairs: no zones then)
+                if (!(ctx->opt_long_helps && wk.n_classes == 2)) dyn_batch_zones(ctx, T, &q, (uint64_t)wgs_c * pl.W * (64 / pl.G), swg_diag_variant_info(variant).K, pl.G, pform);
+                HIP_TRY(ctx, swg_launch_diag_dyn(variant, edges, pform, pl.W, wgs_c, q, qs, 1, fma));
+                ++launches;
+                if (f16_part) ++f16_launches;
+                return SWG_OK;
+            };
+            if (pruned) {
+                // The stages: the segments, or the head and the rest of a single one.  The bound of every pair first;
+                // then, before each stage but the first, the K-th best score so far (every entry of d_scores is at most
+                // its sequence's true score at a kernel boundary) and the stage's cut, held for all its passes.
+                // A cut stage's launches are LIST launches: the list is the pair ids in order, from the stage's first
+                // pair, and its device-side length is the cut -- the kernel reads it once at entry, leaves before it
+                // loads the profile when it is 0, and hands out exactly those pairs in every pass (no batch claims in
+                // list mode).  So the fill kernels are the unpruned search's, instruction for instruction.
+                uint32_t *cw = db->d_counters;
+                const uint32_t n_pairs_all = (uint32_t)swg_db_pair_count(db);
+                uint32_t *d_ids = db->d_pair_bound + n_pairs_all;
+                HIP_TRY(ctx, swg_launch_pair_bound(T.d_tok, T.d_pair_off, n_pairs_all, ctx->prune_colmax, db->d_pair_bound, d_ids, qs));
+                struct Stage { uint32_t b, en; size_t sg; };
+                std::vector<Stage> stages;
+                for (size_t i = 0; i < segs.size(); ++i) {
+                    const uint32_t mid = segs.size() == 1 && prune->head_pairs > 0 ? std::min(segs[i].second, segs[i].first + prune->head_pairs) : segs[i].second;
+                    stages.push_back(Stage{segs[i].first, mid, i});
+                    if (mid < segs[i].second) stages.push_back(Stage{mid, segs[i].second, i});
+                }
+                for (size_t si = 0; si < stages.size(); ++si) {
+                    const Stage &st = stages[si];
+                    q.list = nullptr, q.list_count = nullptr;
+                    if (si > 0) {
+                        HIP_TRY(ctx, swg_launch_prune_threshold(db->d_scores, db->d_order, (uint32_t)((size_t)db->n_bins * SWG_BIN), (uint32_t)prune_k,
+                                                                db->d_hist, cw + SWG_PRUNE_WORD_T, qs));
+                        HIP_TRY(ctx, swg_launch_prune_cut(db->d_pair_bound, T.d_pair_off, st.b, st.en, cw + SWG_PRUNE_WORD_T, cw + SWG_PRUNE_WORD_CUT, qs));
+                        q.list = d_ids + st.b;
+                        q.list_count = cw + SWG_PRUNE_WORD_CUT;
+                    }
+                    for (int pass = 0; pass < pl.npass; ++pass) {
+                        const int rc1 = launch_one(pass, segs[st.sg], st.b, st.en, form, ctx->d_profile[diag_profile_slot(pl, c)], false);
+                        if (rc1 != SWG_OK) return rc1;
+                    }
+                }
+                q.list = nullptr, q.list_count = nullptr;
+            } else
             for (int part = 0; part < (split ? 2 : 1); ++part) {
                 const int pform = split && part == 1 ? 2 : form;
                 const uint32_t part_begin = split && part == 1 ? pl.f16_from : class_begin;
@@ -1168,29 +1245,11 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
                 q.ge = gap_word(pform, ge);
                 if (split && part == 1) HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[5], qs));
                 for (int pass = 0; pass < pl.npass; ++pass) {
-                    // one launch per pass: the kernel boundary is what lets any lane group take any pair
-                    q.profile = prof + (size_t)pass * slice;
-                    q.edge_in = pass > 0 ? T.d_edge[(pass - 1) & 1] : nullptr;
-                    q.edge_out = pass + 1 < pl.npass ? T.d_edge[pass & 1] : nullptr;
                     for (const std::pair<uint32_t, uint32_t> &sg : segs) {
                         const uint32_t b = std::max(sg.first, part_begin), en = std::min(sg.second, part_end);
                         if (b >= en) continue;
-                        if (!first_launch)
-                            HIP_TRY(ctx, hipMemsetAsync(q.queue, 0, (size_t)SWG_DYN_SHARDS * SWG_DYN_SHARD_STRIDE * 4, qs));
-                        first_launch = false;
-                        q.q_begin = b;
-                        q.q_end = en;
-                        if (cut) {
-                            q.seg_origin = T.pair_blocks_prefix[sg.first];
-                            q.seg_blocks = T.pair_blocks_prefix[sg.second] - q.seg_origin;
-                        }
-                        const int variant = pass + 1 == pl.npass && pl.npass > 1 && pl.last_variant >= 0 ? pl.last_variant : pl.variant;
-                        const int wgs_c = diag_class_workgroups(ctx, db, wk, c);
-                        // (with long_helps the long class's kernel reads the bulk's counters too, as single pairs: no zones then)
-                        if (!(ctx->opt_long_helps && wk.n_classes == 2)) dyn_batch_zones(ctx, T, &q, (uint64_t)wgs_c * pl.W * (64 / pl.G), swg_diag_variant_info(variant).K, pl.G, pform);
-                        HIP_TRY(ctx, swg_launch_diag_dyn(variant, edges, pform, pl.W, wgs_c, q, qs, 1, fma));
-                        ++launches;
-                        if (split && part == 1) ++f16_launches;
+                        const int rc1 = launch_one(pass, sg, b, en, pform, prof, split && part == 1);
+                        if (rc1 != SWG_OK) return rc1;
                     }
                 }
             }
@@ -2134,7 +2193,8 @@ static int enqueue_fill(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P, SwgSlo
     HIP_TRY(ctx, swg_launch_zero2(db->d_scores, n_slots * 4, db->d_counters, SWG_COUNTER_BYTES, s)); // (one launch, not two memsets)
     S->two_ends = false;
     S->fill_launches = 0;
-    if (P.use_diag) return launch_diag(ctx, db, P.wk, P.go, P.ge, &S->two_ends);
+    S->pruned = false;
+    if (P.use_diag) return launch_diag(ctx, db, P.wk, P.go, P.ge, &S->two_ends, &P.prune, S->k);
     if (P.use_q32)
         return launch_q32(ctx, db, P.wk32, P.go, P.ge, nullptr, nullptr, 0, db->d_counters + SWG_QUEUE_WORD(0), &S->two_ends, true, P.exact32);
     if (!(P.bits == 32 && P.use_diag32)) return launch_systolic(ctx, db, P.main_pl, P.go, P.ge);
@@ -2224,6 +2284,59 @@ static int enqueue_rescore(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P, Swg
     return SWG_OK;
 }
 
+// Whether this search is pruned (swg_prune_plan has the rules), decided once the plan stands; a pruned search gets the
+// bound's table for the current query and scoring (built on the host when either has changed; it travels to the bound
+// kernel as a launch argument) and its slot's buffer of pair bounds.
+static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgSearchPlan *P)
+{
+    P->prune = SwgPrunePlan();
+    if (!P->use_diag || P->bits != 16) return SWG_OK;
+    const SwgDiagWork &wk = P->wk;
+    const SwgDiagPlan &pl = wk.plan[0];
+    SwgPruneAsk a;
+    a.mode = (int)ctx->opt_prune;
+    a.k = k;
+    a.want_scores = want_scores;
+    a.gap_open = ctx->gap_open;
+    a.gap_extend = ctx->gap_extend;
+    a.bits = P->bits;
+    a.use_diag = P->use_diag;
+    a.n_classes = wk.n_classes;
+    a.work_queue = diag_class_is_dynamic(ctx, db, pl) && db->ptok.ok;
+    a.both_forms = P->split_at != 0u;
+    a.gapless = P->gapless;
+    a.batch = ctx->in_batch;
+    a.prune_head = ctx->opt_prune_head;
+    if (a.mode == 0 || !a.work_queue || wk.n_classes != 1) return SWG_OK;
+    a.range_pairs = wk.pair_end[0] - wk.pair_begin[0];
+    a.groups = diag_class_streams(ctx, db, wk, 0);
+    const int form = diag_class_form(ctx, db, pl);
+    std::vector<std::pair<uint32_t, uint32_t>> segs;
+    bool cut = false;
+    if (!token_segments(db->ptok, (uint32_t)wk.pair_begin[0], (uint32_t)wk.pair_end[0], ctx->opt_seg_blocks, pl.npass > 1 || form == 1, &segs, &cut))
+        return SWG_OK; // (launch_diag reports it)
+    a.n_segments = segs.size();
+    P->prune = swg_prune_plan(a);
+    if (!P->prune.on) return SWG_OK;
+    if (ctx->prune_colmax_epoch != ctx->epoch) {
+        ctx->prune_colmax = ctx->query_pssm ? swg_prune_colmax(ctx->pssm.data(), nullptr, ctx->query_len())
+                                            : swg_prune_colmax(&ctx->sub[0][0], ctx->query.data(), ctx->query_len());
+        ctx->prune_colmax_epoch = ctx->epoch;
+    }
+    // (the bounds, then the pair ids a cut stage's list launches read: two words per pair)
+    swg_db::Bufs &b = db->bufs[ctx->cur - ctx->slots];
+    const size_t n_pairs = (size_t)swg_db_pair_count(db);
+    if (!b.d_pair_bound || b.pair_bound_cap < n_pairs) {
+        (void)hipFree(b.d_pair_bound);
+        b.d_pair_bound = nullptr;
+        b.pair_bound_cap = 0;
+        HIP_TRY(ctx, hipMalloc(&b.d_pair_bound, std::max<size_t>(8, n_pairs * 8)));
+        b.pair_bound_cap = n_pairs;
+    }
+    db->d_pair_bound = b.d_pair_bound;
+    return SWG_OK;
+}
+
 // Top-K and read-out go to their own stream: the next search's fill is queued right behind this
 // one's on the main stream and these small kernels run beside its start instead of holding it
 // up (the output buffers belong to this in-flight slot until swg_search_end).  swg_search_end waits for ev_done.
@@ -2289,6 +2402,7 @@ static int search_begin(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, bo
     S->plan = SwgSearchPlan(); // (bits = 0 marks "nothing queued" for an empty database)
     if (db->n_bins == 0) return SWG_OK;
     if ((rc = plan_search(ctx, db, allow_autotune, &S->plan)) != SWG_OK) return rc;
+    if ((rc = plan_prune(ctx, db, want_scores, k, &S->plan)) != SWG_OK) return rc;
     if ((rc = prepare_search(ctx, db, S->plan)) != SWG_OK) return rc;
     if ((rc = enqueue_fill(ctx, db, S->plan, S)) != SWG_OK) return rc;
     if ((rc = enqueue_rescore(ctx, db, S->plan, S)) != SWG_OK) return rc;
@@ -2389,6 +2503,13 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
         // 4's share with 4 % of the pair rows flagged: f16 + re-run 191 ms, int16 cells alone 200.
         if (some_f16 && !P.gapless && (uint64_t)h_counters[6] * 16ull * 2ull * 16ull > db->residues + 2ull * db->n_local) db->f16_veto_epoch = P.epoch;
     }
+    // what a pruned search left out (swg_prune_last): from the counter words that came back with the search
+    ctx->prune_last[0] = S->pruned ? 1u : 0u;
+    ctx->prune_last[1] = S->pruned ? h_counters[SWG_PRUNE_WORD_CUT + 1u] : 0u;
+    ctx->prune_last[2] = S->pruned ? 4ull * ((uint64_t)h_counters[SWG_PRUNE_WORD_CUT + 2u] | ((uint64_t)h_counters[SWG_PRUNE_WORD_CUT + 3u] << 32)) : 0u;
+    ctx->prune_last[3] = P.use_diag && db->ptok.ok && !db->ptok.pair_blocks_prefix.empty()
+                             ? 4ull * (db->ptok.pair_blocks_prefix[wk.pair_end[0]] - db->ptok.pair_blocks_prefix[wk.pair_begin[0]]) : 0u;
+    ctx->prune_last[4] = S->pruned ? h_counters[SWG_PRUNE_WORD_T] : 0u;
     st.classes_overlapped = -1;
     if (P.use_diag && wk.n_classes == 2 && wk.plan[0].npass == 1 && wk.plan[1].npass == 1) {
         // did the two classes run side by side?  (stamps: complement of the earliest start, latest end)
@@ -2468,6 +2589,17 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
     }
     st.topk_ms = topk_dev_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = st;
+    return SWG_OK;
+}
+
+extern "C" int swg_prune_last(const swg_ctx *ctx, swg_prune_info *out)
+{
+    if (!ctx || !out) return SWG_ERR_ARG;
+    out->pruned = (int32_t)ctx->prune_last[0];
+    out->threshold = (uint32_t)ctx->prune_last[4];
+    out->pairs_skipped = ctx->prune_last[1];
+    out->pair_rows_skipped = ctx->prune_last[2];
+    out->pair_rows = ctx->prune_last[3];
     return SWG_OK;
 }
 
@@ -2716,7 +2848,11 @@ namespace {
 struct KeptQuery { // the context's own query across a batch searched one by one
     bool pssm;
     std::vector<int8_t> bytes;
-    explicit KeptQuery(const swg_ctx *ctx) : pssm(ctx->query_pssm), bytes(ctx->query_pssm ? ctx->pssm : ctx->query) {}
+    swg_ctx *owner; // (a batch's searches are never pruned: in_batch for as long as this object lives)
+    explicit KeptQuery(swg_ctx *ctx) : pssm(ctx->query_pssm), bytes(ctx->query_pssm ? ctx->pssm : ctx->query), owner(ctx) { ctx->in_batch = true; }
+    ~KeptQuery() { owner->in_batch = false; }
+    KeptQuery(const KeptQuery &) = delete;
+    KeptQuery &operator=(const KeptQuery &) = delete;
     int restore(swg_ctx *ctx, int rc) const
     {
         if (!bytes.empty()) {
@@ -2993,6 +3129,7 @@ static int search_multi_impl(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, i
     memset(&st, 0, sizeof st);
     int rc = validate_batch(ctx, db, mq, topk_out, k, &st);
     if (rc != SWG_OK) return rc;
+    memset(ctx->prune_last, 0, sizeof ctx->prune_last); // (swg_prune_last: a batch call ends with nothing pruned)
     if (stats) *stats = st;
     if (mq.n == 0) return SWG_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3516,6 +3653,7 @@ static int search_lists_impl(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, c
     memset(&st, 0, sizeof st);
     int rc = validate_batch(ctx, db, mq, topk_out, k, &st);
     if (rc != SWG_OK) return rc;
+    memset(ctx->prune_last, 0, sizeof ctx->prune_last); // (swg_prune_last: a batch call ends with nothing pruned)
     if (mq.n && (!c_off || (c_off[mq.n] > c_off[0] && !cand))) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: NULL argument", mq.fn);
     if (db->tokens_only)
         return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: a database built from 16-lane batches has no residue bytes to list candidates of", mq.fn);

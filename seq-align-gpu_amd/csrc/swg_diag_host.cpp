@@ -568,6 +568,90 @@ extern "C" int swg_debug_score_bound(const int8_t *rows, const int8_t *idx, size
     return SWG_OK;
 }
 
+// Hits-only pruning (declared in swg_host_internal.h).  The table of the bound: for every database residue
+// the best it can score against any column of the query, never below 0.  With non-positive gap scores a local alignment
+// matches each database residue at most once, at best with its best column, and gaps add nothing positive: a sequence
+// scores at most the sum of its residues' entries.  The padding residue 0 scores nothing.
+SwgColMax swg_prune_colmax(const int8_t *rows, const int8_t *idx, size_t lq)
+{
+    SwgColMax cm;
+    memset(&cm, 0, sizeof cm);
+    bool seen[32] = {false};
+    if (idx)
+        for (size_t i = 0; i < lq; ++i) seen[(uint8_t)idx[i] & 31] = true;
+    const size_t n_rows = idx ? 32 : lq;
+    for (size_t i = 0; i < n_rows; ++i) {
+        if (idx && !seen[i]) continue;
+        const int8_t *row = rows + 32 * i;
+        for (int r = 1; r < 32; ++r)
+            if (row[r] > (int)cm.v[r]) cm.v[r] = (uint8_t)row[r];
+    }
+    return cm;
+}
+
+uint64_t swg_prune_bound(const SwgColMax &cm, const int8_t *seq, size_t len)
+{
+    uint64_t u = 0;
+    for (size_t j = 0; j < len; ++j) u += cm.v[(uint8_t)seq[j] & 31];
+    return u;
+}
+
+// test hook: the table (32 bytes) and U of each of the n sequences flat[offsets[i] .. offsets[i+1]) (table indices)
+extern "C" int swg_debug_prune_bound(const int8_t *rows, const int8_t *idx, size_t lq, const int8_t *flat, const uint64_t *offsets, size_t n,
+                                     uint8_t *colmax_out, uint64_t *u_out)
+{
+    if (!rows || lq == 0 || (n > 0 && (!flat || !offsets || !u_out))) return SWG_ERR_ARG;
+    const SwgColMax cm = swg_prune_colmax(rows, idx, lq);
+    if (colmax_out) memcpy(colmax_out, cm.v, 32);
+    for (size_t i = 0; i < n; ++i) u_out[i] = swg_prune_bound(cm, flat + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+    return SWG_OK;
+}
+
+// Whether a search is pruned, and how its range is staged.  Pruned: hits only (k > 0 within the device top-K's capacity,
+// no score array -- mode 2 prunes with one, skipped sequences then report 0), non-positive gap scores on the 16-bit lane
+// groups' work queue, one class, one cell form, not a gapless search and not one query of a batch call.  A range of several
+// segments is staged by segment (head_pairs 0).  Mode 1 (auto) prunes such ranges only, and of those the ones with at
+// least 4 x prune_head pairs per lane group (under the default segment size every range of several segments is far above
+// that; the rule keeps test-sized segments unpruned): their stage order costs nothing but the small kernels between the
+// segments.  A range of ONE segment would have to be split into a head and a rest whose launches are list launches
+// (one more load per claim, no batch claims); whether that pays has not been measured, so only mode 2 (diagnostic) does
+// it: the head is the longest pairs -- at least k sequences and prune_head pairs per resident lane group, but no longer
+// than a quarter of the range, so that a database of a few thousand sequences still has a rest to cut.
+SwgPrunePlan swg_prune_plan(const SwgPruneAsk &a)
+{
+    SwgPrunePlan r;
+    if (a.mode == 0 || a.k == 0 || a.k > SWG_TOPK_CAND_CAP / 2 || (a.want_scores && a.mode != 2) || a.gap_open > 0 || a.gap_extend > 0 ||
+        a.bits != 16 || !a.use_diag || a.n_classes != 1 || !a.work_queue || a.both_forms || a.gapless || a.batch || a.range_pairs == 0 ||
+        a.prune_head < 0)
+        return r;
+    const uint64_t need = ((uint64_t)a.k + 1) / 2, per_group = (uint64_t)a.prune_head * std::max<uint64_t>(1, a.groups);
+    if (a.mode == 1 && (a.n_segments <= 1 || a.range_pairs < 4 * per_group)) return r;
+    uint64_t head = 0;
+    if (a.n_segments <= 1) {
+        head = std::max(need, std::min(per_group, a.range_pairs / 4));
+        if (head >= a.range_pairs) return r;
+    }
+    r.on = true;
+    r.head_pairs = (uint32_t)head;
+    return r;
+}
+
+// test hook: in[0..15] = mode, k, want_scores, gap_open, gap_extend, bits, use_diag, n_classes, work_queue, both_forms, gapless,
+// batch, range_pairs, groups, prune_head, n_segments; out[0..1] = pruned, head pairs
+extern "C" int swg_debug_prune_plan(const int64_t *in, int64_t *out)
+{
+    if (!in || !out || in[1] < 0 || in[12] < 0 || in[13] < 0 || in[15] < 0) return SWG_ERR_ARG;
+    SwgPruneAsk a;
+    a.mode = (int)in[0], a.k = (size_t)in[1], a.want_scores = in[2] != 0, a.gap_open = (int)in[3], a.gap_extend = (int)in[4];
+    a.bits = (int)in[5], a.use_diag = in[6] != 0, a.n_classes = (int)in[7], a.work_queue = in[8] != 0, a.both_forms = in[9] != 0;
+    a.gapless = in[10] != 0, a.batch = in[11] != 0, a.range_pairs = (uint64_t)in[12], a.groups = (uint64_t)in[13], a.prune_head = (long)in[14];
+    a.n_segments = (size_t)in[15];
+    const SwgPrunePlan r = swg_prune_plan(a);
+    out[0] = r.on ? 1 : 0;
+    out[1] = (int64_t)r.head_pairs;
+    return SWG_OK;
+}
+
 // Both 16-bit forms in one search (plan_search in swg_api.cpp): the length from which a sequence can reach the f16 cells' ceiling
 // as an exact copy of a stretch of the query -- such a copy scores qbound / lq per row on average, qbound being the
 // query's best possible total --, and where that length cuts the sorted pair order (kept per database and length).

@@ -184,12 +184,15 @@ struct swg_db {
                                         // [8..15] class stamps, [16] sequences the f16 fill flagged, [17] their pairs
         uint64_t *d_keys = nullptr;     // top-K candidate keys (SWG_TOPK_CAND_CAP)
         uint32_t *d_hist = nullptr;     // top-K score histogram
+        uint32_t *d_pair_bound = nullptr; // a pruned search's score bound per pair, then the pair ids in order (allocated by the first one)
+        size_t pair_bound_cap = 0;        // pairs it has room for
     } bufs[4];
     int32_t *d_scores = nullptr;
     uint32_t *d_list = nullptr;
     uint32_t *d_counters = nullptr;
     uint64_t *d_keys = nullptr;
     uint32_t *d_hist = nullptr;
+    uint32_t *d_pair_bound = nullptr;
 };
 
 // The score ceilings of the cell forms, and the largest gap magnitude the packed-f16 cells hold as an exact integer.
@@ -221,6 +224,40 @@ struct SwgScoreBound {
 SwgScoreBound swg_score_bound(const int8_t *rows, const int8_t *idx, size_t lq, uint64_t longest);
 // test hook: out[0..2] = qbound, smax, bound
 extern "C" int swg_debug_score_bound(const int8_t *rows, const int8_t *idx, size_t lq, uint64_t longest, uint64_t *out);
+
+// Hits-only pruning (swg_diag_host.cpp, host only): the table of the score bound (rows / idx as
+// swg_score_bound takes them), U of one sequence of table indices, and what a search decides about it.
+SwgColMax swg_prune_colmax(const int8_t *rows, const int8_t *idx, size_t lq);
+uint64_t swg_prune_bound(const SwgColMax &cm, const int8_t *seq, size_t len);
+struct SwgPruneAsk {
+    int mode = 1; // option "prune": 0 off, 1 auto, 2 wherever it is structurally possible (diagnostic)
+    size_t k = 0;
+    bool want_scores = false;
+    int gap_open = 0, gap_extend = 0;
+    int bits = 16;
+    bool use_diag = true;
+    int n_classes = 1;
+    bool work_queue = true;  // the class runs off the lane groups' work queue
+    bool both_forms = false; // the wide / int16 + f16 split of one class
+    bool gapless = false;
+    bool batch = false;      // one query of swg_search_multi* / swg_search_gapless_multi* / a list's fall-back
+    uint64_t range_pairs = 0, groups = 0; // the class's pairs, the lane groups resident on the device
+    long prune_head = 4;     // option "prune_head"
+    size_t n_segments = 1;   // launches per pass (token_segments)
+};
+struct SwgPrunePlan {
+    bool on = false;
+    uint32_t head_pairs = 0; // one segment: pairs of the first stage; 0: the stages are the segments
+};
+SwgPrunePlan swg_prune_plan(const SwgPruneAsk &a);
+extern "C" int swg_debug_prune_bound(const int8_t *rows, const int8_t *idx, size_t lq, const int8_t *flat, const uint64_t *offsets, size_t n,
+                                     uint8_t *colmax_out, uint64_t *u_out);
+extern "C" int swg_debug_prune_plan(const int64_t *in, int64_t *out);
+// the words of a search's counter block (swg_db::Bufs::d_counters) a pruned search uses: the threshold so far and the
+// threshold kernel's status word, then what swg_launch_prune_cut writes: the pairs the stage takes, the pairs skipped so
+// far, their token blocks (64 bits)
+#define SWG_PRUNE_WORD_T 18u
+#define SWG_PRUNE_WORD_CUT 20u
 
 // Geometry of the systolic engine (bin-based kernels) for one query length.
 struct SwgSystolicPlan {
@@ -258,6 +295,7 @@ struct SwgSearchPlan {
     SwgDiagWork wk, wk32;            // lane groups: the 16-bit fill; the int32 work-queue fill of the whole database
     SwgSystolicPlan main_pl, re_pl;  // systolic engine: the fill; the int32 re-score
     int npass32 = 0;                 // passes of the bin-based int32 kernel
+    SwgPrunePlan prune;              // hits-only pruning of the 16-bit fill
 };
 
 // Everything a query batch (swg_search_multi, swg_search_multi_pssm) decides before it queues anything: plan_batch
@@ -304,6 +342,7 @@ struct SwgSlot {
     size_t k = 0, first_chunk = 0;
     bool want_scores = false, dev_topk = false, need_scores = false, two_ends = false;
     int fill_launches = 0; // launches of the bulk class's fill kernel (passes x segments)
+    bool pruned = false;   // the fill was launched stage by stage with cuts (launch_diag)
     int fill_f16_launches = 0; // both forms in one class: those of them that ran the f16 cells
     swg_stats st;
     uint64_t *h_cand = nullptr;     // pinned, SWG_TOPK_CAND_CAP keys
@@ -358,6 +397,12 @@ struct swg_ctx {
     long opt_bounds_groups = 0; // lane groups of a bounds launch (swg_align_bounds*), 0: auto (option "bounds_groups": tests)
     uint32_t bounds_last[4] = {0, 0, 0, 0}; // the last bounds call: pairs on its kernel, pairs on the fallback, its launches, its column limit
     long opt_batch = 8, opt_batch_blocks = 0; // work queue: pairs one request claims where pairs are short (blocks; 0: about 40 us of work, from the geometry)
+    long opt_prune = 1, opt_prune_head = 4; // hits-only pruning (options "prune", "prune_head": swg.h)
+    bool in_batch = false;                  // a batch call is searching its queries one after another: never pruned
+    // the search last ended on this context: pruned or not, pairs skipped, their token blocks, the range's, the last threshold
+    uint64_t prune_last[5] = {0, 0, 0, 0, 0};
+    SwgColMax prune_colmax;                 // the bound's table for the current (query, scoring) ...
+    uint64_t prune_colmax_epoch = 0;        // ... epoch (0: not built)
     uint32_t opt_seg_blocks = SWG_DYN_SEG_BLOCKS; // token blocks per launch of the multi-pass fill (option "segment_blocks": tests)
     // device state
     int8_t *d_sub = nullptr;

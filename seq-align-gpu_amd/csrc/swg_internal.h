@@ -300,6 +300,23 @@ hipError_t swg_launch_collect_saturated(const int32_t *d_scores, uint32_t n_slot
 hipError_t swg_launch_topk(const int32_t *d_scores, const uint32_t *d_order, uint32_t n_slots, uint32_t k,
                            uint32_t *d_hist, uint32_t *d_thr, uint64_t *d_cand, uint32_t cap, uint32_t *d_count,
                            hipStream_t stream);
+// Hits-only pruning.  colmax[r] = max(0, best score of database residue r against any query column):
+// a sequence's local score is at most the sum of colmax over its residues (non-positive gap scores).
+struct SwgColMax {
+    uint8_t v[32]; // [0], the padding residue, is 0
+};
+// d_bound[p] = max(U_x, U_y) of pair p, from the pair tokens (what the fill itself reads; reset and padding rows add 0);
+// d_ids[p] = p, the list a cut stage's launches take their pairs from
+hipError_t swg_launch_pair_bound(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, const SwgColMax &cm,
+                                 uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream);
+// d_thr[0] = the k-th largest entry of d_scores (clamped to 4095; 0 with fewer than k entries): swg_topk_hist_kernel and
+// swg_topk_threshold_kernel on `stream`; d_thr[1] is written too (the status word, not read)
+hipError_t swg_launch_prune_threshold(const int32_t *d_scores, const uint32_t *d_order, uint32_t n_slots, uint32_t k, uint32_t *d_hist,
+                                      uint32_t *d_thr, hipStream_t stream);
+// With cut = 1 + the last pair of [begin, end) with d_bound >= *d_thr, or begin: d_out[0] = cut - begin (the pairs the
+// stage's launches take), d_out[1] += the pairs behind the cut, (uint64 at d_out[2]) += their token blocks
+hipError_t swg_launch_prune_cut(const uint32_t *d_bound, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, const uint32_t *d_thr,
+                                uint32_t *d_out, hipStream_t stream);
 // ... and for the n_queries score rows of a batch (swg_search_multi) at once: d_hist[n_queries][4096],
 // d_meta[n_queries][4] = {threshold, status, candidate count, -}, d_cand[n_queries][cap]
 #define SWG_TOPK_MULTI_CAP 1024u

@@ -2784,6 +2784,102 @@ hipError_t swg_launch_topk_multi(const int32_t *d_scores, uint64_t score_stride,
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// hits-only pruning: the score bound of every pair, the threshold so far, the cut of a stage
+// ---------------------------------------------------------------------------
+// Sixteen lanes per pair walk its token blocks (256 consecutive bytes per step) and add up, for each of the pair's two
+// sequences, the best score each residue can get against any query column.  Reset rows and the rows past a sequence's
+// end hold the padding residue, whose entry is 0.
+__global__ __launch_bounds__(256) void swg_pair_bound_kernel(const uint4 *tok, const uint32_t *pair_off, uint32_t n_pairs, SwgColMax cm,
+                                                             uint32_t *bound, uint32_t *ids)
+{
+    __shared__ uint32_t t[32];
+    if (threadIdx.x < 32u) t[threadIdx.x] = cm.v[threadIdx.x];
+    __syncthreads();
+    const uint32_t p = blockIdx.x * 16u + (threadIdx.x >> 4), l = threadIdx.x & 15u;
+    uint32_t ux = 0u, uy = 0u;
+    if (p < n_pairs) {
+        const uint32_t e = pair_off[p + 1u];
+        for (uint32_t b = pair_off[p] + l; b < e; b += 16u) {
+            const uint4 k = tok[b];
+            ux += t[(k.x >> 3) & 31u] + t[(k.y >> 3) & 31u] + t[(k.z >> 3) & 31u] + t[(k.w >> 3) & 31u];
+            uy += t[(k.x >> 11) & 31u] + t[(k.y >> 11) & 31u] + t[(k.z >> 11) & 31u] + t[(k.w >> 11) & 31u];
+        }
+    }
+#pragma unroll
+    for (int d = 8; d >= 1; d >>= 1) {
+        ux += (uint32_t)__shfl_xor((int)ux, d, 16);
+        uy += (uint32_t)__shfl_xor((int)uy, d, 16);
+    }
+    if (p < n_pairs && l == 0u) {
+        bound[p] = ux > uy ? ux : uy;
+        ids[p] = p; // (the list a cut stage's launches take their pairs from: the pair ids in order)
+    }
+}
+
+hipError_t swg_launch_pair_bound(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, const SwgColMax &cm,
+                                 uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream)
+{
+    if (n_pairs == 0) return hipSuccess;
+    hipLaunchKernelGGL(swg_pair_bound_kernel, dim3((n_pairs + 15u) / 16u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_bound, d_ids);
+    return hipGetLastError();
+}
+
+hipError_t swg_launch_prune_threshold(const int32_t *d_scores, const uint32_t *d_order, uint32_t n_slots, uint32_t k, uint32_t *d_hist,
+                                      uint32_t *d_thr, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(d_hist, 0, SWG_TOPK_BINS * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    const int blocks = (int)((n_slots + 255) / 256 < 512 ? (n_slots + 255) / 256 : 512);
+    hipLaunchKernelGGL(swg_topk_hist_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, stream, d_scores, d_order, n_slots, d_hist,
+                       (uint64_t)0);
+    hipLaunchKernelGGL(swg_topk_threshold_kernel, dim3(1), dim3(SWG_TOPK_THR_THREADS), 0, stream, d_hist, k, 0xFFFFFFFFu, d_thr);
+    return hipGetLastError();
+}
+
+// The cut of a stage: out[0] = the pairs its launches take from its first = 1 + the last pair of [begin, end) whose bound
+// reaches the threshold, less begin (0: none; the host zeroes the word before).  A stage is a segment's few hundred
+// thousand pairs or, as the rest of a single-segment database of short sequences, tens of millions: a grid-stride pass
+// of up to 1024 workgroups, one atomicMax per wavefront that found a pair.
+#define SWG_PRUNE_CUT_THREADS 256
+__global__ __launch_bounds__(SWG_PRUNE_CUT_THREADS) void swg_prune_cut_kernel(const uint32_t *bound, uint32_t begin, uint32_t end, const uint32_t *thr,
+                                                                              uint32_t *out)
+{
+    const uint32_t T = thr[0];
+    uint32_t m = 0u;
+    for (uint64_t p = (uint64_t)begin + blockIdx.x * SWG_PRUNE_CUT_THREADS + threadIdx.x; p < end; p += (uint64_t)gridDim.x * SWG_PRUNE_CUT_THREADS)
+        if (bound[p] >= T) m = (uint32_t)p + 1u - begin; // (ascending: the last one stays)
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)m, d, 64);
+        m = o > m ? o : m;
+    }
+    if ((threadIdx.x & 63u) == 0u && m > 0u) atomicMax(out, m);
+}
+
+// ... and what it leaves out, added to the search's tally: out[1] pairs, out[2..3] their token blocks (64 bits)
+__global__ void swg_prune_tally_kernel(const uint32_t *pair_off, uint32_t begin, uint32_t end, uint32_t *out)
+{
+    if (blockIdx.x != 0u || threadIdx.x != 0u) return;
+    const uint32_t cut = begin + out[0];
+    out[1] += end - cut;
+    *reinterpret_cast<unsigned long long *>(out + 2) += (unsigned long long)(pair_off[end] - pair_off[cut]);
+}
+
+hipError_t swg_launch_prune_cut(const uint32_t *d_bound, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, const uint32_t *d_thr,
+                                uint32_t *d_out, hipStream_t stream)
+{
+    if (end < begin) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(d_out, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    const uint32_t per_wg = SWG_PRUNE_CUT_THREADS * 8u;
+    const uint32_t want = (end - begin + per_wg - 1u) / per_wg;
+    const uint32_t wgs = want < 1u ? 1u : want > 1024u ? 1024u : want;
+    hipLaunchKernelGGL(swg_prune_cut_kernel, dim3(wgs), dim3(SWG_PRUNE_CUT_THREADS), 0, stream, d_bound, begin, end, d_thr, d_out);
+    hipLaunchKernelGGL(swg_prune_tally_kernel, dim3(1), dim3(64), 0, stream, d_pair_off, begin, end, d_out);
+    return hipGetLastError();
+}
+
 #endif // part 0
 
 // ---------------------------------------------------------------------------
