@@ -285,7 +285,13 @@ int swg_search_end(swg_ctx *ctx, int ticket, int32_t *scores_out, swg_hit *topk_
  * 2 DIAGNOSTIC, for tests: prune wherever it is structurally possible, ignoring the size rule, and also when scores are
  * requested -- the sequences of skipped pairs then report a score of 0, which is NOT their score.  "prune_head" (default 4):
  * under "prune" 2 a range of one segment runs its longest pairs first, unpruned -- at least k sequences and prune_head pairs per lane
- * group -- so that the rest has a threshold to be cut by. */
+ * group -- so that the rest has a threshold to be cut by.  "prune_kmer" (default 0): the bound a pruned search cuts by.
+ * 1: the sum of the residues' best scores, above.  4 | 5: the sum, over consecutive blocks of 4 | 5 rows of the
+ * sequence, of each block's own local score against the whole query -- never above the first, never below the
+ * sequence's score -- read from a table of every block of residue classes, which is built on the
+ * device in front of the first pruned search of a (query, scoring): 22^k x k x lq cell updates, 17 ms at k = 5 for
+ * 3000 columns on an MI355X, paid once per query.  0: automatic, the largest k whose table costs at most half of what
+ * its tighter cut is expected to save on this range (small databases: 1).  Hits are the same under every value. */
 typedef struct swg_prune_info {
     uint64_t pairs_skipped;
     uint64_t pair_rows_skipped;

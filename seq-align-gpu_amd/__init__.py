@@ -219,6 +219,9 @@ _sig("swg_debug_list_jobs", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t
 _sig("swg_prune_last", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_bound", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp])
 _sig("swg_debug_prune_plan", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_kmer", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp])
+_sig("swg_debug_prune_kmer_choice", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_kmer_read", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp])
 _sig("swg_debug_list_deal", C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 
 
@@ -428,6 +431,47 @@ def debug_prune_bound(rows, query, flat, offsets):
     u = np.zeros(max(n, 1), dtype=np.uint64)
     _check(lib.swg_debug_prune_bound(rp, qp, lq, fp, off.ctypes.data_as(_vp), n, cm.ctypes.data_as(_vp), u.ctypes.data_as(_vp)))
     return cm, u[:n]
+
+
+KMER_CLASSES = 22
+# residue index -> class of the k-mer bound: 0 padding, 1..20 the standard amino acids in index order, 21 the rest
+KMER_CLASS = [0] + [0] * 31
+_std = sorted(ord(ch) - ord("A") + 1 for ch in "ACDEFGHIKLMNPQRSTVWY")
+for _r in range(1, 32):
+    KMER_CLASS[_r] = _std.index(_r) + 1 if _r in _std else KMER_CLASSES - 1
+del _std, _r
+
+
+def debug_prune_kmer(rows, query, gap_open, gap_extend, k, flat, offsets, table=True):
+    """Test hook (no device needed): the host mirror of the k-mer bound, k = 4 or 5.  rows / query as debug_prune_bound
+    takes them.  -> (table uint16[22^k] or None, U_k uint64[n]): the local score of every class block against the query,
+    and the bound of each sequence flat[offsets[i] .. offsets[i+1]) summed as the device sums it -- over the sequence's
+    token rows (two reset rows first), in blocks of 4 rows, or of 5 over every whole 20 rows and of 4 over the rest.  A
+    residue 0 in a sequence is a padding row (the shorter sequence of a pair, filled up to the longer one's length)."""
+    r, rp = _i8(rows)
+    lq = r.size // 32
+    qp = None
+    if query is not None:
+        q, qp = _i8(query)
+        lq = q.size
+    f, fp = _i8(flat)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = off.size - 1
+    t = np.zeros(KMER_CLASSES ** int(k), dtype=np.uint16) if table and k in (4, 5) else None
+    u = np.zeros(max(n, 1), dtype=np.uint64)
+    _check(lib.swg_debug_prune_kmer(rp, qp, lq, int(gap_open), int(gap_extend), int(k), fp, off.ctypes.data_as(_vp), n,
+                                    t.ctypes.data_as(_vp) if t is not None else None, u.ctypes.data_as(_vp)))
+    return t, u[:n]
+
+
+def debug_prune_kmer_choice(forced=0, pruned=1, lq=3000, pair_rows=1900000000, table_rate=0, fill_rate=0):
+    """Test hook (no device needed): the bound a search cuts by (swg_prune_kmer_choice) -> 0 (not pruned: nothing is
+    built), 1 (colmax), 4 or 5.  forced: option prune_kmer; rates in table cells and fill pair rows per second, 0: the
+    library's own for this lq."""
+    a = np.array([forced, pruned, lq, pair_rows, table_rate, fill_rate], dtype=np.int64)
+    out = np.zeros(1, dtype=np.int64)
+    _check(lib.swg_debug_prune_kmer_choice(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
+    return int(out[0])
 
 
 PRUNE_PLAN_KEYS = ("mode", "k", "want_scores", "gap_open", "gap_extend", "bits", "use_diag", "n_classes", "work_queue", "both_forms",
@@ -903,6 +947,22 @@ class Context:
         _check(lib.swg_prune_last(self.handle, C.cast(C.byref(i), _vp)), self.handle)
         return {"pruned": bool(i.pruned), "threshold": int(i.threshold), "pairs_skipped": int(i.pairs_skipped),
                 "pair_rows_skipped": int(i.pair_rows_skipped), "pair_rows": int(i.pair_rows)}
+
+    def debug_prune_kmer_read(self, db, k=None, bounds=False):
+        """Test hook: what the k-mer bound left on the device, once everything queued has run -> dict: k (what the search
+        last begun cut by; 0: not pruned), builds (table builds of this context so far), pairs (of db), table (the
+        context's table of `k`, uint16[22^k], when k is given) and bounds (uint32 per pair of the search last begun on db,
+        when asked for)."""
+        info = np.zeros(3, dtype=np.uint64)
+        t = np.zeros(KMER_CLASSES ** int(k), dtype=np.uint16) if k else None
+        n = 0
+        if bounds:  # (a first call for the number of pairs)
+            _check(lib.swg_debug_prune_kmer_read(self.handle, db.handle, 0, None, None, 0, info.ctypes.data_as(_vp)), self.handle)
+            n = int(info[2])
+        b = np.zeros(max(n, 1), dtype=np.uint32) if bounds else None
+        _check(lib.swg_debug_prune_kmer_read(self.handle, db.handle, int(k or 0), t.ctypes.data_as(_vp) if t is not None else None,
+                                             b.ctypes.data_as(_vp) if b is not None else None, n, info.ctypes.data_as(_vp)), self.handle)
+        return {"k": int(info[0]), "builds": int(info[1]), "pairs": int(info[2]), "table": t, "bounds": None if b is None else b[:int(info[2])]}
 
     def debug_bounds_last(self):
         """What the last align_bounds* call of this context did (swg_debug_bounds_last) -> dict: pairs on the bounds kernel,

@@ -240,6 +240,9 @@ extern "C" void swg_destroy(swg_ctx *ctx)
     (void)hipFree(ctx->d_sub);
     (void)hipFree(ctx->d_query);
     (void)hipFree(ctx->d_pssm);
+    (void)hipFree(ctx->d_kmer_cprof);
+    (void)hipFree(ctx->d_kmer_table[0]);
+    (void)hipFree(ctx->d_kmer_table[1]);
     (void)hipFree(ctx->d_profile[0]);
     (void)hipFree(ctx->d_profile[1]);
     (void)hipFree(ctx->d_profile[2]);
@@ -332,6 +335,10 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
     } else if (!strcmp(key, "prune_head")) {
         if (value < 0 || value > 4096) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_head must be 0..4096 (pairs per lane group)");
         ctx->opt_prune_head = value;
+    } else if (!strcmp(key, "prune_kmer")) {
+        if (value != 0 && value != 1 && value != 4 && value != 5)
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_kmer must be 0 (auto), 1 (the colmax bound), 4 or 5 (the k-mer bound of that k)");
+        ctx->opt_prune_kmer = value;
     } else if (!strcmp(key, "q32_waves")) {
         ctx->opt_q32_waves = value;
     } else if (!strcmp(key, "wave_budget")) {
@@ -1211,7 +1218,11 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
                 uint32_t *cw = db->d_counters;
                 const uint32_t n_pairs_all = (uint32_t)swg_db_pair_count(db);
                 uint32_t *d_ids = db->d_pair_bound + n_pairs_all;
-                HIP_TRY(ctx, swg_launch_pair_bound(T.d_tok, T.d_pair_off, n_pairs_all, ctx->prune_colmax, db->d_pair_bound, d_ids, qs));
+                if (prune->kmer > 1) // (the table of this epoch: plan_prune queued its build on this stream)
+                    HIP_TRY(ctx, swg_launch_pair_bound_kmer(T.d_tok, T.d_pair_off, n_pairs_all, prune->kmer, ctx->prune_colmax, ctx->d_kmer_table[prune->kmer - 4], db->d_pair_bound,
+                                                            d_ids, qs));
+                else
+                    HIP_TRY(ctx, swg_launch_pair_bound(T.d_tok, T.d_pair_off, n_pairs_all, ctx->prune_colmax, db->d_pair_bound, d_ids, qs));
                 struct Stage { uint32_t b, en; size_t sg; };
                 std::vector<Stage> stages;
                 for (size_t i = 0; i < segs.size(); ++i) {
@@ -2284,6 +2295,33 @@ static int enqueue_rescore(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P, Swg
     return SWG_OK;
 }
 
+// The k-mer bound's table for the current (query, scoring) epoch: the class profile from the device copies
+// of table and query, then every class block's local score, both queued on the context's stream -- behind the copy of
+// the query a set_query queued there and behind any search still in flight, in front of the bound kernel that reads it:
+// the rule the profiles follow (ensure_profile_cols).  One buffer per k, so searches that alternate between the two
+// build each once per epoch.
+static int ensure_kmer_table(swg_ctx *ctx, int k)
+{
+    const int which = k - 4;
+    const size_t lq = ctx->query_len();
+    if (ctx->d_kmer_table[which] && ctx->kmer_table_epoch[which] == ctx->epoch) return SWG_OK;
+    if (lq * 32 > ctx->d_kmer_cprof_cap) {
+        (void)hipFree(ctx->d_kmer_cprof);
+        ctx->d_kmer_cprof = nullptr;
+        ctx->d_kmer_cprof_cap = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->d_kmer_cprof, lq * 32));
+        ctx->d_kmer_cprof_cap = lq * 32;
+    }
+    if (!ctx->d_kmer_table[which]) HIP_TRY(ctx, hipMalloc(&ctx->d_kmer_table[which], (size_t)swg_kmer_entries(k) * sizeof(uint16_t)));
+    // (gap scores: a gap's first residue costs open + extend, every further one extend -- SwgSearchPlan's go / ge)
+    const long go = (long)ctx->gap_open + ctx->gap_extend, ge = ctx->gap_extend;
+    HIP_TRY(ctx, swg_launch_kmer_table(ctx->d_sub, ctx->d_query, ctx->query_pssm ? ctx->d_pssm : nullptr, (uint32_t)lq, (uint32_t)-go, (uint32_t)-ge, k,
+                                       ctx->d_kmer_cprof, ctx->d_kmer_table[which], ctx->stream));
+    ctx->kmer_table_epoch[which] = ctx->epoch;
+    ++ctx->kmer_builds;
+    return SWG_OK;
+}
+
 // Whether this search is pruned (swg_prune_plan has the rules), decided once the plan stands; a pruned search gets the
 // bound's table for the current query and scoring (built on the host when either has changed; it travels to the bound
 // kernel as a launch argument) and its slot's buffer of pair bounds.
@@ -2317,7 +2355,20 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
         return SWG_OK; // (launch_diag reports it)
     a.n_segments = segs.size();
     P->prune = swg_prune_plan(a);
+    ctx->prune_last_kmer = 0;
     if (!P->prune.on) return SWG_OK;
+    // which bound: the colmax table, or the k-mer table of the k that pays for its build on this range (a forced k as it is)
+    SwgKmerAsk ka;
+    ka.forced = ctx->opt_prune_kmer;
+    ka.pruned = true;
+    ka.lq = ctx->query_len();
+    ka.pair_rows = 4ull * (db->ptok.pair_blocks_prefix[wk.pair_end[0]] - db->ptok.pair_blocks_prefix[wk.pair_begin[0]]);
+    ka.fill_rate = swg_kmer_fill_rate(ka.lq);
+    P->prune.kmer = ctx->prune_last_kmer = swg_prune_kmer_choice(ka);
+    if (P->prune.kmer > 1) {
+        const int rk = ensure_kmer_table(ctx, P->prune.kmer);
+        if (rk != SWG_OK) return rk;
+    }
     if (ctx->prune_colmax_epoch != ctx->epoch) {
         ctx->prune_colmax = ctx->query_pssm ? swg_prune_colmax(ctx->pssm.data(), nullptr, ctx->query_len())
                                             : swg_prune_colmax(&ctx->sub[0][0], ctx->query.data(), ctx->query_len());
@@ -2589,6 +2640,31 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
     }
     st.topk_ms = topk_dev_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = st;
+    return SWG_OK;
+}
+
+// test hook: what the k-mer bound left on the device, read once everything queued has run.  table_out (or NULL): the
+// 22^k entries of the context's table of k (an error unless it was built for the current query and scoring); bound_out
+// (or NULL; bound_cap entries): the pair bounds of the search last begun on db.  info[0..2] = the k that search cut by
+// (0: not pruned), the table builds this context has queued so far, the database's pairs.
+extern "C" int swg_debug_prune_kmer_read(swg_ctx *ctx, const swg_db *db, int k, uint16_t *table_out, uint32_t *bound_out, size_t bound_cap,
+                                         uint64_t *info)
+{
+    if (!ctx || !info) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_kmer_read: NULL argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    const size_t n_pairs = db ? (size_t)swg_db_pair_count(db) : 0;
+    info[0] = (uint64_t)ctx->prune_last_kmer, info[1] = ctx->kmer_builds, info[2] = n_pairs;
+    if (table_out) {
+        if ((k != 4 && k != 5) || !ctx->d_kmer_table[k - 4] || ctx->kmer_table_epoch[k - 4] != ctx->epoch)
+            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_kmer_read: no table of k = %d for the current query and scoring", k);
+        HIP_TRY(ctx, hipMemcpy(table_out, ctx->d_kmer_table[k - 4], (size_t)swg_kmer_entries(k) * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    }
+    if (bound_out) {
+        if (!db || !db->d_pair_bound || bound_cap < n_pairs)
+            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_kmer_read: no pair bounds on this database, or too little room");
+        HIP_TRY(ctx, hipMemcpy(bound_out, db->d_pair_bound, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
     return SWG_OK;
 }
 

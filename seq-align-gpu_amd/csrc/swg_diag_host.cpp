@@ -652,6 +652,132 @@ extern "C" int swg_debug_prune_plan(const int64_t *in, int64_t *out)
     return SWG_OK;
 }
 
+// The k-mer form of the bound, on the host: what the device builds (swg_kmer_cprof_kernel,
+// swg_kmer_table_kernel) and sums (swg_pair_bound_kmer_kernel), restated for the tests.  cprof[lq][22]: query column i
+// against residue class c -- the residue's own score for classes 1..20, the best of the merged residues for class 21 (the
+// local score is monotone in the substitution scores), SWG_KMER_PAD_SCORE for the padding class, which can then be
+// neither matched nor crossed for free.
+void swg_kmer_cprof(const int8_t *rows, const int8_t *idx, size_t lq, int8_t *cprof)
+{
+    for (size_t i = 0; i < lq; ++i) {
+        const int8_t *row = idx ? rows + 32 * ((uint8_t)idx[i] & 31) : rows + 32 * i;
+        int8_t *out = cprof + SWG_KMER_CLASSES * i;
+        for (uint32_t c = 0; c < SWG_KMER_CLASSES; ++c) out[c] = SWG_KMER_PAD_SCORE;
+        for (uint32_t r = 1; r < 32; ++r) {
+            const uint32_t c = swg_kmer_class(r);
+            out[c] = std::max(out[c], row[r]);
+        }
+    }
+}
+
+// table[c_1 .. c_k] = the local score of the class block against the query (gap magnitudes g, e; the recurrence of
+// DESIGN 4.1 in int32).  Blocks that share a prefix share its cells: the block runs along the columns, a column is lq
+// cells, and the columns of a prefix are computed once for all the blocks behind it (depth first, the first class in
+// parallel).  Value for value what the device's one-thread-per-block walk along the query gives.
+static void kmer_extend(const int8_t *cprof, size_t lq, int g, int e, int k, int depth, size_t prefix, const int *Mp, const int *Bp, int best_p,
+                        std::vector<int> &work, uint16_t *table, uint32_t c_begin, uint32_t c_end)
+{
+    int *Mn = work.data() + (size_t)depth * 2 * lq, *Bn = Mn + lq;
+    for (uint32_t c = c_begin; c < c_end; ++c) {
+        int a = 0, up = 0, best = best_p;
+        for (size_t i = 0; i < lq; ++i) {
+            const int s = cprof[SWG_KMER_CLASSES * i + c];
+            a = std::max(std::max(up - g, a - e), 0);
+            const int b = depth ? std::max(std::max(Mp[i] - g, Bp[i] - e), 0) : 0;
+            const int diag = depth && i ? Mp[i - 1] : 0;
+            const int m = std::max(std::max(diag + s, a), b);
+            Mn[i] = m, Bn[i] = b, up = m;
+            best = std::max(best, m);
+        }
+        const size_t at = prefix * SWG_KMER_CLASSES + c;
+        if (depth + 1 == k) table[at] = (uint16_t)std::min(best, 65535);
+        else kmer_extend(cprof, lq, g, e, k, depth + 1, at, Mn, Bn, best, work, table, 0, SWG_KMER_CLASSES);
+    }
+}
+
+void swg_kmer_table(const int8_t *cprof, size_t lq, int g, int e, int k, uint16_t *table)
+{
+    g = std::min(g, 65536), e = std::min(e, 65536);
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int c = 0; c < (int)SWG_KMER_CLASSES; ++c) {
+        std::vector<int> work((size_t)k * 2 * lq);
+        kmer_extend(cprof, lq, g, e, k, 0, 0, nullptr, nullptr, 0, work, table, (uint32_t)c, (uint32_t)c + 1u);
+    }
+}
+
+// U_k of one sequence as the device sums it: the sequence's token rows -- two reset rows (padding), its residues (a 0 among
+// them is a padding row: the shorter sequence of a pair, filled up to the longer one's length), padding to a whole 4-row
+// token block -- in blocks of 4 rows (k = 4), or in blocks of 5 over every whole 20 rows and of 4 over the rest (k = 5).
+// A block adds its table entry, or the sum of its rows' colmax entries where that is less: the entry of a block with
+// residues of class 21 is taken under the best scores of all of them, and may exceed what these residues can reach.
+uint64_t swg_kmer_bound(const uint16_t *table, int k, const SwgColMax &cm, const int8_t *seq, size_t len)
+{
+    const size_t n_blocks = (2 + len + 3) / 4, n_rows = 4 * n_blocks;
+    auto res = [&](size_t row) -> uint32_t { return row < 2 || row >= 2 + len ? 0u : (uint8_t)seq[row - 2] & 31u; };
+    const size_t rows5 = k == 5 ? 20 * (n_blocks / 5) : 0;
+    uint64_t u = 0;
+    for (size_t r = 0; r < n_rows;) {
+        const size_t rows = r < rows5 ? 5 : 4;
+        size_t ix = 0;
+        uint64_t sum = 0;
+        for (size_t j = 0; j < rows; ++j) ix = ix * SWG_KMER_CLASSES + swg_kmer_class(res(r + j)), sum += cm.v[res(r + j)];
+        if (k == 5 && rows == 4) ix *= SWG_KMER_CLASSES;
+        u += std::min<uint64_t>(table[ix], sum);
+        r += rows;
+    }
+    return u;
+}
+
+// test hook: the table (22^k uint16, or NULL) and U_k of each of the n sequences, under the gap scores of swg_set_scoring
+extern "C" int swg_debug_prune_kmer(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int k, const int8_t *flat,
+                                    const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out)
+{
+    if (!rows || lq == 0 || (k != 4 && k != 5) || gap_open > 0 || gap_extend > 0 || (n > 0 && (!flat || !offsets || !u_out))) return SWG_ERR_ARG;
+    std::vector<int8_t> cprof(lq * SWG_KMER_CLASSES);
+    swg_kmer_cprof(rows, idx, lq, cprof.data());
+    std::vector<uint16_t> own;
+    if (!table_out) {
+        own.resize(swg_kmer_entries(k));
+        table_out = own.data();
+    }
+    swg_kmer_table(cprof.data(), lq, -(gap_open + gap_extend), -gap_extend, k, table_out);
+    const SwgColMax cm = swg_prune_colmax(rows, idx, lq);
+    for (size_t i = 0; i < n; ++i) u_out[i] = swg_kmer_bound(table_out, k, cm, flat + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+    return SWG_OK;
+}
+
+// Which bound a pruned search cuts by: 1 (colmax), 4 or 5 (k-mer tables).  A forced k is taken as it is wherever the search
+// is pruned; an unpruned search builds nothing (0).  Automatic weighs what a table costs -- 22^k * k * lq cells at
+// table_rate cells per second, paid by every search with a new query -- against what its tighter cut saves: the share of
+// the range's pair rows it takes off the fill (SWG_KMER_GAIN: the hard case, a database of unrelated sequences, DESIGN
+// 4.2.1) at fill_rate pair rows per second for this query.  A step up must cost at most half of what it saves.
+static const double SWG_KMER_GAIN[6] = {0, 0, 0, 0, 0.1426, 0.2006}; // the headline's rows kept: 0.5584 (k = 1), 0.4158 (4), 0.3578 (5)
+int swg_prune_kmer_choice(const SwgKmerAsk &a)
+{
+    if (!a.pruned) return 0;
+    if (a.forced == 1 || a.forced == 4 || a.forced == 5) return (int)a.forced;
+    if (a.table_rate <= 0 || a.fill_rate <= 0 || a.lq == 0) return 1;
+    auto cost = [&](int k) { return k == 1 ? 0.0 : (double)swg_kmer_entries(k) * k * (double)a.lq / a.table_rate; };
+    auto gain = [&](int k) { return SWG_KMER_GAIN[k] * (double)a.pair_rows / a.fill_rate; };
+    int k = 1;
+    if (cost(4) <= 0.5 * gain(4)) k = 4;
+    if (k == 4 && cost(5) - cost(4) <= 0.5 * (gain(5) - gain(4))) k = 5;
+    return k;
+}
+
+// test hook: in[0..5] = forced (option "prune_kmer"), pruned, lq, pair rows, table cells per second, fill pair rows per second
+// (0, 0: the library's own rates for this lq); out[0] = k
+extern "C" int swg_debug_prune_kmer_choice(const int64_t *in, int64_t *out)
+{
+    if (!in || !out || in[2] < 0 || in[3] < 0 || in[4] < 0 || in[5] < 0) return SWG_ERR_ARG;
+    SwgKmerAsk a;
+    a.forced = (long)in[0], a.pruned = in[1] != 0, a.lq = (size_t)in[2], a.pair_rows = (uint64_t)in[3];
+    a.table_rate = in[4] ? (double)in[4] : SWG_KMER_TABLE_RATE;
+    a.fill_rate = in[5] ? (double)in[5] : swg_kmer_fill_rate(a.lq);
+    out[0] = swg_prune_kmer_choice(a);
+    return SWG_OK;
+}
+
 // Both 16-bit forms in one search (plan_search in swg_api.cpp): the length from which a sequence can reach the f16 cells' ceiling
 // as an exact copy of a stretch of the query -- such a copy scores qbound / lq per row on average, qbound being the
 // query's best possible total --, and where that length cuts the sorted pair order (kept per database and length).

@@ -309,6 +309,32 @@ struct SwgColMax {
 // d_ids[p] = p, the list a cut stage's launches take their pairs from
 hipError_t swg_launch_pair_bound(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, const SwgColMax &cm,
                                  uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream);
+// The k-mer form of the bound: a sequence's token rows are cut into blocks of k rows, and a block scores
+// at most its own local score against the whole query, a table over the blocks' residue CLASSES: 0 the padding residue,
+// 1..20 the twenty standard amino acids in index order, 21 every other index (B J O U X Z, 27..31) under the best of
+// their scores.  A block's entry is at base-22 index c_1 c_2 .. c_k, first row first.
+#define SWG_KMER_CLASSES 22u
+#define SWG_KMER_STD_MASK 0x2DF7BFAu // bit r: index r is one of A C D E F G H I K L M N P Q R S T V W Y
+#define SWG_KMER_PAD_SCORE (-128)    // the padding class against any column: never matched
+static inline __host__ __device__ uint32_t swg_kmer_class(uint32_t r)
+{
+    r &= 31u;
+    if (r == 0u) return 0u;
+    if (!((SWG_KMER_STD_MASK >> r) & 1u)) return SWG_KMER_CLASSES - 1u;
+    uint32_t c = 0u;
+    for (uint32_t i = 1u; i <= r; ++i) c += (SWG_KMER_STD_MASK >> i) & 1u;
+    return c;
+}
+static inline uint64_t swg_kmer_entries(int k) { return k == 5 ? 5153632ull : k == 4 ? 234256ull : 0ull; }
+// d_cprof[lq][32] (int8; entries 22..31 of a row unused): query column i against class c, from the device copies of the
+// table and the index query (d_pssm == NULL) or of the PSSM; then d_table[22^k] = the local score of every class block
+// against the query under gap magnitudes g (first residue of a gap) and e (every further one).  k: 4 or 5.
+hipError_t swg_launch_kmer_table(const int8_t *d_sub, const int8_t *d_query, const int8_t *d_pssm, uint32_t lq, uint32_t g, uint32_t e,
+                                 int k, int8_t *d_cprof, uint16_t *d_table, hipStream_t stream);
+// swg_launch_pair_bound with the k-mer bound: blocks of 4 token rows (k = 4), or of 5 with a tail of fewer than 20 rows
+// in blocks of 4 (k = 5); a block adds the lesser of its table entry and its rows' colmax entries
+hipError_t swg_launch_pair_bound_kmer(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, int k, const SwgColMax &cm,
+                                      const uint16_t *d_table, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream);
 // d_thr[0] = the k-th largest entry of d_scores (clamped to 4095; 0 with fewer than k entries): swg_topk_hist_kernel and
 // swg_topk_threshold_kernel on `stream`; d_thr[1] is written too (the status word, not read)
 hipError_t swg_launch_prune_threshold(const int32_t *d_scores, const uint32_t *d_order, uint32_t n_slots, uint32_t k, uint32_t *d_hist,

@@ -2825,6 +2825,157 @@ hipError_t swg_launch_pair_bound(const uint4 *d_tok, const uint32_t *d_pair_off,
     return hipGetLastError();
 }
 
+// The k-mer form of the bound.  The class profile first: query column i against each of the 22 residue classes, 32 bytes
+// per column; one thread per entry.
+__global__ __launch_bounds__(256) void swg_kmer_cprof_kernel(const int8_t *sub, const int8_t *query, const int8_t *pssm, uint32_t lq, int8_t *cprof)
+{
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x, i = t >> 5, c = t & 31u;
+    if (i >= lq) return;
+    const int8_t *row = pssm ? pssm + 32u * (size_t)i : sub + 32u * ((uint32_t)query[i] & 31u);
+    int v = SWG_KMER_PAD_SCORE;
+    if (c >= 1u && c < SWG_KMER_CLASSES) {
+        for (uint32_t r = 1u; r < 32u; ++r)
+            if (swg_kmer_class(r) == c) v = row[r] > v ? row[r] : v; // (one residue for classes 1..20, the best of the rest for 21)
+    }
+    cprof[t] = (int8_t)v;
+}
+
+// table[c_1 .. c_K] = the local score of the class block against the whole query: one thread per block, its K cells'
+// (M, A) in registers, the query along the loop (plain int32 cells, the recurrence of DESIGN 4.1).  The query position is
+// the same for the whole workgroup: the class profile goes through LDS in chunks, a row's 22 bytes are 6 dwords in 6 banks.
+#define SWG_KMER_CHUNK 256u
+template <int K>
+__global__ __launch_bounds__(256) void swg_kmer_table_kernel(const int8_t *cprof, uint32_t lq, int g, int e, uint32_t n_entries, uint16_t *table)
+{
+    __shared__ uint4 rows4[SWG_KMER_CHUNK * 2u];
+    const int8_t *rows = reinterpret_cast<const int8_t *>(rows4);
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    uint32_t c[K];
+    {
+        uint32_t v = idx < n_entries ? idx : 0u;
+#pragma unroll
+        for (int j = K - 1; j >= 0; --j) {
+            c[j] = v % SWG_KMER_CLASSES;
+            v /= SWG_KMER_CLASSES;
+        }
+    }
+    int M[K], A[K], best = 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) M[j] = 0, A[j] = 0;
+    for (uint32_t i0 = 0u; i0 < lq; i0 += SWG_KMER_CHUNK) {
+        const uint32_t n = lq - i0 < SWG_KMER_CHUNK ? lq - i0 : SWG_KMER_CHUNK;
+        __syncthreads();
+        for (uint32_t w = threadIdx.x; w < n * 2u; w += 256u) rows4[w] = reinterpret_cast<const uint4 *>(cprof + 32u * (size_t)i0)[w];
+        __syncthreads();
+        for (uint32_t i = 0u; i < n; ++i) {
+            const int8_t *row = rows + 32u * i;
+            int diag = 0, left = 0, B = 0;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const int s = row[c[j]];
+                const int a = max(max(M[j] - g, A[j] - e), 0);
+                const int b = j ? max(max(left - g, B - e), 0) : 0;
+                const int m = max(max(diag + s, a), b);
+                diag = M[j];
+                M[j] = m, A[j] = a, B = b, left = m;
+                best = max(best, m);
+            }
+        }
+    }
+    if (idx < n_entries) table[idx] = (uint16_t)(best > 65535 ? 65535 : best);
+}
+
+hipError_t swg_launch_kmer_table(const int8_t *d_sub, const int8_t *d_query, const int8_t *d_pssm, uint32_t lq, uint32_t g, uint32_t e,
+                                 int k, int8_t *d_cprof, uint16_t *d_table, hipStream_t stream)
+{
+    const uint32_t n = (uint32_t)swg_kmer_entries(k);
+    if (n == 0u || lq == 0u || lq > (1u << 24)) return hipErrorInvalidValue;
+    // (gap magnitudes beyond any block's score change nothing, and keep the int32 cells far from their range)
+    const int gi = (int)(g > 65536u ? 65536u : g), ei = (int)(e > 65536u ? 65536u : e);
+    hipLaunchKernelGGL(swg_kmer_cprof_kernel, dim3((lq * 32u + 255u) / 256u), dim3(256), 0, stream, d_sub, d_query, d_pssm, lq, d_cprof);
+    if (k == 5)
+        hipLaunchKernelGGL(swg_kmer_table_kernel<5>, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_cprof, lq, gi, ei, n, d_table);
+    else
+        hipLaunchKernelGGL(swg_kmer_table_kernel<4>, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_cprof, lq, gi, ei, n, d_table);
+    return hipGetLastError();
+}
+
+// swg_pair_bound_kernel with the k-mer bound: a block of K token rows adds its table entry -- or the sum of its rows'
+// colmax entries where that is less (it can be with residues of class 21, whose entry is the best of several) -- for each
+// of the pair's two sequences.  K = 4: a block is one uint4.  K = 5: a lane takes five consecutive uint4s as four blocks
+// of 5 rows; the pair's last fewer-than-five uint4s are blocks of 4 rows, which in the table of 5 are class blocks with a
+// padding tail.  Reset rows and the rows past a sequence's end are the padding class wherever they fall in a block.
+template <int K>
+__global__ __launch_bounds__(256) void swg_pair_bound_kmer_kernel(const uint4 *tok, const uint32_t *pair_off, uint32_t n_pairs, SwgColMax cm,
+                                                                  const uint16_t *table, uint32_t *bound, uint32_t *ids)
+{
+    __shared__ uint32_t lut[32]; // residue index -> class | colmax << 8
+    if (threadIdx.x < 32u) lut[threadIdx.x] = swg_kmer_class(threadIdx.x) | (uint32_t)cm.v[threadIdx.x] << 8;
+    __syncthreads();
+    const uint32_t p = blockIdx.x * 16u + (threadIdx.x >> 4), l = threadIdx.x & 15u;
+    const uint32_t C = SWG_KMER_CLASSES;
+    // one block: its rows' lut words, first row first -> min(table entry, sum of colmax)
+    auto block4 = [&](uint32_t a, uint32_t b, uint32_t c, uint32_t d) -> uint32_t {
+        const uint32_t ix = (((a & 255u) * C + (b & 255u)) * C + (c & 255u)) * C + (d & 255u);
+        const uint32_t t = table[K == 5 ? ix * C : ix], u = (a >> 8) + (b >> 8) + (c >> 8) + (d >> 8);
+        return t < u ? t : u;
+    };
+    auto block5 = [&](uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t e) -> uint32_t {
+        const uint32_t ix = ((((a & 255u) * C + (b & 255u)) * C + (c & 255u)) * C + (d & 255u)) * C + (e & 255u);
+        const uint32_t t = table[ix], u = (a >> 8) + (b >> 8) + (c >> 8) + (d >> 8) + (e >> 8);
+        return t < u ? t : u;
+    };
+    uint32_t ux = 0u, uy = 0u;
+    if (p < n_pairs) {
+        const uint32_t b0 = pair_off[p], e = pair_off[p + 1u];
+        uint32_t tail = b0;
+        if (K == 5) {
+            const uint32_t groups = (e - b0) / 5u;
+            tail = b0 + 5u * groups;
+            for (uint32_t gi = l; gi < groups; gi += 16u) {
+                uint32_t x[20], y[20];
+#pragma unroll
+                for (int u = 0; u < 5; ++u) {
+                    const uint4 k = tok[b0 + 5u * gi + (uint32_t)u];
+                    x[4 * u] = lut[(k.x >> 3) & 31u], x[4 * u + 1] = lut[(k.y >> 3) & 31u], x[4 * u + 2] = lut[(k.z >> 3) & 31u], x[4 * u + 3] = lut[(k.w >> 3) & 31u];
+                    y[4 * u] = lut[(k.x >> 11) & 31u], y[4 * u + 1] = lut[(k.y >> 11) & 31u], y[4 * u + 2] = lut[(k.z >> 11) & 31u], y[4 * u + 3] = lut[(k.w >> 11) & 31u];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    ux += block5(x[5 * u], x[5 * u + 1], x[5 * u + 2], x[5 * u + 3], x[5 * u + 4]);
+                    uy += block5(y[5 * u], y[5 * u + 1], y[5 * u + 2], y[5 * u + 3], y[5 * u + 4]);
+                }
+            }
+        }
+        for (uint32_t b = tail + l; b < e; b += 16u) {
+            const uint4 k = tok[b];
+            ux += block4(lut[(k.x >> 3) & 31u], lut[(k.y >> 3) & 31u], lut[(k.z >> 3) & 31u], lut[(k.w >> 3) & 31u]);
+            uy += block4(lut[(k.x >> 11) & 31u], lut[(k.y >> 11) & 31u], lut[(k.z >> 11) & 31u], lut[(k.w >> 11) & 31u]);
+        }
+    }
+#pragma unroll
+    for (int d = 8; d >= 1; d >>= 1) {
+        ux += (uint32_t)__shfl_xor((int)ux, d, 16);
+        uy += (uint32_t)__shfl_xor((int)uy, d, 16);
+    }
+    if (p < n_pairs && l == 0u) {
+        bound[p] = ux > uy ? ux : uy;
+        ids[p] = p;
+    }
+}
+
+hipError_t swg_launch_pair_bound_kmer(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, int k, const SwgColMax &cm,
+                                      const uint16_t *d_table, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream)
+{
+    if (k != 4 && k != 5) return hipErrorInvalidValue;
+    if (n_pairs == 0) return hipSuccess;
+    if (k == 5)
+        hipLaunchKernelGGL(swg_pair_bound_kmer_kernel<5>, dim3((n_pairs + 15u) / 16u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, d_bound, d_ids);
+    else
+        hipLaunchKernelGGL(swg_pair_bound_kmer_kernel<4>, dim3((n_pairs + 15u) / 16u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, d_bound, d_ids);
+    return hipGetLastError();
+}
+
 hipError_t swg_launch_prune_threshold(const int32_t *d_scores, const uint32_t *d_order, uint32_t n_slots, uint32_t k, uint32_t *d_hist,
                                       uint32_t *d_thr, hipStream_t stream)
 {
