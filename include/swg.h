@@ -460,6 +460,32 @@ int swg_align_bounds_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *ps
                                 size_t n_queries, const swg_hit *hits, size_t k, const size_t *n_hits,
                                 swg_alignment *out);
 
+/* The line of a tabular report (BLAST -outfmt 6, MMseqs2 convertalis) without the path: swg_align_stats / _multi /
+ * _multi_pssm take the arguments of swg_align_bounds / _multi / _multi_pssm, write to `out` exactly what those write
+ * (same errors, hit order, repeats, views and fallback; reserved = 0) and to `counts`, parallel to `out` (slot i*k + j in
+ * the batch calls; slots past n_hits[i] are not written), the column counts of the path swg_align_hits* would spell
+ * for the same pair under the tie rules above.  counts, like out, must not be NULL when there is a hit (SWG_ERR_ARG).
+ * A pair of score 0 has all four counts 0.  The forward pass carries n_ident and n_gap_open with every state's tag; the
+ * other two follow from the coordinates (every M takes a query column and a residue, every I or D one of the two).
+ * Percent identity as BLAST prints it is 100 * n_ident / n_ops, mismatches are n_match - n_ident.
+ * A PSSM has no residues: identity is counted against its consensus, as MMseqs2 reports identity for profile queries --
+ * position p's consensus is the lowest residue index b in 1..31 whose score pssm[p*32 + b] is the row's maximum over
+ * 1..31.  DESIGN 8.3. */
+typedef struct swg_align_counts {
+    uint32_t n_ident;    /* 'M' steps whose query residue equals the database residue */
+    uint32_t n_match;    /* 'M' steps (aligned columns); mismatches = n_match - n_ident */
+    uint32_t n_gap_open; /* maximal runs of 'I' or of 'D' in the path ("ID" is two runs) */
+    uint32_t n_gap;      /* 'I' + 'D' steps = n_ops - n_match */
+} swg_align_counts;
+int swg_align_stats(swg_ctx *ctx, const swg_db *db, const swg_hit *hits, size_t n_hits, swg_alignment *out,
+                    swg_align_counts *counts);
+int swg_align_stats_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets,
+                          size_t n_queries, const swg_hit *hits, size_t k, const size_t *n_hits, swg_alignment *out,
+                          swg_align_counts *counts);
+int swg_align_stats_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets,
+                               size_t n_queries, const swg_hit *hits, size_t k, const size_t *n_hits,
+                               swg_alignment *out, swg_align_counts *counts);
+
 /* ---- multi-GPU merge -------------------------------------------------- */
 
 /* 64-bit sort key of a hit: (score << 32) | (0xFFFFFFFF - index).  Larger key =

@@ -38,7 +38,7 @@ ABI_SYMBOLS = [
     "swg_search_multi_pssm", "swg_search_lists", "swg_search_lists_pssm", "swg_search_gapless", "swg_search_gapless_multi",
     "swg_search_gapless_multi_pssm", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_align_hits_multi",
     "swg_align_hits_multi_pssm", "swg_align_ops_bound_multi", "swg_align_bounds", "swg_align_bounds_multi",
-    "swg_align_bounds_multi_pssm", "swg_hit_key",
+    "swg_align_bounds_multi_pssm", "swg_align_stats", "swg_align_stats_multi", "swg_align_stats_multi_pssm", "swg_hit_key",
     "swg_key_hit", "swg_topk_merge_keys",
     "swg_group_create", "swg_group_destroy", "swg_group_size", "swg_group_last_error", "swg_group_set_option",
     "swg_group_set_scoring", "swg_group_set_query", "swg_group_set_query_pssm", "swg_group_load", "swg_group_search",
@@ -67,6 +67,10 @@ class Hit(C.Structure):
 class Alignment(C.Structure):
     _fields_ = [("score", C.c_int32), ("index", C.c_uint32), ("q_begin", C.c_uint32), ("q_end", C.c_uint32),
                 ("d_begin", C.c_uint32), ("d_end", C.c_uint32), ("n_ops", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class AlignCounts(C.Structure):
+    _fields_ = [("n_ident", C.c_uint32), ("n_match", C.c_uint32), ("n_gap_open", C.c_uint32), ("n_gap", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -202,6 +206,9 @@ _sig("swg_pssm_load", C.c_int, [C.c_char_p, C.POINTER(Scoring), C.POINTER(_vp), 
 _sig("swg_pssm_free", None, [_vp, _vp])
 # test hook, declared in csrc/swg_host_internal.h (not part of the public ABI)
 _sig("swg_debug_fail_alloc", None, [C.c_int])
+_sig("swg_align_stats", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp])
+_sig("swg_align_stats_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp])
+_sig("swg_align_stats_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp])
 _sig("swg_debug_bounds_last", C.c_int, [_vp, _vp])
 _sig("swg_debug_sort_count", C.c_ulong, [])
 _sig("swg_debug_engine", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_int, _vp])
@@ -935,6 +942,40 @@ class Context:
         pflat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 32)), dtype=np.int8)
         return self._align_multi(lib.swg_align_bounds_multi_pssm, db, pflat, qoff, hits, False, None, bounds=True)
 
+    def align_stats(self, db, hits):
+        """align_bounds(db, hits) plus the counts of a tabular report's line (swg_align_stats): each dict also has n_ident,
+        n_match, n_gap_open and n_gap of the path align_hits would spell -- still from a forward pass alone."""
+        n = len(hits)
+        arr = (Hit * max(n, 1))()
+        for i, (sc, ix) in enumerate(hits):
+            arr[i].score, arr[i].index = int(sc), int(ix)
+        out = (Alignment * max(n, 1))()
+        cnt = (AlignCounts * max(n, 1))()
+        _check(lib.swg_align_stats(self.handle, db.handle, C.cast(arr, _vp), n, C.cast(out, _vp), C.cast(cnt, _vp)), self.handle)
+        return [self._stats_dict(out[i], cnt[i]) for i in range(n)]
+
+    def align_stats_multi(self, db, queries, hits):
+        """align_bounds_multi(db, queries, hits) plus align_stats' four counts per hit (swg_align_stats_multi)."""
+        qoff = np.zeros(len(queries) + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in queries])
+        qflat = np.ascontiguousarray(np.concatenate(queries) if len(queries) else np.zeros(0), dtype=np.int8)
+        return self._align_multi(lib.swg_align_stats_multi, db, qflat, qoff, hits, False, None, bounds=True, stats=True)
+
+    def align_stats_multi_pssm(self, db, pssms, hits):
+        """align_stats_multi with position-specific queries; identity is counted against each PSSM's consensus (the lowest
+        residue index in 1..31 whose score is the row's maximum over 1..31)."""
+        rows = [_pssm(p)[0] for p in pssms]
+        qoff = np.zeros(len(rows) + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([r.shape[0] for r in rows])
+        pflat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 32)), dtype=np.int8)
+        return self._align_multi(lib.swg_align_stats_multi_pssm, db, pflat, qoff, hits, False, None, bounds=True, stats=True)
+
+    @staticmethod
+    def _stats_dict(al, cnt):
+        a = {f: int(getattr(al, f)) for f, _ in Alignment._fields_ if f != "reserved"}
+        a.update((f, int(getattr(cnt, f))) for f, _ in AlignCounts._fields_)
+        return a
+
     def prune_last(self):
         """What the search last ended on this context left out (swg_prune_last) -> dict: pruned (bool), threshold (the
         last T), pairs_skipped, pair_rows_skipped and pair_rows (rows in whole 4-row token blocks)."""
@@ -971,7 +1012,7 @@ class Context:
         _check(lib.swg_debug_bounds_last(self.handle, out.ctypes.data_as(_vp)), self.handle)
         return dict(zip(("kernel_pairs", "fallback_pairs", "launches", "column_limit"), (int(v) for v in out)))
 
-    def _align_multi(self, fn, db, qflat, qoff, hits, want_ops, ops_stride, bounds=False):
+    def _align_multi(self, fn, db, qflat, qoff, hits, want_ops, ops_stride, bounds=False, stats=False):
         nq = len(qoff) - 1
         if len(hits) != nq:
             raise ValueError("hits: %d rows for %d queries" % (len(hits), nq))
@@ -988,6 +1029,10 @@ class Context:
         ops = C.create_string_buffer(max(1, nq * k * stride)) if want_ops else None
         args = (self.handle, db.handle, qflat.ctypes.data_as(_vp), qoff.ctypes.data_as(_vp), nq, C.cast(arr, _vp), k,
                 C.cast(nh, _vp), C.cast(out, _vp))
+        if stats:
+            cnt = (AlignCounts * max(nq * k, 1))()
+            _check(fn(*args, C.cast(cnt, _vp)), self.handle)
+            return [[self._stats_dict(out[i * k + j], cnt[i * k + j]) for j in range(len(row))] for i, row in enumerate(hits)]
         _check(fn(*args) if bounds else fn(*args, C.cast(ops, _vp) if want_ops else None, stride), self.handle)
         raw = ops.raw if want_ops else None          # (one copy: .raw copies the whole buffer on every access)
         res = []

@@ -23,7 +23,10 @@
  *     segment: swg_search_gapless) instead of the alignment score; --prefilter N --topk K closes the pipeline: per query
  *     the gapless top-N become the candidate list of swg_search_lists, whose K best are reported (and aligned);
  *     --bounds with --topk K appends the coordinates and the length of every reported hit's alignment without its
- *     path (swg_align_bounds, with --allqueries swg_align_bounds_multi / _multi_pssm: no traceback is run).
+ *     path (swg_align_bounds, with --allqueries swg_align_bounds_multi / _multi_pssm: no traceback is run);
+ *     --tabular with --topk K appends one tab-separated line per reported hit in the columns of BLAST's -outfmt 6 up to
+ *     the coordinates, then the raw score (swg_align_stats, with --allqueries swg_align_stats_multi / _multi_pssm: the
+ *     identities and gap openings come from the same forward pass, no traceback is run).
  * There is no CPU backend: without a GPU the tool fails with a message.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -66,6 +69,10 @@ static void usage(const char *argv0, const char *err)
             "    --bounds             with --topk: append one line per reported hit, `Bounds #i: entry E score S query a..b entry c..d\n"
             "                         length N` (the alignment's coordinates, 0-based, end exclusive, and its number of steps; no\n"
             "                         alignment text); not with --align, --gapless or --gpus\n"
+            "    --tabular            with --topk: append `# Fields: query, entry, pident, length, mismatch, gapopen, qstart, qend, sstart,\n"
+            "                         send, score` and one tab-separated line per reported hit of positive score (identity in\n"
+            "                         percent of the alignment's length, coordinates 1-based and inclusive, the raw score; a\n"
+            "                         PSSM's identity is against its consensus); not with --align, --bounds, --gapless or --gpus\n"
             "    --timing             wall time of every phase (reading, packing, upload, search, printing) on stderr\n"
             "    --gpu <N>            HIP device ordinal [default: 0]\n"
             "    --gpus <N>           shard the database over GPUs 0..N-1 (RCCL top-K merge)\n"
@@ -186,7 +193,7 @@ int main(int argc, char **argv)
     const char *qpath = NULL, *dbpath = NULL, *savedb = NULL, *pssm_path = NULL, *pssmlist_path = NULL, *idlist_path = NULL, *cand_path = NULL;
     int print_seq = 0, print_fasta = 0, have_matrix = 0, packed = 0, allq = 0;
     long topk = 0, gpu = 0, gpus = 0, prefilter = 0, v;
-    int align = 0, gapless = 0, bounds = 0;
+    int align = 0, gapless = 0, bounds = 0, tabular = 0;
     if (argc == 1) usage(argv[0], NULL);
     for (int i = 1; i < argc; i++)
         if (!strcasecmp(argv[i], "--help") || !strcasecmp(argv[i], "-help") || !strcasecmp(argv[i], "-h"))
@@ -209,6 +216,8 @@ int main(int argc, char **argv)
             gapless = 1;
         } else if (!strcasecmp(a, "--bounds")) {
             bounds = 1;
+        } else if (!strcasecmp(a, "--tabular")) {
+            tabular = 1;
         } else if (!strcasecmp(a, "--timing")) {
             timing = 1;
         } else if (!strcasecmp(a, "--allqueries")) {
@@ -289,6 +298,11 @@ int main(int argc, char **argv)
     if (bounds && align) usage(argv[0], "--bounds reports coordinates without the alignments: it does not combine with --align (whose headers carry them)");
     if (bounds && gapless) usage(argv[0], "--bounds reports coordinates of gapped alignments: it does not combine with --gapless");
     if (bounds && gpus > 0) usage(argv[0], "--bounds works with one GPU (--gpu)");
+    if (tabular && topk == 0) usage(argv[0], "--tabular reports one tabular line for each of the --topk hits: give --topk K");
+    if (tabular && align) usage(argv[0], "--tabular reports counts without the alignments: it does not combine with --align");
+    if (tabular && bounds) usage(argv[0], "--tabular carries the coordinates itself: it does not combine with --bounds");
+    if (tabular && gapless) usage(argv[0], "--tabular reports gapped alignments: it does not combine with --gapless");
+    if (tabular && gpus > 0) usage(argv[0], "--tabular works with one GPU (--gpu)");
     if (pssm_path && allq) usage(argv[0], "--pssm scores one query: it does not combine with --allqueries");
     if (cand_path && !allq) usage(argv[0], "--candidates lists the entries of --allqueries' records: give --allqueries");
     if (cand_path && gpus > 0) usage(argv[0], "--candidates works with one GPU (--gpu)");
@@ -687,6 +701,7 @@ int main(int argc, char **argv)
     /* --allqueries --bounds: the coordinates of queries [bd_first, bd_first + bd_n) of the current chunk, hit j of query
      * bd_first + i at mq_bd[i*topk + j] */
     swg_alignment *mq_bd = NULL;
+    swg_align_counts *mq_ct = NULL; /* --tabular: the counts beside them */
     size_t bd_first = 0, bd_n = 0;
 next_query:
     if (cands) { /* this record's entries: marks for the printing, scores by entry */
@@ -776,22 +791,34 @@ next_query:
         free(ops);
         free(line);
     }
-    if (bounds && n_hits > 0) {
+    if ((bounds || tabular) && n_hits > 0) {
         /* the first record against the context's query; the others came with their chunk (below) */
         swg_alignment *bd = NULL;
+        swg_align_counts *ct = NULL;
         if (qi == 0) {
             bd = (swg_alignment *)calloc(n_hits, sizeof *bd);
-            if (!bd) return leave(EXIT_FAILURE);
-            if (swg_align_bounds(ctx, sdb, hits, n_hits, bd) != SWG_OK) {
+            ct = (swg_align_counts *)calloc(n_hits, sizeof *ct);
+            if (!bd || !ct) return leave(EXIT_FAILURE);
+            if ((tabular ? swg_align_stats(ctx, sdb, hits, n_hits, bd, ct) : swg_align_bounds(ctx, sdb, hits, n_hits, bd)) != SWG_OK) {
                 fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
                 return leave(EXIT_FAILURE);
             }
         }
         const swg_alignment *bd_q = bd ? bd : mq_bd + (qi - bd_first) * (size_t)topk;
-        for (size_t i = 0; i < n_hits; i++)
+        const swg_align_counts *ct_q = bd ? ct : mq_ct + (qi - bd_first) * (size_t)topk;
+        for (size_t i = 0; i < n_hits && bounds; i++)
             printf("Bounds #%lu: entry %u score %d query %u..%u entry %u..%u length %u\n", (unsigned long)i, bd_q[i].index,
                    bd_q[i].score, bd_q[i].q_begin, bd_q[i].q_end, bd_q[i].d_begin, bd_q[i].d_end, bd_q[i].n_ops);
+        if (tabular) printf("# Fields: query, entry, pident, length, mismatch, gapopen, qstart, qend, sstart, send, score\n");
+        for (size_t i = 0; i < n_hits && tabular; i++) {
+            const swg_alignment *a = &bd_q[i];
+            if (a->score <= 0) continue; /* no alignment: no line */
+            printf("%s\t%s\t%.2f\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%d\n", qname, packed ? "" : db.names + db.name_off[a->index],
+                   100.0 * ct_q[i].n_ident / a->n_ops, a->n_ops, ct_q[i].n_match - ct_q[i].n_ident, ct_q[i].n_gap_open,
+                   a->q_begin + 1, a->q_end, a->d_begin + 1, a->d_end, a->score);
+        }
         free(bd);
+        free(ct);
     }
     if (allq && ++qi < q.n) {
         /* The database stays resident; the remaining queries go through swg_search_multi in chunks (one
@@ -926,7 +953,7 @@ next_query:
             }
             al_records += al_n;
         }
-        if (bounds && qi >= bd_first + bd_n) {
+        if ((bounds || tabular) && qi >= bd_first + bd_n) {
             /* the coordinates of the chunk's hits from this query on, in one swg_align_bounds_multi call (with --pssmlist
              * swg_align_bounds_multi_pssm); a call takes at most 2^20 hits */
             const size_t left = chunk_first + chunk_n - qi, kk = (size_t)topk;
@@ -935,15 +962,21 @@ next_query:
             bd_first = qi;
             bd_n = left < per ? left : per;
             free(mq_bd);
+            free(mq_ct);
             mq_bd = (swg_alignment *)calloc(bd_n * kk, sizeof *mq_bd);
-            if (!mq_bd) {
+            mq_ct = (swg_align_counts *)calloc(bd_n * kk, sizeof *mq_ct);
+            if (!mq_bd || !mq_ct) {
                 fprintf(stderr, "Error: out of memory\n");
                 return leave(EXIT_FAILURE);
             }
             const double t0 = now_ms();
-            const int rc = plist ? swg_align_bounds_multi_pssm(ctx, sdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff + at, bd_n,
-                                                               mq_hits + at * kk, kk, mq_nhits + at, mq_bd)
-                                 : swg_align_bounds_multi(ctx, sdb, qx, qoff + at, bd_n, mq_hits + at * kk, kk, mq_nhits + at, mq_bd);
+            const int8_t *pl = plist ? plist + (size_t)q.seq_off[chunk_first] * 32 : NULL;
+            const int rc = tabular ? (plist ? swg_align_stats_multi_pssm(ctx, sdb, pl, qoff + at, bd_n, mq_hits + at * kk, kk,
+                                                                         mq_nhits + at, mq_bd, mq_ct)
+                                            : swg_align_stats_multi(ctx, sdb, qx, qoff + at, bd_n, mq_hits + at * kk, kk,
+                                                                    mq_nhits + at, mq_bd, mq_ct))
+                           : plist ? swg_align_bounds_multi_pssm(ctx, sdb, pl, qoff + at, bd_n, mq_hits + at * kk, kk, mq_nhits + at, mq_bd)
+                                   : swg_align_bounds_multi(ctx, sdb, qx, qoff + at, bd_n, mq_hits + at * kk, kk, mq_nhits + at, mq_bd);
             if (rc != SWG_OK) {
                 fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
                 return leave(EXIT_FAILURE);
