@@ -157,7 +157,11 @@ int swg_abi_version(void);
  * top-K selection and read-out of a search run on their own stream, beside the fill of the search
  * queued next), "batch" (8 default: pairs one work-queue request claims where pairs are short -- at most
  * "batch_blocks" 4-row token blocks long (0 default: about 40 us of work at the launch's geometry: 30 blocks at 2
- * columns per lane, 5 at 32); batch 0 / 1: every request claims one pair). */
+ * columns per lane, 5 at 32); batch 0 / 1: every request claims one pair), "batch_geometry" (0 default: a batch of
+ * queries -- swg_search_multi*, swg_search_lists* -- with cols_per_wave or group_lanes set is searched one query after
+ * another, each at that geometry | 1: the batch itself takes the two, as one class and in one pass, where every other
+ * rule of its planner allows -- the tests' way to every batch instantiation; max_waves and workgroups still send it one
+ * by one). */
 int swg_set_option(swg_ctx *ctx, const char *key, long value);
 
 /* Replaces scoring_t for the path (reference src/alignment_scoring.h:21-37):

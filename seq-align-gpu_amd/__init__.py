@@ -216,6 +216,8 @@ _sig("swg_debug_plan", C.c_int, [_vp, C.c_size_t, C.c_int, _vp])
 _sig("swg_debug_plan_f16", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_long, _vp])
 _sig("swg_debug_plan_gapless", C.c_int, [_vp, C.c_size_t, C.c_int, _vp])
 _sig("swg_debug_plan_forced", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int, C.c_long, C.c_int, _vp])
+_sig("swg_debug_plan_batch", C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, _vp])
+_sig("swg_debug_plan_lists", C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, _vp])
 _sig("swg_debug_launch_log", None, [C.c_int])
 _sig("swg_debug_launch_log_read", C.c_size_t, [_vp, C.c_size_t])
 _sig("swg_debug_split", C.c_int, [_vp, C.c_size_t, C.c_uint64, _vp])
@@ -633,6 +635,39 @@ class Database:
                 "last_pass_cols", "fma", "lds_bytes", "long_fma")
         d = dict(zip(keys, (int(v) for v in out)))
         d["planned"] = d["classes"] > 0
+        return d
+
+    _BATCH_PLAN_KEYS = ("batch", "K", "G", "W", "per_cu", "qq", "lds_bytes", "classes")
+
+    def debug_plan_batch(self, lq_max, n_queries, form=2, qq=True, cols=0, group=0, batch_geometry=0, n_cu=256):
+        """Test hook: what search_multi launches for n_queries queries, the longest of lq_max columns, on cells of `form`
+        (0 packed int16, 2 packed f16: the hook has no scoring system) with options qq, cols_per_wave, group_lanes and
+        batch_geometry, under engine = 2, no device needed -> dict(batch: launched as one batch -- False: one query after
+        another, and the rest zero --, K, G, W, per_cu: workgroups per CU, qq: two queries per lane, lds_bytes of a
+        workgroup, classes)."""
+        out = np.zeros(8, dtype=np.int32)
+        _check(lib.swg_debug_plan_batch(self.handle, lq_max, n_queries, n_cu, form, 1 if qq else 0, cols, group, batch_geometry,
+                                        out.ctypes.data_as(_vp)))
+        d = dict(zip(self._BATCH_PLAN_KEYS, (int(v) for v in out)))
+        d["batch"], d["qq"] = bool(d["batch"]), bool(d["qq"])
+        return d
+
+    def debug_plan_lists(self, lists, lq_max, form=2, cols=0, group=0, batch_geometry=0, n_cu=256, lengths=None):
+        """Test hook: the same for search_lists and one candidate list per query: the job table (debug_list_jobs) is
+        described to the library by its pairs' lengths.  lengths: residues of every sequence by original index (default: of
+        the sequences this database was packed from)."""
+        if lengths is None:
+            lengths = np.diff(self._off.astype(np.int64))
+        slots, _ = self.debug_list_jobs(lists)
+        order = self.order()
+        lens = np.zeros(slots.size, dtype=np.uint32)
+        held = slots != 0xFFFFFFFF
+        lens[held] = np.asarray(lengths, dtype=np.int64)[order[slots[held]]]
+        out = np.zeros(8, dtype=np.int32)
+        _check(lib.swg_debug_plan_lists(lens.ctypes.data_as(_vp), lens.size // 2, lq_max, n_cu, form, cols, group, batch_geometry,
+                                        out.ctypes.data_as(_vp)))
+        d = dict(zip(self._BATCH_PLAN_KEYS, (int(v) for v in out)))
+        d["batch"], d["qq"] = bool(d["batch"]), bool(d["qq"])
         return d
 
     def debug_plan_gapless(self, lq, n_cu=256):

@@ -321,6 +321,10 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
         ctx->opt_last_pass = value != 0;
     } else if (!strcmp(key, "qq")) {
         ctx->opt_qq = value != 0;
+    } else if (!strcmp(key, "batch_geometry")) {
+        if (value != 0 && value != 1)
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "batch_geometry must be 0 (a forced geometry sends a batch one by one) or 1 (the batch takes it)");
+        ctx->opt_batch_geometry = value;
     } else if (!strcmp(key, "long_helps")) {
         ctx->opt_long_helps = value != 0;
     } else if (!strcmp(key, "segment_blocks")) {
@@ -2817,6 +2821,112 @@ static int multi_rows_ok(swg_ctx *ctx, const MultiBufs &B, const SwgBatchPlan &P
     return SWG_OK;
 }
 
+// The geometry of a batch launch: what plan_batch and plan_lists decide once the cells are known, and what the test
+// hooks swg_debug_plan_batch / swg_debug_plan_lists answer without a device -- one spelling for the three of them.
+// cols / group: options cols_per_wave and group_lanes.  A set one sends the batch one by one (false) unless option
+// batch_geometry is 1: then the planner is asked for exactly that geometry with long split -1 (one class), as a forced
+// single search asks it.  Whatever the planner answers, every class must take the longest query in one pass.
+struct SwgBatchAsk {
+    size_t lq_max;
+    int n_cu;
+    double copies;     // queries that share the launch (the planner's throughput terms grow with it)
+    int form;          // 0 packed int16, 2 packed f16
+    long cols, group, batch_geometry;
+    long long_split;   // option long_split, for a geometry left free
+    bool allow_split;  // a long class may run beside the bulk (not for candidate lists)
+};
+static bool batch_plan_work(const swg_db *db, const SwgBatchAsk &a, SwgDiagWork *wk)
+{
+    const bool forced = a.cols != 0 || a.group != 0;
+    if (forced && a.batch_geometry == 0) return false;
+    if (swg_plan_diag_work(db, a.lq_max, a.n_cu, a.cols, a.group, 0, forced ? -1 : a.long_split, a.allow_split, true, wk, a.copies, a.form, 1) <= 0)
+        return false; // (batches: v_perm_b32 pairing)
+    for (int c = 0; c < wk->n_classes; ++c)
+        if (wk->plan[c].npass != 1 || (size_t)wk->plan[c].G * wk->plan[c].K < a.lq_max) return false;
+    return true;
+}
+// Two queries per lane (swg_diag_qq_kernel) where the batch runs on the f16 cells, option "qq" allows it and the pairs'
+// 4-byte profile fits LDS beside the other class's: then each class gets the W it is launched with, and *per_cu the bulk's
+// workgroups per CU (LDS decides).
+static bool batch_pairs_queries(SwgDiagWork *wk, int form, bool qq_on, int *per_cu)
+{
+    int qq_W = 0;
+    if (form != 2 || !qq_on || !lds_bound_workgroup(*wk, INT_MAX, 0, &qq_W, per_cu)) return false;
+    wk->plan[0].W = qq_W;
+    if (wk->n_classes == 2) wk->plan[1].W = 4;
+    return true;
+}
+// Profile bytes of one grid row of a class: (qq) 128 bytes per column per query PAIR, else 64 per query.
+static size_t batch_prof_row_bytes(const SwgDiagPlan &pl, bool qq)
+{
+    return (size_t)pl.G * (qq ? (size_t)swg_q32_padded_cols(pl.K) * 128 : (size_t)swg_diag_padded_cols(pl.K) * 64);
+}
+// LDS bytes of one workgroup of a class, and the workgroups of it that a CU holds.
+static size_t batch_class_lds_bytes(const SwgDiagPlan &pl, bool qq)
+{
+    return qq ? swg_diag32q_lds_bytes(pl.K, pl.G, pl.W) : swg_diag_dyn_lds_bytes(pl.K, pl.G, pl.W);
+}
+static int batch_class_per_cu(const SwgDiagPlan &pl, bool qq, int qq_per_cu, int c)
+{
+    return qq ? (c == 0 ? qq_per_cu : 1) : swg_workgroups_per_cu(swg_diag_variant_info(pl.variant).max_waves, pl.W, batch_class_lds_bytes(pl, false));
+}
+// The planner's model of a lists call's job table: its pairs' lengths (first, second sequence), longest first -- the
+// planner reads lengths and nothing else.
+static void lists_model_db(std::vector<std::pair<uint32_t, uint32_t>> *pairs, swg_db *M)
+{
+    const size_t np = pairs->size();
+    std::sort(pairs->begin(), pairs->end(), std::greater<std::pair<uint32_t, uint32_t>>());
+    M->n_local = 2 * np;
+    M->n_bins = (uint32_t)((2 * np + SWG_BIN - 1) / SWG_BIN);
+    M->lens.assign((size_t)M->n_bins * SWG_BIN, 0u);
+    for (size_t p = 0; p < np; ++p) M->lens[2 * p] = (*pairs)[p].first, M->lens[2 * p + 1] = (*pairs)[p].second;
+}
+static void debug_plan_answer(const SwgDiagWork &wk, bool qq, int qq_per_cu, int32_t *out)
+{
+    const SwgDiagPlan &b = wk.plan[0];
+    const int32_t v[8] = {1, b.K, b.G, b.W, batch_class_per_cu(b, qq, qq_per_cu, 0), qq ? 1 : 0, (int32_t)batch_class_lds_bytes(b, qq), wk.n_classes};
+    memcpy(out, v, sizeof v);
+}
+// Test hooks (swg_host_internal.h): what plan_batch / plan_lists launch for a batch whose cells are `form`, no device.
+extern "C" int swg_debug_plan_batch(const swg_db *db, size_t lq_max, size_t n_queries, int n_cu, int form, int qq_on, long cols, long group,
+                                    long batch_geometry, int32_t *out)
+{
+    if (!db || !out || lq_max == 0 || n_cu <= 0 || (form != 0 && form != 2) || cols < 0 || group < 0) return SWG_ERR_ARG;
+    memset(out, 0, 8 * sizeof(int32_t));
+    if (n_queries < 2 || db->n_bins == 0) return SWG_OK; // (plan_batch: a batch of one is a single search)
+    try {
+        SwgDiagWork wk;
+        const SwgBatchAsk ask = {lq_max, n_cu, (double)std::min<size_t>(256, n_queries), form, cols, group, batch_geometry, 0, true};
+        if (!batch_plan_work(db, ask, &wk)) return SWG_OK;
+        int per_cu = 1;
+        const bool qq = batch_pairs_queries(&wk, form, qq_on != 0, &per_cu);
+        debug_plan_answer(wk, qq, per_cu, out);
+    } catch (const std::exception &) {
+        return SWG_ERR_NOMEM;
+    }
+    return SWG_OK;
+}
+extern "C" int swg_debug_plan_lists(const uint32_t *pair_lens, size_t n_pairs, size_t lq_max, int n_cu, int form, long cols, long group,
+                                    long batch_geometry, int32_t *out)
+{
+    if (!out || (n_pairs && !pair_lens) || lq_max == 0 || n_cu <= 0 || (form != 0 && form != 2) || cols < 0 || group < 0) return SWG_ERR_ARG;
+    memset(out, 0, 8 * sizeof(int32_t));
+    if (n_pairs == 0) return SWG_OK; // (nothing to launch)
+    try {
+        std::vector<std::pair<uint32_t, uint32_t>> pairs(n_pairs);
+        for (size_t p = 0; p < n_pairs; ++p) pairs[p] = std::make_pair(pair_lens[2 * p], pair_lens[2 * p + 1]);
+        swg_db M;
+        lists_model_db(&pairs, &M);
+        SwgDiagWork wk;
+        const SwgBatchAsk ask = {lq_max, n_cu, 1.0, form, cols, group, batch_geometry, -1, false};
+        if (!batch_plan_work(&M, ask, &wk) || wk.n_classes != 1) return SWG_OK;
+        debug_plan_answer(wk, false, 1, out);
+    } catch (const std::exception &) {
+        return SWG_ERR_NOMEM;
+    }
+    return SWG_OK;
+}
+
 // What the call's arguments and the context's state rule out, and what the batch is worth whichever way it is searched:
 // the real cells and the algorithmic bytes of all its queries.
 static int validate_batch(swg_ctx *ctx, const swg_db *db, const MultiQueries &mq, const swg_hit *topk_out, size_t k, swg_stats *st)
@@ -2857,9 +2967,10 @@ static int plan_batch(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, bool wan
     P.go = ctx->gap_open + ctx->gap_extend;
     P.ge = ctx->gap_extend;
     for (size_t i = 0; i < mq.n; ++i) P.lq_max = std::max(P.lq_max, mq.len(i));
+    // (options max_waves and workgroups: one by one; cols_per_wave and group_lanes: batch_plan_work decides)
     bool fast = ctx->gap_open <= 0 && ctx->gap_extend <= 0 && -P.go <= SWG_I16_CEILING && ctx->opt_force_bits != 32 &&
-                ctx->opt_engine != 1 && ctx->opt_dynamic != 0 && db->n_bins > 0 && mq.n > 1 && ctx->opt_cols == 0 &&
-                ctx->opt_group == 0 && ctx->opt_max_waves == 0 && ctx->opt_workgroups == 0;
+                ctx->opt_engine != 1 && ctx->opt_dynamic != 0 && db->n_bins > 0 && mq.n > 1 && ctx->opt_max_waves == 0 &&
+                ctx->opt_workgroups == 0;
     // no score of any query may reach the int16 ceiling: each query's swg_score_bound, as a single search bounds it
     const uint64_t longest = (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK;
     for (size_t i = 0; i < mq.n && fast; ++i) {
@@ -2875,10 +2986,10 @@ static int plan_batch(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, bool wan
     int rc = ensure_pair_tokens(ctx, db);
     if (rc != SWG_OK) return rc;
     SwgDiagWork &wk = P.wk;
-    fast = db->ptok.ok && swg_plan_diag_work(db, P.lq_max, ctx->n_cu, 0, 0, 0, ctx->opt_long_split, true, true, &wk, (double)P.first_chunk,
-                                             P.form, 1) > 0; // (batches: v_perm_b32 pairing)
-    for (int c = 0; fast && c < wk.n_classes; ++c)
-        fast = wk.plan[c].npass == 1 && diag_class_is_dynamic(ctx, db, wk.plan[c]) && (size_t)wk.plan[c].G * wk.plan[c].K >= P.lq_max;
+    const SwgBatchAsk ask = {P.lq_max, ctx->n_cu, (double)P.first_chunk, P.form, ctx->opt_cols, ctx->opt_group, ctx->opt_batch_geometry,
+                             ctx->opt_long_split, true};
+    fast = db->ptok.ok && batch_plan_work(db, ask, &wk);
+    for (int c = 0; fast && c < wk.n_classes; ++c) fast = diag_class_is_dynamic(ctx, db, wk.plan[c]);
     // A database of short sequences is faster on the systolic engine, one query after another, than as a batch on
     // the lane groups: 16 queries against 500 000 peptides 3 720 GCUPS as a batch, ~7 000 one by one.  Same
     // comparison as a single search makes, per query.
@@ -2891,12 +3002,7 @@ static int plan_batch(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, bool wan
     // wavefront the instantiation allows): four 57 KB workgroups of four do not fit a CU, two of eight do -- the first
     // version of this path ran at two wavefronts per SIMD and lost to the perm.  No room beside the long class: two
     // sequences per lane, as without the option.
-    int qq_W = 0;
-    P.qq = P.form == 2 && ctx->opt_qq != 0 && lds_bound_workgroup(wk, INT_MAX, 0, &qq_W, &P.qq_per_cu);
-    if (P.qq) {
-        wk.plan[0].W = qq_W;
-        if (wk.n_classes == 2) wk.plan[1].W = 4;
-    }
+    P.qq = batch_pairs_queries(&wk, P.form, ctx->opt_qq != 0, &P.qq_per_cu);
     // Top-K only (no score array asked for): selected on the device for the whole batch in three launches, and a few
     // hundred keys per query come back instead of every score (round 3: with 32 queries against 100 000 sequences the
     // copy and the host's selection took longer than the fill: 82 ms of wall time for 49 ms of device time).
@@ -2909,8 +3015,8 @@ static int plan_batch(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, bool wan
     P.class_queue_dwords = SWG_DYN_SHARDS * SWG_DYN_SHARD_STRIDE;
     P.rank_word_base = P.chunk_queries * 2 * P.class_queue_dwords; // (the queues serve a full chunk's grid rows)
     P.queue_dwords = P.rank_word_base + 2 * SWG_DYN_SIMD_SLOTS;
-    for (int c = 0; c < wk.n_classes; ++c) // (qq: one profile of 128 bytes per column per query PAIR, and an odd batch's last pair is a whole pair)
-        P.prof_row_bytes[c] = (size_t)wk.plan[c].G * (P.qq ? (size_t)swg_q32_padded_cols(wk.plan[c].K) * 128 : (size_t)swg_diag_padded_cols(wk.plan[c].K) * 64);
+    for (int c = 0; c < wk.n_classes; ++c) // (qq: an odd batch's last pair is a whole pair)
+        P.prof_row_bytes[c] = batch_prof_row_bytes(wk.plan[c], P.qq);
     P.one_launch = true;
     *plan = P;
     return SWG_OK;
@@ -3057,8 +3163,7 @@ static void batch_chunk_workgroups(const SwgBatchPlan &P, size_t Qrows, int n_cu
     *groups0 = 1;
     for (int c = 0; c < wk.n_classes; ++c) {
         const SwgDiagPlan &pl = wk.plan[c];
-        const int per_cu = P.qq ? (c == 0 ? P.qq_per_cu : 1)
-                                : swg_workgroups_per_cu(swg_diag_variant_info(pl.variant).max_waves, pl.W, swg_diag_dyn_lds_bytes(pl.K, pl.G, pl.W));
+        const int per_cu = batch_class_per_cu(pl, P.qq, P.qq_per_cu, c);
         int total = n_cu * per_cu;
         if (wk.n_classes == 2 && !P.qq) total = c == 1 ? n_cu : std::max(n_cu, total - n_cu); // one wavefront per SIMD for the long class
         const uint64_t items = (wk.pair_end[c] - wk.pair_begin[c]) * (P.qq ? 2u : 1u); // pairs, or (qq) single sequences
@@ -3430,8 +3535,7 @@ static int plan_lists(swg_ctx *ctx, const swg_db *db, const MultiQueries &mq, co
     P.ge = ctx->gap_extend;
     for (size_t i = 0; i < mq.n; ++i) P.lq_max = std::max(P.lq_max, mq.len(i));
     bool fast = ctx->gap_open <= 0 && ctx->gap_extend <= 0 && -P.go <= SWG_I16_CEILING && ctx->opt_force_bits != 32 &&
-                ctx->opt_engine != 1 && ctx->opt_dynamic != 0 && !too_large && ctx->opt_cols == 0 && ctx->opt_group == 0 &&
-                ctx->opt_max_waves == 0 && ctx->opt_workgroups == 0;
+                ctx->opt_engine != 1 && ctx->opt_dynamic != 0 && !too_large && ctx->opt_max_waves == 0 && ctx->opt_workgroups == 0;
     const ListChunk *big = nullptr;
     for (const ListChunk &C : chunks) {
         if (!big || C.blocks() > big->blocks()) big = &C;
@@ -3459,28 +3563,23 @@ static int plan_lists(swg_ctx *ctx, const swg_db *db, const MultiQueries &mq, co
             const uint32_t sy = big->J.slots[2 * p + 1];
             pairs[p] = std::make_pair(root->lens[big->J.slots[2 * p]], sy == 0xFFFFFFFFu ? 0u : root->lens[sy]);
         }
-        std::sort(pairs.begin(), pairs.end(), std::greater<std::pair<uint32_t, uint32_t>>());
-        M.n_local = 2 * np;
-        M.n_bins = (uint32_t)((2 * np + SWG_BIN - 1) / SWG_BIN);
-        M.lens.assign((size_t)M.n_bins * SWG_BIN, 0u);
-        for (size_t p = 0; p < np; ++p) M.lens[2 * p] = pairs[p].first, M.lens[2 * p + 1] = pairs[p].second;
+        lists_model_db(&pairs, &M);
     }
     SwgDiagWork wk;
-    fast = swg_plan_diag_work(&M, P.lq_max, ctx->n_cu, 0, 0, 0, -1, false, true, &wk, 1.0, P.form, 1) == 1 && wk.plan[0].npass == 1 &&
-           (size_t)wk.plan[0].G * wk.plan[0].K >= P.lq_max;
+    const SwgBatchAsk ask = {P.lq_max, ctx->n_cu, 1.0, P.form, ctx->opt_cols, ctx->opt_group, ctx->opt_batch_geometry, -1, false};
+    fast = batch_plan_work(&M, ask, &wk) && wk.n_classes == 1;
     if (!fast) {
         plan->lq_max = P.lq_max;
         return SWG_OK;
     }
     P.pl = wk.plan[0];
-    P.resident_wgs = ctx->n_cu * swg_workgroups_per_cu(swg_diag_variant_info(P.pl.variant).max_waves, P.pl.W,
-                                                       swg_diag_dyn_lds_bytes(P.pl.K, P.pl.G, P.pl.W));
+    P.resident_wgs = ctx->n_cu * batch_class_per_cu(P.pl, false, 1, 0);
     static const bool equal_shares = getenv("SWG_LISTS_EQUAL_SHARES") != nullptr;
     P.equal_shares = equal_shares;
     P.class_queue_dwords = SWG_DYN_SHARDS * SWG_DYN_SHARD_STRIDE;
     P.rank_word_base = P.chunk_queries * P.class_queue_dwords; // (the queues serve a full chunk's rows)
     P.queue_dwords = P.rank_word_base + SWG_DYN_SIMD_SLOTS;
-    P.prof_row_bytes = (size_t)P.pl.G * (size_t)swg_diag_padded_cols(P.pl.K) * 64;
+    P.prof_row_bytes = batch_prof_row_bytes(P.pl, false);
     P.one_launch = true;
     *plan = P;
     return SWG_OK;

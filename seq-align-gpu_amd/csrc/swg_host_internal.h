@@ -416,6 +416,7 @@ struct swg_ctx {
     size_t query_len() const { return query_pssm ? pssm.size() / 32 : query.size(); }
     // options
     long opt_force_bits = 0, opt_cols = 0, opt_max_waves = 0, opt_workgroups = 0, opt_engine = 0, opt_group = 0, opt_long_split = 0, opt_autotune = 1, opt_dynamic = 1, opt_prio_share = 150, opt_long_helps = 0, opt_wide = 1, opt_side_readout = 1, opt_f16 = 1, opt_qq = 1, opt_last_pass = 1, opt_f16_pair = 0;
+    long opt_batch_geometry = 0; // 1: a batch (swg_search_multi*, swg_search_lists*) takes options cols_per_wave / group_lanes instead of going one by one (tests)
     long opt_wave_budget = 0, opt_q32_waves = 0;
     long opt_bounds_groups = 0; // lane groups of a bounds launch (swg_align_bounds*), 0: auto (option "bounds_groups": tests)
     uint32_t bounds_last[4] = {0, 0, 0, 0}; // the last bounds call: pairs on its kernel, pairs on the fallback, its launches, its column limit
@@ -522,6 +523,18 @@ extern "C" int swg_debug_plan_f16(const swg_db *db, size_t lq, int n_cu, long f1
 // per lane, is 0 with last_pass = 0 (option last_pass).
 extern "C" int swg_debug_plan_forced(const swg_db *db, size_t lq, int n_cu, long cols, long group, long waves, int form,
                                      long f16_pair, int last_pass, int32_t *out);
+// test hooks: what a batch launches on cells of `form` (0 packed int16, 2 packed f16; the hooks have no scoring system, so
+// the caller says which cells the score bounds allow), without a device: the geometry rules of plan_batch and plan_lists
+// (swg_api.cpp, which share them with these hooks) for options cols_per_wave = cols, group_lanes = group (0 = free),
+// batch_geometry and, for a batch, qq.  The engine choice (systolic against lane groups) is not part of the answer: it is
+// the answer under option engine = 2.  out[0..7] = launched as a batch (0: one by one, and the rest zero), K, G, W,
+// workgroups per CU, two queries per lane, LDS bytes of a workgroup, classes.  swg_debug_plan_batch: n_queries queries, the
+// longest of lq_max columns, against db.  swg_debug_plan_lists: a job table of n_pairs pairs, pair p of sequences of
+// pair_lens[2p] and pair_lens[2p + 1] residues (0: the empty slot of an odd list), in any order.
+extern "C" int swg_debug_plan_batch(const swg_db *db, size_t lq_max, size_t n_queries, int n_cu, int form, int qq_on, long cols, long group,
+                                    long batch_geometry, int32_t *out);
+extern "C" int swg_debug_plan_lists(const uint32_t *pair_lens, size_t n_pairs, size_t lq_max, int n_cu, int form, long cols, long group,
+                                    long batch_geometry, int32_t *out);
 // test hook: the launch log (swg_launch_log_add, swg_internal.h).  swg_debug_launch_log(on): clears the log and switches
 // it on (1) or off (0); off by default.  While on, the launchers append records until SWG_LAUNCH_LOG_CAP are held (later
 // launches are counted, not kept).  swg_debug_launch_log_read: copies up to cap records of SWG_LAUNCH_LOG_FIELDS int32

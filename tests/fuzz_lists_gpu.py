@@ -2,18 +2,22 @@
 """Randomised parity soak of swg_search_lists (every query of a batch against its own candidate list): batch sizes
 from {1, 3, 255, 257}, lists of 0 .. 300 entries with duplicates and overlap between the queries' lists, random query
 lengths (some beyond one pass: the batch then goes one list after another), tables, gap scores, cell forms (option f16
-0 / 1), with and without the score array.  Every score against the int32 oracle at every entry, every hit list against
-the oracle's order over the list's distinct entries.  Stops at the first mismatch or error.
+0 / 1), now and then a forced batch geometry (option batch_geometry = 1 with cols_per_wave and group_lanes, drawn as
+tests/fuzz_multi_gpu.py draws it), with and without the score array.  Every score against the int32 oracle at every
+entry, every hit list against the oracle's order over the list's distinct entries.  Stops at the first mismatch or error.
 usage: python tests/fuzz_lists_gpu.py [seconds] [seed]"""
 import sys, time, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import swg_loader
+from fuzz_multi_gpu import forced_geometry
 
 
 def main(budget=60.0, seed=1):
     swg = swg_loader.load(); orc = swg_loader.oracle()
     rng = np.random.default_rng(seed)
+    grng = np.random.default_rng([seed, 0xBA7C])     # the forced geometries' own stream: the other draws stay what they were
     ctx = swg.Context(0)
     ctx.set_option("autotune", 0)
     mats = ["BLOSUM62", "PAM250", "BLOSUM45"]
@@ -56,6 +60,10 @@ def main(budget=60.0, seed=1):
         ctx.set_scoring(tab, go, ge)
         f16 = int(rng.choice([0, 1]))
         ctx.set_option("f16", f16)
+        geom = forced_geometry(grng, max(qlens)) if grng.random() < 0.2 else None
+        ctx.set_option("batch_geometry", 1 if geom else 0)
+        ctx.set_option("cols_per_wave", geom[0] if geom else 0)
+        ctx.set_option("group_lanes", geom[1] if geom else 0)
         db = swg.Database(flat, off).upload(ctx)
         k = int(rng.choice([0, 1, 4, 30, 400]))
         want_scores = bool(rng.random() < 0.6) or k == 0
@@ -71,8 +79,8 @@ def main(budget=60.0, seed=1):
                 exp = [(-s, j) for s, j in sorted((-int(want[j]), int(j)) for j in sel)[:k]]
                 ok = (not want_scores or np.array_equal(got[i], want[l])) and hits[i] == exp
             if not ok:
-                print("MISMATCH case", cases, "query", i, "of", nq, "lq", len(q), "n", n, "list", len(l), "gaps", go, ge, "f16", f16, "k", k,
-                      "scores asked", want_scores, "stats", st)
+                print("MISMATCH case", cases, "query", i, "of", nq, "lq", len(q), "n", n, "list", len(l), "gaps", go, ge, "f16", f16,
+                      "geometry", geom, "k", k, "scores asked", want_scores, "stats", st)
                 return 1
         db.close()
         cases += 1

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Randomised parity soak of swg_search_multi (batches of queries against one resident database): random batch
 sizes and query lengths (equal, mixed, some beyond one pass, some high-scoring relatives of database sequences),
-tables, gap scores, cell forms (option f16 0 / 1 / 2), two queries per lane on or off (option qq), with and without
-the score array (hits only: the batch's top-K selected on the device).  Every score against the int32 oracle, every
+tables, gap scores, cell forms (option f16 0 / 1 / 2), two queries per lane on or off (option qq), now and then a forced
+batch geometry (option batch_geometry = 1 with cols_per_wave and group_lanes: the fewest columns per lane that take the
+longest query in one pass of the drawn width, or any K), with and without the score array (hits only: the batch's top-K selected on the device).  Every score against the int32 oracle, every
 hit list against the oracle's order.
 scoring "edges": the tables and gap points of tests/scoring_edges.py, the first query one of two flanks with split_db's
 relatives planted among the random sequences.
@@ -37,10 +38,19 @@ def edge_case(rng, b62, queries, seqs):
     return sub, go, ge, queries, seqs
 
 
+def forced_geometry(grng, lq_max):
+    """A (K, lanes) to force on a batch: mostly the fewest columns per lane that take lq_max in one pass at a drawn width
+    (the batch then launches at that geometry), else any K of the instantiations (one by one where it needs passes)."""
+    G = int(grng.choice([16, 32, 64]))
+    K = int(min(32, max(2, -(-lq_max // G)))) if grng.random() < 0.75 else int(grng.integers(2, 33))
+    return K, G
+
+
 def main(budget=300.0, seed=1, scoring="classic"):
     swg = swg_loader.load(); orc = swg_loader.oracle()
     assert scoring in ("classic", "edges")
     rng = np.random.default_rng(seed)
+    grng = np.random.default_rng([seed, 0xBA7C])     # the forced geometries' own stream: the other draws stay what they were
     ctx = swg.Context(0)
     mats = ["BLOSUM62", "PAM250", "BLOSUM45"]
     t_end = time.time() + budget
@@ -90,7 +100,7 @@ def main(budget=300.0, seed=1, scoring="classic"):
             ctx.set_option(k_, 0)
         for k_ in ("work_queue", "wide16", "autotune", "side_readout", "f16", "qq", "last_pass"):
             ctx.set_option(k_, 1)
-        ctx.set_option("batch", 8); ctx.set_option("batch_blocks", 0)
+        ctx.set_option("batch", 8); ctx.set_option("batch_blocks", 0); ctx.set_option("batch_geometry", 0)
         opts = {}
         if rng.random() < 0.25: opts["batch"] = int(rng.choice([0, 3, 8]))
         if rng.random() < 0.25: opts["batch_blocks"] = int(rng.choice([1, 64, 100000]))
@@ -98,6 +108,9 @@ def main(budget=300.0, seed=1, scoring="classic"):
         if rng.random() < 0.3: opts["f16"] = int(rng.choice([0, 2]))
         if rng.random() < 0.2: opts["autotune"] = 0
         if rng.random() < 0.15: opts["long_split"] = int(rng.choice([-1, 100, 500]))
+        if grng.random() < 0.2:
+            opts["batch_geometry"] = 1
+            opts["cols_per_wave"], opts["group_lanes"] = forced_geometry(grng, max(len(q_) for q_ in queries))
         for k_, v in opts.items(): ctx.set_option(k_, v)
         ctx.set_query(queries[0])
         db = swg.Database(flat, off).upload(ctx)

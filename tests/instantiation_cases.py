@@ -176,25 +176,33 @@ def truth(case):
     return _truth(case["lq"], case["scoring"], case["gaps"][0], case["gaps"][1], case["family"] == "gapless")
 
 
+def query_key(q):
+    """A query as column_best takes it: its bytes (hashable, so the result is computed once per query)."""
+    return np.ascontiguousarray(q, dtype=np.int8).tobytes()
+
+
 @functools.lru_cache(maxsize=None)
-def column_best(scoring, go, ge):
-    """int32 [DB_COUNT, QLEN]: the best match-state cell of every query column, per sequence, in plain numpy -- the
-    oracle's three-state recurrence (oracle/sw_oracle.c), all sequences at once, one residue row at a time.  A cell depends
-    on the columns to its left only, so the score against the prefix of lq columns is column_best[:, :lq].max(1): the host
-    test holds that against the oracle for every case, bit for bit."""
+def column_best(scoring, go, ge, q=None):
+    """int32 [DB_COUNT, columns]: the best match-state cell of every query column, per sequence, in plain numpy -- the
+    oracle's three-state recurrence (oracle/sw_oracle.c), all sequences at once, one residue row at a time.  q: the query
+    as query_key gives it, None for QUERY.  A cell depends on the columns to its left only, so the score against the
+    prefix of lq columns is column_best[:, :lq].max(1): the host tests hold that against the oracle for every case, bit
+    for bit."""
     import swg_loader
     flat, off = database()
     lens = np.diff(off).astype(np.int64)
     by_len = np.argsort(-lens, kind="stable")
     sub = np.asarray(table(swg_loader.load(), scoring), dtype=np.int32)
-    prof = sub[query().astype(np.int64)]                       # [QLEN, 32]
+    qa = query() if q is None else np.frombuffer(q, dtype=np.int8)
+    ncol = len(qa)
+    prof = sub[qa.astype(np.int64)]                            # [columns, 32]
     res = np.zeros((DB_COUNT, int(lens.max())), dtype=np.int64)
     for n in range(DB_COUNT):
         res[n, :lens[n]] = flat[int(off[n]):int(off[n + 1])]
     res = res[by_len]
-    go1, idx = go + ge, np.arange(QLEN + 1, dtype=np.int32)
-    H, A, B = (np.zeros((DB_COUNT, QLEN + 1), dtype=np.int32) for _ in range(3))
-    best = np.zeros((DB_COUNT, QLEN), dtype=np.int32)
+    go1, idx = go + ge, np.arange(ncol + 1, dtype=np.int32)
+    H, A, B = (np.zeros((DB_COUNT, ncol + 1), dtype=np.int32) for _ in range(3))
+    best = np.zeros((DB_COUNT, ncol), dtype=np.int32)
     for j in range(res.shape[1]):
         n = int((lens > j).sum())                              # the sequences that have a row j: the n longest
         Hp, Ap, Bp = H[:n], A[:n], B[:n]
