@@ -295,7 +295,13 @@ int swg_search_end(swg_ctx *ctx, int ticket, int32_t *scores_out, swg_hit *topk_
  * sequence's score -- read from a table of every block of residue classes, which is built on the
  * device in front of the first pruned search of a (query, scoring): 22^k x k x lq cell updates, 17 ms at k = 5 for
  * 3000 columns on an MI355X, paid once per query.  0: automatic, the largest k whose table costs at most half of what
- * its tighter cut is expected to save on this range (small databases: 1).  Hits are the same under every value. */
+ * its tighter cut is expected to save on this range (small databases: 1).  "prune_segments" (default 0): the k-mer
+ * bound's table holds, per block, its best cell within each of 1..32 consecutive segments of the query's columns, and
+ * a sequence's blocks are taken in order -- a later block cannot score in an earlier segment; 1 is the
+ * unordered sum above, a larger value is never above it; the table is 22^k x segments x 2 bytes, refused above 96 MB
+ * (k = 5: up to 9 segments).  0: automatic -- with "prune_kmer" 0 the pair (k, segments) is chosen together from a
+ * fixed list (a database of millions of sequences: k = 4 in 32 segments), with "prune_kmer" forced the sum is
+ * unordered.  Hits are the same under every value. */
 typedef struct swg_prune_info {
     uint64_t pairs_skipped;
     uint64_t pair_rows_skipped;

@@ -231,6 +231,9 @@ _sig("swg_debug_prune_plan", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_kmer", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp])
 _sig("swg_debug_prune_kmer_choice", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_kmer_read", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp])
+_sig("swg_debug_prune_kmer_seg", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp])
+_sig("swg_debug_prune_kmer_choice_seg", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_kmer_seg_read", C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp])
 _sig("swg_debug_list_deal", C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 
 
@@ -475,12 +478,49 @@ def debug_prune_kmer(rows, query, gap_open, gap_extend, k, flat, offsets, table=
 
 def debug_prune_kmer_choice(forced=0, pruned=1, lq=3000, pair_rows=1900000000, table_rate=0, fill_rate=0):
     """Test hook (no device needed): the bound a search cuts by (swg_prune_kmer_choice) -> 0 (not pruned: nothing is
-    built), 1 (colmax), 4 or 5.  forced: option prune_kmer; rates in table cells and fill pair rows per second, 0: the
-    library's own for this lq."""
+    built), 1 (colmax), 4 or 5, with option prune_segments = 1 (the unsegmented bound; debug_prune_kmer_choice_seg has
+    the segments).  forced: option prune_kmer; rates in table cells and fill pair rows per second, 0: the library's own
+    for this lq."""
     a = np.array([forced, pruned, lq, pair_rows, table_rate, fill_rate], dtype=np.int64)
     out = np.zeros(1, dtype=np.int64)
     _check(lib.swg_debug_prune_kmer_choice(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
     return int(out[0])
+
+
+KMER_MAX_SEGMENTS = 32
+KMER_TABLE_BUDGET = 96 << 20   # bytes: the largest table of the k-mer bound a context builds (it admits k = 5 in 8 segments)
+
+
+def debug_prune_kmer_seg(rows, query, gap_open, gap_extend, k, segments, flat, offsets, table=True):
+    """Test hook (no device needed): debug_prune_kmer over `segments` (1..32) segments of the query's columns, each
+    ceil(lq / segments) wide.  -> (table uint16[22^k, segments] or None, U uint64[n]): every class block's best cell
+    within each segment, and the bound of each sequence with its blocks taken in order.  One segment is
+    debug_prune_kmer."""
+    r, rp = _i8(rows)
+    lq = r.size // 32
+    qp = None
+    if query is not None:
+        q, qp = _i8(query)
+        lq = q.size
+    f, fp = _i8(flat)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = off.size - 1
+    S = int(segments)
+    t = np.zeros((KMER_CLASSES ** int(k), S), dtype=np.uint16) if table and k in (4, 5) and 1 <= S <= KMER_MAX_SEGMENTS else None
+    u = np.zeros(max(n, 1), dtype=np.uint64)
+    _check(lib.swg_debug_prune_kmer_seg(rp, qp, lq, int(gap_open), int(gap_extend), int(k), S, fp, off.ctypes.data_as(_vp), n,
+                                        t.ctypes.data_as(_vp) if t is not None else None, u.ctypes.data_as(_vp)))
+    return t, u[:n]
+
+
+def debug_prune_kmer_choice_seg(forced=0, segments=0, pruned=1, lq=3000, pair_rows=1900000000, table_rate=0, fill_rate=0):
+    """Test hook (no device needed): debug_prune_kmer_choice with option prune_segments -> (k, S, the table's bytes,
+    whether a context builds that table: False beyond KMER_TABLE_BUDGET); (0, 0, 0, True) where nothing is pruned,
+    (1, 1, 0, True) for the colmax bound."""
+    a = np.array([forced, pruned, lq, pair_rows, table_rate, fill_rate, segments], dtype=np.int64)
+    out = np.zeros(4, dtype=np.int64)
+    _check(lib.swg_debug_prune_kmer_choice_seg(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
+    return int(out[0]), int(out[1]), int(out[2]), bool(out[3])
 
 
 PRUNE_PLAN_KEYS = ("mode", "k", "want_scores", "gap_open", "gap_extend", "bits", "use_diag", "n_classes", "work_queue", "both_forms",
@@ -1039,6 +1079,22 @@ class Context:
         _check(lib.swg_debug_prune_kmer_read(self.handle, db.handle, int(k or 0), t.ctypes.data_as(_vp) if t is not None else None,
                                              b.ctypes.data_as(_vp) if b is not None else None, n, info.ctypes.data_as(_vp)), self.handle)
         return {"k": int(info[0]), "builds": int(info[1]), "pairs": int(info[2]), "table": t, "bounds": None if b is None else b[:int(info[2])]}
+
+    def debug_prune_kmer_seg_read(self, db, k=None, segments=1, bounds=False):
+        """Test hook: debug_prune_kmer_read for a table of `segments` segments -> the same dict, table uint16[22^k,
+        segments], plus segments (what the search last begun cut by)."""
+        info = np.zeros(4, dtype=np.uint64)
+        S = int(segments)
+        t = np.zeros((KMER_CLASSES ** int(k), S), dtype=np.uint16) if k else None
+        n = 0
+        if bounds:  # (a first call for the number of pairs)
+            _check(lib.swg_debug_prune_kmer_seg_read(self.handle, db.handle, 0, 0, None, None, 0, info.ctypes.data_as(_vp)), self.handle)
+            n = int(info[2])
+        b = np.zeros(max(n, 1), dtype=np.uint32) if bounds else None
+        _check(lib.swg_debug_prune_kmer_seg_read(self.handle, db.handle, int(k or 0), S, t.ctypes.data_as(_vp) if t is not None else None,
+                                                 b.ctypes.data_as(_vp) if b is not None else None, n, info.ctypes.data_as(_vp)), self.handle)
+        return {"k": int(info[0]), "builds": int(info[1]), "pairs": int(info[2]), "segments": int(info[3]), "table": t,
+                "bounds": None if b is None else b[:int(info[2])]}
 
     def debug_bounds_last(self):
         """What the last align_bounds* call of this context did (swg_debug_bounds_last) -> dict: pairs on the bounds kernel,

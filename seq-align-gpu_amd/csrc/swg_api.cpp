@@ -343,6 +343,10 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
         if (value != 0 && value != 1 && value != 4 && value != 5)
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_kmer must be 0 (auto), 1 (the colmax bound), 4 or 5 (the k-mer bound of that k)");
         ctx->opt_prune_kmer = value;
+    } else if (!strcmp(key, "prune_segments")) {
+        if (value < 0 || value > (long)SWG_KMER_MAX_SEGMENTS)
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_segments must be 0 (auto) or 1..32 (the segments of the k-mer bound's table; 1: unsegmented)");
+        ctx->opt_prune_segments = value;
     } else if (!strcmp(key, "q32_waves")) {
         ctx->opt_q32_waves = value;
     } else if (!strcmp(key, "wave_budget")) {
@@ -1222,7 +1226,10 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
                 uint32_t *cw = db->d_counters;
                 const uint32_t n_pairs_all = (uint32_t)swg_db_pair_count(db);
                 uint32_t *d_ids = db->d_pair_bound + n_pairs_all;
-                if (prune->kmer > 1) // (the table of this epoch: plan_prune queued its build on this stream)
+                if (prune->kmer > 1 && prune->segments > 1) // (the table of this epoch: plan_prune queued its build on this stream)
+                    HIP_TRY(ctx, swg_launch_pair_bound_kmer_seg(T.d_tok, T.d_pair_off, n_pairs_all, prune->kmer, (uint32_t)prune->segments, ctx->prune_colmax,
+                                                                ctx->d_kmer_table[prune->kmer - 4], db->d_pair_bound, d_ids, qs));
+                else if (prune->kmer > 1)
                     HIP_TRY(ctx, swg_launch_pair_bound_kmer(T.d_tok, T.d_pair_off, n_pairs_all, prune->kmer, ctx->prune_colmax, ctx->d_kmer_table[prune->kmer - 4], db->d_pair_bound,
                                                             d_ids, qs));
                 else
@@ -2300,15 +2307,21 @@ static int enqueue_rescore(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P, Swg
 }
 
 // The k-mer bound's table for the current (query, scoring) epoch: the class profile from the device copies
-// of table and query, then every class block's local score, both queued on the context's stream -- behind the copy of
-// the query a set_query queued there and behind any search still in flight, in front of the bound kernel that reads it:
-// the rule the profiles follow (ensure_profile_cols).  One buffer per k, so searches that alternate between the two
-// build each once per epoch.
-static int ensure_kmer_table(swg_ctx *ctx, int k)
+// of table and query, then every class block's best cell per segment, both queued on the context's stream -- behind the
+// copy of the query a set_query queued there and behind any search still in flight, in front of the bound kernel that
+// reads it: the rule the profiles follow (ensure_profile_cols).  One buffer per k, keyed by (k, S, epoch), so searches that
+// alternate between the two k build each once per epoch; it grows when S x entries does, and a table beyond
+// SWG_KMER_TABLE_BUDGET is refused.
+static int ensure_kmer_table(swg_ctx *ctx, int k, int S)
 {
     const int which = k - 4;
     const size_t lq = ctx->query_len();
-    if (ctx->d_kmer_table[which] && ctx->kmer_table_epoch[which] == ctx->epoch) return SWG_OK;
+    if (S < 1 || S > (int)SWG_KMER_MAX_SEGMENTS) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the k-mer bound's table: %d segments (1..32)", S);
+    const size_t entries = (size_t)swg_kmer_entries(k) * (size_t)S;
+    if (!swg_kmer_table_admitted(k, S))
+        return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the k-mer bound's table of k = %d in %d segments is %zu MB: above its budget of %zu MB (prune_kmer, prune_segments)", k,
+                                 S, entries * sizeof(uint16_t) >> 20, (size_t)(SWG_KMER_TABLE_BUDGET >> 20));
+    if (ctx->d_kmer_table[which] && ctx->kmer_table_epoch[which] == ctx->epoch && ctx->kmer_table_segments[which] == (uint32_t)S) return SWG_OK;
     if (lq * 32 > ctx->d_kmer_cprof_cap) {
         (void)hipFree(ctx->d_kmer_cprof);
         ctx->d_kmer_cprof = nullptr;
@@ -2316,12 +2329,20 @@ static int ensure_kmer_table(swg_ctx *ctx, int k)
         HIP_TRY(ctx, hipMalloc(&ctx->d_kmer_cprof, lq * 32));
         ctx->d_kmer_cprof_cap = lq * 32;
     }
-    if (!ctx->d_kmer_table[which]) HIP_TRY(ctx, hipMalloc(&ctx->d_kmer_table[which], (size_t)swg_kmer_entries(k) * sizeof(uint16_t)));
+    if (!ctx->d_kmer_table[which] || ctx->kmer_table_cap[which] < entries) {
+        (void)hipFree(ctx->d_kmer_table[which]);
+        ctx->d_kmer_table[which] = nullptr;
+        ctx->kmer_table_cap[which] = 0;
+        ctx->kmer_table_epoch[which] = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->d_kmer_table[which], entries * sizeof(uint16_t)));
+        ctx->kmer_table_cap[which] = entries;
+    }
     // (gap scores: a gap's first residue costs open + extend, every further one extend -- SwgSearchPlan's go / ge)
     const long go = (long)ctx->gap_open + ctx->gap_extend, ge = ctx->gap_extend;
     HIP_TRY(ctx, swg_launch_kmer_table(ctx->d_sub, ctx->d_query, ctx->query_pssm ? ctx->d_pssm : nullptr, (uint32_t)lq, (uint32_t)-go, (uint32_t)-ge, k,
-                                       ctx->d_kmer_cprof, ctx->d_kmer_table[which], ctx->stream));
+                                       (uint32_t)S, ctx->d_kmer_cprof, ctx->d_kmer_table[which], ctx->stream));
     ctx->kmer_table_epoch[which] = ctx->epoch;
+    ctx->kmer_table_segments[which] = (uint32_t)S;
     ++ctx->kmer_builds;
     return SWG_OK;
 }
@@ -2359,18 +2380,20 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
         return SWG_OK; // (launch_diag reports it)
     a.n_segments = segs.size();
     P->prune = swg_prune_plan(a);
-    ctx->prune_last_kmer = 0;
+    ctx->prune_last_kmer = 0, ctx->prune_last_segments = 0;
     if (!P->prune.on) return SWG_OK;
     // which bound: the colmax table, or the k-mer table of the k that pays for its build on this range (a forced k as it is)
     SwgKmerAsk ka;
     ka.forced = ctx->opt_prune_kmer;
+    ka.forced_segments = ctx->opt_prune_segments;
     ka.pruned = true;
     ka.lq = ctx->query_len();
     ka.pair_rows = 4ull * (db->ptok.pair_blocks_prefix[wk.pair_end[0]] - db->ptok.pair_blocks_prefix[wk.pair_begin[0]]);
     ka.fill_rate = swg_kmer_fill_rate(ka.lq);
-    P->prune.kmer = ctx->prune_last_kmer = swg_prune_kmer_choice(ka);
+    P->prune.kmer = ctx->prune_last_kmer = swg_prune_kmer_choice(ka, &P->prune.segments);
+    ctx->prune_last_segments = P->prune.segments;
     if (P->prune.kmer > 1) {
-        const int rk = ensure_kmer_table(ctx, P->prune.kmer);
+        const int rk = ensure_kmer_table(ctx, P->prune.kmer, P->prune.segments);
         if (rk != SWG_OK) return rk;
     }
     if (ctx->prune_colmax_epoch != ctx->epoch) {
@@ -2660,13 +2683,38 @@ extern "C" int swg_debug_prune_kmer_read(swg_ctx *ctx, const swg_db *db, int k, 
     const size_t n_pairs = db ? (size_t)swg_db_pair_count(db) : 0;
     info[0] = (uint64_t)ctx->prune_last_kmer, info[1] = ctx->kmer_builds, info[2] = n_pairs;
     if (table_out) {
-        if ((k != 4 && k != 5) || !ctx->d_kmer_table[k - 4] || ctx->kmer_table_epoch[k - 4] != ctx->epoch)
+        if ((k != 4 && k != 5) || !ctx->d_kmer_table[k - 4] || ctx->kmer_table_epoch[k - 4] != ctx->epoch || ctx->kmer_table_segments[k - 4] != 1u)
             return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_kmer_read: no table of k = %d for the current query and scoring", k);
         HIP_TRY(ctx, hipMemcpy(table_out, ctx->d_kmer_table[k - 4], (size_t)swg_kmer_entries(k) * sizeof(uint16_t), hipMemcpyDeviceToHost));
     }
     if (bound_out) {
         if (!db || !db->d_pair_bound || bound_cap < n_pairs)
             return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_kmer_read: no pair bounds on this database, or too little room");
+        HIP_TRY(ctx, hipMemcpy(bound_out, db->d_pair_bound, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    return SWG_OK;
+}
+
+// ... and over segments: table_out (or NULL) the 22^k x S entries of the context's table of k, an error unless it was
+// built with S segments for the current query and scoring; info[0..3] = k, the table builds, the database's pairs, the S
+// the search last begun cut by
+extern "C" int swg_debug_prune_kmer_seg_read(swg_ctx *ctx, const swg_db *db, int k, int S, uint16_t *table_out, uint32_t *bound_out, size_t bound_cap,
+                                             uint64_t *info)
+{
+    if (!ctx || !info) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_kmer_seg_read: NULL argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    const size_t n_pairs = db ? (size_t)swg_db_pair_count(db) : 0;
+    info[0] = (uint64_t)ctx->prune_last_kmer, info[1] = ctx->kmer_builds, info[2] = n_pairs, info[3] = (uint64_t)ctx->prune_last_segments;
+    if (table_out) {
+        if ((k != 4 && k != 5) || S < 1 || !ctx->d_kmer_table[k - 4] || ctx->kmer_table_epoch[k - 4] != ctx->epoch ||
+            ctx->kmer_table_segments[k - 4] != (uint32_t)S)
+            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_kmer_seg_read: no table of k = %d in %d segments for the current query and scoring", k, S);
+        HIP_TRY(ctx, hipMemcpy(table_out, ctx->d_kmer_table[k - 4], (size_t)swg_kmer_entries(k) * (size_t)S * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    }
+    if (bound_out) {
+        if (!db || !db->d_pair_bound || bound_cap < n_pairs)
+            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_kmer_seg_read: no pair bounds on this database, or too little room");
         HIP_TRY(ctx, hipMemcpy(bound_out, db->d_pair_bound, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     return SWG_OK;

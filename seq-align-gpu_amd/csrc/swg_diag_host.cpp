@@ -670,40 +670,51 @@ void swg_kmer_cprof(const int8_t *rows, const int8_t *idx, size_t lq, int8_t *cp
     }
 }
 
-// table[c_1 .. c_k] = the local score of the class block against the query (gap magnitudes g, e; the recurrence of
-// DESIGN 4.1 in int32).  Blocks that share a prefix share its cells: the block runs along the columns, a column is lq
-// cells, and the columns of a prefix are computed once for all the blocks behind it (depth first, the first class in
-// parallel).  Value for value what the device's one-thread-per-block walk along the query gives.
-static void kmer_extend(const int8_t *cprof, size_t lq, int g, int e, int k, int depth, size_t prefix, const int *Mp, const int *Bp, int best_p,
-                        std::vector<int> &work, uint16_t *table, uint32_t c_begin, uint32_t c_end)
+// table[c_1 .. c_k][s] = the best cell of the class block against the query within segment s of its columns (gap
+// magnitudes g, e; the recurrence of DESIGN 4.1 in int32; S segments of W = ceil(lq / S) columns, one without columns
+// holds 0; S = 1: the block's local score against the whole query).  Blocks that share a prefix share its cells: the block
+// runs along the columns, a column is lq cells, and the columns of a prefix are computed once for all the blocks behind it
+// (depth first, the first class in parallel), its segment maxima handed down.  Value for value what the device's
+// one-thread-per-block walk along the query gives.
+static void kmer_extend(const int8_t *cprof, size_t lq, int g, int e, int k, size_t S, int depth, size_t prefix, const int *Mp, const int *Bp,
+                        const int *best_p, std::vector<int> &work, uint16_t *table, uint32_t c_begin, uint32_t c_end)
 {
-    int *Mn = work.data() + (size_t)depth * 2 * lq, *Bn = Mn + lq;
+    int *Mn = work.data() + (size_t)depth * (2 * lq + S), *Bn = Mn + lq, *best = Bn + lq;
+    const size_t W = (lq + S - 1) / S;
     for (uint32_t c = c_begin; c < c_end; ++c) {
-        int a = 0, up = 0, best = best_p;
-        for (size_t i = 0; i < lq; ++i) {
-            const int s = cprof[SWG_KMER_CLASSES * i + c];
-            a = std::max(std::max(up - g, a - e), 0);
-            const int b = depth ? std::max(std::max(Mp[i] - g, Bp[i] - e), 0) : 0;
-            const int diag = depth && i ? Mp[i - 1] : 0;
-            const int m = std::max(std::max(diag + s, a), b);
-            Mn[i] = m, Bn[i] = b, up = m;
-            best = std::max(best, m);
+        int a = 0, up = 0;
+        for (size_t s = 0; s < S; ++s) best[s] = best_p ? best_p[s] : 0;
+        for (size_t s = 0, i = 0; i < lq; ++s) {
+            int bs = best[s];
+            for (const size_t end = std::min(lq, i + W); i < end; ++i) {
+                const int sc = cprof[SWG_KMER_CLASSES * i + c];
+                a = std::max(std::max(up - g, a - e), 0);
+                const int b = depth ? std::max(std::max(Mp[i] - g, Bp[i] - e), 0) : 0;
+                const int diag = depth && i ? Mp[i - 1] : 0;
+                const int m = std::max(std::max(diag + sc, a), b);
+                Mn[i] = m, Bn[i] = b, up = m;
+                bs = std::max(bs, m);
+            }
+            best[s] = bs;
         }
         const size_t at = prefix * SWG_KMER_CLASSES + c;
-        if (depth + 1 == k) table[at] = (uint16_t)std::min(best, 65535);
-        else kmer_extend(cprof, lq, g, e, k, depth + 1, at, Mn, Bn, best, work, table, 0, SWG_KMER_CLASSES);
+        if (depth + 1 == k)
+            for (size_t s = 0; s < S; ++s) table[at * S + s] = (uint16_t)std::min(best[s], 65535);
+        else kmer_extend(cprof, lq, g, e, k, S, depth + 1, at, Mn, Bn, best, work, table, 0, SWG_KMER_CLASSES);
     }
 }
 
-void swg_kmer_table(const int8_t *cprof, size_t lq, int g, int e, int k, uint16_t *table)
+void swg_kmer_table_seg(const int8_t *cprof, size_t lq, int g, int e, int k, size_t S, uint16_t *table)
 {
     g = std::min(g, 65536), e = std::min(e, 65536);
 #pragma omp parallel for schedule(dynamic, 1)
     for (int c = 0; c < (int)SWG_KMER_CLASSES; ++c) {
-        std::vector<int> work((size_t)k * 2 * lq);
-        kmer_extend(cprof, lq, g, e, k, 0, 0, nullptr, nullptr, 0, work, table, (uint32_t)c, (uint32_t)c + 1u);
+        std::vector<int> work((size_t)k * (2 * lq + S));
+        kmer_extend(cprof, lq, g, e, k, S, 0, 0, nullptr, nullptr, nullptr, work, table, (uint32_t)c, (uint32_t)c + 1u);
     }
 }
+
+void swg_kmer_table(const int8_t *cprof, size_t lq, int g, int e, int k, uint16_t *table) { swg_kmer_table_seg(cprof, lq, g, e, k, 1, table); }
 
 // U_k of one sequence as the device sums it: the sequence's token rows -- two reset rows (padding), its residues (a 0 among
 // them is a padding row: the shorter sequence of a pair, filled up to the longer one's length), padding to a whole 4-row
@@ -746,27 +757,105 @@ extern "C" int swg_debug_prune_kmer(const int8_t *rows, const int8_t *idx, size_
     return SWG_OK;
 }
 
-// Which bound a pruned search cuts by: 1 (colmax), 4 or 5 (k-mer tables).  A forced k is taken as it is wherever the search
-// is pruned; an unpruned search builds nothing (0).  Automatic weighs what a table costs -- 22^k * k * lq cells at
-// table_rate cells per second, paid by every search with a new query -- against what its tighter cut saves: the share of
-// the range's pair rows it takes off the fill (SWG_KMER_GAIN: the hard case, a database of unrelated sequences, DESIGN
-// 4.2.1) at fill_rate pair rows per second for this query.  A step up must cost at most half of what it saves.
-static const double SWG_KMER_GAIN[6] = {0, 0, 0, 0, 0.1426, 0.2006}; // the headline's rows kept: 0.5584 (k = 1), 0.4158 (4), 0.3578 (5)
-int swg_prune_kmer_choice(const SwgKmerAsk &a)
+// U_{k,S} of one sequence: swg_kmer_bound's blocks, taken in order over the table of S segments.  The
+// segment that holds a block's last matched column never decreases along the sequence, so with H[s] the best total of the
+// blocks so far whose last one ended in segment s, a block gives H[s] = max_{s' <= s} H[s'] + min(table[block][s], the
+// block's colmax sum), and the bound is max_s H[s].  S = 1 is swg_kmer_bound.
+uint64_t swg_kmer_bound_seg(const uint16_t *table, int k, size_t S, const SwgColMax &cm, const int8_t *seq, size_t len)
 {
-    if (!a.pruned) return 0;
-    if (a.forced == 1 || a.forced == 4 || a.forced == 5) return (int)a.forced;
-    if (a.table_rate <= 0 || a.fill_rate <= 0 || a.lq == 0) return 1;
-    auto cost = [&](int k) { return k == 1 ? 0.0 : (double)swg_kmer_entries(k) * k * (double)a.lq / a.table_rate; };
-    auto gain = [&](int k) { return SWG_KMER_GAIN[k] * (double)a.pair_rows / a.fill_rate; };
-    int k = 1;
-    if (cost(4) <= 0.5 * gain(4)) k = 4;
-    if (k == 4 && cost(5) - cost(4) <= 0.5 * (gain(5) - gain(4))) k = 5;
+    const size_t n_blocks = (2 + len + 3) / 4, n_rows = 4 * n_blocks;
+    auto res = [&](size_t row) -> uint32_t { return row < 2 || row >= 2 + len ? 0u : (uint8_t)seq[row - 2] & 31u; };
+    const size_t rows5 = k == 5 ? 20 * (n_blocks / 5) : 0;
+    std::vector<uint64_t> H(S, 0);
+    for (size_t r = 0; r < n_rows;) {
+        const size_t rows = r < rows5 ? 5 : 4;
+        size_t ix = 0;
+        uint64_t sum = 0, run = 0;
+        for (size_t j = 0; j < rows; ++j) ix = ix * SWG_KMER_CLASSES + swg_kmer_class(res(r + j)), sum += cm.v[res(r + j)];
+        if (k == 5 && rows == 4) ix *= SWG_KMER_CLASSES;
+        for (size_t s = 0; s < S; ++s) {
+            run = std::max(run, H[s]);
+            H[s] = run + std::min<uint64_t>(table[ix * S + s], sum);
+        }
+        r += rows;
+    }
+    return *std::max_element(H.begin(), H.end());
+}
+
+// test hook: swg_debug_prune_kmer over S segments -- the table (22^k x S uint16, or NULL) and U_{k,S} of each sequence
+extern "C" int swg_debug_prune_kmer_seg(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int k, int S,
+                                        const int8_t *flat, const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out)
+{
+    if (!rows || lq == 0 || (k != 4 && k != 5) || S < 1 || S > (int)SWG_KMER_MAX_SEGMENTS || gap_open > 0 || gap_extend > 0 ||
+        (n > 0 && (!flat || !offsets || !u_out)))
+        return SWG_ERR_ARG;
+    std::vector<int8_t> cprof(lq * SWG_KMER_CLASSES);
+    swg_kmer_cprof(rows, idx, lq, cprof.data());
+    std::vector<uint16_t> own;
+    if (!table_out) {
+        own.resize(swg_kmer_entries(k) * (size_t)S);
+        table_out = own.data();
+    }
+    swg_kmer_table_seg(cprof.data(), lq, -(gap_open + gap_extend), -gap_extend, k, (size_t)S, table_out);
+    const SwgColMax cm = swg_prune_colmax(rows, idx, lq);
+    for (size_t i = 0; i < n; ++i) u_out[i] = swg_kmer_bound_seg(table_out, k, (size_t)S, cm, flat + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+    return SWG_OK;
+}
+
+// Which bound a pruned search cuts by: k = 1 (colmax), 4 or 5 (k-mer tables) and the S segments of its table (1: the
+// unordered sum).  An unpruned search builds nothing (0).  A forced k is taken as it is wherever the search is pruned, with
+// the forced S, or unsegmented when that is left automatic; a forced S alone goes with the k the unsegmented candidates
+// give, stepped down to 4 where the table of (5, S) is beyond SWG_KMER_TABLE_BUDGET.  Automatic weighs, over the fixed
+// list SWG_KMER_CANDIDATES, what a candidate costs -- its table, 22^k * k * lq cells at table_rate cells per second paid by
+// every search with a new query, and its bound kernel's time per pair row beyond the colmax kernel's -- against what its
+// tighter cut saves: the share of the range's pair rows it takes off the fill (the hard case, a database of unrelated
+// sequences) at fill_rate pair rows per second for this query.  In the order of what they save, a step up
+// must cost at most half of what it saves.
+struct SwgKmerCandidate {
+    int k, S;
+    double gain;      // the headline's rows kept at (1, 1), 0.5584, less the candidate's (profiles/prune_segments_ab.txt)
+    double bound_row; // seconds per pair row that a step spends outside the fill's rows, beyond what it spends there at (1, 1)
+};
+static const SwgKmerCandidate SWG_KMER_CANDIDATES[] = {
+    {1, 1, 0.0, 0.0},         {4, 1, 0.1426, 3.1e-12},  {5, 1, 0.2006, 3.1e-12},
+    {4, 16, 0.2493, 4.0e-12}, {4, 32, 0.2741, 6.1e-12}, {5, 8, 0.2760, 9.0e-12},
+};
+int swg_prune_kmer_choice(const SwgKmerAsk &a, int *segments)
+{
+    int S_out = 1;
+    int k = 0;
+    if (a.pruned) {
+        const bool forced_k = a.forced == 1 || a.forced == 4 || a.forced == 5;
+        const long forced_S = a.forced_segments >= 1 && a.forced_segments <= (long)SWG_KMER_MAX_SEGMENTS ? a.forced_segments : 0;
+        if (forced_k) {
+            k = (int)a.forced;
+            S_out = k > 1 && forced_S ? (int)forced_S : 1;
+        } else if (a.table_rate <= 0 || a.fill_rate <= 0 || a.lq == 0) {
+            k = 1;
+        } else {
+            auto cost = [&](const SwgKmerCandidate &c) {
+                return c.k == 1 ? 0.0 : (double)swg_kmer_entries(c.k) * c.k * (double)a.lq / a.table_rate + c.bound_row * (double)a.pair_rows;
+            };
+            auto gain = [&](const SwgKmerCandidate &c) { return c.gain * (double)a.pair_rows / a.fill_rate; };
+            const SwgKmerCandidate *cur = &SWG_KMER_CANDIDATES[0];
+            for (const SwgKmerCandidate &c : SWG_KMER_CANDIDATES) {
+                if (forced_S && c.S != 1) continue; // (a forced S: k from the unsegmented candidates)
+                if (c.gain > cur->gain && cost(c) - cost(*cur) <= 0.5 * (gain(c) - gain(*cur))) cur = &c;
+            }
+            k = cur->k, S_out = cur->S;
+            if (forced_S && k > 1) {
+                if (k == 5 && !swg_kmer_table_admitted(5, forced_S)) k = 4;
+                S_out = (int)forced_S;
+            }
+        }
+    }
+    if (segments) *segments = k > 1 ? S_out : (k ? 1 : 0);
     return k;
 }
 
 // test hook: in[0..5] = forced (option "prune_kmer"), pruned, lq, pair rows, table cells per second, fill pair rows per second
-// (0, 0: the library's own rates for this lq); out[0] = k
+// (0, 0: the library's own rates for this lq); out[0] = k.  Like swg_debug_prune_kmer and swg_debug_prune_kmer_read it
+// keeps its unsegmented meaning: the k of "prune_segments" = 1.
 extern "C" int swg_debug_prune_kmer_choice(const int64_t *in, int64_t *out)
 {
     if (!in || !out || in[2] < 0 || in[3] < 0 || in[4] < 0 || in[5] < 0) return SWG_ERR_ARG;
@@ -774,7 +863,26 @@ extern "C" int swg_debug_prune_kmer_choice(const int64_t *in, int64_t *out)
     a.forced = (long)in[0], a.pruned = in[1] != 0, a.lq = (size_t)in[2], a.pair_rows = (uint64_t)in[3];
     a.table_rate = in[4] ? (double)in[4] : SWG_KMER_TABLE_RATE;
     a.fill_rate = in[5] ? (double)in[5] : swg_kmer_fill_rate(a.lq);
+    a.forced_segments = 1;
     out[0] = swg_prune_kmer_choice(a);
+    return SWG_OK;
+}
+
+// ... and with in[6] = the forced segments (option "prune_segments"); out[0..3] = k, S, the table's bytes, whether a
+// context builds it (1) or refuses it as beyond its budget (0)
+extern "C" int swg_debug_prune_kmer_choice_seg(const int64_t *in, int64_t *out)
+{
+    if (!in || !out || in[2] < 0 || in[3] < 0 || in[4] < 0 || in[5] < 0 || in[6] < 0) return SWG_ERR_ARG;
+    SwgKmerAsk a;
+    a.forced = (long)in[0], a.pruned = in[1] != 0, a.lq = (size_t)in[2], a.pair_rows = (uint64_t)in[3];
+    a.table_rate = in[4] ? (double)in[4] : SWG_KMER_TABLE_RATE;
+    a.fill_rate = in[5] ? (double)in[5] : swg_kmer_fill_rate(a.lq);
+    a.forced_segments = (long)in[6];
+    int S = 0;
+    out[0] = swg_prune_kmer_choice(a, &S);
+    out[1] = S;
+    out[2] = (int64_t)(swg_kmer_entries((int)out[0]) * (uint64_t)S * sizeof(uint16_t));
+    out[3] = out[0] <= 1 || swg_kmer_table_admitted((int)out[0], S) ? 1 : 0;
     return SWG_OK;
 }
 

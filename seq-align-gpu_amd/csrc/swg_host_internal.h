@@ -249,6 +249,7 @@ struct SwgPrunePlan {
     bool on = false;
     uint32_t head_pairs = 0; // one segment: pairs of the first stage; 0: the stages are the segments
     int kmer = 0;            // the bound: 1 colmax, 4 / 5 the k-mer table of that k (swg_prune_kmer_choice); 0 while off
+    int segments = 0;        // ... and the segments of that table (1: the unordered sum of swg_pair_bound_kmer_kernel)
 };
 SwgPrunePlan swg_prune_plan(const SwgPruneAsk &a);
 extern "C" int swg_debug_prune_bound(const int8_t *rows, const int8_t *idx, size_t lq, const int8_t *flat, const uint64_t *offsets, size_t n,
@@ -258,6 +259,9 @@ extern "C" int swg_debug_prune_plan(const int64_t *in, int64_t *out);
 void swg_kmer_cprof(const int8_t *rows, const int8_t *idx, size_t lq, int8_t *cprof);                 // cprof[lq][22]
 void swg_kmer_table(const int8_t *cprof, size_t lq, int g, int e, int k, uint16_t *table);            // table[22^k]
 uint64_t swg_kmer_bound(const uint16_t *table, int k, const SwgColMax &cm, const int8_t *seq, size_t len);
+// ... over S segments of the query's columns, the blocks taken in order (S = 1: the two above)
+void swg_kmer_table_seg(const int8_t *cprof, size_t lq, int g, int e, int k, size_t S, uint16_t *table); // table[22^k][S]
+uint64_t swg_kmer_bound_seg(const uint16_t *table, int k, size_t S, const SwgColMax &cm, const int8_t *seq, size_t len);
 // The two rates the automatic choice weighs, measured on one MI355X (profiles/prune_kmer_ab.txt): the table
 // kernel's cell updates per second (k = 5 at 3000 columns: 7.73e10 cells in 16.6 ms), and the fill's pair rows per second
 // -- a pair row costs one step of a 16-lane group per pass of 512 query columns (the headline unpruned: 1.938e9 pair rows
@@ -267,15 +271,24 @@ uint64_t swg_kmer_bound(const uint16_t *table, int k, const SwgColMax &cm, const
 inline double swg_kmer_fill_rate(size_t lq) { return SWG_KMER_FILL_PASS_RATE / (double)std::max<size_t>(1, (lq + 511) / 512); }
 struct SwgKmerAsk {
     long forced = 0;     // option "prune_kmer": 0 automatic, 1, 4, 5
+    long forced_segments = 0; // option "prune_segments": 0 automatic, 1..SWG_KMER_MAX_SEGMENTS
     bool pruned = false; // swg_prune_plan's answer
     size_t lq = 0;
     uint64_t pair_rows = 0; // rows of the range's pairs
     double table_rate = SWG_KMER_TABLE_RATE, fill_rate = 0;
 };
-int swg_prune_kmer_choice(const SwgKmerAsk &a); // 0 (not pruned: nothing is built), 1, 4 or 5
+// whether a context builds the table of (k, S): within SWG_KMER_TABLE_BUDGET (ensure_kmer_table refuses the others)
+inline bool swg_kmer_table_admitted(int k, long S)
+{
+    return S >= 1 && S <= (long)SWG_KMER_MAX_SEGMENTS && swg_kmer_entries(k) * (uint64_t)S * sizeof(uint16_t) <= SWG_KMER_TABLE_BUDGET;
+}
+int swg_prune_kmer_choice(const SwgKmerAsk &a, int *segments = nullptr); // 0 (not pruned: nothing is built), 1, 4 or 5; *segments: its S
 extern "C" int swg_debug_prune_kmer(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int k, const int8_t *flat,
                                     const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out);
+extern "C" int swg_debug_prune_kmer_seg(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int k, int S,
+                                        const int8_t *flat, const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out);
 extern "C" int swg_debug_prune_kmer_choice(const int64_t *in, int64_t *out);
+extern "C" int swg_debug_prune_kmer_choice_seg(const int64_t *in, int64_t *out);
 // the words of a search's counter block (swg_db::Bufs::d_counters) a pruned search uses: the threshold so far and the
 // threshold kernel's status word, then what swg_launch_prune_cut writes: the pairs the stage takes, the pairs skipped so
 // far, their token blocks (64 bits)
@@ -434,6 +447,10 @@ struct swg_ctx {
     size_t d_kmer_cprof_cap = 0;
     uint16_t *d_kmer_table[2] = {nullptr, nullptr};
     uint64_t kmer_table_epoch[2] = {0, 0};
+    uint32_t kmer_table_segments[2] = {0, 0}; // the S each table was built with
+    size_t kmer_table_cap[2] = {0, 0};        // entries allocated
+    long opt_prune_segments = 0;              // option "prune_segments": 0 auto, 1..32
+    int prune_last_segments = 0;              // the S of the search last begun on this context
     uint64_t kmer_builds = 0; // table builds queued so far (tests)
     int prune_last_kmer = 0;  // the k of the search last begun on this context (0: not pruned)
     uint32_t opt_seg_blocks = SWG_DYN_SEG_BLOCKS; // token blocks per launch of the multi-pass fill (option "segment_blocks": tests)

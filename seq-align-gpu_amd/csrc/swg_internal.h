@@ -326,15 +326,25 @@ static inline __host__ __device__ uint32_t swg_kmer_class(uint32_t r)
     return c;
 }
 static inline uint64_t swg_kmer_entries(int k) { return k == 5 ? 5153632ull : k == 4 ? 234256ull : 0ull; }
+// The segmented table: S entries per block, its best cell within each of S consecutive segments of ceil(lq / S) query
+// columns (S = 1: the block's local score against the whole query).  At most SWG_KMER_MAX_SEGMENTS segments -- one lane
+// of the ordered bound kernel each -- and SWG_KMER_TABLE_BUDGET bytes, which admits (k, S) = (5, 8).
+#define SWG_KMER_MAX_SEGMENTS 32u
+#define SWG_KMER_TABLE_BUDGET (96ull << 20)
 // d_cprof[lq][32] (int8; entries 22..31 of a row unused): query column i against class c, from the device copies of the
-// table and the index query (d_pssm == NULL) or of the PSSM; then d_table[22^k] = the local score of every class block
-// against the query under gap magnitudes g (first residue of a gap) and e (every further one).  k: 4 or 5.
+// table and the index query (d_pssm == NULL) or of the PSSM; then d_table[22^k][S] = the best cell of every class block
+// against the query, segment by segment, under gap magnitudes g (first residue of a gap) and e (every further one).
+// k: 4 or 5; S: 1..SWG_KMER_MAX_SEGMENTS.
 hipError_t swg_launch_kmer_table(const int8_t *d_sub, const int8_t *d_query, const int8_t *d_pssm, uint32_t lq, uint32_t g, uint32_t e,
-                                 int k, int8_t *d_cprof, uint16_t *d_table, hipStream_t stream);
+                                 int k, uint32_t S, int8_t *d_cprof, uint16_t *d_table, hipStream_t stream);
 // swg_launch_pair_bound with the k-mer bound: blocks of 4 token rows (k = 4), or of 5 with a tail of fewer than 20 rows
 // in blocks of 4 (k = 5); a block adds the lesser of its table entry and its rows' colmax entries
 hipError_t swg_launch_pair_bound_kmer(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, int k, const SwgColMax &cm,
                                       const uint16_t *d_table, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream);
+// ... and its ordered form over the table of S segments: the blocks in order, H[s] = max_{s' <= s} H[s'] + the block's
+// entry of segment s (or its colmax sum where that is less), the bound max_s H[s]
+hipError_t swg_launch_pair_bound_kmer_seg(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, int k, uint32_t S, const SwgColMax &cm,
+                                          const uint16_t *d_table, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream);
 // d_thr[0] = the k-th largest entry of d_scores (clamped to 4095; 0 with fewer than k entries): swg_topk_hist_kernel and
 // swg_topk_threshold_kernel on `stream`; d_thr[1] is written too (the status word, not read)
 hipError_t swg_launch_prune_threshold(const int32_t *d_scores, const uint32_t *d_order, uint32_t n_slots, uint32_t k, uint32_t *d_hist,

@@ -2840,12 +2840,15 @@ __global__ __launch_bounds__(256) void swg_kmer_cprof_kernel(const int8_t *sub, 
     cprof[t] = (int8_t)v;
 }
 
-// table[c_1 .. c_K] = the local score of the class block against the whole query: one thread per block, its K cells'
-// (M, A) in registers, the query along the loop (plain int32 cells, the recurrence of DESIGN 4.1).  The query position is
+// table[c_1 .. c_K][s] = the best cell of the class block against the query within segment s of its columns: one thread
+// per block, its K cells' (M, A) in registers, the query along the loop (plain int32 cells, the recurrence of DESIGN 4.1),
+// the running maximum stored and reset where a segment ends.  The S segments are W = ceil(lq / S) columns each; one
+// without columns (lq < S * W) holds 0.  S = 1: the block's local score against the whole query.  The query position is
 // the same for the whole workgroup: the class profile goes through LDS in chunks, a row's 22 bytes are 6 dwords in 6 banks.
 #define SWG_KMER_CHUNK 256u
 template <int K>
-__global__ __launch_bounds__(256) void swg_kmer_table_kernel(const int8_t *cprof, uint32_t lq, int g, int e, uint32_t n_entries, uint16_t *table)
+__global__ __launch_bounds__(256) void swg_kmer_table_kernel(const int8_t *cprof, uint32_t lq, int g, int e, uint32_t n_entries, uint32_t S,
+                                                             uint16_t *table)
 {
     __shared__ uint4 rows4[SWG_KMER_CHUNK * 2u];
     const int8_t *rows = reinterpret_cast<const int8_t *>(rows4);
@@ -2862,6 +2865,9 @@ __global__ __launch_bounds__(256) void swg_kmer_table_kernel(const int8_t *cprof
     int M[K], A[K], best = 0;
 #pragma unroll
     for (int j = 0; j < K; ++j) M[j] = 0, A[j] = 0;
+    const uint32_t W = (lq + S - 1u) / S;
+    uint16_t *out = table + (size_t)(idx < n_entries ? idx : 0u) * S;
+    uint32_t seg = 0u, seg_end = W < lq ? W : lq; // (the column behind the current segment's last)
     for (uint32_t i0 = 0u; i0 < lq; i0 += SWG_KMER_CHUNK) {
         const uint32_t n = lq - i0 < SWG_KMER_CHUNK ? lq - i0 : SWG_KMER_CHUNK;
         __syncthreads();
@@ -2880,23 +2886,29 @@ __global__ __launch_bounds__(256) void swg_kmer_table_kernel(const int8_t *cprof
                 M[j] = m, A[j] = a, B = b, left = m;
                 best = max(best, m);
             }
+            if (i0 + i + 1u == seg_end) { // (the same for every thread)
+                if (idx < n_entries) out[seg] = (uint16_t)(best > 65535 ? 65535 : best);
+                ++seg, best = 0;
+                seg_end = seg_end + W < lq ? seg_end + W : lq;
+            }
         }
     }
-    if (idx < n_entries) table[idx] = (uint16_t)(best > 65535 ? 65535 : best);
+    if (idx < n_entries)
+        for (; seg < S; ++seg) out[seg] = 0;
 }
 
 hipError_t swg_launch_kmer_table(const int8_t *d_sub, const int8_t *d_query, const int8_t *d_pssm, uint32_t lq, uint32_t g, uint32_t e,
-                                 int k, int8_t *d_cprof, uint16_t *d_table, hipStream_t stream)
+                                 int k, uint32_t S, int8_t *d_cprof, uint16_t *d_table, hipStream_t stream)
 {
     const uint32_t n = (uint32_t)swg_kmer_entries(k);
-    if (n == 0u || lq == 0u || lq > (1u << 24)) return hipErrorInvalidValue;
+    if (n == 0u || lq == 0u || lq > (1u << 24) || S == 0u || S > SWG_KMER_MAX_SEGMENTS) return hipErrorInvalidValue;
     // (gap magnitudes beyond any block's score change nothing, and keep the int32 cells far from their range)
     const int gi = (int)(g > 65536u ? 65536u : g), ei = (int)(e > 65536u ? 65536u : e);
     hipLaunchKernelGGL(swg_kmer_cprof_kernel, dim3((lq * 32u + 255u) / 256u), dim3(256), 0, stream, d_sub, d_query, d_pssm, lq, d_cprof);
     if (k == 5)
-        hipLaunchKernelGGL(swg_kmer_table_kernel<5>, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_cprof, lq, gi, ei, n, d_table);
+        hipLaunchKernelGGL(swg_kmer_table_kernel<5>, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_cprof, lq, gi, ei, n, S, d_table);
     else
-        hipLaunchKernelGGL(swg_kmer_table_kernel<4>, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_cprof, lq, gi, ei, n, d_table);
+        hipLaunchKernelGGL(swg_kmer_table_kernel<4>, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_cprof, lq, gi, ei, n, S, d_table);
     return hipGetLastError();
 }
 
@@ -2973,6 +2985,155 @@ hipError_t swg_launch_pair_bound_kmer(const uint4 *d_tok, const uint32_t *d_pair
         hipLaunchKernelGGL(swg_pair_bound_kmer_kernel<5>, dim3((n_pairs + 15u) / 16u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, d_bound, d_ids);
     else
         hipLaunchKernelGGL(swg_pair_bound_kmer_kernel<4>, dim3((n_pairs + 15u) / 16u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, d_bound, d_ids);
+    return hipGetLastError();
+}
+
+// The ordered form of the k-mer bound: the table holds S entries per block, the block's best cell within
+// each of the S segments of the query's columns, and a sequence's blocks are walked IN ORDER with H[0..S) carried along:
+// H[s] = max_{s' <= s} H[s'] + min(table[block][s], the block's colmax sum), the bound max_s H[s].  WD lanes per pair
+// (S <= WD), lane s holding H[s] of x and of y.  A chunk of the pair's blocks first: every lane takes one unit of its own
+// (K = 4: one uint4 = one block; K = 5: five uint4s = four blocks of 5 rows, the pair's last fewer-than-five uint4s as
+// blocks of 4 rows the way swg_pair_bound_kmer_kernel takes them) and works out its blocks' table indices and colmax
+// sums.  Then the chunk's blocks in order: index and sums come from their lane by shuffle, the block's S entries are one
+// coalesced gather (issued for several blocks ahead of the recurrence: they do not depend on H), the prefix maximum is
+// log2(WD) DPP steps.  Units past the chunk's end are the all-padding block, whose entries are 0.
+template <int WD>
+__device__ __forceinline__ uint32_t swg_seg_prefix_max(uint32_t h, uint32_t m1, uint32_t m2, uint32_t m4)
+{
+    // row_shr:d within the 16-lane DPP row; lanes without a source read 0 (every H is >= 0).  Groups of 8 share a row:
+    // m1 / m2 / m4 clear what a lane would take across its group's lower edge.
+    uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)h, 0x111, 0xf, 0xf, true);
+    if (WD == 8) t &= m1;
+    h = t > h ? t : h;
+    t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)h, 0x112, 0xf, 0xf, true);
+    if (WD == 8) t &= m2;
+    h = t > h ? t : h;
+    t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)h, 0x114, 0xf, 0xf, true);
+    if (WD == 8) t &= m4;
+    h = t > h ? t : h;
+    if (WD >= 16) {
+        t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)h, 0x118, 0xf, 0xf, true);
+        h = t > h ? t : h;
+    }
+    if (WD == 32) { // row_bcast:15 into rows 1 and 3: the lower row's maximum
+        t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)h, 0x142, 0xa, 0xf, false);
+        h = t > h ? t : h;
+    }
+    return h;
+}
+
+// one chunk: cnt (<= WD) units of NB blocks each, U units per round of gathers
+template <int WD, int NB, int U>
+__device__ __forceinline__ void swg_seg_chunk(const uint32_t (&ux)[NB], const uint32_t (&uy)[NB], const uint32_t (&uc)[NB], uint32_t cnt,
+                                              const uint16_t *tl, uint32_t S, bool has, uint32_t m1, uint32_t m2, uint32_t m4, uint32_t &hx,
+                                              uint32_t &hy)
+{
+    for (uint32_t j0 = 0u; j0 < cnt; j0 += (uint32_t)U) {
+        uint32_t tx[U * NB], ty[U * NB], cs[U * NB];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                const int src = (int)j0 + u; // (< WD: cnt <= WD, both multiples of U apart from cnt)
+                const uint32_t ix = (uint32_t)__shfl((int)ux[b], src, WD), iy = (uint32_t)__shfl((int)uy[b], src, WD);
+                cs[u * NB + b] = (uint32_t)__shfl((int)uc[b], src, WD);
+                tx[u * NB + b] = has ? (uint32_t)tl[ix * S] : 0u;
+                ty[u * NB + b] = has ? (uint32_t)tl[iy * S] : 0u;
+            }
+#pragma unroll
+        for (int i = 0; i < U * NB; ++i) {
+            const uint32_t cx = cs[i] & 0xFFFFu, cy = cs[i] >> 16;
+            hx = swg_seg_prefix_max<WD>(hx, m1, m2, m4) + (tx[i] < cx ? tx[i] : cx);
+            hy = swg_seg_prefix_max<WD>(hy, m1, m2, m4) + (ty[i] < cy ? ty[i] : cy);
+        }
+    }
+}
+
+template <int K, int WD>
+__global__ __launch_bounds__(256) void swg_pair_bound_kmer_seg_kernel(const uint4 *tok, const uint32_t *pair_off, uint32_t n_pairs, SwgColMax cm,
+                                                                      const uint16_t *table, uint32_t S, uint32_t *bound, uint32_t *ids)
+{
+    __shared__ uint32_t lut[32]; // residue index -> class | colmax << 8
+    if (threadIdx.x < 32u) lut[threadIdx.x] = swg_kmer_class(threadIdx.x) | (uint32_t)cm.v[threadIdx.x] << 8;
+    __syncthreads();
+    const uint32_t p = blockIdx.x * (256u / WD) + threadIdx.x / WD, l = threadIdx.x & (WD - 1u);
+    const uint32_t C = SWG_KMER_CLASSES;
+    const bool has = l < S;
+    const uint16_t *tl = table + (has ? l : 0u);
+    const uint32_t m1 = (l & 7u) >= 1u ? 0xFFFFFFFFu : 0u, m2 = (l & 7u) >= 2u ? 0xFFFFFFFFu : 0u, m4 = (l & 7u) >= 4u ? 0xFFFFFFFFu : 0u;
+    uint32_t hx = 0u, hy = 0u;
+    if (p < n_pairs) { // (the same for all lanes of a group, and so is every loop count below)
+        const uint32_t b0 = pair_off[p], e = pair_off[p + 1u];
+        uint32_t tail = b0;
+        if (K == 5) {
+            const uint32_t groups = (e - b0) / 5u;
+            tail = b0 + 5u * groups;
+            for (uint32_t g0 = 0u; g0 < groups; g0 += WD) {
+                uint32_t ux[4] = {0u, 0u, 0u, 0u}, uy[4] = {0u, 0u, 0u, 0u}, uc[4] = {0u, 0u, 0u, 0u};
+                if (g0 + l < groups) {
+                    uint32_t x[20], y[20];
+#pragma unroll
+                    for (int u = 0; u < 5; ++u) {
+                        const uint4 k = tok[b0 + 5u * (g0 + l) + (uint32_t)u];
+                        x[4 * u] = lut[(k.x >> 3) & 31u], x[4 * u + 1] = lut[(k.y >> 3) & 31u], x[4 * u + 2] = lut[(k.z >> 3) & 31u], x[4 * u + 3] = lut[(k.w >> 3) & 31u];
+                        y[4 * u] = lut[(k.x >> 11) & 31u], y[4 * u + 1] = lut[(k.y >> 11) & 31u], y[4 * u + 2] = lut[(k.z >> 11) & 31u], y[4 * u + 3] = lut[(k.w >> 11) & 31u];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        uint32_t ix = 0u, iy = 0u, sx = 0u, sy = 0u;
+#pragma unroll
+                        for (int j = 0; j < 5; ++j) {
+                            ix = ix * C + (x[5 * u + j] & 255u), sx += x[5 * u + j] >> 8;
+                            iy = iy * C + (y[5 * u + j] & 255u), sy += y[5 * u + j] >> 8;
+                        }
+                        ux[u] = ix, uy[u] = iy, uc[u] = sx | sy << 16;
+                    }
+                }
+                swg_seg_chunk<WD, 4, 1>(ux, uy, uc, groups - g0 < WD ? groups - g0 : WD, tl, S, has, m1, m2, m4, hx, hy);
+            }
+        }
+        for (uint32_t t0 = tail; t0 < e; t0 += WD) {
+            uint32_t ux[1] = {0u}, uy[1] = {0u}, uc[1] = {0u};
+            if (t0 + l < e) {
+                const uint4 k = tok[t0 + l];
+                const uint32_t xa = lut[(k.x >> 3) & 31u], xb = lut[(k.y >> 3) & 31u], xc = lut[(k.z >> 3) & 31u], xd = lut[(k.w >> 3) & 31u];
+                const uint32_t ya = lut[(k.x >> 11) & 31u], yb = lut[(k.y >> 11) & 31u], yc = lut[(k.z >> 11) & 31u], yd = lut[(k.w >> 11) & 31u];
+                const uint32_t ix = (((xa & 255u) * C + (xb & 255u)) * C + (xc & 255u)) * C + (xd & 255u);
+                const uint32_t iy = (((ya & 255u) * C + (yb & 255u)) * C + (yc & 255u)) * C + (yd & 255u);
+                ux[0] = K == 5 ? ix * C : ix, uy[0] = K == 5 ? iy * C : iy;
+                uc[0] = ((xa >> 8) + (xb >> 8) + (xc >> 8) + (xd >> 8)) | ((ya >> 8) + (yb >> 8) + (yc >> 8) + (yd >> 8)) << 16;
+            }
+            swg_seg_chunk<WD, 1, 4>(ux, uy, uc, e - t0 < WD ? e - t0 : WD, tl, S, has, m1, m2, m4, hx, hy);
+        }
+    }
+    const uint32_t h = hx > hy ? hx : hy, u = swg_seg_prefix_max<WD>(h, m1, m2, m4);
+    if (p < n_pairs && l == WD - 1u) {
+        bound[p] = u;
+        ids[p] = p;
+    }
+}
+
+template <int K>
+static void swg_launch_pair_bound_kmer_seg_k(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, const SwgColMax &cm,
+                                             const uint16_t *d_table, uint32_t S, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream)
+{
+    if (S <= 8u)
+        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 8>), dim3((n_pairs + 31u) / 32u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids);
+    else if (S <= 16u)
+        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 16>), dim3((n_pairs + 15u) / 16u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids);
+    else
+        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 32>), dim3((n_pairs + 7u) / 8u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids);
+}
+
+hipError_t swg_launch_pair_bound_kmer_seg(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, int k, uint32_t S, const SwgColMax &cm,
+                                          const uint16_t *d_table, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream)
+{
+    if ((k != 4 && k != 5) || S == 0u || S > SWG_KMER_MAX_SEGMENTS) return hipErrorInvalidValue;
+    if (n_pairs == 0) return hipSuccess;
+    if (k == 5)
+        swg_launch_pair_bound_kmer_seg_k<5>(d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids, stream);
+    else
+        swg_launch_pair_bound_kmer_seg_k<4>(d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids, stream);
     return hipGetLastError();
 }
 
