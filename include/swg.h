@@ -301,7 +301,11 @@ int swg_search_end(swg_ctx *ctx, int ticket, int32_t *scores_out, swg_hit *topk_
  * unordered sum above, a larger value is never above it; the table is 22^k x segments x 2 bytes, refused above 96 MB
  * (k = 5: up to 9 segments).  0: automatic -- with "prune_kmer" 0 the pair (k, segments) is chosen together from a
  * fixed list (a database of millions of sequences: k = 4 in 32 segments), with "prune_kmer" forced the sum is
- * unordered.  Hits are the same under every value. */
+ * unordered.  "prune_cut" (default 0): 0 a stage takes exactly its pairs whose bound reaches the threshold, in order;
+ * 1 the prefix of the length order up to the last such pair.  "prune_refine" (default 0): under "prune_cut" 0 the pairs of
+ * a stage whose bound still reaches the threshold are bounded once more over a k = 4 table of 64 | 128 segments, and the
+ * lesser bound holds; 1 off; 0 automatic -- on where "prune_kmer" and "prune_segments" are both automatic and took k = 4
+ * in segments, off otherwise.  Hits are the same under every value. */
 typedef struct swg_prune_info {
     uint64_t pairs_skipped;
     uint64_t pair_rows_skipped;

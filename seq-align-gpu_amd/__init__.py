@@ -234,6 +234,9 @@ _sig("swg_debug_prune_kmer_read", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_siz
 _sig("swg_debug_prune_kmer_seg", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp])
 _sig("swg_debug_prune_kmer_choice_seg", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_kmer_seg_read", C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp])
+_sig("swg_debug_prune_kmer_refine", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp])
+_sig("swg_debug_prune_refine_choice", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_refine_read", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp])
 _sig("swg_debug_list_deal", C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 
 
@@ -521,6 +524,45 @@ def debug_prune_kmer_choice_seg(forced=0, segments=0, pruned=1, lq=3000, pair_ro
     out = np.zeros(4, dtype=np.int64)
     _check(lib.swg_debug_prune_kmer_choice_seg(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
     return int(out[0]), int(out[1]), int(out[2]), bool(out[3])
+
+
+KMER_REFINE_SEGMENTS = 128
+
+
+def debug_prune_kmer_refine(rows, query, gap_open, gap_extend, segments, flat, offsets, table=True):
+    """Test hook (no device needed): the second-level bound's host mirror -- debug_prune_kmer_seg at k = 4 over the
+    `segments` (32, 64 or 128) segments the refine kernel walks.  -> (table uint16[22^4, segments] or None, U uint64[n])."""
+    r, rp = _i8(rows)
+    lq = r.size // 32
+    qp = None
+    if query is not None:
+        q, qp = _i8(query)
+        lq = q.size
+    f, fp = _i8(flat)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = off.size - 1
+    S = int(segments)
+    t = np.zeros((KMER_CLASSES ** 4, S), dtype=np.uint16) if table and S in (32, 64, 128) else None
+    u = np.zeros(max(n, 1), dtype=np.uint64)
+    _check(lib.swg_debug_prune_kmer_refine(rp, qp, lq, int(gap_open), int(gap_extend), S, fp, off.ctypes.data_as(_vp), n,
+                                           t.ctypes.data_as(_vp) if t is not None else None, u.ctypes.data_as(_vp)))
+    return t, u[:n]
+
+
+def debug_prune_refine_choice(forced=0, segments=0, refine=0, pruned=1, lq=3000, pair_rows=1900000000, table_rate=0, fill_rate=0):
+    """Test hook (no device needed): debug_prune_kmer_choice_seg with option prune_refine -> (k, S, S2): the first-level
+    bound and the segments of the second level's table, 0 without one."""
+    a = np.array([forced, pruned, lq, pair_rows, table_rate, fill_rate, segments, refine], dtype=np.int64)
+    out = np.zeros(3, dtype=np.int64)
+    _check(lib.swg_debug_prune_refine_choice(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def prune_list(bounds, begin, end, threshold):
+    """The list of a stage cut pair by pair, restated in numpy: the ids of the pairs of [begin, end) whose
+    bound reaches the threshold, ascending."""
+    b = np.asarray(bounds)[begin:end]
+    return (begin + np.nonzero(b >= threshold)[0]).astype(np.uint32)
 
 
 PRUNE_PLAN_KEYS = ("mode", "k", "want_scores", "gap_open", "gap_extend", "bits", "use_diag", "n_classes", "work_queue", "both_forms",
@@ -1095,6 +1137,29 @@ class Context:
                                                  b.ctypes.data_as(_vp) if b is not None else None, n, info.ctypes.data_as(_vp)), self.handle)
         return {"k": int(info[0]), "builds": int(info[1]), "pairs": int(info[2]), "segments": int(info[3]), "table": t,
                 "bounds": None if b is None else b[:int(info[2])]}
+
+    def debug_prune_refine_read(self, db, segments=None, arrays=True):
+        """Test hook: the second level and the lists of the search last begun -> dict: k, segments, refine (its S2, 0:
+        none), builds / refine_builds (table builds queued so far, first / second level), table uint16[22^4, segments]
+        (only when `segments` is given), bounds uint32[pairs] as the search left them, stages: a list of (begin, end, T,
+        list) per stage cut pair by pair, list being the pair ids its launches took.  arrays = False: the counters only
+        (before the database's first pruned search there are no bounds to read)."""
+        info = np.zeros(7, dtype=np.uint64)
+        _check(lib.swg_debug_prune_refine_read(self.handle, db.handle, 0, None, None, None, 0, None, 0, info.ctypes.data_as(_vp)), self.handle)
+        n = int(info[2])
+        if not arrays:
+            return {"k": int(info[0]), "builds": int(info[1]), "pairs": n, "segments": int(info[3]), "refine": int(info[4]),
+                    "refine_builds": int(info[5]), "table": None, "bounds": None, "stages": []}
+        S = int(segments or 0)
+        t = np.zeros((KMER_CLASSES ** 4, S), dtype=np.uint16) if S else None
+        b = np.zeros(max(n, 1), dtype=np.uint32)
+        l = np.zeros(max(n, 1), dtype=np.uint32)
+        st = np.zeros((256, 4), dtype=np.uint32)
+        _check(lib.swg_debug_prune_refine_read(self.handle, db.handle, S, t.ctypes.data_as(_vp) if t is not None else None, b.ctypes.data_as(_vp),
+                                               l.ctypes.data_as(_vp), n, st.ctypes.data_as(_vp), 256, info.ctypes.data_as(_vp)), self.handle)
+        stages = [(int(r[0]), int(r[1]), int(r[2]), l[int(r[0]):int(r[0]) + int(r[3])].copy()) for r in st[:int(info[6])]]
+        return {"k": int(info[0]), "builds": int(info[1]), "pairs": n, "segments": int(info[3]), "refine": int(info[4]),
+                "refine_builds": int(info[5]), "table": t, "bounds": b[:n], "stages": stages}
 
     def debug_bounds_last(self):
         """What the last align_bounds* call of this context did (swg_debug_bounds_last) -> dict: pairs on the bounds kernel,

@@ -243,6 +243,7 @@ extern "C" void swg_destroy(swg_ctx *ctx)
     (void)hipFree(ctx->d_kmer_cprof);
     (void)hipFree(ctx->d_kmer_table[0]);
     (void)hipFree(ctx->d_kmer_table[1]);
+    (void)hipFree(ctx->d_kmer_refine);
     (void)hipFree(ctx->d_profile[0]);
     (void)hipFree(ctx->d_profile[1]);
     (void)hipFree(ctx->d_profile[2]);
@@ -347,6 +348,14 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
         if (value < 0 || value > (long)SWG_KMER_MAX_SEGMENTS)
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_segments must be 0 (auto) or 1..32 (the segments of the k-mer bound's table; 1: unsegmented)");
         ctx->opt_prune_segments = value;
+    } else if (!strcmp(key, "prune_refine")) {
+        if (!swg_prune_refine_value_ok(value))
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_refine must be 0 (auto), 1 (off), 64 or 128 (the segments of the second-level bound's table)");
+        ctx->opt_prune_refine = value;
+    } else if (!strcmp(key, "prune_cut")) {
+        if (value != 0 && value != 1)
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_cut must be 0 (a stage's pairs are cut one by one) or 1 (the prefix of the length order)");
+        ctx->opt_prune_cut = value;
     } else if (!strcmp(key, "q32_waves")) {
         ctx->opt_q32_waves = value;
     } else if (!strcmp(key, "wave_budget")) {
@@ -1223,9 +1232,14 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
                 // pair, and its device-side length is the cut -- the kernel reads it once at entry, leaves before it
                 // loads the profile when it is 0, and hands out exactly those pairs in every pass (no batch claims in
                 // list mode).  So the fill kernels are the unpruned search's, instruction for instruction.
+                // Pair by pair (the default): behind the threshold, the second-level bound of the stage's pairs that still
+                // reach it (prune->refine), then the stage's own list -- the ids of its pairs whose bound reaches T, in
+                // order -- and its length; both held for all the stage's passes like the prefix cut.
                 uint32_t *cw = db->d_counters;
                 const uint32_t n_pairs_all = (uint32_t)swg_db_pair_count(db);
-                uint32_t *d_ids = db->d_pair_bound + n_pairs_all;
+                uint32_t *d_ids = db->d_pair_bound + n_pairs_all, *d_lists = d_ids + n_pairs_all, *d_tiles = d_lists + n_pairs_all;
+                uint32_t *d_recs = d_tiles + swg_prune_tile_words(n_pairs_all);
+                std::vector<uint32_t> cut_stages;
                 if (prune->kmer > 1 && prune->segments > 1) // (the table of this epoch: plan_prune queued its build on this stream)
                     HIP_TRY(ctx, swg_launch_pair_bound_kmer_seg(T.d_tok, T.d_pair_off, n_pairs_all, prune->kmer, (uint32_t)prune->segments, ctx->prune_colmax,
                                                                 ctx->d_kmer_table[prune->kmer - 4], db->d_pair_bound, d_ids, qs));
@@ -1247,8 +1261,19 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
                     if (si > 0) {
                         HIP_TRY(ctx, swg_launch_prune_threshold(db->d_scores, db->d_order, (uint32_t)((size_t)db->n_bins * SWG_BIN), (uint32_t)prune_k,
                                                                 db->d_hist, cw + SWG_PRUNE_WORD_T, qs));
-                        HIP_TRY(ctx, swg_launch_prune_cut(db->d_pair_bound, T.d_pair_off, st.b, st.en, cw + SWG_PRUNE_WORD_T, cw + SWG_PRUNE_WORD_CUT, qs));
-                        q.list = d_ids + st.b;
+                        if (prune->prefix_cut) {
+                            HIP_TRY(ctx, swg_launch_prune_cut(db->d_pair_bound, T.d_pair_off, st.b, st.en, cw + SWG_PRUNE_WORD_T, cw + SWG_PRUNE_WORD_CUT, qs));
+                            q.list = d_ids + st.b;
+                        } else {
+                            if (prune->refine) // (the table of this epoch: plan_prune queued its build on this stream)
+                                HIP_TRY(ctx, swg_launch_pair_bound_refine(T.d_tok, T.d_pair_off, st.b, st.en, (uint32_t)prune->refine, ctx->prune_colmax, ctx->d_kmer_refine,
+                                                                          cw + SWG_PRUNE_WORD_T, db->d_pair_bound, qs));
+                            const size_t rec = cut_stages.size() / 2;
+                            HIP_TRY(ctx, swg_launch_prune_list(db->d_pair_bound, T.d_pair_off, st.b, st.en, cw + SWG_PRUNE_WORD_T, d_tiles, d_lists + st.b,
+                                                               cw + SWG_PRUNE_WORD_CUT, rec < SWG_PRUNE_STAGE_RECS ? d_recs + 2 * rec : nullptr, qs));
+                            q.list = d_lists + st.b;
+                            cut_stages.push_back(st.b), cut_stages.push_back(st.en);
+                        }
                         q.list_count = cw + SWG_PRUNE_WORD_CUT;
                     }
                     for (int pass = 0; pass < pl.npass; ++pass) {
@@ -1257,6 +1282,7 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
                     }
                 }
                 q.list = nullptr, q.list_count = nullptr;
+                const_cast<swg_db *>(db)->prune_stages.swap(cut_stages);
             } else
             for (int part = 0; part < (split ? 2 : 1); ++part) {
                 const int pform = split && part == 1 ? 2 : form;
@@ -2347,6 +2373,38 @@ static int ensure_kmer_table(swg_ctx *ctx, int k, int S)
     return SWG_OK;
 }
 
+// The second level's table (k = 4 in S2 = 64 or 128 segments): a buffer of its own, keyed by (S2, epoch), queued behind the
+// first level's under the same rules and counted apart from it (kmer_refine_builds).
+static int ensure_kmer_refine_table(swg_ctx *ctx, int S2)
+{
+    const size_t lq = ctx->query_len();
+    if (S2 != 64 && S2 != 128) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the second-level bound's table: %d segments (64 or 128)", S2);
+    const size_t entries = (size_t)swg_kmer_entries(4) * (size_t)S2;
+    if (ctx->d_kmer_refine && ctx->kmer_refine_epoch == ctx->epoch && ctx->kmer_refine_segments == (uint32_t)S2) return SWG_OK;
+    if (lq * 32 > ctx->d_kmer_cprof_cap) {
+        (void)hipFree(ctx->d_kmer_cprof);
+        ctx->d_kmer_cprof = nullptr;
+        ctx->d_kmer_cprof_cap = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->d_kmer_cprof, lq * 32));
+        ctx->d_kmer_cprof_cap = lq * 32;
+    }
+    if (!ctx->d_kmer_refine || ctx->kmer_refine_cap < entries) {
+        (void)hipFree(ctx->d_kmer_refine);
+        ctx->d_kmer_refine = nullptr;
+        ctx->kmer_refine_cap = 0;
+        ctx->kmer_refine_epoch = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->d_kmer_refine, entries * sizeof(uint16_t)));
+        ctx->kmer_refine_cap = entries;
+    }
+    const long go = (long)ctx->gap_open + ctx->gap_extend, ge = ctx->gap_extend;
+    HIP_TRY(ctx, swg_launch_kmer_table(ctx->d_sub, ctx->d_query, ctx->query_pssm ? ctx->d_pssm : nullptr, (uint32_t)lq, (uint32_t)-go, (uint32_t)-ge, 4,
+                                       (uint32_t)S2, ctx->d_kmer_cprof, ctx->d_kmer_refine, ctx->stream));
+    ctx->kmer_refine_epoch = ctx->epoch;
+    ctx->kmer_refine_segments = (uint32_t)S2;
+    ++ctx->kmer_refine_builds;
+    return SWG_OK;
+}
+
 // Whether this search is pruned (swg_prune_plan has the rules), decided once the plan stands; a pruned search gets the
 // bound's table for the current query and scoring (built on the host when either has changed; it travels to the bound
 // kernel as a launch argument) and its slot's buffer of pair bounds.
@@ -2380,12 +2438,13 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
         return SWG_OK; // (launch_diag reports it)
     a.n_segments = segs.size();
     P->prune = swg_prune_plan(a);
-    ctx->prune_last_kmer = 0, ctx->prune_last_segments = 0;
+    ctx->prune_last_kmer = 0, ctx->prune_last_segments = 0, ctx->prune_last_refine = 0;
     if (!P->prune.on) return SWG_OK;
     // which bound: the colmax table, or the k-mer table of the k that pays for its build on this range (a forced k as it is)
     SwgKmerAsk ka;
     ka.forced = ctx->opt_prune_kmer;
     ka.forced_segments = ctx->opt_prune_segments;
+    ka.forced_refine = ctx->opt_prune_refine;
     ka.pruned = true;
     ka.lq = ctx->query_len();
     ka.pair_rows = 4ull * (db->ptok.pair_blocks_prefix[wk.pair_end[0]] - db->ptok.pair_blocks_prefix[wk.pair_begin[0]]);
@@ -2396,19 +2455,26 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
         const int rk = ensure_kmer_table(ctx, P->prune.kmer, P->prune.segments);
         if (rk != SWG_OK) return rk;
     }
+    // how a stage is cut: pair by pair, behind the second-level bound where that pays, or the prefix of the length order
+    P->prune.prefix_cut = ctx->opt_prune_cut == 1;
+    P->prune.refine = ctx->prune_last_refine = P->prune.prefix_cut ? 0 : swg_prune_refine_choice(ka, P->prune.kmer, P->prune.segments);
+    if (P->prune.refine) {
+        const int rk = ensure_kmer_refine_table(ctx, P->prune.refine);
+        if (rk != SWG_OK) return rk;
+    }
     if (ctx->prune_colmax_epoch != ctx->epoch) {
         ctx->prune_colmax = ctx->query_pssm ? swg_prune_colmax(ctx->pssm.data(), nullptr, ctx->query_len())
                                             : swg_prune_colmax(&ctx->sub[0][0], ctx->query.data(), ctx->query_len());
         ctx->prune_colmax_epoch = ctx->epoch;
     }
-    // (the bounds, then the pair ids a cut stage's list launches read: two words per pair)
+    // (the bounds, the pair ids a prefix-cut stage's list launches read, the stages' own lists: swg_prune_pair_words)
     swg_db::Bufs &b = db->bufs[ctx->cur - ctx->slots];
     const size_t n_pairs = (size_t)swg_db_pair_count(db);
     if (!b.d_pair_bound || b.pair_bound_cap < n_pairs) {
         (void)hipFree(b.d_pair_bound);
         b.d_pair_bound = nullptr;
         b.pair_bound_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&b.d_pair_bound, std::max<size_t>(8, n_pairs * 8)));
+        HIP_TRY(ctx, hipMalloc(&b.d_pair_bound, swg_prune_pair_words(n_pairs) * sizeof(uint32_t)));
         b.pair_bound_cap = n_pairs;
     }
     db->d_pair_bound = b.d_pair_bound;
@@ -2716,6 +2782,42 @@ extern "C" int swg_debug_prune_kmer_seg_read(swg_ctx *ctx, const swg_db *db, int
         if (!db || !db->d_pair_bound || bound_cap < n_pairs)
             return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_kmer_seg_read: no pair bounds on this database, or too little room");
         HIP_TRY(ctx, hipMemcpy(bound_out, db->d_pair_bound, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    return SWG_OK;
+}
+
+// ... and of the second level and the lists: the table of S2 segments (table_out, or NULL), the bounds as the search last
+// begun left them, the list words (one per pair: a stage's list starts at its first pair's word) and, four words per
+// stage cut pair by pair, {begin, end, T, kept pairs}.  info[0..6] = k, first-level builds, pairs, S, S2 (0: no second
+// level), second-level builds, stages written to stages_out.
+extern "C" int swg_debug_prune_refine_read(swg_ctx *ctx, const swg_db *db, int S2, uint16_t *table_out, uint32_t *bound_out, uint32_t *list_out, size_t pair_cap,
+                                           uint32_t *stages_out, size_t stages_cap, uint64_t *info)
+{
+    if (!ctx || !info) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_refine_read: NULL argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    const size_t n_pairs = db ? (size_t)swg_db_pair_count(db) : 0;
+    info[0] = (uint64_t)ctx->prune_last_kmer, info[1] = ctx->kmer_builds, info[2] = n_pairs, info[3] = (uint64_t)ctx->prune_last_segments;
+    info[4] = (uint64_t)ctx->prune_last_refine, info[5] = ctx->kmer_refine_builds, info[6] = 0;
+    if (table_out) {
+        if (!ctx->d_kmer_refine || ctx->kmer_refine_epoch != ctx->epoch || ctx->kmer_refine_segments != (uint32_t)S2)
+            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_refine_read: no second-level table in %d segments for the current query and scoring", S2);
+        HIP_TRY(ctx, hipMemcpy(table_out, ctx->d_kmer_refine, (size_t)swg_kmer_entries(4) * (size_t)S2 * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    }
+    if (bound_out || list_out || stages_out) {
+        if (!db || !db->d_pair_bound || pair_cap < n_pairs)
+            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_refine_read: no pair bounds on this database, or too little room");
+        if (bound_out) HIP_TRY(ctx, hipMemcpy(bound_out, db->d_pair_bound, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (list_out) HIP_TRY(ctx, hipMemcpy(list_out, db->d_pair_bound + 2 * n_pairs, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (stages_out) {
+            const size_t n = std::min<size_t>(std::min<size_t>(db->prune_stages.size() / 2, SWG_PRUNE_STAGE_RECS), stages_cap);
+            std::vector<uint32_t> recs(2 * n);
+            if (n) HIP_TRY(ctx, hipMemcpy(recs.data(), db->d_pair_bound + 3 * n_pairs + swg_prune_tile_words(n_pairs), 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < n; ++i)
+                stages_out[4 * i] = db->prune_stages[2 * i], stages_out[4 * i + 1] = db->prune_stages[2 * i + 1], stages_out[4 * i + 2] = recs[2 * i],
+                               stages_out[4 * i + 3] = recs[2 * i + 1];
+            info[6] = n;
+        }
     }
     return SWG_OK;
 }

@@ -886,6 +886,73 @@ extern "C" int swg_debug_prune_kmer_choice_seg(const int64_t *in, int64_t *out)
     return SWG_OK;
 }
 
+// The second level.  Automatic only behind an automatic first level that took a segmented k = 4 candidate (a forced
+// "prune_kmer" or "prune_segments" leaves d_pair_bound the mirror of exactly that bound); forced, behind any.  The
+// candidates in the style of SWG_KMER_CANDIDATES: what the headline keeps at (4, 32) cut pair by pair less what it keeps
+// with the second level, and the seconds per pair row of the range the refine kernel takes (it walks the pairs of the
+// cut stages whose first bound reaches T); the table is 22^4 * 4 * lq cells like the first.  A step up must cost at most
+// half of what it saves.  Constants: profiles/prune_refine_ab.txt -- rows kept 0.2677 / 0.2443 / 0.2249 (section 2); the
+// refine kernel at 128 segments 4.11 ms per search over 1 938 193 684 pair rows (section 3), which 64 segments, not traced
+// singly and half the bytes, is charged too.
+struct SwgRefineCandidate {
+    int S2;
+    double gain, bound_row;
+};
+static const SwgRefineCandidate SWG_REFINE_CANDIDATES[] = {{0, 0.0, 0.0}, {64, 0.0234, 2.1e-12}, {128, 0.0428, 2.1e-12}};
+int swg_prune_refine_choice(const SwgKmerAsk &a, int k, int S)
+{
+    if (!a.pruned || k < 1) return 0;
+    if (a.forced_refine == 64 || a.forced_refine == 128) return (int)a.forced_refine;
+    if (a.forced_refine != 0 || a.forced != 0 || a.forced_segments != 0 || k != 4 || S <= 1) return 0;
+    if (a.table_rate <= 0 || a.fill_rate <= 0 || a.lq == 0) return 0;
+    auto cost = [&](const SwgRefineCandidate &c) {
+        return c.S2 == 0 ? 0.0 : (double)swg_kmer_entries(4) * 4 * (double)a.lq / a.table_rate + c.bound_row * (double)a.pair_rows;
+    };
+    auto gain = [&](const SwgRefineCandidate &c) { return c.gain * (double)a.pair_rows / a.fill_rate; };
+    const SwgRefineCandidate *cur = &SWG_REFINE_CANDIDATES[0];
+    for (const SwgRefineCandidate &c : SWG_REFINE_CANDIDATES)
+        if (c.gain > cur->gain && cost(c) - cost(*cur) <= 0.5 * (gain(c) - gain(*cur))) cur = &c;
+    return cur->S2;
+}
+
+// test hook: swg_debug_prune_kmer_choice_seg's inputs and in[7] = the forced refinement (option "prune_refine");
+// out[0..2] = k, S, S2 (0: no second level)
+extern "C" int swg_debug_prune_refine_choice(const int64_t *in, int64_t *out)
+{
+    if (!in || !out || in[2] < 0 || in[3] < 0 || in[4] < 0 || in[5] < 0 || in[6] < 0 || !swg_prune_refine_value_ok((long)in[7])) return SWG_ERR_ARG;
+    SwgKmerAsk a;
+    a.forced = (long)in[0], a.pruned = in[1] != 0, a.lq = (size_t)in[2], a.pair_rows = (uint64_t)in[3];
+    a.table_rate = in[4] ? (double)in[4] : SWG_KMER_TABLE_RATE;
+    a.fill_rate = in[5] ? (double)in[5] : swg_kmer_fill_rate(a.lq);
+    a.forced_segments = (long)in[6];
+    a.forced_refine = (long)in[7];
+    int S = 0;
+    out[0] = swg_prune_kmer_choice(a, &S);
+    out[1] = S;
+    out[2] = swg_prune_refine_choice(a, (int)out[0], S);
+    return SWG_OK;
+}
+
+// test hook: the second level's table (22^4 x S2 uint16, or NULL) and its bound of each sequence: swg_debug_prune_kmer_seg
+// at k = 4 with the segments the refine kernel walks -- 32 (the first level's widest), 64 or 128
+extern "C" int swg_debug_prune_kmer_refine(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S2, const int8_t *flat,
+                                           const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out)
+{
+    if (!rows || lq == 0 || (S2 != 32 && S2 != 64 && S2 != 128) || gap_open > 0 || gap_extend > 0 || (n > 0 && (!flat || !offsets || !u_out)))
+        return SWG_ERR_ARG;
+    std::vector<int8_t> cprof(lq * SWG_KMER_CLASSES);
+    swg_kmer_cprof(rows, idx, lq, cprof.data());
+    std::vector<uint16_t> own;
+    if (!table_out) {
+        own.resize(swg_kmer_entries(4) * (size_t)S2);
+        table_out = own.data();
+    }
+    swg_kmer_table_seg(cprof.data(), lq, -(gap_open + gap_extend), -gap_extend, 4, (size_t)S2, table_out);
+    const SwgColMax cm = swg_prune_colmax(rows, idx, lq);
+    for (size_t i = 0; i < n; ++i) u_out[i] = swg_kmer_bound_seg(table_out, 4, (size_t)S2, cm, flat + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+    return SWG_OK;
+}
+
 // Both 16-bit forms in one search (plan_search in swg_api.cpp): the length from which a sequence can reach the f16 cells' ceiling
 // as an exact copy of a stretch of the query -- such a copy scores qbound / lq per row on average, qbound being the
 // query's best possible total --, and where that length cuts the sorted pair order (kept per database and length).

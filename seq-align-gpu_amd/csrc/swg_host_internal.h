@@ -184,7 +184,9 @@ struct swg_db {
                                         // [8..15] class stamps, [16] sequences the f16 fill flagged, [17] their pairs
         uint64_t *d_keys = nullptr;     // top-K candidate keys (SWG_TOPK_CAND_CAP)
         uint32_t *d_hist = nullptr;     // top-K score histogram
-        uint32_t *d_pair_bound = nullptr; // a pruned search's score bound per pair, then the pair ids in order (allocated by the first one)
+        // a pruned search's score bound per pair, then the pair ids in order, then a cut stage's list (its kept pairs, at
+        // most a pair each) and the list's tile counts (swg_prune_pair_words; allocated by the first one)
+        uint32_t *d_pair_bound = nullptr;
         size_t pair_bound_cap = 0;        // pairs it has room for
     } bufs[4];
     int32_t *d_scores = nullptr;
@@ -193,6 +195,7 @@ struct swg_db {
     uint64_t *d_keys = nullptr;
     uint32_t *d_hist = nullptr;
     uint32_t *d_pair_bound = nullptr;
+    std::vector<uint32_t> prune_stages; // {begin, end} of the stages cut pair by pair in the pruned search last launched (tests)
 };
 
 // The score ceilings of the cell forms, and the largest gap magnitude the packed-f16 cells hold as an exact integer.
@@ -250,7 +253,14 @@ struct SwgPrunePlan {
     uint32_t head_pairs = 0; // one segment: pairs of the first stage; 0: the stages are the segments
     int kmer = 0;            // the bound: 1 colmax, 4 / 5 the k-mer table of that k (swg_prune_kmer_choice); 0 while off
     int segments = 0;        // ... and the segments of that table (1: the unordered sum of swg_pair_bound_kmer_kernel)
+    int refine = 0;          // the second level's segments (swg_prune_refine_choice): 64, 128, or 0 without one
+    bool prefix_cut = false; // option "prune_cut" = 1: a stage's list is the prefix up to its last pair that reaches T
 };
+// words of swg_db::Bufs::d_pair_bound for n pairs: bounds, ids, lists (a stage's from its first pair's word), one tile
+// count per SWG_PRUNE_TILE pairs, and {T, kept pairs} of the first SWG_PRUNE_STAGE_RECS cut stages (tests read them back)
+#define SWG_PRUNE_STAGE_RECS 256u
+inline size_t swg_prune_tile_words(size_t n_pairs) { return n_pairs / SWG_PRUNE_TILE + 2; }
+inline size_t swg_prune_pair_words(size_t n_pairs) { return 3 * n_pairs + swg_prune_tile_words(n_pairs) + 2 * SWG_PRUNE_STAGE_RECS; }
 SwgPrunePlan swg_prune_plan(const SwgPruneAsk &a);
 extern "C" int swg_debug_prune_bound(const int8_t *rows, const int8_t *idx, size_t lq, const int8_t *flat, const uint64_t *offsets, size_t n,
                                      uint8_t *colmax_out, uint64_t *u_out);
@@ -272,6 +282,7 @@ inline double swg_kmer_fill_rate(size_t lq) { return SWG_KMER_FILL_PASS_RATE / (
 struct SwgKmerAsk {
     long forced = 0;     // option "prune_kmer": 0 automatic, 1, 4, 5
     long forced_segments = 0; // option "prune_segments": 0 automatic, 1..SWG_KMER_MAX_SEGMENTS
+    long forced_refine = 0;   // option "prune_refine": 0 automatic, 1 off, 64 or 128
     bool pruned = false; // swg_prune_plan's answer
     size_t lq = 0;
     uint64_t pair_rows = 0; // rows of the range's pairs
@@ -289,9 +300,16 @@ extern "C" int swg_debug_prune_kmer_seg(const int8_t *rows, const int8_t *idx, s
                                         const int8_t *flat, const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out);
 extern "C" int swg_debug_prune_kmer_choice(const int64_t *in, int64_t *out);
 extern "C" int swg_debug_prune_kmer_choice_seg(const int64_t *in, int64_t *out);
+// The second level: the segments S2 of the k = 4 table the pairs a first-level bound of (k, S) leaves
+// standing are walked over once more -- 64, 128, or 0 for none.
+int swg_prune_refine_choice(const SwgKmerAsk &a, int k, int S);
+inline bool swg_prune_refine_value_ok(long v) { return v == 0 || v == 1 || v == 64 || v == 128; }
+extern "C" int swg_debug_prune_refine_choice(const int64_t *in, int64_t *out);
+extern "C" int swg_debug_prune_kmer_refine(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S2, const int8_t *flat,
+                                           const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out);
 // the words of a search's counter block (swg_db::Bufs::d_counters) a pruned search uses: the threshold so far and the
-// threshold kernel's status word, then what swg_launch_prune_cut writes: the pairs the stage takes, the pairs skipped so
-// far, their token blocks (64 bits)
+// threshold kernel's status word, then what swg_launch_prune_cut or swg_launch_prune_list writes: the pairs the stage
+// takes, the pairs skipped so far, their token blocks (64 bits)
 #define SWG_PRUNE_WORD_T 18u
 #define SWG_PRUNE_WORD_CUT 20u
 
@@ -452,6 +470,15 @@ struct swg_ctx {
     long opt_prune_segments = 0;              // option "prune_segments": 0 auto, 1..32
     int prune_last_segments = 0;              // the S of the search last begun on this context
     uint64_t kmer_builds = 0; // table builds queued so far (tests)
+    // the second level: its k = 4 table of 64 or 128 segments, keyed by (S2, epoch) and queued behind the first
+    long opt_prune_refine = 0; // option "prune_refine": 0 auto, 1 off, 64, 128
+    long opt_prune_cut = 0;    // option "prune_cut": 0 pair by pair, 1 the prefix of the length order
+    uint16_t *d_kmer_refine = nullptr;
+    uint64_t kmer_refine_epoch = 0;
+    uint32_t kmer_refine_segments = 0;
+    size_t kmer_refine_cap = 0;     // entries allocated
+    uint64_t kmer_refine_builds = 0; // builds of it queued so far (tests)
+    int prune_last_refine = 0;       // the S2 of the search last begun on this context (0: none)
     int prune_last_kmer = 0;  // the k of the search last begun on this context (0: not pruned)
     uint32_t opt_seg_blocks = SWG_DYN_SEG_BLOCKS; // token blocks per launch of the multi-pass fill (option "segment_blocks": tests)
     // device state

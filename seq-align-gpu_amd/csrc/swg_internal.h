@@ -330,11 +330,14 @@ static inline uint64_t swg_kmer_entries(int k) { return k == 5 ? 5153632ull : k 
 // columns (S = 1: the block's local score against the whole query).  At most SWG_KMER_MAX_SEGMENTS segments -- one lane
 // of the ordered bound kernel each -- and SWG_KMER_TABLE_BUDGET bytes, which admits (k, S) = (5, 8).
 #define SWG_KMER_MAX_SEGMENTS 32u
+// ... and of the second level's table, which only the pairs a first-level bound leaves standing are walked over (k = 4:
+// 60 MB at 128 segments), four segments to a lane
+#define SWG_KMER_REFINE_SEGMENTS 128u
 #define SWG_KMER_TABLE_BUDGET (96ull << 20)
 // d_cprof[lq][32] (int8; entries 22..31 of a row unused): query column i against class c, from the device copies of the
 // table and the index query (d_pssm == NULL) or of the PSSM; then d_table[22^k][S] = the best cell of every class block
 // against the query, segment by segment, under gap magnitudes g (first residue of a gap) and e (every further one).
-// k: 4 or 5; S: 1..SWG_KMER_MAX_SEGMENTS.
+// k: 4 or 5; S: 1..SWG_KMER_REFINE_SEGMENTS (the bound kernels take what they can walk: see each).
 hipError_t swg_launch_kmer_table(const int8_t *d_sub, const int8_t *d_query, const int8_t *d_pssm, uint32_t lq, uint32_t g, uint32_t e,
                                  int k, uint32_t S, int8_t *d_cprof, uint16_t *d_table, hipStream_t stream);
 // swg_launch_pair_bound with the k-mer bound: blocks of 4 token rows (k = 4), or of 5 with a tail of fewer than 20 rows
@@ -353,6 +356,16 @@ hipError_t swg_launch_prune_threshold(const int32_t *d_scores, const uint32_t *d
 // stage's launches take), d_out[1] += the pairs behind the cut, (uint64 at d_out[2]) += their token blocks
 hipError_t swg_launch_prune_cut(const uint32_t *d_bound, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, const uint32_t *d_thr,
                                 uint32_t *d_out, hipStream_t stream);
+// The second level: d_bound[p] = min(d_bound[p], the ordered bound over d_table, k = 4 in S2 = 64 or 128 segments) for the
+// pairs of [begin, end) with d_bound[p] >= *d_thr
+hipError_t swg_launch_pair_bound_refine(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, uint32_t S2, const SwgColMax &cm,
+                                        const uint16_t *d_table, const uint32_t *d_thr, uint32_t *d_bound, hipStream_t stream);
+// The cut pair by pair: d_list[0 .. d_out[0]) = the pairs of [begin, end) with d_bound >= *d_thr, ascending; d_out[1] +=
+// the others, (uint64 at d_out[2]) += their token blocks.  d_tiles: one word per SWG_PRUNE_TILE pairs of the range;
+// d_rec (or NULL): {*d_thr, d_out[0]} once more, for the tests.
+#define SWG_PRUNE_TILE 1024u // 256 threads, 4 consecutive pairs each
+hipError_t swg_launch_prune_list(const uint32_t *d_bound, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, const uint32_t *d_thr,
+                                 uint32_t *d_tiles, uint32_t *d_list, uint32_t *d_out, uint32_t *d_rec, hipStream_t stream);
 // ... and for the n_queries score rows of a batch (swg_search_multi) at once: d_hist[n_queries][4096],
 // d_meta[n_queries][4] = {threshold, status, candidate count, -}, d_cand[n_queries][cap]
 #define SWG_TOPK_MULTI_CAP 1024u

@@ -2901,7 +2901,7 @@ hipError_t swg_launch_kmer_table(const int8_t *d_sub, const int8_t *d_query, con
                                  int k, uint32_t S, int8_t *d_cprof, uint16_t *d_table, hipStream_t stream)
 {
     const uint32_t n = (uint32_t)swg_kmer_entries(k);
-    if (n == 0u || lq == 0u || lq > (1u << 24) || S == 0u || S > SWG_KMER_MAX_SEGMENTS) return hipErrorInvalidValue;
+    if (n == 0u || lq == 0u || lq > (1u << 24) || S == 0u || S > SWG_KMER_REFINE_SEGMENTS) return hipErrorInvalidValue;
     // (gap magnitudes beyond any block's score change nothing, and keep the int32 cells far from their range)
     const int gi = (int)(g > 65536u ? 65536u : g), ei = (int)(e > 65536u ? 65536u : e);
     hipLaunchKernelGGL(swg_kmer_cprof_kernel, dim3((lq * 32u + 255u) / 256u), dim3(256), 0, stream, d_sub, d_query, d_pssm, lq, d_cprof);
@@ -3189,6 +3189,226 @@ hipError_t swg_launch_prune_cut(const uint32_t *d_bound, const uint32_t *d_pair_
     const uint32_t wgs = want < 1u ? 1u : want > 1024u ? 1024u : want;
     hipLaunchKernelGGL(swg_prune_cut_kernel, dim3(wgs), dim3(SWG_PRUNE_CUT_THREADS), 0, stream, d_bound, begin, end, d_thr, d_out);
     hipLaunchKernelGGL(swg_prune_tally_kernel, dim3(1), dim3(64), 0, stream, d_pair_off, begin, end, d_out);
+    return hipGetLastError();
+}
+
+// The second level of the ordered bound: the pairs of one cut stage whose first-level bound still reaches
+// the threshold are walked once more over a k = 4 table of S2 = 32 * PL segments.  32 lanes per pair, lane l holding H of
+// the PL consecutive segments from l * PL: a block's S2 entries are one load of 2 * PL bytes per lane and sequence, the
+// prefix maximum runs in the lane over its PL values and then, as an exclusive prefix maximum of the lanes' last ones,
+// across the lanes (swg_seg_prefix_max<32> behind a one-lane shift).  Chunks, padding, reset and tail rules and the
+// gathers issued ahead of the recurrence are swg_pair_bound_kmer_seg_kernel's.  The segments' boundaries are not the
+// first level's, and both are bounds: bound[p] = min(bound[p], refined).  Every walk runs to its pair's end: a pair that
+// is kept reaches T late in its walk (its bound per row is not far above T's), so stopping there would save little, and
+// the bounds a search leaves are exactly the mirror's.
+template <int PL>
+__device__ __forceinline__ void swg_refine_step(uint32_t (&h)[PL], const uint32_t (&t)[PL], uint32_t m0)
+{
+    uint32_t pm[PL];
+    pm[0] = h[0];
+#pragma unroll
+    for (int j = 1; j < PL; ++j) pm[j] = h[j] > pm[j - 1] ? h[j] : pm[j - 1];
+    // wave_shr:1 -- lane l takes lane l - 1's; the group's first lane (no source, or the other group's last) takes 0
+    uint32_t ex = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)pm[PL - 1], 0x138, 0xf, 0xf, true) & m0;
+    ex = swg_seg_prefix_max<32>(ex, 0u, 0u, 0u);
+#pragma unroll
+    for (int j = 0; j < PL; ++j) h[j] = (ex > pm[j] ? ex : pm[j]) + t[j];
+}
+
+// a lane's PL entries of one block, each capped by the block's colmax sum c
+template <int PL>
+__device__ __forceinline__ void swg_refine_entries(const uint16_t *at, uint32_t c, uint32_t (&t)[PL])
+{
+    uint32_t w[2] = {0u, 0u};
+    if (PL == 4) {
+        const uint2 v = *reinterpret_cast<const uint2 *>(at);
+        w[0] = v.x, w[1] = v.y;
+    } else {
+        w[0] = *reinterpret_cast<const uint32_t *>(at);
+    }
+#pragma unroll
+    for (int j = 0; j < PL; ++j) {
+        const uint32_t e = j & 1 ? w[j / 2] >> 16 : w[j / 2] & 0xFFFFu;
+        t[j] = e < c ? e : c;
+    }
+}
+
+template <int K, int PL>
+__global__ __launch_bounds__(256) void swg_pair_bound_refine_kernel(const uint4 *tok, const uint32_t *pair_off, uint32_t begin, uint32_t end, SwgColMax cm,
+                                                                    const uint16_t *table, const uint32_t *thr, uint32_t *bound)
+{
+    static_assert(K == 4 && (PL == 2 || PL == 4), "the refined bound: k = 4 over 64 or 128 segments");
+    __shared__ uint32_t lut[32]; // residue index -> class | colmax << 8
+    if (threadIdx.x < 32u) lut[threadIdx.x] = swg_kmer_class(threadIdx.x) | (uint32_t)cm.v[threadIdx.x] << 8;
+    __syncthreads();
+    const uint32_t p = begin + blockIdx.x * 8u + (threadIdx.x >> 5), l = threadIdx.x & 31u;
+    if (p >= end) return; // (the same for all lanes of a group, and so is everything below)
+    const uint32_t T = thr[0], first = bound[p];
+    if (first < T) return;
+    const uint32_t C = SWG_KMER_CLASSES, S2 = 32u * PL;
+    const uint16_t *tl = table + l * PL;
+    const uint32_t m0 = l >= 1u ? 0xFFFFFFFFu : 0u;
+    uint32_t hx[PL], hy[PL];
+#pragma unroll
+    for (int j = 0; j < PL; ++j) hx[j] = 0u, hy[j] = 0u;
+    auto group_max = [&]() -> uint32_t {
+        uint32_t m = 0u;
+#pragma unroll
+        for (int j = 0; j < PL; ++j) m = hx[j] > m ? hx[j] : m, m = hy[j] > m ? hy[j] : m;
+        return (uint32_t)__shfl((int)swg_seg_prefix_max<32>(m, 0u, 0u, 0u), 31, 32);
+    };
+    const uint32_t b0 = pair_off[p], e = pair_off[p + 1u];
+    constexpr int U = 4; // blocks per round of gathers
+    for (uint32_t t0 = b0; t0 < e; t0 += 32u) {
+        uint32_t ux = 0u, uy = 0u, uc = 0u; // (past the pair's end: the all-padding block, whose entries are 0)
+        if (t0 + l < e) {
+            const uint4 k = tok[t0 + l];
+            const uint32_t xa = lut[(k.x >> 3) & 31u], xb = lut[(k.y >> 3) & 31u], xc = lut[(k.z >> 3) & 31u], xd = lut[(k.w >> 3) & 31u];
+            const uint32_t ya = lut[(k.x >> 11) & 31u], yb = lut[(k.y >> 11) & 31u], yc = lut[(k.z >> 11) & 31u], yd = lut[(k.w >> 11) & 31u];
+            ux = (((xa & 255u) * C + (xb & 255u)) * C + (xc & 255u)) * C + (xd & 255u);
+            uy = (((ya & 255u) * C + (yb & 255u)) * C + (yc & 255u)) * C + (yd & 255u);
+            uc = ((xa >> 8) + (xb >> 8) + (xc >> 8) + (xd >> 8)) | ((ya >> 8) + (yb >> 8) + (yc >> 8) + (yd >> 8)) << 16;
+        }
+        const uint32_t cnt = e - t0 < 32u ? e - t0 : 32u;
+        for (uint32_t j0 = 0u; j0 < cnt; j0 += (uint32_t)U) {
+            uint32_t tx[U][PL], ty[U][PL];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int src = (int)j0 + u; // (< 32: cnt <= 32, both multiples of U apart from cnt)
+                const uint32_t ix = (uint32_t)__shfl((int)ux, src, 32), iy = (uint32_t)__shfl((int)uy, src, 32);
+                const uint32_t cs = (uint32_t)__shfl((int)uc, src, 32);
+                swg_refine_entries<PL>(tl + (size_t)ix * S2, cs & 0xFFFFu, tx[u]);
+                swg_refine_entries<PL>(tl + (size_t)iy * S2, cs >> 16, ty[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                swg_refine_step<PL>(hx, tx[u], m0);
+                swg_refine_step<PL>(hy, ty[u], m0);
+            }
+        }
+    }
+    const uint32_t refined = group_max();
+    if (l == 0u && refined < first) bound[p] = refined;
+}
+
+hipError_t swg_launch_pair_bound_refine(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, uint32_t S2, const SwgColMax &cm,
+                                        const uint16_t *d_table, const uint32_t *d_thr, uint32_t *d_bound, hipStream_t stream)
+{
+    if (end < begin || (S2 != 64u && S2 != 128u)) return hipErrorInvalidValue;
+    if (end == begin) return hipSuccess;
+    const uint32_t wgs = (end - begin + 7u) / 8u;
+    if (S2 == 128u)
+        hipLaunchKernelGGL((swg_pair_bound_refine_kernel<4, 4>), dim3(wgs), dim3(256), 0, stream, d_tok, d_pair_off, begin, end, cm, d_table, d_thr, d_bound);
+    else
+        hipLaunchKernelGGL((swg_pair_bound_refine_kernel<4, 2>), dim3(wgs), dim3(256), 0, stream, d_tok, d_pair_off, begin, end, cm, d_table, d_thr, d_bound);
+    return hipGetLastError();
+}
+
+// The list of a stage, pair by pair: the ids of the pairs of [begin, end) with bound >= T, ascending -- the token order,
+// longest first, which the work queue hands out front to back.  Three launches: the kept pairs of every tile of
+// SWG_PRUNE_TILE consecutive pairs (and, added to the search's tally as swg_prune_tally_kernel adds them, what the tile
+// skips: out[1] pairs, out[2..3] their token blocks); the tiles' offsets and out[0] = the list's length; the scatter.
+__device__ __forceinline__ uint32_t swg_prune_tile_keep(const uint32_t *bound, uint32_t begin, uint32_t end, uint32_t T, uint64_t &first)
+{
+    first = (uint64_t)begin + (uint64_t)blockIdx.x * SWG_PRUNE_TILE + threadIdx.x * 4u;
+    uint32_t keep = 0u;
+#pragma unroll
+    for (uint32_t i = 0u; i < 4u; ++i)
+        if (first + i < end && bound[first + i] >= T) keep |= 1u << i;
+    return keep;
+}
+
+__global__ __launch_bounds__(256) void swg_prune_list_count_kernel(const uint32_t *bound, const uint32_t *pair_off, uint32_t begin, uint32_t end,
+                                                                   const uint32_t *thr, uint32_t *tiles, uint32_t *out)
+{
+    __shared__ uint32_t s_keep[4], s_skip[4];
+    __shared__ unsigned long long s_blocks[4];
+    uint64_t first;
+    const uint32_t keep = swg_prune_tile_keep(bound, begin, end, thr[0], first);
+    uint32_t n_keep = (uint32_t)__popc(keep), n_skip = 0u;
+    unsigned long long blocks = 0ull;
+#pragma unroll
+    for (uint32_t i = 0u; i < 4u; ++i)
+        if (first + i < end && !((keep >> i) & 1u)) ++n_skip, blocks += pair_off[first + i + 1u] - pair_off[first + i];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        n_keep += (uint32_t)__shfl_xor((int)n_keep, d, 64);
+        n_skip += (uint32_t)__shfl_xor((int)n_skip, d, 64);
+        blocks += (unsigned long long)__shfl_xor((long long)blocks, d, 64);
+    }
+    if ((threadIdx.x & 63u) == 0u) s_keep[threadIdx.x >> 6] = n_keep, s_skip[threadIdx.x >> 6] = n_skip, s_blocks[threadIdx.x >> 6] = blocks;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        tiles[blockIdx.x] = s_keep[0] + s_keep[1] + s_keep[2] + s_keep[3];
+        const uint32_t skipped = s_skip[0] + s_skip[1] + s_skip[2] + s_skip[3];
+        if (skipped) {
+            atomicAdd(out + 1, skipped);
+            atomicAdd(reinterpret_cast<unsigned long long *>(out + 2), s_blocks[0] + s_blocks[1] + s_blocks[2] + s_blocks[3]);
+        }
+    }
+}
+
+// tiles[i] -> the kept pairs in front of tile i; out[0] = all of them (rec, where given: {T, that count}).  One
+// workgroup, 1024 tiles a round.
+__global__ __launch_bounds__(1024) void swg_prune_list_scan_kernel(uint32_t *tiles, uint32_t n_tiles, const uint32_t *thr, uint32_t *out, uint32_t *rec)
+{
+    __shared__ uint32_t s_wave[16];
+    __shared__ uint32_t s_carry;
+    if (threadIdx.x == 0u) s_carry = 0u;
+    __syncthreads();
+    for (uint32_t i0 = 0u; i0 < n_tiles; i0 += 1024u) {
+        const uint32_t i = i0 + threadIdx.x, v = i < n_tiles ? tiles[i] : 0u;
+        uint32_t incl = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
+            if ((threadIdx.x & 63u) >= (uint32_t)d) incl += o;
+        }
+        if ((threadIdx.x & 63u) == 63u) s_wave[threadIdx.x >> 6] = incl;
+        __syncthreads();
+        uint32_t before = s_carry;
+        for (uint32_t w = 0u; w < (threadIdx.x >> 6); ++w) before += s_wave[w];
+        if (i < n_tiles) tiles[i] = before + incl - v;
+        __syncthreads();
+        if (threadIdx.x == 1023u) s_carry = before + incl;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0u) {
+        out[0] = s_carry;
+        if (rec) rec[0] = thr[0], rec[1] = s_carry; // (what the stage was cut at and kept: tests read it back)
+    }
+}
+
+__global__ __launch_bounds__(256) void swg_prune_list_scatter_kernel(const uint32_t *bound, uint32_t begin, uint32_t end, const uint32_t *thr,
+                                                                     const uint32_t *tiles, uint32_t *list)
+{
+    __shared__ uint32_t s_wave[4];
+    uint64_t first;
+    const uint32_t keep = swg_prune_tile_keep(bound, begin, end, thr[0], first);
+    const uint32_t n = (uint32_t)__popc(keep);
+    uint32_t incl = n;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
+        if ((threadIdx.x & 63u) >= (uint32_t)d) incl += o;
+    }
+    if ((threadIdx.x & 63u) == 63u) s_wave[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    uint32_t at = tiles[blockIdx.x] + incl - n;
+    for (uint32_t w = 0u; w < (threadIdx.x >> 6); ++w) at += s_wave[w];
+#pragma unroll
+    for (uint32_t i = 0u; i < 4u; ++i)
+        if ((keep >> i) & 1u) list[at++] = (uint32_t)first + i; // (at < the kept pairs of the stage <= end - begin)
+}
+
+hipError_t swg_launch_prune_list(const uint32_t *d_bound, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, const uint32_t *d_thr,
+                                 uint32_t *d_tiles, uint32_t *d_list, uint32_t *d_out, uint32_t *d_rec, hipStream_t stream)
+{
+    if (end < begin) return hipErrorInvalidValue;
+    const uint32_t n_tiles = (end - begin + SWG_PRUNE_TILE - 1u) / SWG_PRUNE_TILE;
+    if (n_tiles) hipLaunchKernelGGL(swg_prune_list_count_kernel, dim3(n_tiles), dim3(256), 0, stream, d_bound, d_pair_off, begin, end, d_thr, d_tiles, d_out);
+    hipLaunchKernelGGL(swg_prune_list_scan_kernel, dim3(1), dim3(1024), 0, stream, d_tiles, n_tiles, d_thr, d_out, d_rec);
+    if (n_tiles) hipLaunchKernelGGL(swg_prune_list_scatter_kernel, dim3(n_tiles), dim3(256), 0, stream, d_bound, begin, end, d_thr, d_tiles, d_list);
     return hipGetLastError();
 }
 

@@ -1,0 +1,68 @@
+"""The headline under every cut of a pruned search's stages (profiles/prune_refine_ab.txt, section 2).
+
+    python tools/sweeps/prune_refine_ab.py [--nseq N] [--reps R]
+
+Config 4's whole database (10M sequences, one shard), its 3000-column query and scoring through the Python wrapper,
+autotune off, ctx.search(db, want_scores=False, k=100), one search in flight.  For (prune_cut, prune_refine) = (1, off),
+(0, off), (0, 64), (0, 128) and automatic: R searches with the tables resident, then two searches each behind a
+set_query of the same query, which starts a new epoch -- the search pays both tables again.  One JSON line per search."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+import swg_loader  # noqa: E402
+
+swg = swg_loader.load()
+
+CANDIDATES = [("prefix", 1, 1), ("pairs", 0, 1), ("pairs+64", 0, 64), ("pairs+128", 0, 128), ("auto", 0, 0)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nseq", type=int, default=10000000)
+    ap.add_argument("--lq", type=int, default=3000)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--unpruned", action="store_true", help="one unpruned search first (hits to compare with, 1.2 s)")
+    a = ap.parse_args()
+    seed = 0x5EED0004
+    q = swg.synth_query(seed, a.lq)
+    sh = swg.synth_db_shard(seed, a.nseq, 0, 1, query=None, fraction=0.0, subst=0.05)
+    ctx = swg.Context(0)
+    ctx.set_scoring(swg.load_scoring("BLOSUM62"), -2, -1)
+    ctx.set_query(q)
+    ctx.set_option("autotune", 0)
+    db = swg.Database(sh["flat"], sh["offsets"], index=sh["index"], n_total=a.nseq).upload(ctx)
+    want = None
+    if a.unpruned:
+        ctx.set_option("prune", 0)
+        _, want, st = ctx.search(db, want_scores=False, k=100)
+        print(json.dumps({"unpruned": True, "fill_ms": st["fill_ms"], "total_ms": st["total_ms"]}), flush=True)
+        ctx.set_option("prune", 1)
+    for name, cut, refine in CANDIDATES:
+        ctx.set_option("prune_cut", cut)
+        ctx.set_option("prune_refine", refine)
+        for rep in range(a.reps + 2):
+            fresh = rep >= a.reps
+            if fresh:
+                ctx.set_query(q)
+            t0 = time.perf_counter()
+            _, hits, st = ctx.search(db, want_scores=False, k=100)
+            wall = (time.perf_counter() - t0) * 1e3
+            info = ctx.prune_last()
+            got = ctx.debug_prune_refine_read(db)
+            if want is None:
+                want = hits
+            print(json.dumps({"candidate": name, "prune_cut": cut, "prune_refine": refine, "fresh_query": fresh, "rep": rep,
+                              "k_used": got["k"], "S_used": got["segments"], "S2_used": got["refine"], "builds": got["builds"],
+                              "refine_builds": got["refine_builds"], "wall_ms": round(wall, 2), "fill_ms": st["fill_ms"],
+                              "total_ms": st["total_ms"], "info": info,
+                              "rows_kept_frac": 1.0 - info["pair_rows_skipped"] / max(1, info["pair_rows"]),
+                              "hits_equal_first": hits == want}), flush=True)
+    db.close()
+
+
+if __name__ == "__main__":
+    main()
