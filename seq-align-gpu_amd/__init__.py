@@ -216,6 +216,9 @@ _sig("swg_debug_plan", C.c_int, [_vp, C.c_size_t, C.c_int, _vp])
 _sig("swg_debug_plan_f16", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_long, _vp])
 _sig("swg_debug_plan_gapless", C.c_int, [_vp, C.c_size_t, C.c_int, _vp])
 _sig("swg_debug_plan_forced", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int, C.c_long, C.c_int, _vp])
+_sig("swg_debug_plan_streams", C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long, _vp])
+_sig("swg_debug_plan_systolic", C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, _vp])
+_sig("swg_debug_systolic_variants", C.c_int, [C.c_int, _vp, C.c_size_t])
 _sig("swg_debug_plan_batch", C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, _vp])
 _sig("swg_debug_plan_lists", C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, _vp])
 _sig("swg_debug_launch_log", None, [C.c_int])
@@ -589,6 +592,15 @@ def debug_prune_plan(**ask):
 LAUNCH_FAMILIES = ("dyn", "lists", "q32", "qq", "streams", "systolic")
 
 
+def debug_systolic_variants(bits):
+    """Test hook: [(K, max_waves)] of the systolic fill's instantiations for 16- or 32-bit cells, in the library's order
+    (the first is the default)."""
+    out = np.zeros((16, 2), dtype=np.int32)
+    n = lib.swg_debug_systolic_variants(bits, out.ctypes.data_as(_vp), 16)
+    assert 0 < n <= 16
+    return [(int(k), int(w)) for k, w in out[:n]]
+
+
 def debug_launch_log(on):
     """Test hook: clears the launch log and switches it on or off (off by default)."""
     lib.swg_debug_launch_log(1 if on else 0)
@@ -717,6 +729,33 @@ class Database:
                 "last_pass_cols", "fma", "lds_bytes", "long_fma")
         d = dict(zip(keys, (int(v) for v in out)))
         d["planned"] = d["classes"] > 0
+        return d
+
+    def debug_plan_streams(self, sub, query, cols=0, group=0, waves=0, workgroups=0, n_cu=256):
+        """Test hook: what a search of `query` under the 32 x 32 table `sub` plans with options engine = 2, work_queue = 0,
+        f16 = 0, long_split = -1, cols_per_wave, group_lanes, max_waves and workgroups (no device needed) -> dict(planned,
+        classes, K, G, W, passes, workgroups, streams, wide: the wide form of the int16 cells)."""
+        t, tp = _i8(np.asarray(sub, dtype=np.int8).reshape(32, 32))
+        q, qp = _i8(query)
+        out = np.zeros(8, dtype=np.int32)
+        _check(lib.swg_debug_plan_streams(self.handle, tp, qp, q.size, n_cu, cols, group, waves, workgroups, out.ctypes.data_as(_vp)))
+        d = dict(zip(("classes", "K", "G", "W", "passes", "workgroups", "streams", "wide"), (int(v) for v in out)))
+        d["planned"] = d["classes"] > 0
+        return d
+
+    def debug_plan_systolic(self, sub, query, gap_open, gap_extend, force_bits=0, cols=0, max_waves=0, workgroups=0, f16=1, n_cu=256):
+        """Test hook: what a search of `query` under `sub` and the gap scores plans with option engine = 1 and force_bits,
+        cols_per_wave, max_waves, workgroups, f16 (no device needed) -> dict(planned, K, W, passes, workgroups, f16: the
+        packed-f16 cells, variant_max_waves, bits, rescore: an int32 re-score follows, and its rescore_K / _W / _passes)."""
+        t, tp = _i8(np.asarray(sub, dtype=np.int8).reshape(32, 32))
+        q, qp = _i8(query)
+        out = np.zeros(12, dtype=np.int32)
+        _check(lib.swg_debug_plan_systolic(self.handle, tp, qp, q.size, gap_open, gap_extend, n_cu, force_bits, cols, max_waves, workgroups,
+                                           f16, out.ctypes.data_as(_vp)))
+        keys = ("planned", "K", "W", "passes", "workgroups", "f16", "variant_max_waves", "bits", "rescore", "rescore_K", "rescore_W",
+                "rescore_passes")
+        d = dict(zip(keys, (int(v) for v in out)))
+        d["planned"] = bool(d["planned"])
         return d
 
     _BATCH_PLAN_KEYS = ("batch", "K", "G", "W", "per_cu", "qq", "lds_bytes", "classes")

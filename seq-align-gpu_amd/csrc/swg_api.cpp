@@ -676,8 +676,10 @@ static int ensure_bins(swg_ctx *ctx, swg_db *db)
 // ---------------------------------------------------------------------------
 // planning
 // ---------------------------------------------------------------------------
-// cols > 0: the instantiation with that many columns per wavefront (option cols_per_wave, or a measured / modelled choice)
-static int make_plan(swg_ctx *ctx, int bits, uint32_t n_items, long cols, SwgSystolicPlan *pl)
+// The systolic plan from plain values (make_plan for a search, swg_debug_plan_systolic for the tests): cols > 0 asks for the
+// instantiation with that many columns per wavefront, max_waves > 0 caps the wavefronts of a workgroup (more passes),
+// workgroups > 0 fixes the grid.  false: no instantiation of `cols` columns is built for these cells.
+static bool systolic_plan(int bits, uint32_t n_items, long cols, long max_waves, long workgroups, size_t lq, int n_cu, SwgSystolicPlan *pl)
 {
     const int nv = swg_num_variants(bits);
     int variant = 0;
@@ -685,22 +687,19 @@ static int make_plan(swg_ctx *ctx, int bits, uint32_t n_items, long cols, SwgSys
         variant = -1;
         for (int v = 0; v < nv; ++v)
             if (swg_variant_info(bits, v).K == (int)cols) variant = v;
-        if (variant < 0)
-            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "cols_per_wave=%ld not built for the %d-bit path",
-                                     cols, bits);
+        if (variant < 0) return false;
     }
     const SwgKernelInfo info = swg_variant_info(bits, variant);
     int maxw = info.max_waves;
-    if (ctx->opt_max_waves > 0) maxw = std::min<int>(maxw, (int)ctx->opt_max_waves);
-    const size_t lq = ctx->query_len();
+    if (max_waves > 0) maxw = std::min<int>(maxw, (int)max_waves);
     const size_t cols_per_pass_max = (size_t)maxw * info.K;
     const int npass = (int)((lq + cols_per_pass_max - 1) / cols_per_pass_max);
     const int W = (int)((lq + (size_t)npass * info.K - 1) / ((size_t)npass * info.K));
     // residency: info.max_waves is also the wave budget of one CU for this
     // instantiation's register allocation; LDS is the other limit
     const size_t lds = info.lds_per_wave * (size_t)W + info.lds_fixed;
-    long wgs = (long)ctx->n_cu * swg_workgroups_per_cu(info.max_waves, W, lds);
-    if (ctx->opt_workgroups > 0) wgs = ctx->opt_workgroups;
+    long wgs = (long)n_cu * swg_workgroups_per_cu(info.max_waves, W, lds);
+    if (workgroups > 0) wgs = workgroups;
     wgs = std::max<long>(1, std::min<long>(wgs, (long)n_items));
     pl->bits = bits;
     pl->variant = variant;
@@ -709,6 +708,15 @@ static int make_plan(swg_ctx *ctx, int bits, uint32_t n_items, long cols, SwgSys
     pl->npass = npass;
     pl->workgroups = (int)wgs;
     pl->info = info;
+    return true;
+}
+
+// cols > 0: the instantiation with that many columns per wavefront (option cols_per_wave, or a measured / modelled choice)
+static int make_plan(swg_ctx *ctx, int bits, uint32_t n_items, long cols, SwgSystolicPlan *pl)
+{
+    if (!systolic_plan(bits, n_items, cols, ctx->opt_max_waves, ctx->opt_workgroups, ctx->query_len(), ctx->n_cu, pl))
+        return swg_set_ctx_error(ctx, SWG_ERR_ARG, "cols_per_wave=%ld not built for the %d-bit path",
+                                 cols, bits);
     return SWG_OK;
 }
 
@@ -1971,6 +1979,25 @@ static bool q32_forced_plan(const swg_db *db, size_t lq, long cols, long group, 
     return false;
 }
 
+// Three of plan_search's rules, spelled once for the search and for the test hooks behind it (swg_debug_plan_streams,
+// swg_debug_plan_systolic).  The wide form first: int16 arithmetic, a score that can pass 32767, lane groups.
+static bool wide_form_first(int bits, uint64_t score_bound, long engine, bool wide_ok)
+{
+    return bits == 16 && score_bound >= SWG_I16_CEILING && engine != 1 && wide_ok;
+}
+// The systolic engine on packed-f16 cells: one pass, gap magnitudes f16 holds, and no score that can reach their ceiling.
+static bool systolic_takes_f16(int bits, bool use_diag, int npass, bool f16_gaps, uint64_t score_bound)
+{
+    return bits == 16 && !use_diag && npass == 1 && f16_gaps && score_bound < SWG_F16_CEILING;
+}
+// Option workgroups on lane groups: at most that many, and the streams that go with them.
+static void cap_workgroups(SwgDiagPlan *d0, long workgroups)
+{
+    const uint64_t per_wg = (uint64_t)d0->W * (64 / d0->G);
+    d0->workgroups = (int)std::min<long>(workgroups, d0->workgroups);
+    d0->n_streams = (uint32_t)((uint64_t)d0->workgroups * per_wg);
+}
+
 // Every decision of one search: arithmetic, cell forms and their hand-overs, engines and geometries.  It allocates no
 // profile, scratch or bin image and puts no launch on the search's own timeline; the only device work it may do is what
 // the decisions themselves read: the pair tokens of the database (ensure_pair_tokens, built once per database) and the
@@ -2016,7 +2043,7 @@ static int plan_search(swg_ctx *ctx, swg_db *db, bool allow_autotune, SwgSearchP
 
     const bool f16_gaps = ctx->opt_f16 != 0 && swg_f16_gaps_ok(go, ge); // the f16 cells are allowed and hold the gap magnitudes
     const bool wide_ok = ctx->opt_wide != 0 && (!gapless || gl_small);
-    P.wide = bits == 16 && score_bound >= SWG_I16_CEILING && ctx->opt_engine != 1 && wide_ok;
+    P.wide = wide_form_first(bits, score_bound, ctx->opt_engine, wide_ok);
     // Gapless, route 1: the gapless cells (CellsGapless, form 3) where the query fits one pass of a geometry the table
     // offers (a forced cols_per_wave / group_lanes included), on the work queue, unless the options rule the f16 cells or
     // the lane groups out or the database came from 16-lane batches.  Everything else is route 0: the machinery below
@@ -2086,12 +2113,7 @@ static int plan_search(swg_ctx *ctx, swg_db *db, bool allow_autotune, SwgSearchP
         }
         if (!P.use_diag && !tuned_systolic && ctx->opt_engine == 2)
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "no diagonal-engine geometry for these options");
-        if (P.use_diag && ctx->opt_workgroups > 0) {
-            SwgDiagPlan &d0 = wk.plan[0];
-            const uint64_t per_wg = (uint64_t)d0.W * (64 / d0.G);
-            d0.workgroups = (int)std::min<long>(ctx->opt_workgroups, d0.workgroups);
-            d0.n_streams = (uint32_t)((uint64_t)d0.workgroups * per_wg);
-        }
+        if (P.use_diag && ctx->opt_workgroups > 0) cap_workgroups(&wk.plan[0], ctx->opt_workgroups);
         if (!P.use_diag && !tuned_systolic && rc != SWG_OK) return rc;
         // the wide form exists in the diagonal engine only
         if (P.wide && P.use_diag)
@@ -2102,7 +2124,7 @@ static int plan_search(swg_ctx *ctx, swg_db *db, bool allow_autotune, SwgSearchP
     // The systolic engine on packed-f16 cells (round 4: 8.5 instead of 10 instructions per column pair) where NO score of
     // this search can reach their ceiling -- the engine has no flag-and-re-run route, and the databases the cost model
     // gives it are the ones whose longest sequence is short (372 residues x BLOSUM62's 11 < 4096).
-    if (bits == 16 && !P.use_diag && P.main_pl.npass == 1 && f16_gaps && score_bound < SWG_F16_CEILING) P.main_pl.f16 = 1;
+    if (systolic_takes_f16(bits, P.use_diag, P.main_pl.npass, f16_gaps, score_bound)) P.main_pl.f16 = 1;
     // int32 work (forced / unusual gap scores / re-score of saturated sequences) also runs on
     // the diagonal engine unless the systolic one is asked for
     P.use_diag32 = ctx->opt_engine != 1;
@@ -2201,6 +2223,63 @@ static int plan_search(swg_ctx *ctx, swg_db *db, bool allow_autotune, SwgSearchP
     }
     P.bin32 = P.use_diag32 && ((bits == 32 && !P.use_q32) || (P.int32_level && !P.q32_ok)); // the bin-based int32 kernel is needed
     return SWG_OK;
+}
+
+// Test hooks (swg_host_internal.h): what plan_search decides for the two engines the work queue does not serve, without a
+// device, from the rules above and the planners the search itself calls.
+// swg_debug_plan_streams: the fixed-stream fill of options engine = 2, work_queue = 0, f16 = 0, long_split = -1 with
+// cols_per_wave, group_lanes, max_waves and workgroups (0 = free) for a query idx[0 .. lq) under the table `rows`.
+extern "C" int swg_debug_plan_streams(const swg_db *db, const int8_t *rows, const int8_t *idx, size_t lq, int n_cu, long cols, long group,
+                                      long waves, long workgroups, int32_t *out)
+{
+    if (!db || !rows || !idx || !out || lq == 0 || n_cu <= 0 || cols < 0 || group < 0 || waves < 0 || workgroups < 0) return SWG_ERR_ARG;
+    memset(out, 0, 8 * sizeof(int32_t));
+    try {
+        const SwgScoreBound sb = swg_score_bound(rows, idx, lq, (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK);
+        SwgDiagWork wk;
+        if (swg_plan_diag_work(db, lq, n_cu, cols, group, waves, -1, workgroups == 0, false, &wk, 1.0, 0, 0) <= 0) return SWG_OK;
+        if (workgroups > 0) cap_workgroups(&wk.plan[0], workgroups);
+        const SwgDiagPlan &b = wk.plan[0];
+        const int32_t v[8] = {wk.n_classes, b.K, b.G, b.W, b.npass, b.workgroups, (int32_t)b.n_streams, wide_form_first(16, sb.bound, 2, true) ? 1 : 0};
+        memcpy(out, v, sizeof v);
+    } catch (const std::exception &) {
+        return SWG_ERR_NOMEM;
+    }
+    return SWG_OK;
+}
+// swg_debug_plan_systolic: the systolic fill of option engine = 1 with force_bits (0 or 32), cols_per_wave, max_waves,
+// workgroups and f16 (0 = never the f16 cells) under the gap scores given, and the int32 re-score behind it.
+extern "C" int swg_debug_plan_systolic(const swg_db *db, const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int n_cu,
+                                       long force_bits, long cols, long max_waves, long workgroups, long f16, int32_t *out)
+{
+    if (!db || !rows || !idx || !out || lq == 0 || n_cu <= 0 || cols < 0 || max_waves < 0 || workgroups < 0 || (force_bits != 0 && force_bits != 32))
+        return SWG_ERR_ARG;
+    memset(out, 0, 12 * sizeof(int32_t));
+    const SwgScoreBound sb = swg_score_bound(rows, idx, lq, (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK);
+    const int go = gap_open + gap_extend, ge = gap_extend;
+    const bool fast_ok = gap_open <= 0 && gap_extend <= 0 && -go <= SWG_I16_CEILING;
+    const int bits = fast_ok && force_bits != 32 ? 16 : 32;
+    SwgSystolicPlan pl, re;
+    if (!systolic_plan(bits, bits == 16 ? db->n_bins : db->n_bins * 2, cols, max_waves, workgroups, lq, n_cu, &pl)) return SWG_OK;
+    const bool takes_f16 = systolic_takes_f16(bits, false, pl.npass, f16 != 0 && swg_f16_gaps_ok(go, ge), sb.bound);
+    const bool rescore = bits == 16 && sb.bound >= (uint64_t)SWG_I16_CEILING;
+    const size_t n_slots = (size_t)db->n_bins * SWG_BIN;
+    if (rescore && !systolic_plan(32, (uint32_t)std::min<size_t>(n_slots / 64, 1u << 30), 0, max_waves, workgroups, lq, n_cu, &re)) return SWG_OK;
+    const int32_t v[12] = {1, pl.K, pl.W, pl.npass, pl.workgroups, takes_f16 ? 1 : 0, pl.info.max_waves, bits, rescore ? 1 : 0, re.K, re.W, re.npass};
+    memcpy(out, v, sizeof v);
+    return SWG_OK;
+}
+// swg_debug_systolic_variants: the systolic instantiations of the 16- or 32-bit cells as (K, max_waves), up to cap pairs;
+// returns how many there are.
+extern "C" int swg_debug_systolic_variants(int bits, int32_t *out, size_t cap)
+{
+    if (bits != 16 && bits != 32) return 0;
+    const int n = swg_num_variants(bits);
+    for (int v = 0; out && v < n && (size_t)v < cap; ++v) {
+        const SwgKernelInfo info = swg_variant_info(bits, v);
+        out[2 * v] = info.K, out[2 * v + 1] = info.max_waves;
+    }
+    return n;
 }
 
 // Profiles, scratch and the bin image of a planned search.

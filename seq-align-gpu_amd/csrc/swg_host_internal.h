@@ -567,6 +567,19 @@ extern "C" int swg_debug_plan_f16(const swg_db *db, size_t lq, int n_cu, long f1
 // per lane, is 0 with last_pass = 0 (option last_pass).
 extern "C" int swg_debug_plan_forced(const swg_db *db, size_t lq, int n_cu, long cols, long group, long waves, int form,
                                      long f16_pair, int last_pass, int32_t *out);
+// test hooks (swg_api.cpp): plan_search's answers for the two engines the work queue does not serve, without a device, for
+// a query idx[0 .. lq) under the 32 x 32 table `rows`.  "No plan" is SWG_OK with out[0] = 0.
+// swg_debug_plan_streams: options engine = 2, work_queue = 0, f16 = 0, long_split = -1, cols_per_wave, group_lanes,
+// max_waves, workgroups (0 = free): out[0..7] = classes, K, G, W, passes, workgroups, streams, wide form.
+// swg_debug_plan_systolic: option engine = 1 with force_bits (0 / 32), cols_per_wave, max_waves, workgroups, f16:
+// out[0..11] = planned, K, W, passes, workgroups, f16 cells, the instantiation's most wavefronts, bits, an int32 re-score
+// follows (a score can reach 32767), and that re-score's K, W, passes.
+// swg_debug_systolic_variants: (K, max_waves) of every systolic instantiation of `bits`; returns their number.
+extern "C" int swg_debug_plan_streams(const swg_db *db, const int8_t *rows, const int8_t *idx, size_t lq, int n_cu, long cols, long group,
+                                      long waves, long workgroups, int32_t *out);
+extern "C" int swg_debug_plan_systolic(const swg_db *db, const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int n_cu,
+                                       long force_bits, long cols, long max_waves, long workgroups, long f16, int32_t *out);
+extern "C" int swg_debug_systolic_variants(int bits, int32_t *out, size_t cap);
 // test hooks: what a batch launches on cells of `form` (0 packed int16, 2 packed f16; the hooks have no scoring system, so
 // the caller says which cells the score bounds allow), without a device: the geometry rules of plan_batch and plan_lists
 // (swg_api.cpp, which share them with these hooks) for options cols_per_wave = cols, group_lanes = group (0 = free),

@@ -239,8 +239,10 @@ def test_geometry_does_not_change_scores(swg, ctx, cols, maxw):
         assert np.array_equal(scores, g["oracle32"]), (name, cols, maxw, st)
         assert st["cols_per_wave"] == cols
         if maxw:
-            assert st["waves"] <= maxw and st["passes"] == -(-len(g["query"]) // (cols * st["waves"])) \
-                or st["passes"] >= 1
+            # make_plan: the fewest passes of at most maxw strips, then the fewest strips that cover the query in that many
+            lq = len(g["query"])
+            assert st["passes"] == -(-lq // (cols * maxw)), (name, cols, maxw, st)
+            assert st["waves"] == -(-lq // (st["passes"] * cols)), (name, cols, maxw, st)
         db.close()
 
 
