@@ -363,6 +363,32 @@ int swg_search_gapless_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queri
 int swg_search_gapless_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets, size_t n_queries,
                                   int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits, swg_stats *stats);
 
+/* Every hit at or above a score: the question a pipeline asks once an E-value cut-off has been turned into a raw score
+ * (the library does not do that: INTEGRATION.md).  For the context's query (index or PSSM) against a resident database,
+ * view or shard, exactly as swg_search takes them:
+ *   *n_total   the sequences of this shard or view whose exact int32 score is >= min_score;
+ *   hits_out   the best min(cap, *n_total) of them in the library's total order (higher score first, ties by lower
+ *              original index); *n_hits says how many were written.  With *n_total > cap the call still succeeds: the
+ *              caller sees it and can call again with more room.  cap = 0 with hits_out NULL is a pure count.
+ * Scores are exact for every input (the f16 -> int16 / wide -> int32 re-runs happen as in swg_search).  Shards: each
+ * rank's call gives its shard's hits, and the union sorted by swg_hit_key is the whole database's answer.
+ * min_score < 1 is SWG_ERR_ARG (every sequence scores at least 0); cap > 0 with hits_out NULL is SWG_ERR_ARG; the other
+ * errors are swg_search's, and searches in flight on the context give SWG_ERR_STATE (there is no begin / end form).
+ * Pruning (option "prune"; the rest of the prune_* options choose the bound as above, "prune_cut" is not read): the
+ * threshold of a pruned search is min_score from its first launch on, so every stage -- the first included, and the
+ * only one of a range of one segment -- fills exactly the pairs whose score bound reaches it; a pair left out scores
+ * below min_score.  0 never | 2 wherever it is structurally possible (non-positive gap scores, the 16-bit lane-group work
+ * queue, one class, one cell form) | 1 (default) those of them whose range has at least 16 pairs per resident lane group
+ * ("A caller's threshold").  Everything else -- positive gap scores, the int32 path, the systolic
+ * engine, two classes, both cell forms -- runs its usual fill; only the read-out differs.  swg_prune_last reports this
+ * search too: threshold = min_score, and pairs_skipped is exactly the number of pairs of the fill whose final bound is
+ * below it.  stats as swg_search (topk_ms: the read-out's kernel and the host's sort). */
+int swg_search_above(swg_ctx *ctx, const swg_db *db, int32_t min_score, swg_hit *hits_out, size_t cap, size_t *n_hits,
+                     uint64_t *n_total, swg_stats *stats);
+/* The same question of the gapless prefilter score (swg_search_gapless): never pruned, errors and outputs as above. */
+int swg_search_gapless_above(swg_ctx *ctx, const swg_db *db, int32_t min_score, swg_hit *hits_out, size_t cap, size_t *n_hits,
+                             uint64_t *n_total, swg_stats *stats);
+
 /* Every query of a batch against ITS OWN candidate list in one pass: what a prefilter, a PSI-BLAST iteration or a list
  * of family members per query hands to the alignment step.  Query i is queries[q_offsets[i] .. q_offsets[i+1]) as
  * swg_search_multi takes it; its candidates are cand[c_offsets[i] .. c_offsets[i+1]): ORIGINAL database indices, in any

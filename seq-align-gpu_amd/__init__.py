@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "swg_db_free", "swg_db_save", "swg_db_load", "swg_db_count", "swg_db_total_count", "swg_db_residues",
     "swg_db_packed_bytes", "swg_db_order", "swg_search", "swg_search_begin", "swg_search_end", "swg_search_multi",
     "swg_search_multi_pssm", "swg_search_lists", "swg_search_lists_pssm", "swg_search_gapless", "swg_search_gapless_multi",
-    "swg_search_gapless_multi_pssm", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_align_hits_multi",
+    "swg_search_gapless_multi_pssm", "swg_search_above", "swg_search_gapless_above", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_align_hits_multi",
     "swg_align_hits_multi_pssm", "swg_align_ops_bound_multi", "swg_align_bounds", "swg_align_bounds_multi",
     "swg_align_bounds_multi_pssm", "swg_align_stats", "swg_align_stats_multi", "swg_align_stats_multi_pssm", "swg_hit_key",
     "swg_key_hit", "swg_topk_merge_keys",
@@ -149,6 +149,8 @@ _sig("swg_search_end", C.c_int, [_vp, C.c_int, _vp, _vp, C.POINTER(C.c_size_t), 
 _sig("swg_search_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
 _sig("swg_search_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
 _sig("swg_search_gapless", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(Stats)])
+for _name in ("swg_search_above", "swg_search_gapless_above"):
+    _sig(_name, C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(Stats)])
 _sig("swg_search_gapless_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
 _sig("swg_search_gapless_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
 _sig("swg_search_lists", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
@@ -231,6 +233,7 @@ _sig("swg_debug_list_jobs", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t
 _sig("swg_prune_last", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_bound", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp])
 _sig("swg_debug_prune_plan", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_plan_above", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_kmer", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp])
 _sig("swg_debug_prune_kmer_choice", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_kmer_read", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp])
@@ -589,6 +592,27 @@ def debug_prune_plan(**ask):
     return bool(out[0]), int(out[1])
 
 
+PRUNE_PLAN_ABOVE_KEYS = ("mode", "gap_open", "gap_extend", "bits", "use_diag", "n_classes", "work_queue", "both_forms", "gapless", "batch",
+                         "range_pairs", "groups", "n_segments", "prune_head")
+
+
+def debug_prune_plan_above(**ask):
+    """Test hook (no device needed): what a search_above decides about pruning (swg_prune_plan under a caller's
+    threshold).  Keyword arguments as PRUNE_PLAN_ABOVE_KEYS; the defaults describe one that is pruned: mode 1, gaps (-2, -1),
+    16-bit lane groups off the work queue, one class, one form, 1 000 000 pairs in 8 segments on 1024 lane groups.
+    -> (pruned, head pairs: always 0)."""
+    d = dict(mode=1, gap_open=-2, gap_extend=-1, bits=16, use_diag=1, n_classes=1, work_queue=1, both_forms=0, gapless=0, batch=0,
+             range_pairs=1000000, groups=1024, n_segments=8, prune_head=4)
+    unknown = set(ask) - set(d)
+    if unknown:
+        raise TypeError("debug_prune_plan_above: unknown arguments %s" % sorted(unknown))
+    d.update(ask)
+    a = np.array([int(d[k]) for k in PRUNE_PLAN_ABOVE_KEYS], dtype=np.int64)
+    out = np.zeros(2, dtype=np.int64)
+    _check(lib.swg_debug_prune_plan_above(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
+    return bool(out[0]), int(out[1])
+
+
 LAUNCH_FAMILIES = ("dyn", "lists", "q32", "qq", "streams", "systolic")
 
 
@@ -926,6 +950,21 @@ class Context:
         """The gapless prefilter score (best ungapped diagonal segment) of the context's query against db, shaped like
         search; the gap scores of set_scoring are not read (swg_search_gapless)."""
         return self.search(db, want_scores, k, _fn=lib.swg_search_gapless)
+
+    def search_above(self, db, min_score, cap=None, gapless=False):
+        """Every sequence of db that scores at least min_score (>= 1) against the context's query: -> (hits [(score,
+        index)] -- the best min(cap, n_total) in the library's order --, n_total, stats dict).  cap None: room for every
+        sequence of db; cap 0: a pure count.  gapless: the gapless prefilter score (swg_search_above,
+        swg_search_gapless_above)."""
+        cap = db.count if cap is None else int(cap)
+        hits = (Hit * max(cap, 1))()
+        nh, nt = C.c_size_t(0), C.c_uint64(0)
+        st = Stats()
+        fn = lib.swg_search_gapless_above if gapless else lib.swg_search_above
+        rc = fn(self.handle, db.handle, int(min_score), C.cast(hits, _vp) if cap else None, cap, C.byref(nh), C.byref(nt), C.byref(st))
+        _check(rc, self.handle)
+        a = np.frombuffer(hits, dtype=np.dtype([("score", np.int32), ("index", np.uint32)]), count=nh.value)
+        return list(zip(a["score"].tolist(), a["index"].tolist())), int(nt.value), st.as_dict()
 
     def search_gapless_multi(self, db, queries, k=0, want_scores=True):
         """search_gapless for a list of index queries, shaped like search_multi; the context's own query is kept."""

@@ -490,6 +490,7 @@ void swg_db_release_search_state(swg_db *db)
         (void)hipFree(b.d_keys);
         (void)hipFree(b.d_hist);
         (void)hipFree(b.d_pair_bound);
+        (void)hipFree(b.d_above);
         b = swg_db::Bufs();
     }
     (void)hipFree(db->ptok.d_tok);
@@ -1258,6 +1259,9 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
                     HIP_TRY(ctx, swg_launch_pair_bound(T.d_tok, T.d_pair_off, n_pairs_all, ctx->prune_colmax, db->d_pair_bound, d_ids, qs));
                 struct Stage { uint32_t b, en; size_t sg; };
                 std::vector<Stage> stages;
+                // A caller's threshold (prune->fixed: swg_search_above) is written once, here, and no threshold kernel runs:
+                // every stage, the first included, is cut at it, and a range of one segment is one stage.
+                if (prune->fixed) HIP_TRY(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cw + SWG_PRUNE_WORD_T), (int)prune->fixed_T, 1, qs));
                 for (size_t i = 0; i < segs.size(); ++i) {
                     const uint32_t mid = segs.size() == 1 && prune->head_pairs > 0 ? std::min(segs[i].second, segs[i].first + prune->head_pairs) : segs[i].second;
                     stages.push_back(Stage{segs[i].first, mid, i});
@@ -1266,16 +1270,25 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
                 for (size_t si = 0; si < stages.size(); ++si) {
                     const Stage &st = stages[si];
                     q.list = nullptr, q.list_count = nullptr;
-                    if (si > 0) {
-                        HIP_TRY(ctx, swg_launch_prune_threshold(db->d_scores, db->d_order, (uint32_t)((size_t)db->n_bins * SWG_BIN), (uint32_t)prune_k,
-                                                                db->d_hist, cw + SWG_PRUNE_WORD_T, qs));
+                    if (si > 0 || prune->fixed) {
+                        if (!prune->fixed)
+                            HIP_TRY(ctx, swg_launch_prune_threshold(db->d_scores, db->d_order, (uint32_t)((size_t)db->n_bins * SWG_BIN), (uint32_t)prune_k,
+                                                                    db->d_hist, cw + SWG_PRUNE_WORD_T, qs));
                         if (prune->prefix_cut) {
                             HIP_TRY(ctx, swg_launch_prune_cut(db->d_pair_bound, T.d_pair_off, st.b, st.en, cw + SWG_PRUNE_WORD_T, cw + SWG_PRUNE_WORD_CUT, qs));
                             q.list = d_ids + st.b;
                         } else {
-                            if (prune->refine) // (the table of this epoch: plan_prune queued its build on this stream)
+                            // (the table of this epoch: plan_prune queued its build on this stream.  Under a caller's threshold
+                            // the first of SEVERAL stages -- the longest pairs, whose bounds stand furthest above any T -- is
+                            // walked a second time only where the first level cut an eighth of it: the gate's word is its T)
+                            const uint32_t *refine_thr = cw + SWG_PRUNE_WORD_T;
+                            if (prune->refine && prune->fixed && si == 0 && stages.size() > 1) {
+                                HIP_TRY(ctx, swg_launch_prune_refine_gate(db->d_pair_bound, st.b, st.en, cw + SWG_PRUNE_WORD_T, cw + SWG_PRUNE_WORD_GATE, qs));
+                                refine_thr = cw + SWG_PRUNE_WORD_GATE;
+                            }
+                            if (prune->refine)
                                 HIP_TRY(ctx, swg_launch_pair_bound_refine(T.d_tok, T.d_pair_off, st.b, st.en, (uint32_t)prune->refine, ctx->prune_colmax, ctx->d_kmer_refine,
-                                                                          cw + SWG_PRUNE_WORD_T, db->d_pair_bound, qs));
+                                                                          refine_thr, db->d_pair_bound, qs));
                             const size_t rec = cut_stages.size() / 2;
                             HIP_TRY(ctx, swg_launch_prune_list(db->d_pair_bound, T.d_pair_off, st.b, st.en, cw + SWG_PRUNE_WORD_T, d_tiles, d_lists + st.b,
                                                                cw + SWG_PRUNE_WORD_CUT, rec < SWG_PRUNE_STAGE_RECS ? d_recs + 2 * rec : nullptr, qs));
@@ -2507,6 +2520,7 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
     a.gapless = P->gapless;
     a.batch = ctx->in_batch;
     a.prune_head = ctx->opt_prune_head;
+    a.fixed = ctx->above_min > 0; // (swg_search_above: the caller's threshold, exact against the uint32 bounds)
     if (a.mode == 0 || !a.work_queue || wk.n_classes != 1) return SWG_OK;
     a.range_pairs = wk.pair_end[0] - wk.pair_begin[0];
     a.groups = diag_class_streams(ctx, db, wk, 0);
@@ -2519,6 +2533,7 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
     P->prune = swg_prune_plan(a);
     ctx->prune_last_kmer = 0, ctx->prune_last_segments = 0, ctx->prune_last_refine = 0;
     if (!P->prune.on) return SWG_OK;
+    P->prune.fixed_T = P->prune.fixed ? (uint32_t)ctx->above_min : 0u;
     // which bound: the colmax table, or the k-mer table of the k that pays for its build on this range (a forced k as it is)
     SwgKmerAsk ka;
     ka.forced = ctx->opt_prune_kmer;
@@ -2535,7 +2550,7 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
         if (rk != SWG_OK) return rk;
     }
     // how a stage is cut: pair by pair, behind the second-level bound where that pays, or the prefix of the length order
-    P->prune.prefix_cut = ctx->opt_prune_cut == 1;
+    P->prune.prefix_cut = ctx->opt_prune_cut == 1 && !P->prune.fixed; // (a caller's threshold takes the list)
     P->prune.refine = ctx->prune_last_refine = P->prune.prefix_cut ? 0 : swg_prune_refine_choice(ka, P->prune.kmer, P->prune.segments);
     if (P->prune.refine) {
         const int rk = ensure_kmer_refine_table(ctx, P->prune.refine);
@@ -2580,6 +2595,15 @@ static int enqueue_readout(swg_ctx *ctx, swg_db *db, SwgSlot *S)
     ++ctx->n_begun;
     // top-K on the device unless every score goes to the host anyway
     S->dev_topk = k > 0 && !S->want_scores && k <= SWG_TOPK_CAND_CAP / 2;
+    // swg_search_above: every slot at or above the caller's threshold, behind the last re-score; the counter word came
+    // zeroed with the block and counts them all, the keys that fit stay on the device until swg_search_end knows how many
+    S->above_min = ctx->above_min;
+    if (S->above_min > 0) {
+        const swg_db::Bufs &b = db->bufs[S - ctx->slots];
+        S->above_cap = b.d_above ? b.above_cap : SWG_ABOVE_KEYS_FLOOR;
+        HIP_TRY(ctx, swg_launch_above_compact(db->d_scores, db->d_order, (uint32_t)n_slots, S->above_min, b.d_above ? b.d_above : db->d_keys,
+                                              (uint32_t)S->above_cap, db->d_counters + SWG_ABOVE_WORD_COUNT, s));
+    }
     if (S->dev_topk)
         HIP_TRY(ctx, swg_launch_topk(db->d_scores, db->d_order, (uint32_t)n_slots, (uint32_t)k, db->d_hist,
                                      db->d_counters + 4, db->d_keys, SWG_TOPK_CAND_CAP, db->d_counters + 3, s));
@@ -2657,8 +2681,62 @@ static void deliver_scores(const swg_db *db, const int32_t *h_scores, size_t n_s
     }
 }
 
+// What swg_search_above hands to search_end: where its hits go, how many fit, and the count of all of them.
+struct SwgAboveOut {
+    swg_hit *hits_out = nullptr;
+    size_t cap = 0;
+    uint64_t n_total = 0;
+};
+
+// The read-out of swg_search_above, once the search's counter words are back: the count of every slot at or above the
+// threshold is the answer's n_total; the keys that fitted the device buffer are copied back and sorted as 64-bit keys
+// (the library's total order).  A count beyond the buffer grows it for the next search -- the new capacity is committed
+// only once the allocation stands -- and, where the caller takes any hits, this search selects from the score array on
+// the host, as the top-K does at its capacity edge: the keys dropped are whichever came last, not the worst.
+static int deliver_above(swg_ctx *ctx, SwgSlot *S, hipStream_t s, SwgAboveOut *out, size_t *n_hits)
+{
+    swg_db *db = S->db;
+    const size_t n_slots = (size_t)db->n_bins * SWG_BIN;
+    const size_t count = S->h_counters[SWG_ABOVE_WORD_COUNT], kept = std::min(count, S->above_cap);
+    out->n_total = count;
+    const size_t m = std::min(out->cap, count);
+    if (count > S->above_cap) {
+        swg_db::Bufs &b = db->bufs[S - ctx->slots];
+        const size_t want = std::min<size_t>(db->n_local, std::max<size_t>(count + count / 4, 2 * (size_t)SWG_ABOVE_KEYS_FLOOR));
+        uint64_t *grown = nullptr;
+        if (hipMalloc(&grown, want * 8) == hipSuccess) { // (no room: the next search falls back as this one does)
+            (void)hipFree(b.d_above);
+            b.d_above = grown;
+            b.above_cap = want;
+        } else
+            (void)hipGetLastError();
+    }
+    std::vector<uint64_t> keys;
+    if (count > S->above_cap && m > 0) { // (the device dropped keys, any of them: what it kept need not hold the best)
+        int rc = slot_scores(ctx, S, n_slots);
+        if (rc != SWG_OK) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(S->h_scores, S->bufs.d_scores, n_slots * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, spin_sync(ctx, s));
+        keys.reserve(count);
+        for (size_t i = 0; i < n_slots; ++i) {
+            const uint32_t oi = db->order[i];
+            if (oi != 0xFFFFFFFFu && S->h_scores[i] >= S->above_min) keys.push_back(swg_hit_key(S->h_scores[i], oi));
+        }
+    } else if (m > 0) {
+        keys.resize(kept);
+        const uint64_t *d_keys = S->above_cap > SWG_ABOVE_KEYS_FLOOR ? S->bufs.d_above : S->bufs.d_keys;
+        HIP_TRY(ctx, hipMemcpyAsync(keys.data(), d_keys, kept * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, spin_sync(ctx, s));
+    }
+    const size_t w = std::min(m, keys.size());
+    std::partial_sort(keys.begin(), keys.begin() + w, keys.end(), std::greater<uint64_t>());
+    for (size_t i = 0; i < w; ++i) swg_key_hit(keys[i], &out->hits_out[i]);
+    if (n_hits) *n_hits = w;
+    return SWG_OK;
+}
+
 static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *topk_out, size_t *n_hits,
-                      swg_stats *stats)
+                      swg_stats *stats, SwgAboveOut *above = nullptr)
 {
     swg_db *db = S->db;
     const size_t k = S->k;
@@ -2669,6 +2747,7 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
     swg_stats &st = S->st;
     const SwgSearchPlan &P = S->plan;
     if (P.bits == 0) { // empty database
+        if (above) above->n_total = 0;
         if (stats) *stats = st;
         return SWG_OK;
     }
@@ -2800,7 +2879,9 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
     if (st.fill_launches <= 0) st.fill_launches = std::max(1, st.passes);
 
     const auto t0 = std::chrono::steady_clock::now();
-    if (k > 0 && cand_ok) { // (the device's candidates: every hit with a score >= the k-th best one; no score array was asked for)
+    if (above) {
+        if ((rc = deliver_above(ctx, S, s, above, n_hits)) != SWG_OK) return rc;
+    } else if (k > 0 && cand_ok) { // (the device's candidates: every hit with a score >= the k-th best one; no score array was asked for)
         uint64_t *keys = S->h_cand;
         const size_t nc = h_counters[3], m = std::min(k, nc);
         std::partial_sort(keys, keys + m, keys + nc, std::greater<uint64_t>());
@@ -3613,6 +3694,56 @@ extern "C" int swg_search_gapless(swg_ctx *ctx, const swg_db *db, int32_t *score
         if (sl.busy) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search_gapless: searches are in flight on this context");
     const GaplessMode mode(ctx);
     return search_now(ctx, const_cast<swg_db *>(db), ctx->opt_autotune != 0, scores_out, topk_out, k, n_hits, stats);
+}
+
+// swg_search_above / swg_search_gapless_above: one search whose read-out is every sequence at or above the caller's
+// score (enqueue_readout, deliver_above), and whose 16-bit fill, where swg_prune_plan admits it, is cut at that score
+// from its first launch on (plan_prune, launch_diag).  ctx->above_min says so for the duration of the call.
+namespace {
+struct AboveMode {
+    swg_ctx *ctx;
+    AboveMode(swg_ctx *c, int32_t min_score) : ctx(c) { ctx->above_min = min_score; }
+    ~AboveMode() { ctx->above_min = 0; }
+};
+} // namespace
+
+static int search_above_impl(swg_ctx *ctx, const swg_db *db, bool gapless, const char *what, int32_t min_score, swg_hit *hits_out, size_t cap,
+                             size_t *n_hits, uint64_t *n_total, swg_stats *stats)
+{
+    if (n_hits) *n_hits = 0;
+    if (n_total) *n_total = 0;
+    if (!ctx || !db) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: NULL argument", what);
+    if (min_score < 1) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: min_score must be at least 1 (every sequence scores at least 0)", what);
+    if (cap > 0 && !hits_out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: cap > 0 but hits_out NULL", what);
+    for (const SwgSlot &sl : ctx->slots)
+        if (sl.busy) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: searches are in flight on this context", what);
+    const AboveMode mode(ctx, min_score);
+    ctx->gapless = gapless;
+    struct Restore {
+        swg_ctx *c;
+        ~Restore() { c->gapless = false; }
+    } restore{ctx};
+    int ticket = -1;
+    int rc = search_begin_ticket(ctx, const_cast<swg_db *>(db), false, 0, ctx->opt_autotune != 0, &ticket);
+    if (rc != SWG_OK) return rc;
+    SwgAboveOut out;
+    out.hits_out = hits_out, out.cap = cap;
+    rc = ctx_guarded(ctx, what, [&]() -> int { return search_end(ctx, &ctx->slots[ticket], nullptr, nullptr, n_hits, stats, &out); });
+    ctx->slots[ticket].busy = false;
+    if (rc == SWG_OK && n_total) *n_total = out.n_total;
+    return rc;
+}
+
+extern "C" int swg_search_above(swg_ctx *ctx, const swg_db *db, int32_t min_score, swg_hit *hits_out, size_t cap, size_t *n_hits, uint64_t *n_total,
+                                swg_stats *stats)
+{
+    return search_above_impl(ctx, db, false, "swg_search_above", min_score, hits_out, cap, n_hits, n_total, stats);
+}
+
+extern "C" int swg_search_gapless_above(swg_ctx *ctx, const swg_db *db, int32_t min_score, swg_hit *hits_out, size_t cap, size_t *n_hits,
+                                        uint64_t *n_total, swg_stats *stats)
+{
+    return search_above_impl(ctx, db, true, "swg_search_gapless_above", min_score, hits_out, cap, n_hits, n_total, stats);
 }
 
 static int search_gapless_multi_impl(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, int32_t *scores_out, swg_hit *topk_out, size_t k,

@@ -617,9 +617,21 @@ extern "C" int swg_debug_prune_bound(const int8_t *rows, const int8_t *idx, size
 // (one more load per claim, no batch claims); whether that pays has not been measured, so only mode 2 (diagnostic) does
 // it: the head is the longest pairs -- at least k sequences and prune_head pairs per resident lane group, but no longer
 // than a quarter of the range, so that a database of a few thousand sequences still has a rest to cut.
+// A caller's threshold (a.fixed: swg_search_above) takes the structural conditions alone: T stands before the first
+// kernel, so every stage is a list launch, no stage is a head, and k, want_scores, n_segments and prune_head decide
+// nothing.  Mode 1 (auto) then asks for the range a list launch's cost is small against (swg_prune_above_auto).
 SwgPrunePlan swg_prune_plan(const SwgPruneAsk &a)
 {
     SwgPrunePlan r;
+    if (a.fixed) {
+        if (a.mode == 0 || a.gap_open > 0 || a.gap_extend > 0 || a.bits != 16 || !a.use_diag || a.n_classes != 1 || !a.work_queue || a.both_forms ||
+            a.gapless || a.batch || a.range_pairs == 0)
+            return r;
+        if (a.mode == 1 && !swg_prune_above_auto(a.range_pairs, a.groups)) return r;
+        r.on = true;
+        r.fixed = true;
+        return r;
+    }
     if (a.mode == 0 || a.k == 0 || a.k > SWG_TOPK_CAND_CAP / 2 || (a.want_scores && a.mode != 2) || a.gap_open > 0 || a.gap_extend > 0 ||
         a.bits != 16 || !a.use_diag || a.n_classes != 1 || !a.work_queue || a.both_forms || a.gapless || a.batch || a.range_pairs == 0 ||
         a.prune_head < 0)
@@ -646,6 +658,22 @@ extern "C" int swg_debug_prune_plan(const int64_t *in, int64_t *out)
     a.bits = (int)in[5], a.use_diag = in[6] != 0, a.n_classes = (int)in[7], a.work_queue = in[8] != 0, a.both_forms = in[9] != 0;
     a.gapless = in[10] != 0, a.batch = in[11] != 0, a.range_pairs = (uint64_t)in[12], a.groups = (uint64_t)in[13], a.prune_head = (long)in[14];
     a.n_segments = (size_t)in[15];
+    const SwgPrunePlan r = swg_prune_plan(a);
+    out[0] = r.on ? 1 : 0;
+    out[1] = (int64_t)r.head_pairs;
+    return SWG_OK;
+}
+
+// test hook: in[0..11] = mode, gap_open, gap_extend, bits, use_diag, n_classes, work_queue, both_forms, gapless, batch,
+// range_pairs, groups; in[12..13] = n_segments, prune_head (read, and without a say); out[0..1] = pruned, head pairs (0)
+extern "C" int swg_debug_prune_plan_above(const int64_t *in, int64_t *out)
+{
+    if (!in || !out || in[10] < 0 || in[11] < 0 || in[12] < 0) return SWG_ERR_ARG;
+    SwgPruneAsk a;
+    a.fixed = true;
+    a.mode = (int)in[0], a.gap_open = (int)in[1], a.gap_extend = (int)in[2], a.bits = (int)in[3], a.use_diag = in[4] != 0, a.n_classes = (int)in[5];
+    a.work_queue = in[6] != 0, a.both_forms = in[7] != 0, a.gapless = in[8] != 0, a.batch = in[9] != 0, a.range_pairs = (uint64_t)in[10];
+    a.groups = (uint64_t)in[11], a.n_segments = (size_t)in[12], a.prune_head = (long)in[13];
     const SwgPrunePlan r = swg_prune_plan(a);
     out[0] = r.on ? 1 : 0;
     out[1] = (int64_t)r.head_pairs;

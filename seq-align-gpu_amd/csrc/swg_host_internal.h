@@ -188,6 +188,9 @@ struct swg_db {
         // most a pair each) and the list's tile counts (swg_prune_pair_words; allocated by the first one)
         uint32_t *d_pair_bound = nullptr;
         size_t pair_bound_cap = 0;        // pairs it has room for
+        // swg_search_above's keys once a search met more than SWG_ABOVE_KEYS_FLOOR of them (until then d_keys serves)
+        uint64_t *d_above = nullptr;
+        size_t above_cap = 0;             // keys it has room for
     } bufs[4];
     int32_t *d_scores = nullptr;
     uint32_t *d_list = nullptr;
@@ -247,6 +250,9 @@ struct SwgPruneAsk {
     uint64_t range_pairs = 0, groups = 0; // the class's pairs, the lane groups resident on the device
     long prune_head = 4;     // option "prune_head"
     size_t n_segments = 1;   // launches per pass (token_segments)
+    // a caller's threshold (swg_search_above): T is min_score from the first launch on, so there is no head and k,
+    // want_scores, n_segments and prune_head decide nothing
+    bool fixed = false;
 };
 struct SwgPrunePlan {
     bool on = false;
@@ -255,6 +261,8 @@ struct SwgPrunePlan {
     int segments = 0;        // ... and the segments of that table (1: the unordered sum of swg_pair_bound_kmer_kernel)
     int refine = 0;          // the second level's segments (swg_prune_refine_choice): 64, 128, or 0 without one
     bool prefix_cut = false; // option "prune_cut" = 1: a stage's list is the prefix up to its last pair that reaches T
+    bool fixed = false;      // a caller's threshold: every stage, the first included, is a list launch cut at fixed_T
+    uint32_t fixed_T = 0;    // ... written once to the threshold word and never recomputed
 };
 // words of swg_db::Bufs::d_pair_bound for n pairs: bounds, ids, lists (a stage's from its first pair's word), one tile
 // count per SWG_PRUNE_TILE pairs, and {T, kept pairs} of the first SWG_PRUNE_STAGE_RECS cut stages (tests read them back)
@@ -262,9 +270,16 @@ struct SwgPrunePlan {
 inline size_t swg_prune_tile_words(size_t n_pairs) { return n_pairs / SWG_PRUNE_TILE + 2; }
 inline size_t swg_prune_pair_words(size_t n_pairs) { return 3 * n_pairs + swg_prune_tile_words(n_pairs) + 2 * SWG_PRUNE_STAGE_RECS; }
 SwgPrunePlan swg_prune_plan(const SwgPruneAsk &a);
+// The automatic rule of a caller's threshold ("A caller's threshold"; profiles/search_above_ab.txt): the
+// bound, list and tally kernels of a stage cost tens of microseconds whatever the range holds, a list launch one
+// dependent load per claim; a range with at least SWG_PRUNE_ABOVE_AUTO_PAIRS pairs per resident lane group has fills
+// long enough for both to vanish in them.
+#define SWG_PRUNE_ABOVE_AUTO_PAIRS 16u
+inline bool swg_prune_above_auto(uint64_t range_pairs, uint64_t groups) { return range_pairs >= SWG_PRUNE_ABOVE_AUTO_PAIRS * std::max<uint64_t>(1, groups); }
 extern "C" int swg_debug_prune_bound(const int8_t *rows, const int8_t *idx, size_t lq, const int8_t *flat, const uint64_t *offsets, size_t n,
                                      uint8_t *colmax_out, uint64_t *u_out);
 extern "C" int swg_debug_prune_plan(const int64_t *in, int64_t *out);
+extern "C" int swg_debug_prune_plan_above(const int64_t *in, int64_t *out);
 // The k-mer form of the bound (swg_internal.h has the classes): its host restatement, and the choice of k.
 void swg_kmer_cprof(const int8_t *rows, const int8_t *idx, size_t lq, int8_t *cprof);                 // cprof[lq][22]
 void swg_kmer_table(const int8_t *cprof, size_t lq, int g, int e, int k, uint16_t *table);            // table[22^k]
@@ -312,6 +327,12 @@ extern "C" int swg_debug_prune_kmer_refine(const int8_t *rows, const int8_t *idx
 // takes, the pairs skipped so far, their token blocks (64 bits)
 #define SWG_PRUNE_WORD_T 18u
 #define SWG_PRUNE_WORD_CUT 20u
+// ... and the word swg_above_compact_kernel counts in: every slot at or above a caller's threshold (swg_search_above)
+#define SWG_ABOVE_WORD_COUNT 24u
+// ... and the threshold word of the second level on its first of several stages (swg_prune_refine_gate_kernel)
+#define SWG_PRUNE_WORD_GATE 25u
+// keys the read-out of swg_search_above has room for before its buffer grows: the top-K's candidate buffer serves
+#define SWG_ABOVE_KEYS_FLOOR SWG_TOPK_CAND_CAP
 
 // Geometry of the systolic engine (bin-based kernels) for one query length.
 struct SwgSystolicPlan {
@@ -397,6 +418,8 @@ struct SwgSlot {
     bool want_scores = false, dev_topk = false, need_scores = false, two_ends = false;
     int fill_launches = 0; // launches of the bulk class's fill kernel (passes x segments)
     bool pruned = false;   // the fill was launched stage by stage with cuts (launch_diag)
+    int32_t above_min = 0; // swg_search_above: the caller's threshold (0: a top-K / score-array search)
+    size_t above_cap = 0;  // ... and the keys its read-out's device buffer had room for
     int fill_f16_launches = 0; // both forms in one class: those of them that ran the f16 cells
     swg_stats st;
     uint64_t *h_cand = nullptr;     // pinned, SWG_TOPK_CAND_CAP keys
@@ -443,6 +466,7 @@ struct swg_ctx {
     std::vector<int8_t> pssm;
     bool query_pssm = false;
     bool gapless = false; // set for the duration of a swg_search_gapless call: plan_search prices the gaps out
+    int32_t above_min = 0; // set for the duration of a swg_search_above call: the caller's threshold
     // query length of either form: what every lq of the planner, the profiles and the traceback is
     size_t query_len() const { return query_pssm ? pssm.size() / 32 : query.size(); }
     // options

@@ -300,6 +300,10 @@ hipError_t swg_launch_collect_saturated(const int32_t *d_scores, uint32_t n_slot
 hipError_t swg_launch_topk(const int32_t *d_scores, const uint32_t *d_order, uint32_t n_slots, uint32_t k,
                            uint32_t *d_hist, uint32_t *d_thr, uint64_t *d_cand, uint32_t cap, uint32_t *d_count,
                            hipStream_t stream);
+// The read-out of swg_search_above: after the call *d_count (zeroed by the caller) is the number of slots with a score
+// >= min_score (>= 1), and d_keys[0 .. min(*d_count, cap)) holds that many of their keys (swg_hit_key), unsorted.
+hipError_t swg_launch_above_compact(const int32_t *d_scores, const uint32_t *d_order, uint32_t n_slots, int32_t min_score, uint64_t *d_keys, uint32_t cap,
+                                    uint32_t *d_count, hipStream_t stream);
 // Hits-only pruning.  colmax[r] = max(0, best score of database residue r against any query column):
 // a sequence's local score is at most the sum of colmax over its residues (non-positive gap scores).
 struct SwgColMax {
@@ -364,6 +368,9 @@ hipError_t swg_launch_pair_bound_refine(const uint4 *d_tok, const uint32_t *d_pa
 // the others, (uint64 at d_out[2]) += their token blocks.  d_tiles: one word per SWG_PRUNE_TILE pairs of the range;
 // d_rec (or NULL): {*d_thr, d_out[0]} once more, for the tests.
 #define SWG_PRUNE_TILE 1024u // 256 threads, 4 consecutive pairs each
+// *d_gate = *d_thr where at least an eighth of the pairs of [begin, end) have a bound below *d_thr, else 0xFFFFFFFF: the
+// threshold word of a refine launch that is to run only where it can cut (swg_search_above's first of several stages)
+hipError_t swg_launch_prune_refine_gate(const uint32_t *d_bound, uint32_t begin, uint32_t end, const uint32_t *d_thr, uint32_t *d_gate, hipStream_t stream);
 hipError_t swg_launch_prune_list(const uint32_t *d_bound, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, const uint32_t *d_thr,
                                  uint32_t *d_tiles, uint32_t *d_list, uint32_t *d_out, uint32_t *d_rec, hipStream_t stream);
 // ... and for the n_queries score rows of a batch (swg_search_multi) at once: d_hist[n_queries][4096],

@@ -2784,6 +2784,45 @@ hipError_t swg_launch_topk_multi(const int32_t *d_scores, uint64_t score_stride,
     return hipGetLastError();
 }
 
+// The read-out of swg_search_above: the key of every slot whose final score is at or above the caller's threshold, in any
+// order (the host sorts), and their number -- all of them, whether or not their key fitted: keys[min(*count, cap)] hold
+// keys, the rest were dropped.  Grid-stride over whole wavefronts, so that every lane of a wavefront takes every round
+// and the append is one atomic per wavefront and round: the ballot of the lanes that qualify, its population count added
+// by the first of them, each lane's place the count of the qualifying lanes below it (mbcnt).
+__global__ __launch_bounds__(256) void swg_above_compact_kernel(const int32_t *scores, const uint32_t *order, uint32_t n, int32_t min_score,
+                                                                uint64_t *keys, uint32_t cap, uint32_t *count)
+{
+    __builtin_amdgcn_s_setprio(3); // (it may run beside the next search's fill: see swg_topk_compact_kernel)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); i0 < n; i0 += stride) { // (the same for a wavefront's lanes)
+        const uint64_t i = i0 + lane;
+        uint32_t oi = 0xFFFFFFFFu;
+        int v = 0;
+        if (i < n) oi = order[i], v = scores[i];
+        const bool hit = oi != 0xFFFFFFFFu && v >= min_score;
+        const unsigned long long mask = __ballot(hit);
+        if (mask == 0ull) continue;
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        const int leader = __ffsll((long long)mask) - 1;
+        uint32_t base = 0u;
+        if ((int)lane == leader) base = atomicAdd(count, (uint32_t)__popcll(mask));
+        base = (uint32_t)__shfl((int)base, leader, 64);
+        const uint32_t at = base + below; // (all qualifying slots are at most n < 2^32)
+        if (hit && at < cap) keys[at] = ((uint64_t)(uint32_t)v << 32) | (uint64_t)(0xFFFFFFFFu - oi); // (swg_hit_key: v >= min_score >= 1)
+    }
+}
+
+hipError_t swg_launch_above_compact(const int32_t *d_scores, const uint32_t *d_order, uint32_t n_slots, int32_t min_score, uint64_t *d_keys, uint32_t cap,
+                                    uint32_t *d_count, hipStream_t stream)
+{
+    if (min_score < 1 || !d_keys) return hipErrorInvalidValue;
+    const uint32_t want = (n_slots + 255u) / 256u;
+    const uint32_t blocks = want < 1u ? 1u : want > 2048u ? 2048u : want;
+    hipLaunchKernelGGL(swg_above_compact_kernel, dim3(blocks), dim3(256), 0, stream, d_scores, d_order, n_slots, min_score, d_keys, cap, d_count);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // hits-only pruning: the score bound of every pair, the threshold so far, the cut of a stage
 // ---------------------------------------------------------------------------
@@ -3301,6 +3340,38 @@ hipError_t swg_launch_pair_bound_refine(const uint4 *d_tok, const uint32_t *d_pa
         hipLaunchKernelGGL((swg_pair_bound_refine_kernel<4, 4>), dim3(wgs), dim3(256), 0, stream, d_tok, d_pair_off, begin, end, cm, d_table, d_thr, d_bound);
     else
         hipLaunchKernelGGL((swg_pair_bound_refine_kernel<4, 2>), dim3(wgs), dim3(256), 0, stream, d_tok, d_pair_off, begin, end, cm, d_table, d_thr, d_bound);
+    return hipGetLastError();
+}
+
+// The gate of the second level on the FIRST of several stages under a caller's threshold (swg_search_above; DESIGN 4.2.1,
+// "A caller's threshold").  That stage holds the longest pairs, whose bounds stand furthest above T: where the first level
+// cuts none of them the second cuts none either and its walk over all of them is lost time (1 % of the headline at the
+// score of its 100th hit), where T lies inside their bounds it cuts many (a quarter of the time at twice that score).  So
+// the stage's refine launch reads its threshold from gate[0]: T where the first level left at least one pair in eight
+// below T, else 0xFFFFFFFF, under which every group of swg_pair_bound_refine_kernel leaves at its first comparison.
+// One workgroup: the pairs of one segment.
+__global__ __launch_bounds__(1024) void swg_prune_refine_gate_kernel(const uint32_t *bound, uint32_t begin, uint32_t end, const uint32_t *thr,
+                                                                     uint32_t *gate)
+{
+    __shared__ uint32_t s_below[16];
+    const uint32_t T = thr[0];
+    uint32_t below = 0u;
+    for (uint64_t p = (uint64_t)begin + threadIdx.x; p < end; p += 1024u) below += bound[p] < T ? 1u : 0u;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) below += (uint32_t)__shfl_xor((int)below, d, 64);
+    if ((threadIdx.x & 63u) == 0u) s_below[threadIdx.x >> 6] = below;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint64_t all = 0u;
+        for (uint32_t w = 0u; w < 16u; ++w) all += s_below[w];
+        gate[0] = all * 8u >= (uint64_t)(end - begin) && end > begin ? T : 0xFFFFFFFFu;
+    }
+}
+
+hipError_t swg_launch_prune_refine_gate(const uint32_t *d_bound, uint32_t begin, uint32_t end, const uint32_t *d_thr, uint32_t *d_gate, hipStream_t stream)
+{
+    if (end < begin) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(swg_prune_refine_gate_kernel, dim3(1), dim3(1024), 0, stream, d_bound, begin, end, d_thr, d_gate);
     return hipGetLastError();
 }
 

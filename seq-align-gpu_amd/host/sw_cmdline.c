@@ -26,7 +26,10 @@
  *     path (swg_align_bounds, with --allqueries swg_align_bounds_multi / _multi_pssm: no traceback is run);
  *     --tabular with --topk K appends one tab-separated line per reported hit in the columns of BLAST's -outfmt 6 up to
  *     the coordinates, then the raw score (swg_align_stats, with --allqueries swg_align_stats_multi / _multi_pssm: the
- *     identities and gap openings come from the same forward pass, no traceback is run).
+ *     identities and gap openings come from the same forward pass, no traceback is run);
+ *     --minscore S reports every entry that scores at least S, best first, in --topk's block (swg_search_above: no score
+ *     array, so no Entry lines), with --topk K the best K of them; under --gpus N each device searches its shard and the
+ *     lists are merged by swg_hit_key.
  * There is no CPU backend: without a GPU the tool fails with a message.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -91,6 +94,10 @@ static void usage(const char *argv0, const char *err)
             "                         entries only\n"
             "    --gapless            report the gapless score (best ungapped diagonal segment; the gap scores are not used)\n"
             "                         instead of the alignment score; not with --align, --candidates or --gpus\n"
+            "    --minscore <S>       report every entry that scores at least S (1 or more), best first, in --topk's block (no Entry\n"
+            "                         lines are printed: no score array is made); with --topk K the best K of them; --align, --bounds and\n"
+            "                         --tabular then report those hits; with --gpus N every GPU searches its shard and the lists are\n"
+            "                         merged; not with --allqueries, --candidates or --prefilter\n"
             "    --prefilter <N>      with --topk K: per query (every record with --allqueries) the N best entries by gapless\n"
             "                         score are searched with gaps and the K best of those reported (--align: aligned);\n"
             "                         no Entry lines are printed; not with --gpus, --candidates or --gapless\n",
@@ -192,7 +199,7 @@ int main(int argc, char **argv)
     swg_scoring_init(&sc);
     const char *qpath = NULL, *dbpath = NULL, *savedb = NULL, *pssm_path = NULL, *pssmlist_path = NULL, *idlist_path = NULL, *cand_path = NULL;
     int print_seq = 0, print_fasta = 0, have_matrix = 0, packed = 0, allq = 0;
-    long topk = 0, gpu = 0, gpus = 0, prefilter = 0, v;
+    long topk = 0, gpu = 0, gpus = 0, prefilter = 0, minscore = 0, v;
     int align = 0, gapless = 0, bounds = 0, tabular = 0;
     if (argc == 1) usage(argv[0], NULL);
     for (int i = 1; i < argc; i++)
@@ -248,6 +255,9 @@ int main(int argc, char **argv)
         } else if (!strcasecmp(a, "--topk")) {
             if (!parse_int(argv[i + 1], 0, 1 << 20, &topk)) usage(argv[0], "Invalid --topk argument");
             i++;
+        } else if (!strcasecmp(a, "--minscore")) {
+            if (!parse_int(argv[i + 1], 1, INT_MAX, &minscore)) usage(argv[0], "Invalid --minscore argument: the least score to report, 1 or more");
+            i++;
         } else if (!strcasecmp(a, "--prefilter")) {
             if (!parse_int(argv[i + 1], 1, 1 << 20, &prefilter)) usage(argv[0], "Invalid --prefilter argument: the number of candidates per query, 1 or more");
             i++;
@@ -293,12 +303,13 @@ int main(int argc, char **argv)
     if (pssmlist_path && pssm_path) usage(argv[0], "--pssmlist and --pssm do not combine (the list names the first record's PSSM too)");
     if (pssmlist_path && gpus > 0) usage(argv[0], "--pssmlist works with one GPU (--gpu)");
     if ((packed || savedb || allq) && gpus > 0) usage(argv[0], "--packed/--savedb/--allqueries work with one GPU (--gpu)");
-    if (align && topk == 0) usage(argv[0], "--align reports the alignments of the --topk hits: give --topk K");
-    if (bounds && topk == 0) usage(argv[0], "--bounds reports the alignment coordinates of the --topk hits: give --topk K");
+    if (minscore && (allq || cand_path || prefilter)) usage(argv[0], "--minscore reports one query's hits: it does not combine with --allqueries, --candidates or --prefilter");
+    if (align && topk == 0 && !minscore) usage(argv[0], "--align reports the alignments of the --topk hits: give --topk K");
+    if (bounds && topk == 0 && !minscore) usage(argv[0], "--bounds reports the alignment coordinates of the --topk hits: give --topk K");
     if (bounds && align) usage(argv[0], "--bounds reports coordinates without the alignments: it does not combine with --align (whose headers carry them)");
     if (bounds && gapless) usage(argv[0], "--bounds reports coordinates of gapped alignments: it does not combine with --gapless");
     if (bounds && gpus > 0) usage(argv[0], "--bounds works with one GPU (--gpu)");
-    if (tabular && topk == 0) usage(argv[0], "--tabular reports one tabular line for each of the --topk hits: give --topk K");
+    if (tabular && topk == 0 && !minscore) usage(argv[0], "--tabular reports one tabular line for each of the --topk hits: give --topk K");
     if (tabular && align) usage(argv[0], "--tabular reports counts without the alignments: it does not combine with --align");
     if (tabular && bounds) usage(argv[0], "--tabular carries the coordinates itself: it does not combine with --bounds");
     if (tabular && gapless) usage(argv[0], "--tabular reports gapped alignments: it does not combine with --gapless");
@@ -309,7 +320,7 @@ int main(int argc, char **argv)
     if (cand_path && idlist_path) usage(argv[0], "--candidates and --seqidlist do not combine (the candidates are the entries to search)");
     if (cand_path && pssm_path) usage(argv[0], "--candidates and --pssm do not combine (--pssmlist names a PSSM per record)");
     if (gapless && align) usage(argv[0], "--gapless reports scores of ungapped segments: it does not combine with --align");
-    if (gapless && (gpus > 0 || cand_path)) usage(argv[0], "--gapless works with one GPU (--gpu) and without --candidates");
+    if (gapless && ((gpus > 0 && !minscore) || cand_path)) usage(argv[0], "--gapless works with one GPU (--gpu) and without --candidates");
     if (prefilter && topk == 0) usage(argv[0], "--prefilter N reports the --topk hits among the N gapless candidates: give --topk K");
     if (prefilter && gpus > 0) usage(argv[0], "--prefilter works with one GPU (--gpu)");
     if (prefilter && (cand_path || gapless)) usage(argv[0], "--prefilter makes the candidate lists itself: it does not combine with --candidates or --gapless");
@@ -579,17 +590,94 @@ int main(int argc, char **argv)
 
     phase("letters to table indices");
     int32_t *scores = (int32_t *)calloc(db.n ? db.n : 1, sizeof(int32_t));
-    swg_hit *hits = (swg_hit *)calloc(topk ? (size_t)topk : 1, sizeof(swg_hit));
+    /* --minscore without --topk: room for every entry searched */
+    const size_t hit_cap = topk ? (size_t)topk : minscore ? (ids ? n_ids : db.n) : 0;
+    swg_hit *hits = (swg_hit *)calloc(hit_cap ? hit_cap : 1, sizeof(swg_hit));
     if (!scores || !hits) {
         fprintf(stderr, "Error: out of memory\n");
         return leave(EXIT_FAILURE);
     }
     size_t n_hits = 0;
+    uint64_t n_above = 0; /* --minscore: the entries at or above it, reported or not */
     double total_ms = 0.0;
     swg_ctx *ctx = NULL;
     swg_group *grp = NULL;
     swg_db *sdb = NULL; /* what is searched: the database, or with --seqidlist the view of its listed entries */
-    if (gpus > 0) {
+    /* --minscore --gpus N: a context, a shard and what is searched of it per GPU; sh_of[i] = the shard hit i came from */
+    size_t sh_n = 0;
+    swg_ctx **sh_ctx = NULL;
+    swg_db **sh_db = NULL, **sh_sdb = NULL;
+    uint32_t *sh_of = NULL;
+    if (gpus > 0 && minscore) {
+        /* --minscore over several GPUs: every GPU searches its shard (swg_search_above has no group form), the shards'
+         * lists are merged in the library's order */
+        sh_n = (size_t)gpus;
+        sh_ctx = (swg_ctx **)calloc(sh_n, sizeof *sh_ctx);
+        sh_db = (swg_db **)calloc(sh_n, sizeof *sh_db);
+        sh_sdb = (swg_db **)calloc(sh_n, sizeof *sh_sdb);
+        sh_of = (uint32_t *)calloc(hit_cap ? hit_cap : 1, sizeof *sh_of);
+        uint64_t *keys = (uint64_t *)malloc((hit_cap ? hit_cap : 1) * sh_n * sizeof *keys);
+        uint32_t *key_sh = (uint32_t *)malloc((hit_cap ? hit_cap : 1) * sh_n * sizeof *key_sh);
+        if (!sh_ctx || !sh_db || !sh_sdb || !sh_of || !keys || !key_sh) return leave(EXIT_FAILURE);
+        int rc = swg_db_pack_shards(didx, db.seq_off, db.n, (int)gpus, sh_db);
+        if (rc != SWG_OK) {
+            fprintf(stderr, "Error: %s\n", swg_global_error());
+            return leave(EXIT_FAILURE);
+        }
+        phase("sort, shard and pack");
+        size_t n_keys = 0;
+        for (size_t g = 0; g < sh_n; g++) {
+            swg_config cfg;
+            swg_stats st;
+            memset(&cfg, 0, sizeof cfg);
+            memset(&st, 0, sizeof st);
+            cfg.device = (int)g;
+            if (swg_create(&cfg, &sh_ctx[g]) != SWG_OK) {
+                fprintf(stderr, "Error: %s\n", swg_global_error());
+                return leave(EXIT_FAILURE);
+            }
+            swg_ctx *c = sh_ctx[g];
+            rc = swg_set_option(c, "autotune", 0);
+            if (rc == SWG_OK) rc = swg_set_scoring(c, (const int8_t(*)[32])sc.sub, sc.gap_open, sc.gap_extend);
+            if (rc == SWG_OK) rc = pssm0 ? swg_set_query_pssm(c, pssm0, lq) : swg_set_query(c, qidx, lq);
+            if (rc == SWG_OK) rc = swg_db_upload(c, sh_db[g]);
+            sh_sdb[g] = sh_db[g];
+            if (rc == SWG_OK && ids) rc = swg_db_view(c, sh_db[g], ids, n_ids, &sh_sdb[g]); /* (the entries of other shards are ignored) */
+            size_t got = 0;
+            uint64_t above = 0;
+            if (rc == SWG_OK)
+                rc = gapless ? swg_search_gapless_above(c, sh_sdb[g], (int32_t)minscore, hits, hit_cap, &got, &above, &st)
+                             : swg_search_above(c, sh_sdb[g], (int32_t)minscore, hits, hit_cap, &got, &above, &st);
+            if (rc != SWG_OK) {
+                fprintf(stderr, "Error: %s\n", swg_last_error(c));
+                return leave(EXIT_FAILURE);
+            }
+            for (size_t i = 0; i < got; i++) keys[n_keys] = swg_hit_key(hits[i].score, hits[i].index), key_sh[n_keys++] = (uint32_t)g;
+            n_above += above;
+            total_ms += st.total_ms; /* (one after another) */
+        }
+        phase("search (shard by shard)");
+        /* the best hit_cap of the shards' lists, each sorted already: pick the largest head hit_cap times */
+        size_t *head = (size_t *)calloc(sh_n + 1, sizeof *head), *end = (size_t *)calloc(sh_n + 1, sizeof *end);
+        if (!head || !end) return leave(EXIT_FAILURE);
+        for (size_t i = 0, g = 0; g < sh_n; g++) {
+            head[g] = i;
+            while (i < n_keys && key_sh[i] == g) i++;
+            end[g] = i;
+        }
+        for (n_hits = 0; n_hits < hit_cap; n_hits++) {
+            size_t best = sh_n;
+            for (size_t g = 0; g < sh_n; g++)
+                if (head[g] < end[g] && (best == sh_n || keys[head[g]] > keys[head[best]])) best = g;
+            if (best == sh_n) break;
+            swg_key_hit(keys[head[best]++], &hits[n_hits]);
+            sh_of[n_hits] = (uint32_t)best;
+        }
+        free(head);
+        free(end);
+        free(keys);
+        free(key_sh);
+    } else if (gpus > 0) {
         /* database sharded over several GPUs of this process */
         swg_stats *st = (swg_stats *)calloc((size_t)gpus, sizeof(swg_stats));
         if (!st) return leave(EXIT_FAILURE);
@@ -673,6 +761,9 @@ int main(int argc, char **argv)
             const uint64_t off01[2] = {0, lq};
             rc = pssm0 ? swg_search_lists_pssm(ctx, sdb, pssm0, off01, 1, cands, c_off, lsc, hits, (size_t)topk, &n_hits, &st)
                        : swg_search_lists(ctx, sdb, qidx, off01, 1, cands, c_off, lsc, hits, (size_t)topk, &n_hits, &st);
+        } else if (rc == SWG_OK && minscore) {
+            rc = gapless ? swg_search_gapless_above(ctx, sdb, (int32_t)minscore, hits, hit_cap, &n_hits, &n_above, &st)
+                         : swg_search_above(ctx, sdb, (int32_t)minscore, hits, hit_cap, &n_hits, &n_above, &st);
         } else if (rc == SWG_OK) {
             rc = gapless ? swg_search_gapless(ctx, sdb, scores, hits, (size_t)topk, &n_hits, &st)
                          : swg_search(ctx, sdb, scores, hits, (size_t)topk, &n_hits, &st);
@@ -714,7 +805,7 @@ next_query:
         }
     }
     if (allq) printf("Query #%lu: %s\n", (unsigned long)qi, qname);
-    for (size_t i = 0, shown = 0; i < db.n && !prefilter; i++) {
+    for (size_t i = 0, shown = 0; i < db.n && !prefilter && !minscore; i++) {
         if (listed && !listed[i]) continue;
         if (shown++ % 16 == 0) {
             if (print_fasta) {
@@ -740,7 +831,8 @@ next_query:
     /* reference src/alignment_cmdline.c:529-530; the time is the device time of the fill */
     printf("Total Time: %f\n", total_ms * 1e-3);
     printf("Total Entries: %lu\n", (unsigned long)(listed ? n_listed : db.n));
-    if (topk > 0) {
+    if (minscore) printf("Entries at or above %ld: %llu\n", minscore, (unsigned long long)n_above);
+    if (topk > 0 || minscore) {
         printf("Top %lu hits (score, entry, name):\n", (unsigned long)n_hits);
         for (size_t i = 0; i < n_hits; i++)
             printf("%d\t%u\t%s\n", hits[i].score, hits[i].index, packed ? "" : db.names + db.name_off[hits[i].index]);
@@ -754,7 +846,39 @@ next_query:
             fprintf(stderr, "Error: %s\n", al_err);
             return leave(EXIT_FAILURE);
         }
-        if (qi == 0) {
+        if (sh_n) { /* --minscore --gpus N: every hit is aligned on the GPU that holds its shard */
+            stride = 1;
+            for (size_t g = 0; g < sh_n; g++) {
+                const size_t b = swg_align_ops_bound(sh_ctx[g], sh_sdb[g]);
+                if (b > stride) stride = b;
+            }
+            al = (swg_alignment *)calloc(n_hits, sizeof *al);
+            ops = (char *)malloc(n_hits * stride);
+            swg_hit *part = (swg_hit *)calloc(n_hits, sizeof *part);
+            swg_alignment *part_al = (swg_alignment *)calloc(n_hits, sizeof *part_al);
+            char *part_ops = (char *)malloc(n_hits * stride);
+            if (!al || !ops || !part || !part_al || !part_ops) return leave(EXIT_FAILURE);
+            for (size_t g = 0; g < sh_n; g++) {
+                size_t m = 0;
+                for (size_t i = 0; i < n_hits; i++)
+                    if (sh_of[i] == g) part[m++] = hits[i];
+                if (m == 0) continue;
+                if (swg_align_hits(sh_ctx[g], sh_sdb[g], part, m, part_al, part_ops, stride) != SWG_OK) {
+                    fprintf(stderr, "Error: %s\n", swg_last_error(sh_ctx[g]));
+                    return leave(EXIT_FAILURE);
+                }
+                m = 0;
+                for (size_t i = 0; i < n_hits; i++)
+                    if (sh_of[i] == g) {
+                        al[i] = part_al[m];
+                        memcpy(ops + i * stride, part_ops + m * stride, stride);
+                        m++;
+                    }
+            }
+            free(part);
+            free(part_al);
+            free(part_ops);
+        } else if (qi == 0) {
             stride = grp ? swg_group_align_ops_bound(grp) : swg_align_ops_bound(ctx, sdb);
             al = (swg_alignment *)calloc(n_hits, sizeof *al);
             ops = (char *)malloc(n_hits * stride);
@@ -1003,6 +1127,15 @@ next_query:
     swg_db_free(pdb);
     swg_destroy(ctx);
     swg_group_destroy(grp);
+    for (size_t g = 0; g < sh_n; g++) {
+        if (sh_sdb[g] != sh_db[g]) swg_db_free(sh_sdb[g]);
+        swg_db_free(sh_db[g]);
+        swg_destroy(sh_ctx[g]);
+    }
+    free(sh_ctx);
+    free(sh_db);
+    free(sh_sdb);
+    free(sh_of);
     swg_seqs_free(&q);
     swg_seqs_free(&db);
     free(qidx);
