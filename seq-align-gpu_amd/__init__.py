@@ -234,6 +234,7 @@ _sig("swg_prune_last", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_bound", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp])
 _sig("swg_debug_prune_plan", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_plan_above", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_stages", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 _sig("swg_debug_prune_kmer", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp])
 _sig("swg_debug_prune_kmer_choice", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_kmer_read", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp])
@@ -463,12 +464,9 @@ for _r in range(1, 32):
 del _std, _r
 
 
-def debug_prune_kmer(rows, query, gap_open, gap_extend, k, flat, offsets, table=True):
-    """Test hook (no device needed): the host mirror of the k-mer bound, k = 4 or 5.  rows / query as debug_prune_bound
-    takes them.  -> (table uint16[22^k] or None, U_k uint64[n]): the local score of every class block against the query,
-    and the bound of each sequence flat[offsets[i] .. offsets[i+1]) summed as the device sums it -- over the sequence's
-    token rows (two reset rows first), in blocks of 4 rows, or of 5 over every whole 20 rows and of 4 over the rest.  A
-    residue 0 in a sequence is a padding row (the shorter sequence of a pair, filled up to the longer one's length)."""
+def _prune_kmer_mirror(hook, rows, query, gap_open, gap_extend, which, flat, offsets, table_shape):
+    """The marshalling of the three k-mer mirror hooks: `which` is the hook's own arguments between the gap scores and
+    the sequences ((k,), (k, S) or (S2,)), table_shape the table to hand it (None: none).  -> (table or None, U uint64[n])."""
     r, rp = _i8(rows)
     lq = r.size // 32
     qp = None
@@ -478,11 +476,21 @@ def debug_prune_kmer(rows, query, gap_open, gap_extend, k, flat, offsets, table=
     f, fp = _i8(flat)
     off = np.ascontiguousarray(offsets, dtype=np.uint64)
     n = off.size - 1
-    t = np.zeros(KMER_CLASSES ** int(k), dtype=np.uint16) if table and k in (4, 5) else None
+    t = np.zeros(table_shape, dtype=np.uint16) if table_shape is not None else None
     u = np.zeros(max(n, 1), dtype=np.uint64)
-    _check(lib.swg_debug_prune_kmer(rp, qp, lq, int(gap_open), int(gap_extend), int(k), fp, off.ctypes.data_as(_vp), n,
-                                    t.ctypes.data_as(_vp) if t is not None else None, u.ctypes.data_as(_vp)))
+    _check(hook(rp, qp, lq, int(gap_open), int(gap_extend), *which, fp, off.ctypes.data_as(_vp), n,
+                t.ctypes.data_as(_vp) if t is not None else None, u.ctypes.data_as(_vp)))
     return t, u[:n]
+
+
+def debug_prune_kmer(rows, query, gap_open, gap_extend, k, flat, offsets, table=True):
+    """Test hook (no device needed): the host mirror of the k-mer bound, k = 4 or 5.  rows / query as debug_prune_bound
+    takes them.  -> (table uint16[22^k] or None, U_k uint64[n]): the local score of every class block against the query,
+    and the bound of each sequence flat[offsets[i] .. offsets[i+1]) summed as the device sums it -- over the sequence's
+    token rows (two reset rows first), in blocks of 4 rows, or of 5 over every whole 20 rows and of 4 over the rest.  A
+    residue 0 in a sequence is a padding row (the shorter sequence of a pair, filled up to the longer one's length)."""
+    return _prune_kmer_mirror(lib.swg_debug_prune_kmer, rows, query, gap_open, gap_extend, (int(k),), flat, offsets,
+                              (KMER_CLASSES ** int(k),) if table and k in (4, 5) else None)
 
 
 def debug_prune_kmer_choice(forced=0, pruned=1, lq=3000, pair_rows=1900000000, table_rate=0, fill_rate=0):
@@ -505,21 +513,9 @@ def debug_prune_kmer_seg(rows, query, gap_open, gap_extend, k, segments, flat, o
     ceil(lq / segments) wide.  -> (table uint16[22^k, segments] or None, U uint64[n]): every class block's best cell
     within each segment, and the bound of each sequence with its blocks taken in order.  One segment is
     debug_prune_kmer."""
-    r, rp = _i8(rows)
-    lq = r.size // 32
-    qp = None
-    if query is not None:
-        q, qp = _i8(query)
-        lq = q.size
-    f, fp = _i8(flat)
-    off = np.ascontiguousarray(offsets, dtype=np.uint64)
-    n = off.size - 1
     S = int(segments)
-    t = np.zeros((KMER_CLASSES ** int(k), S), dtype=np.uint16) if table and k in (4, 5) and 1 <= S <= KMER_MAX_SEGMENTS else None
-    u = np.zeros(max(n, 1), dtype=np.uint64)
-    _check(lib.swg_debug_prune_kmer_seg(rp, qp, lq, int(gap_open), int(gap_extend), int(k), S, fp, off.ctypes.data_as(_vp), n,
-                                        t.ctypes.data_as(_vp) if t is not None else None, u.ctypes.data_as(_vp)))
-    return t, u[:n]
+    return _prune_kmer_mirror(lib.swg_debug_prune_kmer_seg, rows, query, gap_open, gap_extend, (int(k), S), flat, offsets,
+                              (KMER_CLASSES ** int(k), S) if table and k in (4, 5) and 1 <= S <= KMER_MAX_SEGMENTS else None)
 
 
 def debug_prune_kmer_choice_seg(forced=0, segments=0, pruned=1, lq=3000, pair_rows=1900000000, table_rate=0, fill_rate=0):
@@ -538,21 +534,9 @@ KMER_REFINE_SEGMENTS = 128
 def debug_prune_kmer_refine(rows, query, gap_open, gap_extend, segments, flat, offsets, table=True):
     """Test hook (no device needed): the second-level bound's host mirror -- debug_prune_kmer_seg at k = 4 over the
     `segments` (32, 64 or 128) segments the refine kernel walks.  -> (table uint16[22^4, segments] or None, U uint64[n])."""
-    r, rp = _i8(rows)
-    lq = r.size // 32
-    qp = None
-    if query is not None:
-        q, qp = _i8(query)
-        lq = q.size
-    f, fp = _i8(flat)
-    off = np.ascontiguousarray(offsets, dtype=np.uint64)
-    n = off.size - 1
     S = int(segments)
-    t = np.zeros((KMER_CLASSES ** 4, S), dtype=np.uint16) if table and S in (32, 64, 128) else None
-    u = np.zeros(max(n, 1), dtype=np.uint64)
-    _check(lib.swg_debug_prune_kmer_refine(rp, qp, lq, int(gap_open), int(gap_extend), S, fp, off.ctypes.data_as(_vp), n,
-                                           t.ctypes.data_as(_vp) if t is not None else None, u.ctypes.data_as(_vp)))
-    return t, u[:n]
+    return _prune_kmer_mirror(lib.swg_debug_prune_kmer_refine, rows, query, gap_open, gap_extend, (S,), flat, offsets,
+                              (KMER_CLASSES ** 4, S) if table and S in (32, 64, 128) else None)
 
 
 def debug_prune_refine_choice(forced=0, segments=0, refine=0, pruned=1, lq=3000, pair_rows=1900000000, table_rate=0, fill_rate=0):
@@ -611,6 +595,21 @@ def debug_prune_plan_above(**ask):
     out = np.zeros(2, dtype=np.int64)
     _check(lib.swg_debug_prune_plan_above(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
     return bool(out[0]), int(out[1])
+
+
+PRUNE_STAGE_QUEUED = ("threshold", "prefix_cut", "gate", "refine", "list")   # bits 0..4 of a stage's fourth word, in queue order
+
+
+def debug_prune_stages(segments, head_pairs=0, fixed=False, refine=0, prefix_cut=False):
+    """Test hook (no device needed): the stages of a pruned fill over the pair ranges `segments` [(begin, end), ...] and
+    what is queued in front of each (swg_prune_stages) -> [(begin, end, segment index, names of PRUNE_STAGE_QUEUED), ...].
+    head_pairs, fixed (a caller's threshold), refine (the second level's segments, 0: none) and prefix_cut are the plan's."""
+    a = np.array([head_pairs, fixed, refine, prefix_cut, len(segments)] + [int(v) for sg in segments for v in sg], dtype=np.int64)
+    out = np.zeros((2 * len(segments) + 1, 4), dtype=np.int64)
+    n = C.c_size_t(0)
+    _check(lib.swg_debug_prune_stages(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp), out.shape[0], C.byref(n)))
+    return [(int(b), int(e), int(sg), tuple(name for i, name in enumerate(PRUNE_STAGE_QUEUED) if int(qd) >> i & 1))
+            for b, e, sg, qd in out[:n.value]]
 
 
 LAUNCH_FAMILIES = ("dyn", "lists", "q32", "qq", "streams", "systolic")

@@ -58,6 +58,19 @@ int swg_set_ctx_error(swg_ctx *ctx, int code, const char *fmt, ...)
                                      __FILE__, __LINE__);                                       \
     } while (0)
 
+// A device buffer that grows: room for `need` entries (and `extra` more that the capacity does not count), what it held
+// is gone when it had to be allocated anew.
+template <class T> static int device_grow(swg_ctx *ctx, T **d, size_t *cap, size_t need, size_t extra = 0)
+{
+    if (*d && *cap >= need) return SWG_OK;
+    (void)hipFree(*d);
+    *d = nullptr;
+    *cap = 0;
+    HIP_TRY(ctx, hipMalloc(d, std::max<size_t>(16, (need + extra) * sizeof(T))));
+    *cap = need;
+    return SWG_OK;
+}
+
 // Wait for everything queued on the stream by polling an event from user space.  A blocking
 // hipStreamSynchronize may put the thread to sleep; on a busy host the wake-up alone can cost
 // milliseconds per search, several times the fill itself.
@@ -241,9 +254,9 @@ extern "C" void swg_destroy(swg_ctx *ctx)
     (void)hipFree(ctx->d_query);
     (void)hipFree(ctx->d_pssm);
     (void)hipFree(ctx->d_kmer_cprof);
-    (void)hipFree(ctx->d_kmer_table[0]);
-    (void)hipFree(ctx->d_kmer_table[1]);
-    (void)hipFree(ctx->d_kmer_refine);
+    (void)hipFree(ctx->kmer_first[0].d);
+    (void)hipFree(ctx->kmer_first[1].d);
+    (void)hipFree(ctx->kmer_second.d);
     (void)hipFree(ctx->d_profile[0]);
     (void)hipFree(ctx->d_profile[1]);
     (void)hipFree(ctx->d_profile[2]);
@@ -1130,11 +1143,158 @@ static void dyn_batch_zones(const swg_ctx *ctx, const SwgPairTokens &T, SwgDiagD
     q->batch_B = B;
 }
 
+// One class's fill off the work queue, launch by launch: what every launch of the class shares (dyn_fill_begin sets it
+// up), and the launch itself.  The pruned and the unpruned loop both go through launch().
+struct DynFill {
+    swg_ctx *ctx;
+    const swg_db *db;
+    const SwgDiagWork &wk;
+    int c;
+    SwgDiagDynParams q;
+    hipStream_t qs = nullptr;
+    int form = 0;
+    bool edges = false, fma = false, cut = false;
+    size_t slice = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> segs; // pair ranges (token_segments)
+    bool first_launch = true;
+    int launches = 0, f16_launches = 0;
+
+    // one launch: pass `pass` over the pairs [b, en) of segment sg on the cells pform
+    int launch(int pass, const std::pair<uint32_t, uint32_t> &sg, uint32_t b, uint32_t en, int pform, const uint8_t *prof, bool f16_part)
+    {
+        const SwgDiagPlan &pl = wk.plan[c];
+        const SwgPairTokens &T = db->ptok;
+        // one launch per pass: the kernel boundary is what lets any lane group take any pair
+        q.profile = prof + (size_t)pass * slice;
+        q.edge_in = pass > 0 ? T.d_edge[(pass - 1) & 1] : nullptr;
+        q.edge_out = pass + 1 < pl.npass ? T.d_edge[pass & 1] : nullptr;
+        if (!first_launch)
+            HIP_TRY(ctx, hipMemsetAsync(q.queue, 0, (size_t)SWG_DYN_SHARDS * SWG_DYN_SHARD_STRIDE * 4, qs));
+        first_launch = false;
+        q.q_begin = b;
+        q.q_end = en;
+        if (cut) {
+            q.seg_origin = T.pair_blocks_prefix[sg.first];
+            q.seg_blocks = T.pair_blocks_prefix[sg.second] - q.seg_origin;
+        }
+        const int variant = pass + 1 == pl.npass && pl.npass > 1 && pl.last_variant >= 0 ? pl.last_variant : pl.variant;
+        const int wgs_c = diag_class_workgroups(ctx, db, wk, c);
+        // (with long_helps the long class's kernel reads the bulk's counters too, as single pairs: no zones then)
+        if (!(ctx->opt_long_helps && wk.n_classes == 2)) dyn_batch_zones(ctx, T, &q, (uint64_t)wgs_c * pl.W * (64 / pl.G), swg_diag_variant_info(variant).K, pl.G, pform);
+        HIP_TRY(ctx, swg_launch_diag_dyn(variant, edges, pform, pl.W, wgs_c, q, qs, 1, fma));
+        ++launches;
+        if (f16_part) ++f16_launches;
+        return SWG_OK;
+    }
+};
+
+static int dyn_fill_begin(DynFill *F, int go, int ge, uint64_t *d_trace)
+{
+    swg_ctx *ctx = F->ctx;
+    const swg_db *db = F->db;
+    const SwgDiagWork &wk = F->wk;
+    const int c = F->c;
+    const SwgDiagPlan &pl = wk.plan[c];
+    const SwgPairTokens &T = db->ptok;
+    SwgDiagDynParams &q = F->q;
+    F->form = diag_class_form(ctx, db, pl);
+    q = dyn_params_base(T, db->d_scores, (size_t)db->n_bins * SWG_BIN, pl.G, F->form, go, ge, wk.n_classes, db->d_counters + SWG_RANK_WORD(c));
+    q.q_begin = (uint32_t)wk.pair_begin[c];
+    q.q_end = (uint32_t)wk.pair_end[c];
+    q.queue = db->d_counters + SWG_QUEUE_WORD(c); // zeroed with the other counters before the fill
+    q.profile = ctx->d_profile[diag_profile_slot(pl, c)];
+    // the long class always runs at raised priority; in the bulk, a pair that alone is well
+    // above an average lane group's whole share
+    auto bulk_prio = [&]() -> uint32_t {
+        const uint64_t blocks = T.pair_blocks_prefix[wk.pair_end[0]] - T.pair_blocks_prefix[wk.pair_begin[0]];
+        return bulk_prio_blocks(ctx, blocks, (uint64_t)diag_class_workgroups(ctx, db, wk, 0) * wk.plan[0].W * (64 / wk.plan[0].G));
+    };
+    q.prio_blocks = c == 1 ? 0u : bulk_prio();
+    if (c == 1 && ctx->opt_long_helps && diag_class_is_dynamic(ctx, db, wk.plan[0])) {
+        // when the long pairs are done their lane groups go on with the bulk's queue
+        q.q2_begin = (uint32_t)wk.pair_begin[0];
+        q.q2_end = (uint32_t)wk.pair_end[0];
+        q.queue2 = db->d_counters + SWG_QUEUE_WORD(0);
+        q.prio_blocks2 = bulk_prio();
+    }
+    // (f16 sums round to nearest: a computed 32768 needs a true score within a few units of it)
+    q.f16_wipe = ctx->cur->plan.score_bound >= 32000ull ? 1u : 0u;
+    q.trace = d_trace;
+    q.stamps = pl.npass == 1 ? reinterpret_cast<unsigned long long *>(db->d_counters + SWG_WORD_STAMPS(c)) : nullptr; // (single-pass launches only)
+    F->edges = pl.npass > 1 || F->form == 1;
+    F->fma = diag_class_fma(ctx, db, pl); // (never with a split: its f16 part takes the v_perm_b32 profile)
+    F->slice = swg_diag_slice_bytes(pl.K, pl.G, F->fma);
+    F->qs = c == 1 ? ctx->stream2 : ctx->stream;
+    if (!token_segments(T, q.q_begin, q.q_end, ctx->opt_seg_blocks, F->edges, &F->segs, &F->cut))
+        return swg_set_ctx_error(ctx, SWG_ERR_ARG, "a pair of sequences too long for the multi-pass fill");
+    q.seg_origin = 0;
+    q.seg_blocks = (uint32_t)std::min<uint64_t>(T.total_blocks, ctx->opt_seg_blocks);
+    if (F->cut) {
+        q.q2_begin = q.q2_end = 0; // (the other class's pairs lie outside a segment)
+        q.queue2 = nullptr;
+    }
+    return SWG_OK;
+}
+
+// The fill of a pruned search, stage by stage -- all passes of a stage, then the threshold so far and the
+// next stage's cut, all on the fill's stream with no host wait.  The bound of every pair first; then the stages of
+// swg_prune_stages, each behind what that list queues in front of it and nothing else: the K-th best score so far (every
+// entry of d_scores is at most its sequence's true score at a kernel boundary) or, once, a caller's threshold; then the
+// stage's cut, held for all its passes.
+// A cut stage's launches are LIST launches: the kernel reads the list's device-side length once at entry, leaves before
+// it loads the profile when it is 0, and hands out exactly those pairs in every pass (no batch claims in list mode).  So
+// the fill kernels are the unpruned search's, instruction for instruction.  The prefix cut's list is the pair ids in
+// order, from the stage's first pair, and its length is the cut.  Pair by pair (the default): the second-level bound of
+// the stage's pairs that still reach the threshold, then the stage's own list -- the ids of its pairs whose bound reaches
+// T, in order.  Under a caller's threshold the first of SEVERAL stages -- the longest pairs, whose bounds stand furthest
+// above any T -- is walked a second time only where the first level cut an eighth of it: the gate's word is its T.
+// (The tables are this epoch's: prepare_prune queued their builds on this stream.)
+static int enqueue_pruned_fill(swg_ctx *ctx, swg_db *db, const SwgPrunePlan &pr, size_t k, DynFill *F)
+{
+    const SwgPairTokens &T = db->ptok;
+    const SwgDiagPlan &pl = F->wk.plan[F->c];
+    hipStream_t qs = F->qs;
+    uint32_t *thr = db->d_counters + SWG_PRUNE_WORD_T, *cut_word = db->d_counters + SWG_PRUNE_WORD_CUT, *gate = db->d_counters + SWG_PRUNE_WORD_GATE;
+    const uint32_t n_pairs = (uint32_t)swg_db_pair_count(db);
+    const SwgPruneLayout L = swg_prune_layout(db->d_pair_bound, n_pairs);
+    if (pr.kmer > 1 && pr.segments > 1)
+        HIP_TRY(ctx, swg_launch_pair_bound_kmer_seg(T.d_tok, T.d_pair_off, n_pairs, pr.kmer, (uint32_t)pr.segments, ctx->prune_colmax, ctx->kmer_first[pr.kmer - 4].d,
+                                                    L.bounds, L.ids, qs));
+    else if (pr.kmer > 1)
+        HIP_TRY(ctx, swg_launch_pair_bound_kmer(T.d_tok, T.d_pair_off, n_pairs, pr.kmer, ctx->prune_colmax, ctx->kmer_first[pr.kmer - 4].d, L.bounds, L.ids, qs));
+    else
+        HIP_TRY(ctx, swg_launch_pair_bound(T.d_tok, T.d_pair_off, n_pairs, ctx->prune_colmax, L.bounds, L.ids, qs));
+    if (pr.fixed) HIP_TRY(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(thr), (int)pr.fixed_T, 1, qs));
+    db->prune_stages.clear(); // (the stages cut pair by pair, for the tests)
+    for (const SwgPruneStage &st : swg_prune_stages(pr, F->segs)) {
+        if (st.queued & SWG_STAGE_THRESHOLD)
+            HIP_TRY(ctx, swg_launch_prune_threshold(db->d_scores, db->d_order, (uint32_t)((size_t)db->n_bins * SWG_BIN), (uint32_t)k, db->d_hist, thr, qs));
+        if (st.queued & SWG_STAGE_PREFIX_CUT) HIP_TRY(ctx, swg_launch_prune_cut(L.bounds, T.d_pair_off, st.begin, st.end, thr, cut_word, qs));
+        if (st.queued & SWG_STAGE_GATE) HIP_TRY(ctx, swg_launch_prune_refine_gate(L.bounds, st.begin, st.end, thr, gate, qs));
+        if (st.queued & SWG_STAGE_REFINE)
+            HIP_TRY(ctx, swg_launch_pair_bound_refine(T.d_tok, T.d_pair_off, st.begin, st.end, (uint32_t)pr.refine, ctx->prune_colmax, ctx->kmer_second.d,
+                                                      st.queued & SWG_STAGE_GATE ? gate : thr, L.bounds, qs));
+        if (st.queued & SWG_STAGE_LIST) {
+            const size_t rec = db->prune_stages.size() / 2;
+            HIP_TRY(ctx, swg_launch_prune_list(L.bounds, T.d_pair_off, st.begin, st.end, thr, L.tiles, L.lists + st.begin, cut_word,
+                                               rec < SWG_PRUNE_STAGE_RECS ? L.recs + 2 * rec : nullptr, qs));
+            db->prune_stages.push_back(st.begin), db->prune_stages.push_back(st.end);
+        }
+        F->q.list = st.queued & SWG_STAGE_PREFIX_CUT ? L.ids + st.begin : st.queued & SWG_STAGE_LIST ? L.lists + st.begin : nullptr;
+        F->q.list_count = F->q.list ? cut_word : nullptr;
+        for (int pass = 0; pass < pl.npass; ++pass) {
+            const int rc = F->launch(pass, F->segs[st.segment], st.begin, st.end, F->form, ctx->d_profile[diag_profile_slot(pl, F->c)], false);
+            if (rc != SWG_OK) return rc;
+        }
+    }
+    F->q.list = nullptr, F->q.list_count = nullptr;
+    return SWG_OK;
+}
+
 // Launches the fill of one work plan.  Events: ev[1] before, ev[2] after on the main stream;
 // with a long class also ev[5] (bulk end) and ev[7] (long end).
-// prune (or null: the whole range, pass by pass): a pruned search runs stage by stage -- all passes of a
-// stage, then the threshold so far and the next stage's cut, both on the fill's stream with no host wait.
-static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, int go, int ge, bool *two_ends,
+// prune (or null: the whole range, pass by pass): a pruned search runs stage by stage (enqueue_pruned_fill).
+static int launch_diag(swg_ctx *ctx, swg_db *db, const SwgDiagWork &wk, int go, int ge, bool *two_ends,
                        const SwgPrunePlan *prune = nullptr, size_t prune_k = 0)
 {
     hipStream_t s = ctx->stream;
@@ -1157,172 +1317,37 @@ static int launch_diag(swg_ctx *ctx, const swg_db *db, const SwgDiagWork &wk, in
         const SwgDiagLayout &L = db->diag[c];
         const SwgDiagPlan &pl = wk.plan[c];
         if (diag_class_is_dynamic(ctx, db, pl)) {
-            const SwgPairTokens &T = db->ptok;
-            const int form = diag_class_form(ctx, db, pl);
-            SwgDiagDynParams q = dyn_params_base(T, db->d_scores, (size_t)db->n_bins * SWG_BIN, pl.G, form, go, ge, wk.n_classes,
-                                                 db->d_counters + SWG_RANK_WORD(c));
-            q.q_begin = (uint32_t)wk.pair_begin[c];
-            q.q_end = (uint32_t)wk.pair_end[c];
-            q.queue = db->d_counters + SWG_QUEUE_WORD(c); // zeroed with the other counters before the fill
-            q.profile = ctx->d_profile[diag_profile_slot(pl, c)];
-            // the long class always runs at raised priority; in the bulk, a pair that alone is well
-            // above an average lane group's whole share
-            auto bulk_prio = [&]() -> uint32_t {
-                const uint64_t blocks = T.pair_blocks_prefix[wk.pair_end[0]] - T.pair_blocks_prefix[wk.pair_begin[0]];
-                return bulk_prio_blocks(ctx, blocks, (uint64_t)diag_class_workgroups(ctx, db, wk, 0) * wk.plan[0].W * (64 / wk.plan[0].G));
-            };
-            q.prio_blocks = c == 1 ? 0u : bulk_prio();
-            if (c == 1 && ctx->opt_long_helps && diag_class_is_dynamic(ctx, db, wk.plan[0])) {
-                // when the long pairs are done their lane groups go on with the bulk's queue
-                q.q2_begin = (uint32_t)wk.pair_begin[0];
-                q.q2_end = (uint32_t)wk.pair_end[0];
-                q.queue2 = db->d_counters + SWG_QUEUE_WORD(0);
-                q.prio_blocks2 = bulk_prio();
-            }
-            // (f16 sums round to nearest: a computed 32768 needs a true score within a few units of it)
-            q.f16_wipe = ctx->cur->plan.score_bound >= 32000ull ? 1u : 0u;
-            q.trace = d_trace[c];
-            // start / end wall-clock stamps of single-pass launches: words 8..15 of the counters
-            q.stamps = pl.npass == 1 ? reinterpret_cast<unsigned long long *>(db->d_counters + 8 + 4 * c) : nullptr;
-            const bool edges = pl.npass > 1 || form == 1;
-            const bool fma = diag_class_fma(ctx, db, pl); // (never with a split: its f16 part takes the v_perm_b32 profile)
-            const size_t slice = swg_diag_slice_bytes(pl.K, pl.G, fma);
-            hipStream_t qs = c == 1 ? ctx->stream2 : s;
-            std::vector<std::pair<uint32_t, uint32_t>> segs; // pair ranges (token_segments)
-            bool cut = false;
-            if (!token_segments(T, q.q_begin, q.q_end, ctx->opt_seg_blocks, edges, &segs, &cut))
-                return swg_set_ctx_error(ctx, SWG_ERR_ARG, "a pair of sequences too long for the multi-pass fill");
-            q.seg_origin = 0;
-            q.seg_blocks = (uint32_t)std::min<uint64_t>(T.total_blocks, ctx->opt_seg_blocks);
-            if (cut) {
-                q.q2_begin = q.q2_end = 0; // (the other class's pairs lie outside a segment)
-                q.queue2 = nullptr;
-            }
+            DynFill F{ctx, db, wk, c};
+            int rc = dyn_fill_begin(&F, go, ge, d_trace[c]);
+            if (rc != SWG_OK) return rc;
             // Both 16-bit forms in one class (pl.f16_from, see plan_search): the pairs before it -- the longest --
             // take all their passes on the wide form, then the rest theirs on the f16 cells, the same geometry
             // throughout; ev[5] between the two parts tells their times apart.
-            const uint32_t class_begin = q.q_begin, class_end = q.q_end;
-            const bool split = c == 0 && wk.n_classes == 1 && form != 2 && pl.f16_from > class_begin && pl.f16_from < class_end;
-            bool first_launch = true;
-            int launches = 0, f16_launches = 0;
+            const uint32_t class_begin = F.q.q_begin, class_end = F.q.q_end;
+            const bool split = c == 0 && wk.n_classes == 1 && F.form != 2 && pl.f16_from > class_begin && pl.f16_from < class_end;
             // (plan_prune decided; what swg_prune_last reports is what was launched)
             const bool pruned = prune && prune->on && c == 0 && wk.n_classes == 1 && !split && db->d_pair_bound;
             if (c == 0) ctx->cur->pruned = pruned;
-            // one launch: pass `pass` over the pairs [b, en) of segment sg on the cells pform
-            auto launch_one = [&](int pass, const std::pair<uint32_t, uint32_t> &sg, uint32_t b, uint32_t en, int pform, const uint8_t *prof,
-                                  bool f16_part) -> int {
-                // one launch per pass: the kernel boundary is what lets any lane group take any pair
-                q.profile = prof + (size_t)pass * slice;
-                q.edge_in = pass > 0 ? T.d_edge[(pass - 1) & 1] : nullptr;
-                q.edge_out = pass + 1 < pl.npass ? T.d_edge[pass & 1] : nullptr;
-                if (!first_launch)
-                    HIP_TRY(ctx, hipMemsetAsync(q.queue, 0, (size_t)SWG_DYN_SHARDS * SWG_DYN_SHARD_STRIDE * 4, qs));
-                first_launch = false;
-                q.q_begin = b;
-                q.q_end = en;
-                if (cut) {
-                    q.seg_origin = T.pair_blocks_prefix[sg.first];
-                    q.seg_blocks = T.pair_blocks_prefix[sg.second] - q.seg_origin;
-                }
-                const int variant = pass + 1 == pl.npass && pl.npass > 1 && pl.last_variant >= 0 ? pl.last_variant : pl.variant;
-                const int wgs_c = diag_class_workgroups(ctx, db, wk, c);
-                // (with long_helps the long class's kernel reads the bulk's counters too, as single pairs: no zones then)
-                if (!(ctx->opt_long_helps && wk.n_classes == 2)) dyn_batch_zones(ctx, T, &q, (uint64_t)wgs_c * pl.W * (64 / pl.G), swg_diag_variant_info(variant).K, pl.G, pform);
-                HIP_TRY(ctx, swg_launch_diag_dyn(variant, edges, pform, pl.W, wgs_c, q, qs, 1, fma));
-                ++launches;
-                if (f16_part) ++f16_launches;
-                return SWG_OK;
-            };
             if (pruned) {
-                // The stages: the segments, or the head and the rest of a single one.  The bound of every pair first;
-                // then, before each stage but the first, the K-th best score so far (every entry of d_scores is at most
-                // its sequence's true score at a kernel boundary) and the stage's cut, held for all its passes.
-                // A cut stage's launches are LIST launches: the list is the pair ids in order, from the stage's first
-                // pair, and its device-side length is the cut -- the kernel reads it once at entry, leaves before it
-                // loads the profile when it is 0, and hands out exactly those pairs in every pass (no batch claims in
-                // list mode).  So the fill kernels are the unpruned search's, instruction for instruction.
-                // Pair by pair (the default): behind the threshold, the second-level bound of the stage's pairs that still
-                // reach it (prune->refine), then the stage's own list -- the ids of its pairs whose bound reaches T, in
-                // order -- and its length; both held for all the stage's passes like the prefix cut.
-                uint32_t *cw = db->d_counters;
-                const uint32_t n_pairs_all = (uint32_t)swg_db_pair_count(db);
-                uint32_t *d_ids = db->d_pair_bound + n_pairs_all, *d_lists = d_ids + n_pairs_all, *d_tiles = d_lists + n_pairs_all;
-                uint32_t *d_recs = d_tiles + swg_prune_tile_words(n_pairs_all);
-                std::vector<uint32_t> cut_stages;
-                if (prune->kmer > 1 && prune->segments > 1) // (the table of this epoch: plan_prune queued its build on this stream)
-                    HIP_TRY(ctx, swg_launch_pair_bound_kmer_seg(T.d_tok, T.d_pair_off, n_pairs_all, prune->kmer, (uint32_t)prune->segments, ctx->prune_colmax,
-                                                                ctx->d_kmer_table[prune->kmer - 4], db->d_pair_bound, d_ids, qs));
-                else if (prune->kmer > 1)
-                    HIP_TRY(ctx, swg_launch_pair_bound_kmer(T.d_tok, T.d_pair_off, n_pairs_all, prune->kmer, ctx->prune_colmax, ctx->d_kmer_table[prune->kmer - 4], db->d_pair_bound,
-                                                            d_ids, qs));
-                else
-                    HIP_TRY(ctx, swg_launch_pair_bound(T.d_tok, T.d_pair_off, n_pairs_all, ctx->prune_colmax, db->d_pair_bound, d_ids, qs));
-                struct Stage { uint32_t b, en; size_t sg; };
-                std::vector<Stage> stages;
-                // A caller's threshold (prune->fixed: swg_search_above) is written once, here, and no threshold kernel runs:
-                // every stage, the first included, is cut at it, and a range of one segment is one stage.
-                if (prune->fixed) HIP_TRY(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cw + SWG_PRUNE_WORD_T), (int)prune->fixed_T, 1, qs));
-                for (size_t i = 0; i < segs.size(); ++i) {
-                    const uint32_t mid = segs.size() == 1 && prune->head_pairs > 0 ? std::min(segs[i].second, segs[i].first + prune->head_pairs) : segs[i].second;
-                    stages.push_back(Stage{segs[i].first, mid, i});
-                    if (mid < segs[i].second) stages.push_back(Stage{mid, segs[i].second, i});
-                }
-                for (size_t si = 0; si < stages.size(); ++si) {
-                    const Stage &st = stages[si];
-                    q.list = nullptr, q.list_count = nullptr;
-                    if (si > 0 || prune->fixed) {
-                        if (!prune->fixed)
-                            HIP_TRY(ctx, swg_launch_prune_threshold(db->d_scores, db->d_order, (uint32_t)((size_t)db->n_bins * SWG_BIN), (uint32_t)prune_k,
-                                                                    db->d_hist, cw + SWG_PRUNE_WORD_T, qs));
-                        if (prune->prefix_cut) {
-                            HIP_TRY(ctx, swg_launch_prune_cut(db->d_pair_bound, T.d_pair_off, st.b, st.en, cw + SWG_PRUNE_WORD_T, cw + SWG_PRUNE_WORD_CUT, qs));
-                            q.list = d_ids + st.b;
-                        } else {
-                            // (the table of this epoch: plan_prune queued its build on this stream.  Under a caller's threshold
-                            // the first of SEVERAL stages -- the longest pairs, whose bounds stand furthest above any T -- is
-                            // walked a second time only where the first level cut an eighth of it: the gate's word is its T)
-                            const uint32_t *refine_thr = cw + SWG_PRUNE_WORD_T;
-                            if (prune->refine && prune->fixed && si == 0 && stages.size() > 1) {
-                                HIP_TRY(ctx, swg_launch_prune_refine_gate(db->d_pair_bound, st.b, st.en, cw + SWG_PRUNE_WORD_T, cw + SWG_PRUNE_WORD_GATE, qs));
-                                refine_thr = cw + SWG_PRUNE_WORD_GATE;
-                            }
-                            if (prune->refine)
-                                HIP_TRY(ctx, swg_launch_pair_bound_refine(T.d_tok, T.d_pair_off, st.b, st.en, (uint32_t)prune->refine, ctx->prune_colmax, ctx->d_kmer_refine,
-                                                                          refine_thr, db->d_pair_bound, qs));
-                            const size_t rec = cut_stages.size() / 2;
-                            HIP_TRY(ctx, swg_launch_prune_list(db->d_pair_bound, T.d_pair_off, st.b, st.en, cw + SWG_PRUNE_WORD_T, d_tiles, d_lists + st.b,
-                                                               cw + SWG_PRUNE_WORD_CUT, rec < SWG_PRUNE_STAGE_RECS ? d_recs + 2 * rec : nullptr, qs));
-                            q.list = d_lists + st.b;
-                            cut_stages.push_back(st.b), cut_stages.push_back(st.en);
-                        }
-                        q.list_count = cw + SWG_PRUNE_WORD_CUT;
-                    }
-                    for (int pass = 0; pass < pl.npass; ++pass) {
-                        const int rc1 = launch_one(pass, segs[st.sg], st.b, st.en, form, ctx->d_profile[diag_profile_slot(pl, c)], false);
-                        if (rc1 != SWG_OK) return rc1;
-                    }
-                }
-                q.list = nullptr, q.list_count = nullptr;
-                const_cast<swg_db *>(db)->prune_stages.swap(cut_stages);
+                if ((rc = enqueue_pruned_fill(ctx, db, *prune, prune_k, &F)) != SWG_OK) return rc;
             } else
             for (int part = 0; part < (split ? 2 : 1); ++part) {
-                const int pform = split && part == 1 ? 2 : form;
+                const int pform = split && part == 1 ? 2 : F.form;
                 const uint32_t part_begin = split && part == 1 ? pl.f16_from : class_begin;
                 const uint32_t part_end = split && part == 0 ? pl.f16_from : class_end;
                 const uint8_t *prof = ctx->d_profile[split && part == 1 ? 7 : diag_profile_slot(pl, c)];
-                q.go = gap_word(pform, go);
-                q.ge = gap_word(pform, ge);
-                if (split && part == 1) HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[5], qs));
+                F.q.go = gap_word(pform, go);
+                F.q.ge = gap_word(pform, ge);
+                if (split && part == 1) HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[5], F.qs));
                 for (int pass = 0; pass < pl.npass; ++pass) {
-                    for (const std::pair<uint32_t, uint32_t> &sg : segs) {
+                    for (const std::pair<uint32_t, uint32_t> &sg : F.segs) {
                         const uint32_t b = std::max(sg.first, part_begin), en = std::min(sg.second, part_end);
                         if (b >= en) continue;
-                        const int rc1 = launch_one(pass, sg, b, en, pform, prof, split && part == 1);
-                        if (rc1 != SWG_OK) return rc1;
+                        if ((rc = F.launch(pass, sg, b, en, pform, prof, split && part == 1)) != SWG_OK) return rc;
                     }
                 }
             }
-            if (c == 0) ctx->cur->fill_launches = launches, ctx->cur->fill_f16_launches = f16_launches;
+            if (c == 0) ctx->cur->fill_launches = F.launches, ctx->cur->fill_f16_launches = F.f16_launches;
             continue;
         }
         SwgDiagParams d;
@@ -1409,7 +1434,7 @@ static int launch_systolic(swg_ctx *ctx, const swg_db *db, const SwgSystolicPlan
     hipStream_t s = ctx->stream;
     SwgFillParams p = fill_params_base(ctx, db);
     p.profile = ctx->d_profile[pl.bits == 16 ? 0 : 1];
-    p.queue = db->d_counters + 0;
+    p.queue = db->d_counters + SWG_WORD_WORK_QUEUE;
     p.n_items = pl.bits == 16 ? db->n_bins : db->n_bins * 2;
     p.npass = (uint32_t)pl.npass;
     if (pl.bits == 16 && pl.f16) {
@@ -2295,211 +2320,8 @@ extern "C" int swg_debug_systolic_variants(int bits, int32_t *out, size_t cap)
     return n;
 }
 
-// Profiles, scratch and the bin image of a planned search.
-static int prepare_search(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P)
-{
-    int rc = SWG_OK;
-    const bool systolic_fill = !P.use_diag && !P.use_q32 && !(P.bits == 32 && P.use_diag32);
-    const bool systolic_rescore = P.may_saturate && !P.use_diag32;
-    const size_t bin32_scratch = P.bin32 && P.npass32 > 1 ? ((size_t)db->max_nblk * 4 + 4) * 4 * 16 * (size_t)ctx->n_cu : 0; // dwords: one uint4 per stream row
-    if (P.bin32) {
-        rc = ensure_profile_cols(ctx, 1, (uint32_t)(P.npass32 * 64 * SWG_DIAG32_K), 4, (1ull << 30) ^ (uint64_t)P.npass32);
-        if (rc != SWG_OK) return rc;
-        if ((rc = ensure_scratch(ctx, bin32_scratch)) != SWG_OK) return rc;
-    }
-    if (P.use_diag) rc = prepare_diag(ctx, db, P.wk);
-    else if (systolic_fill) rc = ensure_profile(ctx, P.main_pl);
-    // (the int32 work-queue fill builds its profiles at the launch)
-    if (rc != SWG_OK) return rc;
-    if (systolic_rescore && (rc = ensure_profile(ctx, P.re_pl)) != SWG_OK) return rc;
-    size_t need = bin32_scratch;
-    if (systolic_fill && P.main_pl.npass > 1)
-        need = std::max(need, (size_t)P.main_pl.workgroups * db->max_nblk * SWG_ROWS_PER_BLK * 64 * P.main_pl.info.nb);
-    if (systolic_rescore && P.re_pl.npass > 1)
-        need = std::max(need, (size_t)P.re_pl.workgroups * db->max_nblk * SWG_ROWS_PER_BLK * 64 * P.re_pl.info.nb);
-    if ((rc = ensure_scratch(ctx, need)) != SWG_OK) return rc;
-    // the systolic engine and the bin-based int32 kernel read the bin image (built on the device on first use)
-    if ((!P.use_diag && !P.use_q32) || (P.int32_level && !P.q32_ok)) return ensure_bins(ctx, db);
-    return SWG_OK;
-}
-
-// The first level on the main stream: the diagonal engine, the int32 work queue, the bin-based int32 kernel or the
-// systolic engine (events ev[0] before the buffers are cleared, ev[1] .. ev[2] around the fill).
-static int enqueue_fill(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P, SwgSlot *S)
-{
-    hipStream_t s = ctx->stream;
-    const size_t n_slots = (size_t)db->n_bins * SWG_BIN;
-    HIP_TRY(ctx, hipEventRecord(S->ev[0], s));
-    HIP_TRY(ctx, swg_launch_zero2(db->d_scores, n_slots * 4, db->d_counters, SWG_COUNTER_BYTES, s)); // (one launch, not two memsets)
-    S->two_ends = false;
-    S->fill_launches = 0;
-    S->pruned = false;
-    if (P.use_diag) return launch_diag(ctx, db, P.wk, P.go, P.ge, &S->two_ends, &P.prune, S->k);
-    if (P.use_q32)
-        return launch_q32(ctx, db, P.wk32, P.go, P.ge, nullptr, nullptr, 0, db->d_counters + SWG_QUEUE_WORD(0), &S->two_ends, true, P.exact32);
-    if (!(P.bits == 32 && P.use_diag32)) return launch_systolic(ctx, db, P.main_pl, P.go, P.ge);
-    SwgFillParams p = fill_params_base(ctx, db);
-    p.profile = ctx->d_profile[1];
-    p.queue = db->d_counters + 0;
-    p.n_items = (uint32_t)n_slots;
-    p.npass = (uint32_t)P.npass32;
-    p.go = P.go;
-    p.ge = P.ge;
-    p.scratch_wg_dwords = ((uint64_t)db->max_nblk * 4 + 4) * 4;
-    HIP_TRY(ctx, hipEventRecord(S->ev[1], s));
-    HIP_TRY(ctx, swg_launch_diag32(16, (int)std::min<size_t>((size_t)ctx->n_cu, (n_slots + 15) / 16), p, s));
-    HIP_TRY(ctx, hipEventRecord(S->ev[2], s));
-    return SWG_OK;
-}
-
-// The levels behind the first: the pairs the f16 cells flagged are collected and run again on int16 cells, then what
-// saturated the last 16-bit level is collected and re-scored in int32 (event ev[3] at the end).
-static int enqueue_rescore(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P, SwgSlot *S)
-{
-    hipStream_t s = ctx->stream;
-    const size_t lq = ctx->query_len();
-    const size_t n_slots = (size_t)db->n_bins * SWG_BIN;
-    const bool some_f16 = P.some_f16();
-    int rc = SWG_OK;
-    uint32_t *seq_list = db->d_list;
-    if (P.may_saturate && some_f16) {
-        // counters [17] = flagged pairs (the list's length), [16] = flagged sequences, [6] = their rows / 16 (the veto's input)
-        HIP_TRY(ctx, swg_launch_collect_flagged_pairs(db->d_scores, P.split_at, (uint32_t)(n_slots / 2), SWG_F16_CEILING, db->d_list, db->d_counters + 17,
-                                                      db->d_counters + 16, db->d_lens, db->d_counters + 6, s));
-        SwgDiagPlan lp;
-        const uint32_t guess = db->sat_hint > 0 ? (uint32_t)std::min<long long>(db->sat_hint, 1ll << 30) : 1u;
-        if (!i16_list_plan(ctx->n_cu, lq, guess, P.wk.plan[0], &lp)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "no geometry for the int16 re-run");
-        HIP_TRY(ctx, hipMemsetAsync(db->d_counters + SWG_QUEUE_WORD(0), 0, (size_t)(SWG_COUNTER_BYTES - SWG_QUEUE_WORD(0) * 4u), s));
-        if ((rc = launch_dyn_list(ctx, db, lp, P.rerun_wide, P.go, P.ge, db->d_list, db->d_counters + 17, s)) != SWG_OK) return rc;
-        seq_list = db->d_list + n_slots; // (the pair list keeps the first half)
-    }
-    if (P.int32_level) {
-        // counters [1] = saturated sequences (the list's length), [6] = their rows in units of 16
-        HIP_TRY(ctx, swg_launch_collect_saturated(db->d_scores, (uint32_t)n_slots, P.level_ceiling, seq_list, db->d_counters + 1,
-                                                  some_f16 ? nullptr : db->d_lens, db->d_counters + 6, s));
-        SwgFillParams p = fill_params_base(ctx, db);
-        p.profile = ctx->d_profile[1];
-        p.queue = db->d_counters + 2;
-        p.list = seq_list;
-        p.list_count = db->d_counters + 1;
-        p.go = P.go32; // (the first level's gap scores, except in a gapless search: see plan_search)
-        p.ge = P.ge32;
-        SwgDiagWork wkl;
-        // The work-queue re-score reads the count on the device and leaves at once when it is zero, so it is queued
-        // behind every fill that may flag something and the host never waits for the count in the middle of a
-        // search (it did until round 3: a round trip per search, and the end of the two-deep pipeline of
-        // swg_search_begin).  Only its lane-group width is a guess -- few flagged sequences get 64 lanes each,
-        // many the narrowest group that covers the query -- made from what the last search of this database saw.
-        const uint32_t guess = !some_f16 && db->sat_hint > 0 ? (uint32_t)std::min<long long>(db->sat_hint, 1ll << 30) : 1u;
-        if (P.use_diag32 && P.q32_ok && q32_list_plan(ctx, lq, guess, &wkl)) {
-            // (fresh queue counters and rank table: the fill's are spent; no events of its own: the
-            // re-score is timed as ev[2] .. ev[3] like the other re-score forms)
-            HIP_TRY(ctx, hipMemsetAsync(db->d_counters + SWG_QUEUE_WORD(0), 0,
-                                        (size_t)(SWG_COUNTER_BYTES - SWG_QUEUE_WORD(0) * 4u), s));
-            bool two = false;
-            rc = launch_q32(ctx, db, wkl, P.go32, P.ge32, seq_list, db->d_counters + 1, std::max<uint32_t>(2u * guess, 4096u),
-                            db->d_counters + SWG_QUEUE_WORD(0), &two, false);
-            if (rc != SWG_OK) return rc;
-        } else if (P.use_diag32) {
-            // the bin-based kernel (positive gap scores never get here; a database beyond the queue's
-            // indices, work_queue = 0): its shape comes from the count, read back over PCIe
-            uint32_t n_sat = 0;
-            HIP_TRY(ctx, hipMemcpyAsync(&n_sat, db->d_counters + 1, 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(ctx, spin_sync(ctx, s));
-            if (n_sat > 0) {
-                int W = (int)((n_sat + (uint32_t)ctx->n_cu - 1) / (uint32_t)ctx->n_cu);
-                W = std::min(16, std::max(4, (W + 3) / 4 * 4));
-                const int wgs = (int)std::min<uint32_t>((uint32_t)ctx->n_cu, (n_sat + W - 1) / W);
-                p.npass = (uint32_t)P.npass32;
-                p.scratch_wg_dwords = ((uint64_t)db->max_nblk * 4 + 4) * 4;
-                HIP_TRY(ctx, swg_launch_diag32(W, wgs, p, s));
-            }
-        } else {
-            p.npass = (uint32_t)P.re_pl.npass;
-            p.scratch_wg_dwords = (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK * 64 * P.re_pl.info.nb;
-            HIP_TRY(ctx, swg_launch_fill(32, P.re_pl.variant, P.re_pl.W, P.re_pl.workgroups, p, s));
-        }
-    }
-    HIP_TRY(ctx, hipEventRecord(S->ev[3], s));
-    return SWG_OK;
-}
-
-// The k-mer bound's table for the current (query, scoring) epoch: the class profile from the device copies
-// of table and query, then every class block's best cell per segment, both queued on the context's stream -- behind the
-// copy of the query a set_query queued there and behind any search still in flight, in front of the bound kernel that
-// reads it: the rule the profiles follow (ensure_profile_cols).  One buffer per k, keyed by (k, S, epoch), so searches that
-// alternate between the two k build each once per epoch; it grows when S x entries does, and a table beyond
-// SWG_KMER_TABLE_BUDGET is refused.
-static int ensure_kmer_table(swg_ctx *ctx, int k, int S)
-{
-    const int which = k - 4;
-    const size_t lq = ctx->query_len();
-    if (S < 1 || S > (int)SWG_KMER_MAX_SEGMENTS) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the k-mer bound's table: %d segments (1..32)", S);
-    const size_t entries = (size_t)swg_kmer_entries(k) * (size_t)S;
-    if (!swg_kmer_table_admitted(k, S))
-        return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the k-mer bound's table of k = %d in %d segments is %zu MB: above its budget of %zu MB (prune_kmer, prune_segments)", k,
-                                 S, entries * sizeof(uint16_t) >> 20, (size_t)(SWG_KMER_TABLE_BUDGET >> 20));
-    if (ctx->d_kmer_table[which] && ctx->kmer_table_epoch[which] == ctx->epoch && ctx->kmer_table_segments[which] == (uint32_t)S) return SWG_OK;
-    if (lq * 32 > ctx->d_kmer_cprof_cap) {
-        (void)hipFree(ctx->d_kmer_cprof);
-        ctx->d_kmer_cprof = nullptr;
-        ctx->d_kmer_cprof_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_kmer_cprof, lq * 32));
-        ctx->d_kmer_cprof_cap = lq * 32;
-    }
-    if (!ctx->d_kmer_table[which] || ctx->kmer_table_cap[which] < entries) {
-        (void)hipFree(ctx->d_kmer_table[which]);
-        ctx->d_kmer_table[which] = nullptr;
-        ctx->kmer_table_cap[which] = 0;
-        ctx->kmer_table_epoch[which] = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_kmer_table[which], entries * sizeof(uint16_t)));
-        ctx->kmer_table_cap[which] = entries;
-    }
-    // (gap scores: a gap's first residue costs open + extend, every further one extend -- SwgSearchPlan's go / ge)
-    const long go = (long)ctx->gap_open + ctx->gap_extend, ge = ctx->gap_extend;
-    HIP_TRY(ctx, swg_launch_kmer_table(ctx->d_sub, ctx->d_query, ctx->query_pssm ? ctx->d_pssm : nullptr, (uint32_t)lq, (uint32_t)-go, (uint32_t)-ge, k,
-                                       (uint32_t)S, ctx->d_kmer_cprof, ctx->d_kmer_table[which], ctx->stream));
-    ctx->kmer_table_epoch[which] = ctx->epoch;
-    ctx->kmer_table_segments[which] = (uint32_t)S;
-    ++ctx->kmer_builds;
-    return SWG_OK;
-}
-
-// The second level's table (k = 4 in S2 = 64 or 128 segments): a buffer of its own, keyed by (S2, epoch), queued behind the
-// first level's under the same rules and counted apart from it (kmer_refine_builds).
-static int ensure_kmer_refine_table(swg_ctx *ctx, int S2)
-{
-    const size_t lq = ctx->query_len();
-    if (S2 != 64 && S2 != 128) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the second-level bound's table: %d segments (64 or 128)", S2);
-    const size_t entries = (size_t)swg_kmer_entries(4) * (size_t)S2;
-    if (ctx->d_kmer_refine && ctx->kmer_refine_epoch == ctx->epoch && ctx->kmer_refine_segments == (uint32_t)S2) return SWG_OK;
-    if (lq * 32 > ctx->d_kmer_cprof_cap) {
-        (void)hipFree(ctx->d_kmer_cprof);
-        ctx->d_kmer_cprof = nullptr;
-        ctx->d_kmer_cprof_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_kmer_cprof, lq * 32));
-        ctx->d_kmer_cprof_cap = lq * 32;
-    }
-    if (!ctx->d_kmer_refine || ctx->kmer_refine_cap < entries) {
-        (void)hipFree(ctx->d_kmer_refine);
-        ctx->d_kmer_refine = nullptr;
-        ctx->kmer_refine_cap = 0;
-        ctx->kmer_refine_epoch = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_kmer_refine, entries * sizeof(uint16_t)));
-        ctx->kmer_refine_cap = entries;
-    }
-    const long go = (long)ctx->gap_open + ctx->gap_extend, ge = ctx->gap_extend;
-    HIP_TRY(ctx, swg_launch_kmer_table(ctx->d_sub, ctx->d_query, ctx->query_pssm ? ctx->d_pssm : nullptr, (uint32_t)lq, (uint32_t)-go, (uint32_t)-ge, 4,
-                                       (uint32_t)S2, ctx->d_kmer_cprof, ctx->d_kmer_refine, ctx->stream));
-    ctx->kmer_refine_epoch = ctx->epoch;
-    ctx->kmer_refine_segments = (uint32_t)S2;
-    ++ctx->kmer_refine_builds;
-    return SWG_OK;
-}
-
-// Whether this search is pruned (swg_prune_plan has the rules), decided once the plan stands; a pruned search gets the
-// bound's table for the current query and scoring (built on the host when either has changed; it travels to the bound
-// kernel as a launch argument) and its slot's buffer of pair bounds.
+// Whether this search is pruned (swg_prune_plan has the rules) and by which bound, decided once the plan stands.  It only
+// decides: P->prune and the context's record of the choice; prepare_prune builds what the choice needs.
 static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgSearchPlan *P)
 {
     P->prune = SwgPrunePlan();
@@ -2531,7 +2353,7 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
         return SWG_OK; // (launch_diag reports it)
     a.n_segments = segs.size();
     P->prune = swg_prune_plan(a);
-    ctx->prune_last_kmer = 0, ctx->prune_last_segments = 0, ctx->prune_last_refine = 0;
+    ctx->prune_choice = SwgPruneChoice();
     if (!P->prune.on) return SWG_OK;
     P->prune.fixed_T = P->prune.fixed ? (uint32_t)ctx->above_min : 0u;
     // which bound: the colmax table, or the k-mer table of the k that pays for its build on this range (a forced k as it is)
@@ -2543,35 +2365,195 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
     ka.lq = ctx->query_len();
     ka.pair_rows = 4ull * (db->ptok.pair_blocks_prefix[wk.pair_end[0]] - db->ptok.pair_blocks_prefix[wk.pair_begin[0]]);
     ka.fill_rate = swg_kmer_fill_rate(ka.lq);
-    P->prune.kmer = ctx->prune_last_kmer = swg_prune_kmer_choice(ka, &P->prune.segments);
-    ctx->prune_last_segments = P->prune.segments;
-    if (P->prune.kmer > 1) {
-        const int rk = ensure_kmer_table(ctx, P->prune.kmer, P->prune.segments);
-        if (rk != SWG_OK) return rk;
-    }
+    P->prune.kmer = swg_prune_kmer_choice(ka, &P->prune.segments);
     // how a stage is cut: pair by pair, behind the second-level bound where that pays, or the prefix of the length order
     P->prune.prefix_cut = ctx->opt_prune_cut == 1 && !P->prune.fixed; // (a caller's threshold takes the list)
-    P->prune.refine = ctx->prune_last_refine = P->prune.prefix_cut ? 0 : swg_prune_refine_choice(ka, P->prune.kmer, P->prune.segments);
-    if (P->prune.refine) {
-        const int rk = ensure_kmer_refine_table(ctx, P->prune.refine);
-        if (rk != SWG_OK) return rk;
-    }
+    P->prune.refine = P->prune.prefix_cut ? 0 : swg_prune_refine_choice(ka, P->prune.kmer, P->prune.segments);
+    ctx->prune_choice = SwgPruneChoice{P->prune.kmer, P->prune.segments, P->prune.refine};
+    return SWG_OK;
+}
+
+// A k-mer table of (k, S) for the current (query, scoring) epoch: the class profile from the device copies
+// of table and query, then every class block's best cell per segment, both queued on the context's stream -- behind the
+// copy of the query a set_query queued there and behind any search still in flight, in front of the bound kernel that
+// reads it: the rule the profiles follow (ensure_profile_cols).  A table that holds (epoch, k, S) already is left alone; it
+// grows when S x entries does.  Which (k, S) a table may hold is the caller's to say.
+static int ensure_kmer_table(swg_ctx *ctx, SwgKmerTable *t, int k, int S)
+{
+    if (t->holds(ctx->epoch, k, S)) return SWG_OK;
+    const size_t lq = ctx->query_len();
+    int rc;
+    if ((rc = device_grow(ctx, &ctx->d_kmer_cprof, &ctx->d_kmer_cprof_cap, lq * 32)) != SWG_OK) return rc;
+    const size_t entries = (size_t)swg_kmer_entries(k) * (size_t)S;
+    if (t->cap < entries) t->epoch = 0; // (allocated anew below: what it held is gone)
+    if ((rc = device_grow(ctx, &t->d, &t->cap, entries)) != SWG_OK) return rc;
+    // (gap scores: a gap's first residue costs open + extend, every further one extend -- SwgSearchPlan's go / ge)
+    const long go = (long)ctx->gap_open + ctx->gap_extend, ge = ctx->gap_extend;
+    HIP_TRY(ctx, swg_launch_kmer_table(ctx->d_sub, ctx->d_query, ctx->query_pssm ? ctx->d_pssm : nullptr, (uint32_t)lq, (uint32_t)-go, (uint32_t)-ge, k,
+                                       (uint32_t)S, ctx->d_kmer_cprof, t->d, ctx->stream));
+    t->epoch = ctx->epoch, t->k = k, t->segments = S;
+    ++(t == &ctx->kmer_second ? ctx->kmer_refine_builds : ctx->kmer_builds);
+    return SWG_OK;
+}
+
+// What a pruned search reads besides the fill's own: the colmax table for the current query and scoring (built on the
+// host when either has changed; it travels to the bound kernels as a launch argument), the k-mer tables of the plan's
+// choice -- the first level's within SWG_KMER_TABLE_BUDGET, the second level's queued behind it and counted apart -- and
+// the slot's buffer of pair bounds (swg_prune_layout).
+static int prepare_prune(swg_ctx *ctx, swg_db *db, const SwgPrunePlan &pr)
+{
+    int rc;
     if (ctx->prune_colmax_epoch != ctx->epoch) {
         ctx->prune_colmax = ctx->query_pssm ? swg_prune_colmax(ctx->pssm.data(), nullptr, ctx->query_len())
                                             : swg_prune_colmax(&ctx->sub[0][0], ctx->query.data(), ctx->query_len());
         ctx->prune_colmax_epoch = ctx->epoch;
     }
-    // (the bounds, the pair ids a prefix-cut stage's list launches read, the stages' own lists: swg_prune_pair_words)
+    if (pr.kmer > 1) {
+        const int k = pr.kmer, S = pr.segments;
+        if (S < 1 || S > (int)SWG_KMER_MAX_SEGMENTS) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the k-mer bound's table: %d segments (1..32)", S);
+        if (!swg_kmer_table_admitted(k, S))
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the k-mer bound's table of k = %d in %d segments is %zu MB: above its budget of %zu MB (prune_kmer, prune_segments)", k,
+                                     S, (size_t)swg_kmer_entries(k) * (size_t)S * sizeof(uint16_t) >> 20, (size_t)(SWG_KMER_TABLE_BUDGET >> 20));
+        if ((rc = ensure_kmer_table(ctx, &ctx->kmer_first[k - 4], k, S)) != SWG_OK) return rc;
+    }
+    if (pr.refine) {
+        if (pr.refine != 64 && pr.refine != 128) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the second-level bound's table: %d segments (64 or 128)", pr.refine);
+        if ((rc = ensure_kmer_table(ctx, &ctx->kmer_second, 4, pr.refine)) != SWG_OK) return rc;
+    }
     swg_db::Bufs &b = db->bufs[ctx->cur - ctx->slots];
     const size_t n_pairs = (size_t)swg_db_pair_count(db);
-    if (!b.d_pair_bound || b.pair_bound_cap < n_pairs) {
-        (void)hipFree(b.d_pair_bound);
-        b.d_pair_bound = nullptr;
-        b.pair_bound_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&b.d_pair_bound, swg_prune_pair_words(n_pairs) * sizeof(uint32_t)));
-        b.pair_bound_cap = n_pairs;
-    }
+    if ((rc = device_grow(ctx, &b.d_pair_bound, &b.pair_bound_cap, n_pairs, swg_prune_layout(b.d_pair_bound, n_pairs).words - n_pairs)) != SWG_OK) return rc;
     db->d_pair_bound = b.d_pair_bound;
+    return SWG_OK;
+}
+
+// Profiles, scratch and the bin image of a planned search, and what its pruning reads.
+static int prepare_search(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P)
+{
+    int rc = SWG_OK;
+    const bool systolic_fill = !P.use_diag && !P.use_q32 && !(P.bits == 32 && P.use_diag32);
+    const bool systolic_rescore = P.may_saturate && !P.use_diag32;
+    const size_t bin32_scratch = P.bin32 && P.npass32 > 1 ? ((size_t)db->max_nblk * 4 + 4) * 4 * 16 * (size_t)ctx->n_cu : 0; // dwords: one uint4 per stream row
+    if (P.bin32) {
+        rc = ensure_profile_cols(ctx, 1, (uint32_t)(P.npass32 * 64 * SWG_DIAG32_K), 4, (1ull << 30) ^ (uint64_t)P.npass32);
+        if (rc != SWG_OK) return rc;
+        if ((rc = ensure_scratch(ctx, bin32_scratch)) != SWG_OK) return rc;
+    }
+    if (P.use_diag) {
+        if ((rc = prepare_diag(ctx, db, P.wk)) == SWG_OK && P.prune.on) rc = prepare_prune(ctx, db, P.prune);
+    } else if (systolic_fill) rc = ensure_profile(ctx, P.main_pl);
+    // (the int32 work-queue fill builds its profiles at the launch)
+    if (rc != SWG_OK) return rc;
+    if (systolic_rescore && (rc = ensure_profile(ctx, P.re_pl)) != SWG_OK) return rc;
+    size_t need = bin32_scratch;
+    if (systolic_fill && P.main_pl.npass > 1)
+        need = std::max(need, (size_t)P.main_pl.workgroups * db->max_nblk * SWG_ROWS_PER_BLK * 64 * P.main_pl.info.nb);
+    if (systolic_rescore && P.re_pl.npass > 1)
+        need = std::max(need, (size_t)P.re_pl.workgroups * db->max_nblk * SWG_ROWS_PER_BLK * 64 * P.re_pl.info.nb);
+    if ((rc = ensure_scratch(ctx, need)) != SWG_OK) return rc;
+    // the systolic engine and the bin-based int32 kernel read the bin image (built on the device on first use)
+    if ((!P.use_diag && !P.use_q32) || (P.int32_level && !P.q32_ok)) return ensure_bins(ctx, db);
+    return SWG_OK;
+}
+
+// The first level on the main stream: the diagonal engine, the int32 work queue, the bin-based int32 kernel or the
+// systolic engine (events ev[0] before the buffers are cleared, ev[1] .. ev[2] around the fill).
+static int enqueue_fill(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P, SwgSlot *S)
+{
+    hipStream_t s = ctx->stream;
+    const size_t n_slots = (size_t)db->n_bins * SWG_BIN;
+    HIP_TRY(ctx, hipEventRecord(S->ev[0], s));
+    HIP_TRY(ctx, swg_launch_zero2(db->d_scores, n_slots * 4, db->d_counters, SWG_COUNTER_BYTES, s)); // (one launch, not two memsets)
+    S->two_ends = false;
+    S->fill_launches = 0;
+    S->pruned = false;
+    if (P.use_diag) return launch_diag(ctx, db, P.wk, P.go, P.ge, &S->two_ends, &P.prune, S->k);
+    if (P.use_q32)
+        return launch_q32(ctx, db, P.wk32, P.go, P.ge, nullptr, nullptr, 0, db->d_counters + SWG_QUEUE_WORD(0), &S->two_ends, true, P.exact32);
+    if (!(P.bits == 32 && P.use_diag32)) return launch_systolic(ctx, db, P.main_pl, P.go, P.ge);
+    SwgFillParams p = fill_params_base(ctx, db);
+    p.profile = ctx->d_profile[1];
+    p.queue = db->d_counters + SWG_WORD_WORK_QUEUE;
+    p.n_items = (uint32_t)n_slots;
+    p.npass = (uint32_t)P.npass32;
+    p.go = P.go;
+    p.ge = P.ge;
+    p.scratch_wg_dwords = ((uint64_t)db->max_nblk * 4 + 4) * 4;
+    HIP_TRY(ctx, hipEventRecord(S->ev[1], s));
+    HIP_TRY(ctx, swg_launch_diag32(16, (int)std::min<size_t>((size_t)ctx->n_cu, (n_slots + 15) / 16), p, s));
+    HIP_TRY(ctx, hipEventRecord(S->ev[2], s));
+    return SWG_OK;
+}
+
+// The levels behind the first: the pairs the f16 cells flagged are collected and run again on int16 cells, then what
+// saturated the last 16-bit level is collected and re-scored in int32 (event ev[3] at the end).
+static int enqueue_rescore(swg_ctx *ctx, swg_db *db, const SwgSearchPlan &P, SwgSlot *S)
+{
+    hipStream_t s = ctx->stream;
+    const size_t lq = ctx->query_len();
+    const size_t n_slots = (size_t)db->n_bins * SWG_BIN;
+    const bool some_f16 = P.some_f16();
+    int rc = SWG_OK;
+    uint32_t *seq_list = db->d_list;
+    if (P.may_saturate && some_f16) {
+        // (the flagged pairs are the list's length; their rows / 16 the veto's input)
+        HIP_TRY(ctx, swg_launch_collect_flagged_pairs(db->d_scores, P.split_at, (uint32_t)(n_slots / 2), SWG_F16_CEILING, db->d_list, db->d_counters + SWG_WORD_FLAGGED_PAIRS,
+                                                      db->d_counters + SWG_WORD_FLAGGED_SEQS, db->d_lens, db->d_counters + SWG_WORD_FLAGGED_ROWS, s));
+        SwgDiagPlan lp;
+        const uint32_t guess = db->sat_hint > 0 ? (uint32_t)std::min<long long>(db->sat_hint, 1ll << 30) : 1u;
+        if (!i16_list_plan(ctx->n_cu, lq, guess, P.wk.plan[0], &lp)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "no geometry for the int16 re-run");
+        HIP_TRY(ctx, hipMemsetAsync(db->d_counters + SWG_QUEUE_WORD(0), 0, (size_t)(SWG_COUNTER_BYTES - SWG_QUEUE_WORD(0) * 4u), s));
+        if ((rc = launch_dyn_list(ctx, db, lp, P.rerun_wide, P.go, P.ge, db->d_list, db->d_counters + SWG_WORD_FLAGGED_PAIRS, s)) != SWG_OK) return rc;
+        seq_list = db->d_list + n_slots; // (the pair list keeps the first half)
+    }
+    if (P.int32_level) {
+        // (the saturated sequences are the list's length)
+        HIP_TRY(ctx, swg_launch_collect_saturated(db->d_scores, (uint32_t)n_slots, P.level_ceiling, seq_list, db->d_counters + SWG_WORD_SATURATED,
+                                                  some_f16 ? nullptr : db->d_lens, db->d_counters + SWG_WORD_FLAGGED_ROWS, s));
+        SwgFillParams p = fill_params_base(ctx, db);
+        p.profile = ctx->d_profile[1];
+        p.queue = db->d_counters + SWG_WORD_RESCORE_QUEUE;
+        p.list = seq_list;
+        p.list_count = db->d_counters + SWG_WORD_SATURATED;
+        p.go = P.go32; // (the first level's gap scores, except in a gapless search: see plan_search)
+        p.ge = P.ge32;
+        SwgDiagWork wkl;
+        // The work-queue re-score reads the count on the device and leaves at once when it is zero, so it is queued
+        // behind every fill that may flag something and the host never waits for the count in the middle of a
+        // search (it did until round 3: a round trip per search, and the end of the two-deep pipeline of
+        // swg_search_begin).  Only its lane-group width is a guess -- few flagged sequences get 64 lanes each,
+        // many the narrowest group that covers the query -- made from what the last search of this database saw.
+        const uint32_t guess = !some_f16 && db->sat_hint > 0 ? (uint32_t)std::min<long long>(db->sat_hint, 1ll << 30) : 1u;
+        if (P.use_diag32 && P.q32_ok && q32_list_plan(ctx, lq, guess, &wkl)) {
+            // (fresh queue counters and rank table: the fill's are spent; no events of its own: the
+            // re-score is timed as ev[2] .. ev[3] like the other re-score forms)
+            HIP_TRY(ctx, hipMemsetAsync(db->d_counters + SWG_QUEUE_WORD(0), 0,
+                                        (size_t)(SWG_COUNTER_BYTES - SWG_QUEUE_WORD(0) * 4u), s));
+            bool two = false;
+            rc = launch_q32(ctx, db, wkl, P.go32, P.ge32, seq_list, db->d_counters + SWG_WORD_SATURATED, std::max<uint32_t>(2u * guess, 4096u),
+                            db->d_counters + SWG_QUEUE_WORD(0), &two, false);
+            if (rc != SWG_OK) return rc;
+        } else if (P.use_diag32) {
+            // the bin-based kernel (positive gap scores never get here; a database beyond the queue's
+            // indices, work_queue = 0): its shape comes from the count, read back over PCIe
+            uint32_t n_sat = 0;
+            HIP_TRY(ctx, hipMemcpyAsync(&n_sat, db->d_counters + SWG_WORD_SATURATED, 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, spin_sync(ctx, s));
+            if (n_sat > 0) {
+                int W = (int)((n_sat + (uint32_t)ctx->n_cu - 1) / (uint32_t)ctx->n_cu);
+                W = std::min(16, std::max(4, (W + 3) / 4 * 4));
+                const int wgs = (int)std::min<uint32_t>((uint32_t)ctx->n_cu, (n_sat + W - 1) / W);
+                p.npass = (uint32_t)P.npass32;
+                p.scratch_wg_dwords = ((uint64_t)db->max_nblk * 4 + 4) * 4;
+                HIP_TRY(ctx, swg_launch_diag32(W, wgs, p, s));
+            }
+        } else {
+            p.npass = (uint32_t)P.re_pl.npass;
+            p.scratch_wg_dwords = (uint64_t)db->max_nblk * SWG_ROWS_PER_BLK * 64 * P.re_pl.info.nb;
+            HIP_TRY(ctx, swg_launch_fill(32, P.re_pl.variant, P.re_pl.W, P.re_pl.workgroups, p, s));
+        }
+    }
+    HIP_TRY(ctx, hipEventRecord(S->ev[3], s));
     return SWG_OK;
 }
 
@@ -2606,7 +2588,7 @@ static int enqueue_readout(swg_ctx *ctx, swg_db *db, SwgSlot *S)
     }
     if (S->dev_topk)
         HIP_TRY(ctx, swg_launch_topk(db->d_scores, db->d_order, (uint32_t)n_slots, (uint32_t)k, db->d_hist,
-                                     db->d_counters + 4, db->d_keys, SWG_TOPK_CAND_CAP, db->d_counters + 3, s));
+                                     db->d_counters + SWG_WORD_TOPK_THR, db->d_keys, SWG_TOPK_CAND_CAP, db->d_counters + SWG_WORD_TOPK_COUNT, s));
     HIP_TRY(ctx, hipEventRecord(S->ev[4], s));
     // read-out, queued behind the kernels
     S->need_scores = S->want_scores || (k > 0 && !S->dev_topk);
@@ -2768,7 +2750,7 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
     const SwgDiagPlan &dpl = wk.plan[0];
     const uint32_t *h_counters = S->h_counters;
     int rc = SWG_OK;
-    const bool cand_ok = S->dev_topk && h_counters[5] == 0 && h_counters[3] <= SWG_TOPK_CAND_CAP;
+    const bool cand_ok = S->dev_topk && h_counters[SWG_WORD_TOPK_OVERFLOW] == 0 && h_counters[SWG_WORD_TOPK_COUNT] <= SWG_TOPK_CAND_CAP;
     if (S->dev_topk && !cand_ok) { // threshold beyond the histogram or too many ties: select on the host
         if ((rc = slot_scores(ctx, S, n_slots)) != SWG_OK) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(S->h_scores, S->bufs.d_scores, n_slots * 4, hipMemcpyDeviceToHost, s));
@@ -2783,13 +2765,13 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
     st.total_ms = ms;
     HIP_TRY(ctx, hipEventElapsedTime(&ms, S->ev[3], S->ev[4]));
     const double topk_dev_ms = ms;
-    st.n_rescored = some_f16 ? h_counters[16] : h_counters[1];
+    st.n_rescored = h_counters[some_f16 ? SWG_WORD_FLAGGED_SEQS : SWG_WORD_SATURATED];
     st.path_bits = P.bits;
     st.cell_form = P.use_diag ? diag_class_form(ctx, db, dpl) : P.main_pl.f16 ? 2 : 0;
     if (st.cell_form == 3) st.cell_form = 6; // (the gapless cells: kernel form 3, reported as 6 -- 3 .. 5 are taken, see swg.h)
     if (P.use_diag && dpl.f16_from != 0u) {
         st.cell_form = dpl.wide ? 4 : 5;
-        st.n_rescored = (uint64_t)h_counters[16] + h_counters[1]; // flagged by the f16 cells + saturated on the wide form
+        st.n_rescored = (uint64_t)h_counters[SWG_WORD_FLAGGED_SEQS] + h_counters[SWG_WORD_SATURATED]; // flagged by the f16 cells + saturated on the wide form
         st.split_rows = (int32_t)P.split_rows;
         st.fill_f16_launches = S->fill_f16_launches;
         st.cells_f16 = st.cells / std::max<uint64_t>(1, db->residues) * P.split_residues; // (cells = lq * residues)
@@ -2798,25 +2780,29 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
     }
     if (P.may_saturate) {
         // what the next search's plan may assume (never its results)
-        db->sat_hint = (long long)(some_f16 ? h_counters[17] : h_counters[1]); // (f16: pairs; else sequences)
-        // f16 cells whose flagged pairs hold more than 1/16 of the pair rows (counter 6: rows of the flagged pairs / 16;
+        db->sat_hint = (long long)h_counters[some_f16 ? SWG_WORD_FLAGGED_PAIRS : SWG_WORD_SATURATED]; // (f16: pairs; else sequences)
+        // f16 cells whose flagged pairs hold more than 1/16 of the pair rows (SWG_WORD_FLAGGED_ROWS: rows of the flagged pairs / 16;
         // a pair row is two residues) cost more in re-runs than they save: the cells save 15 % of the fill, the list
         // re-run of a share f of the rows costs f x 10 / 8.5 at about half the fill's efficiency.  Measured on config
         // 4's share with 4 % of the pair rows flagged: f16 + re-run 191 ms, int16 cells alone 200.
-        if (some_f16 && !P.gapless && (uint64_t)h_counters[6] * 16ull * 2ull * 16ull > db->residues + 2ull * db->n_local) db->f16_veto_epoch = P.epoch;
+        if (some_f16 && !P.gapless && (uint64_t)h_counters[SWG_WORD_FLAGGED_ROWS] * 16ull * 2ull * 16ull > db->residues + 2ull * db->n_local) db->f16_veto_epoch = P.epoch;
     }
     // what a pruned search left out (swg_prune_last): from the counter words that came back with the search
-    ctx->prune_last[0] = S->pruned ? 1u : 0u;
-    ctx->prune_last[1] = S->pruned ? h_counters[SWG_PRUNE_WORD_CUT + 1u] : 0u;
-    ctx->prune_last[2] = S->pruned ? 4ull * ((uint64_t)h_counters[SWG_PRUNE_WORD_CUT + 2u] | ((uint64_t)h_counters[SWG_PRUNE_WORD_CUT + 3u] << 32)) : 0u;
-    ctx->prune_last[3] = P.use_diag && db->ptok.ok && !db->ptok.pair_blocks_prefix.empty()
-                             ? 4ull * (db->ptok.pair_blocks_prefix[wk.pair_end[0]] - db->ptok.pair_blocks_prefix[wk.pair_begin[0]]) : 0u;
-    ctx->prune_last[4] = S->pruned ? h_counters[SWG_PRUNE_WORD_T] : 0u;
+    swg_prune_info &pi = ctx->prune_last;
+    pi = swg_prune_info();
+    pi.pruned = S->pruned ? 1 : 0;
+    if (S->pruned) {
+        pi.pairs_skipped = h_counters[SWG_PRUNE_WORD_CUT + 1u];
+        pi.pair_rows_skipped = 4ull * ((uint64_t)h_counters[SWG_PRUNE_WORD_CUT + 2u] | ((uint64_t)h_counters[SWG_PRUNE_WORD_CUT + 3u] << 32));
+        pi.threshold = h_counters[SWG_PRUNE_WORD_T];
+    }
+    if (P.use_diag && db->ptok.ok && !db->ptok.pair_blocks_prefix.empty())
+        pi.pair_rows = 4ull * (db->ptok.pair_blocks_prefix[wk.pair_end[0]] - db->ptok.pair_blocks_prefix[wk.pair_begin[0]]);
     st.classes_overlapped = -1;
     if (P.use_diag && wk.n_classes == 2 && wk.plan[0].npass == 1 && wk.plan[1].npass == 1) {
         // did the two classes run side by side?  (stamps: complement of the earliest start, latest end)
         unsigned long long t[4];
-        memcpy(t, h_counters + 8, sizeof t);
+        memcpy(t, h_counters + SWG_WORD_STAMPS(0), sizeof t);
         if (t[0] && t[1] && t[2] && t[3]) {
             const unsigned long long bulk_start = ~t[0], bulk_end = t[1], long_start = ~t[2];
             st.classes_overlapped = (bulk_end > bulk_start && long_start < bulk_start + (bulk_end - bulk_start) / 10) ? 1 : 0;
@@ -2883,7 +2869,7 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
         if ((rc = deliver_above(ctx, S, s, above, n_hits)) != SWG_OK) return rc;
     } else if (k > 0 && cand_ok) { // (the device's candidates: every hit with a score >= the k-th best one; no score array was asked for)
         uint64_t *keys = S->h_cand;
-        const size_t nc = h_counters[3], m = std::min(k, nc);
+        const size_t nc = h_counters[SWG_WORD_TOPK_COUNT], m = std::min(k, nc);
         std::partial_sort(keys, keys + m, keys + nc, std::greater<uint64_t>());
         for (size_t i = 0; i < m; ++i) swg_key_hit(keys[i], &topk_out[i]);
         if (n_hits) *n_hits = m;
@@ -2896,83 +2882,36 @@ static int search_end(swg_ctx *ctx, SwgSlot *S, int32_t *scores_out, swg_hit *to
     return SWG_OK;
 }
 
-// test hook: what the k-mer bound left on the device, read once everything queued has run.  table_out (or NULL): the
-// 22^k entries of the context's table of k (an error unless it was built for the current query and scoring); bound_out
-// (or NULL; bound_cap entries): the pair bounds of the search last begun on db.  info[0..2] = the k that search cut by
-// (0: not pruned), the table builds this context has queued so far, the database's pairs.
-extern "C" int swg_debug_prune_kmer_read(swg_ctx *ctx, const swg_db *db, int k, uint16_t *table_out, uint32_t *bound_out, size_t bound_cap,
-                                         uint64_t *info)
+// test hooks: what a pruned search left on the device, read once everything queued has run.  `table`, with table_out (or
+// NULL): the context's table of (k, S), an error unless it holds exactly that for the current query and scoring.
+// bound_out / list_out (or NULL; pair_cap entries each): the pair bounds of the search last begun on db as it left them,
+// and the list words (one per pair: a stage's list starts at its first pair's word); stages_out (or NULL): four words per
+// stage cut pair by pair, {begin, end, T, kept pairs}.  info[0..6] = the k that search cut by (0: not pruned), first-level
+// builds queued so far, the database's pairs, S, S2 (0: no second level), second-level builds, stages written.
+static int debug_prune_read(swg_ctx *ctx, const swg_db *db, const char *fn, const SwgKmerTable *table, int k, int S, uint16_t *table_out, uint32_t *bound_out,
+                            uint32_t *list_out, size_t pair_cap, uint32_t *stages_out, size_t stages_cap, int n_info, uint64_t *info)
 {
-    if (!ctx || !info) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_kmer_read: NULL argument");
+    if (!ctx || !info) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: NULL argument", fn);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipDeviceSynchronize());
     const size_t n_pairs = db ? (size_t)swg_db_pair_count(db) : 0;
-    info[0] = (uint64_t)ctx->prune_last_kmer, info[1] = ctx->kmer_builds, info[2] = n_pairs;
+    const uint64_t all[7] = {(uint64_t)ctx->prune_choice.kmer, ctx->kmer_builds, n_pairs, (uint64_t)ctx->prune_choice.segments, (uint64_t)ctx->prune_choice.refine,
+                             ctx->kmer_refine_builds, 0};
+    std::copy(all, all + n_info, info);
     if (table_out) {
-        if ((k != 4 && k != 5) || !ctx->d_kmer_table[k - 4] || ctx->kmer_table_epoch[k - 4] != ctx->epoch || ctx->kmer_table_segments[k - 4] != 1u)
-            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_kmer_read: no table of k = %d for the current query and scoring", k);
-        HIP_TRY(ctx, hipMemcpy(table_out, ctx->d_kmer_table[k - 4], (size_t)swg_kmer_entries(k) * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    }
-    if (bound_out) {
-        if (!db || !db->d_pair_bound || bound_cap < n_pairs)
-            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_kmer_read: no pair bounds on this database, or too little room");
-        HIP_TRY(ctx, hipMemcpy(bound_out, db->d_pair_bound, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    return SWG_OK;
-}
-
-// ... and over segments: table_out (or NULL) the 22^k x S entries of the context's table of k, an error unless it was
-// built with S segments for the current query and scoring; info[0..3] = k, the table builds, the database's pairs, the S
-// the search last begun cut by
-extern "C" int swg_debug_prune_kmer_seg_read(swg_ctx *ctx, const swg_db *db, int k, int S, uint16_t *table_out, uint32_t *bound_out, size_t bound_cap,
-                                             uint64_t *info)
-{
-    if (!ctx || !info) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_kmer_seg_read: NULL argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    const size_t n_pairs = db ? (size_t)swg_db_pair_count(db) : 0;
-    info[0] = (uint64_t)ctx->prune_last_kmer, info[1] = ctx->kmer_builds, info[2] = n_pairs, info[3] = (uint64_t)ctx->prune_last_segments;
-    if (table_out) {
-        if ((k != 4 && k != 5) || S < 1 || !ctx->d_kmer_table[k - 4] || ctx->kmer_table_epoch[k - 4] != ctx->epoch ||
-            ctx->kmer_table_segments[k - 4] != (uint32_t)S)
-            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_kmer_seg_read: no table of k = %d in %d segments for the current query and scoring", k, S);
-        HIP_TRY(ctx, hipMemcpy(table_out, ctx->d_kmer_table[k - 4], (size_t)swg_kmer_entries(k) * (size_t)S * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    }
-    if (bound_out) {
-        if (!db || !db->d_pair_bound || bound_cap < n_pairs)
-            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_kmer_seg_read: no pair bounds on this database, or too little room");
-        HIP_TRY(ctx, hipMemcpy(bound_out, db->d_pair_bound, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    return SWG_OK;
-}
-
-// ... and of the second level and the lists: the table of S2 segments (table_out, or NULL), the bounds as the search last
-// begun left them, the list words (one per pair: a stage's list starts at its first pair's word) and, four words per
-// stage cut pair by pair, {begin, end, T, kept pairs}.  info[0..6] = k, first-level builds, pairs, S, S2 (0: no second
-// level), second-level builds, stages written to stages_out.
-extern "C" int swg_debug_prune_refine_read(swg_ctx *ctx, const swg_db *db, int S2, uint16_t *table_out, uint32_t *bound_out, uint32_t *list_out, size_t pair_cap,
-                                           uint32_t *stages_out, size_t stages_cap, uint64_t *info)
-{
-    if (!ctx || !info) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_refine_read: NULL argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    const size_t n_pairs = db ? (size_t)swg_db_pair_count(db) : 0;
-    info[0] = (uint64_t)ctx->prune_last_kmer, info[1] = ctx->kmer_builds, info[2] = n_pairs, info[3] = (uint64_t)ctx->prune_last_segments;
-    info[4] = (uint64_t)ctx->prune_last_refine, info[5] = ctx->kmer_refine_builds, info[6] = 0;
-    if (table_out) {
-        if (!ctx->d_kmer_refine || ctx->kmer_refine_epoch != ctx->epoch || ctx->kmer_refine_segments != (uint32_t)S2)
-            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_refine_read: no second-level table in %d segments for the current query and scoring", S2);
-        HIP_TRY(ctx, hipMemcpy(table_out, ctx->d_kmer_refine, (size_t)swg_kmer_entries(4) * (size_t)S2 * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        if (!table || !table->holds(ctx->epoch, k, S))
+            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: no table of k = %d in %d segments for the current query and scoring", fn, k, S);
+        HIP_TRY(ctx, hipMemcpy(table_out, table->d, (size_t)swg_kmer_entries(k) * (size_t)S * sizeof(uint16_t), hipMemcpyDeviceToHost));
     }
     if (bound_out || list_out || stages_out) {
-        if (!db || !db->d_pair_bound || pair_cap < n_pairs)
-            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_refine_read: no pair bounds on this database, or too little room");
-        if (bound_out) HIP_TRY(ctx, hipMemcpy(bound_out, db->d_pair_bound, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (list_out) HIP_TRY(ctx, hipMemcpy(list_out, db->d_pair_bound + 2 * n_pairs, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (!db || !db->d_pair_bound || pair_cap < n_pairs) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: no pair bounds on this database, or too little room", fn);
+        const SwgPruneLayout L = swg_prune_layout(db->d_pair_bound, n_pairs);
+        if (bound_out) HIP_TRY(ctx, hipMemcpy(bound_out, L.bounds, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (list_out) HIP_TRY(ctx, hipMemcpy(list_out, L.lists, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (stages_out) {
             const size_t n = std::min<size_t>(std::min<size_t>(db->prune_stages.size() / 2, SWG_PRUNE_STAGE_RECS), stages_cap);
             std::vector<uint32_t> recs(2 * n);
-            if (n) HIP_TRY(ctx, hipMemcpy(recs.data(), db->d_pair_bound + 3 * n_pairs + swg_prune_tile_words(n_pairs), 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            if (n) HIP_TRY(ctx, hipMemcpy(recs.data(), L.recs, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost));
             for (size_t i = 0; i < n; ++i)
                 stages_out[4 * i] = db->prune_stages[2 * i], stages_out[4 * i + 1] = db->prune_stages[2 * i + 1], stages_out[4 * i + 2] = recs[2 * i],
                                stages_out[4 * i + 3] = recs[2 * i + 1];
@@ -2981,15 +2920,32 @@ extern "C" int swg_debug_prune_refine_read(swg_ctx *ctx, const swg_db *db, int S
     }
     return SWG_OK;
 }
+// the unsegmented table of k (a table built with more segments is refused) and the bounds: info[0..2]
+extern "C" int swg_debug_prune_kmer_read(swg_ctx *ctx, const swg_db *db, int k, uint16_t *table_out, uint32_t *bound_out, size_t bound_cap,
+                                         uint64_t *info)
+{
+    return debug_prune_read(ctx, db, "swg_debug_prune_kmer_read", ctx && (k == 4 || k == 5) ? &ctx->kmer_first[k - 4] : nullptr, k, 1, table_out, bound_out, nullptr,
+                            bound_cap, nullptr, 0, 3, info);
+}
+// ... the table of k in S segments: info[0..3]
+extern "C" int swg_debug_prune_kmer_seg_read(swg_ctx *ctx, const swg_db *db, int k, int S, uint16_t *table_out, uint32_t *bound_out, size_t bound_cap,
+                                             uint64_t *info)
+{
+    return debug_prune_read(ctx, db, "swg_debug_prune_kmer_seg_read", ctx && (k == 4 || k == 5) ? &ctx->kmer_first[k - 4] : nullptr, k, S, table_out, bound_out, nullptr,
+                            bound_cap, nullptr, 0, 4, info);
+}
+// ... and the second level's table of S2 segments, the lists and the stages: info[0..6]
+extern "C" int swg_debug_prune_refine_read(swg_ctx *ctx, const swg_db *db, int S2, uint16_t *table_out, uint32_t *bound_out, uint32_t *list_out, size_t pair_cap,
+                                           uint32_t *stages_out, size_t stages_cap, uint64_t *info)
+{
+    return debug_prune_read(ctx, db, "swg_debug_prune_refine_read", ctx ? &ctx->kmer_second : nullptr, 4, S2, table_out, bound_out, list_out, pair_cap, stages_out,
+                            stages_cap, 7, info);
+}
 
 extern "C" int swg_prune_last(const swg_ctx *ctx, swg_prune_info *out)
 {
     if (!ctx || !out) return SWG_ERR_ARG;
-    out->pruned = (int32_t)ctx->prune_last[0];
-    out->threshold = (uint32_t)ctx->prune_last[4];
-    out->pairs_skipped = ctx->prune_last[1];
-    out->pair_rows_skipped = ctx->prune_last[2];
-    out->pair_rows = ctx->prune_last[3];
+    *out = ctx->prune_last;
     return SWG_OK;
 }
 
@@ -3620,7 +3576,7 @@ static int search_multi_impl(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, i
     memset(&st, 0, sizeof st);
     int rc = validate_batch(ctx, db, mq, topk_out, k, &st);
     if (rc != SWG_OK) return rc;
-    memset(ctx->prune_last, 0, sizeof ctx->prune_last); // (swg_prune_last: a batch call ends with nothing pruned)
+    ctx->prune_last = swg_prune_info(); // (swg_prune_last: a batch call ends with nothing pruned)
     if (stats) *stats = st;
     if (mq.n == 0) return SWG_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3954,37 +3910,26 @@ static void lists_deal_workgroups(const SwgListsPlan &P, ListChunk *C)
     swg_lists_deal(C->J, (uint64_t)P.pl.W * (64 / P.pl.G), (uint64_t)std::max(0, P.resident_wgs), P.equal_shares, &C->wg_rows);
 }
 
-template <class T> static int lists_grow(swg_ctx *ctx, T **d, size_t *cap, size_t need, size_t extra = 0)
-{
-    if (*d && *cap >= need) return SWG_OK;
-    (void)hipFree(*d);
-    *d = nullptr;
-    *cap = 0;
-    HIP_TRY(ctx, hipMalloc(d, std::max<size_t>(16, (need + extra) * sizeof(T))));
-    *cap = need;
-    return SWG_OK;
-}
-
 // The device buffers for one chunk, each with what it holds written beside it.
 static int lists_allocate(swg_ctx *ctx, const SwgListsPlan &P, const ListChunk &C, const MultiQueries &mq, ListBufs *B)
 {
     int rc;
     size_t cap = B->cap_slots;
-    if ((rc = lists_grow(ctx, &B->d_slots, &cap, C.n_slots())) != SWG_OK) return rc;
+    if ((rc = device_grow(ctx, &B->d_slots, &cap, C.n_slots())) != SWG_OK) return rc;
     cap = B->cap_slots;
-    if ((rc = lists_grow(ctx, &B->d_lens, &cap, C.n_slots())) != SWG_OK) return rc;
+    if ((rc = device_grow(ctx, &B->d_lens, &cap, C.n_slots())) != SWG_OK) return rc;
     cap = B->cap_slots;
-    if ((rc = lists_grow(ctx, &B->d_order, &cap, C.n_slots())) != SWG_OK) return rc;
+    if ((rc = device_grow(ctx, &B->d_order, &cap, C.n_slots())) != SWG_OK) return rc;
     cap = B->cap_slots;
-    if ((rc = lists_grow(ctx, &B->d_code_off, &cap, C.n_slots(), 1)) != SWG_OK) return rc;
-    if ((rc = lists_grow(ctx, &B->d_scores, &B->cap_slots, C.n_slots())) != SWG_OK) return rc;
-    if ((rc = lists_grow(ctx, &B->d_pair_off, &B->cap_pairs, C.n_pairs(), 1)) != SWG_OK) return rc;
+    if ((rc = device_grow(ctx, &B->d_code_off, &cap, C.n_slots(), 1)) != SWG_OK) return rc;
+    if ((rc = device_grow(ctx, &B->d_scores, &B->cap_slots, C.n_slots())) != SWG_OK) return rc;
+    if ((rc = device_grow(ctx, &B->d_pair_off, &B->cap_pairs, C.n_pairs(), 1)) != SWG_OK) return rc;
     size_t cb = (size_t)B->cap_blocks;
-    if ((rc = lists_grow(ctx, &B->d_tok, &cb, (size_t)C.blocks(), 1)) != SWG_OK) return rc; // (+ the block of zeros behind the last pair)
+    if ((rc = device_grow(ctx, &B->d_tok, &cb, (size_t)C.blocks(), 1)) != SWG_OK) return rc; // (+ the block of zeros behind the last pair)
     B->cap_blocks = cb;
-    if ((rc = lists_grow(ctx, &B->d_row_pairs, &B->cap_rows, C.Qb, 1)) != SWG_OK) return rc;
+    if ((rc = device_grow(ctx, &B->d_row_pairs, &B->cap_rows, C.Qb, 1)) != SWG_OK) return rc;
     cap = B->cap_prof_rows;
-    if ((rc = lists_grow(ctx, &B->d_qoff, &cap, C.Qb, 1)) != SWG_OK) return rc;
+    if ((rc = device_grow(ctx, &B->d_qoff, &cap, C.Qb, 1)) != SWG_OK) return rc;
     if (!B->d_prof || B->cap_prof_rows < C.Qb) {
         (void)hipFree(B->d_prof);
         B->d_prof = nullptr;
@@ -3992,13 +3937,13 @@ static int lists_allocate(swg_ctx *ctx, const SwgListsPlan &P, const ListChunk &
         HIP_TRY(ctx, hipMalloc(&B->d_prof, C.Qb * P.prof_row_bytes));
         B->cap_prof_rows = C.Qb;
     }
-    if ((rc = lists_grow(ctx, &B->d_wg_rows, &B->cap_wgs, C.wg_rows.size())) != SWG_OK) return rc;
+    if ((rc = device_grow(ctx, &B->d_wg_rows, &B->cap_wgs, C.wg_rows.size())) != SWG_OK) return rc;
     if (!B->d_cnt) {
         HIP_TRY(ctx, hipMalloc(&B->d_cnt, P.queue_dwords * 4));
         B->cnt_rows = P.chunk_queries;
     }
     const size_t qbytes = (size_t)(mq.off[C.q0 + C.Qb] - mq.off[C.q0]) * mq.row_bytes();
-    return lists_grow(ctx, &B->d_q, &B->cap_q, qbytes);
+    return device_grow(ctx, &B->d_q, &B->cap_q, qbytes);
 }
 
 // The fence before every launch, in the manner of multi_rows_ok: what the launch will index -- from the chunk's tables,
@@ -4188,7 +4133,7 @@ static int search_lists_impl(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, c
     memset(&st, 0, sizeof st);
     int rc = validate_batch(ctx, db, mq, topk_out, k, &st);
     if (rc != SWG_OK) return rc;
-    memset(ctx->prune_last, 0, sizeof ctx->prune_last); // (swg_prune_last: a batch call ends with nothing pruned)
+    ctx->prune_last = swg_prune_info(); // (swg_prune_last: a batch call ends with nothing pruned)
     if (mq.n && (!c_off || (c_off[mq.n] > c_off[0] && !cand))) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: NULL argument", mq.fn);
     if (db->tokens_only)
         return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: a database built from 16-lane batches has no residue bytes to list candidates of", mq.fn);

@@ -680,6 +680,45 @@ extern "C" int swg_debug_prune_plan_above(const int64_t *in, int64_t *out)
     return SWG_OK;
 }
 
+// The stages of a pruned fill and what is queued in front of each (swg_host_internal.h has the rules in words).
+std::vector<SwgPruneStage> swg_prune_stages(const SwgPrunePlan &plan, const std::vector<std::pair<uint32_t, uint32_t>> &segments)
+{
+    std::vector<SwgPruneStage> stages;
+    for (size_t i = 0; i < segments.size(); ++i) {
+        const uint32_t b = segments[i].first, en = segments[i].second;
+        const uint32_t mid = segments.size() == 1 && plan.head_pairs > 0 ? std::min(en, b + plan.head_pairs) : en;
+        stages.push_back(SwgPruneStage{b, mid, (uint32_t)i, 0u});
+        if (mid < en) stages.push_back(SwgPruneStage{mid, en, (uint32_t)i, 0u});
+    }
+    for (size_t si = 0; si < stages.size(); ++si) {
+        if (si == 0 && !plan.fixed) continue; // (nothing to cut by yet)
+        uint32_t q = plan.fixed ? 0u : SWG_STAGE_THRESHOLD;
+        if (plan.prefix_cut) q |= SWG_STAGE_PREFIX_CUT;
+        else {
+            if (plan.refine && plan.fixed && si == 0 && stages.size() > 1) q |= SWG_STAGE_GATE;
+            if (plan.refine) q |= SWG_STAGE_REFINE;
+            q |= SWG_STAGE_LIST;
+        }
+        stages[si].queued = q;
+    }
+    return stages;
+}
+
+extern "C" int swg_debug_prune_stages(const int64_t *in, int64_t *out, size_t cap, size_t *n_out)
+{
+    if (!in || !n_out || (cap > 0 && !out) || in[0] < 0 || in[4] < 0) return SWG_ERR_ARG;
+    SwgPrunePlan plan;
+    plan.on = true;
+    plan.head_pairs = (uint32_t)in[0], plan.fixed = in[1] != 0, plan.refine = (int)in[2], plan.prefix_cut = in[3] != 0;
+    std::vector<std::pair<uint32_t, uint32_t>> segments;
+    for (int64_t i = 0; i < in[4]; ++i) segments.emplace_back((uint32_t)in[5 + 2 * i], (uint32_t)in[6 + 2 * i]);
+    const std::vector<SwgPruneStage> stages = swg_prune_stages(plan, segments);
+    for (size_t i = 0; i < stages.size() && i < cap; ++i)
+        out[4 * i] = stages[i].begin, out[4 * i + 1] = stages[i].end, out[4 * i + 2] = stages[i].segment, out[4 * i + 3] = stages[i].queued;
+    *n_out = stages.size();
+    return SWG_OK;
+}
+
 // The k-mer form of the bound, on the host: what the device builds (swg_kmer_cprof_kernel,
 // swg_kmer_table_kernel) and sums (swg_pair_bound_kmer_kernel), restated for the tests.  cprof[lq][22]: query column i
 // against residue class c -- the residue's own score for classes 1..20, the best of the merged residues for class 21 (the
@@ -742,53 +781,15 @@ void swg_kmer_table_seg(const int8_t *cprof, size_t lq, int g, int e, int k, siz
     }
 }
 
-void swg_kmer_table(const int8_t *cprof, size_t lq, int g, int e, int k, uint16_t *table) { swg_kmer_table_seg(cprof, lq, g, e, k, 1, table); }
-
-// U_k of one sequence as the device sums it: the sequence's token rows -- two reset rows (padding), its residues (a 0 among
-// them is a padding row: the shorter sequence of a pair, filled up to the longer one's length), padding to a whole 4-row
-// token block -- in blocks of 4 rows (k = 4), or in blocks of 5 over every whole 20 rows and of 4 over the rest (k = 5).
-// A block adds its table entry, or the sum of its rows' colmax entries where that is less: the entry of a block with
-// residues of class 21 is taken under the best scores of all of them, and may exceed what these residues can reach.
-uint64_t swg_kmer_bound(const uint16_t *table, int k, const SwgColMax &cm, const int8_t *seq, size_t len)
-{
-    const size_t n_blocks = (2 + len + 3) / 4, n_rows = 4 * n_blocks;
-    auto res = [&](size_t row) -> uint32_t { return row < 2 || row >= 2 + len ? 0u : (uint8_t)seq[row - 2] & 31u; };
-    const size_t rows5 = k == 5 ? 20 * (n_blocks / 5) : 0;
-    uint64_t u = 0;
-    for (size_t r = 0; r < n_rows;) {
-        const size_t rows = r < rows5 ? 5 : 4;
-        size_t ix = 0;
-        uint64_t sum = 0;
-        for (size_t j = 0; j < rows; ++j) ix = ix * SWG_KMER_CLASSES + swg_kmer_class(res(r + j)), sum += cm.v[res(r + j)];
-        if (k == 5 && rows == 4) ix *= SWG_KMER_CLASSES;
-        u += std::min<uint64_t>(table[ix], sum);
-        r += rows;
-    }
-    return u;
-}
-
-// test hook: the table (22^k uint16, or NULL) and U_k of each of the n sequences, under the gap scores of swg_set_scoring
-extern "C" int swg_debug_prune_kmer(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int k, const int8_t *flat,
-                                    const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out)
-{
-    if (!rows || lq == 0 || (k != 4 && k != 5) || gap_open > 0 || gap_extend > 0 || (n > 0 && (!flat || !offsets || !u_out))) return SWG_ERR_ARG;
-    std::vector<int8_t> cprof(lq * SWG_KMER_CLASSES);
-    swg_kmer_cprof(rows, idx, lq, cprof.data());
-    std::vector<uint16_t> own;
-    if (!table_out) {
-        own.resize(swg_kmer_entries(k));
-        table_out = own.data();
-    }
-    swg_kmer_table(cprof.data(), lq, -(gap_open + gap_extend), -gap_extend, k, table_out);
-    const SwgColMax cm = swg_prune_colmax(rows, idx, lq);
-    for (size_t i = 0; i < n; ++i) u_out[i] = swg_kmer_bound(table_out, k, cm, flat + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
-    return SWG_OK;
-}
-
-// U_{k,S} of one sequence: swg_kmer_bound's blocks, taken in order over the table of S segments.  The
-// segment that holds a block's last matched column never decreases along the sequence, so with H[s] the best total of the
-// blocks so far whose last one ended in segment s, a block gives H[s] = max_{s' <= s} H[s'] + min(table[block][s], the
-// block's colmax sum), and the bound is max_s H[s].  S = 1 is swg_kmer_bound.
+// U_{k,S} of one sequence as the device sums it: the sequence's token rows -- two reset rows (padding), its
+// residues (a 0 among them is a padding row: the shorter sequence of a pair, filled up to the longer one's length),
+// padding to a whole 4-row token block -- in blocks of 4 rows (k = 4), or in blocks of 5 over every whole 20 rows and of 4
+// over the rest (k = 5).  A block counts its table entry, or the sum of its rows' colmax entries where that is less: the
+// entry of a block with residues of class 21 is taken under the best scores of all of them, and may exceed what these
+// residues can reach.  The blocks are taken in order over the table's S segments: the segment that holds a block's last
+// matched column never decreases along the sequence, so with H[s] the best total of the blocks so far whose last one ended
+// in segment s, a block gives H[s] = max_{s' <= s} H[s'] + min(table[block][s], the block's colmax sum), and the bound is
+// max_s H[s].  S = 1 is the unordered sum of the blocks.
 uint64_t swg_kmer_bound_seg(const uint16_t *table, int k, size_t S, const SwgColMax &cm, const int8_t *seq, size_t len)
 {
     const size_t n_blocks = (2 + len + 3) / 4, n_rows = 4 * n_blocks;
@@ -810,13 +811,12 @@ uint64_t swg_kmer_bound_seg(const uint16_t *table, int k, size_t S, const SwgCol
     return *std::max_element(H.begin(), H.end());
 }
 
-// test hook: swg_debug_prune_kmer over S segments -- the table (22^k x S uint16, or NULL) and U_{k,S} of each sequence
-extern "C" int swg_debug_prune_kmer_seg(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int k, int S,
-                                        const int8_t *flat, const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out)
+// The body of the three mirror hooks below, each of which admits its own (k, S): the table (22^k x S uint16, or NULL) and
+// U_{k,S} of each of the n sequences flat[offsets[i] .. offsets[i+1]), under the gap scores of swg_set_scoring
+static int debug_prune_kmer(bool admitted, const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int k, int S,
+                            const int8_t *flat, const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out)
 {
-    if (!rows || lq == 0 || (k != 4 && k != 5) || S < 1 || S > (int)SWG_KMER_MAX_SEGMENTS || gap_open > 0 || gap_extend > 0 ||
-        (n > 0 && (!flat || !offsets || !u_out)))
-        return SWG_ERR_ARG;
+    if (!admitted || !rows || lq == 0 || gap_open > 0 || gap_extend > 0 || (n > 0 && (!flat || !offsets || !u_out))) return SWG_ERR_ARG;
     std::vector<int8_t> cprof(lq * SWG_KMER_CLASSES);
     swg_kmer_cprof(rows, idx, lq, cprof.data());
     std::vector<uint16_t> own;
@@ -828,6 +828,24 @@ extern "C" int swg_debug_prune_kmer_seg(const int8_t *rows, const int8_t *idx, s
     const SwgColMax cm = swg_prune_colmax(rows, idx, lq);
     for (size_t i = 0; i < n; ++i) u_out[i] = swg_kmer_bound_seg(table_out, k, (size_t)S, cm, flat + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
     return SWG_OK;
+}
+// test hooks: the unsegmented bound of k = 4 or 5; over S = 1..32 segments; and the second level's -- k = 4 with the
+// segments the refine kernel walks: 32 (the first level's widest), 64 or 128
+extern "C" int swg_debug_prune_kmer(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int k, const int8_t *flat,
+                                    const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out)
+{
+    return debug_prune_kmer(k == 4 || k == 5, rows, idx, lq, gap_open, gap_extend, k, 1, flat, offsets, n, table_out, u_out);
+}
+extern "C" int swg_debug_prune_kmer_seg(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int k, int S,
+                                        const int8_t *flat, const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out)
+{
+    return debug_prune_kmer((k == 4 || k == 5) && S >= 1 && S <= (int)SWG_KMER_MAX_SEGMENTS, rows, idx, lq, gap_open, gap_extend, k, S, flat, offsets, n,
+                            table_out, u_out);
+}
+extern "C" int swg_debug_prune_kmer_refine(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S2, const int8_t *flat,
+                                           const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out)
+{
+    return debug_prune_kmer(S2 == 32 || S2 == 64 || S2 == 128, rows, idx, lq, gap_open, gap_extend, 4, S2, flat, offsets, n, table_out, u_out);
 }
 
 // Which bound a pruned search cuts by: k = 1 (colmax), 4 or 5 (k-mer tables) and the S segments of its table (1: the
@@ -881,31 +899,37 @@ int swg_prune_kmer_choice(const SwgKmerAsk &a, int *segments)
     return k;
 }
 
-// test hook: in[0..5] = forced (option "prune_kmer"), pruned, lq, pair rows, table cells per second, fill pair rows per second
-// (0, 0: the library's own rates for this lq); out[0] = k.  Like swg_debug_prune_kmer and swg_debug_prune_kmer_read it
-// keeps its unsegmented meaning: the k of "prune_segments" = 1.
+// The questions of the three choice hooks below: in[0..5] = forced (option "prune_kmer"), pruned, lq, pair rows, table cells
+// per second, fill pair rows per second (0, 0: the library's own rates for this lq), then in[6] = the forced segments
+// (option "prune_segments") and in[7] = the forced refinement (option "prune_refine") where the hook has them (n_in words)
+static bool debug_kmer_ask(const int64_t *in, int64_t *out, int n_in, SwgKmerAsk *a)
+{
+    if (!in || !out) return false;
+    for (int i = 2; i < std::min(n_in, 7); ++i)
+        if (in[i] < 0) return false;
+    if (n_in > 7 && !swg_prune_refine_value_ok((long)in[7])) return false;
+    a->forced = (long)in[0], a->pruned = in[1] != 0, a->lq = (size_t)in[2], a->pair_rows = (uint64_t)in[3];
+    a->table_rate = in[4] ? (double)in[4] : SWG_KMER_TABLE_RATE;
+    a->fill_rate = in[5] ? (double)in[5] : swg_kmer_fill_rate(a->lq);
+    a->forced_segments = n_in > 6 ? (long)in[6] : 1;
+    a->forced_refine = n_in > 7 ? (long)in[7] : 0;
+    return true;
+}
+// test hook: out[0] = k.  Like swg_debug_prune_kmer and swg_debug_prune_kmer_read it keeps its unsegmented meaning: the k
+// of "prune_segments" = 1.
 extern "C" int swg_debug_prune_kmer_choice(const int64_t *in, int64_t *out)
 {
-    if (!in || !out || in[2] < 0 || in[3] < 0 || in[4] < 0 || in[5] < 0) return SWG_ERR_ARG;
     SwgKmerAsk a;
-    a.forced = (long)in[0], a.pruned = in[1] != 0, a.lq = (size_t)in[2], a.pair_rows = (uint64_t)in[3];
-    a.table_rate = in[4] ? (double)in[4] : SWG_KMER_TABLE_RATE;
-    a.fill_rate = in[5] ? (double)in[5] : swg_kmer_fill_rate(a.lq);
-    a.forced_segments = 1;
+    if (!debug_kmer_ask(in, out, 6, &a)) return SWG_ERR_ARG;
     out[0] = swg_prune_kmer_choice(a);
     return SWG_OK;
 }
-
-// ... and with in[6] = the forced segments (option "prune_segments"); out[0..3] = k, S, the table's bytes, whether a
-// context builds it (1) or refuses it as beyond its budget (0)
+// ... with the forced segments: out[0..3] = k, S, the table's bytes, whether a context builds it (1) or refuses it as
+// beyond its budget (0)
 extern "C" int swg_debug_prune_kmer_choice_seg(const int64_t *in, int64_t *out)
 {
-    if (!in || !out || in[2] < 0 || in[3] < 0 || in[4] < 0 || in[5] < 0 || in[6] < 0) return SWG_ERR_ARG;
     SwgKmerAsk a;
-    a.forced = (long)in[0], a.pruned = in[1] != 0, a.lq = (size_t)in[2], a.pair_rows = (uint64_t)in[3];
-    a.table_rate = in[4] ? (double)in[4] : SWG_KMER_TABLE_RATE;
-    a.fill_rate = in[5] ? (double)in[5] : swg_kmer_fill_rate(a.lq);
-    a.forced_segments = (long)in[6];
+    if (!debug_kmer_ask(in, out, 7, &a)) return SWG_ERR_ARG;
     int S = 0;
     out[0] = swg_prune_kmer_choice(a, &S);
     out[1] = S;
@@ -943,41 +967,15 @@ int swg_prune_refine_choice(const SwgKmerAsk &a, int k, int S)
     return cur->S2;
 }
 
-// test hook: swg_debug_prune_kmer_choice_seg's inputs and in[7] = the forced refinement (option "prune_refine");
-// out[0..2] = k, S, S2 (0: no second level)
+// test hook: ... and with the forced refinement: out[0..2] = k, S, S2 (0: no second level)
 extern "C" int swg_debug_prune_refine_choice(const int64_t *in, int64_t *out)
 {
-    if (!in || !out || in[2] < 0 || in[3] < 0 || in[4] < 0 || in[5] < 0 || in[6] < 0 || !swg_prune_refine_value_ok((long)in[7])) return SWG_ERR_ARG;
     SwgKmerAsk a;
-    a.forced = (long)in[0], a.pruned = in[1] != 0, a.lq = (size_t)in[2], a.pair_rows = (uint64_t)in[3];
-    a.table_rate = in[4] ? (double)in[4] : SWG_KMER_TABLE_RATE;
-    a.fill_rate = in[5] ? (double)in[5] : swg_kmer_fill_rate(a.lq);
-    a.forced_segments = (long)in[6];
-    a.forced_refine = (long)in[7];
+    if (!debug_kmer_ask(in, out, 8, &a)) return SWG_ERR_ARG;
     int S = 0;
     out[0] = swg_prune_kmer_choice(a, &S);
     out[1] = S;
     out[2] = swg_prune_refine_choice(a, (int)out[0], S);
-    return SWG_OK;
-}
-
-// test hook: the second level's table (22^4 x S2 uint16, or NULL) and its bound of each sequence: swg_debug_prune_kmer_seg
-// at k = 4 with the segments the refine kernel walks -- 32 (the first level's widest), 64 or 128
-extern "C" int swg_debug_prune_kmer_refine(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S2, const int8_t *flat,
-                                           const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out)
-{
-    if (!rows || lq == 0 || (S2 != 32 && S2 != 64 && S2 != 128) || gap_open > 0 || gap_extend > 0 || (n > 0 && (!flat || !offsets || !u_out)))
-        return SWG_ERR_ARG;
-    std::vector<int8_t> cprof(lq * SWG_KMER_CLASSES);
-    swg_kmer_cprof(rows, idx, lq, cprof.data());
-    std::vector<uint16_t> own;
-    if (!table_out) {
-        own.resize(swg_kmer_entries(4) * (size_t)S2);
-        table_out = own.data();
-    }
-    swg_kmer_table_seg(cprof.data(), lq, -(gap_open + gap_extend), -gap_extend, 4, (size_t)S2, table_out);
-    const SwgColMax cm = swg_prune_colmax(rows, idx, lq);
-    for (size_t i = 0; i < n; ++i) u_out[i] = swg_kmer_bound_seg(table_out, 4, (size_t)S2, cm, flat + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
     return SWG_OK;
 }
 

@@ -53,9 +53,20 @@ struct SwgDiagLayout {
     uint64_t d_scratch_rows = 0;
 };
 
-// Per-search device counters: words [0..15] work queue of the systolic engine, saturated count,
-// re-score queue, top-K; then the sharded pair queues of the diagonal engine's two classes and their
-// per-SIMD wavefront-rank counters.
+// Per-search device counters (swg_db::Bufs::d_counters; the first 32 words come back with every search, SwgSlot::h_counters):
+// the single words below, then the sharded pair queues of the diagonal engine's two classes and their per-SIMD
+// wavefront-rank counters.  The kernels receive pointers and never see the indices.
+#define SWG_WORD_WORK_QUEUE 0u      // work queue of the bin-based fills
+#define SWG_WORD_SATURATED 1u       // sequences that saturated the last 16-bit level (the int32 re-score's list length)
+#define SWG_WORD_RESCORE_QUEUE 2u   // work queue of the bin-based int32 re-score
+#define SWG_WORD_TOPK_COUNT 3u      // top-K: candidates kept,
+#define SWG_WORD_TOPK_THR 4u        // the threshold its histogram gave,
+#define SWG_WORD_TOPK_OVERFLOW 5u   // and whether that lay beyond the histogram
+#define SWG_WORD_FLAGGED_ROWS 6u    // rows of the flagged pairs / sequences, in units of 16 (the f16 veto's input)
+#define SWG_WORD_STAMPS(c) (8u + 4u * (uint32_t)(c)) // start / end wall-clock stamps of class c's single-pass launch (two 64-bit words)
+#define SWG_WORD_FLAGGED_SEQS 16u   // sequences the f16 fill flagged
+#define SWG_WORD_FLAGGED_PAIRS 17u  // ... and their pairs (the int16 re-run's list length)
+// (18 .. 25: SWG_PRUNE_WORD_*, SWG_ABOVE_WORD_COUNT below)
 #define SWG_QUEUE_WORD(c) (32u + (uint32_t)(c) * SWG_DYN_SHARDS * SWG_DYN_SHARD_STRIDE)
 #define SWG_RANK_WORD(c) (SWG_QUEUE_WORD(2) + (uint32_t)(c) * SWG_DYN_SIMD_SLOTS)
 #define SWG_COUNTER_BYTES ((size_t)SWG_RANK_WORD(2) * 4u)
@@ -180,12 +191,10 @@ struct swg_db {
     struct Bufs {
         int32_t *d_scores = nullptr;    // [n_bins*128] by sorted rank
         uint32_t *d_list = nullptr;     // [2*n_bins*128]: flagged pairs of the f16 fill, then (second half) saturated ranks
-        uint32_t *d_counters = nullptr; // [0] work queue, [1] saturated count, [2] re-score queue, [3..5] top-K, [6] flagged rows / 16,
-                                        // [8..15] class stamps, [16] sequences the f16 fill flagged, [17] their pairs
+        uint32_t *d_counters = nullptr; // SWG_WORD_*, SWG_QUEUE_WORD, SWG_RANK_WORD
         uint64_t *d_keys = nullptr;     // top-K candidate keys (SWG_TOPK_CAND_CAP)
         uint32_t *d_hist = nullptr;     // top-K score histogram
-        // a pruned search's score bound per pair, then the pair ids in order, then a cut stage's list (its kept pairs, at
-        // most a pair each) and the list's tile counts (swg_prune_pair_words; allocated by the first one)
+        // a pruned search's score bound per pair and what follows it (swg_prune_layout; allocated by the first one)
         uint32_t *d_pair_bound = nullptr;
         size_t pair_bound_cap = 0;        // pairs it has room for
         // swg_search_above's keys once a search met more than SWG_ABOVE_KEYS_FLOOR of them (until then d_keys serves)
@@ -264,12 +273,38 @@ struct SwgPrunePlan {
     bool fixed = false;      // a caller's threshold: every stage, the first included, is a list launch cut at fixed_T
     uint32_t fixed_T = 0;    // ... written once to the threshold word and never recomputed
 };
-// words of swg_db::Bufs::d_pair_bound for n pairs: bounds, ids, lists (a stage's from its first pair's word), one tile
-// count per SWG_PRUNE_TILE pairs, and {T, kept pairs} of the first SWG_PRUNE_STAGE_RECS cut stages (tests read them back)
+// swg_db::Bufs::d_pair_bound for n pairs: the bounds, the pair ids in order, the lists (a cut stage's kept pairs, from its
+// first pair's word), one tile count per SWG_PRUNE_TILE pairs, and {T, kept pairs} of the first SWG_PRUNE_STAGE_RECS cut
+// stages (tests read them back).  The allocation, the launch and the read-back hook all take it from here.
 #define SWG_PRUNE_STAGE_RECS 256u
-inline size_t swg_prune_tile_words(size_t n_pairs) { return n_pairs / SWG_PRUNE_TILE + 2; }
-inline size_t swg_prune_pair_words(size_t n_pairs) { return 3 * n_pairs + swg_prune_tile_words(n_pairs) + 2 * SWG_PRUNE_STAGE_RECS; }
+struct SwgPruneLayout {
+    uint32_t *bounds, *ids, *lists, *tiles, *recs;
+    size_t words; // of the whole buffer
+};
+inline SwgPruneLayout swg_prune_layout(uint32_t *base, size_t n_pairs)
+{
+    const size_t tiles = 3 * n_pairs, recs = tiles + n_pairs / SWG_PRUNE_TILE + 2;
+    auto at = [base](size_t word) { return base ? base + word : nullptr; }; // (no buffer yet: the total alone is asked for)
+    return SwgPruneLayout{base, at(n_pairs), at(2 * n_pairs), at(tiles), at(recs), recs + 2 * SWG_PRUNE_STAGE_RECS};
+}
 SwgPrunePlan swg_prune_plan(const SwgPruneAsk &a);
+// The stages of a pruned fill over the pair ranges `segments` (token_segments), and what is queued in front of each: the
+// one place that decides it (enqueue_pruned_fill in swg_api.cpp walks the list).  The stages are the segments, or the
+// head and the rest of a lone segment whose head is shorter than it.  Every stage but the first is cut at the K-th best
+// score so far, which a threshold kernel computes in front of it; under a caller's threshold (plan.fixed) the first is
+// cut too and no threshold kernel runs.  A cut is the prefix cut (plan.prefix_cut), or pair by pair: the refine pass
+// where there is a second level (plan.refine) -- behind the gate on the first of several stages under a caller's
+// threshold --, then the list.
+enum : uint32_t { SWG_STAGE_THRESHOLD = 1u, SWG_STAGE_PREFIX_CUT = 2u, SWG_STAGE_GATE = 4u, SWG_STAGE_REFINE = 8u, SWG_STAGE_LIST = 16u };
+struct SwgPruneStage {
+    uint32_t begin, end; // pairs
+    uint32_t segment;    // index into `segments`
+    uint32_t queued;     // SWG_STAGE_*: the kernels in front of the stage's fill launches, in that order (0: none, an uncut stage)
+};
+std::vector<SwgPruneStage> swg_prune_stages(const SwgPrunePlan &plan, const std::vector<std::pair<uint32_t, uint32_t>> &segments);
+// test hook: in[0..4] = head_pairs, fixed, refine, prefix_cut, the number of segments n, then n x {begin, end}; out: four
+// words per stage {begin, end, segment, queued}, copied while they fit cap stages; *n_out = the number of stages
+extern "C" int swg_debug_prune_stages(const int64_t *in, int64_t *out, size_t cap, size_t *n_out);
 // The automatic rule of a caller's threshold ("A caller's threshold"; profiles/search_above_ab.txt): the
 // bound, list and tally kernels of a stage cost tens of microseconds whatever the range holds, a list launch one
 // dependent load per claim; a range with at least SWG_PRUNE_ABOVE_AUTO_PAIRS pairs per resident lane group has fills
@@ -282,9 +317,7 @@ extern "C" int swg_debug_prune_plan(const int64_t *in, int64_t *out);
 extern "C" int swg_debug_prune_plan_above(const int64_t *in, int64_t *out);
 // The k-mer form of the bound (swg_internal.h has the classes): its host restatement, and the choice of k.
 void swg_kmer_cprof(const int8_t *rows, const int8_t *idx, size_t lq, int8_t *cprof);                 // cprof[lq][22]
-void swg_kmer_table(const int8_t *cprof, size_t lq, int g, int e, int k, uint16_t *table);            // table[22^k]
-uint64_t swg_kmer_bound(const uint16_t *table, int k, const SwgColMax &cm, const int8_t *seq, size_t len);
-// ... over S segments of the query's columns, the blocks taken in order (S = 1: the two above)
+// ... over S segments of the query's columns, the blocks taken in order (S = 1: the unordered sum over the whole query)
 void swg_kmer_table_seg(const int8_t *cprof, size_t lq, int g, int e, int k, size_t S, uint16_t *table); // table[22^k][S]
 uint64_t swg_kmer_bound_seg(const uint16_t *table, int k, size_t S, const SwgColMax &cm, const int8_t *seq, size_t len);
 // The two rates the automatic choice weighs, measured on one MI355X (profiles/prune_kmer_ab.txt): the table
@@ -303,7 +336,7 @@ struct SwgKmerAsk {
     uint64_t pair_rows = 0; // rows of the range's pairs
     double table_rate = SWG_KMER_TABLE_RATE, fill_rate = 0;
 };
-// whether a context builds the table of (k, S): within SWG_KMER_TABLE_BUDGET (ensure_kmer_table refuses the others)
+// whether a context builds the first-level table of (k, S): within SWG_KMER_TABLE_BUDGET (prepare_prune refuses the others)
 inline bool swg_kmer_table_admitted(int k, long S)
 {
     return S >= 1 && S <= (long)SWG_KMER_MAX_SEGMENTS && swg_kmer_entries(k) * (uint64_t)S * sizeof(uint16_t) <= SWG_KMER_TABLE_BUDGET;
@@ -402,6 +435,20 @@ struct SwgBatchPlan {
     size_t prof_row_bytes[2] = {0, 0};            // profile bytes of one grid row, per class
 };
 
+// A k-mer table on the device and what it was built with; one buffer per table, so searches that alternate between
+// two of them build each once per epoch.
+struct SwgKmerTable {
+    uint16_t *d = nullptr;
+    size_t cap = 0;     // entries allocated
+    uint64_t epoch = 0; // the (query, scoring) epoch it holds (0: nothing; a re-allocated table loses it)
+    int k = 0, segments = 0;
+    bool holds(uint64_t e, int k_, int S) const { return d && epoch == e && k == k_ && segments == S; }
+};
+// The bound a pruned search cuts by: k (0: not pruned), its segments S, the second level's S2 (0: none)
+struct SwgPruneChoice {
+    int kmer = 0, segments = 0, refine = 0;
+};
+
 // One search in flight: its timing events, host-side landing buffers and what swg_search_end
 // needs to finish it.  Device buffers are shared: everything of one context runs in stream
 // order, so search i+1 cannot touch them before search i has copied its results out.
@@ -478,32 +525,21 @@ struct swg_ctx {
     long opt_batch = 8, opt_batch_blocks = 0; // work queue: pairs one request claims where pairs are short (blocks; 0: about 40 us of work, from the geometry)
     long opt_prune = 1, opt_prune_head = 4; // hits-only pruning (options "prune", "prune_head": swg.h)
     bool in_batch = false;                  // a batch call is searching its queries one after another: never pruned
-    // the search last ended on this context: pruned or not, pairs skipped, their token blocks, the range's, the last threshold
-    uint64_t prune_last[5] = {0, 0, 0, 0, 0};
+    swg_prune_info prune_last = {}; // what the search last ended on this context left out (swg_prune_last)
+    SwgPruneChoice prune_choice;    // the bound of the search last begun on this context (plan_prune; tests)
     SwgColMax prune_colmax;                 // the bound's table for the current (query, scoring) ...
     uint64_t prune_colmax_epoch = 0;        // ... epoch (0: not built)
-    // the k-mer form of the bound (option "prune_kmer": 0 auto, 1 colmax, 4, 5): the class profile and the tables of k = 4
-    // and k = 5, device buffers built on the fill's stream in front of the first pruned search of an epoch that wants them
+    // the k-mer form of the bound (option "prune_kmer": 0 auto, 1 colmax, 4, 5): the class profile and the tables -- the
+    // first level's of k = 4 and k = 5, the second level's of k = 4 in 64 or 128 segments --, device buffers built on the
+    // fill's stream in front of the first pruned search of an epoch that wants them (ensure_kmer_table)
     long opt_prune_kmer = 0;
+    long opt_prune_segments = 0; // option "prune_segments": 0 auto, 1..32
+    long opt_prune_refine = 0;   // option "prune_refine": 0 auto, 1 off, 64, 128
+    long opt_prune_cut = 0;      // option "prune_cut": 0 pair by pair, 1 the prefix of the length order
     int8_t *d_kmer_cprof = nullptr;
     size_t d_kmer_cprof_cap = 0;
-    uint16_t *d_kmer_table[2] = {nullptr, nullptr};
-    uint64_t kmer_table_epoch[2] = {0, 0};
-    uint32_t kmer_table_segments[2] = {0, 0}; // the S each table was built with
-    size_t kmer_table_cap[2] = {0, 0};        // entries allocated
-    long opt_prune_segments = 0;              // option "prune_segments": 0 auto, 1..32
-    int prune_last_segments = 0;              // the S of the search last begun on this context
-    uint64_t kmer_builds = 0; // table builds queued so far (tests)
-    // the second level: its k = 4 table of 64 or 128 segments, keyed by (S2, epoch) and queued behind the first
-    long opt_prune_refine = 0; // option "prune_refine": 0 auto, 1 off, 64, 128
-    long opt_prune_cut = 0;    // option "prune_cut": 0 pair by pair, 1 the prefix of the length order
-    uint16_t *d_kmer_refine = nullptr;
-    uint64_t kmer_refine_epoch = 0;
-    uint32_t kmer_refine_segments = 0;
-    size_t kmer_refine_cap = 0;     // entries allocated
-    uint64_t kmer_refine_builds = 0; // builds of it queued so far (tests)
-    int prune_last_refine = 0;       // the S2 of the search last begun on this context (0: none)
-    int prune_last_kmer = 0;  // the k of the search last begun on this context (0: not pruned)
+    SwgKmerTable kmer_first[2], kmer_second; // [k - 4]
+    uint64_t kmer_builds = 0, kmer_refine_builds = 0; // builds queued so far of the first level's tables, of the second's (tests)
     uint32_t opt_seg_blocks = SWG_DYN_SEG_BLOCKS; // token blocks per launch of the multi-pass fill (option "segment_blocks": tests)
     // device state
     int8_t *d_sub = nullptr;

@@ -10,7 +10,8 @@
 // Every round draws a random table, an index query or a PSSM of 1..160 columns (fewer columns than segments among them),
 // gap scores and a database of sequences of 0..150 residues, and checks: the bound at 32, 64 and 128 segments is never
 // above the unsegmented one; the table's row maxima are the unsegmented table; segments without columns hold 0; other
-// segment counts are refused.  Exit status 0 = every round agreed.
+// segment counts are refused.  The stage list (swg_debug_prune_stages) is drawn too: its stages tile the segments in
+// order, and a caller's room for fewer stages than there are is respected.  Exit status 0 = every round agreed.
 #include "../seq-align-gpu_amd/csrc/swg_host_internal.h"
 
 #include <cstdio>
@@ -84,6 +85,25 @@ int main(int argc, char **argv)
         }
         in[7] = 32;
         CHECK(swg_debug_prune_refine_choice(in, out) == SWG_ERR_ARG);
+        // the stages of 1..4 segments under a random plan: they tile the segments in order
+        const int64_t n_seg = 1 + (int64_t)(rng() % 4);
+        std::vector<int64_t> ask = {(int64_t)(rng() % 12), (int64_t)(rng() & 1), 64 * (int64_t)(rng() % 3), (int64_t)(rng() & 1), n_seg};
+        for (int64_t i = 0, at = 0; i < n_seg; ++i) {
+            const int64_t end = at + 1 + (int64_t)(rng() % 9);
+            ask.push_back(at), ask.push_back(end), at = end;
+        }
+        std::vector<int64_t> st(4 * (2 * (size_t)n_seg + 1));
+        size_t n_st = 0;
+        CHECK(swg_debug_prune_stages(ask.data(), st.data(), st.size() / 4, &n_st) == SWG_OK);
+        CHECK(n_st >= (size_t)n_seg && n_st <= (size_t)n_seg + 1);
+        for (size_t i = 0; i < n_st; ++i) {
+            CHECK(st[4 * i] < st[4 * i + 1] && st[4 * i] == (i ? st[4 * i - 3] : 0));
+            CHECK(st[4 * i] >= ask[5 + 2 * st[4 * i + 2]] && st[4 * i + 1] <= ask[6 + 2 * st[4 * i + 2]]);
+        }
+        CHECK(st[4 * n_st - 3] == ask.back());
+        size_t n_again = 0;
+        CHECK(swg_debug_prune_stages(ask.data(), st.data(), 1, &n_again) == SWG_OK && n_again == n_st);
+        CHECK(swg_debug_prune_stages(ask.data(), nullptr, 0, &n_again) == SWG_OK && n_again == n_st);
     }
     printf("sanitize_prune_refine: %d rounds agreed\n", rounds);
     return 0;
