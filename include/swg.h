@@ -161,7 +161,9 @@ int swg_abi_version(void);
  * queries -- swg_search_multi*, swg_search_lists* -- with cols_per_wave or group_lanes set is searched one query after
  * another, each at that geometry | 1: the batch itself takes the two, as one class and in one pass, where every other
  * rule of its planner allows -- the tests' way to every batch instantiation; max_waves and workgroups still send it one
- * by one). */
+ * by one), "above_batch" (0 default: swg_search_above_multi* chooses between its two routes | 1: the one launch per
+ * class wherever the batch is admitted to it | 2: always one query after another; anything else is SWG_ERR_ARG -- see
+ * swg_search_above_multi). */
 int swg_set_option(swg_ctx *ctx, const char *key, long value);
 
 /* Replaces scoring_t for the path (reference src/alignment_scoring.h:21-37):
@@ -285,7 +287,7 @@ int swg_search_end(swg_ctx *ctx, int ticket, int32_t *scores_out, swg_hit *topk_
  *   pair_rows          the rows of all pairs of the fill, in the same unit
  * Options (swg_set_option): "prune" 0 off | 1 (default) auto: hits-only searches on the 16-bit lane-group work queue with
  * non-positive gap scores, one class and one cell form, whose range spans several launch segments (a database of some
- * millions of sequences) and has at least 4 x prune_head pairs per resident lane group; never a gapless search, a batch call (swg_search_multi*, swg_search_lists*) or anything on other engines |
+ * millions of sequences) and has at least 4 x prune_head pairs per resident lane group; never a gapless search, a query of swg_search_multi* or swg_search_lists* (swg_search_above_multi* searched one query after another is pruned per query, as swg_search_above is) or anything on other engines |
  * 2 DIAGNOSTIC, for tests: prune wherever it is structurally possible, ignoring the size rule, and also when scores are
  * requested -- the sequences of skipped pairs then report a score of 0, which is NOT their score.  "prune_head" (default 4):
  * under "prune" 2 a range of one segment runs its longest pairs first, unpruned -- at least k sequences and prune_head pairs per lane
@@ -388,6 +390,45 @@ int swg_search_above(swg_ctx *ctx, const swg_db *db, int32_t min_score, swg_hit 
 /* The same question of the gapless prefilter score (swg_search_gapless): never pruned, errors and outputs as above. */
 int swg_search_gapless_above(swg_ctx *ctx, const swg_db *db, int32_t min_score, swg_hit *hits_out, size_t cap, size_t *n_hits,
                              uint64_t *n_total, swg_stats *stats);
+
+/* Every hit at or above a score, for a BATCH of queries with a score each: what a pipeline with a thousand queries and an
+ * E-value cut-off asks (the cut-off turns into a raw score that depends on the query's length: INTEGRATION.md).  Queries
+ * and offsets as swg_search_multi takes them.  By definition row i is what swg_set_query(query i) +
+ * swg_search_above(ctx, db, min_scores[i], hits_out + i*cap, cap, &n_hits[i], &n_total[i], ..) gives:
+ *   n_total[i]       the sequences of this shard or view whose exact int32 score is >= min_scores[i];
+ *   hits_out + i*cap the best min(cap, n_total[i]) of them in the library's order (higher score first, ties by lower
+ *                    original index); n_hits[i] says how many were written, slots of a row past it are not written.
+ *                    cap is the same room for every query; cap = 0 with hits_out NULL is a pure count;
+ *   n_hits, n_total  each NULL or an array of n_queries; both are zeroed before anything can fail;
+ *   stats            NULL, or ONE summed record, as swg_search_multi gives it.
+ * The rows go into swg_align_hits_multi / swg_align_bounds_multi / swg_align_stats_multi unchanged, with k = cap.  The
+ * context's own query (index, PSSM or none) is left as it was.  n_queries = 0 is SWG_OK with nothing written.
+ * Errors: min_scores NULL or min_scores[i] < 1 is SWG_ERR_ARG (the message names the query); cap > 0 with hits_out NULL
+ * is SWG_ERR_ARG; everything else as swg_search_multi (an empty query, a residue outside 1..31, a database that is not
+ * resident, searches in flight: SWG_ERR_STATE).
+ * Two routes, option "above_batch" (swg_set_option): 1 the one launch per class of swg_search_multi for chunks of up to
+ * 256 queries, wherever that call would take it; its fill is NOT pruned, and each score row is compacted on the device
+ * against its own threshold, so that only counts and keys cross PCIe (swg_stats: fill_launches = the chunks, cell_form
+ * 3, 2 or 0) | 2 one query after another, each a plain swg_search_above whose fill is cut at its own min_scores[i]
+ * wherever a single swg_search_above would be (option "prune"; swg_stats sums the searches, fill_launches 0) | 0
+ * (default) automatic: the launch where the batch is admitted to it and swg_search_above of the batch's longest query
+ * on this database would not be pruned, one by one otherwise.  Answers are the same on both routes.
+ * swg_prune_last after the call: pruned = 1 if any query's search was pruned; pairs_skipped, pair_rows_skipped and
+ * pair_rows summed over the batch's queries (the one launch: 0, 0, 0 and pruned 0); threshold = the last query's
+ * min_score.  topk_ms is the read-out's kernels plus the host's sort. */
+int swg_search_above_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets, size_t n_queries,
+                           const int32_t *min_scores, swg_hit *hits_out, size_t cap, size_t *n_hits, uint64_t *n_total, swg_stats *stats);
+/* The same with position-specific queries: pssms and offsets (which count POSITIONS) as swg_search_multi_pssm takes them. */
+int swg_search_above_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets, size_t n_queries,
+                                const int32_t *min_scores, swg_hit *hits_out, size_t cap, size_t *n_hits, uint64_t *n_total, swg_stats *stats);
+/* The same question of the gapless prefilter score, row i as swg_search_gapless_above gives it: always one query after
+ * another (the batch launch has no gapless cells) and never pruned. */
+int swg_search_gapless_above_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets, size_t n_queries,
+                                   const int32_t *min_scores, swg_hit *hits_out, size_t cap, size_t *n_hits, uint64_t *n_total,
+                                   swg_stats *stats);
+int swg_search_gapless_above_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets, size_t n_queries,
+                                        const int32_t *min_scores, swg_hit *hits_out, size_t cap, size_t *n_hits, uint64_t *n_total,
+                                        swg_stats *stats);
 
 /* Every query of a batch against ITS OWN candidate list in one pass: what a prefilter, a PSI-BLAST iteration or a list
  * of family members per query hands to the alignment step.  Query i is queries[q_offsets[i] .. q_offsets[i+1]) as

@@ -36,7 +36,8 @@ ABI_SYMBOLS = [
     "swg_db_free", "swg_db_save", "swg_db_load", "swg_db_count", "swg_db_total_count", "swg_db_residues",
     "swg_db_packed_bytes", "swg_db_order", "swg_search", "swg_search_begin", "swg_search_end", "swg_search_multi",
     "swg_search_multi_pssm", "swg_search_lists", "swg_search_lists_pssm", "swg_search_gapless", "swg_search_gapless_multi",
-    "swg_search_gapless_multi_pssm", "swg_search_above", "swg_search_gapless_above", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_align_hits_multi",
+    "swg_search_gapless_multi_pssm", "swg_search_above", "swg_search_gapless_above", "swg_search_above_multi", "swg_search_above_multi_pssm",
+    "swg_search_gapless_above_multi", "swg_search_gapless_above_multi_pssm", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_align_hits_multi",
     "swg_align_hits_multi_pssm", "swg_align_ops_bound_multi", "swg_align_bounds", "swg_align_bounds_multi",
     "swg_align_bounds_multi_pssm", "swg_align_stats", "swg_align_stats_multi", "swg_align_stats_multi_pssm", "swg_hit_key",
     "swg_key_hit", "swg_topk_merge_keys",
@@ -151,6 +152,8 @@ _sig("swg_search_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp
 _sig("swg_search_gapless", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(Stats)])
 for _name in ("swg_search_above", "swg_search_gapless_above"):
     _sig(_name, C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(Stats)])
+for _name in ("swg_search_above_multi", "swg_search_above_multi_pssm", "swg_search_gapless_above_multi", "swg_search_gapless_above_multi_pssm"):
+    _sig(_name, C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, C.POINTER(Stats)])
 _sig("swg_search_gapless_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
 _sig("swg_search_gapless_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
 _sig("swg_search_lists", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.POINTER(Stats)])
@@ -234,6 +237,7 @@ _sig("swg_prune_last", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_bound", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp])
 _sig("swg_debug_prune_plan", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_plan_above", C.c_int, [_vp, _vp])
+_sig("swg_debug_above_multi_route", C.c_int, [C.c_long, C.c_int, C.c_int])
 _sig("swg_debug_prune_stages", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 _sig("swg_debug_prune_kmer", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp])
 _sig("swg_debug_prune_kmer_choice", C.c_int, [_vp, _vp])
@@ -595,6 +599,17 @@ def debug_prune_plan_above(**ask):
     out = np.zeros(2, dtype=np.int64)
     _check(lib.swg_debug_prune_plan_above(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
     return bool(out[0]), int(out[1])
+
+
+def debug_above_multi_route(option=0, admitted=True, single_pruned=False):
+    """Test hook (no device needed): the route search_above_multi takes (swg_above_multi_route) under option "above_batch"
+    for a batch that plan_batch admits to the one launch or not, where swg_search_above of its longest query on the
+    database would be pruned or not.  -> 1 (one launch per class) or 2 (one query after another); an option outside
+    0..2 raises SwgError."""
+    rc = lib.swg_debug_above_multi_route(int(option), 1 if admitted else 0, 1 if single_pruned else 0)
+    if rc < 0:
+        _check(rc)
+    return rc
 
 
 PRUNE_STAGE_QUEUED = ("threshold", "prefix_cut", "gate", "refine", "list")   # bits 0..4 of a stage's fourth word, in queue order
@@ -964,6 +979,49 @@ class Context:
         _check(rc, self.handle)
         a = np.frombuffer(hits, dtype=np.dtype([("score", np.int32), ("index", np.uint32)]), count=nh.value)
         return list(zip(a["score"].tolist(), a["index"].tolist())), int(nt.value), st.as_dict()
+
+    def search_above_multi(self, db, queries, min_scores, cap=None, gapless=False):
+        """search_above for a list of index queries, each with its own least score (min_scores: a list, or one int for all):
+        -> (hits: list of lists of (score, index) -- per query the best min(cap, n_total[i]) in the library's order --,
+        n_total: list of int, stats dict).  cap None: room for every sequence of db; cap 0: counts only.  gapless: the
+        gapless prefilter score.  The context's own query is kept (swg_search_above_multi,
+        swg_search_gapless_above_multi)."""
+        nq = len(queries)
+        qoff = np.zeros(nq + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in queries])
+        qflat = np.ascontiguousarray(np.concatenate(queries) if nq else np.zeros(0), dtype=np.int8)
+        fn = lib.swg_search_gapless_above_multi if gapless else lib.swg_search_above_multi
+        return self._above_multi(fn, db, qflat, qoff, min_scores, cap)
+
+    def search_above_multi_pssm(self, db, pssms, min_scores, cap=None, gapless=False):
+        """search_above_multi with position-specific queries: pssms as search_multi_pssm takes them."""
+        nq = len(pssms)
+        rows = [_pssm(p)[0] for p in pssms]
+        qoff = np.zeros(nq + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([r.shape[0] for r in rows])
+        pflat = np.ascontiguousarray(np.concatenate(rows) if nq else np.zeros((0, 32)), dtype=np.int8)
+        fn = lib.swg_search_gapless_above_multi_pssm if gapless else lib.swg_search_above_multi_pssm
+        return self._above_multi(fn, db, pflat, qoff, min_scores, cap)
+
+    def _above_multi(self, fn, db, qflat, qoff, min_scores, cap):
+        nq = len(qoff) - 1
+        ms = np.full(nq, min_scores, dtype=np.int32) if np.isscalar(min_scores) else np.ascontiguousarray(min_scores, dtype=np.int32)
+        if ms.shape != (nq,):
+            raise ValueError("min_scores: %s for %d queries" % (ms.shape, nq))
+        ms = np.concatenate([ms, np.zeros(1, dtype=np.int32)])    # (never an empty buffer)
+        cap = db.count if cap is None else int(cap)
+        hits = np.zeros(max(nq * cap, 1), dtype=np.dtype([("score", np.int32), ("index", np.uint32)]))
+        nh = np.zeros(max(nq, 1), dtype=np.uintp)
+        nt = np.zeros(max(nq, 1), dtype=np.uint64)
+        st = Stats()
+        rc = fn(self.handle, db.handle, qflat.ctypes.data_as(_vp), qoff.ctypes.data_as(_vp), nq, ms.ctypes.data_as(_vp),
+                hits.ctypes.data_as(_vp) if cap else None, cap, nh.ctypes.data_as(_vp), nt.ctypes.data_as(_vp), C.byref(st))
+        _check(rc, self.handle)
+        out = []
+        for i in range(nq):
+            a = hits[i * cap:i * cap + int(nh[i])]
+            out.append(list(zip(a["score"].tolist(), a["index"].tolist())))
+        return out, [int(v) for v in nt[:nq]], st.as_dict()
 
     def search_gapless_multi(self, db, queries, k=0, want_scores=True):
         """search_gapless for a list of index queries, shaped like search_multi; the context's own query is kept."""

@@ -105,7 +105,8 @@ template <class F> static int ctx_guarded(swg_ctx *ctx, const char *what, F &&f)
 // Test hook (csrc/swg_host_internal.h, not part of the public ABI): the next time the named site is reached it
 // throws std::bad_alloc as a failed allocation there would.  Sites: 1 = body of swg_search_begin, 2 = body of
 // swg_search_end, 3 = the fall-back key vector of swg_search_end (reached only when the device top-K could not be
-// used).  One shot: the hook clears itself when it fires.
+// used).  One shot: the hook clears itself when it fires.  Site 4 is not an exception: the next growth of
+// swg_search_above_multi's key pool is refused as if the device had no room (above_multi_pool).
 static int g_fail_alloc_site = 0;
 extern "C" void swg_debug_fail_alloc(int site) { g_fail_alloc_site = site; }
 static inline void fail_alloc_here(int site)
@@ -369,6 +370,10 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
         if (value != 0 && value != 1)
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_cut must be 0 (a stage's pairs are cut one by one) or 1 (the prefix of the length order)");
         ctx->opt_prune_cut = value;
+    } else if (!strcmp(key, "above_batch")) {
+        if (value < 0 || value > 2)
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "above_batch must be 0 (auto), 1 (one launch wherever the batch is admitted) or 2 (one query after another)");
+        ctx->opt_above_batch = value;
     } else if (!strcmp(key, "q32_waves")) {
         ctx->opt_q32_waves = value;
     } else if (!strcmp(key, "wave_budget")) {
@@ -3043,10 +3048,16 @@ struct MultiBufs {
     std::vector<int32_t> h_scores;
     std::vector<uint32_t> qoff32, order, h_meta; // order: row r of the score buffer belongs to query order[r] of the chunk
     std::vector<uint64_t> h_cand;
+    // swg_search_above_multi: per score row of a chunk its threshold, count and cursor (d_above_words: three arrays of
+    // above_rows words) and its offset into the key pool (d_above_off), and the pool of the chunk's keys, which grows
+    // with the answers (above_keys_cap keys: committed only once the allocation stands)
+    uint32_t *d_above_words = nullptr;
+    uint64_t *d_above_off = nullptr, *d_above_keys = nullptr;
+    size_t above_rows = 0, above_keys_cap = 0;
     ~MultiBufs()
     {
         for (void *p : {(void *)d_hist, (void *)d_meta, (void *)d_cand, (void *)d_q, (void *)d_qoff, (void *)d_order, (void *)d_prof[0],
-                        (void *)d_prof[1], (void *)d_scores, (void *)d_cnt})
+                        (void *)d_prof[1], (void *)d_scores, (void *)d_cnt, (void *)d_above_words, (void *)d_above_off, (void *)d_above_keys})
             (void)hipFree(p);
     }
 };
@@ -3296,8 +3307,12 @@ namespace {
 struct KeptQuery { // the context's own query across a batch searched one by one
     bool pssm;
     std::vector<int8_t> bytes;
-    swg_ctx *owner; // (a batch's searches are never pruned: in_batch for as long as this object lives)
-    explicit KeptQuery(swg_ctx *ctx) : pssm(ctx->query_pssm), bytes(ctx->query_pssm ? ctx->pssm : ctx->query), owner(ctx) { ctx->in_batch = true; }
+    swg_ctx *owner; // (a batch's searches are never pruned: in_batch for as long as this object lives -- unless each of them is
+                    // a search of its own right, batch_member false: swg_search_above_multi's queries, cut at their own scores)
+    explicit KeptQuery(swg_ctx *ctx, bool batch_member = true) : pssm(ctx->query_pssm), bytes(ctx->query_pssm ? ctx->pssm : ctx->query), owner(ctx)
+    {
+        ctx->in_batch = batch_member;
+    }
     ~KeptQuery() { owner->in_batch = false; }
     KeptQuery(const KeptQuery &) = delete;
     KeptQuery &operator=(const KeptQuery &) = delete;
@@ -3732,6 +3747,282 @@ extern "C" int swg_search_gapless_multi_pssm(swg_ctx *ctx, const swg_db *db, con
     return ctx_guarded(ctx, "swg_search_gapless_multi_pssm", [&]() -> int {
         return search_gapless_multi_impl(ctx, const_cast<swg_db *>(db), MultiQueries{pssms, q_offsets, n_queries, true, "swg_search_gapless_multi_pssm"},
                                          scores_out, topk_out, k, n_hits, stats);
+    });
+}
+
+// ---------------------------------------------------------------------------
+// every hit at or above a score, per query of a batch
+// ---------------------------------------------------------------------------
+// swg_search_above_multi*: row i is what swg_set_query(query i) + swg_search_above(min_scores[i]) gives.  Two routes
+// (swg_above_multi_route decides; DESIGN 4.2.1, "A caller's threshold, per query of a batch"):
+//   1  the batch launch of swg_search_multi as it stands (plan_batch admits it, batch_stage_chunk and batch_launch_chunk
+//      fill it, unpruned), and a read-out of its own: every score row of a chunk is compacted on the device against its
+//      own threshold, and only counts and keys come back;
+//   2  one query after another, each a plain swg_search_above -- NOT a batch member (ctx->in_batch stays false), so its
+//      fill is cut at its own min_scores[i] wherever swg_prune_plan admits a caller's threshold.
+// The gapless forms always take route 2 (the batch kernels have no gapless cells).
+extern "C" int swg_debug_above_multi_route(long option, int admitted, int single_pruned)
+{
+    if (option < 0 || option > 2) return SWG_ERR_ARG;
+    return swg_above_multi_route(option, admitted != 0, single_pruned != 0);
+}
+
+namespace {
+struct AboveMultiOut { // the caller's arrays: rows of cap hits, and per query what was written and what there is
+    const int32_t *min_scores;
+    swg_hit *hits_out;
+    size_t cap;
+    size_t *n_hits;
+    uint64_t *n_total;
+};
+} // namespace
+
+// Whether swg_search_above of the batch's longest query would be pruned on this database under the context's options:
+// plan_search and plan_prune asked with that query as the context's host copy (no device copy, no tuner's trials, nothing
+// queued), and everything put back.
+static bool above_multi_single_pruned(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, const int32_t *min_scores)
+{
+    if (ctx->opt_prune == 0 || db->n_bins == 0) return false;
+    size_t L = 0;
+    for (size_t i = 1; i < mq.n; ++i)
+        if (mq.len(i) > mq.len(L)) L = i;
+    std::vector<int8_t> kept_query, kept_pssm;
+    kept_query.swap(ctx->query);
+    kept_pssm.swap(ctx->pssm);
+    const bool kept_is_pssm = ctx->query_pssm;
+    const SwgPruneChoice kept_choice = ctx->prune_choice;
+    const std::string kept_err = ctx->err;
+    (mq.pssm ? ctx->pssm : ctx->query).assign(mq.at(L), mq.at(L) + mq.len(L) * mq.row_bytes());
+    ctx->query_pssm = mq.pssm;
+    bool pruned = false;
+    {
+        const AboveMode mode(ctx, min_scores[L]);
+        SwgSearchPlan plan;
+        pruned = plan_search(ctx, db, false, &plan) == SWG_OK && plan_prune(ctx, db, false, 0, &plan) == SWG_OK && plan.prune.on;
+    }
+    ctx->query.swap(kept_query);
+    ctx->pssm.swap(kept_pssm);
+    ctx->query_pssm = kept_is_pssm;
+    ctx->prune_choice = kept_choice;
+    ctx->err = kept_err;
+    return pruned;
+}
+
+// Route 2.  swg_prune_last afterwards: the sums over the batch's searches, pruned if any was.
+static int above_multi_one_by_one(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, bool gapless, const AboveMultiOut &o, swg_stats *st)
+{
+    const KeptQuery keep(ctx, false);
+    swg_prune_info sum = swg_prune_info();
+    int rc = SWG_OK;
+    for (size_t i = 0; i < mq.n && rc == SWG_OK; ++i) {
+        swg_stats one;
+        memset(&one, 0, sizeof one);
+        rc = mq.pssm ? swg_set_query_pssm(ctx, mq.at(i), mq.len(i)) : swg_set_query(ctx, mq.at(i), mq.len(i));
+        if (rc == SWG_OK)
+            rc = search_above_impl(ctx, db, gapless, mq.fn, o.min_scores[i], o.hits_out ? o.hits_out + i * o.cap : nullptr, o.cap,
+                                   o.n_hits ? o.n_hits + i : nullptr, o.n_total ? o.n_total + i : nullptr, &one);
+        if (rc != SWG_OK) break;
+        add_one_search(st, one);
+        sum.pruned |= ctx->prune_last.pruned;
+        sum.pairs_skipped += ctx->prune_last.pairs_skipped;
+        sum.pair_rows_skipped += ctx->prune_last.pair_rows_skipped;
+        sum.pair_rows += ctx->prune_last.pair_rows;
+    }
+    sum.threshold = (uint32_t)o.min_scores[mq.n - 1];
+    ctx->prune_last = sum;
+    return keep.restore(ctx, rc);
+}
+
+// The per-row words of the read-out, for the first chunk (the largest), and a key pool to start with.
+static int above_multi_allocate(swg_ctx *ctx, const SwgBatchPlan &P, MultiBufs *B)
+{
+    HIP_TRY(ctx, hipMalloc(&B->d_above_words, 3 * P.first_chunk * sizeof(uint32_t)));
+    HIP_TRY(ctx, hipMalloc(&B->d_above_off, P.first_chunk * sizeof(uint64_t)));
+    B->above_rows = P.first_chunk;
+    return SWG_OK;
+}
+
+// Room for `need` keys in the chunk's pool: false where the device has none (the caller then selects on the host).
+static bool above_multi_pool(MultiBufs *B, size_t need)
+{
+    if (need <= B->above_keys_cap) return true;
+    const bool refuse = g_fail_alloc_site == 4; // (swg_debug_fail_alloc site 4: this allocation fails, once)
+    if (refuse) g_fail_alloc_site = 0;
+    const size_t want = std::max<size_t>(need + need / 4, SWG_ABOVE_KEYS_FLOOR);
+    uint64_t *grown = nullptr;
+    if (refuse || hipMalloc(&grown, want * sizeof(uint64_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    (void)hipFree(B->d_above_keys);
+    B->d_above_keys = grown;
+    B->above_keys_cap = want;
+    return true;
+}
+
+// What a chunk's fill left, to the caller: each score row r < Qb (query order[r] of the chunk; the row of an odd pair's
+// absent partner is never read) against its own threshold.  The count kernel's answers are the n_total; where the caller
+// takes hits the rows' keys are laid end to end in the pool, copied back and sorted per row as 64-bit keys (the appended
+// order is not deterministic, the sorted one is).  Adds the chunk's times to *st.
+static int above_multi_deliver_chunk(swg_ctx *ctx, const swg_db *db, const SwgBatchPlan &P, MultiBufs *B, size_t q0, size_t Qb, const AboveMultiOut &o,
+                                     swg_stats *st)
+{
+    hipStream_t s = ctx->stream;
+    const size_t n_slots = P.n_slots;
+    if (Qb > B->above_rows || Qb > B->rows_scores)
+        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_search_above_multi: the read-out indexes %zu rows, its buffers hold %zu", Qb,
+                                 std::min(B->above_rows, B->rows_scores));
+    uint32_t *d_thr = B->d_above_words, *d_counts = d_thr + B->above_rows, *d_cursors = d_counts + B->above_rows;
+    std::vector<int32_t> thr(Qb); // (row order, not query order)
+    for (size_t r = 0; r < Qb; ++r) thr[r] = o.min_scores[q0 + B->order[r]];
+    std::vector<uint32_t> counts(Qb);
+    HIP_TRY(ctx, hipMemcpyAsync(d_thr, thr.data(), Qb * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, swg_launch_above_rows_count(B->d_scores, n_slots, db->d_order, (uint32_t)n_slots, (uint32_t)Qb, (const int32_t *)d_thr, d_counts, s));
+    HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[3], s));
+    HIP_TRY(ctx, hipMemcpyAsync(counts.data(), d_counts, Qb * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, spin_sync(ctx, s));
+    float ms = 0.f, ms_read = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->cur->ev[1], ctx->cur->ev[2]));
+    st->fill_ms += ms;
+    st->total_ms += ms;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms_read, ctx->cur->ev[2], ctx->cur->ev[3]));
+    std::vector<uint64_t> offsets(Qb), keys;
+    uint64_t total = 0;
+    for (size_t r = 0; r < Qb; ++r) {
+        const size_t i = q0 + B->order[r];
+        if (o.n_total) o.n_total[i] = counts[r];
+        offsets[r] = total;
+        total += counts[r];
+    }
+    double host_ms = 0.0;
+    if (o.cap > 0 && total > 0) {
+        const bool on_device = above_multi_pool(B, total);
+        if (on_device) {
+            HIP_TRY(ctx, hipMemcpyAsync(B->d_above_off, offsets.data(), Qb * 8, hipMemcpyHostToDevice, s));
+            HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[4], s));
+            HIP_TRY(ctx, swg_launch_above_rows_scatter(B->d_scores, n_slots, db->d_order, (uint32_t)n_slots, (uint32_t)Qb, (const int32_t *)d_thr,
+                                                       d_counts, B->d_above_off, d_cursors, B->d_above_keys, B->above_keys_cap, s));
+            HIP_TRY(ctx, hipEventRecord(ctx->cur->ev[5], s));
+            keys.resize(total);
+            HIP_TRY(ctx, hipMemcpyAsync(keys.data(), B->d_above_keys, total * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, spin_sync(ctx, s));
+            HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->cur->ev[4], ctx->cur->ev[5]));
+            ms_read += ms;
+        } else { // no room for the keys on the device: this chunk's score rows to the host, selected there
+            B->h_scores.resize(Qb * n_slots);
+            HIP_TRY(ctx, hipMemcpyAsync(B->h_scores.data(), B->d_scores, Qb * n_slots * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, spin_sync(ctx, s));
+        }
+        const auto t0 = std::chrono::steady_clock::now();
+        for (size_t r = 0; r < Qb; ++r) {
+            const size_t i = q0 + B->order[r], m = std::min<size_t>(o.cap, counts[r]);
+            if (!on_device) {
+                keys.clear();
+                const int32_t *row = B->h_scores.data() + r * n_slots;
+                for (size_t j = 0; j < n_slots; ++j)
+                    if (db->order[j] != 0xFFFFFFFFu && row[j] >= thr[r]) keys.push_back(swg_hit_key(row[j], db->order[j]));
+            }
+            uint64_t *c = on_device ? keys.data() + offsets[r] : keys.data();
+            const size_t nc = on_device ? counts[r] : keys.size(), w = std::min(m, nc);
+            std::partial_sort(c, c + w, c + nc, std::greater<uint64_t>());
+            for (size_t j = 0; j < w; ++j) swg_key_hit(c[j], &o.hits_out[i * o.cap + j]);
+            if (o.n_hits) o.n_hits[i] = w;
+        }
+        host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    st->topk_ms += ms_read + host_ms;
+    st->total_ms += ms_read;
+    return SWG_OK;
+}
+
+static int search_above_multi_impl(swg_ctx *ctx, swg_db *db, const MultiQueries &mq, bool gapless, const AboveMultiOut &o, swg_stats *stats)
+{
+    const char *fn = mq.fn;
+    for (size_t i = 0; i < mq.n; ++i) { // (zeroed before anything can fail)
+        if (o.n_hits) o.n_hits[i] = 0;
+        if (o.n_total) o.n_total[i] = 0;
+    }
+    swg_stats st;
+    memset(&st, 0, sizeof st);
+    if (!ctx || !db || !o.min_scores) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: NULL argument", fn);
+    if (o.cap > 0 && !o.hits_out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: cap > 0 but hits_out NULL", fn);
+    int rc = validate_batch(ctx, db, mq, o.hits_out, o.cap, &st);
+    if (rc != SWG_OK) return rc;
+    for (size_t i = 0; i < mq.n; ++i)
+        if (o.min_scores[i] < 1)
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: min_score %d of query %zu must be at least 1 (every sequence scores at least 0)", fn,
+                                     o.min_scores[i], i);
+    if (stats) *stats = st;
+    if (mq.n == 0) return SWG_OK;
+    ctx->prune_last = swg_prune_info();
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    SwgBatchPlan P;
+    if (!gapless && ctx->opt_above_batch != 2 && (rc = plan_batch(ctx, db, mq, false, 0, &P)) != SWG_OK) return rc;
+    const bool single_pruned = P.one_launch && ctx->opt_above_batch == 0 && above_multi_single_pruned(ctx, db, mq, o.min_scores);
+    if (swg_above_multi_route(ctx->opt_above_batch, P.one_launch, single_pruned) == 2) {
+        rc = above_multi_one_by_one(ctx, db, mq, gapless, o, &st);
+        if (stats) *stats = st;
+        return rc;
+    }
+    MultiBufs B;
+    ctx->cur = &ctx->slots[0];
+    rc = batch_allocate(ctx, P, &B);
+    if (rc == SWG_OK) rc = above_multi_allocate(ctx, P, &B);
+    int chunks = 0;
+    for (size_t q0 = 0; q0 < mq.n && rc == SWG_OK; q0 += P.chunk_queries, ++chunks) {
+        const size_t Qb = std::min(P.chunk_queries, mq.n - q0);
+        const size_t Qrows = P.grid_rows(Qb);
+        rc = multi_rows_ok(ctx, B, P, Qb, Qrows);
+        if (rc == SWG_OK) rc = batch_stage_chunk(ctx, P, mq, q0, Qb, &B);
+        if (rc == SWG_OK) rc = batch_launch_chunk(ctx, db, P, B, Qb, Qrows);
+        if (rc == SWG_OK) rc = above_multi_deliver_chunk(ctx, db, P, &B, q0, Qb, o, &st);
+    }
+    if (rc != SWG_OK) return rc;
+    batch_report(ctx, db, P, mq.n, &st);
+    st.fill_launches = chunks; // (launches of the bulk class's fill kernel: one per chunk)
+    ctx->prune_last.threshold = (uint32_t)o.min_scores[mq.n - 1]; // (nothing pruned; pair_rows is not counted on this route)
+    if (stats) *stats = st;
+    return SWG_OK;
+}
+
+extern "C" int swg_search_above_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets, size_t n_queries,
+                                      const int32_t *min_scores, swg_hit *hits_out, size_t cap, size_t *n_hits, uint64_t *n_total, swg_stats *stats)
+{
+    return ctx_guarded(ctx, "swg_search_above_multi", [&]() -> int {
+        return search_above_multi_impl(ctx, const_cast<swg_db *>(db), MultiQueries{queries, q_offsets, n_queries, false, "swg_search_above_multi"}, false,
+                                       AboveMultiOut{min_scores, hits_out, cap, n_hits, n_total}, stats);
+    });
+}
+
+extern "C" int swg_search_above_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets, size_t n_queries,
+                                           const int32_t *min_scores, swg_hit *hits_out, size_t cap, size_t *n_hits, uint64_t *n_total,
+                                           swg_stats *stats)
+{
+    return ctx_guarded(ctx, "swg_search_above_multi_pssm", [&]() -> int {
+        return search_above_multi_impl(ctx, const_cast<swg_db *>(db), MultiQueries{pssms, q_offsets, n_queries, true, "swg_search_above_multi_pssm"},
+                                       false, AboveMultiOut{min_scores, hits_out, cap, n_hits, n_total}, stats);
+    });
+}
+
+extern "C" int swg_search_gapless_above_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets, size_t n_queries,
+                                              const int32_t *min_scores, swg_hit *hits_out, size_t cap, size_t *n_hits, uint64_t *n_total,
+                                              swg_stats *stats)
+{
+    return ctx_guarded(ctx, "swg_search_gapless_above_multi", [&]() -> int {
+        return search_above_multi_impl(ctx, const_cast<swg_db *>(db),
+                                       MultiQueries{queries, q_offsets, n_queries, false, "swg_search_gapless_above_multi"}, true,
+                                       AboveMultiOut{min_scores, hits_out, cap, n_hits, n_total}, stats);
+    });
+}
+
+extern "C" int swg_search_gapless_above_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets, size_t n_queries,
+                                                   const int32_t *min_scores, swg_hit *hits_out, size_t cap, size_t *n_hits, uint64_t *n_total,
+                                                   swg_stats *stats)
+{
+    return ctx_guarded(ctx, "swg_search_gapless_above_multi_pssm", [&]() -> int {
+        return search_above_multi_impl(ctx, const_cast<swg_db *>(db),
+                                       MultiQueries{pssms, q_offsets, n_queries, true, "swg_search_gapless_above_multi_pssm"}, true,
+                                       AboveMultiOut{min_scores, hits_out, cap, n_hits, n_total}, stats);
     });
 }
 

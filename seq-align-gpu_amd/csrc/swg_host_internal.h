@@ -311,6 +311,20 @@ extern "C" int swg_debug_prune_stages(const int64_t *in, int64_t *out, size_t ca
 // long enough for both to vanish in them.
 #define SWG_PRUNE_ABOVE_AUTO_PAIRS 16u
 inline bool swg_prune_above_auto(uint64_t range_pairs, uint64_t groups) { return range_pairs >= SWG_PRUNE_ABOVE_AUTO_PAIRS * std::max<uint64_t>(1, groups); }
+// How swg_search_above_multi* searches a batch ("A caller's threshold, per query of a batch"): 1 the one
+// launch per class with the per-row read-out, 2 one query after another, each a plain swg_search_above.  option: "above_batch"
+// (0 automatic, 1 the launch wherever plan_batch admits the batch, 2 always one by one); admitted: plan_batch's answer;
+// single_pruned: whether swg_search_above of the batch's longest query on this database would be pruned under the
+// context's "prune".  The automatic rule takes the launch where it is admitted and that search would not be pruned:
+// the launch fills every pair for every query, a pruned search only the pairs whose bound reaches its threshold.
+inline int swg_above_multi_route(long option, bool admitted, bool single_pruned)
+{
+    if (option == 2 || !admitted) return 2;
+    if (option == 1) return 1;
+    return single_pruned ? 2 : 1;
+}
+// test hook: the route (1 | 2), or SWG_ERR_ARG for an option outside 0..2
+extern "C" int swg_debug_above_multi_route(long option, int admitted, int single_pruned);
 extern "C" int swg_debug_prune_bound(const int8_t *rows, const int8_t *idx, size_t lq, const int8_t *flat, const uint64_t *offsets, size_t n,
                                      uint8_t *colmax_out, uint64_t *u_out);
 extern "C" int swg_debug_prune_plan(const int64_t *in, int64_t *out);
@@ -525,6 +539,7 @@ struct swg_ctx {
     long opt_batch = 8, opt_batch_blocks = 0; // work queue: pairs one request claims where pairs are short (blocks; 0: about 40 us of work, from the geometry)
     long opt_prune = 1, opt_prune_head = 4; // hits-only pruning (options "prune", "prune_head": swg.h)
     bool in_batch = false;                  // a batch call is searching its queries one after another: never pruned
+    long opt_above_batch = 0;               // option "above_batch": the route of swg_search_above_multi* (swg_above_multi_route)
     swg_prune_info prune_last = {}; // what the search last ended on this context left out (swg_prune_last)
     SwgPruneChoice prune_choice;    // the bound of the search last begun on this context (plan_prune; tests)
     SwgColMax prune_colmax;                 // the bound's table for the current (query, scoring) ...
@@ -612,7 +627,8 @@ extern "C" int swg_debug_list_deal(const swg_db *db, const uint32_t *cand, const
 extern "C" int swg_debug_list_jobs(const swg_db *db, const uint32_t *cand, const uint64_t *c_off, size_t n_queries, uint32_t *slots_out,
                                    size_t cap, size_t *n_slots, uint64_t *row_pairs_out);
 // test hook: the pair-token image as the device built it, or as the host restatement builds it
-// test hook: the next visit of the named site throws std::bad_alloc (swg_api.cpp); 0 disarms
+// test hook: the next visit of the named site throws std::bad_alloc (swg_api.cpp); 0 disarms.  Site 4 throws nothing: the
+// next growth of swg_search_above_multi's key pool finds no device memory, and that chunk is selected on the host
 extern "C" void swg_debug_fail_alloc(int site);
 extern "C" int swg_debug_plan(const swg_db *db, size_t lq, int n_cu, int32_t *out);
 // a gapless search's plan: out[0..5] = route (1 gapless cells, 0 gapped machinery), K, G, W, workgroups, passes

@@ -304,6 +304,16 @@ hipError_t swg_launch_topk(const int32_t *d_scores, const uint32_t *d_order, uin
 // >= min_score (>= 1), and d_keys[0 .. min(*d_count, cap)) holds that many of their keys (swg_hit_key), unsorted.
 hipError_t swg_launch_above_compact(const int32_t *d_scores, const uint32_t *d_order, uint32_t n_slots, int32_t min_score, uint64_t *d_keys, uint32_t cap,
                                     uint32_t *d_count, hipStream_t stream);
+// The read-out of a chunk of swg_search_above_multi: score row y (row_stride scores apart, n_slots a multiple of 128, at
+// most 65535 rows) against its own threshold d_thr[y] >= 1.  Count: d_counts[y] (zeroed here) = the row's non-padding
+// slots at or above d_thr[y].  Scatter: behind it, with d_offsets[y] the row's place in d_keys (the host's prefix of the
+// counts), the keys (swg_hit_key) of exactly those slots at d_keys[d_offsets[y] .. + d_counts[y]), unsorted; d_cursors
+// (n_rows words) is zeroed here; nothing is written at or beyond keys_cap.
+hipError_t swg_launch_above_rows_count(const int32_t *d_scores, uint64_t row_stride, const uint32_t *d_order, uint32_t n_slots, uint32_t n_rows,
+                                       const int32_t *d_thr, uint32_t *d_counts, hipStream_t stream);
+hipError_t swg_launch_above_rows_scatter(const int32_t *d_scores, uint64_t row_stride, const uint32_t *d_order, uint32_t n_slots, uint32_t n_rows,
+                                         const int32_t *d_thr, const uint32_t *d_counts, const uint64_t *d_offsets, uint32_t *d_cursors,
+                                         uint64_t *d_keys, uint64_t keys_cap, hipStream_t stream);
 // Hits-only pruning.  colmax[r] = max(0, best score of database residue r against any query column):
 // a sequence's local score is at most the sum of colmax over its residues (non-positive gap scores).
 struct SwgColMax {

@@ -2823,6 +2823,91 @@ hipError_t swg_launch_above_compact(const int32_t *d_scores, const uint32_t *d_o
     return hipGetLastError();
 }
 
+// The read-out of swg_search_above_multi's one-launch route ("A caller's threshold, per query of a batch"):
+// score row y of a chunk (row_stride scores apart) against its own threshold thr[y], on a grid of (blocks, rows).  n is a
+// multiple of 128 (SWG_BIN) and the loops step by whole wavefronts within one row, so a wavefront never spans two rows
+// and its ballot speaks of one row alone.  Two kernels, so that the keys take the room the answers need: the first
+// counts -- one atomic per wavefront and round into the row's counter, exact whatever follows --, the host lays the rows
+// that take hits end to end (64-bit offsets), the second appends each row's keys behind the row's offset through a
+// per-row cursor, each lane's place the count of the qualifying lanes below it (mbcnt).
+__global__ __launch_bounds__(256) void swg_above_rows_count_kernel(const int32_t *scores, uint64_t row_stride, const uint32_t *order, uint32_t n,
+                                                                   const int32_t *thr, uint32_t *counts)
+{
+    const uint32_t y = blockIdx.y, lane = threadIdx.x & 63u;
+    const int32_t *row = scores + (uint64_t)y * row_stride;
+    const int32_t t = thr[y];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    uint32_t mine = 0u; // (this wavefront's hits: added once, behind the loop)
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); i0 < n; i0 += stride) {
+        const uint64_t i = i0 + lane;
+        const bool hit = i < n && order[i] != 0xFFFFFFFFu && row[i] >= t;
+        mine += (uint32_t)__popcll(__ballot(hit));
+    }
+    if (lane == 0u && mine != 0u) atomicAdd(&counts[y], mine);
+}
+
+__global__ __launch_bounds__(256) void swg_above_rows_scatter_kernel(const int32_t *scores, uint64_t row_stride, const uint32_t *order, uint32_t n,
+                                                                     const int32_t *thr, const uint32_t *counts, const uint64_t *offsets,
+                                                                     uint32_t *cursors, uint64_t *keys, uint64_t keys_cap)
+{
+    const uint32_t y = blockIdx.y, lane = threadIdx.x & 63u;
+    const uint32_t room = counts[y]; // (what the count kernel found: the row's room behind its offset)
+    if (room == 0u) return;
+    const int32_t *row = scores + (uint64_t)y * row_stride;
+    const int32_t t = thr[y];
+    const uint64_t off = offsets[y];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); i0 < n; i0 += stride) {
+        const uint64_t i = i0 + lane;
+        uint32_t oi = 0xFFFFFFFFu;
+        int v = 0;
+        if (i < n) oi = order[i], v = row[i];
+        const bool hit = oi != 0xFFFFFFFFu && v >= t;
+        const unsigned long long mask = __ballot(hit);
+        if (mask == 0ull) continue;
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        const int leader = __ffsll((long long)mask) - 1;
+        uint32_t base = 0u;
+        if ((int)lane == leader) base = atomicAdd(&cursors[y], (uint32_t)__popcll(mask));
+        base = (uint32_t)__shfl((int)base, leader, 64);
+        const uint32_t at = base + below;
+        if (hit && at < room && off + at < keys_cap) keys[off + at] = ((uint64_t)(uint32_t)v << 32) | (uint64_t)(0xFFFFFFFFu - oi); // (swg_hit_key: v >= 1)
+    }
+}
+
+static uint32_t above_rows_blocks(uint32_t n_slots, uint32_t n_rows)
+{
+    // whole rows of blocks, about 2048 blocks over the grid: a row's atomics stay few, a small database still fills the chip
+    const uint32_t want = (n_slots + 255u) / 256u, share = 2048u / n_rows > 0u ? 2048u / n_rows : 1u;
+    return want < 1u ? 1u : want > share ? share : want;
+}
+
+hipError_t swg_launch_above_rows_count(const int32_t *d_scores, uint64_t row_stride, const uint32_t *d_order, uint32_t n_slots, uint32_t n_rows,
+                                       const int32_t *d_thr, uint32_t *d_counts, hipStream_t stream)
+{
+    if (n_rows == 0) return hipSuccess;
+    if (n_rows > 65535u || n_slots % 128u != 0u || !d_scores || !d_order || !d_thr || !d_counts) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(d_counts, 0, (size_t)n_rows * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(swg_above_rows_count_kernel, dim3(above_rows_blocks(n_slots, n_rows), n_rows), dim3(256), 0, stream, d_scores, row_stride,
+                       d_order, n_slots, d_thr, d_counts);
+    return hipGetLastError();
+}
+
+hipError_t swg_launch_above_rows_scatter(const int32_t *d_scores, uint64_t row_stride, const uint32_t *d_order, uint32_t n_slots, uint32_t n_rows,
+                                         const int32_t *d_thr, const uint32_t *d_counts, const uint64_t *d_offsets, uint32_t *d_cursors,
+                                         uint64_t *d_keys, uint64_t keys_cap, hipStream_t stream)
+{
+    if (n_rows == 0) return hipSuccess;
+    if (n_rows > 65535u || n_slots % 128u != 0u || !d_scores || !d_order || !d_thr || !d_counts || !d_offsets || !d_cursors || !d_keys)
+        return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(d_cursors, 0, (size_t)n_rows * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(swg_above_rows_scatter_kernel, dim3(above_rows_blocks(n_slots, n_rows), n_rows), dim3(256), 0, stream, d_scores, row_stride,
+                       d_order, n_slots, d_thr, d_counts, d_offsets, d_cursors, d_keys, keys_cap);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // hits-only pruning: the score bound of every pair, the threshold so far, the cut of a stage
 // ---------------------------------------------------------------------------

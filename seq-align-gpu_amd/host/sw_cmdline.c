@@ -29,7 +29,10 @@
  *     identities and gap openings come from the same forward pass, no traceback is run);
  *     --minscore S reports every entry that scores at least S, best first, in --topk's block (swg_search_above: no score
  *     array, so no Entry lines), with --topk K the best K of them; under --gpus N each device searches its shard and the
- *     lists are merged by swg_hit_key.
+ *     lists are merged by swg_hit_key;
+ *     --allqueries --minscorelist F --topk K does the same for every record at its own least score, line i of F being
+ *     record i's: the count of the entries at or above it, then the best min(K, count) of them (the records after the
+ *     first go through swg_search_above_multi / _multi_pssm, with --gapless swg_search_gapless_above_multi / _pssm).
  * There is no CPU backend: without a GPU the tool fails with a message.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -98,6 +101,10 @@ static void usage(const char *argv0, const char *err)
             "                         lines are printed: no score array is made); with --topk K the best K of them; --align, --bounds and\n"
             "                         --tabular then report those hits; with --gpus N every GPU searches its shard and the lists are\n"
             "                         merged; not with --allqueries, --candidates or --prefilter\n"
+            "    --minscorelist <file> with --allqueries --topk K: line i is the least score (1 or more) of query record i; every\n"
+            "                         record reports how many entries score at least that, then the best K of them as --minscore\n"
+            "                         does; works with --pssmlist, --gapless, --seqidlist, --align, --bounds and --tabular; not with\n"
+            "                         --minscore, --candidates, --prefilter or --gpus\n"
             "    --prefilter <N>      with --topk K: per query (every record with --allqueries) the N best entries by gapless\n"
             "                         score are searched with gaps and the K best of those reported (--align: aligned);\n"
             "                         no Entry lines are printed; not with --gpus, --candidates or --gapless\n",
@@ -198,6 +205,7 @@ int main(int argc, char **argv)
     swg_scoring sc;
     swg_scoring_init(&sc);
     const char *qpath = NULL, *dbpath = NULL, *savedb = NULL, *pssm_path = NULL, *pssmlist_path = NULL, *idlist_path = NULL, *cand_path = NULL;
+    const char *mslist_path = NULL;
     int print_seq = 0, print_fasta = 0, have_matrix = 0, packed = 0, allq = 0;
     long topk = 0, gpu = 0, gpus = 0, prefilter = 0, minscore = 0, v;
     int align = 0, gapless = 0, bounds = 0, tabular = 0;
@@ -258,6 +266,8 @@ int main(int argc, char **argv)
         } else if (!strcasecmp(a, "--minscore")) {
             if (!parse_int(argv[i + 1], 1, INT_MAX, &minscore)) usage(argv[0], "Invalid --minscore argument: the least score to report, 1 or more");
             i++;
+        } else if (!strcasecmp(a, "--minscorelist")) {
+            mslist_path = argv[++i];
         } else if (!strcasecmp(a, "--prefilter")) {
             if (!parse_int(argv[i + 1], 1, 1 << 20, &prefilter)) usage(argv[0], "Invalid --prefilter argument: the number of candidates per query, 1 or more");
             i++;
@@ -303,7 +313,12 @@ int main(int argc, char **argv)
     if (pssmlist_path && pssm_path) usage(argv[0], "--pssmlist and --pssm do not combine (the list names the first record's PSSM too)");
     if (pssmlist_path && gpus > 0) usage(argv[0], "--pssmlist works with one GPU (--gpu)");
     if ((packed || savedb || allq) && gpus > 0) usage(argv[0], "--packed/--savedb/--allqueries work with one GPU (--gpu)");
+    if (minscore && mslist_path) usage(argv[0], "--minscorelist does not combine with --minscore, --candidates, --prefilter or --gpus");
     if (minscore && (allq || cand_path || prefilter)) usage(argv[0], "--minscore reports one query's hits: it does not combine with --allqueries, --candidates or --prefilter");
+    if (mslist_path && !allq) usage(argv[0], "--minscorelist gives the least score of each of --allqueries' records: give --allqueries");
+    if (mslist_path && topk == 0) usage(argv[0], "--minscorelist reports up to --topk K hits per record: give --topk K");
+    if (mslist_path && (cand_path || prefilter || gpus > 0))
+        usage(argv[0], "--minscorelist does not combine with --minscore, --candidates, --prefilter or --gpus");
     if (align && topk == 0 && !minscore) usage(argv[0], "--align reports the alignments of the --topk hits: give --topk K");
     if (bounds && topk == 0 && !minscore) usage(argv[0], "--bounds reports the alignment coordinates of the --topk hits: give --topk K");
     if (bounds && align) usage(argv[0], "--bounds reports coordinates without the alignments: it does not combine with --align (whose headers carry them)");
@@ -402,6 +417,49 @@ int main(int argc, char **argv)
             fprintf(stderr, "Error: out of memory\n");
             return leave(EXIT_FAILURE);
         }
+    }
+    /* --minscorelist: line i is the least score of query record i; from here on `minscore` is the current record's */
+    int32_t *mslist = NULL;
+    if (mslist_path) {
+        FILE *lf = fopen(mslist_path, "r");
+        if (!lf) {
+            fprintf(stderr, "Error: couldn't open the score list %s\n", mslist_path);
+            return leave(EXIT_FAILURE);
+        }
+        mslist = (int32_t *)calloc(q.n, sizeof *mslist);
+        if (!mslist) return leave(EXIT_FAILURE);
+        size_t n_read = 0;
+        unsigned long line_no = 0;
+        char line[4096], msg[512];
+        while (fgets(line, sizeof line, lf)) {
+            line_no++;
+            char *b = line, *e = line + strlen(line);
+            while (*b == ' ' || *b == '\t') b++;
+            while (e > b && (e[-1] == '\n' || e[-1] == '\r' || e[-1] == ' ' || e[-1] == '\t')) e--;
+            *e = 0;
+            if (e <= b && feof(lf)) break; /* (a trailing empty line is no line) */
+            long val = 0;
+            if (n_read >= q.n) {
+                snprintf(msg, sizeof msg, "--minscorelist %s line %lu: the query file has %lu records, one line each", mslist_path, line_no,
+                         (unsigned long)q.n);
+                (void)leave(0);
+                usage(argv[0], msg);
+            }
+            if (!parse_int(b, 1, INT_MAX, &val)) {
+                snprintf(msg, sizeof msg, "--minscorelist %s line %lu: '%s' is not a least score (an integer of 1 or more)", mslist_path, line_no, b);
+                (void)leave(0);
+                usage(argv[0], msg);
+            }
+            mslist[n_read++] = (int32_t)val;
+        }
+        fclose(lf);
+        if (n_read < q.n) {
+            snprintf(msg, sizeof msg, "--minscorelist %s line %lu is missing: the query file has %lu records, one line each", mslist_path,
+                     (unsigned long)n_read + 1, (unsigned long)q.n);
+            (void)leave(0);
+            usage(argv[0], msg);
+        }
+        minscore = mslist[0];
     }
     /* --candidates: record r's entries are cands[c_off[r] .. c_off[r + 1]) in the file's order; lsc is parallel to cands
      * (swg_search_lists' scores_out), and `listed` marks the current record's entries for the printing */
@@ -952,6 +1010,7 @@ next_query:
         static int32_t *mq_scores = NULL;
         static swg_hit *mq_hits = NULL;
         static size_t *mq_nhits = NULL;
+        static uint64_t *mq_above = NULL; /* --minscorelist: every record's entries at or above its score */
         static size_t chunk_first = 0, chunk_n = 0;
         static double chunk_ms = 0.0;
         static int8_t *qx = NULL;     /* the chunk's queries as table indices */
@@ -970,10 +1029,12 @@ next_query:
             free(mq_scores);
             free(mq_hits);
             free(mq_nhits);
-            mq_scores = (int32_t *)calloc(cands ? 1 : chunk_n * (db.n ? db.n : 1), sizeof(int32_t)); /* (--candidates: lsc) */
+            free(mq_above);
+            mq_above = (uint64_t *)calloc(chunk_n, sizeof(uint64_t));
+            mq_scores = (int32_t *)calloc(cands || mslist ? 1 : chunk_n * (db.n ? db.n : 1), sizeof(int32_t)); /* (--candidates: lsc) */
             mq_hits = (swg_hit *)calloc(chunk_n * (topk ? (size_t)topk : 1), sizeof(swg_hit));
             mq_nhits = (size_t *)calloc(chunk_n, sizeof(size_t));
-            if (!qx || !qoff || !mq_scores || !mq_hits || !mq_nhits) return leave(EXIT_FAILURE);
+            if (!qx || !qoff || !mq_scores || !mq_hits || !mq_nhits || !mq_above) return leave(EXIT_FAILURE);
             for (size_t i = 0; i <= chunk_n; i++) qoff[i] = q.seq_off[chunk_first + i] - q.seq_off[chunk_first];
             for (size_t i = 0; i < chunk_n; i++) {
                 const size_t lqi = (size_t)(qoff[i + 1] - qoff[i]);
@@ -1019,7 +1080,16 @@ next_query:
                                                    c_off + chunk_first, lsc, mq_hits, (size_t)topk, mq_nhits, &st)
                            : swg_search_lists(ctx, sdb, qx, qoff, chunk_n, cands, c_off + chunk_first, lsc, mq_hits, (size_t)topk,
                                               mq_nhits, &st);
-            else if (gapless)
+            else if (mslist) { /* every record of the chunk at its own least score: no score array, K hits of room each */
+                const int8_t *pl = plist ? plist + (size_t)q.seq_off[chunk_first] * 32 : NULL;
+                const int32_t *ms = mslist + chunk_first;
+                if (gapless)
+                    rc = plist ? swg_search_gapless_above_multi_pssm(ctx, sdb, pl, qoff, chunk_n, ms, mq_hits, (size_t)topk, mq_nhits, mq_above, &st)
+                               : swg_search_gapless_above_multi(ctx, sdb, qx, qoff, chunk_n, ms, mq_hits, (size_t)topk, mq_nhits, mq_above, &st);
+                else
+                    rc = plist ? swg_search_above_multi_pssm(ctx, sdb, pl, qoff, chunk_n, ms, mq_hits, (size_t)topk, mq_nhits, mq_above, &st)
+                               : swg_search_above_multi(ctx, sdb, qx, qoff, chunk_n, ms, mq_hits, (size_t)topk, mq_nhits, mq_above, &st);
+            } else if (gapless)
                 rc = plist ? swg_search_gapless_multi_pssm(ctx, sdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff, chunk_n, mq_scores,
                                                            mq_hits, (size_t)topk, mq_nhits, &st)
                            : swg_search_gapless_multi(ctx, sdb, qx, qoff, chunk_n, mq_scores, mq_hits, (size_t)topk, mq_nhits, &st);
@@ -1037,7 +1107,8 @@ next_query:
                         st.fill_ms, st.fill_ms > 0 ? (double)st.cells / (st.fill_ms * 1e-3) / 1e9 : 0.0);
         }
         const size_t at = qi - chunk_first;
-        if (!cands) memcpy(scores, mq_scores + at * (db.n ? db.n : 1), db.n * sizeof(int32_t));
+        if (!cands && !mslist) memcpy(scores, mq_scores + at * (db.n ? db.n : 1), db.n * sizeof(int32_t));
+        if (mslist) minscore = mslist[qi], n_above = mq_above[at];
         n_hits = mq_nhits[at];
         memcpy(hits, mq_hits + at * (topk ? (size_t)topk : 1), n_hits * sizeof(swg_hit));
         if (align && qi >= al_first + al_n) {
@@ -1147,6 +1218,7 @@ next_query:
     free(cands);
     free(c_off);
     free(lsc);
+    free(mslist);
     free(pf_hits);
     free(pf_nhits);
     free(scores);
