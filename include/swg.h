@@ -468,7 +468,9 @@ int swg_search_lists_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, c
  * src/alignment_cmdline.c:434,445), padded rows included and computed as real
  * rows like the reference does; max_scores receives
  * aligner_t.max_scores for lanes 0..vector_size-1, saturated to int16.
- * Uses the scoring and query already set on ctx (a PSSM query included; its scores saturate the same way). */
+ * Uses the scoring and query already set on ctx (a PSSM query included; its scores saturate the same way).
+ * Lanes at or beyond vector_size are never read and their max_scores never written.  A residue index outside
+ * 1..31 in a live lane is SWG_ERR_RESIDUE; searches in flight on the context (swg_search_begin) are SWG_ERR_STATE. */
 typedef struct swg_batch16 {
     const int8_t *db_idx_t;
     size_t max_len;

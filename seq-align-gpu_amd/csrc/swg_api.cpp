@@ -4503,8 +4503,6 @@ static int fill_batches16_device(swg_ctx *ctx, const swg_batch16 *batches, size_
     typedef std::chrono::steady_clock clk;
     const clk::time_point t0 = clk::now();
     if (ctx->opt_engine == 1 || ctx->opt_dynamic == 0 || !ctx->have_scoring || ctx->query_len() == 0) return SWG_TAKE_HOST_ROUTE;
-    for (const SwgSlot &sl : ctx->slots)
-        if (sl.busy) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_fill_batches16: searches are in flight on this context");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     SwgBatch16Cache &C = ctx->b16;
     // batches longest first (the reference's caller passes them sorted: then this is the identity)
@@ -4740,6 +4738,10 @@ static int fill_batches16_impl(swg_ctx *ctx, const swg_batch16 *batches, size_t 
     }
     const size_t n_all = offsets.size() - 1;
     if (n_all == 0) return SWG_OK;
+    // one rule for both routes (the device route searches on slot 0 with the cache's one database; the host route used to
+    // slip past a ticket on another slot)
+    for (const SwgSlot &sl : ctx->slots)
+        if (sl.busy) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_fill_batches16: searches are in flight on this context");
     {
         double t_ms[5] = {0, 0, 0, 0, 0};
         int rd = SWG_OK;
@@ -4767,6 +4769,8 @@ static int fill_batches16_impl(swg_ctx *ctx, const swg_batch16 *batches, size_t 
     swg_db *db = nullptr;
     int rc = swg_db_pack(flat.get(), offsets.data(), n, 0, 1, &db);
     if (rc != SWG_OK) {
+        // (the packer speaks of a database: the caller handed over batches, and the device route says so)
+        if (rc == SWG_ERR_RESIDUE) return swg_set_ctx_error(ctx, SWG_ERR_RESIDUE, "swg_fill_batches16: residue index outside 1..31 in a batch");
         ctx->err = swg_global_error();
         return rc;
     }
