@@ -307,7 +307,15 @@ int swg_search_end(swg_ctx *ctx, int ticket, int32_t *scores_out, swg_hit *topk_
  * 1 the prefix of the length order up to the last such pair.  "prune_refine" (default 0): under "prune_cut" 0 the pairs of
  * a stage whose bound still reaches the threshold are bounded once more over a k = 4 table of 64 | 128 segments, and the
  * lesser bound holds; 1 off; 0 automatic -- on where "prune_kmer" and "prune_segments" are both automatic and took k = 4
- * in segments, off otherwise.  Hits are the same under every value. */
+ * in segments, off otherwise.  "prune_refine3" (default 0): the pairs that still reach the threshold after that are
+ * bounded a third time over a k = 4 table of 256 segments, and the least bound holds; 256 on, behind whatever the second
+ * level is; 1 off; 0 automatic -- on where the second level was chosen automatically and took 128, the tables hold
+ * bytes (below) and the range is large enough for the finer cut to pay for its table and its walk twice over (the
+ * 10M-sequence database: yes; a database of thousands or a few million sequences: no).  "prune_table_bits" (default 0):
+ * the width of the k-mer tables' entries.  0: bytes wherever k x the largest score of the query's profile is at most 255
+ * (every entry fits: BLOSUM62 44, PAM250 68 at k = 4), uint16_t otherwise (a PSSM with an entry of 64 or more); 16:
+ * uint16_t always.  A byte table holds the same values in half the memory and gather traffic.  Hits, bounds and lists are
+ * the same under every value of these options. */
 typedef struct swg_prune_info {
     uint64_t pairs_skipped;
     uint64_t pair_rows_skipped;

@@ -248,6 +248,11 @@ _sig("swg_debug_prune_kmer_seg_read", C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp,
 _sig("swg_debug_prune_kmer_refine", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp])
 _sig("swg_debug_prune_refine_choice", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_refine_read", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp])
+_sig("swg_debug_prune_stages3", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
+_sig("swg_debug_prune_kmer_refine3", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp])
+_sig("swg_debug_prune_refine3_choice", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_table_bits", C.c_int, [_vp, _vp, C.c_size_t, C.c_int])
+_sig("swg_debug_prune_tables", C.c_int, [_vp, _vp])
 _sig("swg_debug_list_deal", C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 
 
@@ -532,15 +537,44 @@ def debug_prune_kmer_choice_seg(forced=0, segments=0, pruned=1, lq=3000, pair_ro
     return int(out[0]), int(out[1]), int(out[2]), bool(out[3])
 
 
-KMER_REFINE_SEGMENTS = 128
+KMER_REFINE_SEGMENTS = 128    # the second level's most
+KMER_REFINE3_SEGMENTS = 256   # the third level's
 
 
 def debug_prune_kmer_refine(rows, query, gap_open, gap_extend, segments, flat, offsets, table=True):
-    """Test hook (no device needed): the second-level bound's host mirror -- debug_prune_kmer_seg at k = 4 over the
-    `segments` (32, 64 or 128) segments the refine kernel walks.  -> (table uint16[22^4, segments] or None, U uint64[n])."""
+    """Test hook (no device needed): the second- and third-level bounds' host mirror -- debug_prune_kmer_seg at k = 4 over
+    the `segments` (32, 64, 128; 256: the third level's, swg_debug_prune_kmer_refine3) segments the refine kernel walks.
+    -> (table uint16[22^4, segments] or None, U uint64[n])."""
     S = int(segments)
-    return _prune_kmer_mirror(lib.swg_debug_prune_kmer_refine, rows, query, gap_open, gap_extend, (S,), flat, offsets,
-                              (KMER_CLASSES ** 4, S) if table and S in (32, 64, 128) else None)
+    hook = lib.swg_debug_prune_kmer_refine3 if S == KMER_REFINE3_SEGMENTS else lib.swg_debug_prune_kmer_refine
+    return _prune_kmer_mirror(hook, rows, query, gap_open, gap_extend, (S,), flat, offsets,
+                              (KMER_CLASSES ** 4, S) if table and S in (32, 64, 128, 256) else None)
+
+
+def debug_prune_table_bits(rows, query, k=4):
+    """Test hook (no device needed): the width of the k-mer tables' entries for this query (rows / query as
+    debug_prune_bound takes them) at k = 4 or 5 under option prune_table_bits = 0 -> 8 where k x the largest colmax entry
+    is at most 255, else 16."""
+    r, rp = _i8(rows)
+    lq = r.size // 32
+    qp = None
+    if query is not None:
+        q, qp = _i8(query)
+        lq = q.size
+    rc = lib.swg_debug_prune_table_bits(rp, qp, lq, int(k))
+    if rc < 0:
+        _check(rc)
+    return rc
+
+
+def debug_prune_refine3_choice(forced=0, segments=0, refine=0, refine3=0, table_bits=8, pruned=1, lq=3000, pair_rows=1900000000,
+                               table_rate=0, fill_rate=0):
+    """Test hook (no device needed): debug_prune_refine_choice with option prune_refine3 and the tables' entry width
+    -> (k, S, S2, S3): S3 = 256 with a third level, 0 without."""
+    a = np.array([forced, pruned, lq, pair_rows, table_rate, fill_rate, segments, refine, refine3, table_bits], dtype=np.int64)
+    out = np.zeros(4, dtype=np.int64)
+    _check(lib.swg_debug_prune_refine3_choice(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
+    return int(out[0]), int(out[1]), int(out[2]), int(out[3])
 
 
 def debug_prune_refine_choice(forced=0, segments=0, refine=0, pruned=1, lq=3000, pair_rows=1900000000, table_rate=0, fill_rate=0):
@@ -612,18 +646,21 @@ def debug_above_multi_route(option=0, admitted=True, single_pruned=False):
     return rc
 
 
-PRUNE_STAGE_QUEUED = ("threshold", "prefix_cut", "gate", "refine", "list")   # bits 0..4 of a stage's fourth word, in queue order
+# a stage's fourth word: (bit, name) in queue order (the third level's walk is bit 5, queued between the second's and the list)
+PRUNE_STAGE_QUEUED = ("threshold", "prefix_cut", "gate", "refine", "list")
+_PRUNE_STAGE_BITS = ((0, "threshold"), (1, "prefix_cut"), (2, "gate"), (3, "refine"), (5, "refine3"), (4, "list"))
 
 
-def debug_prune_stages(segments, head_pairs=0, fixed=False, refine=0, prefix_cut=False):
+def debug_prune_stages(segments, head_pairs=0, fixed=False, refine=0, prefix_cut=False, refine3=0):
     """Test hook (no device needed): the stages of a pruned fill over the pair ranges `segments` [(begin, end), ...] and
-    what is queued in front of each (swg_prune_stages) -> [(begin, end, segment index, names of PRUNE_STAGE_QUEUED), ...].
-    head_pairs, fixed (a caller's threshold), refine (the second level's segments, 0: none) and prefix_cut are the plan's."""
-    a = np.array([head_pairs, fixed, refine, prefix_cut, len(segments)] + [int(v) for sg in segments for v in sg], dtype=np.int64)
+    what is queued in front of each (swg_prune_stages) -> [(begin, end, segment index, names in queue order: those of
+    PRUNE_STAGE_QUEUED, and "refine3" in front of "list"), ...].  head_pairs, fixed (a caller's threshold), refine and
+    refine3 (the second and third levels' segments, 0: none) and prefix_cut are the plan's."""
+    a = np.array([head_pairs, fixed, refine, prefix_cut, refine3, len(segments)] + [int(v) for sg in segments for v in sg], dtype=np.int64)
     out = np.zeros((2 * len(segments) + 1, 4), dtype=np.int64)
     n = C.c_size_t(0)
-    _check(lib.swg_debug_prune_stages(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp), out.shape[0], C.byref(n)))
-    return [(int(b), int(e), int(sg), tuple(name for i, name in enumerate(PRUNE_STAGE_QUEUED) if int(qd) >> i & 1))
+    _check(lib.swg_debug_prune_stages3(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp), out.shape[0], C.byref(n)))
+    return [(int(b), int(e), int(sg), tuple(name for i, name in _PRUNE_STAGE_BITS if int(qd) >> i & 1))
             for b, e, sg, qd in out[:n.value]]
 
 
@@ -1276,7 +1313,8 @@ class Context:
     def debug_prune_refine_read(self, db, segments=None, arrays=True):
         """Test hook: the second level and the lists of the search last begun -> dict: k, segments, refine (its S2, 0:
         none), builds / refine_builds (table builds queued so far, first / second level), table uint16[22^4, segments]
-        (only when `segments` is given), bounds uint32[pairs] as the search left them, stages: a list of (begin, end, T,
+        (only when `segments` is given: 64 | 128 the second level's, 256 the third's; widened where the device keeps
+        bytes), bounds uint32[pairs] as the search left them, stages: a list of (begin, end, T,
         list) per stage cut pair by pair, list being the pair ids its launches took.  arrays = False: the counters only
         (before the database's first pruned search there are no bounds to read)."""
         info = np.zeros(7, dtype=np.uint64)
@@ -1295,6 +1333,15 @@ class Context:
         stages = [(int(r[0]), int(r[1]), int(r[2]), l[int(r[0]):int(r[0]) + int(r[3])].copy()) for r in st[:int(info[6])]]
         return {"k": int(info[0]), "builds": int(info[1]), "pairs": n, "segments": int(info[3]), "refine": int(info[4]),
                 "refine_builds": int(info[5]), "table": t, "bounds": b[:n], "stages": stages}
+
+    def debug_prune_tables(self):
+        """Test hook: the third level and the k-mer tables' entry widths (swg_debug_prune_tables) -> dict: refine3 (S3 of
+        the search last begun, 0: none), refine3_builds, bits: the entry bits of the tables that hold the current query
+        and scoring (0: none) -- first4, first5, second, third --, auto_bits (what prune_table_bits = 0 gives at k = 4)."""
+        out = np.zeros(7, dtype=np.int64)
+        _check(lib.swg_debug_prune_tables(self.handle, out.ctypes.data_as(_vp)), self.handle)
+        return {"refine3": int(out[0]), "refine3_builds": int(out[1]),
+                "bits": dict(zip(("first4", "first5", "second", "third"), (int(v) for v in out[2:6]))), "auto_bits": int(out[6])}
 
     def debug_bounds_last(self):
         """What the last align_bounds* call of this context did (swg_debug_bounds_last) -> dict: pairs on the bounds kernel,

@@ -258,6 +258,7 @@ extern "C" void swg_destroy(swg_ctx *ctx)
     (void)hipFree(ctx->kmer_first[0].d);
     (void)hipFree(ctx->kmer_first[1].d);
     (void)hipFree(ctx->kmer_second.d);
+    (void)hipFree(ctx->kmer_third.d);
     (void)hipFree(ctx->d_profile[0]);
     (void)hipFree(ctx->d_profile[1]);
     (void)hipFree(ctx->d_profile[2]);
@@ -366,6 +367,14 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
         if (!swg_prune_refine_value_ok(value))
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_refine must be 0 (auto), 1 (off), 64 or 128 (the segments of the second-level bound's table)");
         ctx->opt_prune_refine = value;
+    } else if (!strcmp(key, "prune_refine3")) {
+        if (!swg_prune_refine3_value_ok(value))
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_refine3 must be 0 (auto), 1 (off) or 256 (the segments of the third-level bound's table)");
+        ctx->opt_prune_refine3 = value;
+    } else if (!strcmp(key, "prune_table_bits")) {
+        if (value != 0 && value != 16)
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_table_bits must be 0 (auto: bytes where they hold every entry) or 16");
+        ctx->opt_prune_table_bits = value;
     } else if (!strcmp(key, "prune_cut")) {
         if (value != 0 && value != 1)
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_cut must be 0 (a stage's pairs are cut one by one) or 1 (the prefix of the length order)");
@@ -1250,7 +1259,7 @@ static int dyn_fill_begin(DynFill *F, int go, int ge, uint64_t *d_trace)
 // it loads the profile when it is 0, and hands out exactly those pairs in every pass (no batch claims in list mode).  So
 // the fill kernels are the unpruned search's, instruction for instruction.  The prefix cut's list is the pair ids in
 // order, from the stage's first pair, and its length is the cut.  Pair by pair (the default): the second-level bound of
-// the stage's pairs that still reach the threshold, then the stage's own list -- the ids of its pairs whose bound reaches
+// the stage's pairs that still reach the threshold (and the third level's of those that reach it after that), then the stage's own list -- the ids of its pairs whose bound reaches
 // T, in order.  Under a caller's threshold the first of SEVERAL stages -- the longest pairs, whose bounds stand furthest
 // above any T -- is walked a second time only where the first level cut an eighth of it: the gate's word is its T.
 // (The tables are this epoch's: prepare_prune queued their builds on this stream.)
@@ -1264,9 +1273,10 @@ static int enqueue_pruned_fill(swg_ctx *ctx, swg_db *db, const SwgPrunePlan &pr,
     const SwgPruneLayout L = swg_prune_layout(db->d_pair_bound, n_pairs);
     if (pr.kmer > 1 && pr.segments > 1)
         HIP_TRY(ctx, swg_launch_pair_bound_kmer_seg(T.d_tok, T.d_pair_off, n_pairs, pr.kmer, (uint32_t)pr.segments, ctx->prune_colmax, ctx->kmer_first[pr.kmer - 4].d,
-                                                    L.bounds, L.ids, qs));
+                                                    ctx->kmer_first[pr.kmer - 4].bits, L.bounds, L.ids, qs));
     else if (pr.kmer > 1)
-        HIP_TRY(ctx, swg_launch_pair_bound_kmer(T.d_tok, T.d_pair_off, n_pairs, pr.kmer, ctx->prune_colmax, ctx->kmer_first[pr.kmer - 4].d, L.bounds, L.ids, qs));
+        HIP_TRY(ctx, swg_launch_pair_bound_kmer(T.d_tok, T.d_pair_off, n_pairs, pr.kmer, ctx->prune_colmax, ctx->kmer_first[pr.kmer - 4].d,
+                                                ctx->kmer_first[pr.kmer - 4].bits, L.bounds, L.ids, qs));
     else
         HIP_TRY(ctx, swg_launch_pair_bound(T.d_tok, T.d_pair_off, n_pairs, ctx->prune_colmax, L.bounds, L.ids, qs));
     if (pr.fixed) HIP_TRY(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(thr), (int)pr.fixed_T, 1, qs));
@@ -1278,7 +1288,11 @@ static int enqueue_pruned_fill(swg_ctx *ctx, swg_db *db, const SwgPrunePlan &pr,
         if (st.queued & SWG_STAGE_GATE) HIP_TRY(ctx, swg_launch_prune_refine_gate(L.bounds, st.begin, st.end, thr, gate, qs));
         if (st.queued & SWG_STAGE_REFINE)
             HIP_TRY(ctx, swg_launch_pair_bound_refine(T.d_tok, T.d_pair_off, st.begin, st.end, (uint32_t)pr.refine, ctx->prune_colmax, ctx->kmer_second.d,
-                                                      st.queued & SWG_STAGE_GATE ? gate : thr, L.bounds, qs));
+                                                      ctx->kmer_second.bits, st.queued & SWG_STAGE_GATE ? gate : thr, L.bounds, qs));
+        // (the third level: the pairs the second left at or above the same word, so a gated stage skips both walks together)
+        if (st.queued & SWG_STAGE_REFINE3)
+            HIP_TRY(ctx, swg_launch_pair_bound_refine(T.d_tok, T.d_pair_off, st.begin, st.end, (uint32_t)pr.refine3, ctx->prune_colmax, ctx->kmer_third.d,
+                                                      ctx->kmer_third.bits, st.queued & SWG_STAGE_GATE ? gate : thr, L.bounds, qs));
         if (st.queued & SWG_STAGE_LIST) {
             const size_t rec = db->prune_stages.size() / 2;
             HIP_TRY(ctx, swg_launch_prune_list(L.bounds, T.d_pair_off, st.begin, st.end, thr, L.tiles, L.lists + st.begin, cut_word,
@@ -2325,6 +2339,21 @@ extern "C" int swg_debug_systolic_variants(int bits, int32_t *out, size_t cap)
     return n;
 }
 
+// The colmax table of the current (query, scoring) epoch, built on the host when either has changed ...
+static void ensure_prune_colmax(swg_ctx *ctx)
+{
+    if (ctx->prune_colmax_epoch == ctx->epoch) return;
+    ctx->prune_colmax = ctx->query_pssm ? swg_prune_colmax(ctx->pssm.data(), nullptr, ctx->query_len())
+                                        : swg_prune_colmax(&ctx->sub[0][0], ctx->query.data(), ctx->query_len());
+    ctx->prune_colmax_epoch = ctx->epoch;
+}
+// ... and from it the width of this epoch's tables of k: bytes where they hold every entry, unless "prune_table_bits" says 16
+static int kmer_table_bits(swg_ctx *ctx, int k)
+{
+    ensure_prune_colmax(ctx);
+    return ctx->opt_prune_table_bits == 16 ? 16 : swg_kmer_table_bits(ctx->prune_colmax, k);
+}
+
 // Whether this search is pruned (swg_prune_plan has the rules) and by which bound, decided once the plan stands.  It only
 // decides: P->prune and the context's record of the choice; prepare_prune builds what the choice needs.
 static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgSearchPlan *P)
@@ -2366,6 +2395,9 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
     ka.forced = ctx->opt_prune_kmer;
     ka.forced_segments = ctx->opt_prune_segments;
     ka.forced_refine = ctx->opt_prune_refine;
+    ka.forced_refine3 = ctx->opt_prune_refine3;
+    ensure_prune_colmax(ctx);
+    ka.table_bits = kmer_table_bits(ctx, 4);
     ka.pruned = true;
     ka.lq = ctx->query_len();
     ka.pair_rows = 4ull * (db->ptok.pair_blocks_prefix[wk.pair_end[0]] - db->ptok.pair_blocks_prefix[wk.pair_begin[0]]);
@@ -2374,7 +2406,8 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
     // how a stage is cut: pair by pair, behind the second-level bound where that pays, or the prefix of the length order
     P->prune.prefix_cut = ctx->opt_prune_cut == 1 && !P->prune.fixed; // (a caller's threshold takes the list)
     P->prune.refine = P->prune.prefix_cut ? 0 : swg_prune_refine_choice(ka, P->prune.kmer, P->prune.segments);
-    ctx->prune_choice = SwgPruneChoice{P->prune.kmer, P->prune.segments, P->prune.refine};
+    P->prune.refine3 = P->prune.prefix_cut ? 0 : swg_prune_refine3_choice(ka, P->prune.kmer, P->prune.segments, P->prune.refine);
+    ctx->prune_choice = SwgPruneChoice{P->prune.kmer, P->prune.segments, P->prune.refine, P->prune.refine3};
     return SWG_OK;
 }
 
@@ -2385,34 +2418,31 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
 // grows when S x entries does.  Which (k, S) a table may hold is the caller's to say.
 static int ensure_kmer_table(swg_ctx *ctx, SwgKmerTable *t, int k, int S)
 {
-    if (t->holds(ctx->epoch, k, S)) return SWG_OK;
+    const int bits = kmer_table_bits(ctx, k);
+    if (t->holds(ctx->epoch, k, S, bits)) return SWG_OK;
     const size_t lq = ctx->query_len();
     int rc;
     if ((rc = device_grow(ctx, &ctx->d_kmer_cprof, &ctx->d_kmer_cprof_cap, lq * 32)) != SWG_OK) return rc;
-    const size_t entries = (size_t)swg_kmer_entries(k) * (size_t)S;
-    if (t->cap < entries) t->epoch = 0; // (allocated anew below: what it held is gone)
-    if ((rc = device_grow(ctx, &t->d, &t->cap, entries)) != SWG_OK) return rc;
+    const size_t bytes = (size_t)swg_kmer_entries(k) * (size_t)S * (size_t)(bits / 8);
+    if (t->cap < bytes) t->epoch = 0; // (allocated anew below: what it held is gone)
+    if ((rc = device_grow(ctx, &t->d, &t->cap, bytes)) != SWG_OK) return rc;
     // (gap scores: a gap's first residue costs open + extend, every further one extend -- SwgSearchPlan's go / ge)
     const long go = (long)ctx->gap_open + ctx->gap_extend, ge = ctx->gap_extend;
     HIP_TRY(ctx, swg_launch_kmer_table(ctx->d_sub, ctx->d_query, ctx->query_pssm ? ctx->d_pssm : nullptr, (uint32_t)lq, (uint32_t)-go, (uint32_t)-ge, k,
-                                       (uint32_t)S, ctx->d_kmer_cprof, t->d, ctx->stream));
-    t->epoch = ctx->epoch, t->k = k, t->segments = S;
-    ++(t == &ctx->kmer_second ? ctx->kmer_refine_builds : ctx->kmer_builds);
+                                       (uint32_t)S, ctx->d_kmer_cprof, t->d, bits, ctx->stream));
+    t->epoch = ctx->epoch, t->k = k, t->segments = S, t->bits = bits;
+    ++(t == &ctx->kmer_third ? ctx->kmer_refine3_builds : t == &ctx->kmer_second ? ctx->kmer_refine_builds : ctx->kmer_builds);
     return SWG_OK;
 }
 
 // What a pruned search reads besides the fill's own: the colmax table for the current query and scoring (built on the
 // host when either has changed; it travels to the bound kernels as a launch argument), the k-mer tables of the plan's
-// choice -- the first level's within SWG_KMER_TABLE_BUDGET, the second level's queued behind it and counted apart -- and
+// choice -- the first level's within SWG_KMER_TABLE_BUDGET, the second and third levels' queued behind it and counted apart -- and
 // the slot's buffer of pair bounds (swg_prune_layout).
 static int prepare_prune(swg_ctx *ctx, swg_db *db, const SwgPrunePlan &pr)
 {
     int rc;
-    if (ctx->prune_colmax_epoch != ctx->epoch) {
-        ctx->prune_colmax = ctx->query_pssm ? swg_prune_colmax(ctx->pssm.data(), nullptr, ctx->query_len())
-                                            : swg_prune_colmax(&ctx->sub[0][0], ctx->query.data(), ctx->query_len());
-        ctx->prune_colmax_epoch = ctx->epoch;
-    }
+    ensure_prune_colmax(ctx);
     if (pr.kmer > 1) {
         const int k = pr.kmer, S = pr.segments;
         if (S < 1 || S > (int)SWG_KMER_MAX_SEGMENTS) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the k-mer bound's table: %d segments (1..32)", S);
@@ -2424,6 +2454,10 @@ static int prepare_prune(swg_ctx *ctx, swg_db *db, const SwgPrunePlan &pr)
     if (pr.refine) {
         if (pr.refine != 64 && pr.refine != 128) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the second-level bound's table: %d segments (64 or 128)", pr.refine);
         if ((rc = ensure_kmer_table(ctx, &ctx->kmer_second, 4, pr.refine)) != SWG_OK) return rc;
+    }
+    if (pr.refine3) {
+        if (pr.refine3 != 256) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the third-level bound's table: %d segments (256)", pr.refine3);
+        if ((rc = ensure_kmer_table(ctx, &ctx->kmer_third, 4, pr.refine3)) != SWG_OK) return rc;
     }
     swg_db::Bufs &b = db->bufs[ctx->cur - ctx->slots];
     const size_t n_pairs = (size_t)swg_db_pair_count(db);
@@ -2904,9 +2938,15 @@ static int debug_prune_read(swg_ctx *ctx, const swg_db *db, const char *fn, cons
                              ctx->kmer_refine_builds, 0};
     std::copy(all, all + n_info, info);
     if (table_out) {
-        if (!table || !table->holds(ctx->epoch, k, S))
+        if (!table || !table->holds(ctx->epoch, k, S, table->bits))
             return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: no table of k = %d in %d segments for the current query and scoring", fn, k, S);
-        HIP_TRY(ctx, hipMemcpy(table_out, table->d, (size_t)swg_kmer_entries(k) * (size_t)S * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        const size_t entries = (size_t)swg_kmer_entries(k) * (size_t)S;
+        if (table->bits == 8) { // (widened: the hooks hand out uint16_t whatever the device keeps)
+            std::vector<uint8_t> narrow(entries);
+            HIP_TRY(ctx, hipMemcpy(narrow.data(), table->d, entries, hipMemcpyDeviceToHost));
+            std::copy(narrow.begin(), narrow.end(), table_out);
+        } else
+            HIP_TRY(ctx, hipMemcpy(table_out, table->d, entries * sizeof(uint16_t), hipMemcpyDeviceToHost));
     }
     if (bound_out || list_out || stages_out) {
         if (!db || !db->d_pair_bound || pair_cap < n_pairs) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: no pair bounds on this database, or too little room", fn);
@@ -2943,8 +2983,25 @@ extern "C" int swg_debug_prune_kmer_seg_read(swg_ctx *ctx, const swg_db *db, int
 extern "C" int swg_debug_prune_refine_read(swg_ctx *ctx, const swg_db *db, int S2, uint16_t *table_out, uint32_t *bound_out, uint32_t *list_out, size_t pair_cap,
                                            uint32_t *stages_out, size_t stages_cap, uint64_t *info)
 {
-    return debug_prune_read(ctx, db, "swg_debug_prune_refine_read", ctx ? &ctx->kmer_second : nullptr, 4, S2, table_out, bound_out, list_out, pair_cap, stages_out,
-                            stages_cap, 7, info);
+    return debug_prune_read(ctx, db, "swg_debug_prune_refine_read", ctx ? (S2 == 256 ? &ctx->kmer_third : &ctx->kmer_second) : nullptr, 4, S2, table_out, bound_out,
+                            list_out, pair_cap, stages_out, stages_cap, 7, info);
+}
+// ... the third level and the widths: out[0..6] = S3 of the search last begun (0: no third level), third-level builds so
+// far, then the entry bits of the tables that hold the current query and scoring (0: none): first level k = 4, k = 5,
+// second level, third level; out[6] = what "prune_table_bits" left automatic gives at k = 4 (8 or 16)
+extern "C" int swg_debug_prune_tables(swg_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_tables: NULL argument");
+    const SwgKmerTable *t[4] = {&ctx->kmer_first[0], &ctx->kmer_first[1], &ctx->kmer_second, &ctx->kmer_third};
+    out[0] = ctx->prune_choice.refine3;
+    out[1] = (int64_t)ctx->kmer_refine3_builds;
+    for (int i = 0; i < 4; ++i) out[2 + i] = t[i]->d && t[i]->epoch == ctx->epoch ? t[i]->bits : 0;
+    out[6] = 0;
+    if (ctx->query_len() > 0) {
+        ensure_prune_colmax(ctx);
+        out[6] = swg_kmer_table_bits(ctx->prune_colmax, 4);
+    }
+    return SWG_OK;
 }
 
 extern "C" int swg_prune_last(const swg_ctx *ctx, swg_prune_info *out)

@@ -697,6 +697,7 @@ std::vector<SwgPruneStage> swg_prune_stages(const SwgPrunePlan &plan, const std:
         else {
             if (plan.refine && plan.fixed && si == 0 && stages.size() > 1) q |= SWG_STAGE_GATE;
             if (plan.refine) q |= SWG_STAGE_REFINE;
+            if (plan.refine3) q |= SWG_STAGE_REFINE3;
             q |= SWG_STAGE_LIST;
         }
         stages[si].queued = q;
@@ -704,20 +705,24 @@ std::vector<SwgPruneStage> swg_prune_stages(const SwgPrunePlan &plan, const std:
     return stages;
 }
 
-extern "C" int swg_debug_prune_stages(const int64_t *in, int64_t *out, size_t cap, size_t *n_out)
+// (head: the words in front of the segments -- 5, or 6 with the third level's in[4])
+static int debug_prune_stages(const int64_t *in, int head, int64_t *out, size_t cap, size_t *n_out)
 {
-    if (!in || !n_out || (cap > 0 && !out) || in[0] < 0 || in[4] < 0) return SWG_ERR_ARG;
+    if (!in || !n_out || (cap > 0 && !out) || in[0] < 0 || in[head - 1] < 0) return SWG_ERR_ARG;
     SwgPrunePlan plan;
     plan.on = true;
     plan.head_pairs = (uint32_t)in[0], plan.fixed = in[1] != 0, plan.refine = (int)in[2], plan.prefix_cut = in[3] != 0;
+    plan.refine3 = head == 6 ? (int)in[4] : 0;
     std::vector<std::pair<uint32_t, uint32_t>> segments;
-    for (int64_t i = 0; i < in[4]; ++i) segments.emplace_back((uint32_t)in[5 + 2 * i], (uint32_t)in[6 + 2 * i]);
+    for (int64_t i = 0; i < in[head - 1]; ++i) segments.emplace_back((uint32_t)in[head + 2 * i], (uint32_t)in[head + 1 + 2 * i]);
     const std::vector<SwgPruneStage> stages = swg_prune_stages(plan, segments);
     for (size_t i = 0; i < stages.size() && i < cap; ++i)
         out[4 * i] = stages[i].begin, out[4 * i + 1] = stages[i].end, out[4 * i + 2] = stages[i].segment, out[4 * i + 3] = stages[i].queued;
     *n_out = stages.size();
     return SWG_OK;
 }
+extern "C" int swg_debug_prune_stages(const int64_t *in, int64_t *out, size_t cap, size_t *n_out) { return debug_prune_stages(in, 5, out, cap, n_out); }
+extern "C" int swg_debug_prune_stages3(const int64_t *in, int64_t *out, size_t cap, size_t *n_out) { return debug_prune_stages(in, 6, out, cap, n_out); }
 
 // The k-mer form of the bound, on the host: what the device builds (swg_kmer_cprof_kernel,
 // swg_kmer_table_kernel) and sums (swg_pair_bound_kmer_kernel), restated for the tests.  cprof[lq][22]: query column i
@@ -846,6 +851,18 @@ extern "C" int swg_debug_prune_kmer_refine(const int8_t *rows, const int8_t *idx
                                            const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out)
 {
     return debug_prune_kmer(S2 == 32 || S2 == 64 || S2 == 128, rows, idx, lq, gap_open, gap_extend, 4, S2, flat, offsets, n, table_out, u_out);
+}
+// ... and the third level's: k = 4 over the 256 segments swg_pair_bound_refine_kernel<4, 8> walks.  The tables of all
+// these hooks are uint16_t whatever width the device keeps: the values are the same (swg_kmer_table_bits).
+extern "C" int swg_debug_prune_kmer_refine3(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S3, const int8_t *flat,
+                                            const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out)
+{
+    return debug_prune_kmer(S3 == 256, rows, idx, lq, gap_open, gap_extend, 4, S3, flat, offsets, n, table_out, u_out);
+}
+extern "C" int swg_debug_prune_table_bits(const int8_t *rows, const int8_t *idx, size_t lq, int k)
+{
+    if (!rows || lq == 0 || (k != 4 && k != 5)) return SWG_ERR_ARG;
+    return swg_kmer_table_bits(swg_prune_colmax(rows, idx, lq), k);
 }
 
 // Which bound a pruned search cuts by: k = 1 (colmax), 4 or 5 (k-mer tables) and the S segments of its table (1: the
@@ -976,6 +993,42 @@ extern "C" int swg_debug_prune_refine_choice(const int64_t *in, int64_t *out)
     out[0] = swg_prune_kmer_choice(a, &S);
     out[1] = S;
     out[2] = swg_prune_refine_choice(a, (int)out[0], S);
+    return SWG_OK;
+}
+
+// The third level: 256 segments behind the second level's walk.  Forced ("prune_refine3" = 256), behind whatever the
+// second level is; off ("prune_refine3" = 1); automatic only where the second level was chosen automatically and took
+// 128 -- so under no forced "prune_kmer", "prune_segments" or "prune_refine" --, the tables are byte-wide (the 256-segment
+// table is then the 60 MB the 128-segment one is as uint16_t, and a lane's 8 entries one 8-byte load) and the candidate
+// rule of the other levels holds: the table's build and the walk cost at most half of what the tighter cut saves.  The
+// Constants: profiles/prune_bytes_ab.txt -- rows kept 0.2249 at 128 segments, 0.2098 at 256 (section 2); the walk at 256
+// segments over byte tables 3.37 ms per search over 1 938 193 684 pair rows (section 3).
+#define SWG_REFINE3_GAIN 0.0151
+#define SWG_REFINE3_BOUND_ROW 1.74e-12
+int swg_prune_refine3_choice(const SwgKmerAsk &a, int k, int S, int S2)
+{
+    if (!a.pruned || k < 1) return 0;
+    if (a.forced_refine3 == 256) return 256;
+    if (a.forced_refine3 != 0 || a.forced != 0 || a.forced_segments != 0 || a.forced_refine != 0) return 0;
+    if (k != 4 || S <= 1 || S2 != 128 || a.table_bits != 8) return 0;
+    if (a.table_rate <= 0 || a.fill_rate <= 0 || a.lq == 0) return 0;
+    const double cost = (double)swg_kmer_entries(4) * 4 * (double)a.lq / a.table_rate + SWG_REFINE3_BOUND_ROW * (double)a.pair_rows;
+    const double gain = SWG_REFINE3_GAIN * (double)a.pair_rows / a.fill_rate;
+    return cost <= 0.5 * gain ? 256 : 0;
+}
+
+extern "C" int swg_debug_prune_refine3_choice(const int64_t *in, int64_t *out)
+{
+    SwgKmerAsk a;
+    if (!debug_kmer_ask(in, out, 8, &a)) return SWG_ERR_ARG;
+    if (!swg_prune_refine3_value_ok((long)in[8]) || (in[9] != 0 && in[9] != 8 && in[9] != 16)) return SWG_ERR_ARG;
+    a.forced_refine3 = (long)in[8];
+    a.table_bits = in[9] == 16 ? 16 : 8;
+    int S = 0;
+    out[0] = swg_prune_kmer_choice(a, &S);
+    out[1] = S;
+    out[2] = swg_prune_refine_choice(a, (int)out[0], S);
+    out[3] = swg_prune_refine3_choice(a, (int)out[0], S, (int)out[2]);
     return SWG_OK;
 }
 

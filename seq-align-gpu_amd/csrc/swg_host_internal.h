@@ -269,6 +269,7 @@ struct SwgPrunePlan {
     int kmer = 0;            // the bound: 1 colmax, 4 / 5 the k-mer table of that k (swg_prune_kmer_choice); 0 while off
     int segments = 0;        // ... and the segments of that table (1: the unordered sum of swg_pair_bound_kmer_kernel)
     int refine = 0;          // the second level's segments (swg_prune_refine_choice): 64, 128, or 0 without one
+    int refine3 = 0;         // the third level's segments (swg_prune_refine3_choice): 256, or 0 without one
     bool prefix_cut = false; // option "prune_cut" = 1: a stage's list is the prefix up to its last pair that reaches T
     bool fixed = false;      // a caller's threshold: every stage, the first included, is a list launch cut at fixed_T
     uint32_t fixed_T = 0;    // ... written once to the threshold word and never recomputed
@@ -294,8 +295,10 @@ SwgPrunePlan swg_prune_plan(const SwgPruneAsk &a);
 // score so far, which a threshold kernel computes in front of it; under a caller's threshold (plan.fixed) the first is
 // cut too and no threshold kernel runs.  A cut is the prefix cut (plan.prefix_cut), or pair by pair: the refine pass
 // where there is a second level (plan.refine) -- behind the gate on the first of several stages under a caller's
-// threshold --, then the list.
-enum : uint32_t { SWG_STAGE_THRESHOLD = 1u, SWG_STAGE_PREFIX_CUT = 2u, SWG_STAGE_GATE = 4u, SWG_STAGE_REFINE = 8u, SWG_STAGE_LIST = 16u };
+// threshold --, the third level's (plan.refine3) behind it under the same threshold word, then the list.
+enum : uint32_t {
+    SWG_STAGE_THRESHOLD = 1u, SWG_STAGE_PREFIX_CUT = 2u, SWG_STAGE_GATE = 4u, SWG_STAGE_REFINE = 8u, SWG_STAGE_LIST = 16u, SWG_STAGE_REFINE3 = 32u
+};
 struct SwgPruneStage {
     uint32_t begin, end; // pairs
     uint32_t segment;    // index into `segments`
@@ -305,6 +308,8 @@ std::vector<SwgPruneStage> swg_prune_stages(const SwgPrunePlan &plan, const std:
 // test hook: in[0..4] = head_pairs, fixed, refine, prefix_cut, the number of segments n, then n x {begin, end}; out: four
 // words per stage {begin, end, segment, queued}, copied while they fit cap stages; *n_out = the number of stages
 extern "C" int swg_debug_prune_stages(const int64_t *in, int64_t *out, size_t cap, size_t *n_out);
+// ... with the third level: in[0..5] = head_pairs, fixed, refine, prefix_cut, refine3, n, then the n segments
+extern "C" int swg_debug_prune_stages3(const int64_t *in, int64_t *out, size_t cap, size_t *n_out);
 // The automatic rule of a caller's threshold ("A caller's threshold"; profiles/search_above_ab.txt): the
 // bound, list and tally kernels of a stage cost tens of microseconds whatever the range holds, a list launch one
 // dependent load per claim; a range with at least SWG_PRUNE_ABOVE_AUTO_PAIRS pairs per resident lane group has fills
@@ -345,12 +350,15 @@ struct SwgKmerAsk {
     long forced = 0;     // option "prune_kmer": 0 automatic, 1, 4, 5
     long forced_segments = 0; // option "prune_segments": 0 automatic, 1..SWG_KMER_MAX_SEGMENTS
     long forced_refine = 0;   // option "prune_refine": 0 automatic, 1 off, 64 or 128
+    long forced_refine3 = 0;  // option "prune_refine3": 0 automatic, 1 off, 256
+    int table_bits = 8;       // the width of the k = 4 tables' entries for this query and scoring (swg_kmer_table_bits, "prune_table_bits")
     bool pruned = false; // swg_prune_plan's answer
     size_t lq = 0;
     uint64_t pair_rows = 0; // rows of the range's pairs
     double table_rate = SWG_KMER_TABLE_RATE, fill_rate = 0;
 };
-// whether a context builds the first-level table of (k, S): within SWG_KMER_TABLE_BUDGET (prepare_prune refuses the others)
+// whether a context builds the first-level table of (k, S): within SWG_KMER_TABLE_BUDGET at 16 bits an entry, whatever
+// width the table takes (prepare_prune refuses the others)
 inline bool swg_kmer_table_admitted(int k, long S)
 {
     return S >= 1 && S <= (long)SWG_KMER_MAX_SEGMENTS && swg_kmer_entries(k) * (uint64_t)S * sizeof(uint16_t) <= SWG_KMER_TABLE_BUDGET;
@@ -369,6 +377,17 @@ inline bool swg_prune_refine_value_ok(long v) { return v == 0 || v == 1 || v == 
 extern "C" int swg_debug_prune_refine_choice(const int64_t *in, int64_t *out);
 extern "C" int swg_debug_prune_kmer_refine(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S2, const int8_t *flat,
                                            const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out);
+// The third level: 256 segments of the k = 4 table behind the second level's walk, or 0 for none (k, S, S2: what the
+// first and second levels took).
+int swg_prune_refine3_choice(const SwgKmerAsk &a, int k, int S, int S2);
+inline bool swg_prune_refine3_value_ok(long v) { return v == 0 || v == 1 || v == 256; }
+// test hooks: in[0..7] as swg_debug_prune_refine_choice, in[8] = option "prune_refine3", in[9] = the tables' entry width
+// (0: bytes) -> out[0..3] = k, S, S2, S3; the mirror of the third level's bound (S3 = 256); and the entry width of the
+// k-mer tables of a query (rows / idx as the mirrors take them) -> 8 or 16
+extern "C" int swg_debug_prune_refine3_choice(const int64_t *in, int64_t *out);
+extern "C" int swg_debug_prune_kmer_refine3(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S3, const int8_t *flat,
+                                            const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out);
+extern "C" int swg_debug_prune_table_bits(const int8_t *rows, const int8_t *idx, size_t lq, int k);
 // the words of a search's counter block (swg_db::Bufs::d_counters) a pruned search uses: the threshold so far and the
 // threshold kernel's status word, then what swg_launch_prune_cut or swg_launch_prune_list writes: the pairs the stage
 // takes, the pairs skipped so far, their token blocks (64 bits)
@@ -452,15 +471,16 @@ struct SwgBatchPlan {
 // A k-mer table on the device and what it was built with; one buffer per table, so searches that alternate between
 // two of them build each once per epoch.
 struct SwgKmerTable {
-    uint16_t *d = nullptr;
-    size_t cap = 0;     // entries allocated
+    uint8_t *d = nullptr;
+    size_t cap = 0;     // bytes allocated
     uint64_t epoch = 0; // the (query, scoring) epoch it holds (0: nothing; a re-allocated table loses it)
     int k = 0, segments = 0;
-    bool holds(uint64_t e, int k_, int S) const { return d && epoch == e && k == k_ && segments == S; }
+    int bits = 0;       // of an entry: 8 or 16 (swg_kmer_table_bits, or 16 under option "prune_table_bits")
+    bool holds(uint64_t e, int k_, int S, int bits_) const { return d && epoch == e && k == k_ && segments == S && bits == bits_; }
 };
-// The bound a pruned search cuts by: k (0: not pruned), its segments S, the second level's S2 (0: none)
+// The bound a pruned search cuts by: k (0: not pruned), its segments S, the second level's S2 and the third's S3 (0: none)
 struct SwgPruneChoice {
-    int kmer = 0, segments = 0, refine = 0;
+    int kmer = 0, segments = 0, refine = 0, refine3 = 0;
 };
 
 // One search in flight: its timing events, host-side landing buffers and what swg_search_end
@@ -550,11 +570,13 @@ struct swg_ctx {
     long opt_prune_kmer = 0;
     long opt_prune_segments = 0; // option "prune_segments": 0 auto, 1..32
     long opt_prune_refine = 0;   // option "prune_refine": 0 auto, 1 off, 64, 128
+    long opt_prune_refine3 = 0;  // option "prune_refine3": 0 auto, 1 off, 256
+    long opt_prune_table_bits = 0; // option "prune_table_bits": 0 auto (bytes where they hold every entry), 16
     long opt_prune_cut = 0;      // option "prune_cut": 0 pair by pair, 1 the prefix of the length order
     int8_t *d_kmer_cprof = nullptr;
     size_t d_kmer_cprof_cap = 0;
-    SwgKmerTable kmer_first[2], kmer_second; // [k - 4]
-    uint64_t kmer_builds = 0, kmer_refine_builds = 0; // builds queued so far of the first level's tables, of the second's (tests)
+    SwgKmerTable kmer_first[2], kmer_second, kmer_third; // [k - 4]
+    uint64_t kmer_builds = 0, kmer_refine_builds = 0, kmer_refine3_builds = 0; // builds queued so far, level by level (tests)
     uint32_t opt_seg_blocks = SWG_DYN_SEG_BLOCKS; // token blocks per launch of the multi-pass fill (option "segment_blocks": tests)
     // device state
     int8_t *d_sub = nullptr;

@@ -344,24 +344,35 @@ static inline uint64_t swg_kmer_entries(int k) { return k == 5 ? 5153632ull : k 
 // columns (S = 1: the block's local score against the whole query).  At most SWG_KMER_MAX_SEGMENTS segments -- one lane
 // of the ordered bound kernel each -- and SWG_KMER_TABLE_BUDGET bytes, which admits (k, S) = (5, 8).
 #define SWG_KMER_MAX_SEGMENTS 32u
-// ... and of the second level's table, which only the pairs a first-level bound leaves standing are walked over (k = 4:
-// 60 MB at 128 segments), four segments to a lane
-#define SWG_KMER_REFINE_SEGMENTS 128u
+// ... and of the second and third levels' tables, which only the pairs an earlier bound leaves standing are walked over
+// (k = 4: 128 segments, four to a lane, then 256, eight to a lane -- 30 and 60 MB as bytes)
+#define SWG_KMER_REFINE_SEGMENTS 256u
 #define SWG_KMER_TABLE_BUDGET (96ull << 20)
+// The width of a table's entries: an entry is at most k times the largest colmax entry (a block's rows are matched once
+// each, class 21's score is the best of residues that each have their colmax entry, gaps add nothing), so a table whose
+// k x max colmax is at most 255 holds bytes, value for value what the uint16_t table holds; any other keeps uint16_t.
+// A property of (query, scoring, k).
+static inline int swg_kmer_table_bits(const SwgColMax &cm, int k)
+{
+    uint32_t m = 0u;
+    for (int r = 0; r < 32; ++r) m = cm.v[r] > m ? cm.v[r] : m;
+    return (uint32_t)k * m <= 255u ? 8 : 16;
+}
 // d_cprof[lq][32] (int8; entries 22..31 of a row unused): query column i against class c, from the device copies of the
 // table and the index query (d_pssm == NULL) or of the PSSM; then d_table[22^k][S] = the best cell of every class block
 // against the query, segment by segment, under gap magnitudes g (first residue of a gap) and e (every further one).
-// k: 4 or 5; S: 1..SWG_KMER_REFINE_SEGMENTS (the bound kernels take what they can walk: see each).
+// k: 4 or 5; S: 1..SWG_KMER_REFINE_SEGMENTS (the bound kernels take what they can walk: see each).  bits: 8 or 16, the
+// width of d_table's entries, here and in every launch below that reads the table (swg_kmer_table_bits).
 hipError_t swg_launch_kmer_table(const int8_t *d_sub, const int8_t *d_query, const int8_t *d_pssm, uint32_t lq, uint32_t g, uint32_t e,
-                                 int k, uint32_t S, int8_t *d_cprof, uint16_t *d_table, hipStream_t stream);
+                                 int k, uint32_t S, int8_t *d_cprof, void *d_table, int bits, hipStream_t stream);
 // swg_launch_pair_bound with the k-mer bound: blocks of 4 token rows (k = 4), or of 5 with a tail of fewer than 20 rows
 // in blocks of 4 (k = 5); a block adds the lesser of its table entry and its rows' colmax entries
 hipError_t swg_launch_pair_bound_kmer(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, int k, const SwgColMax &cm,
-                                      const uint16_t *d_table, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream);
+                                      const void *d_table, int bits, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream);
 // ... and its ordered form over the table of S segments: the blocks in order, H[s] = max_{s' <= s} H[s'] + the block's
 // entry of segment s (or its colmax sum where that is less), the bound max_s H[s]
 hipError_t swg_launch_pair_bound_kmer_seg(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, int k, uint32_t S, const SwgColMax &cm,
-                                          const uint16_t *d_table, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream);
+                                          const void *d_table, int bits, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream);
 // d_thr[0] = the k-th largest entry of d_scores (clamped to 4095; 0 with fewer than k entries): swg_topk_hist_kernel and
 // swg_topk_threshold_kernel on `stream`; d_thr[1] is written too (the status word, not read)
 hipError_t swg_launch_prune_threshold(const int32_t *d_scores, const uint32_t *d_order, uint32_t n_slots, uint32_t k, uint32_t *d_hist,
@@ -370,10 +381,10 @@ hipError_t swg_launch_prune_threshold(const int32_t *d_scores, const uint32_t *d
 // stage's launches take), d_out[1] += the pairs behind the cut, (uint64 at d_out[2]) += their token blocks
 hipError_t swg_launch_prune_cut(const uint32_t *d_bound, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, const uint32_t *d_thr,
                                 uint32_t *d_out, hipStream_t stream);
-// The second level: d_bound[p] = min(d_bound[p], the ordered bound over d_table, k = 4 in S2 = 64 or 128 segments) for the
-// pairs of [begin, end) with d_bound[p] >= *d_thr
+// The second and third levels: d_bound[p] = min(d_bound[p], the ordered bound over d_table, k = 4 in S2 = 64, 128 or 256
+// segments) for the pairs of [begin, end) with d_bound[p] >= *d_thr
 hipError_t swg_launch_pair_bound_refine(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, uint32_t S2, const SwgColMax &cm,
-                                        const uint16_t *d_table, const uint32_t *d_thr, uint32_t *d_bound, hipStream_t stream);
+                                        const void *d_table, int bits, const uint32_t *d_thr, uint32_t *d_bound, hipStream_t stream);
 // The cut pair by pair: d_list[0 .. d_out[0]) = the pairs of [begin, end) with d_bound >= *d_thr, ascending; d_out[1] +=
 // the others, (uint64 at d_out[2]) += their token blocks.  d_tiles: one word per SWG_PRUNE_TILE pairs of the range;
 // d_rec (or NULL): {*d_thr, d_out[0]} once more, for the tests.

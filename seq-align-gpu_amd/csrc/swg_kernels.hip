@@ -2969,11 +2969,13 @@ __global__ __launch_bounds__(256) void swg_kmer_cprof_kernel(const int8_t *sub, 
 // the running maximum stored and reset where a segment ends.  The S segments are W = ceil(lq / S) columns each; one
 // without columns (lq < S * W) holds 0.  S = 1: the block's local score against the whole query.  The query position is
 // the same for the whole workgroup: the class profile goes through LDS in chunks, a row's 22 bytes are 6 dwords in 6 banks.
+// E: the entries' type -- uint8_t where swg_kmer_table_bits allows it (no entry reaches the clamp then), else uint16_t.
 #define SWG_KMER_CHUNK 256u
-template <int K>
+template <int K, class E>
 __global__ __launch_bounds__(256) void swg_kmer_table_kernel(const int8_t *cprof, uint32_t lq, int g, int e, uint32_t n_entries, uint32_t S,
-                                                             uint16_t *table)
+                                                             E *table)
 {
+    constexpr int top = sizeof(E) == 1 ? 255 : 65535;
     __shared__ uint4 rows4[SWG_KMER_CHUNK * 2u];
     const int8_t *rows = reinterpret_cast<const int8_t *>(rows4);
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
@@ -2990,7 +2992,7 @@ __global__ __launch_bounds__(256) void swg_kmer_table_kernel(const int8_t *cprof
 #pragma unroll
     for (int j = 0; j < K; ++j) M[j] = 0, A[j] = 0;
     const uint32_t W = (lq + S - 1u) / S;
-    uint16_t *out = table + (size_t)(idx < n_entries ? idx : 0u) * S;
+    E *out = table + (size_t)(idx < n_entries ? idx : 0u) * S;
     uint32_t seg = 0u, seg_end = W < lq ? W : lq; // (the column behind the current segment's last)
     for (uint32_t i0 = 0u; i0 < lq; i0 += SWG_KMER_CHUNK) {
         const uint32_t n = lq - i0 < SWG_KMER_CHUNK ? lq - i0 : SWG_KMER_CHUNK;
@@ -3011,7 +3013,7 @@ __global__ __launch_bounds__(256) void swg_kmer_table_kernel(const int8_t *cprof
                 best = max(best, m);
             }
             if (i0 + i + 1u == seg_end) { // (the same for every thread)
-                if (idx < n_entries) out[seg] = (uint16_t)(best > 65535 ? 65535 : best);
+                if (idx < n_entries) out[seg] = (E)(best > top ? top : best);
                 ++seg, best = 0;
                 seg_end = seg_end + W < lq ? seg_end + W : lq;
             }
@@ -3022,17 +3024,22 @@ __global__ __launch_bounds__(256) void swg_kmer_table_kernel(const int8_t *cprof
 }
 
 hipError_t swg_launch_kmer_table(const int8_t *d_sub, const int8_t *d_query, const int8_t *d_pssm, uint32_t lq, uint32_t g, uint32_t e,
-                                 int k, uint32_t S, int8_t *d_cprof, uint16_t *d_table, hipStream_t stream)
+                                 int k, uint32_t S, int8_t *d_cprof, void *d_table, int bits, hipStream_t stream)
 {
     const uint32_t n = (uint32_t)swg_kmer_entries(k);
-    if (n == 0u || lq == 0u || lq > (1u << 24) || S == 0u || S > SWG_KMER_REFINE_SEGMENTS) return hipErrorInvalidValue;
+    if (n == 0u || lq == 0u || lq > (1u << 24) || S == 0u || S > SWG_KMER_REFINE_SEGMENTS || (bits != 8 && bits != 16)) return hipErrorInvalidValue;
     // (gap magnitudes beyond any block's score change nothing, and keep the int32 cells far from their range)
     const int gi = (int)(g > 65536u ? 65536u : g), ei = (int)(e > 65536u ? 65536u : e);
     hipLaunchKernelGGL(swg_kmer_cprof_kernel, dim3((lq * 32u + 255u) / 256u), dim3(256), 0, stream, d_sub, d_query, d_pssm, lq, d_cprof);
-    if (k == 5)
-        hipLaunchKernelGGL(swg_kmer_table_kernel<5>, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_cprof, lq, gi, ei, n, S, d_table);
+    const dim3 grid((n + 255u) / 256u);
+    if (k == 5 && bits == 8)
+        hipLaunchKernelGGL((swg_kmer_table_kernel<5, uint8_t>), grid, dim3(256), 0, stream, d_cprof, lq, gi, ei, n, S, static_cast<uint8_t *>(d_table));
+    else if (k == 5)
+        hipLaunchKernelGGL((swg_kmer_table_kernel<5, uint16_t>), grid, dim3(256), 0, stream, d_cprof, lq, gi, ei, n, S, static_cast<uint16_t *>(d_table));
+    else if (bits == 8)
+        hipLaunchKernelGGL((swg_kmer_table_kernel<4, uint8_t>), grid, dim3(256), 0, stream, d_cprof, lq, gi, ei, n, S, static_cast<uint8_t *>(d_table));
     else
-        hipLaunchKernelGGL(swg_kmer_table_kernel<4>, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_cprof, lq, gi, ei, n, S, d_table);
+        hipLaunchKernelGGL((swg_kmer_table_kernel<4, uint16_t>), grid, dim3(256), 0, stream, d_cprof, lq, gi, ei, n, S, static_cast<uint16_t *>(d_table));
     return hipGetLastError();
 }
 
@@ -3041,9 +3048,9 @@ hipError_t swg_launch_kmer_table(const int8_t *d_sub, const int8_t *d_query, con
 // of the pair's two sequences.  K = 4: a block is one uint4.  K = 5: a lane takes five consecutive uint4s as four blocks
 // of 5 rows; the pair's last fewer-than-five uint4s are blocks of 4 rows, which in the table of 5 are class blocks with a
 // padding tail.  Reset rows and the rows past a sequence's end are the padding class wherever they fall in a block.
-template <int K>
+template <int K, class E>
 __global__ __launch_bounds__(256) void swg_pair_bound_kmer_kernel(const uint4 *tok, const uint32_t *pair_off, uint32_t n_pairs, SwgColMax cm,
-                                                                  const uint16_t *table, uint32_t *bound, uint32_t *ids)
+                                                                  const E *table, uint32_t *bound, uint32_t *ids)
 {
     __shared__ uint32_t lut[32]; // residue index -> class | colmax << 8
     if (threadIdx.x < 32u) lut[threadIdx.x] = swg_kmer_class(threadIdx.x) | (uint32_t)cm.v[threadIdx.x] << 8;
@@ -3101,14 +3108,21 @@ __global__ __launch_bounds__(256) void swg_pair_bound_kmer_kernel(const uint4 *t
 }
 
 hipError_t swg_launch_pair_bound_kmer(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, int k, const SwgColMax &cm,
-                                      const uint16_t *d_table, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream)
+                                      const void *d_table, int bits, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream)
 {
-    if (k != 4 && k != 5) return hipErrorInvalidValue;
+    if ((k != 4 && k != 5) || (bits != 8 && bits != 16)) return hipErrorInvalidValue;
     if (n_pairs == 0) return hipSuccess;
-    if (k == 5)
-        hipLaunchKernelGGL(swg_pair_bound_kmer_kernel<5>, dim3((n_pairs + 15u) / 16u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, d_bound, d_ids);
+    const dim3 grid((n_pairs + 15u) / 16u);
+    const uint8_t *t8 = static_cast<const uint8_t *>(d_table);
+    const uint16_t *t16 = static_cast<const uint16_t *>(d_table);
+    if (k == 5 && bits == 8)
+        hipLaunchKernelGGL((swg_pair_bound_kmer_kernel<5, uint8_t>), grid, dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, t8, d_bound, d_ids);
+    else if (k == 5)
+        hipLaunchKernelGGL((swg_pair_bound_kmer_kernel<5, uint16_t>), grid, dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, t16, d_bound, d_ids);
+    else if (bits == 8)
+        hipLaunchKernelGGL((swg_pair_bound_kmer_kernel<4, uint8_t>), grid, dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, t8, d_bound, d_ids);
     else
-        hipLaunchKernelGGL(swg_pair_bound_kmer_kernel<4>, dim3((n_pairs + 15u) / 16u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, d_bound, d_ids);
+        hipLaunchKernelGGL((swg_pair_bound_kmer_kernel<4, uint16_t>), grid, dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, t16, d_bound, d_ids);
     return hipGetLastError();
 }
 
@@ -3147,9 +3161,9 @@ __device__ __forceinline__ uint32_t swg_seg_prefix_max(uint32_t h, uint32_t m1, 
 }
 
 // one chunk: cnt (<= WD) units of NB blocks each, U units per round of gathers
-template <int WD, int NB, int U>
+template <int WD, int NB, int U, class E>
 __device__ __forceinline__ void swg_seg_chunk(const uint32_t (&ux)[NB], const uint32_t (&uy)[NB], const uint32_t (&uc)[NB], uint32_t cnt,
-                                              const uint16_t *tl, uint32_t S, bool has, uint32_t m1, uint32_t m2, uint32_t m4, uint32_t &hx,
+                                              const E *tl, uint32_t S, bool has, uint32_t m1, uint32_t m2, uint32_t m4, uint32_t &hx,
                                               uint32_t &hy)
 {
     for (uint32_t j0 = 0u; j0 < cnt; j0 += (uint32_t)U) {
@@ -3173,9 +3187,9 @@ __device__ __forceinline__ void swg_seg_chunk(const uint32_t (&ux)[NB], const ui
     }
 }
 
-template <int K, int WD>
+template <int K, int WD, class E>
 __global__ __launch_bounds__(256) void swg_pair_bound_kmer_seg_kernel(const uint4 *tok, const uint32_t *pair_off, uint32_t n_pairs, SwgColMax cm,
-                                                                      const uint16_t *table, uint32_t S, uint32_t *bound, uint32_t *ids)
+                                                                      const E *table, uint32_t S, uint32_t *bound, uint32_t *ids)
 {
     __shared__ uint32_t lut[32]; // residue index -> class | colmax << 8
     if (threadIdx.x < 32u) lut[threadIdx.x] = swg_kmer_class(threadIdx.x) | (uint32_t)cm.v[threadIdx.x] << 8;
@@ -3183,7 +3197,7 @@ __global__ __launch_bounds__(256) void swg_pair_bound_kmer_seg_kernel(const uint
     const uint32_t p = blockIdx.x * (256u / WD) + threadIdx.x / WD, l = threadIdx.x & (WD - 1u);
     const uint32_t C = SWG_KMER_CLASSES;
     const bool has = l < S;
-    const uint16_t *tl = table + (has ? l : 0u);
+    const E *tl = table + (has ? l : 0u);
     const uint32_t m1 = (l & 7u) >= 1u ? 0xFFFFFFFFu : 0u, m2 = (l & 7u) >= 2u ? 0xFFFFFFFFu : 0u, m4 = (l & 7u) >= 4u ? 0xFFFFFFFFu : 0u;
     uint32_t hx = 0u, hy = 0u;
     if (p < n_pairs) { // (the same for all lanes of a group, and so is every loop count below)
@@ -3237,27 +3251,33 @@ __global__ __launch_bounds__(256) void swg_pair_bound_kmer_seg_kernel(const uint
     }
 }
 
-template <int K>
+template <int K, class E>
 static void swg_launch_pair_bound_kmer_seg_k(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, const SwgColMax &cm,
-                                             const uint16_t *d_table, uint32_t S, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream)
+                                             const E *d_table, uint32_t S, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream)
 {
     if (S <= 8u)
-        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 8>), dim3((n_pairs + 31u) / 32u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids);
+        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 8, E>), dim3((n_pairs + 31u) / 32u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids);
     else if (S <= 16u)
-        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 16>), dim3((n_pairs + 15u) / 16u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids);
+        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 16, E>), dim3((n_pairs + 15u) / 16u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids);
     else
-        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 32>), dim3((n_pairs + 7u) / 8u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids);
+        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 32, E>), dim3((n_pairs + 7u) / 8u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids);
 }
 
 hipError_t swg_launch_pair_bound_kmer_seg(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, int k, uint32_t S, const SwgColMax &cm,
-                                          const uint16_t *d_table, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream)
+                                          const void *d_table, int bits, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream)
 {
-    if ((k != 4 && k != 5) || S == 0u || S > SWG_KMER_MAX_SEGMENTS) return hipErrorInvalidValue;
+    if ((k != 4 && k != 5) || S == 0u || S > SWG_KMER_MAX_SEGMENTS || (bits != 8 && bits != 16)) return hipErrorInvalidValue;
     if (n_pairs == 0) return hipSuccess;
-    if (k == 5)
-        swg_launch_pair_bound_kmer_seg_k<5>(d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids, stream);
+    const uint8_t *t8 = static_cast<const uint8_t *>(d_table);
+    const uint16_t *t16 = static_cast<const uint16_t *>(d_table);
+    if (k == 5 && bits == 8)
+        swg_launch_pair_bound_kmer_seg_k<5>(d_tok, d_pair_off, n_pairs, cm, t8, S, d_bound, d_ids, stream);
+    else if (k == 5)
+        swg_launch_pair_bound_kmer_seg_k<5>(d_tok, d_pair_off, n_pairs, cm, t16, S, d_bound, d_ids, stream);
+    else if (bits == 8)
+        swg_launch_pair_bound_kmer_seg_k<4>(d_tok, d_pair_off, n_pairs, cm, t8, S, d_bound, d_ids, stream);
     else
-        swg_launch_pair_bound_kmer_seg_k<4>(d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids, stream);
+        swg_launch_pair_bound_kmer_seg_k<4>(d_tok, d_pair_off, n_pairs, cm, t16, S, d_bound, d_ids, stream);
     return hipGetLastError();
 }
 
@@ -3316,9 +3336,10 @@ hipError_t swg_launch_prune_cut(const uint32_t *d_bound, const uint32_t *d_pair_
     return hipGetLastError();
 }
 
-// The second level of the ordered bound: the pairs of one cut stage whose first-level bound still reaches
-// the threshold are walked once more over a k = 4 table of S2 = 32 * PL segments.  32 lanes per pair, lane l holding H of
-// the PL consecutive segments from l * PL: a block's S2 entries are one load of 2 * PL bytes per lane and sequence, the
+// The second and third levels of the ordered bound: the pairs of one cut stage whose bound so far still
+// reaches the threshold are walked once more over a k = 4 table of S2 = 32 * PL segments (PL = 2, 4: the second level;
+// PL = 8: the third, behind it).  32 lanes per pair, lane l holding H of the PL consecutive segments from l * PL: a block's
+// S2 entries are one load of PL entries (PL bytes, or 2 * PL as uint16_t) per lane and sequence, the
 // prefix maximum runs in the lane over its PL values and then, as an exclusive prefix maximum of the lanes' last ones,
 // across the lanes (swg_seg_prefix_max<32> behind a one-lane shift).  Chunks, padding, reset and tail rules and the
 // gathers issued ahead of the recurrence are swg_pair_bound_kmer_seg_kernel's.  The segments' boundaries are not the
@@ -3339,12 +3360,16 @@ __device__ __forceinline__ void swg_refine_step(uint32_t (&h)[PL], const uint32_
     for (int j = 0; j < PL; ++j) h[j] = (ex > pm[j] ? ex : pm[j]) + t[j];
 }
 
-// a lane's PL entries of one block, each capped by the block's colmax sum c
+// a lane's PL entries of one block, each capped by the block's colmax sum c: one load of PL * sizeof(E) bytes (`at` is
+// aligned to that: the table's base to 256 bytes, a block's row and a lane's place in it to multiples of PL entries)
 template <int PL>
 __device__ __forceinline__ void swg_refine_entries(const uint16_t *at, uint32_t c, uint32_t (&t)[PL])
 {
-    uint32_t w[2] = {0u, 0u};
-    if (PL == 4) {
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (PL == 8) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(at);
+        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+    } else if (PL == 4) {
         const uint2 v = *reinterpret_cast<const uint2 *>(at);
         w[0] = v.x, w[1] = v.y;
     } else {
@@ -3356,12 +3381,30 @@ __device__ __forceinline__ void swg_refine_entries(const uint16_t *at, uint32_t 
         t[j] = e < c ? e : c;
     }
 }
-
-template <int K, int PL>
-__global__ __launch_bounds__(256) void swg_pair_bound_refine_kernel(const uint4 *tok, const uint32_t *pair_off, uint32_t begin, uint32_t end, SwgColMax cm,
-                                                                    const uint16_t *table, const uint32_t *thr, uint32_t *bound)
+template <int PL>
+__device__ __forceinline__ void swg_refine_entries(const uint8_t *at, uint32_t c, uint32_t (&t)[PL])
 {
-    static_assert(K == 4 && (PL == 2 || PL == 4), "the refined bound: k = 4 over 64 or 128 segments");
+    uint32_t w[2] = {0u, 0u};
+    if (PL == 8) {
+        const uint2 v = *reinterpret_cast<const uint2 *>(at);
+        w[0] = v.x, w[1] = v.y;
+    } else if (PL == 4) {
+        w[0] = *reinterpret_cast<const uint32_t *>(at);
+    } else {
+        w[0] = *reinterpret_cast<const uint16_t *>(at);
+    }
+#pragma unroll
+    for (int j = 0; j < PL; ++j) {
+        const uint32_t e = (w[j / 4] >> (8 * (j & 3))) & 0xFFu;
+        t[j] = e < c ? e : c;
+    }
+}
+
+template <int K, int PL, class E>
+__global__ __launch_bounds__(256) void swg_pair_bound_refine_kernel(const uint4 *tok, const uint32_t *pair_off, uint32_t begin, uint32_t end, SwgColMax cm,
+                                                                    const E *table, const uint32_t *thr, uint32_t *bound)
+{
+    static_assert(K == 4 && (PL == 2 || PL == 4 || PL == 8), "the refined bound: k = 4 over 64, 128 or 256 segments");
     __shared__ uint32_t lut[32]; // residue index -> class | colmax << 8
     if (threadIdx.x < 32u) lut[threadIdx.x] = swg_kmer_class(threadIdx.x) | (uint32_t)cm.v[threadIdx.x] << 8;
     __syncthreads();
@@ -3370,7 +3413,7 @@ __global__ __launch_bounds__(256) void swg_pair_bound_refine_kernel(const uint4 
     const uint32_t T = thr[0], first = bound[p];
     if (first < T) return;
     const uint32_t C = SWG_KMER_CLASSES, S2 = 32u * PL;
-    const uint16_t *tl = table + l * PL;
+    const E *tl = table + l * PL;
     const uint32_t m0 = l >= 1u ? 0xFFFFFFFFu : 0u;
     uint32_t hx[PL], hy[PL];
 #pragma unroll
@@ -3416,15 +3459,22 @@ __global__ __launch_bounds__(256) void swg_pair_bound_refine_kernel(const uint4 
 }
 
 hipError_t swg_launch_pair_bound_refine(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, uint32_t S2, const SwgColMax &cm,
-                                        const uint16_t *d_table, const uint32_t *d_thr, uint32_t *d_bound, hipStream_t stream)
+                                        const void *d_table, int bits, const uint32_t *d_thr, uint32_t *d_bound, hipStream_t stream)
 {
-    if (end < begin || (S2 != 64u && S2 != 128u)) return hipErrorInvalidValue;
+    if (end < begin || (S2 != 64u && S2 != 128u && S2 != 256u) || (bits != 8 && bits != 16)) return hipErrorInvalidValue;
     if (end == begin) return hipSuccess;
-    const uint32_t wgs = (end - begin + 7u) / 8u;
-    if (S2 == 128u)
-        hipLaunchKernelGGL((swg_pair_bound_refine_kernel<4, 4>), dim3(wgs), dim3(256), 0, stream, d_tok, d_pair_off, begin, end, cm, d_table, d_thr, d_bound);
-    else
-        hipLaunchKernelGGL((swg_pair_bound_refine_kernel<4, 2>), dim3(wgs), dim3(256), 0, stream, d_tok, d_pair_off, begin, end, cm, d_table, d_thr, d_bound);
+    const dim3 grid((end - begin + 7u) / 8u);
+    const uint8_t *t8 = static_cast<const uint8_t *>(d_table);
+    const uint16_t *t16 = static_cast<const uint16_t *>(d_table);
+#define SWG_REFINE_LAUNCH(PL, E, t) \
+    hipLaunchKernelGGL((swg_pair_bound_refine_kernel<4, PL, E>), grid, dim3(256), 0, stream, d_tok, d_pair_off, begin, end, cm, t, d_thr, d_bound)
+    if (S2 == 256u && bits == 8) SWG_REFINE_LAUNCH(8, uint8_t, t8);
+    else if (S2 == 256u) SWG_REFINE_LAUNCH(8, uint16_t, t16);
+    else if (S2 == 128u && bits == 8) SWG_REFINE_LAUNCH(4, uint8_t, t8);
+    else if (S2 == 128u) SWG_REFINE_LAUNCH(4, uint16_t, t16);
+    else if (bits == 8) SWG_REFINE_LAUNCH(2, uint8_t, t8);
+    else SWG_REFINE_LAUNCH(2, uint16_t, t16);
+#undef SWG_REFINE_LAUNCH
     return hipGetLastError();
 }
 

@@ -1,11 +1,13 @@
 """The headline under every cut of a pruned search's stages (profiles/prune_refine_ab.txt, section 2).
 
-    python tools/sweeps/prune_refine_ab.py [--nseq N] [--reps R]
+    python tools/sweeps/prune_refine_ab.py [--nseq N] [--reps R] [--levels]
 
 Config 4's whole database (10M sequences, one shard), its 3000-column query and scoring through the Python wrapper,
 autotune off, ctx.search(db, want_scores=False, k=100), one search in flight.  For (prune_cut, prune_refine) = (1, off),
 (0, off), (0, 64), (0, 128) and automatic: R searches with the tables resident, then two searches each behind a
-set_query of the same query, which starts a new epoch -- the search pays both tables again.  One JSON line per search."""
+set_query of the same query, which starts a new epoch -- the search pays both tables again.  One JSON line per search.
+--levels (profiles/prune_bytes_ab.txt, section 2): the candidates are (prune_table_bits, prune_refine3) = (16, off),
+(0, off), (0, 256) and automatic instead, everything else automatic."""
 import argparse
 import json
 import os
@@ -17,7 +19,10 @@ import swg_loader  # noqa: E402
 
 swg = swg_loader.load()
 
-CANDIDATES = [("prefix", 1, 1), ("pairs", 0, 1), ("pairs+64", 0, 64), ("pairs+128", 0, 128), ("auto", 0, 0)]
+CANDIDATES = [(name, {"prune_cut": cut, "prune_refine": refine})
+              for name, cut, refine in (("prefix", 1, 1), ("pairs", 0, 1), ("pairs+64", 0, 64), ("pairs+128", 0, 128), ("auto", 0, 0))]
+LEVEL_CANDIDATES = [(name, {"prune_table_bits": bits, "prune_refine3": refine3})
+                    for name, bits, refine3 in (("uint16", 16, 1), ("bytes", 0, 1), ("bytes+256", 0, 256), ("auto", 0, 0))]
 
 
 def main():
@@ -26,6 +31,7 @@ def main():
     ap.add_argument("--lq", type=int, default=3000)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--unpruned", action="store_true", help="one unpruned search first (hits to compare with, 1.2 s)")
+    ap.add_argument("--levels", action="store_true", help="the table widths and the third level instead of the cuts")
     a = ap.parse_args()
     seed = 0x5EED0004
     q = swg.synth_query(seed, a.lq)
@@ -41,9 +47,9 @@ def main():
         _, want, st = ctx.search(db, want_scores=False, k=100)
         print(json.dumps({"unpruned": True, "fill_ms": st["fill_ms"], "total_ms": st["total_ms"]}), flush=True)
         ctx.set_option("prune", 1)
-    for name, cut, refine in CANDIDATES:
-        ctx.set_option("prune_cut", cut)
-        ctx.set_option("prune_refine", refine)
+    for name, options in (LEVEL_CANDIDATES if a.levels else CANDIDATES):
+        for key, value in options.items():
+            ctx.set_option(key, value)
         for rep in range(a.reps + 2):
             fresh = rep >= a.reps
             if fresh:
@@ -52,12 +58,14 @@ def main():
             _, hits, st = ctx.search(db, want_scores=False, k=100)
             wall = (time.perf_counter() - t0) * 1e3
             info = ctx.prune_last()
-            got = ctx.debug_prune_refine_read(db)
+            got = ctx.debug_prune_refine_read(db, arrays=False)
+            tables = ctx.debug_prune_tables()
             if want is None:
                 want = hits
-            print(json.dumps({"candidate": name, "prune_cut": cut, "prune_refine": refine, "fresh_query": fresh, "rep": rep,
-                              "k_used": got["k"], "S_used": got["segments"], "S2_used": got["refine"], "builds": got["builds"],
-                              "refine_builds": got["refine_builds"], "wall_ms": round(wall, 2), "fill_ms": st["fill_ms"],
+            print(json.dumps({"candidate": name, **options, "fresh_query": fresh, "rep": rep,
+                              "k_used": got["k"], "S_used": got["segments"], "S2_used": got["refine"], "S3_used": tables["refine3"],
+                              "bits": tables["bits"], "builds": got["builds"], "refine_builds": got["refine_builds"],
+                              "refine3_builds": tables["refine3_builds"], "wall_ms": round(wall, 2), "fill_ms": st["fill_ms"],
                               "total_ms": st["total_ms"], "info": info,
                               "rows_kept_frac": 1.0 - info["pair_rows_skipped"] / max(1, info["pair_rows"]),
                               "hits_equal_first": hits == want}), flush=True)
