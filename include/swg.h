@@ -374,7 +374,7 @@ int swg_search_gapless_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *
                                   int32_t *scores_out, swg_hit *topk_out, size_t k, size_t *n_hits, swg_stats *stats);
 
 /* Every hit at or above a score: the question a pipeline asks once an E-value cut-off has been turned into a raw score
- * (the library does not do that: INTEGRATION.md).  For the context's query (index or PSSM) against a resident database,
+ * (swg_calibrate + swg_evalue_min_score do that).  For the context's query (index or PSSM) against a resident database,
  * view or shard, exactly as swg_search takes them:
  *   *n_total   the sequences of this shard or view whose exact int32 score is >= min_score;
  *   hits_out   the best min(cap, *n_total) of them in the library's total order (higher score first, ties by lower
@@ -400,7 +400,7 @@ int swg_search_gapless_above(swg_ctx *ctx, const swg_db *db, int32_t min_score, 
                              uint64_t *n_total, swg_stats *stats);
 
 /* Every hit at or above a score, for a BATCH of queries with a score each: what a pipeline with a thousand queries and an
- * E-value cut-off asks (the cut-off turns into a raw score that depends on the query's length: INTEGRATION.md).  Queries
+ * E-value cut-off asks (the cut-off turns into a raw score per query: swg_calibrate_multi + swg_evalue_min_score).  Queries
  * and offsets as swg_search_multi takes them.  By definition row i is what swg_set_query(query i) +
  * swg_search_above(ctx, db, min_scores[i], hits_out + i*cap, cap, &n_hits[i], &n_total[i], ..) gives:
  *   n_total[i]       the sequences of this shard or view whose exact int32 score is >= min_scores[i];
@@ -437,6 +437,63 @@ int swg_search_gapless_above_multi(swg_ctx *ctx, const swg_db *db, const int8_t 
 int swg_search_gapless_above_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets, size_t n_queries,
                                         const int32_t *min_scores, swg_hit *hits_out, size_t cap, size_t *n_hits, uint64_t *n_total,
                                         swg_stats *stats);
+
+/* ---- E-values and bit scores: a query calibrated on the device ---------- */
+
+/* The residue counts of a resident database, shard or view: counts[r] = how many residues of index r it holds
+ * (counts[0], the padding residue, is 0; the sum is swg_db_residues(db); the shards of a database add up).  One kernel
+ * over the resident bytes -- a view walks its own slots over its parent's bytes --, so that a caller can calibrate
+ * against the composition of what it searches (freq[r] = counts[r]).  A database that is not resident on ctx's device,
+ * or one built from 16-lane batches (swg_fill_batches16: it has no residue bytes), is SWG_ERR_STATE. */
+int swg_db_composition(swg_ctx *ctx, const swg_db *db, uint64_t counts[32]);
+
+/* What a calibration leaves per query: the Gumbel fit of the query's scores against random sequences, and the
+ * Karlin-Altschul pair (lambda, K) read off it.  The score S of the query against n_seqs random sequences of seq_len
+ * residues each follows P(S >= x) = 1 - exp(-exp(-lambda (x - mu))); with K = exp(lambda mu) / (lq seq_len) the expected
+ * number of sequences of a database of N residues in all that score S or more by chance is
+ *     E = K lq N exp(-lambda S)
+ * (no edge correction: the fit is made at a finite length and carries the effect that the correction estimates --
+ * DESIGN 8.4).  status: 0 a fit; 1 no fit, fewer than two distinct scores (lambda, K and mu are 0); 2 Newton's iteration
+ * did not converge in 100 steps (lambda and mu are where it stopped). */
+typedef struct swg_evalue_params {
+    double lambda, K, mu;
+    uint32_t lq, n_seqs, seq_len;
+    int32_t status;
+} swg_evalue_params;
+
+/* Pure helpers (host only, no context).  With status != 0 (or p NULL) they return NaN, NaN and -1.
+ *   swg_evalue            K lq db_residues exp(-lambda score)
+ *   swg_bitscore          (lambda score - ln K) / ln 2, so that E = lq db_residues 2^-bits
+ *   swg_evalue_min_score  the smallest S >= 1 with swg_evalue(p, db_residues, S) <= E, checked against its neighbour
+ *                         S - 1; -1 where there is none in int32 (E <= 0 or not a number) */
+double swg_evalue(const swg_evalue_params *p, uint64_t db_residues, int32_t score);
+double swg_bitscore(const swg_evalue_params *p, int32_t score);
+int32_t swg_evalue_min_score(const swg_evalue_params *p, uint64_t db_residues, double E);
+
+/* Calibration by simulation (what HMMER and SSEARCH do): the query is scored against "calib_seqs" random sequences of
+ * "calib_len" residues each, i.i.d. from a background composition (swg_synth_db_iid with seed "calib_seed"), the scores
+ * stay on the device, one workgroup per query histograms its row and fits a Gumbel distribution to it by maximum
+ * likelihood (swg_gumbel_fit_hist is the same fit on the host), and 32 bytes per query come back.  Works for whatever
+ * the library scores: any table and gap scores, a PSSM, the gapless score (gapless != 0: swg_search_gapless's score).
+ *   freq     NULL: the built-in Swiss-Prot-like table; else 32 weights by residue index as swg_synth_db_iid takes them
+ *            (swg_db_composition's counts, as doubles, calibrate against a database's own composition)
+ *   out      swg_calibrate: one record, for the context's query (index or PSSM; none set: SWG_ERR_STATE);
+ *            the batch calls: n_queries records, queries / pssms and offsets as swg_search_multi / swg_search_multi_pssm
+ *            take them; the context's own query is left as it was; n_queries = 0 is SWG_OK.
+ * The scores come from the planner's usual routes: one launch per chunk of up to 256 queries where swg_search_multi
+ * would take it, one query after another otherwise (several passes, gapless, a batch of one); every re-run of flagged
+ * sequences happens as in a search, so the histogram is of exact scores (those of 4095 and more count as 4095).  A query
+ * whose fit has status != 0 does not fail the call.  The random database is generated, packed and uploaded on first use
+ * and kept on the context, for the last (freq, calib_seqs, calib_len, calib_seed) asked for, until swg_destroy.
+ * Options (swg_set_option): "calib_seqs" (default 8192; 2 .. 1048576), "calib_len" (default 384; 8 .. 16384),
+ * "calib_seed" (default 1; >= 0); anything outside is SWG_ERR_ARG.  8192 samples give lambda a standard error of
+ * 0.78 lambda / sqrt(n), about 0.9 %.  Errors: NULL arguments, a malformed freq: SWG_ERR_ARG; no scoring set, searches in
+ * flight on the context: SWG_ERR_STATE.  A sharded caller calibrates on one context and sums swg_db_residues. */
+int swg_calibrate(swg_ctx *ctx, const double *freq, int gapless, swg_evalue_params *out);
+int swg_calibrate_multi(swg_ctx *ctx, const int8_t *queries, const uint64_t *q_offsets, size_t n_queries, const double *freq,
+                        int gapless, swg_evalue_params *out);
+int swg_calibrate_multi_pssm(swg_ctx *ctx, const int8_t *pssms, const uint64_t *q_offsets, size_t n_queries, const double *freq,
+                             int gapless, swg_evalue_params *out);
 
 /* Every query of a batch against ITS OWN candidate list in one pass: what a prefilter, a PSI-BLAST iteration or a list
  * of family members per query hands to the alignment step.  Query i is queries[q_offsets[i] .. q_offsets[i+1]) as

@@ -114,6 +114,26 @@ int swg_synth_db_shard(uint64_t seed, size_t n, double median, double sigma_ln, 
                        int shard_rank, int shard_count, int8_t **flat_out, uint64_t **offsets_out,
                        uint32_t **index_out, size_t *n_local, uint64_t *residues_total, size_t *n_planted);
 void swg_synth_free(void *p);
+/* The random database a calibration scores against (swg_calibrate): n sequences of exactly len residues each, i.i.d.
+ * from freq, in the order generated (offsets_out[i] = i * len).  freq[r] is the weight of residue index r (1..26 for
+ * A..Z, 31 for '*'); NULL is the built-in table of swg_synth_db.  The weights must be finite and non-negative, freq[0]
+ * (the padding residue) must be 0 and the sum positive; the library normalises.  Anything else, n or len of 0 or NULL
+ * outputs: SWG_ERR_ARG.  Residue j of sequence i depends only on (seed, i, j): a longer or larger database with the same
+ * seed begins with the same residues.  Release both buffers with swg_synth_free. */
+int swg_synth_db_iid(uint64_t seed, size_t n, uint32_t len, const double freq[32], int8_t **flat_out, uint64_t **offsets_out);
+
+/* ---- score statistics (HMMER / SSEARCH style calibration) -------------- */
+
+/* Maximum-likelihood fit of a Gumbel distribution P(S >= x) = 1 - exp(-exp(-lambda (x - mu))) to a histogram of integer
+ * scores: hist[s] = how many samples scored s, for s < n_bins.  All in double, bins in ascending order.  With n the
+ * number of samples, x0 the lowest populated bin, xbar the mean and var the (population) variance:
+ *     lambda_0 = pi / sqrt(6 var);   e_s = hist[s] exp(-lambda (s - x0)),  A = sum e_s,  B = sum s e_s,  D = sum s^2 e_s;
+ *     Newton on f = 1/lambda - xbar + B/A with f' = (B/A)^2 - D/A - 1/lambda^2; a step that would make lambda <= 0 halves
+ *     lambda instead; it stops once |step| <= 1e-12 lambda, or after 100 steps;   mu = x0 - ln(A/n) / lambda.
+ * *n_iter = the steps taken.  Returns 0 for a fit, 1 when fewer than two distinct scores are populated (no fit:
+ * *lambda = *mu = 0, *n_iter = 0), 2 when it did not converge (lambda and mu where it stopped), SWG_ERR_ARG for NULL
+ * arguments.  The device's fit of swg_calibrate is this one, bin for bin. */
+int swg_gumbel_fit_hist(const uint32_t *hist, size_t n_bins, double *lambda, double *mu, int *n_iter);
 
 /* Threads the host helpers' parallel loops use: the smallest of OpenMP's maximum (OMP_NUM_THREADS),
  * the CPUs this process may run on, and its cgroup CPU quota.  (The reference sizes its loop by

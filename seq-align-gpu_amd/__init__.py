@@ -48,6 +48,8 @@ ABI_SYMBOLS = [
     "swg_scoring_load_matrix", "swg_query_sanitize", "swg_seqs_read", "swg_seqs_free",
     "swg_seqs_to_indices", "swg_synth_db", "swg_synth_query", "swg_synth_db_similar", "swg_synth_db_family", "swg_synth_db_shard",
     "swg_synth_free", "swg_host_threads", "swg_pssm_load", "swg_pssm_free",
+    "swg_db_composition", "swg_calibrate", "swg_calibrate_multi", "swg_calibrate_multi_pssm", "swg_evalue", "swg_bitscore",
+    "swg_evalue_min_score", "swg_synth_db_iid", "swg_gumbel_fit_hist",
 ]
 
 
@@ -72,6 +74,23 @@ class Alignment(C.Structure):
 
 class AlignCounts(C.Structure):
     _fields_ = [("n_ident", C.c_uint32), ("n_match", C.c_uint32), ("n_gap_open", C.c_uint32), ("n_gap", C.c_uint32)]
+
+
+class EvalueParams(C.Structure):
+    """swg_evalue_params: the Gumbel fit of a calibrated query and the (lambda, K) read off it."""
+    _fields_ = [("lambda_", C.c_double), ("K", C.c_double), ("mu", C.c_double), ("lq", C.c_uint32), ("n_seqs", C.c_uint32),
+                ("seq_len", C.c_uint32), ("status", C.c_int32)]
+
+    def as_dict(self):
+        return {"lambda": self.lambda_, "K": self.K, "mu": self.mu, "lq": self.lq, "n_seqs": self.n_seqs, "seq_len": self.seq_len,
+                "status": self.status}
+
+    @classmethod
+    def of(cls, p):
+        """From a dict as as_dict gives it (or an EvalueParams, returned as it is)."""
+        if isinstance(p, cls):
+            return p
+        return cls(float(p["lambda"]), float(p["K"]), float(p["mu"]), int(p["lq"]), int(p["n_seqs"]), int(p["seq_len"]), int(p["status"]))
 
 
 class Stats(C.Structure):
@@ -254,6 +273,16 @@ _sig("swg_debug_prune_refine3_choice", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_table_bits", C.c_int, [_vp, _vp, C.c_size_t, C.c_int])
 _sig("swg_debug_prune_tables", C.c_int, [_vp, _vp])
 _sig("swg_debug_list_deal", C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
+_sig("swg_debug_calib_iters", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
+_sig("swg_db_composition", C.c_int, [_vp, _vp, _vp])
+_sig("swg_calibrate", C.c_int, [_vp, _vp, C.c_int, _vp])
+_sig("swg_calibrate_multi", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_int, _vp])
+_sig("swg_calibrate_multi_pssm", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_int, _vp])
+_sig("swg_evalue", C.c_double, [_vp, C.c_uint64, C.c_int32])
+_sig("swg_bitscore", C.c_double, [_vp, C.c_int32])
+_sig("swg_evalue_min_score", C.c_int32, [_vp, C.c_uint64, C.c_double])
+_sig("swg_synth_db_iid", C.c_int, [C.c_uint64, C.c_size_t, C.c_uint32, _vp, C.POINTER(_vp), C.POINTER(_vp)])
+_sig("swg_gumbel_fit_hist", C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)])
 
 
 def _check(rc, ctx=None):
@@ -411,6 +440,52 @@ def synth_db(seed, n, median=290.0, sigma_ln=0.75, min_len=20, max_len=5000, que
     offsets = _take(off, (n + 1) * 8, np.uint64)
     residues = _take(flat, int(offsets[n]), np.int8)
     return (residues, offsets) if planted is None else (residues, offsets, planted)
+
+
+def _freq(freq):
+    """A composition (32 weights by residue index) -> (array, pointer); None -> (None, None): the built-in table."""
+    if freq is None:
+        return None, None
+    f = np.ascontiguousarray(freq, dtype=np.float64)
+    if f.shape != (32,):
+        raise ValueError("freq is 32 weights by residue index, got shape %s" % (f.shape,))
+    return f, f.ctypes.data_as(_vp)
+
+
+def synth_db_iid(seed, n, length, freq=None):
+    """n sequences of exactly `length` residues, i.i.d. from freq (32 weights by residue index; None: the built-in
+    table) -> (flat int8, offsets uint64[n+1]) (swg_synth_db_iid: what a calibration scores against)."""
+    f, fp = _freq(freq)
+    flat, off = _vp(), _vp()
+    _check(lib.swg_synth_db_iid(seed, n, length, fp, C.byref(flat), C.byref(off)))
+    offsets = _take(off, (n + 1) * 8, np.uint64)
+    return _take(flat, int(offsets[n]), np.int8), offsets
+
+
+def gumbel_fit_hist(hist):
+    """Maximum-likelihood Gumbel fit of a histogram of integer scores (swg_gumbel_fit_hist) -> dict(lambda, mu, n_iter,
+    status); status 0 a fit, 1 fewer than two distinct scores, 2 not converged."""
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    lam, mu, it = C.c_double(0), C.c_double(0), C.c_int(0)
+    rc = lib.swg_gumbel_fit_hist(h.ctypes.data_as(_vp) if h.size else None, h.size, C.byref(lam), C.byref(mu), C.byref(it))
+    if rc < 0:
+        _check(rc)
+    return {"lambda": lam.value, "mu": mu.value, "n_iter": it.value, "status": rc}
+
+
+def evalue(params, db_residues, score):
+    """E = K lq db_residues exp(-lambda score) of a calibrated query (a dict from Context.calibrate*); NaN without a fit."""
+    return lib.swg_evalue(C.byref(EvalueParams.of(params)), int(db_residues), int(score))
+
+
+def bitscore(params, score):
+    """(lambda score - ln K) / ln 2; NaN without a fit."""
+    return lib.swg_bitscore(C.byref(EvalueParams.of(params)), int(score))
+
+
+def evalue_min_score(params, db_residues, E):
+    """The smallest score S >= 1 with evalue(params, db_residues, S) <= E; -1 without a fit or for E <= 0."""
+    return lib.swg_evalue_min_score(C.byref(EvalueParams.of(params)), int(db_residues), float(E))
 
 
 def synth_db_shard(seed, n, shard_rank, shard_count, median=290.0, sigma_ln=0.75, min_len=20, max_len=5000,
@@ -942,6 +1017,12 @@ class Database:
         v.handle = h
         return v
 
+    def composition(self, ctx):
+        """Residue counts of this resident database, shard or view: uint64[32] by residue index (swg_db_composition)."""
+        counts = np.zeros(32, dtype=np.uint64)
+        _check(lib.swg_db_composition(ctx.handle, self.handle, counts.ctypes.data_as(_vp)), ctx.handle)
+        return counts
+
     def save(self, path):
         _check(lib.swg_db_save(self.handle, path.encode()))
 
@@ -1016,6 +1097,47 @@ class Context:
         _check(rc, self.handle)
         a = np.frombuffer(hits, dtype=np.dtype([("score", np.int32), ("index", np.uint32)]), count=nh.value)
         return list(zip(a["score"].tolist(), a["index"].tolist())), int(nt.value), st.as_dict()
+
+    def calibrate(self, freq=None, gapless=False):
+        """The context's query scored against random sequences and fitted on the device (swg_calibrate) -> dict(lambda, K,
+        mu, lq, n_seqs, seq_len, status), what evalue / bitscore / evalue_min_score take.  freq: 32 weights by residue
+        index (None: the built-in table; Database.composition's counts: the database's own)."""
+        f, fp = _freq(freq)
+        p = EvalueParams()
+        _check(lib.swg_calibrate(self.handle, fp, int(bool(gapless)), C.byref(p)), self.handle)
+        return p.as_dict()
+
+    def calibrate_multi(self, queries, freq=None, gapless=False):
+        """calibrate for a list of index queries -> list of dicts; the context's own query is kept (swg_calibrate_multi)."""
+        nq = len(queries)
+        qoff = np.zeros(nq + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in queries])
+        qflat = np.ascontiguousarray(np.concatenate(queries) if nq else np.zeros(1), dtype=np.int8)
+        return self._calibrate_multi(lib.swg_calibrate_multi, qflat, qoff, freq, gapless)
+
+    def calibrate_multi_pssm(self, pssms, freq=None, gapless=False):
+        """calibrate_multi with position-specific queries: pssms as search_multi_pssm takes them."""
+        nq = len(pssms)
+        rows = [_pssm(p)[0] for p in pssms]
+        qoff = np.zeros(nq + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([r.shape[0] for r in rows])
+        pflat = np.ascontiguousarray(np.concatenate(rows) if nq else np.zeros((1, 32)), dtype=np.int8)
+        return self._calibrate_multi(lib.swg_calibrate_multi_pssm, pflat, qoff, freq, gapless)
+
+    def _calibrate_multi(self, fn, qflat, qoff, freq, gapless):
+        nq = len(qoff) - 1
+        f, fp = _freq(freq)
+        out = (EvalueParams * max(nq, 1))()
+        _check(fn(self.handle, qflat.ctypes.data_as(_vp), qoff.ctypes.data_as(_vp), nq, fp, int(bool(gapless)), C.cast(out, _vp)), self.handle)
+        return [out[i].as_dict() for i in range(nq)]
+
+    def debug_calib_iters(self):
+        """Newton steps of each query's fit in the last calibrate* call (tests)."""
+        n = C.c_size_t(0)
+        _check(lib.swg_debug_calib_iters(self.handle, None, 0, C.byref(n)), self.handle)
+        out = np.zeros(max(n.value, 1), dtype=np.int32)
+        _check(lib.swg_debug_calib_iters(self.handle, out.ctypes.data_as(_vp), n.value, C.byref(n)), self.handle)
+        return out[:n.value].tolist()
 
     def search_above_multi(self, db, queries, min_scores, cap=None, gapless=False):
         """search_above for a list of index queries, each with its own least score (min_scores: a list, or one int for all):

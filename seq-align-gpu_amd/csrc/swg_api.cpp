@@ -6,11 +6,13 @@
 // bookkeeping in front of it (src/alignment.c:190-233).  There is no CPU
 // fallback in this file: without a GPU swg_create fails with SWG_ERR_NODEVICE.
 #include "swg_host_internal.h"
+#include "../../include/swg_host.h"
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <climits>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -277,6 +279,7 @@ extern "C" void swg_destroy(swg_ctx *ctx)
         (void)hipHostFree(sl.h_scores);
     }
     if (ctx->b16.db) swg_db_free(ctx->b16.db);
+    if (ctx->calib.db) swg_db_free(ctx->calib.db);
     (void)hipHostFree(ctx->b16.h_stage);
     (void)hipHostFree(ctx->b16.h_meta);
     (void)hipFree(ctx->b16.d_stage);
@@ -383,6 +386,15 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
         if (value < 0 || value > 2)
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "above_batch must be 0 (auto), 1 (one launch wherever the batch is admitted) or 2 (one query after another)");
         ctx->opt_above_batch = value;
+    } else if (!strcmp(key, "calib_seqs")) {
+        if (value < 2 || value > (1l << 20)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "calib_seqs must be 2..1048576 (random sequences a calibration scores)");
+        ctx->opt_calib_seqs = value;
+    } else if (!strcmp(key, "calib_len")) {
+        if (value < 8 || value > (1l << 14)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "calib_len must be 8..16384 (residues of a calibration's random sequences)");
+        ctx->opt_calib_len = value;
+    } else if (!strcmp(key, "calib_seed")) {
+        if (value < 0) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "calib_seed must be >= 0");
+        ctx->opt_calib_seed = value;
     } else if (!strcmp(key, "q32_waves")) {
         ctx->opt_q32_waves = value;
     } else if (!strcmp(key, "wave_budget")) {
@@ -4080,6 +4092,231 @@ extern "C" int swg_search_gapless_above_multi_pssm(swg_ctx *ctx, const swg_db *d
         return search_above_multi_impl(ctx, const_cast<swg_db *>(db),
                                        MultiQueries{pssms, q_offsets, n_queries, true, "swg_search_gapless_above_multi_pssm"}, true,
                                        AboveMultiOut{min_scores, hits_out, cap, n_hits, n_total}, stats);
+    });
+}
+
+// ---------------------------------------------------------------------------
+// E-values: the residue counts of a database, and queries calibrated on the device
+// ---------------------------------------------------------------------------
+extern "C" int swg_db_composition(swg_ctx *ctx, const swg_db *db, uint64_t counts[32])
+{
+    if (!ctx || !db || !counts) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_db_composition: NULL argument");
+    memset(counts, 0, 32 * sizeof(uint64_t));
+    if (db->tokens_only)
+        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_db_composition: a database built from 16-lane batches has no residue bytes");
+    if (db->device != ctx->device || !db->d_codes)
+        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_db_composition: database is not resident on device %d", ctx->device);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    unsigned long long *d_counts = nullptr;
+    HIP_TRY(ctx, hipMalloc(&d_counts, 32 * sizeof(unsigned long long)));
+    hipError_t e = swg_launch_db_composition(db->d_codes, db->d_code_off, db->d_lens, (uint32_t)((size_t)db->n_bins * SWG_BIN), d_counts, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, 32 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = spin_sync(ctx, ctx->stream);
+    (void)hipFree(d_counts);
+    HIP_TRY(ctx, e);
+    return SWG_OK;
+}
+
+// swg_calibrate*: the queries are scored against the context's random database by the routes a search takes -- the one
+// launch per chunk of swg_search_multi where plan_batch admits the batch, one search after another otherwise --, with
+// the score rows left where the fill wrote them; swg_calib_fit_kernel histograms and fits each row, and one record per
+// query comes back.
+extern "C" int swg_debug_calib_iters(const swg_ctx *ctx, int32_t *out, size_t cap, size_t *n)
+{
+    if (!ctx || !n || (cap && !out)) return SWG_ERR_ARG;
+    *n = ctx->calib_iters.size();
+    if (*n <= cap && *n) memcpy(out, ctx->calib_iters.data(), *n * sizeof(int32_t));
+    return SWG_OK;
+}
+
+// The random database of (freq, options calib_seqs / calib_len / calib_seed): the context's, or made now in its place.
+static int calib_database(swg_ctx *ctx, const char *fn, const double *freq, swg_db **out)
+{
+    double key[32] = {};
+    if (freq) {
+        double tot = 0.0;
+        for (int r = 0; r < 32; ++r) {
+            if (!(freq[r] >= 0.0) || freq[r] > 1.7e308) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: freq[%d] is not a finite, non-negative weight", fn, r);
+            tot += freq[r];
+        }
+        if (freq[0] != 0.0) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: freq[0], the padding residue's weight, must be 0", fn);
+        if (!(tot > 0.0) || tot > 1.7e308) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: the weights of freq must add up to a positive, finite sum", fn);
+        for (int r = 0; r < 32; ++r) key[r] = freq[r] / tot;
+    } else {
+        key[0] = -1.0; // (the built-in table: no caller's freq normalises to this)
+    }
+    auto &c = ctx->calib;
+    if (c.db && c.seqs == ctx->opt_calib_seqs && c.len == ctx->opt_calib_len && c.seed == ctx->opt_calib_seed && !memcmp(c.freq, key, sizeof key)) {
+        *out = c.db;
+        return SWG_OK;
+    }
+    int8_t *flat = nullptr;
+    uint64_t *off = nullptr;
+    int rc = swg_synth_db_iid((uint64_t)ctx->opt_calib_seed, (size_t)ctx->opt_calib_seqs, (uint32_t)ctx->opt_calib_len, freq, &flat, &off);
+    if (rc != SWG_OK) return swg_set_ctx_error(ctx, rc, "%s: the random database could not be generated", fn);
+    swg_db *db = nullptr;
+    rc = swg_db_pack(flat, off, (size_t)ctx->opt_calib_seqs, 0, 1, &db);
+    swg_synth_free(flat);
+    swg_synth_free(off);
+    if (rc != SWG_OK) return swg_set_ctx_error(ctx, rc, "%s: the random database could not be packed: %s", fn, swg_global_error());
+    if ((rc = swg_db_upload(ctx, db)) != SWG_OK) {
+        swg_db_free(db);
+        return rc;
+    }
+    if (c.db) swg_db_free(c.db);
+    c.db = db;
+    memcpy(c.freq, key, sizeof key);
+    c.seqs = ctx->opt_calib_seqs, c.len = ctx->opt_calib_len, c.seed = ctx->opt_calib_seed;
+    *out = db;
+    return SWG_OK;
+}
+
+static void calib_record(const swg_ctx *ctx, const SwgCalibFit &f, size_t lq, swg_evalue_params *p)
+{
+    p->lambda = f.lambda;
+    p->mu = f.mu;
+    p->K = f.status == 1 ? 0.0 : exp(f.lambda * f.mu) / ((double)lq * (double)ctx->calib.len);
+    p->lq = (uint32_t)lq;
+    p->n_seqs = (uint32_t)ctx->calib.seqs;
+    p->seq_len = (uint32_t)ctx->calib.len;
+    p->status = f.status;
+}
+
+// One search of the context's query against the random database, begun and ended with nothing read out; its exact
+// scores -- the re-runs of flagged sequences included -- then lie in the slot's score buffer by sorted rank, and the fit
+// kernel takes them as a single row.  Never tuned (a calibration is one search) and never pruned (ctx->in_batch).
+static int calib_search_fit(swg_ctx *ctx, swg_db *cdb, bool gapless, const char *fn, SwgCalibFit *d_fit, SwgCalibFit *h_fit)
+{
+    struct Mode {
+        swg_ctx *c;
+        bool was_batch;
+        Mode(swg_ctx *c_, bool g) : c(c_), was_batch(c_->in_batch) { c->gapless = g, c->in_batch = true; }
+        ~Mode() { c->gapless = false, c->in_batch = was_batch; }
+    } mode(ctx, gapless);
+    int ticket = -1;
+    int rc = search_begin_ticket(ctx, cdb, false, 0, false, &ticket);
+    if (rc != SWG_OK) return rc;
+    SwgSlot *S = &ctx->slots[ticket];
+    // (search_begin has queued the fill and every re-run on the context's stream, or on streams joined to it: the fit
+    // goes in behind them now, and the search's own end costs no idle gap in front of it)
+    hipError_t e = swg_launch_calib_fit(S->bufs.d_scores, 0, cdb->d_order, (uint32_t)((size_t)cdb->n_bins * SWG_BIN), 1, d_fit, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_fit, d_fit, sizeof *h_fit, hipMemcpyDeviceToHost, ctx->stream);
+    rc = ctx_guarded(ctx, fn, [&]() -> int { return search_end(ctx, S, nullptr, nullptr, nullptr, nullptr); });
+    S->busy = false;
+    if (rc != SWG_OK) return rc;
+    HIP_TRY(ctx, e);
+    HIP_TRY(ctx, spin_sync(ctx, ctx->stream));
+    return SWG_OK;
+}
+
+namespace {
+struct CalibFits { // the fit records of a chunk on the device
+    SwgCalibFit *d = nullptr;
+    ~CalibFits() { (void)hipFree(d); }
+};
+} // namespace
+
+static int calib_state_ok(swg_ctx *ctx, const char *fn)
+{
+    if (!ctx->have_scoring) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: no scoring set", fn);
+    for (const SwgSlot &sl : ctx->slots)
+        if (sl.busy) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: searches are in flight on this context", fn);
+    return SWG_OK;
+}
+
+static int calibrate_multi_impl(swg_ctx *ctx, const MultiQueries &mq, const double *freq, bool gapless, swg_evalue_params *out)
+{
+    const char *fn = mq.fn;
+    if (!ctx || (mq.n && (!mq.src || !mq.off || !out))) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: NULL argument", fn);
+    int rc = calib_state_ok(ctx, fn);
+    if (rc != SWG_OK) return rc;
+    ctx->calib_iters.clear();
+    if (mq.n == 0) return SWG_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    swg_db *cdb = nullptr;
+    if ((rc = calib_database(ctx, fn, freq, &cdb)) != SWG_OK) return rc;
+    swg_stats st;
+    memset(&st, 0, sizeof st);
+    if ((rc = validate_batch(ctx, cdb, mq, nullptr, 0, &st)) != SWG_OK) return rc;
+    ctx->prune_last = swg_prune_info();
+    ctx->calib_iters.assign(mq.n, 0);
+    SwgBatchPlan P;
+    if (!gapless && (rc = plan_batch(ctx, cdb, mq, false, 0, &P)) != SWG_OK) return rc;
+    CalibFits fits;
+    const size_t rows = P.one_launch ? P.first_chunk : 1;
+    HIP_TRY(ctx, hipMalloc(&fits.d, rows * sizeof(SwgCalibFit)));
+    std::vector<SwgCalibFit> h(rows);
+    if (!P.one_launch) {
+        const KeptQuery keep(ctx);
+        for (size_t i = 0; i < mq.n && rc == SWG_OK; ++i) {
+            rc = mq.pssm ? swg_set_query_pssm(ctx, mq.at(i), mq.len(i)) : swg_set_query(ctx, mq.at(i), mq.len(i));
+            if (rc == SWG_OK) rc = calib_search_fit(ctx, cdb, gapless, fn, fits.d, h.data());
+            if (rc != SWG_OK) break;
+            calib_record(ctx, h[0], mq.len(i), &out[i]);
+            ctx->calib_iters[i] = h[0].n_iter;
+        }
+        return keep.restore(ctx, rc);
+    }
+    MultiBufs B;
+    ctx->cur = &ctx->slots[0];
+    rc = batch_allocate(ctx, P, &B);
+    for (size_t q0 = 0; q0 < mq.n && rc == SWG_OK; q0 += P.chunk_queries) {
+        const size_t Qb = std::min(P.chunk_queries, mq.n - q0);
+        const size_t Qrows = P.grid_rows(Qb);
+        rc = multi_rows_ok(ctx, B, P, Qb, Qrows);
+        if (rc == SWG_OK) rc = batch_stage_chunk(ctx, P, mq, q0, Qb, &B);
+        if (rc == SWG_OK) rc = batch_launch_chunk(ctx, cdb, P, B, Qb, Qrows);
+        if (rc != SWG_OK) break;
+        if (Qb > rows || Qb > B.rows_scores)
+            return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: the fit indexes %zu rows, its buffers hold %zu", fn, Qb, std::min(rows, B.rows_scores));
+        // score row r of the chunk belongs to its query order[r] (the row of an odd pair's absent partner is not read)
+        HIP_TRY(ctx, swg_launch_calib_fit(B.d_scores, P.n_slots, cdb->d_order, (uint32_t)P.n_slots, (uint32_t)Qb, fits.d, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h.data(), fits.d, Qb * sizeof(SwgCalibFit), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, spin_sync(ctx, ctx->stream));
+        for (size_t r = 0; r < Qb; ++r) {
+            const size_t i = q0 + B.order[r];
+            calib_record(ctx, h[r], mq.len(i), &out[i]);
+            ctx->calib_iters[i] = h[r].n_iter;
+        }
+    }
+    return rc;
+}
+
+extern "C" int swg_calibrate(swg_ctx *ctx, const double *freq, int gapless, swg_evalue_params *out)
+{
+    const char *fn = "swg_calibrate";
+    if (!ctx || !out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: NULL argument", fn);
+    return ctx_guarded(ctx, fn, [&]() -> int {
+        int rc = calib_state_ok(ctx, fn);
+        if (rc != SWG_OK) return rc;
+        if (ctx->query_len() == 0) return swg_set_ctx_error(ctx, SWG_ERR_STATE, "%s: no query set", fn);
+        ctx->calib_iters.clear();
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        swg_db *cdb = nullptr;
+        if ((rc = calib_database(ctx, fn, freq, &cdb)) != SWG_OK) return rc;
+        CalibFits fits;
+        HIP_TRY(ctx, hipMalloc(&fits.d, sizeof(SwgCalibFit)));
+        SwgCalibFit h;
+        if ((rc = calib_search_fit(ctx, cdb, gapless != 0, fn, fits.d, &h)) != SWG_OK) return rc;
+        calib_record(ctx, h, ctx->query_len(), out);
+        ctx->calib_iters.assign(1, h.n_iter);
+        return SWG_OK;
+    });
+}
+
+extern "C" int swg_calibrate_multi(swg_ctx *ctx, const int8_t *queries, const uint64_t *q_offsets, size_t n_queries, const double *freq,
+                                   int gapless, swg_evalue_params *out)
+{
+    return ctx_guarded(ctx, "swg_calibrate_multi", [&]() -> int {
+        return calibrate_multi_impl(ctx, MultiQueries{queries, q_offsets, n_queries, false, "swg_calibrate_multi"}, freq, gapless != 0, out);
+    });
+}
+
+extern "C" int swg_calibrate_multi_pssm(swg_ctx *ctx, const int8_t *pssms, const uint64_t *q_offsets, size_t n_queries, const double *freq,
+                                        int gapless, swg_evalue_params *out)
+{
+    return ctx_guarded(ctx, "swg_calibrate_multi_pssm", [&]() -> int {
+        return calibrate_multi_impl(ctx, MultiQueries{pssms, q_offsets, n_queries, true, "swg_calibrate_multi_pssm"}, freq, gapless != 0, out);
     });
 }
 

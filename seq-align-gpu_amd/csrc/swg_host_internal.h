@@ -595,6 +595,15 @@ struct swg_ctx {
     uint32_t *d_scratch = nullptr;
     size_t d_scratch_cap = 0; // dwords
     SwgBatch16Cache b16;
+    // swg_calibrate*: options "calib_seqs", "calib_len", "calib_seed", and the random database of the last (normalised
+    // freq, seqs, len, seed) asked for -- generated, packed and uploaded on first use, released by swg_destroy
+    long opt_calib_seqs = 8192, opt_calib_len = 384, opt_calib_seed = 1;
+    struct {
+        swg_db *db = nullptr;
+        double freq[32] = {};
+        long seqs = 0, len = 0, seed = 0;
+    } calib;
+    std::vector<int32_t> calib_iters; // Newton steps of each query's fit in the last swg_calibrate* call (tests)
     SwgSlot slots[SWG_MAX_INFLIGHT];
     SwgSlot *cur = nullptr; // slot whose events the launch helpers record into
     int next_slot = 0;
@@ -711,6 +720,9 @@ uint32_t swg_split_rows(size_t lq, uint64_t qbound);
 void swg_db_split_at(swg_db *db, uint32_t rows);
 extern "C" int swg_debug_pair_tokens(swg_ctx *ctx, swg_db *db, int from_host, uint32_t *out, size_t cap_dwords,
                                      size_t *n_dwords);
+
+// test hook: the Newton steps of each query's fit in the context's last swg_calibrate* call (copied when they fit cap)
+extern "C" int swg_debug_calib_iters(const swg_ctx *ctx, int32_t *out, size_t cap, size_t *n);
 
 // swg_trace.hip: the pairs of one alignment call.  Query i is src[q_offsets[i] .. q_offsets[i+1]) in positions (index
 // bytes, or PSSM rows of 32 bytes), its hits are hits[i*k .. i*k + n_hits[i]), and out / ops take the same layout.

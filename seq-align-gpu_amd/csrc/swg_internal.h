@@ -400,3 +400,21 @@ hipError_t swg_launch_prune_list(const uint32_t *d_bound, const uint32_t *d_pair
 hipError_t swg_launch_topk_multi(const int32_t *d_scores, uint64_t score_stride, const uint32_t *d_order, uint32_t n_slots,
                                  uint32_t n_queries, uint32_t k, uint32_t *d_hist, uint32_t *d_meta, uint64_t *d_cand, uint32_t cap,
                                  hipStream_t stream);
+
+// ---- calibration (swg_calib.hip) ----------------------------------------------------------------------------------
+// Residue counts of the n_slots sequences of a resident database or view (slot s: lens[s] residue bytes, index << 3,
+// from dword code_off[s] of codes): d_counts[r] (32 words of 64 bits, zeroed here) = the residues of index r; bytes past
+// a sequence's end are not counted.
+hipError_t swg_launch_db_composition(const uint32_t *d_codes, const uint64_t *d_code_off, const uint32_t *d_lens, uint32_t n_slots,
+                                     unsigned long long *d_counts, hipStream_t stream);
+// What swg_calib_fit_kernel leaves per score row: the Gumbel fit of swg_gumbel_fit_hist (include/swg_host.h) over the
+// row's histogram; n = the scores counted.
+#define SWG_CALIB_BINS 4096u // scores of SWG_CALIB_BINS - 1 and more count as that
+struct SwgCalibFit {
+    double lambda, mu;
+    int32_t n_iter, status;
+    uint32_t n, reserved;
+};
+// Score row y (row_stride scores apart; slots with d_order == ~0u are skipped) of n_rows <= 65535 rows -> d_out[y].
+hipError_t swg_launch_calib_fit(const int32_t *d_scores, uint64_t row_stride, const uint32_t *d_order, uint32_t n_slots, uint32_t n_rows,
+                                SwgCalibFit *d_out, hipStream_t stream);

@@ -32,7 +32,12 @@
  *     lists are merged by swg_hit_key;
  *     --allqueries --minscorelist F --topk K does the same for every record at its own least score, line i of F being
  *     record i's: the count of the entries at or above it, then the best min(K, count) of them (the records after the
- *     first go through swg_search_above_multi / _multi_pssm, with --gapless swg_search_gapless_above_multi / _pssm).
+ *     first go through swg_search_above_multi / _multi_pssm, with --gapless swg_search_gapless_above_multi / _pssm);
+ *     --evalue E derives those least scores itself: the query -- with --allqueries every record, in one
+ *     swg_calibrate_multi / _multi_pssm -- is calibrated on the device against random sequences (swg_calibrate), E becomes a
+ *     raw score per query over the residues of what is searched (swg_evalue_min_score), and --minscore's / --minscorelist's
+ *     searches run at those; --compfromdb draws the random sequences from the searched entries' own composition
+ *     (swg_db_composition); --tabular then prints BLAST's twelve columns, evalue and bitscore included.
  * There is no CPU backend: without a GPU the tool fails with a message.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -40,6 +45,7 @@
 #include "../../include/swg_host.h"
 
 #include <limits.h>
+#include <math.h>
 #include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -105,6 +111,14 @@ static void usage(const char *argv0, const char *err)
             "                         record reports how many entries score at least that, then the best K of them as --minscore\n"
             "                         does; works with --pssmlist, --gapless, --seqidlist, --align, --bounds and --tabular; not with\n"
             "                         --minscore, --candidates, --prefilter or --gpus\n"
+            "    --evalue <E>         report every entry whose E-value is at most E (above 0): the query -- with --allqueries --topk K every\n"
+            "                         record -- is calibrated on the GPU against random sequences, E becomes a least score over the\n"
+            "                         residues of the entries searched (--seqidlist: the listed ones; --gpus N: all shards), and the\n"
+            "                         report is --minscore's / --minscorelist's at that score; --tabular then prints the columns\n"
+            "                         `..., send, evalue, bitscore, score`; works with --topk, --pssm, --pssmlist, --gapless, --align,\n"
+            "                         --bounds; not with --minscore, --minscorelist, --candidates or --prefilter\n"
+            "    --compfromdb         with --evalue: the random sequences follow the composition of the entries searched instead of\n"
+            "                         the built-in amino-acid frequencies\n"
             "    --prefilter <N>      with --topk K: per query (every record with --allqueries) the N best entries by gapless\n"
             "                         score are searched with gaps and the K best of those reported (--align: aligned);\n"
             "                         no Entry lines are printed; not with --gpus, --candidates or --gapless\n",
@@ -200,6 +214,38 @@ static void die_illegal(char c)
     exit(1);
 }
 
+/* --evalue: the context's query (n_rec == 1 without qx / pssms), or every record of the query file in one batch call, is
+ * calibrated on ctx -- against the composition `counts` where --compfromdb gave one -- and E becomes each record's least
+ * score over `residues` (least[i]).  A record without a fit is refused by name.  Returns 0 after an error message. */
+static int evalue_scores(swg_ctx *ctx, const swg_seqs *q, size_t n_rec, const int8_t *qx, const int8_t *pssms, int gapless,
+                         const uint64_t *counts, uint64_t residues, double E, swg_evalue_params *ev, int32_t *least)
+{
+    double freq[32];
+    for (int r = 0; r < 32; r++) freq[r] = counts ? (double)counts[r] : 0.0;
+    const double *fq = counts ? freq : NULL;
+    const int rc = pssms ? swg_calibrate_multi_pssm(ctx, pssms, q->seq_off, n_rec, fq, gapless, ev)
+                   : qx  ? swg_calibrate_multi(ctx, qx, q->seq_off, n_rec, fq, gapless, ev)
+                         : swg_calibrate(ctx, fq, gapless, ev);
+    if (rc != SWG_OK) {
+        fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
+        return 0;
+    }
+    for (size_t i = 0; i < n_rec; i++) {
+        if (ev[i].status != 0) {
+            fprintf(stderr, "Error: query #%lu (%s) has no E-value statistics: %s\n", (unsigned long)i, q->names + q->name_off[i],
+                    ev[i].status == 1 ? "its scores against the random sequences are all the same"
+                                      : "the fit of its scores against the random sequences did not converge");
+            return 0;
+        }
+        least[i] = swg_evalue_min_score(&ev[i], residues, E);
+        if (least[i] < 1) {
+            fprintf(stderr, "Error: query #%lu (%s): no score has an E-value of %g or less\n", (unsigned long)i, q->names + q->name_off[i], E);
+            return 0;
+        }
+    }
+    return 1;
+}
+
 int main(int argc, char **argv)
 {
     swg_scoring sc;
@@ -208,7 +254,8 @@ int main(int argc, char **argv)
     const char *mslist_path = NULL;
     int print_seq = 0, print_fasta = 0, have_matrix = 0, packed = 0, allq = 0;
     long topk = 0, gpu = 0, gpus = 0, prefilter = 0, minscore = 0, v;
-    int align = 0, gapless = 0, bounds = 0, tabular = 0;
+    int align = 0, gapless = 0, bounds = 0, tabular = 0, have_evalue = 0, compfromdb = 0;
+    double evalue = 0.0;
     if (argc == 1) usage(argv[0], NULL);
     for (int i = 1; i < argc; i++)
         if (!strcasecmp(argv[i], "--help") || !strcasecmp(argv[i], "-help") || !strcasecmp(argv[i], "-h"))
@@ -233,6 +280,8 @@ int main(int argc, char **argv)
             bounds = 1;
         } else if (!strcasecmp(a, "--tabular")) {
             tabular = 1;
+        } else if (!strcasecmp(a, "--compfromdb")) {
+            compfromdb = 1;
         } else if (!strcasecmp(a, "--timing")) {
             timing = 1;
         } else if (!strcasecmp(a, "--allqueries")) {
@@ -268,6 +317,13 @@ int main(int argc, char **argv)
             i++;
         } else if (!strcasecmp(a, "--minscorelist")) {
             mslist_path = argv[++i];
+        } else if (!strcasecmp(a, "--evalue")) {
+            char *end = NULL;
+            evalue = strtod(argv[i + 1], &end);
+            if (end == argv[i + 1] || *end != '\0' || !(evalue > 0.0) || isinf(evalue))
+                usage(argv[0], "Invalid --evalue argument: the largest E-value to report, a number above 0");
+            have_evalue = 1;
+            i++;
         } else if (!strcasecmp(a, "--prefilter")) {
             if (!parse_int(argv[i + 1], 1, 1 << 20, &prefilter)) usage(argv[0], "Invalid --prefilter argument: the number of candidates per query, 1 or more");
             i++;
@@ -313,6 +369,14 @@ int main(int argc, char **argv)
     if (pssmlist_path && pssm_path) usage(argv[0], "--pssmlist and --pssm do not combine (the list names the first record's PSSM too)");
     if (pssmlist_path && gpus > 0) usage(argv[0], "--pssmlist works with one GPU (--gpu)");
     if ((packed || savedb || allq) && gpus > 0) usage(argv[0], "--packed/--savedb/--allqueries work with one GPU (--gpu)");
+    if (have_evalue && (minscore || mslist_path)) usage(argv[0], "--evalue derives the least score itself: it does not combine with --minscore or --minscorelist");
+    if (have_evalue && (cand_path || prefilter)) usage(argv[0], "--evalue does not combine with --candidates or --prefilter");
+    if (have_evalue && allq && topk == 0) usage(argv[0], "--allqueries --evalue reports up to --topk K hits per record: give --topk K");
+    if (compfromdb && !have_evalue) usage(argv[0], "--compfromdb chooses the background of --evalue's calibration: give --evalue E");
+    /* --evalue: the searches of --minscore (one query) or of --minscorelist (every record) at scores the calibration gives;
+     * until it has run, 1 stands for them */
+    const int ev_batch = have_evalue && allq;
+    if (have_evalue && !allq) minscore = 1;
     if (minscore && mslist_path) usage(argv[0], "--minscorelist does not combine with --minscore, --candidates, --prefilter or --gpus");
     if (minscore && (allq || cand_path || prefilter)) usage(argv[0], "--minscore reports one query's hits: it does not combine with --allqueries, --candidates or --prefilter");
     if (mslist_path && !allq) usage(argv[0], "--minscorelist gives the least score of each of --allqueries' records: give --allqueries");
@@ -460,7 +524,16 @@ int main(int argc, char **argv)
             usage(argv[0], msg);
         }
         minscore = mslist[0];
+    } else if (ev_batch) {
+        mslist = (int32_t *)calloc(q.n, sizeof *mslist);
+        if (!mslist) return leave(EXIT_FAILURE);
+        minscore = 1;
     }
+    /* --evalue: every record's fit, the residues E counts over, and with --allqueries every record as table indices */
+    swg_evalue_params *ev = NULL;
+    uint64_t ev_residues = 0;
+    int8_t *ev_qx = NULL;
+    if (have_evalue && !(ev = (swg_evalue_params *)calloc(q.n, sizeof *ev))) return leave(EXIT_FAILURE);
     /* --candidates: record r's entries are cands[c_off[r] .. c_off[r + 1]) in the file's order; lsc is parallel to cands
      * (swg_search_lists' scores_out), and `listed` marks the current record's entries for the printing */
     uint32_t *cands = NULL;
@@ -686,9 +759,7 @@ int main(int argc, char **argv)
         size_t n_keys = 0;
         for (size_t g = 0; g < sh_n; g++) {
             swg_config cfg;
-            swg_stats st;
             memset(&cfg, 0, sizeof cfg);
-            memset(&st, 0, sizeof st);
             cfg.device = (int)g;
             if (swg_create(&cfg, &sh_ctx[g]) != SWG_OK) {
                 fprintf(stderr, "Error: %s\n", swg_global_error());
@@ -701,11 +772,36 @@ int main(int argc, char **argv)
             if (rc == SWG_OK) rc = swg_db_upload(c, sh_db[g]);
             sh_sdb[g] = sh_db[g];
             if (rc == SWG_OK && ids) rc = swg_db_view(c, sh_db[g], ids, n_ids, &sh_sdb[g]); /* (the entries of other shards are ignored) */
+            if (rc != SWG_OK) {
+                fprintf(stderr, "Error: %s\n", swg_last_error(c));
+                return leave(EXIT_FAILURE);
+            }
+        }
+        if (have_evalue) { /* calibrated once, on the first GPU; E counts over the residues of all shards */
+            uint64_t counts[32] = {0}, part[32];
+            for (size_t g = 0; g < sh_n; g++) {
+                ev_residues += swg_db_residues(sh_sdb[g]);
+                if (!compfromdb) continue;
+                if (swg_db_composition(sh_ctx[g], sh_sdb[g], part) != SWG_OK) {
+                    fprintf(stderr, "Error: %s\n", swg_last_error(sh_ctx[g]));
+                    return leave(EXIT_FAILURE);
+                }
+                for (int r = 0; r < 32; r++) counts[r] += part[r];
+            }
+            int32_t one = 0;
+            if (!evalue_scores(sh_ctx[0], &q, 1, NULL, NULL, gapless, compfromdb ? counts : NULL, ev_residues, evalue, ev, &one))
+                return leave(EXIT_FAILURE);
+            minscore = one;
+            phase("calibrate (E-value to least score)");
+        }
+        for (size_t g = 0; g < sh_n; g++) {
+            swg_ctx *c = sh_ctx[g];
+            swg_stats st;
+            memset(&st, 0, sizeof st);
             size_t got = 0;
             uint64_t above = 0;
-            if (rc == SWG_OK)
-                rc = gapless ? swg_search_gapless_above(c, sh_sdb[g], (int32_t)minscore, hits, hit_cap, &got, &above, &st)
-                             : swg_search_above(c, sh_sdb[g], (int32_t)minscore, hits, hit_cap, &got, &above, &st);
+            rc = gapless ? swg_search_gapless_above(c, sh_sdb[g], (int32_t)minscore, hits, hit_cap, &got, &above, &st)
+                         : swg_search_above(c, sh_sdb[g], (int32_t)minscore, hits, hit_cap, &got, &above, &st);
             if (rc != SWG_OK) {
                 fprintf(stderr, "Error: %s\n", swg_last_error(c));
                 return leave(EXIT_FAILURE);
@@ -803,6 +899,31 @@ int main(int argc, char **argv)
             rc = swg_db_view(ctx, pdb, ids, n_ids, &sdb);
             phase("select the listed entries");
         }
+        if (rc == SWG_OK && have_evalue) { /* the least score of the query, or of every record, from its calibration */
+            uint64_t counts[32];
+            if (compfromdb) rc = swg_db_composition(ctx, sdb, counts);
+            if (rc == SWG_OK && allq && !plist) { /* every record as table indices, record i from q.seq_off[i] on */
+                ev_qx = (int8_t *)malloc((size_t)q.seq_off[q.n] + 1);
+                if (!ev_qx) return leave(EXIT_FAILURE);
+                for (size_t r = 0; r < q.n; r++) {
+                    for (uint64_t c = q.seq_off[r]; c < q.seq_off[r + 1]; c++) {
+                        const int ix = swg_letter_index((unsigned char)q.seq[c]);
+                        if (ix < 0) die_illegal(q.seq[c]);
+                        ev_qx[c] = (int8_t)ix;
+                    }
+                    swg_query_sanitize(&sc, ev_qx + q.seq_off[r], (size_t)(q.seq_off[r + 1] - q.seq_off[r]));
+                }
+            }
+            if (rc == SWG_OK) {
+                int32_t one = 0;
+                ev_residues = swg_db_residues(sdb);
+                if (!evalue_scores(ctx, &q, allq ? q.n : 1, ev_qx, allq ? plist : NULL, gapless, compfromdb ? counts : NULL, ev_residues, evalue, ev,
+                                   allq ? mslist : &one))
+                    return leave(EXIT_FAILURE);
+                minscore = allq ? mslist[0] : one;
+            }
+            phase("calibrate (E-value to least score)");
+        }
         if (rc == SWG_OK && prefilter) { /* the first record's candidates: its gapless top-N */
             memset(listed, 0, db.n ? db.n : 1); /* (--seqidlist's marks: no Entry lines here, the marks count the candidates) */
             pf_hits = (swg_hit *)calloc(pf_n ? pf_n : 1, sizeof *pf_hits);
@@ -889,6 +1010,9 @@ next_query:
     /* reference src/alignment_cmdline.c:529-530; the time is the device time of the fill */
     printf("Total Time: %f\n", total_ms * 1e-3);
     printf("Total Entries: %lu\n", (unsigned long)(listed ? n_listed : db.n));
+    if (have_evalue)
+        printf("E-value %g: lambda %.4f, K %.4f, least score %ld over %llu residues\n", evalue, ev[qi].lambda, ev[qi].K, minscore,
+               (unsigned long long)ev_residues);
     if (minscore) printf("Entries at or above %ld: %llu\n", minscore, (unsigned long long)n_above);
     if (topk > 0 || minscore) {
         printf("Top %lu hits (score, entry, name):\n", (unsigned long)n_hits);
@@ -991,10 +1115,17 @@ next_query:
         for (size_t i = 0; i < n_hits && bounds; i++)
             printf("Bounds #%lu: entry %u score %d query %u..%u entry %u..%u length %u\n", (unsigned long)i, bd_q[i].index,
                    bd_q[i].score, bd_q[i].q_begin, bd_q[i].q_end, bd_q[i].d_begin, bd_q[i].d_end, bd_q[i].n_ops);
-        if (tabular) printf("# Fields: query, entry, pident, length, mismatch, gapopen, qstart, qend, sstart, send, score\n");
+        if (tabular && have_evalue) printf("# Fields: query, entry, pident, length, mismatch, gapopen, qstart, qend, sstart, send, evalue, bitscore, score\n");
+        else if (tabular) printf("# Fields: query, entry, pident, length, mismatch, gapopen, qstart, qend, sstart, send, score\n");
         for (size_t i = 0; i < n_hits && tabular; i++) {
             const swg_alignment *a = &bd_q[i];
             if (a->score <= 0) continue; /* no alignment: no line */
+            if (have_evalue) { /* BLAST's twelve columns, then the raw score */
+                printf("%s\t%s\t%.2f\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%.3g\t%.1f\t%d\n", qname, packed ? "" : db.names + db.name_off[a->index],
+                       100.0 * ct_q[i].n_ident / a->n_ops, a->n_ops, ct_q[i].n_match - ct_q[i].n_ident, ct_q[i].n_gap_open, a->q_begin + 1,
+                       a->q_end, a->d_begin + 1, a->d_end, swg_evalue(&ev[qi], ev_residues, a->score), swg_bitscore(&ev[qi], a->score), a->score);
+                continue;
+            }
             printf("%s\t%s\t%.2f\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%d\n", qname, packed ? "" : db.names + db.name_off[a->index],
                    100.0 * ct_q[i].n_ident / a->n_ops, a->n_ops, ct_q[i].n_match - ct_q[i].n_ident, ct_q[i].n_gap_open,
                    a->q_begin + 1, a->q_end, a->d_begin + 1, a->d_end, a->score);
@@ -1219,6 +1350,8 @@ next_query:
     free(c_off);
     free(lsc);
     free(mslist);
+    free(ev);
+    free(ev_qx);
     free(pf_hits);
     free(pf_nhits);
     free(scores);

@@ -265,4 +265,58 @@ int swg_synth_db_shard(uint64_t seed, size_t n, double median, double sigma_ln, 
     return rc;
 }
 
+/* i.i.d. sequences of one length from a caller's composition (the database a calibration scores against).  Draw j of
+ * sequence i is the j-th output of the splitmix64 stream seeded with mix(seed ^ 0x11D, i) -- splitmix64 is a counter
+ * hashed, so that is a function of (seed, i, j) alone --, its top 53 bits a uniform in [0, 1) looked up in the
+ * cumulative table; the last residue with a positive weight takes whatever rounding leaves below 1. */
+int swg_synth_db_iid(uint64_t seed, size_t n, uint32_t len, const double freq[32], int8_t **flat_out, uint64_t **offsets_out)
+{
+    if (!flat_out || !offsets_out || n == 0 || len == 0) return SWG_ERR_ARG;
+    *flat_out = NULL;
+    *offsets_out = NULL;
+    double w[32] = {0}, tot = 0.0;
+    if (freq) {
+        for (int r = 0; r < 32; r++) {
+            if (!(freq[r] >= 0.0) || isinf(freq[r])) return SWG_ERR_ARG; /* (a NaN fails the comparison) */
+            w[r] = freq[r];
+        }
+        if (w[0] != 0.0) return SWG_ERR_ARG;
+    } else {
+        for (int i = 0; i < 20; i++) w[swg_letter_index(AA[i])] = FREQ[i];
+    }
+    for (int r = 0; r < 32; r++) tot += w[r];
+    if (!(tot > 0.0) || isinf(tot)) return SWG_ERR_ARG;
+    double cum[32], acc = 0.0;
+    int last = 0;
+    for (int r = 0; r < 32; r++) {
+        acc += w[r] / tot;
+        cum[r] = acc;
+        if (w[r] > 0.0) last = r;
+    }
+    for (int r = last; r < 32; r++) cum[r] = 2.0;
+    if ((uint64_t)n > UINT64_MAX / len) return SWG_ERR_ARG;
+    int8_t *flat = (int8_t *)malloc((size_t)n * len);
+    uint64_t *off = (uint64_t *)malloc((n + 1) * sizeof(uint64_t));
+    if (!flat || !off) {
+        free(flat);
+        free(off);
+        return SWG_ERR_NOMEM;
+    }
+    for (size_t i = 0; i <= n; i++) off[i] = (uint64_t)i * len;
+#pragma omp parallel for schedule(static) num_threads(swg_host_threads())
+    for (long long i = 0; i < (long long)n; i++) {
+        uint64_t st = mix(seed ^ 0x11Du, (uint64_t)i);
+        int8_t *dst = flat + (size_t)i * len;
+        for (uint32_t j = 0; j < len; j++) {
+            const double u = (double)(splitmix64(&st) >> 11) / 9007199254740992.0;
+            int r = 1;
+            while (!(w[r] > 0.0 && u < cum[r])) r++; /* (ends at `last` at the latest: cum is 2 there) */
+            dst[j] = (int8_t)r;
+        }
+    }
+    *flat_out = flat;
+    *offsets_out = off;
+    return SWG_OK;
+}
+
 void swg_synth_free(void *p) { free(p); }
