@@ -634,6 +634,64 @@ int swg_align_stats_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pss
                                size_t n_queries, const swg_hit *hits, size_t k, const size_t *n_hits,
                                swg_alignment *out, swg_align_counts *counts);
 
+/* ---- a PSSM from a query's hits (the step between two iterations of a profile search) ------------------- */
+
+/* PSI-BLAST's construction (Altschul et al. 1997) with one simplification: the alignment block of every column is the
+ * whole query, so a query has ONE set of sequence weights and ONE diversity figure.
+ *   background  P = freq normalised (32 weights by residue index, validated as swg_synth_db_iid validates them; NULL: the
+ *               built-in table of swg_synth_db), A = {a in 1..31 : P_a > 0}; lambda = swg_matrix_lambda(sub, freq).
+ *   rows        row 0 is the query's own residues; row r >= 1 is hit r under the path swg_align_hits* spells for it (the
+ *               same kernel, the same tie rules): an 'M' step puts the database residue into its query column, a 'D'
+ *               step a gap, 'I' steps are dropped, columns outside [q_begin, q_end) are empty.  A residue outside A and
+ *               a gap count as empty in everything below; a hit of score 0 contributes nothing; a hit listed twice
+ *               counts twice.
+ *   counts      n[p][a] rows showing a in column p; k_p distinct residues of column p; m_p = sum_a n[p][a]; Nbar = the
+ *               mean of k_p over the columns with m_p >= 1.
+ *   weights     w_r = sum over the columns p where row r shows a residue x of 1 / (k_p n[p][x])   (Henikoff).
+ *   frequencies f[p][a] = (sum of w_r over the rows showing a in p) / (sum of w_r over the rows showing anything in p).
+ *   pseudocounts alpha_p = min(Nbar, m_p) - 1, beta = pseudocount (finite, > 0),
+ *               g[p][a] = P_a sum_{b in A} f[p][b] exp(lambda sub[b][a]),   Q = (alpha_p f + beta g) / (alpha_p + beta).
+ *   scores      v[p][a] = ln(Q[p][a] / P_a) / lambda for a in A; pssm[p*32 + a] = v rounded half away from zero and
+ *               clamped to -128..127; for a >= 1 outside A sub[query residue p][a], as swg_pssm_load fills the columns
+ *               a file does not name; column 0 is 0; a column with m_p = 0 takes its whole row from sub[query residue p].
+ * With no hits the PSSM is sub[query residue p][a] in every entry.  Every floating sum has a fixed order and nothing is
+ * added atomically in floating point: two calls give the same bytes.  The host twin is swg_pssm_from_paths
+ * (include/swg_host.h). */
+#define SWG_PSSM_PSEUDOCOUNT_DEFAULT 10.0 /* PSI-BLAST's constant */
+typedef struct swg_pssm_info {
+    double lambda;       /* of (sub, freq) */
+    double n_distinct;   /* Nbar; 0 when no column holds a residue of A */
+    uint32_t n_rows;     /* rows used: the query and every hit of score > 0 */
+    uint32_t n_observed; /* columns in which some hit shows a residue of A */
+    uint32_t n_clamped;  /* entries whose rounded score lay outside -128..127 */
+    uint32_t reserved;
+} swg_pssm_info;
+
+/* swg_pssm_build: the PSSM of the context's query from hits[n_hits] (only .index is read, as swg_align_hits reads them).
+ * query_residues is NULL for an index query; for a PSSM query it is required -- the query's residues, as many as the
+ * PSSM has rows: the hits are then aligned under the PSSM and row 0 is query_residues.  pssm_out [lq*32] in
+ * swg_set_query_pssm's layout; values_out NULL or double[lq*32], the unrounded v (0 where there is none); info NULL or
+ * one record.  The batch calls take the hit layout of swg_align_hits_multi, so swg_search_above_multi's hits_out with its
+ * n_total clipped to cap goes in unchanged; PSSM i is written at pssms_out + q_offsets[i]*32 (values_out alike), ready
+ * for swg_search_multi_pssm; info NULL or n_queries records.  swg_pssm_build_multi_pssm: pssms scores the alignments,
+ * queries (same offsets) are the residues.  The context's own query is neither read nor changed by the batch calls.
+ * The alignments' paths stay on the device: swg_pssm_rows_kernel turns them into the rows, three more kernels count,
+ * weight and score (csrc/swg_pssm.hip); only the outputs come back.  The rows of a launch group take sum rows x lq bytes
+ * of device memory; option "pssm_msa_mb" (default 1024; 0 .. 65536, 0: every query alone) bounds them -- a batch over the bound runs
+ * in chunks of queries, a single query over it alone --, with the same bytes out.  The database must be resident; a view is
+ * accepted.  Errors, all before anything is launched: those of swg_align_hits_multi (a hit not in the shard, a pair
+ * outside what a traceback holds, NULL arguments, ...), pssm_out NULL with a query to build, a malformed freq, a
+ * pseudocount that is not finite and positive, a matrix without a lambda: SWG_ERR_ARG. */
+int swg_pssm_build(swg_ctx *ctx, const swg_db *db, const swg_hit *hits, size_t n_hits, const int8_t *query_residues,
+                   const double *freq, double pseudocount, int8_t *pssm_out, double *values_out, swg_pssm_info *info);
+int swg_pssm_build_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets, size_t n_queries,
+                         const swg_hit *hits, size_t k, const size_t *n_hits, const double *freq, double pseudocount,
+                         int8_t *pssms_out, double *values_out, swg_pssm_info *info);
+int swg_pssm_build_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const int8_t *queries,
+                              const uint64_t *q_offsets, size_t n_queries, const swg_hit *hits, size_t k, const size_t *n_hits,
+                              const double *freq, double pseudocount, int8_t *pssms_out, double *values_out,
+                              swg_pssm_info *info);
+
 /* ---- multi-GPU merge -------------------------------------------------- */
 
 /* 64-bit sort key of a hit: (score << 32) | (0xFFFFFFFF - index).  Larger key =

@@ -12,6 +12,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "swg.h" /* swg_alignment, swg_pssm_info */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -134,6 +136,32 @@ int swg_synth_db_iid(uint64_t seed, size_t n, uint32_t len, const double freq[32
  * *lambda = *mu = 0, *n_iter = 0), 2 when it did not converge (lambda and mu where it stopped), SWG_ERR_ARG for NULL
  * arguments.  The device's fit of swg_calibrate is this one, bin for bin. */
 int swg_gumbel_fit_hist(const uint32_t *hist, size_t n_bins, double *lambda, double *mu, int *n_iter);
+
+/* ---- a PSSM from alignments (the model of swg_pssm_build, include/swg.h) -- */
+
+/* The scale of a substitution matrix under a background: the unique lambda > 0 with
+ *     sum over a, b in A of P_a P_b exp(lambda sub[a][b]) = 1,
+ * P = freq normalised (NULL: the built-in table), A = {a in 1..31 : P_a > 0}; solved in double by bracketing and Newton
+ * steps kept inside the bracket until the residual is at most 1e-12.  It exists only if the expected score over A is
+ * negative and some sub[a][b] over A is positive: otherwise, and for a malformed freq or a NULL argument, SWG_ERR_ARG
+ * with a message in swg_global_error().  BLOSUM62 with the built-in table: 0.3172837580. */
+int swg_matrix_lambda(const int8_t sub[32][32], const double *freq, double *lambda);
+/* The host twin of swg_pssm_build: the same model, fed by exactly what swg_align_hits* returns -- al[n_hits] with
+ * al[i].index an index into flat / offsets (sequence j is flat[offsets[j] .. offsets[j+1]), table indices), the paths
+ * at ops + i*ops_stride -- for the query[lq] (table indices 1..31).  Rows and columns are summed in ascending order.
+ * pssm_out [lq*32]; values_out NULL or double[lq*32]: the unrounded v, 0 where there is none; info NULL or one record.
+ * A path that leaves its pair (a step past the query or the sequence, more steps than n_ops), NULL arguments, a bad
+ * freq, a pseudocount that is not finite and positive, a matrix without a lambda: SWG_ERR_ARG with a message in
+ * swg_global_error(). */
+int swg_pssm_from_paths(const int8_t sub[32][32], const double *freq, double pseudocount, const int8_t *query, size_t lq,
+                        const int8_t *flat, const uint64_t *offsets, const swg_alignment *al, const char *ops,
+                        size_t ops_stride, size_t n_hits, int8_t *pssm_out, double *values_out, swg_pssm_info *info);
+/* Writes the ASCII layout swg_pssm_load reads: a header of the 20 standard amino acids (A R N D C Q E G H I L K M F P S
+ * T W Y V), then `pos letter s1 .. s20` per query position and a blank line.  The other residue codes are not written:
+ * swg_pssm_load rebuilds them from the matrix, as swg_pssm_build filled them, so loading the file with the same
+ * scoring returns the same bytes.  SWG_ERR_ARG for NULL arguments, lq of 0 or a query residue without a letter;
+ * SWG_ERR_IO when the file cannot be written. */
+int swg_pssm_save(const char *path, const int8_t *pssm, const int8_t *query, size_t lq);
 
 /* Threads the host helpers' parallel loops use: the smallest of OpenMP's maximum (OMP_NUM_THREADS),
  * the CPUs this process may run on, and its cgroup CPU quota.  (The reference sizes its loop by

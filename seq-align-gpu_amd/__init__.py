@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "swg_synth_free", "swg_host_threads", "swg_pssm_load", "swg_pssm_free",
     "swg_db_composition", "swg_calibrate", "swg_calibrate_multi", "swg_calibrate_multi_pssm", "swg_evalue", "swg_bitscore",
     "swg_evalue_min_score", "swg_synth_db_iid", "swg_gumbel_fit_hist",
+    "swg_matrix_lambda", "swg_pssm_from_paths", "swg_pssm_save", "swg_pssm_build", "swg_pssm_build_multi", "swg_pssm_build_multi_pssm",
 ]
 
 
@@ -91,6 +92,19 @@ class EvalueParams(C.Structure):
         if isinstance(p, cls):
             return p
         return cls(float(p["lambda"]), float(p["K"]), float(p["mu"]), int(p["lq"]), int(p["n_seqs"]), int(p["seq_len"]), int(p["status"]))
+
+
+class PssmInfo(C.Structure):
+    """swg_pssm_info: what a PSSM construction reports per query."""
+    _fields_ = [("lambda_", C.c_double), ("n_distinct", C.c_double), ("n_rows", C.c_uint32), ("n_observed", C.c_uint32),
+                ("n_clamped", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {"lambda": self.lambda_, "n_distinct": self.n_distinct, "n_rows": self.n_rows, "n_observed": self.n_observed,
+                "n_clamped": self.n_clamped}
+
+
+PSSM_PSEUDOCOUNT_DEFAULT = 10.0
 
 
 class Stats(C.Structure):
@@ -283,6 +297,12 @@ _sig("swg_bitscore", C.c_double, [_vp, C.c_int32])
 _sig("swg_evalue_min_score", C.c_int32, [_vp, C.c_uint64, C.c_double])
 _sig("swg_synth_db_iid", C.c_int, [C.c_uint64, C.c_size_t, C.c_uint32, _vp, C.POINTER(_vp), C.POINTER(_vp)])
 _sig("swg_gumbel_fit_hist", C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)])
+_sig("swg_matrix_lambda", C.c_int, [_vp, _vp, C.POINTER(C.c_double)])
+_sig("swg_pssm_from_paths", C.c_int, [_vp, _vp, C.c_double, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp])
+_sig("swg_pssm_save", C.c_int, [C.c_char_p, _vp, _vp, C.c_size_t])
+_sig("swg_pssm_build", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_double, _vp, _vp, _vp])
+_sig("swg_pssm_build_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, C.c_double, _vp, _vp, _vp])
+_sig("swg_pssm_build_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, C.c_double, _vp, _vp, _vp])
 
 
 def _check(rc, ctx=None):
@@ -471,6 +491,56 @@ def gumbel_fit_hist(hist):
     if rc < 0:
         _check(rc)
     return {"lambda": lam.value, "mu": mu.value, "n_iter": it.value, "status": rc}
+
+
+def matrix_lambda(sub, freq=None):
+    """The scale of a substitution matrix under a background (swg_matrix_lambda): the positive root of
+    sum P_a P_b exp(lambda sub[a][b]) = 1.  freq: 32 weights by residue index (None: the built-in table)."""
+    if isinstance(sub, Scoring):
+        sub = sub.table()
+    s, sp = _i8(np.asarray(sub).reshape(32, 32))
+    f, fp = _freq(freq)
+    lam = C.c_double(0)
+    _check(lib.swg_matrix_lambda(sp, fp, C.byref(lam)))
+    return lam.value
+
+
+def pssm_from_paths(sub, query, flat, offsets, alignments, freq=None, pseudocount=PSSM_PSEUDOCOUNT_DEFAULT, want_values=False):
+    """The PSSM of `query` (table indices) from its hits' alignments on the host (swg_pssm_from_paths, the twin of
+    Context.build_pssm): alignments is what align_hits returns with want_ops=True -- dicts whose "index" is an index
+    into flat / offsets -> (pssm int8[lq, 32], values float64[lq, 32] or None, info dict)."""
+    if isinstance(sub, Scoring):
+        sub = sub.table()
+    s, sp = _i8(np.asarray(sub).reshape(32, 32))
+    q, qp = _i8(query)
+    fl, flp = _i8(flat)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    f, fp = _freq(freq)
+    n = len(alignments)
+    stride = max((a["n_ops"] for a in alignments), default=0) + 1
+    al = (Alignment * max(n, 1))()
+    ops = C.create_string_buffer(max(1, n * stride))
+    for i, a in enumerate(alignments):
+        for name, _ in Alignment._fields_:
+            if name != "reserved":
+                setattr(al[i], name, int(a[name]))
+        ops[i * stride:i * stride + len(a["ops"])] = a["ops"].encode()
+    pssm = np.zeros((q.size, 32), dtype=np.int8)
+    values = np.zeros((q.size, 32), dtype=np.float64) if want_values else None
+    info = PssmInfo()
+    _check(lib.swg_pssm_from_paths(sp, fp, float(pseudocount), qp, q.size, flp, off.ctypes.data_as(_vp), C.cast(al, _vp), C.cast(ops, _vp),
+                                   stride, n, pssm.ctypes.data_as(_vp), values.ctypes.data_as(_vp) if want_values else None, C.byref(info)))
+    return pssm, values, info.as_dict()
+
+
+def write_pssm(path, pssm, query):
+    """The ASCII PSSM file read_pssm reads (swg_pssm_save): the 20 standard columns of pssm int8[lq, 32] and the query's
+    residues (table indices)."""
+    p, pp, lq = _pssm(pssm)
+    q, qp = _i8(query)
+    if q.size != lq:
+        raise ValueError("query: %d residues for a PSSM of %d rows" % (q.size, lq))
+    _check(lib.swg_pssm_save(os.fsencode(path), pp, qp, lq))
 
 
 def evalue(params, db_residues, score):
@@ -1043,6 +1113,7 @@ class Context:
 
     def __init__(self, device=0):
         self.handle = None
+        self._lq = 0        # length of the query last set (build_pssm sizes its output by it)
         cfg = Config()
         cfg.device = device
         h = _vp()
@@ -1061,11 +1132,13 @@ class Context:
     def set_query(self, idx):
         q, qp = _i8(idx)
         _check(lib.swg_set_query(self.handle, qp, q.size), self.handle)
+        self._lq = q.size
 
     def set_query_pssm(self, pssm):
         """A position-specific query: pssm int8[lq, 32], row i = query position i's scores by residue index."""
         p, pp, lq = _pssm(pssm)
         _check(lib.swg_set_query_pssm(self.handle, pp, lq), self.handle)
+        self._lq = lq
 
     def search(self, db, want_scores=True, k=0, _fn=None):
         """-> (scores int32[total] or None, hits [(score, index)], stats dict)."""
@@ -1327,6 +1400,71 @@ class Context:
         qoff[1:] = np.cumsum([r.shape[0] for r in rows])
         pflat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 32)), dtype=np.int8)
         return self._align_multi(lib.swg_align_hits_multi_pssm, db, pflat, qoff, hits, want_ops, ops_stride)
+
+    def build_pssm(self, db, hits, query_residues=None, freq=None, pseudocount=PSSM_PSEUDOCOUNT_DEFAULT, want_values=False):
+        """The PSSM of the context's query from its hits [(score, index)], built on the device (swg_pssm_build) -> (pssm
+        int8[lq, 32], values float64[lq, 32] or None, info dict).  query_residues: None for an index query; the query's
+        residues when the context's query is a PSSM (the next iteration of a profile search)."""
+        n = len(hits)
+        arr = (Hit * max(n, 1))()
+        for i, (sc, ix) in enumerate(hits):
+            arr[i].score, arr[i].index = int(sc), int(ix)
+        lq = self._lq                   # (the library writes as many rows as the context's query has)
+        qr, qrp = (None, None) if query_residues is None else _i8(query_residues)
+        if qr is not None and qr.size != lq:
+            raise ValueError("query_residues: %d residues for a query of %d positions" % (qr.size, lq))
+        f, fp = _freq(freq)
+        pssm = np.zeros((max(lq, 1), 32), dtype=np.int8)
+        values = np.zeros((max(lq, 1), 32), dtype=np.float64) if want_values else None
+        info = PssmInfo()
+        _check(lib.swg_pssm_build(self.handle, db.handle, C.cast(arr, _vp), n, qrp, fp, float(pseudocount), pssm.ctypes.data_as(_vp),
+                                  values.ctypes.data_as(_vp) if want_values else None, C.byref(info)), self.handle)
+        return pssm[:lq], (values[:lq] if want_values else None), info.as_dict()
+
+    def build_pssm_multi(self, db, queries, hits, freq=None, pseudocount=PSSM_PSEUDOCOUNT_DEFAULT, want_values=False):
+        """build_pssm for a batch: queries as search_multi takes them, hits the list of lists of (score, index) that
+        search_multi or search_above_multi returns -> (pssms: list of int8[lq_i, 32], ready for search_multi_pssm; values:
+        list of float64[lq_i, 32] or None; infos: list of dicts).  The context's own query is kept (swg_pssm_build_multi)."""
+        return self._build_pssm_multi(db, None, queries, hits, freq, pseudocount, want_values)
+
+    def build_pssm_multi_pssm(self, db, pssms, queries, hits, freq=None, pseudocount=PSSM_PSEUDOCOUNT_DEFAULT, want_values=False):
+        """build_pssm_multi with position-specific queries: pssms score the alignments, queries are their residues."""
+        return self._build_pssm_multi(db, pssms, queries, hits, freq, pseudocount, want_values)
+
+    def _build_pssm_multi(self, db, pssms, queries, hits, freq, pseudocount, want_values):
+        nq = len(queries)
+        if len(hits) != nq or (pssms is not None and len(pssms) != nq):
+            raise ValueError("hits / pssms: one row per query (%d queries)" % nq)
+        qoff = np.zeros(nq + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in queries])
+        total = int(qoff[nq])
+        qflat = np.ascontiguousarray(np.concatenate(queries) if nq else np.zeros(1), dtype=np.int8)
+        k = max((len(row) for row in hits), default=0)
+        arr = (Hit * max(nq * k, 1))()
+        nh = (C.c_size_t * max(nq, 1))()
+        for i, row in enumerate(hits):
+            nh[i] = len(row)
+            for j, (sc, ix) in enumerate(row):
+                arr[i * k + j].score, arr[i * k + j].index = int(sc), int(ix)
+        f, fp = _freq(freq)
+        out = np.zeros((max(total, 1), 32), dtype=np.int8)
+        values = np.zeros((max(total, 1), 32), dtype=np.float64) if want_values else None
+        info = (PssmInfo * max(nq, 1))()
+        tail = (C.cast(arr, _vp), k, C.cast(nh, _vp), fp, float(pseudocount), out.ctypes.data_as(_vp),
+                values.ctypes.data_as(_vp) if want_values else None, C.cast(info, _vp))
+        if pssms is None:
+            rc = lib.swg_pssm_build_multi(self.handle, db.handle, qflat.ctypes.data_as(_vp), qoff.ctypes.data_as(_vp), nq, *tail)
+        else:
+            rows = [_pssm(p)[0] for p in pssms]
+            if [r.shape[0] for r in rows] != [len(q) for q in queries]:
+                raise ValueError("pssms and queries differ in length")
+            pflat = np.ascontiguousarray(np.concatenate(rows) if nq else np.zeros((1, 32)), dtype=np.int8)
+            rc = lib.swg_pssm_build_multi_pssm(self.handle, db.handle, pflat.ctypes.data_as(_vp), qflat.ctypes.data_as(_vp),
+                                               qoff.ctypes.data_as(_vp), nq, *tail)
+        _check(rc, self.handle)
+        cut = [(int(qoff[i]), int(qoff[i + 1])) for i in range(nq)]
+        return ([out[a:b].copy() for a, b in cut], [values[a:b].copy() for a, b in cut] if want_values else None,
+                [info[i].as_dict() for i in range(nq)])
 
     def align_bounds(self, db, hits):
         """align_hits(db, hits, want_ops=False) from a forward pass alone (swg_align_bounds: no traceback is run)."""

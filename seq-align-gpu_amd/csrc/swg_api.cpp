@@ -389,6 +389,9 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
     } else if (!strcmp(key, "calib_seqs")) {
         if (value < 2 || value > (1l << 20)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "calib_seqs must be 2..1048576 (random sequences a calibration scores)");
         ctx->opt_calib_seqs = value;
+    } else if (!strcmp(key, "pssm_msa_mb")) {
+        if (value < 0 || value > 65536) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "pssm_msa_mb must be 0..65536 (MiB of device rows one group of queries of swg_pssm_build* may take; 0: every query alone)");
+        ctx->opt_pssm_msa_mb = value;
     } else if (!strcmp(key, "calib_len")) {
         if (value < 8 || value > (1l << 14)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "calib_len must be 8..16384 (residues of a calibration's random sequences)");
         ctx->opt_calib_len = value;

@@ -604,6 +604,7 @@ struct swg_ctx {
         long seqs = 0, len = 0, seed = 0;
     } calib;
     std::vector<int32_t> calib_iters; // Newton steps of each query's fit in the last swg_calibrate* call (tests)
+    long opt_pssm_msa_mb = 1024; // swg_pssm_build*: MiB of device rows (sum rows x lq) one group of queries may take (option "pssm_msa_mb")
     SwgSlot slots[SWG_MAX_INFLIGHT];
     SwgSlot *cur = nullptr; // slot whose events the launch helpers record into
     int next_slot = 0;
@@ -742,8 +743,50 @@ struct SwgTraceBatch {
 // stride0: paths are wanted with an ops_stride of 0 (refused where it always was: after the database, before the rows)
 int swg_trace_check_batch(swg_ctx *ctx, const swg_db *db, const SwgTraceBatch &tb, const swg_alignment *out, bool stride0,
                           size_t *total);
+// One pair of a traceback launch and what the kernel leaves for it (device structs of swg_trace.hip).  A job carries its
+// own query, so one launch can hold the hits of several queries of a batch; the offsets into the launch's predecessor
+// bytes, rotating diagonals and paths are the job's own because all three are sized by its lq (and the path by its len).
+struct SwgTraceJob {
+    uint64_t q_off;    // into the batch's query: first index byte, or first PSSM row
+    uint64_t res_off;  // into the gathered residue indices
+    uint64_t dir_off;  // into the launch's predecessor bytes: (lq + len - 1) * lq of them
+    uint64_t diag_off; // into the launch's rotating anti-diagonals (kernels without LDS): 9 * (lq + 1) words
+    uint64_t ops_off;  // into the launch's paths: lq + len + 1 bytes (a path has at most lq + len steps)
+    uint32_t lq;       // query length
+    uint32_t len;      // database sequence length
+};
+struct SwgTraceOut {
+    int32_t score;
+    uint32_t q_begin, q_end, d_begin, d_end, n_ops, pad[2];
+};
+// An optional sink of a traceback call: run(user, v, stream) is called once per launch, after the launch's kernel was
+// queued on `stream` and before the call waits for it, while the device buffers of the launch are valid -- jobs[n_jobs]
+// with their results out[n_jobs], their paths in ops (job j's at jobs[j].ops_off) and the gathered residues res (job j's
+// at jobs[j].res_off); dest[j] (host) is job j's slot i*k + j' of the batch.  What it queues on the stream is waited for
+// with the launch.  A failure ends the call with SWG_ERR_HIP.
+struct SwgTraceLaunchView {
+    const SwgTraceJob *d_jobs;
+    const SwgTraceOut *d_out;
+    const char *d_ops;
+    const int8_t *d_res;
+    const size_t *dest;
+    size_t n_jobs;
+};
+struct SwgTraceSink {
+    void *user;
+    hipError_t (*run)(void *user, const SwgTraceLaunchView &v, hipStream_t stream);
+};
 int swg_trace_align_batch(swg_ctx *ctx, const swg_db *db, const SwgTraceBatch &tb, size_t total, swg_alignment *out, char *ops,
-                          size_t ops_stride);
+                          size_t ops_stride, const SwgTraceSink *sink = nullptr);
+// The refusals of swg_trace_align_batch that depend on the database (a hit this shard does not hold, a pair outside what
+// a traceback holds), on their own: a caller that runs a batch in several calls refuses all of it first.
+int swg_trace_check_pairs(swg_ctx *ctx, const swg_db *db, const SwgTraceBatch &tb);
+
+// swg_pssm_host.cpp: the checks every PSSM construction makes before anything else (the background P and the mask of A
+// from freq, the pseudocount, lambda of (sub, P)); SWG_ERR_ARG with a message naming fn in swg_global_error().
+extern "C" int swg_freq_weights(const double *freq, double w[32], double *tot_out); // host/swg_synth.c
+int swg_pssm_check_model(const char *fn, const int8_t sub[32][32], const double *freq, double pseudocount, double P[32],
+                         uint32_t *mask, double *lambda);
 // swg_bounds.hip, test hook: what the context's last swg_align_bounds* call did -- out[0..3] = pairs on the bounds kernel,
 // pairs on the fallback (the traceback's kernel), launches of the bounds kernel, its column limit
 #define SWG_BOUNDS_COLS 1024         /* 64 lanes x 16 columns */

@@ -20,24 +20,7 @@
 #include <cstring>
 #include <unordered_map>
 
-// One pair.  A job carries its own query, so one launch can hold the hits of several queries of a batch; the offsets
-// into the launch's predecessor bytes, rotating diagonals and paths are the job's own because all three are sized by
-// its lq (and the path by its len).
-struct SwgTraceJob {
-    uint64_t q_off;    // into the batch's query: first index byte, or first PSSM row
-    uint64_t res_off;  // into the gathered residue indices
-    uint64_t dir_off;  // into the launch's predecessor bytes: (lq + len - 1) * lq of them
-    uint64_t diag_off; // into the launch's rotating anti-diagonals (kernels without LDS): 9 * (lq + 1) words
-    uint64_t ops_off;  // into the launch's paths: lq + len + 1 bytes (a path has at most lq + len steps)
-    uint32_t lq;       // query length
-    uint32_t len;      // database sequence length
-};
-
-struct SwgTraceOut {
-    int32_t score;
-    uint32_t q_begin, q_end, d_begin, d_end, n_ops, pad[2];
-};
-
+// (SwgTraceJob, one pair, and SwgTraceOut, what the kernel leaves for it: swg_host_internal.h)
 struct SwgTraceParams {
     const int8_t *query; // table indices of the batch's queries, back to back (PSSM kernel: unread)
     const int8_t *sub;   // [32][32], row = query residue (PSSM kernel: unread)
@@ -212,7 +195,7 @@ static int trace_class(uint32_t lq) { return lq > SWG_TRACE_LDS_COLS ? 0 : 32 - 
 // allocated once per call; jobs are ordered by query length and cut into launches by class and by the 2 GiB budget of
 // predecessor bytes; each launch ends in one stream synchronisation, then its results are copied out.
 static int align_batch(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, size_t total, swg_alignment *out, char *ops,
-                       size_t ops_stride)
+                       size_t ops_stride, const SwgTraceSink *sink)
 {
     const char *fn = tb.fn;
     // original index -> slot of the sorted order, for the wanted sequences only
@@ -324,6 +307,10 @@ static int align_batch(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, siz
         else
             hipLaunchKernelGGL((swg_trace_kernel<false, true>), dim3((unsigned)nb), dim3(SWG_TRACE_THREADS), 0, ctx->stream, p);
         TRACE_TRY(ctx, hipGetLastError());
+        if (sink) { // (the launch's buffers are valid until the synchronisation below)
+            const SwgTraceLaunchView v = {d_jobs + L.b, d_out + L.b, d_ops, d_res, dest.data() + L.b, nb};
+            TRACE_TRY(ctx, sink->run(sink->user, v, ctx->stream));
+        }
         TRACE_TRY(ctx, hipMemcpyAsync(h_out.data() + L.b, d_out + L.b, nb * sizeof(SwgTraceOut), hipMemcpyDeviceToHost,
                                       ctx->stream));
         if (ops) TRACE_TRY(ctx, hipMemcpyAsync(h_ops.data(), d_ops, L.ops, hipMemcpyDeviceToHost, ctx->stream));
@@ -349,12 +336,49 @@ done:
     return rc;
 }
 
-// try/catch: no C++ exception crosses the ABI (the host vectors are sized by the batch)
-int swg_trace_align_batch(swg_ctx *ctx, const swg_db *db, const SwgTraceBatch &tb, size_t total, swg_alignment *out, char *ops,
-                          size_t ops_stride)
+// align_batch's refusals by the database, without the rest of it (same order, same messages)
+static int check_pairs(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb)
+{
+    const char *fn = tb.fn;
+    std::unordered_map<uint32_t, size_t> slot_of;
+    for (size_t i = 0; i < tb.n_queries; ++i)
+        for (size_t j = 0; j < tb.n_hits[i]; ++j) slot_of[tb.hits[i * tb.k + j].index] = SIZE_MAX;
+    for (size_t s = 0; s < db->order.size(); ++s) {
+        if (db->order[s] == ~0u) continue;
+        auto it = slot_of.find(db->order[s]);
+        if (it != slot_of.end()) it->second = s;
+    }
+    for (size_t i = 0; i < tb.n_queries; ++i) {
+        const size_t lq = (size_t)(tb.q_offsets[i + 1] - tb.q_offsets[i]);
+        for (size_t j = 0; j < tb.n_hits[i]; ++j) {
+            const uint32_t index = tb.hits[i * tb.k + j].index;
+            const size_t s = slot_of[index];
+            if (s == SIZE_MAX)
+                return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: sequence %u is not in this database shard", fn, index);
+            const size_t len = db->lens[s];
+            if (len == 0 || (uint64_t)(lq + len) * lq > (16ull << 30))
+                return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s: pair %u (%zu x %zu) is outside what a traceback holds", fn,
+                                         index, lq, len);
+        }
+    }
+    return SWG_OK;
+}
+
+int swg_trace_check_pairs(swg_ctx *ctx, const swg_db *db, const SwgTraceBatch &tb)
 {
     try {
-        return align_batch(ctx, db, tb, total, out, ops, ops_stride);
+        return check_pairs(ctx, db, tb);
+    } catch (const std::exception &) {
+        return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "%s: out of host memory", tb.fn);
+    }
+}
+
+// try/catch: no C++ exception crosses the ABI (the host vectors are sized by the batch)
+int swg_trace_align_batch(swg_ctx *ctx, const swg_db *db, const SwgTraceBatch &tb, size_t total, swg_alignment *out, char *ops,
+                          size_t ops_stride, const SwgTraceSink *sink)
+{
+    try {
+        return align_batch(ctx, db, tb, total, out, ops, ops_stride, sink);
     } catch (const std::bad_alloc &) {
         return swg_set_ctx_error(ctx, SWG_ERR_NOMEM, "%s: out of host memory", tb.fn);
     } catch (const std::exception &e) {

@@ -37,7 +37,11 @@
  *     swg_calibrate_multi / _multi_pssm -- is calibrated on the device against random sequences (swg_calibrate), E becomes a
  *     raw score per query over the residues of what is searched (swg_evalue_min_score), and --minscore's / --minscorelist's
  *     searches run at those; --compfromdb draws the random sequences from the searched entries' own composition
- *     (swg_db_composition); --tabular then prints BLAST's twelve columns, evalue and bitscore included.
+ *     (swg_db_composition); --tabular then prints BLAST's twelve columns, evalue and bitscore included;
+ *     --iterations N searches N times, PSI-BLAST's way: each iteration but the last calibrates the current query, turns
+ *     --inclusion's E-value into a least score, collects up to --maxincluded hits at or above it (swg_search_above), builds
+ *     their PSSM on the device (swg_pssm_build) and makes it the query; the last iteration is the report above with that
+ *     PSSM as the query, and --out_pssm writes it in the layout --pssm reads.
  * There is no CPU backend: without a GPU the tool fails with a message.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -119,6 +123,16 @@ static void usage(const char *argv0, const char *err)
             "                         --bounds; not with --minscore, --minscorelist, --candidates or --prefilter\n"
             "    --compfromdb         with --evalue: the random sequences follow the composition of the entries searched instead of\n"
             "                         the built-in amino-acid frequencies\n"
+            "    --iterations <N>     search N times (2 or more): every iteration but the last calibrates the current query, includes the\n"
+            "                         entries whose E-value is at most --inclusion (the best --maxincluded of them), builds their\n"
+            "                         position-specific scoring matrix on the GPU and makes it the query; the last iteration is the\n"
+            "                         usual report (--topk, --align, --tabular, --evalue, ...) with that PSSM as the query; an iteration\n"
+            "                         that includes nothing new ends the iterations (said on stderr); --compfromdb gives the\n"
+            "                         background; one query record, one GPU: not with --allqueries, --gpus N > 1, --candidates,\n"
+            "                         --prefilter or --gapless\n"
+            "    --inclusion <E>      with --iterations: the largest E-value of an included entry [default: 0.002]\n"
+            "    --maxincluded <M>    with --iterations: the most entries included per iteration [default: 500]\n"
+            "    --out_pssm <file>    with --iterations: write the last PSSM (readable by --pssm)\n"
             "    --prefilter <N>      with --topk K: per query (every record with --allqueries) the N best entries by gapless\n"
             "                         score are searched with gaps and the K best of those reported (--align: aligned);\n"
             "                         no Entry lines are printed; not with --gpus, --candidates or --gapless\n",
@@ -255,7 +269,10 @@ int main(int argc, char **argv)
     int print_seq = 0, print_fasta = 0, have_matrix = 0, packed = 0, allq = 0;
     long topk = 0, gpu = 0, gpus = 0, prefilter = 0, minscore = 0, v;
     int align = 0, gapless = 0, bounds = 0, tabular = 0, have_evalue = 0, compfromdb = 0;
-    double evalue = 0.0;
+    double evalue = 0.0, inclusion = 0.002;
+    long iterations = 0, maxincluded = 500;
+    int have_inclusion = 0, have_maxincluded = 0;
+    const char *out_pssm = NULL;
     if (argc == 1) usage(argv[0], NULL);
     for (int i = 1; i < argc; i++)
         if (!strcasecmp(argv[i], "--help") || !strcasecmp(argv[i], "-help") || !strcasecmp(argv[i], "-h"))
@@ -324,6 +341,22 @@ int main(int argc, char **argv)
                 usage(argv[0], "Invalid --evalue argument: the largest E-value to report, a number above 0");
             have_evalue = 1;
             i++;
+        } else if (!strcasecmp(a, "--iterations")) {
+            if (!parse_int(argv[i + 1], 2, 1000, &iterations)) usage(argv[0], "Invalid --iterations argument: the number of searches, 2 or more");
+            i++;
+        } else if (!strcasecmp(a, "--inclusion")) {
+            char *end = NULL;
+            inclusion = strtod(argv[i + 1], &end);
+            if (end == argv[i + 1] || *end != '\0' || !(inclusion > 0.0) || isinf(inclusion))
+                usage(argv[0], "Invalid --inclusion argument: the largest E-value of an included entry, a number above 0");
+            have_inclusion = 1;
+            i++;
+        } else if (!strcasecmp(a, "--maxincluded")) {
+            if (!parse_int(argv[i + 1], 1, 1 << 20, &maxincluded)) usage(argv[0], "Invalid --maxincluded argument: the most entries included per iteration, 1 or more");
+            have_maxincluded = 1;
+            i++;
+        } else if (!strcasecmp(a, "--out_pssm")) {
+            out_pssm = argv[++i];
         } else if (!strcasecmp(a, "--prefilter")) {
             if (!parse_int(argv[i + 1], 1, 1 << 20, &prefilter)) usage(argv[0], "Invalid --prefilter argument: the number of candidates per query, 1 or more");
             i++;
@@ -372,7 +405,15 @@ int main(int argc, char **argv)
     if (have_evalue && (minscore || mslist_path)) usage(argv[0], "--evalue derives the least score itself: it does not combine with --minscore or --minscorelist");
     if (have_evalue && (cand_path || prefilter)) usage(argv[0], "--evalue does not combine with --candidates or --prefilter");
     if (have_evalue && allq && topk == 0) usage(argv[0], "--allqueries --evalue reports up to --topk K hits per record: give --topk K");
-    if (compfromdb && !have_evalue) usage(argv[0], "--compfromdb chooses the background of --evalue's calibration: give --evalue E");
+    if (compfromdb && !have_evalue && !iterations) usage(argv[0], "--compfromdb chooses the background of --evalue's calibration: give --evalue E");
+    if (!iterations && (have_inclusion || have_maxincluded || out_pssm))
+        usage(argv[0], "--inclusion, --maxincluded and --out_pssm belong to the iterated search: give --iterations N");
+    if (iterations && allq) usage(argv[0], "--iterations iterates one query record: it does not combine with --allqueries");
+    if (iterations && gpus > 1) usage(argv[0], "--iterations works with one GPU (--gpu): it does not combine with --gpus N > 1");
+    if (iterations && cand_path) usage(argv[0], "--iterations makes its own lists of included entries: it does not combine with --candidates");
+    if (iterations && prefilter) usage(argv[0], "--iterations makes its own lists of included entries: it does not combine with --prefilter");
+    if (iterations && gapless) usage(argv[0], "--iterations builds its PSSM from gapped alignments: it does not combine with --gapless");
+    if (iterations && gpus == 1) gpus = 0; /* (one GPU either way: the iterations run on a context, not on a group of one) */
     /* --evalue: the searches of --minscore (one query) or of --minscorelist (every record) at scores the calibration gives;
      * until it has run, 1 stands for them */
     const int ev_batch = have_evalue && allq;
@@ -716,6 +757,7 @@ int main(int argc, char **argv)
         free(names);
     }
     const int8_t *pssm0 = pssm ? pssm : plist; /* the first record's PSSM, if any */
+    int8_t *iter_pssm = NULL;                  /* --iterations: the PSSM of the last iteration that built one (then pssm0) */
     swg_query_sanitize(&sc, qidx, lq); /* reference src/alignment_cmdline.c:391-396 */
     if (!packed && swg_seqs_to_indices(&db, didx, &bad) != SWG_OK) die_illegal(bad);
 
@@ -898,6 +940,54 @@ int main(int argc, char **argv)
         if (rc == SWG_OK && ids) {
             rc = swg_db_view(ctx, pdb, ids, n_ids, &sdb);
             phase("select the listed entries");
+        }
+        if (rc == SWG_OK && iterations) { /* every iteration but the last: calibrate, include, build the PSSM, make it the query */
+            uint64_t counts[32];
+            double freq[32];
+            if (compfromdb) rc = swg_db_composition(ctx, sdb, counts);
+            for (int r = 0; r < 32; r++) freq[r] = compfromdb && rc == SWG_OK ? (double)counts[r] : 0.0;
+            swg_hit *inc = (swg_hit *)calloc((size_t)maxincluded, sizeof *inc);
+            unsigned char *was = (unsigned char *)calloc(db.n ? db.n : 1, 1); /* the entries the previous iteration included */
+            iter_pssm = (int8_t *)malloc(lq * 32);
+            if (!inc || !was || !iter_pssm) return leave(EXIT_FAILURE);
+            for (long it = 1; rc == SWG_OK && it < iterations; it++) {
+                swg_evalue_params p;
+                size_t n_inc = 0, n_new = 0;
+                uint64_t n_at = 0;
+                rc = swg_calibrate(ctx, compfromdb ? freq : NULL, 0, &p);
+                if (rc != SWG_OK) break;
+                const int32_t least = swg_evalue_min_score(&p, swg_db_residues(sdb), inclusion);
+                if (least < 1) {
+                    fprintf(stderr, "Error: iteration %ld: the query could not be calibrated (fit status %d): no least score for --inclusion %g\n", it,
+                            p.status, inclusion);
+                    return leave(EXIT_FAILURE);
+                }
+                rc = swg_search_above(ctx, sdb, least, inc, (size_t)maxincluded, &n_inc, &n_at, NULL);
+                if (rc != SWG_OK) break;
+                for (size_t h = 0; h < n_inc; h++) n_new += !was[inc[h].index];
+                fprintf(stderr, "iteration %ld: %lu entries at or above score %d (E-value %g), %lu included, %lu of them new\n", it,
+                        (unsigned long)n_at, least, inclusion, (unsigned long)n_inc, (unsigned long)n_new);
+                if (it > 1 && n_new == 0) {
+                    fprintf(stderr, "iteration %ld includes no entry beyond iteration %ld's: the iterations end here\n", it, it - 1);
+                    break;
+                }
+                memset(was, 0, db.n ? db.n : 1);
+                for (size_t h = 0; h < n_inc; h++) was[inc[h].index] = 1;
+                /* the context's query is the record itself (no residues to name) or a PSSM (--pssm, or the iteration before) */
+                rc = swg_pssm_build(ctx, sdb, inc, n_inc, pssm0 ? qidx : NULL, compfromdb ? freq : NULL, SWG_PSSM_PSEUDOCOUNT_DEFAULT,
+                                    iter_pssm, NULL, NULL);
+                if (rc == SWG_OK) rc = swg_set_query_pssm(ctx, iter_pssm, lq);
+                if (rc == SWG_OK) pssm0 = iter_pssm;
+            }
+            free(inc);
+            free(was);
+            if (rc == SWG_OK && out_pssm) { /* (iteration 1 always builds one) */
+                if (swg_pssm_save(out_pssm, iter_pssm, qidx, lq) != SWG_OK) {
+                    fprintf(stderr, "Error: %s\n", swg_global_error());
+                    return leave(EXIT_FAILURE);
+                }
+            }
+            phase("iterations (calibrate, include, build the PSSM)");
         }
         if (rc == SWG_OK && have_evalue) { /* the least score of the query, or of every record, from its calibration */
             uint64_t counts[32];

@@ -265,16 +265,15 @@ int swg_synth_db_shard(uint64_t seed, size_t n, double median, double sigma_ln, 
     return rc;
 }
 
-/* i.i.d. sequences of one length from a caller's composition (the database a calibration scores against).  Draw j of
- * sequence i is the j-th output of the splitmix64 stream seeded with mix(seed ^ 0x11D, i) -- splitmix64 is a counter
- * hashed, so that is a function of (seed, i, j) alone --, its top 53 bits a uniform in [0, 1) looked up in the
- * cumulative table; the last residue with a positive weight takes whatever rounding leaves below 1. */
-int swg_synth_db_iid(uint64_t seed, size_t n, uint32_t len, const double freq[32], int8_t **flat_out, uint64_t **offsets_out)
+/* A composition as the library takes it (swg_synth_db_iid, swg_calibrate*, swg_pssm_build*; declared in
+ * csrc/swg_host_internal.h): freq[r] is the weight of residue index r, NULL the built-in table above.  The weights must
+ * be finite and non-negative, freq[0] must be 0 and the sum positive and finite: else SWG_ERR_ARG.  -> w[32] as given,
+ * *tot their sum in ascending order (the caller normalises). */
+int swg_freq_weights(const double *freq, double w[32], double *tot_out);
+int swg_freq_weights(const double *freq, double w[32], double *tot_out)
 {
-    if (!flat_out || !offsets_out || n == 0 || len == 0) return SWG_ERR_ARG;
-    *flat_out = NULL;
-    *offsets_out = NULL;
-    double w[32] = {0}, tot = 0.0;
+    double tot = 0.0;
+    for (int r = 0; r < 32; r++) w[r] = 0.0;
     if (freq) {
         for (int r = 0; r < 32; r++) {
             if (!(freq[r] >= 0.0) || isinf(freq[r])) return SWG_ERR_ARG; /* (a NaN fails the comparison) */
@@ -286,6 +285,21 @@ int swg_synth_db_iid(uint64_t seed, size_t n, uint32_t len, const double freq[32
     }
     for (int r = 0; r < 32; r++) tot += w[r];
     if (!(tot > 0.0) || isinf(tot)) return SWG_ERR_ARG;
+    *tot_out = tot;
+    return SWG_OK;
+}
+
+/* i.i.d. sequences of one length from a caller's composition (the database a calibration scores against).  Draw j of
+ * sequence i is the j-th output of the splitmix64 stream seeded with mix(seed ^ 0x11D, i) -- splitmix64 is a counter
+ * hashed, so that is a function of (seed, i, j) alone --, its top 53 bits a uniform in [0, 1) looked up in the
+ * cumulative table; the last residue with a positive weight takes whatever rounding leaves below 1. */
+int swg_synth_db_iid(uint64_t seed, size_t n, uint32_t len, const double freq[32], int8_t **flat_out, uint64_t **offsets_out)
+{
+    if (!flat_out || !offsets_out || n == 0 || len == 0) return SWG_ERR_ARG;
+    *flat_out = NULL;
+    *offsets_out = NULL;
+    double w[32], tot;
+    if (swg_freq_weights(freq, w, &tot) != SWG_OK) return SWG_ERR_ARG;
     double cum[32], acc = 0.0;
     int last = 0;
     for (int r = 0; r < 32; r++) {
