@@ -692,6 +692,72 @@ int swg_pssm_build_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssm
                               const double *freq, double pseudocount, int8_t *pssms_out, double *values_out,
                               swg_pssm_info *info);
 
+/* ---- masking of low-complexity regions -------------------------------------------------------------------- */
+
+/* The rule: the trigger and extension stages of SEG (Wootton & Federhen 1993), decided in integers.  There is NO third
+ * stage: a kept segment is not trimmed to its least probable sub-segment, so this masks a little more than SEG does.
+ *   window W (4..64), trigger K1 and extend K2 in bits (0 <= K1 <= K2), replace = the residue index written (1..31).
+ *   T[0] = 0, T[c] = rint(c log2(c) 65536) for c = 1..W, computed once on the host in double.
+ *   A window start s (0 <= s <= len - W) has counts c_a of each residue index a (all 32 indices, each a letter of its
+ *   own) in [s, s + W); its weight is S(s) = sum_a T[c_a].  The window is LOW AT K iff
+ *       S(s) >= ceil(W (log2 W - K) 65536),
+ *   which is "entropy <= K".  For W = 12 the thresholds of K1 = 2.2 and K2 = 2.5 are 1089179 and 853250.
+ *   A maximal run of consecutive window starts that are all low at K2 is KEPT iff at least one of its starts is low at
+ *   K1.  Position i is masked iff some kept start s has s <= i < s + W.  A sequence shorter than W has no window and is
+ *   left alone.
+ * The device kernels (csrc/swg_mask.hip) and the host twin swg_seg_mask receive the same T and the same two thresholds
+ * (swg_mask_tables), so their results are equal byte for byte. */
+typedef struct swg_mask_params {
+    int32_t window;  /* W */
+    int32_t replace; /* residue index written at a masked position */
+    double trigger;  /* K1 */
+    double extend;   /* K2 */
+} swg_mask_params;
+#define SWG_MASK_WINDOW_DEFAULT 12
+#define SWG_MASK_TRIGGER_DEFAULT 2.2
+#define SWG_MASK_EXTEND_DEFAULT 2.5
+#define SWG_MASK_REPLACE_DEFAULT 24 /* swg_letter_index('X') */
+void swg_mask_params_default(swg_mask_params *p);
+/* The integers of the rule: T[0..64] (entries past W are 0) and the thresholds of K1 and K2.  p NULL: the defaults.
+ * SWG_ERR_ARG for parameters out of range (or not finite). */
+int swg_mask_tables(const swg_mask_params *p, int32_t T[65], int64_t *thr_trigger, int64_t *thr_extend);
+/* The host twin, and what a caller masks a QUERY with: mask_out[i] = 1 where position i of idx[len] (table indices 0..31)
+ * is masked, 0 elsewhere (mask_out NULL: counts only); n_masked, n_segments (either NULL): the positions covered and the
+ * kept runs.  idx is not changed: a caller writes p->replace where mask_out says so.  p NULL: the defaults. */
+int swg_seg_mask(const int8_t *idx, size_t len, const swg_mask_params *p, uint8_t *mask_out, size_t *n_masked);
+int swg_seg_mask_segments(const int8_t *idx, size_t len, const swg_mask_params *p, uint8_t *mask_out, size_t *n_masked,
+                          size_t *n_segments);
+/* One sequence back out of a database's host image (root, view, loaded file, masked copy): the table indices of the
+ * sequence whose ORIGINAL index is given.  *len is always its length; the residues are written when cap >= *len (else
+ * SWG_ERR_ARG with *len set, so that a caller can ask again).  A sequence this shard or view does not hold: SWG_ERR_ARG;
+ * a database built from 16-lane batches: SWG_ERR_STATE.  Host only; a call walks the shard's slot table (it is for tests
+ * and read-backs of a few sequences, not a bulk export). */
+int swg_db_sequence(const swg_db *db, uint32_t original_index, int8_t *idx_out, size_t cap, size_t *len);
+
+/* A masked copy of a resident database, made on the device: *out is an ordinary packed, resident ROOT database with
+ * the parent's sequences, order, lengths, offsets and original indices and residue bytes of its own (one more byte
+ * per residue on the host and on the device), in which every masked position holds `replace`; the fill bytes of a
+ * sequence's last dword stay the padding residue.  Every call that takes a swg_db takes it unchanged; hits carry the
+ * parent's original indices, so a caller may search the masked copy and align the hits against the parent (soft
+ * masking).  It shares nothing with the parent: either may be freed first, and nothing the parent planned or tuned
+ * changes.  Three kernels run over the resident bytes (window flags into bitmaps by sliding counts; kept runs, the
+ * widening by W and the counts on 64-bit words; the bytes), then ONE device-to-host copy makes the host image.
+ * Refusals, all before anything is launched: parent a view: SWG_ERR_ARG (mask the root and take the view of the
+ * result); parent not resident on ctx's device, or built from 16-lane batches: SWG_ERR_STATE; parameters out of range:
+ * SWG_ERR_ARG.  A failed allocation leaves nothing behind.  p NULL: the defaults. */
+typedef struct swg_mask_info {
+    swg_mask_params params;
+    uint64_t residues_masked;  /* positions covered */
+    uint64_t sequences_masked; /* sequences with at least one */
+    uint64_t segments;         /* kept runs */
+    double kernel_ms;          /* the kernels, from HIP events */
+    double host_image_ms;      /* the device-to-host copy of the bytes that makes the host image (wall clock) */
+} swg_mask_info;
+int swg_db_mask(swg_ctx *ctx, const swg_db *parent, const swg_mask_params *p, swg_db **out);
+/* What swg_db_mask made `db` with and what it covered (summed on the device); any other database -- one loaded from a
+ * file included, which is an ordinary root whatever it was saved from --: SWG_ERR_STATE. */
+int swg_db_mask_info(const swg_db *db, swg_mask_info *out);
+
 /* ---- multi-GPU merge -------------------------------------------------- */
 
 /* 64-bit sort key of a hit: (score << 32) | (0xFFFFFFFF - index).  Larger key =

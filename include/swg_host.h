@@ -163,6 +163,12 @@ int swg_pssm_from_paths(const int8_t sub[32][32], const double *freq, double pse
  * SWG_ERR_IO when the file cannot be written. */
 int swg_pssm_save(const char *path, const int8_t *pssm, const int8_t *query, size_t lq);
 
+/* swg_seg_mask (include/swg.h) over a whole database laid end to end, in place and on every core: sequence i is
+ * flat[offsets[i] .. offsets[i+1]); masked positions take p->replace (p NULL: the defaults).  What a caller does in
+ * front of swg_db_pack where swg_db_mask cannot be used.  totals NULL, or {positions masked, sequences with any,
+ * kept runs}. */
+int swg_seg_mask_flat(int8_t *flat, const uint64_t *offsets, size_t n, const swg_mask_params *p, uint64_t totals[3]);
+
 /* Threads the host helpers' parallel loops use: the smallest of OpenMP's maximum (OMP_NUM_THREADS),
  * the CPUs this process may run on, and its cgroup CPU quota.  (The reference sizes its loop by
  * omp_get_max_threads() alone, src/alignment_cmdline.c:341-347.) */

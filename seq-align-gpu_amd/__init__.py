@@ -51,6 +51,8 @@ ABI_SYMBOLS = [
     "swg_db_composition", "swg_calibrate", "swg_calibrate_multi", "swg_calibrate_multi_pssm", "swg_evalue", "swg_bitscore",
     "swg_evalue_min_score", "swg_synth_db_iid", "swg_gumbel_fit_hist",
     "swg_matrix_lambda", "swg_pssm_from_paths", "swg_pssm_save", "swg_pssm_build", "swg_pssm_build_multi", "swg_pssm_build_multi_pssm",
+    "swg_mask_params_default", "swg_mask_tables", "swg_seg_mask", "swg_seg_mask_segments", "swg_db_sequence", "swg_db_mask",
+    "swg_db_mask_info", "swg_seg_mask_flat",
 ]
 
 
@@ -105,6 +107,25 @@ class PssmInfo(C.Structure):
 
 
 PSSM_PSEUDOCOUNT_DEFAULT = 10.0
+
+
+class MaskParams(C.Structure):
+    """swg_mask_params: the window, the residue index written, and the two entropy bounds in bits."""
+    _fields_ = [("window", C.c_int32), ("replace", C.c_int32), ("trigger", C.c_double), ("extend", C.c_double)]
+
+
+class MaskInfo(C.Structure):
+    """swg_mask_info: what swg_db_mask made a database with, what it covered, and what it took."""
+    _fields_ = [("params", MaskParams), ("residues_masked", C.c_uint64), ("sequences_masked", C.c_uint64), ("segments", C.c_uint64),
+                ("kernel_ms", C.c_double), ("host_image_ms", C.c_double)]
+
+    def as_dict(self):
+        return {"window": self.params.window, "replace": self.params.replace, "trigger": self.params.trigger,
+                "extend": self.params.extend, "residues_masked": self.residues_masked, "sequences_masked": self.sequences_masked,
+                "segments": self.segments, "kernel_ms": self.kernel_ms, "host_image_ms": self.host_image_ms}
+
+
+MASK_REPLACE_DEFAULT = 24  # swg_letter_index('X')
 
 
 class Stats(C.Structure):
@@ -303,6 +324,15 @@ _sig("swg_pssm_save", C.c_int, [C.c_char_p, _vp, _vp, C.c_size_t])
 _sig("swg_pssm_build", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_double, _vp, _vp, _vp])
 _sig("swg_pssm_build_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, C.c_double, _vp, _vp, _vp])
 _sig("swg_pssm_build_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, C.c_double, _vp, _vp, _vp])
+_sig("swg_mask_params_default", None, [_vp])
+_sig("swg_mask_tables", C.c_int, [_vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)])
+_sig("swg_seg_mask", C.c_int, [_vp, C.c_size_t, _vp, _vp, C.POINTER(C.c_size_t)])
+_sig("swg_seg_mask_segments", C.c_int, [_vp, C.c_size_t, _vp, _vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)])
+_sig("swg_seg_mask_flat", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp])
+_sig("swg_db_sequence", C.c_int, [_vp, C.c_uint32, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
+_sig("swg_db_mask", C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)])
+_sig("swg_db_mask_info", C.c_int, [_vp, _vp])
+_sig("swg_debug_mask_fail_alloc", None, [C.c_int])
 
 
 def _check(rc, ctx=None):
@@ -872,6 +902,48 @@ def topk_merge_keys(keys, k):
     return [(int(out[i].score), int(out[i].index)) for i in range(m)]
 
 
+def mask_params(window=12, trigger=2.2, extend=2.5, replace=MASK_REPLACE_DEFAULT):
+    return MaskParams(int(window), int(replace), float(trigger), float(extend))
+
+
+def mask_tables(window=12, trigger=2.2, extend=2.5, replace=MASK_REPLACE_DEFAULT):
+    """The integers of the masking rule: (T int32[65], threshold of `trigger`, threshold of `extend`) (swg_mask_tables)."""
+    p = mask_params(window, trigger, extend, replace)
+    T = np.zeros(65, dtype=np.int32)
+    t1, t2 = C.c_int64(0), C.c_int64(0)
+    _check(lib.swg_mask_tables(C.byref(p), T.ctypes.data_as(_vp), C.byref(t1), C.byref(t2)))
+    return T, t1.value, t2.value
+
+
+def seg_mask(seq, window=12, trigger=2.2, extend=2.5, replace=MASK_REPLACE_DEFAULT, want_segments=False):
+    """The low-complexity mask of one sequence of table indices (swg_seg_mask, the host twin of Database.mask): a bool
+    array, True where the position is masked; with want_segments also the number of kept runs.  The sequence is not
+    changed: np.where(mask, replace, seq) is what a masked database holds."""
+    a, ap = _i8(seq)
+    p = mask_params(window, trigger, extend, replace)
+    m = np.zeros(max(1, a.size), dtype=np.uint8)
+    nm, ns = C.c_size_t(0), C.c_size_t(0)
+    _check(lib.swg_seg_mask_segments(ap, a.size, C.byref(p), m.ctypes.data_as(_vp), C.byref(nm), C.byref(ns)))
+    mask = m[:a.size].astype(bool)
+    assert int(mask.sum()) == nm.value
+    return (mask, ns.value) if want_segments else mask
+
+
+def debug_mask_fail_alloc(n):
+    """Test hook: the n-th device allocation of the next Database.mask finds no memory (0 disarms)."""
+    lib.swg_debug_mask_fail_alloc(int(n))
+
+
+def seg_mask_flat(flat, offsets, window=12, trigger=2.2, extend=2.5, replace=MASK_REPLACE_DEFAULT):
+    """swg_seg_mask over a whole database laid end to end, on every core -> (masked copy of flat, {counts})."""
+    a = np.array(flat, dtype=np.int8, order="C")
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    p = mask_params(window, trigger, extend, replace)
+    tot = np.zeros(3, dtype=np.uint64)
+    _check(lib.swg_seg_mask_flat(a.ctypes.data_as(_vp), off.ctypes.data_as(_vp), off.size - 1, C.byref(p), tot.ctypes.data_as(_vp)))
+    return a, {"residues_masked": int(tot[0]), "sequences_masked": int(tot[1]), "segments": int(tot[2])}
+
+
 # ---------------------------------------------------------------------------
 # database + context
 # ---------------------------------------------------------------------------
@@ -1092,6 +1164,33 @@ class Database:
         counts = np.zeros(32, dtype=np.uint64)
         _check(lib.swg_db_composition(ctx.handle, self.handle, counts.ctypes.data_as(_vp)), ctx.handle)
         return counts
+
+    def mask(self, ctx, window=12, trigger=2.2, extend=2.5, replace=MASK_REPLACE_DEFAULT):
+        """A masked copy of this resident root database, made on the device (swg_db_mask): the same sequences, order
+        and original indices, with `replace` at every position of a low-complexity region.  A Database of its own."""
+        p = mask_params(window, trigger, extend, replace)
+        h = _vp()
+        _check(lib.swg_db_mask(ctx.handle, self.handle, C.byref(p), C.byref(h)), ctx.handle)
+        m = Database.__new__(Database)
+        m.handle = h
+        return m
+
+    def mask_info(self):
+        """What Database.mask made this database with and what it covered (swg_db_mask_info)."""
+        info = MaskInfo()
+        _check(lib.swg_db_mask_info(self.handle, C.byref(info)))
+        return info.as_dict()
+
+    def sequence(self, i):
+        """The table indices of the sequence with ORIGINAL index i, from the host image (swg_db_sequence)."""
+        n = C.c_size_t(0)
+        rc = lib.swg_db_sequence(self.handle, int(i), None, 0, C.byref(n))
+        if rc != SWG_OK and n.value == 0:
+            _check(rc)
+        out = np.zeros(n.value, dtype=np.int8)
+        if n.value:
+            _check(lib.swg_db_sequence(self.handle, int(i), out.ctypes.data_as(_vp), out.size, C.byref(n)))
+        return out
 
     def save(self, path):
         _check(lib.swg_db_save(self.handle, path.encode()))

@@ -163,6 +163,9 @@ struct swg_db {
     // a database whose pair tokens were built straight from reference-shaped 16-lane batches
     // (swg_fill_batches16): there are no residue bytes by sorted rank, so nothing that needs them can run
     bool tokens_only = false;
+    // a masked copy (swg_db_mask): what it was made with and what the kernels covered (swg_db_mask_info)
+    bool masked = false;
+    swg_mask_info mask_info = {};
     // A view (swg_db_view): a database of its own whose slots are some of `root`'s sequences.  Its residue bytes are the
     // root's on the host and on the device -- codes is empty, code_off[s] is the ROOT's byte offset of slot s's sequence
     // (so consecutive slots are not adjacent in memory: a sequence ends at code_off[s] + its length, never at

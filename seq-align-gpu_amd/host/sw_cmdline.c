@@ -135,7 +135,15 @@ static void usage(const char *argv0, const char *err)
             "    --out_pssm <file>    with --iterations: write the last PSSM (readable by --pssm)\n"
             "    --prefilter <N>      with --topk K: per query (every record with --allqueries) the N best entries by gapless\n"
             "                         score are searched with gaps and the K best of those reported (--align: aligned);\n"
-            "                         no Entry lines are printed; not with --gpus, --candidates or --gapless\n",
+            "                         no Entry lines are printed; not with --gpus, --candidates or --gapless\n"
+            "    --maskdb [W,K1,K2]   mask the low-complexity regions of the database on the GPU, after the upload or the --packed\n"
+            "                         load: windows of W residues [12] whose entropy is at most K2 bits [2.5] form runs, a run with\n"
+            "                         a window of at most K1 bits [2.2] is masked with X (SEG's trigger and extension stages); every\n"
+            "                         stage then reads the masked copy, and --savedb writes it; one GPU: not with --gpus N > 1\n"
+            "    --softmask           with --prefilter N: only the gapless prefilter reads the masked copy (--maskdb's parameters, or the\n"
+            "                         defaults); the gapped search of the candidates and the alignments read the database as it is\n"
+            "    --maskquery          mask every query record the same way on the host before it is searched; not with --pssm or\n"
+            "                         --pssmlist\n",
             argv0);
     exit(EXIT_FAILURE);
 }
@@ -260,6 +268,19 @@ static int evalue_scores(swg_ctx *ctx, const swg_seqs *q, size_t n_rec, const in
     return 1;
 }
 
+/* --maskquery: the masked positions of a query record take the replacement residue */
+static int mask_query(int8_t *idx, size_t n, const swg_mask_params *mp)
+{
+    uint8_t *m = (uint8_t *)malloc(n ? n : 1);
+    size_t n_masked = 0;
+    if (!m) return SWG_ERR_NOMEM;
+    const int rc = swg_seg_mask(idx, n, mp, m, &n_masked);
+    for (size_t i = 0; rc == SWG_OK && n_masked && i < n; i++)
+        if (m[i]) idx[i] = (int8_t)mp->replace;
+    free(m);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     swg_scoring sc;
@@ -273,6 +294,9 @@ int main(int argc, char **argv)
     long iterations = 0, maxincluded = 500;
     int have_inclusion = 0, have_maxincluded = 0;
     const char *out_pssm = NULL;
+    int maskdb = 0, softmask = 0, maskquery = 0;
+    swg_mask_params mp;
+    swg_mask_params_default(&mp);
     if (argc == 1) usage(argv[0], NULL);
     for (int i = 1; i < argc; i++)
         if (!strcasecmp(argv[i], "--help") || !strcasecmp(argv[i], "-help") || !strcasecmp(argv[i], "-h"))
@@ -303,6 +327,25 @@ int main(int argc, char **argv)
             timing = 1;
         } else if (!strcasecmp(a, "--allqueries")) {
             allq = 1;
+        } else if (!strcasecmp(a, "--softmask")) {
+            softmask = 1;
+        } else if (!strcasecmp(a, "--maskquery")) {
+            maskquery = 1;
+        } else if (!strcasecmp(a, "--maskdb")) {
+            maskdb = 1;
+            /* the parameters are optional: W,K1,K2 in one argument that starts with a digit and holds a comma */
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' && strchr(argv[i + 1], ',')) {
+                long w = 0;
+                double k1 = 0.0, k2 = 0.0;
+                char tail = 0;
+                int32_t T[65];
+                int64_t t1, t2;
+                const int got = sscanf(argv[i + 1], "%ld,%lf,%lf%c", &w, &k1, &k2, &tail);
+                if (got == 3 && w >= INT_MIN && w <= INT_MAX) mp.window = (int32_t)w, mp.trigger = k1, mp.extend = k2;
+                if (got != 3 || swg_mask_tables(&mp, T, &t1, &t2) != SWG_OK)
+                    usage(argv[0], "Invalid --maskdb argument: W,K1,K2 with a window W of 4..64 residues and 0 <= K1 <= K2 bits");
+                i++;
+            }
         } else if (i == argc - 1) {
             char msg[256];
             snprintf(msg, sizeof msg, "Unknown argument without parameter: %s", a);
@@ -413,6 +456,11 @@ int main(int argc, char **argv)
     if (iterations && cand_path) usage(argv[0], "--iterations makes its own lists of included entries: it does not combine with --candidates");
     if (iterations && prefilter) usage(argv[0], "--iterations makes its own lists of included entries: it does not combine with --prefilter");
     if (iterations && gapless) usage(argv[0], "--iterations builds its PSSM from gapped alignments: it does not combine with --gapless");
+    if (softmask && !prefilter) usage(argv[0], "--softmask masks what the gapless prefilter reads: give --prefilter N");
+    if (softmask) maskdb = 1;
+    if (maskdb && gpus > 1) usage(argv[0], "--maskdb works with one GPU (--gpu): it does not combine with --gpus N > 1");
+    if (maskquery && (pssm_path || pssmlist_path)) usage(argv[0], "--maskquery masks residues: it does not combine with --pssm or --pssmlist");
+    if (maskdb && gpus == 1) gpus = 0; /* (one GPU either way: the copy is made on a context) */
     if (iterations && gpus == 1) gpus = 0; /* (one GPU either way: the iterations run on a context, not on a group of one) */
     /* --evalue: the searches of --minscore (one query) or of --minscorelist (every record) at scores the calibration gives;
      * until it has run, 1 stands for them */
@@ -759,6 +807,10 @@ int main(int argc, char **argv)
     const int8_t *pssm0 = pssm ? pssm : plist; /* the first record's PSSM, if any */
     int8_t *iter_pssm = NULL;                  /* --iterations: the PSSM of the last iteration that built one (then pssm0) */
     swg_query_sanitize(&sc, qidx, lq); /* reference src/alignment_cmdline.c:391-396 */
+    if (maskquery && mask_query(qidx, lq, &mp) != SWG_OK) {
+        fprintf(stderr, "Error: %s\n", swg_global_error());
+        return leave(EXIT_FAILURE);
+    }
     if (!packed && swg_seqs_to_indices(&db, didx, &bad) != SWG_OK) die_illegal(bad);
 
     phase("letters to table indices");
@@ -776,6 +828,8 @@ int main(int argc, char **argv)
     swg_ctx *ctx = NULL;
     swg_group *grp = NULL;
     swg_db *sdb = NULL; /* what is searched: the database, or with --seqidlist the view of its listed entries */
+    swg_db *mdb = NULL; /* --softmask: the masked copy, */
+    swg_db *gdb = NULL; /* ... and what the gapless prefilter reads: the copy, or with --seqidlist the view of its listed entries */
     /* --minscore --gpus N: a context, a shard and what is searched of it per GPU; sh_of[i] = the shard hit i came from */
     size_t sh_n = 0;
     swg_ctx **sh_ctx = NULL;
@@ -927,7 +981,7 @@ int main(int argc, char **argv)
         if (rc == SWG_OK) rc = swg_set_option(ctx, "autotune", 0);
         if (rc == SWG_OK) rc = swg_set_scoring(ctx, (const int8_t(*)[32])sc.sub, sc.gap_open, sc.gap_extend);
         if (rc == SWG_OK) rc = pssm0 ? swg_set_query_pssm(ctx, pssm0, lq) : swg_set_query(ctx, qidx, lq);
-        if (rc == SWG_OK && savedb) {
+        if (rc == SWG_OK && savedb && !(maskdb && !softmask)) {
             if (swg_db_save(pdb, savedb) != SWG_OK) {
                 fprintf(stderr, "Error: %s\n", swg_global_error());
                 return leave(EXIT_FAILURE);
@@ -936,10 +990,40 @@ int main(int argc, char **argv)
         }
         if (rc == SWG_OK) rc = swg_db_upload(ctx, pdb);
         phase("upload");
+        if (rc == SWG_OK && maskdb) {
+            swg_mask_info mi;
+            rc = swg_db_mask(ctx, pdb, &mp, &mdb);
+            if (rc == SWG_OK && swg_db_mask_info(mdb, &mi) == SWG_OK) {
+                fprintf(stderr, "masked %llu residues in %llu of %lu entries (%llu regions; window %d, %g / %g bits)\n",
+                        (unsigned long long)mi.residues_masked, (unsigned long long)mi.sequences_masked, (unsigned long)swg_db_count(mdb),
+                        (unsigned long long)mi.segments, (int)mp.window, mp.trigger, mp.extend);
+                if (timing)
+                    fprintf(stderr, "[timing] %-28s %9.2f ms of kernels, %.2f ms for the host image\n", "mask the database", mi.kernel_ms,
+                            mi.host_image_ms);
+            }
+            if (rc == SWG_OK && !softmask) { /* every stage reads the masked copy */
+                swg_db_free(pdb);
+                pdb = mdb;
+                mdb = NULL;
+                if (savedb) {
+                    if (swg_db_save(pdb, savedb) != SWG_OK) {
+                        fprintf(stderr, "Error: %s\n", swg_global_error());
+                        return leave(EXIT_FAILURE);
+                    }
+                    fprintf(stderr, "packed database (masked) written to %s\n", savedb);
+                }
+            }
+            phase("mask the database");
+        }
         sdb = pdb;
         if (rc == SWG_OK && ids) {
             rc = swg_db_view(ctx, pdb, ids, n_ids, &sdb);
             phase("select the listed entries");
+        }
+        gdb = sdb;
+        if (rc == SWG_OK && mdb) { /* --softmask: the same selection of the masked copy */
+            gdb = mdb;
+            if (ids) rc = swg_db_view(ctx, mdb, ids, n_ids, &gdb);
         }
         if (rc == SWG_OK && iterations) { /* every iteration but the last: calibrate, include, build the PSSM, make it the query */
             uint64_t counts[32];
@@ -1002,6 +1086,7 @@ int main(int argc, char **argv)
                         ev_qx[c] = (int8_t)ix;
                     }
                     swg_query_sanitize(&sc, ev_qx + q.seq_off[r], (size_t)(q.seq_off[r + 1] - q.seq_off[r]));
+                    if (maskquery && mask_query(ev_qx + q.seq_off[r], (size_t)(q.seq_off[r + 1] - q.seq_off[r]), &mp) != SWG_OK) return leave(EXIT_FAILURE);
                 }
             }
             if (rc == SWG_OK) {
@@ -1019,7 +1104,7 @@ int main(int argc, char **argv)
             pf_hits = (swg_hit *)calloc(pf_n ? pf_n : 1, sizeof *pf_hits);
             size_t got = 0;
             if (!pf_hits) return leave(EXIT_FAILURE);
-            rc = swg_search_gapless(ctx, sdb, NULL, pf_hits, pf_n, &got, NULL);
+            rc = swg_search_gapless(ctx, gdb, NULL, pf_hits, pf_n, &got, NULL);
             for (size_t i = 0; rc == SWG_OK && i < got; i++) cands[i] = pf_hits[i].index;
             c_off[1] = got;
             free(pf_hits);
@@ -1270,6 +1355,7 @@ next_query:
                     qx[qoff[i] + c] = (int8_t)v;
                 }
                 swg_query_sanitize(&sc, qx + qoff[i], lqi);
+                if (maskquery && mask_query(qx + qoff[i], lqi, &mp) != SWG_OK) return leave(EXIT_FAILURE);
             }
             swg_stats st;
             memset(&st, 0, sizeof st);
@@ -1281,9 +1367,9 @@ next_query:
                 pf_hits = (swg_hit *)calloc(chunk_n * (pf_n ? pf_n : 1), sizeof *pf_hits);
                 pf_nhits = (size_t *)calloc(chunk_n, sizeof *pf_nhits);
                 if (!pf_hits || !pf_nhits) return leave(EXIT_FAILURE);
-                rc = plist ? swg_search_gapless_multi_pssm(ctx, sdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff, chunk_n, NULL,
+                rc = plist ? swg_search_gapless_multi_pssm(ctx, gdb, plist + (size_t)q.seq_off[chunk_first] * 32, qoff, chunk_n, NULL,
                                                            pf_hits, pf_n, pf_nhits, NULL)
-                           : swg_search_gapless_multi(ctx, sdb, qx, qoff, chunk_n, NULL, pf_hits, pf_n, pf_nhits, NULL);
+                           : swg_search_gapless_multi(ctx, gdb, qx, qoff, chunk_n, NULL, pf_hits, pf_n, pf_nhits, NULL);
                 if (rc != SWG_OK) {
                     fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
                     return leave(EXIT_FAILURE);
@@ -1415,6 +1501,8 @@ next_query:
         fflush(stderr);
         _exit(leave(EXIT_SUCCESS));
     }
+    if (gdb != sdb && gdb != mdb) swg_db_free(gdb);
+    swg_db_free(mdb);
     if (sdb != pdb) swg_db_free(sdb);
     swg_db_free(pdb);
     swg_destroy(ctx);
