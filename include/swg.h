@@ -295,8 +295,9 @@ int swg_search_end(swg_ctx *ctx, int ticket, int32_t *scores_out, swg_hit *topk_
  * 1: the sum of the residues' best scores, above.  4 | 5: the sum, over consecutive blocks of 4 | 5 rows of the
  * sequence, of each block's own local score against the whole query -- never above the first, never below the
  * sequence's score -- read from a table of every block of residue classes, which is built on the
- * device in front of the first pruned search of a (query, scoring): 22^k x k x lq cell updates, 17 ms at k = 5 for
- * 3000 columns on an MI355X, paid once per query.  0: automatic, the largest k whose table costs at most half of what
+ * device in front of the first pruned search of a (query, scoring): 22^4 x 4 x lq cell updates at k = 4, 22^4 x 26 x lq
+ * at k = 5 (the 22 blocks behind four classes share those four rows), 4 ms at k = 5 for 3000 columns on an MI355X, paid
+ * once per query.  0: automatic, the largest k whose table costs at most half of what
  * its tighter cut is expected to save on this range (small databases: 1).  "prune_segments" (default 0): the k-mer
  * bound's table holds, per block, its best cell within each of 1..32 consecutive segments of the query's columns, and
  * a sequence's blocks are taken in order -- a later block cannot score in an earlier segment; 1 is the
@@ -311,7 +312,14 @@ int swg_search_end(swg_ctx *ctx, int ticket, int32_t *scores_out, swg_hit *topk_
  * bounded a third time over a k = 4 table of 256 segments, and the least bound holds; 256 on, behind whatever the second
  * level is; 1 off; 0 automatic -- on where the second level was chosen automatically and took 128, the tables hold
  * bytes (below) and the range is large enough for the finer cut to pay for its table and its walk twice over (the
- * 10M-sequence database: yes; a database of thousands or a few million sequences: no).  "prune_table_bits" (default 0):
+ * 10M-sequence database: yes; a database of thousands or a few million sequences: no).  "prune_refine4" (default 0):
+ * the pairs that still reach the threshold after the third level are bounded a fourth time over a table of 5-residue
+ * blocks in 256 segments (22^5 x 256 bytes = 1.32 GB of device memory, built in about 5 ms per query of 3000 columns), and
+ * the least bound holds; 5256 on, behind whatever the other levels are; 1 off; 0 automatic -- on where the third level
+ * was chosen automatically and the range is large enough (the 10M-sequence database: yes; smaller ones: no).  The table
+ * holds bytes only: a query whose blocks of 5 can score above 255 (a PSSM entry of 52 or more) is searched without the
+ * level under every value, and so is every search of a context whose device had no room for the table -- neither is an
+ * error.  "prune_table_bits" (default 0):
  * the width of the k-mer tables' entries.  0: bytes wherever k x the largest score of the query's profile is at most 255
  * (every entry fits: BLOSUM62 44, PAM250 68 at k = 4), uint16_t otherwise (a PSSM with an entry of 64 or more); 16:
  * uint16_t always.  A byte table holds the same values in half the memory and gather traffic.  Hits, bounds and lists are

@@ -305,8 +305,13 @@ _sig("swg_debug_prune_refine_read", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, 
 _sig("swg_debug_prune_stages3", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 _sig("swg_debug_prune_kmer_refine3", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp])
 _sig("swg_debug_prune_refine3_choice", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_kmer_refine4", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp])
 _sig("swg_debug_prune_table_bits", C.c_int, [_vp, _vp, C.c_size_t, C.c_int])
 _sig("swg_debug_prune_tables", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_tables4", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_refine4_read", C.c_int, [_vp, _vp, C.c_size_t, _vp])
+_sig("swg_debug_prune_refine4_choice", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_stages4", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 _sig("swg_debug_list_deal", C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 _sig("swg_debug_calib_iters", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 _sig("swg_db_composition", C.c_int, [_vp, _vp, _vp])
@@ -726,6 +731,25 @@ def debug_prune_kmer_refine(rows, query, gap_open, gap_extend, segments, flat, o
                               (KMER_CLASSES ** 4, S) if table and S in (32, 64, 128, 256) else None)
 
 
+def debug_prune_kmer_refine4(rows, query, gap_open, gap_extend, segments, flat, offsets):
+    """Test hook (no device needed): the fourth-level bound's host mirror -- k = 5 over `segments` (128 or 256) segments,
+    the blocks taken as debug_prune_kmer takes k = 5.  There is no table (22^5 x 256 entries): the mirror computes the
+    entries of the blocks the sequences hold.  -> U uint64[n]."""
+    r, rp = _i8(rows)
+    lq = r.size // 32
+    qp = None
+    if query is not None:
+        q, qp = _i8(query)
+        lq = q.size
+    f, fp = _i8(flat)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = off.size - 1
+    u = np.zeros(max(n, 1), dtype=np.uint64)
+    _check(lib.swg_debug_prune_kmer_refine4(rp, qp, lq, int(gap_open), int(gap_extend), int(segments), fp, off.ctypes.data_as(_vp), n,
+                                            u.ctypes.data_as(_vp)))
+    return u[:n]
+
+
 def debug_prune_table_bits(rows, query, k=4):
     """Test hook (no device needed): the width of the k-mer tables' entries for this query (rows / query as
     debug_prune_bound takes them) at k = 4 or 5 under option prune_table_bits = 0 -> 8 where k x the largest colmax entry
@@ -750,6 +774,20 @@ def debug_prune_refine3_choice(forced=0, segments=0, refine=0, refine3=0, table_
     out = np.zeros(4, dtype=np.int64)
     _check(lib.swg_debug_prune_refine3_choice(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
     return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+
+KMER_REFINE4_SEGMENTS = 256   # the fourth level's, of the k = 5 table
+PRUNE_REFINE4_FORCED = 5256   # option "prune_refine4": (k, S) = (5, 256) as 1000 k + S
+
+
+def debug_prune_refine4_choice(forced=0, segments=0, refine=0, refine3=0, refine4=0, table_bits=8, table_bits5=8, pruned=1, lq=3000,
+                               pair_rows=1900000000, table_rate=0, fill_rate=0):
+    """Test hook (no device needed): debug_prune_refine3_choice with option prune_refine4 and the k = 5 tables' entry width
+    -> (k, S, S2, S3, S4): S4 = 256 with a fourth level, 0 without."""
+    a = np.array([forced, pruned, lq, pair_rows, table_rate, fill_rate, segments, refine, refine3, table_bits, refine4, table_bits5], dtype=np.int64)
+    out = np.zeros(5, dtype=np.int64)
+    _check(lib.swg_debug_prune_refine4_choice(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
+    return tuple(int(v) for v in out)
 
 
 def debug_prune_refine_choice(forced=0, segments=0, refine=0, pruned=1, lq=3000, pair_rows=1900000000, table_rate=0, fill_rate=0):
@@ -823,18 +861,18 @@ def debug_above_multi_route(option=0, admitted=True, single_pruned=False):
 
 # a stage's fourth word: (bit, name) in queue order (the third level's walk is bit 5, queued between the second's and the list)
 PRUNE_STAGE_QUEUED = ("threshold", "prefix_cut", "gate", "refine", "list")
-_PRUNE_STAGE_BITS = ((0, "threshold"), (1, "prefix_cut"), (2, "gate"), (3, "refine"), (5, "refine3"), (4, "list"))
+_PRUNE_STAGE_BITS = ((0, "threshold"), (1, "prefix_cut"), (2, "gate"), (3, "refine"), (5, "refine3"), (6, "refine4"), (4, "list"))
 
 
-def debug_prune_stages(segments, head_pairs=0, fixed=False, refine=0, prefix_cut=False, refine3=0):
+def debug_prune_stages(segments, head_pairs=0, fixed=False, refine=0, prefix_cut=False, refine3=0, refine4=0):
     """Test hook (no device needed): the stages of a pruned fill over the pair ranges `segments` [(begin, end), ...] and
     what is queued in front of each (swg_prune_stages) -> [(begin, end, segment index, names in queue order: those of
-    PRUNE_STAGE_QUEUED, and "refine3" in front of "list"), ...].  head_pairs, fixed (a caller's threshold), refine and
-    refine3 (the second and third levels' segments, 0: none) and prefix_cut are the plan's."""
-    a = np.array([head_pairs, fixed, refine, prefix_cut, refine3, len(segments)] + [int(v) for sg in segments for v in sg], dtype=np.int64)
+    PRUNE_STAGE_QUEUED, and "refine3" then "refine4" in front of "list"), ...].  head_pairs, fixed (a caller's threshold),
+    refine, refine3 and refine4 (the second, third and fourth levels' segments, 0: none) and prefix_cut are the plan's."""
+    a = np.array([head_pairs, fixed, refine, prefix_cut, refine3, refine4, len(segments)] + [int(v) for sg in segments for v in sg], dtype=np.int64)
     out = np.zeros((2 * len(segments) + 1, 4), dtype=np.int64)
     n = C.c_size_t(0)
-    _check(lib.swg_debug_prune_stages3(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp), out.shape[0], C.byref(n)))
+    _check(lib.swg_debug_prune_stages4(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp), out.shape[0], C.byref(n)))
     return [(int(b), int(e), int(sg), tuple(name for i, name in _PRUNE_STAGE_BITS if int(qd) >> i & 1))
             for b, e, sg, qd in out[:n.value]]
 
@@ -1701,6 +1739,22 @@ class Context:
         _check(lib.swg_debug_prune_tables(self.handle, out.ctypes.data_as(_vp)), self.handle)
         return {"refine3": int(out[0]), "refine3_builds": int(out[1]),
                 "bits": dict(zip(("first4", "first5", "second", "third"), (int(v) for v in out[2:6]))), "auto_bits": int(out[6])}
+
+    def debug_prune_tables4(self):
+        """Test hook: the fourth level (swg_debug_prune_tables4) -> dict: refine4 (S4 of the search last begun, 0: none),
+        refine4_builds, bits (of the fourth table if it holds the current query and scoring, else 0), refused (its
+        allocation failed once on this context)."""
+        out = np.zeros(4, dtype=np.int64)
+        _check(lib.swg_debug_prune_tables4(self.handle, out.ctypes.data_as(_vp)), self.handle)
+        return {"refine4": int(out[0]), "refine4_builds": int(out[1]), "bits": int(out[2]), "refused": bool(out[3])}
+
+    def debug_prune_refine4_read(self, blocks):
+        """Test hook: rows of the fourth level's table -> uint16[len(blocks), 256]: the entries of the class blocks
+        `blocks` (indices below 22^5, first class most significant)."""
+        b = np.ascontiguousarray(blocks, dtype=np.uint32)
+        out = np.zeros((max(b.size, 1), KMER_REFINE4_SEGMENTS), dtype=np.uint16)
+        _check(lib.swg_debug_prune_refine4_read(self.handle, b.ctypes.data_as(_vp), b.size, out.ctypes.data_as(_vp)), self.handle)
+        return out[:b.size]
 
     def debug_bounds_last(self):
         """What the last align_bounds* call of this context did (swg_debug_bounds_last) -> dict: pairs on the bounds kernel,

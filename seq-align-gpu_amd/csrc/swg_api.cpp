@@ -261,6 +261,7 @@ extern "C" void swg_destroy(swg_ctx *ctx)
     (void)hipFree(ctx->kmer_first[1].d);
     (void)hipFree(ctx->kmer_second.d);
     (void)hipFree(ctx->kmer_third.d);
+    (void)hipFree(ctx->kmer_fourth.d);
     (void)hipFree(ctx->d_profile[0]);
     (void)hipFree(ctx->d_profile[1]);
     (void)hipFree(ctx->d_profile[2]);
@@ -374,6 +375,10 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
         if (!swg_prune_refine3_value_ok(value))
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_refine3 must be 0 (auto), 1 (off) or 256 (the segments of the third-level bound's table)");
         ctx->opt_prune_refine3 = value;
+    } else if (!strcmp(key, "prune_refine4")) {
+        if (!swg_prune_refine4_value_ok(value))
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_refine4 must be 0 (auto), 1 (off) or 5256 (the fourth-level bound's table: k = 5 in 256 segments)");
+        ctx->opt_prune_refine4 = value;
     } else if (!strcmp(key, "prune_table_bits")) {
         if (value != 0 && value != 16)
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_table_bits must be 0 (auto: bytes where they hold every entry) or 16");
@@ -1308,6 +1313,10 @@ static int enqueue_pruned_fill(swg_ctx *ctx, swg_db *db, const SwgPrunePlan &pr,
         if (st.queued & SWG_STAGE_REFINE3)
             HIP_TRY(ctx, swg_launch_pair_bound_refine(T.d_tok, T.d_pair_off, st.begin, st.end, (uint32_t)pr.refine3, ctx->prune_colmax, ctx->kmer_third.d,
                                                       ctx->kmer_third.bits, st.queued & SWG_STAGE_GATE ? gate : thr, L.bounds, qs));
+        // (the fourth: blocks of 5 over the pairs every k = 4 level has left at or above that word)
+        if (st.queued & SWG_STAGE_REFINE4)
+            HIP_TRY(ctx, swg_launch_pair_bound_refine(T.d_tok, T.d_pair_off, st.begin, st.end, (uint32_t)pr.refine4, ctx->prune_colmax, ctx->kmer_fourth.d,
+                                                      ctx->kmer_fourth.bits, st.queued & SWG_STAGE_GATE ? gate : thr, L.bounds, qs, 5));
         if (st.queued & SWG_STAGE_LIST) {
             const size_t rec = db->prune_stages.size() / 2;
             HIP_TRY(ctx, swg_launch_prune_list(L.bounds, T.d_pair_off, st.begin, st.end, thr, L.tiles, L.lists + st.begin, cut_word,
@@ -2411,8 +2420,10 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
     ka.forced_segments = ctx->opt_prune_segments;
     ka.forced_refine = ctx->opt_prune_refine;
     ka.forced_refine3 = ctx->opt_prune_refine3;
+    ka.forced_refine4 = ctx->opt_prune_refine4;
     ensure_prune_colmax(ctx);
     ka.table_bits = kmer_table_bits(ctx, 4);
+    ka.table_bits5 = kmer_table_bits(ctx, 5);
     ka.pruned = true;
     ka.lq = ctx->query_len();
     ka.pair_rows = 4ull * (db->ptok.pair_blocks_prefix[wk.pair_end[0]] - db->ptok.pair_blocks_prefix[wk.pair_begin[0]]);
@@ -2422,7 +2433,11 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
     P->prune.prefix_cut = ctx->opt_prune_cut == 1 && !P->prune.fixed; // (a caller's threshold takes the list)
     P->prune.refine = P->prune.prefix_cut ? 0 : swg_prune_refine_choice(ka, P->prune.kmer, P->prune.segments);
     P->prune.refine3 = P->prune.prefix_cut ? 0 : swg_prune_refine3_choice(ka, P->prune.kmer, P->prune.segments, P->prune.refine);
-    ctx->prune_choice = SwgPruneChoice{P->prune.kmer, P->prune.segments, P->prune.refine, P->prune.refine3};
+    // (a context whose fourth table could not be allocated searches without the level: reserve_kmer_fourth)
+    P->prune.refine4 = P->prune.prefix_cut || ctx->kmer_fourth_refused
+                           ? 0
+                           : swg_prune_refine4_choice(ka, P->prune.kmer, P->prune.segments, P->prune.refine, P->prune.refine3);
+    ctx->prune_choice = SwgPruneChoice{P->prune.kmer, P->prune.segments, P->prune.refine, P->prune.refine3, P->prune.refine4};
     return SWG_OK;
 }
 
@@ -2446,8 +2461,31 @@ static int ensure_kmer_table(swg_ctx *ctx, SwgKmerTable *t, int k, int S)
     HIP_TRY(ctx, swg_launch_kmer_table(ctx->d_sub, ctx->d_query, ctx->query_pssm ? ctx->d_pssm : nullptr, (uint32_t)lq, (uint32_t)-go, (uint32_t)-ge, k,
                                        (uint32_t)S, ctx->d_kmer_cprof, t->d, bits, ctx->stream));
     t->epoch = ctx->epoch, t->k = k, t->segments = S, t->bits = bits;
-    ++(t == &ctx->kmer_third ? ctx->kmer_refine3_builds : t == &ctx->kmer_second ? ctx->kmer_refine_builds : ctx->kmer_builds);
+    ++(t == &ctx->kmer_fourth  ? ctx->kmer_refine4_builds
+       : t == &ctx->kmer_third ? ctx->kmer_refine3_builds
+       : t == &ctx->kmer_second ? ctx->kmer_refine_builds
+                                : ctx->kmer_builds);
     return SWG_OK;
+}
+
+// The fourth level's table is 1.32 GB: its buffer is allocated in front of the search that first wants it, and an
+// allocation that fails is no error -- the search, and every later one of this context, runs without the level (the
+// capacity is written only once the buffer stands).  -> whether the buffer stands.
+static bool reserve_kmer_fourth(swg_ctx *ctx)
+{
+    SwgKmerTable *t = &ctx->kmer_fourth;
+    const size_t bytes = (size_t)swg_kmer_entries(5) * SWG_KMER_REFINE4_SEGMENTS;
+    if (t->d && t->cap >= bytes) return true;
+    (void)hipFree(t->d);
+    t->d = nullptr, t->cap = 0, t->epoch = 0;
+    uint8_t *d = nullptr;
+    if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&d, bytes) != hipSuccess) {
+        (void)hipGetLastError(); // (taken: the search goes on)
+        ctx->kmer_fourth_refused = true;
+        return false;
+    }
+    t->d = d, t->cap = bytes;
+    return true;
 }
 
 // What a pruned search reads besides the fill's own: the colmax table for the current query and scoring (built on the
@@ -2473,6 +2511,11 @@ static int prepare_prune(swg_ctx *ctx, swg_db *db, const SwgPrunePlan &pr)
     if (pr.refine3) {
         if (pr.refine3 != 256) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the third-level bound's table: %d segments (256)", pr.refine3);
         if ((rc = ensure_kmer_table(ctx, &ctx->kmer_third, 4, pr.refine3)) != SWG_OK) return rc;
+    }
+    if (pr.refine4) {
+        if (pr.refine4 != (int)SWG_KMER_REFINE4_SEGMENTS || !swg_kmer_refine4_admitted(kmer_table_bits(ctx, 5)))
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the fourth-level bound's table: %d segments (256) of bytes", pr.refine4);
+        if ((rc = ensure_kmer_table(ctx, &ctx->kmer_fourth, 5, pr.refine4)) != SWG_OK) return rc;
     }
     swg_db::Bufs &b = db->bufs[ctx->cur - ctx->slots];
     const size_t n_pairs = (size_t)swg_db_pair_count(db);
@@ -2686,6 +2729,7 @@ static int search_begin(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, bo
     if (db->n_bins == 0) return SWG_OK;
     if ((rc = plan_search(ctx, db, allow_autotune, &S->plan)) != SWG_OK) return rc;
     if ((rc = plan_prune(ctx, db, want_scores, k, &S->plan)) != SWG_OK) return rc;
+    if (S->plan.prune.refine4 && !reserve_kmer_fourth(ctx)) S->plan.prune.refine4 = 0, ctx->prune_choice.refine4 = 0;
     if ((rc = prepare_search(ctx, db, S->plan)) != SWG_OK) return rc;
     if ((rc = enqueue_fill(ctx, db, S->plan, S)) != SWG_OK) return rc;
     if ((rc = enqueue_rescore(ctx, db, S->plan, S)) != SWG_OK) return rc;
@@ -3015,6 +3059,36 @@ extern "C" int swg_debug_prune_tables(swg_ctx *ctx, int64_t *out)
     if (ctx->query_len() > 0) {
         ensure_prune_colmax(ctx);
         out[6] = swg_kmer_table_bits(ctx->prune_colmax, 4);
+    }
+    return SWG_OK;
+}
+
+// ... the fourth level: out[0..3] = S4 of the search last begun (0: no fourth level), fourth-level builds so far, the
+// entry bits of the fourth table if it holds the current query and scoring (0: not), whether its allocation was refused
+extern "C" int swg_debug_prune_tables4(swg_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_tables4: NULL argument");
+    out[0] = ctx->prune_choice.refine4;
+    out[1] = (int64_t)ctx->kmer_refine4_builds;
+    out[2] = ctx->kmer_fourth.d && ctx->kmer_fourth.epoch == ctx->epoch ? ctx->kmer_fourth.bits : 0;
+    out[3] = ctx->kmer_fourth_refused ? 1 : 0;
+    return SWG_OK;
+}
+// ... and n rows of its table: out[i][0..256) = the entries of class block blocks[i] (< 22^5), an error unless the table
+// holds the current query and scoring
+extern "C" int swg_debug_prune_refine4_read(swg_ctx *ctx, const uint32_t *blocks, size_t n, uint16_t *out)
+{
+    if (!ctx || (n > 0 && (!blocks || !out))) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_refine4_read: NULL argument");
+    const SwgKmerTable &t = ctx->kmer_fourth;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    if (!t.holds(ctx->epoch, 5, (int)SWG_KMER_REFINE4_SEGMENTS, 8))
+        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_refine4_read: no fourth-level table for the current query and scoring");
+    uint8_t row[SWG_KMER_REFINE4_SEGMENTS];
+    for (size_t i = 0; i < n; ++i) {
+        if (blocks[i] >= swg_kmer_entries(5)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_refine4_read: block %u", blocks[i]);
+        HIP_TRY(ctx, hipMemcpy(row, t.d + (size_t)blocks[i] * SWG_KMER_REFINE4_SEGMENTS, sizeof row, hipMemcpyDeviceToHost));
+        std::copy(row, row + SWG_KMER_REFINE4_SEGMENTS, out + i * SWG_KMER_REFINE4_SEGMENTS);
     }
     return SWG_OK;
 }

@@ -698,6 +698,7 @@ std::vector<SwgPruneStage> swg_prune_stages(const SwgPrunePlan &plan, const std:
             if (plan.refine && plan.fixed && si == 0 && stages.size() > 1) q |= SWG_STAGE_GATE;
             if (plan.refine) q |= SWG_STAGE_REFINE;
             if (plan.refine3) q |= SWG_STAGE_REFINE3;
+            if (plan.refine4) q |= SWG_STAGE_REFINE4;
             q |= SWG_STAGE_LIST;
         }
         stages[si].queued = q;
@@ -705,14 +706,15 @@ std::vector<SwgPruneStage> swg_prune_stages(const SwgPrunePlan &plan, const std:
     return stages;
 }
 
-// (head: the words in front of the segments -- 5, or 6 with the third level's in[4])
+// (head: the words in front of the segments -- 5, 6 with the third level's in[4], 7 with the fourth's in[5] as well)
 static int debug_prune_stages(const int64_t *in, int head, int64_t *out, size_t cap, size_t *n_out)
 {
     if (!in || !n_out || (cap > 0 && !out) || in[0] < 0 || in[head - 1] < 0) return SWG_ERR_ARG;
     SwgPrunePlan plan;
     plan.on = true;
     plan.head_pairs = (uint32_t)in[0], plan.fixed = in[1] != 0, plan.refine = (int)in[2], plan.prefix_cut = in[3] != 0;
-    plan.refine3 = head == 6 ? (int)in[4] : 0;
+    plan.refine3 = head >= 6 ? (int)in[4] : 0;
+    plan.refine4 = head == 7 ? (int)in[5] : 0;
     std::vector<std::pair<uint32_t, uint32_t>> segments;
     for (int64_t i = 0; i < in[head - 1]; ++i) segments.emplace_back((uint32_t)in[head + 2 * i], (uint32_t)in[head + 1 + 2 * i]);
     const std::vector<SwgPruneStage> stages = swg_prune_stages(plan, segments);
@@ -723,6 +725,7 @@ static int debug_prune_stages(const int64_t *in, int head, int64_t *out, size_t 
 }
 extern "C" int swg_debug_prune_stages(const int64_t *in, int64_t *out, size_t cap, size_t *n_out) { return debug_prune_stages(in, 5, out, cap, n_out); }
 extern "C" int swg_debug_prune_stages3(const int64_t *in, int64_t *out, size_t cap, size_t *n_out) { return debug_prune_stages(in, 6, out, cap, n_out); }
+extern "C" int swg_debug_prune_stages4(const int64_t *in, int64_t *out, size_t cap, size_t *n_out) { return debug_prune_stages(in, 7, out, cap, n_out); }
 
 // The k-mer form of the bound, on the host: what the device builds (swg_kmer_cprof_kernel,
 // swg_kmer_table_kernel) and sums (swg_pair_bound_kmer_kernel), restated for the tests.  cprof[lq][22]: query column i
@@ -748,27 +751,35 @@ void swg_kmer_cprof(const int8_t *rows, const int8_t *idx, size_t lq, int8_t *cp
 // runs along the columns, a column is lq cells, and the columns of a prefix are computed once for all the blocks behind it
 // (depth first, the first class in parallel), its segment maxima handed down.  Value for value what the device's
 // one-thread-per-block walk along the query gives.
+// one row of a class block: class c behind the row (Mp, Bp) of its prefix (none: the block's first row), the segment maxima
+// best_p of the prefix handed down
+static void kmer_row(const int8_t *cprof, size_t lq, int g, int e, size_t S, uint32_t c, const int *Mp, const int *Bp, const int *best_p, int *Mn,
+                     int *Bn, int *best)
+{
+    const size_t W = (lq + S - 1) / S;
+    int a = 0, up = 0;
+    for (size_t s = 0; s < S; ++s) best[s] = best_p ? best_p[s] : 0;
+    for (size_t s = 0, i = 0; i < lq; ++s) {
+        int bs = best[s];
+        for (const size_t end = std::min(lq, i + W); i < end; ++i) {
+            const int sc = cprof[SWG_KMER_CLASSES * i + c];
+            a = std::max(std::max(up - g, a - e), 0);
+            const int b = Mp ? std::max(std::max(Mp[i] - g, Bp[i] - e), 0) : 0;
+            const int diag = Mp && i ? Mp[i - 1] : 0;
+            const int m = std::max(std::max(diag + sc, a), b);
+            Mn[i] = m, Bn[i] = b, up = m;
+            bs = std::max(bs, m);
+        }
+        best[s] = bs;
+    }
+}
+
 static void kmer_extend(const int8_t *cprof, size_t lq, int g, int e, int k, size_t S, int depth, size_t prefix, const int *Mp, const int *Bp,
                         const int *best_p, std::vector<int> &work, uint16_t *table, uint32_t c_begin, uint32_t c_end)
 {
     int *Mn = work.data() + (size_t)depth * (2 * lq + S), *Bn = Mn + lq, *best = Bn + lq;
-    const size_t W = (lq + S - 1) / S;
     for (uint32_t c = c_begin; c < c_end; ++c) {
-        int a = 0, up = 0;
-        for (size_t s = 0; s < S; ++s) best[s] = best_p ? best_p[s] : 0;
-        for (size_t s = 0, i = 0; i < lq; ++s) {
-            int bs = best[s];
-            for (const size_t end = std::min(lq, i + W); i < end; ++i) {
-                const int sc = cprof[SWG_KMER_CLASSES * i + c];
-                a = std::max(std::max(up - g, a - e), 0);
-                const int b = depth ? std::max(std::max(Mp[i] - g, Bp[i] - e), 0) : 0;
-                const int diag = depth && i ? Mp[i - 1] : 0;
-                const int m = std::max(std::max(diag + sc, a), b);
-                Mn[i] = m, Bn[i] = b, up = m;
-                bs = std::max(bs, m);
-            }
-            best[s] = bs;
-        }
+        kmer_row(cprof, lq, g, e, S, c, depth ? Mp : nullptr, Bp, best_p, Mn, Bn, best);
         const size_t at = prefix * SWG_KMER_CLASSES + c;
         if (depth + 1 == k)
             for (size_t s = 0; s < S; ++s) table[at * S + s] = (uint16_t)std::min(best[s], 65535);
@@ -795,7 +806,9 @@ void swg_kmer_table_seg(const int8_t *cprof, size_t lq, int g, int e, int k, siz
 // matched column never decreases along the sequence, so with H[s] the best total of the blocks so far whose last one ended
 // in segment s, a block gives H[s] = max_{s' <= s} H[s'] + min(table[block][s], the block's colmax sum), and the bound is
 // max_s H[s].  S = 1 is the unordered sum of the blocks.
-uint64_t swg_kmer_bound_seg(const uint16_t *table, int k, size_t S, const SwgColMax &cm, const int8_t *seq, size_t len)
+// (entries(ix): the S entries of block ix)
+template <class Entries>
+static uint64_t kmer_bound_walk(Entries entries, int k, size_t S, const SwgColMax &cm, const int8_t *seq, size_t len)
 {
     const size_t n_blocks = (2 + len + 3) / 4, n_rows = 4 * n_blocks;
     auto res = [&](size_t row) -> uint32_t { return row < 2 || row >= 2 + len ? 0u : (uint8_t)seq[row - 2] & 31u; };
@@ -807,13 +820,19 @@ uint64_t swg_kmer_bound_seg(const uint16_t *table, int k, size_t S, const SwgCol
         uint64_t sum = 0, run = 0;
         for (size_t j = 0; j < rows; ++j) ix = ix * SWG_KMER_CLASSES + swg_kmer_class(res(r + j)), sum += cm.v[res(r + j)];
         if (k == 5 && rows == 4) ix *= SWG_KMER_CLASSES;
+        const uint16_t *t = entries(ix);
         for (size_t s = 0; s < S; ++s) {
             run = std::max(run, H[s]);
-            H[s] = run + std::min<uint64_t>(table[ix * S + s], sum);
+            H[s] = run + std::min<uint64_t>(t[s], sum);
         }
         r += rows;
     }
     return *std::max_element(H.begin(), H.end());
+}
+
+uint64_t swg_kmer_bound_seg(const uint16_t *table, int k, size_t S, const SwgColMax &cm, const int8_t *seq, size_t len)
+{
+    return kmer_bound_walk([&](size_t ix) { return table + ix * S; }, k, S, cm, seq, len);
 }
 
 // The body of the three mirror hooks below, each of which admits its own (k, S): the table (22^k x S uint16, or NULL) and
@@ -859,6 +878,59 @@ extern "C" int swg_debug_prune_kmer_refine3(const int8_t *rows, const int8_t *id
 {
     return debug_prune_kmer(S3 == 256, rows, idx, lq, gap_open, gap_extend, 4, S3, flat, offsets, n, table_out, u_out);
 }
+// ... and the fourth level's: k = 5 over the 128 or 256 segments swg_pair_bound_refine_kernel<5, PL> walks, blocked as
+// swg_kmer_bound_seg blocks k = 5.  The table of (5, 256) is 22^5 x 256 entries, so there is none here: the sequences are
+// taken in batches of up to SWG_REFINE4_BATCH blocks, and a batch computes the entries of the blocks it holds -- sorted, so
+// that blocks behind one prefix share its rows the way the table's build shares them.
+#define SWG_REFINE4_BATCH 32768u
+extern "C" int swg_debug_prune_kmer_refine4(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S4, const int8_t *flat,
+                                            const uint64_t *offsets, size_t n, uint64_t *u_out)
+{
+    if ((S4 != 128 && S4 != 256) || !rows || lq == 0 || gap_open > 0 || gap_extend > 0 || (n > 0 && (!flat || !offsets || !u_out))) return SWG_ERR_ARG;
+    const size_t S = (size_t)S4, C = SWG_KMER_CLASSES;
+    std::vector<int8_t> cprof(lq * C);
+    swg_kmer_cprof(rows, idx, lq, cprof.data());
+    const SwgColMax cm = swg_prune_colmax(rows, idx, lq);
+    const int g = std::min(-(gap_open + gap_extend), 65536), e = std::min(-gap_extend, 65536);
+    std::vector<size_t> batch{0}; // (the first sequence of each batch, and n)
+    for (size_t i = 0, blocks = 0; i < n; ++i) {
+        const size_t nb = (2 + (size_t)(offsets[i + 1] - offsets[i]) + 3) / 4;
+        if (blocks > 0 && blocks + nb > SWG_REFINE4_BATCH) batch.push_back(i), blocks = 0;
+        blocks += nb;
+    }
+    batch.push_back(n);
+#pragma omp parallel for schedule(dynamic, 1)
+    for (long bi = 0; bi < (long)batch.size() - 1; ++bi) {
+        std::vector<uint32_t> held;
+        const uint16_t none = 0;
+        for (size_t i = batch[bi]; i < batch[bi + 1]; ++i)
+            kmer_bound_walk([&](size_t ix) { held.push_back((uint32_t)ix); return &none; }, 5, 1, cm, flat + offsets[i],
+                            (size_t)(offsets[i + 1] - offsets[i]));
+        std::sort(held.begin(), held.end());
+        held.erase(std::unique(held.begin(), held.end()), held.end());
+        std::vector<uint16_t> entries(held.size() * S);
+        std::vector<int> work(5 * (2 * lq + S));
+        uint32_t prev[5] = {0, 0, 0, 0, 0};
+        for (size_t h = 0; h < held.size(); ++h) {
+            uint32_t c[5];
+            for (uint32_t j = 5, v = held[h]; j-- > 0; v /= (uint32_t)C) c[j] = v % (uint32_t)C;
+            int d = 0;
+            while (h > 0 && d < 4 && c[d] == prev[d]) ++d; // (the rows above d are the previous block's)
+            for (; d < 5; ++d) {
+                int *Mn = work.data() + (size_t)d * (2 * lq + S), *Mp = d ? Mn - (2 * lq + S) : nullptr;
+                kmer_row(cprof.data(), lq, g, e, S, c[d], Mp, Mp ? Mp + lq : nullptr, Mp ? Mp + 2 * lq : nullptr, Mn, Mn + lq, Mn + 2 * lq);
+                prev[d] = c[d];
+            }
+            const int *best = work.data() + 4 * (2 * lq + S) + 2 * lq;
+            for (size_t s = 0; s < S; ++s) entries[h * S + s] = (uint16_t)std::min(best[s], 65535);
+        }
+        for (size_t i = batch[bi]; i < batch[bi + 1]; ++i)
+            u_out[i] = kmer_bound_walk(
+                [&](size_t ix) { return entries.data() + (size_t)(std::lower_bound(held.begin(), held.end(), (uint32_t)ix) - held.begin()) * S; }, 5, S, cm,
+                flat + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+    }
+    return SWG_OK;
+}
 extern "C" int swg_debug_prune_table_bits(const int8_t *rows, const int8_t *idx, size_t lq, int k)
 {
     if (!rows || lq == 0 || (k != 4 && k != 5)) return SWG_ERR_ARG;
@@ -869,7 +941,7 @@ extern "C" int swg_debug_prune_table_bits(const int8_t *rows, const int8_t *idx,
 // unordered sum).  An unpruned search builds nothing (0).  A forced k is taken as it is wherever the search is pruned, with
 // the forced S, or unsegmented when that is left automatic; a forced S alone goes with the k the unsegmented candidates
 // give, stepped down to 4 where the table of (5, S) is beyond SWG_KMER_TABLE_BUDGET.  Automatic weighs, over the fixed
-// list SWG_KMER_CANDIDATES, what a candidate costs -- its table, 22^k * k * lq cells at table_rate cells per second paid by
+// list SWG_KMER_CANDIDATES, what a candidate costs -- its table, swg_kmer_table_cells(k) * lq cells at table_rate cells per second paid by
 // every search with a new query, and its bound kernel's time per pair row beyond the colmax kernel's -- against what its
 // tighter cut saves: the share of the range's pair rows it takes off the fill (the hard case, a database of unrelated
 // sequences) at fill_rate pair rows per second for this query.  In the order of what they save, a step up
@@ -897,7 +969,7 @@ int swg_prune_kmer_choice(const SwgKmerAsk &a, int *segments)
             k = 1;
         } else {
             auto cost = [&](const SwgKmerCandidate &c) {
-                return c.k == 1 ? 0.0 : (double)swg_kmer_entries(c.k) * c.k * (double)a.lq / a.table_rate + c.bound_row * (double)a.pair_rows;
+                return c.k == 1 ? 0.0 : swg_kmer_table_cells(c.k) * (double)a.lq / a.table_rate + c.bound_row * (double)a.pair_rows;
             };
             auto gain = [&](const SwgKmerCandidate &c) { return c.gain * (double)a.pair_rows / a.fill_rate; };
             const SwgKmerCandidate *cur = &SWG_KMER_CANDIDATES[0];
@@ -1029,6 +1101,45 @@ extern "C" int swg_debug_prune_refine3_choice(const int64_t *in, int64_t *out)
     out[1] = S;
     out[2] = swg_prune_refine_choice(a, (int)out[0], S);
     out[3] = swg_prune_refine3_choice(a, (int)out[0], S, (int)out[2]);
+    return SWG_OK;
+}
+
+// The fourth level: blocks of 5 residues over 256 segments behind the third level's walk -- the table is 22^5 x 256 bytes,
+// walked only by the pairs the third level leaves at or above T.  Forced ("prune_refine4" = 5256), behind whatever the
+// other levels are; off ("prune_refine4" = 1); automatic only where the third level was itself chosen automatically and
+// took 256 -- so under no forced earlier level --, the tables of k = 4 and of k = 5 are byte-wide, and the candidate rule of
+// the other levels holds.  The build is the prefix-shared kernel's: 22^4 x (4 + 22) x lq cells.  A table of 16-bit entries
+// is refused at this size whoever asks (swg_kmer_refine4_admitted): the level is then off.
+// Constants: profiles/prune_deep_ab.txt -- SWG_REFINE4_GAIN the rows kept behind the third level less those behind the
+// fourth, SWG_REFINE4_BOUND_ROW the fourth walk per pair row of the range.
+#define SWG_REFINE4_GAIN 0.0374
+#define SWG_REFINE4_BOUND_ROW 1.31e-12
+int swg_prune_refine4_choice(const SwgKmerAsk &a, int k, int S, int S2, int S3)
+{
+    if (!a.pruned || k < 1 || !swg_kmer_refine4_admitted(a.table_bits5)) return 0;
+    if (a.forced_refine4 == SWG_REFINE4_FORCED) return (int)SWG_KMER_REFINE4_SEGMENTS;
+    if (a.forced_refine4 != 0 || a.forced != 0 || a.forced_segments != 0 || a.forced_refine != 0 || a.forced_refine3 != 0) return 0;
+    if (k != 4 || S <= 1 || S2 != 128 || S3 != 256 || a.table_bits != 8) return 0;
+    if (a.table_rate <= 0 || a.fill_rate <= 0 || a.lq == 0) return 0;
+    const double cost = swg_kmer_table_cells(5) * (double)a.lq / a.table_rate + SWG_REFINE4_BOUND_ROW * (double)a.pair_rows;
+    const double gain = SWG_REFINE4_GAIN * (double)a.pair_rows / a.fill_rate;
+    return cost <= 0.5 * gain ? (int)SWG_KMER_REFINE4_SEGMENTS : 0;
+}
+
+extern "C" int swg_debug_prune_refine4_choice(const int64_t *in, int64_t *out)
+{
+    SwgKmerAsk a;
+    if (!debug_kmer_ask(in, out, 8, &a)) return SWG_ERR_ARG;
+    if (!swg_prune_refine3_value_ok((long)in[8]) || (in[9] != 0 && in[9] != 8 && in[9] != 16)) return SWG_ERR_ARG;
+    if (!swg_prune_refine4_value_ok((long)in[10]) || (in[11] != 0 && in[11] != 8 && in[11] != 16)) return SWG_ERR_ARG;
+    a.forced_refine3 = (long)in[8], a.forced_refine4 = (long)in[10];
+    a.table_bits = in[9] == 16 ? 16 : 8, a.table_bits5 = in[11] == 16 ? 16 : 8;
+    int S = 0;
+    out[0] = swg_prune_kmer_choice(a, &S);
+    out[1] = S;
+    out[2] = swg_prune_refine_choice(a, (int)out[0], S);
+    out[3] = swg_prune_refine3_choice(a, (int)out[0], S, (int)out[2]);
+    out[4] = swg_prune_refine4_choice(a, (int)out[0], S, (int)out[2], (int)out[3]);
     return SWG_OK;
 }
 

@@ -273,6 +273,7 @@ struct SwgPrunePlan {
     int segments = 0;        // ... and the segments of that table (1: the unordered sum of swg_pair_bound_kmer_kernel)
     int refine = 0;          // the second level's segments (swg_prune_refine_choice): 64, 128, or 0 without one
     int refine3 = 0;         // the third level's segments (swg_prune_refine3_choice): 256, or 0 without one
+    int refine4 = 0;         // the fourth level's segments, of the k = 5 table (swg_prune_refine4_choice): 256, or 0 without one
     bool prefix_cut = false; // option "prune_cut" = 1: a stage's list is the prefix up to its last pair that reaches T
     bool fixed = false;      // a caller's threshold: every stage, the first included, is a list launch cut at fixed_T
     uint32_t fixed_T = 0;    // ... written once to the threshold word and never recomputed
@@ -298,9 +299,11 @@ SwgPrunePlan swg_prune_plan(const SwgPruneAsk &a);
 // score so far, which a threshold kernel computes in front of it; under a caller's threshold (plan.fixed) the first is
 // cut too and no threshold kernel runs.  A cut is the prefix cut (plan.prefix_cut), or pair by pair: the refine pass
 // where there is a second level (plan.refine) -- behind the gate on the first of several stages under a caller's
-// threshold --, the third level's (plan.refine3) behind it under the same threshold word, then the list.
+// threshold --, the third level's (plan.refine3) behind it under the same threshold word, the fourth's (plan.refine4) behind
+// that, then the list.
 enum : uint32_t {
-    SWG_STAGE_THRESHOLD = 1u, SWG_STAGE_PREFIX_CUT = 2u, SWG_STAGE_GATE = 4u, SWG_STAGE_REFINE = 8u, SWG_STAGE_LIST = 16u, SWG_STAGE_REFINE3 = 32u
+    SWG_STAGE_THRESHOLD = 1u, SWG_STAGE_PREFIX_CUT = 2u, SWG_STAGE_GATE = 4u, SWG_STAGE_REFINE = 8u, SWG_STAGE_LIST = 16u, SWG_STAGE_REFINE3 = 32u,
+    SWG_STAGE_REFINE4 = 64u
 };
 struct SwgPruneStage {
     uint32_t begin, end; // pairs
@@ -313,6 +316,8 @@ std::vector<SwgPruneStage> swg_prune_stages(const SwgPrunePlan &plan, const std:
 extern "C" int swg_debug_prune_stages(const int64_t *in, int64_t *out, size_t cap, size_t *n_out);
 // ... with the third level: in[0..5] = head_pairs, fixed, refine, prefix_cut, refine3, n, then the n segments
 extern "C" int swg_debug_prune_stages3(const int64_t *in, int64_t *out, size_t cap, size_t *n_out);
+// ... and the fourth: in[0..6] = head_pairs, fixed, refine, prefix_cut, refine3, refine4, n, then the n segments
+extern "C" int swg_debug_prune_stages4(const int64_t *in, int64_t *out, size_t cap, size_t *n_out);
 // The automatic rule of a caller's threshold ("A caller's threshold"; profiles/search_above_ab.txt): the
 // bound, list and tally kernels of a stage cost tens of microseconds whatever the range holds, a list launch one
 // dependent load per claim; a range with at least SWG_PRUNE_ABOVE_AUTO_PAIRS pairs per resident lane group has fills
@@ -343,17 +348,26 @@ void swg_kmer_cprof(const int8_t *rows, const int8_t *idx, size_t lq, int8_t *cp
 void swg_kmer_table_seg(const int8_t *cprof, size_t lq, int g, int e, int k, size_t S, uint16_t *table); // table[22^k][S]
 uint64_t swg_kmer_bound_seg(const uint16_t *table, int k, size_t S, const SwgColMax &cm, const int8_t *seq, size_t len);
 // The two rates the automatic choice weighs, measured on one MI355X (profiles/prune_kmer_ab.txt): the table
-// kernel's cell updates per second (k = 5 at 3000 columns: 7.73e10 cells in 16.6 ms), and the fill's pair rows per second
+// kernel's cell updates per second (k = 5 at 3000 columns: 7.73e10 cells in 16.6 ms a thread per block; 1.83e10 in 4.0 ms
+// a thread per prefix, profiles/prune_deep_ab.txt: the same rate), and the fill's pair rows per second
 // -- a pair row costs one step of a 16-lane group per pass of 512 query columns (the headline unpruned: 1.938e9 pair rows
 // x 6 passes in 1237.7 ms).
 #define SWG_KMER_TABLE_RATE 4.6e12
 #define SWG_KMER_FILL_PASS_RATE 9.4e9
+// the table kernels' cell updates per query column: a thread per block and k cells each (k = 4), or a thread per 4-class
+// prefix -- its four rows once, then the 22 fifth rows (k = 5: swg_kmer_table5_kernel, 4.2 times fewer than 22^5 x 5)
+inline double swg_kmer_table_cells(int k)
+{
+    return k == 5 ? (double)swg_kmer_entries(4) * (4 + SWG_KMER_CLASSES) : (double)swg_kmer_entries(k) * k;
+}
 inline double swg_kmer_fill_rate(size_t lq) { return SWG_KMER_FILL_PASS_RATE / (double)std::max<size_t>(1, (lq + 511) / 512); }
 struct SwgKmerAsk {
     long forced = 0;     // option "prune_kmer": 0 automatic, 1, 4, 5
     long forced_segments = 0; // option "prune_segments": 0 automatic, 1..SWG_KMER_MAX_SEGMENTS
     long forced_refine = 0;   // option "prune_refine": 0 automatic, 1 off, 64 or 128
     long forced_refine3 = 0;  // option "prune_refine3": 0 automatic, 1 off, 256
+    long forced_refine4 = 0;  // option "prune_refine4": 0 automatic, 1 off, 5256 (k = 5 in 256 segments)
+    int table_bits5 = 8;      // ... and of the k = 5 tables' (the fourth level takes bytes only)
     int table_bits = 8;       // the width of the k = 4 tables' entries for this query and scoring (swg_kmer_table_bits, "prune_table_bits")
     bool pruned = false; // swg_prune_plan's answer
     size_t lq = 0;
@@ -391,6 +405,18 @@ extern "C" int swg_debug_prune_refine3_choice(const int64_t *in, int64_t *out);
 extern "C" int swg_debug_prune_kmer_refine3(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S3, const int8_t *flat,
                                             const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out);
 extern "C" int swg_debug_prune_table_bits(const int8_t *rows, const int8_t *idx, size_t lq, int k);
+// The fourth level: the k = 5 table in 256 segments behind the third level's walk, or 0 for none (k, S, S2, S3: what the
+// levels in front of it took).  Option "prune_refine4" names (k, S) as 1000 k + S: 5256.
+#define SWG_REFINE4_FORCED 5256
+int swg_prune_refine4_choice(const SwgKmerAsk &a, int k, int S, int S2, int S3);
+inline bool swg_prune_refine4_value_ok(long v) { return v == 0 || v == 1 || v == SWG_REFINE4_FORCED; }
+// test hook: in[0..9] as swg_debug_prune_refine3_choice, in[10] = option "prune_refine4", in[11] = the k = 5 tables' entry
+// width (0: bytes) -> out[0..4] = k, S, S2, S3, S4
+extern "C" int swg_debug_prune_refine4_choice(const int64_t *in, int64_t *out);
+// ... the mirror of the fourth level's bound: k = 5 over S4 = 128 or 256 segments.  It has no table to hand out: it
+// computes the entries of the blocks the sequences hold.
+extern "C" int swg_debug_prune_kmer_refine4(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S4, const int8_t *flat,
+                                            const uint64_t *offsets, size_t n, uint64_t *u_out);
 // the words of a search's counter block (swg_db::Bufs::d_counters) a pruned search uses: the threshold so far and the
 // threshold kernel's status word, then what swg_launch_prune_cut or swg_launch_prune_list writes: the pairs the stage
 // takes, the pairs skipped so far, their token blocks (64 bits)
@@ -481,9 +507,10 @@ struct SwgKmerTable {
     int bits = 0;       // of an entry: 8 or 16 (swg_kmer_table_bits, or 16 under option "prune_table_bits")
     bool holds(uint64_t e, int k_, int S, int bits_) const { return d && epoch == e && k == k_ && segments == S && bits == bits_; }
 };
-// The bound a pruned search cuts by: k (0: not pruned), its segments S, the second level's S2 and the third's S3 (0: none)
+// The bound a pruned search cuts by: k (0: not pruned), its segments S, the second level's S2, the third's S3 and the
+// fourth's S4 (0: none)
 struct SwgPruneChoice {
-    int kmer = 0, segments = 0, refine = 0, refine3 = 0;
+    int kmer = 0, segments = 0, refine = 0, refine3 = 0, refine4 = 0;
 };
 
 // One search in flight: its timing events, host-side landing buffers and what swg_search_end
@@ -574,12 +601,14 @@ struct swg_ctx {
     long opt_prune_segments = 0; // option "prune_segments": 0 auto, 1..32
     long opt_prune_refine = 0;   // option "prune_refine": 0 auto, 1 off, 64, 128
     long opt_prune_refine3 = 0;  // option "prune_refine3": 0 auto, 1 off, 256
+    long opt_prune_refine4 = 0;  // option "prune_refine4": 0 auto, 1 off, 5256
     long opt_prune_table_bits = 0; // option "prune_table_bits": 0 auto (bytes where they hold every entry), 16
     long opt_prune_cut = 0;      // option "prune_cut": 0 pair by pair, 1 the prefix of the length order
     int8_t *d_kmer_cprof = nullptr;
     size_t d_kmer_cprof_cap = 0;
-    SwgKmerTable kmer_first[2], kmer_second, kmer_third; // [k - 4]
-    uint64_t kmer_builds = 0, kmer_refine_builds = 0, kmer_refine3_builds = 0; // builds queued so far, level by level (tests)
+    SwgKmerTable kmer_first[2], kmer_second, kmer_third, kmer_fourth; // [k - 4]
+    uint64_t kmer_builds = 0, kmer_refine_builds = 0, kmer_refine3_builds = 0, kmer_refine4_builds = 0; // builds queued so far, level by level (tests)
+    bool kmer_fourth_refused = false; // the fourth table's allocation failed once: this context searches without the level
     uint32_t opt_seg_blocks = SWG_DYN_SEG_BLOCKS; // token blocks per launch of the multi-pass fill (option "segment_blocks": tests)
     // device state
     int8_t *d_sub = nullptr;

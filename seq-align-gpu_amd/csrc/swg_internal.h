@@ -382,9 +382,15 @@ hipError_t swg_launch_prune_threshold(const int32_t *d_scores, const uint32_t *d
 hipError_t swg_launch_prune_cut(const uint32_t *d_bound, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, const uint32_t *d_thr,
                                 uint32_t *d_out, hipStream_t stream);
 // The second and third levels: d_bound[p] = min(d_bound[p], the ordered bound over d_table, k = 4 in S2 = 64, 128 or 256
-// segments) for the pairs of [begin, end) with d_bound[p] >= *d_thr
+// segments) for the pairs of [begin, end) with d_bound[p] >= *d_thr.  The fourth: k = 5 in 256 segments of bytes.
 hipError_t swg_launch_pair_bound_refine(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, uint32_t S2, const SwgColMax &cm,
-                                        const void *d_table, int bits, const uint32_t *d_thr, uint32_t *d_bound, hipStream_t stream);
+                                        const void *d_table, int bits, const uint32_t *d_thr, uint32_t *d_bound, hipStream_t stream, int k = 4);
+// The fourth level's table: 5-residue blocks in 256 segments, 22^5 x 256 bytes = 1.32 GB.  It is admitted
+// on a limit of its own (SWG_KMER_TABLE_BUDGET is the first-level tables'), as bytes only: the table of a query whose
+// entries need 16 bits is refused and the search runs without the level.
+#define SWG_KMER_REFINE4_SEGMENTS 256u
+#define SWG_KMER_REFINE4_BUDGET (2ull << 30)
+static inline bool swg_kmer_refine4_admitted(int bits) { return bits == 8 && swg_kmer_entries(5) * SWG_KMER_REFINE4_SEGMENTS <= SWG_KMER_REFINE4_BUDGET; }
 // The cut pair by pair: d_list[0 .. d_out[0]) = the pairs of [begin, end) with d_bound >= *d_thr, ascending; d_out[1] +=
 // the others, (uint64 at d_out[2]) += their token blocks.  d_tiles: one word per SWG_PRUNE_TILE pairs of the range;
 // d_rec (or NULL): {*d_thr, d_out[0]} once more, for the tests.

@@ -3023,6 +3023,108 @@ __global__ __launch_bounds__(256) void swg_kmer_table_kernel(const int8_t *cprof
         for (; seg < S; ++seg) out[seg] = 0;
 }
 
+// The table of k = 5, one thread per 4-class PREFIX: the 22 blocks behind a prefix share four of their five rows, so the
+// thread computes the prefix's four rows once per column and then the 22 fifth rows, each with its own M, its own
+// horizontal-gap state and its own running segment maximum -- 4 + 22 cell updates per column for 22 blocks where
+// swg_kmer_table_kernel<5> does 110.  Every fifth row sees the same cell above it (the prefix's last row: its M, its
+// vertical-gap state, its M one column back), so values are swg_kmer_table_kernel<5>'s bit for bit; an entry is the
+// maximum over all five rows' cells in the segment (the prefix's maximum joins each block's at the segment's end).  The
+// fifth row's class is a compile-time index: its scores come out of the row's dwords, read once per column.  Stores: a
+// thread's 22 table rows lie S entries apart, so one entry per store would be 22 single bytes into 22 cache lines at every
+// segment's end; where S is a multiple of 8 bytes' worth of entries (PACK) the entries are collected PACK segments at a
+// time and leave as one 8-byte store per row.  Segment rule, clamp and the zeros of segments without columns as above.
+template <class E>
+__global__ __launch_bounds__(256) void swg_kmer_table5_kernel(const int8_t *cprof, uint32_t lq, int g, int e, uint32_t n_prefixes, uint32_t S,
+                                                              E *table)
+{
+    constexpr int top = sizeof(E) == 1 ? 255 : 65535;
+    constexpr int NC = (int)SWG_KMER_CLASSES;
+    constexpr uint32_t PACK = 8u / sizeof(E), EB = 8u * sizeof(E);
+    __shared__ uint4 rows4[SWG_KMER_CHUNK * 2u];
+    const int8_t *rows = reinterpret_cast<const int8_t *>(rows4);
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    const bool mine = idx < n_prefixes;
+    uint32_t c[4];
+    {
+        uint32_t v = mine ? idx : 0u;
+#pragma unroll
+        for (int j = 3; j >= 0; --j) {
+            c[j] = v % SWG_KMER_CLASSES;
+            v /= SWG_KMER_CLASSES;
+        }
+    }
+    int M[4], A[4], pbest = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) M[j] = 0, A[j] = 0;
+    int M5[NC], A5[NC], best5[NC];
+    uint32_t lo[NC], hi[NC]; // (the entries of up to PACK segments, first segment lowest)
+#pragma unroll
+    for (int k = 0; k < NC; ++k) M5[k] = 0, A5[k] = 0, best5[k] = 0, lo[k] = 0u, hi[k] = 0u;
+    const uint32_t W = (lq + S - 1u) / S;
+    const bool packed = S % PACK == 0u;
+    E *out = table + (size_t)(mine ? idx : 0u) * NC * S; // (the row of the prefix's first block)
+    uint32_t seg = 0u, seg_end = W < lq ? W : lq;
+    // segment `seg` ends: every block's entry (zero: a segment without columns) joins its pack, or leaves alone
+    auto close_segment = [&](bool zero) {
+        const uint32_t slot = seg % PACK;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            const int b = zero ? 0 : max(pbest, best5[k]);
+            const uint32_t v = (uint32_t)(b > top ? top : b);
+            best5[k] = 0;
+            if (!packed) {
+                if (mine) out[(size_t)k * S + seg] = (E)v;
+                continue;
+            }
+            if (slot * EB < 32u) lo[k] |= v << ((slot * EB) & 31u);
+            else hi[k] |= v << ((slot * EB) & 31u);
+            if (slot == PACK - 1u) {
+                if (mine) *reinterpret_cast<uint2 *>(out + (size_t)k * S + (seg - slot)) = make_uint2(lo[k], hi[k]);
+                lo[k] = 0u, hi[k] = 0u;
+            }
+        }
+        pbest = 0;
+        ++seg;
+    };
+    for (uint32_t i0 = 0u; i0 < lq; i0 += SWG_KMER_CHUNK) {
+        const uint32_t n = lq - i0 < SWG_KMER_CHUNK ? lq - i0 : SWG_KMER_CHUNK;
+        __syncthreads();
+        for (uint32_t w = threadIdx.x; w < n * 2u; w += 256u) rows4[w] = reinterpret_cast<const uint4 *>(cprof + 32u * (size_t)i0)[w];
+        __syncthreads();
+        for (uint32_t i = 0u; i < n; ++i) {
+            const int8_t *row = rows + 32u * i;
+            int diag = 0, left = 0, B = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int s = row[c[j]];
+                const int a = max(max(M[j] - g, A[j] - e), 0);
+                const int b = j ? max(max(left - g, B - e), 0) : 0;
+                const int m = max(max(diag + s, a), b);
+                diag = M[j];
+                M[j] = m, A[j] = a, B = b, left = m;
+                pbest = max(pbest, m);
+            }
+            // the fifth rows: diag is the prefix's last row one column back, (left, B) that row in this column
+            const int b5 = max(max(left - g, B - e), 0);
+            const uint4 w0 = rows4[2u * i], w1 = rows4[2u * i + 1u];
+            const uint32_t w[6] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y};
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                const int s = (int)(int8_t)(w[k >> 2] >> (8 * (k & 3)));
+                const int a = max(max(M5[k] - g, A5[k] - e), 0);
+                const int m = max(max(diag + s, a), b5);
+                M5[k] = m, A5[k] = a;
+                best5[k] = max(best5[k], m);
+            }
+            if (i0 + i + 1u == seg_end) { // (the same for every thread)
+                close_segment(false);
+                seg_end = seg_end + W < lq ? seg_end + W : lq;
+            }
+        }
+    }
+    while (seg < S) close_segment(true);
+}
+
 hipError_t swg_launch_kmer_table(const int8_t *d_sub, const int8_t *d_query, const int8_t *d_pssm, uint32_t lq, uint32_t g, uint32_t e,
                                  int k, uint32_t S, int8_t *d_cprof, void *d_table, int bits, hipStream_t stream)
 {
@@ -3032,10 +3134,11 @@ hipError_t swg_launch_kmer_table(const int8_t *d_sub, const int8_t *d_query, con
     const int gi = (int)(g > 65536u ? 65536u : g), ei = (int)(e > 65536u ? 65536u : e);
     hipLaunchKernelGGL(swg_kmer_cprof_kernel, dim3((lq * 32u + 255u) / 256u), dim3(256), 0, stream, d_sub, d_query, d_pssm, lq, d_cprof);
     const dim3 grid((n + 255u) / 256u);
+    const uint32_t n4 = (uint32_t)swg_kmer_entries(4); // (k = 5: a thread per 4-class prefix)
     if (k == 5 && bits == 8)
-        hipLaunchKernelGGL((swg_kmer_table_kernel<5, uint8_t>), grid, dim3(256), 0, stream, d_cprof, lq, gi, ei, n, S, static_cast<uint8_t *>(d_table));
+        hipLaunchKernelGGL((swg_kmer_table5_kernel<uint8_t>), dim3((n4 + 255u) / 256u), dim3(256), 0, stream, d_cprof, lq, gi, ei, n4, S, static_cast<uint8_t *>(d_table));
     else if (k == 5)
-        hipLaunchKernelGGL((swg_kmer_table_kernel<5, uint16_t>), grid, dim3(256), 0, stream, d_cprof, lq, gi, ei, n, S, static_cast<uint16_t *>(d_table));
+        hipLaunchKernelGGL((swg_kmer_table5_kernel<uint16_t>), dim3((n4 + 255u) / 256u), dim3(256), 0, stream, d_cprof, lq, gi, ei, n4, S, static_cast<uint16_t *>(d_table));
     else if (bits == 8)
         hipLaunchKernelGGL((swg_kmer_table_kernel<4, uint8_t>), grid, dim3(256), 0, stream, d_cprof, lq, gi, ei, n, S, static_cast<uint8_t *>(d_table));
     else
@@ -3400,11 +3503,38 @@ __device__ __forceinline__ void swg_refine_entries(const uint8_t *at, uint32_t c
     }
 }
 
+// U blocks in order: their indices and colmax sums come from lane `src + u` (K = 4: U consecutive units of one block) or
+// all from lane `src` (K = 5: one unit of U = 4 blocks), the entries are gathered ahead of the recurrence
+template <int PL, int U, bool ONE_UNIT, class E>
+__device__ __forceinline__ void swg_refine_round(const uint32_t (&ux)[ONE_UNIT ? U : 1], const uint32_t (&uy)[ONE_UNIT ? U : 1],
+                                                 const uint32_t (&uc)[ONE_UNIT ? U : 1], int src, const E *tl, uint32_t S2, uint32_t (&hx)[PL],
+                                                 uint32_t (&hy)[PL], uint32_t m0)
+{
+    uint32_t tx[U][PL], ty[U][PL];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int from = ONE_UNIT ? src : src + u, b = ONE_UNIT ? u : 0;
+        const uint32_t ix = (uint32_t)__shfl((int)ux[b], from, 32), iy = (uint32_t)__shfl((int)uy[b], from, 32);
+        const uint32_t cs = (uint32_t)__shfl((int)uc[b], from, 32);
+        swg_refine_entries<PL>(tl + (size_t)ix * S2, cs & 0xFFFFu, tx[u]);
+        swg_refine_entries<PL>(tl + (size_t)iy * S2, cs >> 16, ty[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        swg_refine_step<PL>(hx, tx[u], m0);
+        swg_refine_step<PL>(hy, ty[u], m0);
+    }
+}
+
+// K = 5, PL = 8 is the fourth level: the table of 5-residue blocks in 256 segments, the pair's blocks taken as
+// swg_pair_bound_kmer_seg_kernel<5, WD> takes them -- a lane's unit is five uint4s as four blocks of 5 rows, the pair's
+// last fewer-than-five uint4s are blocks of 4 rows, which in the table of 5 are class blocks with a padding tail.
 template <int K, int PL, class E>
 __global__ __launch_bounds__(256) void swg_pair_bound_refine_kernel(const uint4 *tok, const uint32_t *pair_off, uint32_t begin, uint32_t end, SwgColMax cm,
                                                                     const E *table, const uint32_t *thr, uint32_t *bound)
 {
-    static_assert(K == 4 && (PL == 2 || PL == 4 || PL == 8), "the refined bound: k = 4 over 64, 128 or 256 segments");
+    static_assert((K == 4 && (PL == 2 || PL == 4 || PL == 8)) || (K == 5 && PL == 8),
+                  "the refined bound: k = 4 over 64, 128 or 256 segments, k = 5 over 256");
     __shared__ uint32_t lut[32]; // residue index -> class | colmax << 8
     if (threadIdx.x < 32u) lut[threadIdx.x] = swg_kmer_class(threadIdx.x) | (uint32_t)cm.v[threadIdx.x] << 8;
     __syncthreads();
@@ -3426,46 +3556,67 @@ __global__ __launch_bounds__(256) void swg_pair_bound_refine_kernel(const uint4 
     };
     const uint32_t b0 = pair_off[p], e = pair_off[p + 1u];
     constexpr int U = 4; // blocks per round of gathers
-    for (uint32_t t0 = b0; t0 < e; t0 += 32u) {
-        uint32_t ux = 0u, uy = 0u, uc = 0u; // (past the pair's end: the all-padding block, whose entries are 0)
+    uint32_t tail = b0;
+    if (K == 5) {
+        const uint32_t groups = (e - b0) / 5u;
+        tail = b0 + 5u * groups;
+        for (uint32_t g0 = 0u; g0 < groups; g0 += 32u) {
+            uint32_t ux[4] = {0u, 0u, 0u, 0u}, uy[4] = {0u, 0u, 0u, 0u}, uc[4] = {0u, 0u, 0u, 0u};
+            if (g0 + l < groups) {
+                uint32_t x[20], y[20];
+#pragma unroll
+                for (int u = 0; u < 5; ++u) {
+                    const uint4 k = tok[b0 + 5u * (g0 + l) + (uint32_t)u];
+                    x[4 * u] = lut[(k.x >> 3) & 31u], x[4 * u + 1] = lut[(k.y >> 3) & 31u], x[4 * u + 2] = lut[(k.z >> 3) & 31u], x[4 * u + 3] = lut[(k.w >> 3) & 31u];
+                    y[4 * u] = lut[(k.x >> 11) & 31u], y[4 * u + 1] = lut[(k.y >> 11) & 31u], y[4 * u + 2] = lut[(k.z >> 11) & 31u], y[4 * u + 3] = lut[(k.w >> 11) & 31u];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    uint32_t ix = 0u, iy = 0u, sx = 0u, sy = 0u;
+#pragma unroll
+                    for (int j = 0; j < 5; ++j) {
+                        ix = ix * C + (x[5 * u + j] & 255u), sx += x[5 * u + j] >> 8;
+                        iy = iy * C + (y[5 * u + j] & 255u), sy += y[5 * u + j] >> 8;
+                    }
+                    ux[u] = ix, uy[u] = iy, uc[u] = sx | sy << 16;
+                }
+            }
+            const uint32_t cnt = groups - g0 < 32u ? groups - g0 : 32u;
+            for (uint32_t j = 0u; j < cnt; ++j) swg_refine_round<PL, 4, true>(ux, uy, uc, (int)j, tl, S2, hx, hy, m0);
+        }
+    }
+    for (uint32_t t0 = tail; t0 < e; t0 += 32u) {
+        uint32_t ux[1] = {0u}, uy[1] = {0u}, uc[1] = {0u}; // (past the pair's end: the all-padding block, whose entries are 0)
         if (t0 + l < e) {
             const uint4 k = tok[t0 + l];
             const uint32_t xa = lut[(k.x >> 3) & 31u], xb = lut[(k.y >> 3) & 31u], xc = lut[(k.z >> 3) & 31u], xd = lut[(k.w >> 3) & 31u];
             const uint32_t ya = lut[(k.x >> 11) & 31u], yb = lut[(k.y >> 11) & 31u], yc = lut[(k.z >> 11) & 31u], yd = lut[(k.w >> 11) & 31u];
-            ux = (((xa & 255u) * C + (xb & 255u)) * C + (xc & 255u)) * C + (xd & 255u);
-            uy = (((ya & 255u) * C + (yb & 255u)) * C + (yc & 255u)) * C + (yd & 255u);
-            uc = ((xa >> 8) + (xb >> 8) + (xc >> 8) + (xd >> 8)) | ((ya >> 8) + (yb >> 8) + (yc >> 8) + (yd >> 8)) << 16;
+            const uint32_t ix = (((xa & 255u) * C + (xb & 255u)) * C + (xc & 255u)) * C + (xd & 255u);
+            const uint32_t iy = (((ya & 255u) * C + (yb & 255u)) * C + (yc & 255u)) * C + (yd & 255u);
+            ux[0] = K == 5 ? ix * C : ix, uy[0] = K == 5 ? iy * C : iy;
+            uc[0] = ((xa >> 8) + (xb >> 8) + (xc >> 8) + (xd >> 8)) | ((ya >> 8) + (yb >> 8) + (yc >> 8) + (yd >> 8)) << 16;
         }
         const uint32_t cnt = e - t0 < 32u ? e - t0 : 32u;
-        for (uint32_t j0 = 0u; j0 < cnt; j0 += (uint32_t)U) {
-            uint32_t tx[U][PL], ty[U][PL];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int src = (int)j0 + u; // (< 32: cnt <= 32, both multiples of U apart from cnt)
-                const uint32_t ix = (uint32_t)__shfl((int)ux, src, 32), iy = (uint32_t)__shfl((int)uy, src, 32);
-                const uint32_t cs = (uint32_t)__shfl((int)uc, src, 32);
-                swg_refine_entries<PL>(tl + (size_t)ix * S2, cs & 0xFFFFu, tx[u]);
-                swg_refine_entries<PL>(tl + (size_t)iy * S2, cs >> 16, ty[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                swg_refine_step<PL>(hx, tx[u], m0);
-                swg_refine_step<PL>(hy, ty[u], m0);
-            }
-        }
+        // (src + u < 32: cnt <= 32, both multiples of U apart from cnt)
+        for (uint32_t j0 = 0u; j0 < cnt; j0 += (uint32_t)U) swg_refine_round<PL, U, false>(ux, uy, uc, (int)j0, tl, S2, hx, hy, m0);
     }
     const uint32_t refined = group_max();
     if (l == 0u && refined < first) bound[p] = refined;
 }
 
 hipError_t swg_launch_pair_bound_refine(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, uint32_t S2, const SwgColMax &cm,
-                                        const void *d_table, int bits, const uint32_t *d_thr, uint32_t *d_bound, hipStream_t stream)
+                                        const void *d_table, int bits, const uint32_t *d_thr, uint32_t *d_bound, hipStream_t stream, int k)
 {
     if (end < begin || (S2 != 64u && S2 != 128u && S2 != 256u) || (bits != 8 && bits != 16)) return hipErrorInvalidValue;
+    if (k != 4 && !(k == 5 && S2 == SWG_KMER_REFINE4_SEGMENTS && bits == 8)) return hipErrorInvalidValue;
     if (end == begin) return hipSuccess;
     const dim3 grid((end - begin + 7u) / 8u);
     const uint8_t *t8 = static_cast<const uint8_t *>(d_table);
     const uint16_t *t16 = static_cast<const uint16_t *>(d_table);
+    if (k == 5) {
+        hipLaunchKernelGGL((swg_pair_bound_refine_kernel<5, 8, uint8_t>), grid, dim3(256), 0, stream, d_tok, d_pair_off, begin, end, cm, t8, d_thr, d_bound);
+        return hipGetLastError();
+    }
 #define SWG_REFINE_LAUNCH(PL, E, t) \
     hipLaunchKernelGGL((swg_pair_bound_refine_kernel<4, PL, E>), grid, dim3(256), 0, stream, d_tok, d_pair_off, begin, end, cm, t, d_thr, d_bound)
     if (S2 == 256u && bits == 8) SWG_REFINE_LAUNCH(8, uint8_t, t8);
