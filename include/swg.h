@@ -319,7 +319,12 @@ int swg_search_end(swg_ctx *ctx, int ticket, int32_t *scores_out, swg_hit *topk_
  * was chosen automatically and the range is large enough (the 10M-sequence database: yes; smaller ones: no).  The table
  * holds bytes only: a query whose blocks of 5 can score above 255 (a PSSM entry of 52 or more) is searched without the
  * level under every value, and so is every search of a context whose device had no room for the table -- neither is an
- * error.  "prune_table_bits" (default 0):
+ * error.  "prune_gate" (default 0): where the first-level bound is a k-mer bound in segments, its kernel can wait for a
+ * threshold -- the K-th best score behind the first stage, or swg_search_above's -- and leave out every pair whose
+ * colmax bound is already below it (no other bound of the pair can be above that one, so no hit and no count changes);
+ * the pairs of the first stage, which is never cut, are then not bounded at all.  2 on wherever the first level is
+ * segmented; 1 off; 0 automatic -- on where "prune_kmer" and "prune_segments" are both automatic and the range is large
+ * enough for the third level (the 10M-sequence database: yes; smaller ones: no).  "prune_table_bits" (default 0):
  * the width of the k-mer tables' entries.  0: bytes wherever k x the largest score of the query's profile is at most 255
  * (every entry fits: BLOSUM62 44, PAM250 68 at k = 4), uint16_t otherwise (a PSSM with an entry of 64 or more); 16:
  * uint16_t always.  A byte table holds the same values in half the memory and gather traffic.  Hits, bounds and lists are

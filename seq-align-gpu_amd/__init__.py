@@ -311,6 +311,9 @@ _sig("swg_debug_prune_tables", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_tables4", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_refine4_read", C.c_int, [_vp, _vp, C.c_size_t, _vp])
 _sig("swg_debug_prune_refine4_choice", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_gate_choice", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_gate", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_stages5", C.c_int, [_vp, _vp, C.c_size_t, _vp])
 _sig("swg_debug_prune_stages4", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 _sig("swg_debug_list_deal", C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
 _sig("swg_debug_calib_iters", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)])
@@ -790,6 +793,16 @@ def debug_prune_refine4_choice(forced=0, segments=0, refine=0, refine3=0, refine
     return tuple(int(v) for v in out)
 
 
+def debug_prune_gate_choice(forced=0, segments=0, gate=0, pruned=1, lq=3000, pair_rows=1900000000, table_rate=0, fill_rate=0):
+    """Test hook (no device needed): debug_prune_kmer_choice_seg with option prune_gate (0 automatic, 1 off, 2 wherever
+    the first level is a segmented k-mer bound) -> (k, S, gate): whether the first level's launch waits for a threshold
+    and leaves out the pairs whose colmax bound is below it (swg_prune_gate_choice)."""
+    a = np.array([forced, pruned, lq, pair_rows, table_rate, fill_rate, segments, 0, gate], dtype=np.int64)
+    out = np.zeros(3, dtype=np.int64)
+    _check(lib.swg_debug_prune_gate_choice(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
+    return int(out[0]), int(out[1]), bool(out[2])
+
+
 def debug_prune_refine_choice(forced=0, segments=0, refine=0, pruned=1, lq=3000, pair_rows=1900000000, table_rate=0, fill_rate=0):
     """Test hook (no device needed): debug_prune_kmer_choice_seg with option prune_refine -> (k, S, S2): the first-level
     bound and the segments of the second level's table, 0 without one."""
@@ -861,18 +874,22 @@ def debug_above_multi_route(option=0, admitted=True, single_pruned=False):
 
 # a stage's fourth word: (bit, name) in queue order (the third level's walk is bit 5, queued between the second's and the list)
 PRUNE_STAGE_QUEUED = ("threshold", "prefix_cut", "gate", "refine", "list")
-_PRUNE_STAGE_BITS = ((0, "threshold"), (1, "prefix_cut"), (2, "gate"), (3, "refine"), (5, "refine3"), (6, "refine4"), (4, "list"))
+_PRUNE_STAGE_BITS = ((0, "threshold"), (7, "bound"), (1, "prefix_cut"), (2, "gate"), (3, "refine"), (5, "refine3"), (6, "refine4"), (4, "list"))
 
 
-def debug_prune_stages(segments, head_pairs=0, fixed=False, refine=0, prefix_cut=False, refine3=0, refine4=0):
+def debug_prune_stages(segments, head_pairs=0, fixed=False, refine=0, prefix_cut=False, refine3=0, refine4=0, gate=False):
     """Test hook (no device needed): the stages of a pruned fill over the pair ranges `segments` [(begin, end), ...] and
     what is queued in front of each (swg_prune_stages) -> [(begin, end, segment index, names in queue order: those of
     PRUNE_STAGE_QUEUED, and "refine3" then "refine4" in front of "list"), ...].  head_pairs, fixed (a caller's threshold),
-    refine, refine3 and refine4 (the second, third and fourth levels' segments, 0: none) and prefix_cut are the plan's."""
-    a = np.array([head_pairs, fixed, refine, prefix_cut, refine3, refine4, len(segments)] + [int(v) for sg in segments for v in sg], dtype=np.int64)
+    refine, refine3 and refine4 (the second, third and fourth levels' segments, 0: none) and prefix_cut are the plan's.
+    gate (the plan's: swg_debug_prune_stages5): "bound", the first level's gated launch, sits behind "threshold" on the
+    stage that first has one."""
+    head = [head_pairs, fixed, refine, prefix_cut, refine3, refine4] + ([1] if gate else [])
+    a = np.array(head + [len(segments)] + [int(v) for sg in segments for v in sg], dtype=np.int64)
     out = np.zeros((2 * len(segments) + 1, 4), dtype=np.int64)
     n = C.c_size_t(0)
-    _check(lib.swg_debug_prune_stages4(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp), out.shape[0], C.byref(n)))
+    hook = lib.swg_debug_prune_stages5 if gate else lib.swg_debug_prune_stages4
+    _check(hook(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp), out.shape[0], C.byref(n)))
     return [(int(b), int(e), int(sg), tuple(name for i, name in _PRUNE_STAGE_BITS if int(qd) >> i & 1))
             for b, e, sg, qd in out[:n.value]]
 
@@ -1747,6 +1764,12 @@ class Context:
         out = np.zeros(4, dtype=np.int64)
         _check(lib.swg_debug_prune_tables4(self.handle, out.ctypes.data_as(_vp)), self.handle)
         return {"refine4": int(out[0]), "refine4_builds": int(out[1]), "bits": int(out[2]), "refused": bool(out[3])}
+
+    def debug_prune_gate(self):
+        """Test hook: whether the search last begun took the gate in front of the first level (option prune_gate)."""
+        out = np.zeros(1, dtype=np.int64)
+        _check(lib.swg_debug_prune_gate(self.handle, out.ctypes.data_as(_vp)), self.handle)
+        return bool(out[0])
 
     def debug_prune_refine4_read(self, blocks):
         """Test hook: rows of the fourth level's table -> uint16[len(blocks), 256]: the entries of the class blocks

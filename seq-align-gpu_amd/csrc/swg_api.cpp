@@ -379,6 +379,10 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
         if (!swg_prune_refine4_value_ok(value))
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_refine4 must be 0 (auto), 1 (off) or 5256 (the fourth-level bound's table: k = 5 in 256 segments)");
         ctx->opt_prune_refine4 = value;
+    } else if (!strcmp(key, "prune_gate")) {
+        if (!swg_prune_gate_value_ok(value))
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_gate must be 0 (auto), 1 (off) or 2 (wherever the first-level bound is a segmented k-mer bound)");
+        ctx->opt_prune_gate = value;
     } else if (!strcmp(key, "prune_table_bits")) {
         if (value != 0 && value != 16)
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_table_bits must be 0 (auto: bytes where they hold every entry) or 16");
@@ -1271,7 +1275,8 @@ static int dyn_fill_begin(DynFill *F, int go, int ge, uint64_t *d_trace)
 }
 
 // The fill of a pruned search, stage by stage -- all passes of a stage, then the threshold so far and the
-// next stage's cut, all on the fill's stream with no host wait.  The bound of every pair first; then the stages of
+// next stage's cut, all on the fill's stream with no host wait.  The bound of every pair first -- unless the list queues
+// the first level with a stage (the gate: behind that stage's threshold, for the pairs from it on) --; then the stages of
 // swg_prune_stages, each behind what that list queues in front of it and nothing else: the K-th best score so far (every
 // entry of d_scores is at most its sequence's true score at a kernel boundary) or, once, a caller's threshold; then the
 // stage's cut, held for all its passes.
@@ -1291,19 +1296,38 @@ static int enqueue_pruned_fill(swg_ctx *ctx, swg_db *db, const SwgPrunePlan &pr,
     uint32_t *thr = db->d_counters + SWG_PRUNE_WORD_T, *cut_word = db->d_counters + SWG_PRUNE_WORD_CUT, *gate = db->d_counters + SWG_PRUNE_WORD_GATE;
     const uint32_t n_pairs = (uint32_t)swg_db_pair_count(db);
     const SwgPruneLayout L = swg_prune_layout(db->d_pair_bound, n_pairs);
-    if (pr.kmer > 1 && pr.segments > 1)
-        HIP_TRY(ctx, swg_launch_pair_bound_kmer_seg(T.d_tok, T.d_pair_off, n_pairs, pr.kmer, (uint32_t)pr.segments, ctx->prune_colmax, ctx->kmer_first[pr.kmer - 4].d,
-                                                    ctx->kmer_first[pr.kmer - 4].bits, L.bounds, L.ids, qs));
-    else if (pr.kmer > 1)
-        HIP_TRY(ctx, swg_launch_pair_bound_kmer(T.d_tok, T.d_pair_off, n_pairs, pr.kmer, ctx->prune_colmax, ctx->kmer_first[pr.kmer - 4].d,
-                                                ctx->kmer_first[pr.kmer - 4].bits, L.bounds, L.ids, qs));
-    else
-        HIP_TRY(ctx, swg_launch_pair_bound(T.d_tok, T.d_pair_off, n_pairs, ctx->prune_colmax, L.bounds, L.ids, qs));
+    // (a caller's threshold stands in its word before anything reads it)
     if (pr.fixed) HIP_TRY(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(thr), (int)pr.fixed_T, 1, qs));
+    const std::vector<SwgPruneStage> stages = swg_prune_stages(pr, F->segs);
+    // the first level of the pairs [b, en): gated by the threshold word, or (gated_by null) of every pair from the first
+    // (only a segmented k-mer bound is ever gated: swg_prune_gate_choice; the other forms would bound [0, en) ungated)
+    auto first_level = [&](uint32_t b, uint32_t en, const uint32_t *gated_by) -> int {
+        if (pr.kmer > 1 && pr.segments > 1)
+            HIP_TRY(ctx, swg_launch_pair_bound_kmer_seg(T.d_tok, T.d_pair_off, b, en, pr.kmer, (uint32_t)pr.segments, ctx->prune_colmax, ctx->kmer_first[pr.kmer - 4].d,
+                                                        ctx->kmer_first[pr.kmer - 4].bits, gated_by, L.bounds, L.ids, qs));
+        else if (pr.kmer > 1)
+            HIP_TRY(ctx, swg_launch_pair_bound_kmer(T.d_tok, T.d_pair_off, en, pr.kmer, ctx->prune_colmax, ctx->kmer_first[pr.kmer - 4].d,
+                                                    ctx->kmer_first[pr.kmer - 4].bits, L.bounds, L.ids, qs));
+        else
+            HIP_TRY(ctx, swg_launch_pair_bound(T.d_tok, T.d_pair_off, en, ctx->prune_colmax, L.bounds, L.ids, qs));
+        return SWG_OK;
+    };
+    // Where no stage queues the first level, every pair is bounded here; where one does, the pairs in front of that
+    // stage are launched unpruned and their words say "not bounded" (swg_prune_bound_range).
+    const SwgPruneBoundRange br = swg_prune_bound_range(stages, n_pairs);
+    if (br.stage == stages.size()) {
+        const int rc = first_level(br.begin, br.end, nullptr);
+        if (rc != SWG_OK) return rc;
+    } else if (br.skip_end > br.skip_begin)
+        HIP_TRY(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(L.bounds + br.skip_begin), (int)SWG_PRUNE_NOT_BOUNDED, br.skip_end - br.skip_begin, qs));
     db->prune_stages.clear(); // (the stages cut pair by pair, for the tests)
-    for (const SwgPruneStage &st : swg_prune_stages(pr, F->segs)) {
+    for (const SwgPruneStage &st : stages) {
         if (st.queued & SWG_STAGE_THRESHOLD)
             HIP_TRY(ctx, swg_launch_prune_threshold(db->d_scores, db->d_order, (uint32_t)((size_t)db->n_bins * SWG_BIN), (uint32_t)k, db->d_hist, thr, qs));
+        if (st.queued & SWG_STAGE_BOUND) {
+            const int rc = first_level(br.begin, br.end, thr);
+            if (rc != SWG_OK) return rc;
+        }
         if (st.queued & SWG_STAGE_PREFIX_CUT) HIP_TRY(ctx, swg_launch_prune_cut(L.bounds, T.d_pair_off, st.begin, st.end, thr, cut_word, qs));
         if (st.queued & SWG_STAGE_GATE) HIP_TRY(ctx, swg_launch_prune_refine_gate(L.bounds, st.begin, st.end, thr, gate, qs));
         if (st.queued & SWG_STAGE_REFINE)
@@ -2437,7 +2461,11 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
     P->prune.refine4 = P->prune.prefix_cut || ctx->kmer_fourth_refused
                            ? 0
                            : swg_prune_refine4_choice(ka, P->prune.kmer, P->prune.segments, P->prune.refine, P->prune.refine3);
-    ctx->prune_choice = SwgPruneChoice{P->prune.kmer, P->prune.segments, P->prune.refine, P->prune.refine3, P->prune.refine4};
+    // whether the first level's launch waits for a threshold (the pairs whose colmax bound is below it are not walked)
+    ka.forced_gate = ctx->opt_prune_gate;
+    // (not under the prefix cut, which like the levels behind the first keeps to what it was measured with)
+    P->prune.gate = !P->prune.prefix_cut && swg_prune_gate_choice(ka, P->prune.kmer, P->prune.segments);
+    ctx->prune_choice = SwgPruneChoice{P->prune.kmer, P->prune.segments, P->prune.refine, P->prune.refine3, P->prune.refine4, P->prune.gate ? 1 : 0};
     return SWG_OK;
 }
 
@@ -3072,6 +3100,13 @@ extern "C" int swg_debug_prune_tables4(swg_ctx *ctx, int64_t *out)
     out[1] = (int64_t)ctx->kmer_refine4_builds;
     out[2] = ctx->kmer_fourth.d && ctx->kmer_fourth.epoch == ctx->epoch ? ctx->kmer_fourth.bits : 0;
     out[3] = ctx->kmer_fourth_refused ? 1 : 0;
+    return SWG_OK;
+}
+// ... the gate in front of the first level: out[0] = whether the search last begun took it (swg_prune_gate_choice)
+extern "C" int swg_debug_prune_gate(swg_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_gate: NULL argument");
+    out[0] = ctx->prune_choice.gate;
     return SWG_OK;
 }
 // ... and n rows of its table: out[i][0..256) = the entries of class block blocks[i] (< 22^5), an error unless the table

@@ -693,6 +693,7 @@ std::vector<SwgPruneStage> swg_prune_stages(const SwgPrunePlan &plan, const std:
     for (size_t si = 0; si < stages.size(); ++si) {
         if (si == 0 && !plan.fixed) continue; // (nothing to cut by yet)
         uint32_t q = plan.fixed ? 0u : SWG_STAGE_THRESHOLD;
+        if (plan.gate && si == (plan.fixed ? 0u : 1u)) q |= SWG_STAGE_BOUND; // (the first stage with a threshold)
         if (plan.prefix_cut) q |= SWG_STAGE_PREFIX_CUT;
         else {
             if (plan.refine && plan.fixed && si == 0 && stages.size() > 1) q |= SWG_STAGE_GATE;
@@ -706,7 +707,15 @@ std::vector<SwgPruneStage> swg_prune_stages(const SwgPrunePlan &plan, const std:
     return stages;
 }
 
-// (head: the words in front of the segments -- 5, 6 with the third level's in[4], 7 with the fourth's in[5] as well)
+SwgPruneBoundRange swg_prune_bound_range(const std::vector<SwgPruneStage> &stages, uint32_t n_pairs)
+{
+    for (size_t i = 0; i < stages.size(); ++i)
+        if (stages[i].queued & SWG_STAGE_BOUND) return SwgPruneBoundRange{i, stages[i].begin, stages.back().end, stages.front().begin, stages[i].begin};
+    return SwgPruneBoundRange{stages.size(), 0u, n_pairs, 0u, 0u};
+}
+
+// (head: the words in front of the segments -- 5, 6 with the third level's in[4], 7 with the fourth's in[5] as well, 8
+// with the gate's in[6])
 static int debug_prune_stages(const int64_t *in, int head, int64_t *out, size_t cap, size_t *n_out)
 {
     if (!in || !n_out || (cap > 0 && !out) || in[0] < 0 || in[head - 1] < 0) return SWG_ERR_ARG;
@@ -714,7 +723,8 @@ static int debug_prune_stages(const int64_t *in, int head, int64_t *out, size_t 
     plan.on = true;
     plan.head_pairs = (uint32_t)in[0], plan.fixed = in[1] != 0, plan.refine = (int)in[2], plan.prefix_cut = in[3] != 0;
     plan.refine3 = head >= 6 ? (int)in[4] : 0;
-    plan.refine4 = head == 7 ? (int)in[5] : 0;
+    plan.refine4 = head >= 7 ? (int)in[5] : 0;
+    plan.gate = head == 8 && in[6] != 0;
     std::vector<std::pair<uint32_t, uint32_t>> segments;
     for (int64_t i = 0; i < in[head - 1]; ++i) segments.emplace_back((uint32_t)in[head + 2 * i], (uint32_t)in[head + 1 + 2 * i]);
     const std::vector<SwgPruneStage> stages = swg_prune_stages(plan, segments);
@@ -726,6 +736,7 @@ static int debug_prune_stages(const int64_t *in, int head, int64_t *out, size_t 
 extern "C" int swg_debug_prune_stages(const int64_t *in, int64_t *out, size_t cap, size_t *n_out) { return debug_prune_stages(in, 5, out, cap, n_out); }
 extern "C" int swg_debug_prune_stages3(const int64_t *in, int64_t *out, size_t cap, size_t *n_out) { return debug_prune_stages(in, 6, out, cap, n_out); }
 extern "C" int swg_debug_prune_stages4(const int64_t *in, int64_t *out, size_t cap, size_t *n_out) { return debug_prune_stages(in, 7, out, cap, n_out); }
+extern "C" int swg_debug_prune_stages5(const int64_t *in, int64_t *out, size_t cap, size_t *n_out) { return debug_prune_stages(in, 8, out, cap, n_out); }
 
 // The k-mer form of the bound, on the host: what the device builds (swg_kmer_cprof_kernel,
 // swg_kmer_table_kernel) and sums (swg_pair_bound_kmer_kernel), restated for the tests.  cprof[lq][22]: query column i
@@ -1077,16 +1088,45 @@ extern "C" int swg_debug_prune_refine_choice(const int64_t *in, int64_t *out)
 // segments over byte tables 3.37 ms per search over 1 938 193 684 pair rows (section 3).
 #define SWG_REFINE3_GAIN 0.0151
 #define SWG_REFINE3_BOUND_ROW 1.74e-12
+// the range's floor: the third level's table build and walk cost at most half of what its tighter cut saves
+static bool refine3_pays(const SwgKmerAsk &a)
+{
+    if (a.table_rate <= 0 || a.fill_rate <= 0 || a.lq == 0) return false;
+    const double cost = (double)swg_kmer_entries(4) * 4 * (double)a.lq / a.table_rate + SWG_REFINE3_BOUND_ROW * (double)a.pair_rows;
+    const double gain = SWG_REFINE3_GAIN * (double)a.pair_rows / a.fill_rate;
+    return cost <= 0.5 * gain;
+}
 int swg_prune_refine3_choice(const SwgKmerAsk &a, int k, int S, int S2)
 {
     if (!a.pruned || k < 1) return 0;
     if (a.forced_refine3 == 256) return 256;
     if (a.forced_refine3 != 0 || a.forced != 0 || a.forced_segments != 0 || a.forced_refine != 0) return 0;
     if (k != 4 || S <= 1 || S2 != 128 || a.table_bits != 8) return 0;
-    if (a.table_rate <= 0 || a.fill_rate <= 0 || a.lq == 0) return 0;
-    const double cost = (double)swg_kmer_entries(4) * 4 * (double)a.lq / a.table_rate + SWG_REFINE3_BOUND_ROW * (double)a.pair_rows;
-    const double gain = SWG_REFINE3_GAIN * (double)a.pair_rows / a.fill_rate;
-    return cost <= 0.5 * gain ? 256 : 0;
+    return refine3_pays(a) ? 256 : 0;
+}
+
+// The gate in front of the first level (swg_host_internal.h has the rule in words).  Nothing smaller than the headline
+// was measured (profiles/prune_gate_ab.txt): the automatic rule keeps the third level's floor, about 2e8 pair rows at
+// 3000 columns, below which a stage's fill no longer hides the one launch moved behind the first stage.
+bool swg_prune_gate_choice(const SwgKmerAsk &a, int k, int S)
+{
+    if (!a.pruned || k <= 1 || S <= 1 || a.forced_gate == 1) return false;
+    if (a.forced_gate == 2) return true;
+    if (a.forced != 0 || a.forced_segments != 0) return false;
+    return refine3_pays(a);
+}
+
+extern "C" int swg_debug_prune_gate_choice(const int64_t *in, int64_t *out)
+{
+    SwgKmerAsk a;
+    if (!debug_kmer_ask(in, out, 8, &a)) return SWG_ERR_ARG;
+    if (!swg_prune_gate_value_ok((long)in[8])) return SWG_ERR_ARG;
+    a.forced_gate = (long)in[8];
+    int S = 0;
+    out[0] = swg_prune_kmer_choice(a, &S);
+    out[1] = S;
+    out[2] = swg_prune_gate_choice(a, (int)out[0], S) ? 1 : 0;
+    return SWG_OK;
 }
 
 extern "C" int swg_debug_prune_refine3_choice(const int64_t *in, int64_t *out)

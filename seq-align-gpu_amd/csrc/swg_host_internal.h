@@ -275,6 +275,7 @@ struct SwgPrunePlan {
     int refine3 = 0;         // the third level's segments (swg_prune_refine3_choice): 256, or 0 without one
     int refine4 = 0;         // the fourth level's segments, of the k = 5 table (swg_prune_refine4_choice): 256, or 0 without one
     bool prefix_cut = false; // option "prune_cut" = 1: a stage's list is the prefix up to its last pair that reaches T
+    bool gate = false;       // the first level's launch is gated by T and queued with a stage (swg_prune_gate_choice)
     bool fixed = false;      // a caller's threshold: every stage, the first included, is a list launch cut at fixed_T
     uint32_t fixed_T = 0;    // ... written once to the threshold word and never recomputed
 };
@@ -300,10 +301,13 @@ SwgPrunePlan swg_prune_plan(const SwgPruneAsk &a);
 // cut too and no threshold kernel runs.  A cut is the prefix cut (plan.prefix_cut), or pair by pair: the refine pass
 // where there is a second level (plan.refine) -- behind the gate on the first of several stages under a caller's
 // threshold --, the third level's (plan.refine3) behind it under the same threshold word, the fourth's (plan.refine4) behind
-// that, then the list.
+// that, then the list.  With the gate in front of the first level (plan.gate) the stage that first has a threshold --
+// the second of several, or the first under a caller's threshold -- also queues the first level's launch, behind the
+// threshold kernel and in front of everything else: gated by that threshold, over all pairs from the stage's first to the
+// range's last.  A fill whose list holds no such stage bounds every pair before its first stage, ungated.
 enum : uint32_t {
     SWG_STAGE_THRESHOLD = 1u, SWG_STAGE_PREFIX_CUT = 2u, SWG_STAGE_GATE = 4u, SWG_STAGE_REFINE = 8u, SWG_STAGE_LIST = 16u, SWG_STAGE_REFINE3 = 32u,
-    SWG_STAGE_REFINE4 = 64u
+    SWG_STAGE_REFINE4 = 64u, SWG_STAGE_BOUND = 128u
 };
 struct SwgPruneStage {
     uint32_t begin, end; // pairs
@@ -311,6 +315,17 @@ struct SwgPruneStage {
     uint32_t queued;     // SWG_STAGE_*: the kernels in front of the stage's fill launches, in that order (0: none, an uncut stage)
 };
 std::vector<SwgPruneStage> swg_prune_stages(const SwgPrunePlan &plan, const std::vector<std::pair<uint32_t, uint32_t>> &segments);
+// What the first level's launch takes under a stage list: `stage` the stage that queues it (SWG_STAGE_BOUND), or
+// stages.size() where none does -- the pairs [begin, end) = [0, n_pairs) are then bounded, ungated, before the first
+// stage.  Queued with a stage, the launch takes [begin, end) from that stage's first pair to the last stage's last, and
+// the pairs [skip_begin, skip_end) of the stages in front of it, which are launched unpruned, have their words set to
+// SWG_PRUNE_NOT_BOUNDED.
+#define SWG_PRUNE_NOT_BOUNDED 0xFFFFFFFFu
+struct SwgPruneBoundRange {
+    size_t stage;
+    uint32_t begin, end, skip_begin, skip_end;
+};
+SwgPruneBoundRange swg_prune_bound_range(const std::vector<SwgPruneStage> &stages, uint32_t n_pairs);
 // test hook: in[0..4] = head_pairs, fixed, refine, prefix_cut, the number of segments n, then n x {begin, end}; out: four
 // words per stage {begin, end, segment, queued}, copied while they fit cap stages; *n_out = the number of stages
 extern "C" int swg_debug_prune_stages(const int64_t *in, int64_t *out, size_t cap, size_t *n_out);
@@ -318,6 +333,8 @@ extern "C" int swg_debug_prune_stages(const int64_t *in, int64_t *out, size_t ca
 extern "C" int swg_debug_prune_stages3(const int64_t *in, int64_t *out, size_t cap, size_t *n_out);
 // ... and the fourth: in[0..6] = head_pairs, fixed, refine, prefix_cut, refine3, refine4, n, then the n segments
 extern "C" int swg_debug_prune_stages4(const int64_t *in, int64_t *out, size_t cap, size_t *n_out);
+// ... and the gate: in[0..7] = head_pairs, fixed, refine, prefix_cut, refine3, refine4, gate, n, then the n segments
+extern "C" int swg_debug_prune_stages5(const int64_t *in, int64_t *out, size_t cap, size_t *n_out);
 // The automatic rule of a caller's threshold ("A caller's threshold"; profiles/search_above_ab.txt): the
 // bound, list and tally kernels of a stage cost tens of microseconds whatever the range holds, a list launch one
 // dependent load per claim; a range with at least SWG_PRUNE_ABOVE_AUTO_PAIRS pairs per resident lane group has fills
@@ -367,6 +384,7 @@ struct SwgKmerAsk {
     long forced_refine = 0;   // option "prune_refine": 0 automatic, 1 off, 64 or 128
     long forced_refine3 = 0;  // option "prune_refine3": 0 automatic, 1 off, 256
     long forced_refine4 = 0;  // option "prune_refine4": 0 automatic, 1 off, 5256 (k = 5 in 256 segments)
+    long forced_gate = 0;     // option "prune_gate": 0 automatic, 1 off, 2 wherever the first level is a segmented k-mer bound
     int table_bits5 = 8;      // ... and of the k = 5 tables' (the fourth level takes bytes only)
     int table_bits = 8;       // the width of the k = 4 tables' entries for this query and scoring (swg_kmer_table_bits, "prune_table_bits")
     bool pruned = false; // swg_prune_plan's answer
@@ -417,6 +435,14 @@ extern "C" int swg_debug_prune_refine4_choice(const int64_t *in, int64_t *out);
 // computes the entries of the blocks the sequences hold.
 extern "C" int swg_debug_prune_kmer_refine4(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S4, const int8_t *flat,
                                             const uint64_t *offsets, size_t n, uint64_t *u_out);
+// The gate in front of the first level: whether the first level's launch, of (k, S), waits for a threshold
+// and leaves out the pairs whose colmax bound is below it.  Forced ("prune_gate" = 2) wherever the first level is a
+// segmented k-mer bound; off ("prune_gate" = 1); automatic only where k and S were both chosen automatically and the range
+// is one the third level's walk pays on.
+bool swg_prune_gate_choice(const SwgKmerAsk &a, int k, int S);
+inline bool swg_prune_gate_value_ok(long v) { return v == 0 || v == 1 || v == 2; }
+// test hook: in[0..7] as swg_debug_prune_refine_choice, in[8] = option "prune_gate" -> out[0..2] = k, S, gate (0 | 1)
+extern "C" int swg_debug_prune_gate_choice(const int64_t *in, int64_t *out);
 // the words of a search's counter block (swg_db::Bufs::d_counters) a pruned search uses: the threshold so far and the
 // threshold kernel's status word, then what swg_launch_prune_cut or swg_launch_prune_list writes: the pairs the stage
 // takes, the pairs skipped so far, their token blocks (64 bits)
@@ -511,6 +537,7 @@ struct SwgKmerTable {
 // fourth's S4 (0: none)
 struct SwgPruneChoice {
     int kmer = 0, segments = 0, refine = 0, refine3 = 0, refine4 = 0;
+    int gate = 0; // 1: the first level's launch is gated (swg_prune_gate_choice)
 };
 
 // One search in flight: its timing events, host-side landing buffers and what swg_search_end
@@ -602,6 +629,7 @@ struct swg_ctx {
     long opt_prune_refine = 0;   // option "prune_refine": 0 auto, 1 off, 64, 128
     long opt_prune_refine3 = 0;  // option "prune_refine3": 0 auto, 1 off, 256
     long opt_prune_refine4 = 0;  // option "prune_refine4": 0 auto, 1 off, 5256
+    long opt_prune_gate = 0;     // option "prune_gate": 0 auto, 1 off, 2 wherever the first level is segmented
     long opt_prune_table_bits = 0; // option "prune_table_bits": 0 auto (bytes where they hold every entry), 16
     long opt_prune_cut = 0;      // option "prune_cut": 0 pair by pair, 1 the prefix of the length order
     int8_t *d_kmer_cprof = nullptr;

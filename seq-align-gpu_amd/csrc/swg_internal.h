@@ -370,9 +370,10 @@ hipError_t swg_launch_kmer_table(const int8_t *d_sub, const int8_t *d_query, con
 hipError_t swg_launch_pair_bound_kmer(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, int k, const SwgColMax &cm,
                                       const void *d_table, int bits, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream);
 // ... and its ordered form over the table of S segments: the blocks in order, H[s] = max_{s' <= s} H[s'] + the block's
-// entry of segment s (or its colmax sum where that is less), the bound max_s H[s]
-hipError_t swg_launch_pair_bound_kmer_seg(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, int k, uint32_t S, const SwgColMax &cm,
-                                          const void *d_table, int bits, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream);
+// entry of segment s (or its colmax sum where that is less), the bound max_s H[s].  The pairs [begin, end); d_thr (or
+// null, and then begin = 0): the gate -- a pair whose colmax bound u1 is below d_thr[0] is not walked and keeps u1
+hipError_t swg_launch_pair_bound_kmer_seg(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, int k, uint32_t S, const SwgColMax &cm,
+                                          const void *d_table, int bits, const uint32_t *d_thr, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream);
 // d_thr[0] = the k-th largest entry of d_scores (clamped to 4095; 0 with fewer than k entries): swg_topk_hist_kernel and
 // swg_topk_threshold_kernel on `stream`; d_thr[1] is written too (the status word, not read)
 hipError_t swg_launch_prune_threshold(const int32_t *d_scores, const uint32_t *d_order, uint32_t n_slots, uint32_t k, uint32_t *d_hist,

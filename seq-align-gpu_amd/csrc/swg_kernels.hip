@@ -3290,20 +3290,48 @@ __device__ __forceinline__ void swg_seg_chunk(const uint32_t (&ux)[NB], const ui
     }
 }
 
-template <int K, int WD, class E>
-__global__ __launch_bounds__(256) void swg_pair_bound_kmer_seg_kernel(const uint4 *tok, const uint32_t *pair_off, uint32_t n_pairs, SwgColMax cm,
-                                                                      const E *table, uint32_t S, uint32_t *bound, uint32_t *ids)
+// GATED ("The gate in front of the first level"): the launch takes the pairs [begin, n_pairs) and a threshold
+// word.  A pair's lane group first sums colmax over the pair's token rows -- swg_pair_bound_kernel's U_1, the same
+// residue table, reset, padding and shorter-sequence rules -- and a pair whose u1 = max(U_1x, U_1y) is below T leaves
+// with bound[p] = u1: every level's bound is at most u1, so no list and no hit can tell.  T = 0 gates nothing.  Without
+// GATED begin is 0 and thr is not read: the body is then the kernel of every search that does not take the gate.
+template <int K, int WD, class E, bool GATED>
+__device__ __forceinline__ void swg_pair_bound_kmer_seg_body(const uint4 *tok, const uint32_t *pair_off, uint32_t begin, uint32_t n_pairs, const SwgColMax &cm,
+                                                             const E *table, uint32_t S, const uint32_t *thr, uint32_t *bound, uint32_t *ids)
 {
     __shared__ uint32_t lut[32]; // residue index -> class | colmax << 8
     if (threadIdx.x < 32u) lut[threadIdx.x] = swg_kmer_class(threadIdx.x) | (uint32_t)cm.v[threadIdx.x] << 8;
     __syncthreads();
-    const uint32_t p = blockIdx.x * (256u / WD) + threadIdx.x / WD, l = threadIdx.x & (WD - 1u);
+    const uint32_t p = (GATED ? begin : 0u) + blockIdx.x * (256u / WD) + threadIdx.x / WD, l = threadIdx.x & (WD - 1u);
     const uint32_t C = SWG_KMER_CLASSES;
     const bool has = l < S;
     const E *tl = table + (has ? l : 0u);
     const uint32_t m1 = (l & 7u) >= 1u ? 0xFFFFFFFFu : 0u, m2 = (l & 7u) >= 2u ? 0xFFFFFFFFu : 0u, m4 = (l & 7u) >= 4u ? 0xFFFFFFFFu : 0u;
     uint32_t hx = 0u, hy = 0u;
-    if (p < n_pairs) { // (the same for all lanes of a group, and so is every loop count below)
+    bool walk = p < n_pairs; // (the same for all lanes of a group, and so is every loop count below)
+    if (GATED && walk) {
+        const uint32_t e = pair_off[p + 1u];
+        uint32_t sx = 0u, sy = 0u;
+        for (uint32_t b = pair_off[p] + l; b < e; b += WD) {
+            const uint4 k = tok[b];
+            sx += (lut[(k.x >> 3) & 31u] >> 8) + (lut[(k.y >> 3) & 31u] >> 8) + (lut[(k.z >> 3) & 31u] >> 8) + (lut[(k.w >> 3) & 31u] >> 8);
+            sy += (lut[(k.x >> 11) & 31u] >> 8) + (lut[(k.y >> 11) & 31u] >> 8) + (lut[(k.z >> 11) & 31u] >> 8) + (lut[(k.w >> 11) & 31u] >> 8);
+        }
+#pragma unroll
+        for (int d = WD / 2; d >= 1; d >>= 1) {
+            sx += (uint32_t)__shfl_xor((int)sx, d, WD);
+            sy += (uint32_t)__shfl_xor((int)sy, d, WD);
+        }
+        const uint32_t u1 = sx > sy ? sx : sy;
+        if (u1 < thr[0]) {
+            if (l == WD - 1u) {
+                bound[p] = u1;
+                ids[p] = p;
+            }
+            walk = false;
+        }
+    }
+    if (walk) {
         const uint32_t b0 = pair_off[p], e = pair_off[p + 1u];
         uint32_t tail = b0;
         if (K == 5) {
@@ -3348,39 +3376,68 @@ __global__ __launch_bounds__(256) void swg_pair_bound_kmer_seg_kernel(const uint
         }
     }
     const uint32_t h = hx > hy ? hx : hy, u = swg_seg_prefix_max<WD>(h, m1, m2, m4);
-    if (p < n_pairs && l == WD - 1u) {
+    if ((GATED ? walk : p < n_pairs) && l == WD - 1u) {
         bound[p] = u;
         ids[p] = p;
     }
 }
 
-template <int K, class E>
-static void swg_launch_pair_bound_kmer_seg_k(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, const SwgColMax &cm,
-                                             const E *d_table, uint32_t S, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream)
+template <int K, int WD, class E>
+__global__ __launch_bounds__(256) void swg_pair_bound_kmer_seg_kernel(const uint4 *tok, const uint32_t *pair_off, uint32_t n_pairs, SwgColMax cm,
+                                                                      const E *table, uint32_t S, uint32_t *bound, uint32_t *ids)
 {
-    if (S <= 8u)
-        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 8, E>), dim3((n_pairs + 31u) / 32u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids);
-    else if (S <= 16u)
-        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 16, E>), dim3((n_pairs + 15u) / 16u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids);
-    else
-        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 32, E>), dim3((n_pairs + 7u) / 8u), dim3(256), 0, stream, d_tok, d_pair_off, n_pairs, cm, d_table, S, d_bound, d_ids);
+    swg_pair_bound_kmer_seg_body<K, WD, E, false>(tok, pair_off, 0u, n_pairs, cm, table, S, nullptr, bound, ids);
 }
 
-hipError_t swg_launch_pair_bound_kmer_seg(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, int k, uint32_t S, const SwgColMax &cm,
-                                          const void *d_table, int bits, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream)
+// ... behind the gate: the pairs [begin, end) under the threshold word thr
+template <int K, int WD, class E>
+__global__ __launch_bounds__(256) void swg_pair_bound_kmer_seg_gated_kernel(const uint4 *tok, const uint32_t *pair_off, uint32_t begin, uint32_t end,
+                                                                            SwgColMax cm, const E *table, uint32_t S, const uint32_t *thr, uint32_t *bound,
+                                                                            uint32_t *ids)
 {
-    if ((k != 4 && k != 5) || S == 0u || S > SWG_KMER_MAX_SEGMENTS || (bits != 8 && bits != 16)) return hipErrorInvalidValue;
-    if (n_pairs == 0) return hipSuccess;
+    swg_pair_bound_kmer_seg_body<K, WD, E, true>(tok, pair_off, begin, end, cm, table, S, thr, bound, ids);
+}
+
+template <int K, class E>
+static void swg_launch_pair_bound_kmer_seg_k(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, const SwgColMax &cm,
+                                             const E *d_table, uint32_t S, const uint32_t *d_thr, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream)
+{
+    const uint32_t n = end - begin;
+    if (d_thr) {
+        if (S <= 8u)
+            hipLaunchKernelGGL((swg_pair_bound_kmer_seg_gated_kernel<K, 8, E>), dim3((n + 31u) / 32u), dim3(256), 0, stream, d_tok, d_pair_off, begin, end, cm, d_table, S, d_thr, d_bound, d_ids);
+        else if (S <= 16u)
+            hipLaunchKernelGGL((swg_pair_bound_kmer_seg_gated_kernel<K, 16, E>), dim3((n + 15u) / 16u), dim3(256), 0, stream, d_tok, d_pair_off, begin, end, cm, d_table, S, d_thr, d_bound, d_ids);
+        else
+            hipLaunchKernelGGL((swg_pair_bound_kmer_seg_gated_kernel<K, 32, E>), dim3((n + 7u) / 8u), dim3(256), 0, stream, d_tok, d_pair_off, begin, end, cm, d_table, S, d_thr, d_bound, d_ids);
+        return;
+    }
+    if (S <= 8u)
+        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 8, E>), dim3((n + 31u) / 32u), dim3(256), 0, stream, d_tok, d_pair_off, n, cm, d_table, S, d_bound, d_ids);
+    else if (S <= 16u)
+        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 16, E>), dim3((n + 15u) / 16u), dim3(256), 0, stream, d_tok, d_pair_off, n, cm, d_table, S, d_bound, d_ids);
+    else
+        hipLaunchKernelGGL((swg_pair_bound_kmer_seg_kernel<K, 32, E>), dim3((n + 7u) / 8u), dim3(256), 0, stream, d_tok, d_pair_off, n, cm, d_table, S, d_bound, d_ids);
+}
+
+// The pairs [begin, end).  d_thr (or null): the threshold word of the gated form; without it the launch is the ungated
+// kernel's over every pair from the first (begin = 0).
+hipError_t swg_launch_pair_bound_kmer_seg(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, int k, uint32_t S, const SwgColMax &cm,
+                                          const void *d_table, int bits, const uint32_t *d_thr, uint32_t *d_bound, uint32_t *d_ids, hipStream_t stream)
+{
+    if ((k != 4 && k != 5) || S == 0u || S > SWG_KMER_MAX_SEGMENTS || (bits != 8 && bits != 16) || end < begin || (!d_thr && begin != 0u))
+        return hipErrorInvalidValue;
+    if (end == begin) return hipSuccess;
     const uint8_t *t8 = static_cast<const uint8_t *>(d_table);
     const uint16_t *t16 = static_cast<const uint16_t *>(d_table);
     if (k == 5 && bits == 8)
-        swg_launch_pair_bound_kmer_seg_k<5>(d_tok, d_pair_off, n_pairs, cm, t8, S, d_bound, d_ids, stream);
+        swg_launch_pair_bound_kmer_seg_k<5>(d_tok, d_pair_off, begin, end, cm, t8, S, d_thr, d_bound, d_ids, stream);
     else if (k == 5)
-        swg_launch_pair_bound_kmer_seg_k<5>(d_tok, d_pair_off, n_pairs, cm, t16, S, d_bound, d_ids, stream);
+        swg_launch_pair_bound_kmer_seg_k<5>(d_tok, d_pair_off, begin, end, cm, t16, S, d_thr, d_bound, d_ids, stream);
     else if (bits == 8)
-        swg_launch_pair_bound_kmer_seg_k<4>(d_tok, d_pair_off, n_pairs, cm, t8, S, d_bound, d_ids, stream);
+        swg_launch_pair_bound_kmer_seg_k<4>(d_tok, d_pair_off, begin, end, cm, t8, S, d_thr, d_bound, d_ids, stream);
     else
-        swg_launch_pair_bound_kmer_seg_k<4>(d_tok, d_pair_off, n_pairs, cm, t16, S, d_bound, d_ids, stream);
+        swg_launch_pair_bound_kmer_seg_k<4>(d_tok, d_pair_off, begin, end, cm, t16, S, d_thr, d_bound, d_ids, stream);
     return hipGetLastError();
 }
 
