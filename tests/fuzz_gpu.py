@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised parity soak: random databases (tiny to long-tailed), query lengths, scoring tables,
 gap scores and engine options through the C ABI, every score against the int32 oracle, and the hits of a
-search without a score array (k small, or around the number of sequences) against the oracle's top-K.
+search without a score array (k small, or around the number of sequences; option prune 1 or 2) against the oracle's top-K.
 scoring "edges": the tables and gap points of tests/scoring_edges.py (entries over all of int8, gap magnitudes at the
 hand-overs between cell forms) with split_db's relatives planted among the random sequences.
 usage: python tests/fuzz_gpu.py [seconds] [seed] [classic|edges]"""
@@ -40,6 +40,7 @@ def main(budget=300.0, seed=1, scoring="classic"):
     assert scoring in ("classic", "edges")
     rng = np.random.default_rng(seed)
     rng_k = np.random.default_rng([seed, 4096])   # (its own stream: the cases of a seed stay what they were)
+    rng_p = np.random.default_rng([seed, 4097])   # (and so has option prune of the hits-only search)
     ctx = swg.Context(0)
     mats = ["BLOSUM62", "PAM250", "BLOSUM45"]
     t_end = time.time() + budget
@@ -96,6 +97,7 @@ def main(budget=300.0, seed=1, scoring="classic"):
             ctx.set_option(k, 1)
         ctx.set_option("long_helps", 0)
         ctx.set_option("batch", 8); ctx.set_option("batch_blocks", 0)
+        ctx.set_option("prune", 1)
         opts = {}
         r = rng.random()
         if r < 0.25:
@@ -139,9 +141,12 @@ def main(budget=300.0, seed=1, scoring="classic"):
             return 1
         # hits only (the top-K is selected on the device for k <= 4096): k around the number of sequences, or small
         k_hits = max(1, len(lens) + int(rng_k.integers(-2, 3))) if rng_k.random() < 0.5 else int(rng_k.integers(1, 20))
+        # pruned wherever it is structurally possible (prune = 2: a database this small is otherwise left alone), or as shipped
+        prune = int(rng_p.integers(1, 3))
+        ctx.set_option("prune", prune if go <= 0 and ge <= 0 else 1)
         none, hits_only, _ = ctx.search(db, want_scores=False, k=k_hits)
         if none is not None or hits_only != orc.topk(want, k_hits):
-            print("TOP-K MISMATCH case", cases, "n", len(lens), "lq", lq, "k", k_hits, "gaps", go, ge, "opts", opts, "stats", st)
+            print("TOP-K MISMATCH case", cases, "n", len(lens), "lq", lq, "k", k_hits, "gaps", go, ge, "opts", opts, "prune", prune, ctx.prune_last(), "stats", st)
             return 1
         db.close()
         cases += 1
