@@ -319,7 +319,14 @@ int swg_search_end(swg_ctx *ctx, int ticket, int32_t *scores_out, swg_hit *topk_
  * was chosen automatically and the range is large enough (the 10M-sequence database: yes; smaller ones: no).  The table
  * holds bytes only: a query whose blocks of 5 can score above 255 (a PSSM entry of 52 or more) is searched without the
  * level under every value, and so is every search of a context whose device had no room for the table -- neither is an
- * error.  "prune_gate" (default 0): where the first-level bound is a k-mer bound in segments, its kernel can wait for a
+ * error.  "prune_refine5" (default 0): the pairs that still reach the threshold after the fourth level are bounded a fifth
+ * time by the fourth level's walk with the query columns jumped over between two blocks charged as a gap, over a second
+ * table of 5-residue blocks in 256 segments (another 1.32 GB, about 3.3 ms per query of 3000 columns), and the least
+ * bound holds; 5256 on, behind whatever the other levels are; 1 off; 0 automatic -- on where the fourth level was chosen
+ * automatically, the range is large enough and the threshold is the K-th best score (under swg_search_above's threshold
+ * the level runs only where it is forced).  It needs gap_extend < 0 and entries that are bytes (5 x (the largest
+ * substitution score - gap_extend) <= 255); a search that has neither, or a context whose device had no room for the
+ * table, runs without the level under every value -- not an error.  "prune_gate" (default 0): where the first-level bound is a k-mer bound in segments, its kernel can wait for a
  * threshold -- the K-th best score behind the first stage, or swg_search_above's -- and leave out every pair whose
  * colmax bound is already below it (no other bound of the pair can be above that one, so no hit and no count changes);
  * the pairs of the first stage, which is never cut, are then not bounded at all.  2 on wherever the first level is

@@ -309,6 +309,11 @@ _sig("swg_debug_prune_kmer_refine4", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.
 _sig("swg_debug_prune_table_bits", C.c_int, [_vp, _vp, C.c_size_t, C.c_int])
 _sig("swg_debug_prune_tables", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_tables4", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_kmer_refine5", C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp])
+_sig("swg_debug_prune_refine5_read", C.c_int, [_vp, _vp, C.c_size_t, _vp])
+_sig("swg_debug_prune_tables5", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_refine5_choice", C.c_int, [_vp, _vp])
+_sig("swg_debug_prune_stages6", C.c_int, [_vp, _vp, C.c_size_t, _vp])
 _sig("swg_debug_prune_refine4_read", C.c_int, [_vp, _vp, C.c_size_t, _vp])
 _sig("swg_debug_prune_refine4_choice", C.c_int, [_vp, _vp])
 _sig("swg_debug_prune_gate_choice", C.c_int, [_vp, _vp])
@@ -753,6 +758,30 @@ def debug_prune_kmer_refine4(rows, query, gap_open, gap_extend, segments, flat, 
     return u[:n]
 
 
+REFINE5_EXPLICIT = 1   # N of the fifth level's walk: the segments between two chains' ends taken one by one
+
+
+def debug_prune_kmer_refine5(rows, query, gap_open, gap_extend, segments, flat, offsets, explicit=0):
+    """Test hook (no device needed): the host mirror of a fifth-level bound -- the fourth level's blocks over
+    `segments` (256) segments, the query columns jumped over between two blocks charged at -gap_extend each.  explicit: N
+    of the walk (0: REFINE5_EXPLICIT; `segments` or more: the exact form).  -> U uint64[n], or None where the level is
+    off (gap_extend = 0, or second entries that are no bytes)."""
+    r, rp = _i8(rows)
+    lq = r.size // 32
+    qp = None
+    if query is not None:
+        q, qp = _i8(query)
+        lq = q.size
+    f, fp = _i8(flat)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = off.size - 1
+    u = np.zeros(max(n, 1), dtype=np.uint64)
+    on = C.c_int(0)
+    _check(lib.swg_debug_prune_kmer_refine5(rp, qp, lq, int(gap_open), int(gap_extend), int(segments), int(explicit), fp, off.ctypes.data_as(_vp), n,
+                                            u.ctypes.data_as(_vp), C.byref(on)))
+    return u[:n] if on.value else None
+
+
 def debug_prune_table_bits(rows, query, k=4):
     """Test hook (no device needed): the width of the k-mer tables' entries for this query (rows / query as
     debug_prune_bound takes them) at k = 4 or 5 under option prune_table_bits = 0 -> 8 where k x the largest colmax entry
@@ -790,6 +819,21 @@ def debug_prune_refine4_choice(forced=0, segments=0, refine=0, refine3=0, refine
     a = np.array([forced, pruned, lq, pair_rows, table_rate, fill_rate, segments, refine, refine3, table_bits, refine4, table_bits5], dtype=np.int64)
     out = np.zeros(5, dtype=np.int64)
     _check(lib.swg_debug_prune_refine4_choice(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
+    return tuple(int(v) for v in out)
+
+
+PRUNE_REFINE5_FORCED = 5256   # option "prune_refine5": both k = 5 tables in 256 segments
+
+
+def debug_prune_refine5_choice(forced=0, segments=0, refine=0, refine3=0, refine4=0, refine5=0, table_bits=8, table_bits5=8, admitted=True,
+                               fixed=False, pruned=1, lq=3000, pair_rows=1900000000, table_rate=0, fill_rate=0):
+    """Test hook (no device needed): debug_prune_refine4_choice with option prune_refine5 and whether the query and scoring
+    admit the fifth level (gap_extend < 0 and second entries that are bytes); fixed: a caller's threshold (search_above)
+    -> (k, S, S2, S3, S4, S5): S5 = 256 with a fifth level, 0 without."""
+    a = np.array([forced, pruned, lq, pair_rows, table_rate, fill_rate, segments, refine, refine3, table_bits, refine4, table_bits5, refine5,
+                  1 if admitted else 0, 1 if fixed else 0], dtype=np.int64)
+    out = np.zeros(6, dtype=np.int64)
+    _check(lib.swg_debug_prune_refine5_choice(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp)))
     return tuple(int(v) for v in out)
 
 
@@ -874,21 +918,22 @@ def debug_above_multi_route(option=0, admitted=True, single_pruned=False):
 
 # a stage's fourth word: (bit, name) in queue order (the third level's walk is bit 5, queued between the second's and the list)
 PRUNE_STAGE_QUEUED = ("threshold", "prefix_cut", "gate", "refine", "list")
-_PRUNE_STAGE_BITS = ((0, "threshold"), (7, "bound"), (1, "prefix_cut"), (2, "gate"), (3, "refine"), (5, "refine3"), (6, "refine4"), (4, "list"))
+_PRUNE_STAGE_BITS = ((0, "threshold"), (7, "bound"), (1, "prefix_cut"), (2, "gate"), (3, "refine"), (5, "refine3"), (6, "refine4"), (8, "refine5"),
+                     (4, "list"))
 
 
-def debug_prune_stages(segments, head_pairs=0, fixed=False, refine=0, prefix_cut=False, refine3=0, refine4=0, gate=False):
+def debug_prune_stages(segments, head_pairs=0, fixed=False, refine=0, prefix_cut=False, refine3=0, refine4=0, gate=False, refine5=0):
     """Test hook (no device needed): the stages of a pruned fill over the pair ranges `segments` [(begin, end), ...] and
     what is queued in front of each (swg_prune_stages) -> [(begin, end, segment index, names in queue order: those of
     PRUNE_STAGE_QUEUED, and "refine3" then "refine4" in front of "list"), ...].  head_pairs, fixed (a caller's threshold),
     refine, refine3 and refine4 (the second, third and fourth levels' segments, 0: none) and prefix_cut are the plan's.
     gate (the plan's: swg_debug_prune_stages5): "bound", the first level's gated launch, sits behind "threshold" on the
-    stage that first has one."""
-    head = [head_pairs, fixed, refine, prefix_cut, refine3, refine4] + ([1] if gate else [])
+    stage that first has one.  refine5 (the fifth level's segments: swg_debug_prune_stages6): "refine5" behind "refine4"."""
+    head = [head_pairs, fixed, refine, prefix_cut, refine3, refine4] + ([1 if gate else 0, refine5] if refine5 else [1] if gate else [])
     a = np.array(head + [len(segments)] + [int(v) for sg in segments for v in sg], dtype=np.int64)
     out = np.zeros((2 * len(segments) + 1, 4), dtype=np.int64)
     n = C.c_size_t(0)
-    hook = lib.swg_debug_prune_stages5 if gate else lib.swg_debug_prune_stages4
+    hook = lib.swg_debug_prune_stages6 if refine5 else lib.swg_debug_prune_stages5 if gate else lib.swg_debug_prune_stages4
     _check(hook(a.ctypes.data_as(_vp), out.ctypes.data_as(_vp), out.shape[0], C.byref(n)))
     return [(int(b), int(e), int(sg), tuple(name for i, name in _PRUNE_STAGE_BITS if int(qd) >> i & 1))
             for b, e, sg, qd in out[:n.value]]
@@ -1764,6 +1809,21 @@ class Context:
         out = np.zeros(4, dtype=np.int64)
         _check(lib.swg_debug_prune_tables4(self.handle, out.ctypes.data_as(_vp)), self.handle)
         return {"refine4": int(out[0]), "refine4_builds": int(out[1]), "bits": int(out[2]), "refused": bool(out[3])}
+
+    def debug_prune_tables5(self):
+        """Test hook: the fifth level (swg_debug_prune_tables5) -> dict: refine5 (S5 of the search last begun, 0: none),
+        refine5_builds (of its second table), bits (of that table if it holds the current query and scoring, else 0),
+        refused (its allocation failed once on this context)."""
+        out = np.zeros(4, dtype=np.int64)
+        _check(lib.swg_debug_prune_tables5(self.handle, out.ctypes.data_as(_vp)), self.handle)
+        return {"refine5": int(out[0]), "refine5_builds": int(out[1]), "bits": int(out[2]), "refused": bool(out[3])}
+
+    def debug_prune_refine5_read(self, blocks):
+        """Test hook: rows of the fifth level's second table -> uint16[len(blocks), 256] (as debug_prune_refine4_read)."""
+        b = np.ascontiguousarray(blocks, dtype=np.uint32)
+        out = np.zeros((max(b.size, 1), KMER_REFINE4_SEGMENTS), dtype=np.uint16)
+        _check(lib.swg_debug_prune_refine5_read(self.handle, b.ctypes.data_as(_vp), b.size, out.ctypes.data_as(_vp)), self.handle)
+        return out[:b.size]
 
     def debug_prune_gate(self):
         """Test hook: whether the search last begun took the gate in front of the first level (option prune_gate)."""

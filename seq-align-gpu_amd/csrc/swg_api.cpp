@@ -262,6 +262,7 @@ extern "C" void swg_destroy(swg_ctx *ctx)
     (void)hipFree(ctx->kmer_second.d);
     (void)hipFree(ctx->kmer_third.d);
     (void)hipFree(ctx->kmer_fourth.d);
+    (void)hipFree(ctx->kmer_fifth.d);
     (void)hipFree(ctx->d_profile[0]);
     (void)hipFree(ctx->d_profile[1]);
     (void)hipFree(ctx->d_profile[2]);
@@ -379,6 +380,10 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
         if (!swg_prune_refine4_value_ok(value))
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_refine4 must be 0 (auto), 1 (off) or 5256 (the fourth-level bound's table: k = 5 in 256 segments)");
         ctx->opt_prune_refine4 = value;
+    } else if (!strcmp(key, "prune_refine5")) {
+        if (!swg_prune_refine5_value_ok(value))
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_refine5 must be 0 (auto), 1 (off) or 5256 (the fifth-level bound: both k = 5 tables in 256 segments)");
+        ctx->opt_prune_refine5 = value;
     } else if (!strcmp(key, "prune_gate")) {
         if (!swg_prune_gate_value_ok(value))
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_gate must be 0 (auto), 1 (off) or 2 (wherever the first-level bound is a segmented k-mer bound)");
@@ -1341,6 +1346,11 @@ static int enqueue_pruned_fill(swg_ctx *ctx, swg_db *db, const SwgPrunePlan &pr,
         if (st.queued & SWG_STAGE_REFINE4)
             HIP_TRY(ctx, swg_launch_pair_bound_refine(T.d_tok, T.d_pair_off, st.begin, st.end, (uint32_t)pr.refine4, ctx->prune_colmax, ctx->kmer_fourth.d,
                                                       ctx->kmer_fourth.bits, st.queued & SWG_STAGE_GATE ? gate : thr, L.bounds, qs, 5));
+        // (the fifth: the same blocks over both k = 5 tables, the columns between two blocks charged)
+        if (st.queued & SWG_STAGE_REFINE5)
+            HIP_TRY(ctx, swg_launch_pair_bound_refine5(T.d_tok, T.d_pair_off, st.begin, st.end, ctx->prune_colmax, ctx->kmer_fourth.d, ctx->kmer_fifth.d,
+                                                       (uint32_t)ctx->query_len(), (uint32_t)-(long)ctx->gap_extend, st.queued & SWG_STAGE_GATE ? gate : thr,
+                                                       L.bounds, qs));
         if (st.queued & SWG_STAGE_LIST) {
             const size_t rec = db->prune_stages.size() / 2;
             HIP_TRY(ctx, swg_launch_prune_list(L.bounds, T.d_pair_off, st.begin, st.end, thr, L.tiles, L.lists + st.begin, cut_word,
@@ -2461,11 +2471,16 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
     P->prune.refine4 = P->prune.prefix_cut || ctx->kmer_fourth_refused
                            ? 0
                            : swg_prune_refine4_choice(ka, P->prune.kmer, P->prune.segments, P->prune.refine, P->prune.refine3);
+    // (the fifth: e > 0, second entries that are bytes, and like the fourth a buffer that could be allocated)
+    ka.forced_refine5 = ctx->opt_prune_refine5;
+    ka.fixed = P->prune.fixed;
+    ka.refine5_ok = ctx->gap_extend <= 0 && swg_kmer_refine5_admitted(ctx->prune_colmax, (int)std::min<long>(-(long)ctx->gap_extend, 65536), ka.lq);
+    P->prune.refine5 = P->prune.prefix_cut || ctx->kmer_fourth_refused || ctx->kmer_fifth_refused ? 0 : swg_prune_refine5_choice(ka, P->prune.kmer, P->prune.refine4);
     // whether the first level's launch waits for a threshold (the pairs whose colmax bound is below it are not walked)
     ka.forced_gate = ctx->opt_prune_gate;
     // (not under the prefix cut, which like the levels behind the first keeps to what it was measured with)
     P->prune.gate = !P->prune.prefix_cut && swg_prune_gate_choice(ka, P->prune.kmer, P->prune.segments);
-    ctx->prune_choice = SwgPruneChoice{P->prune.kmer, P->prune.segments, P->prune.refine, P->prune.refine3, P->prune.refine4, P->prune.gate ? 1 : 0};
+    ctx->prune_choice = SwgPruneChoice{P->prune.kmer, P->prune.segments, P->prune.refine, P->prune.refine3, P->prune.refine4, P->prune.gate ? 1 : 0, P->prune.refine5};
     return SWG_OK;
 }
 
@@ -2474,7 +2489,8 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
 // copy of the query a set_query queued there and behind any search still in flight, in front of the bound kernel that
 // reads it: the rule the profiles follow (ensure_profile_cols).  A table that holds (epoch, k, S) already is left alone; it
 // grows when S x entries does.  Which (k, S) a table may hold is the caller's to say.
-static int ensure_kmer_table(swg_ctx *ctx, SwgKmerTable *t, int k, int S)
+// spans: the fifth level's second entries instead (swg_kmer_table5_kernel<E, true>), of k = 5 as bytes.
+static int ensure_kmer_table(swg_ctx *ctx, SwgKmerTable *t, int k, int S, bool spans = false)
 {
     const int bits = kmer_table_bits(ctx, k);
     if (t->holds(ctx->epoch, k, S, bits)) return SWG_OK;
@@ -2487,9 +2503,10 @@ static int ensure_kmer_table(swg_ctx *ctx, SwgKmerTable *t, int k, int S)
     // (gap scores: a gap's first residue costs open + extend, every further one extend -- SwgSearchPlan's go / ge)
     const long go = (long)ctx->gap_open + ctx->gap_extend, ge = ctx->gap_extend;
     HIP_TRY(ctx, swg_launch_kmer_table(ctx->d_sub, ctx->d_query, ctx->query_pssm ? ctx->d_pssm : nullptr, (uint32_t)lq, (uint32_t)-go, (uint32_t)-ge, k,
-                                       (uint32_t)S, ctx->d_kmer_cprof, t->d, bits, ctx->stream));
+                                       (uint32_t)S, ctx->d_kmer_cprof, t->d, bits, ctx->stream, spans));
     t->epoch = ctx->epoch, t->k = k, t->segments = S, t->bits = bits;
-    ++(t == &ctx->kmer_fourth  ? ctx->kmer_refine4_builds
+    ++(t == &ctx->kmer_fifth   ? ctx->kmer_refine5_builds
+       : t == &ctx->kmer_fourth ? ctx->kmer_refine4_builds
        : t == &ctx->kmer_third ? ctx->kmer_refine3_builds
        : t == &ctx->kmer_second ? ctx->kmer_refine_builds
                                 : ctx->kmer_builds);
@@ -2499,9 +2516,9 @@ static int ensure_kmer_table(swg_ctx *ctx, SwgKmerTable *t, int k, int S)
 // The fourth level's table is 1.32 GB: its buffer is allocated in front of the search that first wants it, and an
 // allocation that fails is no error -- the search, and every later one of this context, runs without the level (the
 // capacity is written only once the buffer stands).  -> whether the buffer stands.
-static bool reserve_kmer_fourth(swg_ctx *ctx)
+static bool reserve_kmer_fourth(swg_ctx *ctx, bool fifth = false)
 {
-    SwgKmerTable *t = &ctx->kmer_fourth;
+    SwgKmerTable *t = fifth ? &ctx->kmer_fifth : &ctx->kmer_fourth;
     const size_t bytes = (size_t)swg_kmer_entries(5) * SWG_KMER_REFINE4_SEGMENTS;
     if (t->d && t->cap >= bytes) return true;
     (void)hipFree(t->d);
@@ -2509,7 +2526,7 @@ static bool reserve_kmer_fourth(swg_ctx *ctx)
     uint8_t *d = nullptr;
     if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&d, bytes) != hipSuccess) {
         (void)hipGetLastError(); // (taken: the search goes on)
-        ctx->kmer_fourth_refused = true;
+        (fifth ? ctx->kmer_fifth_refused : ctx->kmer_fourth_refused) = true;
         return false;
     }
     t->d = d, t->cap = bytes;
@@ -2544,6 +2561,12 @@ static int prepare_prune(swg_ctx *ctx, swg_db *db, const SwgPrunePlan &pr)
         if (pr.refine4 != (int)SWG_KMER_REFINE4_SEGMENTS || !swg_kmer_refine4_admitted(kmer_table_bits(ctx, 5)))
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the fourth-level bound's table: %d segments (256) of bytes", pr.refine4);
         if ((rc = ensure_kmer_table(ctx, &ctx->kmer_fourth, 5, pr.refine4)) != SWG_OK) return rc;
+    }
+    if (pr.refine5) { // (behind the table of (5, 256), which it reads as well -- with or without a fourth level's walk)
+        if (pr.refine5 != (int)SWG_KMER_REFINE4_SEGMENTS || !swg_kmer_refine4_admitted(kmer_table_bits(ctx, 5)))
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the fifth-level bound's tables: %d segments (256) of bytes", pr.refine5);
+        if ((rc = ensure_kmer_table(ctx, &ctx->kmer_fourth, 5, pr.refine5)) != SWG_OK) return rc;
+        if ((rc = ensure_kmer_table(ctx, &ctx->kmer_fifth, 5, pr.refine5, true)) != SWG_OK) return rc;
     }
     swg_db::Bufs &b = db->bufs[ctx->cur - ctx->slots];
     const size_t n_pairs = (size_t)swg_db_pair_count(db);
@@ -2758,6 +2781,9 @@ static int search_begin(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, bo
     if ((rc = plan_search(ctx, db, allow_autotune, &S->plan)) != SWG_OK) return rc;
     if ((rc = plan_prune(ctx, db, want_scores, k, &S->plan)) != SWG_OK) return rc;
     if (S->plan.prune.refine4 && !reserve_kmer_fourth(ctx)) S->plan.prune.refine4 = 0, ctx->prune_choice.refine4 = 0;
+    // (the fifth level reads the fourth's table and its own; without either buffer the search runs without it -- and where
+    // it was chosen behind an automatic fourth level that is now off, without both)
+    if (S->plan.prune.refine5 && (!reserve_kmer_fourth(ctx) || !reserve_kmer_fourth(ctx, true))) S->plan.prune.refine5 = 0, ctx->prune_choice.refine5 = 0;
     if ((rc = prepare_search(ctx, db, S->plan)) != SWG_OK) return rc;
     if ((rc = enqueue_fill(ctx, db, S->plan, S)) != SWG_OK) return rc;
     if ((rc = enqueue_rescore(ctx, db, S->plan, S)) != SWG_OK) return rc;
@@ -3102,6 +3128,17 @@ extern "C" int swg_debug_prune_tables4(swg_ctx *ctx, int64_t *out)
     out[3] = ctx->kmer_fourth_refused ? 1 : 0;
     return SWG_OK;
 }
+// ... the fifth level: out[0..3] = S5 of the search last begun (0: no fifth level), builds of its second table so far, 8
+// if that table holds the current query and scoring (0: not), whether its allocation was refused
+extern "C" int swg_debug_prune_tables5(swg_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_tables5: NULL argument");
+    out[0] = ctx->prune_choice.refine5;
+    out[1] = (int64_t)ctx->kmer_refine5_builds;
+    out[2] = ctx->kmer_fifth.d && ctx->kmer_fifth.epoch == ctx->epoch ? ctx->kmer_fifth.bits : 0;
+    out[3] = ctx->kmer_fifth_refused ? 1 : 0;
+    return SWG_OK;
+}
 // ... the gate in front of the first level: out[0] = whether the search last begun took it (swg_prune_gate_choice)
 extern "C" int swg_debug_prune_gate(swg_ctx *ctx, int64_t *out)
 {
@@ -3111,17 +3148,27 @@ extern "C" int swg_debug_prune_gate(swg_ctx *ctx, int64_t *out)
 }
 // ... and n rows of its table: out[i][0..256) = the entries of class block blocks[i] (< 22^5), an error unless the table
 // holds the current query and scoring
+static int debug_prune_refine45_read(swg_ctx *ctx, const SwgKmerTable &t, const uint32_t *blocks, size_t n, uint16_t *out);
 extern "C" int swg_debug_prune_refine4_read(swg_ctx *ctx, const uint32_t *blocks, size_t n, uint16_t *out)
 {
     if (!ctx || (n > 0 && (!blocks || !out))) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_refine4_read: NULL argument");
-    const SwgKmerTable &t = ctx->kmer_fourth;
+    return debug_prune_refine45_read(ctx, ctx->kmer_fourth, blocks, n, out);
+}
+// ... and of the fifth level's second table
+extern "C" int swg_debug_prune_refine5_read(swg_ctx *ctx, const uint32_t *blocks, size_t n, uint16_t *out)
+{
+    if (!ctx || (n > 0 && (!blocks || !out))) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_refine5_read: NULL argument");
+    return debug_prune_refine45_read(ctx, ctx->kmer_fifth, blocks, n, out);
+}
+static int debug_prune_refine45_read(swg_ctx *ctx, const SwgKmerTable &t, const uint32_t *blocks, size_t n, uint16_t *out)
+{
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipDeviceSynchronize());
     if (!t.holds(ctx->epoch, 5, (int)SWG_KMER_REFINE4_SEGMENTS, 8))
-        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "swg_debug_prune_refine4_read: no fourth-level table for the current query and scoring");
+        return swg_set_ctx_error(ctx, SWG_ERR_STATE, "no table of 5-residue blocks in 256 segments of this kind for the current query and scoring");
     uint8_t row[SWG_KMER_REFINE4_SEGMENTS];
     for (size_t i = 0; i < n; ++i) {
-        if (blocks[i] >= swg_kmer_entries(5)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_refine4_read: block %u", blocks[i]);
+        if (blocks[i] >= swg_kmer_entries(5)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "a table of 5-residue blocks: block %u", blocks[i]);
         HIP_TRY(ctx, hipMemcpy(row, t.d + (size_t)blocks[i] * SWG_KMER_REFINE4_SEGMENTS, sizeof row, hipMemcpyDeviceToHost));
         std::copy(row, row + SWG_KMER_REFINE4_SEGMENTS, out + i * SWG_KMER_REFINE4_SEGMENTS);
     }

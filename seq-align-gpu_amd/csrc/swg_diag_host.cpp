@@ -700,6 +700,7 @@ std::vector<SwgPruneStage> swg_prune_stages(const SwgPrunePlan &plan, const std:
             if (plan.refine) q |= SWG_STAGE_REFINE;
             if (plan.refine3) q |= SWG_STAGE_REFINE3;
             if (plan.refine4) q |= SWG_STAGE_REFINE4;
+            if (plan.refine5) q |= SWG_STAGE_REFINE5;
             q |= SWG_STAGE_LIST;
         }
         stages[si].queued = q;
@@ -715,7 +716,7 @@ SwgPruneBoundRange swg_prune_bound_range(const std::vector<SwgPruneStage> &stage
 }
 
 // (head: the words in front of the segments -- 5, 6 with the third level's in[4], 7 with the fourth's in[5] as well, 8
-// with the gate's in[6])
+// with the gate's in[6], 9 with the fifth level's in[7])
 static int debug_prune_stages(const int64_t *in, int head, int64_t *out, size_t cap, size_t *n_out)
 {
     if (!in || !n_out || (cap > 0 && !out) || in[0] < 0 || in[head - 1] < 0) return SWG_ERR_ARG;
@@ -724,7 +725,8 @@ static int debug_prune_stages(const int64_t *in, int head, int64_t *out, size_t 
     plan.head_pairs = (uint32_t)in[0], plan.fixed = in[1] != 0, plan.refine = (int)in[2], plan.prefix_cut = in[3] != 0;
     plan.refine3 = head >= 6 ? (int)in[4] : 0;
     plan.refine4 = head >= 7 ? (int)in[5] : 0;
-    plan.gate = head == 8 && in[6] != 0;
+    plan.gate = head >= 8 && in[6] != 0;
+    plan.refine5 = head >= 9 ? (int)in[7] : 0;
     std::vector<std::pair<uint32_t, uint32_t>> segments;
     for (int64_t i = 0; i < in[head - 1]; ++i) segments.emplace_back((uint32_t)in[head + 2 * i], (uint32_t)in[head + 1 + 2 * i]);
     const std::vector<SwgPruneStage> stages = swg_prune_stages(plan, segments);
@@ -737,6 +739,7 @@ extern "C" int swg_debug_prune_stages(const int64_t *in, int64_t *out, size_t ca
 extern "C" int swg_debug_prune_stages3(const int64_t *in, int64_t *out, size_t cap, size_t *n_out) { return debug_prune_stages(in, 6, out, cap, n_out); }
 extern "C" int swg_debug_prune_stages4(const int64_t *in, int64_t *out, size_t cap, size_t *n_out) { return debug_prune_stages(in, 7, out, cap, n_out); }
 extern "C" int swg_debug_prune_stages5(const int64_t *in, int64_t *out, size_t cap, size_t *n_out) { return debug_prune_stages(in, 8, out, cap, n_out); }
+extern "C" int swg_debug_prune_stages6(const int64_t *in, int64_t *out, size_t cap, size_t *n_out) { return debug_prune_stages(in, 9, out, cap, n_out); }
 
 // The k-mer form of the bound, on the host: what the device builds (swg_kmer_cprof_kernel,
 // swg_kmer_table_kernel) and sums (swg_pair_bound_kmer_kernel), restated for the tests.  cprof[lq][22]: query column i
@@ -818,26 +821,38 @@ void swg_kmer_table_seg(const int8_t *cprof, size_t lq, int g, int e, int k, siz
 // in segment s, a block gives H[s] = max_{s' <= s} H[s'] + min(table[block][s], the block's colmax sum), and the bound is
 // max_s H[s].  S = 1 is the unordered sum of the blocks.
 // (entries(ix): the S entries of block ix)
-template <class Entries>
-static uint64_t kmer_bound_walk(Entries entries, int k, size_t S, const SwgColMax &cm, const int8_t *seq, size_t len)
+// (each(ix, sum): a block's index in the table of k and the colmax sum of its rows, in the sequence's order)
+template <class Each>
+static void kmer_blocks(Each each, int k, const SwgColMax &cm, const int8_t *seq, size_t len)
 {
     const size_t n_blocks = (2 + len + 3) / 4, n_rows = 4 * n_blocks;
     auto res = [&](size_t row) -> uint32_t { return row < 2 || row >= 2 + len ? 0u : (uint8_t)seq[row - 2] & 31u; };
     const size_t rows5 = k == 5 ? 20 * (n_blocks / 5) : 0;
-    std::vector<uint64_t> H(S, 0);
     for (size_t r = 0; r < n_rows;) {
         const size_t rows = r < rows5 ? 5 : 4;
         size_t ix = 0;
-        uint64_t sum = 0, run = 0;
+        uint64_t sum = 0;
         for (size_t j = 0; j < rows; ++j) ix = ix * SWG_KMER_CLASSES + swg_kmer_class(res(r + j)), sum += cm.v[res(r + j)];
         if (k == 5 && rows == 4) ix *= SWG_KMER_CLASSES;
-        const uint16_t *t = entries(ix);
-        for (size_t s = 0; s < S; ++s) {
-            run = std::max(run, H[s]);
-            H[s] = run + std::min<uint64_t>(t[s], sum);
-        }
+        each(ix, sum);
         r += rows;
     }
+}
+
+template <class Entries>
+static uint64_t kmer_bound_walk(Entries entries, int k, size_t S, const SwgColMax &cm, const int8_t *seq, size_t len)
+{
+    std::vector<uint64_t> H(S, 0);
+    kmer_blocks(
+        [&](size_t ix, uint64_t sum) {
+            const uint16_t *t = entries(ix);
+            uint64_t run = 0;
+            for (size_t s = 0; s < S; ++s) {
+                run = std::max(run, H[s]);
+                H[s] = run + std::min<uint64_t>(t[s], sum);
+            }
+        },
+        k, cm, seq, len);
     return *std::max_element(H.begin(), H.end());
 }
 
@@ -894,6 +909,51 @@ extern "C" int swg_debug_prune_kmer_refine3(const int8_t *rows, const int8_t *id
 // taken in batches of up to SWG_REFINE4_BATCH blocks, and a batch computes the entries of the blocks it holds -- sorted, so
 // that blocks behind one prefix share its rows the way the table's build shares them.
 #define SWG_REFINE4_BATCH 32768u
+// (the first sequence of each batch, and n)
+static std::vector<size_t> refine4_batches(const uint64_t *offsets, size_t n)
+{
+    std::vector<size_t> batch{0};
+    for (size_t i = 0, blocks = 0; i < n; ++i) {
+        const size_t nb = (2 + (size_t)(offsets[i + 1] - offsets[i]) + 3) / 4;
+        if (blocks > 0 && blocks + nb > SWG_REFINE4_BATCH) batch.push_back(i), blocks = 0;
+        blocks += nb;
+    }
+    batch.push_back(n);
+    return batch;
+}
+// (the blocks of 5 the sequences [first, last) hold, sorted, each once)
+static std::vector<uint32_t> refine4_held(const SwgColMax &cm, const int8_t *flat, const uint64_t *offsets, size_t first, size_t last)
+{
+    std::vector<uint32_t> held;
+    for (size_t i = first; i < last; ++i)
+        kmer_blocks([&](size_t ix, uint64_t) { held.push_back((uint32_t)ix); }, 5, cm, flat + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+    std::sort(held.begin(), held.end());
+    held.erase(std::unique(held.begin(), held.end()), held.end());
+    return held;
+}
+// (their S entries each, by the row recurrence `row`: kmer_row, or kmer_row2 of the fifth level)
+template <class Row>
+static std::vector<uint16_t> refine4_entries(Row row, const std::vector<uint32_t> &held, const int8_t *cprof, size_t lq, int g, int e, size_t S)
+{
+    const uint32_t C = SWG_KMER_CLASSES;
+    std::vector<uint16_t> entries(held.size() * S);
+    std::vector<int> work(5 * (2 * lq + S));
+    uint32_t prev[5] = {0, 0, 0, 0, 0};
+    for (size_t h = 0; h < held.size(); ++h) {
+        uint32_t c[5];
+        for (uint32_t j = 5, v = held[h]; j-- > 0; v /= C) c[j] = v % C;
+        int d = 0;
+        while (h > 0 && d < 4 && c[d] == prev[d]) ++d; // (the rows above d are the previous block's)
+        for (; d < 5; ++d) {
+            int *Mn = work.data() + (size_t)d * (2 * lq + S), *Mp = d ? Mn - (2 * lq + S) : nullptr;
+            row(cprof, lq, g, e, S, c[d], Mp, Mp ? Mp + lq : nullptr, Mp ? Mp + 2 * lq : nullptr, Mn, Mn + lq, Mn + 2 * lq);
+            prev[d] = c[d];
+        }
+        const int *best = work.data() + 4 * (2 * lq + S) + 2 * lq;
+        for (size_t s = 0; s < S; ++s) entries[h * S + s] = (uint16_t)std::min(best[s], 65535);
+    }
+    return entries;
+}
 extern "C" int swg_debug_prune_kmer_refine4(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S4, const int8_t *flat,
                                             const uint64_t *offsets, size_t n, uint64_t *u_out)
 {
@@ -903,42 +963,105 @@ extern "C" int swg_debug_prune_kmer_refine4(const int8_t *rows, const int8_t *id
     swg_kmer_cprof(rows, idx, lq, cprof.data());
     const SwgColMax cm = swg_prune_colmax(rows, idx, lq);
     const int g = std::min(-(gap_open + gap_extend), 65536), e = std::min(-gap_extend, 65536);
-    std::vector<size_t> batch{0}; // (the first sequence of each batch, and n)
-    for (size_t i = 0, blocks = 0; i < n; ++i) {
-        const size_t nb = (2 + (size_t)(offsets[i + 1] - offsets[i]) + 3) / 4;
-        if (blocks > 0 && blocks + nb > SWG_REFINE4_BATCH) batch.push_back(i), blocks = 0;
-        blocks += nb;
-    }
-    batch.push_back(n);
+    const std::vector<size_t> batch = refine4_batches(offsets, n);
 #pragma omp parallel for schedule(dynamic, 1)
     for (long bi = 0; bi < (long)batch.size() - 1; ++bi) {
-        std::vector<uint32_t> held;
-        const uint16_t none = 0;
-        for (size_t i = batch[bi]; i < batch[bi + 1]; ++i)
-            kmer_bound_walk([&](size_t ix) { held.push_back((uint32_t)ix); return &none; }, 5, 1, cm, flat + offsets[i],
-                            (size_t)(offsets[i + 1] - offsets[i]));
-        std::sort(held.begin(), held.end());
-        held.erase(std::unique(held.begin(), held.end()), held.end());
-        std::vector<uint16_t> entries(held.size() * S);
-        std::vector<int> work(5 * (2 * lq + S));
-        uint32_t prev[5] = {0, 0, 0, 0, 0};
-        for (size_t h = 0; h < held.size(); ++h) {
-            uint32_t c[5];
-            for (uint32_t j = 5, v = held[h]; j-- > 0; v /= (uint32_t)C) c[j] = v % (uint32_t)C;
-            int d = 0;
-            while (h > 0 && d < 4 && c[d] == prev[d]) ++d; // (the rows above d are the previous block's)
-            for (; d < 5; ++d) {
-                int *Mn = work.data() + (size_t)d * (2 * lq + S), *Mp = d ? Mn - (2 * lq + S) : nullptr;
-                kmer_row(cprof.data(), lq, g, e, S, c[d], Mp, Mp ? Mp + lq : nullptr, Mp ? Mp + 2 * lq : nullptr, Mn, Mn + lq, Mn + 2 * lq);
-                prev[d] = c[d];
-            }
-            const int *best = work.data() + 4 * (2 * lq + S) + 2 * lq;
-            for (size_t s = 0; s < S; ++s) entries[h * S + s] = (uint16_t)std::min(best[s], 65535);
-        }
+        const std::vector<uint32_t> held = refine4_held(cm, flat, offsets, batch[bi], batch[bi + 1]);
+        const std::vector<uint16_t> entries = refine4_entries(kmer_row, held, cprof.data(), lq, g, e, S);
         for (size_t i = batch[bi]; i < batch[bi + 1]; ++i)
             u_out[i] = kmer_bound_walk(
                 [&](size_t ix) { return entries.data() + (size_t)(std::lower_bound(held.begin(), held.end(), (uint32_t)ix) - held.begin()) * S; }, 5, S, cm,
                 flat + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+    }
+    return SWG_OK;
+}
+
+// The fifth level: the fourth level's blocks, segments and walk, with the query columns a chain jumps over
+// between two blocks charged as the gap they are.  A second entry per block and segment, T2 = the best of score + e x span
+// over the block's chains whose LAST MATCH lies in the segment (span: last matched column - first matched column), by the
+// table's recurrence with the credit e paid per column a chain advances: a diagonal step that continues a chain earns e,
+// opening a gap along the query costs g - e and extending it nothing, gaps along the block are unchanged, a chain starts at a
+// match without credit, and "no chain" is SWG_KMER_NO_CHAIN, not 0.  Only cells that end in a match enter a segment's
+// maximum (the state of a gap along the query no longer decays).
+static void kmer_row2(const int8_t *cprof, size_t lq, int g, int e, size_t S, uint32_t c, const int *Mp, const int *Bp, const int *best_p, int *Mn,
+                      int *Bn, int *best)
+{
+    const size_t W = (lq + S - 1) / S;
+    int a = SWG_KMER_NO_CHAIN, up = SWG_KMER_NO_CHAIN;
+    for (size_t s = 0; s < S; ++s) best[s] = best_p ? best_p[s] : 0;
+    for (size_t s = 0, i = 0; i < lq; ++s) {
+        int bs = best[s];
+        for (const size_t end = std::min(lq, i + W); i < end; ++i) {
+            const int sc = cprof[SWG_KMER_CLASSES * i + c];
+            a = std::max(std::max(up - (g - e), a), SWG_KMER_NO_CHAIN);
+            const int b = Mp ? std::max(std::max(Mp[i] - g, Bp[i] - e), SWG_KMER_NO_CHAIN) : SWG_KMER_NO_CHAIN;
+            const int diag = Mp && i ? Mp[i - 1] : SWG_KMER_NO_CHAIN;
+            const int h = sc + std::max(0, diag + e);
+            const int m = std::max(std::max(h, a), b);
+            Mn[i] = m, Bn[i] = b, up = m;
+            bs = std::max(bs, h);
+        }
+        best[s] = bs;
+    }
+}
+
+// The walk.  H[s]: the best total of the blocks so far over the chains whose last block ended in segment s (a running
+// maximum: a block may be left out).  A block with entries t, t2 and colmax sum `sum`, tm[s] = min(t[s], sum), gives
+//   H'[s] = max( H[s],  max_{s'' in {s, s - 1}} H[s''] + tm[s],  max_{n = 1..N} H[s - 1 - n] + min(tm[s], t2[s] - e W n),
+//                min( tm[s] + max_{s'' < s - 1 - N} H[s''],  t2[s] - e W (s - 1) + max_{s'' < s - 1 - N} (H[s''] + e W s'') ) )
+// -- n = s - s'' - 1 whole segments lie between the two chains' ends, e W n is the least their columns cost, the first N are
+// taken one by one and the rest by two prefix maxima (the least of two maxima is at least the maximum of the leasts).  Every
+// term is at most the fourth level's H[s''] + tm[s].  N >= S: the exact form.
+static uint64_t kmer_bound_walk5(const uint16_t *t, const uint16_t *t2, const std::vector<uint32_t> &held, size_t S, size_t W, int e, size_t N,
+                                 const SwgColMax &cm, const int8_t *seq, size_t len)
+{
+    const int64_t c = (int64_t)e * (int64_t)W;
+    std::vector<int64_t> H(S, 0), Hn(S), PH(S), PC(S);
+    kmer_blocks(
+        [&](size_t ix, uint64_t sum) {
+            const size_t at = (size_t)(std::lower_bound(held.begin(), held.end(), (uint32_t)ix) - held.begin()) * S;
+            for (size_t s = 0; s < S; ++s) {
+                PH[s] = std::max(s ? PH[s - 1] : 0, H[s]);
+                PC[s] = std::max(s ? PC[s - 1] : INT64_MIN, H[s] + c * (int64_t)s);
+            }
+            for (size_t s = 0; s < S; ++s) {
+                const int64_t tm = (int64_t)std::min<uint64_t>(t[at + s], sum), v2 = t2[at + s];
+                int64_t best = std::max(H[s], std::max(H[s], s ? H[s - 1] : 0) + tm);
+                for (size_t n = 1; n <= N && n + 1 <= s; ++n) best = std::max(best, H[s - 1 - n] + std::min(tm, v2 - c * (int64_t)n));
+                if (s >= N + 2) best = std::max(best, std::min(tm + PH[s - 2 - N], v2 - c * (int64_t)(s - 1) + PC[s - 2 - N]));
+                Hn[s] = best;
+            }
+            H.swap(Hn);
+        },
+        5, cm, seq, len);
+    return (uint64_t)*std::max_element(H.begin(), H.end());
+}
+
+// ... and the fifth level's mirror: like the fourth's it holds no table and computes batch by batch.  It is on (*on_out = 1)
+// where e > 0 and both kinds of entry are bytes -- 5 x (the largest colmax entry + e) <= 255 (swg_kmer_refine5_admitted) --;
+// elsewhere the level is off, *on_out = 0 and u_out is not written.  n_explicit: N of the walk, 0 for the device's
+// (SWG_REFINE5_EXPLICIT).
+extern "C" int swg_debug_prune_kmer_refine5(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S5, int n_explicit,
+                                            const int8_t *flat, const uint64_t *offsets, size_t n, uint64_t *u_out, int *on_out)
+{
+    if (S5 != 256 || n_explicit < 0 || !rows || lq == 0 || gap_open > 0 || gap_extend > 0 || !on_out || (n > 0 && (!flat || !offsets || !u_out)))
+        return SWG_ERR_ARG;
+    const size_t S = (size_t)S5, C = SWG_KMER_CLASSES, W = (lq + S - 1) / S;
+    const SwgColMax cm = swg_prune_colmax(rows, idx, lq);
+    const int g = std::min(-(gap_open + gap_extend), 65536), e = std::min(-gap_extend, 65536);
+    *on_out = swg_kmer_refine5_admitted(cm, e, lq) ? 1 : 0;
+    if (!*on_out) return SWG_OK;
+    std::vector<int8_t> cprof(lq * C);
+    swg_kmer_cprof(rows, idx, lq, cprof.data());
+    const std::vector<size_t> batch = refine4_batches(offsets, n);
+#pragma omp parallel for schedule(dynamic, 1)
+    for (long bi = 0; bi < (long)batch.size() - 1; ++bi) {
+        const std::vector<uint32_t> held = refine4_held(cm, flat, offsets, batch[bi], batch[bi + 1]);
+        const std::vector<uint16_t> t = refine4_entries(kmer_row, held, cprof.data(), lq, g, e, S);
+        const std::vector<uint16_t> t2 = refine4_entries(kmer_row2, held, cprof.data(), lq, g, e, S);
+        for (size_t i = batch[bi]; i < batch[bi + 1]; ++i)
+            u_out[i] = kmer_bound_walk5(t.data(), t2.data(), held, S, W, e, n_explicit ? (size_t)n_explicit : (size_t)SWG_REFINE5_EXPLICIT, cm,
+                                        flat + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
     }
     return SWG_OK;
 }
@@ -1166,6 +1289,27 @@ int swg_prune_refine4_choice(const SwgKmerAsk &a, int k, int S, int S2, int S3)
     return cost <= 0.5 * gain ? (int)SWG_KMER_REFINE4_SEGMENTS : 0;
 }
 
+// The fifth level: the fourth level's walk once more over both k = 5 tables, the query columns jumped over between two
+// blocks charged ("a fifth level"); walked only by the pairs the fourth level leaves at or above T.  Forced
+// ("prune_refine5" = 5256), behind whatever the other levels are; off ("prune_refine5" = 1); automatic only where the fourth
+// level was itself chosen automatically (so every forced earlier level stays without it) and the threshold is not a
+// caller's (a.fixed), under the rule of the other levels: the second table's build and the walk may cost at most half of what the cut saves.  Whoever asks, the level
+// needs both tables as bytes and e > 0 (a.table_bits5, a.refine5_ok).
+// Constants: profiles/prune_adjacent_ab.txt -- SWG_REFINE5_GAIN the rows kept behind the fourth level less those behind the
+// fifth (the host model, section 0), SWG_REFINE5_BOUND_ROW the fifth walk per pair row of the range.
+#define SWG_REFINE5_GAIN 0.0254
+#define SWG_REFINE5_BOUND_ROW 4.0e-12
+int swg_prune_refine5_choice(const SwgKmerAsk &a, int k, int S4)
+{
+    if (!a.pruned || k < 1 || !a.refine5_ok || !swg_kmer_refine4_admitted(a.table_bits5)) return 0;
+    if (a.forced_refine5 == SWG_REFINE5_FORCED) return (int)SWG_KMER_REFINE4_SEGMENTS;
+    if (a.forced_refine5 != 0 || a.forced_refine4 != 0 || S4 == 0 || a.fixed) return 0;
+    if (a.table_rate <= 0 || a.fill_rate <= 0 || a.lq == 0) return 0;
+    const double cost = swg_kmer_table_cells(5) * (double)a.lq / a.table_rate + SWG_REFINE5_BOUND_ROW * (double)a.pair_rows;
+    const double gain = SWG_REFINE5_GAIN * (double)a.pair_rows / a.fill_rate;
+    return cost <= 0.5 * gain ? (int)SWG_KMER_REFINE4_SEGMENTS : 0;
+}
+
 extern "C" int swg_debug_prune_refine4_choice(const int64_t *in, int64_t *out)
 {
     SwgKmerAsk a;
@@ -1180,6 +1324,19 @@ extern "C" int swg_debug_prune_refine4_choice(const int64_t *in, int64_t *out)
     out[2] = swg_prune_refine_choice(a, (int)out[0], S);
     out[3] = swg_prune_refine3_choice(a, (int)out[0], S, (int)out[2]);
     out[4] = swg_prune_refine4_choice(a, (int)out[0], S, (int)out[2], (int)out[3]);
+    return SWG_OK;
+}
+
+extern "C" int swg_debug_prune_refine5_choice(const int64_t *in, int64_t *out)
+{
+    SwgKmerAsk a;
+    if (!debug_kmer_ask(in, out, 8, &a)) return SWG_ERR_ARG;
+    if (!swg_prune_refine5_value_ok((long)in[12]) || (in[13] != 0 && in[13] != 1) || (in[14] != 0 && in[14] != 1)) return SWG_ERR_ARG;
+    const int rc = swg_debug_prune_refine4_choice(in, out);
+    if (rc != SWG_OK) return rc;
+    a.forced_refine3 = (long)in[8], a.forced_refine4 = (long)in[10], a.forced_refine5 = (long)in[12];
+    a.table_bits = in[9] == 16 ? 16 : 8, a.table_bits5 = in[11] == 16 ? 16 : 8, a.refine5_ok = in[13] != 0, a.fixed = in[14] != 0;
+    out[5] = swg_prune_refine5_choice(a, (int)out[0], (int)out[4]);
     return SWG_OK;
 }
 

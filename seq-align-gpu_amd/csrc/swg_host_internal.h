@@ -274,6 +274,7 @@ struct SwgPrunePlan {
     int refine = 0;          // the second level's segments (swg_prune_refine_choice): 64, 128, or 0 without one
     int refine3 = 0;         // the third level's segments (swg_prune_refine3_choice): 256, or 0 without one
     int refine4 = 0;         // the fourth level's segments, of the k = 5 table (swg_prune_refine4_choice): 256, or 0 without one
+    int refine5 = 0;         // the fifth level's segments, of both k = 5 tables (swg_prune_refine5_choice): 256, or 0 without one
     bool prefix_cut = false; // option "prune_cut" = 1: a stage's list is the prefix up to its last pair that reaches T
     bool gate = false;       // the first level's launch is gated by T and queued with a stage (swg_prune_gate_choice)
     bool fixed = false;      // a caller's threshold: every stage, the first included, is a list launch cut at fixed_T
@@ -301,13 +302,13 @@ SwgPrunePlan swg_prune_plan(const SwgPruneAsk &a);
 // cut too and no threshold kernel runs.  A cut is the prefix cut (plan.prefix_cut), or pair by pair: the refine pass
 // where there is a second level (plan.refine) -- behind the gate on the first of several stages under a caller's
 // threshold --, the third level's (plan.refine3) behind it under the same threshold word, the fourth's (plan.refine4) behind
-// that, then the list.  With the gate in front of the first level (plan.gate) the stage that first has a threshold --
+// that, the fifth's (plan.refine5) behind the fourth's, then the list.  With the gate in front of the first level (plan.gate) the stage that first has a threshold --
 // the second of several, or the first under a caller's threshold -- also queues the first level's launch, behind the
 // threshold kernel and in front of everything else: gated by that threshold, over all pairs from the stage's first to the
 // range's last.  A fill whose list holds no such stage bounds every pair before its first stage, ungated.
 enum : uint32_t {
     SWG_STAGE_THRESHOLD = 1u, SWG_STAGE_PREFIX_CUT = 2u, SWG_STAGE_GATE = 4u, SWG_STAGE_REFINE = 8u, SWG_STAGE_LIST = 16u, SWG_STAGE_REFINE3 = 32u,
-    SWG_STAGE_REFINE4 = 64u, SWG_STAGE_BOUND = 128u
+    SWG_STAGE_REFINE4 = 64u, SWG_STAGE_BOUND = 128u, SWG_STAGE_REFINE5 = 256u
 };
 struct SwgPruneStage {
     uint32_t begin, end; // pairs
@@ -335,6 +336,8 @@ extern "C" int swg_debug_prune_stages3(const int64_t *in, int64_t *out, size_t c
 extern "C" int swg_debug_prune_stages4(const int64_t *in, int64_t *out, size_t cap, size_t *n_out);
 // ... and the gate: in[0..7] = head_pairs, fixed, refine, prefix_cut, refine3, refine4, gate, n, then the n segments
 extern "C" int swg_debug_prune_stages5(const int64_t *in, int64_t *out, size_t cap, size_t *n_out);
+// ... and the fifth level: in[0..8] = head_pairs, fixed, refine, prefix_cut, refine3, refine4, gate, refine5, n, then the n segments
+extern "C" int swg_debug_prune_stages6(const int64_t *in, int64_t *out, size_t cap, size_t *n_out);
 // The automatic rule of a caller's threshold ("A caller's threshold"; profiles/search_above_ab.txt): the
 // bound, list and tally kernels of a stage cost tens of microseconds whatever the range holds, a list launch one
 // dependent load per claim; a range with at least SWG_PRUNE_ABOVE_AUTO_PAIRS pairs per resident lane group has fills
@@ -384,6 +387,9 @@ struct SwgKmerAsk {
     long forced_refine = 0;   // option "prune_refine": 0 automatic, 1 off, 64 or 128
     long forced_refine3 = 0;  // option "prune_refine3": 0 automatic, 1 off, 256
     long forced_refine4 = 0;  // option "prune_refine4": 0 automatic, 1 off, 5256 (k = 5 in 256 segments)
+    long forced_refine5 = 0;  // option "prune_refine5": 0 automatic, 1 off, 5256 (both k = 5 tables in 256 segments)
+    bool refine5_ok = false;  // swg_kmer_refine5_admitted for this query and scoring: e > 0 and second entries that are bytes
+    bool fixed = false;       // a caller's threshold (swg_search_above): the fifth level is then forced or off
     long forced_gate = 0;     // option "prune_gate": 0 automatic, 1 off, 2 wherever the first level is a segmented k-mer bound
     int table_bits5 = 8;      // ... and of the k = 5 tables' (the fourth level takes bytes only)
     int table_bits = 8;       // the width of the k = 4 tables' entries for this query and scoring (swg_kmer_table_bits, "prune_table_bits")
@@ -435,6 +441,24 @@ extern "C" int swg_debug_prune_refine4_choice(const int64_t *in, int64_t *out);
 // computes the entries of the blocks the sequences hold.
 extern "C" int swg_debug_prune_kmer_refine4(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S4, const int8_t *flat,
                                             const uint64_t *offsets, size_t n, uint64_t *u_out);
+// ... and of a fifth level's bound ("a fifth level"): the fourth level's blocks in S5 = 256 segments, with the
+// query columns jumped over between two blocks charged.  *on_out = 0 and u_out unwritten where the level is off
+// (swg_kmer_refine5_admitted); n_explicit: the walk's N, 0 for SWG_REFINE5_EXPLICIT, S5 or more for the exact form.
+extern "C" int swg_debug_prune_kmer_refine5(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S5, int n_explicit,
+                                            const int8_t *flat, const uint64_t *offsets, size_t n, uint64_t *u_out, int *on_out);
+// The fifth level ("a fifth level"): the fourth level's walk over both k = 5 tables with the query columns
+// jumped over between two blocks charged, or 0 for none (S4: what the fourth level took).  Forced ("prune_refine5" = 5256),
+// behind whatever the fourth level is, wherever both tables are bytes and e > 0 (a.refine5_ok, a.table_bits5); off (1);
+// automatic only where the fourth level was itself chosen automatically and the threshold is the K-th best so far: under a
+// caller's threshold what the level saves depends on where T lies among the bounds (profiles/prune_adjacent_ab.txt, section
+// 4: 23.6 ms saved at the score of the 100th hit, 3.3 ms lost at twice that), so there it runs only where it is forced.
+#define SWG_REFINE5_FORCED 5256
+int swg_prune_refine5_choice(const SwgKmerAsk &a, int k, int S4);
+inline bool swg_prune_refine5_value_ok(long v) { return v == 0 || v == 1 || v == SWG_REFINE5_FORCED; }
+// test hook: in[0..11] as swg_debug_prune_refine4_choice, in[12] = option "prune_refine5", in[13] = whether the query and
+// scoring admit the level (swg_kmer_refine5_admitted), in[14] = whether the threshold is a caller's -> out[0..5] = k, S, S2,
+// S3, S4, S5
+extern "C" int swg_debug_prune_refine5_choice(const int64_t *in, int64_t *out);
 // The gate in front of the first level: whether the first level's launch, of (k, S), waits for a threshold
 // and leaves out the pairs whose colmax bound is below it.  Forced ("prune_gate" = 2) wherever the first level is a
 // segmented k-mer bound; off ("prune_gate" = 1); automatic only where k and S were both chosen automatically and the range
@@ -538,6 +562,7 @@ struct SwgKmerTable {
 struct SwgPruneChoice {
     int kmer = 0, segments = 0, refine = 0, refine3 = 0, refine4 = 0;
     int gate = 0; // 1: the first level's launch is gated (swg_prune_gate_choice)
+    int refine5 = 0; // the fifth level's S5 (0: none)
 };
 
 // One search in flight: its timing events, host-side landing buffers and what swg_search_end
@@ -629,6 +654,7 @@ struct swg_ctx {
     long opt_prune_refine = 0;   // option "prune_refine": 0 auto, 1 off, 64, 128
     long opt_prune_refine3 = 0;  // option "prune_refine3": 0 auto, 1 off, 256
     long opt_prune_refine4 = 0;  // option "prune_refine4": 0 auto, 1 off, 5256
+    long opt_prune_refine5 = 0;  // option "prune_refine5": 0 auto, 1 off, 5256
     long opt_prune_gate = 0;     // option "prune_gate": 0 auto, 1 off, 2 wherever the first level is segmented
     long opt_prune_table_bits = 0; // option "prune_table_bits": 0 auto (bytes where they hold every entry), 16
     long opt_prune_cut = 0;      // option "prune_cut": 0 pair by pair, 1 the prefix of the length order
@@ -637,6 +663,9 @@ struct swg_ctx {
     SwgKmerTable kmer_first[2], kmer_second, kmer_third, kmer_fourth; // [k - 4]
     uint64_t kmer_builds = 0, kmer_refine_builds = 0, kmer_refine3_builds = 0, kmer_refine4_builds = 0; // builds queued so far, level by level (tests)
     bool kmer_fourth_refused = false; // the fourth table's allocation failed once: this context searches without the level
+    SwgKmerTable kmer_fifth;          // the fifth level's second entries: k = 5 in 256 segments of bytes, built with spans
+    uint64_t kmer_refine5_builds = 0;
+    bool kmer_fifth_refused = false;  // ... and the same for the fifth's
     uint32_t opt_seg_blocks = SWG_DYN_SEG_BLOCKS; // token blocks per launch of the multi-pass fill (option "segment_blocks": tests)
     // device state
     int8_t *d_sub = nullptr;

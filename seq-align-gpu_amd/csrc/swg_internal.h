@@ -364,7 +364,7 @@ static inline int swg_kmer_table_bits(const SwgColMax &cm, int k)
 // k: 4 or 5; S: 1..SWG_KMER_REFINE_SEGMENTS (the bound kernels take what they can walk: see each).  bits: 8 or 16, the
 // width of d_table's entries, here and in every launch below that reads the table (swg_kmer_table_bits).
 hipError_t swg_launch_kmer_table(const int8_t *d_sub, const int8_t *d_query, const int8_t *d_pssm, uint32_t lq, uint32_t g, uint32_t e,
-                                 int k, uint32_t S, int8_t *d_cprof, void *d_table, int bits, hipStream_t stream);
+                                 int k, uint32_t S, int8_t *d_cprof, void *d_table, int bits, hipStream_t stream, bool spans = false);
 // swg_launch_pair_bound with the k-mer bound: blocks of 4 token rows (k = 4), or of 5 with a tail of fewer than 20 rows
 // in blocks of 4 (k = 5); a block adds the lesser of its table entry and its rows' colmax entries
 hipError_t swg_launch_pair_bound_kmer(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t n_pairs, int k, const SwgColMax &cm,
@@ -392,6 +392,26 @@ hipError_t swg_launch_pair_bound_refine(const uint4 *d_tok, const uint32_t *d_pa
 #define SWG_KMER_REFINE4_SEGMENTS 256u
 #define SWG_KMER_REFINE4_BUDGET (2ull << 30)
 static inline bool swg_kmer_refine4_admitted(int bits) { return bits == 8 && swg_kmer_entries(5) * SWG_KMER_REFINE4_SEGMENTS <= SWG_KMER_REFINE4_BUDGET; }
+// The fifth level charges the query columns jumped over between two blocks of the fourth: it needs a gap's
+// further residues to cost something (e > 0; with e = 0 it is the fourth level) and its second entries, at most
+// 5 x (the largest colmax entry + e), to be bytes; e x lq below 2^24 keeps the walk's e W s in its int32.
+// SWG_REFINE5_EXPLICIT: the segments between two chains' ends that its walk takes one by one (N); the headline's rows kept
+// are the exact form's from N = 1 on (profiles/prune_adjacent_ab.txt, section 0).
+#define SWG_REFINE5_EXPLICIT 1
+#define SWG_KMER_NO_CHAIN (-(1 << 28)) // a cell of the second entries' recurrence that no chain reaches
+static inline bool swg_kmer_refine5_admitted(const SwgColMax &cm, int e, size_t lq)
+{
+    uint32_t m = 0u;
+    for (int r = 0; r < 32; ++r) m = cm.v[r] > m ? cm.v[r] : m;
+    return e > 0 && e <= 255 && 5u * (m + (uint32_t)e) <= 255u && (uint64_t)e * lq < (1ull << 24);
+}
+// d_bound[p] = min(d_bound[p], the fifth level's bound) for the pairs of [begin, end) with d_bound[p] >= *d_thr: d_table the
+// fourth level's (k = 5 in 256 segments of bytes), d_table2 the second entries (swg_launch_kmer_table with spans); e: what a
+// gap's further residues cost
+hipError_t swg_launch_pair_bound_refine5(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, const SwgColMax &cm,
+                                         const uint8_t *d_table, const uint8_t *d_table2, uint32_t lq, uint32_t e, const uint32_t *d_thr, uint32_t *d_bound,
+                                         hipStream_t stream);
+
 // The cut pair by pair: d_list[0 .. d_out[0]) = the pairs of [begin, end) with d_bound >= *d_thr, ascending; d_out[1] +=
 // the others, (uint64 at d_out[2]) += their token blocks.  d_tiles: one word per SWG_PRUNE_TILE pairs of the range;
 // d_rec (or NULL): {*d_thr, d_out[0]} once more, for the tests.

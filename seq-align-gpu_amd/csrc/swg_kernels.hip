@@ -3033,13 +3033,20 @@ __global__ __launch_bounds__(256) void swg_kmer_table_kernel(const int8_t *cprof
 // thread's 22 table rows lie S entries apart, so one entry per store would be 22 single bytes into 22 cache lines at every
 // segment's end; where S is a multiple of 8 bytes' worth of entries (PACK) the entries are collected PACK segments at a
 // time and leave as one 8-byte store per row.  Segment rule, clamp and the zeros of segments without columns as above.
-template <class E>
+// SPAN: the fifth level's second entries ("a fifth level") instead -- the best of score + e x span over the
+// block's chains whose last match lies in the segment.  The same cells with the credit e paid per column a chain advances:
+// a diagonal step that continues a chain earns e, opening a gap along the query costs g - e and extending it nothing, a
+// chain starts at a match without credit, "no chain" is SWG_KMER_NO_CHAIN and not 0, and only the cells that end in a match
+// enter a segment's maximum.
+template <class E, bool SPAN = false>
 __global__ __launch_bounds__(256) void swg_kmer_table5_kernel(const int8_t *cprof, uint32_t lq, int g, int e, uint32_t n_prefixes, uint32_t S,
                                                               E *table)
 {
     constexpr int top = sizeof(E) == 1 ? 255 : 65535;
     constexpr int NC = (int)SWG_KMER_CLASSES;
     constexpr uint32_t PACK = 8u / sizeof(E), EB = 8u * sizeof(E);
+    constexpr int none = SPAN ? SWG_KMER_NO_CHAIN : 0;
+    const int ga = SPAN ? g - e : g, ea = SPAN ? 0 : e; // (what a gap along the query costs)
     __shared__ uint4 rows4[SWG_KMER_CHUNK * 2u];
     const int8_t *rows = reinterpret_cast<const int8_t *>(rows4);
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
@@ -3055,11 +3062,11 @@ __global__ __launch_bounds__(256) void swg_kmer_table5_kernel(const int8_t *cpro
     }
     int M[4], A[4], pbest = 0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) M[j] = 0, A[j] = 0;
+    for (int j = 0; j < 4; ++j) M[j] = none, A[j] = none;
     int M5[NC], A5[NC], best5[NC];
     uint32_t lo[NC], hi[NC]; // (the entries of up to PACK segments, first segment lowest)
 #pragma unroll
-    for (int k = 0; k < NC; ++k) M5[k] = 0, A5[k] = 0, best5[k] = 0, lo[k] = 0u, hi[k] = 0u;
+    for (int k = 0; k < NC; ++k) M5[k] = none, A5[k] = none, best5[k] = 0, lo[k] = 0u, hi[k] = 0u;
     const uint32_t W = (lq + S - 1u) / S;
     const bool packed = S % PACK == 0u;
     E *out = table + (size_t)(mine ? idx : 0u) * NC * S; // (the row of the prefix's first block)
@@ -3093,28 +3100,30 @@ __global__ __launch_bounds__(256) void swg_kmer_table5_kernel(const int8_t *cpro
         __syncthreads();
         for (uint32_t i = 0u; i < n; ++i) {
             const int8_t *row = rows + 32u * i;
-            int diag = 0, left = 0, B = 0;
+            int diag = none, left = none, B = none;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int s = row[c[j]];
-                const int a = max(max(M[j] - g, A[j] - e), 0);
-                const int b = j ? max(max(left - g, B - e), 0) : 0;
-                const int m = max(max(diag + s, a), b);
+                const int a = max(max(M[j] - ga, A[j] - ea), none);
+                const int b = j ? max(max(left - g, B - e), none) : none;
+                const int h = SPAN ? s + max(diag + e, 0) : diag + s;
+                const int m = max(max(h, a), b);
                 diag = M[j];
                 M[j] = m, A[j] = a, B = b, left = m;
-                pbest = max(pbest, m);
+                pbest = max(pbest, SPAN ? h : m);
             }
             // the fifth rows: diag is the prefix's last row one column back, (left, B) that row in this column
-            const int b5 = max(max(left - g, B - e), 0);
+            const int b5 = max(max(left - g, B - e), none);
             const uint4 w0 = rows4[2u * i], w1 = rows4[2u * i + 1u];
             const uint32_t w[6] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y};
 #pragma unroll
             for (int k = 0; k < NC; ++k) {
                 const int s = (int)(int8_t)(w[k >> 2] >> (8 * (k & 3)));
-                const int a = max(max(M5[k] - g, A5[k] - e), 0);
-                const int m = max(max(diag + s, a), b5);
+                const int a = max(max(M5[k] - ga, A5[k] - ea), none);
+                const int h = SPAN ? s + max(diag + e, 0) : diag + s;
+                const int m = max(max(h, a), b5);
                 M5[k] = m, A5[k] = a;
-                best5[k] = max(best5[k], m);
+                best5[k] = max(best5[k], SPAN ? h : m);
             }
             if (i0 + i + 1u == seg_end) { // (the same for every thread)
                 close_segment(false);
@@ -3126,16 +3135,19 @@ __global__ __launch_bounds__(256) void swg_kmer_table5_kernel(const int8_t *cpro
 }
 
 hipError_t swg_launch_kmer_table(const int8_t *d_sub, const int8_t *d_query, const int8_t *d_pssm, uint32_t lq, uint32_t g, uint32_t e,
-                                 int k, uint32_t S, int8_t *d_cprof, void *d_table, int bits, hipStream_t stream)
+                                 int k, uint32_t S, int8_t *d_cprof, void *d_table, int bits, hipStream_t stream, bool spans)
 {
     const uint32_t n = (uint32_t)swg_kmer_entries(k);
     if (n == 0u || lq == 0u || lq > (1u << 24) || S == 0u || S > SWG_KMER_REFINE_SEGMENTS || (bits != 8 && bits != 16)) return hipErrorInvalidValue;
+    if (spans && (k != 5 || bits != 8 || e == 0u || e > 255u)) return hipErrorInvalidValue; // (the fifth level's second entries: bytes of k = 5)
     // (gap magnitudes beyond any block's score change nothing, and keep the int32 cells far from their range)
     const int gi = (int)(g > 65536u ? 65536u : g), ei = (int)(e > 65536u ? 65536u : e);
     hipLaunchKernelGGL(swg_kmer_cprof_kernel, dim3((lq * 32u + 255u) / 256u), dim3(256), 0, stream, d_sub, d_query, d_pssm, lq, d_cprof);
     const dim3 grid((n + 255u) / 256u);
     const uint32_t n4 = (uint32_t)swg_kmer_entries(4); // (k = 5: a thread per 4-class prefix)
-    if (k == 5 && bits == 8)
+    if (spans)
+        hipLaunchKernelGGL((swg_kmer_table5_kernel<uint8_t, true>), dim3((n4 + 255u) / 256u), dim3(256), 0, stream, d_cprof, lq, gi, ei, n4, S, static_cast<uint8_t *>(d_table));
+    else if (k == 5 && bits == 8)
         hipLaunchKernelGGL((swg_kmer_table5_kernel<uint8_t>), dim3((n4 + 255u) / 256u), dim3(256), 0, stream, d_cprof, lq, gi, ei, n4, S, static_cast<uint8_t *>(d_table));
     else if (k == 5)
         hipLaunchKernelGGL((swg_kmer_table5_kernel<uint16_t>), dim3((n4 + 255u) / 256u), dim3(256), 0, stream, d_cprof, lq, gi, ei, n4, S, static_cast<uint16_t *>(d_table));
@@ -3659,6 +3671,165 @@ __global__ __launch_bounds__(256) void swg_pair_bound_refine_kernel(const uint4 
     }
     const uint32_t refined = group_max();
     if (l == 0u && refined < first) bound[p] = refined;
+}
+
+// The fifth level ("a fifth level"): the fourth level's walk -- swg_pair_bound_refine_kernel<5, 8>'s lanes,
+// blocks, tail, padding, reset and leave-at-once rules -- over two tables of bytes, the fourth level's entries t and the
+// second entries t2 (swg_kmer_table5_kernel<E, true>), with the query columns between two blocks' chains charged: n whole
+// segments between the segments s'' < s where they end cost at least c n, c = e W.  With tm[s] = min(t[s], colmax sum):
+//   H'[s] = max( max(H[s], H[s - 1]) + tm[s],  max_{n = 1..N} H[s - 1 - n] + min(tm[s], t2[s] - c n),
+//                min( tm[s] + max_{s'' < s - 1 - N} H[s''],  t2[s] - c (s - 1) + max_{s'' < s - 1 - N} (H[s''] + c s'') ) )
+// (tm >= 0: the first term keeps H[s], a block may be left out).  Lane l holds segments 8 l .. 8 l + 7: the two prefix
+// maxima run in the lane and then across the lanes as swg_refine_step's does, and what a segment needs from below its
+// lane's first -- N + 1 values of H, N + 2 of each prefix maximum -- comes from the lane below by wave_shr:1, 0 in the
+// group's first lane: H = 0 in a segment that does not exist adds at most tm, which the first term holds already.
+// wt, wt2: the lane's 8 entries of the block in each table; cs: the block's colmax sum; cl = c x 8 l.
+template <int N>
+__device__ __forceinline__ void swg_refine_step5(uint32_t (&h)[8], uint2 wt, uint2 wt2, uint32_t cs, uint32_t m0, int c, int cl)
+{
+    static_assert(N >= 0 && N + 2 <= 8, "what a segment needs from below comes from its own lane and the one below it");
+    auto below = [&](uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true) & m0; };
+    uint32_t ph[8], pc[8];
+    ph[0] = h[0], pc[0] = h[0] + (uint32_t)cl;
+#pragma unroll
+    for (int j = 1; j < 8; ++j) {
+        const uint32_t v = h[j] + (uint32_t)(cl + c * j);
+        ph[j] = h[j] > ph[j - 1] ? h[j] : ph[j - 1];
+        pc[j] = v > pc[j - 1] ? v : pc[j - 1];
+    }
+    const uint32_t exh = swg_seg_prefix_max<32>(below(ph[7]), 0u, 0u, 0u), exc = swg_seg_prefix_max<32>(below(pc[7]), 0u, 0u, 0u);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ph[j] = exh > ph[j] ? exh : ph[j], pc[j] = exc > pc[j] ? exc : pc[j];
+    uint32_t qh[N + 1], qph[N + 2], qpc[N + 2]; // (of the lane below: its h[7 - i], ph[7 - i], pc[7 - i])
+#pragma unroll
+    for (int i = 0; i < N + 1; ++i) qh[i] = below(h[7 - i]);
+#pragma unroll
+    for (int i = 0; i < N + 2; ++i) qph[i] = below(ph[7 - i]), qpc[i] = below(pc[7 - i]);
+    uint32_t hn[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint32_t wa = j < 4 ? wt.x : wt.y, wb = j < 4 ? wt2.x : wt2.y;
+        const uint32_t en = (wa >> (8 * (j & 3))) & 0xFFu;
+        const int tm = (int)(en < cs ? en : cs), t2 = (int)((wb >> (8 * (j & 3))) & 0xFFu);
+        const uint32_t h1 = j >= 1 ? h[j - 1] : qh[0];
+        int best = (int)(h[j] > h1 ? h[j] : h1) + tm;
+        // (j and n are compile-time: each of the two sources below is one register; the branch not taken gets index 0)
+#pragma unroll
+        for (int n = 1; n <= N; ++n) {
+            const int hb = (int)(j - 1 - n >= 0 ? h[j - 1 - n >= 0 ? j - 1 - n : 0] : qh[n - j >= 0 && n - j <= N ? n - j : 0]);
+            best = max(best, hb + min(tm, t2 - c * n));
+        }
+        constexpr int D = N + 2;
+        const int fh = (int)(j >= D ? ph[j >= D ? j - D : 0] : qph[j < D ? D - 1 - j : 0]);
+        const int fc = (int)(j >= D ? pc[j >= D ? j - D : 0] : qpc[j < D ? D - 1 - j : 0]);
+        best = max(best, min(tm + fh, t2 - (cl + c * j - c) + fc));
+        hn[j] = (uint32_t)best;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) h[j] = hn[j];
+}
+
+// U blocks in order, as swg_refine_round takes them, both tables' entries gathered ahead of the recurrence
+template <int U, bool ONE_UNIT>
+__device__ __forceinline__ void swg_refine_round5(const uint32_t (&ux)[ONE_UNIT ? U : 1], const uint32_t (&uy)[ONE_UNIT ? U : 1],
+                                                  const uint32_t (&uc)[ONE_UNIT ? U : 1], int src, const uint8_t *tl, const uint8_t *tl2, uint32_t (&hx)[8],
+                                                  uint32_t (&hy)[8], uint32_t m0, int c, int cl)
+{
+    uint2 tx[U], ty[U], sx[U], sy[U];
+    uint32_t cs[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int from = ONE_UNIT ? src : src + u, b = ONE_UNIT ? u : 0;
+        const uint32_t ix = (uint32_t)__shfl((int)ux[b], from, 32), iy = (uint32_t)__shfl((int)uy[b], from, 32);
+        cs[u] = (uint32_t)__shfl((int)uc[b], from, 32);
+        tx[u] = *reinterpret_cast<const uint2 *>(tl + (size_t)ix * 256u), sx[u] = *reinterpret_cast<const uint2 *>(tl2 + (size_t)ix * 256u);
+        ty[u] = *reinterpret_cast<const uint2 *>(tl + (size_t)iy * 256u), sy[u] = *reinterpret_cast<const uint2 *>(tl2 + (size_t)iy * 256u);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        swg_refine_step5<SWG_REFINE5_EXPLICIT>(hx, tx[u], sx[u], cs[u] & 0xFFFFu, m0, c, cl);
+        swg_refine_step5<SWG_REFINE5_EXPLICIT>(hy, ty[u], sy[u], cs[u] >> 16, m0, c, cl);
+    }
+}
+
+// c = e W: what the columns of one segment cost at least, as a gap
+// (four wavefronts per SIMD: a round is a gather and then eight dependent steps, and the wavefronts beside it are what hides
+// the gather)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void swg_pair_bound_refine5_kernel(const uint4 *tok, const uint32_t *pair_off, uint32_t begin, uint32_t end, SwgColMax cm,
+                                                                     const uint8_t *table, const uint8_t *table2, int c, const uint32_t *thr,
+                                                                     uint32_t *bound)
+{
+    __shared__ uint32_t lut[32]; // residue index -> class | colmax << 8
+    if (threadIdx.x < 32u) lut[threadIdx.x] = swg_kmer_class(threadIdx.x) | (uint32_t)cm.v[threadIdx.x] << 8;
+    __syncthreads();
+    const uint32_t p = begin + blockIdx.x * 8u + (threadIdx.x >> 5), l = threadIdx.x & 31u;
+    if (p >= end) return; // (the same for all lanes of a group, and so is everything below)
+    const uint32_t T = thr[0], first = bound[p];
+    if (first < T) return;
+    const uint32_t C = SWG_KMER_CLASSES;
+    const uint8_t *tl = table + l * 8u, *tl2 = table2 + l * 8u;
+    const uint32_t m0 = l >= 1u ? 0xFFFFFFFFu : 0u;
+    const int cl = c * 8 * (int)l;
+    uint32_t hx[8], hy[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) hx[j] = 0u, hy[j] = 0u;
+    const uint32_t b0 = pair_off[p], e = pair_off[p + 1u];
+    const uint32_t groups = (e - b0) / 5u, tail = b0 + 5u * groups;
+    for (uint32_t g0 = 0u; g0 < groups; g0 += 32u) {
+        uint32_t ux[4] = {0u, 0u, 0u, 0u}, uy[4] = {0u, 0u, 0u, 0u}, uc[4] = {0u, 0u, 0u, 0u};
+        if (g0 + l < groups) {
+            uint32_t x[20], y[20];
+#pragma unroll
+            for (int u = 0; u < 5; ++u) {
+                const uint4 k = tok[b0 + 5u * (g0 + l) + (uint32_t)u];
+                x[4 * u] = lut[(k.x >> 3) & 31u], x[4 * u + 1] = lut[(k.y >> 3) & 31u], x[4 * u + 2] = lut[(k.z >> 3) & 31u], x[4 * u + 3] = lut[(k.w >> 3) & 31u];
+                y[4 * u] = lut[(k.x >> 11) & 31u], y[4 * u + 1] = lut[(k.y >> 11) & 31u], y[4 * u + 2] = lut[(k.z >> 11) & 31u], y[4 * u + 3] = lut[(k.w >> 11) & 31u];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                uint32_t ix = 0u, iy = 0u, sx = 0u, sy = 0u;
+#pragma unroll
+                for (int j = 0; j < 5; ++j) {
+                    ix = ix * C + (x[5 * u + j] & 255u), sx += x[5 * u + j] >> 8;
+                    iy = iy * C + (y[5 * u + j] & 255u), sy += y[5 * u + j] >> 8;
+                }
+                ux[u] = ix, uy[u] = iy, uc[u] = sx | sy << 16;
+            }
+        }
+        const uint32_t cnt = groups - g0 < 32u ? groups - g0 : 32u;
+        for (uint32_t j = 0u; j < cnt; ++j) swg_refine_round5<4, true>(ux, uy, uc, (int)j, tl, tl2, hx, hy, m0, c, cl);
+    }
+    for (uint32_t t0 = tail; t0 < e; t0 += 32u) {
+        uint32_t ux[1] = {0u}, uy[1] = {0u}, uc[1] = {0u}; // (past the pair's end: the all-padding block, whose entries are 0)
+        if (t0 + l < e) {
+            const uint4 k = tok[t0 + l];
+            const uint32_t xa = lut[(k.x >> 3) & 31u], xb = lut[(k.y >> 3) & 31u], xc = lut[(k.z >> 3) & 31u], xd = lut[(k.w >> 3) & 31u];
+            const uint32_t ya = lut[(k.x >> 11) & 31u], yb = lut[(k.y >> 11) & 31u], yc = lut[(k.z >> 11) & 31u], yd = lut[(k.w >> 11) & 31u];
+            ux[0] = ((((xa & 255u) * C + (xb & 255u)) * C + (xc & 255u)) * C + (xd & 255u)) * C;
+            uy[0] = ((((ya & 255u) * C + (yb & 255u)) * C + (yc & 255u)) * C + (yd & 255u)) * C;
+            uc[0] = ((xa >> 8) + (xb >> 8) + (xc >> 8) + (xd >> 8)) | ((ya >> 8) + (yb >> 8) + (yc >> 8) + (yd >> 8)) << 16;
+        }
+        const uint32_t cnt = e - t0 < 32u ? e - t0 : 32u;
+        // (src + u < 32: cnt <= 32, both multiples of 4 apart from cnt)
+        for (uint32_t j0 = 0u; j0 < cnt; j0 += 4u) swg_refine_round5<4, false>(ux, uy, uc, (int)j0, tl, tl2, hx, hy, m0, c, cl);
+    }
+    uint32_t m = 0u;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m = hx[j] > m ? hx[j] : m, m = hy[j] > m ? hy[j] : m;
+    const uint32_t refined = (uint32_t)__shfl((int)swg_seg_prefix_max<32>(m, 0u, 0u, 0u), 31, 32);
+    if (l == 0u && refined < first) bound[p] = refined;
+}
+
+hipError_t swg_launch_pair_bound_refine5(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, const SwgColMax &cm,
+                                         const uint8_t *d_table, const uint8_t *d_table2, uint32_t lq, uint32_t e, const uint32_t *d_thr, uint32_t *d_bound,
+                                         hipStream_t stream)
+{
+    if (end < begin || !swg_kmer_refine5_admitted(cm, (int)(e > 65536u ? 65536u : e), lq)) return hipErrorInvalidValue;
+    if (end == begin) return hipSuccess;
+    const uint32_t W = (lq + SWG_KMER_REFINE4_SEGMENTS - 1u) / SWG_KMER_REFINE4_SEGMENTS;
+    hipLaunchKernelGGL(swg_pair_bound_refine5_kernel, dim3((end - begin + 7u) / 8u), dim3(256), 0, stream, d_tok, d_pair_off, begin, end, cm, d_table, d_table2,
+                       (int)(e * W), d_thr, d_bound);
+    return hipGetLastError();
 }
 
 hipError_t swg_launch_pair_bound_refine(const uint4 *d_tok, const uint32_t *d_pair_off, uint32_t begin, uint32_t end, uint32_t S2, const SwgColMax &cm,
