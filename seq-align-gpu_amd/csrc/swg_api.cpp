@@ -108,7 +108,9 @@ template <class F> static int ctx_guarded(swg_ctx *ctx, const char *what, F &&f)
 // throws std::bad_alloc as a failed allocation there would.  Sites: 1 = body of swg_search_begin, 2 = body of
 // swg_search_end, 3 = the fall-back key vector of swg_search_end (reached only when the device top-K could not be
 // used).  One shot: the hook clears itself when it fires.  Site 4 is not an exception: the next growth of
-// swg_search_above_multi's key pool is refused as if the device had no room (above_multi_pool).
+// swg_search_above_multi's key pool is refused as if the device had no room (above_multi_pool).  Nor are sites 5 and 6:
+// the next reservation of the fourth level's table (5) or of the fifth's (6) of a pruned search is refused in the same
+// way (reserve_refine_table).
 static int g_fail_alloc_site = 0;
 extern "C" void swg_debug_fail_alloc(int site) { g_fail_alloc_site = site; }
 static inline void fail_alloc_here(int site)
@@ -259,10 +261,7 @@ extern "C" void swg_destroy(swg_ctx *ctx)
     (void)hipFree(ctx->d_kmer_cprof);
     (void)hipFree(ctx->kmer_first[0].d);
     (void)hipFree(ctx->kmer_first[1].d);
-    (void)hipFree(ctx->kmer_second.d);
-    (void)hipFree(ctx->kmer_third.d);
-    (void)hipFree(ctx->kmer_fourth.d);
-    (void)hipFree(ctx->kmer_fifth.d);
+    for (SwgKmerTable &t : ctx->kmer_refine) (void)hipFree(t.d);
     (void)hipFree(ctx->d_profile[0]);
     (void)hipFree(ctx->d_profile[1]);
     (void)hipFree(ctx->d_profile[2]);
@@ -295,6 +294,14 @@ extern "C" void swg_destroy(swg_ctx *ctx)
     if (ctx->stream3) (void)hipStreamDestroy(ctx->stream3);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
+}
+
+// the row of SWG_REFINE_LEVEL whose option `key` names, or -1
+static int refine_option_row(const char *key)
+{
+    for (int i = 0; i < SWG_REFINE_LEVELS; ++i)
+        if (!strcmp(key, SWG_REFINE_LEVEL[i].option)) return i;
+    return -1;
 }
 
 extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
@@ -368,22 +375,9 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
         if (value < 0 || value > (long)SWG_KMER_MAX_SEGMENTS)
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_segments must be 0 (auto) or 1..32 (the segments of the k-mer bound's table; 1: unsegmented)");
         ctx->opt_prune_segments = value;
-    } else if (!strcmp(key, "prune_refine")) {
-        if (!swg_prune_refine_value_ok(value))
-            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_refine must be 0 (auto), 1 (off), 64 or 128 (the segments of the second-level bound's table)");
-        ctx->opt_prune_refine = value;
-    } else if (!strcmp(key, "prune_refine3")) {
-        if (!swg_prune_refine3_value_ok(value))
-            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_refine3 must be 0 (auto), 1 (off) or 256 (the segments of the third-level bound's table)");
-        ctx->opt_prune_refine3 = value;
-    } else if (!strcmp(key, "prune_refine4")) {
-        if (!swg_prune_refine4_value_ok(value))
-            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_refine4 must be 0 (auto), 1 (off) or 5256 (the fourth-level bound's table: k = 5 in 256 segments)");
-        ctx->opt_prune_refine4 = value;
-    } else if (!strcmp(key, "prune_refine5")) {
-        if (!swg_prune_refine5_value_ok(value))
-            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_refine5 must be 0 (auto), 1 (off) or 5256 (the fifth-level bound: both k = 5 tables in 256 segments)");
-        ctx->opt_prune_refine5 = value;
+    } else if (const int row = refine_option_row(key); row >= 0) { // "prune_refine" .. "prune_refine5"
+        if (!swg_refine_value_ok(row, value)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "%s", SWG_REFINE_LEVEL[row].option_error);
+        ctx->opt_prune_refine[row] = value;
     } else if (!strcmp(key, "prune_gate")) {
         if (!swg_prune_gate_value_ok(value))
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "prune_gate must be 0 (auto), 1 (off) or 2 (wherever the first-level bound is a segmented k-mer bound)");
@@ -1279,6 +1273,21 @@ static int dyn_fill_begin(DynFill *F, int go, int ge, uint64_t *d_trace)
     return SWG_OK;
 }
 
+// The walk of the level of row i of SWG_REFINE_LEVEL over the pairs of [begin, end) whose bound reaches *d_thr, in S
+// segments of the level's table: blocks of the table's k over the pairs every earlier level has left at or above that
+// word.  The fifth level's walk is a kernel of its own: the same blocks over both k = 5 tables, the columns between two
+// blocks charged.
+static hipError_t launch_refine_level(swg_ctx *ctx, const SwgPairTokens &T, int i, uint32_t begin, uint32_t end, int S, const uint32_t *d_thr,
+                                      uint32_t *d_bound, hipStream_t qs)
+{
+    const SwgRefineLevel &L = SWG_REFINE_LEVEL[i];
+    const SwgKmerTable &t = ctx->kmer_refine[i];
+    if (L.reads >= 0)
+        return swg_launch_pair_bound_refine5(T.d_tok, T.d_pair_off, begin, end, ctx->prune_colmax, ctx->kmer_refine[L.reads].d, t.d, (uint32_t)ctx->query_len(),
+                                             (uint32_t)-(long)ctx->gap_extend, d_thr, d_bound, qs);
+    return swg_launch_pair_bound_refine(T.d_tok, T.d_pair_off, begin, end, (uint32_t)S, ctx->prune_colmax, t.d, t.bits, d_thr, d_bound, qs, L.k);
+}
+
 // The fill of a pruned search, stage by stage -- all passes of a stage, then the threshold so far and the
 // next stage's cut, all on the fill's stream with no host wait.  The bound of every pair first -- unless the list queues
 // the first level with a stage (the gate: behind that stage's threshold, for the pairs from it on) --; then the stages of
@@ -1335,22 +1344,10 @@ static int enqueue_pruned_fill(swg_ctx *ctx, swg_db *db, const SwgPrunePlan &pr,
         }
         if (st.queued & SWG_STAGE_PREFIX_CUT) HIP_TRY(ctx, swg_launch_prune_cut(L.bounds, T.d_pair_off, st.begin, st.end, thr, cut_word, qs));
         if (st.queued & SWG_STAGE_GATE) HIP_TRY(ctx, swg_launch_prune_refine_gate(L.bounds, st.begin, st.end, thr, gate, qs));
-        if (st.queued & SWG_STAGE_REFINE)
-            HIP_TRY(ctx, swg_launch_pair_bound_refine(T.d_tok, T.d_pair_off, st.begin, st.end, (uint32_t)pr.refine, ctx->prune_colmax, ctx->kmer_second.d,
-                                                      ctx->kmer_second.bits, st.queued & SWG_STAGE_GATE ? gate : thr, L.bounds, qs));
-        // (the third level: the pairs the second left at or above the same word, so a gated stage skips both walks together)
-        if (st.queued & SWG_STAGE_REFINE3)
-            HIP_TRY(ctx, swg_launch_pair_bound_refine(T.d_tok, T.d_pair_off, st.begin, st.end, (uint32_t)pr.refine3, ctx->prune_colmax, ctx->kmer_third.d,
-                                                      ctx->kmer_third.bits, st.queued & SWG_STAGE_GATE ? gate : thr, L.bounds, qs));
-        // (the fourth: blocks of 5 over the pairs every k = 4 level has left at or above that word)
-        if (st.queued & SWG_STAGE_REFINE4)
-            HIP_TRY(ctx, swg_launch_pair_bound_refine(T.d_tok, T.d_pair_off, st.begin, st.end, (uint32_t)pr.refine4, ctx->prune_colmax, ctx->kmer_fourth.d,
-                                                      ctx->kmer_fourth.bits, st.queued & SWG_STAGE_GATE ? gate : thr, L.bounds, qs, 5));
-        // (the fifth: the same blocks over both k = 5 tables, the columns between two blocks charged)
-        if (st.queued & SWG_STAGE_REFINE5)
-            HIP_TRY(ctx, swg_launch_pair_bound_refine5(T.d_tok, T.d_pair_off, st.begin, st.end, ctx->prune_colmax, ctx->kmer_fourth.d, ctx->kmer_fifth.d,
-                                                       (uint32_t)ctx->query_len(), (uint32_t)-(long)ctx->gap_extend, st.queued & SWG_STAGE_GATE ? gate : thr,
-                                                       L.bounds, qs));
+        // (the levels behind the first, in their order and under one word: a gated stage skips all the walks together)
+        for (int i = 0; i < SWG_REFINE_LEVELS; ++i)
+            if (st.queued & SWG_REFINE_LEVEL[i].stage_bit)
+                HIP_TRY(ctx, launch_refine_level(ctx, T, i, st.begin, st.end, pr.refine[i], st.queued & SWG_STAGE_GATE ? gate : thr, L.bounds, qs));
         if (st.queued & SWG_STAGE_LIST) {
             const size_t rec = db->prune_stages.size() / 2;
             HIP_TRY(ctx, swg_launch_prune_list(L.bounds, T.d_pair_off, st.begin, st.end, thr, L.tiles, L.lists + st.begin, cut_word,
@@ -2452,9 +2449,7 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
     SwgKmerAsk ka;
     ka.forced = ctx->opt_prune_kmer;
     ka.forced_segments = ctx->opt_prune_segments;
-    ka.forced_refine = ctx->opt_prune_refine;
-    ka.forced_refine3 = ctx->opt_prune_refine3;
-    ka.forced_refine4 = ctx->opt_prune_refine4;
+    std::copy(ctx->opt_prune_refine, ctx->opt_prune_refine + SWG_REFINE_LEVELS, ka.forced_refine);
     ensure_prune_colmax(ctx);
     ka.table_bits = kmer_table_bits(ctx, 4);
     ka.table_bits5 = kmer_table_bits(ctx, 5);
@@ -2465,22 +2460,22 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
     P->prune.kmer = swg_prune_kmer_choice(ka, &P->prune.segments);
     // how a stage is cut: pair by pair, behind the second-level bound where that pays, or the prefix of the length order
     P->prune.prefix_cut = ctx->opt_prune_cut == 1 && !P->prune.fixed; // (a caller's threshold takes the list)
-    P->prune.refine = P->prune.prefix_cut ? 0 : swg_prune_refine_choice(ka, P->prune.kmer, P->prune.segments);
-    P->prune.refine3 = P->prune.prefix_cut ? 0 : swg_prune_refine3_choice(ka, P->prune.kmer, P->prune.segments, P->prune.refine);
-    // (a context whose fourth table could not be allocated searches without the level: reserve_kmer_fourth)
-    P->prune.refine4 = P->prune.prefix_cut || ctx->kmer_fourth_refused
-                           ? 0
-                           : swg_prune_refine4_choice(ka, P->prune.kmer, P->prune.segments, P->prune.refine, P->prune.refine3);
-    // (the fifth: e > 0, second entries that are bytes, and like the fourth a buffer that could be allocated)
-    ka.forced_refine5 = ctx->opt_prune_refine5;
+    // (the fifth level: e > 0 and second entries that are bytes)
     ka.fixed = P->prune.fixed;
     ka.refine5_ok = ctx->gap_extend <= 0 && swg_kmer_refine5_admitted(ctx->prune_colmax, (int)std::min<long>(-(long)ctx->gap_extend, 65536), ka.lq);
-    P->prune.refine5 = P->prune.prefix_cut || ctx->kmer_fourth_refused || ctx->kmer_fifth_refused ? 0 : swg_prune_refine5_choice(ka, P->prune.kmer, P->prune.refine4);
+    swg_prune_refine_choices(ka, P->prune.kmer, P->prune.segments, P->prune.refine);
+    // (not under the prefix cut; and a context that could not allocate a table a level reads searches without the level:
+    // reserve_refine_table)
+    for (int i = 0; i < SWG_REFINE_LEVELS; ++i) {
+        const int reads = SWG_REFINE_LEVEL[i].reads;
+        if (P->prune.prefix_cut || ctx->kmer_refine_refused[i] || (reads >= 0 && ctx->kmer_refine_refused[reads])) P->prune.refine[i] = 0;
+    }
     // whether the first level's launch waits for a threshold (the pairs whose colmax bound is below it are not walked)
     ka.forced_gate = ctx->opt_prune_gate;
     // (not under the prefix cut, which like the levels behind the first keeps to what it was measured with)
     P->prune.gate = !P->prune.prefix_cut && swg_prune_gate_choice(ka, P->prune.kmer, P->prune.segments);
-    ctx->prune_choice = SwgPruneChoice{P->prune.kmer, P->prune.segments, P->prune.refine, P->prune.refine3, P->prune.refine4, P->prune.gate ? 1 : 0, P->prune.refine5};
+    ctx->prune_choice.kmer = P->prune.kmer, ctx->prune_choice.segments = P->prune.segments, ctx->prune_choice.gate = P->prune.gate ? 1 : 0;
+    std::copy(P->prune.refine, P->prune.refine + SWG_REFINE_LEVELS, ctx->prune_choice.refine);
     return SWG_OK;
 }
 
@@ -2489,8 +2484,9 @@ static int plan_prune(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, SwgS
 // copy of the query a set_query queued there and behind any search still in flight, in front of the bound kernel that
 // reads it: the rule the profiles follow (ensure_profile_cols).  A table that holds (epoch, k, S) already is left alone; it
 // grows when S x entries does.  Which (k, S) a table may hold is the caller's to say.
-// spans: the fifth level's second entries instead (swg_kmer_table5_kernel<E, true>), of k = 5 as bytes.
-static int ensure_kmer_table(swg_ctx *ctx, SwgKmerTable *t, int k, int S, bool spans = false)
+// spans: the fifth level's second entries instead (swg_kmer_table5_kernel<E, true>), of k = 5 as bytes.  *builds: the
+// counter of the level the table belongs to.
+static int ensure_kmer_table(swg_ctx *ctx, SwgKmerTable *t, uint64_t *builds, int k, int S, bool spans = false)
 {
     const int bits = kmer_table_bits(ctx, k);
     if (t->holds(ctx->epoch, k, S, bits)) return SWG_OK;
@@ -2505,32 +2501,43 @@ static int ensure_kmer_table(swg_ctx *ctx, SwgKmerTable *t, int k, int S, bool s
     HIP_TRY(ctx, swg_launch_kmer_table(ctx->d_sub, ctx->d_query, ctx->query_pssm ? ctx->d_pssm : nullptr, (uint32_t)lq, (uint32_t)-go, (uint32_t)-ge, k,
                                        (uint32_t)S, ctx->d_kmer_cprof, t->d, bits, ctx->stream, spans));
     t->epoch = ctx->epoch, t->k = k, t->segments = S, t->bits = bits;
-    ++(t == &ctx->kmer_fifth   ? ctx->kmer_refine5_builds
-       : t == &ctx->kmer_fourth ? ctx->kmer_refine4_builds
-       : t == &ctx->kmer_third ? ctx->kmer_refine3_builds
-       : t == &ctx->kmer_second ? ctx->kmer_refine_builds
-                                : ctx->kmer_builds);
+    ++*builds;
     return SWG_OK;
 }
 
-// The fourth level's table is 1.32 GB: its buffer is allocated in front of the search that first wants it, and an
-// allocation that fails is no error -- the search, and every later one of this context, runs without the level (the
-// capacity is written only once the buffer stands).  -> whether the buffer stands.
-static bool reserve_kmer_fourth(swg_ctx *ctx, bool fifth = false)
+// A reserved table (SwgRefineLevel::reserved: the fourth level's and the fifth's, 1.32 GB each): the buffer of row i's
+// table is allocated in front of the search that first wants it, and an allocation that fails is no error -- the search,
+// and every later one of this context, runs without the levels that read the table (the capacity is written only once
+// the buffer stands; a table refused once is not asked for again).  -> whether the buffer stands.
+static bool reserve_refine_table(swg_ctx *ctx, int i)
 {
-    SwgKmerTable *t = fifth ? &ctx->kmer_fifth : &ctx->kmer_fourth;
-    const size_t bytes = (size_t)swg_kmer_entries(5) * SWG_KMER_REFINE4_SEGMENTS;
+    SwgKmerTable *t = &ctx->kmer_refine[i];
+    const size_t bytes = (size_t)swg_kmer_entries(SWG_REFINE_LEVEL[i].k) * SWG_KMER_REFINE4_SEGMENTS;
+    if (ctx->kmer_refine_refused[i]) return false;
     if (t->d && t->cap >= bytes) return true;
     (void)hipFree(t->d);
     t->d = nullptr, t->cap = 0, t->epoch = 0;
     uint8_t *d = nullptr;
-    if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&d, bytes) != hipSuccess) {
+    const bool refuse = g_fail_alloc_site == 3 + i; // (swg_debug_fail_alloc sites 5 and 6, 1 + the level: this allocation fails, once)
+    if (refuse) g_fail_alloc_site = 0;
+    if (refuse || hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&d, bytes) != hipSuccess) {
         (void)hipGetLastError(); // (taken: the search goes on)
-        (fifth ? ctx->kmer_fifth_refused : ctx->kmer_fourth_refused) = true;
+        ctx->kmer_refine_refused[i] = true;
         return false;
     }
     t->d = d, t->cap = bytes;
     return true;
+}
+// The reserved tables of the levels a plan has; a level that reads a table which cannot be had goes, from the plan and
+// from what the context reports (the fifth level reads the fourth's table and its own: without either buffer the search
+// runs without it -- and where it was chosen behind an automatic fourth level that is now off, without both).
+static void reserve_refine_tables(swg_ctx *ctx, SwgPrunePlan *pr)
+{
+    for (int i = 0; i < SWG_REFINE_LEVELS; ++i) {
+        const SwgRefineLevel &L = SWG_REFINE_LEVEL[i];
+        if (!pr->refine[i] || !L.reserved) continue;
+        if ((L.reads >= 0 && !reserve_refine_table(ctx, L.reads)) || !reserve_refine_table(ctx, i)) pr->refine[i] = 0, ctx->prune_choice.refine[i] = 0;
+    }
 }
 
 // What a pruned search reads besides the fill's own: the colmax table for the current query and scoring (built on the
@@ -2547,26 +2554,19 @@ static int prepare_prune(swg_ctx *ctx, swg_db *db, const SwgPrunePlan &pr)
         if (!swg_kmer_table_admitted(k, S))
             return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the k-mer bound's table of k = %d in %d segments is %zu MB: above its budget of %zu MB (prune_kmer, prune_segments)", k,
                                      S, (size_t)swg_kmer_entries(k) * (size_t)S * sizeof(uint16_t) >> 20, (size_t)(SWG_KMER_TABLE_BUDGET >> 20));
-        if ((rc = ensure_kmer_table(ctx, &ctx->kmer_first[k - 4], k, S)) != SWG_OK) return rc;
+        if ((rc = ensure_kmer_table(ctx, &ctx->kmer_first[k - 4], &ctx->kmer_builds, k, S)) != SWG_OK) return rc;
     }
-    if (pr.refine) {
-        if (pr.refine != 64 && pr.refine != 128) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the second-level bound's table: %d segments (64 or 128)", pr.refine);
-        if ((rc = ensure_kmer_table(ctx, &ctx->kmer_second, 4, pr.refine)) != SWG_OK) return rc;
-    }
-    if (pr.refine3) {
-        if (pr.refine3 != 256) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the third-level bound's table: %d segments (256)", pr.refine3);
-        if ((rc = ensure_kmer_table(ctx, &ctx->kmer_third, 4, pr.refine3)) != SWG_OK) return rc;
-    }
-    if (pr.refine4) {
-        if (pr.refine4 != (int)SWG_KMER_REFINE4_SEGMENTS || !swg_kmer_refine4_admitted(kmer_table_bits(ctx, 5)))
-            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the fourth-level bound's table: %d segments (256) of bytes", pr.refine4);
-        if ((rc = ensure_kmer_table(ctx, &ctx->kmer_fourth, 5, pr.refine4)) != SWG_OK) return rc;
-    }
-    if (pr.refine5) { // (behind the table of (5, 256), which it reads as well -- with or without a fourth level's walk)
-        if (pr.refine5 != (int)SWG_KMER_REFINE4_SEGMENTS || !swg_kmer_refine4_admitted(kmer_table_bits(ctx, 5)))
-            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "the fifth-level bound's tables: %d segments (256) of bytes", pr.refine5);
-        if ((rc = ensure_kmer_table(ctx, &ctx->kmer_fourth, 5, pr.refine5)) != SWG_OK) return rc;
-        if ((rc = ensure_kmer_table(ctx, &ctx->kmer_fifth, 5, pr.refine5, true)) != SWG_OK) return rc;
+    // the levels behind the first: segments the level's option can name, a table of 5-residue blocks as bytes only; then
+    // the table it reads besides its own (the fifth level the fourth's -- with or without a fourth level's walk) and its own
+    for (int i = 0; i < SWG_REFINE_LEVELS; ++i) {
+        const SwgRefineLevel &L = SWG_REFINE_LEVEL[i];
+        const int S = pr.refine[i];
+        if (!S) continue;
+        if ((S != L.forced[0].segments && S != L.forced[1].segments) || (L.k == 5 && !swg_kmer_refine4_admitted(kmer_table_bits(ctx, 5))))
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, L.table_error, S);
+        if (L.reads >= 0 && (rc = ensure_kmer_table(ctx, &ctx->kmer_refine[L.reads], &ctx->kmer_refine_builds[L.reads], SWG_REFINE_LEVEL[L.reads].k, S)) != SWG_OK)
+            return rc;
+        if ((rc = ensure_kmer_table(ctx, &ctx->kmer_refine[i], &ctx->kmer_refine_builds[i], L.k, S, L.spans)) != SWG_OK) return rc;
     }
     swg_db::Bufs &b = db->bufs[ctx->cur - ctx->slots];
     const size_t n_pairs = (size_t)swg_db_pair_count(db);
@@ -2780,10 +2780,7 @@ static int search_begin(swg_ctx *ctx, swg_db *db, bool want_scores, size_t k, bo
     if (db->n_bins == 0) return SWG_OK;
     if ((rc = plan_search(ctx, db, allow_autotune, &S->plan)) != SWG_OK) return rc;
     if ((rc = plan_prune(ctx, db, want_scores, k, &S->plan)) != SWG_OK) return rc;
-    if (S->plan.prune.refine4 && !reserve_kmer_fourth(ctx)) S->plan.prune.refine4 = 0, ctx->prune_choice.refine4 = 0;
-    // (the fifth level reads the fourth's table and its own; without either buffer the search runs without it -- and where
-    // it was chosen behind an automatic fourth level that is now off, without both)
-    if (S->plan.prune.refine5 && (!reserve_kmer_fourth(ctx) || !reserve_kmer_fourth(ctx, true))) S->plan.prune.refine5 = 0, ctx->prune_choice.refine5 = 0;
+    reserve_refine_tables(ctx, &S->plan.prune);
     if ((rc = prepare_search(ctx, db, S->plan)) != SWG_OK) return rc;
     if ((rc = enqueue_fill(ctx, db, S->plan, S)) != SWG_OK) return rc;
     if ((rc = enqueue_rescore(ctx, db, S->plan, S)) != SWG_OK) return rc;
@@ -3047,8 +3044,8 @@ static int debug_prune_read(swg_ctx *ctx, const swg_db *db, const char *fn, cons
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipDeviceSynchronize());
     const size_t n_pairs = db ? (size_t)swg_db_pair_count(db) : 0;
-    const uint64_t all[7] = {(uint64_t)ctx->prune_choice.kmer, ctx->kmer_builds, n_pairs, (uint64_t)ctx->prune_choice.segments, (uint64_t)ctx->prune_choice.refine,
-                             ctx->kmer_refine_builds, 0};
+    const uint64_t all[7] = {(uint64_t)ctx->prune_choice.kmer, ctx->kmer_builds, n_pairs, (uint64_t)ctx->prune_choice.segments, (uint64_t)ctx->prune_choice.refine[0],
+                             ctx->kmer_refine_builds[0], 0};
     std::copy(all, all + n_info, info);
     if (table_out) {
         if (!table || !table->holds(ctx->epoch, k, S, table->bits))
@@ -3096,7 +3093,7 @@ extern "C" int swg_debug_prune_kmer_seg_read(swg_ctx *ctx, const swg_db *db, int
 extern "C" int swg_debug_prune_refine_read(swg_ctx *ctx, const swg_db *db, int S2, uint16_t *table_out, uint32_t *bound_out, uint32_t *list_out, size_t pair_cap,
                                            uint32_t *stages_out, size_t stages_cap, uint64_t *info)
 {
-    return debug_prune_read(ctx, db, "swg_debug_prune_refine_read", ctx ? (S2 == 256 ? &ctx->kmer_third : &ctx->kmer_second) : nullptr, 4, S2, table_out, bound_out,
+    return debug_prune_read(ctx, db, "swg_debug_prune_refine_read", ctx ? &ctx->kmer_refine[S2 == 256 ? 1 : 0] : nullptr, 4, S2, table_out, bound_out,
                             list_out, pair_cap, stages_out, stages_cap, 7, info);
 }
 // ... the third level and the widths: out[0..6] = S3 of the search last begun (0: no third level), third-level builds so
@@ -3105,9 +3102,9 @@ extern "C" int swg_debug_prune_refine_read(swg_ctx *ctx, const swg_db *db, int S
 extern "C" int swg_debug_prune_tables(swg_ctx *ctx, int64_t *out)
 {
     if (!ctx || !out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_tables: NULL argument");
-    const SwgKmerTable *t[4] = {&ctx->kmer_first[0], &ctx->kmer_first[1], &ctx->kmer_second, &ctx->kmer_third};
-    out[0] = ctx->prune_choice.refine3;
-    out[1] = (int64_t)ctx->kmer_refine3_builds;
+    const SwgKmerTable *t[4] = {&ctx->kmer_first[0], &ctx->kmer_first[1], &ctx->kmer_refine[0], &ctx->kmer_refine[1]};
+    out[0] = ctx->prune_choice.refine[1];
+    out[1] = (int64_t)ctx->kmer_refine_builds[1];
     for (int i = 0; i < 4; ++i) out[2 + i] = t[i]->d && t[i]->epoch == ctx->epoch ? t[i]->bits : 0;
     out[6] = 0;
     if (ctx->query_len() > 0) {
@@ -3117,28 +3114,22 @@ extern "C" int swg_debug_prune_tables(swg_ctx *ctx, int64_t *out)
     return SWG_OK;
 }
 
-// ... the fourth level: out[0..3] = S4 of the search last begun (0: no fourth level), fourth-level builds so far, the
-// entry bits of the fourth table if it holds the current query and scoring (0: not), whether its allocation was refused
-extern "C" int swg_debug_prune_tables4(swg_ctx *ctx, int64_t *out)
+// ... a level with a reserved table, the fourth or the fifth (its own table: the second entries): out[0..3] = the
+// level's segments in the search last begun (0: without the level), builds of its table so far, the entry bits of the
+// table if it holds the current query and scoring (0: not), whether its allocation was refused
+static int debug_prune_level_tables(swg_ctx *ctx, int level, int64_t *out)
 {
-    if (!ctx || !out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_tables4: NULL argument");
-    out[0] = ctx->prune_choice.refine4;
-    out[1] = (int64_t)ctx->kmer_refine4_builds;
-    out[2] = ctx->kmer_fourth.d && ctx->kmer_fourth.epoch == ctx->epoch ? ctx->kmer_fourth.bits : 0;
-    out[3] = ctx->kmer_fourth_refused ? 1 : 0;
+    if (!ctx || !out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_tables%d: NULL argument", level);
+    const int i = level - 2;
+    const SwgKmerTable &t = ctx->kmer_refine[i];
+    out[0] = ctx->prune_choice.refine[i];
+    out[1] = (int64_t)ctx->kmer_refine_builds[i];
+    out[2] = t.d && t.epoch == ctx->epoch ? t.bits : 0;
+    out[3] = ctx->kmer_refine_refused[i] ? 1 : 0;
     return SWG_OK;
 }
-// ... the fifth level: out[0..3] = S5 of the search last begun (0: no fifth level), builds of its second table so far, 8
-// if that table holds the current query and scoring (0: not), whether its allocation was refused
-extern "C" int swg_debug_prune_tables5(swg_ctx *ctx, int64_t *out)
-{
-    if (!ctx || !out) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_tables5: NULL argument");
-    out[0] = ctx->prune_choice.refine5;
-    out[1] = (int64_t)ctx->kmer_refine5_builds;
-    out[2] = ctx->kmer_fifth.d && ctx->kmer_fifth.epoch == ctx->epoch ? ctx->kmer_fifth.bits : 0;
-    out[3] = ctx->kmer_fifth_refused ? 1 : 0;
-    return SWG_OK;
-}
+extern "C" int swg_debug_prune_tables4(swg_ctx *ctx, int64_t *out) { return debug_prune_level_tables(ctx, 4, out); }
+extern "C" int swg_debug_prune_tables5(swg_ctx *ctx, int64_t *out) { return debug_prune_level_tables(ctx, 5, out); }
 // ... the gate in front of the first level: out[0] = whether the search last begun took it (swg_prune_gate_choice)
 extern "C" int swg_debug_prune_gate(swg_ctx *ctx, int64_t *out)
 {
@@ -3146,22 +3137,12 @@ extern "C" int swg_debug_prune_gate(swg_ctx *ctx, int64_t *out)
     out[0] = ctx->prune_choice.gate;
     return SWG_OK;
 }
-// ... and n rows of its table: out[i][0..256) = the entries of class block blocks[i] (< 22^5), an error unless the table
-// holds the current query and scoring
-static int debug_prune_refine45_read(swg_ctx *ctx, const SwgKmerTable &t, const uint32_t *blocks, size_t n, uint16_t *out);
-extern "C" int swg_debug_prune_refine4_read(swg_ctx *ctx, const uint32_t *blocks, size_t n, uint16_t *out)
+// ... and n rows of the table of the fourth level, or of the fifth's second entries: out[i][0..256) = the entries of class
+// block blocks[i] (< 22^5), an error unless the table holds the current query and scoring
+static int debug_prune_level_rows(swg_ctx *ctx, int level, const uint32_t *blocks, size_t n, uint16_t *out)
 {
-    if (!ctx || (n > 0 && (!blocks || !out))) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_refine4_read: NULL argument");
-    return debug_prune_refine45_read(ctx, ctx->kmer_fourth, blocks, n, out);
-}
-// ... and of the fifth level's second table
-extern "C" int swg_debug_prune_refine5_read(swg_ctx *ctx, const uint32_t *blocks, size_t n, uint16_t *out)
-{
-    if (!ctx || (n > 0 && (!blocks || !out))) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_refine5_read: NULL argument");
-    return debug_prune_refine45_read(ctx, ctx->kmer_fifth, blocks, n, out);
-}
-static int debug_prune_refine45_read(swg_ctx *ctx, const SwgKmerTable &t, const uint32_t *blocks, size_t n, uint16_t *out)
-{
+    if (!ctx || (n > 0 && (!blocks || !out))) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_debug_prune_refine%d_read: NULL argument", level);
+    const SwgKmerTable &t = ctx->kmer_refine[level - 2];
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipDeviceSynchronize());
     if (!t.holds(ctx->epoch, 5, (int)SWG_KMER_REFINE4_SEGMENTS, 8))
@@ -3174,6 +3155,8 @@ static int debug_prune_refine45_read(swg_ctx *ctx, const SwgKmerTable &t, const 
     }
     return SWG_OK;
 }
+extern "C" int swg_debug_prune_refine4_read(swg_ctx *ctx, const uint32_t *blocks, size_t n, uint16_t *out) { return debug_prune_level_rows(ctx, 4, blocks, n, out); }
+extern "C" int swg_debug_prune_refine5_read(swg_ctx *ctx, const uint32_t *blocks, size_t n, uint16_t *out) { return debug_prune_level_rows(ctx, 5, blocks, n, out); }
 
 extern "C" int swg_prune_last(const swg_ctx *ctx, swg_prune_info *out)
 {

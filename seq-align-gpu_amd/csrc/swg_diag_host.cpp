@@ -696,11 +696,9 @@ std::vector<SwgPruneStage> swg_prune_stages(const SwgPrunePlan &plan, const std:
         if (plan.gate && si == (plan.fixed ? 0u : 1u)) q |= SWG_STAGE_BOUND; // (the first stage with a threshold)
         if (plan.prefix_cut) q |= SWG_STAGE_PREFIX_CUT;
         else {
-            if (plan.refine && plan.fixed && si == 0 && stages.size() > 1) q |= SWG_STAGE_GATE;
-            if (plan.refine) q |= SWG_STAGE_REFINE;
-            if (plan.refine3) q |= SWG_STAGE_REFINE3;
-            if (plan.refine4) q |= SWG_STAGE_REFINE4;
-            if (plan.refine5) q |= SWG_STAGE_REFINE5;
+            if (plan.refine[0] && plan.fixed && si == 0 && stages.size() > 1) q |= SWG_STAGE_GATE;
+            for (int i = 0; i < SWG_REFINE_LEVELS; ++i)
+                if (plan.refine[i]) q |= SWG_REFINE_LEVEL[i].stage_bit;
             q |= SWG_STAGE_LIST;
         }
         stages[si].queued = q;
@@ -722,11 +720,10 @@ static int debug_prune_stages(const int64_t *in, int head, int64_t *out, size_t 
     if (!in || !n_out || (cap > 0 && !out) || in[0] < 0 || in[head - 1] < 0) return SWG_ERR_ARG;
     SwgPrunePlan plan;
     plan.on = true;
-    plan.head_pairs = (uint32_t)in[0], plan.fixed = in[1] != 0, plan.refine = (int)in[2], plan.prefix_cut = in[3] != 0;
-    plan.refine3 = head >= 6 ? (int)in[4] : 0;
-    plan.refine4 = head >= 7 ? (int)in[5] : 0;
-    plan.gate = head >= 8 && in[6] != 0;
-    plan.refine5 = head >= 9 ? (int)in[7] : 0;
+    plan.head_pairs = (uint32_t)in[0], plan.fixed = in[1] != 0, plan.prefix_cut = in[3] != 0;
+    plan.gate = head > 7 && in[6] != 0;
+    static const int level_word[SWG_REFINE_LEVELS] = {2, 4, 5, 7}; // (a level's word, where the head reaches past it: the last word is n)
+    for (int i = 0; i < SWG_REFINE_LEVELS; ++i) plan.refine[i] = head > level_word[i] + 1 ? (int)in[level_word[i]] : 0;
     std::vector<std::pair<uint32_t, uint32_t>> segments;
     for (int64_t i = 0; i < in[head - 1]; ++i) segments.emplace_back((uint32_t)in[head + 2 * i], (uint32_t)in[head + 1 + 2 * i]);
     const std::vector<SwgPruneStage> stages = swg_prune_stages(plan, segments);
@@ -910,7 +907,7 @@ extern "C" int swg_debug_prune_kmer_refine3(const int8_t *rows, const int8_t *id
 // that blocks behind one prefix share its rows the way the table's build shares them.
 #define SWG_REFINE4_BATCH 32768u
 // (the first sequence of each batch, and n)
-static std::vector<size_t> refine4_batches(const uint64_t *offsets, size_t n)
+static std::vector<size_t> blocks5_batches(const uint64_t *offsets, size_t n)
 {
     std::vector<size_t> batch{0};
     for (size_t i = 0, blocks = 0; i < n; ++i) {
@@ -922,7 +919,7 @@ static std::vector<size_t> refine4_batches(const uint64_t *offsets, size_t n)
     return batch;
 }
 // (the blocks of 5 the sequences [first, last) hold, sorted, each once)
-static std::vector<uint32_t> refine4_held(const SwgColMax &cm, const int8_t *flat, const uint64_t *offsets, size_t first, size_t last)
+static std::vector<uint32_t> blocks5_held(const SwgColMax &cm, const int8_t *flat, const uint64_t *offsets, size_t first, size_t last)
 {
     std::vector<uint32_t> held;
     for (size_t i = first; i < last; ++i)
@@ -933,7 +930,7 @@ static std::vector<uint32_t> refine4_held(const SwgColMax &cm, const int8_t *fla
 }
 // (their S entries each, by the row recurrence `row`: kmer_row, or kmer_row2 of the fifth level)
 template <class Row>
-static std::vector<uint16_t> refine4_entries(Row row, const std::vector<uint32_t> &held, const int8_t *cprof, size_t lq, int g, int e, size_t S)
+static std::vector<uint16_t> blocks5_entries(Row row, const std::vector<uint32_t> &held, const int8_t *cprof, size_t lq, int g, int e, size_t S)
 {
     const uint32_t C = SWG_KMER_CLASSES;
     std::vector<uint16_t> entries(held.size() * S);
@@ -963,11 +960,11 @@ extern "C" int swg_debug_prune_kmer_refine4(const int8_t *rows, const int8_t *id
     swg_kmer_cprof(rows, idx, lq, cprof.data());
     const SwgColMax cm = swg_prune_colmax(rows, idx, lq);
     const int g = std::min(-(gap_open + gap_extend), 65536), e = std::min(-gap_extend, 65536);
-    const std::vector<size_t> batch = refine4_batches(offsets, n);
+    const std::vector<size_t> batch = blocks5_batches(offsets, n);
 #pragma omp parallel for schedule(dynamic, 1)
     for (long bi = 0; bi < (long)batch.size() - 1; ++bi) {
-        const std::vector<uint32_t> held = refine4_held(cm, flat, offsets, batch[bi], batch[bi + 1]);
-        const std::vector<uint16_t> entries = refine4_entries(kmer_row, held, cprof.data(), lq, g, e, S);
+        const std::vector<uint32_t> held = blocks5_held(cm, flat, offsets, batch[bi], batch[bi + 1]);
+        const std::vector<uint16_t> entries = blocks5_entries(kmer_row, held, cprof.data(), lq, g, e, S);
         for (size_t i = batch[bi]; i < batch[bi + 1]; ++i)
             u_out[i] = kmer_bound_walk(
                 [&](size_t ix) { return entries.data() + (size_t)(std::lower_bound(held.begin(), held.end(), (uint32_t)ix) - held.begin()) * S; }, 5, S, cm,
@@ -1053,12 +1050,12 @@ extern "C" int swg_debug_prune_kmer_refine5(const int8_t *rows, const int8_t *id
     if (!*on_out) return SWG_OK;
     std::vector<int8_t> cprof(lq * C);
     swg_kmer_cprof(rows, idx, lq, cprof.data());
-    const std::vector<size_t> batch = refine4_batches(offsets, n);
+    const std::vector<size_t> batch = blocks5_batches(offsets, n);
 #pragma omp parallel for schedule(dynamic, 1)
     for (long bi = 0; bi < (long)batch.size() - 1; ++bi) {
-        const std::vector<uint32_t> held = refine4_held(cm, flat, offsets, batch[bi], batch[bi + 1]);
-        const std::vector<uint16_t> t = refine4_entries(kmer_row, held, cprof.data(), lq, g, e, S);
-        const std::vector<uint16_t> t2 = refine4_entries(kmer_row2, held, cprof.data(), lq, g, e, S);
+        const std::vector<uint32_t> held = blocks5_held(cm, flat, offsets, batch[bi], batch[bi + 1]);
+        const std::vector<uint16_t> t = blocks5_entries(kmer_row, held, cprof.data(), lq, g, e, S);
+        const std::vector<uint16_t> t2 = blocks5_entries(kmer_row2, held, cprof.data(), lq, g, e, S);
         for (size_t i = batch[bi]; i < batch[bi + 1]; ++i)
             u_out[i] = kmer_bound_walk5(t.data(), t2.data(), held, S, W, e, n_explicit ? (size_t)n_explicit : (size_t)SWG_REFINE5_EXPLICIT, cm,
                                         flat + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
@@ -1130,12 +1127,12 @@ static bool debug_kmer_ask(const int64_t *in, int64_t *out, int n_in, SwgKmerAsk
     if (!in || !out) return false;
     for (int i = 2; i < std::min(n_in, 7); ++i)
         if (in[i] < 0) return false;
-    if (n_in > 7 && !swg_prune_refine_value_ok((long)in[7])) return false;
+    if (n_in > 7 && !swg_refine_value_ok(0, (long)in[7])) return false;
     a->forced = (long)in[0], a->pruned = in[1] != 0, a->lq = (size_t)in[2], a->pair_rows = (uint64_t)in[3];
     a->table_rate = in[4] ? (double)in[4] : SWG_KMER_TABLE_RATE;
     a->fill_rate = in[5] ? (double)in[5] : swg_kmer_fill_rate(a->lq);
     a->forced_segments = n_in > 6 ? (long)in[6] : 1;
-    a->forced_refine = n_in > 7 ? (long)in[7] : 0;
+    a->forced_refine[0] = n_in > 7 ? (long)in[7] : 0;
     return true;
 }
 // test hook: out[0] = k.  Like swg_debug_prune_kmer and swg_debug_prune_kmer_read it keeps its unsegmented meaning: the k
@@ -1161,71 +1158,67 @@ extern "C" int swg_debug_prune_kmer_choice_seg(const int64_t *in, int64_t *out)
     return SWG_OK;
 }
 
-// The second level.  Automatic only behind an automatic first level that took a segmented k = 4 candidate (a forced
-// "prune_kmer" or "prune_segments" leaves d_pair_bound the mirror of exactly that bound); forced, behind any.  The
-// candidates in the style of SWG_KMER_CANDIDATES: what the headline keeps at (4, 32) cut pair by pair less what it keeps
-// with the second level, and the seconds per pair row of the range the refine kernel takes (it walks the pairs of the
-// cut stages whose first bound reaches T); the table is 22^4 * 4 * lq cells like the first.  A step up must cost at most
-// half of what it saves.  Constants: profiles/prune_refine_ab.txt -- rows kept 0.2677 / 0.2443 / 0.2249 (section 2); the
-// refine kernel at 128 segments 4.11 ms per search over 1 938 193 684 pair rows (section 3), which 64 segments, not traced
-// singly and half the bytes, is charged too.
-struct SwgRefineCandidate {
-    int S2;
-    double gain, bound_row;
-};
-static const SwgRefineCandidate SWG_REFINE_CANDIDATES[] = {{0, 0.0, 0.0}, {64, 0.0234, 2.1e-12}, {128, 0.0428, 2.1e-12}};
-int swg_prune_refine_choice(const SwgKmerAsk &a, int k, int S)
+// The automatic rule of a level behind the first, in the style of SWG_KMER_CANDIDATES: over the level's candidates (the
+// segments its option can force, in the order of what they save: SWG_REFINE_LEVEL has the shares, the seconds and where
+// they were measured), what a candidate costs -- its table, swg_kmer_table_cells(k) * lq cells at table_rate cells per
+// second like a first-level table of that k, and its walk's seconds per pair row of the range (it walks the pairs of the
+// cut stages whose earlier bounds reach T) -- against what its tighter cut saves: the share of the range's pair rows it
+// takes off the fill at fill_rate pair rows per second.  A step up must cost at most half of what it saves.  -> the
+// segments of the candidate the range pays for, or 0: none.
+static int refine_level_pays(const SwgKmerAsk &a, const SwgRefineLevel &L)
 {
-    if (!a.pruned || k < 1) return 0;
-    if (a.forced_refine == 64 || a.forced_refine == 128) return (int)a.forced_refine;
-    if (a.forced_refine != 0 || a.forced != 0 || a.forced_segments != 0 || k != 4 || S <= 1) return 0;
     if (a.table_rate <= 0 || a.fill_rate <= 0 || a.lq == 0) return 0;
-    auto cost = [&](const SwgRefineCandidate &c) {
-        return c.S2 == 0 ? 0.0 : (double)swg_kmer_entries(4) * 4 * (double)a.lq / a.table_rate + c.bound_row * (double)a.pair_rows;
-    };
-    auto gain = [&](const SwgRefineCandidate &c) { return c.gain * (double)a.pair_rows / a.fill_rate; };
-    const SwgRefineCandidate *cur = &SWG_REFINE_CANDIDATES[0];
-    for (const SwgRefineCandidate &c : SWG_REFINE_CANDIDATES)
-        if (c.gain > cur->gain && cost(c) - cost(*cur) <= 0.5 * (gain(c) - gain(*cur))) cur = &c;
-    return cur->S2;
-}
-
-// test hook: ... and with the forced refinement: out[0..2] = k, S, S2 (0: no second level)
-extern "C" int swg_debug_prune_refine_choice(const int64_t *in, int64_t *out)
-{
-    SwgKmerAsk a;
-    if (!debug_kmer_ask(in, out, 8, &a)) return SWG_ERR_ARG;
+    const double cost = swg_kmer_table_cells(L.k) * (double)a.lq / a.table_rate + L.bound_row * (double)a.pair_rows;
     int S = 0;
-    out[0] = swg_prune_kmer_choice(a, &S);
-    out[1] = S;
-    out[2] = swg_prune_refine_choice(a, (int)out[0], S);
-    return SWG_OK;
+    double cur_share = 0.0, cur_cost = 0.0, cur_gain = 0.0;
+    for (const SwgRefineLevel::Forced &c : L.forced) {
+        const double gain = c.gain * (double)a.pair_rows / a.fill_rate;
+        if (c.gain > cur_share && cost - cur_cost <= 0.5 * (gain - cur_gain)) S = c.segments, cur_share = c.gain, cur_cost = cost, cur_gain = gain;
+    }
+    return S;
 }
 
-// The third level: 256 segments behind the second level's walk.  Forced ("prune_refine3" = 256), behind whatever the
-// second level is; off ("prune_refine3" = 1); automatic only where the second level was chosen automatically and took
-// 128 -- so under no forced "prune_kmer", "prune_segments" or "prune_refine" --, the tables are byte-wide (the 256-segment
-// table is then the 60 MB the 128-segment one is as uint16_t, and a lane's 8 entries one 8-byte load) and the candidate
-// rule of the other levels holds: the table's build and the walk cost at most half of what the tighter cut saves.  The
-// Constants: profiles/prune_bytes_ab.txt -- rows kept 0.2249 at 128 segments, 0.2098 at 256 (section 2); the walk at 256
-// segments over byte tables 3.37 ms per search over 1 938 193 684 pair rows (section 3).
-#define SWG_REFINE3_GAIN 0.0151
-#define SWG_REFINE3_BOUND_ROW 1.74e-12
-// the range's floor: the third level's table build and walk cost at most half of what its tighter cut saves
-static bool refine3_pays(const SwgKmerAsk &a)
+// The chain, in level order.  Whoever asks, a level whose table holds blocks of 5 needs that table as bytes (16-bit
+// entries are refused at this size: swg_kmer_refine4_admitted), and the fifth e > 0 and second entries that are bytes
+// (a.refine5_ok).  Forced by its option a level is taken behind whatever the other levels are; "off" is off.  Automatic
+// only where no level or first-level option in front of it was forced (a forced "prune_kmer" or "prune_segments" leaves
+// d_pair_bound the mirror of exactly that bound; every forced earlier level stays without the later ones), behind a
+// predecessor that took what the level was measured behind, and where refine_level_pays.
+void swg_prune_refine_choices(const SwgKmerAsk &a, int k, int S, int out[SWG_REFINE_LEVELS])
 {
-    if (a.table_rate <= 0 || a.fill_rate <= 0 || a.lq == 0) return false;
-    const double cost = (double)swg_kmer_entries(4) * 4 * (double)a.lq / a.table_rate + SWG_REFINE3_BOUND_ROW * (double)a.pair_rows;
-    const double gain = SWG_REFINE3_GAIN * (double)a.pair_rows / a.fill_rate;
-    return cost <= 0.5 * gain;
-}
-int swg_prune_refine3_choice(const SwgKmerAsk &a, int k, int S, int S2)
-{
-    if (!a.pruned || k < 1) return 0;
-    if (a.forced_refine3 == 256) return 256;
-    if (a.forced_refine3 != 0 || a.forced != 0 || a.forced_segments != 0 || a.forced_refine != 0) return 0;
-    if (k != 4 || S <= 1 || S2 != 128 || a.table_bits != 8) return 0;
-    return refine3_pays(a) ? 256 : 0;
+    std::fill(out, out + SWG_REFINE_LEVELS, 0);
+    if (!a.pruned || k < 1) return;
+    for (int i = 0; i < SWG_REFINE_LEVELS; ++i) {
+        const SwgRefineLevel &L = SWG_REFINE_LEVEL[i];
+        if (L.k == 5 && !swg_kmer_refine4_admitted(a.table_bits5)) continue;
+        if (i == 3 && !a.refine5_ok) continue;
+        if (a.forced_refine[i] != 0) {
+            out[i] = swg_refine_forced_segments(i, a.forced_refine[i]); // (0 for "off")
+            continue;
+        }
+        bool forced_in_front = a.forced != 0 || a.forced_segments != 0;
+        for (int j = 0; j < i; ++j) forced_in_front = forced_in_front || a.forced_refine[j] != 0;
+        if (forced_in_front) continue;
+        bool behind = false;
+        switch (i) {
+        case 0: // the second level: an automatic first level that took a segmented k = 4 candidate
+            behind = k == 4 && S > 1;
+            break;
+        case 1: // the third: the second took 128, and the k = 4 tables are byte-wide (the 256-segment table is then the 60 MB
+                // the 128-segment one is as uint16_t, and a lane's 8 entries one 8-byte load)
+            behind = out[0] == 128 && a.table_bits == 8;
+            break;
+        case 2: // the fourth: the third took 256 (so the tables of k = 4 are bytes, as those of k = 5 are)
+            behind = out[1] == 256;
+            break;
+        case 3: // the fifth: the fourth was taken, and the threshold is the K-th best so far -- under a caller's what the level
+                // saves depends on where T lies among the bounds (profiles/prune_adjacent_ab.txt, section 4: 23.6 ms saved at
+                // the score of the 100th hit, 3.3 ms lost at twice that), so there it runs only where it is forced
+            behind = out[2] != 0 && !a.fixed;
+            break;
+        }
+        if (behind) out[i] = refine_level_pays(a, L);
+    }
 }
 
 // The gate in front of the first level (swg_host_internal.h has the rule in words).  Nothing smaller than the headline
@@ -1236,7 +1229,7 @@ bool swg_prune_gate_choice(const SwgKmerAsk &a, int k, int S)
     if (!a.pruned || k <= 1 || S <= 1 || a.forced_gate == 1) return false;
     if (a.forced_gate == 2) return true;
     if (a.forced != 0 || a.forced_segments != 0) return false;
-    return refine3_pays(a);
+    return refine_level_pays(a, SWG_REFINE_LEVEL[1]) != 0;
 }
 
 extern "C" int swg_debug_prune_gate_choice(const int64_t *in, int64_t *out)
@@ -1252,93 +1245,44 @@ extern "C" int swg_debug_prune_gate_choice(const int64_t *in, int64_t *out)
     return SWG_OK;
 }
 
-extern "C" int swg_debug_prune_refine3_choice(const int64_t *in, int64_t *out)
+// test hooks: the chain up to its n_levels-th level (swg_host_internal.h has the words of in): in[0..7] the first level's
+// question and option "prune_refine"; then, where the hook has them, in[8] "prune_refine3" and in[9] the width of the k = 4
+// tables' entries (0: bytes); in[10] "prune_refine4" and in[11] the width of the k = 5 tables'; in[12] "prune_refine5",
+// in[13] whether the query and scoring admit the fifth level, in[14] whether the threshold is a caller's
+// -> out[0..1 + n_levels] = k, S, then the segments of the levels
+static int debug_prune_refine_choices(const int64_t *in, int n_levels, int64_t *out)
 {
     SwgKmerAsk a;
     if (!debug_kmer_ask(in, out, 8, &a)) return SWG_ERR_ARG;
-    if (!swg_prune_refine3_value_ok((long)in[8]) || (in[9] != 0 && in[9] != 8 && in[9] != 16)) return SWG_ERR_ARG;
-    a.forced_refine3 = (long)in[8];
-    a.table_bits = in[9] == 16 ? 16 : 8;
-    int S = 0;
+    static const int option_word[SWG_REFINE_LEVELS] = {7, 8, 10, 12};
+    auto width_ok = [](int64_t w) { return w == 0 || w == 8 || w == 16; };
+    for (int i = 1; i < n_levels; ++i) {
+        if (!swg_refine_value_ok(i, (long)in[option_word[i]])) return SWG_ERR_ARG;
+        a.forced_refine[i] = (long)in[option_word[i]];
+    }
+    if (n_levels >= 2) {
+        if (!width_ok(in[9])) return SWG_ERR_ARG;
+        a.table_bits = in[9] == 16 ? 16 : 8;
+    }
+    if (n_levels >= 3) {
+        if (!width_ok(in[11])) return SWG_ERR_ARG;
+        a.table_bits5 = in[11] == 16 ? 16 : 8;
+    }
+    if (n_levels >= 4) {
+        if ((in[13] != 0 && in[13] != 1) || (in[14] != 0 && in[14] != 1)) return SWG_ERR_ARG;
+        a.refine5_ok = in[13] != 0, a.fixed = in[14] != 0;
+    }
+    int S = 0, levels[SWG_REFINE_LEVELS];
     out[0] = swg_prune_kmer_choice(a, &S);
     out[1] = S;
-    out[2] = swg_prune_refine_choice(a, (int)out[0], S);
-    out[3] = swg_prune_refine3_choice(a, (int)out[0], S, (int)out[2]);
+    swg_prune_refine_choices(a, (int)out[0], S, levels);
+    std::copy(levels, levels + n_levels, out + 2);
     return SWG_OK;
 }
-
-// The fourth level: blocks of 5 residues over 256 segments behind the third level's walk -- the table is 22^5 x 256 bytes,
-// walked only by the pairs the third level leaves at or above T.  Forced ("prune_refine4" = 5256), behind whatever the
-// other levels are; off ("prune_refine4" = 1); automatic only where the third level was itself chosen automatically and
-// took 256 -- so under no forced earlier level --, the tables of k = 4 and of k = 5 are byte-wide, and the candidate rule of
-// the other levels holds.  The build is the prefix-shared kernel's: 22^4 x (4 + 22) x lq cells.  A table of 16-bit entries
-// is refused at this size whoever asks (swg_kmer_refine4_admitted): the level is then off.
-// Constants: profiles/prune_deep_ab.txt -- SWG_REFINE4_GAIN the rows kept behind the third level less those behind the
-// fourth, SWG_REFINE4_BOUND_ROW the fourth walk per pair row of the range.
-#define SWG_REFINE4_GAIN 0.0374
-#define SWG_REFINE4_BOUND_ROW 1.31e-12
-int swg_prune_refine4_choice(const SwgKmerAsk &a, int k, int S, int S2, int S3)
-{
-    if (!a.pruned || k < 1 || !swg_kmer_refine4_admitted(a.table_bits5)) return 0;
-    if (a.forced_refine4 == SWG_REFINE4_FORCED) return (int)SWG_KMER_REFINE4_SEGMENTS;
-    if (a.forced_refine4 != 0 || a.forced != 0 || a.forced_segments != 0 || a.forced_refine != 0 || a.forced_refine3 != 0) return 0;
-    if (k != 4 || S <= 1 || S2 != 128 || S3 != 256 || a.table_bits != 8) return 0;
-    if (a.table_rate <= 0 || a.fill_rate <= 0 || a.lq == 0) return 0;
-    const double cost = swg_kmer_table_cells(5) * (double)a.lq / a.table_rate + SWG_REFINE4_BOUND_ROW * (double)a.pair_rows;
-    const double gain = SWG_REFINE4_GAIN * (double)a.pair_rows / a.fill_rate;
-    return cost <= 0.5 * gain ? (int)SWG_KMER_REFINE4_SEGMENTS : 0;
-}
-
-// The fifth level: the fourth level's walk once more over both k = 5 tables, the query columns jumped over between two
-// blocks charged ("a fifth level"); walked only by the pairs the fourth level leaves at or above T.  Forced
-// ("prune_refine5" = 5256), behind whatever the other levels are; off ("prune_refine5" = 1); automatic only where the fourth
-// level was itself chosen automatically (so every forced earlier level stays without it) and the threshold is not a
-// caller's (a.fixed), under the rule of the other levels: the second table's build and the walk may cost at most half of what the cut saves.  Whoever asks, the level
-// needs both tables as bytes and e > 0 (a.table_bits5, a.refine5_ok).
-// Constants: profiles/prune_adjacent_ab.txt -- SWG_REFINE5_GAIN the rows kept behind the fourth level less those behind the
-// fifth (the host model, section 0), SWG_REFINE5_BOUND_ROW the fifth walk per pair row of the range.
-#define SWG_REFINE5_GAIN 0.0254
-#define SWG_REFINE5_BOUND_ROW 4.0e-12
-int swg_prune_refine5_choice(const SwgKmerAsk &a, int k, int S4)
-{
-    if (!a.pruned || k < 1 || !a.refine5_ok || !swg_kmer_refine4_admitted(a.table_bits5)) return 0;
-    if (a.forced_refine5 == SWG_REFINE5_FORCED) return (int)SWG_KMER_REFINE4_SEGMENTS;
-    if (a.forced_refine5 != 0 || a.forced_refine4 != 0 || S4 == 0 || a.fixed) return 0;
-    if (a.table_rate <= 0 || a.fill_rate <= 0 || a.lq == 0) return 0;
-    const double cost = swg_kmer_table_cells(5) * (double)a.lq / a.table_rate + SWG_REFINE5_BOUND_ROW * (double)a.pair_rows;
-    const double gain = SWG_REFINE5_GAIN * (double)a.pair_rows / a.fill_rate;
-    return cost <= 0.5 * gain ? (int)SWG_KMER_REFINE4_SEGMENTS : 0;
-}
-
-extern "C" int swg_debug_prune_refine4_choice(const int64_t *in, int64_t *out)
-{
-    SwgKmerAsk a;
-    if (!debug_kmer_ask(in, out, 8, &a)) return SWG_ERR_ARG;
-    if (!swg_prune_refine3_value_ok((long)in[8]) || (in[9] != 0 && in[9] != 8 && in[9] != 16)) return SWG_ERR_ARG;
-    if (!swg_prune_refine4_value_ok((long)in[10]) || (in[11] != 0 && in[11] != 8 && in[11] != 16)) return SWG_ERR_ARG;
-    a.forced_refine3 = (long)in[8], a.forced_refine4 = (long)in[10];
-    a.table_bits = in[9] == 16 ? 16 : 8, a.table_bits5 = in[11] == 16 ? 16 : 8;
-    int S = 0;
-    out[0] = swg_prune_kmer_choice(a, &S);
-    out[1] = S;
-    out[2] = swg_prune_refine_choice(a, (int)out[0], S);
-    out[3] = swg_prune_refine3_choice(a, (int)out[0], S, (int)out[2]);
-    out[4] = swg_prune_refine4_choice(a, (int)out[0], S, (int)out[2], (int)out[3]);
-    return SWG_OK;
-}
-
-extern "C" int swg_debug_prune_refine5_choice(const int64_t *in, int64_t *out)
-{
-    SwgKmerAsk a;
-    if (!debug_kmer_ask(in, out, 8, &a)) return SWG_ERR_ARG;
-    if (!swg_prune_refine5_value_ok((long)in[12]) || (in[13] != 0 && in[13] != 1) || (in[14] != 0 && in[14] != 1)) return SWG_ERR_ARG;
-    const int rc = swg_debug_prune_refine4_choice(in, out);
-    if (rc != SWG_OK) return rc;
-    a.forced_refine3 = (long)in[8], a.forced_refine4 = (long)in[10], a.forced_refine5 = (long)in[12];
-    a.table_bits = in[9] == 16 ? 16 : 8, a.table_bits5 = in[11] == 16 ? 16 : 8, a.refine5_ok = in[13] != 0, a.fixed = in[14] != 0;
-    out[5] = swg_prune_refine5_choice(a, (int)out[0], (int)out[4]);
-    return SWG_OK;
-}
+extern "C" int swg_debug_prune_refine_choice(const int64_t *in, int64_t *out) { return debug_prune_refine_choices(in, 1, out); }
+extern "C" int swg_debug_prune_refine3_choice(const int64_t *in, int64_t *out) { return debug_prune_refine_choices(in, 2, out); }
+extern "C" int swg_debug_prune_refine4_choice(const int64_t *in, int64_t *out) { return debug_prune_refine_choices(in, 3, out); }
+extern "C" int swg_debug_prune_refine5_choice(const int64_t *in, int64_t *out) { return debug_prune_refine_choices(in, 4, out); }
 
 // Both 16-bit forms in one search (plan_search in swg_api.cpp): the length from which a sequence can reach the f16 cells' ceiling
 // as an exact copy of a stretch of the query -- such a copy scores qbound / lq per row on average, qbound being the

@@ -266,15 +266,69 @@ struct SwgPruneAsk {
     // want_scores, n_segments and prune_head decide nothing
     bool fixed = false;
 };
+// What a stage of a pruned fill queues in front of its fill launches (swg_prune_stages below has the rules in words).
+enum : uint32_t {
+    SWG_STAGE_THRESHOLD = 1u, SWG_STAGE_PREFIX_CUT = 2u, SWG_STAGE_GATE = 4u, SWG_STAGE_REFINE = 8u, SWG_STAGE_LIST = 16u, SWG_STAGE_REFINE3 = 32u,
+    SWG_STAGE_REFINE4 = 64u, SWG_STAGE_BOUND = 128u, SWG_STAGE_REFINE5 = 256u
+};
+// The refinement levels behind the first, the second to the fifth: one row each, [level - 2], in the order
+// their walks are queued.  Everything on the host that touches a level walks this table -- the options (swg_set_option),
+// the choice (swg_prune_refine_choices), the stage list (swg_prune_stages), the tables (prepare_prune, reserve_refine_table,
+// swg_destroy), the launches (enqueue_pruned_fill) and the test hooks.  A further level is a row here, its launch
+// (launch_refine_level, swg_api.cpp) and the few lines of its own in swg_prune_refine_choices.
+// A level's walk takes the pairs the levels in front of it left at or above the threshold word and keeps the lesser bound.
+#define SWG_REFINE_LEVELS 4
+struct SwgRefineLevel {
+    const char *option;       // its option: 0 automatic, 1 off, or one of `forced`
+    const char *option_error; // ... and what swg_set_option says to any other value
+    const char *table_error;  // what prepare_prune says to segments or a width the level does not walk (%d: the segments)
+    // the option values that force the level, the segments each stands for, and what the automatic rule books for it: the
+    // share of the headline's rows kept behind the level in front less that kept behind this one (value 0: no such entry)
+    struct Forced {
+        long value;
+        int segments;
+        double gain;
+    } forced[2];
+    uint32_t stage_bit; // SWG_STAGE_*: a stage that queues the level's walk
+    int k;              // its table (swg_ctx::kmer_refine[level - 2]): blocks of k residues in the level's segments,
+    bool spans;         // ... of the second entries, built with the spans credited (swg_kmer_table5_kernel<E, true>)
+    int reads;          // the row of another level whose table its walk reads as well (-1: none)
+    bool reserved;      // the table is a buffer of fixed size reserved in front of the search, whose allocation may be refused (reserve_refine_table)
+    double bound_row;   // the automatic rule: seconds of its walk per pair row of the range; its table costs swg_kmer_table_cells(k) cells per query column
+};
+constexpr SwgRefineLevel SWG_REFINE_LEVEL[SWG_REFINE_LEVELS] = {
+    // the second: k = 4 in 64 or 128 segments.  profiles/prune_refine_ab.txt -- rows kept 0.2677 / 0.2443 / 0.2249 (section 2); the
+    // refine kernel at 128 segments 4.11 ms per search over 1 938 193 684 pair rows (section 3), which 64 segments, not traced
+    // singly and half the bytes, is charged too
+    {"prune_refine", "prune_refine must be 0 (auto), 1 (off), 64 or 128 (the segments of the second-level bound's table)",
+     "the second-level bound's table: %d segments (64 or 128)", {{64, 64, 0.0234}, {128, 128, 0.0428}}, SWG_STAGE_REFINE, 4, false, -1, false, 2.1e-12},
+    // the third: k = 4 in 256 segments of bytes.  profiles/prune_bytes_ab.txt -- rows kept 0.2249 at 128 segments, 0.2098 at 256
+    // (section 2); the walk at 256 segments over byte tables 3.37 ms per search over 1 938 193 684 pair rows (section 3)
+    {"prune_refine3", "prune_refine3 must be 0 (auto), 1 (off) or 256 (the segments of the third-level bound's table)",
+     "the third-level bound's table: %d segments (256)", {{256, 256, 0.0151}, {0, 0, 0.0}}, SWG_STAGE_REFINE3, 4, false, -1, false, 1.74e-12},
+    // the fourth: k = 5 in 256 segments of bytes, 1.32 GB; its option names (k, S) as 1000 k + S.  profiles/prune_deep_ab.txt -- the
+    // rows kept behind the third level less those behind the fourth, the fourth walk per pair row of the range
+    {"prune_refine4", "prune_refine4 must be 0 (auto), 1 (off) or 5256 (the fourth-level bound's table: k = 5 in 256 segments)",
+     "the fourth-level bound's table: %d segments (256) of bytes", {{5256, 256, 0.0374}, {0, 0, 0.0}}, SWG_STAGE_REFINE4, 5, false, -1, true, 1.31e-12},
+    // the fifth: the fourth's table and its own of the second entries.  profiles/prune_adjacent_ab.txt -- the rows kept behind the
+    // fourth level less those behind the fifth (the host model, section 0), the fifth walk per pair row of the range
+    {"prune_refine5", "prune_refine5 must be 0 (auto), 1 (off) or 5256 (the fifth-level bound: both k = 5 tables in 256 segments)",
+     "the fifth-level bound's tables: %d segments (256) of bytes", {{5256, 256, 0.0254}, {0, 0, 0.0}}, SWG_STAGE_REFINE5, 5, true, 2, true, 4.0e-12},
+};
+// the segments an option value forces on level row i (0: the value forces nothing), and whether it is a value of the option at all
+constexpr int swg_refine_forced_segments(int i, long v)
+{
+    return v != 0 && v == SWG_REFINE_LEVEL[i].forced[0].value ? SWG_REFINE_LEVEL[i].forced[0].segments
+           : v != 0 && v == SWG_REFINE_LEVEL[i].forced[1].value ? SWG_REFINE_LEVEL[i].forced[1].segments
+                                                               : 0;
+}
+constexpr bool swg_refine_value_ok(int i, long v) { return v == 0 || v == 1 || swg_refine_forced_segments(i, v) != 0; }
 struct SwgPrunePlan {
     bool on = false;
     uint32_t head_pairs = 0; // one segment: pairs of the first stage; 0: the stages are the segments
     int kmer = 0;            // the bound: 1 colmax, 4 / 5 the k-mer table of that k (swg_prune_kmer_choice); 0 while off
     int segments = 0;        // ... and the segments of that table (1: the unordered sum of swg_pair_bound_kmer_kernel)
-    int refine = 0;          // the second level's segments (swg_prune_refine_choice): 64, 128, or 0 without one
-    int refine3 = 0;         // the third level's segments (swg_prune_refine3_choice): 256, or 0 without one
-    int refine4 = 0;         // the fourth level's segments, of the k = 5 table (swg_prune_refine4_choice): 256, or 0 without one
-    int refine5 = 0;         // the fifth level's segments, of both k = 5 tables (swg_prune_refine5_choice): 256, or 0 without one
+    int refine[SWG_REFINE_LEVELS] = {}; // the segments of the levels behind the first, [level - 2] (swg_prune_refine_choices): 0 without the level
     bool prefix_cut = false; // option "prune_cut" = 1: a stage's list is the prefix up to its last pair that reaches T
     bool gate = false;       // the first level's launch is gated by T and queued with a stage (swg_prune_gate_choice)
     bool fixed = false;      // a caller's threshold: every stage, the first included, is a list launch cut at fixed_T
@@ -300,16 +354,12 @@ SwgPrunePlan swg_prune_plan(const SwgPruneAsk &a);
 // head and the rest of a lone segment whose head is shorter than it.  Every stage but the first is cut at the K-th best
 // score so far, which a threshold kernel computes in front of it; under a caller's threshold (plan.fixed) the first is
 // cut too and no threshold kernel runs.  A cut is the prefix cut (plan.prefix_cut), or pair by pair: the refine pass
-// where there is a second level (plan.refine) -- behind the gate on the first of several stages under a caller's
-// threshold --, the third level's (plan.refine3) behind it under the same threshold word, the fourth's (plan.refine4) behind
-// that, the fifth's (plan.refine5) behind the fourth's, then the list.  With the gate in front of the first level (plan.gate) the stage that first has a threshold --
+// where there is a second level (plan.refine[0]) -- behind the gate on the first of several stages under a caller's
+// threshold --, then the walk of every further level the plan has, in the order of SWG_REFINE_LEVEL and under the same
+// threshold word, then the list.  With the gate in front of the first level (plan.gate) the stage that first has a threshold --
 // the second of several, or the first under a caller's threshold -- also queues the first level's launch, behind the
 // threshold kernel and in front of everything else: gated by that threshold, over all pairs from the stage's first to the
 // range's last.  A fill whose list holds no such stage bounds every pair before its first stage, ungated.
-enum : uint32_t {
-    SWG_STAGE_THRESHOLD = 1u, SWG_STAGE_PREFIX_CUT = 2u, SWG_STAGE_GATE = 4u, SWG_STAGE_REFINE = 8u, SWG_STAGE_LIST = 16u, SWG_STAGE_REFINE3 = 32u,
-    SWG_STAGE_REFINE4 = 64u, SWG_STAGE_BOUND = 128u, SWG_STAGE_REFINE5 = 256u
-};
 struct SwgPruneStage {
     uint32_t begin, end; // pairs
     uint32_t segment;    // index into `segments`
@@ -384,10 +434,7 @@ inline double swg_kmer_fill_rate(size_t lq) { return SWG_KMER_FILL_PASS_RATE / (
 struct SwgKmerAsk {
     long forced = 0;     // option "prune_kmer": 0 automatic, 1, 4, 5
     long forced_segments = 0; // option "prune_segments": 0 automatic, 1..SWG_KMER_MAX_SEGMENTS
-    long forced_refine = 0;   // option "prune_refine": 0 automatic, 1 off, 64 or 128
-    long forced_refine3 = 0;  // option "prune_refine3": 0 automatic, 1 off, 256
-    long forced_refine4 = 0;  // option "prune_refine4": 0 automatic, 1 off, 5256 (k = 5 in 256 segments)
-    long forced_refine5 = 0;  // option "prune_refine5": 0 automatic, 1 off, 5256 (both k = 5 tables in 256 segments)
+    long forced_refine[SWG_REFINE_LEVELS] = {}; // the levels' options, [level - 2]: 0 automatic, 1 off, or a value that forces the level (SWG_REFINE_LEVEL)
     bool refine5_ok = false;  // swg_kmer_refine5_admitted for this query and scoring: e > 0 and second entries that are bytes
     bool fixed = false;       // a caller's threshold (swg_search_above): the fifth level is then forced or off
     long forced_gate = 0;     // option "prune_gate": 0 automatic, 1 off, 2 wherever the first level is a segmented k-mer bound
@@ -411,17 +458,17 @@ extern "C" int swg_debug_prune_kmer_seg(const int8_t *rows, const int8_t *idx, s
                                         const int8_t *flat, const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out);
 extern "C" int swg_debug_prune_kmer_choice(const int64_t *in, int64_t *out);
 extern "C" int swg_debug_prune_kmer_choice_seg(const int64_t *in, int64_t *out);
-// The second level: the segments S2 of the k = 4 table the pairs a first-level bound of (k, S) leaves
-// standing are walked over once more -- 64, 128, or 0 for none.
-int swg_prune_refine_choice(const SwgKmerAsk &a, int k, int S);
-inline bool swg_prune_refine_value_ok(long v) { return v == 0 || v == 1 || v == 64 || v == 128; }
+// The levels behind a first-level bound of (k, S), chosen in their order: out[level - 2] = the segments of
+// the level's walk, or 0 without it.  A level is forced by its option behind whatever the others are, or off; left
+// automatic it is taken only behind a chain of automatic choices, where its table's build and its walk cost at most half
+// of what its tighter cut saves (swg_diag_host.cpp has each level's own conditions).
+void swg_prune_refine_choices(const SwgKmerAsk &a, int k, int S, int out[SWG_REFINE_LEVELS]);
+// test hooks: the chain up to one level.  in[0..5] = forced (option "prune_kmer"), pruned, lq, pair rows, table cells per
+// second, fill pair rows per second (0, 0: the library's own rates for this lq), in[6] = option "prune_segments", in[7] =
+// option "prune_refine" -> out[0..2] = k, S, S2 (0: no second level)
 extern "C" int swg_debug_prune_refine_choice(const int64_t *in, int64_t *out);
 extern "C" int swg_debug_prune_kmer_refine(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S2, const int8_t *flat,
                                            const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out);
-// The third level: 256 segments of the k = 4 table behind the second level's walk, or 0 for none (k, S, S2: what the
-// first and second levels took).
-int swg_prune_refine3_choice(const SwgKmerAsk &a, int k, int S, int S2);
-inline bool swg_prune_refine3_value_ok(long v) { return v == 0 || v == 1 || v == 256; }
 // test hooks: in[0..7] as swg_debug_prune_refine_choice, in[8] = option "prune_refine3", in[9] = the tables' entry width
 // (0: bytes) -> out[0..3] = k, S, S2, S3; the mirror of the third level's bound (S3 = 256); and the entry width of the
 // k-mer tables of a query (rows / idx as the mirrors take them) -> 8 or 16
@@ -429,11 +476,6 @@ extern "C" int swg_debug_prune_refine3_choice(const int64_t *in, int64_t *out);
 extern "C" int swg_debug_prune_kmer_refine3(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S3, const int8_t *flat,
                                             const uint64_t *offsets, size_t n, uint16_t *table_out, uint64_t *u_out);
 extern "C" int swg_debug_prune_table_bits(const int8_t *rows, const int8_t *idx, size_t lq, int k);
-// The fourth level: the k = 5 table in 256 segments behind the third level's walk, or 0 for none (k, S, S2, S3: what the
-// levels in front of it took).  Option "prune_refine4" names (k, S) as 1000 k + S: 5256.
-#define SWG_REFINE4_FORCED 5256
-int swg_prune_refine4_choice(const SwgKmerAsk &a, int k, int S, int S2, int S3);
-inline bool swg_prune_refine4_value_ok(long v) { return v == 0 || v == 1 || v == SWG_REFINE4_FORCED; }
 // test hook: in[0..9] as swg_debug_prune_refine3_choice, in[10] = option "prune_refine4", in[11] = the k = 5 tables' entry
 // width (0: bytes) -> out[0..4] = k, S, S2, S3, S4
 extern "C" int swg_debug_prune_refine4_choice(const int64_t *in, int64_t *out);
@@ -446,15 +488,6 @@ extern "C" int swg_debug_prune_kmer_refine4(const int8_t *rows, const int8_t *id
 // (swg_kmer_refine5_admitted); n_explicit: the walk's N, 0 for SWG_REFINE5_EXPLICIT, S5 or more for the exact form.
 extern "C" int swg_debug_prune_kmer_refine5(const int8_t *rows, const int8_t *idx, size_t lq, int gap_open, int gap_extend, int S5, int n_explicit,
                                             const int8_t *flat, const uint64_t *offsets, size_t n, uint64_t *u_out, int *on_out);
-// The fifth level ("a fifth level"): the fourth level's walk over both k = 5 tables with the query columns
-// jumped over between two blocks charged, or 0 for none (S4: what the fourth level took).  Forced ("prune_refine5" = 5256),
-// behind whatever the fourth level is, wherever both tables are bytes and e > 0 (a.refine5_ok, a.table_bits5); off (1);
-// automatic only where the fourth level was itself chosen automatically and the threshold is the K-th best so far: under a
-// caller's threshold what the level saves depends on where T lies among the bounds (profiles/prune_adjacent_ab.txt, section
-// 4: 23.6 ms saved at the score of the 100th hit, 3.3 ms lost at twice that), so there it runs only where it is forced.
-#define SWG_REFINE5_FORCED 5256
-int swg_prune_refine5_choice(const SwgKmerAsk &a, int k, int S4);
-inline bool swg_prune_refine5_value_ok(long v) { return v == 0 || v == 1 || v == SWG_REFINE5_FORCED; }
 // test hook: in[0..11] as swg_debug_prune_refine4_choice, in[12] = option "prune_refine5", in[13] = whether the query and
 // scoring admit the level (swg_kmer_refine5_admitted), in[14] = whether the threshold is a caller's -> out[0..5] = k, S, S2,
 // S3, S4, S5
@@ -557,12 +590,12 @@ struct SwgKmerTable {
     int bits = 0;       // of an entry: 8 or 16 (swg_kmer_table_bits, or 16 under option "prune_table_bits")
     bool holds(uint64_t e, int k_, int S, int bits_) const { return d && epoch == e && k == k_ && segments == S && bits == bits_; }
 };
-// The bound a pruned search cuts by: k (0: not pruned), its segments S, the second level's S2, the third's S3 and the
-// fourth's S4 (0: none)
+// The bound a pruned search cuts by: k (0: not pruned), its segments S, and the segments of the levels behind it,
+// [level - 2] (0: none)
 struct SwgPruneChoice {
-    int kmer = 0, segments = 0, refine = 0, refine3 = 0, refine4 = 0;
+    int kmer = 0, segments = 0;
+    int refine[SWG_REFINE_LEVELS] = {};
     int gate = 0; // 1: the first level's launch is gated (swg_prune_gate_choice)
-    int refine5 = 0; // the fifth level's S5 (0: none)
 };
 
 // One search in flight: its timing events, host-side landing buffers and what swg_search_end
@@ -651,21 +684,16 @@ struct swg_ctx {
     // fill's stream in front of the first pruned search of an epoch that wants them (ensure_kmer_table)
     long opt_prune_kmer = 0;
     long opt_prune_segments = 0; // option "prune_segments": 0 auto, 1..32
-    long opt_prune_refine = 0;   // option "prune_refine": 0 auto, 1 off, 64, 128
-    long opt_prune_refine3 = 0;  // option "prune_refine3": 0 auto, 1 off, 256
-    long opt_prune_refine4 = 0;  // option "prune_refine4": 0 auto, 1 off, 5256
-    long opt_prune_refine5 = 0;  // option "prune_refine5": 0 auto, 1 off, 5256
-    long opt_prune_gate = 0;     // option "prune_gate": 0 auto, 1 off, 2 wherever the first level is segmented
+    long opt_prune_refine[SWG_REFINE_LEVELS] = {}; // options "prune_refine" .. "prune_refine5", [level - 2]: 0 auto, 1 off, or a forcing value (SWG_REFINE_LEVEL)
+    long opt_prune_gate = 0;    // option "prune_gate": 0 auto, 1 off, 2 wherever the first level is segmented
     long opt_prune_table_bits = 0; // option "prune_table_bits": 0 auto (bytes where they hold every entry), 16
     long opt_prune_cut = 0;      // option "prune_cut": 0 pair by pair, 1 the prefix of the length order
     int8_t *d_kmer_cprof = nullptr;
     size_t d_kmer_cprof_cap = 0;
-    SwgKmerTable kmer_first[2], kmer_second, kmer_third, kmer_fourth; // [k - 4]
-    uint64_t kmer_builds = 0, kmer_refine_builds = 0, kmer_refine3_builds = 0, kmer_refine4_builds = 0; // builds queued so far, level by level (tests)
-    bool kmer_fourth_refused = false; // the fourth table's allocation failed once: this context searches without the level
-    SwgKmerTable kmer_fifth;          // the fifth level's second entries: k = 5 in 256 segments of bytes, built with spans
-    uint64_t kmer_refine5_builds = 0;
-    bool kmer_fifth_refused = false;  // ... and the same for the fifth's
+    SwgKmerTable kmer_first[2];                     // [k - 4]
+    SwgKmerTable kmer_refine[SWG_REFINE_LEVELS];    // the table each level behind the first owns, [level - 2]
+    uint64_t kmer_builds = 0, kmer_refine_builds[SWG_REFINE_LEVELS] = {}; // builds queued so far: the first level's, and level by level (tests)
+    bool kmer_refine_refused[SWG_REFINE_LEVELS] = {}; // a reserved table's allocation failed once: this context searches without the level
     uint32_t opt_seg_blocks = SWG_DYN_SEG_BLOCKS; // token blocks per launch of the multi-pass fill (option "segment_blocks": tests)
     // device state
     int8_t *d_sub = nullptr;
@@ -749,7 +777,9 @@ extern "C" int swg_debug_list_jobs(const swg_db *db, const uint32_t *cand, const
                                    size_t cap, size_t *n_slots, uint64_t *row_pairs_out);
 // test hook: the pair-token image as the device built it, or as the host restatement builds it
 // test hook: the next visit of the named site throws std::bad_alloc (swg_api.cpp); 0 disarms.  Site 4 throws nothing: the
-// next growth of swg_search_above_multi's key pool finds no device memory, and that chunk is selected on the host
+// next growth of swg_search_above_multi's key pool finds no device memory, and that chunk is selected on the host.  Sites
+// 5 and 6 throw nothing either: the next reservation of the fourth level's table (5) or of the fifth's (6) is refused as
+// if the device had no room, and the context searches on without the level (reserve_refine_table: site 1 + level)
 extern "C" void swg_debug_fail_alloc(int site);
 extern "C" int swg_debug_plan(const swg_db *db, size_t lq, int n_cu, int32_t *out);
 // a gapless search's plan: out[0..5] = route (1 gapless cells, 0 gapped machinery), K, G, W, workgroups, passes

@@ -5,6 +5,8 @@ The device's second table must be the recurrence's entry for entry; after a sear
 bound must be the least the mirrors give, level by level, each stage's list the pairs whose bound reaches its T and
 pairs_skipped their count; the hits must be the oracle's, from a view, a shard and two searches in flight too; and with
 the option left automatic on databases of this size the level is not taken."""
+import contextlib
+
 import numpy as np
 import pytest
 
@@ -173,6 +175,64 @@ def test_one_launch_segment_under_a_callers_threshold(swg, orc, ctx, data):  # n
     _, top, _ = ctx.search(db, want_scores=False, k=10)
     assert top == orc.topk(scores, 10)
     db.close()
+
+
+@contextlib.contextmanager
+def _own_context(swg, data):  # noqa: F811
+    """A context of its own -- a refused table is refused for the rest of a context's life, and the session's holds both
+    already -- with the module's query and database and all five levels forced -> (context, database, the unpruned hits)"""
+    c = swg.Context(0)
+    db = None
+    try:
+        c.set_option("autotune", 0)
+        _set_query(c, swg, _sub(swg, "BLOSUM62"), data["q"], (GO, GE))
+        _geometry(c, data["off"])
+        db = swg.Database(data["flat"], data["off"]).upload(c)
+        c.set_option("prune", 0)
+        _, plain, _ = c.search(db, want_scores=False, k=10)
+        _force_levels(c, swg)
+        yield c, db, plain
+    finally:
+        swg.lib.swg_debug_fail_alloc(0)
+        if db is not None:
+            db.close()
+        c.close()
+
+
+def test_a_refused_fifth_table_leaves_the_fourth_level(swg, data):  # noqa: F811
+    """swg_debug_fail_alloc site 6: the reservation of the fifth level's table finds no room (simulated on the host)."""
+    with _own_context(swg, data) as (c, db, plain):
+        swg.lib.swg_debug_fail_alloc(6)
+        _, hits, _ = c.search(db, want_scores=False, k=10)
+        assert hits == plain and c.prune_last()["pruned"]
+        four, five = c.debug_prune_tables4(), c.debug_prune_tables5()
+        assert four["refine4"] == 256 and four["bits"] == 8 and not four["refused"]
+        assert five["refine5"] == 0 and five["refused"] is True and five["refine5_builds"] == 0
+
+
+def test_a_refused_fourth_table_takes_the_fifth_level_with_it(swg, data):  # noqa: F811
+    """Site 5: the fourth level's table, which the fifth reads too; and the context stays without both."""
+    with _own_context(swg, data) as (c, db, plain):
+        swg.lib.swg_debug_fail_alloc(5)
+        for _ in range(2):
+            _, hits, _ = c.search(db, want_scores=False, k=10)
+            assert hits == plain and c.prune_last()["pruned"]
+            four, five = c.debug_prune_tables4(), c.debug_prune_tables5()
+            assert four["refine4"] == 0 and four["refused"] is True and four["refine4_builds"] == 0
+            assert five["refine5"] == 0 and five["refine5_builds"] == 0
+            assert c.debug_prune_tables()["refine3"] == 256     # (the levels in front stand)
+
+
+def test_a_refusal_is_the_contexts_own(swg, data):  # noqa: F811
+    with _own_context(swg, data) as (c, db, plain):
+        swg.lib.swg_debug_fail_alloc(5)
+        c.search(db, want_scores=False, k=10)
+        assert c.debug_prune_tables4()["refused"] is True
+        with _own_context(swg, data) as (c2, db2, plain2):
+            _, hits, _ = c2.search(db2, want_scores=False, k=10)
+            four, five = c2.debug_prune_tables4(), c2.debug_prune_tables5()
+            assert hits == plain2 == plain
+            assert four["refine4"] == 256 and not four["refused"] and five["refine5"] == 256 and not five["refused"]
 
 
 def test_views_shards_searches_in_flight_and_the_automatic_choice(swg, ctx, data):  # noqa: F811
