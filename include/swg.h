@@ -676,15 +676,45 @@ int swg_align_stats_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pss
  *               a file does not name; column 0 is 0; a column with m_p = 0 takes its whole row from sub[query residue p].
  * With no hits the PSSM is sub[query residue p][a] in every entry.  Every floating sum has a fixed order and nothing is
  * added atomically in floating point: two calls give the same bytes.  The host twin is swg_pssm_from_paths
- * (include/swg_host.h). */
+ * (include/swg_host.h).
+ *
+ * Two options (swg_set_option, both default 0: the model above, byte for byte) take the simplification back and purge
+ * near-identical hits, as PSI-BLAST does; swg_pssm_build, _multi and _multi_pssm read both.
+ *   extents     row 0 has extent [0, lq); row r >= 1 of a hit of score > 0 has extent [b_r, e_r) = [q_begin, q_end) of
+ *               the path swg_align_hits* spells; a hit of score 0 and a purged row have no extent and contribute nothing
+ *               anywhere.
+ *   "pssm_purge" = T, 0 (off) or 50..100 (percent identity; 94 is PSI-BLAST's), anything else SWG_ERR_ARG.  The purge
+ *               runs before everything else, on the rows as written above.  For rows r and s, c(r, s) = the columns where
+ *               both show a residue 1..31 (gaps and empty cells do not count; membership in A plays no part), i(r, s) =
+ *               those of them where the two residues are equal.  Rows are taken in hit order, r = 1, 2, ...: row r is
+ *               purged if c(r, 0) >= 1 and i(r, 0) = c(r, 0) (a copy of the query, at any T), or if some KEPT s with
+ *               1 <= s < r has c(r, s) >= 1 and 100 i(r, s) >= T c(r, s) -- integers only; a row purged earlier purges
+ *               no later one.  A purged row is then exactly a hit of score 0: not counted in n_rows, counted in n_purged.
+ *   "pssm_blocks" = 1: per-column blocks.  For column p,
+ *     rows      R_p = the rows whose extent contains p (a row that shows a gap or a residue outside A at p included;
+ *               row 0 always);
+ *     block     [L_p, U_p), L_p = max b_r and U_p = min e_r over R_p;
+ *     counts    within the block and over the rows of R_p only: n^(p)[c][a] rows showing a in column c, k^(p)_c distinct
+ *               residues of column c, m^(p)_c = sum_a n^(p)[c][a];
+ *     weights   w^(p)_r = sum over the block's columns c where row r shows a residue x in A of 1 / (k^(p)_c n^(p)[c][x]);
+ *     diversity Nbar_p = the mean of k^(p)_c over the block's columns with m^(p)_c >= 1;
+ *     frequencies f[p][a] = (sum of w^(p)_r over the rows of R_p showing a at p) / (the same sum over the rows of R_p
+ *               showing any residue of A at p);
+ *     pseudocounts alpha_p = min(Nbar_p, m_p) - 1 with m_p as above; g, Q, v, the rounding, the clamping and the
+ *               fallback columns are unchanged; info.n_distinct = the mean of Nbar_p over the columns with m_p >= 1.
+ *               Gaps stay "empty", not a 21st letter.  Columns between two consecutive extent boundaries (a segment)
+ *               share R_p, hence the block, the weights and Nbar_p; where every row spans the query the two models
+ *               coincide.
+ *   With pssm_blocks = 0 and the purge on, the whole-query model runs on the kept rows.
+ * The host twin with the options is swg_pssm_from_paths_ex. */
 #define SWG_PSSM_PSEUDOCOUNT_DEFAULT 10.0 /* PSI-BLAST's constant */
 typedef struct swg_pssm_info {
     double lambda;       /* of (sub, freq) */
     double n_distinct;   /* Nbar; 0 when no column holds a residue of A */
-    uint32_t n_rows;     /* rows used: the query and every hit of score > 0 */
+    uint32_t n_rows;     /* rows used: the query and every hit of score > 0 that was not purged */
     uint32_t n_observed; /* columns in which some hit shows a residue of A */
     uint32_t n_clamped;  /* entries whose rounded score lay outside -128..127 */
-    uint32_t reserved;
+    uint32_t n_purged;   /* hits dropped as near-identical ("pssm_purge"); 0 when purging is off */
 } swg_pssm_info;
 
 /* swg_pssm_build: the PSSM of the context's query from hits[n_hits] (only .index is read, as swg_align_hits reads them).
@@ -698,7 +728,12 @@ typedef struct swg_pssm_info {
  * The alignments' paths stay on the device: swg_pssm_rows_kernel turns them into the rows, three more kernels count,
  * weight and score (csrc/swg_pssm.hip); only the outputs come back.  The rows of a launch group take sum rows x lq bytes
  * of device memory; option "pssm_msa_mb" (default 1024; 0 .. 65536, 0: every query alone) bounds them -- a batch over the bound runs
- * in chunks of queries, a single query over it alone --, with the same bytes out.  The database must be resident; a view is
+ * in chunks of queries, a single query over it alone --, with the same bytes out.  With "pssm_purge" on, one kernel
+ * compares every pair of a query's rows and a second resolves the greedy order; with "pssm_blocks" = 1 the segments are
+ * listed on the device and one workgroup per (query, segment) counts, weights and scores in place of the three kernels.
+ * What they keep in device memory counts against the same bound: the purge's bits, (rows + 1) x ceil(rows / 64) x 8 bytes
+ * per query, and, for a query of more than 1024 rows, the weights of the rows beyond the 1024 a workgroup holds in LDS,
+ * min(lq, 2 rows) x (rows - 1024) x 8 bytes.  The database must be resident; a view is
  * accepted.  Errors, all before anything is launched: those of swg_align_hits_multi (a hit not in the shard, a pair
  * outside what a traceback holds, NULL arguments, ...), pssm_out NULL with a query to build, a malformed freq, a
  * pseudocount that is not finite and positive, a matrix without a lambda: SWG_ERR_ARG. */

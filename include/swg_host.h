@@ -156,6 +156,14 @@ int swg_matrix_lambda(const int8_t sub[32][32], const double *freq, double *lamb
 int swg_pssm_from_paths(const int8_t sub[32][32], const double *freq, double pseudocount, const int8_t *query, size_t lq,
                         const int8_t *flat, const uint64_t *offsets, const swg_alignment *al, const char *ops,
                         size_t ops_stride, size_t n_hits, int8_t *pssm_out, double *values_out, swg_pssm_info *info);
+/* The same with the two options of swg_pssm_build (include/swg.h, "per-column blocks" and "purge"): blocks 0 or 1 as
+ * option "pssm_blocks", purge 0 or 50..100 as option "pssm_purge"; any other value is SWG_ERR_ARG.  swg_pssm_from_paths
+ * is this routine called with 0, 0.  Under blocks = 1 the segments (runs of columns between two consecutive extent
+ * boundaries) are taken in ascending order, a block's columns and its member rows likewise. */
+int swg_pssm_from_paths_ex(const int8_t sub[32][32], const double *freq, double pseudocount, const int8_t *query, size_t lq,
+                           const int8_t *flat, const uint64_t *offsets, const swg_alignment *al, const char *ops,
+                           size_t ops_stride, size_t n_hits, int blocks, int purge, int8_t *pssm_out, double *values_out,
+                           swg_pssm_info *info);
 /* Writes the ASCII layout swg_pssm_load reads: a header of the 20 standard amino acids (A R N D C Q E G H I L K M F P S
  * T W Y V), then `pos letter s1 .. s20` per query position and a blank line.  The other residue codes are not written:
  * swg_pssm_load rebuilds them from the matrix, as swg_pssm_build filled them, so loading the file with the same

@@ -50,7 +50,7 @@ ABI_SYMBOLS = [
     "swg_synth_free", "swg_host_threads", "swg_pssm_load", "swg_pssm_free",
     "swg_db_composition", "swg_calibrate", "swg_calibrate_multi", "swg_calibrate_multi_pssm", "swg_evalue", "swg_bitscore",
     "swg_evalue_min_score", "swg_synth_db_iid", "swg_gumbel_fit_hist",
-    "swg_matrix_lambda", "swg_pssm_from_paths", "swg_pssm_save", "swg_pssm_build", "swg_pssm_build_multi", "swg_pssm_build_multi_pssm",
+    "swg_matrix_lambda", "swg_pssm_from_paths", "swg_pssm_from_paths_ex", "swg_pssm_save", "swg_pssm_build", "swg_pssm_build_multi", "swg_pssm_build_multi_pssm",
     "swg_mask_params_default", "swg_mask_tables", "swg_seg_mask", "swg_seg_mask_segments", "swg_db_sequence", "swg_db_mask",
     "swg_db_mask_info", "swg_seg_mask_flat",
 ]
@@ -99,11 +99,11 @@ class EvalueParams(C.Structure):
 class PssmInfo(C.Structure):
     """swg_pssm_info: what a PSSM construction reports per query."""
     _fields_ = [("lambda_", C.c_double), ("n_distinct", C.c_double), ("n_rows", C.c_uint32), ("n_observed", C.c_uint32),
-                ("n_clamped", C.c_uint32), ("reserved", C.c_uint32)]
+                ("n_clamped", C.c_uint32), ("n_purged", C.c_uint32)]
 
     def as_dict(self):
         return {"lambda": self.lambda_, "n_distinct": self.n_distinct, "n_rows": self.n_rows, "n_observed": self.n_observed,
-                "n_clamped": self.n_clamped}
+                "n_clamped": self.n_clamped, "n_purged": self.n_purged}
 
 
 PSSM_PSEUDOCOUNT_DEFAULT = 10.0
@@ -333,6 +333,8 @@ _sig("swg_synth_db_iid", C.c_int, [C.c_uint64, C.c_size_t, C.c_uint32, _vp, C.PO
 _sig("swg_gumbel_fit_hist", C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)])
 _sig("swg_matrix_lambda", C.c_int, [_vp, _vp, C.POINTER(C.c_double)])
 _sig("swg_pssm_from_paths", C.c_int, [_vp, _vp, C.c_double, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp])
+_sig("swg_pssm_from_paths_ex", C.c_int, [_vp, _vp, C.c_double, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
+                                         _vp, _vp, _vp])
 _sig("swg_pssm_save", C.c_int, [C.c_char_p, _vp, _vp, C.c_size_t])
 _sig("swg_pssm_build", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_double, _vp, _vp, _vp])
 _sig("swg_pssm_build_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, C.c_double, _vp, _vp, _vp])
@@ -548,10 +550,12 @@ def matrix_lambda(sub, freq=None):
     return lam.value
 
 
-def pssm_from_paths(sub, query, flat, offsets, alignments, freq=None, pseudocount=PSSM_PSEUDOCOUNT_DEFAULT, want_values=False):
+def pssm_from_paths(sub, query, flat, offsets, alignments, freq=None, pseudocount=PSSM_PSEUDOCOUNT_DEFAULT, want_values=False,
+                    blocks=False, purge=0):
     """The PSSM of `query` (table indices) from its hits' alignments on the host (swg_pssm_from_paths, the twin of
     Context.build_pssm): alignments is what align_hits returns with want_ops=True -- dicts whose "index" is an index
-    into flat / offsets -> (pssm int8[lq, 32], values float64[lq, 32] or None, info dict)."""
+    into flat / offsets -> (pssm int8[lq, 32], values float64[lq, 32] or None, info dict).  blocks, purge: the model's
+    options "pssm_blocks" and "pssm_purge" (swg_pssm_from_paths_ex); both off, the old entry point is called."""
     if isinstance(sub, Scoring):
         sub = sub.table()
     s, sp = _i8(np.asarray(sub).reshape(32, 32))
@@ -571,8 +575,12 @@ def pssm_from_paths(sub, query, flat, offsets, alignments, freq=None, pseudocoun
     pssm = np.zeros((q.size, 32), dtype=np.int8)
     values = np.zeros((q.size, 32), dtype=np.float64) if want_values else None
     info = PssmInfo()
-    _check(lib.swg_pssm_from_paths(sp, fp, float(pseudocount), qp, q.size, flp, off.ctypes.data_as(_vp), C.cast(al, _vp), C.cast(ops, _vp),
-                                   stride, n, pssm.ctypes.data_as(_vp), values.ctypes.data_as(_vp) if want_values else None, C.byref(info)))
+    head = (sp, fp, float(pseudocount), qp, q.size, flp, off.ctypes.data_as(_vp), C.cast(al, _vp), C.cast(ops, _vp), stride, n)
+    tail = (pssm.ctypes.data_as(_vp), values.ctypes.data_as(_vp) if want_values else None, C.byref(info))
+    if not blocks and not purge:
+        _check(lib.swg_pssm_from_paths(*head, *tail))
+    else:
+        _check(lib.swg_pssm_from_paths_ex(*head, int(blocks), int(purge), *tail))
     return pssm, values, info.as_dict()
 
 

@@ -400,6 +400,14 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
     } else if (!strcmp(key, "pssm_msa_mb")) {
         if (value < 0 || value > 65536) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "pssm_msa_mb must be 0..65536 (MiB of device rows one group of queries of swg_pssm_build* may take; 0: every query alone)");
         ctx->opt_pssm_msa_mb = value;
+    } else if (!strcmp(key, "pssm_blocks")) {
+        if (value != 0 && value != 1)
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "pssm_blocks must be 0 (swg_pssm_build*: the whole query is every column's block) or 1 (per-column blocks)");
+        ctx->opt_pssm_blocks = value;
+    } else if (!strcmp(key, "pssm_purge")) {
+        if (value != 0 && (value < 50 || value > 100))
+            return swg_set_ctx_error(ctx, SWG_ERR_ARG, "pssm_purge must be 0 (off) or 50..100 (swg_pssm_build*: percent identity at which a hit is dropped)");
+        ctx->opt_pssm_purge = value;
     } else if (!strcmp(key, "calib_len")) {
         if (value < 8 || value > (1l << 14)) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "calib_len must be 8..16384 (residues of a calibration's random sequences)");
         ctx->opt_calib_len = value;

@@ -725,6 +725,8 @@ struct swg_ctx {
     SwgSlot slots[SWG_MAX_INFLIGHT];
     SwgSlot *cur = nullptr; // slot whose events the launch helpers record into
     int next_slot = 0;
+    long opt_pssm_blocks = 0;    // swg_pssm_build*: 1: per-column alignment blocks (option "pssm_blocks"); 0: the whole query is every column's block
+    long opt_pssm_purge = 0;     // swg_pssm_build*: percent identity at which a hit is dropped, 50..100 (option "pssm_purge"); 0: no purge
 };
 
 // Internal status (positive: never a public SWG_ERR_*): a database built from 16-lane batches has pair tokens only, and

@@ -108,13 +108,15 @@ static inline int8_t pssm_round(double v, bool *clamped)
     return (int8_t)(r < -128.0 ? -128.0 : r > 127.0 ? 127.0 : r);
 }
 
-static int from_paths(const int8_t sub[32][32], const double *freq, double beta, const int8_t *query, size_t lq, const int8_t *flat,
-                      const uint64_t *offsets, const swg_alignment *al, const char *ops, size_t ops_stride, size_t n_hits,
-                      int8_t *pssm_out, double *values_out, swg_pssm_info *info)
+static int from_paths(const char *fn, const int8_t sub[32][32], const double *freq, double beta, const int8_t *query, size_t lq,
+                      const int8_t *flat, const uint64_t *offsets, const swg_alignment *al, const char *ops, size_t ops_stride, size_t n_hits,
+                      int blocks, int purge, int8_t *pssm_out, double *values_out, swg_pssm_info *info)
 {
-    const char *fn = "swg_pssm_from_paths";
     if (!sub || !query || lq == 0 || !pssm_out || (n_hits && (!flat || !offsets || !al || !ops)))
         return swg_set_global_error(SWG_ERR_ARG, "%s: NULL argument or empty query", fn);
+    if (blocks != 0 && blocks != 1) return swg_set_global_error(SWG_ERR_ARG, "%s: blocks must be 0 (the whole query) or 1 (per-column blocks)", fn);
+    if (purge != 0 && (purge < 50 || purge > 100))
+        return swg_set_global_error(SWG_ERR_ARG, "%s: purge must be 0 (off) or 50..100 (percent identity)", fn);
     double P[32], lambda;
     uint32_t mask;
     int rc = swg_pssm_check_model(fn, sub, freq, beta, P, &mask, &lambda);
@@ -123,11 +125,13 @@ static int from_paths(const int8_t sub[32][32], const double *freq, double beta,
         if (query[p] < 1 || query[p] > 31)
             return swg_set_global_error(SWG_ERR_RESIDUE, "%s: residue index %d in the query outside 1..31", fn, query[p]);
 
-    // the rows: 0 empty, 1..31 a residue, 32 a gap
+    // the rows: 0 empty, 1..31 a residue, 32 a gap; row r's extent is [eb[r], ee[r]) (empty: a hit of score 0)
     const size_t R = n_hits + 1;
     std::vector<uint8_t> msa(R * lq, 0);
+    std::vector<size_t> eb(R, 0), ee(R, 0);
     for (size_t p = 0; p < lq; ++p) msa[p] = (uint8_t)query[p];
-    uint32_t n_rows = 1;
+    ee[0] = lq;
+    uint32_t n_rows = 1, n_purged = 0;
     for (size_t h = 0; h < n_hits; ++h) {
         const swg_alignment &a = al[h];
         if (a.score <= 0 || a.n_ops == 0) continue;
@@ -147,10 +151,68 @@ static int from_paths(const int8_t sub[32][32], const double *freq, double beta,
             else if (op == 'D') row[qp] = 32;
             qp += uq, dp += ud;
         }
+        eb[h + 1] = a.q_begin, ee[h + 1] = qp;
     }
     const auto in_A = [&](uint8_t x) { return x >= 1 && x <= 31 && (mask >> x & 1u); };
 
-    // counts
+    // the purge: rows in hit order, in integers; a purged row becomes a hit of score 0
+    if (purge > 0) {
+        const auto near = [&](size_t r, size_t s, bool to_query) {
+            const uint8_t *x = msa.data() + r * lq, *y = msa.data() + s * lq;
+            uint64_t c = 0, i = 0;
+            for (size_t p = 0; p < lq; ++p) {
+                const bool both = x[p] >= 1 && x[p] <= 31 && y[p] >= 1 && y[p] <= 31;
+                c += both, i += both && x[p] == y[p];
+            }
+            return c >= 1 && (to_query ? i == c : 100u * i >= (uint64_t)purge * c);
+        };
+        std::vector<size_t> kept;
+        for (size_t r = 1; r < R; ++r) {
+            if (eb[r] >= ee[r]) continue;
+            bool drop = near(r, 0, true);
+            for (size_t j = 0; j < kept.size() && !drop; ++j) drop = near(r, kept[j], false);
+            if (!drop) {
+                kept.push_back(r);
+                continue;
+            }
+            std::memset(msa.data() + r * lq, 0, lq);
+            eb[r] = ee[r] = 0;
+            --n_rows, ++n_purged;
+        }
+    }
+
+    // exp(lambda sub[b][a]): b in the query's role
+    double E[32][32];
+    for (int b = 0; b < 32; ++b)
+        for (int a = 0; a < 32; ++a) E[b][a] = std::exp(lambda * (double)sub[b][a]);
+    uint32_t n_clamped = 0;
+    // column p with m_p >= 1 from its frequencies and alpha_p: g, Q, v, the rounding
+    const auto score_column = [&](size_t p, const double f[32], double alpha) {
+        int8_t *out = pssm_out + p * 32;
+        double *val = values_out ? values_out + p * 32 : nullptr;
+        for (int a = 1; a < 32; ++a) {
+            if (!(mask >> a & 1u)) continue;
+            double g = 0.0;
+            for (int b = 1; b < 32; ++b)
+                if (mask >> b & 1u) g += f[b] * E[b][a];
+            g *= P[a];
+            const double Q = (alpha * f[a] + beta * g) / (alpha + beta);
+            const double v = std::log(Q / P[a]) / lambda;
+            bool clamped;
+            out[a] = pssm_round(v, &clamped);
+            n_clamped += clamped;
+            if (val) val[a] = v;
+        }
+    };
+    for (size_t p = 0; p < lq; ++p) { // the fallback every column starts from
+        int8_t *out = pssm_out + p * 32;
+        out[0] = 0;
+        for (int a = 1; a < 32; ++a) out[a] = sub[query[p]][a];
+        if (values_out)
+            for (int a = 0; a < 32; ++a) values_out[p * 32 + a] = 0.0;
+    }
+
+    // counts over all rows: m_p and the columns some hit shows a residue in are the same under both models
     std::vector<uint32_t> n(lq * 32, 0), kp(lq, 0), mp(lq, 0);
     uint64_t sum_k = 0, n_m = 0, n_obs = 0;
     for (size_t p = 0; p < lq; ++p) {
@@ -165,60 +227,100 @@ static int from_paths(const int8_t sub[32][32], const double *freq, double beta,
         if (mp[p] >= 1) sum_k += kp[p], ++n_m;
         n_obs += m_hits > 0;
     }
-    const double nbar = n_m ? (double)sum_k / (double)n_m : 0.0;
+    double nbar = n_m ? (double)sum_k / (double)n_m : 0.0;
 
-    // weights
-    std::vector<double> w(R, 0.0);
-    for (size_t r = 0; r < R; ++r) {
-        double s = 0.0;
-        for (size_t p = 0; p < lq; ++p) {
-            const uint8_t x = msa[r * lq + p];
-            if (in_A(x)) s += 1.0 / ((double)kp[p] * (double)n[p * 32 + x]);
-        }
-        w[r] = s;
-    }
-
-    // exp(lambda sub[b][a]): b in the query's role
-    double E[32][32];
-    for (int b = 0; b < 32; ++b)
-        for (int a = 0; a < 32; ++a) E[b][a] = std::exp(lambda * (double)sub[b][a]);
-
-    uint32_t n_clamped = 0;
-    for (size_t p = 0; p < lq; ++p) {
-        const int q = query[p];
-        int8_t *out = pssm_out + p * 32;
-        double *val = values_out ? values_out + p * 32 : nullptr;
-        out[0] = 0;
-        for (int a = 1; a < 32; ++a) out[a] = sub[q][a];
-        if (val)
-            for (int a = 0; a < 32; ++a) val[a] = 0.0;
-        if (mp[p] == 0) continue;
-        double acc[32] = {0.0}, W = 0.0, f[32];
+    if (!blocks) {
+        // weights
+        std::vector<double> w(R, 0.0);
         for (size_t r = 0; r < R; ++r) {
-            const uint8_t x = msa[r * lq + p];
-            if (in_A(x)) acc[x] += w[r], W += w[r];
+            double s = 0.0;
+            for (size_t p = 0; p < lq; ++p) {
+                const uint8_t x = msa[r * lq + p];
+                if (in_A(x)) s += 1.0 / ((double)kp[p] * (double)n[p * 32 + x]);
+            }
+            w[r] = s;
         }
-        for (int a = 0; a < 32; ++a) f[a] = acc[a] / W;
-        const double alpha = std::fmin(nbar, (double)mp[p]) - 1.0;
-        for (int a = 1; a < 32; ++a) {
-            if (!(mask >> a & 1u)) continue;
-            double g = 0.0;
-            for (int b = 1; b < 32; ++b)
-                if (mask >> b & 1u) g += f[b] * E[b][a];
-            g *= P[a];
-            const double Q = (alpha * f[a] + beta * g) / (alpha + beta);
-            const double v = std::log(Q / P[a]) / lambda;
-            bool clamped;
-            out[a] = pssm_round(v, &clamped);
-            n_clamped += clamped;
-            if (val) val[a] = v;
+        for (size_t p = 0; p < lq; ++p) {
+            if (mp[p] == 0) continue;
+            double acc[32] = {0.0}, W = 0.0, f[32];
+            for (size_t r = 0; r < R; ++r) {
+                const uint8_t x = msa[r * lq + p];
+                if (in_A(x)) acc[x] += w[r], W += w[r];
+            }
+            for (int a = 0; a < 32; ++a) f[a] = acc[a] / W;
+            score_column(p, f, std::fmin(nbar, (double)mp[p]) - 1.0);
         }
+    } else {
+        // segments: the columns between two consecutive extent boundaries share R_p, hence the block and the weights
+        std::vector<uint8_t> cut(lq + 1, 0);
+        for (size_t r = 0; r < R; ++r)
+            if (eb[r] < ee[r]) cut[eb[r]] = cut[ee[r]] = 1;
+        std::vector<size_t> member;
+        std::vector<uint32_t> bn, bk;
+        std::vector<double> w;
+        double sum_nbar = 0.0;
+        for (size_t p0 = 0; p0 < lq;) {
+            size_t p1 = p0 + 1;
+            while (!cut[p1]) ++p1;
+            member.clear();
+            size_t L = 0, U = lq;
+            for (size_t r = 0; r < R; ++r)
+                if (eb[r] <= p0 && p0 < ee[r]) member.push_back(r), L = eb[r] > L ? eb[r] : L, U = ee[r] < U ? ee[r] : U;
+            const size_t width = U - L;
+            bn.assign(width * 32, 0), bk.assign(width, 0);
+            uint64_t bsum_k = 0, bn_m = 0;
+            for (size_t c = 0; c < width; ++c) {
+                uint32_t m = 0;
+                for (size_t r : member) {
+                    const uint8_t x = msa[r * lq + L + c];
+                    if (in_A(x)) ++bn[c * 32 + x];
+                }
+                for (int a = 1; a < 32; ++a) bk[c] += bn[c * 32 + a] > 0, m += bn[c * 32 + a];
+                if (m >= 1) bsum_k += bk[c], ++bn_m;
+            }
+            const double bnbar = bn_m ? (double)bsum_k / (double)bn_m : 0.0;
+            w.assign(member.size(), 0.0);
+            for (size_t j = 0; j < member.size(); ++j) {
+                double s = 0.0;
+                for (size_t c = 0; c < width; ++c) {
+                    const uint8_t x = msa[member[j] * lq + L + c];
+                    if (in_A(x)) s += 1.0 / ((double)bk[c] * (double)bn[c * 32 + x]);
+                }
+                w[j] = s;
+            }
+            for (size_t p = p0; p < p1; ++p) {
+                if (mp[p] == 0) continue;
+                double acc[32] = {0.0}, W = 0.0, f[32];
+                for (size_t j = 0; j < member.size(); ++j) {
+                    const uint8_t x = msa[member[j] * lq + p];
+                    if (in_A(x)) acc[x] += w[j], W += w[j];
+                }
+                for (int a = 0; a < 32; ++a) f[a] = acc[a] / W;
+                score_column(p, f, std::fmin(bnbar, (double)mp[p]) - 1.0);
+                sum_nbar += bnbar;
+            }
+            p0 = p1;
+        }
+        nbar = n_m ? sum_nbar / (double)n_m : 0.0;
     }
     if (info) {
         info->lambda = lambda, info->n_distinct = nbar;
-        info->n_rows = n_rows, info->n_observed = (uint32_t)n_obs, info->n_clamped = n_clamped, info->reserved = 0;
+        info->n_rows = n_rows, info->n_observed = (uint32_t)n_obs, info->n_clamped = n_clamped, info->n_purged = n_purged;
     }
     return SWG_OK;
+}
+
+extern "C" int swg_pssm_from_paths_ex(const int8_t sub[32][32], const double *freq, double pseudocount, const int8_t *query, size_t lq,
+                                      const int8_t *flat, const uint64_t *offsets, const swg_alignment *al, const char *ops,
+                                      size_t ops_stride, size_t n_hits, int blocks, int purge, int8_t *pssm_out, double *values_out,
+                                      swg_pssm_info *info)
+{
+    try {
+        return from_paths("swg_pssm_from_paths_ex", sub, freq, pseudocount, query, lq, flat, offsets, al, ops, ops_stride, n_hits, blocks, purge,
+                          pssm_out, values_out, info);
+    } catch (const std::bad_alloc &) {
+        return swg_set_global_error(SWG_ERR_NOMEM, "swg_pssm_from_paths_ex: out of host memory");
+    }
 }
 
 extern "C" int swg_pssm_from_paths(const int8_t sub[32][32], const double *freq, double pseudocount, const int8_t *query, size_t lq,
@@ -226,7 +328,8 @@ extern "C" int swg_pssm_from_paths(const int8_t sub[32][32], const double *freq,
                                    size_t ops_stride, size_t n_hits, int8_t *pssm_out, double *values_out, swg_pssm_info *info)
 {
     try {
-        return from_paths(sub, freq, pseudocount, query, lq, flat, offsets, al, ops, ops_stride, n_hits, pssm_out, values_out, info);
+        return from_paths("swg_pssm_from_paths", sub, freq, pseudocount, query, lq, flat, offsets, al, ops, ops_stride, n_hits, 0, 0, pssm_out,
+                          values_out, info);
     } catch (const std::bad_alloc &) {
         return swg_set_global_error(SWG_ERR_NOMEM, "swg_pssm_from_paths: out of host memory");
     }

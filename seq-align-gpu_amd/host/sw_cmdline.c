@@ -41,7 +41,8 @@
  *     --iterations N searches N times, PSI-BLAST's way: each iteration but the last calibrates the current query, turns
  *     --inclusion's E-value into a least score, collects up to --maxincluded hits at or above it (swg_search_above), builds
  *     their PSSM on the device (swg_pssm_build) and makes it the query; the last iteration is the report above with that
- *     PSSM as the query, and --out_pssm writes it in the layout --pssm reads.
+ *     PSSM as the query, and --out_pssm writes it in the layout --pssm reads; --psiblocks and --purge P set the
+ *     construction's options "pssm_blocks" and "pssm_purge" (per-column blocks, near-identical hits dropped).
  * There is no CPU backend: without a GPU the tool fails with a message.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -133,6 +134,10 @@ static void usage(const char *argv0, const char *err)
             "    --inclusion <E>      with --iterations: the largest E-value of an included entry [default: 0.002]\n"
             "    --maxincluded <M>    with --iterations: the most entries included per iteration [default: 500]\n"
             "    --out_pssm <file>    with --iterations: write the last PSSM (readable by --pssm)\n"
+            "    --psiblocks          with --iterations: PSI-BLAST's per-column alignment blocks (option pssm_blocks) instead of one block,\n"
+            "                         the whole query, for every column\n"
+            "    --purge <P>          with --iterations: drop a hit that is P percent (50 to 100; PSI-BLAST: 94) identical to a kept hit, or\n"
+            "                         identical to the query, before the PSSM is built (option pssm_purge)\n"
             "    --prefilter <N>      with --topk K: per query (every record with --allqueries) the N best entries by gapless\n"
             "                         score are searched with gaps and the K best of those reported (--align: aligned);\n"
             "                         no Entry lines are printed; not with --gpus, --candidates or --gapless\n"
@@ -292,7 +297,8 @@ int main(int argc, char **argv)
     int align = 0, gapless = 0, bounds = 0, tabular = 0, have_evalue = 0, compfromdb = 0;
     double evalue = 0.0, inclusion = 0.002;
     long iterations = 0, maxincluded = 500;
-    int have_inclusion = 0, have_maxincluded = 0;
+    int have_inclusion = 0, have_maxincluded = 0, psiblocks = 0;
+    long purge = 0;
     const char *out_pssm = NULL;
     int maskdb = 0, softmask = 0, maskquery = 0;
     swg_mask_params mp;
@@ -323,6 +329,8 @@ int main(int argc, char **argv)
             tabular = 1;
         } else if (!strcasecmp(a, "--compfromdb")) {
             compfromdb = 1;
+        } else if (!strcasecmp(a, "--psiblocks")) {
+            psiblocks = 1;
         } else if (!strcasecmp(a, "--timing")) {
             timing = 1;
         } else if (!strcasecmp(a, "--allqueries")) {
@@ -400,6 +408,9 @@ int main(int argc, char **argv)
             i++;
         } else if (!strcasecmp(a, "--out_pssm")) {
             out_pssm = argv[++i];
+        } else if (!strcasecmp(a, "--purge")) {
+            if (!parse_int(argv[i + 1], 50, 100, &purge)) usage(argv[0], "Invalid --purge argument: the percent identity at which a hit is dropped, 50 to 100");
+            i++;
         } else if (!strcasecmp(a, "--prefilter")) {
             if (!parse_int(argv[i + 1], 1, 1 << 20, &prefilter)) usage(argv[0], "Invalid --prefilter argument: the number of candidates per query, 1 or more");
             i++;
@@ -451,6 +462,8 @@ int main(int argc, char **argv)
     if (compfromdb && !have_evalue && !iterations) usage(argv[0], "--compfromdb chooses the background of --evalue's calibration: give --evalue E");
     if (!iterations && (have_inclusion || have_maxincluded || out_pssm))
         usage(argv[0], "--inclusion, --maxincluded and --out_pssm belong to the iterated search: give --iterations N");
+    if (!iterations && psiblocks) usage(argv[0], "--psiblocks chooses the model of the iterated search's PSSM: give --iterations N");
+    if (!iterations && purge) usage(argv[0], "--purge drops near-identical hits from the iterated search's PSSM: give --iterations N");
     if (iterations && allq) usage(argv[0], "--iterations iterates one query record: it does not combine with --allqueries");
     if (iterations && gpus > 1) usage(argv[0], "--iterations works with one GPU (--gpu): it does not combine with --gpus N > 1");
     if (iterations && cand_path) usage(argv[0], "--iterations makes its own lists of included entries: it does not combine with --candidates");
@@ -1034,6 +1047,8 @@ int main(int argc, char **argv)
             unsigned char *was = (unsigned char *)calloc(db.n ? db.n : 1, 1); /* the entries the previous iteration included */
             iter_pssm = (int8_t *)malloc(lq * 32);
             if (!inc || !was || !iter_pssm) return leave(EXIT_FAILURE);
+            if (rc == SWG_OK && psiblocks) rc = swg_set_option(ctx, "pssm_blocks", 1);
+            if (rc == SWG_OK && purge) rc = swg_set_option(ctx, "pssm_purge", purge);
             for (long it = 1; rc == SWG_OK && it < iterations; it++) {
                 swg_evalue_params p;
                 size_t n_inc = 0, n_new = 0;
