@@ -654,6 +654,48 @@ int swg_align_stats_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pss
                                size_t n_queries, const swg_hit *hits, size_t k, const size_t *n_hits,
                                swg_alignment *out, swg_align_counts *counts);
 
+/* Several alignments per hit: every non-overlapping local alignment of a pair at or above a score, best first (the
+ * HSPs of BLAST, the alignments upstream seq-align's smith_waterman prints one after another; Waterman and Eggert 1987).
+ * Alignment 0 of a pair is what swg_align_hits gives: recurrence, tie rules, coordinates and path letters as above.
+ * Alignment r >= 1 is the best alignment of the same recurrence with one change.  A cell (j, i) is USED when database
+ * residue j was aligned to query column i by an 'M' step of alignments 0 .. r-1 of this pair, and the H state of a used
+ * cell is minus infinity: a used cell is never the best cell, and no state of a neighbouring cell takes the used cell's
+ * H as a predecessor.  The used cell's own A and B states (the gap states) are computed as before from its neighbours,
+ * so a later alignment may cross an earlier one through a gap; it never shares an aligned residue pair with it.
+ * Everything else is unchanged: the best cell is the highest H, then the smallest database position, then the smallest
+ * query position; a state whose maximum is 0 starts the alignment; otherwise the first maximal predecessor in the
+ * order H, A, B.  The rounds of a pair stop at the first alignment whose score is below min_score (>= 1), or after
+ * max_hsps (1 .. SWG_MAX_HSPS) alignments; the scores of a pair's alignments never increase from one to the next.
+ * Each round fills the pair's whole matrix again: max_hsps fills at worst.
+ *
+ * The arguments are those of swg_align_hits / _multi / _multi_pssm (only .index of a hit is read; hits in any order
+ * and repeated; a view is accepted; the database must be resident; swg_align_hsps uses the context's query, index or
+ * PSSM, and the batch calls neither read nor change it).  Outputs by hit slot s (s = h for swg_align_hsps, s = i*k + j
+ * for the batch calls): n_hsps[s] alignments were written, to out[s*max_hsps + r], and, where the pointers are not
+ * NULL, their counts (the four fields of swg_align_stats, for that alignment's path; a PSSM's identity against its
+ * consensus) to counts[s*max_hsps + r] and their paths to ops + (s*max_hsps + r)*ops_stride.  n_hsps[s] is 0 when the
+ * pair's best is below min_score.  Slots past n_hsps[s] are not written, nor those of hits past n_hits[i]; reserved = 0.
+ * swg_align_ops_bound* still give a sufficient ops_stride.  With max_hsps = 1 and min_score = 1 every written field
+ * and path equals swg_align_hits*.  Errors, all before anything is launched: max_hsps outside 1 .. SWG_MAX_HSPS,
+ * min_score < 1, out or n_hsps NULL with a hit present (SWG_ERR_ARG); everything else as the swg_align_hits* call of the
+ * same shape. */
+#define SWG_MAX_HSPS 64
+int swg_align_hsps(swg_ctx *ctx, const swg_db *db, const swg_hit *hits, size_t n_hits, uint32_t max_hsps, int32_t min_score,
+                   swg_alignment *out, uint32_t *n_hsps, swg_align_counts *counts, char *ops, size_t ops_stride);
+int swg_align_hsps_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets, size_t n_queries,
+                         const swg_hit *hits, size_t k, const size_t *n_hits, uint32_t max_hsps, int32_t min_score,
+                         swg_alignment *out, uint32_t *n_hsps, swg_align_counts *counts, char *ops, size_t ops_stride);
+int swg_align_hsps_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets, size_t n_queries,
+                              const swg_hit *hits, size_t k, const size_t *n_hits, uint32_t max_hsps, int32_t min_score,
+                              swg_alignment *out, uint32_t *n_hsps, swg_align_counts *counts, char *ops, size_t ops_stride);
+/* The host twin: the same rule for one pair in plain C++ (no GPU needed).  Exactly one of query (lq table indices 1..31,
+ * scored by sub) and pssm (lq rows of 32) is not NULL; seq holds len table indices.  out[max_hsps] (index = 0), and where
+ * not NULL counts[max_hsps] and the paths at ops + r*ops_stride (lq + len + 1 is always enough); *n_out alignments were
+ * written.  Errors are SWG_ERR_ARG / SWG_ERR_RESIDUE with swg_global_error() set. */
+int swg_align_hsps_host(const int8_t sub[32][32], int gap_open, int gap_extend, const int8_t *query, const int8_t *pssm, size_t lq,
+                        const int8_t *seq, size_t len, uint32_t max_hsps, int32_t min_score, swg_alignment *out,
+                        swg_align_counts *counts, char *ops, size_t ops_stride, uint32_t *n_out);
+
 /* ---- a PSSM from a query's hits (the step between two iterations of a profile search) ------------------- */
 
 /* PSI-BLAST's construction (Altschul et al. 1997) with one simplification: the alignment block of every column is the

@@ -39,7 +39,8 @@ ABI_SYMBOLS = [
     "swg_search_gapless_multi_pssm", "swg_search_above", "swg_search_gapless_above", "swg_search_above_multi", "swg_search_above_multi_pssm",
     "swg_search_gapless_above_multi", "swg_search_gapless_above_multi_pssm", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_align_hits_multi",
     "swg_align_hits_multi_pssm", "swg_align_ops_bound_multi", "swg_align_bounds", "swg_align_bounds_multi",
-    "swg_align_bounds_multi_pssm", "swg_align_stats", "swg_align_stats_multi", "swg_align_stats_multi_pssm", "swg_hit_key",
+    "swg_align_bounds_multi_pssm", "swg_align_stats", "swg_align_stats_multi", "swg_align_stats_multi_pssm", "swg_align_hsps",
+    "swg_align_hsps_multi", "swg_align_hsps_multi_pssm", "swg_align_hsps_host", "swg_hit_key",
     "swg_key_hit", "swg_topk_merge_keys",
     "swg_group_create", "swg_group_destroy", "swg_group_size", "swg_group_last_error", "swg_group_set_option",
     "swg_group_set_scoring", "swg_group_set_query", "swg_group_set_query_pssm", "swg_group_load", "swg_group_search",
@@ -268,6 +269,10 @@ _sig("swg_debug_fail_alloc", None, [C.c_int])
 _sig("swg_align_stats", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp])
 _sig("swg_align_stats_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp])
 _sig("swg_align_stats_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp])
+_sig("swg_align_hsps", C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, C.c_size_t])
+_sig("swg_align_hsps_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, C.c_size_t])
+_sig("swg_align_hsps_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, C.c_size_t])
+_sig("swg_align_hsps_host", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint32, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp])
 _sig("swg_debug_bounds_last", C.c_int, [_vp, _vp])
 _sig("swg_debug_sort_count", C.c_ulong, [])
 _sig("swg_debug_engine", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_int, _vp])
@@ -1023,6 +1028,35 @@ def mask_tables(window=12, trigger=2.2, extend=2.5, replace=MASK_REPLACE_DEFAULT
     return T, t1.value, t2.value
 
 
+def align_hsps_host(sub, gap_open, gap_extend, seq, max_hsps, min_score=1, query=None, pssm=None, want_ops=True, want_counts=False):
+    """The alignments of one pair on the host (swg_align_hsps_host, the twin of Context.align_hsps): sub int8[32, 32], one of
+    query (table indices) and pssm (int8[lq, 32]), seq table indices -> the list of alignments as align_hsps gives it
+    (index 0)."""
+    t = np.ascontiguousarray(sub, dtype=np.int8) if sub is not None else None
+    q = np.ascontiguousarray(query, dtype=np.int8) if query is not None else None
+    p = np.ascontiguousarray(pssm, dtype=np.int8) if pssm is not None else None
+    d = np.ascontiguousarray(seq, dtype=np.int8)
+    lq = q.size if q is not None else (p.shape[0] if p is not None else 0)
+    per, stride = max(int(max_hsps), 1), lq + d.size + 1
+    out = (Alignment * per)()
+    cnt = (AlignCounts * per)() if want_counts else None
+    ops = C.create_string_buffer(per * stride) if want_ops else None
+    n = C.c_uint32(0)
+    _check(lib.swg_align_hsps_host(t.ctypes.data_as(_vp) if t is not None else None, int(gap_open), int(gap_extend),
+                                   q.ctypes.data_as(_vp) if q is not None else None, p.ctypes.data_as(_vp) if p is not None else None, lq,
+                                   d.ctypes.data_as(_vp), d.size, int(max_hsps), int(min_score), C.cast(out, _vp),
+                                   C.cast(cnt, _vp) if want_counts else None, C.cast(ops, _vp) if want_ops else None, stride, C.byref(n)))
+    res = []
+    for r in range(n.value):
+        a = {f: int(getattr(out[r], f)) for f, _ in Alignment._fields_ if f != "reserved"}
+        if want_counts:
+            a.update((f, int(getattr(cnt[r], f))) for f, _ in AlignCounts._fields_)
+        if want_ops:
+            a["ops"] = ops.raw[r * stride:r * stride + a["n_ops"]].decode()
+        res.append(a)
+    return res
+
+
 def seg_mask(seq, window=12, trigger=2.2, extend=2.5, replace=MASK_REPLACE_DEFAULT, want_segments=False):
     """The low-complexity mask of one sequence of table indices (swg_seg_mask, the host twin of Database.mask): a bool
     array, True where the position is masked; with want_segments also the number of kept runs.  The sequence is not
@@ -1725,6 +1759,78 @@ class Context:
         qoff[1:] = np.cumsum([r.shape[0] for r in rows])
         pflat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 32)), dtype=np.int8)
         return self._align_multi(lib.swg_align_stats_multi_pssm, db, pflat, qoff, hits, False, None, bounds=True, stats=True)
+
+    def align_hsps(self, db, hits, max_hsps, min_score=1, want_ops=True, want_counts=False):
+        """Every non-overlapping alignment of each hit at or above min_score, at most max_hsps of them, best first
+        (swg_align_hsps) -> per hit the list of its alignments: align_hits' dicts, with align_stats' four counts when
+        want_counts.  The first of a hit's alignments is align_hits' one."""
+        n = len(hits)
+        arr = (Hit * max(n, 1))()
+        for i, (sc, ix) in enumerate(hits):
+            arr[i].score, arr[i].index = int(sc), int(ix)
+        stride = int(lib.swg_align_ops_bound(self.handle, db.handle))
+        return self._align_hsps(lambda *tail: lib.swg_align_hsps(self.handle, db.handle, C.cast(arr, _vp), n, *tail),
+                                [n], n, stride, max_hsps, min_score, want_ops, want_counts)[0]
+
+    def align_hsps_multi(self, db, queries, hits, max_hsps, min_score=1, want_ops=True, want_counts=False):
+        """align_hsps for a batch: queries and hits as align_hits_multi takes them -> per query, per hit, the list of its
+        alignments.  The context's own query is left as it was."""
+        qoff = np.zeros(len(queries) + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in queries])
+        qflat = np.ascontiguousarray(np.concatenate(queries) if len(queries) else np.zeros(0), dtype=np.int8)
+        return self._align_hsps_multi(lib.swg_align_hsps_multi, db, qflat, qoff, hits, max_hsps, min_score, want_ops, want_counts)
+
+    def align_hsps_multi_pssm(self, db, pssms, hits, max_hsps, min_score=1, want_ops=True, want_counts=False):
+        """align_hsps_multi with position-specific queries; identity is counted against each PSSM's consensus."""
+        rows = [_pssm(p)[0] for p in pssms]
+        qoff = np.zeros(len(rows) + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([r.shape[0] for r in rows])
+        pflat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 32)), dtype=np.int8)
+        return self._align_hsps_multi(lib.swg_align_hsps_multi_pssm, db, pflat, qoff, hits, max_hsps, min_score, want_ops, want_counts)
+
+    def _align_hsps_multi(self, fn, db, qflat, qoff, hits, max_hsps, min_score, want_ops, want_counts):
+        nq = len(qoff) - 1
+        if len(hits) != nq:
+            raise ValueError("hits: %d rows for %d queries" % (len(hits), nq))
+        k = max((len(row) for row in hits), default=0)
+        arr = (Hit * max(nq * k, 1))()
+        nh = (C.c_size_t * max(nq, 1))()
+        for i, row in enumerate(hits):
+            nh[i] = len(row)
+            for j, (sc, ix) in enumerate(row):
+                arr[i * k + j].score, arr[i * k + j].index = int(sc), int(ix)
+        stride = int(lib.swg_align_ops_bound_multi(db.handle, qoff.ctypes.data_as(_vp), nq))
+        return self._align_hsps(lambda *tail: fn(self.handle, db.handle, qflat.ctypes.data_as(_vp), qoff.ctypes.data_as(_vp), nq,
+                                                 C.cast(arr, _vp), k, C.cast(nh, _vp), *tail),
+                                [len(row) for row in hits], k, stride, max_hsps, min_score, want_ops, want_counts)
+
+    def _align_hsps(self, call, row_lens, k, stride, max_hsps, min_score, want_ops, want_counts):
+        """The outputs of one swg_align_hsps* call over rows of k hit slots, row i holding row_lens[i] hits."""
+        per = max(int(max_hsps), 1)                     # (a refused max_hsps still needs buffers to hand over)
+        slots = max(len(row_lens) * k, 1)
+        out = (Alignment * (slots * per))()
+        nout = (C.c_uint32 * slots)()
+        cnt = (AlignCounts * (slots * per))() if want_counts else None
+        ops = C.create_string_buffer(max(1, slots * per * stride)) if want_ops else None
+        _check(call(int(max_hsps), int(min_score), C.cast(out, _vp), C.cast(nout, _vp), C.cast(cnt, _vp) if want_counts else None,
+                    C.cast(ops, _vp) if want_ops else None, stride), self.handle)
+        raw = ops.raw if want_ops else None
+        res = []
+        for i, nrow in enumerate(row_lens):
+            row = []
+            for j in range(nrow):
+                s = i * k + j
+                als = []
+                for r in range(int(nout[s])):
+                    e = s * per + r
+                    a = self._stats_dict(out[e], cnt[e]) if want_counts else \
+                        {f: int(getattr(out[e], f)) for f, _ in Alignment._fields_ if f != "reserved"}
+                    if want_ops:
+                        a["ops"] = raw[e * stride:e * stride + a["n_ops"]].decode()
+                    als.append(a)
+                row.append(als)
+            res.append(row)
+        return res
 
     @staticmethod
     def _stats_dict(al, cnt):

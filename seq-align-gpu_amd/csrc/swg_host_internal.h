@@ -899,6 +899,31 @@ struct SwgTraceSink {
 };
 int swg_trace_align_batch(swg_ctx *ctx, const swg_db *db, const SwgTraceBatch &tb, size_t total, swg_alignment *out, char *ops,
                           size_t ops_stride, const SwgTraceSink *sink = nullptr);
+// The launch rule of the traceback's kernels, which swg_align_hsps* (swg_hsps.hip) launches its own kernel by: 256 lanes a
+// pair; a launch holds the queries of one class -- one power-of-two range of lengths among those whose nine rotating
+// diagonals fit LDS (so its dynamic LDS, sized by its longest query, is less than twice what any of its jobs needs), or
+// every longer query -- and at most 2 GiB of predecessor bytes (a single larger pair goes alone).
+#define SWG_TRACE_THREADS 256
+#define SWG_TRACE_LDS_COLS 1700 /* 9 * (cols + 1) * 4 bytes <= 60 KB */
+inline int swg_trace_class(uint32_t lq) { return lq > SWG_TRACE_LDS_COLS ? 0 : 32 - __builtin_clz(lq); }
+// One launch: jobs [b, e) of the launch order, the bytes its buffers need, its longest query.
+struct SwgTraceLaunch {
+    size_t b, e;
+    uint64_t dir, diag, ops;
+    uint32_t lq_max;
+};
+// The jobs of a checked batch in launch order (by query length, stable), dest[h] = job h's slot i*k + j of the batch, the
+// launches, the gathered residue indices, and the most bytes any launch needs of each buffer.
+struct SwgTracePlan {
+    std::vector<SwgTraceJob> jobs;
+    std::vector<size_t> dest;
+    std::vector<SwgTraceLaunch> launches;
+    std::vector<int8_t> res;
+    uint64_t max_dir = 4, max_diag = 4, max_ops = 4;
+};
+// ... for a call whose jobs own `paths` path slots of lq + len + 1 bytes each, which count against a launch's 2 GiB;
+// refuses what swg_trace_check_pairs refuses, with the same messages.  May throw (host vectors).
+int swg_trace_plan_batch(swg_ctx *ctx, const swg_db *db, const SwgTraceBatch &tb, size_t total, uint32_t paths, SwgTracePlan *plan);
 // The refusals of swg_trace_align_batch that depend on the database (a hit this shard does not hold, a pair outside what
 // a traceback holds), on their own: a caller that runs a batch in several calls refuses all of it first.
 int swg_trace_check_pairs(swg_ctx *ctx, const swg_db *db, const SwgTraceBatch &tb);

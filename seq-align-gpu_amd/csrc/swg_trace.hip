@@ -34,8 +34,7 @@ struct SwgTraceParams {
     int go, ge;
 };
 
-#define SWG_TRACE_THREADS 256
-#define SWG_TRACE_LDS_COLS 1700 /* 9 * (cols + 1) * 4 bytes <= 60 KB */
+// (SWG_TRACE_THREADS, SWG_TRACE_LDS_COLS: swg_host_internal.h, shared with swg_hsps.hip)
 
 // predecessor code of one state: 0 = the alignment starts here, 1/2/3 = came from H/A/B
 __device__ __forceinline__ uint32_t trace_pick(int32_t m, int32_t x, int32_t y)
@@ -180,22 +179,11 @@ extern "C" size_t swg_align_ops_bound_multi(const swg_db *db, const uint64_t *q_
 
 using TraceBatch = SwgTraceBatch; // (swg_host_internal.h: the bounds calls hand their fallback pairs over as one)
 
-// One launch: jobs [b, e) of the launch order, the bytes its buffers need, its longest query.
-struct TraceLaunch {
-    size_t b, e;
-    uint64_t dir, diag, ops;
-    uint32_t lq_max;
-};
-
-// A launch holds the queries of one class: one power-of-two range of lengths among those whose diagonals fit LDS (so
-// its dynamic LDS, sized by its longest query, is less than twice what any of its jobs needs), or every longer query.
-static int trace_class(uint32_t lq) { return lq > SWG_TRACE_LDS_COLS ? 0 : 32 - __builtin_clz(lq); }
-
-// Every hit of a checked batch (total > 0 hits): the shared body of all three entry points.  Device buffers are
-// allocated once per call; jobs are ordered by query length and cut into launches by class and by the 2 GiB budget of
-// predecessor bytes; each launch ends in one stream synchronisation, then its results are copied out.
-static int align_batch(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, size_t total, swg_alignment *out, char *ops,
-                       size_t ops_stride, const SwgTraceSink *sink)
+// The launches of a checked batch (total > 0 hits), and its refusals by the database: jobs are ordered by query length and
+// cut into launches by class (swg_trace_class) and by the 2 GiB budget of predecessor bytes.  paths: the path slots of lq + len + 1 bytes a
+// job owns (1: the traceback's one); paths_in_budget: they count against the launch's bytes as well (swg_align_hsps*).
+static int plan_batch(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, size_t total, uint32_t paths, bool paths_in_budget,
+                      SwgTracePlan &pl)
 {
     const char *fn = tb.fn;
     // original index -> slot of the sorted order, for the wanted sequences only
@@ -212,7 +200,7 @@ static int align_batch(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, siz
     std::vector<size_t> dest_in_order; // out[] index of each job
     in_order.reserve(total), dest_in_order.reserve(total);
     std::unordered_map<size_t, uint64_t> res_of; // slot -> its residues in `res` (a sequence is gathered once)
-    std::vector<int8_t> res;
+    std::vector<int8_t> &res = pl.res;
     for (size_t i = 0; i < tb.n_queries; ++i) {
         const size_t lq = (size_t)(tb.q_offsets[i + 1] - tb.q_offsets[i]);
         for (size_t j = 0; j < tb.n_hits[i]; ++j) {
@@ -243,20 +231,22 @@ static int align_batch(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, siz
     std::vector<size_t> perm(n);
     for (size_t h = 0; h < n; ++h) perm[h] = h;
     std::stable_sort(perm.begin(), perm.end(), [&](size_t a, size_t b) { return in_order[a].lq < in_order[b].lq; });
-    std::vector<SwgTraceJob> jobs(n);
-    std::vector<size_t> dest(n);
+    std::vector<SwgTraceJob> &jobs = pl.jobs;
+    std::vector<size_t> &dest = pl.dest;
+    jobs.resize(n), dest.resize(n);
     for (size_t h = 0; h < n; ++h) jobs[h] = in_order[perm[h]], dest[h] = dest_in_order[perm[h]];
-    std::vector<TraceLaunch> launches;
-    uint64_t max_dir = 4, max_diag = 4, max_ops = 4;
+    std::vector<SwgTraceLaunch> &launches = pl.launches;
+    uint64_t &max_dir = pl.max_dir, &max_diag = pl.max_diag, &max_ops = pl.max_ops;
     for (size_t b = 0; b < n;) {
         const uint64_t budget = 2ull << 30;
-        TraceLaunch L = {b, b, 0, 0, 0, 0};
+        SwgTraceLaunch L = {b, b, 0, 0, 0, 0};
         for (; L.e < n; ++L.e) {
             SwgTraceJob &jb = jobs[L.e];
-            const uint64_t need = (uint64_t)(jb.lq + jb.len - 1) * jb.lq;
-            if (L.e > b && (L.dir + need > budget || trace_class(jb.lq) != trace_class(jobs[b].lq))) break;
+            const uint64_t path_bytes = ((uint64_t)jb.lq + jb.len + 1) * paths;
+            const uint64_t need = (uint64_t)(jb.lq + jb.len - 1) * jb.lq, held = paths_in_budget ? L.ops + path_bytes : 0;
+            if (L.e > b && (L.dir + need + held > budget || swg_trace_class(jb.lq) != swg_trace_class(jobs[b].lq))) break;
             jb.dir_off = L.dir, jb.diag_off = L.diag, jb.ops_off = L.ops;
-            L.dir += need, L.diag += 9ull * (jb.lq + 1), L.ops += (uint64_t)jb.lq + jb.len + 1;
+            L.dir += need, L.diag += 9ull * (jb.lq + 1), L.ops += path_bytes;
             L.lq_max = std::max(L.lq_max, jb.lq);
         }
         max_dir = std::max(max_dir, L.dir), max_ops = std::max(max_ops, L.ops);
@@ -264,6 +254,29 @@ static int align_batch(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, siz
         launches.push_back(L);
         b = L.e;
     }
+    return SWG_OK;
+}
+
+int swg_trace_plan_batch(swg_ctx *ctx, const swg_db *db, const SwgTraceBatch &tb, size_t total, uint32_t paths, SwgTracePlan *plan)
+{
+    return plan_batch(ctx, db, tb, total, paths, true, *plan);
+}
+
+// Every hit of a checked batch (total > 0 hits): the shared body of all three entry points.  Device buffers are
+// allocated once per call; each launch of the plan ends in one stream synchronisation, then its results are copied out.
+static int align_batch(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, size_t total, swg_alignment *out, char *ops,
+                       size_t ops_stride, const SwgTraceSink *sink)
+{
+    const char *fn = tb.fn;
+    SwgTracePlan pl;
+    const int prc = plan_batch(ctx, db, tb, total, 1, false, pl);
+    if (prc != SWG_OK) return prc;
+    const std::vector<SwgTraceJob> &jobs = pl.jobs;
+    const std::vector<size_t> &dest = pl.dest;
+    const std::vector<SwgTraceLaunch> &launches = pl.launches;
+    const std::vector<int8_t> &res = pl.res;
+    const uint64_t max_dir = pl.max_dir, max_diag = pl.max_diag, max_ops = pl.max_ops;
+    const size_t n = jobs.size();
     const size_t row_bytes = tb.pssm ? 32 : 1;
     const size_t q_bytes = (size_t)(tb.q_offsets[tb.n_queries] - tb.q_offsets[0]) * row_bytes;
     std::vector<SwgTraceOut> h_out(n);
@@ -290,7 +303,7 @@ static int align_batch(swg_ctx *ctx, const swg_db *db, const TraceBatch &tb, siz
     if (!tb.pssm) TRACE_TRY(ctx, hipMemcpyAsync(d_sub, &ctx->sub[0][0], 1024, hipMemcpyHostToDevice, ctx->stream));
     TRACE_TRY(ctx, hipMemcpyAsync(d_res, res.data(), res.size(), hipMemcpyHostToDevice, ctx->stream));
     TRACE_TRY(ctx, hipMemcpyAsync(d_jobs, jobs.data(), n * sizeof(SwgTraceJob), hipMemcpyHostToDevice, ctx->stream));
-    for (const TraceLaunch &L : launches) {
+    for (const SwgTraceLaunch &L : launches) {
         const size_t nb = L.e - L.b;
         SwgTraceParams p;
         p.query = d_query, p.sub = d_sub, p.pssm = d_query, p.res = d_res, p.jobs = d_jobs + L.b, p.diag = d_diag, p.dir = d_dir;

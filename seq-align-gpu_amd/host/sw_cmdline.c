@@ -27,6 +27,9 @@
  *     --tabular with --topk K appends one tab-separated line per reported hit in the columns of BLAST's -outfmt 6 up to
  *     the coordinates, then the raw score (swg_align_stats, with --allqueries swg_align_stats_multi / _multi_pssm: the
  *     identities and gap openings come from the same forward pass, no traceback is run);
+ *     --maxhsps N with --align, --bounds or --tabular reports up to N non-overlapping alignments of every reported hit, of
+ *     score --hspscore S or more, best first, in those reports' own formats (swg_align_hsps, the records after the first
+ *     through swg_align_hsps_multi / _multi_pssm, a record per call);
  *     --minscore S reports every entry that scores at least S, best first, in --topk's block (swg_search_above: no score
  *     array, so no Entry lines), with --topk K the best K of them; under --gpus N each device searches its shard and the
  *     lists are merged by swg_hit_key;
@@ -90,6 +93,15 @@ static void usage(const char *argv0, const char *err)
             "                         send, score` and one tab-separated line per reported hit of positive score (identity in\n"
             "                         percent of the alignment's length, coordinates 1-based and inclusive, the raw score; a\n"
             "                         PSSM's identity is against its consensus); not with --align, --bounds, --gapless or --gpus\n"
+            "    --maxhsps <N>        with --align, --bounds or --tabular: up to N (1 to 64) alignments per reported hit instead of its best\n"
+            "                         one -- every non-overlapping local alignment of the pair (no aligned residue pair is shared;\n"
+            "                         a later alignment may cross an earlier one through a gap), best first, as blocks or lines of the\n"
+            "                         same format, a hit's own one after another under the hit's number; --tabular under --evalue gives\n"
+            "                         each line its own evalue and bitscore; works with --topk, --minscore, --minscorelist, --evalue,\n"
+            "                         --allqueries, --pssm and --pssmlist; not with --gapless, --gpus, --iterations, --candidates or\n"
+            "                         --prefilter\n"
+            "    --hspscore <S>       with --maxhsps: the least score (1 or more) of an alignment [default: --minscore's S, the record's\n"
+            "                         score of --minscorelist, the score --evalue's E becomes for the query, else 1]\n"
             "    --timing             wall time of every phase (reading, packing, upload, search, printing) on stderr\n"
             "    --gpu <N>            HIP device ordinal [default: 0]\n"
             "    --gpus <N>           shard the database over GPUs 0..N-1 (RCCL top-K merge)\n"
@@ -233,6 +245,40 @@ static int parse_int(const char *s, long lo, long hi, long *out)
     return 1;
 }
 
+/* --maxhsps: the alignments of one record's hits (swg_align_hsps*): hit i's r-th of n[i] at al / ct [i*per + r], its path
+ * at ops + (i*per + r)*stride.  One record per call: qoff == NULL takes the context's query, else src is the record's
+ * index bytes or (pssm) PSSM rows at qoff[0] .. qoff[1]. */
+struct hsps {
+    swg_alignment *al;
+    swg_align_counts *ct;
+    uint32_t *n;
+    char *ops;
+    size_t per, stride;
+};
+
+static int hsps_run(struct hsps *h, swg_ctx *ctx, const swg_db *sdb, const int8_t *src, int pssm, const uint64_t *qoff, const swg_hit *hits,
+                    size_t n_hits, long maxhsps, long least)
+{
+    free(h->al), free(h->ct), free(h->n), free(h->ops);
+    h->per = (size_t)maxhsps;
+    h->stride = qoff ? swg_align_ops_bound_multi(sdb, qoff, 1) : swg_align_ops_bound(ctx, sdb);
+    h->al = (swg_alignment *)calloc(n_hits * h->per, sizeof *h->al);
+    h->ct = (swg_align_counts *)calloc(n_hits * h->per, sizeof *h->ct);
+    h->n = (uint32_t *)calloc(n_hits, sizeof *h->n);
+    h->ops = (char *)malloc(n_hits * h->per * h->stride);
+    if (!h->al || !h->ct || !h->n || !h->ops) {
+        fprintf(stderr, "Error: out of memory\n");
+        return SWG_ERR_NOMEM;
+    }
+    const int rc = !qoff ? swg_align_hsps(ctx, sdb, hits, n_hits, (uint32_t)maxhsps, (int32_t)least, h->al, h->n, h->ct, h->ops, h->stride)
+                   : pssm ? swg_align_hsps_multi_pssm(ctx, sdb, src, qoff, 1, hits, n_hits, &n_hits, (uint32_t)maxhsps, (int32_t)least, h->al,
+                                                      h->n, h->ct, h->ops, h->stride)
+                          : swg_align_hsps_multi(ctx, sdb, src, qoff, 1, hits, n_hits, &n_hits, (uint32_t)maxhsps, (int32_t)least, h->al, h->n,
+                                                 h->ct, h->ops, h->stride);
+    if (rc != SWG_OK) fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
+    return rc;
+}
+
 static void die_illegal(char c)
 {
     /* reference src/alignment_scoring.c:78-79 */
@@ -294,6 +340,7 @@ int main(int argc, char **argv)
     const char *mslist_path = NULL;
     int print_seq = 0, print_fasta = 0, have_matrix = 0, packed = 0, allq = 0;
     long topk = 0, gpu = 0, gpus = 0, prefilter = 0, minscore = 0, v;
+    long maxhsps = 0, hspscore = 0;
     int align = 0, gapless = 0, bounds = 0, tabular = 0, have_evalue = 0, compfromdb = 0;
     double evalue = 0.0, inclusion = 0.002;
     long iterations = 0, maxincluded = 500;
@@ -383,6 +430,12 @@ int main(int argc, char **argv)
         } else if (!strcasecmp(a, "--minscore")) {
             if (!parse_int(argv[i + 1], 1, INT_MAX, &minscore)) usage(argv[0], "Invalid --minscore argument: the least score to report, 1 or more");
             i++;
+        } else if (!strcasecmp(a, "--maxhsps")) {
+            if (!parse_int(argv[i + 1], 1, SWG_MAX_HSPS, &maxhsps)) usage(argv[0], "Invalid --maxhsps argument: the most alignments per reported hit, 1 to 64");
+            i++;
+        } else if (!strcasecmp(a, "--hspscore")) {
+            if (!parse_int(argv[i + 1], 1, INT_MAX, &hspscore)) usage(argv[0], "Invalid --hspscore argument: the least score of an alignment, 1 or more");
+            i++;
         } else if (!strcasecmp(a, "--minscorelist")) {
             mslist_path = argv[++i];
         } else if (!strcasecmp(a, "--evalue")) {
@@ -451,6 +504,11 @@ int main(int argc, char **argv)
     }
     if (!qpath || !dbpath) usage(argv[0], "No input specified"); /* reference src/alignment_cmdline.c:303-305 */
     if (!have_matrix) usage(argv[0], "--substitution_matrix is required (the fill scores from the matrix only)");
+    if (maxhsps && !align && !bounds && !tabular)
+        usage(argv[0], "--maxhsps N reports up to N alignments per hit of --align, --bounds or --tabular: give one of them");
+    if (maxhsps && (gapless || gpus > 0 || iterations || cand_path || prefilter))
+        usage(argv[0], "--maxhsps does not combine with --gapless, --gpus, --iterations, --candidates or --prefilter");
+    if (hspscore && !maxhsps) usage(argv[0], "--hspscore is the least score of --maxhsps' alignments: give --maxhsps N");
     if (packed && (print_seq || print_fasta)) usage(argv[0], "--printseq/--printfasta need the FASTA database, not --packed");
     if (pssmlist_path && !allq) usage(argv[0], "--pssmlist names the PSSMs of --allqueries' records: give --allqueries");
     if (pssmlist_path && pssm_path) usage(argv[0], "--pssmlist and --pssm do not combine (the list names the first record's PSSM too)");
@@ -1163,6 +1221,7 @@ int main(int argc, char **argv)
     swg_alignment *mq_bd = NULL;
     swg_align_counts *mq_ct = NULL; /* --tabular: the counts beside them */
     size_t bd_first = 0, bd_n = 0;
+    struct hsps hs = {NULL, NULL, NULL, NULL, 1, 0}; /* --maxhsps: the current record's alignments (a later record's come with its results, below) */
 next_query:
     if (cands) { /* this record's entries: marks for the printing, scores by entry */
         if (qi > 0)
@@ -1218,7 +1277,11 @@ next_query:
             fprintf(stderr, "Error: %s\n", al_err);
             return leave(EXIT_FAILURE);
         }
-        if (sh_n) { /* --minscore --gpus N: every hit is aligned on the GPU that holds its shard */
+        if (maxhsps) { /* (the first record's against the context's query) */
+            if (qi == 0 && hsps_run(&hs, ctx, sdb, NULL, 0, NULL, hits, n_hits, maxhsps, hspscore ? hspscore : minscore ? minscore : 1) != SWG_OK)
+                return leave(EXIT_FAILURE);
+            stride = hs.stride;
+        } else if (sh_n) { /* --minscore --gpus N: every hit is aligned on the GPU that holds its shard */
             stride = 1;
             for (size_t g = 0; g < sh_n; g++) {
                 const size_t b = swg_align_ops_bound(sh_ctx[g], sh_sdb[g]);
@@ -1261,13 +1324,16 @@ next_query:
                 return leave(EXIT_FAILURE);
             }
         }
-        const swg_alignment *al_q = al ? al : mq_al + (qi - al_first) * (size_t)topk;
-        const char *ops_q = ops ? ops : mq_ops + (qi - al_first) * (size_t)topk * stride;
+        const swg_alignment *al_q = maxhsps ? hs.al : al ? al : mq_al + (qi - al_first) * (size_t)topk;
+        const char *ops_q = maxhsps ? hs.ops : ops ? ops : mq_ops + (qi - al_first) * (size_t)topk * stride;
         char *line = (char *)malloc(stride);
         if (!line) return leave(EXIT_FAILURE);
-        for (size_t i = 0; i < n_hits; i++) {
-            const swg_alignment *a = &al_q[i];
-            const char *o = ops_q + i * stride;
+        /* one block per hit; with --maxhsps hit i's hs.n[i] blocks one after another, all under the hit's number */
+        for (size_t e = 0; e < n_hits * hs.per; e++) {
+            const size_t i = e / hs.per;
+            if (maxhsps && e % hs.per >= hs.n[i]) continue;
+            const swg_alignment *a = &al_q[e];
+            const char *o = ops_q + e * stride;
             printf("Alignment #%lu: entry %u score %d query %u..%u entry %u..%u\n", (unsigned long)i, a->index,
                    a->score, a->q_begin, a->q_end, a->d_begin, a->d_end);
             if (packed) { /* no letters in a packed database: the path itself */
@@ -1291,7 +1357,10 @@ next_query:
         /* the first record against the context's query; the others came with their chunk (below) */
         swg_alignment *bd = NULL;
         swg_align_counts *ct = NULL;
-        if (qi == 0) {
+        if (maxhsps) { /* (--maxhsps --align is refused with either: this is the record's one call) */
+            if (qi == 0 && hsps_run(&hs, ctx, sdb, NULL, 0, NULL, hits, n_hits, maxhsps, hspscore ? hspscore : minscore ? minscore : 1) != SWG_OK)
+                return leave(EXIT_FAILURE);
+        } else if (qi == 0) {
             bd = (swg_alignment *)calloc(n_hits, sizeof *bd);
             ct = (swg_align_counts *)calloc(n_hits, sizeof *ct);
             if (!bd || !ct) return leave(EXIT_FAILURE);
@@ -1300,14 +1369,18 @@ next_query:
                 return leave(EXIT_FAILURE);
             }
         }
-        const swg_alignment *bd_q = bd ? bd : mq_bd + (qi - bd_first) * (size_t)topk;
-        const swg_align_counts *ct_q = bd ? ct : mq_ct + (qi - bd_first) * (size_t)topk;
-        for (size_t i = 0; i < n_hits && bounds; i++)
-            printf("Bounds #%lu: entry %u score %d query %u..%u entry %u..%u length %u\n", (unsigned long)i, bd_q[i].index,
-                   bd_q[i].score, bd_q[i].q_begin, bd_q[i].q_end, bd_q[i].d_begin, bd_q[i].d_end, bd_q[i].n_ops);
+        const swg_alignment *bd_q = maxhsps ? hs.al : bd ? bd : mq_bd + (qi - bd_first) * (size_t)topk;
+        const swg_align_counts *ct_q = maxhsps ? hs.ct : bd ? ct : mq_ct + (qi - bd_first) * (size_t)topk;
+        /* one line per hit; with --maxhsps hit e / hs.per's hs.n[] lines one after another (hs.per is 1 without it) */
+        for (size_t e = 0; e < n_hits * hs.per && bounds; e++) {
+            if (maxhsps && e % hs.per >= hs.n[e / hs.per]) continue;
+            printf("Bounds #%lu: entry %u score %d query %u..%u entry %u..%u length %u\n", (unsigned long)(e / hs.per), bd_q[e].index,
+                   bd_q[e].score, bd_q[e].q_begin, bd_q[e].q_end, bd_q[e].d_begin, bd_q[e].d_end, bd_q[e].n_ops);
+        }
         if (tabular && have_evalue) printf("# Fields: query, entry, pident, length, mismatch, gapopen, qstart, qend, sstart, send, evalue, bitscore, score\n");
         else if (tabular) printf("# Fields: query, entry, pident, length, mismatch, gapopen, qstart, qend, sstart, send, score\n");
-        for (size_t i = 0; i < n_hits && tabular; i++) {
+        for (size_t i = 0; i < n_hits * hs.per && tabular; i++) {
+            if (maxhsps && i % hs.per >= hs.n[i / hs.per]) continue;
             const swg_alignment *a = &bd_q[i];
             if (a->score <= 0) continue; /* no alignment: no line */
             if (have_evalue) { /* BLAST's twelve columns, then the raw score */
@@ -1433,7 +1506,14 @@ next_query:
         if (mslist) minscore = mslist[qi], n_above = mq_above[at];
         n_hits = mq_nhits[at];
         memcpy(hits, mq_hits + at * (topk ? (size_t)topk : 1), n_hits * sizeof(swg_hit));
-        if (align && qi >= al_first + al_n) {
+        if (maxhsps && n_hits > 0) { /* this record's alignments, against its own query or PSSM */
+            const double t0 = now_ms();
+            if (hsps_run(&hs, ctx, sdb, plist ? plist + (size_t)q.seq_off[chunk_first] * 32 : qx, plist != NULL, qoff + at, hits, n_hits, maxhsps,
+                         hspscore ? hspscore : minscore ? minscore : 1) != SWG_OK)
+                return leave(EXIT_FAILURE);
+            al_ms += now_ms() - t0, ++al_calls, ++al_records;
+        }
+        if (align && !maxhsps && qi >= al_first + al_n) {
             /* The alignments of the chunk's hits from this query on, in one swg_align_hits_multi call (with --pssmlist
              * swg_align_hits_multi_pssm: each record against its own PSSM).  A call takes at most 2^20 hits, and its
              * paths are kept to about 256 MB, so a chunk past either is aligned in several calls. */
@@ -1470,7 +1550,7 @@ next_query:
             }
             al_records += al_n;
         }
-        if ((bounds || tabular) && qi >= bd_first + bd_n) {
+        if ((bounds || tabular) && !maxhsps && qi >= bd_first + bd_n) {
             /* the coordinates of the chunk's hits from this query on, in one swg_align_bounds_multi call (with --pssmlist
              * swg_align_bounds_multi_pssm); a call takes at most 2^20 hits */
             const size_t left = chunk_first + chunk_n - qi, kk = (size_t)topk;
@@ -1552,6 +1632,10 @@ next_query:
     free(mq_al);
     free(mq_ops);
     free(mq_bd);
+    free(hs.al);
+    free(hs.ct);
+    free(hs.n);
+    free(hs.ops);
     phase("release (context, buffers)");
     return leave(EXIT_SUCCESS);
 }
