@@ -789,6 +789,78 @@ int swg_pssm_build_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssm
                               const double *freq, double pseudocount, int8_t *pssms_out, double *values_out,
                               swg_pssm_info *info);
 
+/* ---- composition-based score adjustment of reported hits -------------------------------------------------- */
+
+/* The calibration behind swg_evalue scores the query against random sequences of ONE background composition; a database
+ * sequence whose own composition is skewed the way the query's is scores far above what that predicts.  This is the
+ * correction PSI-BLAST applies ("composition-based statistics", Schaffer et al. 2001, its mode 1): the pair is scored
+ * again under scores scaled by the ratio of two ungapped lambdas.  It applies per query and per hit; the query is an
+ * index query or a PSSM.  DESIGN 8.7.
+ *   profile      R_p[a], p in 0..lq-1, a in 0..31: sub[q_p][a] for an index query, pssm[p*32 + a] for a PSSM.
+ *   background   freq as swg_pssm_build takes it (NULL: the built-in table; validated the same way);
+ *                A = {a in 1..31 : freq_a > 0}, P_a = freq_a / sum_A freq.
+ *   composition  c_a = the number of residues a in A in the WHOLE hit sequence, n = sum_A c_a; residues outside A (X, B,
+ *                Z, padding) are not counted.
+ *   distribution C[a][s] = the number of positions p with R_p[a] == s, s in -128..127.  Against the subject
+ *                h[s] = sum_{a in A} c_a C[a][s] (exact integers of total weight n lq); against the background
+ *                hP[s] = sum_{a in A} P_a C[a][s].
+ *   lambda       for weights w[s] of total W, lambda(w) is the positive root of sum_s w[s] exp(lambda s) = W; it exists
+ *                exactly when sum_s s w[s] < 0 and some w[s] > 0 with s > 0.  lambda_std = lambda(hP), lambda_hit = lambda(h).
+ *   ratio        r = min(1, max(0.5, lambda_hit / lambda_std)): scores are only ever scaled down, and by at most a half
+ *                (constants of this contract).  ratio16 = floor(r 65536 + 0.5), in 32768..65536.
+ *                n == 0, or either lambda does not exist: status 1, ratio16 = 65536.  The iteration does not converge in
+ *                100 steps: status 2, ratio16 = 65536.  Otherwise status 0.  (lambda_hit is 0 unless it was solved.)
+ *   rescaling    everything from here on is integer.  F = option "comp_scale", 1..64, default 32 (NCBI's scaling factor
+ *                of this step).  T[s] = floor((s F ratio16 + 32768) / 65536), floor toward minus infinity, s in
+ *                -128..127; |T| <= 8192, an int16.  The pair is scored by the library's recurrence unchanged (H, A and B
+ *                floored at 0, go = open + extend, any signs) with the substitution score T[R_p[d_j]] and the gap scores
+ *                F gap_open and F gap_extend -- the ratio does not scale the gaps --, in int32 cells.  scaled_score is
+ *                that maximum, adj_score = floor((2 scaled_score + F) / (2 F)).
+ * Consequences: ratio16 == 65536 gives T[s] = F s, scaled_score = F x (the pair's exact score) and adj_score = the exact
+ * score.  F = 1 makes T an int8 table, so any scorer of the recurrence can score the pair.  The adjusted E-value is
+ * swg_evalue(params, residues, adj_score) with the params of swg_calibrate on the same background.
+ * The solver, one iteration for host and device (csrc/swg_comp_rule.h): hi = 1 / (the highest populated score) doubled
+ * until the sum exceeds W, then Newton steps from hi, a step that leaves the bracket replaced by its middle; double
+ * arithmetic, a fixed order of additions, no fused multiply-add; it stops at |step| <= 1e-12 lambda.  lambda_std is
+ * solved once per query on the host, lambda_hit on the device from the exact integers h[s].
+ *
+ * swg_comp_adjust: the context's query (index or PSSM) against hits[n_hits]; only .index is read; hits in any order and
+ * repeated.  out[n_hits] is parallel to the hits.  A hit whose sequence this handle (shard, view) does not hold is NOT
+ * written and is no error, so the shards of one database fill one array between them; an index outside the whole
+ * database is SWG_ERR_ARG.  lambda_std: NULL or one double (0 where it does not exist).  The batch calls take the layout of
+ * swg_align_bounds_multi / _multi_pssm (row i's hits at hits[i*k .. i*k + n_hits[i]), out alike; slots past n_hits[i] are
+ * not written; lambda_std NULL or n_queries doubles) and neither read nor change the context's own query; row i equals
+ * swg_set_query(query i) + swg_comp_adjust.  The database must be resident (a view or a masked root is accepted: the
+ * composition is that of the bytes the handle holds).  Three kernels (csrc/swg_comp.hip): the count tables C per query,
+ * one workgroup per hit for composition, lambda_hit, ratio16 and the pair's table T, and a score-only lane-group fill
+ * that reads every score through T; results come back in one copy.  A query of more than 2048 columns goes through the
+ * host twin below inside the same call, with the same results.  Alignments, coordinates and counts (swg_align_*) stay
+ * those of the unadjusted scores.
+ * Errors, all before anything is launched: NULL arguments, a malformed freq, a pair whose cells could leave int32
+ * ((lq + len) F max(127, |gap_open + gap_extend|, |gap_extend|) >= 2^31): SWG_ERR_ARG; a database that is not resident
+ * or was built from 16-lane batches, no query or no scoring set, searches in flight on the context: SWG_ERR_STATE.
+ * n_hits = 0 returns SWG_OK.  Group forms (swg_group_*) are out of scope. */
+typedef struct swg_comp_result {
+    int32_t adj_score, scaled_score;
+    uint32_t ratio16;
+    int32_t status;
+    double lambda_hit;
+} swg_comp_result;
+int swg_comp_adjust(swg_ctx *ctx, const swg_db *db, const swg_hit *hits, size_t n_hits, const double *freq,
+                    swg_comp_result *out, double *lambda_std);
+int swg_comp_adjust_multi(swg_ctx *ctx, const swg_db *db, const int8_t *queries, const uint64_t *q_offsets, size_t n_queries,
+                          const swg_hit *hits, size_t k, const size_t *n_hits, const double *freq, swg_comp_result *out,
+                          double *lambda_std);
+int swg_comp_adjust_multi_pssm(swg_ctx *ctx, const swg_db *db, const int8_t *pssms, const uint64_t *q_offsets, size_t n_queries,
+                               const swg_hit *hits, size_t k, const size_t *n_hits, const double *freq, swg_comp_result *out,
+                               double *lambda_std);
+/* The host twin for one pair, in plain C++ (no GPU needed): exactly one of query (lq table indices 1..31, scored by sub)
+ * and pssm (lq rows of 32) is not NULL; seq holds len table indices 0..31; scale is F.  out: one record; lambda_std NULL
+ * or one double.  Errors are SWG_ERR_ARG / SWG_ERR_RESIDUE with swg_global_error() set. */
+int swg_comp_adjust_host(const int8_t sub[32][32], int gap_open, int gap_extend, const int8_t *query, const int8_t *pssm,
+                         size_t lq, const int8_t *seq, size_t len, const double *freq, int scale, swg_comp_result *out,
+                         double *lambda_std);
+
 /* ---- masking of low-complexity regions -------------------------------------------------------------------- */
 
 /* The rule: the trigger and extension stages of SEG (Wootton & Federhen 1993), decided in integers.  There is NO third

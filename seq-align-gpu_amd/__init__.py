@@ -40,7 +40,8 @@ ABI_SYMBOLS = [
     "swg_search_gapless_above_multi", "swg_search_gapless_above_multi_pssm", "swg_fill_batches16", "swg_align_hits", "swg_align_ops_bound", "swg_align_hits_multi",
     "swg_align_hits_multi_pssm", "swg_align_ops_bound_multi", "swg_align_bounds", "swg_align_bounds_multi",
     "swg_align_bounds_multi_pssm", "swg_align_stats", "swg_align_stats_multi", "swg_align_stats_multi_pssm", "swg_align_hsps",
-    "swg_align_hsps_multi", "swg_align_hsps_multi_pssm", "swg_align_hsps_host", "swg_hit_key",
+    "swg_align_hsps_multi", "swg_align_hsps_multi_pssm", "swg_align_hsps_host", "swg_comp_adjust", "swg_comp_adjust_multi",
+    "swg_comp_adjust_multi_pssm", "swg_comp_adjust_host", "swg_hit_key",
     "swg_key_hit", "swg_topk_merge_keys",
     "swg_group_create", "swg_group_destroy", "swg_group_size", "swg_group_last_error", "swg_group_set_option",
     "swg_group_set_scoring", "swg_group_set_query", "swg_group_set_query_pssm", "swg_group_load", "swg_group_search",
@@ -274,6 +275,11 @@ _sig("swg_align_hsps_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_
 _sig("swg_align_hsps_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, C.c_size_t])
 _sig("swg_align_hsps_host", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint32, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp])
 _sig("swg_debug_bounds_last", C.c_int, [_vp, _vp])
+_sig("swg_comp_adjust", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp])
+_sig("swg_comp_adjust_multi", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, _vp])
+_sig("swg_comp_adjust_multi_pssm", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, _vp])
+_sig("swg_comp_adjust_host", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_int, _vp, C.POINTER(C.c_double)])
+_sig("swg_debug_comp_last", C.c_int, [_vp, _vp])
 _sig("swg_debug_sort_count", C.c_ulong, [])
 _sig("swg_debug_engine", C.c_int, [_vp, C.c_size_t, C.c_int, C.c_int, _vp])
 _sig("swg_debug_plan", C.c_int, [_vp, C.c_size_t, C.c_int, _vp])
@@ -1057,6 +1063,39 @@ def align_hsps_host(sub, gap_open, gap_extend, seq, max_hsps, min_score=1, query
     return res
 
 
+# swg_comp_result, as a numpy record; COMP_UNWRITTEN is the status the Python layer puts into a record before the call, so
+# that a hit the handle does not hold (which the library does not write) can be told from one it adjusted
+COMP_DTYPE = np.dtype([("adj_score", "<i4"), ("scaled_score", "<i4"), ("ratio16", "<u4"), ("status", "<i4"), ("lambda_hit", "<f8")])
+COMP_UNWRITTEN = -1
+COMP_SCALE_DEFAULT = 32
+COMP_CLASSES = ((16, 4), (16, 8), (32, 8), (64, 8), (64, 16), (64, 32))     # the fill kernel's (lanes, columns per lane)
+COMP_COLS = 2048                                                           # its column limit: beyond it the host route
+
+
+def _comp_records(n):
+    out = np.zeros(max(n, 1), dtype=COMP_DTYPE)
+    out["status"] = COMP_UNWRITTEN
+    return out
+
+
+def comp_adjust_host(sub, gap_open, gap_extend, seq, query=None, pssm=None, freq=None, scale=COMP_SCALE_DEFAULT):
+    """Composition-based score adjustment of one pair on the host (swg_comp_adjust_host, the twin of Context.comp_adjust):
+    sub int8[32, 32], one of query (table indices) and pssm (int8[lq, 32]), seq table indices, freq the background (None:
+    the built-in table), scale the F of the rule -> (record of COMP_DTYPE, lambda_std)."""
+    t = np.ascontiguousarray(sub, dtype=np.int8) if sub is not None else None
+    q = np.ascontiguousarray(query, dtype=np.int8) if query is not None else None
+    p = np.ascontiguousarray(pssm, dtype=np.int8) if pssm is not None else None
+    d = np.ascontiguousarray(seq, dtype=np.int8)
+    lq = q.size if q is not None else (p.shape[0] if p is not None else 0)
+    f, fp = _freq(freq)
+    out = _comp_records(1)
+    lam = C.c_double(0.0)
+    _check(lib.swg_comp_adjust_host(t.ctypes.data_as(_vp) if t is not None else None, int(gap_open), int(gap_extend),
+                                    q.ctypes.data_as(_vp) if q is not None else None, p.ctypes.data_as(_vp) if p is not None else None, lq,
+                                    d.ctypes.data_as(_vp), d.size, fp, int(scale), out.ctypes.data_as(_vp), C.byref(lam)))
+    return out[0], lam.value
+
+
 def seg_mask(seq, window=12, trigger=2.2, extend=2.5, replace=MASK_REPLACE_DEFAULT, want_segments=False):
     """The low-complexity mask of one sequence of table indices (swg_seg_mask, the host twin of Database.mask): a bool
     array, True where the position is masked; with want_segments also the number of kept runs.  The sequence is not
@@ -1759,6 +1798,66 @@ class Context:
         qoff[1:] = np.cumsum([r.shape[0] for r in rows])
         pflat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 32)), dtype=np.int8)
         return self._align_multi(lib.swg_align_stats_multi_pssm, db, pflat, qoff, hits, False, None, bounds=True, stats=True)
+
+    def comp_adjust(self, db, hits, freq=None):
+        """Composition-based score adjustment of the context's query's hits [(score, index)] (swg_comp_adjust) -> (records
+        of COMP_DTYPE parallel to hits, lambda_std).  A hit the handle does not hold keeps status COMP_UNWRITTEN.  The scale
+        F is option "comp_scale"; alignments and counts stay those of the unadjusted scores."""
+        n = len(hits)
+        arr = (Hit * max(n, 1))()
+        for i, (sc, ix) in enumerate(hits):
+            arr[i].score, arr[i].index = int(sc), int(ix)
+        f, fp = _freq(freq)
+        out = _comp_records(n)
+        lam = np.zeros(1, dtype=np.float64)
+        _check(lib.swg_comp_adjust(self.handle, db.handle, C.cast(arr, _vp), n, fp, out.ctypes.data_as(_vp), lam.ctypes.data_as(_vp)),
+               self.handle)
+        return out[:n], float(lam[0])
+
+    def comp_adjust_multi(self, db, queries, hits, freq=None):
+        """comp_adjust for a batch: queries as search_multi takes them, hits one list of (score, index) per query -> (list of
+        record arrays, one per query, parallel to its hits; lambda_std float64[n_queries]).  The context's own query is
+        kept (swg_comp_adjust_multi)."""
+        qoff = np.zeros(len(queries) + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in queries])
+        qflat = np.ascontiguousarray(np.concatenate(queries) if len(queries) else np.zeros(1), dtype=np.int8)
+        return self._comp_multi(lib.swg_comp_adjust_multi, db, qflat, qoff, hits, freq)
+
+    def comp_adjust_multi_pssm(self, db, pssms, hits, freq=None):
+        """comp_adjust_multi with position-specific queries: pssms as search_multi_pssm takes them."""
+        rows = [_pssm(p)[0] for p in pssms]
+        qoff = np.zeros(len(rows) + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([r.shape[0] for r in rows])
+        pflat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((1, 32)), dtype=np.int8)
+        return self._comp_multi(lib.swg_comp_adjust_multi_pssm, db, pflat, qoff, hits, freq)
+
+    def _comp_multi(self, fn, db, qflat, qoff, hits, freq):
+        nq = len(qoff) - 1
+        if len(hits) != nq:
+            raise ValueError("hits: %d rows for %d queries" % (len(hits), nq))
+        k = max((len(row) for row in hits), default=0)
+        arr = (Hit * max(nq * k, 1))()
+        nh = (C.c_size_t * max(nq, 1))()
+        for i, row in enumerate(hits):
+            nh[i] = len(row)
+            for j, (sc, ix) in enumerate(row):
+                arr[i * k + j].score, arr[i * k + j].index = int(sc), int(ix)
+        f, fp = _freq(freq)
+        out = _comp_records(nq * k)
+        lam = np.zeros(max(nq, 1), dtype=np.float64)
+        _check(fn(self.handle, db.handle, qflat.ctypes.data_as(_vp), qoff.ctypes.data_as(_vp), nq, C.cast(arr, _vp), k, C.cast(nh, _vp), fp,
+                  out.ctypes.data_as(_vp), lam.ctypes.data_as(_vp)), self.handle)
+        return [out[i * k:i * k + len(row)].copy() for i, row in enumerate(hits)], lam[:nq]
+
+    def debug_comp_last(self):
+        """What the last comp_adjust* call of this context did (swg_debug_comp_last) -> dict: pairs on the fill kernel, pairs
+        on the host route, launches of the fill kernel, its column limit, the scale, and the pairs of each instantiation
+        (G, K), narrowest first."""
+        out = np.zeros(12, dtype=np.uint32)
+        _check(lib.swg_debug_comp_last(self.handle, out.ctypes.data_as(_vp)), self.handle)
+        res = dict(zip(("kernel_pairs", "host_pairs", "launches", "column_limit", "scale"), (int(v) for v in out[:5])))
+        res["class_pairs"] = dict(zip(COMP_CLASSES, (int(v) for v in out[5:11])))
+        return res
 
     def align_hsps(self, db, hits, max_hsps, min_score=1, want_ops=True, want_counts=False):
         """Every non-overlapping alignment of each hit at or above min_score, at most max_hsps of them, best first

@@ -436,6 +436,9 @@ extern "C" int swg_set_option(swg_ctx *ctx, const char *key, long value)
         if (value < 0) return swg_set_ctx_error(ctx, SWG_ERR_ARG, "workgroups must be >= 0");
         ctx->opt_workgroups = value;
     } else {
+        bool known = false; // (the options of swg_comp_adjust* are checked beside the calls that read them)
+        const int rc = swg_comp_set_option(ctx, key, value, &known);
+        if (known) return rc;
         return swg_set_ctx_error(ctx, SWG_ERR_ARG, "swg_set_option: unknown key '%s'", key);
     }
     return SWG_OK;

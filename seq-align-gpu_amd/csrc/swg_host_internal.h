@@ -727,6 +727,8 @@ struct swg_ctx {
     int next_slot = 0;
     long opt_pssm_blocks = 0;    // swg_pssm_build*: 1: per-column alignment blocks (option "pssm_blocks"); 0: the whole query is every column's block
     long opt_pssm_purge = 0;     // swg_pssm_build*: percent identity at which a hit is dropped, 50..100 (option "pssm_purge"); 0: no purge
+    long opt_comp_scale = 32;    // swg_comp_adjust*: the scale F of the rescaled scores, 1..64 (option "comp_scale")
+    uint32_t comp_last[12] = {}; // the last swg_comp_adjust* call (swg_debug_comp_last)
 };
 
 // Internal status (positive: never a public SWG_ERR_*): a database built from 16-lane batches has pair tokens only, and
@@ -938,6 +940,33 @@ int swg_pssm_check_model(const char *fn, const int8_t sub[32][32], const double 
 #define SWG_BOUNDS_COLS 1024         /* 64 lanes x 16 columns */
 #define SWG_BOUNDS_LEN (1u << 20)    /* a sequence below this many residues: the tag holds its origin in 20 bits */
 extern "C" int swg_debug_bounds_last(const swg_ctx *ctx, uint32_t out[4]);
+
+// swg_comp.hip / swg_comp_host.cpp: composition-based score adjustment (include/swg.h).
+// The option of the call family ("comp_scale"), checked and stored where the family lives: swg_set_option asks this about a
+// key it does not hold itself.  *known = whether the key is this family's; the return value is the call's when it is.
+int swg_comp_set_option(swg_ctx *ctx, const char *key, long value, bool *known);
+// Host side of the rule (no GPU).  swg_comp_counts: C[a][s + 128] of one query (index bytes scored by sub, or PSSM rows).
+// swg_comp_lambda_std: lambda(hP) -> status 0, 1 (does not exist), 2 (did not converge); *lambda is 0 unless 0 is returned.
+// swg_comp_pair: the whole rule for one pair from the query's count table, its lambda_std (with that status) and the
+// sequence's table indices.  swg_comp_pairs_host: the pairs the fill kernel cannot hold, on every core.
+#define SWG_COMP_COLS 2048 /* 64 lanes x 32 columns: the fill kernel's widest instantiation */
+void swg_comp_counts(const int8_t sub[32][32], const int8_t *query, const int8_t *pssm, size_t lq, uint32_t *C);
+int swg_comp_lambda_std(const uint32_t *C, const double P[32], uint32_t mask, double *lambda);
+void swg_comp_pair(const int8_t sub[32][32], int go, int ge, const int8_t *query, const int8_t *pssm, size_t lq, const uint32_t *C,
+                   uint32_t mask, double lambda_std, int std_status, const int8_t *seq, size_t len, int F, swg_comp_result *out);
+struct SwgCompHostPair {
+    size_t query, cq, dest; // the batch's query, its place among the queries that have hits (C, lambda_std, std_status), the slot of `out`
+    uint32_t index;     // the sequence's original index
+    size_t len;         // its length
+};
+bool swg_comp_pair_fits(size_t lq, size_t len, int go, int ge, int F); // the refusal of a pair whose int32 cells could wrap
+int swg_comp_pairs_host(const swg_db *db, const int8_t sub[32][32], int go, int ge, const int8_t *src, bool pssm,
+                        const uint64_t *q_offsets, const uint32_t *C, uint32_t mask, const double *lambda_std, const int *std_status,
+                        int F, const SwgCompHostPair *pairs, size_t n, swg_comp_result *out);
+// test hook: what the context's last swg_comp_adjust* call did -- out[0..11] = pairs on the fill kernel, pairs on the host
+// route, launches of the fill kernel, its column limit, the scale F, then the pairs of each of its six instantiations,
+// narrowest first, and 0
+extern "C" int swg_debug_comp_last(const swg_ctx *ctx, uint32_t out[12]);
 
 // swg_diag_host.cpp (host only)
 // geometry of both classes for one query length on one device; returns the number of

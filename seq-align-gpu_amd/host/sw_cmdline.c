@@ -45,7 +45,11 @@
  *     --inclusion's E-value into a least score, collects up to --maxincluded hits at or above it (swg_search_above), builds
  *     their PSSM on the device (swg_pssm_build) and makes it the query; the last iteration is the report above with that
  *     PSSM as the query, and --out_pssm writes it in the layout --pssm reads; --psiblocks and --purge P set the
- *     construction's options "pssm_blocks" and "pssm_purge" (per-column blocks, near-identical hits dropped).
+ *     construction's options "pssm_blocks" and "pssm_purge" (per-column blocks, near-identical hits dropped); --compstats [F]
+ *     scores every entry an iteration would include again under its composition-adjusted scores (swg_comp_adjust) and
+ *     keeps it only if the E-value of the adjusted score is within --inclusion; in the reports it ranks --topk's hits again
+ *     by adjusted score (both scores printed), keeps --evalue's hits by the adjusted E-value and prints --tabular's evalue,
+ *     bitscore and score columns adjusted (comp_rerank below; swg_comp_adjust_multi / _multi_pssm under --allqueries).
  * There is no CPU backend: without a GPU the tool fails with a message.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -148,6 +152,17 @@ static void usage(const char *argv0, const char *err)
             "    --out_pssm <file>    with --iterations: write the last PSSM (readable by --pssm)\n"
             "    --psiblocks          with --iterations: PSI-BLAST's per-column alignment blocks (option pssm_blocks) instead of one block,\n"
             "                         the whole query, for every column\n"
+            "    --compstats [F]      composition-based score adjustment of the reported hits (swg_comp_adjust, PSI-BLAST's\n"
+            "                         composition-based statistics): each is scored again under scores scaled by the ratio of the\n"
+            "                         ungapped lambdas of its own composition and of the background, at scale F (1 to 64) [default: 32].\n"
+            "                         --topk K: the K hits are ranked again by adjusted score (ties: the lower entry) and the block prints\n"
+            "                         `adjusted score, score, entry, name`; --evalue E: the unadjusted cut finds the candidates, a hit is\n"
+            "                         kept only if the E-value of its ADJUSTED score is within E; --tabular: the evalue, bitscore and\n"
+            "                         score columns are the adjusted ones; --iterations N: an entry is included only if the E-value of\n"
+            "                         its adjusted score is within --inclusion (the entries that leave are named on stderr); works\n"
+            "                         with --allqueries, --pssm, --pssmlist and --seqidlist; not with --gapless, --gpus, --candidates,\n"
+            "                         --prefilter or --maxhsps, nor where there is nothing to adjust (the plain Entry lines).\n"
+            "                         Alignments, bounds and counts stay those of the unadjusted scores\n"
             "    --purge <P>          with --iterations: drop a hit that is P percent (50 to 100; PSI-BLAST: 94) identical to a kept hit, or\n"
             "                         identical to the query, before the PSSM is built (option pssm_purge)\n"
             "    --prefilter <N>      with --topk K: per query (every record with --allqueries) the N best entries by gapless\n"
@@ -279,6 +294,41 @@ static int hsps_run(struct hsps *h, swg_ctx *ctx, const swg_db *sdb, const int8_
     return rc;
 }
 
+/* --compstats: the hits of nq records -- row r's at hits[r*k .. r*k + nh[r]) -- scored again under their composition-adjusted
+ * scores (swg_comp_adjust for the context's query when src is NULL, else the batch call), adj[r*k + j] beside hit j of row r.
+ * ev != NULL: a hit stays only if the E-value of its adjusted score, by its record's fit, is within E.  Each row is then
+ * ranked by adjusted score, ties by the lower entry.  The hits keep their unadjusted scores. */
+static int comp_rerank(swg_ctx *ctx, const swg_db *sdb, long F, const int8_t *src, int pssm, const uint64_t *qoff, size_t nq, swg_hit *hits,
+                       size_t k, size_t *nh, const double *freq, int32_t *adj, const swg_evalue_params *ev, uint64_t residues, double E)
+{
+    size_t total = 0;
+    for (size_t r = 0; r < nq; r++) total += nh[r];
+    if (total == 0) return SWG_OK;
+    swg_comp_result *cr = (swg_comp_result *)calloc(nq * k, sizeof *cr);
+    if (!cr) return SWG_ERR_NOMEM;
+    int rc = swg_set_option(ctx, "comp_scale", F);
+    if (rc == SWG_OK)
+        rc = !src ? swg_comp_adjust(ctx, sdb, hits, nh[0], freq, cr, NULL)
+                  : pssm ? swg_comp_adjust_multi_pssm(ctx, sdb, src, qoff, nq, hits, k, nh, freq, cr, NULL)
+                         : swg_comp_adjust_multi(ctx, sdb, src, qoff, nq, hits, k, nh, freq, cr, NULL);
+    for (size_t r = 0; rc == SWG_OK && r < nq; r++) {
+        swg_hit *h = hits + r * k;
+        int32_t *a = adj + r * k;
+        size_t kept = 0;
+        for (size_t j = 0; j < nh[r]; j++) {
+            const int32_t s = cr[r * k + j].adj_score;
+            if (ev && swg_evalue(&ev[r], residues, s) > E) continue;
+            const swg_hit moved = h[j]; /* (read before the shift below, which may write slot j) */
+            size_t at = kept++;         /* insertion: the rows are short and nearly in order already */
+            for (; at > 0 && (a[at - 1] < s || (a[at - 1] == s && h[at - 1].index > moved.index)); at--) h[at] = h[at - 1], a[at] = a[at - 1];
+            h[at] = moved, a[at] = s;
+        }
+        nh[r] = kept;
+    }
+    free(cr);
+    return rc;
+}
+
 static void die_illegal(char c)
 {
     /* reference src/alignment_scoring.c:78-79 */
@@ -344,6 +394,7 @@ int main(int argc, char **argv)
     int align = 0, gapless = 0, bounds = 0, tabular = 0, have_evalue = 0, compfromdb = 0;
     double evalue = 0.0, inclusion = 0.002;
     long iterations = 0, maxincluded = 500;
+    long compstats = 0; /* --compstats [F]: the scale of the composition-based adjustment, 0 = off */
     int have_inclusion = 0, have_maxincluded = 0, psiblocks = 0;
     long purge = 0;
     const char *out_pssm = NULL;
@@ -378,6 +429,13 @@ int main(int argc, char **argv)
             compfromdb = 1;
         } else if (!strcasecmp(a, "--psiblocks")) {
             psiblocks = 1;
+        } else if (!strcasecmp(a, "--compstats")) { /* the scale is optional: a number 1 to 64 behind the flag is taken as it */
+            long f;
+            compstats = 32;
+            if (i + 1 < argc && parse_int(argv[i + 1], LONG_MIN, LONG_MAX, &f)) { /* (any whole number behind the flag is meant as F) */
+                if (f < 1 || f > 64) usage(argv[0], "Invalid --compstats argument: the scale F of the adjusted scores, 1 to 64");
+                compstats = f, i++;
+            }
         } else if (!strcasecmp(a, "--timing")) {
             timing = 1;
         } else if (!strcasecmp(a, "--allqueries")) {
@@ -520,6 +578,11 @@ int main(int argc, char **argv)
     if (compfromdb && !have_evalue && !iterations) usage(argv[0], "--compfromdb chooses the background of --evalue's calibration: give --evalue E");
     if (!iterations && (have_inclusion || have_maxincluded || out_pssm))
         usage(argv[0], "--inclusion, --maxincluded and --out_pssm belong to the iterated search: give --iterations N");
+    if (compstats && !iterations && topk == 0 && !minscore && !have_evalue && !mslist_path)
+        usage(argv[0], "--compstats adjusts the scores of reported hits: give --topk K, --evalue E, --minscore S or --iterations N (the plain "
+                       "Entry lines have nothing to adjust)");
+    if (compstats && (gapless || gpus > 0 || cand_path || prefilter || maxhsps))
+        usage(argv[0], "--compstats does not combine with --gapless, --gpus, --candidates, --prefilter or --maxhsps");
     if (!iterations && psiblocks) usage(argv[0], "--psiblocks chooses the model of the iterated search's PSSM: give --iterations N");
     if (!iterations && purge) usage(argv[0], "--purge drops near-identical hits from the iterated search's PSSM: give --iterations N");
     if (iterations && allq) usage(argv[0], "--iterations iterates one query record: it does not combine with --allqueries");
@@ -889,6 +952,8 @@ int main(int argc, char **argv)
     /* --minscore without --topk: room for every entry searched */
     const size_t hit_cap = topk ? (size_t)topk : minscore ? (ids ? n_ids : db.n) : 0;
     swg_hit *hits = (swg_hit *)calloc(hit_cap ? hit_cap : 1, sizeof(swg_hit));
+    int32_t *adj = (int32_t *)calloc(hit_cap ? hit_cap : 1, sizeof(int32_t)); /* --compstats: the adjusted scores beside the current record's hits */
+    double comp_freq[32];                                                     /* ... and its background under --compfromdb */
     if (!scores || !hits) {
         fprintf(stderr, "Error: out of memory\n");
         return leave(EXIT_FAILURE);
@@ -1107,6 +1172,7 @@ int main(int argc, char **argv)
             if (!inc || !was || !iter_pssm) return leave(EXIT_FAILURE);
             if (rc == SWG_OK && psiblocks) rc = swg_set_option(ctx, "pssm_blocks", 1);
             if (rc == SWG_OK && purge) rc = swg_set_option(ctx, "pssm_purge", purge);
+            if (rc == SWG_OK && compstats) rc = swg_set_option(ctx, "comp_scale", compstats);
             for (long it = 1; rc == SWG_OK && it < iterations; it++) {
                 swg_evalue_params p;
                 size_t n_inc = 0, n_new = 0;
@@ -1121,6 +1187,26 @@ int main(int argc, char **argv)
                 }
                 rc = swg_search_above(ctx, sdb, least, inc, (size_t)maxincluded, &n_inc, &n_at, NULL);
                 if (rc != SWG_OK) break;
+                if (compstats && n_inc) { /* an entry stays only if the E-value of its ADJUSTED score is within --inclusion */
+                    swg_comp_result *cr = (swg_comp_result *)malloc(n_inc * sizeof *cr);
+                    if (!cr) return leave(EXIT_FAILURE);
+                    rc = swg_comp_adjust(ctx, sdb, inc, n_inc, compfromdb ? freq : NULL, cr, NULL);
+                    size_t kept = 0;
+                    for (size_t h = 0; rc == SWG_OK && h < n_inc; h++) {
+                        const double e = swg_evalue(&p, swg_db_residues(sdb), cr[h].adj_score);
+                        if (e <= inclusion) {
+                            inc[kept++] = inc[h];
+                            continue;
+                        }
+                        fprintf(stderr, "iteration %ld: entry %u leaves by its composition: score %d adjusted to %d (ratio %.4f), E-value %g\n", it,
+                                inc[h].index, inc[h].score, cr[h].adj_score, cr[h].ratio16 / 65536.0, e);
+                    }
+                    free(cr);
+                    if (rc != SWG_OK) break;
+                    fprintf(stderr, "iteration %ld: %lu of %lu entries stay after the composition-based adjustment\n", it, (unsigned long)kept,
+                            (unsigned long)n_inc);
+                    n_inc = kept;
+                }
                 for (size_t h = 0; h < n_inc; h++) n_new += !was[inc[h].index];
                 fprintf(stderr, "iteration %ld: %lu entries at or above score %d (E-value %g), %lu included, %lu of them new\n", it,
                         (unsigned long)n_at, least, inclusion, (unsigned long)n_inc, (unsigned long)n_new);
@@ -1201,6 +1287,21 @@ int main(int argc, char **argv)
             return leave(EXIT_FAILURE);
         }
         total_ms = st.total_ms;
+        if (compstats) { /* the first record's hits, against the context's query */
+            uint64_t counts[32];
+            if (!adj) return leave(EXIT_FAILURE);
+            if (compfromdb && swg_db_composition(ctx, sdb, counts) != SWG_OK) {
+                fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
+                return leave(EXIT_FAILURE);
+            }
+            for (int r = 0; r < 32; r++) comp_freq[r] = compfromdb ? (double)counts[r] : 0.0;
+            if (comp_rerank(ctx, sdb, compstats, NULL, 0, NULL, 1, hits, hit_cap ? hit_cap : 1, &n_hits, compfromdb ? comp_freq : NULL, adj,
+                            have_evalue ? ev : NULL, ev_residues, evalue) != SWG_OK) {
+                fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
+                return leave(EXIT_FAILURE);
+            }
+            phase("composition-based adjustment (first record)");
+        }
     }
 
     /* reference src/tools/sw_cmdline.c:38-75: per 16 records the query lines, then per record */
@@ -1264,9 +1365,15 @@ next_query:
                (unsigned long long)ev_residues);
     if (minscore) printf("Entries at or above %ld: %llu\n", minscore, (unsigned long long)n_above);
     if (topk > 0 || minscore) {
-        printf("Top %lu hits (score, entry, name):\n", (unsigned long)n_hits);
-        for (size_t i = 0; i < n_hits; i++)
-            printf("%d\t%u\t%s\n", hits[i].score, hits[i].index, packed ? "" : db.names + db.name_off[hits[i].index]);
+        if (compstats) { /* ranked by adjusted score; both scores */
+            printf("Top %lu hits (adjusted score, score, entry, name):\n", (unsigned long)n_hits);
+            for (size_t i = 0; i < n_hits; i++)
+                printf("%d\t%d\t%u\t%s\n", adj[i], hits[i].score, hits[i].index, packed ? "" : db.names + db.name_off[hits[i].index]);
+        } else {
+            printf("Top %lu hits (score, entry, name):\n", (unsigned long)n_hits);
+            for (size_t i = 0; i < n_hits; i++)
+                printf("%d\t%u\t%s\n", hits[i].score, hits[i].index, packed ? "" : db.names + db.name_off[hits[i].index]);
+        }
     }
     if (align && n_hits > 0) {
         /* the first record against the context's query; the others were aligned with their chunk (below) */
@@ -1383,15 +1490,18 @@ next_query:
             if (maxhsps && i % hs.per >= hs.n[i / hs.per]) continue;
             const swg_alignment *a = &bd_q[i];
             if (a->score <= 0) continue; /* no alignment: no line */
+            /* --compstats: the score columns are the adjusted ones (line i is hit i: --maxhsps is refused beside it); the
+             * coordinates and counts stay those of the unadjusted alignment */
+            const int32_t shown = compstats ? adj[i] : a->score;
             if (have_evalue) { /* BLAST's twelve columns, then the raw score */
                 printf("%s\t%s\t%.2f\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%.3g\t%.1f\t%d\n", qname, packed ? "" : db.names + db.name_off[a->index],
                        100.0 * ct_q[i].n_ident / a->n_ops, a->n_ops, ct_q[i].n_match - ct_q[i].n_ident, ct_q[i].n_gap_open, a->q_begin + 1,
-                       a->q_end, a->d_begin + 1, a->d_end, swg_evalue(&ev[qi], ev_residues, a->score), swg_bitscore(&ev[qi], a->score), a->score);
+                       a->q_end, a->d_begin + 1, a->d_end, swg_evalue(&ev[qi], ev_residues, shown), swg_bitscore(&ev[qi], shown), shown);
                 continue;
             }
             printf("%s\t%s\t%.2f\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%d\n", qname, packed ? "" : db.names + db.name_off[a->index],
                    100.0 * ct_q[i].n_ident / a->n_ops, a->n_ops, ct_q[i].n_match - ct_q[i].n_ident, ct_q[i].n_gap_open,
-                   a->q_begin + 1, a->q_end, a->d_begin + 1, a->d_end, a->score);
+                   a->q_begin + 1, a->q_end, a->d_begin + 1, a->d_end, shown);
         }
         free(bd);
         free(ct);
@@ -1404,6 +1514,7 @@ next_query:
         static int32_t *mq_scores = NULL;
         static swg_hit *mq_hits = NULL;
         static size_t *mq_nhits = NULL;
+        static int32_t *mq_adj = NULL; /* --compstats: the adjusted scores beside mq_hits */
         static uint64_t *mq_above = NULL; /* --minscorelist: every record's entries at or above its score */
         static size_t chunk_first = 0, chunk_n = 0;
         static double chunk_ms = 0.0;
@@ -1428,6 +1539,9 @@ next_query:
             mq_scores = (int32_t *)calloc(cands || mslist ? 1 : chunk_n * (db.n ? db.n : 1), sizeof(int32_t)); /* (--candidates: lsc) */
             mq_hits = (swg_hit *)calloc(chunk_n * (topk ? (size_t)topk : 1), sizeof(swg_hit));
             mq_nhits = (size_t *)calloc(chunk_n, sizeof(size_t));
+            free(mq_adj);
+            mq_adj = (int32_t *)calloc(chunk_n * (topk ? (size_t)topk : 1), sizeof(int32_t));
+            if (!mq_adj) return leave(EXIT_FAILURE);
             if (!qx || !qoff || !mq_scores || !mq_hits || !mq_nhits || !mq_above) return leave(EXIT_FAILURE);
             for (size_t i = 0; i <= chunk_n; i++) qoff[i] = q.seq_off[chunk_first + i] - q.seq_off[chunk_first];
             for (size_t i = 0; i < chunk_n; i++) {
@@ -1496,6 +1610,12 @@ next_query:
                 fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
                 return leave(EXIT_FAILURE);
             }
+            if (compstats && comp_rerank(ctx, sdb, compstats, plist ? plist + (size_t)q.seq_off[chunk_first] * 32 : qx, plist != NULL, qoff, chunk_n,
+                                         mq_hits, topk ? (size_t)topk : 1, mq_nhits, compfromdb ? comp_freq : NULL, mq_adj,
+                                         have_evalue ? ev + chunk_first : NULL, ev_residues, evalue) != SWG_OK) {
+                fprintf(stderr, "Error: %s\n", swg_last_error(ctx));
+                return leave(EXIT_FAILURE);
+            }
             chunk_ms = st.total_ms / (double)chunk_n; /* the chunk's device time, shared out over its queries */
             if (timing)
                 fprintf(stderr, "[timing] %lu queries in one pass: %.3f ms of fill, %.1f GCUPS\n", (unsigned long)chunk_n,
@@ -1506,6 +1626,7 @@ next_query:
         if (mslist) minscore = mslist[qi], n_above = mq_above[at];
         n_hits = mq_nhits[at];
         memcpy(hits, mq_hits + at * (topk ? (size_t)topk : 1), n_hits * sizeof(swg_hit));
+        if (compstats) memcpy(adj, mq_adj + at * (topk ? (size_t)topk : 1), n_hits * sizeof(int32_t));
         if (maxhsps && n_hits > 0) { /* this record's alignments, against its own query or PSSM */
             const double t0 = now_ms();
             if (hsps_run(&hs, ctx, sdb, plist ? plist + (size_t)q.seq_off[chunk_first] * 32 : qx, plist != NULL, qoff + at, hits, n_hits, maxhsps,
