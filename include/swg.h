@@ -927,6 +927,77 @@ int swg_db_mask(swg_ctx *ctx, const swg_db *parent, const swg_mask_params *p, sw
  * file included, which is an ordinary root whatever it was saved from --: SWG_ERR_STATE. */
 int swg_db_mask_info(const swg_db *db, swg_mask_info *out);
 
+/* ---- translated search: the six frames of a nucleotide database ------------------------------------------------ */
+
+/* The rule.  A nucleotide database is an ordinary database packed from nucleotide letters (residue index = position of
+ * the letter: swg_letter_index).  A residue index names a BASE with a 2-bit code, in NCBI's TCAG order:
+ *     20 (T) or 21 (U) -> 0,   3 (C) -> 1,   1 (A) -> 2,   7 (G) -> 3,   anything else (N, IUPAC codes, '*', 0) -> no base.
+ * The three bit planes below give, at bit `index`, the low and the high bit of the code and whether there is a base;
+ * the kernel and the host twin read the same three words.  The complement of code c is c ^ 2 (T <-> A, C <-> G).
+ *   A codon of bases b1 b2 b3 translates to codon[16 b1 + 4 b2 + b3] (a residue index 1..31; 31 = '*' is a stop); a
+ *   codon with any position that is no base translates to `unknown` (default 24 = X).  An ambiguous codon that still
+ *   names one amino acid (GCN) is NOT resolved.
+ *   For a sequence of L nucleotides, frame f = 0, 1, 2 reads the codons that start at f, f + 3, ... of the forward
+ *   strand and frame 3 + f the same offsets of the reverse complement; both have (L - f) / 3 residues (0 when
+ *   L - f < 3): a trailing partial codon is dropped, and a stop is a residue in place -- it does not split the frame.
+ *   Frame g (0..5) of the sequence with original index i is the sequence with original index 6 i + g. */
+#define SWG_NT_PLANE_LO 0x00000088u   /* bit 0 of the code: C (3), G (7) */
+#define SWG_NT_PLANE_HI 0x00000082u   /* bit 1 of the code: A (1), G (7) */
+#define SWG_NT_PLANE_BASE 0x0030008Au /* a base at all: A, C, G, T (20), U (21) */
+#define SWG_TRANSLATE_UNKNOWN_DEFAULT 24 /* swg_letter_index('X') */
+typedef struct swg_translate_params {
+    int8_t codon[64]; /* residue index (1..31) of codon 16 b1 + 4 b2 + b3, TCAG order */
+    int8_t unknown;   /* residue index (1..31) of a codon with a position that is no base */
+} swg_translate_params;
+/* NCBI genetic codes 1, 2, 3, 4, 5, 6 and 11 with unknown = X; any other id: SWG_ERR_ARG (a caller with another code
+ * fills the struct).  Host only. */
+int swg_codon_table(int ncbi_id, swg_translate_params *out);
+/* The host twin: the six frames of nt[nt_len] (residue indices 0..31).  out[g] must have room for nt_len / 3 residues;
+ * len_out[g] is frame g's length.  p NULL: code 1.  SWG_ERR_ARG: NULL arguments, a table entry or unknown outside
+ * 1..31. */
+int swg_translate_seq(const int8_t *nt, size_t nt_len, const swg_translate_params *p, int8_t *out[6], size_t len_out[6]);
+/* The same over a whole database laid end to end, on every core: sequence i is flat[offsets[i] .. offsets[i+1]); frame
+ * g of sequence i becomes sequence 6 i + g of out_flat / out_offsets[6 n + 1].  out_flat needs room for
+ * 2 (offsets[n] - offsets[0]) residues.  What a caller without swg_db_translate does in front of swg_db_pack. */
+int swg_translate_flat(const int8_t *flat, const uint64_t *offsets, size_t n, const swg_translate_params *p, int8_t *out_flat,
+                       uint64_t *out_offsets);
+/* A hit of a translated database back to the nucleotide record: index = 6 nt_index + frame, frame 0..5 (0..2 forward,
+ * 3..5 = offsets 0..2 of the reverse complement; BLAST writes them +1 +2 +3 -1 -2 -3).  Pure arithmetic. */
+void swg_translate_hit(uint32_t index, uint32_t *nt_index, int *frame);
+/* The nucleotides a residue range of a frame covers.  [d_begin, d_end) is 0-based and half-open in the frame's residues,
+ * as swg_alignment gives it; the answer is 0-based and half-open on the FORWARD strand, nt_begin < nt_end:
+ *     frame f:      [f + 3 d_begin, f + 3 d_end)          frame 3 + f:  [L - f - 3 d_end, L - f - 3 d_begin)
+ * with L = nt_len, the length of the nucleotide record.  An alignment of score 0 has n_ops = 0 and the empty range
+ * d_begin = d_end: it covers no nucleotide and is SWG_ERR_ARG here, as are a frame outside 0..5 and a range that ends
+ * past the frame's (L - f) / 3 residues. */
+int swg_translate_coords(int frame, uint32_t nt_len, uint32_t d_begin, uint32_t d_end, uint32_t *nt_begin, uint32_t *nt_end);
+
+/* The six-frame translation of a resident NUCLEOTIDE database, made on the device: *out is an ordinary packed, resident
+ * ROOT database of 6 x the parent's sequences -- frame g of the parent's original index i has original index 6 i + g,
+ * swg_db_total_count is 6 x the parent's -- indistinguishable from swg_db_pack + swg_db_upload of the host twin's
+ * frames given in index order: the same order (length descending, stable), bins, offsets and residue bytes, fill bytes
+ * included.  Every call that takes a swg_db takes it unchanged (searches, batches, PSSMs, lists, alignments,
+ * statistics, calibration, swg_db_mask, swg_db_view).  The host builds the slot tables from the parent's lengths alone
+ * and uploads them with one word per (parent slot, frame) that says where the frame goes: tens of bytes per translated
+ * sequence and never a residue.  One kernel writes the residue bytes from the parent's resident ones; ONE
+ * device-to-host copy then makes the host image.  Nothing is shared with the parent: either may be freed first.
+ * Refusals, all before anything is launched: parent a view: SWG_ERR_ARG (translate the root and take the view of the
+ * result: its indices are 6 i + g); parent not resident on ctx's device, or built from 16-lane batches: SWG_ERR_STATE;
+ * a table entry or unknown outside 1..31, or a parent with 6 x total count >= 0xFFFFFFF0: SWG_ERR_ARG.  A shard is a
+ * root: its frames keep 6 x the global index + g.  A masked root is accepted.  p NULL: code 1. */
+typedef struct swg_translate_info {
+    swg_translate_params params;
+    uint64_t codons;         /* residues written: the sum of the six frames' lengths */
+    uint64_t stops;          /* codons of three bases that the table sends to 31 ('*') */
+    uint64_t unknown_codons; /* codons with a position that is no base */
+    double kernel_ms;        /* the kernel, from HIP events */
+    double host_image_ms;    /* the device-to-host copy of the bytes that makes the host image (wall clock) */
+} swg_translate_info;
+int swg_db_translate(swg_ctx *ctx, const swg_db *parent, const swg_translate_params *p, swg_db **out);
+/* What swg_db_translate made `db` with and what it wrote; any other database -- a saved translation that was loaded
+ * again included, which is the ordinary root it was saved as --: SWG_ERR_STATE. */
+int swg_db_translate_info(const swg_db *db, swg_translate_info *out);
+
 /* ---- multi-GPU merge -------------------------------------------------- */
 
 /* 64-bit sort key of a hit: (score << 32) | (0xFFFFFFFF - index).  Larger key =

@@ -55,6 +55,8 @@ ABI_SYMBOLS = [
     "swg_matrix_lambda", "swg_pssm_from_paths", "swg_pssm_from_paths_ex", "swg_pssm_save", "swg_pssm_build", "swg_pssm_build_multi", "swg_pssm_build_multi_pssm",
     "swg_mask_params_default", "swg_mask_tables", "swg_seg_mask", "swg_seg_mask_segments", "swg_db_sequence", "swg_db_mask",
     "swg_db_mask_info", "swg_seg_mask_flat",
+    "swg_codon_table", "swg_translate_seq", "swg_translate_flat", "swg_translate_hit", "swg_translate_coords", "swg_db_translate",
+    "swg_db_translate_info",
 ]
 
 
@@ -128,6 +130,25 @@ class MaskInfo(C.Structure):
 
 
 MASK_REPLACE_DEFAULT = 24  # swg_letter_index('X')
+
+
+class TranslateParams(C.Structure):
+    """swg_translate_params: the residue index of each of the 64 codons (TCAG order) and of a codon with a non-base."""
+    _fields_ = [("codon", C.c_int8 * 64), ("unknown", C.c_int8)]
+
+
+class TranslateInfo(C.Structure):
+    """swg_translate_info: what swg_db_translate made a database with, what it wrote, and what it took."""
+    _fields_ = [("params", TranslateParams), ("codons", C.c_uint64), ("stops", C.c_uint64), ("unknown_codons", C.c_uint64),
+                ("kernel_ms", C.c_double), ("host_image_ms", C.c_double)]
+
+    def as_dict(self):
+        return {"codon": np.array(self.params.codon[:], dtype=np.int8), "unknown": int(self.params.unknown), "codons": self.codons,
+                "stops": self.stops, "unknown_codons": self.unknown_codons, "kernel_ms": self.kernel_ms,
+                "host_image_ms": self.host_image_ms}
+
+
+TRANSLATE_UNKNOWN_DEFAULT = 24  # swg_letter_index('X')
 
 
 class Stats(C.Structure):
@@ -359,6 +380,15 @@ _sig("swg_db_sequence", C.c_int, [_vp, C.c_uint32, _vp, C.c_size_t, C.POINTER(C.
 _sig("swg_db_mask", C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)])
 _sig("swg_db_mask_info", C.c_int, [_vp, _vp])
 _sig("swg_debug_mask_fail_alloc", None, [C.c_int])
+_sig("swg_codon_table", C.c_int, [C.c_int, _vp])
+_sig("swg_translate_seq", C.c_int, [_vp, C.c_size_t, _vp, _vp, _vp])
+_sig("swg_translate_flat", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, _vp])
+_sig("swg_translate_hit", None, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int)])
+_sig("swg_translate_coords", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
+_sig("swg_db_translate", C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)])
+_sig("swg_db_translate_info", C.c_int, [_vp, _vp])
+_sig("swg_translate_tile_codons", C.c_uint, [])
+TRANSLATE_TILE_CODONS = int(lib.swg_translate_tile_codons())  # codons of a frame per tile of the translation kernel
 
 
 def _check(rc, ctx=None):
@@ -1125,6 +1155,69 @@ def seg_mask_flat(flat, offsets, window=12, trigger=2.2, extend=2.5, replace=MAS
     return a, {"residues_masked": int(tot[0]), "sequences_masked": int(tot[1]), "segments": int(tot[2])}
 
 
+def codon_table(ncbi_id):
+    """NCBI genetic code 1, 2, 3, 4, 5, 6 or 11 as int8[64] residue indices in TCAG order (swg_codon_table)."""
+    p = TranslateParams()
+    _check(lib.swg_codon_table(int(ncbi_id), C.byref(p)))
+    return np.array(p.codon[:], dtype=np.int8)
+
+
+def translate_params(code=1, unknown=TRANSLATE_UNKNOWN_DEFAULT):
+    """swg_translate_params of `code`: an NCBI id, or a 64-entry array of residue indices.  Values are passed as they are:
+    the library refuses what is outside 1..31."""
+    p = TranslateParams()
+    if np.ndim(code) == 0:
+        _check(lib.swg_codon_table(int(code), C.byref(p)))
+    else:
+        t = np.asarray(code)
+        if t.shape != (64,) or t.min() < -128 or t.max() > 127:
+            raise ValueError("a codon table is 64 residue indices")
+        p.codon[:] = [int(v) for v in t]
+    if not -128 <= int(unknown) <= 127:
+        raise ValueError("unknown is a residue index")
+    p.unknown = int(unknown)
+    return p
+
+
+def translate_seq(nt, code=1, unknown=TRANSLATE_UNKNOWN_DEFAULT):
+    """The six frames of one nucleotide sequence of residue indices (swg_translate_seq, the host twin of
+    Database.translate): six int8 arrays, frames 0..2 of the forward strand, then of the reverse complement."""
+    a, ap = _i8(nt)
+    p = translate_params(code, unknown)
+    outs = [np.zeros(a.size // 3, dtype=np.int8) for _ in range(6)]
+    ptrs = (_vp * 6)(*[o.ctypes.data_as(_vp) for o in outs])
+    lens = (C.c_size_t * 6)()
+    _check(lib.swg_translate_seq(ap, a.size, C.byref(p), ptrs, lens))
+    return [o[:lens[g]].copy() for g, o in enumerate(outs)]
+
+
+def translate_flat(flat, offsets, code=1, unknown=TRANSLATE_UNKNOWN_DEFAULT):
+    """swg_translate_seq over a whole database laid end to end, on every core -> (flat, offsets) of its 6 n frames,
+    frame g of sequence i at 6 i + g (swg_translate_flat)."""
+    a, ap = _i8(flat)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    p = translate_params(code, unknown)
+    out = np.zeros(2 * int(off[-1] - off[0]) if off.size > 1 else 0, dtype=np.int8)
+    out_off = np.zeros(6 * (off.size - 1) + 1, dtype=np.uint64)
+    _check(lib.swg_translate_flat(ap, off.ctypes.data_as(_vp), off.size - 1, C.byref(p), out.ctypes.data_as(_vp), out_off.ctypes.data_as(_vp)))
+    return out[:int(out_off[-1])], out_off
+
+
+def translate_hit(index):
+    """A hit's index in a translated database -> (index of the nucleotide record, frame 0..5) (swg_translate_hit)."""
+    i, f = C.c_uint32(0), C.c_int(0)
+    lib.swg_translate_hit(int(index), C.byref(i), C.byref(f))
+    return i.value, f.value
+
+
+def translate_coords(frame, nt_len, d_begin, d_end):
+    """The nucleotides that residues [d_begin, d_end) of `frame` cover: (nt_begin, nt_end), 0-based and half-open on
+    the forward strand (swg_translate_coords)."""
+    b, e = C.c_uint32(0), C.c_uint32(0)
+    _check(lib.swg_translate_coords(int(frame), int(nt_len), int(d_begin), int(d_end), C.byref(b), C.byref(e)))
+    return b.value, e.value
+
+
 # ---------------------------------------------------------------------------
 # database + context
 # ---------------------------------------------------------------------------
@@ -1360,6 +1453,23 @@ class Database:
         """What Database.mask made this database with and what it covered (swg_db_mask_info)."""
         info = MaskInfo()
         _check(lib.swg_db_mask_info(self.handle, C.byref(info)))
+        return info.as_dict()
+
+    def translate(self, ctx, code=1, unknown=TRANSLATE_UNKNOWN_DEFAULT):
+        """The six-frame translation of this resident root NUCLEOTIDE database, made on the device (swg_db_translate):
+        frame g of sequence i is sequence 6 i + g of the result.  code: an NCBI id or 64 residue indices in TCAG order.
+        A Database of its own."""
+        p = translate_params(code, unknown)
+        h = _vp()
+        _check(lib.swg_db_translate(ctx.handle, self.handle, C.byref(p), C.byref(h)), ctx.handle)
+        t = Database.__new__(Database)
+        t.handle = h
+        return t
+
+    def translate_info(self):
+        """What Database.translate made this database with and what it wrote (swg_db_translate_info)."""
+        info = TranslateInfo()
+        _check(lib.swg_db_translate_info(self.handle, C.byref(info)))
         return info.as_dict()
 
     def sequence(self, i):

@@ -40,9 +40,9 @@ ARCH = "gfx950"
 DEVICE_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-load-store-opt",
                 "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 
-HIP_SOURCES = ["swg_kernels.hip", "swg_trace.hip", "swg_hsps.hip", "swg_bounds.hip", "swg_comp.hip", "swg_calib.hip", "swg_pssm.hip", "swg_mask.hip", "swg_api.cpp", "swg_group.cpp"]
+HIP_SOURCES = ["swg_kernels.hip", "swg_trace.hip", "swg_hsps.hip", "swg_bounds.hip", "swg_comp.hip", "swg_calib.hip", "swg_pssm.hip", "swg_mask.hip", "swg_translate.hip", "swg_api.cpp", "swg_group.cpp"]
 KERNEL_PARTS = [0, 1, 2, 3, 4, 5]  # swg_kernels.hip is compiled once per part (-DSWG_PART=n), in parallel
-CXX_SOURCES = ["swg_pack.cpp", "swg_diag_host.cpp", "swg_pssm_host.cpp", "swg_mask_host.cpp", "swg_hsps_host.cpp", "swg_comp_host.cpp"]  # host-only C++, OpenMP via g++
+CXX_SOURCES = ["swg_pack.cpp", "swg_diag_host.cpp", "swg_pssm_host.cpp", "swg_mask_host.cpp", "swg_translate_host.cpp", "swg_hsps_host.cpp", "swg_comp_host.cpp"]  # host-only C++, OpenMP via g++
 C_SOURCES = ["swg_scoring.c", "swg_seqio.c", "swg_synth.c", "swg_evalue.c", "swg_threads.c"]
 CLI_SOURCES = ["sw_cmdline.c"]
 

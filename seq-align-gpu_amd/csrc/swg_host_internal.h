@@ -166,6 +166,9 @@ struct swg_db {
     // a masked copy (swg_db_mask): what it was made with and what the kernels covered (swg_db_mask_info)
     bool masked = false;
     swg_mask_info mask_info = {};
+    // a six-frame translation (swg_db_translate): what it was made with and what the kernel wrote (swg_db_translate_info)
+    bool translated = false;
+    swg_translate_info translate_info = {};
     // A view (swg_db_view): a database of its own whose slots are some of `root`'s sequences.  Its residue bytes are the
     // root's on the host and on the device -- codes is empty, code_off[s] is the ROOT's byte offset of slot s's sequence
     // (so consecutive slots are not adjacent in memory: a sequence ends at code_off[s] + its length, never at
@@ -742,6 +745,16 @@ void swg_db_release_device(swg_db *db);
 void swg_db_release_search_state(swg_db *db);
 // the residue bytes a database's code_off points into: its own, or for a view its root's
 inline const uint8_t *swg_db_codes(const swg_db *db) { return (db->root ? db->root : db)->codes.data(); }
+// The slot tables of the six-frame translation of `parent` (swg_db_translate; swg_pack.cpp, no GPU): everything of db's
+// host image but the residue bytes (sized, not written), built from the parent's lengths and original indices alone the
+// way swg_db_pack builds them from the frames given in index order; dst[6 s + g] = the slot of frame g of the parent's
+// slot s (~0u for an empty slot).  Throws what the containers throw.
+void swg_translate_slots(const swg_db *parent, swg_db *db, std::vector<uint32_t> *dst);
+// *out = *p, or genetic code 1 for p NULL; SWG_ERR_ARG (global error, naming `what`) for an entry outside 1..31
+// (swg_translate_host.cpp)
+int swg_translate_params_get(const char *what, const swg_translate_params *p, swg_translate_params *out);
+// length of frame f or 3 + f of a sequence of L nucleotides
+inline uint32_t swg_frame_len(uint32_t L, uint32_t f) { return L >= f + 3u ? (L - f) / 3u : 0u; }
 // Views, host side (swg_pack.cpp; no GPU).  swg_view_select: the ROOT's slots that `indices` (original indices, any
 // order, duplicates collapse, those of other shards ignored) select among parent's sequences, ascending; SWG_ERR_ARG for
 // an index outside the whole database.  swg_view_host: the view of those slots with its whole host image, holding a

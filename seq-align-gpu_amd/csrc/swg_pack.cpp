@@ -66,6 +66,44 @@ static void derive_tables(swg_db *db)
 static std::atomic<unsigned long> g_sorts{0}; // how many global sorts this process has run (swg_debug_sort_count)
 extern "C" unsigned long swg_debug_sort_count(void) { return g_sorts.load(); }
 
+// The order itself: positions 0 .. n-1 by len(position) descending, equal lengths in position order (a counting sort).
+template <class Len> static void sort_by_length(size_t n, uint64_t max_len, Len len, std::vector<uint32_t> *sorted)
+{
+    sorted->resize(n);
+    std::vector<uint64_t> cnt(max_len + 2, 0);
+    for (size_t i = 0; i < n; ++i) cnt[max_len - len(i) + 1]++;
+    for (size_t l = 1; l < cnt.size(); ++l) cnt[l] += cnt[l - 1];
+    for (size_t i = 0; i < n; ++i) (*sorted)[cnt[max_len - len(i)]++] = (uint32_t)i;
+}
+
+// The slots of the bins b % shard_count == shard_rank of a global order of n sequences (db->n_bins, order, lens), then
+// the tables derived from them; index(i) and len(i) are the original index and the length of the sequence at position i.
+// src_of (or NULL): the position of each slot's sequence.
+template <class Index, class Len>
+static void fill_slots(swg_db *db, size_t n, const std::vector<uint32_t> &sorted, int shard_rank, int shard_count, Index index, Len len,
+                       std::vector<uint32_t> *src_of)
+{
+    const size_t n_bins_global = (n + SWG_BIN - 1) / SWG_BIN;
+    std::vector<size_t> my_bins;
+    for (size_t b = (size_t)shard_rank; b < n_bins_global; b += (size_t)shard_count)
+        my_bins.push_back(b);
+    const size_t nb = my_bins.size();
+    db->n_bins = (uint32_t)nb;
+    db->order.assign(nb * SWG_BIN, 0xFFFFFFFFu);
+    db->lens.assign(nb * SWG_BIN, 0u);
+    if (src_of) src_of->assign(nb * SWG_BIN, 0u);
+    for (size_t lb = 0; lb < nb; ++lb) {
+        const size_t first = my_bins[lb] * SWG_BIN;
+        for (size_t s = 0; s < SWG_BIN && first + s < n; ++s) {
+            const uint32_t oi = sorted[first + s];
+            if (src_of) (*src_of)[lb * SWG_BIN + s] = oi;
+            db->order[lb * SWG_BIN + s] = index(oi);
+            db->lens[lb * SWG_BIN + s] = len(oi);
+        }
+    }
+    derive_tables(db);
+}
+
 static int sort_database(const char *what, const int8_t *flat, const uint64_t *offsets, size_t n, std::vector<uint32_t> *sorted)
 {
     if (!offsets && n > 0) return swg_set_global_error(SWG_ERR_ARG, "%s: NULL input", what);
@@ -89,11 +127,7 @@ static int sort_database(const char *what, const int8_t *flat, const uint64_t *o
         }
         if (bad) return swg_set_global_error(SWG_ERR_RESIDUE, "%s: residue index outside 1..31 in database", what);
     }
-    sorted->resize(n);
-    std::vector<uint64_t> cnt(max_len + 2, 0);
-    for (size_t i = 0; i < n; ++i) cnt[max_len - (offsets[i + 1] - offsets[i]) + 1]++;
-    for (size_t l = 1; l < cnt.size(); ++l) cnt[l] += cnt[l - 1];
-    for (size_t i = 0; i < n; ++i) (*sorted)[cnt[max_len - (offsets[i + 1] - offsets[i])]++] = (uint32_t)i;
+    sort_by_length(n, max_len, [&](size_t i) { return offsets[i + 1] - offsets[i]; }, sorted);
     g_sorts.fetch_add(1);
     return SWG_OK;
 }
@@ -114,26 +148,10 @@ static int build_shard(const int8_t *flat, const uint64_t *offsets, size_t n, co
         *out = holder.release();
         return SWG_OK;
     }
-    // bins of the global order that belong to this shard
-    const size_t n_bins_global = (n + SWG_BIN - 1) / SWG_BIN;
-    std::vector<size_t> my_bins;
-    for (size_t b = (size_t)shard_rank; b < n_bins_global; b += (size_t)shard_count)
-        my_bins.push_back(b);
-    const size_t nb = my_bins.size();
-    db->n_bins = (uint32_t)nb;
-    db->order.assign(nb * SWG_BIN, 0xFFFFFFFFu);
-    db->lens.assign(nb * SWG_BIN, 0u);
-    std::vector<uint32_t> src_of(nb * SWG_BIN, 0u); // position of a slot's sequence in the caller's arrays
-    for (size_t lb = 0; lb < nb; ++lb) {
-        const size_t first = my_bins[lb] * SWG_BIN;
-        for (size_t s = 0; s < SWG_BIN && first + s < n; ++s) {
-            const uint32_t oi = sorted[first + s];
-            src_of[lb * SWG_BIN + s] = oi;
-            db->order[lb * SWG_BIN + s] = global_index ? global_index[oi] : oi;
-            db->lens[lb * SWG_BIN + s] = (uint32_t)(offsets[oi + 1] - offsets[oi]);
-        }
-    }
-    derive_tables(db);
+    std::vector<uint32_t> src_of; // position of a slot's sequence in the caller's arrays
+    fill_slots(db, n, sorted, shard_rank, shard_count, [&](uint32_t oi) { return global_index ? global_index[oi] : oi; },
+               [&](uint32_t oi) { return (uint32_t)(offsets[oi + 1] - offsets[oi]); }, &src_of);
+    const size_t nb = db->n_bins;
     db->codes.resize(db->code_off.back()); // written completely, sequence by sequence, below
     const long long ns = (long long)(nb * SWG_BIN);
 #pragma omp parallel for schedule(dynamic, 512) num_threads(threads)
@@ -251,6 +269,30 @@ extern "C" int swg_db_pack_shard(const int8_t *flat, const uint64_t *offsets, si
 extern "C" int swg_db_pack_shards(const int8_t *flat, const uint64_t *offsets, size_t n, int shard_count, swg_db **out)
 {
     return guarded("swg_db_pack_shards", [&] { return swg_pack_shards(flat, offsets, n, shard_count, out, nullptr); });
+}
+
+// The six-frame translation's slot tables (swg_db_translate): the 6 n frames in index order -- the parent's sequences by
+// original index, frames 0..5 of each -- sorted like any database.  No residue byte is read.
+void swg_translate_slots(const swg_db *parent, swg_db *db, std::vector<uint32_t> *dst)
+{
+    const size_t pns = parent->order.size();
+    std::vector<uint32_t> by_index; // the parent's held slots by original index
+    by_index.reserve(parent->n_local);
+    for (size_t s = 0; s < pns; ++s)
+        if (parent->order[s] != 0xFFFFFFFFu) by_index.push_back((uint32_t)s);
+    std::sort(by_index.begin(), by_index.end(), [&](uint32_t a, uint32_t b) { return parent->order[a] < parent->order[b]; });
+    const size_t n = by_index.size() * 6;
+    auto len = [&](size_t e) { return swg_frame_len(parent->lens[by_index[e / 6]], (uint32_t)(e % 6 % 3)); };
+    const uint64_t max_len = pns ? parent->lens[0] / 3u : 0; // (sorted: slot 0 is the longest; frame 0 is a sequence's longest)
+    std::vector<uint32_t> sorted;
+    sort_by_length(n, max_len, len, &sorted);
+    db->n_total = parent->n_total * 6;
+    std::vector<uint32_t> src_of;
+    fill_slots(db, n, sorted, 0, 1, [&](uint32_t e) { return parent->order[by_index[e / 6]] * 6u + e % 6u; },
+               [&](uint32_t e) { return len(e); }, &src_of);
+    db->codes.resize(db->code_off.back());
+    dst->assign(pns * 6, 0xFFFFFFFFu);
+    for (size_t s = 0; s < n; ++s) (*dst)[(size_t)by_index[src_of[s] / 6] * 6 + src_of[s] % 6] = (uint32_t)s; // (one shard: slot = sorted position)
 }
 
 // ---------------------------------------------------------------------------

@@ -49,7 +49,10 @@
  *     scores every entry an iteration would include again under its composition-adjusted scores (swg_comp_adjust) and
  *     keeps it only if the E-value of the adjusted score is within --inclusion; in the reports it ranks --topk's hits again
  *     by adjusted score (both scores printed), keeps --evalue's hits by the adjusted E-value and prints --tabular's evalue,
- *     bitscore and score columns adjusted (comp_rerank below; swg_comp_adjust_multi / _multi_pssm under --allqueries).
+ *     bitscore and score columns adjusted (comp_rerank below; swg_comp_adjust_multi / _multi_pssm under --allqueries);
+ *     --translatedb [CODE] takes a NUCLEOTIDE database: its six frames are translated on the device after the upload
+ *     (swg_db_translate), every stage reads the translation, and a hit is printed as the nucleotide record, its frame and,
+ *     in --bounds and --tabular, its nucleotide coordinates (swg_translate_hit, swg_translate_coords).
  * There is no CPU backend: without a GPU the tool fails with a message.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -175,7 +178,19 @@ static void usage(const char *argv0, const char *err)
             "    --softmask           with --prefilter N: only the gapless prefilter reads the masked copy (--maskdb's parameters, or the\n"
             "                         defaults); the gapped search of the candidates and the alignments read the database as it is\n"
             "    --maskquery          mask every query record the same way on the host before it is searched; not with --pssm or\n"
-            "                         --pssmlist\n",
+            "                         --pssmlist\n"
+            "    --translatedb [CODE] the database file is NUCLEOTIDE (A C G T/U; anything else is no base): its six reading frames are\n"
+            "                         translated on the GPU, after the upload or the --packed load, under NCBI genetic code CODE (1, 2, 3,\n"
+            "                         4, 5, 6 or 11) [1], and every stage reads the translation (tblastn's question).  A codon with a\n"
+            "                         non-base is X; a stop is `*` in place.  Hits name the nucleotide record and its frame (+1 +2 +3 -1\n"
+            "                         -2 -3): the --topk block prints `score, entry, frame, name`, --bounds and --tabular print subject\n"
+            "                         coordinates in nucleotides, 1-based and inclusive, start above end on a minus frame, and\n"
+            "                         --tabular gains a last column sframe; --align prints the frame's protein alignment.  E-values count\n"
+            "                         over the nucleotide residues / 3 (tblastn's convention: the six frames / 6).  Give --topk K,\n"
+            "                         --minscore S or --evalue E: no Entry lines are printed.  Works with --allqueries, --pssm,\n"
+            "                         --pssmlist, --maskdb (which masks the translation) and --compfromdb (the translation's\n"
+            "                         composition); not with --gpus N > 1, --savedb, --seqidlist, --candidates, --prefilter, --softmask,\n"
+            "                         --iterations, --compstats or --maxhsps\n",
             argv0);
     exit(EXIT_FAILURE);
 }
@@ -370,6 +385,46 @@ static int evalue_scores(swg_ctx *ctx, const swg_seqs *q, size_t n_rec, const in
 }
 
 /* --maskquery: the masked positions of a query record take the replacement residue */
+/* --translatedb: a hit's entry is frame (index % 6) of the nucleotide record (index / 6); BLAST's names of the frames */
+static const char *const frame_names[6] = {"+1", "+2", "+3", "-1", "-2", "-3"};
+
+/* the nucleotides an alignment in a frame covers, 1-based and inclusive, the start above the end on a minus frame */
+static void nt_span(int frame, uint32_t nt_len, const swg_alignment *a, uint32_t *start, uint32_t *end)
+{
+    uint32_t b = 0, e = 0;
+    *start = *end = 0;
+    if (swg_translate_coords(frame, nt_len, a->d_begin, a->d_end, &b, &e) != SWG_OK) return; /* (a score of 0: no alignment) */
+    *start = frame < 3 ? b + 1 : e;
+    *end = frame < 3 ? e : b + 1;
+}
+
+/* the length of nucleotide record `rec`: from the FASTA's offsets, or for a --packed database from its host image */
+static uint32_t nt_length(const swg_db *ntdb, const swg_seqs *db, int packed, uint32_t rec)
+{
+    size_t len = 0;
+    if (!packed) return (uint32_t)(db->seq_off[rec + 1] - db->seq_off[rec]);
+    (void)swg_db_sequence(ntdb, rec, NULL, 0, &len); /* (no room given: the length alone comes back) */
+    return (uint32_t)len;
+}
+
+/* the letters of one frame of nt[len] (table indices), NUL-terminated; NULL: out of memory */
+static char *frame_letters(const int8_t *nt, size_t len, int frame, const swg_translate_params *tp)
+{
+    int8_t *buf = (int8_t *)malloc(6 * (len / 3) + 1), *out[6];
+    size_t n[6];
+    char *s = (char *)malloc(len / 3 + 1);
+    for (int g = 0; g < 6; g++) out[g] = buf ? buf + (size_t)g * (len / 3) : NULL;
+    if (!buf || !s || swg_translate_seq(nt, len, tp, out, n) != SWG_OK) {
+        free(buf);
+        free(s);
+        return NULL;
+    }
+    for (size_t k = 0; k < n[frame]; k++) s[k] = (char)swg_index_letter(out[frame][k]);
+    s[n[frame]] = 0;
+    free(buf);
+    return s;
+}
+
 static int mask_query(int8_t *idx, size_t n, const swg_mask_params *mp)
 {
     uint8_t *m = (uint8_t *)malloc(n ? n : 1);
@@ -399,6 +454,9 @@ int main(int argc, char **argv)
     long purge = 0;
     const char *out_pssm = NULL;
     int maskdb = 0, softmask = 0, maskquery = 0;
+    int translatedb = 0; /* --translatedb [CODE]: the database is nucleotide, its six frames are what is searched */
+    swg_translate_params tp;
+    (void)swg_codon_table(1, &tp);
     swg_mask_params mp;
     swg_mask_params_default(&mp);
     if (argc == 1) usage(argv[0], NULL);
@@ -444,6 +502,14 @@ int main(int argc, char **argv)
             softmask = 1;
         } else if (!strcasecmp(a, "--maskquery")) {
             maskquery = 1;
+        } else if (!strcasecmp(a, "--translatedb")) { /* the code is optional: a whole number behind the flag is taken as it */
+            long code;
+            translatedb = 1;
+            if (i + 1 < argc && parse_int(argv[i + 1], LONG_MIN, LONG_MAX, &code)) {
+                if (code < INT_MIN || code > INT_MAX || swg_codon_table((int)code, &tp) != SWG_OK)
+                    usage(argv[0], "Invalid --translatedb argument: an NCBI genetic code, one of 1, 2, 3, 4, 5, 6 and 11");
+                i++;
+            }
         } else if (!strcasecmp(a, "--maskdb")) {
             maskdb = 1;
             /* the parameters are optional: W,K1,K2 in one argument that starts with a digit and holds a comma */
@@ -562,6 +628,20 @@ int main(int argc, char **argv)
     }
     if (!qpath || !dbpath) usage(argv[0], "No input specified"); /* reference src/alignment_cmdline.c:303-305 */
     if (!have_matrix) usage(argv[0], "--substitution_matrix is required (the fill scores from the matrix only)");
+    if (translatedb) { /* what a translated search does not combine with: each by name, before a device is opened */
+        if (gpus > 1) usage(argv[0], "--translatedb works with one GPU (--gpu): it does not combine with --gpus N > 1");
+        if (savedb) usage(argv[0], "--translatedb does not combine with --savedb (the file would hold the translation, not the database given)");
+        if (idlist_path) usage(argv[0], "--translatedb does not combine with --seqidlist (the entries searched are frames, not the records listed)");
+        if (cand_path) usage(argv[0], "--translatedb does not combine with --candidates (the entries searched are frames, not the records listed)");
+        if (prefilter) usage(argv[0], "--translatedb does not combine with --prefilter");
+        if (softmask) usage(argv[0], "--translatedb does not combine with --softmask (--maskdb masks the translation)");
+        if (iterations) usage(argv[0], "--translatedb does not combine with --iterations");
+        if (compstats) usage(argv[0], "--translatedb does not combine with --compstats");
+        if (maxhsps) usage(argv[0], "--translatedb does not combine with --maxhsps");
+        if (topk == 0 && !minscore && !mslist_path && !have_evalue)
+            usage(argv[0], "--translatedb reports hits, not the Entry lines of every frame: give --topk K, --minscore S or --evalue E");
+        if (gpus == 1) gpus = 0; /* (one GPU either way: the translation is made on a context) */
+    }
     if (maxhsps && !align && !bounds && !tabular)
         usage(argv[0], "--maxhsps N reports up to N alignments per hit of --align, --bounds or --tabular: give one of them");
     if (maxhsps && (gapless || gpus > 0 || iterations || cand_path || prefilter))
@@ -659,6 +739,8 @@ int main(int argc, char **argv)
         return leave(EXIT_SUCCESS);
     }
     phase(packed ? "read query, load packed db" : "read query and database");
+    /* the entries searched, scored and numbered in hits: the records, or with --translatedb their six frames each */
+    const size_t n_entries = translatedb ? 6 * db.n : db.n;
     /* --seqidlist: the entries to search, and a mark per entry for the printing */
     uint32_t *ids = NULL;
     size_t n_ids = 0, n_listed = 0;
@@ -948,9 +1030,9 @@ int main(int argc, char **argv)
     if (!packed && swg_seqs_to_indices(&db, didx, &bad) != SWG_OK) die_illegal(bad);
 
     phase("letters to table indices");
-    int32_t *scores = (int32_t *)calloc(db.n ? db.n : 1, sizeof(int32_t));
+    int32_t *scores = (int32_t *)calloc(n_entries ? n_entries : 1, sizeof(int32_t));
     /* --minscore without --topk: room for every entry searched */
-    const size_t hit_cap = topk ? (size_t)topk : minscore ? (ids ? n_ids : db.n) : 0;
+    const size_t hit_cap = topk ? (size_t)topk : minscore ? (ids ? n_ids : n_entries) : 0;
     swg_hit *hits = (swg_hit *)calloc(hit_cap ? hit_cap : 1, sizeof(swg_hit));
     int32_t *adj = (int32_t *)calloc(hit_cap ? hit_cap : 1, sizeof(int32_t)); /* --compstats: the adjusted scores beside the current record's hits */
     double comp_freq[32];                                                     /* ... and its background under --compfromdb */
@@ -965,6 +1047,7 @@ int main(int argc, char **argv)
     swg_group *grp = NULL;
     swg_db *sdb = NULL; /* what is searched: the database, or with --seqidlist the view of its listed entries */
     swg_db *mdb = NULL; /* --softmask: the masked copy, */
+    swg_db *ntdb = NULL; /* --translatedb: the nucleotide database the frames were made from */
     swg_db *gdb = NULL; /* ... and what the gapless prefilter reads: the copy, or with --seqidlist the view of its listed entries */
     /* --minscore --gpus N: a context, a shard and what is searched of it per GPU; sh_of[i] = the shard hit i came from */
     size_t sh_n = 0;
@@ -1126,6 +1209,21 @@ int main(int argc, char **argv)
         }
         if (rc == SWG_OK) rc = swg_db_upload(ctx, pdb);
         phase("upload");
+        if (rc == SWG_OK && translatedb) { /* every stage reads the six frames; the nucleotide database stays for its records' lengths */
+            swg_translate_info ti;
+            ntdb = pdb;
+            pdb = NULL;
+            rc = swg_db_translate(ctx, ntdb, &tp, &pdb);
+            if (rc == SWG_OK && swg_db_translate_info(pdb, &ti) == SWG_OK) {
+                fprintf(stderr, "translated %lu entries into %lu frames: %llu codons, %llu stops, %llu with a non-base\n", (unsigned long)swg_db_count(ntdb),
+                        (unsigned long)swg_db_count(pdb), (unsigned long long)ti.codons, (unsigned long long)ti.stops,
+                        (unsigned long long)ti.unknown_codons);
+                if (timing)
+                    fprintf(stderr, "[timing] %-28s %9.2f ms of kernel, %.2f ms for the host image\n", "translate the database", ti.kernel_ms,
+                            ti.host_image_ms);
+            }
+            phase("translate the database");
+        }
         if (rc == SWG_OK && maskdb) {
             swg_mask_info mi;
             rc = swg_db_mask(ctx, pdb, &mp, &mdb);
@@ -1250,7 +1348,8 @@ int main(int argc, char **argv)
             }
             if (rc == SWG_OK) {
                 int32_t one = 0;
-                ev_residues = swg_db_residues(sdb);
+                /* --translatedb: tblastn's convention, the nucleotides / 3 (= the six frames / 6, up to rounding) */
+                ev_residues = translatedb ? swg_db_residues(ntdb) / 3 : swg_db_residues(sdb);
                 if (!evalue_scores(ctx, &q, allq ? q.n : 1, ev_qx, allq ? plist : NULL, gapless, compfromdb ? counts : NULL, ev_residues, evalue, ev,
                                    allq ? mslist : &one))
                     return leave(EXIT_FAILURE);
@@ -1334,7 +1433,7 @@ next_query:
         }
     }
     if (allq) printf("Query #%lu: %s\n", (unsigned long)qi, qname);
-    for (size_t i = 0, shown = 0; i < db.n && !prefilter && !minscore; i++) {
+    for (size_t i = 0, shown = 0; i < db.n && !prefilter && !minscore && !translatedb; i++) {
         if (listed && !listed[i]) continue;
         if (shown++ % 16 == 0) {
             if (print_fasta) {
@@ -1359,7 +1458,7 @@ next_query:
     }
     /* reference src/alignment_cmdline.c:529-530; the time is the device time of the fill */
     printf("Total Time: %f\n", total_ms * 1e-3);
-    printf("Total Entries: %lu\n", (unsigned long)(listed ? n_listed : db.n));
+    printf("Total Entries: %lu\n", (unsigned long)(listed ? n_listed : n_entries));
     if (have_evalue)
         printf("E-value %g: lambda %.4f, K %.4f, least score %ld over %llu residues\n", evalue, ev[qi].lambda, ev[qi].K, minscore,
                (unsigned long long)ev_residues);
@@ -1369,6 +1468,14 @@ next_query:
             printf("Top %lu hits (adjusted score, score, entry, name):\n", (unsigned long)n_hits);
             for (size_t i = 0; i < n_hits; i++)
                 printf("%d\t%d\t%u\t%s\n", adj[i], hits[i].score, hits[i].index, packed ? "" : db.names + db.name_off[hits[i].index]);
+        } else if (translatedb) { /* the nucleotide record and the frame of it */
+            printf("Top %lu hits (score, entry, frame, name):\n", (unsigned long)n_hits);
+            for (size_t i = 0; i < n_hits; i++) {
+                uint32_t rec;
+                int fr;
+                swg_translate_hit(hits[i].index, &rec, &fr);
+                printf("%d\t%u\t%s\t%s\n", hits[i].score, rec, frame_names[fr], packed ? "" : db.names + db.name_off[rec]);
+            }
         } else {
             printf("Top %lu hits (score, entry, name):\n", (unsigned long)n_hits);
             for (size_t i = 0; i < n_hits; i++)
@@ -1441,13 +1548,24 @@ next_query:
             if (maxhsps && e % hs.per >= hs.n[i]) continue;
             const swg_alignment *a = &al_q[e];
             const char *o = ops_q + e * stride;
-            printf("Alignment #%lu: entry %u score %d query %u..%u entry %u..%u\n", (unsigned long)i, a->index,
-                   a->score, a->q_begin, a->q_end, a->d_begin, a->d_end);
+            uint32_t rec = a->index;
+            int fr = 0;
+            if (translatedb) { /* the frame's protein alignment under the record and the frame; the coordinates are the frame's residues */
+                swg_translate_hit(a->index, &rec, &fr);
+                printf("Alignment #%lu: entry %u frame %s score %d query %u..%u frame residues %u..%u\n", (unsigned long)i, rec, frame_names[fr],
+                       a->score, a->q_begin, a->q_end, a->d_begin, a->d_end);
+            } else {
+                printf("Alignment #%lu: entry %u score %d query %u..%u entry %u..%u\n", (unsigned long)i, a->index,
+                       a->score, a->q_begin, a->q_end, a->d_begin, a->d_end);
+            }
             if (packed) { /* no letters in a packed database: the path itself */
                 printf("%s\n\n", o);
                 continue;
             }
-            const char *qs = q.seq + q.seq_off[qi] + a->q_begin, *ds = db.seq + db.seq_off[a->index] + a->d_begin;
+            char *fl = NULL;
+            if (translatedb && !(fl = frame_letters(didx + db.seq_off[rec], (size_t)(db.seq_off[rec + 1] - db.seq_off[rec]), fr, &tp)))
+                return leave(EXIT_FAILURE);
+            const char *qs = q.seq + q.seq_off[qi] + a->q_begin, *ds = (fl ? fl : db.seq + db.seq_off[a->index]) + a->d_begin;
             size_t c = 0;
             for (uint32_t k = 0; k < a->n_ops; k++) line[k] = o[k] == 'I' ? '-' : qs[c++];
             line[a->n_ops] = 0;
@@ -1455,6 +1573,7 @@ next_query:
             c = 0;
             for (uint32_t k = 0; k < a->n_ops; k++) line[k] = o[k] == 'D' ? '-' : ds[c++];
             printf("%s\n\n", line);
+            free(fl);
         }
         free(al);
         free(ops);
@@ -1481,11 +1600,23 @@ next_query:
         /* one line per hit; with --maxhsps hit e / hs.per's hs.n[] lines one after another (hs.per is 1 without it) */
         for (size_t e = 0; e < n_hits * hs.per && bounds; e++) {
             if (maxhsps && e % hs.per >= hs.n[e / hs.per]) continue;
+            if (translatedb) { /* the subject in nucleotides of the record, 1-based and inclusive */
+                uint32_t rec, s1, e1;
+                int fr;
+                swg_translate_hit(bd_q[e].index, &rec, &fr);
+                nt_span(fr, nt_length(ntdb, &db, packed, rec), &bd_q[e], &s1, &e1);
+                printf("Bounds #%lu: entry %u frame %s score %d query %u..%u entry %u..%u length %u\n", (unsigned long)e, rec, frame_names[fr],
+                       bd_q[e].score, bd_q[e].q_begin, bd_q[e].q_end, s1, e1, bd_q[e].n_ops);
+                continue;
+            }
             printf("Bounds #%lu: entry %u score %d query %u..%u entry %u..%u length %u\n", (unsigned long)(e / hs.per), bd_q[e].index,
                    bd_q[e].score, bd_q[e].q_begin, bd_q[e].q_end, bd_q[e].d_begin, bd_q[e].d_end, bd_q[e].n_ops);
         }
-        if (tabular && have_evalue) printf("# Fields: query, entry, pident, length, mismatch, gapopen, qstart, qend, sstart, send, evalue, bitscore, score\n");
-        else if (tabular) printf("# Fields: query, entry, pident, length, mismatch, gapopen, qstart, qend, sstart, send, score\n");
+        if (tabular && have_evalue)
+            printf("# Fields: query, entry, pident, length, mismatch, gapopen, qstart, qend, sstart, send, evalue, bitscore, score%s\n",
+                   translatedb ? ", sframe" : "");
+        else if (tabular)
+            printf("# Fields: query, entry, pident, length, mismatch, gapopen, qstart, qend, sstart, send, score%s\n", translatedb ? ", sframe" : "");
         for (size_t i = 0; i < n_hits * hs.per && tabular; i++) {
             if (maxhsps && i % hs.per >= hs.n[i / hs.per]) continue;
             const swg_alignment *a = &bd_q[i];
@@ -1493,6 +1624,18 @@ next_query:
             /* --compstats: the score columns are the adjusted ones (line i is hit i: --maxhsps is refused beside it); the
              * coordinates and counts stay those of the unadjusted alignment */
             const int32_t shown = compstats ? adj[i] : a->score;
+            if (translatedb) { /* the nucleotide record, its coordinates (1-based, inclusive, start above end on a minus frame), the frame last */
+                uint32_t rec, s1, e1;
+                int fr;
+                swg_translate_hit(a->index, &rec, &fr);
+                nt_span(fr, nt_length(ntdb, &db, packed, rec), a, &s1, &e1);
+                printf("%s\t%s\t%.2f\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t", qname, packed ? "" : db.names + db.name_off[rec],
+                       100.0 * ct_q[i].n_ident / a->n_ops, a->n_ops, ct_q[i].n_match - ct_q[i].n_ident, ct_q[i].n_gap_open, a->q_begin + 1,
+                       a->q_end, s1, e1);
+                if (have_evalue) printf("%.3g\t%.1f\t", swg_evalue(&ev[qi], ev_residues, shown), swg_bitscore(&ev[qi], shown));
+                printf("%d\t%s\n", shown, frame_names[fr]);
+                continue;
+            }
             if (have_evalue) { /* BLAST's twelve columns, then the raw score */
                 printf("%s\t%s\t%.2f\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%.3g\t%.1f\t%d\n", qname, packed ? "" : db.names + db.name_off[a->index],
                        100.0 * ct_q[i].n_ident / a->n_ops, a->n_ops, ct_q[i].n_match - ct_q[i].n_ident, ct_q[i].n_gap_open, a->q_begin + 1,
@@ -1521,7 +1664,7 @@ next_query:
         static int8_t *qx = NULL;     /* the chunk's queries as table indices */
         static uint64_t *qoff = NULL;
         if (qi >= chunk_first + chunk_n) {
-            size_t budget = cands ? 1024 : ((size_t)256 << 20) / (sizeof(int32_t) * (db.n ? db.n : 1));
+            size_t budget = cands ? 1024 : ((size_t)256 << 20) / (sizeof(int32_t) * (n_entries ? n_entries : 1));
             if (budget < 1) budget = 1;
             if (budget > 1024) budget = 1024;
             chunk_first = qi;
@@ -1536,7 +1679,7 @@ next_query:
             free(mq_nhits);
             free(mq_above);
             mq_above = (uint64_t *)calloc(chunk_n, sizeof(uint64_t));
-            mq_scores = (int32_t *)calloc(cands || mslist ? 1 : chunk_n * (db.n ? db.n : 1), sizeof(int32_t)); /* (--candidates: lsc) */
+            mq_scores = (int32_t *)calloc(cands || mslist ? 1 : chunk_n * (n_entries ? n_entries : 1), sizeof(int32_t)); /* (--candidates: lsc) */
             mq_hits = (swg_hit *)calloc(chunk_n * (topk ? (size_t)topk : 1), sizeof(swg_hit));
             mq_nhits = (size_t *)calloc(chunk_n, sizeof(size_t));
             free(mq_adj);
@@ -1622,7 +1765,7 @@ next_query:
                         st.fill_ms, st.fill_ms > 0 ? (double)st.cells / (st.fill_ms * 1e-3) / 1e9 : 0.0);
         }
         const size_t at = qi - chunk_first;
-        if (!cands && !mslist) memcpy(scores, mq_scores + at * (db.n ? db.n : 1), db.n * sizeof(int32_t));
+        if (!cands && !mslist) memcpy(scores, mq_scores + at * (n_entries ? n_entries : 1), n_entries * sizeof(int32_t));
         if (mslist) minscore = mslist[qi], n_above = mq_above[at];
         n_hits = mq_nhits[at];
         memcpy(hits, mq_hits + at * (topk ? (size_t)topk : 1), n_hits * sizeof(swg_hit));
@@ -1721,6 +1864,7 @@ next_query:
     swg_db_free(mdb);
     if (sdb != pdb) swg_db_free(sdb);
     swg_db_free(pdb);
+    swg_db_free(ntdb);
     swg_destroy(ctx);
     swg_group_destroy(grp);
     for (size_t g = 0; g < sh_n; g++) {
